@@ -8,7 +8,14 @@ constants, source parameters) are resident in HBM before the timed region; outpu
 struct _polycap_images, written by the kernel itself in coalesced runs: the photons a wave finalises together take the next
 free positions of the planes) stay in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float64, under 64 MB in all):
+efficiencies, sum_weights and photon_counts (exit, not entered, not transmitted, reflections) of the whole job, and with
+image planes a fixed sample of rank 0's exit photons, exit_images [k, 17] (the planes of struct _polycap_images, the
+reflection count as a float) and exit_weights [k, n_energies].  The compact store keeps exit photons in the order of
+completion, which varies from run to run, so the sample is chosen by a fixed hash of each photon's source start
+coordinates and sorted by them: with the same arguments two runs, or two builds, dump the same photons in the same order.
 
 With N > 1 and no torch.distributed environment the command starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...`, before anything touches the GPU) and relays
@@ -64,7 +71,12 @@ def parse_args():
                     help="collective backend for --gpus > 1 (nccl = RCCL over xGMI; gloo only to rehearse the multi-process "
                          "path on a box with fewer GPUs than ranks: ranks then share devices)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py starts the ranks itself")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -171,6 +183,10 @@ def main():
     if rank == 0:
         counters, sums = last
         eff = pcd.efficiencies_from_totals(counters, sums)
+        dumped = None
+        if args.dump_outputs:
+            # before anything else runs on the context: the instrumented launch below overwrites the last step's planes
+            dumped = dump_outputs(args.dump_outputs, ctx, counters, sums, eff, n_local if keep_images else 0)
         avg_ms = float(np.mean(kernel_ms))
         alg_bytes = n_local * (BYTES_PER_EXIT_PHOTON + 8 * ne) if keep_images else 8.0 * (ne + 6)
         achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
@@ -242,10 +258,65 @@ def main():
             out["parity_fixture"] = parity_fixture(prob, dev_index)
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(prob, args, ctx)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     ctx.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_BYTES = 48 << 20     # --dump-outputs: bound of the exit photon sample (the totals add a few bytes)
+DUMP_CHUNK = 1 << 20             # exit photons fetched from the device at a time
+
+
+def photon_keys(planes):
+    """A fixed 64-bit hash per exit photon of its source start coordinates (planes 0 and 1, drawn from the photon's own
+    Philox stream): the same photon gets the same key in every run, wherever the compact store put it."""
+    import numpy as np
+    x = np.ascontiguousarray(planes[0]).view(np.uint64) ^ (np.ascontiguousarray(planes[1]).view(np.uint64) * np.uint64(0x9E3779B97F4A7C15))
+    x ^= x >> np.uint64(31)
+    x *= np.uint64(0xBF58476D1CE4E5B9)
+    x ^= x >> np.uint64(29)
+    return x
+
+
+def sample_exit_photons(fetch, n_exit, n_energies):
+    """Rows [k, 17 + n_energies] (the 17 image planes, then the exit weights) of a fixed sample of the n_exit photons that
+    fetch(first, count) -> (planes [17, count], exit_weights [count, n_energies]) hands out in any order: every photon
+    whose key falls in the sample, sorted by its columns (source start coordinates first), at most DUMP_SAMPLE_BYTES."""
+    import numpy as np
+    cap = max(1, DUMP_SAMPLE_BYTES // (8 * (17 + n_energies)))
+    period = np.uint64(max(1, -(-8 * n_exit // (7 * cap))))     # expected sample: 7/8 of the bound, or every photon
+    rows = [np.zeros((0, 17 + n_energies))]
+    for first in range(0, n_exit, DUMP_CHUNK):
+        planes, weights = fetch(first, min(DUMP_CHUNK, n_exit - first))
+        keep = photon_keys(planes) % period == 0
+        rows.append(np.concatenate([planes[:, keep].T, weights[keep]], axis=1))
+    rows = np.concatenate(rows)
+    return rows[np.lexsort(rows.T[::-1])][:cap]
+
+
+def dump_outputs(out_dir, ctx, counters, sums, eff, n_images):
+    """--dump-outputs: the last timed step's results as out_dir/<name>.npy (float64); n_images = exit photons the context
+    holds image planes of (0: none)."""
+    import numpy as np
+    arrays = {"efficiencies": np.asarray(eff, dtype=np.float64),
+              "sum_weights": np.asarray(sums, dtype=np.float64),
+              "photon_counts": np.asarray(counters[:4], dtype=np.float64)}     # the launch count (counters[5]) is scheduling
+    if n_images:
+        def fetch(first, count):
+            p = ctx.image_planes(first, count)
+            return p["planes"], p["exit_weights"]
+        rows = sample_exit_photons(fetch, n_images, ctx.problem.n_energies)
+        arrays["exit_images"] = np.ascontiguousarray(rows[:, :17])
+        arrays["exit_weights"] = np.ascontiguousarray(rows[:, 17:])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "exit_photons_with_images": n_images,
+            "exit_photons_sampled": len(arrays["exit_images"]) if n_images else 0,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def pmc_summary(n_local, keep_images, kernel):

@@ -57,6 +57,58 @@ def test_committed_counters_are_readable():
             assert lo < bench.simd_valu_busy(json.load(f)) < hi, name
 
 
+def test_dump_sample_does_not_depend_on_the_store_order(monkeypatch):
+    """--dump-outputs samples the compact image store, whose order of completion varies from run to run: the same photons
+    handed out in another order give the same rows, within the byte bound; a small run is dumped whole."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 1000 * 8 * 19)      # 1000 rows of 17 planes + 2 energies
+    monkeypatch.setattr(bench, "DUMP_CHUNK", 4096)
+    rng = np.random.default_rng(3)
+    n, ne = 20_000, 2
+    planes, weights = rng.uniform(-1, 1, size=(17, n)), rng.uniform(0, 1, size=(n, ne))
+    perm = rng.permutation(n)
+
+    def fetcher(p, w):
+        return lambda first, count: (p[:, first:first + count], w[first:first + count])
+    a = bench.sample_exit_photons(fetcher(planes, weights), n, ne)
+    b = bench.sample_exit_photons(fetcher(planes[:, perm], weights[perm]), n, ne)
+    assert np.array_equal(a, b) and 500 < len(a) <= 1000 and a.shape[1] == 17 + ne
+    assert np.all(np.diff(a[:, 0]) >= 0)                                  # sorted by the source start x coordinate
+    rows = np.concatenate([planes.T, weights], axis=1)
+    sorted_rows = rows[np.argsort(rows[:, 0])]
+    assert np.array_equal(sorted_rows[np.searchsorted(sorted_rows[:, 0], a[:, 0])], a)      # whole photons, as they were
+    small = bench.sample_exit_photons(fetcher(planes[:, :700], weights[:700]), 700, ne)
+    assert np.array_equal(small, rows[:700][np.lexsort(rows[:700].T[::-1])])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same inputs, hence the same outputs, file for file; the result
+    line still carries the step time of exactly --steps timed steps."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--photons", "300000",
+           "--no-extras", "--no-cpu-baseline"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run(cmd + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["efficiencies.npy", "exit_images.npy", "exit_weights.npy", "photon_counts.npy", "sum_weights.npy"]
+        assert sum((d / f).stat().st_size for f in files) <= 64 << 20
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in files})
+    a, b = dumps
+    assert a["photon_counts"][0] == 300000 and a["exit_images"].shape == (300000, 17) and a["exit_weights"].shape == (300000, 1)
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f], equal_nan=True), f
+    assert a["efficiencies"][0] == line["efficiency_10keV"]
+
+
 def test_host_cpu_description():
     sys.path.insert(0, ROOT)
     import bench
