@@ -83,7 +83,9 @@ POLYCAP_EXTERN void pc_hip_ctx_destroy(pc_hip_ctx *ctx);
  *                      that parks 64 more photons per wave in LDS (pc_pool_kernel.h); "pool" 0 by default = one photon per lane
  *   "run_parts"        a transmission run that keeps images is traced as this many consecutive launches on two streams,
  *                      so that pc_hip_transmission_images can fetch finished parts while later ones run (default 1;
- *                      polycap_source_get_transmission_efficiencies uses 4 from 2e6 photons on)
+ *                      polycap_source_get_transmission_efficiencies uses 4 from 2e6 photons on; at most n_slots / 65536
+ *                      launches).  Launches on the two streams overlap, so such a run keeps two sets of the kernels'
+ *                      per-lane scratch (weight rows, reflection logs, compact start fields), one per stream
  *   "plane_images"     1 = a run that keeps images stores the planes of pc_hip_images itself (no records): pc_hip_transmission_images
  *                      is then a copy-engine transfer into the caller's planes, pinned for the duration of the call;
  *                      pc_hip_transmission_records is not available for such a run.  0 (default) = one record per slot,
@@ -115,6 +117,9 @@ POLYCAP_EXTERN void pc_hip_ctx_destroy(pc_hip_ctx *ctx);
  *   "sweep_fuse"       histogram-only runs of the logging kernel: the sweep of a photon that has left the optic adds its weights
  *                      to the sums itself, no weight row is written (default 1; 2: also for photons whose proxy energies are
  *                      dead, which exercises the exact take-back pass; 0: off)
+ *   "sweep_exact_every" test hook of the logging kernel: N > 0 sweeps the logs of every photon whose slot is a multiple of N by
+ *                      the EXACT loop (range tests at every reflection), as if they held an untame reflection, so that sweep
+ *                      passes mixing such photons with others are common; results stay correct (default 0 = off)
  *   "fetch_threads"    host threads of the staging fallback of the image fetch (0 = min(16, cores))
  *   leak runs: "leak_max_depth" (stack frames per lane = walls one photon may cross), "leak_stack_mb" (HBM for those
  *                      stacks), "leak_capacity" (leak record buffer, 0 = automatic; a run that outgrows it is repeated). */

@@ -103,12 +103,14 @@ struct pc_kargs {
 	 * where. */
 	unsigned long long *img_cursor;   /* next free position, or NULL: a photon is stored at its slot */
 	long long *img_ids;               /* slot of position p (option "slot_ids"), or NULL */
+	long long img_id0;                /* what img_ids adds to a launch's slot numbers: the launch's first slot in the run (compact_parts) */
 	unsigned int *blk_done;           /* per block: positions written so far */
 	unsigned int *blk_flag;           /* per block, host-visible: complete */
 	int blk_shift;
 	long long img_n;                  /* positions of the launch: its slots */
 	double *lane_start;               /* compact store in the kernels that launch in the tracing lane: the 8 start fields of the
-	                                   * lane's photon wait here, one 64-byte line per lane, until the photon has left the optic */
+	                                   * lane's photon wait here, one 64-byte line per lane, until the photon has left the optic.
+	                                   * Per-lane state: two launches in flight (parts on two streams) get disjoint halves */
 	int new_threshold;
 	int lds_acc;                  /* NE == 0: accumulate weight sums in LDS (2*n_energies u64 of dynamic LDS) */
 	int lds_ec;                   /* NE == 0: per-energy constants staged in LDS behind the sums (6*n_energies doubles) */
@@ -116,16 +118,18 @@ struct pc_kargs {
 	int pool_event_min;           /* pool kernel: photons waiting for an EVENT phase that make it run before anything else */
 	int event_march;              /* pool kernel: march steps taken right after an EVENT phase, while the wave is still full of fresh flights */
 	int pool_refill;              /* pool kernel: lanes that must be free before a march burst tops itself up from the pool */
-	double *wscratch;             /* NE==0: n_energies * total_threads */
+	double *wscratch;             /* NE==0: n_energies * total_threads (per-lane state: two launches in flight get disjoint halves) */
 	long long total_threads;
 	/* pc_trace_log_kernel (pc_sweep_kernel.h): many-energy source runs whose reflections are logged */
-	double *rlog;                 /* [total_threads][log_cap][3]: cos theta, fs, fp (pc_refl_geom3) of the lane's logged reflections */
+	double *rlog;                 /* [total_threads][log_cap][3]: cos theta, fs, fp (pc_refl_geom3) of the lane's logged reflections (per-lane
+	                               * state, as wscratch) */
 	int log_cap;                  /* reflections per log */
 	int stage_ps;                 /* photons of a wave swept per round: their logs are staged in LDS (stage_ps*log_cap*PCS_ENT doubles per wave) */
 	int n_proxy, proxy_e[2];      /* energies whose weights every lane carries itself (pc_sweep_certificate) */
 	int flush_min;                /* photons of a wave that wait for a sweep before one is run for them alone */
 	int sweep_skip;               /* histogram-only runs: a weight below 2^-64 is not multiplied any further */
 	int sweep_fuse;               /* histogram-only runs: the sweep of a finished photon adds its weights to the sums itself (2: whatever its proxies say -- tests) */
+	int sweep_exact_every;        /* tests: > 0 = the logs of the photons whose slot is a multiple of this are swept as untame (EXACT loop) */
 	double ct_tame;               /* a reflection with cos theta >= ct_tame has 0 <= rtot < 1 - 1e-11 at every energy of the run */
 	/* explicit-photon mode */
 	const double *in_start, *in_dir, *in_elecv;
@@ -555,7 +559,7 @@ pc_trace_kernel(pc_kargs a)
 							const double *ls = a.lane_start + gtid*8;
 							pc_write_start_fields<true>(a, done_slot, ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
 							pc_write_exit_fields<true>(a, Pm, done_slot, ph.Px, ph.Py, ph.Pz, ph.dx, ph.dy, ph.dz, ph.ex, ph.ey, ph.ez, cosalpha0, (long long)ph.irefl, ph.dtravel);
-							if (a.img_ids) pc_store_wt(a.img_ids + done_slot, slot);
+							if (a.img_ids) pc_store_wt(a.img_ids + done_slot, a.img_id0 + slot);
 						} else {
 							pc_write_exit_fields<false>(a, Pm, done_slot, ph.Px, ph.Py, ph.Pz, ph.dx, ph.dy, ph.dz, ph.ex, ph.ey, ph.ez, cosalpha0, (long long)ph.irefl, ph.dtravel);
 						}
@@ -943,6 +947,8 @@ struct pc_hip_ctx {
 	                                * weights are not in registers; measured 9 ... 100 energies: +2 ... +130 % against the immediate sweep) */
 	int sweep_fuse = 1;            /* option "sweep_fuse": histogram-only log runs add a finished photon's weights to the sums in its sweep; 2 = also when
 	                                * its proxies are dead, so that photons the sweep finds dead exercise the take-back pass (tests) */
+	int sweep_exact_every = 0;     /* option "sweep_exact_every" (test hook): > 0 = the logs of every photon whose slot is a multiple of it are swept by the
+	                                * EXACT loop, so that sweep passes that mix EXACT and FAST photons are common (0 = off) */
 	double *d_rlog = nullptr;
 	size_t rlog_elems = 0;
 	int sweep_cert = 0;            /* pc_sweep_certificate has run */
@@ -982,7 +988,7 @@ struct pc_hip_ctx {
 	 * plane and batch, and the planes are published block by block while the kernel runs (pc_kargs::img_cursor) */
 	int compact_images = 0;
 	int compact_parts = 1;                 /* option "compact_parts": launches a compact run of 4e6 slots or more is traced in (alternating between two
-	                                        * streams).  Measured, not adopted: 2 launches 20.95 ms against 19.6 ms for one (1e7 slots; profiles/r04/kernel_history.md) */
+	                                        * streams, each with its own half of the per-lane scratch: scratch_halves).  Measured, not adopted: 2 launches 20.95 ms against 19.6 ms for one (1e7 slots; profiles/r04/kernel_history.md) */
 	int run_compact = 0;                   /* the last run did so */
 	int dst_prepinned = 0;                 /* the caller (a device group) has pinned the destination planes itself: the fetch pins nothing */
 	int keep_pinned = 0;                   /* option "keep_pinned": pc_hip_transmission_images leaves the destination planes pinned */
@@ -1002,6 +1008,11 @@ struct pc_hip_ctx {
 	size_t lane_start_elems = 0;
 	double *d_wscratch = nullptr;
 	size_t wscratch_elems = 0;
+	/* per-lane scratch (d_wscratch, d_rlog, d_lane_start) of a run cut into parts: launches on the two streams overlap, so the
+	 * buffers are allocated twice over (scratch_halves = 2), each half sized for the largest launch the run can make, and the
+	 * launches on stream2 use the second half (scratch_half = 1).  Set by the parts loop of pc_hip_transmission_run only. */
+	int scratch_halves = 1;
+	int scratch_half = 0;
 	/* explicit-photon calls (polycap_photon_launch, polycap_source_get_photon): one device buffer and one pinned host
 	 * buffer, kept between calls, so that a single photon costs two copies and a launch instead of ten copies and
 	 * as many allocations */
@@ -1282,7 +1293,10 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			int grid = (int)(want < pc_cus(ctx) ? want : pc_cus(ctx));
 			if (grid < 1) grid = 1;
 			a.total_threads = (long long)grid * PCS_BLOCK;
-			const size_t need_w = (size_t)ne * (size_t)a.total_threads, need_l = 3*(size_t)log_cap * (size_t)a.total_threads;
+			/* one launch: its own lanes; parts: halves for the largest launch, the second one for the launches on stream2 */
+			const size_t lanes = (ctx->scratch_halves > 1) ? (size_t)pc_cus(ctx) * PCS_BLOCK : (size_t)a.total_threads;
+			const size_t half_w = (size_t)ne * lanes, half_l = 3*(size_t)log_cap * lanes;
+			const size_t need_w = half_w * (size_t)ctx->scratch_halves, need_l = half_l * (size_t)ctx->scratch_halves;
 			if (need_w > ctx->wscratch_elems) {
 				if (ctx->d_wscratch) PC_HIP_CHECK(hipFree(ctx->d_wscratch));
 				ctx->d_wscratch = nullptr; ctx->wscratch_elems = 0;
@@ -1295,8 +1309,8 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 				if (hipMalloc(&ctx->d_rlog, need_l*sizeof(double)) != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "could not allocate the reflection logs");
 				ctx->rlog_elems = need_l;
 			}
-			a.wscratch = ctx->d_wscratch;
-			a.rlog = ctx->d_rlog;
+			a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half_w;
+			a.rlog = ctx->d_rlog + (size_t)ctx->scratch_half * half_l;
 			a.log_cap = log_cap;
 			a.stage_ps = (int)(stage/(PCS_ENT*(size_t)log_cap));
 			{
@@ -1315,6 +1329,7 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			a.ct_tame = ctx->sweep_ct_tame;
 			a.sweep_skip = (ctx->sweep_skip && !a.keep_images) ? 1 : 0;
 			a.sweep_fuse = a.keep_images ? 0 : ctx->sweep_fuse;
+			a.sweep_exact_every = ctx->sweep_exact_every;
 			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
 			hipLaunchKernelGGL((pc_trace_log_kernel<MODE>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage), ctx->stream, a);
 			ctx->last_kernel = 4;
@@ -1330,7 +1345,9 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 	if (grid < 1) grid = 1;
 	a.total_threads = (long long)grid * block;
 	if (kne == 0) {
-		size_t need = (size_t)ne * (size_t)a.total_threads;
+		/* one launch: its own lanes; parts: halves for the largest launch, the second one for the launches on stream2 */
+		const size_t half = (size_t)ne * ((ctx->scratch_halves > 1) ? (size_t)max_blocks * (size_t)block : (size_t)a.total_threads);
+		const size_t need = half * (size_t)ctx->scratch_halves;
 		if (need > ctx->wscratch_elems) {
 			if (ctx->d_wscratch) PC_HIP_CHECK(hipFree(ctx->d_wscratch));
 			ctx->d_wscratch = nullptr; ctx->wscratch_elems = 0;
@@ -1338,7 +1355,7 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			if (e != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "could not allocate the per-lane weight scratch");
 			ctx->wscratch_elems = need;
 		}
-		a.wscratch = ctx->d_wscratch;
+		a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half;
 	}
 	if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
 	ctx->last_kernel = 0;
@@ -1495,6 +1512,7 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "sweep_skip") ctx->sweep_skip = value ? 1 : 0;
 	else if (n == "log_min_energies") { if (value < 9) return pc_fail(PC_HIP_ERR_INVALID, "log_min_energies must be >= 9 (up to 8 energies have their weights in registers)"); ctx->log_min_energies = (int)value; }
 	else if (n == "flush_max") { if (value < 1 || value > 16) return pc_fail(PC_HIP_ERR_INVALID, "flush_max must be in [1,16]"); ctx->flush_max = (int)value; }
+	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->sweep_exact_every = (int)value; }
 	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->sweep_fuse = (int)value; }
 	else if (n == "plane_images") ctx->plane_images = value ? 1 : 0;
 	else if (n == "compact_images") ctx->compact_images = value ? 1 : 0;
@@ -1743,8 +1761,15 @@ static int pc_probe_lifetime(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, uint
 	return (st == PC_HIP_ERR_ATTEMPTS) ? PC_HIP_OK : st;
 }
 
+/* lanes of the largest launch the context makes: one 64-byte line of pc_kargs::lane_start each */
+static size_t pc_lane_start_lanes(const pc_hip_ctx *ctx)
+{
+	return (size_t)ctx->n_cu * (size_t)std::max(ctx->blocks_per_cu*ctx->block_size, 1024);
+}
+
 /* buffers of a compact run of n_slots (pc_kargs::img_cursor): position counter, per-block counters, the host-visible block
- * flags, the lanes' start-image lines and, on request, the plane of slot indices; counters and flags are cleared */
+ * flags, the lanes' start-image lines (ctx->scratch_halves sets of them) and, on request, the plane of slot indices; counters
+ * and flags are cleared */
 static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots)
 {
 	/* the block flags are cleared from the host below: a run of this context that is still in flight would set flags of its own
@@ -1776,13 +1801,13 @@ static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots)
 		ctx->ids_slots = n_slots;
 	}
 	{
-		/* one 64-byte line per lane of the largest launch the context makes */
-		const size_t lanes = (size_t)ctx->n_cu * (size_t)std::max(ctx->blocks_per_cu*ctx->block_size, 1024);
-		if (ctx->lane_start_elems < 8*lanes) {
+		/* one 64-byte line per lane of the largest launch the context makes, per half */
+		const size_t need = 8*pc_lane_start_lanes(ctx)*(size_t)ctx->scratch_halves;
+		if (ctx->lane_start_elems < need) {
 			if (ctx->d_lane_start) (void)hipFree(ctx->d_lane_start);
 			ctx->d_lane_start = nullptr; ctx->lane_start_elems = 0;
-			PC_HIP_CHECK(hipMalloc(&ctx->d_lane_start, 8*lanes*sizeof(double)));
-			ctx->lane_start_elems = 8*lanes;
+			PC_HIP_CHECK(hipMalloc(&ctx->d_lane_start, need*sizeof(double)));
+			ctx->lane_start_elems = need;
 		}
 	}
 	ctx->run_blk_shift = shift;
@@ -1816,6 +1841,25 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	ctx->run_planes = planes ? 1 : 0;
 	const bool compact = planes && ctx->compact_images;
 	ctx->run_compact = compact ? 1 : 0;
+	/* parts: consecutive slot ranges traced by consecutive launches into the same totals and image records (a photon
+	 * depends on its global slot number only, so the result does not depend on the cut) */
+	/* A compact run publishes its blocks itself: it needs no parts for the copy-back.  Option "compact_parts" > 1 traces a big one
+	 * as that many launches on two streams all the same (the positions, block counters and totals are the run's, so a launch simply
+	 * goes on where the one before leaves off): meant to cover the tail of one launch with the head of the next, it costs more
+	 * than it saves (default 1). */
+	int parts = (keep_images && ctx->run_parts > 1 && !compact) ? ctx->run_parts : 1;
+	if (compact && ctx->compact_parts > 1 && n_slots >= 4000000) parts = ctx->compact_parts;
+	if (parts > PC_MAX_PARTS) parts = PC_MAX_PARTS;
+	if ((long long)parts > n_slots / 65536) parts = (int)(n_slots / 65536);
+	if (parts < 1) parts = 1;
+	hipStream_t main_stream = ctx->stream;
+	struct restore_ctx {          /* the launch helpers read the stream, the event flags and the scratch half from the context */
+		pc_hip_ctx *c; hipStream_t s;
+		~restore_ctx() { c->stream = s; c->rec_ev0 = c->rec_ev1 = true; c->scratch_halves = 1; c->scratch_half = 0; }
+	} restore{ctx, main_stream};
+	/* launches in flight at the same time (parts on two streams) must not share per-lane scratch: two halves of it */
+	ctx->scratch_halves = (parts > 1) ? 2 : 1;
+	ctx->scratch_half = 0;
 	if (compact) {
 		int st = pc_compact_prepare(ctx, n_slots);
 		if (st) return st;
@@ -1839,25 +1883,9 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	}
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
 	a.seed = seed; a.max_attempts = max_attempts; a.keep_images = keep_images ? 1 : 0;
-	/* parts: consecutive slot ranges traced by consecutive launches into the same totals and image records (a photon
-	 * depends on its global slot number only, so the result does not depend on the cut) */
-	/* A compact run publishes its blocks itself: it needs no parts for the copy-back.  Option "compact_parts" > 1 traces a big one
-	 * as that many launches on two streams all the same (the positions, block counters and totals are the run's, so a launch simply
-	 * goes on where the one before leaves off): meant to cover the tail of one launch with the head of the next, it costs more
-	 * than it saves (default 1). */
-	int parts = (keep_images && ctx->run_parts > 1 && !compact) ? ctx->run_parts : 1;
-	if (compact && ctx->compact_parts > 1 && n_slots >= 4000000) parts = ctx->compact_parts;
-	if (parts > PC_MAX_PARTS) parts = PC_MAX_PARTS;
-	if ((long long)parts > n_slots / 65536) parts = (int)(n_slots / 65536);
-	if (parts < 1) parts = 1;
 	ctx->n_parts = compact ? 1 : parts;     /* what the fetch goes by: a compact run is fetched block by block whatever its launches */
 	const size_t rec = (size_t)PC_N_PLANES + ne;
 	int status = PC_HIP_OK;
-	hipStream_t main_stream = ctx->stream;
-	struct restore_ctx {          /* the launch helpers read the stream and the event flags from the context */
-		pc_hip_ctx *c; hipStream_t s;
-		~restore_ctx() { c->stream = s; c->rec_ev0 = c->rec_ev1 = true; }
-	} restore{ctx, main_stream};
 	if (parts > 1) {
 		/* Parts alternate between two streams.  Every launch fills the device with persistent workgroups, so the
 		 * workgroups of part k+1 start exactly as those of part k run out of slots and leave: the tail of one part (its
@@ -1878,6 +1906,11 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		if (parts > 1) {
 			a.work = ctx->d_work + k;
 			ctx->stream = (k & 1) ? ctx->stream2 : main_stream;
+			ctx->scratch_half = k & 1;       /* the launch before and the one after run on the other stream: the other half */
+			if (compact) {
+				a.lane_start = ctx->d_lane_start + (size_t)(k & 1)*8*pc_lane_start_lanes(ctx);
+				a.img_id0 = lo;           /* slot ids are the run's */
+			}
 		}
 		if (compact) ctx->rec_ev1 = false;       /* the kernel time ends behind the tail kernel below */
 		status = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, a, hi - lo)
@@ -1889,6 +1922,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		}
 	}
 	ctx->stream = main_stream;
+	ctx->scratch_half = 0;
 	if (parts > 1 && status == PC_HIP_OK) {
 		/* the main stream ends after every part: wait() synchronises it, and the kernel time runs to here */
 		for (int k = 0; k < parts; k++)

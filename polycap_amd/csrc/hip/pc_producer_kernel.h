@@ -209,7 +209,7 @@ pc_trace_producer_kernel(pc_kargs a)
 							pc_write_start_fields<true>(a, pos, s.srcx, s.srcy, s.x, s.y, s.dx, s.dy, evx, evy);
 							pc_write_exit_fields<true>(a, Pm, pos, gPx, gPy, gPz, gdx, gdy, gdz, gex, gey, gez, cosalpha0, (long long)g_irefl, gdt);
 							pc_store_wt(a.img_w + pos*ws, gw);
-							if (a.img_ids) pc_store_wt(a.img_ids + pos, g_slot);
+							if (a.img_ids) pc_store_wt(a.img_ids + pos, a.img_id0 + g_slot);
 						}
 						if (a.blk_done) {
 							asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* the stores above have reached memory */

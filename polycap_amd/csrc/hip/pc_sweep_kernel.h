@@ -31,8 +31,12 @@
  *   roughness.  r_rough = exp(-(k_E cos theta)^2) (:626-627) multiplies every factor.  The FAST loop applies the product of a
  *     log's roughness factors at once, exp(-k_E^2 sum cos^2 theta): one exponential per energy and sweep instead of one per
  *     energy and reflection (25 of 71 instructions), and one rounding of the device's 6e-15 exponential instead of one per
- *     reflection.  With roughness the weights therefore equal those of the immediate sweep to ~1e-14, not bit for bit; where a
- *     log is cut depends on the photon alone, so a photon's weights do not depend on scheduling, partition or device count.
+ *     reflection.  With roughness the weights therefore equal those of the immediate sweep to ~1e-14, not bit for bit, and
+ *     depend on where logs are cut: on the photon and the log capacity (a.log_cap) alone.  A pass takes the EXACT loop when
+ *     any of its items needs it, but every item gets the arithmetic its own log asks for (a tame log's items the FAST loop's
+ *     products and lumped roughness), so for a given log capacity a photon's weights do not depend on its pass-mates,
+ *     scheduling, partition or device count.  Option sweep_exact_every (a.sweep_exact_every, tests) sweeps the logs of every
+ *     N-th slot by the EXACT loop, which makes mixed passes common.
  *   fused finalisation, dead weights (histogram-only runs).  A photon that has reached the exit window with a live proxy is alive
  *     at the end of its log, so its sweep adds its weights to the exact LDS sums itself: no weight row is written for it and
  *     none read back by the NEW phase.  Should the sweep find it dead all the same, a second pass over its items takes the sums
@@ -200,7 +204,7 @@ pc_trace_log_kernel(pc_kargs a)
 			const unsigned info = map[qc];
 			const int p = (int)(info & 63u);
 			const int n = act ? (int)((info >> 8) & 255u) : 0;
-			const bool exact = act && (info & 0x80u);
+			const bool exact = act && (info & 0x80u);      /* this item's own log is untame (the pass is EXACT if any item's is) */
 			double *const wrow = a.wscratch + (wave_gtid0 + p)*(long long)ne + ee;
 			double w = 1.0;
 			if (act && (info & 0x40u)) w = *wrow;
@@ -246,7 +250,10 @@ pc_trace_log_kernel(pc_kargs a)
 				alive = act && (w >= 1.e-4);
 			} else {
 				/* EXACT: the reference's tests at every reflection.  cnt = leading reflections after which this energy still holds
-				 * >= 1e-4; bad = first reflection whose rtot the reference rejects at this energy */
+				 * >= 1e-4; bad = first reflection whose rtot the reference rejects at this energy.  Items of tame logs in such a pass
+				 * (`exact` is the item's own log's flag) get what the FAST loop gives them: the same products in the same order and
+				 * the log's roughness as one factor at the end.  So a photon's weights do not depend on its pass-mates, and the
+				 * take-back pass of a fused photon subtracts exactly what its first pass added */
 				unsigned cnt = 0u, bad = 255u;
 				bool lead = true;
 				const double k2 = rough ? ecs[4*ne + ee] : 0.;
@@ -255,7 +262,7 @@ pc_trace_log_kernel(pc_kargs a)
 						const double rt = pc_fresnel3(d2, n2r, n2i, zi2, gq[PCS_ENT*r], gq[PCS_ENT*r + 1], gq[PCS_ENT*r + 2], gq[PCS_ENT*r + 3]);
 						if ((rt < 0. || rt > 1.) && bad == 255u) bad = (unsigned)r;          /* src/polycap-capil.c:633-637 */
 						double f = rt;
-						if (rough) f = rt*pc_exp_neg_fast(-(k2*gq[PCS_ENT*r + 1]));
+						if (rough && exact) f = rt*pc_exp_neg_fast(-(k2*gq[PCS_ENT*r + 1]));
 						w = w*f;
 						lead = lead && (w >= 1.e-4);
 						cnt += lead ? 1u : 0u;
@@ -266,7 +273,8 @@ pc_trace_log_kernel(pc_kargs a)
 					atomicMax(&vcnt[qc], cnt);
 					if (bad != 255u) atomicMin(&vbad[qc], bad);
 				}
-				alive = act && (cnt == (unsigned)n);
+				if (rough && !exact) w = w*pc_exp_neg_fast(-(k2*l_csum[qc]));
+				alive = act && (exact ? (cnt == (unsigned)n) : (w >= 1.e-4));
 			}
 			if (act) {
 				if (info & 0x10000u) {
@@ -349,6 +357,9 @@ pc_trace_log_kernel(pc_kargs a)
 				/* tame: cos theta above the host's certificate, fractions as the geometry makes them (fs in [0, 1], fp = 1 - fs to
 				 * rounding).  NaNs fail every comparison. */
 				if (!(fr_c >= a.ct_tame && fr_c <= 1.0 && fs >= 0. && fs <= 1.0000001 && fp >= -1.e-7 && fp <= 1.0000001)) untame = 1;
+				/* test hook (option sweep_exact_every): the logs of every N-th slot are swept by the EXACT loop all the same -- always
+				 * correct (EXACT adds the range tests only), and it makes passes that mix EXACT and FAST photons common */
+				if (a.sweep_exact_every > 0 && (a.slot0 + slot) % a.sweep_exact_every == 0) untame = 1;
 				if (lim == K) {
 					{
 						const int pe = a.proxy_e[0];
@@ -467,7 +478,7 @@ pc_trace_log_kernel(pc_kargs a)
 							const double *ls = a.lane_start + gtid*8;
 							pc_write_start_fields<true>(a, done_slot, ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
 							pc_write_exit_fields<true>(a, Pm, done_slot, ph.Px, ph.Py, ph.Pz, ph.dx, ph.dy, ph.dz, ph.ex, ph.ey, ph.ez, cosalpha0, (long long)ph.irefl, ph.dtravel);
-							if (a.img_ids) pc_store_wt(a.img_ids + done_slot, slot);
+							if (a.img_ids) pc_store_wt(a.img_ids + done_slot, a.img_id0 + slot);
 						} else {
 							pc_write_exit_fields<false>(a, Pm, done_slot, ph.Px, ph.Py, ph.Pz, ph.dx, ph.dy, ph.dz, ph.ex, ph.ey, ph.ez, cosalpha0, (long long)ph.irefl, ph.dtravel);
 						}

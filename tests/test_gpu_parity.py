@@ -919,12 +919,14 @@ def test_plane_images_equal_records(pa, oracle):
     """Option "plane_images" (what polycap_source_get_transmission_efficiencies uses): the kernels store the planes of
     struct _polycap_images themselves and the fetch is a copy of planes into the caller's pinned arrays.  Same bits as the
     record store, for one energy (pool kernel), seven (register weights) and twelve (weights in memory), whole and in
-    parts, full and partial fetches; the record fetch refuses a plane run."""
+    parts, full and partial fetches; the record fetch refuses a plane run.  Every run of 3 parts is big enough to be traced as
+    three launches (a run is cut into at most n_slots / 65536)."""
     cases = [make_pair(oracle, "xos1", source=(2000., 0.2065, 0.2065, 0., 0., 0., 0., 0.0))[2],
              make_pair(oracle, "ellip", energies=(5.0, 8.0, 11.0, 14.0, 17.0, 20.0, 25.0))[2],
              make_pair(oracle, "xos1", energies=np.linspace(3.0, 30.0, 12))[2]]
     for prob in cases:
-        n = 300_000 if prob.n_energies == 1 else 120_000
+        n = 300_000 if prob.n_energies == 1 else 200_000
+        assert n >= 3 * 65536
         with pa.TraceContext(prob) as ctx:
             ctx.run(13, 7, n, keep_images=True)
             ref = ctx.image_planes(0, n)
