@@ -225,6 +225,53 @@ POLYCAP_EXTERN int pc_hip_group_images(pc_hip_group *group, const pc_hip_images 
 POLYCAP_EXTERN int pc_hip_group_totals(pc_hip_group *group, int reduce, double *sum_weights, int64_t counters[6], uint64_t *sumw_fixed,
 	int *reduced_by, float *kernel_ms);
 
+/* ---- spot maps: weighted 2-D histograms of where the photons of the last run cross planes perpendicular to the optic axis,
+ * downstream of its exit face, one map per selected energy, accumulated on the device in exact integers from what the run left
+ * there (no copy to the host, no change to the run).
+ *
+ * The contract (IEEE fp64, evaluated in the order written, no contraction):
+ *   planes     zp_k = z[nmax] + d_k, computed once on the host; d_k >= 0 in cm
+ *   per entry  with position (x, y, z), direction (dx, dy, dz) and weights w[e]:
+ *              exit photons: dz = sqrt((1 - dx*dx) - dy*dy) (their records carry dx and dy only); leak events: the stored dz
+ *              t = (zp - z) / dz,  xd = x + dx*t,  yd = y + dy*t
+ *              fx = ((xd - x0) / (x1 - x0)) * nx,  ix = floor(fx);  fy, iy the same way with y0, y1, ny
+ *              inside when 0 <= fx < nx and 0 <= fy < ny; anything else is outside: NaN, dz <= 0, off the window
+ *   weights    q(w) = round_half_even(w * 2^32) as uint64 (w <= 0 and NaN give 0); a bin holds the sum of q(w[e]) over its
+ *              entries, and every (plane, energy) pair has one outside counter for the rest, so that for every map
+ *              sum(bins) + outside == sum over the entries of q(w[e]), exactly
+ *   entries    one map takes at most 2^32 - 1 entries over all its adds (then no uint64 can wrap); an add past that fails
+ * Sums are integer sums: a map depends neither on launch shape ("run_parts", compact or slot order, the kernel that traced the
+ * run), nor on how the slots were split into consecutive runs added to one map, nor on the device count.
+ * Output layout: bins [plane][selected energy][iy][ix], outside [plane][selected energy]. */
+typedef struct {
+	int32_t n_planes;             /* 1 .. 64 */
+	const double *distances;      /* [n_planes] cm downstream of the exit face, finite, >= 0 */
+	double x0, x1, y0, y1;        /* window, cm: finite, x0 < x1, y0 < y1 */
+	int32_t nx, ny;               /* bins, >= 1; n_planes * n_selected * nx * ny <= 2^27 */
+	int32_t n_energies;           /* selected energies: 0 = all, in order */
+	const int32_t *energies;      /* [n_energies] distinct indices into the problem's energies */
+	int32_t regime;               /* 0 automatic (= 2, measured: pc_spot.h); 1 LDS tiles, 2 energies across lanes */
+} pc_hip_spot_spec;
+typedef struct pc_hip_spot pc_hip_spot;
+/* PC_HIP_ERR_INVALID with a message unless the spec is valid for a problem of n_energies energies (no device is touched) */
+POLYCAP_EXTERN int pc_hip_spot_validate(const pc_hip_spot_spec *spec, size_t n_energies);
+/* An empty map on the context's device (the context must outlive it).  The group variant keeps one map per member; reading it
+ * sums the members' maps exactly on the host. */
+POLYCAP_EXTERN int pc_hip_spot_create(pc_hip_ctx *ctx, const pc_hip_spot_spec *spec, pc_hip_spot **spot);
+POLYCAP_EXTERN int pc_hip_group_spot_create(pc_hip_group *group, const pc_hip_spot_spec *spec, pc_hip_spot **spot);
+POLYCAP_EXTERN void pc_hip_spot_destroy(pc_hip_spot *spot);
+/* Adds the entries of the last run: kind 0 = exit photons (a run that kept images), 1 = extleak, 2 = intleak events (a leak_calc
+ * source run).  Enqueued on the context's stream behind the run, so pc_hip_transmission_wait orders it; leak kinds wait for the
+ * run first (its events are ordered when it is waited for).  Anything else is PC_HIP_ERR_INVALID. */
+POLYCAP_EXTERN int pc_hip_spot_add(pc_hip_spot *spot, int kind);
+/* bins [n_planes * n_selected * ny * nx], outside [n_planes * n_selected], *n_entries (any may be NULL); waits for the adds */
+POLYCAP_EXTERN int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t *outside, int64_t *n_entries);
+POLYCAP_EXTERN int pc_hip_spot_reset(pc_hip_spot *spot);
+/* dims = {n_planes, n_selected, ny, nx}; *wide (optional) = 1 when the map accumulates with energies across lanes, 0 in LDS tiles */
+POLYCAP_EXTERN int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide);
+/* free and total memory of the context's device, bytes */
+POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
+
 /* Scheduler statistics of the last transmission run (diagnostics): {march steps, march lane-steps, event phases,
  * event lanes, new phases, new lanes}, summed over all waves; lanes/phases = average active lanes per phase. */
 POLYCAP_EXTERN int pc_hip_phase_stats(pc_hip_ctx *ctx, int64_t stats[6]);
@@ -258,6 +305,15 @@ POLYCAP_EXTERN double pc_hip_fixed_to_double(uint64_t lo, uint64_t hi);
  * Returns a polycap_transmission_efficiencies* or NULL with *error (a polycap_error**) set. */
 POLYCAP_EXTERN void *pc_transmission_efficiencies_from_totals(void *source, int64_t n_exit, const double *sum_weights,
 	const int64_t counters[6], const pc_hip_images *planes, void *error);
+
+/* Spot maps of a result of polycap_source_get_transmission_efficiencies made with POLYCAP_SPOT set (efficiencies: a
+ * polycap_transmission_efficiencies*, error: a polycap_error**).  kind 0 = exit photons, 1 = extleak, 2 = intleak (leak_calc runs).
+ * dims = {n_planes, n_energies, ny, nx}; window = {x0, x1, y0, y1} cm; *distances [n_planes] cm, *energies [n_energies] keV,
+ * *maps [plane][energy][iy][ix] and *outside [plane][energy] are copies to be freed with polycap_free (any of them may be NULL).
+ * The maps are in efficiency units: map = efficiency[e] * S_bin / (S_inside + S_outside) from the exact sums, so that a map plus
+ * its outside part sums to the efficiency.  Returns 1, or 0 with *error set. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_spot(void *efficiencies, int kind, int32_t dims[4], double **distances, double window[4],
+	double **energies, double **maps, double **outside, void *error);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,13 @@ class ImagesS(C.Structure):
                 ("pc_exit_dtravel", c_double_p), ("exit_coord_weights", c_double_p)]
 
 
+class SpotSpecS(C.Structure):
+    """struct pc_hip_spot_spec"""
+    _fields_ = [("n_planes", C.c_int32), ("distances", c_double_p), ("x0", C.c_double), ("x1", C.c_double),
+                ("y0", C.c_double), ("y1", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("n_energies", C.c_int32), ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -176,6 +183,24 @@ def lib():
     L.pc_hip_efficiencies.restype = None
     L.pc_hip_fixed_to_double.argtypes = [C.c_uint64, C.c_uint64]
     L.pc_hip_fixed_to_double.restype = C.c_double
+    L.pc_hip_spot_validate.argtypes = [P(SpotSpecS), C.c_size_t]
+    L.pc_hip_spot_validate.restype = C.c_int
+    L.pc_hip_spot_create.argtypes = [C.c_void_p, P(SpotSpecS), P(C.c_void_p)]
+    L.pc_hip_spot_create.restype = C.c_int
+    L.pc_hip_group_spot_create.argtypes = [C.c_void_p, P(SpotSpecS), P(C.c_void_p)]
+    L.pc_hip_group_spot_create.restype = C.c_int
+    L.pc_hip_spot_destroy.argtypes = [C.c_void_p]
+    L.pc_hip_spot_destroy.restype = None
+    L.pc_hip_spot_add.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_spot_add.restype = C.c_int
+    L.pc_hip_spot_read.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), c_int64_p]
+    L.pc_hip_spot_read.restype = C.c_int
+    L.pc_hip_spot_reset.argtypes = [C.c_void_p]
+    L.pc_hip_spot_reset.restype = C.c_int
+    L.pc_hip_spot_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int)]
+    L.pc_hip_spot_info.restype = C.c_int
+    L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
+    L.pc_hip_device_memory.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

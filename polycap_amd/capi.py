@@ -128,6 +128,7 @@ def _lib():
         "polycap_transmission_efficiencies_get_exit_data": (C.c_bool, [vp, P(C.c_int64)] + [P(P(_Vec3))] * 3 +
                                                              [P(P(C.c_int64)), P(_dp), P(C.c_size_t), P(P(_dp)), epp]),
         "polycap_transmission_efficiencies_write_hdf5": (C.c_bool, [vp, C.c_char_p, epp]),
+        "pc_transmission_efficiencies_get_spot": (C.c_int, [vp, C.c_int, P(C.c_int32), P(_dp), _dp, P(_dp), P(_dp), P(_dp), epp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -402,6 +403,23 @@ class TransmissionEfficiencies(_LeakData):
             F.flags.writeable = False
             self._data = (E, F)
         return self._data
+
+    SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}
+
+    def spot_map(self, kind="exit"):
+        """Spot maps of a run made with POLYCAP_SPOT set (extension, pc_transmission_efficiencies_get_spot): dict of
+        maps [plane, energy, iy, ix] and outside [plane, energy] in efficiency units, distances (cm), window (x0, x1, y0, y1; cm)
+        and energies (keV).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        dims = (C.c_int32 * 4)()
+        win = (C.c_double * 4)()
+        d, e, m, o = _dp(), _dp(), _dp(), _dp()
+        err = _ErrP()
+        _lib().pc_transmission_efficiencies_get_spot(self._h, self.SPOT_KINDS[kind], dims, C.byref(d), win, C.byref(e), C.byref(m),
+                                                     C.byref(o), C.byref(err))
+        _check(err)
+        npl, ns, ny, nx = (int(v) for v in dims)
+        return dict(maps=_take(m, npl * ns * ny * nx).reshape(npl, ns, ny, nx), outside=_take(o, npl * ns).reshape(npl, ns),
+                    distances=_take(d, npl), energies=_take(e, ns), window=tuple(win))
 
     def _start(self):
         L = _lib()

@@ -1061,6 +1061,7 @@ struct pc_hip_ctx {
 	void *d_leak_order_tmp = nullptr;
 	size_t leak_order_bytes = 0;
 	long long leak_n_ext = 0, leak_n_int = 0;
+	int leak_events_of_run = 0;            /* the event lists are those of the last source run (a leak run): pc_hip_spot_add may read them */
 };
 
 static int pc_cus(const pc_hip_ctx *ctx)
@@ -1651,6 +1652,7 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 done:
 #undef PC_LP_CHECK
 	ctx->img_valid = 0;
+	ctx->leak_events_of_run = 0;
 	return status;
 }
 
@@ -1831,6 +1833,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		if (st != PC_HIP_OK) return st;
 	}
 	ctx->last_run_plain = 1;
+	ctx->leak_events_of_run = 0;
 	pc_kargs a;
 	pc_fill_common(ctx, a);
 	ctx->img_valid = 0;
@@ -1960,6 +1963,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	ctx->n_parts = 1;
 	ctx->run_planes = 0;
 	ctx->last_run_plain = 0;
+	ctx->leak_events_of_run = 1;
 	ctx->leak_seed = seed; ctx->leak_slot0 = slot0; ctx->leak_n_slots = n_slots;
 	ctx->leak_max_attempts = max_attempts; ctx->leak_keep_images = keep_images ? 1 : 0;
 	/* record buffer: events per slot grow with the number of energies (a leak is kept while ANY energy holds >= 1e-4):
@@ -2549,6 +2553,7 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 } /* extern "C" */
 
 #include "pc_group.h"
+#include "pc_spot.h"
 
 /* Heaviest slots first.  A leak launch ends with its longest slot: 20 000 units of work on one lane, which advances several
  * times faster alone in its wave than among 63 others (a wave runs one class of work at a time).  Which slots are long is known

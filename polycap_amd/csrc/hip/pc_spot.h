@@ -1,0 +1,433 @@
+/*
+ * pc_spot.h -- spot maps: weighted 2-D histograms of where the photons of the last run cross planes perpendicular to the optic
+ * axis downstream of its exit face (include/polycap-hip.h, pc_hip_spot_*).  A post-pass over data the run left in HBM: the exit
+ * photons (image records or planes) and the ordered leak event lists.  Nothing is uploaded from the host and no trace kernel is
+ * involved.  Sums are exact integer sums (uint64, weights quantised to 2^-32), so a map depends on the set of entries only:
+ * not on launch shape, entry order, how the slots were split into runs, or the device count.
+ *
+ * The first part (the per-entry arithmetic) compiles for the host as well: -DPC_SPOT_HOST_ONLY stops the header after it.
+ */
+#ifndef PC_SPOT_H
+#define PC_SPOT_H
+
+#include <math.h>
+#include <stdint.h>
+
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
+
+/* Bin of one entry on the plane z = zp, in [0, nx*ny) as iy*nx + ix, or -1 when it is outside (NaN anywhere, dz <= 0, off the
+ * window).  The contract of include/polycap-hip.h, operation by operation (the library is built with -ffp-contract=off). */
+static inline __host__ __device__ long long pc_spot_bin(double x, double y, double z, double dx, double dy, double dz, double zp,
+	double x0, double x1, double y0, double y1, int nx, int ny)
+{
+	const double t = (zp - z) / dz;
+	const double xd = x + dx*t, yd = y + dy*t;
+	const double fx = ((xd - x0) / (x1 - x0)) * (double)nx;
+	const double fy = ((yd - y0) / (y1 - y0)) * (double)ny;
+	if (!(dz > 0.) || !(fx >= 0. && fx < (double)nx && fy >= 0. && fy < (double)ny))
+		return -1;
+	return (long long)floor(fy) * nx + (long long)floor(fx);
+}
+
+/* exit photons carry the x and y components of their direction only */
+static inline __host__ __device__ double pc_spot_exit_dz(double dx, double dy)
+{
+	return sqrt((1. - dx*dx) - dy*dy);
+}
+
+/* q(w) = round_half_even(w * 2^32); weights are in [0, 1], anything not above zero (NaN included) counts 0 */
+static inline __host__ __device__ unsigned long long pc_spot_q(double w)
+{
+	const double v = w * 4294967296.0;
+	return (v > 0.) ? (unsigned long long)rint(v) : 0ull;
+}
+
+#ifndef PC_SPOT_HOST_ONLY
+
+/* Where the entries are: field f of entry i at p[i*ss + f*fs], weight e at w[i*ws + e] */
+struct pc_spot_src {
+	const double *p;
+	long long ss, fs, n;
+	int f_x, f_dx;          /* x, y, z at f_x .. f_x + 2; dx, dy (, dz when has_dz) from f_dx on */
+	int has_dz;
+	const double *w;
+	long long ws;
+};
+
+struct pc_spot_geo {
+	const double *zp;       /* [np] plane positions */
+	const int *sel;         /* [ns] energy indices */
+	double x0, x1, y0, y1;
+	int nx, ny, np, ns;
+};
+
+static __device__ __forceinline__ long long pc_spot_entry_bin(const pc_spot_src &s, const pc_spot_geo &g, long long i, int p)
+{
+	const double *e = s.p + i*s.ss;
+	const double x = e[(long long)s.f_x*s.fs], y = e[(long long)(s.f_x + 1)*s.fs], z = e[(long long)(s.f_x + 2)*s.fs];
+	const double dx = e[(long long)s.f_dx*s.fs], dy = e[(long long)(s.f_dx + 1)*s.fs];
+	const double dz = s.has_dz ? e[(long long)(s.f_dx + 2)*s.fs] : pc_spot_exit_dz(dx, dy);
+	return pc_spot_bin(x, y, z, dx, dy, dz, g.zp[p], g.x0, g.x1, g.y0, g.y1, g.nx, g.ny);
+}
+
+/* Small maps.  The flat map [plane][energy][iy][ix] followed by the outside counters [plane][energy] is cut into tiles of
+ * PC_SPOT_TILE uint64 bins; workgroup (x, y) adds the entries x, x + gridDim.x, ... that fall into tile y to a private copy of it
+ * in LDS (ds_add_u64), then adds each non-zero bin of that copy to the map with one global atomic.  Maps of several tiles are
+ * several passes over the entries (blockIdx.y). */
+#define PC_SPOT_TILE 8192
+#define PC_SPOT_LDS_BLOCK 512
+__global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
+{
+	__shared__ unsigned long long tile[PC_SPOT_TILE];
+	const long long nb = (long long)g.nx*g.ny, n_bins = (long long)g.np*g.ns*nb, total = n_bins + (long long)g.np*g.ns;
+	const long long t0 = (long long)blockIdx.y*PC_SPOT_TILE;
+	const long long t1 = (t0 + PC_SPOT_TILE < total) ? t0 + PC_SPOT_TILE : total;
+	for (int k = threadIdx.x; k < PC_SPOT_TILE; k += blockDim.x) tile[k] = 0ull;
+	__syncthreads();
+	for (long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x; i < s.n; i += (long long)gridDim.x*blockDim.x) {
+		for (int p = 0; p < g.np; p++) {
+			const long long b = pc_spot_entry_bin(s, g, i, p);
+			/* the entry's cells for energies 0 .. ns-1: base + k*step */
+			const long long base = (b >= 0) ? (long long)p*g.ns*nb + b : n_bins + (long long)p*g.ns;
+			const long long step = (b >= 0) ? nb : 1;
+			if (base >= t1) continue;
+			const long long k_lo = (base >= t0) ? 0 : (t0 - base + step - 1)/step;
+			long long k_hi = (t1 - 1 - base)/step + 1;
+			if (k_hi > g.ns) k_hi = g.ns;
+			for (long long k = k_lo; k < k_hi; k++) {
+				const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[k]]);
+				if (q) atomicAdd(&tile[base + k*step - t0], q);
+			}
+		}
+	}
+	__syncthreads();
+	for (long long k = threadIdx.x; k < t1 - t0; k += blockDim.x) {
+		const unsigned long long v = tile[k];
+		if (v) atomicAdd(&map[t0 + k], v);
+	}
+}
+
+/* Many selected energies.  The bins are laid out [plane][iy][ix][energy] with the energies innermost: the lanes of a wave take
+ * the energies of one entry (64 / gw entries per wave when fewer than 64 are selected, gw = the next power of two), so that one
+ * wave instruction is a contiguous run of 8-byte global atomics.  Workgroup (x, p, c) does plane p for energies
+ * [c*PC_SPOT_ECHUNK, ...); the outside counters of those energies are summed in LDS first (every entry that misses the window
+ * adds to the same few counters). */
+#define PC_SPOT_ECHUNK 4096
+#define PC_SPOT_WIDE_BLOCK 256
+__global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
+{
+	__shared__ unsigned long long out[PC_SPOT_ECHUNK];
+	const int p = blockIdx.y, s0 = blockIdx.z*PC_SPOT_ECHUNK;
+	const int sn = (g.ns - s0 < PC_SPOT_ECHUNK) ? g.ns - s0 : PC_SPOT_ECHUNK;
+	const long long nb = (long long)g.nx*g.ny, n_bins = (long long)g.np*g.ns*nb;
+	for (int k = threadIdx.x; k < sn; k += blockDim.x) out[k] = 0ull;
+	__syncthreads();
+	int gw = 1;
+	while (gw < sn && gw < 64) gw <<= 1;
+	const int lane = threadIdx.x & 63, sub = lane & (gw - 1), per_wave = 64 / gw;
+	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
+	for (long long i = wave*per_wave + lane / gw; i < s.n; i += n_waves*per_wave) {
+		const long long b = pc_spot_entry_bin(s, g, i, p);
+		unsigned long long *cell = map + ((long long)p*nb + (b >= 0 ? b : 0))*g.ns + s0;
+		for (int k = sub; k < sn; k += gw) {
+			const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[s0 + k]]);
+			if (!q) continue;
+			if (b >= 0) atomicAdd(cell + k, q);
+			else atomicAdd(&out[k], q);
+		}
+	}
+	__syncthreads();
+	for (int k = threadIdx.x; k < sn; k += blockDim.x) {
+		const unsigned long long v = out[k];
+		if (v) atomicAdd(&map[n_bins + (long long)p*g.ns + s0 + k], v);
+	}
+}
+
+/* Regime of a map (spec->regime 0): energies across lanes.  Measured on an MI355X (scripts/bench_spot.py; xos1, 1e7 exit photons,
+ * one plane, window +-0.02 cm): at 10 keV 128^2 LDS tiles 0.86 ms per add against 0.38 ms, 1024^2 37.1 ms (128 passes) against
+ * 0.37 ms; at 291 energies x 64^2 with 3 / 9 / 291 energies selected 1.03 / 4.16 / 1117 ms against 0.83 / 2.51 / 15.5 ms.  The
+ * LDS tiles won no measured case, so there is no crossover to apply: they stay available as regime 1 (maps of a single tile with
+ * a very concentrated spot are where they could still win; not measured). */
+
+struct pc_spot_member {
+	pc_hip_ctx *ctx = nullptr;
+	unsigned long long *d_map = nullptr;
+	double *d_zp = nullptr;
+	int *d_sel = nullptr;
+};
+
+struct pc_hip_spot {
+	std::vector<pc_spot_member> m;
+	pc_hip_group *group = nullptr;
+	int np = 0, ns = 0, nx = 0, ny = 0, wide = 0;
+	double x0 = 0., x1 = 0., y0 = 0., y1 = 0.;
+	std::vector<int> sel;
+	long long n_entries = 0;
+	size_t map_elems = 0;             /* np*ns*nx*ny bins + np*ns outside counters */
+};
+
+static void pc_spot_free_member(pc_spot_member &mb)
+{
+	if (!mb.ctx) return;
+	(void)hipSetDevice(mb.ctx->device);
+	if (mb.ctx->stream) (void)hipStreamSynchronize(mb.ctx->stream);
+	if (mb.d_map) (void)hipFree(mb.d_map);
+	if (mb.d_zp) (void)hipFree(mb.d_zp);
+	if (mb.d_sel) (void)hipFree(mb.d_sel);
+	mb = pc_spot_member();
+}
+
+static int pc_spot_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *group, const pc_hip_spot_spec *spec, pc_hip_spot **out)
+{
+	if (!out) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_create: spot must not be NULL");
+	*out = nullptr;
+	const pc_hip_ctx *c0 = ctxs[0];
+	int st = pc_hip_spot_validate(spec, (size_t)c0->host.pm.n_energies);
+	if (st) return st;
+	pc_hip_spot *sp = new pc_hip_spot();
+	sp->group = group;
+	sp->np = spec->n_planes; sp->nx = spec->nx; sp->ny = spec->ny;
+	sp->x0 = spec->x0; sp->x1 = spec->x1; sp->y0 = spec->y0; sp->y1 = spec->y1;
+	if (spec->n_energies == 0)
+		for (int e = 0; e < c0->host.pm.n_energies; e++) sp->sel.push_back(e);
+	else
+		sp->sel.assign(spec->energies, spec->energies + spec->n_energies);
+	sp->ns = (int)sp->sel.size();
+	const long long nb = (long long)sp->nx*sp->ny, total = (long long)sp->np*sp->ns*nb + (long long)sp->np*sp->ns;
+	sp->map_elems = (size_t)total;
+	sp->wide = spec->regime != 1;
+	/* zp = z[nmax] + d, once, on the host */
+	std::vector<double> zp(sp->np);
+	const double zexit = c0->host.z[c0->host.pm.nmax];
+	for (int k = 0; k < sp->np; k++) zp[k] = zexit + spec->distances[k];
+	for (pc_hip_ctx *c : ctxs) {
+		pc_spot_member mb;
+		mb.ctx = c;
+		sp->m.push_back(mb);
+		pc_spot_member &m = sp->m.back();
+		hipError_t e = hipSetDevice(c->device);
+		if (e == hipSuccess) e = hipMalloc(&m.d_map, sp->map_elems*sizeof(unsigned long long));
+		if (e == hipSuccess) e = hipMalloc(&m.d_zp, zp.size()*sizeof(double));
+		if (e == hipSuccess) e = hipMalloc(&m.d_sel, sp->sel.size()*sizeof(int));
+		if (e == hipSuccess) e = hipMemcpy(m.d_zp, zp.data(), zp.size()*sizeof(double), hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = hipMemcpy(m.d_sel, sp->sel.data(), sp->sel.size()*sizeof(int), hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = hipMemsetAsync(m.d_map, 0, sp->map_elems*sizeof(unsigned long long), c->stream);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			pc_hip_spot_destroy(sp);
+			return pc_fail(e == hipErrorOutOfMemory ? PC_HIP_ERR_MEMORY : PC_HIP_ERR_RUNTIME, std::string("pc_hip_spot_create: ") + hipGetErrorString(e));
+		}
+	}
+	*out = sp;
+	return PC_HIP_OK;
+}
+
+/* the entries of `kind` that the last run of c left on its device */
+static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s)
+{
+	const long long ne = c->host.pm.n_energies;
+	memset(&s, 0, sizeof(s));
+	if (kind == 0) {
+		if (!c->img_valid)
+			return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: the last run kept no exit photons (run it with keep_images)");
+		if (c->leak_pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
+			int st = pc_hip_transmission_wait(c, nullptr);
+			if (st) return st;
+		}
+		const long long n = c->run_slots;
+		s.n = n; s.f_x = 8; s.f_dx = 11; s.has_dz = 0;          /* pc_exit_coords, pc_exit_dir: planes 8..10, 11..12 */
+		if (c->run_planes) {
+			s.p = c->d_soa; s.ss = 1; s.fs = n;
+			s.w = c->d_soa + (long long)PC_N_FIELDS*n; s.ws = ne;
+		} else {
+			s.p = c->d_img; s.ss = PC_N_FIELDS + ne; s.fs = 1;
+			s.w = c->d_img + PC_N_FIELDS; s.ws = PC_N_FIELDS + ne;
+		}
+		return PC_HIP_OK;
+	}
+	if (!c->leak_events_of_run)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: leak events need a leak_calc source run (pc_hip_transmission_run_leak) as the last run");
+	int st = pc_hip_transmission_wait(c, nullptr);      /* the events are ordered into d_leak_out when the run is waited for */
+	if (st) return st;
+	const long long stride = PC_HIP_LEAK_HDR + ne;
+	s.n = (kind == 1) ? c->leak_n_ext : c->leak_n_int;
+	s.p = c->d_leak_out + ((kind == 1) ? 0 : c->leak_n_ext*stride);
+	s.ss = stride; s.fs = 1; s.f_x = 2; s.f_dx = 5; s.has_dz = 1;
+	s.w = s.p + PC_HIP_LEAK_HDR; s.ws = stride;
+	return PC_HIP_OK;
+}
+
+static int pc_spot_launch(pc_hip_spot *sp, pc_spot_member &m, const pc_spot_src &s)
+{
+	if (s.n == 0) return PC_HIP_OK;
+	pc_hip_ctx *c = m.ctx;
+	pc_spot_geo g;
+	g.zp = m.d_zp; g.sel = m.d_sel;
+	g.x0 = sp->x0; g.x1 = sp->x1; g.y0 = sp->y0; g.y1 = sp->y1;
+	g.nx = sp->nx; g.ny = sp->ny; g.np = sp->np; g.ns = sp->ns;
+	const long long cus = c->n_cu;
+	if (!sp->wide) {
+		const long long tiles = ((long long)sp->map_elems + PC_SPOT_TILE - 1)/PC_SPOT_TILE;
+		long long bx = (2*cus + tiles - 1)/tiles;                       /* two workgroups per CU in all (LDS: 64 KiB each) */
+		const long long need = (s.n + PC_SPOT_LDS_BLOCK - 1)/PC_SPOT_LDS_BLOCK;
+		if (bx > need) bx = need;
+		if (bx < 1) bx = 1;
+		hipLaunchKernelGGL(pc_spot_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_map);
+	} else {
+		const long long chunks = (sp->ns + PC_SPOT_ECHUNK - 1)/PC_SPOT_ECHUNK;
+		long long bx = (8*cus + sp->np*chunks - 1)/(sp->np*chunks);
+		int gw = 1;
+		while (gw < sp->ns && gw < 64) gw <<= 1;
+		const long long need = (s.n*gw + PC_SPOT_WIDE_BLOCK - 1)/PC_SPOT_WIDE_BLOCK;
+		if (bx > need) bx = need;
+		if (bx < 1) bx = 1;
+		hipLaunchKernelGGL(pc_spot_wide_kernel, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_map);
+	}
+	PC_HIP_CHECK(hipGetLastError());
+	return PC_HIP_OK;
+}
+
+extern "C" {
+
+int pc_hip_spot_validate(const pc_hip_spot_spec *spec, size_t n_energies)
+{
+	if (!spec) return pc_fail(PC_HIP_ERR_INVALID, "spot spec must not be NULL");
+	if (spec->n_planes < 1 || spec->n_planes > 64 || !spec->distances)
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: 1 to 64 plane distances are needed, got " + std::to_string(spec->n_planes));
+	for (int k = 0; k < spec->n_planes; k++)
+		if (!(spec->distances[k] >= 0.) || !std::isfinite(spec->distances[k]))
+			return pc_fail(PC_HIP_ERR_INVALID, "spot spec: plane distances must be finite and >= 0");
+	if (!std::isfinite(spec->x0) || !std::isfinite(spec->x1) || !std::isfinite(spec->y0) || !std::isfinite(spec->y1)
+	    || !(spec->x0 < spec->x1) || !(spec->y0 < spec->y1))
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: the window needs finite x0 < x1 and y0 < y1");
+	if (spec->nx < 1 || spec->ny < 1)
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: nx and ny must be >= 1");
+	if (spec->regime < 0 || spec->regime > 2)
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: regime must be 0 (automatic), 1 (LDS tiles) or 2 (energies across lanes)");
+	if (spec->n_energies < 0 || (size_t)spec->n_energies > n_energies || (spec->n_energies > 0 && !spec->energies))
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: between 1 and n_energies energy indices (0 = all energies)");
+	std::vector<char> seen(n_energies, 0);
+	for (int k = 0; k < spec->n_energies; k++) {
+		const int e = spec->energies[k];
+		if (e < 0 || (size_t)e >= n_energies)
+			return pc_fail(PC_HIP_ERR_INVALID, "spot spec: energy index " + std::to_string(e) + " out of range (" + std::to_string(n_energies) + " energies)");
+		if (seen[e]) return pc_fail(PC_HIP_ERR_INVALID, "spot spec: energy index " + std::to_string(e) + " given twice");
+		seen[e] = 1;
+	}
+	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
+	if ((double)spec->n_planes*ns*(double)spec->nx*(double)spec->ny > (double)(1ll << 27))
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: n_planes * n_energies * nx * ny exceeds 2^27 bins");
+	return PC_HIP_OK;
+}
+
+int pc_hip_spot_create(pc_hip_ctx *ctx, const pc_hip_spot_spec *spec, pc_hip_spot **spot)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_create: ctx must not be NULL");
+	return pc_spot_make(std::vector<pc_hip_ctx *>{ctx}, nullptr, spec, spot);
+}
+
+int pc_hip_group_spot_create(pc_hip_group *group, const pc_hip_spot_spec *spec, pc_hip_spot **spot)
+{
+	if (!group) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_spot_create: group must not be NULL");
+	return pc_spot_make(group->ctx, group, spec, spot);
+}
+
+void pc_hip_spot_destroy(pc_hip_spot *spot)
+{
+	if (!spot) return;
+	for (pc_spot_member &m : spot->m) pc_spot_free_member(m);
+	delete spot;
+}
+
+int pc_hip_spot_add(pc_hip_spot *spot, int kind)
+{
+	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: spot must not be NULL");
+	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
+	pc_hip_group *g = spot->group;
+	if (g && kind == 0 && !g->keep_images)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: the last run kept no exit photons (run it with keep_images)");
+	if (g && kind > 0 && !g->leak_run)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: leak events need a leak_calc run of the group as the last run");
+	/* every member's source first: nothing is added unless the whole add can be */
+	std::vector<pc_spot_src> src(spot->m.size());
+	long long n = 0;
+	for (size_t k = 0; k < spot->m.size(); k++) {
+		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
+		PC_HIP_CHECK(hipSetDevice(spot->m[k].ctx->device));
+		int st = pc_spot_source(spot->m[k].ctx, kind, src[k]);
+		if (st) return st;
+		n += src[k].n;
+	}
+	if (spot->n_entries + n > (long long)0xffffffffll)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: a map takes at most 2^32 - 1 entries (its uint64 bins could wrap beyond)");
+	for (size_t k = 0; k < spot->m.size(); k++) {
+		PC_HIP_CHECK(hipSetDevice(spot->m[k].ctx->device));
+		int st = pc_spot_launch(spot, spot->m[k], src[k]);
+		if (st) return st;
+	}
+	spot->n_entries += n;
+	return PC_HIP_OK;
+}
+
+int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t *outside, int64_t *n_entries)
+{
+	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_read: spot must not be NULL");
+	const size_t nb = (size_t)spot->nx*spot->ny, n_bins = (size_t)spot->np*spot->ns*nb, n_out = (size_t)spot->np*spot->ns;
+	std::vector<unsigned long long> sum(spot->map_elems, 0ull), part(spot->map_elems);
+	for (pc_spot_member &m : spot->m) {
+		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
+		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_map, spot->map_elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
+		for (size_t k = 0; k < spot->map_elems; k++) sum[k] += part[k];       /* exact: the entry cap keeps every sum below 2^64 */
+	}
+	if (bins) {
+		if (!spot->wide)
+			memcpy(bins, sum.data(), n_bins*sizeof(uint64_t));
+		else      /* [plane][iy][ix][energy] -> [plane][energy][iy][ix] */
+			for (int p = 0; p < spot->np; p++)
+				for (size_t b = 0; b < nb; b++)
+					for (int s = 0; s < spot->ns; s++)
+						bins[((size_t)p*spot->ns + s)*nb + b] = sum[((size_t)p*nb + b)*spot->ns + s];
+	}
+	if (outside) memcpy(outside, sum.data() + n_bins, n_out*sizeof(uint64_t));
+	if (n_entries) *n_entries = spot->n_entries;
+	return PC_HIP_OK;
+}
+
+int pc_hip_spot_reset(pc_hip_spot *spot)
+{
+	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_reset: spot must not be NULL");
+	for (pc_spot_member &m : spot->m) {
+		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
+		PC_HIP_CHECK(hipMemsetAsync(m.d_map, 0, spot->map_elems*sizeof(unsigned long long), m.ctx->stream));
+	}
+	spot->n_entries = 0;
+	return PC_HIP_OK;
+}
+
+int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide)
+{
+	if (!spot || !dims) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_info: NULL argument");
+	dims[0] = spot->np; dims[1] = spot->ns; dims[2] = spot->ny; dims[3] = spot->nx;
+	if (wide) *wide = spot->wide;
+	return PC_HIP_OK;
+}
+
+int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_device_memory: ctx must not be NULL");
+	PC_HIP_CHECK(hipSetDevice(ctx->device));
+	size_t f = 0, t = 0;
+	PC_HIP_CHECK(hipMemGetInfo(&f, &t));
+	if (free_bytes) *free_bytes = f;
+	if (total_bytes) *total_bytes = t;
+	return PC_HIP_OK;
+}
+
+} /* extern "C" */
+
+#endif /* PC_SPOT_HOST_ONLY */
+#endif /* PC_SPOT_H */

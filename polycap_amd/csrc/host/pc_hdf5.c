@@ -144,8 +144,8 @@ static bool pc_h5_dataset(pc_hid file, int rank, const pc_hsize *dim, const char
 	bool ok = false;
 	/* HDF5 has no zero-sized simple extents in this usage; an empty run writes one zero instead of failing */
 	static const double zero = 0.;
-	pc_hsize d[2] = { dim[0], rank > 1 ? dim[1] : 1 };
-	if (d[0] * d[1] == 0) {
+	pc_hsize d[4] = { dim[0], rank > 1 ? dim[1] : 1, rank > 2 ? dim[2] : 1, rank > 3 ? dim[3] : 1 };
+	if (rank <= 2 && d[0] * d[1] == 0) {
 		d[0] = d[0] ? d[0] : 1;
 		d[1] = d[1] ? d[1] : 1;
 		if (d[0] * d[1] != 1) {
@@ -307,6 +307,36 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		lok = lok && pc_h5_dataset(file, 1, dim, name, ltmp, "a.u.", error);
 		free(ltmp);
 		if (!lok) goto close;
+	}
+
+	if (efficiencies->spot != NULL) {
+		/* extension: the spot maps of POLYCAP_SPOT, in efficiency units; [plane][energy][iy][ix] */
+		const struct pc_spot_result *sp = efficiencies->spot;
+		static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+		bool sok = pc_h5_group(file, "/Spot", error);
+		double *sel_e = malloc(sizeof(double) * (size_t)sp->n_sel);
+		sok = sok && sel_e != NULL;
+		for (int32_t k = 0; sok && k < sp->n_sel; k++)
+			sel_e[k] = efficiencies->energies[sp->sel[k]];
+		pc_hsize sd[4];
+		sd[0] = (pc_hsize)sp->n_planes;
+		sok = sok && pc_h5_dataset(file, 1, sd, "/Spot/Distances", sp->distances, "cm", error);
+		sd[0] = 4;
+		sok = sok && pc_h5_dataset(file, 1, sd, "/Spot/Window", sp->window, "cm", error);
+		sd[0] = (pc_hsize)sp->n_sel;
+		sok = sok && pc_h5_dataset(file, 1, sd, "/Spot/Energies", sel_e, "keV", error);
+		for (int k = 0; k < 3 && sok; k++) {
+			if (sp->maps[k] == NULL)
+				continue;
+			char name[64];
+			sd[0] = (pc_hsize)sp->n_planes; sd[1] = (pc_hsize)sp->n_sel; sd[2] = (pc_hsize)sp->ny; sd[3] = (pc_hsize)sp->nx;
+			snprintf(name, sizeof name, "/Spot/%s", names[k]);
+			sok = sok && pc_h5_dataset(file, 4, sd, name, sp->maps[k], "a.u.", error);
+			snprintf(name, sizeof name, "/Spot/%s_Outside", names[k]);
+			sok = sok && pc_h5_dataset(file, 2, sd, name, sp->outside[k], "a.u.", error);
+		}
+		free(sel_e);
+		if (!sok) goto close;
 	}
 
 	if (!pc_h5_group(file, "/Input", error)) goto close;

@@ -126,6 +126,16 @@ struct _polycap_images {
 	double *intleak_coord_weights;
 };
 
+/* extension: spot maps of a run made with POLYCAP_SPOT set, in efficiency units (pc_transmission_efficiencies_get_spot) */
+struct pc_spot_result {
+	int32_t n_planes, n_sel, ny, nx;
+	double *distances;         /* [n_planes] cm behind the exit face */
+	double window[4];          /* x0, x1, y0, y1, cm */
+	int32_t *sel;              /* [n_sel] energy indices */
+	double *maps[3];           /* exit photons, extleak, intleak: [plane][energy][iy][ix], NULL when the run has none */
+	double *outside[3];        /* [plane][energy] */
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -133,6 +143,7 @@ struct _polycap_transmission_efficiencies {
 	struct _polycap_images *images;
 	polycap_source *source;
 	int synthetic_constants;   /* extension: see pc_transmission_efficiencies_synthetic */
+	struct pc_spot_result *spot;
 };
 
 /* internal helpers */
@@ -181,5 +192,6 @@ pc_hip_ctx *pc_ctx_for_device(pc_ctx_cache *c, polycap_description *description,
 pc_hip_group *pc_group_for(pc_ctx_cache *c, polycap_description *description, size_t n_energies, const double *energies,
 	const polycap_source *source, int n_devices, const int *devices, const char *caller, polycap_error **error);
 void pc_set_hip_error(polycap_error **error, const char *caller, int status);
+void pc_spot_result_free(struct pc_spot_result *spot);
 
 #endif

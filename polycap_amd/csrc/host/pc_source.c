@@ -358,6 +358,203 @@ static double pc_now_ms(void)
 	return ts.tv_sec*1e3 + ts.tv_nsec*1e-6;
 }
 
+/* POLYCAP_SPOT, e.g. "dist=0.5,1,2;window=-0.02,0.02,-0.02,0.02;bins=256x256;energies=all" (cm; energy indices into the source's
+ * list, or all): spot maps of the run (include/polycap-hip.h, pc_hip_spot_*).  Parsed and validated before any device is used. */
+struct pc_spot_request {
+	int set;
+	double dist[65];
+	int n_dist;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_spot_spec spec;
+	double share;              /* POLYCAP_SPOT_SHARE: fraction of the device's memory the exit data of one run may take (0.5) */
+};
+
+static int pc_spot_parse_doubles(const char *v, double *out, int max, int *n)
+{
+	*n = 0;
+	while (*v != '\0') {
+		char *end = NULL;
+		errno = 0;
+		const double d = strtod(v, &end);
+		if (end == v || errno != 0 || *n >= max)
+			return -1;
+		out[(*n)++] = d;
+		v = end;
+		if (*v == ',')
+			v++;
+		else if (*v != '\0')
+			return -1;
+	}
+	return *n > 0 ? 0 : -1;
+}
+
+static int pc_spot_request_parse(struct pc_spot_request *r, size_t n_energies, polycap_error **error)
+{
+	memset(r, 0, sizeof(*r));
+	const char *env = getenv("POLYCAP_SPOT");
+	if (env == NULL || *env == '\0')
+		return 0;
+	r->set = 1;
+	char *buf = strdup(env), *save = NULL;
+	const char *bad = NULL;
+	int have_dist = 0, have_window = 0, have_bins = 0;
+	r->spec.n_energies = 0;
+	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save)) {
+		char *eq = strchr(item, '=');
+		if (eq == NULL) { bad = "every item must be key=value"; break; }
+		*eq = '\0';
+		const char *key = item, *v = eq + 1;
+		if (strcmp(key, "dist") == 0) {
+			if (pc_spot_parse_doubles(v, r->dist, 65, &r->n_dist) != 0) bad = "dist must be a list of at most 64 distances in cm";
+			have_dist = 1;
+		} else if (strcmp(key, "window") == 0) {
+			double w[4];
+			int n = 0;
+			if (pc_spot_parse_doubles(v, w, 4, &n) != 0 || n != 4) { bad = "window must be x0,x1,y0,y1 in cm"; break; }
+			r->spec.x0 = w[0]; r->spec.x1 = w[1]; r->spec.y0 = w[2]; r->spec.y1 = w[3];
+			have_window = 1;
+		} else if (strcmp(key, "bins") == 0) {
+			long nx = 0, ny = 0;
+			char *end = NULL;
+			nx = strtol(v, &end, 10);
+			if (end == v || (*end != 'x' && *end != 'X')) { bad = "bins must be NXxNY"; break; }
+			const char *v2 = end + 1;
+			ny = strtol(v2, &end, 10);
+			if (end == v2 || *end != '\0' || nx < 0 || ny < 0 || nx > 1 << 27 || ny > 1 << 27) { bad = "bins must be NXxNY"; break; }
+			r->spec.nx = (int32_t)nx; r->spec.ny = (int32_t)ny;
+			have_bins = 1;
+		} else if (strcmp(key, "energies") == 0) {
+			free(r->energies);
+			r->energies = NULL;
+			r->n_energies = 0;
+			if (strcmp(v, "all") == 0)
+				continue;
+			r->energies = malloc(sizeof(int32_t) * (n_energies + 1));
+			while (r->energies != NULL && *v != '\0') {
+				char *end = NULL;
+				const long e = strtol(v, &end, 10);
+				if (end == v || (size_t)r->n_energies > n_energies) { bad = "energies must be all or a list of energy indices"; break; }
+				r->energies[r->n_energies++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
+				v = end;
+				if (*v == ',') v++;
+				else if (*v != '\0') { bad = "energies must be all or a list of energy indices"; break; }
+			}
+			if (bad == NULL && r->n_energies == 0) bad = "energies must be all or a list of energy indices";
+		} else {
+			bad = "unknown key (dist, window, bins, energies)";
+		}
+	}
+	free(buf);
+	if (bad == NULL && !(have_dist && have_window && have_bins))
+		bad = "dist, window and bins are required";
+	r->share = 0.5;
+	const char *share = getenv("POLYCAP_SPOT_SHARE");
+	if (bad == NULL && share != NULL && *share != '\0') {
+		char *end = NULL;
+		r->share = strtod(share, &end);
+		if (*end != '\0' || !(r->share > 0. && r->share <= 1.))
+			bad = "POLYCAP_SPOT_SHARE must be a fraction in (0, 1]";
+	}
+	if (bad == NULL) {
+		r->spec.n_planes = r->n_dist;
+		r->spec.distances = r->dist;
+		r->spec.n_energies = r->n_energies;
+		r->spec.energies = r->energies;
+		if (pc_hip_spot_validate(&r->spec, n_energies) != PC_HIP_OK)
+			bad = pc_hip_last_error();
+	}
+	if (bad != NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SPOT=%s: %s", env, bad);
+		free(r->energies);
+		r->energies = NULL;
+		return -1;
+	}
+	return 0;
+}
+
+/* POLYCAP_IMAGES=0 with spot maps on one context: the exit data of the run stay on the device, and a run whose exit data would take
+ * more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by (seed, slot): the
+ * same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is added to the map. */
+static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
+	size_t ne, double *sum_weights, int64_t counters[6])
+{
+	uint64_t *fixed = calloc(2*ne, sizeof(uint64_t)), *part = malloc(2*ne*sizeof(uint64_t));
+	int st = (fixed != NULL && part != NULL) ? PC_HIP_OK : PC_HIP_ERR_MEMORY;
+	for (int k = 0; k < 6; k++)
+		counters[k] = 0;
+	for (int64_t lo = 0; lo < n_photons && st == PC_HIP_OK; lo += chunk) {
+		const int64_t n = (n_photons - lo < chunk) ? n_photons - lo : chunk;
+		int64_t c[6];
+		st = pc_hip_transmission_run(ctx, seed, lo, n, max_attempts, 1);
+		if (st == PC_HIP_OK)
+			st = pc_hip_spot_add(spot, 0);
+		if (st == PC_HIP_OK)
+			st = pc_hip_transmission_totals(ctx, NULL, c, part);
+		if (st != PC_HIP_OK)
+			break;
+		for (int k = 0; k < 6; k++)
+			counters[k] += c[k];
+		for (size_t e = 0; e < ne; e++) {      /* 128-bit (lo, hi) sums */
+			const uint64_t l = fixed[2*e] + part[2*e];
+			fixed[2*e + 1] += part[2*e + 1] + (l < fixed[2*e] ? 1 : 0);
+			fixed[2*e] = l;
+		}
+	}
+	for (size_t e = 0; st == PC_HIP_OK && e < ne; e++)
+		sum_weights[e] = pc_hip_fixed_to_double(fixed[2*e], fixed[2*e + 1]);
+	free(fixed);
+	free(part);
+	return st;
+}
+
+/* the maps of `spot` in efficiency units into the result */
+static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *spot, const struct pc_spot_request *r, int kind)
+{
+	int32_t dims[4];
+	int st = pc_hip_spot_info(spot, dims, NULL);
+	if (st != PC_HIP_OK)
+		return st;
+	const size_t n_out = (size_t)dims[0]*dims[1], nb = (size_t)dims[2]*dims[3];
+	struct pc_spot_result *sp = eff->spot;
+	if (sp == NULL) {
+		sp = eff->spot = calloc(1, sizeof(*sp));
+		if (sp == NULL)
+			return PC_HIP_ERR_MEMORY;
+		sp->n_planes = dims[0]; sp->n_sel = dims[1]; sp->ny = dims[2]; sp->nx = dims[3];
+		sp->distances = malloc(sizeof(double)*dims[0]);
+		sp->sel = malloc(sizeof(int32_t)*dims[1]);
+		if (sp->distances == NULL || sp->sel == NULL)
+			return PC_HIP_ERR_MEMORY;
+		memcpy(sp->distances, r->dist, sizeof(double)*dims[0]);
+		for (int32_t k = 0; k < dims[1]; k++)
+			sp->sel[k] = r->n_energies ? r->energies[k] : k;
+		sp->window[0] = r->spec.x0; sp->window[1] = r->spec.x1; sp->window[2] = r->spec.y0; sp->window[3] = r->spec.y1;
+	}
+	uint64_t *bins = malloc(sizeof(uint64_t)*n_out*nb), *out = malloc(sizeof(uint64_t)*n_out);
+	sp->maps[kind] = malloc(sizeof(double)*n_out*nb);
+	sp->outside[kind] = malloc(sizeof(double)*n_out);
+	if (bins == NULL || out == NULL || sp->maps[kind] == NULL || sp->outside[kind] == NULL) {
+		free(bins); free(out);
+		return PC_HIP_ERR_MEMORY;
+	}
+	st = pc_hip_spot_read(spot, bins, out, NULL);
+	for (size_t m = 0; st == PC_HIP_OK && m < n_out; m++) {
+		/* map = efficiency[e] * S_bin / (S_inside + S_outside): a map and its outside part sum to the efficiency */
+		uint64_t total = out[m];
+		for (size_t b = 0; b < nb; b++)
+			total += bins[m*nb + b];
+		const double eff_e = eff->efficiencies[sp->sel[m % (size_t)dims[1]]];
+		const double tot = (double)total;
+		for (size_t b = 0; b < nb; b++)
+			sp->maps[kind][m*nb + b] = total ? eff_e * (double)bins[m*nb + b] / tot : 0.;
+		sp->outside[kind][m] = total ? eff_e * (double)out[m] / tot : 0.;
+	}
+	free(bins);
+	free(out);
+	return st;
+}
+
 polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(polycap_source *source, int max_threads, int n_photons,
 	bool leak_calc, polycap_progress_monitor *progress_monitor, polycap_error **error)
 {
@@ -396,18 +593,24 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 
 	const size_t ne = source->n_energies;
 	const int timing = getenv("POLYCAP_TIMING") != NULL;
+	struct pc_spot_request spot_req;
+	if (pc_spot_request_parse(&spot_req, ne, error) != 0)
+		return NULL;
 	/* Extensions of the reference call, all through the environment so that the signature stays the reference's:
 	 *   POLYCAP_HIP_DEVICES=all | i,j,...  the photon loop is sharded over these devices from this one process (the
 	 *       reference's OpenMP team, :697-745, becomes a team of GPUs); totals are summed by one RCCL all-reduce (:973-980)
 	 *   POLYCAP_IMAGES=0                   histogram-only result: efficiencies and counts, no per-photon planes (at 1e8
 	 *       photons x 291 energies the weight plane alone is 233 GB); the start/exit getters then report no events */
 	int devices[64], n_devices = 0;
-	if (pc_env_devices(devices, &n_devices, error) != 0)
+	if (pc_env_devices(devices, &n_devices, error) != 0) {
+		free(spot_req.energies);
 		return NULL;
+	}
 	const char *img_env = getenv("POLYCAP_IMAGES");
 	const int keep_images = !(img_env != NULL && strcmp(img_env, "0") == 0);
 	if (leak_calc && !keep_images) {
 		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_IMAGES=0 cannot be combined with leak_calc (leak events are per-photon data)");
+		free(spot_req.energies);
 		return NULL;
 	}
 	double t_stage[8];
@@ -418,6 +621,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		if (eff != NULL)
 			polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for efficiencies -> %s", strerror(errno));
 		free(sum_weights);
+		free(spot_req.energies);
 		polycap_transmission_efficiencies_free(eff);
 		return NULL;
 	}
@@ -431,6 +635,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		                        "polycap_source_get_transmission_efficiencies", error);
 	if (ctx == NULL && group == NULL) {
 		free(sum_weights);
+		free(spot_req.energies);
 		polycap_transmission_efficiencies_free(eff);
 		return NULL;
 	}
@@ -443,7 +648,22 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	uint32_t max_attempts = (uint32_t)pc_env_u64("POLYCAP_MAX_ATTEMPTS", 1u << 20, NULL);
 
 	int64_t counters[6] = {0, 0, 0, 0, 0, 0};
-	int status;
+	int status = PC_HIP_OK;
+	/* POLYCAP_SPOT: the run keeps its exit data on the device for the maps even with POLYCAP_IMAGES=0 (then nothing is copied back) */
+	const int device_images = keep_images || spot_req.set;
+	pc_hip_spot *spot[3] = {NULL, NULL, NULL};      /* exit photons, extleak, intleak */
+	int64_t chunk = 0;
+	if (spot_req.set) {
+		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK; kind++)
+			status = (group != NULL) ? pc_hip_group_spot_create(group, &spot_req.spec, &spot[kind]) : pc_hip_spot_create(ctx, &spot_req.spec, &spot[kind]);
+		if (status == PC_HIP_OK && group == NULL && !keep_images && !leak_calc) {
+			uint64_t total_b = 0;
+			status = pc_hip_device_memory(ctx, NULL, &total_b);
+			chunk = (int64_t)(spot_req.share * (double)total_b / ((17. + (double)ne) * 8.));
+			if (chunk < 1)
+				chunk = 1;
+		}
+	}
 	/* big plain runs are traced in four parts so that the images of a finished part cross PCIe while the next part runs */
 	const int parts = (!leak_calc && keep_images && n_photons >= 2000000) ? (int)pc_env_u64("POLYCAP_RUN_PARTS", 4, NULL) : 1;
 	/* Plain runs store their exit photons in the order of completion (option "compact_images": coalesced plane stores, blocks
@@ -451,7 +671,10 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	 * the arrays.  POLYCAP_COMPACT=0 keeps every photon at the position of its slot (reproducible order for a given POLYCAP_SEED). */
 	const char *compact_env = getenv("POLYCAP_COMPACT");
 	const int compact = !(compact_env != NULL && strcmp(compact_env, "0") == 0) && !leak_calc;
-	if (group != NULL) {
+	const int chunked = status == PC_HIP_OK && chunk > 0 && chunk < (int64_t)n_photons;
+	if (status != PC_HIP_OK) {
+		/* the map could not be made: reported below */
+	} else if (group != NULL) {
 		status = pc_hip_group_set_option(group, "run_parts", parts);
 		if (status == PC_HIP_OK)
 			status = pc_hip_group_set_option(group, "compact_images", compact);
@@ -459,7 +682,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			status = pc_hip_group_set_option(group, "plane_images", leak_calc ? 0 : 1);
 		if (status == PC_HIP_OK)
 			status = leak_calc ? pc_hip_group_run_leak(group, seed, n_photons, max_attempts, 1)
-			                   : pc_hip_group_run(group, seed, n_photons, max_attempts, keep_images);
+			                   : pc_hip_group_run(group, seed, n_photons, max_attempts, device_images);
 	} else {
 		status = pc_hip_set_option(ctx, "run_parts", parts);
 		if (status == PC_HIP_OK)
@@ -468,9 +691,11 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			status = pc_hip_set_option(ctx, "block_shift", (int64_t)pc_env_u64("POLYCAP_BLOCK_SHIFT", 18, NULL));
 		if (status == PC_HIP_OK)
 			status = pc_hip_set_option(ctx, "plane_images", leak_calc ? 0 : 1);   /* the result object wants planes: let the kernel write them */
-		if (status == PC_HIP_OK)
+		if (status == PC_HIP_OK && chunked)
+			status = pc_spot_chunked(ctx, spot[0], seed, n_photons, chunk, max_attempts, ne, sum_weights, counters);
+		else if (status == PC_HIP_OK)
 			status = leak_calc ? pc_hip_transmission_run_leak(ctx, seed, 0, n_photons, max_attempts, 1)
-			                   : pc_hip_transmission_run(ctx, seed, 0, n_photons, max_attempts, keep_images);
+			                   : pc_hip_transmission_run(ctx, seed, 0, n_photons, max_attempts, device_images);
 	}
 	t_stage[2] = pc_now_ms();
 	t_stage[3] = t_stage[2];
@@ -493,7 +718,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	}
 	t_stage[4] = pc_now_ms();
 	int reduced_by = 0;
-	if (status == PC_HIP_OK) {
+	if (status == PC_HIP_OK && !chunked) {
 		if (group != NULL) {
 			const char *r = getenv("POLYCAP_RCCL");      /* 0: host sum, 1: RCCL or fail; default: RCCL when possible */
 			status = pc_hip_group_totals(group, (r != NULL && *r != '\0') ? atoi(r) : -1, sum_weights, counters, NULL, &reduced_by, NULL);
@@ -510,8 +735,14 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			group != NULL ? (reduced_by ? " (devices summed by RCCL all-reduce)" : " (devices summed on the host)") : "");
 	if (status == PC_HIP_OK && leak_calc)
 		status = pc_transeff_fetch_leaks(eff, ctx, group);      /* reference :925-1032 */
+	for (int kind = chunked ? 1 : 0; kind <= 2 && status == PC_HIP_OK; kind++)
+		if (spot[kind] != NULL)
+			status = pc_hip_spot_add(spot[kind], kind);
 	if (status != PC_HIP_OK) {
 		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
+		for (int kind = 0; kind <= 2; kind++)
+			pc_hip_spot_destroy(spot[kind]);
+		free(spot_req.energies);
 		free(sum_weights);
 		polycap_transmission_efficiencies_free(eff);
 		return NULL;
@@ -527,6 +758,20 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 
 	pc_transeff_finish(eff, sum_weights, counters);
 	eff->synthetic_constants = source->cache.synthetic;
+	if (spot_req.set) {
+		for (int kind = 0; kind <= 2; kind++) {
+			if (spot[kind] != NULL && status == PC_HIP_OK)
+				status = pc_spot_store(eff, spot[kind], &spot_req, kind);
+			pc_hip_spot_destroy(spot[kind]);
+		}
+		free(spot_req.energies);
+		if (status != PC_HIP_OK) {
+			pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
+			free(sum_weights);
+			polycap_transmission_efficiencies_free(eff);
+			return NULL;
+		}
+	}
 	if (!keep_images)
 		eff->images->i_exit = 0;     /* no per-photon planes were kept: the exit/start getters report no events */
 	free(sum_weights);

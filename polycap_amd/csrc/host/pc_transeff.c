@@ -203,7 +203,73 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	free(efficiencies->energies);
 	free(efficiencies->efficiencies);
 	pc_images_free(efficiencies->images);
+	pc_spot_result_free(efficiencies->spot);
 	free(efficiencies);
+}
+
+void pc_spot_result_free(struct pc_spot_result *spot)
+{
+	if (spot == NULL)
+		return;
+	free(spot->distances);
+	free(spot->sel);
+	for (int k = 0; k < 3; k++) {
+		free(spot->maps[k]);
+		free(spot->outside[k]);
+	}
+	free(spot);
+}
+
+static void *pc_dup(const void *p, size_t bytes)
+{
+	void *q = malloc(bytes ? bytes : 1);
+	if (q != NULL && bytes)
+		memcpy(q, p, bytes);
+	return q;
+}
+
+int pc_transmission_efficiencies_get_spot(void *efficiencies_, int kind, int32_t dims[4], double **distances, double window[4],
+	double **energies, double **maps, double **outside, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || dims == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_spot: efficiencies and dims cannot be NULL");
+		return 0;
+	}
+	const struct pc_spot_result *sp = efficiencies->spot;
+	if (sp == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_spot: the run was made without POLYCAP_SPOT");
+		return 0;
+	}
+	if (kind < 0 || kind > 2 || sp->maps[kind] == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_spot: kind must be 0 (exit photons), or 1 (extleak) / 2 (intleak) for a leak_calc run");
+		return 0;
+	}
+	const size_t n_out = (size_t)sp->n_planes*sp->n_sel, n_bins = n_out*sp->ny*sp->nx;
+	dims[0] = sp->n_planes; dims[1] = sp->n_sel; dims[2] = sp->ny; dims[3] = sp->nx;
+	if (window != NULL)
+		memcpy(window, sp->window, sizeof(sp->window));
+	double *d = NULL, *e = NULL, *m = NULL, *o = NULL;
+	int ok = 1;
+	if (distances != NULL) ok = ok && (d = pc_dup(sp->distances, sizeof(double)*sp->n_planes)) != NULL;
+	if (energies != NULL && ok) {
+		ok = (e = malloc(sizeof(double)*(sp->n_sel ? sp->n_sel : 1))) != NULL;
+		for (int32_t k = 0; ok && k < sp->n_sel; k++)
+			e[k] = efficiencies->energies[sp->sel[k]];
+	}
+	if (maps != NULL && ok) ok = (m = pc_dup(sp->maps[kind], sizeof(double)*n_bins)) != NULL;
+	if (outside != NULL && ok) ok = (o = pc_dup(sp->outside[kind], sizeof(double)*n_out)) != NULL;
+	if (!ok) {
+		free(d); free(e); free(m); free(o);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_spot: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (distances != NULL) *distances = d;
+	if (energies != NULL) *energies = e;
+	if (maps != NULL) *maps = m;
+	if (outside != NULL) *outside = o;
+	return 1;
 }
 
 /* result object with every plane allocated for np exit photons (reference: src/polycap-source.c:556-681) */

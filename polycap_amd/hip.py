@@ -134,6 +134,14 @@ class TraceContext:
             out.append(a)
         return out[0], out[1]
 
+    def device_memory(self):
+        """(free, total) bytes of the context's device"""
+        f, t = C.c_uint64(0), C.c_uint64(0)
+        st = self._L.pc_hip_device_memory(self._h, C.byref(f), C.byref(t))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_device_memory", st)
+        return int(f.value), int(t.value)
+
     def wait(self):
         ms = C.c_float(0)
         st = self._L.pc_hip_transmission_wait(self._h, C.byref(ms))
@@ -319,6 +327,83 @@ class TraceGroup:
         r.update(sum_weights=sw, counters=cnt, sumw_fixed=fx.reshape(ne, 2), reduced_by_rccl=bool(by.value), kernel_ms=float(ms.value),
                  i_exit=int(cnt[0]), i_start=int(cnt[0] + cnt[1] + cnt[2]), efficiencies=efficiencies(sw, cnt))
         return r
+
+
+SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}
+
+
+class SpotMap:
+    """Spot maps of a TraceContext or a TraceGroup (pc_hip_spot_*): weighted 2-D histograms of where the entries of the last run
+    cross planes `distances` cm behind the optic's exit face, inside the window (x0, x1, y0, y1) cm cut into bins = (nx, ny),
+    one map per selected energy (energies: indices, None = all).  Exact uint64 sums of round_half_even(w * 2^32); the contract is
+    written down in include/polycap-hip.h.  regime: 0 automatic, 1 LDS tiles, 2 energies across lanes."""
+
+    def __init__(self, owner, distances, window, bins, energies=None, regime=0):
+        self._L = _cabi.lib()
+        self.owner = owner                      # keeps the context alive as long as the map
+        self.distances = np.ascontiguousarray(distances, dtype=np.float64).ravel()
+        self.window = tuple(float(v) for v in window)
+        self.nx, self.ny = (int(bins[0]), int(bins[1]))
+        self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
+        spec = _cabi.SpotSpecS(self.distances.shape[0], dptr(self.distances), *self.window, self.nx, self.ny,
+                               0 if self.energies is None else self.energies.shape[0],
+                               None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
+        h = C.c_void_p()
+        if isinstance(owner, TraceGroup):
+            st = self._L.pc_hip_group_spot_create(owner._h, C.byref(spec), C.byref(h))
+        else:
+            st = self._L.pc_hip_spot_create(owner._h, C.byref(spec), C.byref(h))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_spot_create", st)
+        self._h = h
+        dims = (C.c_int32 * 4)()
+        wide = C.c_int(0)
+        self._L.pc_hip_spot_info(self._h, dims, C.byref(wide))
+        self.shape = tuple(int(d) for d in dims)       # (planes, selected energies, ny, nx)
+        self.wide = bool(wide.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pc_hip_spot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, kind="exit"):
+        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
+        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        st = self._L.pc_hip_spot_add(self._h, k)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_spot_add", st)
+
+    def reset(self):
+        st = self._L.pc_hip_spot_reset(self._h)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_spot_reset", st)
+
+    def read(self):
+        """bins [planes, energies, ny, nx] and outside [planes, energies] as uint64, the entry count, and the same as weights
+        (maps = bins * 2^-32, outside_map)."""
+        np_, ns = self.shape[0], self.shape[1]
+        bins = np.zeros(self.shape, dtype=np.uint64)
+        out = np.zeros((np_, ns), dtype=np.uint64)
+        n = C.c_int64(0)
+        st = self._L.pc_hip_spot_read(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      C.byref(n))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_spot_read", st)
+        return dict(bins=bins, outside=out, n_entries=int(n.value), maps=bins.astype(np.float64) * 2.0 ** -32,
+                    outside_map=out.astype(np.float64) * 2.0 ** -32)
 
 
 def efficiencies(sum_weights, counters):

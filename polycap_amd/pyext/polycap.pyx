@@ -5,7 +5,7 @@ to the same Python exceptions.  Every call goes straight to the C API of include
 Composition strings / element symbols are resolved by polycap_amd.capi's small parser (the reference calls xraylib's
 CompoundParser for this; it is not on the trace path)."""
 from collections import namedtuple
-from libc.stdint cimport int64_t
+from libc.stdint cimport int32_t, int64_t
 from libc.stddef cimport size_t
 from libcpp cimport bool as cbool
 import numpy as np
@@ -96,6 +96,9 @@ cdef extern from "polycap.h" nogil:
     cbool polycap_transmission_efficiencies_get_exit_data(polycap_transmission_efficiencies *efficiencies, int64_t *n_exit,
         polycap_vector3 **exit_coords, polycap_vector3 **exit_direction, polycap_vector3 **exit_elecv, int64_t **n_refl, double **d_travel,
         size_t *n_energies, double ***exit_weights, polycap_error **error)
+
+    int pc_transmission_efficiencies_get_spot(void *efficiencies, int kind, int32_t *dims, double **distances, double *window,
+        double **energies, double **maps, double **outside, void *error)
 
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
@@ -592,6 +595,24 @@ cdef class TransmissionEfficiencies:
         [n_exit, 17] image array + [n_exit, nE] weights of polycap_amd.TraceContext.images(), produced elsewhere
         (several GPUs / ranks), so that the getters and write_hdf5 serve a sharded run too."""
         return source._efficiencies_from_totals(sum_weights, counters, images, exit_weights)
+
+    def spot_map(self, kind="exit"):
+        """Extension of this build: the spot maps of a run made with POLYCAP_SPOT set (pc_transmission_efficiencies_get_spot),
+        a dict of maps [plane, energy, iy, ix] and outside [plane, energy] in efficiency units, distances (cm), window
+        (x0, x1, y0, y1; cm) and energies (keV).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        cdef polycap_error *error = NULL
+        cdef int32_t dims[4]
+        cdef double window[4]
+        cdef double *d = NULL
+        cdef double *e = NULL
+        cdef double *m = NULL
+        cdef double *o = NULL
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_spot(<void *>self._eff, k, dims, &d, window, &e, &m, &o, <void *>&error)
+        _raise_if(error)
+        npl, ns, ny, nx = dims[0], dims[1], dims[2], dims[3]
+        return dict(maps=_take_doubles(m, npl * ns * ny * nx).reshape(npl, ns, ny, nx), outside=_take_doubles(o, npl * ns).reshape(npl, ns),
+                    distances=_take_doubles(d, npl), energies=_take_doubles(e, ns), window=(window[0], window[1], window[2], window[3]))
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
