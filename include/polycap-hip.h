@@ -150,6 +150,22 @@ POLYCAP_EXTERN int pc_hip_transmission_wait(pc_hip_ctx *ctx, float *kernel_ms);
  * sum_irefl, failed_slots, launches}; sumw_fixed (optional) [2*n_energies] = exact 128-bit fixed-point sums
  * (lo, hi) in units of 2^-62, which add exactly across devices. */
 POLYCAP_EXTERN int pc_hip_transmission_totals(pc_hip_ctx *ctx, double *sum_weights, int64_t counters[6], uint64_t *sumw_fixed);
+/* ---- standard errors.  Every efficiency is a Monte Carlo mean: eff = sum(w) / N over the N started photons (an exit photon adds
+ * its weight, one that did not enter or was not transmitted adds 0; the open_area factor of pc_hip_efficiencies cancels).  With
+ * option "weight_squares" = 1 (pc_hip_set_option / pc_hip_group_set_option; default 0) source runs -- leak_calc runs included,
+ * explicit-photon launches not -- also keep a second exact sum per energy, of the squared weights.  The contract, for each
+ * exit photon and energy, with w the fp64 weight the sums already use (IEEE, no contraction):
+ *   A += (uint64)(w * 2^62)            truncated: sumw_fixed, as without the option
+ *   B += (uint64)((w * w) * 2^62)      w * w one fp64 product, then the scaling, truncated
+ * B is a 128-bit (lo, hi) sum per energy laid out like sumw_fixed.  Both are integer sums, so B does not depend on the launch
+ * shape, the kernel, "run_parts", the store, how the slots are split into runs, or the device count.
+ * With N = counters[0] + counters[1] + counters[2], m = A / (N 2^62) and q = B / (N 2^62), all in long double:
+ *   stderr = sqrt(max(0, q - m*m) / (N - 1)),  NaN when N < 2.
+ * pc_hip_transmission_moments: B of the last run, sumw2_fixed [2*n_energies]; PC_HIP_ERR_INVALID when the last run was made
+ * without the option.  pc_hip_efficiency_stderr: the formula above (pure host function, out [n_energies]). */
+POLYCAP_EXTERN int pc_hip_transmission_moments(pc_hip_ctx *ctx, uint64_t *sumw2_fixed);
+POLYCAP_EXTERN void pc_hip_efficiency_stderr(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed,
+	const int64_t counters[6], double *out);
 /* Copies image planes of slots [first, first+count) (relative to slot0 of the last run) to the host.  May be called
  * before pc_hip_transmission_wait: with "run_parts" > 1 it waits for the run part by part and copies the finished parts
  * while the later ones are traced (pinned staging, host threads build the planes).  NULL planes are skipped. */
@@ -224,6 +240,9 @@ POLYCAP_EXTERN int pc_hip_group_images(pc_hip_group *group, const pc_hip_images 
  * *kernel_ms (optional) = the longest member kernel.  reduce: -1 automatic, 0 host, 1 RCCL (fails when it cannot) */
 POLYCAP_EXTERN int pc_hip_group_totals(pc_hip_group *group, int reduce, double *sum_weights, int64_t counters[6], uint64_t *sumw_fixed,
 	int *reduced_by, float *kernel_ms);
+/* B of the group's last run (option "weight_squares"), summed over the members like the weights -- in the same all-reduce, the
+ * packed vector growing to 6 + 8 n_energies int64 -- by the pc_hip_group_totals call for that run, which must come first */
+POLYCAP_EXTERN int pc_hip_group_moments(pc_hip_group *group, uint64_t *sumw2_fixed);
 
 /* ---- spot maps: weighted 2-D histograms of where the photons of the last run cross planes perpendicular to the optic axis,
  * downstream of its exit face, one map per selected energy, accumulated on the device in exact integers from what the run left
@@ -314,6 +333,15 @@ POLYCAP_EXTERN void *pc_transmission_efficiencies_from_totals(void *source, int6
  * its outside part sums to the efficiency.  Returns 1, or 0 with *error set. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_spot(void *efficiencies, int kind, int32_t dims[4], double **distances, double window[4],
 	double **energies, double **maps, double **outside, void *error);
+
+/* Standard errors of a result of polycap_source_get_transmission_efficiencies made with POLYCAP_STDERR=1 (every path of the call:
+ * one device, POLYCAP_HIP_DEVICES groups, leak_calc, POLYCAP_IMAGES=0 with the chunked POLYCAP_SPOT runs): *stderr [n_energies],
+ * pc_hip_efficiency_stderr of the run's exact moments, to be freed with polycap_free.  _get_moments: N (started photons) and
+ * copies of the exact (lo, hi) sums A and B [2*n_energies] (either may be NULL), so that the results of several seeds can be pooled
+ * exactly.  A result made without the variable is an error.  Return 1, or 0 with *error (a polycap_error**) set. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_stderr(void *efficiencies, size_t *n_energies, double **stderr_, void *error);
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_moments(void *efficiencies, int64_t *n_started, uint64_t **sumw_fixed,
+	uint64_t **sumw2_fixed, void *error);
 
 #ifdef __cplusplus
 }

@@ -173,12 +173,20 @@ def lib():
     L.pc_hip_group_set_option.restype = C.c_int
     L.pc_hip_group_run.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_uint32, C.c_int]
     L.pc_hip_group_run.restype = C.c_int
+    L.pc_hip_group_run_leak.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_uint32, C.c_int]
+    L.pc_hip_group_run_leak.restype = C.c_int
     L.pc_hip_group_last_kernel.argtypes = [C.c_void_p, C.c_int]
     L.pc_hip_group_last_kernel.restype = C.c_int
     L.pc_hip_group_images.argtypes = [C.c_void_p, P(ImagesS)]
     L.pc_hip_group_images.restype = C.c_int
     L.pc_hip_group_totals.argtypes = [C.c_void_p, C.c_int, c_double_p, c_int64_p, P(C.c_uint64), P(C.c_int), P(C.c_float)]
     L.pc_hip_group_totals.restype = C.c_int
+    L.pc_hip_transmission_moments.argtypes = [C.c_void_p, P(C.c_uint64)]
+    L.pc_hip_transmission_moments.restype = C.c_int
+    L.pc_hip_group_moments.argtypes = [C.c_void_p, P(C.c_uint64)]
+    L.pc_hip_group_moments.restype = C.c_int
+    L.pc_hip_efficiency_stderr.argtypes = [C.c_size_t, P(C.c_uint64), P(C.c_uint64), c_int64_p, c_double_p]
+    L.pc_hip_efficiency_stderr.restype = None
     L.pc_hip_efficiencies.argtypes = [C.c_size_t, c_double_p, c_int64_p, c_double_p]
     L.pc_hip_efficiencies.restype = None
     L.pc_hip_fixed_to_double.argtypes = [C.c_uint64, C.c_uint64]

@@ -129,6 +129,8 @@ def _lib():
                                                              [P(P(C.c_int64)), P(_dp), P(C.c_size_t), P(P(_dp)), epp]),
         "polycap_transmission_efficiencies_write_hdf5": (C.c_bool, [vp, C.c_char_p, epp]),
         "pc_transmission_efficiencies_get_spot": (C.c_int, [vp, C.c_int, P(C.c_int32), P(_dp), _dp, P(_dp), P(_dp), P(_dp), epp]),
+        "pc_transmission_efficiencies_get_stderr": (C.c_int, [vp, P(C.c_size_t), P(_dp), epp]),
+        "pc_transmission_efficiencies_get_moments": (C.c_int, [vp, P(C.c_int64), P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -420,6 +422,29 @@ class TransmissionEfficiencies(_LeakData):
         npl, ns, ny, nx = (int(v) for v in dims)
         return dict(maps=_take(m, npl * ns * ny * nx).reshape(npl, ns, ny, nx), outside=_take(o, npl * ns).reshape(npl, ns),
                     distances=_take(d, npl), energies=_take(e, ns), window=tuple(win))
+
+    def efficiency_stderr(self):
+        """Standard error of every efficiency of a run made with POLYCAP_STDERR=1 (extension,
+        pc_transmission_efficiencies_get_stderr), as an array over the energies."""
+        n = C.c_size_t(0)
+        p = _dp()
+        err = _ErrP()
+        _lib().pc_transmission_efficiencies_get_stderr(self._h, C.byref(n), C.byref(p), C.byref(err))
+        _check(err)
+        return _take(p, n.value)
+
+    def moments(self):
+        """The exact moments of a run made with POLYCAP_STDERR=1 (extension, pc_transmission_efficiencies_get_moments): dict of
+        n_started and the (lo, hi) sums of the weights (sumw_fixed) and of their squares (sumw2_fixed), uint64 [n_energies, 2] in
+        units of 2^-62.  Runs of several seeds pool exactly by adding them."""
+        ns = C.c_int64(0)
+        a, b = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        err = _ErrP()
+        _lib().pc_transmission_efficiencies_get_moments(self._h, C.byref(ns), C.byref(a), C.byref(b), C.byref(err))
+        _check(err)
+        ne = len(self.data[0])
+        return dict(n_started=int(ns.value), sumw_fixed=_take(a, 2 * ne, np.uint64).reshape(ne, 2),
+                    sumw2_fixed=_take(b, 2 * ne, np.uint64).reshape(ne, 2))
 
     def _start(self):
         L = _lib()

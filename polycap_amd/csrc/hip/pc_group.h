@@ -3,7 +3,8 @@
  * The reference parallelises the photon loop with an OpenMP team and adds the threads' partial sums in an omp critical
  * (src/polycap-source.c:697-745, 973-980).  Here the team is a set of device contexts.  Slots are independent and keyed by
  * their global index, so the members get contiguous ranges and nothing is exchanged while they trace; at the end their
- * totals -- 6 counters + the exact fixed-point weight sums as four 32-bit limbs per energy -- are summed by one
+ * totals -- 6 counters + the exact fixed-point weight sums as four 32-bit limbs per energy (and with option "weight_squares" the
+ * squared weights' sums the same way) -- are summed by one
  * ncclAllReduce (RCCL over xGMI; librccl is bound with dlopen like libhdf5, so the library loads without it) or, when RCCL
  * is absent or a device appears twice in the group, limb by limb on the host.  Integer sums: identical bits both ways. */
 #ifndef PC_GROUP_H
@@ -55,19 +56,25 @@ struct pc_hip_group {
 	std::vector<long long> first, count;       /* slot range of every member in the last run */
 	bool distinct = true;                       /* no device twice: the members can form one RCCL communicator */
 	std::vector<pc_nccl_comm> comms;
-	std::vector<long long *> d_vec;             /* per member: packed totals on its device, 6 + 4 n_energies int64 */
-	size_t vec_len = 0;
+	std::vector<long long *> d_vec;             /* per member: packed totals on its device, 6 + 4 n_energies int64 (6 + 8 n_energies with
+	                                             * option "weight_squares") */
+	size_t d_vec_len = 0;                       /* int64 that every d_vec[k] holds */
+	int weight_squares = 0;                     /* option "weight_squares" of the members */
+	int run_squares = 0;                        /* the last run summed the squared weights */
+	std::vector<uint64_t> sumw2;                /* their group sums, [2*n_energies], made by the last pc_hip_group_totals */
+	int have_sumw2 = 0;
 	long long run_slots = 0;
 	int keep_images = 0;
 	int leak_run = 0;                           /* the last run was a leak run (pc_hip_group_run_leak) */
 };
 
-/* totals of one device -> the vector that is all-reduced: counters, then the (lo, hi) sums as 32-bit limbs */
-__global__ void pc_pack_totals_kernel(const pc_totals *t, int n_energies, long long *vec)
+/* totals of one device -> the vector that is all-reduced: counters, then the (lo, hi) sums as 32-bit limbs.  n_sums = n_energies,
+ * or 2 n_energies with the squared weights' sums, which follow the weights' in pc_totals and in the vector */
+__global__ void pc_pack_totals_kernel(const pc_totals *t, int n_sums, long long *vec)
 {
 	const int k = blockIdx.x*blockDim.x + threadIdx.x;
 	if (k < 6) vec[k] = (long long)t->counters[k];
-	if (k < n_energies) {
+	if (k < n_sums) {
 		const unsigned long long *sw = (const unsigned long long *)(t + 1);
 		const unsigned long long lo = sw[2*k], hi = sw[2*k + 1];
 		vec[6 + 4*k] = (long long)(lo & 0xffffffffull);
@@ -117,7 +124,6 @@ int pc_hip_group_create(const pc_hip_problem *problem, int n_devices, const int 
 	}
 	g->first.assign(n_devices, 0);
 	g->count.assign(n_devices, 0);
-	g->vec_len = 6 + 4*(size_t)problem->n_energies;
 	*out = g;
 	return PC_HIP_OK;
 }
@@ -134,6 +140,7 @@ int pc_hip_group_set_option(pc_hip_group *g, const char *name, int64_t value)
 		int st = pc_hip_set_option(c, name, value);
 		if (st) return st;
 	}
+	if (std::string(name) == "weight_squares") g->weight_squares = (int)value;
 	return PC_HIP_OK;
 }
 
@@ -142,6 +149,8 @@ static int pc_group_run_impl(pc_hip_group *g, uint64_t seed, int64_t n_slots, ui
 	if (!g) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_run: group must not be NULL");
 	if (n_slots < 1) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_run: n_slots must be >= 1");
 	g->leak_run = 0;                            /* set once every member's leak run has succeeded */
+	g->run_squares = g->weight_squares;
+	g->have_sumw2 = 0;
 	const size_t N = g->ctx.size();
 	g->run_slots = n_slots;
 	g->keep_images = keep_images ? 1 : 0;
@@ -312,7 +321,8 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
                         int *reduced_by, float *kernel_ms)
 {
 	if (!g || !counters) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_totals: NULL argument");
-	const size_t N = g->ctx.size(), ne = (size_t)g->ctx[0]->host.pm.n_energies, len = g->vec_len;
+	const size_t N = g->ctx.size(), ne = (size_t)g->ctx[0]->host.pm.n_energies;
+	const size_t n_sums = g->run_squares ? 2*ne : ne, len = 6 + 4*n_sums;
 	float ms_max = 0.f;
 	for (size_t k = 0; k < N; k++) {
 		if (g->count[k] == 0) continue;
@@ -339,20 +349,24 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 		}
 	}
 	if (use_rccl) {
-		if (g->d_vec.empty()) {
+		if (g->d_vec.empty() || g->d_vec_len < len) {
+			for (size_t k = 0; k < g->d_vec.size(); k++)
+				if (g->d_vec[k]) { PC_HIP_CHECK(hipSetDevice(g->devices[k])); PC_HIP_CHECK(hipFree(g->d_vec[k])); }
 			g->d_vec.assign(N, nullptr);
+			g->d_vec_len = 0;
 			for (size_t k = 0; k < N; k++) {
 				PC_HIP_CHECK(hipSetDevice(g->devices[k]));
 				PC_HIP_CHECK(hipMalloc(&g->d_vec[k], len*sizeof(long long)));
 			}
+			g->d_vec_len = len;
 		}
-		const int threads = 64, blocks = (int)((std::max<size_t>(ne, 6) + threads - 1)/threads);
+		const int threads = 64, blocks = (int)((std::max<size_t>(n_sums, 6) + threads - 1)/threads);
 		for (size_t k = 0; k < N; k++) {
 			PC_HIP_CHECK(hipSetDevice(g->devices[k]));
 			if (g->count[k] == 0) {
 				PC_HIP_CHECK(hipMemsetAsync(g->d_vec[k], 0, len*sizeof(long long), g->ctx[k]->stream));
 			} else {
-				hipLaunchKernelGGL(pc_pack_totals_kernel, dim3(blocks), dim3(threads), 0, g->ctx[k]->stream, g->ctx[k]->d_totals, (int)ne, g->d_vec[k]);
+				hipLaunchKernelGGL(pc_pack_totals_kernel, dim3(blocks), dim3(threads), 0, g->ctx[k]->stream, g->ctx[k]->d_totals, (int)n_sums, g->d_vec[k]);
 				PC_HIP_CHECK(hipGetLastError());
 			}
 		}
@@ -371,13 +385,17 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 	} else {
 		/* the same sum on the host: limb by limb, so that it cannot differ from the all-reduce */
 		std::vector<int64_t> c(6);
-		std::vector<uint64_t> fx(2*ne);
+		std::vector<uint64_t> fx(2*n_sums);
 		for (size_t k = 0; k < N; k++) {
 			if (g->count[k] == 0) continue;
 			int st = pc_hip_transmission_totals(g->ctx[k], nullptr, c.data(), fx.data());
 			if (st != PC_HIP_OK && st != PC_HIP_ERR_ATTEMPTS) return st;
+			if (g->run_squares) {
+				st = pc_hip_transmission_moments(g->ctx[k], fx.data() + 2*ne);
+				if (st) return st;
+			}
 			for (int j = 0; j < 6; j++) total[j] += c[j];
-			for (size_t e = 0; e < ne; e++) {
+			for (size_t e = 0; e < n_sums; e++) {
 				total[6 + 4*e] += (long long)(fx[2*e] & 0xffffffffull);
 				total[6 + 4*e + 1] += (long long)(fx[2*e] >> 32);
 				total[6 + 4*e + 2] += (long long)(fx[2*e + 1] & 0xffffffffull);
@@ -386,14 +404,27 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 		}
 	}
 	if (reduced_by) *reduced_by = use_rccl ? 1 : 0;
-	std::vector<uint64_t> fixed(2*ne);
-	pc_unpack_limbs(total.data(), ne, counters, fixed.data());
+	std::vector<uint64_t> fixed(2*n_sums);
+	pc_unpack_limbs(total.data(), n_sums, counters, fixed.data());
+	if (g->run_squares) {
+		g->sumw2.assign(fixed.begin() + 2*ne, fixed.end());
+		g->have_sumw2 = 1;
+	}
 	for (size_t e = 0; e < ne; e++) {
 		if (sum_weights) sum_weights[e] = pc_hip_fixed_to_double(fixed[2*e], fixed[2*e + 1]);
 		if (sumw_fixed) { sumw_fixed[2*e] = fixed[2*e]; sumw_fixed[2*e + 1] = fixed[2*e + 1]; }
 	}
 	if (counters[4] != 0)
 		return pc_fail(PC_HIP_ERR_ATTEMPTS, "pc_hip_group_totals: some slots exhausted max_attempts without a transmitted photon");
+	return PC_HIP_OK;
+}
+
+int pc_hip_group_moments(pc_hip_group *g, uint64_t *sumw2_fixed)
+{
+	if (!g || !sumw2_fixed) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_moments: NULL argument");
+	if (!g->run_squares) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_moments: the last run of the group was made without option weight_squares");
+	if (!g->have_sumw2) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_moments: call pc_hip_group_totals for the last run first");
+	std::copy(g->sumw2.begin(), g->sumw2.end(), sumw2_fixed);
 	return PC_HIP_OK;
 }
 

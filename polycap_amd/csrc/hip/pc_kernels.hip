@@ -32,6 +32,7 @@
 #include "pc_device.h"
 #include "pc_leak.h"
 #include "pc_problem.h"
+#include "pc_moments.h"
 
 #ifndef PC_BLOCK
 #define PC_BLOCK 512            /* maximum workgroup size the trace kernel is compiled for */
@@ -69,7 +70,8 @@ struct pc_totals {             /* device-resident totals of one run */
 	unsigned long long phase[8];      /* scheduler statistics: march steps, march lane-steps, event phases, event lanes, new phases, new lanes */
 	unsigned long long next_slot;     /* work counter (relative slot index) */
 	unsigned long long pad;
-	/* followed by 2*n_energies u64: (lo, hi) fixed-point weight sums */
+	/* followed by 2*n_energies u64: (lo, hi) fixed-point weight sums, then 2*n_energies u64: the same of the squared weights
+	 * (option "weight_squares") */
 };
 
 struct pc_kargs {
@@ -112,7 +114,7 @@ struct pc_kargs {
 	                                   * lane's photon wait here, one 64-byte line per lane, until the photon has left the optic.
 	                                   * Per-lane state: two launches in flight (parts on two streams) get disjoint halves */
 	int new_threshold;
-	int lds_acc;                  /* NE == 0: accumulate weight sums in LDS (2*n_energies u64 of dynamic LDS) */
+	int lds_acc;                  /* NE == 0: accumulate weight sums in LDS (2*n_energies u64 of dynamic LDS, 4* with sumw2) */
 	int lds_ec;                   /* NE == 0: per-energy constants staged in LDS behind the sums (6*n_energies doubles) */
 	int sweep_rough;              /* NE == 0: some energy has a roughness factor (sig_rough != 0): the sweeps evaluate exp(-(c alfa)^2) */
 	int pool_event_min;           /* pool kernel: photons waiting for an EVENT phase that make it run before anything else */
@@ -136,6 +138,10 @@ struct pc_kargs {
 	int *out_rc;
 	double *out_weights, *out_exit_coords, *out_exit_dir, *out_exit_elecv, *out_dtravel;
 	long long *out_irefl;
+	/* option "weight_squares": 2*n_energies (lo, hi) sums of the squared weights (include/polycap-hip.h) right behind sumw, or NULL.
+	 * The kernels that add to it are instantiated with SQ = true; where the sums are kept in LDS, the squares take another
+	 * 2*n_energies u64 behind the weights'.  (Last in the struct: the default kernels' argument offsets stay as they were.) */
+	unsigned long long *sumw2;
 };
 
 /* Stores of the compact image store: written through to memory (system-coherent), so that a block can be handed to the copy
@@ -228,6 +234,24 @@ __device__ __forceinline__ unsigned long long pc_wave_sum_u64(unsigned long long
 	return v;
 }
 
+/* exact 128-bit accumulation of the wave's 64-bit fixed-point values into a wave-uniform (hi:lo) through two 32-bit partial sums */
+__device__ __forceinline__ void pc_wave_acc128(unsigned long long f, unsigned long long &acc_lo, unsigned long long &acc_hi)
+{
+	const unsigned long long s_low = pc_wave_sum_u64(f & 0xffffffffull), s_high = pc_wave_sum_u64(f >> 32);
+	const unsigned long long lo = s_low + (s_high << 32);
+	const unsigned long long hi = (s_high >> 32) + ((lo < s_low) ? 1ull : 0ull);
+	const unsigned long long old = acc_lo;
+	acc_lo = old + lo;
+	acc_hi += hi + ((acc_lo < old) ? 1ull : 0ull);
+}
+
+/* exact add of a value below 2^64 to an LDS (lo, hi) pair */
+__device__ __forceinline__ void pc_lds_add128(unsigned long long *lohi, unsigned long long f)
+{
+	const unsigned long long old = atomicAdd(&lohi[0], f);
+	if (old + f < old) atomicAdd(&lohi[1], 1ull);
+}
+
 /* exact add of a 128-bit (hi:lo) value to a global (lo,hi) pair; carries are derived from each add's old value */
 __device__ __forceinline__ void pc_atomic_add128(unsigned long long *lohi, unsigned long long lo, unsigned long long hi)
 {
@@ -263,11 +287,12 @@ __device__ __forceinline__ int pc_reflect_energy_sweep(const pc_energy_const &ec
 enum { PC_MODE_SRC_CIRCULAR = 0, PC_MODE_SRC_GENERIC = 1, PC_MODE_EXPLICIT = 2 };
 
 /* Source runs with more than 8 energies have a kernel of their own: pc_trace_log_kernel (pc_sweep_kernel.h). */
-template <int NE, int MODE, int PITCH>
+template <int NE, int MODE, int PITCH, bool SQ = false>
 __global__ void __launch_bounds__(PC_BLOCK, NE == 0 ? PC_MIN_WAVES_NE0 : PC_MIN_WAVES)
 pc_trace_kernel(pc_kargs a)
 {
 	constexpr bool EXPLICIT = (MODE == PC_MODE_EXPLICIT);
+	static_assert(!(SQ && EXPLICIT), "explicit launches keep no sums");
 	/* static LDS with a compile-time pitch: table reads become ds_read with immediate offsets */
 	__shared__ double lds[6*PITCH];
 	__shared__ pc_marg4 ldsg[PITCH];
@@ -285,12 +310,13 @@ pc_trace_kernel(pc_kargs a)
 		l_idz[k] = a.g_idz[k];
 		ldsg[k] = a.g_mg[k];
 	}
+	/* u64 of the LDS sums: 2 per energy, 4 with the squared weights (A at [0, 2 ne), B at [2 ne, 4 ne)) */
 	if (NE != 1 && a.lds_acc)
-		for (int k = threadIdx.x; k < 2*a.pm.n_energies; k += blockDim.x) l_acc[k] = 0ull;
+		for (int k = threadIdx.x; k < (SQ ? 4 : 2)*a.pm.n_energies; k += blockDim.x) l_acc[k] = 0ull;
 	/* NE == 0: the per-energy constants of the cooperative sweeps, staged behind the sums when they fit (a.lds_ec):
 	 * every reflection of every photon reads all 6*n_energies of them */
 	if (NE == 0 && a.lds_ec) {
-		double *l_ec = (double *)(l_acc + 2*a.pm.n_energies);
+		double *l_ec = (double *)(l_acc + (SQ ? 4 : 2)*a.pm.n_energies);
 		for (int k = threadIdx.x; k < 6*a.pm.n_energies; k += blockDim.x) l_ec[k] = a.ec_soa[k];
 	}
 	__syncthreads();
@@ -326,6 +352,7 @@ pc_trace_kernel(pc_kargs a)
 	 * of every NEW phase, so no per-lane counter stays live across the march and event loops */
 	unsigned long long u_exit = 0, u_not_entered = 0, u_not_trans = 0, u_irefl = 0, u_failed = 0, u_launch = 0;
 	unsigned long long u_acc_lo = 0, u_acc_hi = 0;   /* NE == 1: exact 128-bit weight sum; NE > 1 and NE == 0 sum in LDS */
+	unsigned long long u_sq_lo = 0, u_sq_hi = 0;     /* NE == 1: the same of the squared weights (a.sumw2) */
 
 	/* wave-uniform scheduler statistics (diagnostics: lane utilisation per phase type) */
 	unsigned long long st_march = 0, st_march_l = 0, st_event = 0, st_event_l = 0, st_new = 0, st_new_l = 0;
@@ -475,7 +502,7 @@ pc_trace_kernel(pc_kargs a)
 						if (lane == p) res = anybad ? -1 : (anykeep ? 1 : 0);
 					}
 				};
-				if (NE == 0 && a.lds_ec) sweep((const double *)(l_acc + 2*a.pm.n_energies));
+				if (NE == 0 && a.lds_ec) sweep((const double *)(l_acc + (SQ ? 4 : 2)*a.pm.n_energies));
 				else sweep(a.ec_soa);
 				if (pend) {
 					if (pend == 1) { ph.wset = 1; ph.ex = fabs(ph.ex); ph.ey = fabs(ph.ey); ph.ez = fabs(ph.ez); }
@@ -488,7 +515,7 @@ pc_trace_kernel(pc_kargs a)
 			int coop = 0;                 /* NE == 0: what the cooperative weight sweep has to do for this lane's photon */
 			int f_exit = 0, f_not_entered = 0, f_not_trans = 0, f_failed = 0, f_launch = 0;   /* this lane's contributions */
 			unsigned int f_irefl = 0;
-			unsigned long long f_w = 0;
+			unsigned long long f_w = 0, f_w2 = 0;
 			long long done_slot = slot;   /* where the finished photon's images go: its slot, or (compact store) the next free position */
 			int ok = 0;                   /* the photon left through the exit window: src/polycap-source.c:758-777 */
 			if (state == LS_DONE) {
@@ -536,6 +563,7 @@ pc_trace_kernel(pc_kargs a)
 					if (NE == 1) {
 						double w = ph.w[0];
 						f_w = (unsigned long long)(w * PC_FIX_SCALE);
+						if (SQ) f_w2 = pc_fix_sq(w);
 						if (a.keep_images) { if (compact) pc_store_wt(a.img_w + done_slot*ws, w); else a.img_w[done_slot*ws] = w; }
 					} else if (NE > 1) {
 						/* a few energies: exact sums in LDS (2 x u64 per energy), flushed once per workgroup */
@@ -546,6 +574,7 @@ pc_trace_kernel(pc_kargs a)
 								unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
 								unsigned long long old = atomicAdd(&l_acc[2*e], f);
 								if (old + f < old) atomicAdd(&l_acc[2*e + 1], 1ull);
+								if (SQ) pc_lds_add128(&l_acc[2*ner + 2*e], pc_fix_sq(w));
 								if (a.keep_images) { if (compact) pc_store_wt(a.img_w + done_slot*ws + e, w); else a.img_w[done_slot*ws + e] = w; }
 							}
 						}
@@ -600,8 +629,10 @@ pc_trace_kernel(pc_kargs a)
 								if (a.lds_acc) {
 									unsigned long long old = atomicAdd(&l_acc[2*e], f);
 									if (old + f < old) atomicAdd(&l_acc[2*e + 1], 1ull);
+									if (SQ) pc_lds_add128(&l_acc[2*ne + 2*e], pc_fix_sq(w));
 								} else {
 									pc_atomic_add128(a.sumw + 2*e, f, 0ull);
+									if (SQ) pc_atomic_add128(a.sumw2 + 2*e, pc_fix_sq(w), 0ull);
 								}
 							}
 							if (a.keep_images) { if (compact) pc_store_wt(a.img_w + slot_p*ws + e, w); else a.img_w[slot_p*ws + e] = w; }
@@ -699,6 +730,7 @@ pc_trace_kernel(pc_kargs a)
 					const unsigned long long old = u_acc_lo;
 					u_acc_lo = old + lo;
 					u_acc_hi += hi + ((u_acc_lo < old) ? 1ull : 0ull);
+					if (SQ) pc_wave_acc128(f_w2, u_sq_lo, u_sq_hi);
 				}
 			}
 		}
@@ -708,6 +740,11 @@ pc_trace_kernel(pc_kargs a)
 		__syncthreads();          /* every wave of the workgroup has finished its photons */
 		for (int e = threadIdx.x; e < a.pm.n_energies; e += blockDim.x)
 			if (l_acc[2*e] | l_acc[2*e + 1]) pc_atomic_add128(a.sumw + 2*e, l_acc[2*e], l_acc[2*e + 1]);
+		if (SQ) {
+			const unsigned long long *l_sq = l_acc + 2*a.pm.n_energies;
+			for (int e = threadIdx.x; e < a.pm.n_energies; e += blockDim.x)
+				if (l_sq[2*e] | l_sq[2*e + 1]) pc_atomic_add128(a.sumw2 + 2*e, l_sq[2*e], l_sq[2*e + 1]);
+		}
 	}
 	if (!EXPLICIT) {
 		/* one set of atomics per wave */
@@ -725,6 +762,8 @@ pc_trace_kernel(pc_kargs a)
 		}
 		if (NE == 1 && lane == 0)
 			pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
+		if (NE == 1 && lane == 0 && SQ && (u_sq_lo | u_sq_hi))
+			pc_atomic_add128(a.sumw2, u_sq_lo, u_sq_hi);
 	}
 }
 
@@ -949,13 +988,15 @@ struct pc_hip_ctx {
 	                                * its proxies are dead, so that photons the sweep finds dead exercise the take-back pass (tests) */
 	int sweep_exact_every = 0;     /* option "sweep_exact_every" (test hook): > 0 = the logs of every photon whose slot is a multiple of it are swept by the
 	                                * EXACT loop, so that sweep passes that mix EXACT and FAST photons are common (0 = off) */
+	int weight_squares = 0;        /* option "weight_squares": source runs also sum the squared exit weights (pc_kargs::sumw2) */
+	int run_squares = 0;           /* the last run did so (pc_hip_transmission_moments) */
 	double *d_rlog = nullptr;
 	size_t rlog_elems = 0;
 	int sweep_cert = 0;            /* pc_sweep_certificate has run */
 	double sweep_ct_tame = 1.;
 	int sweep_n_proxy = 0, sweep_proxy_e[2] = {0, 0};
 	/* last run */
-	pc_totals *d_totals = nullptr;         /* pc_totals + 2*nE u64 */
+	pc_totals *d_totals = nullptr;         /* pc_totals + 2*nE u64 weight sums + 2*nE u64 squared-weight sums */
 	size_t totals_bytes = 0;
 	double *d_img = nullptr;               /* image records: n_slots x (17 + n_energies) doubles */
 	double *h_stage = nullptr;             /* image fetches: two pinned chunks of records on the host */
@@ -1091,12 +1132,19 @@ static void pc_fill_common(pc_hip_ctx *ctx, pc_kargs &a)
 	a.totals = ctx->d_totals;
 	a.work = &ctx->d_totals->next_slot;
 	a.sumw = (unsigned long long *)(ctx->d_totals + 1);
+	a.sumw2 = ctx->weight_squares ? a.sumw + 2*(size_t)ctx->host.pm.n_energies : nullptr;
+}
+
+/* u64 per energy of the exact sums a workgroup keeps in LDS: (lo, hi) of the weights, and of their squares with "weight_squares" */
+static size_t pc_acc_words(const pc_kargs &a)
+{
+	return a.sumw2 ? 4 : 2;
 }
 
 /* dynamic LDS of the any-n_energies kernel: exact sums and per-energy constants */
-static size_t pc_ne0_dyn_lds(size_t ne, int lds_acc, int lds_ec)
+static size_t pc_ne0_dyn_lds(size_t ne, int lds_acc, int lds_ec, size_t acc_words)
 {
-	return (lds_acc ? 2*ne*sizeof(unsigned long long) : 0) + (lds_ec ? 6*ne*sizeof(double) : 0);
+	return (lds_acc ? acc_words*ne*sizeof(unsigned long long) : 0) + (lds_ec ? 6*ne*sizeof(double) : 0);
 }
 
 
@@ -1158,14 +1206,13 @@ static void pc_sweep_certificate(pc_hip_ctx *ctx)
  * constants fit in LDS beside a stage of at least one log per wave; returns the stage size (doubles per wave), 0 if not */
 static size_t pc_log_stage_doubles(const pc_hip_ctx *ctx, int ne, int log_cap)
 {
-	const size_t fixed = 6*PCS_PITCH*sizeof(double) + PCS_PITCH*sizeof(pc_marg4) + pcs_dyn_lds((size_t)ne, PCS_BLOCK, 0);
+	const size_t fixed = 6*PCS_PITCH*sizeof(double) + PCS_PITCH*sizeof(pc_marg4) + pcs_dyn_lds((size_t)ne, PCS_BLOCK, 0, ctx->weight_squares != 0);
 	if (fixed >= 163840) return 0;
 	size_t per_wave = ((163840 - fixed)/(PCS_BLOCK/PC_WAVE))/sizeof(double);
 	const size_t one = PCS_ENT*(size_t)log_cap;
 	if (per_wave < one) return 0;
 	size_t ps = per_wave/one;
 	if (ps > PCS_MAXPS) ps = PCS_MAXPS;
-	(void)ctx;
 	return ps*one;
 }
 
@@ -1174,13 +1221,18 @@ static int pc_launch_one(pc_hip_ctx *ctx, const pc_kargs &a, int grid)
 {
 	/* table pitch: 1024 entries (48 KB of LDS) covers the reference's generated profiles (nmax = 999) and its example decks */
 	const int block = (int)(a.total_threads / grid);
-	const size_t dyn = (NE == 0) ? pc_ne0_dyn_lds((size_t)ctx->host.pm.n_energies, a.lds_acc, a.lds_ec)
-	                             : ((NE != 1 && a.lds_acc) ? 2*(size_t)ctx->host.pm.n_energies*sizeof(unsigned long long) : 0);
-	if (ctx->host.pm.nmax + 1 <= 1024)
-		hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	else if (NE <= 1)   /* long profiles: only the NE = 1 and the any-n_energies kernels are built for the 2048 pitch */
-		hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	else
+	const size_t dyn = (NE == 0) ? pc_ne0_dyn_lds((size_t)ctx->host.pm.n_energies, a.lds_acc, a.lds_ec, pc_acc_words(a))
+	                             : ((NE != 1 && a.lds_acc) ? pc_acc_words(a)*(size_t)ctx->host.pm.n_energies*sizeof(unsigned long long) : 0);
+	/* option "weight_squares": kernels of their own (SQ), so that the default kernels keep their registers */
+	constexpr bool CAN_SQ = MODE != PC_MODE_EXPLICIT;
+	const bool sq = CAN_SQ && a.sumw2 != nullptr;
+	if (ctx->host.pm.nmax + 1 <= 1024) {
+		if (sq) hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, CAN_SQ>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+		else hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+	} else if (NE <= 1) {   /* long profiles: only the NE = 1 and the any-n_energies kernels are built for the 2048 pitch */
+		if (sq) hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, CAN_SQ>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+		else hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+	} else
 		return pc_fail(PC_HIP_ERR_INVALID, "internal: register-weight kernels are built for profiles of up to 1024 points");
 	PC_HIP_CHECK(hipGetLastError());
 	return PC_HIP_OK;
@@ -1198,8 +1250,10 @@ static bool pc_pool_applies(const pc_hip_ctx *ctx, const pc_kargs &a)
 template <int MODE>
 static void pc_launch_pool(pc_hip_ctx *ctx, const pc_kargs &a, int grid)
 {
-	if constexpr (MODE != PC_MODE_EXPLICIT)
-		hipLaunchKernelGGL((pc_trace_pool_kernel<MODE>), dim3(grid), dim3(PQ_BLOCK), 0, ctx->stream, a);
+	if constexpr (MODE != PC_MODE_EXPLICIT) {
+		if (a.sumw2) hipLaunchKernelGGL((pc_trace_pool_kernel<MODE, true>), dim3(grid), dim3(PQ_BLOCK), 0, ctx->stream, a);
+		else hipLaunchKernelGGL((pc_trace_pool_kernel<MODE>), dim3(grid), dim3(PQ_BLOCK), 0, ctx->stream, a);
+	}
 }
 
 template <int MODE>
@@ -1208,10 +1262,11 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 	const int ne = ctx->host.pm.n_energies;
 	/* weights in registers for up to 8 energies (kernels NE = 1, 4, 8), in the per-lane scratch beyond */
 	const int kne = (ne == 1) ? 1 : ((ne <= 4 && ctx->host.pm.nmax + 1 <= 1024) ? 4 : ((ne <= 8 && ctx->host.pm.nmax + 1 <= 1024) ? 8 : 0));
-	a.lds_acc = (ne != 1 && 2*(size_t)ne*sizeof(unsigned long long) <= 16384) ? 1 : 0;
+	/* with "weight_squares" the squared weights' sums sit beside the weights' and fall back to global atomics with them */
+	a.lds_acc = (ne != 1 && pc_acc_words(a)*(size_t)ne*sizeof(unsigned long long) <= 16384) ? 1 : 0;
 	/* many energies on a profile of up to 1024 points: one workgroup of 1024 threads per CU (the same 16 waves as two of
 	 * 512) leaves room in LDS for the per-energy constants next to the tables and the sums */
-	a.lds_ec = (kne == 0 && a.lds_acc && ctx->lds_ec && ctx->host.pm.nmax + 1 <= 1024 && 64*(size_t)ne <= 28672) ? 1 : 0;
+	a.lds_ec = (kne == 0 && a.lds_acc && ctx->lds_ec && ctx->host.pm.nmax + 1 <= 1024 && (48 + 8*pc_acc_words(a))*(size_t)ne <= 28672) ? 1 : 0;
 	bool all_valid = true;
 	a.sweep_rough = 0;
 	for (const pc_energy_const &c : ctx->host.ec) {
@@ -1252,7 +1307,9 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			a.new_threshold = ctx->producer_new_min;
 			a.pool_event_min = ctx->producer_new_first;
 			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-			if (ctx->march_stats) hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, true>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
+			/* "weight_squares": one instantiation, without the march statistics (diagnostics) */
+			if (a.sumw2) hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, false, true>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
+			else if (ctx->march_stats) hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, true>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
 			else hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, false>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
 			ctx->last_kernel = 2;
 			PC_HIP_CHECK(hipGetLastError());
@@ -1332,7 +1389,8 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			a.sweep_fuse = a.keep_images ? 0 : ctx->sweep_fuse;
 			a.sweep_exact_every = ctx->sweep_exact_every;
 			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-			hipLaunchKernelGGL((pc_trace_log_kernel<MODE>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage), ctx->stream, a);
+			if (a.sumw2) hipLaunchKernelGGL((pc_trace_log_kernel<MODE, true>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage, true), ctx->stream, a);
+			else hipLaunchKernelGGL((pc_trace_log_kernel<MODE>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage, false), ctx->stream, a);
 			ctx->last_kernel = 4;
 			PC_HIP_CHECK(hipGetLastError());
 			if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
@@ -1488,7 +1546,7 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 		PC_CTX_CHECK(hipMemcpy(ctx->d_ec_soa, soa.data(), soa.size()*sizeof(double), hipMemcpyHostToDevice));
 	}
 	ctx->leak_max_depth = (int)std::min(65536.0, 2.0*ctx->host.pm.n_shells + 16.0);
-	ctx->totals_bytes = sizeof(pc_totals) + 2*ctx->host.ec.size()*sizeof(unsigned long long);
+	ctx->totals_bytes = sizeof(pc_totals) + 4*ctx->host.ec.size()*sizeof(unsigned long long);
 	PC_CTX_CHECK(hipMalloc(&ctx->d_totals, ctx->totals_bytes));
 	PC_CTX_CHECK(hipMemset(ctx->d_totals, 0, ctx->totals_bytes));
 #undef PC_CTX_CHECK
@@ -1514,6 +1572,7 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "log_min_energies") { if (value < 9) return pc_fail(PC_HIP_ERR_INVALID, "log_min_energies must be >= 9 (up to 8 energies have their weights in registers)"); ctx->log_min_energies = (int)value; }
 	else if (n == "flush_max") { if (value < 1 || value > 16) return pc_fail(PC_HIP_ERR_INVALID, "flush_max must be in [1,16]"); ctx->flush_max = (int)value; }
 	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->sweep_exact_every = (int)value; }
+	else if (n == "weight_squares") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "weight_squares must be 0 or 1"); ctx->weight_squares = (int)value; }
 	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->sweep_fuse = (int)value; }
 	else if (n == "plane_images") ctx->plane_images = value ? 1 : 0;
 	else if (n == "compact_images") ctx->compact_images = value ? 1 : 0;
@@ -1603,9 +1662,11 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 		memcpy(h + 6*N, start_elecv, 3*N*sizeof(double));
 		PC_LP_CHECK(hipMemcpyAsync(d, h, 9*N*sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 		PC_LP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
+		ctx->run_squares = 0;          /* explicit launches keep no sums */
 		pc_kargs a;
 		pc_fill_common(ctx, a);
 		a.n_slots = n; a.slot0 = 0; a.max_attempts = 1; a.keep_images = 0;
+		a.sumw2 = nullptr;
 		a.in_start = d_start; a.in_dir = d_dir; a.in_elecv = d_ev;
 		a.out_rc = d_rc; a.out_weights = d_w; a.out_exit_coords = d_ec; a.out_exit_dir = d_ed; a.out_exit_elecv = d_ee;
 		a.out_irefl = d_ir; a.out_dtravel = d_dt;
@@ -1834,6 +1895,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	}
 	ctx->last_run_plain = 1;
 	ctx->leak_events_of_run = 0;
+	ctx->run_squares = ctx->weight_squares;
 	pc_kargs a;
 	pc_fill_common(ctx, a);
 	ctx->img_valid = 0;
@@ -1964,6 +2026,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	ctx->run_planes = 0;
 	ctx->last_run_plain = 0;
 	ctx->leak_events_of_run = 1;
+	ctx->run_squares = ctx->weight_squares;
 	ctx->leak_seed = seed; ctx->leak_slot0 = slot0; ctx->leak_n_slots = n_slots;
 	ctx->leak_max_attempts = max_attempts; ctx->leak_keep_images = keep_images ? 1 : 0;
 	/* record buffer: events per slot grow with the number of energies (a leak is kept while ANY energy holds >= 1e-4):
@@ -2086,6 +2149,32 @@ int pc_hip_transmission_totals(pc_hip_ctx *ctx, double *sum_weights, int64_t cou
 	if (t->counters[4] != 0)
 		return pc_fail(PC_HIP_ERR_ATTEMPTS, "pc_hip_transmission_totals: some slots exhausted max_attempts without a transmitted photon");
 	return PC_HIP_OK;
+}
+
+int pc_hip_transmission_moments(pc_hip_ctx *ctx, uint64_t *sumw2_fixed)
+{
+	if (!ctx || !sumw2_fixed) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_moments: NULL argument");
+	if (!ctx->run_squares) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_moments: the last run was made without option weight_squares");
+	int st = pc_hip_transmission_wait(ctx, nullptr);
+	if (st) return st;
+	const size_t ne = (size_t)ctx->host.pm.n_energies;
+	PC_HIP_CHECK(hipMemcpy(sumw2_fixed, (const unsigned long long *)(ctx->d_totals + 1) + 2*ne, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return PC_HIP_OK;
+}
+
+void pc_hip_efficiency_stderr(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed, const int64_t counters[6], double *out)
+{
+	/* N = every started photon: exit photons, not entered, not transmitted (the efficiency's denominator, open_area cancelled) */
+	const long double n = (long double)counters[0] + (long double)counters[1] + (long double)counters[2];
+	for (size_t e = 0; e < n_energies; e++) {
+		if (!(n >= 2.0L)) { out[e] = NAN; continue; }
+		const long double a = (long double)sumw_fixed[2*e + 1] * 18446744073709551616.0L + (long double)sumw_fixed[2*e];
+		const long double b = (long double)sumw2_fixed[2*e + 1] * 18446744073709551616.0L + (long double)sumw2_fixed[2*e];
+		const long double m = a / (n * 4611686018427387904.0L), q = b / (n * 4611686018427387904.0L);
+		long double v = q - m*m;
+		if (v < 0.0L) v = 0.0L;
+		out[e] = (double)sqrtl(v / (n - 1.0L));
+	}
 }
 
 int pc_hip_last_kernel(pc_hip_ctx *ctx)

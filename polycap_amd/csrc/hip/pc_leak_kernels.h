@@ -49,7 +49,7 @@ struct pc_leak_kargs {
 /* lane modes of the scheduler on top of pc_leak_lane::st */
 enum { PC_LM_NEED = 0, PC_LM_RUN = 1, PC_LM_IDLE = 2, PC_LM_PARKED = 3 };
 
-template <int MODE, int PITCH>
+template <int MODE, int PITCH, bool SQ = false>
 __global__ void __launch_bounds__(PC_LEAK_BLOCK, PC_LEAK_MIN_WAVES)
 pc_leak_kernel(pc_kargs a, pc_leak_kargs lk)
 {
@@ -211,6 +211,7 @@ pc_leak_kernel(pc_kargs a, pc_leak_kargs lk)
 							for (int e = 0; e < ne; e++) {
 								const double w = w0[e];
 								pc_atomic_add128(a.sumw + 2*e, (unsigned long long)(w * PC_FIX_SCALE), 0ull);
+								if (SQ) pc_atomic_add128(a.sumw2 + 2*e, pc_fix_sq(w), 0ull);
 								if (a.keep_images) a.img[slot*rec + PC_F_WEIGHTS + e] = w;
 							}
 							if (a.keep_images) {
@@ -433,10 +434,16 @@ static int pc_leak_enqueue(pc_hip_ctx *ctx, pc_kargs &a, long long n_items, long
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_cursor, 0, 4*sizeof(unsigned long long), ctx->stream));
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
 	if (!ctx->leak_ev0_done) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-	if (ctx->host.pm.nmax + 1 <= 1024)
-		hipLaunchKernelGGL((pc_leak_kernel<MODE, 1024>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
-	else
-		hipLaunchKernelGGL((pc_leak_kernel<MODE, PC_MAX_PITCH>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
+	/* option "weight_squares": kernels of their own (SQ), so that the default kernels keep their registers */
+	constexpr bool CAN_SQ = MODE != PC_MODE_EXPLICIT;
+	const bool sq = CAN_SQ && a.sumw2 != nullptr;
+	if (ctx->host.pm.nmax + 1 <= 1024) {
+		if (sq) hipLaunchKernelGGL((pc_leak_kernel<MODE, 1024, CAN_SQ>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
+		else hipLaunchKernelGGL((pc_leak_kernel<MODE, 1024>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
+	} else {
+		if (sq) hipLaunchKernelGGL((pc_leak_kernel<MODE, PC_MAX_PITCH, CAN_SQ>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
+		else hipLaunchKernelGGL((pc_leak_kernel<MODE, PC_MAX_PITCH>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
+	}
 	PC_HIP_CHECK(hipGetLastError());
 	ctx->last_kernel = 5;
 	PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));

@@ -120,7 +120,7 @@ __device__ __forceinline__ void pq_swap_in(const pc_tables &T, int X, unsigned l
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int MODE>
+template <int MODE, bool SQ = false>
 __global__ void __launch_bounds__(PQ_BLOCK, PQ_MIN_WAVES)
 pc_trace_pool_kernel(pc_kargs a)
 {
@@ -161,6 +161,7 @@ pc_trace_pool_kernel(pc_kargs a)
 	long long chunk_next = 0, chunk_end = 0;
 	unsigned long long u_exit = 0, u_not_entered = 0, u_not_trans = 0, u_irefl = 0, u_failed = 0, u_launch = 0;
 	unsigned long long u_acc_lo = 0, u_acc_hi = 0;
+	unsigned long long u_sq_lo = 0, u_sq_hi = 0;     /* the squared weights' sum (a.sumw2) */
 	unsigned long long st_march = 0, st_march_l = 0, st_event = 0, st_event_l = 0, st_new = 0, st_new_l = 0, st_swap = 0;
 	unsigned long long pM, pE, pN;
 	pq_masks(est, lane, pM, pE, pN);
@@ -226,7 +227,7 @@ pc_trace_pool_kernel(pc_kargs a)
 			st_new += 1; st_new_l += (unsigned)__popcll(__ballot(L.state == LS_DONE || L.state == LS_NEED_SLOT || L.state == LS_START));
 			int f_exit = 0, f_not_entered = 0, f_not_trans = 0, f_failed = 0, f_launch = 0;
 			unsigned int f_irefl = 0;
-			unsigned long long f_w = 0;
+			unsigned long long f_w = 0, f_w2 = 0;
 			if (L.state == LS_DONE) {
 				/* src/polycap-source.c:758-777 */
 				const int rc = ph.rc;
@@ -240,6 +241,7 @@ pc_trace_pool_kernel(pc_kargs a)
 					f_irefl = (unsigned int)ph.irefl;
 					const double w = ph.w[0];
 					f_w = (unsigned long long)(w * PC_FIX_SCALE);
+					if (SQ) f_w2 = pc_fix_sq(w);
 					if (a.keep_images) {
 						/* src/polycap-source.c:900-923; cos(alpha) of the start vectors was left in the record by the launch */
 						double *r = a.img + slot*ss;
@@ -328,6 +330,7 @@ pc_trace_pool_kernel(pc_kargs a)
 				const unsigned long long old = u_acc_lo;
 				u_acc_lo = old + lo;
 				u_acc_hi += hi + ((u_acc_lo < old) ? 1ull : 0ull);
+				if (SQ) pc_wave_acc128(f_w2, u_sq_lo, u_sq_hi);
 			}
 		}
 	}
@@ -344,6 +347,7 @@ pc_trace_pool_kernel(pc_kargs a)
 		atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
 		atomicAdd(&a.totals->phase[6], st_swap);
 		pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
+		if (SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(a.sumw2, u_sq_lo, u_sq_hi);
 	}
 }
 

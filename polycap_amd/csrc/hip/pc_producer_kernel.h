@@ -65,7 +65,7 @@ __device__ __forceinline__ void pc3_store(unsigned int *p, unsigned int v)
 
 /* STATS: the march burst counts its steps and their active lanes (pc_hip_phase_stats; option "march_stats").  The production
  * instantiation leaves those two counters at zero: their ballot + popcount sat inside the unrolled hot loop. */
-template <int MODE, bool STATS = false>
+template <int MODE, bool STATS = false, bool SQ = false>
 __global__ void __launch_bounds__(PC3_BLOCK, 4)
 pc_trace_producer_kernel(pc_kargs a)
 {
@@ -99,6 +99,7 @@ pc_trace_producer_kernel(pc_kargs a)
 	const pc_params &Pm = a.pm;
 	unsigned long long u_exit = 0, u_not_entered = 0, u_not_trans = 0, u_irefl = 0, u_failed = 0, u_launch = 0;
 	unsigned long long u_acc_lo = 0, u_acc_hi = 0;
+	unsigned long long u_sq_lo = 0, u_sq_hi = 0;     /* the squared weights' sum (a.sumw2) */
 	unsigned long long st_march = 0, st_march_l = 0, st_event = 0, st_event_l = 0, st_new = 0, st_new_l = 0, st_batches = 0;
 	long long polls = 0;
 
@@ -152,7 +153,7 @@ pc_trace_producer_kernel(pc_kargs a)
 				if (mFin) {
 					polls = 0;
 					int f_exit = 0, f_nt = 0, f_fail = 0;
-					unsigned long long f_w = 0;
+					unsigned long long f_w = 0, f_w2 = 0;
 					if (fin) {
 						int ok = 0;
 						if (g_rc == 0) f_nt = 1;
@@ -164,6 +165,7 @@ pc_trace_producer_kernel(pc_kargs a)
 						if (ok) {
 							f_exit = 1;
 							f_w = (unsigned long long)(gw * PC_FIX_SCALE);
+							if (SQ) f_w2 = pc_fix_sq(gw);
 							if (a.keep_images && !a.img_cursor) {
 								double *r = a.img + g_slot*ss;
 								const double cosalpha0 = __longlong_as_double((long long)__hip_atomic_load((unsigned long long *)(r + PC_F_EEVX*fs),
@@ -227,6 +229,7 @@ pc_trace_producer_kernel(pc_kargs a)
 						const unsigned long long old = u_acc_lo;
 						u_acc_lo = old + lo;
 						u_acc_hi += hi + ((u_acc_lo < old) ? 1ull : 0ull);
+						if (SQ) pc_wave_acc128(f_w2, u_sq_lo, u_sq_hi);
 					}
 				}
 			}
@@ -525,6 +528,7 @@ pc_trace_producer_kernel(pc_kargs a)
 			atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
 		}
 		if (u_acc_lo | u_acc_hi) pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
+		if (SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(a.sumw2, u_sq_lo, u_sq_hi);
 		if (wave == 0) atomicAdd(&a.totals->phase[6], st_batches);
 	}
 	__syncthreads();

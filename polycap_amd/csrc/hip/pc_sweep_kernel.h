@@ -72,15 +72,15 @@
 #define PCS_LEASH 4            /* reflections between sweeps of a photon whose proxies are dead but which a sweep found alive */
 #endif
 
-/* dynamic LDS of pc_trace_log_kernel: exact sums, per-energy constants (5 fields), per wave the sweep tables (4 x 16 words +
- * 16 doubles) and `stage` doubles of staged logs */
-static size_t pcs_dyn_lds(size_t ne, int block, size_t stage_doubles_per_wave)
+/* dynamic LDS of pc_trace_log_kernel: exact sums (with `squares`, those of the squared weights too), per-energy constants
+ * (5 fields), per wave the sweep tables (4 x 16 words + 16 doubles) and `stage` doubles of staged logs */
+static size_t pcs_dyn_lds(size_t ne, int block, size_t stage_doubles_per_wave, bool squares)
 {
-	return 2*ne*sizeof(unsigned long long) + 5*ne*sizeof(double)
+	return (squares ? 4 : 2)*ne*sizeof(unsigned long long) + 5*ne*sizeof(double)
 	     + (size_t)(block/PC_WAVE)*(4*PCS_MAXPS*sizeof(unsigned int) + PCS_MAXPS*sizeof(double) + stage_doubles_per_wave*sizeof(double));
 }
 
-template <int MODE>
+template <int MODE, bool SQ = false>
 __global__ void __launch_bounds__(PCS_BLOCK, PCS_WAVES)
 pc_trace_log_kernel(pc_kargs a)
 {
@@ -92,8 +92,10 @@ pc_trace_log_kernel(pc_kargs a)
 	const int npts = Pm.nmax + 1, ne = Pm.n_energies;
 	double *l_z = lds, *l_cap = lds + PCS_PITCH, *l_zh = lds + 2*PCS_PITCH, *l_cap2 = lds + 3*PCS_PITCH;
 	double *l_hexd = lds + 4*PCS_PITCH, *l_idz = lds + 5*PCS_PITCH;
+	/* the exact sums: (lo, hi) per energy at [0, 2 ne), those of the squared weights (a.sumw2) at [2 ne, 4 ne) */
+	unsigned long long *const l_sq = l_acc + 2*ne;
 	/* per-energy constants of FORM 3 in LDS: d2, Re n^2, Im n^2, zi2 (fields 0-3 of ec_soa) and rough_c^2 (field 6) */
-	double *const ecs = (double *)(l_acc + 2*ne);
+	double *const ecs = (double *)(l_acc + (SQ ? 4 : 2)*ne);
 	for (int k = threadIdx.x; k < npts; k += blockDim.x) {
 		l_z[k] = a.g_z[k];
 		l_cap[k] = a.g_cap[k];
@@ -103,7 +105,7 @@ pc_trace_log_kernel(pc_kargs a)
 		l_idz[k] = a.g_idz[k];
 		ldsg[k] = a.g_mg[k];
 	}
-	for (int k = threadIdx.x; k < 2*ne; k += blockDim.x) l_acc[k] = 0ull;
+	for (int k = threadIdx.x; k < (SQ ? 4 : 2)*ne; k += blockDim.x) l_acc[k] = 0ull;
 	for (int k = threadIdx.x; k < 4*ne; k += blockDim.x) ecs[k] = a.ec_soa[k];
 	for (int k = threadIdx.x; k < ne; k += blockDim.x) ecs[4*ne + k] = a.ec_soa[6*ne + k];
 	__syncthreads();
@@ -280,12 +282,20 @@ pc_trace_log_kernel(pc_kargs a)
 				if (info & 0x10000u) {
 					const unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
 					if (f) {
+						/* the take-back subtracts exactly what the first pass added: the same w, so the same f and f2 (w < 2^-62: f = 0 and
+						 * w*w < 2^-124, f2 = 0 as well -- nothing to add or take back) */
+						const unsigned long long f2 = SQ ? pc_fix_sq(w) : 0ull;
 						if (!undo) {
 							const unsigned long long old = atomicAdd(&l_acc[2*ee], f);
 							if (old + f < old) atomicAdd(&l_acc[2*ee + 1], 1ull);
+							if (f2) pc_lds_add128(&l_sq[2*ee], f2);
 						} else {
 							const unsigned long long old = atomicSub(&l_acc[2*ee], f);
 							if (old < f) atomicSub(&l_acc[2*ee + 1], 1ull);
+							if (f2) {
+								const unsigned long long old2 = atomicSub(&l_sq[2*ee], f2);
+								if (old2 < f2) atomicSub(&l_sq[2*ee + 1], 1ull);
+							}
 						}
 					}
 				} else {
@@ -512,6 +522,7 @@ pc_trace_log_kernel(pc_kargs a)
 							if (f) {
 								const unsigned long long old = atomicAdd(&l_acc[2*e], f);
 								if (old + f < old) atomicAdd(&l_acc[2*e + 1], 1ull);
+								if (SQ) { const unsigned long long f2 = pc_fix_sq(w); if (f2) pc_lds_add128(&l_sq[2*e], f2); }
 							}
 						}
 						if (a.keep_images) { if (compact) pc_store_wt(a.img_w + slot_p*ws + e, w); else a.img_w[slot_p*ws + e] = w; }
@@ -596,6 +607,9 @@ pc_trace_log_kernel(pc_kargs a)
 	__syncthreads();          /* every wave of the workgroup has finished its photons */
 	for (int e = threadIdx.x; e < ne; e += blockDim.x)
 		if (l_acc[2*e] | l_acc[2*e + 1]) pc_atomic_add128(a.sumw + 2*e, l_acc[2*e], l_acc[2*e + 1]);
+	if (SQ)
+		for (int e = threadIdx.x; e < ne; e += blockDim.x)
+			if (l_sq[2*e] | l_sq[2*e + 1]) pc_atomic_add128(a.sumw2 + 2*e, l_sq[2*e], l_sq[2*e + 1]);
 	if (lane == 0) {
 		atomicAdd(&a.totals->counters[0], u_exit);
 		atomicAdd(&a.totals->counters[1], u_not_entered);

@@ -244,6 +244,8 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 	dim[0] = ne;
 	if (!pc_h5_dataset(file, 1, dim, "/Energies", efficiencies->energies, "keV", error)) goto close;
 	if (!pc_h5_dataset(file, 1, dim, "/Transmission_Efficiencies", efficiencies->efficiencies, "a.u.", error)) goto close;
+	/* extension: the standard errors of a run made with POLYCAP_STDERR=1 */
+	if (efficiencies->stderrs != NULL && !pc_h5_dataset(file, 1, dim, "/Transmission_Efficiencies_StdErr", efficiencies->stderrs, "a.u.", error)) goto close;
 
 	if (!pc_h5_group(file, "/PC_Start", error)) goto close;
 	if (!pc_h5_planes(file, "/PC_Start/Coordinates", 2, im->pc_start_coords, n, "[cm,cm]", tmp, error)) goto close;

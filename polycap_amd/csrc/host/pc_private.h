@@ -144,6 +144,11 @@ struct _polycap_transmission_efficiencies {
 	polycap_source *source;
 	int synthetic_constants;   /* extension: see pc_transmission_efficiencies_synthetic */
 	struct pc_spot_result *spot;
+	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
+	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
+	int64_t n_started;
+	uint64_t *sumw_fixed, *sumw2_fixed;
+	double *stderrs;           /* [n_energies] pc_hip_efficiency_stderr of the moments */
 };
 
 /* internal helpers */

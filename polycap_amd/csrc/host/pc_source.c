@@ -473,14 +473,44 @@ static int pc_spot_request_parse(struct pc_spot_request *r, size_t n_energies, p
 	return 0;
 }
 
+/* POLYCAP_STDERR: 1 = the result carries a standard error per energy (option "weight_squares", pc_hip_efficiency_stderr); unset or 0 =
+ * nothing changes.  Parsed and validated before any device is used; returns -1 with *error set for anything but 0 or 1. */
+static int pc_stderr_request_parse(int *on, polycap_error **error)
+{
+	const char *env = getenv("POLYCAP_STDERR");
+	*on = 0;
+	if (env == NULL || strcmp(env, "0") == 0)
+		return 0;
+	if (strcmp(env, "1") == 0) {
+		*on = 1;
+		return 0;
+	}
+	polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_STDERR=%s: must be 0 or 1", env);
+	return -1;
+}
+
+/* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
+static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
+{
+	for (size_t e = 0; e < ne; e++) {
+		const uint64_t l = acc[2*e] + part[2*e];
+		acc[2*e + 1] += part[2*e + 1] + (l < acc[2*e] ? 1 : 0);
+		acc[2*e] = l;
+	}
+}
+
 /* POLYCAP_IMAGES=0 with spot maps on one context: the exit data of the run stay on the device, and a run whose exit data would take
  * more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by (seed, slot): the
- * same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is added to the map. */
+ * same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is added to the map.
+ * fixed [2*ne] receives the weights' sums; fixed2 (NULL unless POLYCAP_STDERR) those of the squared weights. */
 static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
-	size_t ne, double *sum_weights, int64_t counters[6])
+	size_t ne, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
-	uint64_t *fixed = calloc(2*ne, sizeof(uint64_t)), *part = malloc(2*ne*sizeof(uint64_t));
-	int st = (fixed != NULL && part != NULL) ? PC_HIP_OK : PC_HIP_ERR_MEMORY;
+	uint64_t *part = malloc(2*ne*sizeof(uint64_t));
+	int st = (part != NULL) ? PC_HIP_OK : PC_HIP_ERR_MEMORY;
+	memset(fixed, 0, 2*ne*sizeof(uint64_t));
+	if (fixed2 != NULL)
+		memset(fixed2, 0, 2*ne*sizeof(uint64_t));
 	for (int k = 0; k < 6; k++)
 		counters[k] = 0;
 	for (int64_t lo = 0; lo < n_photons && st == PC_HIP_OK; lo += chunk) {
@@ -495,15 +525,16 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, in
 			break;
 		for (int k = 0; k < 6; k++)
 			counters[k] += c[k];
-		for (size_t e = 0; e < ne; e++) {      /* 128-bit (lo, hi) sums */
-			const uint64_t l = fixed[2*e] + part[2*e];
-			fixed[2*e + 1] += part[2*e + 1] + (l < fixed[2*e] ? 1 : 0);
-			fixed[2*e] = l;
+		pc_fixed_add(fixed, part, ne);      /* 128-bit (lo, hi) sums */
+		if (fixed2 != NULL) {
+			st = pc_hip_transmission_moments(ctx, part);
+			if (st != PC_HIP_OK)
+				break;
+			pc_fixed_add(fixed2, part, ne);
 		}
 	}
 	for (size_t e = 0; st == PC_HIP_OK && e < ne; e++)
 		sum_weights[e] = pc_hip_fixed_to_double(fixed[2*e], fixed[2*e + 1]);
-	free(fixed);
 	free(part);
 	return st;
 }
@@ -593,6 +624,9 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 
 	const size_t ne = source->n_energies;
 	const int timing = getenv("POLYCAP_TIMING") != NULL;
+	int stderr_on = 0;
+	if (pc_stderr_request_parse(&stderr_on, error) != 0)
+		return NULL;
 	struct pc_spot_request spot_req;
 	if (pc_spot_request_parse(&spot_req, ne, error) != 0)
 		return NULL;
@@ -617,7 +651,15 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	t_stage[0] = pc_now_ms();
 	polycap_transmission_efficiencies *eff = pc_transeff_alloc(source, keep_images ? (size_t)n_photons : 0, 0, "polycap_source_get_transmission_efficiencies", error);
 	double *sum_weights = malloc(sizeof(double)*ne);
-	if (eff == NULL || sum_weights == NULL) {
+	/* POLYCAP_STDERR: the exact moments of the run (A = weights, B = squared weights), kept by the result */
+	uint64_t *sum_fixed = malloc(sizeof(uint64_t)*2*ne), *sum_fixed2 = stderr_on ? malloc(sizeof(uint64_t)*2*ne) : NULL;
+	if (eff != NULL && stderr_on) {
+		eff->sumw_fixed = sum_fixed; eff->sumw2_fixed = sum_fixed2;      /* freed with the result from here on */
+		sum_fixed = NULL; sum_fixed2 = NULL;
+	}
+	if (eff == NULL || sum_weights == NULL || (stderr_on ? (eff->sumw_fixed == NULL || eff->sumw2_fixed == NULL) : sum_fixed == NULL)) {
+		free(sum_fixed);
+		free(sum_fixed2);
 		if (eff != NULL)
 			polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for efficiencies -> %s", strerror(errno));
 		free(sum_weights);
@@ -635,6 +677,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		                        "polycap_source_get_transmission_efficiencies", error);
 	if (ctx == NULL && group == NULL) {
 		free(sum_weights);
+		free(sum_fixed);
 		free(spot_req.energies);
 		polycap_transmission_efficiencies_free(eff);
 		return NULL;
@@ -677,6 +720,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	} else if (group != NULL) {
 		status = pc_hip_group_set_option(group, "run_parts", parts);
 		if (status == PC_HIP_OK)
+			status = pc_hip_group_set_option(group, "weight_squares", stderr_on);     /* the group is cached: set either way */
+		if (status == PC_HIP_OK)
 			status = pc_hip_group_set_option(group, "compact_images", compact);
 		if (status == PC_HIP_OK)
 			status = pc_hip_group_set_option(group, "plane_images", leak_calc ? 0 : 1);
@@ -686,13 +731,16 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	} else {
 		status = pc_hip_set_option(ctx, "run_parts", parts);
 		if (status == PC_HIP_OK)
+			status = pc_hip_set_option(ctx, "weight_squares", stderr_on);     /* the context is cached: set either way */
+		if (status == PC_HIP_OK)
 			status = pc_hip_set_option(ctx, "compact_images", compact);
 		if (status == PC_HIP_OK && getenv("POLYCAP_BLOCK_SHIFT") != NULL)
 			status = pc_hip_set_option(ctx, "block_shift", (int64_t)pc_env_u64("POLYCAP_BLOCK_SHIFT", 18, NULL));
 		if (status == PC_HIP_OK)
 			status = pc_hip_set_option(ctx, "plane_images", leak_calc ? 0 : 1);   /* the result object wants planes: let the kernel write them */
 		if (status == PC_HIP_OK && chunked)
-			status = pc_spot_chunked(ctx, spot[0], seed, n_photons, chunk, max_attempts, ne, sum_weights, counters);
+			status = pc_spot_chunked(ctx, spot[0], seed, n_photons, chunk, max_attempts, ne, sum_weights, counters,
+			                         stderr_on ? eff->sumw_fixed : sum_fixed, eff->sumw2_fixed);
 		else if (status == PC_HIP_OK)
 			status = leak_calc ? pc_hip_transmission_run_leak(ctx, seed, 0, n_photons, max_attempts, 1)
 			                   : pc_hip_transmission_run(ctx, seed, 0, n_photons, max_attempts, device_images);
@@ -721,11 +769,15 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	if (status == PC_HIP_OK && !chunked) {
 		if (group != NULL) {
 			const char *r = getenv("POLYCAP_RCCL");      /* 0: host sum, 1: RCCL or fail; default: RCCL when possible */
-			status = pc_hip_group_totals(group, (r != NULL && *r != '\0') ? atoi(r) : -1, sum_weights, counters, NULL, &reduced_by, NULL);
+			status = pc_hip_group_totals(group, (r != NULL && *r != '\0') ? atoi(r) : -1, sum_weights, counters, eff->sumw_fixed, &reduced_by, NULL);
+			if (status == PC_HIP_OK && stderr_on)
+				status = pc_hip_group_moments(group, eff->sumw2_fixed);
 		} else {
 			status = pc_hip_transmission_wait(ctx, NULL);
 			if (status == PC_HIP_OK)
-				status = pc_hip_transmission_totals(ctx, sum_weights, counters, NULL);
+				status = pc_hip_transmission_totals(ctx, sum_weights, counters, eff->sumw_fixed);
+			if (status == PC_HIP_OK && stderr_on)
+				status = pc_hip_transmission_moments(ctx, eff->sumw2_fixed);
 		}
 	}
 	t_stage[5] = pc_now_ms();
@@ -744,6 +796,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			pc_hip_spot_destroy(spot[kind]);
 		free(spot_req.energies);
 		free(sum_weights);
+		free(sum_fixed);
 		polycap_transmission_efficiencies_free(eff);
 		return NULL;
 	}
@@ -758,6 +811,21 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 
 	pc_transeff_finish(eff, sum_weights, counters);
 	eff->synthetic_constants = source->cache.synthetic;
+	if (stderr_on) {
+		eff->n_started = sum_iexit + sum_not_entered + sum_not_transmitted;
+		eff->stderrs = malloc(sizeof(double)*ne);
+		if (eff->stderrs == NULL) {
+			polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for the standard errors -> %s", strerror(errno));
+			for (int kind = 0; kind <= 2; kind++)
+				pc_hip_spot_destroy(spot[kind]);
+			free(spot_req.energies);
+			free(sum_weights);
+			free(sum_fixed);
+			polycap_transmission_efficiencies_free(eff);
+			return NULL;
+		}
+		pc_hip_efficiency_stderr(ne, eff->sumw_fixed, eff->sumw2_fixed, counters, eff->stderrs);
+	}
 	if (spot_req.set) {
 		for (int kind = 0; kind <= 2; kind++) {
 			if (spot[kind] != NULL && status == PC_HIP_OK)
@@ -768,6 +836,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		if (status != PC_HIP_OK) {
 			pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
 			free(sum_weights);
+			free(sum_fixed);
 			polycap_transmission_efficiencies_free(eff);
 			return NULL;
 		}
@@ -775,6 +844,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	if (!keep_images)
 		eff->images->i_exit = 0;     /* no per-photon planes were kept: the exit/start getters report no events */
 	free(sum_weights);
+	free(sum_fixed);
 	return eff;
 }
 

@@ -204,6 +204,9 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	free(efficiencies->efficiencies);
 	pc_images_free(efficiencies->images);
 	pc_spot_result_free(efficiencies->spot);
+	free(efficiencies->sumw_fixed);
+	free(efficiencies->sumw2_fixed);
+	free(efficiencies->stderrs);
 	free(efficiencies);
 }
 
@@ -269,6 +272,56 @@ int pc_transmission_efficiencies_get_spot(void *efficiencies_, int kind, int32_t
 	if (energies != NULL) *energies = e;
 	if (maps != NULL) *maps = m;
 	if (outside != NULL) *outside = o;
+	return 1;
+}
+
+int pc_transmission_efficiencies_get_stderr(void *efficiencies_, size_t *n_energies, double **stderrs, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || stderrs == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_stderr: efficiencies and stderr cannot be NULL");
+		return 0;
+	}
+	if (efficiencies->stderrs == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_stderr: the run was made without POLYCAP_STDERR=1");
+		return 0;
+	}
+	double *d = pc_dup(efficiencies->stderrs, sizeof(double)*efficiencies->n_energies);
+	if (d == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_stderr: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (n_energies != NULL) *n_energies = efficiencies->n_energies;
+	*stderrs = d;
+	return 1;
+}
+
+int pc_transmission_efficiencies_get_moments(void *efficiencies_, int64_t *n_started, uint64_t **sumw_fixed, uint64_t **sumw2_fixed, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_moments: efficiencies cannot be NULL");
+		return 0;
+	}
+	if (efficiencies->sumw2_fixed == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_moments: the run was made without POLYCAP_STDERR=1");
+		return 0;
+	}
+	const size_t bytes = 2*sizeof(uint64_t)*efficiencies->n_energies;
+	uint64_t *a = NULL, *b = NULL;
+	int ok = 1;
+	if (sumw_fixed != NULL) ok = (a = pc_dup(efficiencies->sumw_fixed, bytes)) != NULL;
+	if (sumw2_fixed != NULL && ok) ok = (b = pc_dup(efficiencies->sumw2_fixed, bytes)) != NULL;
+	if (!ok) {
+		free(a); free(b);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_moments: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (n_started != NULL) *n_started = efficiencies->n_started;
+	if (sumw_fixed != NULL) *sumw_fixed = a;
+	if (sumw2_fixed != NULL) *sumw2_fixed = b;
 	return 1;
 }
 

@@ -162,6 +162,17 @@ class TraceContext:
                     i_exit=int(cnt[0]), not_entered=int(cnt[1]), not_transmitted=int(cnt[2]), sum_irefl=int(cnt[3]),
                     failed_slots=int(cnt[4]), launches=int(cnt[5]), i_start=int(cnt[0] + cnt[1] + cnt[2]))
 
+    def moments(self):
+        """Exact sums of the squared exit weights of the last run, made with option "weight_squares" = 1
+        (pc_hip_transmission_moments): uint64 array [n_energies, 2] of (lo, hi) pairs in units of 2^-62, laid out like
+        totals()["sumw_fixed"].  With those and the counters, efficiency_stderr() gives the standard errors."""
+        ne = self.problem.n_energies
+        fx = np.zeros(2 * ne, dtype=np.uint64)
+        st = self._L.pc_hip_transmission_moments(self._h, fx.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_transmission_moments", st)
+        return fx.reshape(ne, 2)
+
     KERNELS = {0: "pc_trace_kernel", 1: "pc_trace_pool_kernel", 2: "pc_trace_producer_kernel", 3: "pc_trace_wave_kernel",
                4: "pc_trace_log_kernel", 5: "pc_leak_kernel"}
 
@@ -328,6 +339,16 @@ class TraceGroup:
                  i_exit=int(cnt[0]), i_start=int(cnt[0] + cnt[1] + cnt[2]), efficiencies=efficiencies(sw, cnt))
         return r
 
+    def moments(self):
+        """The squared exit weights' exact sums of the group's last run (option "weight_squares" = 1), summed over the members with
+        the weights' sums by the run's totals (pc_hip_group_moments): uint64 [n_energies, 2] of (lo, hi) pairs."""
+        ne = self.problem.n_energies
+        fx = np.zeros(2 * ne, dtype=np.uint64)
+        st = self._L.pc_hip_group_moments(self._h, fx.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_group_moments", st)
+        return fx.reshape(ne, 2)
+
 
 SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}
 
@@ -418,3 +439,20 @@ def efficiencies(sum_weights, counters):
 
 def fixed_to_double(lo, hi):
     return float(_cabi.lib().pc_hip_fixed_to_double(int(lo), int(hi)))
+
+
+def efficiency_stderr(sumw_fixed, sumw2_fixed, counters):
+    """Standard error of every efficiency from a run's exact moments (pc_hip_efficiency_stderr, include/polycap-hip.h):
+    sumw_fixed / sumw2_fixed as totals()["sumw_fixed"] and moments() ([n_energies, 2] or flat uint64 (lo, hi) pairs), counters as
+    totals()["counters"].  NaN where fewer than two photons were started."""
+    a = np.ascontiguousarray(sumw_fixed, dtype=np.uint64).reshape(-1)
+    b = np.ascontiguousarray(sumw2_fixed, dtype=np.uint64).reshape(-1)
+    if a.shape != b.shape or a.shape[0] % 2:
+        raise ValueError("efficiency_stderr: sumw_fixed and sumw2_fixed must both hold n_energies (lo, hi) pairs")
+    cnt = np.ascontiguousarray(counters, dtype=np.int64)
+    if cnt.shape[0] < 6:
+        cnt = np.concatenate([cnt, np.zeros(6 - cnt.shape[0], dtype=np.int64)])
+    out = np.zeros(a.shape[0] // 2)
+    _cabi.lib().pc_hip_efficiency_stderr(out.shape[0], a.ctypes.data_as(C.POINTER(C.c_uint64)), b.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         cnt.ctypes.data_as(c_int64_p), dptr(out))
+    return out
