@@ -473,22 +473,6 @@ static int pc_spot_request_parse(struct pc_spot_request *r, size_t n_energies, p
 	return 0;
 }
 
-/* POLYCAP_STDERR: 1 = the result carries a standard error per energy (option "weight_squares", pc_hip_efficiency_stderr); unset or 0 =
- * nothing changes.  Parsed and validated before any device is used; returns -1 with *error set for anything but 0 or 1. */
-static int pc_stderr_request_parse(int *on, polycap_error **error)
-{
-	const char *env = getenv("POLYCAP_STDERR");
-	*on = 0;
-	if (env == NULL || strcmp(env, "0") == 0)
-		return 0;
-	if (strcmp(env, "1") == 0) {
-		*on = 1;
-		return 0;
-	}
-	polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_STDERR=%s: must be 0 or 1", env);
-	return -1;
-}
-
 /* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
 static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 {
@@ -539,7 +523,8 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, in
 	return st;
 }
 
-/* the maps of `spot` in efficiency units into the result */
+/* the maps of `spot` in efficiency units into the result.  A failure after eff->spot was created leaves the maps stored so far
+ * (and the plane distances and energy selection) in it: polycap_transmission_efficiencies_free frees them with the result. */
 static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *spot, const struct pc_spot_request *r, int kind)
 {
 	int32_t dims[4];
@@ -563,13 +548,8 @@ static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *sp
 		sp->window[0] = r->spec.x0; sp->window[1] = r->spec.x1; sp->window[2] = r->spec.y0; sp->window[3] = r->spec.y1;
 	}
 	uint64_t *bins = malloc(sizeof(uint64_t)*n_out*nb), *out = malloc(sizeof(uint64_t)*n_out);
-	sp->maps[kind] = malloc(sizeof(double)*n_out*nb);
-	sp->outside[kind] = malloc(sizeof(double)*n_out);
-	if (bins == NULL || out == NULL || sp->maps[kind] == NULL || sp->outside[kind] == NULL) {
-		free(bins); free(out);
-		return PC_HIP_ERR_MEMORY;
-	}
-	st = pc_hip_spot_read(spot, bins, out, NULL);
+	double *map = malloc(sizeof(double)*n_out*nb), *outside = malloc(sizeof(double)*n_out);
+	st = (bins != NULL && out != NULL && map != NULL && outside != NULL) ? pc_hip_spot_read(spot, bins, out, NULL) : PC_HIP_ERR_MEMORY;
 	for (size_t m = 0; st == PC_HIP_OK && m < n_out; m++) {
 		/* map = efficiency[e] * S_bin / (S_inside + S_outside): a map and its outside part sum to the efficiency */
 		uint64_t total = out[m];
@@ -578,11 +558,169 @@ static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *sp
 		const double eff_e = eff->efficiencies[sp->sel[m % (size_t)dims[1]]];
 		const double tot = (double)total;
 		for (size_t b = 0; b < nb; b++)
-			sp->maps[kind][m*nb + b] = total ? eff_e * (double)bins[m*nb + b] / tot : 0.;
-		sp->outside[kind][m] = total ? eff_e * (double)out[m] / tot : 0.;
+			map[m*nb + b] = total ? eff_e * (double)bins[m*nb + b] / tot : 0.;
+		outside[m] = total ? eff_e * (double)out[m] / tot : 0.;
 	}
-	free(bins);
-	free(out);
+	if (st == PC_HIP_OK) {
+		sp->maps[kind] = map; sp->outside[kind] = outside;
+		map = outside = NULL;
+	}
+	free(bins); free(out); free(map); free(outside);
+	return st;
+}
+
+/* the argument checks of the reference call, in its order: the message of the first one that fails, or NULL */
+static const char *pc_transmission_args_bad(const polycap_source *source, const polycap_progress_monitor *progress_monitor, int n_photons)
+{
+	if (source == NULL)
+		return "source cannot be NULL";
+	if (progress_monitor != NULL)
+		return "progress_monitor must be NULL as polycap_progress_monitor currently has no implementation";
+	if (source->description == NULL)
+		return "description cannot be NULL";
+	if (source->n_energies < 1)
+		return "source->n_energies must be greater than or equal to 1";
+	if (source->energies == NULL)
+		return "source->energies cannot be NULL";
+	for (size_t i = 0; i < source->n_energies; i++)
+		if (source->energies[i] < 1. || source->energies[i] > 100.)
+			return "source->energies[i] must be greater than 1 and less than 100";
+	return n_photons < 1 ? "n_photons must be greater than 1" : NULL;
+}
+
+/* Everything polycap_source_get_transmission_efficiencies takes from the environment, read by pc_run_request_parse before any device
+ * is used.  These are extensions of the reference call, all through the environment so that the signature stays the reference's:
+ *   POLYCAP_HIP_DEVICES=all | i,j,...  the photon loop is sharded over these devices from this one process (the reference's OpenMP
+ *       team, :697-745, becomes a team of GPUs); totals are summed by one RCCL all-reduce (:973-980)
+ *   POLYCAP_IMAGES=0                   histogram-only result: efficiencies and counts, no per-photon planes (at 1e8 photons x 291
+ *       energies the weight plane alone is 233 GB); the start/exit getters then report no events
+ * Numbers that do not parse fall back to their defaults; out-of-range option values fail when the option is set. */
+struct pc_run_request {
+	int timing;                /* POLYCAP_TIMING: stage times on stderr */
+	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
+	struct pc_spot_request spot;
+	int devices[64], n_devices;
+	int keep_images;
+	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
+	int compact;               /* POLYCAP_COMPACT, plain runs only */
+	int have_block_shift;      /* POLYCAP_BLOCK_SHIFT set (one device only) */
+	int64_t block_shift;
+	int rccl;                  /* POLYCAP_RCCL: 0 host sum, 1 RCCL or fail, -1 (unset) RCCL when possible */
+	uint32_t max_attempts;     /* POLYCAP_MAX_ATTEMPTS */
+	int have_seed;             /* POLYCAP_SEED given: seed, else derived from the source */
+	uint64_t seed;
+};
+
+static void pc_run_request_free(struct pc_run_request *r)
+{
+	free(r->spot.energies);
+}
+
+static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_calc, int n_photons, polycap_error **error)
+{
+	memset(r, 0, sizeof(*r));
+	r->timing = getenv("POLYCAP_TIMING") != NULL;
+	const char *stderr_env = getenv("POLYCAP_STDERR");
+	if (stderr_env != NULL && strcmp(stderr_env, "0") != 0 && strcmp(stderr_env, "1") != 0) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_STDERR=%s: must be 0 or 1", stderr_env);
+		return -1;
+	}
+	r->stderr_on = stderr_env != NULL && strcmp(stderr_env, "1") == 0;
+	if (pc_spot_request_parse(&r->spot, ne, error) != 0 || pc_env_devices(r->devices, &r->n_devices, error) != 0)
+		return -1;
+	const char *img_env = getenv("POLYCAP_IMAGES");
+	r->keep_images = !(img_env != NULL && strcmp(img_env, "0") == 0);
+	if (leak_calc && !r->keep_images) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_IMAGES=0 cannot be combined with leak_calc (leak events are per-photon data)");
+		return -1;
+	}
+	/* big plain runs are traced in four parts so that the images of a finished part cross PCIe while the next part runs */
+	r->run_parts = (!leak_calc && r->keep_images && n_photons >= 2000000) ? (int)pc_env_u64("POLYCAP_RUN_PARTS", 4, NULL) : 1;
+	/* Plain runs store their exit photons in the order of completion (option "compact_images": coalesced plane stores, blocks
+	 * copied to the host while the kernel runs); the reference's own order is the order in which randomly seeded threads fill
+	 * the arrays.  POLYCAP_COMPACT=0 keeps every photon at the position of its slot (reproducible order for a given POLYCAP_SEED). */
+	const char *compact_env = getenv("POLYCAP_COMPACT");
+	r->compact = !(compact_env != NULL && strcmp(compact_env, "0") == 0) && !leak_calc;
+	r->have_block_shift = getenv("POLYCAP_BLOCK_SHIFT") != NULL;
+	r->block_shift = (int64_t)pc_env_u64("POLYCAP_BLOCK_SHIFT", 18, NULL);
+	const char *rccl = getenv("POLYCAP_RCCL");
+	r->rccl = (rccl != NULL && *rccl != '\0') ? atoi(rccl) : -1;
+	r->max_attempts = (uint32_t)pc_env_u64("POLYCAP_MAX_ATTEMPTS", 1u << 20, NULL);
+	r->seed = pc_env_u64("POLYCAP_SEED", 0, &r->have_seed);
+	return 0;
+}
+
+/* where a run goes: one device or a device group, exactly one of them set (both belong to the source's context cache) */
+struct pc_target {
+	pc_hip_ctx *ctx;
+	pc_hip_group *group;
+};
+
+/* Trace stage: with POLYCAP_SPOT the maps are made first (exit photons; leak runs also extleak and intleak), then the options are
+ * set and the run is enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the totals and moments, and added
+ * every range to spot[0]. */
+static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak_calc, uint64_t seed, int64_t n_photons, size_t ne,
+	pc_hip_spot *spot[3], int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
+{
+	int st = PC_HIP_OK;
+	int64_t chunk = 0;
+	if (r->spot.set) {
+		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++)
+			st = t.group != NULL ? pc_hip_group_spot_create(t.group, &r->spot.spec, &spot[kind]) : pc_hip_spot_create(t.ctx, &r->spot.spec, &spot[kind]);
+		/* POLYCAP_IMAGES=0 with spot maps is chunked on one device only: a group traces the whole run at once */
+		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
+			uint64_t total_b = 0;
+			st = pc_hip_device_memory(t.ctx, NULL, &total_b);
+			chunk = (int64_t)(r->spot.share * (double)total_b / ((17. + (double)ne) * 8.));
+			if (chunk < 1)
+				chunk = 1;
+		}
+	}
+	/* the context or group is cached, so every option is set on every call */
+	const struct { const char *name; int64_t value; int set; } opt[] = {
+		{ "run_parts", r->run_parts, 1 },
+		{ "weight_squares", r->stderr_on, 1 },
+		{ "compact_images", r->compact, 1 },
+		{ "block_shift", r->block_shift, r->have_block_shift && t.group == NULL },    /* one device only */
+		{ "plane_images", leak_calc ? 0 : 1, 1 },      /* the result object wants planes: let the kernel write them */
+	};
+	for (size_t k = 0; k < sizeof(opt)/sizeof(opt[0]) && st == PC_HIP_OK; k++)
+		if (opt[k].set)
+			st = t.group != NULL ? pc_hip_group_set_option(t.group, opt[k].name, opt[k].value) : pc_hip_set_option(t.ctx, opt[k].name, opt[k].value);
+	if (st != PC_HIP_OK)
+		return st;
+	if (chunk > 0 && chunk < n_photons) {
+		*chunked = 1;
+		return pc_spot_chunked(t.ctx, spot[0], seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
+	}
+	/* POLYCAP_SPOT: the run keeps its exit data on the device for the maps even with POLYCAP_IMAGES=0 (then nothing is copied back) */
+	const int device_images = r->keep_images || r->spot.set;
+	if (leak_calc)
+		return t.group != NULL ? pc_hip_group_run_leak(t.group, seed, n_photons, r->max_attempts, 1)
+		                       : pc_hip_transmission_run_leak(t.ctx, seed, 0, n_photons, r->max_attempts, 1);
+	return t.group != NULL ? pc_hip_group_run(t.group, seed, n_photons, r->max_attempts, device_images)
+	                       : pc_hip_transmission_run(t.ctx, seed, 0, n_photons, r->max_attempts, device_images);
+}
+
+/* Image stage, while the kernel is still running; *t_prefault = the time the prefault ended */
+static int pc_fetch_images(struct pc_target t, polycap_transmission_efficiencies *eff, int64_t n_photons, double *t_prefault)
+{
+	pc_transeff_prefault(eff, (size_t)n_photons);    /* the kernel is running: fault the result pages in meanwhile */
+	*t_prefault = pc_now_ms();
+	pc_hip_images dst;
+	pc_transeff_plane_pointers(eff, &dst);
+	if (t.group != NULL)
+		return pc_hip_group_images(t.group, &dst);
+	/* One device only: a result in one slab stays pinned while it lives and in the pool after it (pc_transeff.c); planes of their
+	 * own are pinned for the call only */
+	const int keep_pinned = eff->images->slab != NULL;
+	if (keep_pinned)
+		(void)pc_hip_set_option(t.ctx, "keep_pinned", 1);
+	const int st = pc_hip_transmission_images(t.ctx, 0, n_photons, &dst);    /* block by block behind the kernel (a leak run: after it) */
+	if (keep_pinned) {
+		(void)pc_hip_set_option(t.ctx, "keep_pinned", 0);
+		pc_transeff_planes_pinned(eff);      /* also after a failure: what the fetch pinned stays pinned until the slab is freed */
+	}
 	return st;
 }
 
@@ -590,262 +728,122 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	bool leak_calc, polycap_progress_monitor *progress_monitor, polycap_error **error)
 {
 	(void)max_threads; /* host-thread cap in the reference (:492-493); the photon loop runs on the GPU here */
-	if (source == NULL) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: source cannot be NULL");
-		return NULL;
-	}
-	if (progress_monitor != NULL) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: progress_monitor must be NULL as polycap_progress_monitor currently has no implementation");
-		return NULL;
-	}
-	polycap_description *description = source->description;
-	if (description == NULL) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: description cannot be NULL");
-		return NULL;
-	}
-	if (source->n_energies < 1) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: source->n_energies must be greater than or equal to 1");
-		return NULL;
-	}
-	if (source->energies == NULL) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: source->energies cannot be NULL");
-		return NULL;
-	}
-	for (size_t i = 0; i < source->n_energies; i++) {
-		if (source->energies[i] < 1. || source->energies[i] > 100.) {
-			polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: source->energies[i] must be greater than 1 and less than 100");
-			return NULL;
-		}
-	}
-	if (n_photons < 1) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: n_photons must be greater than 1");
+	const char *bad = pc_transmission_args_bad(source, progress_monitor, n_photons);
+	if (bad != NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: %s", bad);
 		return NULL;
 	}
 
+	/* everything owned starts empty; every failure below sets the error once and goes to `out`, which frees what is set */
 	const size_t ne = source->n_energies;
-	const int timing = getenv("POLYCAP_TIMING") != NULL;
-	int stderr_on = 0;
-	if (pc_stderr_request_parse(&stderr_on, error) != 0)
-		return NULL;
-	struct pc_spot_request spot_req;
-	if (pc_spot_request_parse(&spot_req, ne, error) != 0)
-		return NULL;
-	/* Extensions of the reference call, all through the environment so that the signature stays the reference's:
-	 *   POLYCAP_HIP_DEVICES=all | i,j,...  the photon loop is sharded over these devices from this one process (the
-	 *       reference's OpenMP team, :697-745, becomes a team of GPUs); totals are summed by one RCCL all-reduce (:973-980)
-	 *   POLYCAP_IMAGES=0                   histogram-only result: efficiencies and counts, no per-photon planes (at 1e8
-	 *       photons x 291 energies the weight plane alone is 233 GB); the start/exit getters then report no events */
-	int devices[64], n_devices = 0;
-	if (pc_env_devices(devices, &n_devices, error) != 0) {
-		free(spot_req.energies);
-		return NULL;
-	}
-	const char *img_env = getenv("POLYCAP_IMAGES");
-	const int keep_images = !(img_env != NULL && strcmp(img_env, "0") == 0);
-	if (leak_calc && !keep_images) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_IMAGES=0 cannot be combined with leak_calc (leak events are per-photon data)");
-		free(spot_req.energies);
-		return NULL;
-	}
-	double t_stage[8];
+	struct pc_run_request req;
+	struct pc_target t = { NULL, NULL };
+	polycap_transmission_efficiencies *eff = NULL, *result = NULL;
+	double *sum_weights = NULL;
+	uint64_t *sum_fixed = NULL, *sum_fixed2 = NULL;      /* the exact moments A and B; B and the result's copy only with POLYCAP_STDERR */
+	pc_hip_spot *spot[3] = { NULL, NULL, NULL };         /* exit photons, extleak, intleak */
+	int64_t counters[6] = { 0, 0, 0, 0, 0, 0 };
+	int status = PC_HIP_OK, chunked = 0, reduced_by = 0;      /* a failed HIP call: its error is set at `out` */
+	double t_stage[6];
+
+	if (pc_run_request_parse(&req, ne, leak_calc, n_photons, error) != 0)
+		goto out;
 	t_stage[0] = pc_now_ms();
-	polycap_transmission_efficiencies *eff = pc_transeff_alloc(source, keep_images ? (size_t)n_photons : 0, 0, "polycap_source_get_transmission_efficiencies", error);
-	double *sum_weights = malloc(sizeof(double)*ne);
-	/* POLYCAP_STDERR: the exact moments of the run (A = weights, B = squared weights), kept by the result */
-	uint64_t *sum_fixed = malloc(sizeof(uint64_t)*2*ne), *sum_fixed2 = stderr_on ? malloc(sizeof(uint64_t)*2*ne) : NULL;
-	if (eff != NULL && stderr_on) {
-		eff->sumw_fixed = sum_fixed; eff->sumw2_fixed = sum_fixed2;      /* freed with the result from here on */
-		sum_fixed = NULL; sum_fixed2 = NULL;
-	}
-	if (eff == NULL || sum_weights == NULL || (stderr_on ? (eff->sumw_fixed == NULL || eff->sumw2_fixed == NULL) : sum_fixed == NULL)) {
-		free(sum_fixed);
-		free(sum_fixed2);
-		if (eff != NULL)
-			polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for efficiencies -> %s", strerror(errno));
-		free(sum_weights);
-		free(spot_req.energies);
-		polycap_transmission_efficiencies_free(eff);
-		return NULL;
+	eff = pc_transeff_alloc(source, req.keep_images ? (size_t)n_photons : 0, 0, "polycap_source_get_transmission_efficiencies", error);
+	if (eff == NULL)
+		goto out;
+	sum_weights = malloc(sizeof(double)*ne);
+	sum_fixed = malloc(sizeof(uint64_t)*2*ne);
+	sum_fixed2 = req.stderr_on ? malloc(sizeof(uint64_t)*2*ne) : NULL;
+	if (sum_weights == NULL || sum_fixed == NULL || (req.stderr_on && sum_fixed2 == NULL)) {
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for efficiencies -> %s", strerror(errno));
+		goto out;
 	}
 
-	pc_hip_ctx *ctx = NULL;
-	pc_hip_group *group = NULL;
-	if (n_devices > 1 || (n_devices > 0 && !leak_calc))      /* leak runs are sharded like plain runs (reference :744-884, 925-1032) */
-		group = pc_group_for(&source->cache, description, ne, source->energies, source, n_devices, devices, "polycap_source_get_transmission_efficiencies", error);
+	if (req.n_devices > 1 || (req.n_devices > 0 && !leak_calc))      /* leak runs are sharded like plain runs (reference :744-884, 925-1032) */
+		t.group = pc_group_for(&source->cache, source->description, ne, source->energies, source, req.n_devices, req.devices,
+		                       "polycap_source_get_transmission_efficiencies", error);
 	else      /* a one-entry list selects the device of a leak run; none: POLYCAP_HIP_DEVICE, default 0 */
-		ctx = pc_ctx_for_device(&source->cache, description, ne, source->energies, source, n_devices >= 1 ? devices[0] : -1,
-		                        "polycap_source_get_transmission_efficiencies", error);
-	if (ctx == NULL && group == NULL) {
-		free(sum_weights);
-		free(sum_fixed);
-		free(spot_req.energies);
-		polycap_transmission_efficiencies_free(eff);
-		return NULL;
-	}
+		t.ctx = pc_ctx_for_device(&source->cache, source->description, ne, source->energies, source, req.n_devices >= 1 ? req.devices[0] : -1,
+		                          "polycap_source_get_transmission_efficiencies", error);
+	if (t.ctx == NULL && t.group == NULL)
+		goto out;
 	t_stage[1] = pc_now_ms();
-	int have_seed = 0;
-	uint64_t seed = pc_env_u64("POLYCAP_SEED", 0, &have_seed);
-	if (!have_seed)
-		seed = source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
+	/* the run index moves only once a device was obtained: the seeds of all later runs depend on it */
+	const uint64_t seed = req.have_seed ? req.seed : source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
 	source->run_index++;
-	uint32_t max_attempts = (uint32_t)pc_env_u64("POLYCAP_MAX_ATTEMPTS", 1u << 20, NULL);
 
-	int64_t counters[6] = {0, 0, 0, 0, 0, 0};
-	int status = PC_HIP_OK;
-	/* POLYCAP_SPOT: the run keeps its exit data on the device for the maps even with POLYCAP_IMAGES=0 (then nothing is copied back) */
-	const int device_images = keep_images || spot_req.set;
-	pc_hip_spot *spot[3] = {NULL, NULL, NULL};      /* exit photons, extleak, intleak */
-	int64_t chunk = 0;
-	if (spot_req.set) {
-		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK; kind++)
-			status = (group != NULL) ? pc_hip_group_spot_create(group, &spot_req.spec, &spot[kind]) : pc_hip_spot_create(ctx, &spot_req.spec, &spot[kind]);
-		if (status == PC_HIP_OK && group == NULL && !keep_images && !leak_calc) {
-			uint64_t total_b = 0;
-			status = pc_hip_device_memory(ctx, NULL, &total_b);
-			chunk = (int64_t)(spot_req.share * (double)total_b / ((17. + (double)ne) * 8.));
-			if (chunk < 1)
-				chunk = 1;
-		}
-	}
-	/* big plain runs are traced in four parts so that the images of a finished part cross PCIe while the next part runs */
-	const int parts = (!leak_calc && keep_images && n_photons >= 2000000) ? (int)pc_env_u64("POLYCAP_RUN_PARTS", 4, NULL) : 1;
-	/* Plain runs store their exit photons in the order of completion (option "compact_images": coalesced plane stores, blocks
-	 * copied to the host while the kernel runs); the reference's own order is the order in which randomly seeded threads fill
-	 * the arrays.  POLYCAP_COMPACT=0 keeps every photon at the position of its slot (reproducible order for a given POLYCAP_SEED). */
-	const char *compact_env = getenv("POLYCAP_COMPACT");
-	const int compact = !(compact_env != NULL && strcmp(compact_env, "0") == 0) && !leak_calc;
-	const int chunked = status == PC_HIP_OK && chunk > 0 && chunk < (int64_t)n_photons;
-	if (status != PC_HIP_OK) {
-		/* the map could not be made: reported below */
-	} else if (group != NULL) {
-		status = pc_hip_group_set_option(group, "run_parts", parts);
-		if (status == PC_HIP_OK)
-			status = pc_hip_group_set_option(group, "weight_squares", stderr_on);     /* the group is cached: set either way */
-		if (status == PC_HIP_OK)
-			status = pc_hip_group_set_option(group, "compact_images", compact);
-		if (status == PC_HIP_OK)
-			status = pc_hip_group_set_option(group, "plane_images", leak_calc ? 0 : 1);
-		if (status == PC_HIP_OK)
-			status = leak_calc ? pc_hip_group_run_leak(group, seed, n_photons, max_attempts, 1)
-			                   : pc_hip_group_run(group, seed, n_photons, max_attempts, device_images);
-	} else {
-		status = pc_hip_set_option(ctx, "run_parts", parts);
-		if (status == PC_HIP_OK)
-			status = pc_hip_set_option(ctx, "weight_squares", stderr_on);     /* the context is cached: set either way */
-		if (status == PC_HIP_OK)
-			status = pc_hip_set_option(ctx, "compact_images", compact);
-		if (status == PC_HIP_OK && getenv("POLYCAP_BLOCK_SHIFT") != NULL)
-			status = pc_hip_set_option(ctx, "block_shift", (int64_t)pc_env_u64("POLYCAP_BLOCK_SHIFT", 18, NULL));
-		if (status == PC_HIP_OK)
-			status = pc_hip_set_option(ctx, "plane_images", leak_calc ? 0 : 1);   /* the result object wants planes: let the kernel write them */
-		if (status == PC_HIP_OK && chunked)
-			status = pc_spot_chunked(ctx, spot[0], seed, n_photons, chunk, max_attempts, ne, sum_weights, counters,
-			                         stderr_on ? eff->sumw_fixed : sum_fixed, eff->sumw2_fixed);
-		else if (status == PC_HIP_OK)
-			status = leak_calc ? pc_hip_transmission_run_leak(ctx, seed, 0, n_photons, max_attempts, 1)
-			                   : pc_hip_transmission_run(ctx, seed, 0, n_photons, max_attempts, device_images);
-	}
-	t_stage[2] = pc_now_ms();
-	t_stage[3] = t_stage[2];
-	if (status == PC_HIP_OK && keep_images) {
-		pc_transeff_prefault(eff, (size_t)n_photons);    /* the kernel is running: fault the result pages in meanwhile */
-		t_stage[3] = pc_now_ms();
-		pc_hip_images dst;
-		pc_transeff_plane_pointers(eff, &dst);
-		/* a result in one slab stays pinned while it lives and in the pool after it (pc_transeff.c); planes of their own are
-		 * pinned for the call only */
-		const int keep_pinned = (group == NULL && eff->images->slab != NULL);
-		if (keep_pinned)
-			(void)pc_hip_set_option(ctx, "keep_pinned", 1);
-		status = (group != NULL) ? pc_hip_group_images(group, &dst)
-		                         : pc_hip_transmission_images(ctx, 0, n_photons, &dst);    /* block by block behind the kernel (a leak run: after it) */
-		if (keep_pinned) {
-			(void)pc_hip_set_option(ctx, "keep_pinned", 0);
-			pc_transeff_planes_pinned(eff);      /* also after a failure: what the fetch pinned stays pinned until the slab is freed */
-		}
-	}
+	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
+	t_stage[2] = t_stage[3] = pc_now_ms();
+	if (status == PC_HIP_OK && req.keep_images)
+		status = pc_fetch_images(t, eff, n_photons, &t_stage[3]);
 	t_stage[4] = pc_now_ms();
-	int reduced_by = 0;
-	if (status == PC_HIP_OK && !chunked) {
-		if (group != NULL) {
-			const char *r = getenv("POLYCAP_RCCL");      /* 0: host sum, 1: RCCL or fail; default: RCCL when possible */
-			status = pc_hip_group_totals(group, (r != NULL && *r != '\0') ? atoi(r) : -1, sum_weights, counters, eff->sumw_fixed, &reduced_by, NULL);
-			if (status == PC_HIP_OK && stderr_on)
-				status = pc_hip_group_moments(group, eff->sumw2_fixed);
-		} else {
-			status = pc_hip_transmission_wait(ctx, NULL);
-			if (status == PC_HIP_OK)
-				status = pc_hip_transmission_totals(ctx, sum_weights, counters, eff->sumw_fixed);
-			if (status == PC_HIP_OK && stderr_on)
-				status = pc_hip_transmission_moments(ctx, eff->sumw2_fixed);
-		}
+	if (status == PC_HIP_OK && !chunked && t.group != NULL) {
+		status = pc_hip_group_totals(t.group, req.rccl, sum_weights, counters, req.stderr_on ? sum_fixed : NULL, &reduced_by, NULL);
+		if (status == PC_HIP_OK && req.stderr_on)
+			status = pc_hip_group_moments(t.group, sum_fixed2);
+	} else if (status == PC_HIP_OK && !chunked) {
+		status = pc_hip_transmission_wait(t.ctx, NULL);      /* one device: the run has finished before its totals are read */
+		if (status == PC_HIP_OK)
+			status = pc_hip_transmission_totals(t.ctx, sum_weights, counters, req.stderr_on ? sum_fixed : NULL);
+		if (status == PC_HIP_OK && req.stderr_on)
+			status = pc_hip_transmission_moments(t.ctx, sum_fixed2);
 	}
 	t_stage[5] = pc_now_ms();
-	if (timing)
+	if (req.timing)
 		fprintf(stderr, "polycap timing [ms]: alloc+context %.1f, enqueue %.1f, prefault %.1f, images (incl. waiting for the kernel) %.1f, totals %.1f%s\n",
 			t_stage[1] - t_stage[0], t_stage[2] - t_stage[1], t_stage[3] - t_stage[2], t_stage[4] - t_stage[3], t_stage[5] - t_stage[4],
-			group != NULL ? (reduced_by ? " (devices summed by RCCL all-reduce)" : " (devices summed on the host)") : "");
+			t.group != NULL ? (reduced_by ? " (devices summed by RCCL all-reduce)" : " (devices summed on the host)") : "");
 	if (status == PC_HIP_OK && leak_calc)
-		status = pc_transeff_fetch_leaks(eff, ctx, group);      /* reference :925-1032 */
-	for (int kind = chunked ? 1 : 0; kind <= 2 && status == PC_HIP_OK; kind++)
+		status = pc_transeff_fetch_leaks(eff, t.ctx, t.group);      /* reference :925-1032 */
+	for (int kind = chunked ? 1 : 0; kind <= 2 && status == PC_HIP_OK; kind++)      /* a chunked run has added its exit map */
 		if (spot[kind] != NULL)
 			status = pc_hip_spot_add(spot[kind], kind);
-	if (status != PC_HIP_OK) {
-		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
-		for (int kind = 0; kind <= 2; kind++)
-			pc_hip_spot_destroy(spot[kind]);
-		free(spot_req.energies);
-		free(sum_weights);
-		free(sum_fixed);
-		polycap_transmission_efficiencies_free(eff);
-		return NULL;
-	}
+	if (status != PC_HIP_OK)
+		goto out;
 
 	/* totals, summary lines and efficiency formula of the reference, :1055-1076 */
+	const polycap_description *description = source->description;
 	int64_t sum_iexit = counters[0], sum_not_entered = counters[1], sum_not_transmitted = counters[2], sum_irefl = counters[3];
 	printf("Average number of reflections: %lf, Simulated photons: %" PRId64 "\n", (double)sum_irefl/n_photons, sum_iexit+sum_not_entered+sum_not_transmitted);
 	printf("Open area Calculated: %lf, Simulated: %lf\n",
 		((pc_n_shells(description->n_cap)+0.5)*6.)*((pc_n_shells(description->n_cap)+0.5)*6.)/12.*(description->profile->cap[0]*description->profile->cap[0]*M_PI)/(3.*sin(M_PI/3)*description->profile->ext[0]*description->profile->ext[0]),
 		(double)(sum_iexit+sum_not_transmitted)/(sum_iexit+sum_not_entered+sum_not_transmitted));
 	printf("iexit: %" PRId64 ", no enter: %" PRId64 ", no trans: %" PRId64 "\n", sum_iexit, sum_not_entered, sum_not_transmitted);
-
 	pc_transeff_finish(eff, sum_weights, counters);
 	eff->synthetic_constants = source->cache.synthetic;
-	if (stderr_on) {
-		eff->n_started = sum_iexit + sum_not_entered + sum_not_transmitted;
+	for (int kind = 0; kind <= 2 && status == PC_HIP_OK; kind++)
+		if (spot[kind] != NULL)
+			status = pc_spot_store(eff, spot[kind], &req.spot, kind);
+	if (status != PC_HIP_OK)
+		goto out;
+	if (req.stderr_on) {      /* without POLYCAP_STDERR the result keeps no moments, and its stderr and moment getters fail */
+		eff->n_started = counters[0] + counters[1] + counters[2];
 		eff->stderrs = malloc(sizeof(double)*ne);
 		if (eff->stderrs == NULL) {
 			polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_source_get_transmission_efficiencies: could not allocate memory for the standard errors -> %s", strerror(errno));
-			for (int kind = 0; kind <= 2; kind++)
-				pc_hip_spot_destroy(spot[kind]);
-			free(spot_req.energies);
-			free(sum_weights);
-			free(sum_fixed);
-			polycap_transmission_efficiencies_free(eff);
-			return NULL;
+			goto out;
 		}
-		pc_hip_efficiency_stderr(ne, eff->sumw_fixed, eff->sumw2_fixed, counters, eff->stderrs);
+		pc_hip_efficiency_stderr(ne, sum_fixed, sum_fixed2, counters, eff->stderrs);
+		eff->sumw_fixed = sum_fixed; eff->sumw2_fixed = sum_fixed2;      /* the result is complete: it owns them from here on */
+		sum_fixed = sum_fixed2 = NULL;
 	}
-	if (spot_req.set) {
-		for (int kind = 0; kind <= 2; kind++) {
-			if (spot[kind] != NULL && status == PC_HIP_OK)
-				status = pc_spot_store(eff, spot[kind], &spot_req, kind);
-			pc_hip_spot_destroy(spot[kind]);
-		}
-		free(spot_req.energies);
-		if (status != PC_HIP_OK) {
-			pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
-			free(sum_weights);
-			free(sum_fixed);
-			polycap_transmission_efficiencies_free(eff);
-			return NULL;
-		}
-	}
-	if (!keep_images)
+	if (!req.keep_images)
 		eff->images->i_exit = 0;     /* no per-photon planes were kept: the exit/start getters report no events */
+	result = eff;
+	eff = NULL;
+
+out:
+	if (status != PC_HIP_OK)
+		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
+	for (int kind = 0; kind <= 2; kind++)
+		pc_hip_spot_destroy(spot[kind]);
+	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);
-	return eff;
+	free(sum_fixed2);
+	polycap_transmission_efficiencies_free(eff);
+	return result;
 }
 
 void polycap_source_free(polycap_source *source)
