@@ -288,6 +288,53 @@ POLYCAP_EXTERN int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t 
 POLYCAP_EXTERN int pc_hip_spot_reset(pc_hip_spot *spot);
 /* dims = {n_planes, n_selected, ny, nx}; *wide (optional) = 1 when the map accumulates with energies across lanes, 0 in LDS tiles */
 POLYCAP_EXTERN int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide);
+/* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
+ * a focusing optic) in one launch, with exact totals per point.
+ *
+ * A scan has P = n_points points, each a source position (d_source, src_shiftx, src_shifty); every other source field (size,
+ * divergence, polarisation) and the optic are the context's problem's.  Every point gets n_per_point slots and the scan one
+ * max_attempts (0 is taken as 1).  Slot j of point k -- flat index i = k*n_per_point + j -- is traced exactly like slot slot0 + j
+ * of a source run: its attempts use the Philox stream (seed, slot0 + j, attempt), and it stops at the first transmitted photon
+ * or after max_attempts attempts.  The guarantee: for every point k the scan's counters[6], sumw_fixed and (option
+ * "weight_squares") sumw2_fixed are bit-identical to those of pc_hip_transmission_run(ctx_k, seed, slot0, n_per_point,
+ * max_attempts, 0) -- read whatever pc_hip_transmission_totals returns -- where ctx_k is a context whose problem equals the
+ * scan's but for point k's three fields.  Consequences:
+ *   - common random numbers: all points use the same streams (as separate runs with one seed do), so neighbouring points are
+ *     positively correlated and curves come out smooth; each point's standard error on its own is still right;
+ *   - slots that exhaust max_attempts are no error in a scan: counters[4] reports them per point.  With max_attempts = 1 a point
+ *     is a budget of exactly n_per_point started photons.  sum(w) / (counters[0] + counters[1] + counters[2]) stays a
+ *     consistent estimator of the efficiency under this stopping rule (Wald's identity), so the efficiency and standard-error
+ *     formulas apply row by row (pc_hip_scan_efficiencies);
+ *   - a point where nothing entered a capillary has efficiency 0 (pc_hip_efficiencies would divide by zero there).
+ * A scan is not a run: the last run's totals, moments, images, records, slot ids, leak events and what pc_hip_spot_add reads
+ * stay as they were.  The scan is enqueued on the context's stream behind every launch of the last run (also when that run was
+ * cut into parts on two streams) and keeps buffers of its own; a scan call waits for the context's previous scan first.
+ * Scans with more than 8 energies use the immediate weight sweep (option "batch_reflections" 0): same results, slower than the
+ * logging kernel.  Invalid arguments give PC_HIP_ERR_INVALID with a message that names the function and the field. */
+typedef struct { double d_source, src_shiftx, src_shifty; } pc_hip_scan_point;
+/* host only: d_source > 0 and finite, finite shifts, n_points >= 1, n_per_point >= 1, n_points * n_per_point fits in int64 */
+POLYCAP_EXTERN int pc_hip_scan_validate(const pc_hip_scan_point *points, int64_t n_points, int64_t n_per_point);
+/* traces the flat indices [first, first + count) of the scan (1 <= count; slot0 >= 0 and slot0 + n_per_point fits in int64);
+ * several calls over ranges that cut the flat range into pieces add up to the whole scan, exactly */
+POLYCAP_EXTERN int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_scan_point *points, int64_t n_points,
+	int64_t n_per_point, int64_t first, int64_t count, uint32_t max_attempts);
+/* waits for the last scan call; *kernel_ms (optional) = its kernel time */
+POLYCAP_EXTERN int pc_hip_scan_wait(pc_hip_ctx *ctx, float *kernel_ms);
+/* waits; totals of the last scan call, per point: counters [P][6] as pc_hip_transmission_totals, sumw_fixed [P][2*n_energies] and
+ * sumw2_fixed [P][2*n_energies] (the scan must have been made with option "weight_squares") as (lo, hi) pairs; any may be NULL.
+ * Points outside the call's range have zero totals. */
+POLYCAP_EXTERN int pc_hip_scan_totals(pc_hip_ctx *ctx, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed);
+/* host only, row by row: efficiencies [P][n_energies] as pc_hip_efficiencies, 0 where counters[0] + counters[2] == 0; with
+ * sumw2_fixed and stderr_ (both or neither) the standard errors of pc_hip_efficiency_stderr */
+POLYCAP_EXTERN void pc_hip_scan_efficiencies(size_t n_energies, int64_t n_points, const int64_t *counters, const uint64_t *sumw_fixed,
+	const uint64_t *sumw2_fixed, double *efficiencies, double *stderr_);
+/* the flat range [0, n_points * n_per_point) split over the group's members in contiguous pieces; the totals are the members'
+ * added exactly on the host (the same bits as one device); *kernel_ms (optional) of pc_hip_group_scan_wait = the longest member */
+POLYCAP_EXTERN int pc_hip_group_scan_run(pc_hip_group *group, uint64_t seed, int64_t slot0, const pc_hip_scan_point *points,
+	int64_t n_points, int64_t n_per_point, uint32_t max_attempts);
+POLYCAP_EXTERN int pc_hip_group_scan_wait(pc_hip_group *group, float *kernel_ms);
+POLYCAP_EXTERN int pc_hip_group_scan_totals(pc_hip_group *group, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed);
+
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 

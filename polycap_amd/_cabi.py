@@ -209,6 +209,23 @@ def lib():
     L.pc_hip_spot_info.restype = C.c_int
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
+    u64p = P(C.c_uint64)
+    L.pc_hip_scan_validate.argtypes = [c_double_p, C.c_int64, C.c_int64]     # points: [P, 3] doubles = pc_hip_scan_point[P]
+    L.pc_hip_scan_validate.restype = C.c_int
+    L.pc_hip_scan_run.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, c_double_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32]
+    L.pc_hip_scan_run.restype = C.c_int
+    L.pc_hip_scan_wait.argtypes = [C.c_void_p, P(C.c_float)]
+    L.pc_hip_scan_wait.restype = C.c_int
+    L.pc_hip_scan_totals.argtypes = [C.c_void_p, c_int64_p, u64p, u64p]
+    L.pc_hip_scan_totals.restype = C.c_int
+    L.pc_hip_scan_efficiencies.argtypes = [C.c_size_t, C.c_int64, c_int64_p, u64p, u64p, c_double_p, c_double_p]
+    L.pc_hip_scan_efficiencies.restype = None
+    L.pc_hip_group_scan_run.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, c_double_p, C.c_int64, C.c_int64, C.c_uint32]
+    L.pc_hip_group_scan_run.restype = C.c_int
+    L.pc_hip_group_scan_wait.argtypes = [C.c_void_p, P(C.c_float)]
+    L.pc_hip_group_scan_wait.restype = C.c_int
+    L.pc_hip_group_scan_totals.argtypes = [C.c_void_p, c_int64_p, u64p, u64p]
+    L.pc_hip_group_scan_totals.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

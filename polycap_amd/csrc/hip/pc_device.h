@@ -312,6 +312,107 @@ PC_HD void pc_sample_photon(const pc_params &Pm, uint64_t seed, uint64_t slot, u
 	pc_norm3(s.ex, s.ey, s.ez);
 }
 
+/* pc_sample_photon_at takes the source's distance and shifts as arguments (a scan's point, pc_scan_point); every other field
+ * comes from Pm.  The same arithmetic as pc_sample_photon, line by line; a copy rather than a common body, so that the source
+ * runs' kernels stay exactly as they were compiled before scans existed (tests/test_scan_cpu.py checks the copy). */
+template <bool GENERIC>
+PC_HD void pc_sample_photon_at(const pc_params &Pm, double d_source, double src_shiftx, double src_shifty,
+                               uint64_t seed, uint64_t slot, uint32_t attempt, pc_start &s)
+{
+	pc_rng g;
+	pc_rng_init(g, seed, slot, attempt);
+	double r = pc_rng_uniform(g);
+	double cphi, sphi;
+	if (GENERIC) {
+		double phi = atan(Pm.src_y/Pm.src_x * tan(2.0*PC_PI*r/4.));
+		r = pc_rng_uniform(g);
+		if ((r >= 0.25) && (r < 0.5)) phi = PC_PI - phi;
+		if ((r >= 0.5) && (r < 0.75)) phi = PC_PI + phi;
+		if (r >= 0.75) phi = -1.0 * phi;
+		cphi = cos(phi); sphi = sin(phi);
+	} else {
+		double phi = 2.0*PC_PI*r/4.;
+		pc_sincos_quadrant(phi, sphi, cphi);
+		r = pc_rng_uniform(g);
+		/* phi -> pi-phi, pi+phi, -phi : :57-62 */
+		if ((r >= 0.25) && (r < 0.75)) cphi = -cphi;
+		if (r >= 0.5) sphi = -sphi;
+	}
+	double max_rad = Pm.src_x*Pm.src_y / sqrt((Pm.src_y*cphi)*(Pm.src_y*cphi) + (Pm.src_x*sphi)*(Pm.src_x*sphi));
+	r = pc_rng_uniform(g);
+	double sr = sqrt(r);
+	s.srcx = sr * max_rad * cphi + src_shiftx;
+	s.srcy = sr * max_rad * sphi + src_shifty;
+	if (Pm.uniform_illum) {
+		/* :74-96 */
+		if (Pm.mono) {
+			r = pc_rng_uniform(g);
+			s.x = (2.*r-1.) * Pm.cap0;
+			r = pc_rng_uniform(g);
+			s.y = (2.*r-1.) * Pm.cap0;
+		} else {
+			int outside;
+			do {
+				r = pc_rng_uniform(g);
+				s.x = (2.*r-1.) * Pm.ext0;
+				r = pc_rng_uniform(g);
+				s.y = (2.*r-1.) * Pm.ext0;
+				outside = pc_outside_hex(Pm.ext0, s.x, s.y);
+			} while (outside && g.d < 4096u); /* the reference loops unbounded; acceptance is ~65 % per try */
+		}
+		s.dx = s.x - s.srcx;
+		s.dy = s.y - s.srcy;
+		s.dz = d_source;
+	} else {
+		/* :97-108 */
+		r = pc_rng_uniform(g);
+		s.dx = Pm.src_sigx * (1.-2.*fabs(r));
+		r = pc_rng_uniform(g);
+		s.dy = Pm.src_sigy * (1.-2.*fabs(r));
+		s.dz = 1.;
+		s.x = s.srcx + s.dx * d_source / s.dz;
+		s.y = s.srcy + s.dy * d_source / s.dz;
+	}
+	s.z = 0.;
+	pc_norm3(s.dx, s.dy, s.dz);
+	/* :114-137 polarisation */
+	r = pc_rng_uniform(g);
+	double e0x, e0y;
+	if (fabs(r) <= Pm.frac_hor_pol) { e0x = 1.; e0y = 0.; } else { e0x = 0.; e0y = 1.; }
+	double cosalpha = e0x*s.dx + e0y*s.dy;
+	/* c_ae = 1/sin(acos(c)), c_be = -c_ae*c */
+	double c_ae = 1.0 / sqrt(1.0 - cosalpha*cosalpha);
+	double c_be = -1.*c_ae*cosalpha;
+	s.ex = e0x * c_ae + s.dx * c_be;
+	s.ey = e0y * c_ae + s.dy * c_be;
+	s.ez = s.dz * c_be;
+	pc_norm3(s.ex, s.ey, s.ez);
+}
+
+
+/* ------------------------------------------------------------------ scans (pc_hip_scan_run, include/polycap-hip.h)
+ * P points, each a source position; n_per_point slots per point.  Flat index i = k*n_per_point + j is slot j of point k, traced
+ * like slot slot0 + j of a source run whose source sits at point k. */
+struct pc_scan_point { double d_source, src_shiftx, src_shifty; };
+
+/* i -> (k, j); 0 <= i, 1 <= n_per_point */
+PC_HD void pc_scan_map(long long i, long long n_per_point, long long &k, long long &j)
+{
+	k = i / n_per_point;
+	j = i - k*n_per_point;
+}
+
+/* attempt `attempt` of flat index i: the point's three fields are read once, the stream is (seed, slot0 + j, attempt) */
+template <bool GENERIC>
+PC_HD void pc_scan_sample(const pc_params &Pm, const pc_scan_point *pts, long long n_per_point, long long slot0, uint64_t seed,
+                          long long i, uint32_t attempt, pc_start &s)
+{
+	long long k, j;
+	pc_scan_map(i, n_per_point, k, j);
+	const pc_scan_point p = pts[k];
+	pc_sample_photon_at<GENERIC>(Pm, p.d_source, p.src_shiftx, p.src_shifty, seed, (uint64_t)(slot0 + j), attempt, s);
+}
+
 /* ------------------------------------------------------------------ launch entrance tests */
 
 PC_HD int pc_last_node_le(const pc_tables &T, int upto, double zval)

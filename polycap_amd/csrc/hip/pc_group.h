@@ -66,6 +66,8 @@ struct pc_hip_group {
 	long long run_slots = 0;
 	int keep_images = 0;
 	int leak_run = 0;                           /* the last run was a leak run (pc_hip_group_run_leak) */
+	std::vector<long long> scan_count;          /* flat indices every member traced in the last scan (pc_scan.h); 0 = none */
+	long long scan_points = 0;                  /* points of the last scan (0: none yet) */
 };
 
 /* totals of one device -> the vector that is all-reduced: counters, then the (lo, hi) sums as 32-bit limbs.  n_sums = n_energies,

@@ -142,7 +142,17 @@ struct pc_kargs {
 	 * The kernels that add to it are instantiated with SQ = true; where the sums are kept in LDS, the squares take another
 	 * 2*n_energies u64 behind the weights'.  (Last in the struct: the default kernels' argument offsets stay as they were.) */
 	unsigned long long *sumw2;
+	/* Scans (MODE PC_MODE_SCAN_*, pc_hip_scan_run) keep no images and launch no explicit photons; they take their arguments in
+	 * fields of those (PC_SCAN_* below), so that the struct -- and with it every other kernel -- stays exactly as it was: relative slot
+	 * s of the launch is flat index img_id0 + s = point k, slot j (pc_scan_map with img_n slots per point), sampled at point k of
+	 * the table in in_start on the stream (seed, slot0 + j, attempt).  Per point, 6 + 4 n_energies u64 of exact totals at sumw +
+	 * k (6 + 4 n_energies): the 6 counters, 2 n_energies (lo, hi) weight sums, 2 n_energies of the squares (SQ). */
 };
+
+/* the scan's view of pc_kargs (see there) */
+#define PC_SCAN_PTS(a) ((const pc_scan_point *)(a).in_start)
+#define PC_SCAN_FIRST(a) ((a).img_id0)
+#define PC_SCAN_NPP(a) ((a).img_n)
 
 /* Stores of the compact image store: written through to memory (system-coherent), so that a block can be handed to the copy
  * engine while the kernel runs without a write-back of the whole L2 (an agent-scope release on gfx950) per batch of photons */
@@ -285,6 +295,11 @@ __device__ __forceinline__ int pc_reflect_energy_sweep(const pc_energy_const &ec
  * MODE: PC_MODE_EXPLICIT: photons come from in_start/in_dir/in_elecv (polycap_photon_launch), no retry, no
  * source; PC_MODE_SRC_CIRCULAR / _GENERIC: photons are sampled from the source (circular / elliptical). */
 enum { PC_MODE_SRC_CIRCULAR = 0, PC_MODE_SRC_GENERIC = 1, PC_MODE_EXPLICIT = 2 };
+/* scans (pc_hip_scan_run): source runs whose slots belong to points with a source position each, totals kept per point.  The
+ * finishing lanes' contributions are gathered into the wave-uniform totals as in a source run; those are tagged with the point they
+ * belong to and flushed to it when a phase's lanes belong to another one (slots are handed out in contiguous PC_CHUNK ranges, so a
+ * wave holds one or two consecutive points at a time).  Sums that a source run keeps in LDS go to the point's global sums. */
+enum { PC_MODE_SCAN_CIRCULAR = 3, PC_MODE_SCAN_GENERIC = 4 };
 
 /* Source runs with more than 8 energies have a kernel of their own: pc_trace_log_kernel (pc_sweep_kernel.h). */
 template <int NE, int MODE, int PITCH, bool SQ = false>
@@ -292,6 +307,8 @@ __global__ void __launch_bounds__(PC_BLOCK, NE == 0 ? PC_MIN_WAVES_NE0 : PC_MIN_
 pc_trace_kernel(pc_kargs a)
 {
 	constexpr bool EXPLICIT = (MODE == PC_MODE_EXPLICIT);
+	constexpr bool SCAN = (MODE == PC_MODE_SCAN_CIRCULAR || MODE == PC_MODE_SCAN_GENERIC);
+	constexpr bool GENERIC = (MODE == PC_MODE_SRC_GENERIC || MODE == PC_MODE_SCAN_GENERIC);
 	static_assert(!(SQ && EXPLICIT), "explicit launches keep no sums");
 	/* static LDS with a compile-time pitch: table reads become ds_read with immediate offsets */
 	__shared__ double lds[6*PITCH];
@@ -316,7 +333,7 @@ pc_trace_kernel(pc_kargs a)
 	/* NE == 0: the per-energy constants of the cooperative sweeps, staged behind the sums when they fit (a.lds_ec):
 	 * every reflection of every photon reads all 6*n_energies of them */
 	if (NE == 0 && a.lds_ec) {
-		double *l_ec = (double *)(l_acc + (SQ ? 4 : 2)*a.pm.n_energies);
+		double *l_ec = (double *)(l_acc + (SCAN ? 0 : (SQ ? 4 : 2)*a.pm.n_energies));
 		for (int k = threadIdx.x; k < 6*a.pm.n_energies; k += blockDim.x) l_ec[k] = a.ec_soa[k];
 	}
 	__syncthreads();
@@ -341,6 +358,7 @@ pc_trace_kernel(pc_kargs a)
 
 	int state = LS_NEED_SLOT;
 	long long slot = -1;          /* relative slot index in [0, n_slots) */
+	long long sk = 0;             /* scans: the slot's point */
 	unsigned int attempt = 0;
 	double cosalpha0 = 0.;         /* start_electric_vector . start_direction: projection constants of src/polycap-source.c:789-796 */
 	/* wave-uniform chunk of slots */
@@ -353,6 +371,24 @@ pc_trace_kernel(pc_kargs a)
 	unsigned long long u_exit = 0, u_not_entered = 0, u_not_trans = 0, u_irefl = 0, u_failed = 0, u_launch = 0;
 	unsigned long long u_acc_lo = 0, u_acc_hi = 0;   /* NE == 1: exact 128-bit weight sum; NE > 1 and NE == 0 sum in LDS */
 	unsigned long long u_sq_lo = 0, u_sq_hi = 0;     /* NE == 1: the same of the squared weights (a.sumw2) */
+	long long u_pt = -1;                             /* scans: the point the wave-uniform totals belong to (-1: none yet) */
+	/* scans: adds the wave-uniform totals to point u_pt and clears them (a macro: a lambda that captures the totals by reference
+	 * would change how the source runs' instantiations are compiled) */
+#define PC_SCAN_FLUSH() do { \
+		if (u_pt >= 0 && lane == 0) { \
+			unsigned long long *t_ = a.sumw + u_pt*(6 + 4*(long long)a.pm.n_energies); \
+			if (u_exit) atomicAdd(&t_[0], u_exit); \
+			if (u_not_entered) atomicAdd(&t_[1], u_not_entered); \
+			if (u_not_trans) atomicAdd(&t_[2], u_not_trans); \
+			if (u_irefl) atomicAdd(&t_[3], u_irefl); \
+			if (u_failed) atomicAdd(&t_[4], u_failed); \
+			if (u_launch) atomicAdd(&t_[5], u_launch); \
+			if (NE == 1 && (u_acc_lo | u_acc_hi)) pc_atomic_add128(t_ + 6, u_acc_lo, u_acc_hi); \
+			if (NE == 1 && SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(t_ + 8, u_sq_lo, u_sq_hi); \
+		} \
+		u_exit = u_not_entered = u_not_trans = u_irefl = u_failed = u_launch = 0; \
+		u_acc_lo = u_acc_hi = u_sq_lo = u_sq_hi = 0; \
+	} while (0)
 
 	/* wave-uniform scheduler statistics (diagnostics: lane utilisation per phase type) */
 	unsigned long long st_march = 0, st_march_l = 0, st_event = 0, st_event_l = 0, st_new = 0, st_new_l = 0;
@@ -502,7 +538,7 @@ pc_trace_kernel(pc_kargs a)
 						if (lane == p) res = anybad ? -1 : (anykeep ? 1 : 0);
 					}
 				};
-				if (NE == 0 && a.lds_ec) sweep((const double *)(l_acc + (SQ ? 4 : 2)*a.pm.n_energies));
+				if (NE == 0 && a.lds_ec) sweep((const double *)(l_acc + (SCAN ? 0 : (SQ ? 4 : 2)*a.pm.n_energies)));
 				else sweep(a.ec_soa);
 				if (pend) {
 					if (pend == 1) { ph.wset = 1; ph.ex = fabs(ph.ex); ph.ey = fabs(ph.ey); ph.ez = fabs(ph.ez); }
@@ -566,10 +602,10 @@ pc_trace_kernel(pc_kargs a)
 						if (SQ) f_w2 = pc_fix_sq(w);
 						if (a.keep_images) { if (compact) pc_store_wt(a.img_w + done_slot*ws, w); else a.img_w[done_slot*ws] = w; }
 					} else if (NE > 1) {
-						/* a few energies: exact sums in LDS (2 x u64 per energy), flushed once per workgroup */
+						/* a few energies: exact sums in LDS (2 x u64 per energy), flushed once per workgroup (scans: per point, below) */
 #pragma unroll
 						for (int e = 0; e < (NE > 0 ? NE : 1); e++) {
-							if (e < ner) {
+							if (!SCAN && e < ner) {
 								double w = ph.w[NE > 0 ? e : 0];
 								unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
 								unsigned long long old = atomicAdd(&l_acc[2*e], f);
@@ -618,6 +654,8 @@ pc_trace_kernel(pc_kargs a)
 					const int what = __shfl(coop, p, PC_WAVE);
 					const int wset_p = __shfl(ph.wset, p, PC_WAVE);
 					const long long slot_p = __shfl(done_slot, p, PC_WAVE);
+					long long k_p = 0;        /* scans: the photon's point */
+					if constexpr (SCAN) k_p = __shfl(sk, p, PC_WAVE);
 					const double *wp = a.wscratch + (wave_gtid0 + p)*(long long)ne;
 					for (int e = lane; e < ne; e += PC_WAVE) {
 						double w = (what == 2) ? 0. : (wset_p ? wp[e] : 1.0);
@@ -626,7 +664,11 @@ pc_trace_kernel(pc_kargs a)
 						} else {
 							if (what == 1) {
 								unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
-								if (a.lds_acc) {
+								if constexpr (SCAN) {
+									unsigned long long *t = a.sumw + k_p*(6 + 4*(long long)a.pm.n_energies) + 6;
+									pc_atomic_add128(t + 2*e, f, 0ull);
+									if (SQ) pc_atomic_add128(t + 2*ne + 2*e, pc_fix_sq(w), 0ull);
+								} else if (a.lds_acc) {
 									unsigned long long old = atomicAdd(&l_acc[2*e], f);
 									if (old + f < old) atomicAdd(&l_acc[2*e + 1], 1ull);
 									if (SQ) pc_lds_add128(&l_acc[2*ne + 2*e], pc_fix_sq(w));
@@ -636,6 +678,47 @@ pc_trace_kernel(pc_kargs a)
 								}
 							}
 							if (a.keep_images) { if (compact) pc_store_wt(a.img_w + slot_p*ws + e, w); else a.img_w[slot_p*ws + e] = w; }
+						}
+					}
+				}
+			}
+			if constexpr (SCAN) {
+				/* the finished photons' contributions, point by point over the lanes that share one (sk is still the finished slot's) */
+				const bool has = (f_exit | f_not_entered | f_not_trans | f_failed) != 0;
+				unsigned long long pend = __ballot(has);
+				while (pend) {
+					const long long k = __shfl(sk, __ffsll((long long)pend) - 1, PC_WAVE);
+					const bool mine = has && sk == k;
+					pend &= ~__ballot(mine);
+					if (k != u_pt) { PC_SCAN_FLUSH(); u_pt = k; }
+					u_not_trans += (unsigned long long)__popcll(__ballot(mine && f_not_trans));
+					u_not_entered += (unsigned long long)__popcll(__ballot(mine && f_not_entered));
+					u_failed += (unsigned long long)__popcll(__ballot(mine && f_failed));
+					const bool mx = mine && f_exit;
+					const unsigned long long mX = __ballot(mx);
+					if (mX) {
+						u_exit += (unsigned long long)__popcll(mX);
+						u_irefl += pc_wave_sum_u64(mx ? (unsigned long long)f_irefl : 0ull);
+						if (NE == 1) {
+							pc_wave_acc128(mx ? f_w : 0ull, u_acc_lo, u_acc_hi);
+							if (SQ) pc_wave_acc128(mx ? f_w2 : 0ull, u_sq_lo, u_sq_hi);
+						} else if (NE > 1) {
+							/* a few energies: the group's exact sums go to the point at once (the weights are the lanes' until the launch below) */
+							unsigned long long *t = a.sumw + k*(6 + 4*(long long)a.pm.n_energies) + 6;
+#pragma unroll
+							for (int e = 0; e < (NE > 0 ? NE : 1); e++) {
+								if (e < ner) {
+									const double w = ph.w[NE > 0 ? e : 0];
+									unsigned long long lo = 0, hi = 0;
+									pc_wave_acc128(mx ? (unsigned long long)(w * PC_FIX_SCALE) : 0ull, lo, hi);
+									if (lane == 0 && (lo | hi)) pc_atomic_add128(t + 2*e, lo, hi);
+									if (SQ) {
+										unsigned long long lo2 = 0, hi2 = 0;
+										pc_wave_acc128(mx ? pc_fix_sq(w) : 0ull, lo2, hi2);
+										if (lane == 0 && (lo2 | hi2)) pc_atomic_add128(t + 2*ner + 2*e, lo2, hi2);
+									}
+								}
+							}
 						}
 					}
 				}
@@ -671,7 +754,13 @@ pc_trace_kernel(pc_kargs a)
 					}
 					if (state == LS_NEED_SLOT) {
 						if (slot >= a.n_slots) { state = LS_IDLE; }
-						else { attempt = 0; state = LS_START; }
+						else {
+							attempt = 0; state = LS_START;
+							if constexpr (SCAN) {
+								long long j;
+								pc_scan_map(PC_SCAN_FIRST(a) + slot, PC_SCAN_NPP(a), sk, j);
+							}
+						}
 					}
 				}
 			}
@@ -689,7 +778,12 @@ pc_trace_kernel(pc_kargs a)
 					}
 				} else {
 					pc_start s;
-					pc_sample_photon<MODE == PC_MODE_SRC_GENERIC>(Pm, a.seed, (unsigned long long)(a.slot0 + slot), attempt, s);
+					if constexpr (SCAN) {
+						const pc_scan_point pt = PC_SCAN_PTS(a)[sk];       /* the point's source position, once per attempt */
+						const long long j = PC_SCAN_FIRST(a) + slot - sk*PC_SCAN_NPP(a);   /* slot j of point sk (pc_scan_map) */
+						pc_sample_photon_at<GENERIC>(Pm, pt.d_source, pt.src_shiftx, pt.src_shifty, a.seed, (unsigned long long)(a.slot0 + j), attempt, s);
+					} else
+						pc_sample_photon<MODE == PC_MODE_SRC_GENERIC>(Pm, a.seed, (unsigned long long)(a.slot0 + slot), attempt, s);
 					state = pc_launch_init(T, Pm, ph, s.x, s.y, s.z, s.dx, s.dy, s.dz, s.ex, s.ey, s.ez);
 					if (NE > 1) {
 #pragma unroll
@@ -714,6 +808,18 @@ pc_trace_kernel(pc_kargs a)
 				}
 			}
 			/* gather this phase's contributions into the wave-uniform totals */
+			if constexpr (SCAN) {
+				/* the finished photons' went to their points above; the launches belong to the points of the lanes' (new) slots */
+				unsigned long long pend = __ballot(f_launch);
+				while (pend) {
+					const long long k = __shfl(sk, __ffsll((long long)pend) - 1, PC_WAVE);
+					const unsigned long long grp = __ballot(f_launch && sk == k);
+					pend &= ~grp;
+					if (k != u_pt) { PC_SCAN_FLUSH(); u_pt = k; }
+					u_launch += (unsigned long long)__popcll(grp);
+				}
+				continue;
+			}
 			u_not_trans += (unsigned long long)__popcll(__ballot(f_not_trans));
 			u_not_entered += (unsigned long long)__popcll(__ballot(f_not_entered));
 			u_failed += (unsigned long long)__popcll(__ballot(f_failed));
@@ -736,6 +842,16 @@ pc_trace_kernel(pc_kargs a)
 		}
 	}
 
+	if constexpr (SCAN) {
+		PC_SCAN_FLUSH();
+		if (lane == 0) {
+			atomicAdd(&a.totals->phase[0], st_march); atomicAdd(&a.totals->phase[1], st_march_l);
+			atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event_l);
+			atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
+		}
+		return;
+	}
+#undef PC_SCAN_FLUSH
 	if (NE != 1 && !EXPLICIT && a.lds_acc) {
 		__syncthreads();          /* every wave of the workgroup has finished its photons */
 		for (int e = threadIdx.x; e < a.pm.n_energies; e += blockDim.x)
@@ -1103,6 +1219,19 @@ struct pc_hip_ctx {
 	size_t leak_order_bytes = 0;
 	long long leak_n_ext = 0, leak_n_int = 0;
 	int leak_events_of_run = 0;            /* the event lists are those of the last source run (a leak run): pc_hip_spot_add may read them */
+	/* scans (pc_scan.h): buffers of their own, so that a scan leaves everything of the last run as it was */
+	pc_totals *d_scan_totals = nullptr;    /* work counter and scheduler statistics of the last scan launch */
+	unsigned long long *d_scan_tot = nullptr;   /* per point: 6 counters, 2*ne weight sums, 2*ne squared-weight sums (pc_kargs::sumw of a scan) */
+	size_t scan_tot_elems = 0;
+	pc_scan_point *d_scan_pts = nullptr;
+	size_t scan_pts_cap = 0;
+	double *d_scan_wscratch = nullptr;     /* more than 8 energies: the scan kernel's per-lane weights */
+	size_t scan_wscratch_elems = 0;
+	hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;
+	long long scan_points = 0;             /* points of the last scan call (0: none yet) */
+	int scan_squares = 0;                  /* the last scan summed the squared weights */
+	int scan_pending = 0;                  /* the last scan has not been waited for */
+	float scan_ms = 0.f;
 };
 
 static int pc_cus(const pc_hip_ctx *ctx)
@@ -1487,6 +1616,12 @@ void pc_hip_ctx_destroy(pc_hip_ctx *ctx)
 	if (ctx->d_leak_order) (void)hipFree(ctx->d_leak_order);
 	if (ctx->d_work_est) (void)hipFree(ctx->d_work_est);
 	if (ctx->d_leak_slot_units) (void)hipFree(ctx->d_leak_slot_units);
+	if (ctx->d_scan_totals) (void)hipFree(ctx->d_scan_totals);
+	if (ctx->d_scan_tot) (void)hipFree(ctx->d_scan_tot);
+	if (ctx->d_scan_pts) (void)hipFree(ctx->d_scan_pts);
+	if (ctx->d_scan_wscratch) (void)hipFree(ctx->d_scan_wscratch);
+	if (ctx->ev_scan0) (void)hipEventDestroy(ctx->ev_scan0);
+	if (ctx->ev_scan1) (void)hipEventDestroy(ctx->ev_scan1);
 	if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
 	if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2643,6 +2778,7 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 
 #include "pc_group.h"
 #include "pc_spot.h"
+#include "pc_scan.h"
 
 /* Heaviest slots first.  A leak launch ends with its longest slot: 20 000 units of work on one lane, which advances several
  * times faster alone in its wave than among 63 others (a wave runs one class of work at a time).  Which slots are long is known

@@ -1,0 +1,306 @@
+/*
+ * pc_scan.h -- scans: transmission as a function of the source position, one launch of the lane kernel for a whole grid of
+ * points with exact totals per point (include/polycap-hip.h, pc_hip_scan_*).  The kernel is pc_trace_kernel with MODE
+ * PC_MODE_SCAN_CIRCULAR / _GENERIC (pc_kernels.hip); the mapping of a flat index to its point and the per-point source are
+ * pc_scan_map / pc_sample_photon_at of pc_device.h.  Included at the end of pc_kernels.hip.
+ */
+#ifndef PC_SCAN_H
+#define PC_SCAN_H
+
+static_assert(sizeof(pc_scan_point) == sizeof(pc_hip_scan_point), "pc_scan_point mirrors pc_hip_scan_point");
+
+/* u64 of exact totals per point: 6 counters, (lo, hi) weight sums, (lo, hi) squared-weight sums */
+static size_t pc_scan_stride(size_t ne)
+{
+	return 6 + 4*ne;
+}
+
+static int pc_scan_check(const char *fn, const pc_hip_scan_point *pts, int64_t n_points, int64_t n_per_point)
+{
+	const std::string f(fn);
+	if (n_points < 1) return pc_fail(PC_HIP_ERR_INVALID, f + ": n_points must be >= 1");
+	if (n_per_point < 1) return pc_fail(PC_HIP_ERR_INVALID, f + ": n_per_point must be >= 1");
+	if (n_points > INT64_MAX / n_per_point) return pc_fail(PC_HIP_ERR_INVALID, f + ": n_points * n_per_point overflows int64");
+	if (!pts) return pc_fail(PC_HIP_ERR_INVALID, f + ": points must not be NULL");
+	for (int64_t k = 0; k < n_points; k++) {
+		const std::string at = f + ": point " + std::to_string((long long)k) + ": ";
+		if (!(pts[k].d_source > 0.)) return pc_fail(PC_HIP_ERR_INVALID, at + "d_source must be greater than 0");
+		if (!std::isfinite(pts[k].d_source)) return pc_fail(PC_HIP_ERR_INVALID, at + "d_source must be finite");
+		if (!std::isfinite(pts[k].src_shiftx)) return pc_fail(PC_HIP_ERR_INVALID, at + "src_shiftx must be finite");
+		if (!std::isfinite(pts[k].src_shifty)) return pc_fail(PC_HIP_ERR_INVALID, at + "src_shifty must be finite");
+	}
+	return PC_HIP_OK;
+}
+
+/* one launch: NE = 1, 4, 8 (weights in registers) or 0 (any count, weights in the scan's own per-lane scratch) */
+template <int NE, int MODE>
+static int pc_scan_launch(pc_hip_ctx *ctx, const pc_kargs &a, int grid, int block, size_t dyn, bool sq)
+{
+	if (ctx->host.pm.nmax + 1 <= 1024) {
+		if (sq) hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, true>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+		else hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, false>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+	} else if (NE <= 1) {
+		if (sq) hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, true>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+		else hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, false>), dim3(grid), dim3(block), dyn, ctx->stream, a);
+	} else
+		return pc_fail(PC_HIP_ERR_INVALID, "internal: register-weight kernels are built for profiles of up to 1024 points");
+	PC_HIP_CHECK(hipGetLastError());
+	return PC_HIP_OK;
+}
+
+template <int MODE>
+static int pc_scan_launch_kne(pc_hip_ctx *ctx, int kne, const pc_kargs &a, int grid, int block, size_t dyn, bool sq)
+{
+	return (kne == 1) ? pc_scan_launch<1, MODE>(ctx, a, grid, block, dyn, sq) : (kne == 4) ? pc_scan_launch<4, MODE>(ctx, a, grid, block, dyn, sq)
+	     : (kne == 8) ? pc_scan_launch<8, MODE>(ctx, a, grid, block, dyn, sq) : pc_scan_launch<0, MODE>(ctx, a, grid, block, dyn, sq);
+}
+
+/* device buffers of a scan of n_points points and up to `lanes` lanes (kne == 0: per-lane weights) */
+static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points, size_t wscratch_elems)
+{
+	const size_t ne = (size_t)ctx->host.pm.n_energies;
+	if (!ctx->d_scan_totals) PC_HIP_CHECK(hipMalloc(&ctx->d_scan_totals, sizeof(pc_totals)));
+	if (!ctx->ev_scan0) PC_HIP_CHECK(hipEventCreate(&ctx->ev_scan0));
+	if (!ctx->ev_scan1) PC_HIP_CHECK(hipEventCreate(&ctx->ev_scan1));
+	if (ctx->scan_pts_cap < (size_t)n_points) {
+		if (ctx->d_scan_pts) PC_HIP_CHECK(hipFree(ctx->d_scan_pts));
+		ctx->d_scan_pts = nullptr; ctx->scan_pts_cap = 0;
+		if (hipMalloc(&ctx->d_scan_pts, (size_t)n_points*sizeof(pc_scan_point)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the point table"); }
+		ctx->scan_pts_cap = (size_t)n_points;
+	}
+	const size_t tot = (size_t)n_points*pc_scan_stride(ne);
+	if (ctx->scan_tot_elems < tot) {
+		if (ctx->d_scan_tot) PC_HIP_CHECK(hipFree(ctx->d_scan_tot));
+		ctx->d_scan_tot = nullptr; ctx->scan_tot_elems = 0;
+		if (hipMalloc(&ctx->d_scan_tot, tot*sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the per-point totals"); }
+		ctx->scan_tot_elems = tot;
+	}
+	if (ctx->scan_wscratch_elems < wscratch_elems) {
+		if (ctx->d_scan_wscratch) PC_HIP_CHECK(hipFree(ctx->d_scan_wscratch));
+		ctx->d_scan_wscratch = nullptr; ctx->scan_wscratch_elems = 0;
+		if (hipMalloc(&ctx->d_scan_wscratch, wscratch_elems*sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the per-lane weight scratch"); }
+		ctx->scan_wscratch_elems = wscratch_elems;
+	}
+	return PC_HIP_OK;
+}
+
+extern "C" {
+
+int pc_hip_scan_validate(const pc_hip_scan_point *points, int64_t n_points, int64_t n_per_point)
+{
+	return pc_scan_check("pc_hip_scan_validate", points, n_points, n_per_point);
+}
+
+int pc_hip_scan_wait(pc_hip_ctx *ctx, float *kernel_ms)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_wait: ctx must not be NULL");
+	if (!ctx->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_wait: no scan has been made on this context");
+	if (ctx->scan_pending) {
+		PC_HIP_CHECK(hipSetDevice(ctx->device));
+		PC_HIP_CHECK(hipEventSynchronize(ctx->ev_scan1));
+		float ms = 0.f;
+		PC_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_scan0, ctx->ev_scan1));
+		ctx->scan_ms = ms;
+		ctx->scan_pending = 0;
+	}
+	if (kernel_ms) *kernel_ms = ctx->scan_ms;
+	return PC_HIP_OK;
+}
+
+int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_scan_point *points, int64_t n_points,
+                    int64_t n_per_point, int64_t first, int64_t count, uint32_t max_attempts)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_run: ctx must not be NULL");
+	int st = pc_scan_check("pc_hip_scan_run", points, n_points, n_per_point);
+	if (st) return st;
+	if (slot0 < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_run: slot0 must be >= 0");
+	if (slot0 > INT64_MAX - n_per_point) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_run: slot0 + n_per_point overflows int64");
+	const int64_t total = n_points*n_per_point;
+	if (first < 0 || count < 1 || first > total - count)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_run: first and count must select a non-empty range of [0, n_points * n_per_point)");
+	if (max_attempts < 1) max_attempts = 1;
+	PC_HIP_CHECK(hipSetDevice(ctx->device));
+	/* the previous scan's kernel may still read the point table and add to the totals that are reused below */
+	if (ctx->scan_pending) {
+		st = pc_hip_scan_wait(ctx, nullptr);
+		if (st) return st;
+	}
+	ctx->scan_points = 0;       /* until this scan is enqueued */
+	/* behind every launch of the last run: a run cut into parts ends its main stream behind the parts on stream2 already
+	 * (pc_hip_transmission_run); this also orders the scan after anything else enqueued there */
+	if (ctx->stream2) {
+		PC_HIP_CHECK(hipEventRecord(ctx->ev_sync, ctx->stream2));
+		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_sync, 0));
+	}
+	const int ne = ctx->host.pm.n_energies;
+	const int npts = ctx->host.pm.nmax + 1;
+	/* weights in registers for up to 8 energies (kernels NE = 1, 4, 8), in the scan's per-lane scratch beyond */
+	const int kne = (ne == 1) ? 1 : ((ne <= 4 && npts <= 1024) ? 4 : ((ne <= 8 && npts <= 1024) ? 8 : 0));
+	const long long max_blocks = (long long)pc_cus(ctx) * ((kne == 0) ? 1 : ctx->blocks_per_cu);
+	const int block = ctx->block_size;
+	const long long want_blocks = (count + block - 1) / block;
+	int grid = (int)(want_blocks < max_blocks ? want_blocks : max_blocks);
+	if (grid < 1) grid = 1;
+	const size_t wscratch = (kne == 0) ? (size_t)ne * (size_t)grid * (size_t)block : 0;
+	st = pc_scan_buffers(ctx, n_points, wscratch);
+	if (st) return st;
+	PC_HIP_CHECK(hipMemcpy(ctx->d_scan_pts, points, (size_t)n_points*sizeof(pc_scan_point), hipMemcpyHostToDevice));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_totals, 0, sizeof(pc_totals), ctx->stream));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_tot, 0, (size_t)n_points*pc_scan_stride((size_t)ne)*sizeof(unsigned long long), ctx->stream));
+	pc_kargs a;
+	pc_fill_common(ctx, a);
+	a.totals = ctx->d_scan_totals;
+	a.work = &ctx->d_scan_totals->next_slot;
+	/* the scan's arguments in pc_kargs (PC_SCAN_*): point table, per-point totals, first flat index, slots per point */
+	a.in_start = (const double *)ctx->d_scan_pts;
+	a.sumw = ctx->d_scan_tot;
+	a.sumw2 = nullptr;
+	a.img_id0 = first;
+	a.img_n = n_per_point;
+	a.seed = seed; a.slot0 = slot0; a.n_slots = count; a.max_attempts = max_attempts; a.keep_images = 0;
+	a.lds_acc = 0;
+	a.lds_ec = (kne == 0 && ctx->lds_ec && npts <= 1024 && 48*(size_t)ne <= 28672) ? 1 : 0;
+	a.sweep_rough = 0;
+	for (const pc_energy_const &c : ctx->host.ec) if (c.rough_c != 0.) a.sweep_rough = 1;
+	a.total_threads = (long long)grid * block;
+	if (kne == 0) a.wscratch = ctx->d_scan_wscratch;
+	const size_t dyn = (kne == 0) ? pc_ne0_dyn_lds((size_t)ne, 0, a.lds_ec, 0) : 0;
+	const bool sq = ctx->weight_squares != 0;
+	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan0, ctx->stream));
+	st = ctx->host.pm.generic_src ? pc_scan_launch_kne<PC_MODE_SCAN_GENERIC>(ctx, kne, a, grid, block, dyn, sq)
+	                              : pc_scan_launch_kne<PC_MODE_SCAN_CIRCULAR>(ctx, kne, a, grid, block, dyn, sq);
+	if (st) return st;
+	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan1, ctx->stream));
+	ctx->scan_points = n_points;
+	ctx->scan_squares = sq ? 1 : 0;
+	ctx->scan_pending = 1;
+	return PC_HIP_OK;
+}
+
+int pc_hip_scan_totals(pc_hip_ctx *ctx, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: ctx must not be NULL");
+	if (!ctx->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: no scan has been made on this context");
+	if (sumw2_fixed && !ctx->scan_squares)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: sumw2_fixed: the last scan was made without option weight_squares");
+	int st = pc_hip_scan_wait(ctx, nullptr);
+	if (st) return st;
+	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = pc_scan_stride(ne), P = (size_t)ctx->scan_points;
+	std::vector<unsigned long long> buf(P*stride);
+	PC_HIP_CHECK(hipMemcpy(buf.data(), ctx->d_scan_tot, buf.size()*sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	for (size_t k = 0; k < P; k++) {
+		const unsigned long long *t = buf.data() + k*stride;
+		if (counters) for (int c = 0; c < 6; c++) counters[6*k + c] = (int64_t)t[c];
+		if (sumw_fixed) for (size_t e = 0; e < 2*ne; e++) sumw_fixed[2*ne*k + e] = t[6 + e];
+		if (sumw2_fixed) for (size_t e = 0; e < 2*ne; e++) sumw2_fixed[2*ne*k + e] = t[6 + 2*ne + e];
+	}
+	return PC_HIP_OK;
+}
+
+void pc_hip_scan_efficiencies(size_t n_energies, int64_t n_points, const int64_t *counters, const uint64_t *sumw_fixed,
+                              const uint64_t *sumw2_fixed, double *efficiencies, double *stderr_)
+{
+	std::vector<double> sw(n_energies);
+	for (int64_t k = 0; k < n_points; k++) {
+		const int64_t *c = counters + 6*k;
+		const uint64_t *a = sumw_fixed + 2*n_energies*k;
+		double *eff = efficiencies + n_energies*k;
+		if (c[0] + c[2] == 0) {
+			/* nothing entered a capillary (or nothing was started): efficiency 0 */
+			for (size_t e = 0; e < n_energies; e++) eff[e] = 0.;
+		} else {
+			for (size_t e = 0; e < n_energies; e++) sw[e] = pc_hip_fixed_to_double(a[2*e], a[2*e + 1]);
+			pc_hip_efficiencies(n_energies, sw.data(), c, eff);
+		}
+		if (sumw2_fixed && stderr_)
+			pc_hip_efficiency_stderr(n_energies, a, sumw2_fixed + 2*n_energies*k, c, stderr_ + n_energies*k);
+	}
+}
+
+int pc_hip_group_scan_run(pc_hip_group *g, uint64_t seed, int64_t slot0, const pc_hip_scan_point *points, int64_t n_points,
+                          int64_t n_per_point, uint32_t max_attempts)
+{
+	if (!g) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_run: group must not be NULL");
+	int st = pc_scan_check("pc_hip_group_scan_run", points, n_points, n_per_point);
+	if (st) return st;
+	if (slot0 < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_run: slot0 must be >= 0");
+	if (slot0 > INT64_MAX - n_per_point) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_run: slot0 + n_per_point overflows int64");
+	const size_t N = g->ctx.size();
+	const long long total = n_points*n_per_point;
+	g->scan_points = 0;
+	g->scan_count.assign(N, 0);
+	std::vector<long long> first(N, 0);
+	for (size_t k = 0; k < N; k++) {
+		/* contiguous ranges that differ by at most one flat index (a range may cut through a point: the sums are exact) */
+		const long long lo = (long long)((__int128)total*(long long)k/(long long)N), hi = (long long)((__int128)total*(long long)(k + 1)/(long long)N);
+		first[k] = lo; g->scan_count[k] = hi - lo;
+	}
+	std::vector<int> status(N, PC_HIP_OK);
+	std::vector<std::string> msg(N);
+	auto enqueue = [&](size_t k) {
+		if (g->scan_count[k] == 0) return;
+		status[k] = pc_hip_scan_run(g->ctx[k], seed, slot0, points, n_points, n_per_point, first[k], g->scan_count[k], max_attempts);
+		if (status[k]) msg[k] = g_last_error;       /* the error text is per thread */
+	};
+	{
+		std::vector<std::thread> th;
+		for (size_t k = 1; k < N; k++) th.emplace_back(enqueue, k);
+		enqueue(0);
+		for (auto &t : th) t.join();
+	}
+	for (size_t k = 0; k < N; k++) {
+		if (status[k] == PC_HIP_OK) continue;
+		for (size_t j = 0; j < N; j++)
+			if (g->ctx[j]->scan_pending) (void)pc_hip_scan_wait(g->ctx[j], nullptr);
+		g->scan_count.assign(N, 0);
+		return pc_fail(status[k], msg[k]);
+	}
+	g->scan_points = n_points;
+	return PC_HIP_OK;
+}
+
+int pc_hip_group_scan_wait(pc_hip_group *g, float *kernel_ms)
+{
+	if (!g) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_wait: group must not be NULL");
+	if (!g->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_wait: no scan has been made on this group");
+	float longest = 0.f;
+	for (size_t k = 0; k < g->ctx.size(); k++) {
+		if (!g->scan_count[k]) continue;
+		float ms = 0.f;
+		int st = pc_hip_scan_wait(g->ctx[k], &ms);
+		if (st) return st;
+		longest = std::max(longest, ms);
+	}
+	if (kernel_ms) *kernel_ms = longest;
+	return PC_HIP_OK;
+}
+
+int pc_hip_group_scan_totals(pc_hip_group *g, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed)
+{
+	if (!g) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_totals: group must not be NULL");
+	if (!g->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_scan_totals: no scan has been made on this group");
+	const size_t P = (size_t)g->scan_points, ne2 = 2*(size_t)g->ctx[0]->host.pm.n_energies;
+	std::vector<int64_t> c(6*P), c_sum(6*P, 0);
+	std::vector<uint64_t> a(ne2*P), b(sumw2_fixed ? ne2*P : 0);
+	std::vector<unsigned __int128> a_sum(ne2/2*P, 0), b_sum(sumw2_fixed ? ne2/2*P : 0, 0);
+	for (size_t k = 0; k < g->ctx.size(); k++) {
+		if (!g->scan_count[k]) continue;
+		int st = pc_hip_scan_totals(g->ctx[k], c.data(), a.data(), sumw2_fixed ? b.data() : nullptr);
+		if (st) return pc_fail(st, std::string("pc_hip_group_scan_totals: ") + g_last_error);
+		for (size_t i = 0; i < 6*P; i++) c_sum[i] += c[i];
+		for (size_t i = 0; i < ne2/2*P; i++) {
+			a_sum[i] += ((unsigned __int128)a[2*i + 1] << 64) | a[2*i];
+			if (sumw2_fixed) b_sum[i] += ((unsigned __int128)b[2*i + 1] << 64) | b[2*i];
+		}
+	}
+	if (counters) memcpy(counters, c_sum.data(), 6*P*sizeof(int64_t));
+	for (size_t i = 0; i < ne2/2*P; i++) {
+		if (sumw_fixed) { sumw_fixed[2*i] = (uint64_t)a_sum[i]; sumw_fixed[2*i + 1] = (uint64_t)(a_sum[i] >> 64); }
+		if (sumw2_fixed) { sumw2_fixed[2*i] = (uint64_t)b_sum[i]; sumw2_fixed[2*i + 1] = (uint64_t)(b_sum[i] >> 64); }
+	}
+	return PC_HIP_OK;
+}
+
+} /* extern "C" */
+
+#endif /* PC_SCAN_H */

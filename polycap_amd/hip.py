@@ -63,6 +63,29 @@ class TraceContext:
         st = self._L.pc_hip_set_option(self._h, name.encode(), int(value))
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_set_option", st)
+        if name == "weight_squares":
+            self._weight_squares = bool(value)
+
+    def scan(self, seed, points, n_per_point, max_attempts=1, slot0=0, first=0, count=None):
+        """Transmission per source position in one launch (pc_hip_scan_run; the contract is in include/polycap-hip.h): points
+        [P, 3] of (d_source, src_shiftx, src_shifty), e.g. from scan_points() (NaN d_source = the problem's own); n_per_point
+        slots per point, slot j of every point on the stream of slot slot0 + j; the flat indices [first, first + count) are traced
+        (default: all).  Returns counters [P, 6], sumw_fixed [P, ne, 2], sumw2_fixed (option "weight_squares") or None,
+        efficiencies [P, ne], stderr [P, ne] or None, kernel_ms."""
+        pts = _scan_array(points, self.problem)
+        n_pts = pts.shape[0]
+        count = n_pts * int(n_per_point) - int(first) if count is None else int(count)
+        st = self._L.pc_hip_scan_run(self._h, int(seed), int(slot0), dptr(pts), n_pts, int(n_per_point), int(first), count,
+                                     int(max_attempts))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_scan_run", st)
+        ms = C.c_float(0)
+        st = self._L.pc_hip_scan_wait(self._h, C.byref(ms))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_scan_wait", st)
+        r = _scan_fetch(self._L.pc_hip_scan_totals, self._h, n_pts, self.problem.n_energies, getattr(self, "_weight_squares", False))
+        r["kernel_ms"] = float(ms.value)
+        return r
 
     def device_synchronize(self):
         """hipDeviceSynchronize on the context's device (every stream)."""
@@ -301,6 +324,24 @@ class TraceGroup:
         st = self._L.pc_hip_group_set_option(self._h, name.encode(), int(value))
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_group_set_option", st)
+        if name == "weight_squares":
+            self._weight_squares = bool(value)
+
+    def scan(self, seed, points, n_per_point, max_attempts=1, slot0=0):
+        """TraceContext.scan over the group: the flat range [0, P * n_per_point) is split into one contiguous piece per member
+        (pc_hip_group_scan_run) and the members' totals are added exactly; kernel_ms is the longest member's."""
+        pts = _scan_array(points, self.problem)
+        n_pts = pts.shape[0]
+        st = self._L.pc_hip_group_scan_run(self._h, int(seed), int(slot0), dptr(pts), n_pts, int(n_per_point), int(max_attempts))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_group_scan_run", st)
+        ms = C.c_float(0)
+        st = self._L.pc_hip_group_scan_wait(self._h, C.byref(ms))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_group_scan_wait", st)
+        r = _scan_fetch(self._L.pc_hip_group_scan_totals, self._h, n_pts, self.problem.n_energies, getattr(self, "_weight_squares", False))
+        r["kernel_ms"] = float(ms.value)
+        return r
 
     def last_kernels(self):
         """Names of the kernels that traced the members' shares of the last run."""
@@ -425,6 +466,53 @@ class SpotMap:
             raise HipError("pc_hip_spot_read", st)
         return dict(bins=bins, outside=out, n_entries=int(n.value), maps=bins.astype(np.float64) * 2.0 ** -32,
                     outside_map=out.astype(np.float64) * 2.0 ** -32)
+
+
+def scan_points(x=(0.,), y=(0.,), d_source=None):
+    """Points of a scan, [len(d) * len(y) * len(x), 3] rows of (d_source, src_shiftx, src_shifty) in cm: the grid of the axes with
+    x varying fastest, then y, then d_source (row = (id * len(y) + iy) * len(x) + ix).  d_source None = the problem's own (NaN
+    in the rows, filled in by scan()); a number or a sequence of them otherwise."""
+    xs = np.atleast_1d(np.asarray(x, dtype=np.float64)).ravel()
+    ys = np.atleast_1d(np.asarray(y, dtype=np.float64)).ravel()
+    ds = np.array([np.nan]) if d_source is None else np.atleast_1d(np.asarray(d_source, dtype=np.float64)).ravel()
+    d, yy, xx = np.meshgrid(ds, ys, xs, indexing="ij")
+    return np.stack([d.ravel(), xx.ravel(), yy.ravel()], axis=1)
+
+
+def _scan_array(points, problem):
+    pts = np.array(points, dtype=np.float64, order="C", copy=True)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("scan points must be an array [P, 3] of (d_source, src_shiftx, src_shifty)")
+    pts[np.isnan(pts[:, 0]), 0] = problem.source[0]
+    return pts
+
+
+def _scan_fetch(fn, h, n_pts, ne, squares):
+    cnt = np.zeros((n_pts, 6), dtype=np.int64)
+    a = np.zeros((n_pts, ne, 2), dtype=np.uint64)
+    b = np.zeros((n_pts, ne, 2), dtype=np.uint64) if squares else None
+    u64p = C.POINTER(C.c_uint64)
+    st = fn(h, cnt.ctypes.data_as(c_int64_p), a.ctypes.data_as(u64p), b.ctypes.data_as(u64p) if squares else None)
+    if st != _cabi.PC_HIP_OK:
+        raise HipError(fn.__name__, st)
+    eff, err = scan_efficiencies(cnt, a, b)
+    return dict(counters=cnt, sumw_fixed=a, sumw2_fixed=b, efficiencies=eff, stderr=err)
+
+
+def scan_efficiencies(counters, sumw_fixed, sumw2_fixed=None):
+    """Per-row efficiencies [P, ne] and (with sumw2_fixed) standard errors of a scan's totals (pc_hip_scan_efficiencies):
+    counters [P, 6], sumw_fixed / sumw2_fixed [P, ne, 2].  A row where nothing entered a capillary has efficiency 0."""
+    cnt = np.ascontiguousarray(counters, dtype=np.int64).reshape(-1, 6)
+    n_pts = cnt.shape[0]
+    a = np.ascontiguousarray(sumw_fixed, dtype=np.uint64).reshape(n_pts, -1)
+    ne = a.shape[1] // 2
+    b = None if sumw2_fixed is None else np.ascontiguousarray(sumw2_fixed, dtype=np.uint64).reshape(n_pts, 2 * ne)
+    eff = np.zeros((n_pts, ne))
+    err = None if b is None else np.zeros((n_pts, ne))
+    u64p = C.POINTER(C.c_uint64)
+    _cabi.lib().pc_hip_scan_efficiencies(ne, n_pts, cnt.ctypes.data_as(c_int64_p), a.ctypes.data_as(u64p),
+                                         None if b is None else b.ctypes.data_as(u64p), dptr(eff), None if err is None else dptr(err))
+    return eff, err
 
 
 def efficiencies(sum_weights, counters):
