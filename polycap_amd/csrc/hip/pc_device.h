@@ -861,16 +861,19 @@ PC_HD int pc_reflect_energy(const pc_energy_const &ec, const pc_refl_geom &g, do
  * factor: 291 energies x 21 reflections per started photon.  FORM 3 is the same reflectivity (polycap_refl_polar,
  * src/polycap-capil.c:497-545) written for that loop:
  *   - g = n csq = sqrt(n^2 - sin^2) is formed directly: z = g^2 = (cos^2 - d2) + i n2_im with d2 = 1 - Re n^2 kept as a
- *     constant of its own (no 1 - (1 + 2 delta)(1 - cos^2): the reference's cancellation is not reproduced, the result is
- *     closer to the exact value than the reference's own), Im z is a constant >= 0, so no sign handling and |z|^2 is one
- *     fma; the complex product n * csq of FORMs 0-2 disappears;
+ *     constant of its own (no 1 - (1 + 2 delta)(1 - cos^2): the reference's cancellation is not reproduced; near the critical
+ *     angle, where FORMs 0/1 lose up to 2e-5 relative, the result is far closer to the exact value; at steep angles, where
+ *     R < 1e-6 and c - g cancels here instead, it is at most 1e-15 further away), Im z is a constant >= 0, so no sign handling
+ *     and |z|^2 is one fma; the complex product n * csq of FORMs 0-2 disappears;
  *   - everything is carried multiplied by S = 2 max(Re g, Im g) = sqrt(2Q), Q = |z| + |Re z|: S g = (Q, Im z) or (Im z, Q);
  *   - r_s = (cos - g)/(cos + g), r_p = (g - n^2 cos)/(g + n^2 cos) (:507-515 multiplied by n);
  *   - the polarisation fractions fs = es2/sd2, fp = ep2/sd2 come per reflection (two IEEE divisions in the lane that
  *     reflects), so rtot = (fs Ns Dp + fp Np Ds)/(Ds Dp): one reciprocal;
  *   - on the device the two roots come from v_rsq_f64 and the quotient from v_rcp_f64 (2^-24, scripts/analysis/fp64_rates.hip)
- *     with one Newton step each (~4e-15 relative); |z|^2 >= zi2 >= 2^-200 keeps them finite.  The host compile evaluates
- *     the same expressions with IEEE sqrt and division.
+ *     with one Newton step each (measured: 3.9e-15 and 2.0e-15 relative); |z|^2 >= zi2 >= 2^-200 keeps them finite.  The host
+ *     compile evaluates the same expressions with IEEE sqrt and division.  Like any rounding of the inputs, the roots' error is
+ *     amplified by the conditioning of R: near the critical angle the device's factors differ from the host's by up to 2.1e-12
+ *     relative at R >= 1e-6, everywhere within 20 eps of the condition sum of the exact value (tests/test_gpu_devmath.py).
  * 45 instructions per energy and reflection (FORM 2, round 3: 57).  The weights differ from FORMs 0/1 by the reference's own
  * rounding noise (~1e-10 relative near the critical angle, where 1 - sin^2/n^2 cancels); the trajectory does not depend on
  * them.  Callers guarantee ec.valid != 0 (runs with an invalid energy keep FORM 1). */
@@ -905,10 +908,14 @@ PC_HD double pc_div_fast(double a, double b)
 #endif
 }
 
-/* exp(x) for x <= 0 (the roughness factor exp(-(c alfa)^2)): 2^k e^r with |r| <= ln2/2 and a degree-11 polynomial, 6e-15 */
+/* exp(x) for x <= 0 (the roughness factor exp(-(c alfa)^2)): 2^k e^r with |r| <= ln2/2 and a degree-11 polynomial, < 1e-14
+ * relative where the result is normal (tests/test_gpu_devmath.py).  Arguments below -746 (exp rounds to 0 there) are clamped to
+ * it: sig_rough has no upper bound, and far down the reduction loses r (|x| ~ 1e44 made the polynomial overflow to inf, -inf
+ * gave NaN) */
 PC_HD double pc_exp_neg_fast(double x)
 {
 #if PC_FAST_MATH_DEVICE
+	x = fmax(x, -746.0);
 	const double k = rint(x*1.4426950408889634074);
 	double r = fma(-k, 6.93147180369123816490e-01, x);
 	r = fma(-k, 1.90821492927058770002e-10, r);
@@ -965,7 +972,8 @@ PC_HD double pc_fresnel3(double d2, double n2r, double n2i, double zi2, double c
  * register-weight kernels of SOURCE runs multiply with (pc_reflect<NE, true>).  A photon's trajectory does not depend on its
  * weights, so these runs trace the same photons as with FORMs 0/1 -- counters and image planes bit for bit -- and their weights
  * differ from the IEEE forms by the reference's own rounding noise (1e-10 relative near the critical angle) and from the host
- * compile of this form by the device's reciprocal / reciprocal square root + Newton (4e-15 per factor).  47 instructions
+ * compile of this form by the device's reciprocal / reciprocal square root + Newton (a few 1e-15 per factor where R is well
+ * conditioned, up to 2.1e-12 near the critical angle).  47 instructions
  * against ~100 of FORM 0 with its two correctly rounded square roots and two divisions.  polycap_photon_launch (explicit
  * photons, where callers compare per photon) keeps FORMs 0/1. */
 PC_HD double pc_fresnel3s(double d2, double n2r, double n2i, double zi2, double cr2, double c2, double es2, double ep2, double sd2)

@@ -1283,7 +1283,8 @@ static size_t pc_ne0_dyn_lds(size_t ne, int lds_acc, int lds_ec, size_t acc_word
  *     rejected by the reference's range test (src/polycap-capil.c:633-637) and every weight only falls.  Found by evaluating
  *     1 - R_s = 4 c Re(g) / |c + g|^2 and 1 - R_p = 4 c Re(conj(g) n^2) / |g + n^2 c|^2, g = sqrt(n^2 - sin^2) from the device's own
  *     constants (pc_fresnel3), in extended precision on 64 points per decade of c from 1 down to 1e-13, per energy: ct_tame =
- *     4 x the largest grid point at which some energy comes closer than 1e-11 (the device's factors are good to ~2e-14).
+ *     4 x the largest grid point at which some energy comes closer than 1e-11 (the device's factors are within 2.1e-12 relative of
+ *     the host's at R >= 1e-6; tests/test_gpu_devmath.py checks that they stay below 1 - 1e-12 above ct_tame).
  *     Below the critical angle 1 - R ~ 4 c beta / (2 delta)^1.5, so for glass ct_tame ~ 1e-11.
  *   proxies -- the energies that reflect best at 3 and at 30 mrad (roughness included): the last ones to fall below 1e-4. */
 static void pc_sweep_certificate(pc_hip_ctx *ctx)

@@ -1,0 +1,96 @@
+/*
+ * probe.hip -- TEST-ONLY: the arithmetic of pc_device.h on the device, element by element (tests/test_gpu_devmath.py).
+ *
+ * One kernel per primitive or Fresnel form (pc_probe_eval<OP>, tests/devmath/probe_ops.h); the per-energy constants come from
+ * the product's own setup (pc_build_tables, pc_problem.h) of the problem passed in.  Built by tests/devmath/pyprobe.py with the
+ * library's flags (polycap_amd._build.HIPFLAGS) into tests/devmath/libpc_probe.so; never part of libpolycap.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "pc_problem.h"
+#include "probe_ops.h"
+
+namespace {
+
+template <int OP>
+__global__ void __launch_bounds__(256) pc_probe_kernel(int64_t n_groups, const pc_energy_const *__restrict__ ec,
+                                                       const int32_t *__restrict__ e, const double *__restrict__ in,
+                                                       double *__restrict__ out, int32_t *__restrict__ code)
+{
+	constexpr int G = (OP == PC_PROBE_F3X2) ? 2 : 1;
+	const int64_t t = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if (t >= n_groups) return;
+	const int64_t i = t*G;
+	int cd[G];
+	double o[2*G];
+	pc_probe_eval<OP>(ec[e[i]], in + i*PC_PROBE_IN, o, cd);
+	for (int j = 0; j < G; j++) {
+		out[2*(i + j)] = o[2*j]; out[2*(i + j) + 1] = o[2*j + 1];
+		code[i + j] = cd[j];
+	}
+}
+
+template <int OP>
+void launch(int64_t n_groups, const pc_energy_const *ec, const int32_t *e, const double *in, double *out, int32_t *code)
+{
+	const unsigned blocks = (unsigned)((n_groups + 255)/256);
+	hipLaunchKernelGGL(pc_probe_kernel<OP>, dim3(blocks), dim3(256), 0, 0, n_groups, ec, e, in, out, code);
+}
+
+typedef void (*launch_fn)(int64_t, const pc_energy_const *, const int32_t *, const double *, double *, int32_t *);
+const launch_fn LAUNCH[PC_PROBE_NOPS] = {
+	launch<0>, launch<1>, launch<2>, launch<3>, launch<4>, launch<5>, launch<6>, launch<7>, launch<8>, launch<9>, launch<10>,
+	launch<11>, launch<12>};
+
+} // namespace
+
+extern "C" {
+
+/* Evaluates op on n elements: e[n] energy indices, in[n][PC_PROBE_IN], out[n][2], code[n] (host arrays).  Returns 0, -2 on
+ * invalid arguments, -3 on a HIP error (message in err[256]). */
+__attribute__((visibility("default")))
+int probe_run(const pc_hip_problem *p, int op, int64_t n, const int32_t *e, const double *in, double *out, int32_t *code,
+              char *err)
+{
+	err[0] = 0;
+	pc_host_tables t;
+	std::string msg;
+	if (pc_build_tables(p, t, msg)) { snprintf(err, 256, "%s", msg.c_str()); return -2; }
+	if (pc_probe_check(op, n, e, (int)t.ec.size())) { snprintf(err, 256, "invalid op, size or energy index"); return -2; }
+	if (n == 0) return 0;
+	pc_energy_const *d_ec = nullptr;
+	int32_t *d_e = nullptr, *d_code = nullptr;
+	double *d_in = nullptr, *d_out = nullptr;
+	int rc = 0;
+	hipError_t s = hipSuccess;
+#define PC_PROBE_TRY(call) do { if (s == hipSuccess) { s = (call); if (s != hipSuccess) snprintf(err, 256, "%s: %s", #call, hipGetErrorString(s)); } } while (0)
+	const size_t ne = t.ec.size();
+	PC_PROBE_TRY(hipMalloc(&d_ec, ne*sizeof(pc_energy_const)));
+	PC_PROBE_TRY(hipMalloc(&d_e, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_code, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_in, n*PC_PROBE_IN*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_out, n*2*sizeof(double)));
+	PC_PROBE_TRY(hipMemcpy(d_ec, t.ec.data(), ne*sizeof(pc_energy_const), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_e, e, n*sizeof(int32_t), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_in, in, n*PC_PROBE_IN*sizeof(double), hipMemcpyHostToDevice));
+	if (s == hipSuccess) {
+		LAUNCH[op](n/pc_probe_group(op), d_ec, d_e, d_in, d_out, d_code);
+		PC_PROBE_TRY(hipGetLastError());
+	}
+	PC_PROBE_TRY(hipDeviceSynchronize());
+	PC_PROBE_TRY(hipMemcpy(out, d_out, n*2*sizeof(double), hipMemcpyDeviceToHost));
+	PC_PROBE_TRY(hipMemcpy(code, d_code, n*sizeof(int32_t), hipMemcpyDeviceToHost));
+	if (s != hipSuccess) rc = -3;
+	/* frees run whatever happened above; their status is reported only when everything before succeeded */
+	const hipError_t f[5] = {hipFree(d_ec), hipFree(d_e), hipFree(d_code), hipFree(d_in), hipFree(d_out)};
+	for (int j = 0; j < 5 && rc == 0; j++)
+		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
+#undef PC_PROBE_TRY
+	return rc;
+}
+
+} // extern "C"

@@ -1,0 +1,97 @@
+"""TEST-ONLY: the arithmetic of pc_device.h element by element, on the device (probe.hip) or in the host compile of the same header
+(tests/emul/pc_emul.cpp, IEEE sqrt, division and exp).  Both take the per-energy constants from the product's own setup
+(pc_build_tables) of the Problem passed in."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from polycap_amd._cabi import ProblemS, c_double_p
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(os.path.dirname(_HERE))
+SO = os.path.join(_HERE, "libpc_probe.so")
+_LIB = None
+
+OPS = dict(sqrt=0, div=1, exp=2, f3=3, f3s=4, f3x1=5, f3x2=6, ff0=7, ff1=8, re_fast=9, re3=10, re0=11, re1=12)
+GROUP = dict(f3x2=2)              # elements one device thread evaluates (one energy per group)
+# columns of the input rows (probe_ops.h)
+COLS = ("c", "st2", "es2", "ep2", "sd2", "fs", "fp", "w")
+EC_FIELDS = ("n_re", "n_im", "ninv2_re", "ninv2_im", "rough_c", "valid", "d2", "n2_re", "n2_im", "zi2", "rough_k2")
+
+
+def _sources():
+    hip = os.path.join(_ROOT, "polycap_amd", "csrc", "hip")
+    return [os.path.join(_HERE, "probe.hip"), os.path.join(_HERE, "probe_ops.h"),
+            os.path.join(hip, "pc_device.h"), os.path.join(hip, "pc_problem.h"), os.path.join(_ROOT, "include", "polycap-hip.h")]
+
+
+def compile_cmd(out=SO):
+    """hipcc with the library's own code generation (polycap_amd._build.HIPFLAGS: -O3 -ffp-contract=off, gfx950)."""
+    from polycap_amd import _build
+    return ["hipcc"] + _build.HIPFLAGS + ["-I" + _HERE, "-shared", "-o", out, _sources()[0]]
+
+
+def build(force=False):
+    """Builds libpc_probe.so when it is missing or older than its sources; returns its path."""
+    srcs = _sources()
+    if force or not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in srcs):
+        tmp = SO + ".%d.tmp" % os.getpid()
+        subprocess.check_call(compile_cmd(tmp))
+        os.replace(tmp, SO)
+    return SO
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        L = C.CDLL(build())
+        L.probe_run.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                C.POINTER(C.c_int32), C.c_char_p]
+        L.probe_run.restype = C.c_int
+        _LIB = L
+    return _LIB
+
+
+def rows(n, **cols):
+    """Input rows [n, 8]: named columns (COLS) broadcast to n, the rest 0 (w defaults to 1)."""
+    x = np.zeros((n, len(COLS)))
+    x[:, COLS.index("w")] = 1.0
+    for k, v in cols.items():
+        x[:, COLS.index(k)] = v
+    return x
+
+
+def run(problem, op, e, x, device=True):
+    """Evaluates op on the rows x [n, 8] at energy indices e [n] of `problem`: (out [n, 2], code [n]).  device=False: the
+    host compile of the same call."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, len(COLS))
+    n = x.shape[0]
+    e = np.ascontiguousarray(np.broadcast_to(np.asarray(e, dtype=np.int32), (n,)))
+    out = np.zeros((n, 2))
+    code = np.zeros(n, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    if device:
+        err = C.create_string_buffer(256)
+        r = lib().probe_run(C.byref(problem.s), OPS[op], n, e.ctypes.data_as(ip), x.ctypes.data_as(c_double_p),
+                            out.ctypes.data_as(c_double_p), code.ctypes.data_as(ip), err)
+        if r:
+            raise RuntimeError("probe_run(%s) failed: %d %s" % (op, r, err.value.decode(errors="replace")))
+    else:
+        from tests.emul import pyemul
+        r = pyemul.lib().emul_probe_run(C.byref(problem.s), OPS[op], n, e.ctypes.data_as(ip), x.ctypes.data_as(c_double_p),
+                                        out.ctypes.data_as(c_double_p), code.ctypes.data_as(ip))
+        if r:
+            raise RuntimeError("emul_probe_run(%s) failed: %d" % (op, r))
+    return out, code
+
+
+def energy_consts(problem):
+    """pc_energy_const of every energy as pc_build_tables makes it: dict of arrays named after the struct's fields."""
+    from tests.emul import pyemul
+    a = np.zeros((problem.n_energies, len(EC_FIELDS)))
+    r = pyemul.lib().emul_energy_consts(C.byref(problem.s), a.ctypes.data_as(c_double_p))
+    if r:
+        raise RuntimeError("emul_energy_consts failed: %d" % r)
+    return {k: a[:, j].copy() for j, k in enumerate(EC_FIELDS)}

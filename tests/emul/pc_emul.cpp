@@ -18,6 +18,7 @@
 
 #include "pc_problem.h"
 #include "pc_leak.h"
+#include "../devmath/probe_ops.h"
 
 namespace {
 
@@ -315,6 +316,34 @@ int emul_sample(const pc_hip_problem *p, uint64_t seed, int64_t n, const int64_t
 		o[0]=s.x; o[1]=s.y; o[2]=s.z; o[3]=s.dx; o[4]=s.dy; o[5]=s.dz; o[6]=s.ex; o[7]=s.ey; o[8]=s.ez;
 		o[9]=s.srcx; o[10]=s.srcy; o[11]=0.;
 	}
+	return 0;
+}
+
+/* the host (IEEE) build of tests/devmath/probe.hip's probe_run: the same op on the same inputs, same layout and codes */
+int emul_probe_run(const pc_hip_problem *p, int op, int64_t n, const int32_t *e, const double *in, double *out, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_check(op, n, e, (int)E.t.ec.size())) return -2;
+	typedef void (*eval_fn)(const pc_energy_const &, const double *, double *, int *);
+	static const eval_fn EVAL[PC_PROBE_NOPS] = {
+		pc_probe_eval<0>, pc_probe_eval<1>, pc_probe_eval<2>, pc_probe_eval<3>, pc_probe_eval<4>, pc_probe_eval<5>, pc_probe_eval<6>,
+		pc_probe_eval<7>, pc_probe_eval<8>, pc_probe_eval<9>, pc_probe_eval<10>, pc_probe_eval<11>, pc_probe_eval<12>};
+	const int G = pc_probe_group(op);
+	for (int64_t i = 0; i < n; i += G)
+		EVAL[op](E.t.ec[e[i]], in + i*PC_PROBE_IN, out + 2*i, code + i);
+	return 0;
+}
+
+/* the per-energy constants pc_build_tables derives (struct pc_energy_const, field by field): ne x 11 doubles */
+int emul_energy_consts(const pc_hip_problem *p, double *out)
+{
+	static_assert(sizeof(pc_energy_const) == 11*sizeof(double), "pc_energy_const is 11 doubles");
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	memcpy(out, E.t.ec.data(), E.t.ec.size()*sizeof(pc_energy_const));
 	return 0;
 }
 

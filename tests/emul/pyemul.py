@@ -20,7 +20,8 @@ def lib():
         srcs = [os.path.join(_HERE, "pc_emul.cpp"),
                 os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_device.h"),
                 os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_problem.h"),
-                os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_leak.h")]
+                os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_leak.h"),
+                os.path.join(_ROOT, "tests", "devmath", "probe_ops.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
                                    "-ffp-contract=off", "-mfma", "-fopenmp",   # same IEEE operation sequence as the gfx950 build (fma only where written)
@@ -44,6 +45,11 @@ def lib():
         L.emul_transmission.restype = C.c_int
         L.emul_sample.argtypes = [C.POINTER(ProblemS), C.c_uint64, C.c_int64, c_int64_p, C.POINTER(C.c_uint32), c_double_p]
         L.emul_sample.restype = C.c_int
+        L.emul_probe_run.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                     C.POINTER(C.c_int32)]
+        L.emul_probe_run.restype = C.c_int
+        L.emul_energy_consts.argtypes = [C.POINTER(ProblemS), c_double_p]
+        L.emul_energy_consts.restype = C.c_int
         _LIB = L
     return _LIB
 

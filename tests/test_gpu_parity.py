@@ -407,7 +407,7 @@ def test_command_line_program(pa, tmp_path):
 
 def _same_photons_weights_to_rounding(g, e, rtol=1e-11):
     """Kernels whose weights live in memory (more than 8 energies, or several on a long profile) evaluate the Fresnel factor
-    in FORM 3 of pc_device.h with the hardware reciprocal square root / reciprocal + one Newton step (4e-15 per factor); the
+    in FORM 3 of pc_device.h with the hardware reciprocal square root / reciprocal + one Newton step (a few 1e-15 per factor, tests/test_gpu_devmath.py); the
     host compile evaluates the same expressions with IEEE sqrt and division.  The trajectory does not depend on the weights
     (only the "no weight above 1e-4 left" decision does): everything but the weights is identical bit for bit, the weights to
     accumulated rounding."""
