@@ -56,9 +56,8 @@ struct pc_hip_group {
 	std::vector<long long> first, count;       /* slot range of every member in the last run */
 	bool distinct = true;                       /* no device twice: the members can form one RCCL communicator */
 	std::vector<pc_nccl_comm> comms;
-	std::vector<long long *> d_vec;             /* per member: packed totals on its device, 6 + 4 n_energies int64 (6 + 8 n_energies with
+	std::vector<pc_dev_buf<long long>> d_vec;   /* per member: packed totals on its device, 6 + 4 n_energies int64 (6 + 8 n_energies with
 	                                             * option "weight_squares") */
-	size_t d_vec_len = 0;                       /* int64 that every d_vec[k] holds */
 	int weight_squares = 0;                     /* option "weight_squares" of the members */
 	int run_squares = 0;                        /* the last run summed the squared weights */
 	std::vector<uint64_t> sumw2;                /* their group sums, [2*n_energies], made by the last pc_hip_group_totals */
@@ -105,7 +104,7 @@ void pc_hip_group_destroy(pc_hip_group *g)
 	for (size_t k = 0; k < g->comms.size(); k++)
 		if (g->comms[k] && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comms[k]);
 	for (size_t k = 0; k < g->d_vec.size(); k++)
-		if (g->d_vec[k]) { (void)hipSetDevice(g->devices[k]); (void)hipFree(g->d_vec[k]); }
+		if (g->d_vec[k]) { (void)hipSetDevice(g->devices[k]); g->d_vec[k].reset(); }
 	for (pc_hip_ctx *c : g->ctx) pc_hip_ctx_destroy(c);
 	delete g;
 }
@@ -351,17 +350,13 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 		}
 	}
 	if (use_rccl) {
-		if (g->d_vec.empty() || g->d_vec_len < len) {
-			for (size_t k = 0; k < g->d_vec.size(); k++)
-				if (g->d_vec[k]) { PC_HIP_CHECK(hipSetDevice(g->devices[k])); PC_HIP_CHECK(hipFree(g->d_vec[k])); }
-			g->d_vec.assign(N, nullptr);
-			g->d_vec_len = 0;
-			for (size_t k = 0; k < N; k++) {
+		g->d_vec.resize(N);
+		for (size_t k = 0; k < N; k++)
+			if (g->d_vec[k].cap < len) {
 				PC_HIP_CHECK(hipSetDevice(g->devices[k]));
-				PC_HIP_CHECK(hipMalloc(&g->d_vec[k], len*sizeof(long long)));
+				const int st = g->d_vec[k].grow(len, "pc_hip_group_totals: could not allocate the packed totals");
+				if (st) return st;
 			}
-			g->d_vec_len = len;
-		}
 		const int threads = 64, blocks = (int)((std::max<size_t>(n_sums, 6) + threads - 1)/threads);
 		for (size_t k = 0; k < N; k++) {
 			PC_HIP_CHECK(hipSetDevice(g->devices[k]));

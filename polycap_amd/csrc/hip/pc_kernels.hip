@@ -1047,20 +1047,150 @@ static int pc_fail(int code, const std::string &msg)
 
 #define PC_MAX_PARTS 16
 
+/* Owners of the GPU resources of a context: each frees what it holds when it is reset or destroyed.  None of them switches
+ * devices; whoever resets or destroys one has made its device current. */
+
+/* device buffer of `cap` elements */
+template <typename T>
+struct pc_dev_buf {
+	T *p = nullptr;
+	size_t cap = 0;
+	pc_dev_buf() = default;
+	pc_dev_buf(pc_dev_buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	pc_dev_buf &operator=(pc_dev_buf &&o) noexcept
+	{
+		if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+		return *this;
+	}
+	~pc_dev_buf() { reset(); }
+	operator T *() const { return p; }
+	T *operator->() const { return p; }
+	void reset()
+	{
+		if (p) (void)hipFree(p);
+		p = nullptr; cap = 0;
+	}
+	/* at least `elems` elements: unless it has them, the buffer is replaced (contents lost) by one of max(elems, alloc).  A refused
+	 * allocation leaves it empty and no HIP error stored, and is PC_HIP_ERR_MEMORY with `msg`. */
+	int grow(size_t elems, const char *msg, size_t alloc = 0)
+	{
+		if (cap >= elems) return PC_HIP_OK;
+		T *old = p;
+		p = nullptr; cap = 0;
+		if (old) PC_HIP_CHECK(hipFree(old));
+		const size_t n = std::max(elems, alloc);
+		if (hipMalloc(&p, n*sizeof(T)) != hipSuccess) {
+			(void)hipGetLastError();
+			p = nullptr;
+			return pc_fail(PC_HIP_ERR_MEMORY, msg);
+		}
+		cap = n;
+		return PC_HIP_OK;
+	}
+};
+
+/* host buffer of `cap` elements in one of three shapes: pinned, or plain memory when pinning is refused (locked-memory limit);
+ * pinned only; mapped into the device (coherent if the runtime grants it), with its device address `dev` */
+enum pc_pin_kind { PC_PIN_OR_PLAIN, PC_PIN_ONLY, PC_PIN_MAPPED };
+
+template <typename T, pc_pin_kind KIND>
+struct pc_host_buf {
+	T *p = nullptr;
+	T *dev = nullptr;
+	size_t cap = 0;
+	bool pinned = false;
+	pc_host_buf() = default;
+	pc_host_buf(const pc_host_buf &) = delete;
+	pc_host_buf &operator=(const pc_host_buf &) = delete;
+	~pc_host_buf() { reset(); }
+	operator T *() const { return p; }
+	void reset()
+	{
+		if (p) { if (pinned) (void)hipHostFree(p); else free(p); }
+		p = dev = nullptr; cap = 0; pinned = false;
+	}
+	/* as pc_dev_buf::grow */
+	int grow(size_t elems, const char *msg, size_t alloc = 0)
+	{
+		if (cap >= elems) return PC_HIP_OK;
+		T *old = p;
+		const bool old_pinned = pinned;
+		p = dev = nullptr; cap = 0; pinned = false;
+		if (old && old_pinned) PC_HIP_CHECK(hipHostFree(old));
+		else free(old);
+		const size_t n = std::max(elems, alloc);
+		void *q = nullptr;
+		hipError_t e;
+		if (KIND == PC_PIN_MAPPED) {
+			e = hipHostMalloc(&q, n*sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
+			if (e != hipSuccess) { (void)hipGetLastError(); e = hipHostMalloc(&q, n*sizeof(T), hipHostMallocMapped); }
+		} else
+			e = hipHostMalloc(&q, n*sizeof(T), hipHostMallocDefault);
+		pinned = e == hipSuccess;
+		if (!pinned) {
+			(void)hipGetLastError();
+			/* no pinned memory to be had: copies then go through the runtime's own staging, slower but correct */
+			q = (KIND == PC_PIN_OR_PLAIN) ? malloc(n*sizeof(T)) : nullptr;
+			if (!q) return pc_fail(PC_HIP_ERR_MEMORY, msg);
+		}
+		p = (T *)q;
+		cap = n;
+		if (KIND == PC_PIN_MAPPED) {
+			e = hipHostGetDevicePointer((void **)&dev, p, 0);
+			if (e != hipSuccess) { reset(); return pc_fail(PC_HIP_ERR_RUNTIME, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e)); }
+		}
+		return PC_HIP_OK;
+	}
+};
+
+/* stream, created on first use: non-blocking, at the device's greatest priority when `high` and the device has priorities */
+struct pc_stream_handle {
+	hipStream_t s = nullptr;
+	pc_stream_handle() = default;
+	pc_stream_handle(const pc_stream_handle &) = delete;
+	pc_stream_handle &operator=(const pc_stream_handle &) = delete;
+	~pc_stream_handle() { if (s) (void)hipStreamDestroy(s); }
+	operator hipStream_t() const { return s; }
+	hipError_t ensure(bool high = false)
+	{
+		if (s) return hipSuccess;
+		int least = 0, greatest = 0;
+		if (high) {
+			if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least
+			    && hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) == hipSuccess)
+				return hipSuccess;
+			(void)hipGetLastError();
+		}
+		return hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+	}
+};
+
+/* event, created on first use */
+struct pc_event_handle {
+	hipEvent_t e = nullptr;
+	pc_event_handle() = default;
+	pc_event_handle(const pc_event_handle &) = delete;
+	pc_event_handle &operator=(const pc_event_handle &) = delete;
+	~pc_event_handle() { if (e) (void)hipEventDestroy(e); }
+	operator hipEvent_t() const { return e; }
+	hipError_t ensure(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+};
+
 struct pc_hip_ctx {
+	pc_stream_handle main_stream;          /* first: destroyed after everything that may still be queued on it */
 	int device = 0;
 	int n_cu = 256;
 	int cu_share = 1;              /* option "cu_share": the context's launches fill n_cu / cu_share compute units.  Tried for device groups that list
 	                                * a device m times (m kernels side by side on a quarter of the CUs each): the kernels of one process's streams
 	                                * did not overlap (21.7 ms against 15.1 ms one after the other, xos1 5e6 slots, 4 members), so groups leave it at 1 */
-	hipStream_t stream = nullptr;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	hipStream_t stream = nullptr;          /* where the launch helpers enqueue: main_stream, or stream2 for the odd parts of a run */
+	pc_event_handle ev0, ev1;
 	pc_host_tables host;
-	double *d_tables = nullptr;            /* z, cap, zh, cap2, hexd, idz, ext: 7 x npts */
-	pc_energy_const *d_ec = nullptr;
-	double *d_ec_soa = nullptr;
-	pc_marg4 *d_mg = nullptr;              /* block-certificate records, npts */
-	pc_drdev *d_dr = nullptr;              /* leak path: chord deviations of cap, npts */
+	pc_dev_buf<double> d_tables;           /* z, cap, zh, cap2, hexd, idz, ext: 7 x npts */
+	pc_dev_buf<pc_energy_const> d_ec;
+	pc_dev_buf<double> d_ec_soa;
+	pc_dev_buf<pc_marg4> d_mg;             /* block-certificate records, npts */
+	pc_dev_buf<pc_drdev> d_dr;             /* leak path: chord deviations of cap, npts */
 	/* options */
 	int literal = 0;
 	int event_threshold = 48;      /* lanes that must be marching for a MARCH burst to run before the waiting EVENTs.  With the short flights of
@@ -1106,39 +1236,34 @@ struct pc_hip_ctx {
 	                                * EXACT loop, so that sweep passes that mix EXACT and FAST photons are common (0 = off) */
 	int weight_squares = 0;        /* option "weight_squares": source runs also sum the squared exit weights (pc_kargs::sumw2) */
 	int run_squares = 0;           /* the last run did so (pc_hip_transmission_moments) */
-	double *d_rlog = nullptr;
-	size_t rlog_elems = 0;
+	pc_dev_buf<double> d_rlog;
 	int sweep_cert = 0;            /* pc_sweep_certificate has run */
 	double sweep_ct_tame = 1.;
 	int sweep_n_proxy = 0, sweep_proxy_e[2] = {0, 0};
 	/* last run */
-	pc_totals *d_totals = nullptr;         /* pc_totals + 2*nE u64 weight sums + 2*nE u64 squared-weight sums */
+	pc_dev_buf<pc_totals> d_totals;        /* totals_bytes: pc_totals + 2*nE u64 weight sums + 2*nE u64 squared-weight sums */
 	size_t totals_bytes = 0;
-	double *d_img = nullptr;               /* image records: n_slots x (17 + n_energies) doubles */
-	double *h_stage = nullptr;             /* image fetches: two pinned chunks of records on the host */
-	size_t h_stage_elems = 0;
-	bool h_stage_pinned = false;           /* false: pinning was refused (locked-memory limit), plain memory is used instead */
-	hipEvent_t ev_fetch[2] = {nullptr, nullptr};
-	hipStream_t fetch_stream = nullptr;    /* copies of finished parts run beside the kernel of the next part */
-	hipStream_t fetch_stream_b = nullptr;  /* compact runs: the planes of a group of blocks alternate between two copy streams */
-	hipEvent_t ev_group[2][4] = {{nullptr}};   /* compact runs: end of a group of copies, per stream, ring of 4 */
-	hipStream_t stream2 = nullptr;         /* odd parts: a part's first workgroups start as the previous part's last ones leave */
-	unsigned long long *d_work = nullptr;  /* one work counter per part */
-	hipEvent_t ev_sync = nullptr;
+	pc_dev_buf<double> d_img;              /* image records: n_slots x (17 + n_energies) doubles */
+	pc_host_buf<double, PC_PIN_OR_PLAIN> h_stage; /* image fetches: two pinned chunks of records on the host */
+	pc_event_handle ev_fetch[2];
+	pc_stream_handle fetch_stream;         /* copies of finished parts run beside the kernel of the next part */
+	pc_stream_handle fetch_stream_b;       /* compact runs: the planes of a group of blocks alternate between two copy streams */
+	pc_event_handle ev_group[2][4];        /* compact runs: end of a group of copies, per stream, ring of 4 */
+	pc_stream_handle stream2;              /* odd parts: a part's first workgroups start as the previous part's last ones leave */
+	pc_dev_buf<unsigned long long> d_work; /* one work counter per part */
+	pc_event_handle ev_sync;
 	/* a transmission run can be cut into parts (kernel launches over consecutive slot ranges, same totals): the images of
 	 * a finished part are fetched while the next part is traced */
 	int run_parts = 1;
 	int n_parts = 1;
 	long long part_end[PC_MAX_PARTS] = {0};
-	hipEvent_t ev_part[PC_MAX_PARTS] = {nullptr};
+	pc_event_handle ev_part[PC_MAX_PARTS];
 	bool rec_ev0 = true, rec_ev1 = true;
 	int fetch_threads = 0;                 /* host threads that scatter a fetched chunk into the caller's planes; 0 = min(16, cores) */
-	long long img_slots = 0;
 	int img_valid = 0;
-	/* plane (SoA) copy of the image records on the device: 17 planes of soa_slots doubles, then the weights [slot][n_energies].
+	/* plane (SoA) copy of the image records on the device: 17 planes of the run's n_slots doubles, then the weights [slot][n_energies].
 	 * pc_hip_transmission_images copies from here straight into the caller's (registered) planes -- no host transposition */
-	double *d_soa = nullptr;
-	long long soa_slots = 0;
+	pc_dev_buf<double> d_soa;
 	int plane_images = 0;                  /* option "plane_images": runs that keep images write the planes themselves (no records) */
 	int run_planes = 0;                    /* the last run did so */
 	/* option "compact_images" (with plane_images): exit photons are stored in the order of completion, one coalesced run per
@@ -1154,17 +1279,12 @@ struct pc_hip_ctx {
 	                                        * copies all the blocks that are complete at a time in one go) */
 	int run_blk_shift = 16;
 	long long run_blocks = 0;
-	unsigned long long *d_cursor = nullptr;
-	unsigned int *d_blk_done = nullptr;
-	size_t blk_capacity = 0;
-	unsigned int *h_blk_flag = nullptr;    /* host memory mapped into the device: 1 when a block is complete */
-	unsigned int *d_blk_flag = nullptr;    /* its device address */
-	long long *d_ids = nullptr;
-	long long ids_slots = 0;
-	double *d_lane_start = nullptr;
-	size_t lane_start_elems = 0;
-	double *d_wscratch = nullptr;
-	size_t wscratch_elems = 0;
+	pc_dev_buf<unsigned long long> d_cursor;
+	pc_dev_buf<unsigned int> d_blk_done;
+	pc_host_buf<unsigned int, PC_PIN_MAPPED> h_blk_flag; /* mapped into the device (h_blk_flag.dev): 1 when a block is complete */
+	pc_dev_buf<long long> d_ids;
+	pc_dev_buf<double> d_lane_start;
+	pc_dev_buf<double> d_wscratch;
 	/* per-lane scratch (d_wscratch, d_rlog, d_lane_start) of a run cut into parts: launches on the two streams overlap, so the
 	 * buffers are allocated twice over (scratch_halves = 2), each half sized for the largest launch the run can make, and the
 	 * launches on stream2 use the second half (scratch_half = 1).  Set by the parts loop of pc_hip_transmission_run only. */
@@ -1173,9 +1293,8 @@ struct pc_hip_ctx {
 	/* explicit-photon calls (polycap_photon_launch, polycap_source_get_photon): one device buffer and one pinned host
 	 * buffer, kept between calls, so that a single photon costs two copies and a launch instead of ten copies and
 	 * as many allocations */
-	double *d_batch = nullptr, *h_batch = nullptr;
-	size_t batch_elems = 0;
-	bool h_batch_pinned = false;
+	pc_dev_buf<double> d_batch;
+	pc_host_buf<double, PC_PIN_OR_PLAIN> h_batch;
 	long long run_slots = 0;
 	int run_pending = 0;
 	float last_ms = 0.f;
@@ -1184,28 +1303,23 @@ struct pc_hip_ctx {
 	size_t leak_stack_bytes = (size_t)8 << 30;
 	long long leak_capacity = 0;           /* record buffer size of the next run; 0 = 8 per slot, grown on demand */
 	long long leak_capacity_used = 0;
-	double *d_leak_frames = nullptr;
-	size_t leak_frames_elems = 0;
-	double *d_leak_records = nullptr;
-	size_t leak_records_elems = 0;
-	unsigned long long *d_leak_cursor = nullptr;
-	double *d_amu = nullptr;
-	unsigned int *d_leak_attempts = nullptr;
-	unsigned long long *d_leak_timing = nullptr;   /* POLYCAP_LEAK_TIMING diagnostics */
-	size_t leak_timing_bytes = 0;
+	pc_dev_buf<double> d_leak_frames;
+	pc_dev_buf<double> d_leak_records;
+	pc_dev_buf<unsigned long long> d_leak_cursor;
+	pc_dev_buf<double> d_amu;              /* copied when it is allocated, once */
+	pc_dev_buf<unsigned int> d_leak_attempts;
+	pc_dev_buf<unsigned long long> d_leak_timing; /* POLYCAP_LEAK_TIMING diagnostics */
 	long long leak_timing_waves = 0;
-	unsigned int *d_leak_order = nullptr;  /* order in which the next leak run hands out its slots (pc_hip_leak_set_order) */
+	pc_dev_buf<unsigned int> d_leak_order; /* order in which the next leak run hands out its slots (pc_hip_leak_set_order); empty: none */
 	int leak_order = 1;                    /* option: 1 = source runs of >= 196608 slots order their slots by a plain pre-pass, 0 = slot order */
 	int leak_order_user = 0;               /* the order was set by the caller */
 	unsigned long long leak_order_seed = 0; long long leak_order_slot0 = -1; unsigned int leak_order_attempts = 0;   /* what the automatic order was made for */
-	unsigned int *d_work_est = nullptr; long long work_est_n = 0, leak_order_cap = 0;
+	pc_dev_buf<unsigned int> d_work_est;
 	int leak_ev0_done = 0;                 /* ev0 of the run in flight was recorded before its pre-pass */
 	long long leak_order_n = 0, leak_n_heavy = 0;
 	int leak_heavy_lanes = 1, leak_heavy_every = 1;
 	int leak_slot_units = 0;               /* option: keep the units of work per slot of leak runs (pc_hip_leak_slot_units) */
-	unsigned int *d_leak_slot_units = nullptr;
-	long long leak_slot_units_n = 0;
-	long long leak_attempt_slots = 0;
+	pc_dev_buf<unsigned int> d_leak_slot_units;
 	int leak_pending = 0;                  /* a leak transmission run is in flight: wait() collects its events */
 	unsigned long long leak_seed = 0;
 	long long leak_slot0 = 0, leak_n_slots = 0;
@@ -1213,21 +1327,17 @@ struct pc_hip_ctx {
 	int leak_keep_images = 0;
 	/* events of the last leak run in the reference's list order, PC_HIP_LEAK_HDR + n_energies doubles each: the extleak list, then
 	 * the intleak list, ordered on the device (pc_leak_collect) and kept in pinned host memory */
-	double *d_leak_out = nullptr, *h_leak_out = nullptr;
-	size_t leak_out_elems = 0;
-	void *d_leak_order_tmp = nullptr;
-	size_t leak_order_bytes = 0;
+	pc_dev_buf<double> d_leak_out;
+	pc_host_buf<double, PC_PIN_ONLY> h_leak_out;
+	pc_dev_buf<char> d_leak_order_tmp;
 	long long leak_n_ext = 0, leak_n_int = 0;
 	int leak_events_of_run = 0;            /* the event lists are those of the last source run (a leak run): pc_hip_spot_add may read them */
 	/* scans (pc_scan.h): buffers of their own, so that a scan leaves everything of the last run as it was */
-	pc_totals *d_scan_totals = nullptr;    /* work counter and scheduler statistics of the last scan launch */
-	unsigned long long *d_scan_tot = nullptr;   /* per point: 6 counters, 2*ne weight sums, 2*ne squared-weight sums (pc_kargs::sumw of a scan) */
-	size_t scan_tot_elems = 0;
-	pc_scan_point *d_scan_pts = nullptr;
-	size_t scan_pts_cap = 0;
-	double *d_scan_wscratch = nullptr;     /* more than 8 energies: the scan kernel's per-lane weights */
-	size_t scan_wscratch_elems = 0;
-	hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr;
+	pc_dev_buf<pc_totals> d_scan_totals;   /* work counter and scheduler statistics of the last scan launch */
+	pc_dev_buf<unsigned long long> d_scan_tot; /* per point: 6 counters, 2*ne weight sums, 2*ne squared-weight sums (pc_kargs::sumw of a scan) */
+	pc_dev_buf<pc_scan_point> d_scan_pts;
+	pc_dev_buf<double> d_scan_wscratch;    /* more than 8 energies: the scan kernel's per-lane weights */
+	pc_event_handle ev_scan0, ev_scan1;
 	long long scan_points = 0;             /* points of the last scan call (0: none yet) */
 	int scan_squares = 0;                  /* the last scan summed the squared weights */
 	int scan_pending = 0;                  /* the last scan has not been waited for */
@@ -1485,18 +1595,9 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 			const size_t lanes = (ctx->scratch_halves > 1) ? (size_t)pc_cus(ctx) * PCS_BLOCK : (size_t)a.total_threads;
 			const size_t half_w = (size_t)ne * lanes, half_l = 3*(size_t)log_cap * lanes;
 			const size_t need_w = half_w * (size_t)ctx->scratch_halves, need_l = half_l * (size_t)ctx->scratch_halves;
-			if (need_w > ctx->wscratch_elems) {
-				if (ctx->d_wscratch) PC_HIP_CHECK(hipFree(ctx->d_wscratch));
-				ctx->d_wscratch = nullptr; ctx->wscratch_elems = 0;
-				if (hipMalloc(&ctx->d_wscratch, need_w*sizeof(double)) != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "could not allocate the per-lane weight scratch");
-				ctx->wscratch_elems = need_w;
-			}
-			if (need_l > ctx->rlog_elems) {
-				if (ctx->d_rlog) PC_HIP_CHECK(hipFree(ctx->d_rlog));
-				ctx->d_rlog = nullptr; ctx->rlog_elems = 0;
-				if (hipMalloc(&ctx->d_rlog, need_l*sizeof(double)) != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "could not allocate the reflection logs");
-				ctx->rlog_elems = need_l;
-			}
+			int st = ctx->d_wscratch.grow(need_w, "could not allocate the per-lane weight scratch");
+			if (!st) st = ctx->d_rlog.grow(need_l, "could not allocate the reflection logs");
+			if (st) return st;
 			a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half_w;
 			a.rlog = ctx->d_rlog + (size_t)ctx->scratch_half * half_l;
 			a.log_cap = log_cap;
@@ -1537,13 +1638,8 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
 		/* one launch: its own lanes; parts: halves for the largest launch, the second one for the launches on stream2 */
 		const size_t half = (size_t)ne * ((ctx->scratch_halves > 1) ? (size_t)max_blocks * (size_t)block : (size_t)a.total_threads);
 		const size_t need = half * (size_t)ctx->scratch_halves;
-		if (need > ctx->wscratch_elems) {
-			if (ctx->d_wscratch) PC_HIP_CHECK(hipFree(ctx->d_wscratch));
-			ctx->d_wscratch = nullptr; ctx->wscratch_elems = 0;
-			hipError_t e = hipMalloc(&ctx->d_wscratch, need*sizeof(double));
-			if (e != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "could not allocate the per-lane weight scratch");
-			ctx->wscratch_elems = need;
-		}
+		int st = ctx->d_wscratch.grow(need, "could not allocate the per-lane weight scratch");
+		if (st) return st;
 		a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half;
 	}
 	if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
@@ -1578,54 +1674,7 @@ void pc_hip_ctx_destroy(pc_hip_ctx *ctx)
 {
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->device);
-	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-	if (ctx->d_ec) (void)hipFree(ctx->d_ec);
-	if (ctx->d_ec_soa) (void)hipFree(ctx->d_ec_soa);
-	if (ctx->d_mg) (void)hipFree(ctx->d_mg);
-	if (ctx->d_dr) (void)hipFree(ctx->d_dr);
-	if (ctx->d_totals) (void)hipFree(ctx->d_totals);
-	if (ctx->d_img) (void)hipFree(ctx->d_img);
-	if (ctx->d_soa) (void)hipFree(ctx->d_soa);
-	if (ctx->h_stage) { if (ctx->h_stage_pinned) (void)hipHostFree(ctx->h_stage); else free(ctx->h_stage); }
-	for (int k = 0; k < 2; k++) if (ctx->ev_fetch[k]) (void)hipEventDestroy(ctx->ev_fetch[k]);
-	for (int k = 0; k < PC_MAX_PARTS; k++) if (ctx->ev_part[k]) (void)hipEventDestroy(ctx->ev_part[k]);
-	if (ctx->fetch_stream) (void)hipStreamDestroy(ctx->fetch_stream);
-	if (ctx->fetch_stream_b) (void)hipStreamDestroy(ctx->fetch_stream_b);
-	for (int k = 0; k < 2; k++) for (int j = 0; j < 4; j++) if (ctx->ev_group[k][j]) (void)hipEventDestroy(ctx->ev_group[k][j]);
-	if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-	if (ctx->d_work) (void)hipFree(ctx->d_work);
-	if (ctx->ev_sync) (void)hipEventDestroy(ctx->ev_sync);
-	if (ctx->d_wscratch) (void)hipFree(ctx->d_wscratch);
-	if (ctx->d_rlog) (void)hipFree(ctx->d_rlog);
-	if (ctx->d_cursor) (void)hipFree(ctx->d_cursor);
-	if (ctx->d_blk_done) (void)hipFree(ctx->d_blk_done);
-	if (ctx->h_blk_flag) (void)hipHostFree(ctx->h_blk_flag);
-	if (ctx->d_ids) (void)hipFree(ctx->d_ids);
-	if (ctx->d_lane_start) (void)hipFree(ctx->d_lane_start);
-	if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-	if (ctx->h_batch) { if (ctx->h_batch_pinned) (void)hipHostFree(ctx->h_batch); else free(ctx->h_batch); }
-	if (ctx->d_leak_frames) (void)hipFree(ctx->d_leak_frames);
-	if (ctx->d_leak_records) (void)hipFree(ctx->d_leak_records);
-	if (ctx->d_leak_out) (void)hipFree(ctx->d_leak_out);
-	if (ctx->h_leak_out) (void)hipHostFree(ctx->h_leak_out);
-	if (ctx->d_leak_order_tmp) (void)hipFree(ctx->d_leak_order_tmp);
-	if (ctx->d_leak_cursor) (void)hipFree(ctx->d_leak_cursor);
-	if (ctx->d_amu) (void)hipFree(ctx->d_amu);
-	if (ctx->d_leak_attempts) (void)hipFree(ctx->d_leak_attempts);
-	if (ctx->d_leak_timing) (void)hipFree(ctx->d_leak_timing);
-	if (ctx->d_leak_order) (void)hipFree(ctx->d_leak_order);
-	if (ctx->d_work_est) (void)hipFree(ctx->d_work_est);
-	if (ctx->d_leak_slot_units) (void)hipFree(ctx->d_leak_slot_units);
-	if (ctx->d_scan_totals) (void)hipFree(ctx->d_scan_totals);
-	if (ctx->d_scan_tot) (void)hipFree(ctx->d_scan_tot);
-	if (ctx->d_scan_pts) (void)hipFree(ctx->d_scan_pts);
-	if (ctx->d_scan_wscratch) (void)hipFree(ctx->d_scan_wscratch);
-	if (ctx->ev_scan0) (void)hipEventDestroy(ctx->ev_scan0);
-	if (ctx->ev_scan1) (void)hipEventDestroy(ctx->ev_scan1);
-	if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-	if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+	if (ctx->main_stream) (void)hipStreamSynchronize(ctx->main_stream);
 	delete ctx;
 }
 
@@ -1644,29 +1693,31 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 	const size_t npts = (size_t)ctx->host.pm.nmax + 1;
 	if (npts > PC_MAX_PITCH) { delete ctx; return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_ctx_create: profile too long for the LDS tables (nmax <= 2047)"); }
 #define PC_CTX_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); pc_hip_ctx_destroy(ctx); return pc_fail(PC_HIP_ERR_RUNTIME, m); } } while (0)
+#define PC_CTX_GROW(buf, elems, what) do { int _st = (buf).grow((elems), "pc_hip_ctx_create: could not allocate " what); if (_st) { pc_hip_ctx_destroy(ctx); return _st; } } while (0)
 	PC_CTX_CHECK(hipSetDevice(device));
 	hipDeviceProp_t prop;
 	PC_CTX_CHECK(hipGetDeviceProperties(&prop, device));
 	ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-	PC_CTX_CHECK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+	PC_CTX_CHECK(ctx->main_stream.ensure());
+	ctx->stream = ctx->main_stream;
 	if (const char *e = getenv("POLYCAP_PRODUCER"))          /* tests: force (1) or forbid (0) the launching-wave kernel */
 		if (*e == '0' || *e == '1') ctx->producer = *e - '0';
-	PC_CTX_CHECK(hipEventCreate(&ctx->ev0));
-	PC_CTX_CHECK(hipEventCreate(&ctx->ev1));
-	PC_CTX_CHECK(hipMalloc(&ctx->d_tables, 9*npts*sizeof(double)));
+	PC_CTX_CHECK(ctx->ev0.ensure(hipEventDefault));
+	PC_CTX_CHECK(ctx->ev1.ensure(hipEventDefault));
+	PC_CTX_GROW(ctx->d_tables, 9*npts, "the profile tables");
 	const std::vector<double> *src[9] = { &ctx->host.z, &ctx->host.cap, &ctx->host.zh, &ctx->host.cap2, &ctx->host.hexd, &ctx->host.idz, &ctx->host.ext,
 	                                      &ctx->host.stp, &ctx->host.istp };
 	for (int k = 0; k < 9; k++)
 		PC_CTX_CHECK(hipMemcpy(ctx->d_tables + k*npts, src[k]->data(), npts*sizeof(double), hipMemcpyHostToDevice));
-	PC_CTX_CHECK(hipMalloc(&ctx->d_mg, npts*sizeof(pc_marg4)));
+	PC_CTX_GROW(ctx->d_mg, npts, "the block certificates");
 	PC_CTX_CHECK(hipMemcpy(ctx->d_mg, ctx->host.mg.data(), npts*sizeof(pc_marg4), hipMemcpyHostToDevice));
-	PC_CTX_CHECK(hipMalloc(&ctx->d_dr, npts*sizeof(pc_drdev)));
+	PC_CTX_GROW(ctx->d_dr, npts, "the chord deviations");
 	PC_CTX_CHECK(hipMemcpy(ctx->d_dr, ctx->host.dr.data(), npts*sizeof(pc_drdev), hipMemcpyHostToDevice));
 	{
 		/* at least 8 entries: the register-weight kernels read NE constants whatever n_energies is (surplus = copies of the last) */
 		std::vector<pc_energy_const> ecp(ctx->host.ec);
 		while (ecp.size() < 8) ecp.push_back(ecp.back());
-		PC_CTX_CHECK(hipMalloc(&ctx->d_ec, ecp.size()*sizeof(pc_energy_const)));
+		PC_CTX_GROW(ctx->d_ec, ecp.size(), "the energy constants");
 		PC_CTX_CHECK(hipMemcpy(ctx->d_ec, ecp.data(), ecp.size()*sizeof(pc_energy_const), hipMemcpyHostToDevice));
 	}
 	{
@@ -1678,14 +1729,15 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 			soa[e] = c.d2; soa[ne + e] = c.n2_re; soa[2*ne + e] = c.n2_im; soa[3*ne + e] = c.zi2;
 			soa[4*ne + e] = c.rough_c; soa[5*ne + e] = c.valid; soa[6*ne + e] = c.rough_k2;
 		}
-		PC_CTX_CHECK(hipMalloc(&ctx->d_ec_soa, soa.size()*sizeof(double)));
+		PC_CTX_GROW(ctx->d_ec_soa, soa.size(), "the energy constants");
 		PC_CTX_CHECK(hipMemcpy(ctx->d_ec_soa, soa.data(), soa.size()*sizeof(double), hipMemcpyHostToDevice));
 	}
 	ctx->leak_max_depth = (int)std::min(65536.0, 2.0*ctx->host.pm.n_shells + 16.0);
 	ctx->totals_bytes = sizeof(pc_totals) + 4*ctx->host.ec.size()*sizeof(unsigned long long);
-	PC_CTX_CHECK(hipMalloc(&ctx->d_totals, ctx->totals_bytes));
+	PC_CTX_GROW(ctx->d_totals, (ctx->totals_bytes + sizeof(pc_totals) - 1)/sizeof(pc_totals), "the totals");
 	PC_CTX_CHECK(hipMemset(ctx->d_totals, 0, ctx->totals_bytes));
 #undef PC_CTX_CHECK
+#undef PC_CTX_GROW
 	*out = ctx;
 	return PC_HIP_OK;
 }
@@ -1750,21 +1802,9 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 /* device + pinned host buffer of at least `elems` doubles for the explicit-photon calls */
 static int pc_batch_buffers(pc_hip_ctx *ctx, size_t elems)
 {
-	if (ctx->batch_elems >= elems) return PC_HIP_OK;
-	if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-	if (ctx->h_batch) { if (ctx->h_batch_pinned) (void)hipHostFree(ctx->h_batch); else free(ctx->h_batch); }
-	ctx->d_batch = ctx->h_batch = nullptr; ctx->batch_elems = 0;
 	const size_t want = elems < 4096 ? 4096 : elems + elems/4;
-	if (hipMalloc(&ctx->d_batch, want*sizeof(double)) != hipSuccess) { ctx->d_batch = nullptr; return pc_fail(PC_HIP_ERR_MEMORY, "explicit-photon batch: device allocation failed"); }
-	ctx->h_batch_pinned = true;
-	if (hipHostMalloc(&ctx->h_batch, want*sizeof(double), hipHostMallocDefault) != hipSuccess) {
-		(void)hipGetLastError();
-		ctx->h_batch_pinned = false;
-		ctx->h_batch = (double *)malloc(want*sizeof(double));
-		if (!ctx->h_batch) { (void)hipFree(ctx->d_batch); ctx->d_batch = nullptr; return pc_fail(PC_HIP_ERR_MEMORY, "explicit-photon batch: host allocation failed"); }
-	}
-	ctx->batch_elems = want;
-	return PC_HIP_OK;
+	int st = ctx->d_batch.grow(elems, "explicit-photon batch: device allocation failed", want);
+	return st ? st : ctx->h_batch.grow(elems, "explicit-photon batch: host allocation failed", want);
 }
 
 static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *start_coords, const double *start_dir, const double *start_elecv,
@@ -1913,13 +1953,7 @@ static void pc_set_img(const pc_hip_ctx *ctx, pc_kargs &a, long long lo, long lo
 /* device plane buffer for a run of n_slots (see pc_soa_kernel) */
 static int pc_soa_ensure(pc_hip_ctx *ctx, long long n_slots)
 {
-	if (ctx->d_soa && ctx->soa_slots >= n_slots) return PC_HIP_OK;
-	if (ctx->d_soa) (void)hipFree(ctx->d_soa);
-	ctx->d_soa = nullptr; ctx->soa_slots = 0;
-	const size_t bytes = ((size_t)PC_N_FIELDS + (size_t)ctx->host.pm.n_energies) * (size_t)n_slots * sizeof(double);
-	if (hipMalloc(&ctx->d_soa, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->d_soa = nullptr; return PC_HIP_ERR_MEMORY; }
-	ctx->soa_slots = n_slots;
-	return PC_HIP_OK;
+	return ctx->d_soa.grow(((size_t)PC_N_FIELDS + (size_t)ctx->host.pm.n_energies) * (size_t)n_slots, "could not allocate the device image planes");
 }
 
 /* records of slots [lo, lo + count) of the current run -> planes (pitch = the run's n_slots), on `stream` */
@@ -1979,36 +2013,14 @@ static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots)
 	}
 	const int shift = ctx->blk_shift;
 	const size_t blocks = (size_t)((n_slots + (1ll << shift) - 1) >> shift);
-	if (!ctx->d_cursor) PC_HIP_CHECK(hipMalloc(&ctx->d_cursor, sizeof(unsigned long long)));
-	if (ctx->blk_capacity < blocks) {
-		if (ctx->d_blk_done) (void)hipFree(ctx->d_blk_done);
-		if (ctx->h_blk_flag) (void)hipHostFree(ctx->h_blk_flag);
-		ctx->d_blk_done = nullptr; ctx->h_blk_flag = nullptr; ctx->d_blk_flag = nullptr; ctx->blk_capacity = 0;
-		const size_t cap = blocks + blocks/2 + 16;
-		PC_HIP_CHECK(hipMalloc(&ctx->d_blk_done, cap*sizeof(unsigned int)));
-		if (hipHostMalloc(&ctx->h_blk_flag, cap*sizeof(unsigned int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-			(void)hipGetLastError();
-			PC_HIP_CHECK(hipHostMalloc(&ctx->h_blk_flag, cap*sizeof(unsigned int), hipHostMallocMapped));
-		}
-		PC_HIP_CHECK(hipHostGetDevicePointer((void **)&ctx->d_blk_flag, ctx->h_blk_flag, 0));
-		ctx->blk_capacity = cap;
-	}
-	if (ctx->slot_ids && ctx->ids_slots < n_slots) {
-		if (ctx->d_ids) (void)hipFree(ctx->d_ids);
-		ctx->d_ids = nullptr; ctx->ids_slots = 0;
-		if (hipMalloc(&ctx->d_ids, (size_t)n_slots*sizeof(long long)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_transmission_run: could not allocate the slot-index plane"); }
-		ctx->ids_slots = n_slots;
-	}
-	{
-		/* one 64-byte line per lane of the largest launch the context makes, per half */
-		const size_t need = 8*pc_lane_start_lanes(ctx)*(size_t)ctx->scratch_halves;
-		if (ctx->lane_start_elems < need) {
-			if (ctx->d_lane_start) (void)hipFree(ctx->d_lane_start);
-			ctx->d_lane_start = nullptr; ctx->lane_start_elems = 0;
-			PC_HIP_CHECK(hipMalloc(&ctx->d_lane_start, need*sizeof(double)));
-			ctx->lane_start_elems = need;
-		}
-	}
+	const size_t cap = blocks + blocks/2 + 16;
+	int st = ctx->d_cursor.grow(1, "pc_hip_transmission_run: could not allocate the position counter");
+	if (!st) st = ctx->d_blk_done.grow(blocks, "pc_hip_transmission_run: could not allocate the block counters", cap);
+	if (!st) st = ctx->h_blk_flag.grow(blocks, "pc_hip_transmission_run: could not allocate the block flags", cap);
+	if (!st && ctx->slot_ids) st = ctx->d_ids.grow((size_t)n_slots, "pc_hip_transmission_run: could not allocate the slot-index plane");
+	/* one 64-byte line per lane of the largest launch the context makes, per half */
+	if (!st) st = ctx->d_lane_start.grow(8*pc_lane_start_lanes(ctx)*(size_t)ctx->scratch_halves, "pc_hip_transmission_run: could not allocate the lanes' start-image lines");
+	if (st) return st;
 	ctx->run_blk_shift = shift;
 	ctx->run_blocks = (long long)blocks;
 	memset(ctx->h_blk_flag, 0, blocks*sizeof(unsigned int));      /* the previous run has been waited for (above): nobody looks at them now */
@@ -2067,20 +2079,14 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		a.img_cursor = ctx->d_cursor;
 		a.img_ids = ctx->slot_ids ? ctx->d_ids : nullptr;
 		a.blk_done = ctx->d_blk_done;
-		a.blk_flag = ctx->d_blk_flag;
+		a.blk_flag = ctx->h_blk_flag.dev;
 		a.blk_shift = ctx->run_blk_shift;
 		a.img_n = n_slots;
 		a.lane_start = ctx->d_lane_start;
 	}
 	if (keep_images && !planes) {
-		if (ctx->img_slots < n_slots) {
-			if (ctx->d_img) PC_HIP_CHECK(hipFree(ctx->d_img));
-			ctx->d_img = nullptr; ctx->img_slots = 0;
-			size_t bytes = ((size_t)PC_N_PLANES + ne) * (size_t)n_slots * sizeof(double);
-			if (hipMalloc(&ctx->d_img, bytes) != hipSuccess)
-				return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_transmission_run: could not allocate the image planes; use keep_images=0");
-			ctx->img_slots = n_slots;
-		}
+		int st = ctx->d_img.grow(((size_t)PC_N_PLANES + ne) * (size_t)n_slots, "pc_hip_transmission_run: could not allocate the image planes; use keep_images=0");
+		if (st) return st;
 	}
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
 	a.seed = seed; a.max_attempts = max_attempts; a.keep_images = keep_images ? 1 : 0;
@@ -2091,9 +2097,10 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		/* Parts alternate between two streams.  Every launch fills the device with persistent workgroups, so the
 		 * workgroups of part k+1 start exactly as those of part k run out of slots and leave: the tail of one part (its
 		 * longest photons) is covered by the head of the next, and the parts still finish in order. */
-		if (!ctx->stream2) PC_HIP_CHECK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-		if (!ctx->ev_sync) PC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_sync, hipEventDisableTiming));
-		if (!ctx->d_work) PC_HIP_CHECK(hipMalloc(&ctx->d_work, PC_MAX_PARTS*sizeof(unsigned long long)));
+		PC_HIP_CHECK(ctx->stream2.ensure());
+		PC_HIP_CHECK(ctx->ev_sync.ensure());
+		int st = ctx->d_work.grow(PC_MAX_PARTS, "pc_hip_transmission_run: could not allocate the work counters of the parts");
+		if (st) return st;
 		PC_HIP_CHECK(hipMemsetAsync(ctx->d_work, 0, PC_MAX_PARTS*sizeof(unsigned long long), main_stream));
 		PC_HIP_CHECK(hipEventRecord(ctx->ev0, main_stream));
 		PC_HIP_CHECK(hipEventRecord(ctx->ev_sync, main_stream));
@@ -2118,7 +2125,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		                                  : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, a, hi - lo);
 		ctx->part_end[k] = hi;
 		if (status == PC_HIP_OK && parts > 1) {
-			if (!ctx->ev_part[k]) PC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_part[k], hipEventDisableTiming));
+			PC_HIP_CHECK(ctx->ev_part[k].ensure());
 			PC_HIP_CHECK(hipEventRecord(ctx->ev_part[k], ctx->stream));
 		}
 	}
@@ -2150,13 +2157,9 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	ctx->img_valid = 0;
-	if (keep_images && ctx->img_slots < n_slots) {
-		if (ctx->d_img) PC_HIP_CHECK(hipFree(ctx->d_img));
-		ctx->d_img = nullptr; ctx->img_slots = 0;
-		size_t bytes = ((size_t)PC_N_PLANES + ne) * (size_t)n_slots * sizeof(double);
-		if (hipMalloc(&ctx->d_img, bytes) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
-		ctx->img_slots = n_slots;
+	if (keep_images) {
+		int st = ctx->d_img.grow(((size_t)PC_N_PLANES + ne) * (size_t)n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
+		if (st) return st;
 	}
 	ctx->n_parts = 1;
 	ctx->run_planes = 0;
@@ -2395,13 +2398,7 @@ static bool pc_pin_ranges(std::vector<std::pair<char *, size_t>> ranges, unsigne
 
 static hipError_t pc_fetch_stream_ensure(pc_hip_ctx *ctx)
 {
-	if (ctx->fetch_stream) return hipSuccess;
-	int least = 0, greatest = 0;
-	if (!getenv("POLYCAP_FETCH_PRIORITY_OFF") && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least
-	    && hipStreamCreateWithPriority(&ctx->fetch_stream, hipStreamNonBlocking, greatest) == hipSuccess)
-		return hipSuccess;
-	(void)hipGetLastError();
-	return hipStreamCreateWithFlags(&ctx->fetch_stream, hipStreamNonBlocking);
+	return ctx->fetch_stream.ensure(!getenv("POLYCAP_FETCH_PRIORITY_OFF"));
 }
 
 /* see pc_fetch_images.  Returns PC_HIP_OK, an error, or 1 when the direct path cannot be used */
@@ -2411,7 +2408,7 @@ static int pc_fetch_planes_direct(pc_hip_ctx *ctx, int64_t first, int64_t count,
 	const long long n_total = ctx->run_slots;
 	if (!ctx->run_planes && ((size_t)PC_SOA_TILE*(PC_N_FIELDS + ne)*sizeof(double) > 65536 || pc_soa_ensure(ctx, n_total) != PC_HIP_OK)) return 1;
 	PC_HIP_CHECK(pc_fetch_stream_ensure(ctx));
-	if (!ctx->ev_sync) PC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_sync, hipEventDisableTiming));
+	PC_HIP_CHECK(ctx->ev_sync.ensure());
 	const bool timing = getenv("POLYCAP_TIMING") != nullptr;
 	auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double t_begin = now_ms();
@@ -2479,17 +2476,10 @@ static int pc_fetch_planes_direct(pc_hip_ctx *ctx, int64_t first, int64_t count,
 		int n_streams = 2, depth = 2;
 		if (const char *ev = getenv("POLYCAP_FETCH_STREAMS")) n_streams = (*ev == '1') ? 1 : 2;
 		if (const char *ev = getenv("POLYCAP_FETCH_DEPTH")) depth = (*ev >= '1' && *ev <= '3') ? *ev - '0' : 2;
-		if (n_streams == 2 && !ctx->fetch_stream_b) {
-			int least = 0, greatest = 0;
-			if (!(hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least
-			      && hipStreamCreateWithPriority(&ctx->fetch_stream_b, hipStreamNonBlocking, greatest) == hipSuccess)) {
-				(void)hipGetLastError();
-				PC_HIP_CHECK(hipStreamCreateWithFlags(&ctx->fetch_stream_b, hipStreamNonBlocking));
-			}
-		}
+		if (n_streams == 2) PC_HIP_CHECK(ctx->fetch_stream_b.ensure(true));
 		for (int k = 0; k < 2; k++)
 			for (int j = 0; j < 4; j++)
-				if (!ctx->ev_group[k][j]) PC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_group[k][j], hipEventDisableTiming));
+				PC_HIP_CHECK(ctx->ev_group[k][j].ensure());
 		hipStream_t streams[2] = { ctx->fetch_stream, n_streams == 2 ? ctx->fetch_stream_b : ctx->fetch_stream };
 		while (b < b_end && status == PC_HIP_OK) {
 			volatile unsigned int *flag = ctx->h_blk_flag;
@@ -2628,22 +2618,10 @@ static int pc_fetch_images(pc_hip_ctx *ctx, int64_t first, int64_t count, const 
 	size_t chunk = ((size_t)16 << 20) / (rec*sizeof(double));
 	if (chunk < 256) chunk = 256;
 	if (chunk > (size_t)count) chunk = (size_t)count;
-	if (ctx->h_stage_elems < 2*chunk*rec) {
-		if (ctx->h_stage) { if (ctx->h_stage_pinned) PC_HIP_CHECK(hipHostFree(ctx->h_stage)); else free(ctx->h_stage); }
-		ctx->h_stage = nullptr; ctx->h_stage_elems = 0;
-		ctx->h_stage_pinned = true;
-		if (hipHostMalloc(&ctx->h_stage, 2*chunk*rec*sizeof(double), hipHostMallocDefault) != hipSuccess) {
-			/* no pinned memory to be had: the copies then go through the runtime's own staging, slower but correct */
-			(void)hipGetLastError();
-			ctx->h_stage_pinned = false;
-			ctx->h_stage = (double *)malloc(2*chunk*rec*sizeof(double));
-			if (!ctx->h_stage)
-				return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_transmission_images: could not allocate the staging buffer");
-		}
-		ctx->h_stage_elems = 2*chunk*rec;
-	}
+	int st = ctx->h_stage.grow(2*chunk*rec, "pc_hip_transmission_images: could not allocate the staging buffer");
+	if (st) return st;
 	for (int k = 0; k < 2; k++)
-		if (!ctx->ev_fetch[k]) PC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_fetch[k], hipEventDisableTiming));
+		PC_HIP_CHECK(ctx->ev_fetch[k].ensure());
 	PC_HIP_CHECK(pc_fetch_stream_ensure(ctx));
 	int nthreads = ctx->fetch_threads;
 	if (nthreads <= 0) {
@@ -2718,7 +2696,7 @@ int pc_hip_leak_set_order(pc_hip_ctx *ctx, const uint32_t *order, int64_t n, int
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	int st = pc_hip_transmission_wait(ctx, nullptr);
 	if (st) return st;
-	if (ctx->d_leak_order) { PC_HIP_CHECK(hipFree(ctx->d_leak_order)); ctx->d_leak_order = nullptr; }
+	ctx->d_leak_order.reset();
 	ctx->leak_order_n = 0; ctx->leak_n_heavy = 0; ctx->leak_order_user = 0; ctx->leak_order_slot0 = -1;
 	if (n == 0) return PC_HIP_OK;
 	{
@@ -2729,8 +2707,8 @@ int pc_hip_leak_set_order(pc_hip_ctx *ctx, const uint32_t *order, int64_t n, int
 			seen[order[k]] = 1;
 		}
 	}
-	PC_HIP_CHECK(hipMalloc(&ctx->d_leak_order, (size_t)n*sizeof(unsigned int)));
-	ctx->leak_order_cap = n;
+	st = ctx->d_leak_order.grow((size_t)n, "pc_hip_leak_set_order: could not allocate the order");
+	if (st) return st;
 	PC_HIP_CHECK(hipMemcpy(ctx->d_leak_order, order, (size_t)n*sizeof(unsigned int), hipMemcpyHostToDevice));
 	ctx->leak_order_n = n; ctx->leak_n_heavy = n_heavy; ctx->leak_order_user = 1;
 	return PC_HIP_OK;
@@ -2741,7 +2719,7 @@ int pc_hip_leak_slot_units(pc_hip_ctx *ctx, int64_t first, int64_t count, uint32
 	if (!ctx || (count > 0 && !units) || first < 0 || count < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_slot_units: invalid argument");
 	int st = pc_hip_transmission_wait(ctx, nullptr);
 	if (st) return st;
-	if (!ctx->d_leak_slot_units || first + count > ctx->leak_slot_units_n) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_slot_units: no leak run with the option leak_slot_units covers this range");
+	if (!ctx->d_leak_slot_units || (size_t)(first + count) > ctx->d_leak_slot_units.cap) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_slot_units: no leak run with the option leak_slot_units covers this range");
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	if (count) PC_HIP_CHECK(hipMemcpy(units, ctx->d_leak_slot_units + first, (size_t)count*sizeof(unsigned int), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;
@@ -2797,19 +2775,15 @@ static int pc_leak_auto_order(pc_hip_ctx *ctx)
 	/* considered when every lane gets two to five slots: with fewer there is nothing to order, with more the launch is not bound
 	 * by its longest slot (the check below, made beforehand with the reference optic's ratio of longest to mean slot, 11.6) */
 	if (!ctx->leak_order || n < 2*lanes || n >= 5*lanes || n >= (1ll << 32)) {
-		if (ctx->d_leak_order) { PC_HIP_CHECK(hipFree(ctx->d_leak_order)); ctx->d_leak_order = nullptr; }
-		ctx->leak_order_n = 0; ctx->leak_order_slot0 = -1; ctx->leak_order_cap = 0;
+		ctx->d_leak_order.reset();
+		ctx->leak_order_n = 0; ctx->leak_order_slot0 = -1;
 		return PC_HIP_OK;
 	}
 	if (ctx->d_leak_order && ctx->leak_order_n == n && ctx->leak_order_seed == ctx->leak_seed && ctx->leak_order_slot0 == ctx->leak_slot0
 	    && ctx->leak_order_attempts == ctx->leak_max_attempts)
 		return PC_HIP_OK;                                               /* the same slots as last time */
-	if (ctx->work_est_n < n) {
-		if (ctx->d_work_est) PC_HIP_CHECK(hipFree(ctx->d_work_est));
-		ctx->d_work_est = nullptr; ctx->work_est_n = 0;
-		if (hipMalloc(&ctx->d_work_est, (size_t)n*sizeof(unsigned int)) != hipSuccess) return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the work estimate");
-		ctx->work_est_n = n;
-	}
+	int st = ctx->d_work_est.grow((size_t)n, "leak run: could not allocate the work estimate");
+	if (st) return st;
 	const bool tim = getenv("POLYCAP_LEAK_TIMING") != nullptr;
 	const auto t_0 = std::chrono::steady_clock::now();
 	/* the time of the launch starts here */
@@ -2828,7 +2802,7 @@ static int pc_leak_auto_order(pc_hip_ctx *ctx)
 		~restore_ctx() { c->producer = producer; c->pool = pool; c->rec_ev0 = c->rec_ev1 = true; }
 	} restore{ctx, ctx->producer, ctx->pool};
 	ctx->producer = 0; ctx->pool = 0; ctx->rec_ev0 = ctx->rec_ev1 = false;
-	int st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, a, n) : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, a, n);
+	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, a, n) : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, a, n);
 	if (st) return st;
 	std::vector<unsigned int> est((size_t)n);
 	PC_HIP_CHECK(hipMemcpyAsync(est.data(), ctx->d_work_est, (size_t)n*sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -2859,8 +2833,8 @@ static int pc_leak_auto_order(pc_hip_ctx *ctx)
 		std::stable_sort(order.begin(), order.end(), [&](unsigned int x, unsigned int y) { return est[x] > est[y]; });
 	}
 	const auto t_2 = std::chrono::steady_clock::now();
-	if (ctx->d_leak_order && ctx->leak_order_cap < n) { PC_HIP_CHECK(hipFree(ctx->d_leak_order)); ctx->d_leak_order = nullptr; }
-	if (!ctx->d_leak_order) { PC_HIP_CHECK(hipMalloc(&ctx->d_leak_order, (size_t)n*sizeof(unsigned int))); ctx->leak_order_cap = n; }
+	st = ctx->d_leak_order.grow((size_t)n, "leak run: could not allocate the slot order");
+	if (st) return st;
 	PC_HIP_CHECK(hipMemcpyAsync(ctx->d_leak_order, order.data(), (size_t)n*sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
 	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));      /* `order` leaves scope */
 	if (tim) {

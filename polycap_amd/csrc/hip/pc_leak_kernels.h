@@ -361,38 +361,15 @@ static int pc_leak_buffers(pc_hip_ctx *ctx, long long lanes, long long capacity,
 {
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	const size_t frames = (size_t)lanes * (size_t)ctx->leak_max_depth * (PC_LF_HDR + ne);
-	if (frames > ctx->leak_frames_elems) {
-		if (ctx->d_leak_frames) PC_HIP_CHECK(hipFree(ctx->d_leak_frames));
-		ctx->d_leak_frames = nullptr; ctx->leak_frames_elems = 0;
-		if (hipMalloc(&ctx->d_leak_frames, frames*sizeof(double)) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the per-lane stacks (lower leak_stack_mb or leak_max_depth)");
-		ctx->leak_frames_elems = frames;
+	int st = ctx->d_leak_frames.grow(frames, "leak run: could not allocate the per-lane stacks (lower leak_stack_mb or leak_max_depth)");
+	if (!st) st = ctx->d_leak_records.grow((size_t)capacity * (PC_LR_HDR + ne), "leak run: could not allocate the leak record buffer");
+	if (!st) st = ctx->d_leak_cursor.grow(4, "leak run: could not allocate the record cursor");
+	if (!st && !ctx->d_amu) {
+		st = ctx->d_amu.grow(ne, "leak run: could not allocate the attenuation table");
+		if (!st) PC_HIP_CHECK(hipMemcpy(ctx->d_amu, ctx->host.amu.data(), ne*sizeof(double), hipMemcpyHostToDevice));
 	}
-	const size_t recs = (size_t)capacity * (PC_LR_HDR + ne);
-	if (recs > ctx->leak_records_elems) {
-		if (ctx->d_leak_records) PC_HIP_CHECK(hipFree(ctx->d_leak_records));
-		ctx->d_leak_records = nullptr; ctx->leak_records_elems = 0;
-		if (hipMalloc(&ctx->d_leak_records, recs*sizeof(double)) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the leak record buffer");
-		ctx->leak_records_elems = recs;
-	}
-	if (!ctx->d_leak_cursor) {
-		if (hipMalloc(&ctx->d_leak_cursor, 4*sizeof(unsigned long long)) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the record cursor");
-	}
-	if (!ctx->d_amu) {
-		if (hipMalloc(&ctx->d_amu, ne*sizeof(double)) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the attenuation table");
-		PC_HIP_CHECK(hipMemcpy(ctx->d_amu, ctx->host.amu.data(), ne*sizeof(double), hipMemcpyHostToDevice));
-	}
-	if (n_slots > ctx->leak_attempt_slots) {
-		if (ctx->d_leak_attempts) PC_HIP_CHECK(hipFree(ctx->d_leak_attempts));
-		ctx->d_leak_attempts = nullptr; ctx->leak_attempt_slots = 0;
-		if (hipMalloc(&ctx->d_leak_attempts, (size_t)n_slots*sizeof(unsigned int)) != hipSuccess)
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the per-slot attempt table");
-		ctx->leak_attempt_slots = n_slots;
-	}
-	return PC_HIP_OK;
+	if (!st) st = ctx->d_leak_attempts.grow((size_t)n_slots, "leak run: could not allocate the per-slot attempt table");
+	return st;
 }
 
 template <int MODE>
@@ -415,8 +392,8 @@ static int pc_leak_enqueue(pc_hip_ctx *ctx, pc_kargs &a, long long n_items, long
 			lk.n_heavy = (lk.heavy_lanes > 0 && lk.heavy_every > 0) ? std::min<long long>(ctx->leak_n_heavy, n_items) : 0;
 		}
 		if (ctx->leak_slot_units) {
-			if (ctx->d_leak_slot_units && ctx->leak_slot_units_n < n_items) { (void)hipFree(ctx->d_leak_slot_units); ctx->d_leak_slot_units = nullptr; }
-			if (!ctx->d_leak_slot_units) { PC_HIP_CHECK(hipMalloc(&ctx->d_leak_slot_units, (size_t)n_items*sizeof(unsigned int))); ctx->leak_slot_units_n = n_items; }
+			st = ctx->d_leak_slot_units.grow((size_t)n_items, "leak run: could not allocate the units of work per slot");
+			if (st) return st;
 			PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_slot_units, 0, (size_t)n_items*sizeof(unsigned int), ctx->stream));
 			lk.slot_units = ctx->d_leak_slot_units;
 		}
@@ -424,8 +401,8 @@ static int pc_leak_enqueue(pc_hip_ctx *ctx, pc_kargs &a, long long n_items, long
 	if (getenv("POLYCAP_LEAK_TIMING")) {
 		/* diagnostics: where the waves of the leak kernel spend their time (printed by pc_leak_collect) */
 		const size_t nb = (size_t)(lanes / PC_WAVE) * 8 * sizeof(unsigned long long);
-		if (ctx->d_leak_timing && ctx->leak_timing_bytes < nb) { (void)hipFree(ctx->d_leak_timing); ctx->d_leak_timing = nullptr; }
-		if (!ctx->d_leak_timing) { PC_HIP_CHECK(hipMalloc(&ctx->d_leak_timing, nb)); ctx->leak_timing_bytes = nb; }
+		st = ctx->d_leak_timing.grow(nb/sizeof(unsigned long long), "leak run: could not allocate the timing records");
+		if (st) return st;
 		PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_timing, 0, nb, ctx->stream));
 		lk.timing = ctx->d_leak_timing;
 		ctx->leak_timing_waves = lanes / PC_WAVE;
@@ -527,25 +504,11 @@ static int pc_leak_order_buffers(pc_hip_ctx *ctx, size_t n, size_t ostride, size
 {
 	/* keys n x 8 x 3, seq n x 4 x 2, idx n x 4 x 3, flags + positions (n + 1) x 4 x 4, void keys n x 8 x 2, counters */
 	const size_t need = n*8*3 + n*4*2 + n*4*3 + (n + 1)*4*4 + n*8*2 + 256 + temp_bytes + 4096;
-	if (need > ctx->leak_order_bytes) {
-		if (ctx->d_leak_order_tmp) (void)hipFree(ctx->d_leak_order_tmp);
-		ctx->d_leak_order_tmp = nullptr; ctx->leak_order_bytes = 0;
-		if (hipMalloc(&ctx->d_leak_order_tmp, need) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the ordering buffers"); }
-		ctx->leak_order_bytes = need;
-	}
+	int st = ctx->d_leak_order_tmp.grow(need, "leak run: could not allocate the ordering buffers");
 	const size_t out_elems = (n ? n : 1)*ostride;
-	if (out_elems > ctx->leak_out_elems) {
-		if (ctx->d_leak_out) (void)hipFree(ctx->d_leak_out);
-		if (ctx->h_leak_out) (void)hipHostFree(ctx->h_leak_out);
-		ctx->d_leak_out = nullptr; ctx->h_leak_out = nullptr; ctx->leak_out_elems = 0;
-		const size_t grow = out_elems + out_elems/8;
-		if (hipMalloc(&ctx->d_leak_out, grow*sizeof(double)) != hipSuccess || hipHostMalloc(&ctx->h_leak_out, grow*sizeof(double)) != hipSuccess) {
-			(void)hipGetLastError();
-			return pc_fail(PC_HIP_ERR_MEMORY, "leak run: could not allocate the event lists");
-		}
-		ctx->leak_out_elems = grow;
-	}
-	return PC_HIP_OK;
+	if (!st) st = ctx->d_leak_out.grow(out_elems, "leak run: could not allocate the event lists", out_elems + out_elems/8);
+	if (!st) st = ctx->h_leak_out.grow(out_elems, "leak run: could not allocate the event lists", out_elems + out_elems/8);
+	return st;
 }
 
 /* Orders the event records of the finished run on the device and brings the two lists to the host (pinned memory, kept by the

@@ -59,29 +59,14 @@ static int pc_scan_launch_kne(pc_hip_ctx *ctx, int kne, const pc_kargs &a, int g
 static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points, size_t wscratch_elems)
 {
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	if (!ctx->d_scan_totals) PC_HIP_CHECK(hipMalloc(&ctx->d_scan_totals, sizeof(pc_totals)));
-	if (!ctx->ev_scan0) PC_HIP_CHECK(hipEventCreate(&ctx->ev_scan0));
-	if (!ctx->ev_scan1) PC_HIP_CHECK(hipEventCreate(&ctx->ev_scan1));
-	if (ctx->scan_pts_cap < (size_t)n_points) {
-		if (ctx->d_scan_pts) PC_HIP_CHECK(hipFree(ctx->d_scan_pts));
-		ctx->d_scan_pts = nullptr; ctx->scan_pts_cap = 0;
-		if (hipMalloc(&ctx->d_scan_pts, (size_t)n_points*sizeof(pc_scan_point)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the point table"); }
-		ctx->scan_pts_cap = (size_t)n_points;
-	}
-	const size_t tot = (size_t)n_points*pc_scan_stride(ne);
-	if (ctx->scan_tot_elems < tot) {
-		if (ctx->d_scan_tot) PC_HIP_CHECK(hipFree(ctx->d_scan_tot));
-		ctx->d_scan_tot = nullptr; ctx->scan_tot_elems = 0;
-		if (hipMalloc(&ctx->d_scan_tot, tot*sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the per-point totals"); }
-		ctx->scan_tot_elems = tot;
-	}
-	if (ctx->scan_wscratch_elems < wscratch_elems) {
-		if (ctx->d_scan_wscratch) PC_HIP_CHECK(hipFree(ctx->d_scan_wscratch));
-		ctx->d_scan_wscratch = nullptr; ctx->scan_wscratch_elems = 0;
-		if (hipMalloc(&ctx->d_scan_wscratch, wscratch_elems*sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return pc_fail(PC_HIP_ERR_MEMORY, "pc_hip_scan_run: could not allocate the per-lane weight scratch"); }
-		ctx->scan_wscratch_elems = wscratch_elems;
-	}
-	return PC_HIP_OK;
+	int st = ctx->d_scan_totals.grow(1, "pc_hip_scan_run: could not allocate the scan totals");
+	if (st) return st;
+	PC_HIP_CHECK(ctx->ev_scan0.ensure(hipEventDefault));
+	PC_HIP_CHECK(ctx->ev_scan1.ensure(hipEventDefault));
+	st = ctx->d_scan_pts.grow((size_t)n_points, "pc_hip_scan_run: could not allocate the point table");
+	if (!st) st = ctx->d_scan_tot.grow((size_t)n_points*pc_scan_stride(ne), "pc_hip_scan_run: could not allocate the per-point totals");
+	if (!st) st = ctx->d_scan_wscratch.grow(wscratch_elems, "pc_hip_scan_run: could not allocate the per-lane weight scratch");
+	return st;
 }
 
 extern "C" {
@@ -152,7 +137,7 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	a.totals = ctx->d_scan_totals;
 	a.work = &ctx->d_scan_totals->next_slot;
 	/* the scan's arguments in pc_kargs (PC_SCAN_*): point table, per-point totals, first flat index, slots per point */
-	a.in_start = (const double *)ctx->d_scan_pts;
+	a.in_start = (const double *)ctx->d_scan_pts.p;
 	a.sumw = ctx->d_scan_tot;
 	a.sumw2 = nullptr;
 	a.img_id0 = first;

@@ -154,9 +154,9 @@ __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spo
 
 struct pc_spot_member {
 	pc_hip_ctx *ctx = nullptr;
-	unsigned long long *d_map = nullptr;
-	double *d_zp = nullptr;
-	int *d_sel = nullptr;
+	pc_dev_buf<unsigned long long> d_map;
+	pc_dev_buf<double> d_zp;
+	pc_dev_buf<int> d_sel;
 };
 
 struct pc_hip_spot {
@@ -174,9 +174,6 @@ static void pc_spot_free_member(pc_spot_member &mb)
 	if (!mb.ctx) return;
 	(void)hipSetDevice(mb.ctx->device);
 	if (mb.ctx->stream) (void)hipStreamSynchronize(mb.ctx->stream);
-	if (mb.d_map) (void)hipFree(mb.d_map);
-	if (mb.d_zp) (void)hipFree(mb.d_zp);
-	if (mb.d_sel) (void)hipFree(mb.d_sel);
 	mb = pc_spot_member();
 }
 
@@ -204,15 +201,17 @@ static int pc_spot_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *gro
 	const double zexit = c0->host.z[c0->host.pm.nmax];
 	for (int k = 0; k < sp->np; k++) zp[k] = zexit + spec->distances[k];
 	for (pc_hip_ctx *c : ctxs) {
-		pc_spot_member mb;
-		mb.ctx = c;
-		sp->m.push_back(mb);
+		sp->m.emplace_back();
 		pc_spot_member &m = sp->m.back();
+		m.ctx = c;
 		hipError_t e = hipSetDevice(c->device);
-		if (e == hipSuccess) e = hipMalloc(&m.d_map, sp->map_elems*sizeof(unsigned long long));
-		if (e == hipSuccess) e = hipMalloc(&m.d_zp, zp.size()*sizeof(double));
-		if (e == hipSuccess) e = hipMalloc(&m.d_sel, sp->sel.size()*sizeof(int));
-		if (e == hipSuccess) e = hipMemcpy(m.d_zp, zp.data(), zp.size()*sizeof(double), hipMemcpyHostToDevice);
+		if (e == hipSuccess) {
+			st = m.d_map.grow(sp->map_elems, "pc_hip_spot_create: could not allocate the maps");
+			if (!st) st = m.d_zp.grow(zp.size(), "pc_hip_spot_create: could not allocate the plane positions");
+			if (!st) st = m.d_sel.grow(sp->sel.size(), "pc_hip_spot_create: could not allocate the energy selection");
+			if (st) { pc_hip_spot_destroy(sp); return st; }
+			e = hipMemcpy(m.d_zp, zp.data(), zp.size()*sizeof(double), hipMemcpyHostToDevice);
+		}
 		if (e == hipSuccess) e = hipMemcpy(m.d_sel, sp->sel.data(), sp->sel.size()*sizeof(int), hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipMemsetAsync(m.d_map, 0, sp->map_elems*sizeof(unsigned long long), c->stream);
 		if (e != hipSuccess) {
