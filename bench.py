@@ -8,7 +8,10 @@ constants, source parameters) are resident in HBM before the timed region; outpu
 struct _polycap_images, written by the kernel itself in coalesced runs: the photons a wave finalises together take the next
 free positions of the planes) stay in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs: set up, warm up, time the K steps, dump (with --dump-outputs) and print
+the result line.  Everything else it can measure runs with --full only (below).
 
 --dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float64, under 64 MB in all):
 efficiencies, sum_weights and photon_counts (exit, not entered, not transmitted, reflections) of the whole job, and with
@@ -25,7 +28,9 @@ value = started photons per second (i_start / wall; the unit of simulation work 
 efficiency), whole job, max-over-ranks wall time; exit photons/s is printed next to it.
 Weak scaling: every rank traces --photons slots.
 
-Extra legs, rank 0 at N = 1 only, after the timed region (each bounded to seconds):
+--full adds, after the timed region: `scheduler` and `roofline.valu_fp64` from one instrumented launch of the last step's
+slots, the `rccl` block (every rank's mean kernel time, one extra gather) under torch.distributed.run, and these legs,
+rank 0 at N = 1 only (each bounded to seconds; --no-extras leaves out all but cpu_baseline, --no-cpu-baseline that one):
   wall_incl_copyback  the same workload through the public C API with all 18 image planes copied back into host arrays
                       (SURVEY 8d's wall = kernel + reduce + result copy-back; never `value`)
   sweep_291           BASELINE C3's kernel: xos1 on the deck's 291-energy grid, histogram only, launches of 1e6 and 4e6 slots
@@ -62,10 +67,14 @@ def parse_args():
     ap.add_argument("--photons", type=int, default=10_000_000, help="exit-photon slots per GPU per step")
     ap.add_argument("--seed", type=int, default=20000)
     ap.add_argument("--no-images", action="store_true", help="histogram-only mode (no per-photon planes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip wall_incl_copyback, sweep_291 and ellip_l9_rough (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: scheduler statistics, the rccl block, the extra "
+                         "legs and the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the legs other than the CPU baseline (profiling runs)")
     ap.add_argument("--cpu-sample", type=int, default=0,
-                    help="exit-photon slots of the CPU baseline sample (0 = sized from a short probe to about 15 s of CPU work)")
+                    help="with --full: exit-photon slots of the CPU baseline sample (0 = sized from a short probe to about 15 s "
+                         "of CPU work)")
     ap.add_argument("--opt", action="append", default=[], help="kernel option name=value (event_threshold, blocks_per_cu, ...)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="collective backend for --gpus > 1 (nccl = RCCL over xGMI; gloo only to rehearse the multi-process "
@@ -176,40 +185,23 @@ def main():
         tt = torch.tensor([wall], dtype=torch.float64, device=red_dev if red_dev is not None else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
-        # one extra gather, outside the timed region: every rank's mean kernel time, so that the scaling record shows that the
-        # collective saw all the ranks and where the tail of a step is
-        rccl = pcd.ranks_report(float(np.mean(kernel_ms)), red_dev)
+        if args.full:
+            # one extra gather, outside the timed region: every rank's mean kernel time, so that the scaling record shows that
+            # the collective saw all the ranks and where the tail of a step is
+            rccl = pcd.ranks_report(float(np.mean(kernel_ms)), red_dev)
 
     if rank == 0:
         counters, sums = last
         eff = pcd.efficiencies_from_totals(counters, sums)
         dumped = None
         if args.dump_outputs:
-            # before anything else runs on the context: the instrumented launch below overwrites the last step's planes
+            # before anything else runs on the context: the instrumented launch of --full overwrites the last step's planes
             dumped = dump_outputs(args.dump_outputs, ctx, counters, sums, eff, n_local if keep_images else 0)
         avg_ms = float(np.mean(kernel_ms))
         alg_bytes = n_local * (BYTES_PER_EXIT_PHOTON + 8 * ne) if keep_images else 8.0 * (ne + 6)
         achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
         kernel = ctx.last_kernel() or "pc_trace_kernel"        # what traced the timed steps (the context picks it, hip.py)
-        # scheduler statistics: the production instantiation of the launching-wave kernel does not count march steps (the ballot
-        # sat in its hot loop); one instrumented launch of the last step's slots outside the timed region fills them in
-        ctx.set_option("march_stats", 1)
-        ctx.run(args.seed + args.steps - 1, slot0, n_local, keep_images=keep_images)
-        ctx.wait()
-        sched = ctx.phase_stats()
-        ctx.set_option("march_stats", 0)
         pmc = pmc_summary(n_local, keep_images, kernel)
-        # useful fp64 work of the kernel as executed (after certified skipping), from its own counters: a march lane-step is
-        # 6 FMA = 12 flop; a segment visit ~150 flop-equivalents (quadratic, 7 div, 1-2 sqrt, hexagon tests) and a reflection
-        # ~120 + 100 per energy; against the 78.6 TFLOP/s vector-fp64 peak of the MI355X
-        useful_flop = 12.0 * sched["march"]["lanes"] + 150.0 * sched["event"]["lanes"] \
-            + (120.0 + 100.0 * ne) * float(counters[3]) / max(1, int(counters[0])) * n_local
-        ref_flop_eq = 9.0e4 * (started / args.steps / world)   # the reference's literal march: ~9e4 flop-eq per started photon (8d)
-        valu = {"peak_tflops": 78.6, "useful_tflops": useful_flop / (avg_ms * 1e-3) / 1e12,
-                "frac": useful_flop / (avg_ms * 1e-3) / 1e12 / 78.6,
-                "reference_algorithm_equivalent_tflops": ref_flop_eq / (avg_ms * 1e-3) / 1e12,
-                "note": "useful = arithmetic the certified march still needs, from the kernel's own lane-step counters; the same "
-                        "photons cost the reference's literal march ~9e4 flop-equivalents each"}
         out = {
             "metric": "photons/s (started photons, whole job), xos1 10 keV",
             "value": started / wall,
@@ -232,7 +224,6 @@ def main():
             "efficiency_10keV": float(eff[0]),
             "avg_reflections": float(counters[3]) / max(1, int(counters[0])),
             "started_per_exit": started / max(1, exited),
-            "scheduler": sched,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "traffic": (pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0 if pmc else None,
@@ -242,9 +233,30 @@ def main():
                                  "runs (compact store); traffic and the VALU counters come from the committed rocprofv3 --pmc summary "
                                  "of this command (FETCH_SIZE + WRITE_SIZE in KB, raw: the guide's gfx950 x2 correction applies to "
                                  "16-B-per-lane streaming reads, this kernel's traffic is 8-B-per-lane stores), kernel_ms is measured live",
-                         "valu_fp64": valu, "valu_issue": valu_issue(pmc, avg_ms)},
+                         "valu_issue": valu_issue(pmc, avg_ms)},
         }
-        if world == 1 and not args.no_extras:
+        if args.full:
+            # scheduler statistics: the production instantiation of the launching-wave kernel does not count march steps (the
+            # ballot sat in its hot loop); one instrumented launch of the last step's slots outside the timed region fills them in
+            ctx.set_option("march_stats", 1)
+            ctx.run(args.seed + args.steps - 1, slot0, n_local, keep_images=keep_images)
+            ctx.wait()
+            sched = ctx.phase_stats()
+            ctx.set_option("march_stats", 0)
+            # useful fp64 work of the kernel as executed (after certified skipping), from its own counters: a march lane-step is
+            # 6 FMA = 12 flop; a segment visit ~150 flop-equivalents (quadratic, 7 div, 1-2 sqrt, hexagon tests) and a reflection
+            # ~120 + 100 per energy; against the 78.6 TFLOP/s vector-fp64 peak of the MI355X
+            useful_flop = 12.0 * sched["march"]["lanes"] + 150.0 * sched["event"]["lanes"] \
+                + (120.0 + 100.0 * ne) * float(counters[3]) / max(1, int(counters[0])) * n_local
+            ref_flop_eq = 9.0e4 * (started / args.steps / world)   # the reference's literal march: ~9e4 flop-eq per started photon (8d)
+            out["scheduler"] = sched
+            out["roofline"]["valu_fp64"] = {
+                "peak_tflops": 78.6, "useful_tflops": useful_flop / (avg_ms * 1e-3) / 1e12,
+                "frac": useful_flop / (avg_ms * 1e-3) / 1e12 / 78.6,
+                "reference_algorithm_equivalent_tflops": ref_flop_eq / (avg_ms * 1e-3) / 1e12,
+                "note": "useful = arithmetic the certified march still needs, from the kernel's own lane-step counters; the same "
+                        "photons cost the reference's literal march ~9e4 flop-equivalents each"}
+        if args.full and world == 1 and not args.no_extras:
             if keep_images:
                 out["wall_incl_copyback"] = wall_incl_copyback(deck, n_local, started / float(args.steps * n_local))
             out["sweep_291"] = side_workload("xos1", None, None, 1_000_000, dev_index, "profiles/r04/ne291_pmc_summary.json")
@@ -254,9 +266,8 @@ def main():
                                      "n_energies_291": side_workload("ellip_l9", None, 5.0, 500_000, dev_index,
                                                                      "profiles/r04/ellip291_pmc_summary.json")}
             out["leak_262144"] = leak_workload(262_144, dev_index)
-        if world == 1 and not args.no_extras:
             out["parity_fixture"] = parity_fixture(prob, dev_index)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prob, args, ctx)
         if dumped is not None:
             out["dump_outputs"] = dumped

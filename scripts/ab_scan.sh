@@ -19,7 +19,7 @@ done
 wait
 for name in $names; do
   if [ -f /tmp/abs/lib_$name.so ]; then
-    POLYCAP_AMD_LIB=/tmp/abs/lib_$name.so timeout -k 10 120 python bench.py --steps 5 --warmup 1 --no-extras --no-cpu-baseline $BENCH_OPTS 2>/dev/null | python -c "
+    POLYCAP_AMD_LIB=/tmp/abs/lib_$name.so timeout -k 10 120 python bench.py --full --steps 5 --warmup 1 --no-extras --no-cpu-baseline $BENCH_OPTS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['scheduler']
 print('$name: %.2f ms  %.4g started/s  march %.3g steps x %.1f lanes, event %.3g x %.1f, new %.3g x %.1f' % (d['roofline']['kernel_ms'], d['value'], s['march']['phases'], s['march']['avg_lanes'], s['event']['phases'], s['event']['avg_lanes'], s['new']['phases'], s['new']['avg_lanes']))" | tee -a gpurun_out/ab_scan/results.txt

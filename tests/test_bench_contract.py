@@ -83,29 +83,43 @@ def test_dump_sample_does_not_depend_on_the_store_order(monkeypatch):
     assert np.array_equal(small, rows[:700][np.lexsort(rows[:700].T[::-1])])
 
 
+FULL_ONLY = ("scheduler", "wall_incl_copyback", "sweep_291", "sweep_300", "ellip_l9_rough", "leak_262144", "parity_fixture",
+             "cpu_baseline")     # what a bench line carries with --full only
+
+
 @pytest.mark.gpu
 def test_dump_outputs_repeat_from_run_to_run(tmp_path):
-    """bench.py --dump-outputs: the same arguments give the same inputs, hence the same outputs, file for file; the result
-    line still carries the step time of exactly --steps timed steps."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--photons", "300000",
-           "--no-extras", "--no-cpu-baseline"]
+    """bench.py --dump-outputs: the same arguments give the same inputs, hence the same outputs, file for file, and --full
+    (which runs its instrumented launch on the same context after the dump) dumps the same files again; the result line
+    still carries the step time of exactly --steps timed steps.  A plain run measures nothing but its steps: none of what
+    --full adds, and at most 30 s of its whole time outside them."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--photons", "300000"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    import time
     import numpy as np
     dumps = []
-    for k in range(2):
+    for k, extra in enumerate(([], [], ["--full", "--no-extras", "--no-cpu-baseline"])):
         d = tmp_path / ("run%d" % k)
-        r = subprocess.run(cmd + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        t0 = time.perf_counter()
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        wall = time.perf_counter() - t0
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
         assert line["steps"] == 2 and line["ms_per_step"] > 0
+        if extra:
+            assert "scheduler" in line and "valu_fp64" in line["roofline"]
+        else:
+            assert not [key for key in FULL_ONLY if key in line] and "valu_fp64" not in line["roofline"]
+            assert wall - 3 * line["ms_per_step"] * 1e-3 < 30.0
         files = sorted(p.name for p in d.iterdir())
         assert files == ["efficiencies.npy", "exit_images.npy", "exit_weights.npy", "photon_counts.npy", "sum_weights.npy"]
         assert sum((d / f).stat().st_size for f in files) <= 64 << 20
         dumps.append({f[:-len(".npy")]: np.load(d / f) for f in files})
-    a, b = dumps
+    a = dumps[0]
     assert a["photon_counts"][0] == 300000 and a["exit_images"].shape == (300000, 17) and a["exit_weights"].shape == (300000, 1)
-    for f in a:
-        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f], equal_nan=True), f
+    for b in dumps[1:]:
+        for f in a:
+            assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f], equal_nan=True), f
     assert a["efficiencies"][0] == line["efficiency_10keV"]
 
 
@@ -151,8 +165,9 @@ def test_summariser_fails_on_a_missing_kernel(tmp_path):
 
 
 def test_committed_bench_line_has_the_contract_keys():
-    """profiles/r04/headline_bench.json is the line `python bench.py` printed on the MI355X box of the round's final evidence run:
-    the keys the driver reads, the two objects the tier asks for, and the extra legs DESIGN section 7 quotes."""
+    """profiles/r04/headline_bench.json is the line `python bench.py` printed on the MI355X box of the round's final evidence run
+    (the legs are `--full`'s now): the keys the driver reads, the two objects the tier asks for, and the extra legs DESIGN
+    section 7 quotes."""
     with open(os.path.join(ROOT, "profiles", "r04", "headline_bench.json")) as f:
         d = json.load(f)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",

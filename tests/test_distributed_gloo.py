@@ -50,7 +50,7 @@ def _worker(rank, world, port, n_total, seed, out_q):
     try:
         _, _, prob, _ = make_pair(O, "ellip", energies=(8.0, 10.0))
         r = pcd.run_sharded(prob, seed, n_total, rank=rank, world_size=world, trace_fn=_oracle_trace_fn())
-        rep = pcd.ranks_report(10.0 + rank)             # what bench.py prints as "rccl" under N > 1
+        rep = pcd.ranks_report(10.0 + rank)             # what bench.py --full prints as "rccl" under N > 1
         out_q.put((rank, r["counters"].tolist(), [str(v) for v in r["sumw_exact"]], r["efficiencies"].tolist(), r["slot0"], r["n_local"], rep))
     finally:
         dist.destroy_process_group()
@@ -99,8 +99,8 @@ def test_two_rank_gloo_equals_single_rank():
     _, _, prob, _ = make_pair(O, "ellip", energies=(8.0, 10.0))
     single = pcd.run_sharded(prob, seed, n_total, trace_fn=_oracle_trace_fn())
     for rank, counters, exact, eff, slot0, n_local, rep in res:
-        # the "rccl" block of a multi-rank bench line (bench.py under N > 1): every rank saw both ranks and the spread of their
-        # kernel times
+        # the "rccl" block of a multi-rank bench line (bench.py --full under N > 1): every rank saw both ranks and the spread of
+        # their kernel times
         assert rep == {"world_size": 2, "backend": "gloo", "ranks_seen": 2, "per_rank_kernel_ms": [10.0, 11.0]}
         assert counters == single["counters"].tolist()
         assert exact == [str(v) for v in single["sumw_exact"]]
@@ -156,15 +156,18 @@ def test_two_ranks_with_the_hip_kernel_equal_one_rank():
 @pytest.mark.gpu
 def test_bench_under_the_launcher_with_rccl_world_of_one():
     """bench.py exactly as the driver starts it for N > 1 (python -m torch.distributed.run ... bench.py --gpus N), with the
-    one rank a one-GPU box allows: process group on RCCL, the all-reduce of the packed totals on the device, the barrier."""
+    one rank a one-GPU box allows: process group on RCCL, the all-reduce of the packed totals on the device, the barrier, and
+    with --full the gather of the ranks' kernel times behind the "rccl" block."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--photons", "300000", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, env=env)
+                        "--photons", "300000", "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600,
+                       env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 1 and d["value"] > 1e7 and d["roofline"]["kernel_ms"] > 0
+    assert d["rccl"]["world_size"] == d["rccl"]["ranks_seen"] == 1 and d["rccl"]["backend"] == "nccl"
