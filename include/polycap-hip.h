@@ -288,6 +288,61 @@ POLYCAP_EXTERN int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t 
 POLYCAP_EXTERN int pc_hip_spot_reset(pc_hip_spot *spot);
 /* dims = {n_planes, n_selected, ny, nx}; *wide (optional) = 1 when the map accumulates with energies across lanes, 0 in LDS tiles */
 POLYCAP_EXTERN int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide);
+/* ---- exit-beam moments: the exact second-moment ("sigma") matrix of the entries of the last run at the optic's exit face, per
+ * energy, accumulated on the device in exact integers from what the run left there (pc_beam.h).  From it follow, in closed form
+ * and with no planes or window, the centroid, the RMS size at any distance d behind the exit face, the waist (focal) distance and
+ * size, and the divergence.  RMS values include the halo tails by definition; spot maps remain the tool for the profile's shape.
+ *
+ * The contract (IEEE fp64, evaluated in the order written, no contraction):
+ *   entries    those pc_hip_spot_add reads: exit photons (kind 0), extleak (1) and intleak (2) events of a leak_calc run
+ *   per entry  with position (x, y, z), direction (dx, dy, dz) and weights w[e], on the exit face ze = z[nmax]:
+ *              exit photons: dz = sqrt((1 - dx*dx) - dy*dy); leak events: the stored dz
+ *              t = (ze - z) / dz,  xe = x + dx*t,  ye = y + dy*t,  sx = dx / dz,  sy = dy / dz
+ *              X = rne(xe * 2^24), Y = rne(ye * 2^24), U = rne(sx * 2^24), V = rne(sy * 2^24) as int64 (rne: round half even)
+ *              W = round_half_even(w[e] * 2^32) as uint64, 0 for w <= 0 and NaN (the spot maps' q(w))
+ *              in range when dz > 0 and |X|, |Y|, |U|, |V| < 2^31 (|position| < 128 cm, |slope| < 128); anything else, NaN
+ *              included, adds its W to the (kind, energy) pair's outside counter
+ *   sums       per (kind, energy), over the entries in range, 15 signed 128-bit two's-complement sums as (lo, hi) uint64 pairs:
+ *              W, WX, WY, WU, WV, WXX, WXY, WXU, WXV, WYY, WYU, WYV, WUU, WUV, WVV (in this order); every term is below 2^94
+ *   entries    the sums of one kind take at most 2^32 - 1 entries over all adds (then none can wrap); an add past that fails
+ * Sums are integer sums: they depend neither on launch shape ("run_parts", compact or slot order, the kernel that traced the run),
+ * nor on how the slots were split into consecutive runs added to one set of sums, nor on the device count.
+ *
+ * Derived parameters (pc_hip_beam_params, host only), per energy from its 15 sums S, S_a, S_ab (a, b in X, Y, U, V):
+ *   N_ab = S*S_ab - S_a*S_b exactly (192 bits suffice); every integer is converted to the nearest double (ties to even) once
+ *   s = dbl(S);  weight = s * 2^-32;  mean_a = (dbl(S_a) / s) * 2^-24;  C_ab = (dbl(N_ab) / (s*s)) * 2^-48
+ *   waist_x = -C_xx' / C_x'x',  waist_y = -C_yy' / C_y'y',  waist_r = -(C_xx' + C_yy') / (C_x'x' + C_y'y')   (cm behind the exit face)
+ *   size_waist_x = sqrt(max(C_xx - (C_xx'*C_xx') / C_x'x', 0)), size_waist_y likewise,
+ *   size_waist_r = sqrt(max((C_xx + C_yy) - (B*B) / D, 0)) with B = C_xx' + C_yy', D = C_x'x' + C_y'y'
+ *   size_exit_x = sqrt(C_xx), size_exit_y = sqrt(C_yy), size_exit_r = sqrt(C_xx + C_yy), div_x = sqrt(C_x'x'), div_y = sqrt(C_y'y')
+ *   a column whose denominator is 0 is NaN; with S == 0 every column but the weight is NaN
+ * Columns of a row, in order (cm, rad; x' = dx/dz): weight, x, y, xp, yp, cov_xx, cov_xy, cov_xxp, cov_xyp, cov_yy, cov_yxp,
+ * cov_yyp, cov_xpxp, cov_xpyp, cov_ypyp, waist_x, waist_y, waist_r, size_waist_x, size_waist_y, size_waist_r, size_exit_x,
+ * size_exit_y, size_exit_r, div_x, div_y (pc_hip_beam_columns).
+ * At a distance d (pc_hip_beam_at): x(d) = x + d*xp, y(d) = y + d*yp, vx = (C_xx + (2*d)*C_xx') + (d*d)*C_x'x', vy likewise,
+ * size_x = sqrt(max(vx, 0)), size_y = sqrt(max(vy, 0)), size_r = sqrt(max(vx, 0) + max(vy, 0)); NaN when S == 0. */
+typedef struct pc_hip_beam pc_hip_beam;
+#define PC_HIP_BEAM_NSUMS 15
+#define PC_HIP_BEAM_NCOLS 26
+#define PC_HIP_BEAM_NAT 5
+/* Empty sums for all three kinds on the context's device (the context must outlive them).  The group variant keeps one set per
+ * member; reading it adds the members' sums exactly on the host. */
+POLYCAP_EXTERN int pc_hip_beam_create(pc_hip_ctx *ctx, pc_hip_beam **beam);
+POLYCAP_EXTERN int pc_hip_group_beam_create(pc_hip_group *group, pc_hip_beam **beam);
+POLYCAP_EXTERN void pc_hip_beam_destroy(pc_hip_beam *beam);
+/* Adds the entries of kind 0, 1 or 2 of the last run, as pc_hip_spot_add: enqueued on the context's stream behind the run; leak kinds
+ * wait for the run first (its events are ordered when it is waited for).  Anything else is PC_HIP_ERR_INVALID. */
+POLYCAP_EXTERN int pc_hip_beam_add(pc_hip_beam *beam, int kind);
+/* sums [3][n_energies][15][2], outside [3][n_energies], n_entries [3] (any may be NULL); waits for the adds */
+POLYCAP_EXTERN int pc_hip_beam_read(pc_hip_beam *beam, uint64_t *sums, uint64_t *outside, int64_t *n_entries);
+POLYCAP_EXTERN int pc_hip_beam_reset(pc_hip_beam *beam);
+POLYCAP_EXTERN int pc_hip_beam_info(const pc_hip_beam *beam, int *n_energies);
+/* host only: params [n_energies][26] from sums [n_energies][15][2] of one kind */
+POLYCAP_EXTERN void pc_hip_beam_params(size_t n_energies, const uint64_t *sums, double *params);
+/* host only: out [n_energies][n_distances][5] = {x, y, size_x, size_y, size_r} at the distances (cm behind the exit face) */
+POLYCAP_EXTERN void pc_hip_beam_at(size_t n_energies, const uint64_t *sums, size_t n_distances, const double *distances, double *out);
+/* the 26 column names of pc_hip_beam_params, comma-separated */
+POLYCAP_EXTERN const char *pc_hip_beam_columns(void);
 /* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
  * a focusing optic) in one launch, with exact totals per point.
  *
@@ -389,6 +444,16 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_spot(void *efficiencies, int
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_stderr(void *efficiencies, size_t *n_energies, double **stderr_, void *error);
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_moments(void *efficiencies, int64_t *n_started, uint64_t **sumw_fixed,
 	uint64_t **sumw2_fixed, void *error);
+
+/* Exit-beam moments of a result made with POLYCAP_BEAM=1 (every path of the call: one device, POLYCAP_HIP_DEVICES groups, leak_calc,
+ * POLYCAP_IMAGES=0 with the chunked runs of POLYCAP_SPOT_SHARE).  kind 0 = exit photons, 1 = extleak, 2 = intleak (leak_calc runs).
+ * _get_beam: *params [n_energies][26], pc_hip_beam_params of the run's exact sums (columns: pc_hip_beam_columns).  _get_beam_sums:
+ * copies of the sums [n_energies][15][2] and outside counters [n_energies] (either may be NULL) and the entry count, so that the
+ * results of several seeds can be pooled exactly (add the sums as 128-bit integers, then pc_hip_beam_params).  Copies are freed
+ * with polycap_free.  A result made without the variable is an error.  Return 1, or 0 with *error (a polycap_error**) set. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_beam(void *efficiencies, int kind, size_t *n_energies, double **params, void *error);
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_beam_sums(void *efficiencies, int kind, size_t *n_energies, uint64_t **sums,
+	uint64_t **outside, int64_t *n_entries, void *error);
 
 #ifdef __cplusplus
 }

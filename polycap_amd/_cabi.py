@@ -207,6 +207,26 @@ def lib():
     L.pc_hip_spot_reset.restype = C.c_int
     L.pc_hip_spot_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int)]
     L.pc_hip_spot_info.restype = C.c_int
+    L.pc_hip_beam_create.argtypes = [C.c_void_p, P(C.c_void_p)]
+    L.pc_hip_beam_create.restype = C.c_int
+    L.pc_hip_group_beam_create.argtypes = [C.c_void_p, P(C.c_void_p)]
+    L.pc_hip_group_beam_create.restype = C.c_int
+    L.pc_hip_beam_destroy.argtypes = [C.c_void_p]
+    L.pc_hip_beam_destroy.restype = None
+    L.pc_hip_beam_add.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_beam_add.restype = C.c_int
+    L.pc_hip_beam_read.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), c_int64_p]
+    L.pc_hip_beam_read.restype = C.c_int
+    L.pc_hip_beam_reset.argtypes = [C.c_void_p]
+    L.pc_hip_beam_reset.restype = C.c_int
+    L.pc_hip_beam_info.argtypes = [C.c_void_p, P(C.c_int)]
+    L.pc_hip_beam_info.restype = C.c_int
+    L.pc_hip_beam_params.argtypes = [C.c_size_t, P(C.c_uint64), c_double_p]
+    L.pc_hip_beam_params.restype = None
+    L.pc_hip_beam_at.argtypes = [C.c_size_t, P(C.c_uint64), C.c_size_t, c_double_p, c_double_p]
+    L.pc_hip_beam_at.restype = None
+    L.pc_hip_beam_columns.argtypes = []
+    L.pc_hip_beam_columns.restype = C.c_char_p
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
     u64p = P(C.c_uint64)

@@ -131,6 +131,9 @@ def _lib():
         "pc_transmission_efficiencies_get_spot": (C.c_int, [vp, C.c_int, P(C.c_int32), P(_dp), _dp, P(_dp), P(_dp), P(_dp), epp]),
         "pc_transmission_efficiencies_get_stderr": (C.c_int, [vp, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_moments": (C.c_int, [vp, P(C.c_int64), P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
+        "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
+        "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
+                                                               P(C.c_int64), epp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -445,6 +448,28 @@ class TransmissionEfficiencies(_LeakData):
         ne = len(self.data[0])
         return dict(n_started=int(ns.value), sumw_fixed=_take(a, 2 * ne, np.uint64).reshape(ne, 2),
                     sumw2_fixed=_take(b, 2 * ne, np.uint64).reshape(ne, 2))
+
+    def beam(self, kind="exit"):
+        """Exit-beam moments of a run made with POLYCAP_BEAM=1 (extension, pc_transmission_efficiencies_get_beam / _get_beam_sums):
+        dict of the 26 named columns of pc_hip_beam_params (arrays over the energies; cm, rad), the exact sums uint64
+        [n_energies, 15, 2], outside [n_energies] and n_entries.  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        from .hip import beam_columns
+        L = _lib()
+        k = self.SPOT_KINDS[kind]
+        n = C.c_size_t(0)
+        p = _dp()
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_beam(self._h, k, C.byref(n), C.byref(p), C.byref(err))
+        _check(err)
+        ne = n.value
+        rows = _take(p, ne * 26).reshape(ne, 26)
+        a, b = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        ni = C.c_int64(0)
+        L.pc_transmission_efficiencies_get_beam_sums(self._h, k, C.byref(n), C.byref(a), C.byref(b), C.byref(ni), C.byref(err))
+        _check(err)
+        out = {name: rows[:, j].copy() for j, name in enumerate(beam_columns())}
+        out.update(sums=_take(a, ne * 30, np.uint64).reshape(ne, 15, 2), outside=_take(b, ne, np.uint64), n_entries=int(ni.value))
+        return out
 
     def _start(self):
         L = _lib()

@@ -2757,6 +2757,7 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 
 #include "pc_group.h"
 #include "pc_spot.h"
+#include "pc_beam.h"
 #include "pc_scan.h"
 
 /* Heaviest slots first.  A leak launch ends with its longest slot: 20 000 units of work on one lane, which advances several

@@ -19,6 +19,10 @@
  *   /<G>/Weight_Total [nE] a.u. (sum of the event weights / started photons)   /<G>/N_Reflections [n] a.u.
  *   /InternalLeaks/Electric_Vector [2, n] "[cm,cm]"
  *
+ *   extensions: /Transmission_Efficiencies_StdErr (POLYCAP_STDERR=1), /Spot (POLYCAP_SPOT), and with POLYCAP_BEAM=1, for <K> in Exit,
+ *   ExtLeak, IntLeak (the kinds the run has): /Beam/<K>_Sums [nE, 15, 2] uint64, /Beam/<K>_Outside [nE] uint64,
+ *   /Beam/<K>_Entries [1] uint64 and /Beam/<K> [nE, 26] fp64 with a "Columns" attribute (include/polycap-hip.h)
+ *
  * libhdf5 is bound at run time (dlopen), like xraylib in pc_optconst.c, so libpolycap.so carries no link-time
  * dependency on it: hosts without HDF5 get POLYCAP_ERROR_UNSUPPORTED from this one function and nothing else changes.
  * POLYCAP_HDF5_LIB names the library explicitly.
@@ -64,6 +68,7 @@ static struct {
 	pc_herr (*awrite)(pc_hid, pc_hid, const void *);
 	pc_herr (*aclose)(pc_hid);
 	pc_hid *native_double;   /* H5T_NATIVE_DOUBLE_g, valid after H5open() */
+	pc_hid *native_ullong;   /* H5T_NATIVE_ULLONG_g (the /Beam sums) */
 	pc_hid *c_s1;            /* H5T_C_S1_g */
 	char name[256];
 } h5;
@@ -92,6 +97,7 @@ static int pc_h5_bind(void *handle)
 	PC_SYM(awrite, "H5Awrite");
 	PC_SYM(aclose, "H5Aclose");
 	PC_SYM(native_double, "H5T_NATIVE_DOUBLE_g");
+	PC_SYM(native_ullong, "H5T_NATIVE_ULLONG_g");
 	PC_SYM(c_s1, "H5T_C_S1_g");
 #undef PC_SYM
 	unsigned maj = 0, min = 0, rel = 0;
@@ -134,6 +140,45 @@ static int pc_h5_load(void)
 const char *pc_hdf5_provider(void)
 {
 	return pc_h5_load() ? h5.name : "none";
+}
+
+/* one string attribute of a dataset */
+static bool pc_h5_attr(pc_hid dset, const char *name, const char *value)
+{
+	pc_hid aspace = -1, atype = -1, attr = -1;
+	bool ok = false;
+	if ((aspace = h5.screate(PC_H5S_SCALAR)) < 0) goto fail;
+	if ((atype = h5.tcopy(*h5.c_s1)) < 0) goto fail;
+	if (h5.tset_size(atype, strlen(value)) < 0) goto fail;
+	if ((attr = h5.acreate2(dset, name, atype, aspace, PC_H5P_DEFAULT, PC_H5P_DEFAULT)) < 0) goto fail;
+	if (h5.awrite(attr, atype, value) < 0) goto fail;
+	ok = true;
+fail:
+	if (attr >= 0 && h5.aclose(attr) < 0) ok = false;
+	if (atype >= 0 && h5.tclose(atype) < 0) ok = false;
+	if (aspace >= 0 && h5.sclose(aspace) < 0) ok = false;
+	return ok;
+}
+
+/* extension: one dataset of a native type (uint64 or fp64, non-empty) with its "Units" attribute and, when columns is not NULL, a
+ * "Columns" attribute naming the last dimension's entries */
+static bool pc_h5_typed(pc_hid file, int rank, const pc_hsize *dim, const char *name, pc_hid type, const void *data, const char *units,
+	const char *columns, polycap_error **error)
+{
+	pc_hid space = -1, dset = -1;
+	bool ok = false;
+	if ((space = h5.screate_simple(rank, dim, NULL)) < 0) goto fail;
+	if ((dset = h5.dcreate2(file, name, type, space, PC_H5P_DEFAULT, PC_H5P_DEFAULT, PC_H5P_DEFAULT)) < 0) goto fail;
+	if (h5.dwrite(dset, type, PC_H5S_ALL, PC_H5S_ALL, PC_H5P_DEFAULT, data) < 0) goto fail;
+	if (!pc_h5_attr(dset, "Units", units)) goto fail;
+	if (columns != NULL && !pc_h5_attr(dset, "Columns", columns)) goto fail;
+	ok = true;
+fail:
+	if (dset >= 0 && h5.dclose(dset) < 0) ok = false;
+	if (space >= 0 && h5.sclose(space) < 0) ok = false;
+	if (!ok)
+		polycap_set_error(error, POLYCAP_ERROR_IO, "polycap_transmission_efficiencies_write_hdf5: could not write dataset %s", name);
+	return ok;
 }
 
 /* one fp64 dataset + its "Units" attribute (reference :229-318) */
@@ -339,6 +384,36 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		}
 		free(sel_e);
 		if (!sok) goto close;
+	}
+
+	if (efficiencies->beam != NULL) {
+		/* extension: the exact exit-beam sums of POLYCAP_BEAM=1 and their derived rows (include/polycap-hip.h) */
+		const struct pc_beam_result *br = efficiencies->beam;
+		static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+		bool bok = pc_h5_group(file, "/Beam", error);
+		double *rows = malloc(sizeof(double) * PC_HIP_BEAM_NCOLS * (ne ? ne : 1));
+		bok = bok && rows != NULL;
+		for (int k = 0; k < 3 && bok; k++) {
+			if (br->sums[k] == NULL)
+				continue;
+			char name[64];
+			pc_hsize bd[3] = { (pc_hsize)ne, PC_HIP_BEAM_NSUMS, 2 };
+			const uint64_t n_entries = (uint64_t)br->n_entries[k];
+			snprintf(name, sizeof name, "/Beam/%s_Sums", names[k]);
+			bok = bok && pc_h5_typed(file, 3, bd, name, *h5.native_ullong, br->sums[k], "2^-32 x (1, 2^-24 cm|rad, 2^-48 cm^2|cm rad|rad^2)",
+			                         "W,WX,WY,WU,WV,WXX,WXY,WXU,WXV,WYY,WYU,WYV,WUU,WUV,WVV", error);
+			snprintf(name, sizeof name, "/Beam/%s_Outside", names[k]);
+			bok = bok && pc_h5_typed(file, 1, bd, name, *h5.native_ullong, br->outside[k], "2^-32", NULL, error);
+			snprintf(name, sizeof name, "/Beam/%s_Entries", names[k]);
+			pc_hsize one = 1;
+			bok = bok && pc_h5_typed(file, 1, &one, name, *h5.native_ullong, &n_entries, "a.u.", NULL, error);
+			pc_hip_beam_params(ne, br->sums[k], rows);
+			pc_hsize pd[2] = { (pc_hsize)ne, PC_HIP_BEAM_NCOLS };
+			snprintf(name, sizeof name, "/Beam/%s", names[k]);
+			bok = bok && pc_h5_typed(file, 2, pd, name, *h5.native_double, rows, "a.u., cm, rad", pc_hip_beam_columns(), error);
+		}
+		free(rows);
+		if (!bok) goto close;
 	}
 
 	if (!pc_h5_group(file, "/Input", error)) goto close;

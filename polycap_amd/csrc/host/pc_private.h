@@ -136,6 +136,13 @@ struct pc_spot_result {
 	double *outside[3];        /* [plane][energy] */
 };
 
+/* extension: exact exit-beam sums of a run made with POLYCAP_BEAM=1 (pc_transmission_efficiencies_get_beam / _get_beam_sums) */
+struct pc_beam_result {
+	uint64_t *sums[3];         /* exit photons, extleak, intleak: [energy][15][2] (lo, hi), NULL when the run has none */
+	uint64_t *outside[3];      /* [energy] */
+	int64_t n_entries[3];
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -144,6 +151,7 @@ struct _polycap_transmission_efficiencies {
 	polycap_source *source;
 	int synthetic_constants;   /* extension: see pc_transmission_efficiencies_synthetic */
 	struct pc_spot_result *spot;
+	struct pc_beam_result *beam;
 	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
 	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
 	int64_t n_started;
@@ -198,5 +206,6 @@ pc_hip_group *pc_group_for(pc_ctx_cache *c, polycap_description *description, si
 	const polycap_source *source, int n_devices, const int *devices, const char *caller, polycap_error **error);
 void pc_set_hip_error(polycap_error **error, const char *caller, int status);
 void pc_spot_result_free(struct pc_spot_result *spot);
+void pc_beam_result_free(struct pc_beam_result *beam);
 
 #endif

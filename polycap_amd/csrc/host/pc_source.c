@@ -483,11 +483,12 @@ static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 	}
 }
 
-/* POLYCAP_IMAGES=0 with spot maps on one context: the exit data of the run stay on the device, and a run whose exit data would take
- * more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by (seed, slot): the
- * same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is added to the map.
- * fixed [2*ne] receives the weights' sums; fixed2 (NULL unless POLYCAP_STDERR) those of the squared weights. */
-static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
+/* POLYCAP_IMAGES=0 with spot maps or beam moments on one context: the exit data of the run stay on the device, and a run whose exit
+ * data would take more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by
+ * (seed, slot): the same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is
+ * added to the map and to the beam sums (either may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
+ * POLYCAP_STDERR) those of the squared weights. */
+static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
 	size_t ne, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	uint64_t *part = malloc(2*ne*sizeof(uint64_t));
@@ -501,8 +502,10 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, uint64_t seed, in
 		const int64_t n = (n_photons - lo < chunk) ? n_photons - lo : chunk;
 		int64_t c[6];
 		st = pc_hip_transmission_run(ctx, seed, lo, n, max_attempts, 1);
-		if (st == PC_HIP_OK)
+		if (st == PC_HIP_OK && spot != NULL)
 			st = pc_hip_spot_add(spot, 0);
+		if (st == PC_HIP_OK && beam != NULL)
+			st = pc_hip_beam_add(beam, 0);
 		if (st == PC_HIP_OK)
 			st = pc_hip_transmission_totals(ctx, NULL, c, part);
 		if (st != PC_HIP_OK)
@@ -569,6 +572,32 @@ static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *sp
 	return st;
 }
 
+static void *pc_beam_dup(const void *p, size_t bytes)
+{
+	void *q = malloc(bytes ? bytes : 1);
+	if (q != NULL && bytes)
+		memcpy(q, p, bytes);
+	return q;
+}
+
+/* the exact beam sums of every kind the run has (exit photons; leak runs also extleak and intleak) into the result */
+static int pc_beam_store(polycap_transmission_efficiencies *eff, pc_hip_beam *beam, int leak_calc)
+{
+	const size_t ne = eff->n_energies, per_kind = ne*PC_HIP_BEAM_NSUMS*2;
+	struct pc_beam_result *br = eff->beam = calloc(1, sizeof(*br));
+	uint64_t *sums = malloc(sizeof(uint64_t)*3*per_kind), *out = malloc(sizeof(uint64_t)*3*ne);
+	int st = (br != NULL && sums != NULL && out != NULL) ? pc_hip_beam_read(beam, sums, out, br->n_entries) : PC_HIP_ERR_MEMORY;
+	for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++) {
+		br->sums[kind] = pc_beam_dup(sums + kind*per_kind, sizeof(uint64_t)*per_kind);
+		br->outside[kind] = pc_beam_dup(out + kind*ne, sizeof(uint64_t)*ne);
+		if (br->sums[kind] == NULL || br->outside[kind] == NULL)
+			st = PC_HIP_ERR_MEMORY;
+	}
+	free(sums);
+	free(out);
+	return st;
+}
+
 /* the argument checks of the reference call, in its order: the message of the first one that fails, or NULL */
 static const char *pc_transmission_args_bad(const polycap_source *source, const polycap_progress_monitor *progress_monitor, int n_photons)
 {
@@ -598,6 +627,7 @@ static const char *pc_transmission_args_bad(const polycap_source *source, const 
 struct pc_run_request {
 	int timing;                /* POLYCAP_TIMING: stage times on stderr */
 	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
+	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
 	struct pc_spot_request spot;
 	int devices[64], n_devices;
 	int keep_images;
@@ -626,7 +656,27 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 		return -1;
 	}
 	r->stderr_on = stderr_env != NULL && strcmp(stderr_env, "1") == 0;
-	if (pc_spot_request_parse(&r->spot, ne, error) != 0 || pc_env_devices(r->devices, &r->n_devices, error) != 0)
+	const char *beam_env = getenv("POLYCAP_BEAM");
+	if (beam_env != NULL && strcmp(beam_env, "0") != 0 && strcmp(beam_env, "1") != 0) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_BEAM=%s: must be 0 or 1", beam_env);
+		return -1;
+	}
+	r->beam_on = beam_env != NULL && strcmp(beam_env, "1") == 0;
+	if (pc_spot_request_parse(&r->spot, ne, error) != 0)
+		return -1;
+	if (r->beam_on && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the beam moments' chunked runs too */
+		r->spot.share = 0.5;
+		const char *share = getenv("POLYCAP_SPOT_SHARE");
+		if (share != NULL && *share != '\0') {
+			char *end = NULL;
+			r->spot.share = strtod(share, &end);
+			if (*end != '\0' || !(r->spot.share > 0. && r->spot.share <= 1.)) {
+				polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SPOT_SHARE=%s: must be a fraction in (0, 1]", share);
+				return -1;
+			}
+		}
+	}
+	if (pc_env_devices(r->devices, &r->n_devices, error) != 0)
 		return -1;
 	const char *img_env = getenv("POLYCAP_IMAGES");
 	r->keep_images = !(img_env != NULL && strcmp(img_env, "0") == 0);
@@ -656,18 +706,21 @@ struct pc_target {
 	pc_hip_group *group;
 };
 
-/* Trace stage: with POLYCAP_SPOT the maps are made first (exit photons; leak runs also extleak and intleak), then the options are
- * set and the run is enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the totals and moments, and added
- * every range to spot[0]. */
+/* Trace stage: with POLYCAP_SPOT the maps are made first (exit photons; leak runs also extleak and intleak), with POLYCAP_BEAM the
+ * beam sums, then the options are set and the run is enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the
+ * totals and moments, and added every range to spot[0] and *beam. */
 static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak_calc, uint64_t seed, int64_t n_photons, size_t ne,
-	pc_hip_spot *spot[3], int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
+	pc_hip_spot *spot[3], pc_hip_beam **beam, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	int st = PC_HIP_OK;
 	int64_t chunk = 0;
-	if (r->spot.set) {
+	if (r->spot.set)
 		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++)
 			st = t.group != NULL ? pc_hip_group_spot_create(t.group, &r->spot.spec, &spot[kind]) : pc_hip_spot_create(t.ctx, &r->spot.spec, &spot[kind]);
-		/* POLYCAP_IMAGES=0 with spot maps is chunked on one device only: a group traces the whole run at once */
+	if (r->beam_on && st == PC_HIP_OK)
+		st = t.group != NULL ? pc_hip_group_beam_create(t.group, beam) : pc_hip_beam_create(t.ctx, beam);
+	if (r->spot.set || r->beam_on) {
+		/* POLYCAP_IMAGES=0 with spot maps or beam moments is chunked on one device only: a group traces the whole run at once */
 		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
 			uint64_t total_b = 0;
 			st = pc_hip_device_memory(t.ctx, NULL, &total_b);
@@ -691,10 +744,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		return st;
 	if (chunk > 0 && chunk < n_photons) {
 		*chunked = 1;
-		return pc_spot_chunked(t.ctx, spot[0], seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
+		return pc_spot_chunked(t.ctx, spot[0], *beam, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
 	}
-	/* POLYCAP_SPOT: the run keeps its exit data on the device for the maps even with POLYCAP_IMAGES=0 (then nothing is copied back) */
-	const int device_images = r->keep_images || r->spot.set;
+	/* POLYCAP_SPOT, POLYCAP_BEAM: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
+	const int device_images = r->keep_images || r->spot.set || r->beam_on;
 	if (leak_calc)
 		return t.group != NULL ? pc_hip_group_run_leak(t.group, seed, n_photons, r->max_attempts, 1)
 		                       : pc_hip_transmission_run_leak(t.ctx, seed, 0, n_photons, r->max_attempts, 1);
@@ -742,6 +795,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	double *sum_weights = NULL;
 	uint64_t *sum_fixed = NULL, *sum_fixed2 = NULL;      /* the exact moments A and B; B and the result's copy only with POLYCAP_STDERR */
 	pc_hip_spot *spot[3] = { NULL, NULL, NULL };         /* exit photons, extleak, intleak */
+	pc_hip_beam *beam = NULL;                            /* POLYCAP_BEAM: the exact beam sums of every kind */
 	int64_t counters[6] = { 0, 0, 0, 0, 0, 0 };
 	int status = PC_HIP_OK, chunked = 0, reduced_by = 0;      /* a failed HIP call: its error is set at `out` */
 	double t_stage[6];
@@ -773,7 +827,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	const uint64_t seed = req.have_seed ? req.seed : source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
 	source->run_index++;
 
-	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
+	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
 	t_stage[2] = t_stage[3] = pc_now_ms();
 	if (status == PC_HIP_OK && req.keep_images)
 		status = pc_fetch_images(t, eff, n_photons, &t_stage[3]);
@@ -799,6 +853,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	for (int kind = chunked ? 1 : 0; kind <= 2 && status == PC_HIP_OK; kind++)      /* a chunked run has added its exit map */
 		if (spot[kind] != NULL)
 			status = pc_hip_spot_add(spot[kind], kind);
+	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && beam != NULL; kind++)
+		status = pc_hip_beam_add(beam, kind);
 	if (status != PC_HIP_OK)
 		goto out;
 
@@ -815,6 +871,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	for (int kind = 0; kind <= 2 && status == PC_HIP_OK; kind++)
 		if (spot[kind] != NULL)
 			status = pc_spot_store(eff, spot[kind], &req.spot, kind);
+	if (status == PC_HIP_OK && beam != NULL)
+		status = pc_beam_store(eff, beam, leak_calc);
 	if (status != PC_HIP_OK)
 		goto out;
 	if (req.stderr_on) {      /* without POLYCAP_STDERR the result keeps no moments, and its stderr and moment getters fail */
@@ -838,6 +896,7 @@ out:
 		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
 	for (int kind = 0; kind <= 2; kind++)
 		pc_hip_spot_destroy(spot[kind]);
+	pc_hip_beam_destroy(beam);
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

@@ -204,6 +204,7 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	free(efficiencies->efficiencies);
 	pc_images_free(efficiencies->images);
 	pc_spot_result_free(efficiencies->spot);
+	pc_beam_result_free(efficiencies->beam);
 	free(efficiencies->sumw_fixed);
 	free(efficiencies->sumw2_fixed);
 	free(efficiencies->stderrs);
@@ -272,6 +273,83 @@ int pc_transmission_efficiencies_get_spot(void *efficiencies_, int kind, int32_t
 	if (energies != NULL) *energies = e;
 	if (maps != NULL) *maps = m;
 	if (outside != NULL) *outside = o;
+	return 1;
+}
+
+void pc_beam_result_free(struct pc_beam_result *beam)
+{
+	if (beam == NULL)
+		return;
+	for (int k = 0; k < 3; k++) {
+		free(beam->sums[k]);
+		free(beam->outside[k]);
+	}
+	free(beam);
+}
+
+/* the beam sums of `kind` of a result, or NULL with *error set */
+static const struct pc_beam_result *pc_beam_of(const polycap_transmission_efficiencies *efficiencies, int kind, const char *fn, polycap_error **error)
+{
+	if (efficiencies == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: efficiencies cannot be NULL", fn);
+		return NULL;
+	}
+	if (efficiencies->beam == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run was made without POLYCAP_BEAM=1", fn);
+		return NULL;
+	}
+	if (kind < 0 || kind > 2 || efficiencies->beam->sums[kind] == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: kind must be 0 (exit photons), or 1 (extleak) / 2 (intleak) for a leak_calc run", fn);
+		return NULL;
+	}
+	return efficiencies->beam;
+}
+
+int pc_transmission_efficiencies_get_beam(void *efficiencies_, int kind, size_t *n_energies, double **params, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	const struct pc_beam_result *br = pc_beam_of(efficiencies, kind, "pc_transmission_efficiencies_get_beam", error);
+	if (br == NULL)
+		return 0;
+	if (params == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_beam: params cannot be NULL");
+		return 0;
+	}
+	const size_t ne = efficiencies->n_energies;
+	double *p = malloc(sizeof(double)*PC_HIP_BEAM_NCOLS*(ne ? ne : 1));
+	if (p == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_beam: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	pc_hip_beam_params(ne, br->sums[kind], p);
+	if (n_energies != NULL) *n_energies = ne;
+	*params = p;
+	return 1;
+}
+
+int pc_transmission_efficiencies_get_beam_sums(void *efficiencies_, int kind, size_t *n_energies, uint64_t **sums, uint64_t **outside,
+	int64_t *n_entries, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	const struct pc_beam_result *br = pc_beam_of(efficiencies, kind, "pc_transmission_efficiencies_get_beam_sums", error);
+	if (br == NULL)
+		return 0;
+	const size_t ne = efficiencies->n_energies;
+	uint64_t *a = NULL, *b = NULL;
+	int ok = 1;
+	if (sums != NULL) ok = (a = pc_dup(br->sums[kind], sizeof(uint64_t)*PC_HIP_BEAM_NSUMS*2*ne)) != NULL;
+	if (outside != NULL && ok) ok = (b = pc_dup(br->outside[kind], sizeof(uint64_t)*ne)) != NULL;
+	if (!ok) {
+		free(a); free(b);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_beam_sums: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (n_energies != NULL) *n_energies = ne;
+	if (sums != NULL) *sums = a;
+	if (outside != NULL) *outside = b;
+	if (n_entries != NULL) *n_entries = br->n_entries[kind];
 	return 1;
 }
 

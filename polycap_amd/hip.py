@@ -468,6 +468,102 @@ class SpotMap:
                     outside_map=out.astype(np.float64) * 2.0 ** -32)
 
 
+BEAM_SUMS = ("W", "WX", "WY", "WU", "WV", "WXX", "WXY", "WXU", "WXV", "WYY", "WYU", "WYV", "WUU", "WUV", "WVV")
+BEAM_AT = ("x", "y", "size_x", "size_y", "size_r")
+
+
+def beam_columns():
+    """the 26 column names of pc_hip_beam_params, in order"""
+    return tuple(_cabi.lib().pc_hip_beam_columns().decode().split(","))
+
+
+def beam_params(sums, distances=None):
+    """Derived parameters of exact beam sums uint64 [n_energies, 15, 2] (pc_hip_beam_params, host only): a dict of the named
+    columns (arrays over the energies).  With distances (cm behind the exit face) also the centroid and RMS sizes there
+    (pc_hip_beam_at) as at_x, at_y, at_size_x, at_size_y, at_size_r [n_energies, n_distances]."""
+    L = _cabi.lib()
+    S = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1, 15, 2)
+    ne = S.shape[0]
+    rows = np.zeros((ne, 26), dtype=np.float64)
+    L.pc_hip_beam_params(ne, S.ctypes.data_as(C.POINTER(C.c_uint64)), dptr(rows))
+    out = {name: rows[:, k].copy() for k, name in enumerate(beam_columns())}
+    if distances is not None:
+        d = np.ascontiguousarray(distances, dtype=np.float64).ravel()
+        at = np.zeros((ne, d.shape[0], 5), dtype=np.float64)
+        L.pc_hip_beam_at(ne, S.ctypes.data_as(C.POINTER(C.c_uint64)), d.shape[0], dptr(d), dptr(at))
+        out["distances"] = d
+        for k, name in enumerate(BEAM_AT):
+            out["at_" + name] = at[:, :, k].copy()
+    return out
+
+
+class BeamMoments:
+    """Exit-beam moments of a TraceContext or a TraceGroup (pc_hip_beam_*): the exact second-moment matrix of position and slope
+    of the entries of the last run at the optic's exit face, per energy, as signed 128-bit integer sums on the device.  The
+    contract is written down in include/polycap-hip.h.  One object keeps the sums of all three kinds (exit, extleak, intleak)."""
+
+    def __init__(self, owner):
+        self._L = _cabi.lib()
+        self.owner = owner                      # keeps the context alive as long as the sums
+        h = C.c_void_p()
+        if isinstance(owner, TraceGroup):
+            st = self._L.pc_hip_group_beam_create(owner._h, C.byref(h))
+        else:
+            st = self._L.pc_hip_beam_create(owner._h, C.byref(h))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_beam_create", st)
+        self._h = h
+        ne = C.c_int(0)
+        self._L.pc_hip_beam_info(self._h, C.byref(ne))
+        self.n_energies = int(ne.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pc_hip_beam_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, kind="exit"):
+        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
+        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        st = self._L.pc_hip_beam_add(self._h, k)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_beam_add", st)
+
+    def reset(self):
+        st = self._L.pc_hip_beam_reset(self._h)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_beam_reset", st)
+
+    def read(self):
+        """sums uint64 [3, n_energies, 15, 2] of (lo, hi) pairs (kinds exit, extleak, intleak; sums in the order of BEAM_SUMS),
+        outside uint64 [3, n_energies] and n_entries [3]"""
+        ne = self.n_energies
+        sums = np.zeros((3, ne, 15, 2), dtype=np.uint64)
+        out = np.zeros((3, ne), dtype=np.uint64)
+        n = (C.c_int64 * 3)()
+        st = self._L.pc_hip_beam_read(self._h, sums.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_beam_read", st)
+        return dict(sums=sums, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64))
+
+    def params(self, distances=None, kind="exit"):
+        """beam_params of the sums of `kind` read now"""
+        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        return beam_params(self.read()["sums"][k], distances)
+
+
 def scan_points(x=(0.,), y=(0.,), d_source=None):
     """Points of a scan, [len(d) * len(y) * len(x), 3] rows of (d_source, src_shiftx, src_shifty) in cm: the grid of the axes with
     x varying fastest, then y, then d_source (row = (id * len(y) + iy) * len(x) + ix).  d_source None = the problem's own (NaN

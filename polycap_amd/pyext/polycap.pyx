@@ -102,6 +102,10 @@ cdef extern from "polycap.h" nogil:
     int pc_transmission_efficiencies_get_stderr(void *efficiencies, size_t *n_energies, double **stderr_, void *error)
     int pc_transmission_efficiencies_get_moments(void *efficiencies, int64_t *n_started, uint64_t **sumw_fixed, uint64_t **sumw2_fixed,
         void *error)
+    int pc_transmission_efficiencies_get_beam(void *efficiencies, int kind, size_t *n_energies, double **params, void *error)
+    int pc_transmission_efficiencies_get_beam_sums(void *efficiencies, int kind, size_t *n_energies, uint64_t **sums, uint64_t **outside,
+        int64_t *n_entries, void *error)
+    const char *pc_hip_beam_columns()
 
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
@@ -646,6 +650,36 @@ cdef class TransmissionEfficiencies:
         polycap_free(a)
         polycap_free(b)
         return dict(n_started=int(ns), sumw_fixed=A.reshape(ne, 2), sumw2_fixed=B.reshape(ne, 2))
+
+    def beam(self, kind="exit"):
+        """Extension of this build: the exit-beam moments of a run made with POLYCAP_BEAM=1 (pc_transmission_efficiencies_get_beam /
+        _get_beam_sums): dict of the 26 named columns of pc_hip_beam_params (arrays over the energies; cm, rad), the exact sums
+        uint64 [n_energies, 15, 2], outside [n_energies] and n_entries.  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        cdef polycap_error *error = NULL
+        cdef size_t n = 0
+        cdef double *p = NULL
+        cdef uint64_t *a = NULL
+        cdef uint64_t *b = NULL
+        cdef int64_t ni = 0
+        cdef size_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_beam(<void *>self._eff, k, &n, &p, <void *>&error)
+        _raise_if(error)
+        rows = _take_doubles(p, n * 26).reshape(n, 26)
+        pc_transmission_efficiencies_get_beam_sums(<void *>self._eff, k, &n, &a, &b, &ni, <void *>&error)
+        _raise_if(error)
+        S = np.empty(30 * n, dtype=np.uint64)
+        O = np.empty(n, dtype=np.uint64)
+        for i in range(30 * n):
+            S[i] = a[i]
+        for i in range(n):
+            O[i] = b[i]
+        polycap_free(a)
+        polycap_free(b)
+        names = pc_hip_beam_columns().decode().split(",")
+        out = {name: rows[:, j].copy() for j, name in enumerate(names)}
+        out.update(sums=S.reshape(n, 15, 2), outside=O, n_entries=int(ni))
+        return out
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
