@@ -121,6 +121,8 @@ POLYCAP_EXTERN void pc_hip_ctx_destroy(pc_hip_ctx *ctx);
  *                      the EXACT loop (range tests at every reflection), as if they held an untame reflection, so that sweep
  *                      passes mixing such photons with others are common; results stay correct (default 0 = off)
  *   "fetch_threads"    host threads of the staging fallback of the image fetch (0 = min(16, cores))
+ *   "relay_acc_lds"    relays into this context (pc_hip_relay_run): 1 (default) = the finish kernel gathers a workgroup's exact sums in
+ *                      LDS when they fit in 32 KB, 0 = it adds every wave's sums to the global pairs at once, as it does beyond
  *   leak runs: "leak_max_depth" (stack frames per lane = walls one photon may cross), "leak_stack_mb" (HBM for those
  *                      stacks), "leak_capacity" (leak record buffer, 0 = automatic; a run that outgrows it is repeated). */
 POLYCAP_EXTERN int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value);
@@ -389,6 +391,60 @@ POLYCAP_EXTERN int pc_hip_group_scan_run(pc_hip_group *group, uint64_t seed, int
 	int64_t n_points, int64_t n_per_point, uint32_t max_attempts);
 POLYCAP_EXTERN int pc_hip_group_scan_wait(pc_hip_group *group, float *kernel_ms);
 POLYCAP_EXTERN int pc_hip_group_scan_totals(pc_hip_group *group, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed);
+
+/* ---- relays: the exit beam of one optic through a second one (a focusing lens and a second lens that looks at its focus:
+ * confocal set-ups), without a per-photon copy to the host.  Context A holds the first optic and has just made a source run that
+ * kept images; context B holds the second optic: its own profile and glass constants, the same energy grid (its source fields are
+ * not used).  pc_hip_relay_run flies A's exit photons through free space to B's entrance plane, traces them through B with the
+ * explicit-photon kernel of pc_hip_launch_photons, and leaves on B what a source run leaves there.
+ *
+ * The contract (IEEE fp64, evaluated in the order written, no contraction).  Placement = {gap, off_x, off_y} in cm, all finite,
+ * gap >= 0: B's axis is parallel to A's and displaced by (off_x, off_y); gap is measured from A's exit plane (pc_exit_coords[2] of
+ * A's records) to B's z = 0.
+ *   entries    the entries of A's store in the order of their positions (slot order; the order of completion after a run with
+ *              "compact_images").  An entry whose slot failed is skipped and counted: it has pc_exit_coords[2] <= 0 (compact
+ *              store: every plane zero) or a first weight <= 0 (slot-ordered store: zero weights)
+ *              (only the first weight is read: when more entries are skipped than A's run counted failed slots -- a first energy
+ *              without valid constants, a first weight that underflowed to 0 -- the relay is refused, PC_HIP_ERR_INVALID)
+ *   inject     from A's record: position (x, y) = pc_exit_coords[0..1], direction (dx, dy) = pc_exit_dir, electric vector (ex, ey) =
+ *              pc_exit_elecv (the records hold two components of each, as the reference's images do):
+ *              dz = sqrt((1 - dx*dx) - dy*dy),  ez = -(ex*dx + ey*dy) / dz,  t = gap / dz
+ *              start in B's frame = ((x + dx*t) - off_x, (y + dy*t) - off_y, 0), direction (dx, dy, dz), electric vector (ex, ey, ez)
+ *   stage 2    pc_hip_launch_photons of B on these photons: rc in {1, 0, 2, -2, -1}, weights wB[e], state at the last interaction
+ *   finish     for every photon with rc 1 and every energy: w = wA[e] * wB[e], one fp64 product;
+ *              A += (uint64)(w * 2^62), and with B's option "weight_squares" B += (uint64)((w * w) * 2^62), truncated, into B's
+ *              128-bit totals exactly as a source run adds them (see "standard errors" above)
+ *   records    the photons with rc 1, in the order of the entries they came from, become B's image records: src_start_coords from
+ *              A's record; pc_start_coords, pc_start_dir, pc_start_elecv = the injected state (x, y components); pc_exit_coords (3),
+ *              pc_exit_dir and pc_exit_elecv (x, y) = the state stage 2 reports (at the last interaction, not flown to B's exit
+ *              plane -- spot maps and beam moments fly every entry to their planes themselves; a photon that met no wall in B keeps
+ *              the injected electric vector); pc_exit_nrefl = nA + nB; pc_exit_dtravel = (dA + t) + dB; weights w[e]
+ * After the call pc_hip_transmission_records / _images, pc_hip_spot_add (kind 0) and pc_hip_beam_add (kind 0) on B read these
+ * records (run size = the number of transmitted photons, which may be 0); pc_hip_transmission_totals on B gives the sums and
+ * counters {rc 1, every other photon that was not absorbed, rc 0, reflections of the rc-1 photons in both optics, 0, photons
+ * injected}, and pc_hip_transmission_moments the squares' sums.  All sums are integer sums over the set of photons: they depend
+ * neither on how A's run was launched or stored nor on the relay's launch shape.  Many-energy relays run the immediate weight
+ * sweep (the logging kernel serves source runs only).  The call returns when the relay is complete.
+ *
+ * Refused with PC_HIP_ERR_INVALID and a message, before anything is launched and with both contexts left as they were: a NULL or
+ * repeated context, contexts on different devices, energy grids that are not bit-equal, a negative or non-finite placement, and
+ * an A whose last call was not a source run that kept images (no run yet, keep_images 0, a leak_calc run, an explicit-photon
+ * launch, a scan, or a relay into A -- relays are not chained). */
+typedef struct { double gap, off_x, off_y; } pc_hip_relay_placement;
+/* host only: the placement alone */
+POLYCAP_EXTERN int pc_hip_relay_validate(const pc_hip_relay_placement *placement);
+POLYCAP_EXTERN int pc_hip_relay_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_relay_placement *placement);
+/* of the last relay into ctx_b: counters = {n_in (photons injected), exit (rc 1), absorbed (rc 0), glass (rc 2), outside (rc -2),
+ * error (rc -1), skipped (failed slots of A), n_started_A (counters[0] + [1] + [2] of A's run)}; sumw_fixed / sumw2_fixed
+ * [2*n_energies] (lo, hi) pairs (sumw2_fixed: the relay must have been made with option "weight_squares" on ctx_b); any may be
+ * NULL.  PC_HIP_ERR_INVALID when the last call into ctx_b was not a relay. */
+POLYCAP_EXTERN int pc_hip_relay_totals(pc_hip_ctx *ctx_b, int64_t counters[8], uint64_t *sumw_fixed, uint64_t *sumw2_fixed);
+/* host only: the efficiency of the train, per energy.  Every photon started into A is one trial of the Monte Carlo mean and one
+ * lost anywhere -- not entered, absorbed or failed in either optic -- adds 0: eff[e] = A[e] / (n_started_A 2^62) in long double
+ * (0 when n_started_A is 0).  A's open-area factor cancels as it does in pc_hip_efficiencies, and B's open area is in the geometry
+ * (rc 2), not a factor.  With sumw2_fixed and stderr_ (both or neither): pc_hip_efficiency_stderr with N = n_started_A. */
+POLYCAP_EXTERN void pc_hip_relay_efficiencies(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed,
+	const int64_t counters[8], double *efficiencies, double *stderr_);
 
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);

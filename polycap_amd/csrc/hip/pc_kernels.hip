@@ -1176,6 +1176,9 @@ struct pc_event_handle {
 	hipError_t ensure(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
 };
 
+/* what a context was last asked to do (pc_hip_ctx::last_call) */
+enum { PC_CALL_NONE = 0, PC_CALL_RUN, PC_CALL_RUN_LEAK, PC_CALL_EXPLICIT, PC_CALL_SCAN, PC_CALL_RELAY };
+
 struct pc_hip_ctx {
 	pc_stream_handle main_stream;          /* first: destroyed after everything that may still be queued on it */
 	int device = 0;
@@ -1342,6 +1345,14 @@ struct pc_hip_ctx {
 	int scan_squares = 0;                  /* the last scan summed the squared weights */
 	int scan_pending = 0;                  /* the last scan has not been waited for */
 	float scan_ms = 0.f;
+	/* relays (pc_relay.h): what a context did last decides whether its exit photons can be relayed, and the context a relay was
+	 * traced into keeps the relay's counters beside what a source run leaves */
+	int last_call = PC_CALL_NONE;
+	std::vector<double> energies;          /* the problem's energy grid as given: two contexts relay only over bit-equal grids */
+	pc_dev_buf<long long> d_relay_map;     /* position in the first optic's store of every injected photon */
+	pc_dev_buf<unsigned long long> d_relay_scan; /* per-wave counts and offsets of the two compactions, then the relay's device counters */
+	int relay_acc_lds = 1;                 /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
+	int64_t relay_counters[8] = {0};
 };
 
 static int pc_cus(const pc_hip_ctx *ctx)
@@ -1690,6 +1701,7 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 	std::string err;
 	int rc = pc_build_tables(problem, ctx->host, err);
 	if (rc) { delete ctx; return pc_fail(rc, "pc_hip_ctx_create: " + err); }
+	ctx->energies.assign(problem->energies, problem->energies + problem->n_energies);
 	const size_t npts = (size_t)ctx->host.pm.nmax + 1;
 	if (npts > PC_MAX_PITCH) { delete ctx; return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_ctx_create: profile too long for the LDS tables (nmax <= 2047)"); }
 #define PC_CTX_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(_e); pc_hip_ctx_destroy(ctx); return pc_fail(PC_HIP_ERR_RUNTIME, m); } } while (0)
@@ -1769,6 +1781,7 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "keep_pinned") ctx->keep_pinned = value ? 1 : 0;
 	else if (n == "block_shift") { if (value < 7 || value > 30) return pc_fail(PC_HIP_ERR_INVALID, "block_shift must be in [7,30]"); ctx->blk_shift = (int)value; }
 	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->run_parts = (int)value; }
+	else if (n == "relay_acc_lds") ctx->relay_acc_lds = value ? 1 : 0;
 	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->fetch_threads = (int)value; }
 	else if (n == "pool") ctx->pool = value ? 1 : 0;
 	else if (n == "wave_per_photon") {
@@ -1807,6 +1820,109 @@ static int pc_batch_buffers(pc_hip_ctx *ctx, size_t elems)
 	return st ? st : ctx->h_batch.grow(elems, "explicit-photon batch: host allocation failed", want);
 }
 
+/* An explicit-photon launch in three stages over one device buffer: 3 inputs [3N], rc [N ints padded], weights [N*ne], 3 outputs
+ * [3N], irefl [N], dtravel [N].  upload: the caller's inputs through the pinned host buffer, which mirrors the device buffer (one
+ * copy in); trace: the kernel over inputs that are on the device -- whoever put them there (pc_relay.h injects them with a
+ * kernel); download: everything behind the inputs (one copy out) into the caller's arrays. */
+struct pc_batch {
+	size_t N = 0, ne = 0, doubles = 0;
+	double *d_start = nullptr, *d_dir = nullptr, *d_ev = nullptr;
+	int *d_rc = nullptr;
+	double *d_w = nullptr, *d_ec = nullptr, *d_ed = nullptr, *d_ee = nullptr;
+	long long *d_ir = nullptr;
+	double *d_dt = nullptr;
+};
+
+/* the buffer(s) for n photons and where everything lies in them; host = false: the device buffer alone */
+static int pc_batch_layout(pc_hip_ctx *ctx, int64_t n, bool host, pc_batch &b)
+{
+	const size_t ne = (size_t)ctx->host.pm.n_energies;
+	const size_t N = (size_t)n;
+	b.N = N; b.ne = ne;
+	b.doubles = 9*N + N + N*ne + 9*N + N + N;
+	int st = host ? pc_batch_buffers(ctx, b.doubles)
+	              : ctx->d_batch.grow(b.doubles, "explicit-photon batch: device allocation failed", b.doubles < 4096 ? 4096 : b.doubles + b.doubles/4);
+	if (st) return st;
+	double *d = ctx->d_batch;
+	b.d_start = d; b.d_dir = d + 3*N; b.d_ev = d + 6*N;
+	b.d_rc = (int *)(d + 9*N);
+	b.d_w = d + 10*N; b.d_ec = b.d_w + N*ne; b.d_ed = b.d_ec + 3*N; b.d_ee = b.d_ed + 3*N;
+	b.d_ir = (long long *)(b.d_ee + 3*N);
+	b.d_dt = (double *)(b.d_ir + N);
+	return PC_HIP_OK;
+}
+
+#define PC_LP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pc_fail(PC_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
+
+static int pc_batch_upload(pc_hip_ctx *ctx, const pc_batch &b, const double *start_coords, const double *start_dir, const double *start_elecv)
+{
+	const size_t N = b.N;
+	double *h = ctx->h_batch;
+	memcpy(h, start_coords, 3*N*sizeof(double));
+	memcpy(h + 3*N, start_dir, 3*N*sizeof(double));
+	memcpy(h + 6*N, start_elecv, 3*N*sizeof(double));
+	PC_LP_CHECK(hipMemcpyAsync(ctx->d_batch, h, 9*N*sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	return PC_HIP_OK;
+}
+
+/* clears the totals and traces the N photons whose inputs are in the device buffer; a leak launch has been waited for when it returns */
+static int pc_batch_trace(pc_hip_ctx *ctx, const pc_batch &b, int leak)
+{
+	const int64_t n = (int64_t)b.N;
+	PC_LP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
+	ctx->run_squares = 0;          /* explicit launches keep no sums */
+	pc_kargs a;
+	pc_fill_common(ctx, a);
+	a.n_slots = n; a.slot0 = 0; a.max_attempts = 1; a.keep_images = 0;
+	a.sumw2 = nullptr;
+	a.in_start = b.d_start; a.in_dir = b.d_dir; a.in_elecv = b.d_ev;
+	a.out_rc = b.d_rc; a.out_weights = b.d_w; a.out_exit_coords = b.d_ec; a.out_exit_dir = b.d_ed; a.out_exit_elecv = b.d_ee;
+	a.out_irefl = b.d_ir; a.out_dtravel = b.d_dt;
+	if (!leak) return pc_launch_kernel<PC_MODE_EXPLICIT>(ctx, a, n);
+	/* polycap_photon_launch(..., leak_calc=true): rerun with a larger record buffer until every event fits */
+	long long capacity = ctx->leak_capacity > 0 ? ctx->leak_capacity : std::max<long long>(4096, (16 + 8*(long long)b.ne)*n);
+	ctx->leak_slot0 = 0;
+	for (;;) {
+		ctx->leak_capacity_used = capacity;
+		ctx->leak_ev0_done = 0;
+		int status = pc_leak_enqueue<PC_MODE_EXPLICIT>(ctx, a, n, capacity);
+		if (status) return status;
+		PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
+		long long needed = 0;
+		status = pc_leak_collect(ctx, n, true, &needed);
+		if (status == 1) { capacity = needed + needed/4 + 1024; continue; }
+		return status;
+	}
+}
+
+static int pc_batch_download(pc_hip_ctx *ctx, const pc_batch &b, const double *start_elecv, int32_t *rc, double *weights, double *exit_coords,
+                             double *exit_dir, double *exit_elecv, int64_t *i_refl, double *d_travel, int leak)
+{
+	const size_t N = b.N, ne = b.ne;
+	double *d = ctx->d_batch, *h = ctx->h_batch;
+	PC_LP_CHECK(hipMemcpyAsync(h + 9*N, d + 9*N, (b.doubles - 9*N)*sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
+	{
+		const double *o = h + 9*N;        /* rc (ints, padded to N doubles), weights, exit coords / dir / elecv, irefl, dtravel */
+		memcpy(rc, o, N*sizeof(int)); o += N;
+		memcpy(weights, o, N*ne*sizeof(double)); o += N*ne;
+		memcpy(exit_coords, o, 3*N*sizeof(double)); o += 3*N;
+		memcpy(exit_dir, o, 3*N*sizeof(double)); o += 3*N;
+		memcpy(exit_elecv, o, 3*N*sizeof(double)); o += 3*N;
+		memcpy(i_refl, o, N*sizeof(long long)); o += N;
+		memcpy(d_travel, o, N*sizeof(double));
+	}
+	/* The kernels work with the normalised electric vector (polycap_refl_polar normalises it in place at the first
+	 * reflection, src/polycap-capil.c:492-494); a photon that never reached a reflection keeps the caller's vector */
+	for (size_t j = 0; j < N; j++) {
+		const bool untouched = (rc[j] == -2) || (!leak && (rc[j] == 2 || (rc[j] == 1 && i_refl[j] == 0)));
+		if (untouched)
+			for (int c = 0; c < 3; c++) exit_elecv[3*j + c] = start_elecv[3*j + c];
+	}
+	return PC_HIP_OK;
+}
+#undef PC_LP_CHECK
+
 static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *start_coords, const double *start_dir, const double *start_elecv,
                                   int32_t *rc, double *weights, double *exit_coords, double *exit_dir, double *exit_elecv,
                                   int64_t *i_refl, double *d_travel, int leak)
@@ -1815,79 +1931,13 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_launch_photons: NULL argument");
 	if (n == 0) return PC_HIP_OK;
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	const size_t N = (size_t)n;
-	/* one device buffer: 3 inputs [3N], rc [N ints padded], weights [N*ne], 3 outputs [3N], irefl [N], dtravel [N]; the pinned
-	 * host buffer mirrors it: one copy in (the inputs), one copy out (everything behind them) */
-	const size_t doubles = 9*N + N + N*ne + 9*N + N + N;
-	{
-		int st = pc_batch_buffers(ctx, doubles);
-		if (st) return st;
-	}
-	double *d = ctx->d_batch, *h = ctx->h_batch;
-	double *d_start = d, *d_dir = d + 3*N, *d_ev = d + 6*N;
-	int *d_rc = (int *)(d + 9*N);
-	double *d_w = d + 10*N, *d_ec = d_w + N*ne, *d_ed = d_ec + 3*N, *d_ee = d_ed + 3*N;
-	long long *d_ir = (long long *)(d_ee + 3*N);
-	double *d_dt = (double *)(d_ir + N);
-	int status = PC_HIP_OK;
-#define PC_LP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { status = pc_fail(PC_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e)); goto done; } } while (0)
-	{
-		memcpy(h, start_coords, 3*N*sizeof(double));
-		memcpy(h + 3*N, start_dir, 3*N*sizeof(double));
-		memcpy(h + 6*N, start_elecv, 3*N*sizeof(double));
-		PC_LP_CHECK(hipMemcpyAsync(d, h, 9*N*sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-		PC_LP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
-		ctx->run_squares = 0;          /* explicit launches keep no sums */
-		pc_kargs a;
-		pc_fill_common(ctx, a);
-		a.n_slots = n; a.slot0 = 0; a.max_attempts = 1; a.keep_images = 0;
-		a.sumw2 = nullptr;
-		a.in_start = d_start; a.in_dir = d_dir; a.in_elecv = d_ev;
-		a.out_rc = d_rc; a.out_weights = d_w; a.out_exit_coords = d_ec; a.out_exit_dir = d_ed; a.out_exit_elecv = d_ee;
-		a.out_irefl = d_ir; a.out_dtravel = d_dt;
-		if (leak) {
-			/* polycap_photon_launch(..., leak_calc=true): rerun with a larger record buffer until every event fits */
-			long long capacity = ctx->leak_capacity > 0 ? ctx->leak_capacity : std::max<long long>(4096, (16 + 8*(long long)ne)*n);
-			ctx->leak_slot0 = 0;
-			for (;;) {
-				ctx->leak_capacity_used = capacity;
-				ctx->leak_ev0_done = 0;
-				status = pc_leak_enqueue<PC_MODE_EXPLICIT>(ctx, a, n, capacity);
-				if (status) goto done;
-				PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
-				long long needed = 0;
-				status = pc_leak_collect(ctx, n, true, &needed);
-				if (status == 1) { capacity = needed + needed/4 + 1024; status = PC_HIP_OK; continue; }
-				if (status) goto done;
-				break;
-			}
-		} else {
-			status = pc_launch_kernel<PC_MODE_EXPLICIT>(ctx, a, n);
-			if (status) goto done;
-		}
-		PC_LP_CHECK(hipMemcpyAsync(h + 9*N, d + 9*N, (doubles - 9*N)*sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
-		{
-			const double *o = h + 9*N;        /* rc (ints, padded to N doubles), weights, exit coords / dir / elecv, irefl, dtravel */
-			memcpy(rc, o, N*sizeof(int)); o += N;
-			memcpy(weights, o, N*ne*sizeof(double)); o += N*ne;
-			memcpy(exit_coords, o, 3*N*sizeof(double)); o += 3*N;
-			memcpy(exit_dir, o, 3*N*sizeof(double)); o += 3*N;
-			memcpy(exit_elecv, o, 3*N*sizeof(double)); o += 3*N;
-			memcpy(i_refl, o, N*sizeof(long long)); o += N;
-			memcpy(d_travel, o, N*sizeof(double));
-		}
-		/* The kernels work with the normalised electric vector (polycap_refl_polar normalises it in place at the first
-		 * reflection, src/polycap-capil.c:492-494); a photon that never reached a reflection keeps the caller's vector */
-		for (size_t j = 0; j < N; j++) {
-			const bool untouched = (rc[j] == -2) || (!leak && (rc[j] == 2 || (rc[j] == 1 && i_refl[j] == 0)));
-			if (untouched)
-				for (int c = 0; c < 3; c++) exit_elecv[3*j + c] = start_elecv[3*j + c];
-		}
-	}
-done:
-#undef PC_LP_CHECK
+	pc_batch b;
+	int status = pc_batch_layout(ctx, n, true, b);
+	if (status) return status;
+	ctx->last_call = PC_CALL_EXPLICIT;
+	status = pc_batch_upload(ctx, b, start_coords, start_dir, start_elecv);
+	if (!status) status = pc_batch_trace(ctx, b, leak);
+	if (!status) status = pc_batch_download(ctx, b, start_elecv, rc, weights, exit_coords, exit_dir, exit_elecv, i_refl, d_travel, leak);
 	ctx->img_valid = 0;
 	ctx->leak_events_of_run = 0;
 	return status;
@@ -2044,6 +2094,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	ctx->last_run_plain = 1;
 	ctx->leak_events_of_run = 0;
 	ctx->run_squares = ctx->weight_squares;
+	ctx->last_call = PC_CALL_RUN;
 	pc_kargs a;
 	pc_fill_common(ctx, a);
 	ctx->img_valid = 0;
@@ -2157,6 +2208,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	ctx->img_valid = 0;
+	ctx->last_call = PC_CALL_RUN_LEAK;
 	if (keep_images) {
 		int st = ctx->d_img.grow(((size_t)PC_N_PLANES + ne) * (size_t)n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
 		if (st) return st;
@@ -2759,6 +2811,7 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 #include "pc_spot.h"
 #include "pc_beam.h"
 #include "pc_scan.h"
+#include "pc_relay.h"
 
 /* Heaviest slots first.  A leak launch ends with its longest slot: 20 000 units of work on one lane, which advances several
  * times faster alone in its wave than among 63 others (a wave runs one class of work at a time).  Which slots are long is known

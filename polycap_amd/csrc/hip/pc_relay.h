@@ -1,0 +1,418 @@
+/*
+ * pc_relay.h -- relays: the exit photons that the last source run of one context left on the device are flown through free space
+ * to the entrance plane of a second optic (another context on the same device), traced through it with their weights carried on,
+ * and left on the second context as a source run leaves its own: exact weight sums, counters and image records
+ * (include/polycap-hip.h, pc_hip_relay_*).  Nothing per-photon crosses PCIe: an inject kernel writes the second context's
+ * explicit-launch inputs from the first one's store, the explicit-photon trace kernel runs over them as it does for
+ * pc_hip_launch_photons, and a finish kernel multiplies the weights, adds the exact sums and compacts the transmitted photons, in
+ * the order of their positions in the first store, into the second context's image records.
+ *
+ * The first part (the per-photon arithmetic) compiles for the host as well: -DPC_RELAY_HOST_ONLY stops the header after it.
+ */
+#ifndef PC_RELAY_H
+#define PC_RELAY_H
+
+#include <math.h>
+#include <stdint.h>
+
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
+
+/* An entry of the first store is an exit photon unless its slot failed: a failed slot has zero weights (slot-ordered store) or
+ * every plane zero (compact store), and the exit plane of an optic lies at z > 0. */
+static inline __host__ __device__ int pc_relay_entry_valid(double exit_z, double w0)
+{
+	return (exit_z > 0. && w0 > 0.) ? 1 : 0;
+}
+
+/* From an exit record's position (x, y), direction (dx, dy) and electric vector (ex, ey) to the start of the photon in the second
+ * optic's frame: out = {x, y, z, dx, dy, dz, ex, ey, ez, t}.  The contract of include/polycap-hip.h, operation by operation (the
+ * library is built with -ffp-contract=off). */
+static inline __host__ __device__ void pc_relay_fly(double x, double y, double dx, double dy, double ex, double ey,
+	double gap, double off_x, double off_y, double *out)
+{
+	const double dz = sqrt((1. - dx*dx) - dy*dy);
+	const double ez = -(ex*dx + ey*dy) / dz;
+	const double t = gap / dz;
+	out[0] = (x + dx*t) - off_x;
+	out[1] = (y + dy*t) - off_y;
+	out[2] = 0.;
+	out[3] = dx; out[4] = dy; out[5] = dz;
+	out[6] = ex; out[7] = ey; out[8] = ez;
+	out[9] = t;
+}
+
+/* weight of a photon behind both optics: one fp64 product */
+static inline __host__ __device__ double pc_relay_weight(double w_a, double w_b)
+{
+	return w_a * w_b;
+}
+
+/* (uint64)(w * 2^62), truncated: what the weight adds to the exact sum */
+static inline __host__ __device__ unsigned long long pc_relay_fix(double w)
+{
+	return (unsigned long long)(w * 4611686018427387904.0);
+}
+
+/* path of a photon behind both optics: first optic, free flight, second optic, added in this order */
+static inline __host__ __device__ double pc_relay_dtravel(double d_a, double t, double d_b)
+{
+	return (d_a + t) + d_b;
+}
+
+/* the placement of the second optic: finite, gap >= 0 */
+static inline __host__ __device__ int pc_relay_placement_ok(double gap, double off_x, double off_y)
+{
+	return (gap >= 0. && gap <= 1.7976931348623157e308 && fabs(off_x) <= 1.7976931348623157e308 && fabs(off_y) <= 1.7976931348623157e308) ? 1 : 0;
+}
+
+/* efficiency of the train of optics from the exact sum (lo, hi) and the photons started into the first optic: sum / (N 2^62) in
+ * long double, 0 when nothing was started */
+static inline double pc_relay_efficiency(uint64_t lo, uint64_t hi, int64_t n_started)
+{
+	if (n_started <= 0) return 0.;
+	const long double a = (long double)hi * 18446744073709551616.0L + (long double)lo;
+	return (double)(a / ((long double)n_started * 4611686018427387904.0L));
+}
+
+#ifndef PC_RELAY_HOST_ONLY
+
+struct pc_relay_place { double gap, off_x, off_y; };
+
+static __device__ __forceinline__ int pc_relay_src_valid(const pc_spot_src &s, long long i)
+{
+	return pc_relay_entry_valid(s.p[i*s.ss + (long long)PC_F_EXITZ*s.fs], s.w[i*s.ws]);
+}
+
+/* Stable compaction, step 1: how many of the 64 items of every wave are kept.  rc == NULL: item i is entry i of the first store,
+ * kept when it is an exit photon; else item i is photon i of the second stage, kept when it was transmitted (rc 1).
+ * One thread per item; counts[i / 64] for every wave that holds an item. */
+__global__ void __launch_bounds__(256) pc_relay_count_kernel(pc_spot_src s, const int *rc, long long n, unsigned long long *counts)
+{
+	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+	const int keep = (i < n) ? (rc ? (rc[i] == 1) : pc_relay_src_valid(s, i)) : 0;
+	const unsigned long long m = __ballot(keep);
+	if ((threadIdx.x & 63) == 0 && i < n) counts[i >> 6] = (unsigned long long)__popcll(m);
+}
+
+/* Step 2, one workgroup: counts[0 .. nw) -> their exclusive prefix sums in place, counts[nw] = the total */
+__global__ void __launch_bounds__(1024) pc_relay_scan_kernel(unsigned long long *counts, long long nw)
+{
+	__shared__ unsigned long long wsum[16];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	unsigned long long carry = 0ull;
+	for (long long base = 0; base < nw; base += 1024) {
+		const long long k = base + tid;
+		const unsigned long long v = (k < nw) ? counts[k] : 0ull;
+		unsigned long long x = v;
+#pragma unroll
+		for (int off = 1; off < 64; off <<= 1) {
+			const unsigned long long y = __shfl_up(x, off, 64);
+			if (lane >= off) x += y;
+		}
+		if (lane == 63) wsum[wave] = x;
+		__syncthreads();
+		unsigned long long before = 0ull, all = 0ull;
+		for (int j = 0; j < 16; j++) {
+			const unsigned long long t = wsum[j];
+			if (j < wave) before += t;
+			all += t;
+		}
+		if (k < nw) counts[k] = carry + before + (x - v);
+		carry += all;
+		__syncthreads();
+	}
+	if (tid == 0) counts[nw] = carry;
+}
+
+/* Inject: every exit photon of the first store becomes one explicit photon of the second context, at the position the prefix
+ * sums give it (the order of the store); map[position] = its entry.  Reads are coalesced when the store is planes and strided by
+ * the record when it is records. */
+__global__ void __launch_bounds__(256) pc_relay_inject_kernel(pc_spot_src s, pc_relay_place pl, const unsigned long long *offs, long long n,
+	double *in_start, double *in_dir, double *in_elecv, long long *map)
+{
+	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+	const int keep = (i < n) ? pc_relay_src_valid(s, i) : 0;
+	const unsigned long long m = __ballot(keep);
+	if (!keep) return;
+	const int lane = threadIdx.x & 63;
+	const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
+	const double *e = s.p + i*s.ss;
+	double o[10];
+	pc_relay_fly(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
+	             e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, o);
+	in_start[3*pos] = o[0]; in_start[3*pos + 1] = o[1]; in_start[3*pos + 2] = o[2];
+	in_dir[3*pos] = o[3]; in_dir[3*pos + 1] = o[4]; in_dir[3*pos + 2] = o[5];
+	in_elecv[3*pos] = o[6]; in_elecv[3*pos + 1] = o[7]; in_elecv[3*pos + 2] = o[8];
+	map[pos] = i;
+}
+
+struct pc_relay_stage2 {          /* what the explicit-photon trace left in the batch buffer */
+	const int *rc;
+	const double *w, *exit_coords, *exit_dir, *exit_elecv, *dtravel;
+	const long long *irefl;
+};
+
+/* Finish: counters of the second stage's outcomes; for every transmitted photon the product weights, their exact sums (and the
+ * squares' when sumw2 is given) and its image record at the position the prefix sums give it.  A wave takes 64 consecutive
+ * photons at a time; the sums of a workgroup are gathered in LDS (acc_lds) when they fit, else go to the global pairs at once.
+ * Integer sums only: the totals depend on the set of photons, not on the launch shape. */
+__global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_relay_place pl, pc_relay_stage2 b, const long long *map,
+	const unsigned long long *offs, long long n_in, int ne, int acc_lds, double *rec_out, pc_totals *totals, unsigned long long *sumw,
+	unsigned long long *sumw2, unsigned long long *relay_cnt)
+{
+	extern __shared__ unsigned long long l_acc[];
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int words = sumw2 ? 4 : 2;
+	if (acc_lds) {
+		for (int k = tid; k < words*ne; k += blockDim.x) l_acc[k] = 0ull;
+		__syncthreads();
+	}
+	unsigned long long *acc = acc_lds ? l_acc : sumw, *acc2 = acc_lds ? l_acc + 2*ne : sumw2;
+	const long long recd = PC_N_FIELDS + ne;
+	unsigned long long c_in = 0, c_exit = 0, c_abs = 0, c_glass = 0, c_out = 0, c_err = 0, c_irefl = 0;
+	for (long long i0 = (long long)blockIdx.x*blockDim.x + (tid - lane); i0 < n_in; i0 += (long long)gridDim.x*blockDim.x) {
+		const long long i = i0 + lane;
+		const bool act = i < n_in;
+		const int rc = act ? b.rc[i] : -99;
+		const bool ok = rc == 1;
+		const unsigned long long m = __ballot(ok);
+		c_in += (unsigned long long)__popcll(__ballot(act));
+		c_exit += (unsigned long long)__popcll(m);
+		c_abs += (unsigned long long)__popcll(__ballot(rc == 0));
+		c_glass += (unsigned long long)__popcll(__ballot(rc == 2));
+		c_out += (unsigned long long)__popcll(__ballot(rc == -2));
+		c_err += (unsigned long long)__popcll(__ballot(act && rc != 1 && rc != 0 && rc != 2 && rc != -2));
+		if (!m) continue;
+		long long ia = 0;
+		double *r = nullptr;
+		unsigned long long f_irefl = 0ull;
+		if (ok) {
+			ia = map[i];
+			const double *e = s.p + ia*s.ss;
+			/* the injected state again, from A's entry: the same operations give the same bits as the inject kernel wrote, and the
+			 * flight t, which the batch buffer does not hold, comes with them */
+			double o[10];
+			pc_relay_fly(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
+			             e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, o);
+			const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
+			r = rec_out + pos*recd;
+			const long long n_a = ((const long long *)e)[(long long)PC_F_NREFL*s.fs], n_b = b.irefl[i];
+			r[PC_F_SRCX] = e[(long long)PC_F_SRCX*s.fs]; r[PC_F_SRCY] = e[(long long)PC_F_SRCY*s.fs];
+			r[PC_F_STARTX] = o[0]; r[PC_F_STARTY] = o[1];
+			r[PC_F_SDIRX] = o[3]; r[PC_F_SDIRY] = o[4];
+			r[PC_F_SEVX] = o[6]; r[PC_F_SEVY] = o[7];
+			r[PC_F_EXITX] = b.exit_coords[3*i]; r[PC_F_EXITY] = b.exit_coords[3*i + 1]; r[PC_F_EXITZ] = b.exit_coords[3*i + 2];
+			r[PC_F_EDIRX] = b.exit_dir[3*i]; r[PC_F_EDIRY] = b.exit_dir[3*i + 1];
+			/* a photon that met no wall keeps the electric vector it was given (as pc_hip_launch_photons reports it) */
+			r[PC_F_EEVX] = n_b ? b.exit_elecv[3*i] : o[6]; r[PC_F_EEVY] = n_b ? b.exit_elecv[3*i + 1] : o[7];
+			((long long *)r)[PC_F_NREFL] = n_a + n_b;
+			r[PC_F_DTRAVEL] = pc_relay_dtravel(e[(long long)PC_F_DTRAVEL*s.fs], o[9], b.dtravel[i]);
+			f_irefl = (unsigned long long)(n_a + n_b);
+		}
+		c_irefl += pc_wave_sum_u64(f_irefl);
+		for (int en = 0; en < ne; en++) {
+			double w = 0.;
+			if (ok) {
+				w = pc_relay_weight(s.w[ia*s.ws + en], b.w[i*ne + en]);
+				r[PC_F_WEIGHTS + en] = w;
+			}
+			unsigned long long lo = 0ull, hi = 0ull;
+			pc_wave_acc128(ok ? pc_relay_fix(w) : 0ull, lo, hi);
+			if (lane == 0 && (lo | hi)) pc_atomic_add128(acc + 2*en, lo, hi);
+			if (sumw2) {
+				lo = hi = 0ull;
+				pc_wave_acc128(ok ? pc_fix_sq(w) : 0ull, lo, hi);
+				if (lane == 0 && (lo | hi)) pc_atomic_add128(acc2 + 2*en, lo, hi);
+			}
+		}
+	}
+	if (acc_lds) {
+		__syncthreads();
+		for (int en = tid; en < ne; en += blockDim.x) {
+			if (l_acc[2*en] | l_acc[2*en + 1]) pc_atomic_add128(sumw + 2*en, l_acc[2*en], l_acc[2*en + 1]);
+			if (sumw2 && (l_acc[2*ne + 2*en] | l_acc[2*ne + 2*en + 1])) pc_atomic_add128(sumw2 + 2*en, l_acc[2*ne + 2*en], l_acc[2*ne + 2*en + 1]);
+		}
+	}
+	if (lane == 0 && c_in) {
+		/* the second context's totals as a source run of the injected photons would count them: exit, not entered (everything
+		 * that neither left nor was absorbed), not transmitted, reflections of the exit photons (both optics), launches */
+		atomicAdd(&totals->counters[0], c_exit);
+		atomicAdd(&totals->counters[1], c_in - c_exit - c_abs);
+		atomicAdd(&totals->counters[2], c_abs);
+		atomicAdd(&totals->counters[3], c_irefl);
+		atomicAdd(&totals->counters[5], c_in);
+		atomicAdd(&relay_cnt[0], c_in); atomicAdd(&relay_cnt[1], c_exit); atomicAdd(&relay_cnt[2], c_abs);
+		atomicAdd(&relay_cnt[3], c_glass); atomicAdd(&relay_cnt[4], c_out); atomicAdd(&relay_cnt[5], c_err);
+	}
+}
+
+/* counts + prefix sums of n items on the context's stream (pc_relay_count_kernel, pc_relay_scan_kernel); *total = how many are
+ * kept (waits for the stream) */
+static int pc_relay_compact_offsets(pc_hip_ctx *b, const pc_spot_src &s, const int *rc, long long n, long long *total)
+{
+	const long long nw = (n + 63)/64;
+	hipLaunchKernelGGL(pc_relay_count_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, b->stream, s, rc, n, (unsigned long long *)b->d_relay_scan);
+	PC_HIP_CHECK(hipGetLastError());
+	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, (unsigned long long *)b->d_relay_scan, nw);
+	PC_HIP_CHECK(hipGetLastError());
+	unsigned long long t = 0;
+	PC_HIP_CHECK(hipMemcpyAsync(&t, b->d_relay_scan + nw, sizeof(t), hipMemcpyDeviceToHost, b->stream));
+	PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+	*total = (long long)t;
+	return PC_HIP_OK;
+}
+
+/* everything that can refuse a relay, before anything is launched */
+static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement *pl)
+{
+	if (!a || !b) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts must not be NULL");
+	if (a == b) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the second optic needs a context of its own");
+	int st = pc_hip_relay_validate(pl);
+	if (st) return st;
+	if (a->device != b->device)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
+	if (a->energies.size() != b->energies.size() || memcmp(a->energies.data(), b->energies.data(), a->energies.size()*sizeof(double)) != 0)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts need the same energy grid, bit for bit");
+	switch (a->last_call) {
+	case PC_CALL_RUN: break;
+	case PC_CALL_RUN_LEAK: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last run was a leak_calc run");
+	case PC_CALL_EXPLICIT: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last call was an explicit-photon launch, not a source run");
+	case PC_CALL_SCAN: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last call was a scan, not a source run");
+	case PC_CALL_RELAY: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context holds the result of a relay, not of a source run");
+	default: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context has made no source run");
+	}
+	if (!a->img_valid)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last run kept no exit photons (run it with keep_images)");
+	return PC_HIP_OK;
+}
+
+extern "C" {
+
+int pc_hip_relay_validate(const pc_hip_relay_placement *pl)
+{
+	if (!pl) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_validate: placement must not be NULL");
+	if (!pc_relay_placement_ok(pl->gap, pl->off_x, pl->off_y))
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_validate: gap must be finite and >= 0, off_x and off_y finite");
+	return PC_HIP_OK;
+}
+
+int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement *placement)
+{
+	int st = pc_relay_check(a, b, placement);
+	if (st) return st;
+	PC_HIP_CHECK(hipSetDevice(a->device));
+	/* the first run is complete, and nothing of the second context is in flight */
+	st = pc_hip_transmission_wait(a, nullptr);
+	if (!st) st = pc_hip_transmission_wait(b, nullptr);
+	if (st) return st;
+	int64_t cnt_a[6];
+	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
+	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
+	pc_spot_src s;
+	st = pc_spot_source(a, 0, s);
+	if (st) return st;
+	const long long n_a = s.n;
+	const int ne = b->host.pm.n_energies;
+	const pc_relay_place pl = { placement->gap, placement->off_x, placement->off_y };
+
+	/* from here on the second context holds the relay, or nothing */
+	b->img_valid = 0; b->leak_events_of_run = 0; b->last_run_plain = 0;
+	b->last_call = PC_CALL_NONE;
+	b->run_planes = 0; b->run_compact = 0; b->n_parts = 1; b->run_pending = 0; b->run_slots = 0;
+	b->run_squares = b->weight_squares;
+	b->last_ms = 0.f;
+	const size_t nw_a = (size_t)((n_a + 63)/64);
+	st = b->d_relay_scan.grow(nw_a + 1 + 8, "pc_hip_relay_run: could not allocate the compaction counters");
+	if (!st) st = b->d_relay_map.grow((size_t)n_a, "pc_hip_relay_run: could not allocate the photon map");
+	if (st) return st;
+
+	long long n_in = 0, n_out = 0;
+	st = pc_relay_compact_offsets(b, s, nullptr, n_a, &n_in);
+	if (st) return st;
+	/* The predicate reads the first weight only.  Every entry it skips must be a failed slot of A's run: a grid whose first
+	 * energy has no valid constants, or a first weight that underflowed to 0, would otherwise vanish without a word */
+	if (n_a - n_in != cnt_a[4])
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: " + std::to_string(n_a - n_in) + " entries of the first run have no exit plane or a zero first weight, but "
+		               + std::to_string(cnt_a[4]) + " of its slots failed: exit photons with a zero first weight cannot be relayed");
+	unsigned long long h_cnt[8] = {0};
+	if (n_in > 0) {
+		pc_batch bt;
+		st = pc_batch_layout(b, n_in, false, bt);
+		if (st) return st;
+		hipLaunchKernelGGL(pc_relay_inject_kernel, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
+		                   (const unsigned long long *)b->d_relay_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)b->d_relay_map);
+		PC_HIP_CHECK(hipGetLastError());
+		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
+		st = pc_batch_trace(b, bt, 0);
+		if (st) return st;
+		b->run_squares = b->weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
+		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
+		if (st) return st;
+		st = b->d_img.grow(((size_t)PC_N_FIELDS + (size_t)ne) * (size_t)std::max<long long>(n_out, 1), "pc_hip_relay_run: could not allocate the image records");
+		if (st) return st;
+		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
+		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
+		unsigned long long *sumw = (unsigned long long *)(b->d_totals + 1);
+		unsigned long long *sumw2 = b->weight_squares ? sumw + 2*(size_t)ne : nullptr;
+		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
+		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
+		long long grid = (n_in + 255)/256;
+		if (grid > 8ll*pc_cus(b)) grid = 8ll*pc_cus(b);
+		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
+		hipLaunchKernelGGL(pc_relay_finish_kernel, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
+		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->d_img,
+		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
+		PC_HIP_CHECK(hipGetLastError());
+		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+		float ms = 0.f;
+		PC_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+		b->last_ms = ms;
+	} else {
+		/* nothing to trace (pc_batch_trace clears the totals otherwise) */
+		PC_HIP_CHECK(hipMemsetAsync(b->d_totals, 0, b->totals_bytes, b->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+	}
+	for (int k = 0; k < 6; k++) b->relay_counters[k] = (int64_t)h_cnt[k];
+	b->relay_counters[6] = n_a - n_in;
+	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
+	b->run_slots = n_out;
+	b->img_valid = 1;
+	b->last_call = PC_CALL_RELAY;
+	return PC_HIP_OK;
+}
+
+int pc_hip_relay_totals(pc_hip_ctx *ctx, int64_t counters[8], uint64_t *sumw_fixed, uint64_t *sumw2_fixed)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_totals: ctx must not be NULL");
+	if (ctx->last_call != PC_CALL_RELAY) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_totals: the context's last call was not a relay into it");
+	if (sumw2_fixed && !ctx->run_squares)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_totals: the relay was made without option weight_squares");
+	PC_HIP_CHECK(hipSetDevice(ctx->device));
+	const size_t ne = (size_t)ctx->host.pm.n_energies;
+	const unsigned long long *sw = (const unsigned long long *)(ctx->d_totals + 1);
+	if (counters) memcpy(counters, ctx->relay_counters, sizeof(ctx->relay_counters));
+	if (sumw_fixed) PC_HIP_CHECK(hipMemcpy(sumw_fixed, sw, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (sumw2_fixed) PC_HIP_CHECK(hipMemcpy(sumw2_fixed, sw + 2*ne, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return PC_HIP_OK;
+}
+
+void pc_hip_relay_efficiencies(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed, const int64_t counters[8],
+                               double *efficiencies, double *stderr_)
+{
+	const int64_t n = counters[7];
+	for (size_t e = 0; e < n_energies; e++)
+		efficiencies[e] = pc_relay_efficiency(sumw_fixed[2*e], sumw_fixed[2*e + 1], n);
+	if (sumw2_fixed && stderr_) {
+		const int64_t c6[6] = { n, 0, 0, 0, 0, 0 };      /* N = every photon started into the first optic */
+		pc_hip_efficiency_stderr(n_energies, sumw_fixed, sumw2_fixed, c6, stderr_);
+	}
+}
+
+} /* extern "C" */
+
+#endif /* PC_RELAY_HOST_ONLY */
+#endif /* PC_RELAY_H */

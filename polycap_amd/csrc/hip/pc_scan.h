@@ -111,6 +111,7 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 		if (st) return st;
 	}
 	ctx->scan_points = 0;       /* until this scan is enqueued */
+	ctx->last_call = PC_CALL_SCAN;
 	/* behind every launch of the last run: a run cut into parts ends its main stream behind the parts on stream2 already
 	 * (pc_hip_transmission_run); this also orders the scan after anything else enqueued there */
 	if (ctx->stream2) {

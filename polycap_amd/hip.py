@@ -281,6 +281,52 @@ class TraceContext:
             raise HipError("pc_hip_leak_slot_units", st)
         return u
 
+    def relay(self, other, gap, offset=(0., 0.)):
+        """Relays the exit photons of this context's last source run (made with keep_images) through the optic of `other`, a
+        context on the same device with the same energy grid whose z = 0 lies `gap` cm behind this optic's exit plane, its axis
+        displaced by `offset` = (x, y) cm (pc_hip_relay_run; the contract is in include/polycap-hip.h).  Nothing per-photon
+        leaves the device.  Returns efficiencies of the train per energy, efficiency_stderr (option "weight_squares" on `other`,
+        else None), counters by name (RELAY_COUNTERS), sum_weights, sumw_fixed [ne, 2], sumw2_fixed or None, n_records and
+        kernel_ms of the second stage's trace.  Afterwards other.records() / images(), SpotMap(other, ...) and
+        BeamMoments(other) describe the beam behind the second optic."""
+        if not isinstance(other, TraceContext):
+            raise TypeError("relay: other must be a TraceContext")
+        pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
+        st = self._L.pc_hip_relay_run(self._h, other._h, dptr(pl))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_relay_run", st)
+        other._relay_squares = getattr(other, "_weight_squares", False)      # as the relay was made, whatever the option is set to later
+        r = other.relay_totals()
+        other._last_n = r["n_records"]
+        r["kernel_ms"] = other.wait()
+        return r
+
+    def relay_totals(self):
+        """Totals of the last relay into this context (pc_hip_relay_totals, pc_hip_relay_efficiencies): see relay()."""
+        ne = self.problem.n_energies
+        sq = getattr(self, "_relay_squares", False)
+        cnt = np.zeros(8, dtype=np.int64)
+        a = np.zeros(2 * ne, dtype=np.uint64)
+        b = np.zeros(2 * ne, dtype=np.uint64) if sq else None
+        u64p = C.POINTER(C.c_uint64)
+        st = self._L.pc_hip_relay_totals(self._h, cnt.ctypes.data_as(c_int64_p), a.ctypes.data_as(u64p), b.ctypes.data_as(u64p) if sq else None)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_relay_totals", st)
+        eff, err = relay_efficiencies(a, b, cnt)
+        return dict(efficiencies=eff, efficiency_stderr=err, counters=dict(zip(RELAY_COUNTERS, (int(v) for v in cnt))),
+                    counters_array=cnt, sum_weights=np.array([fixed_to_double(a[2 * e], a[2 * e + 1]) for e in range(ne)]),
+                    sumw_fixed=a.reshape(ne, 2), sumw2_fixed=None if b is None else b.reshape(ne, 2), n_records=int(cnt[1]))
+
+    def records(self, first=0, count=None):
+        """Image records [count, 17 + nE] of the last run or relay as the device keeps them (pc_hip_transmission_records): the
+        planes of IMG_FIELDS in their order, the reflection count as int64 bits in column 15, then the weights."""
+        count = self._last_n - first if count is None else count
+        rec = np.empty((count, 17 + self.problem.n_energies))
+        st = self._L.pc_hip_transmission_records(self._h, int(first), int(count), dptr(rec))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_transmission_records", st)
+        return rec
+
     def transmission(self, seed, slot0, n_slots, max_attempts=1 << 20, keep_images=False, leak_calc=False, leak_views=False):
         """run + wait + totals (+ images, + leak events: copies, or with leak_views views of the context's lists) in one call."""
         self.run(seed, slot0, n_slots, max_attempts, keep_images, leak_calc)
@@ -389,6 +435,32 @@ class TraceGroup:
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_group_moments", st)
         return fx.reshape(ne, 2)
+
+
+RELAY_COUNTERS = ("n_in", "exit", "absorbed", "glass", "outside", "error", "skipped", "n_started_a")
+
+
+def relay_placement_valid(gap, offset=(0., 0.)):
+    """True when pc_hip_relay_validate accepts the placement (host only)."""
+    pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
+    return _cabi.lib().pc_hip_relay_validate(dptr(pl)) == _cabi.PC_HIP_OK
+
+
+def relay_efficiencies(sumw_fixed, sumw2_fixed, counters):
+    """(efficiencies, standard errors or None) of a train of two optics from a relay's exact totals (pc_hip_relay_efficiencies,
+    host only): sumw_fixed / sumw2_fixed [n_energies, 2] or flat (lo, hi) pairs, counters the relay's eight."""
+    a = np.ascontiguousarray(sumw_fixed, dtype=np.uint64).reshape(-1)
+    b = None if sumw2_fixed is None else np.ascontiguousarray(sumw2_fixed, dtype=np.uint64).reshape(-1)
+    cnt = np.ascontiguousarray(counters, dtype=np.int64)
+    if cnt.shape[0] != 8 or a.shape[0] % 2 or (b is not None and b.shape != a.shape):
+        raise ValueError("relay_efficiencies: eight counters and n_energies (lo, hi) pairs per sum are needed")
+    ne = a.shape[0] // 2
+    eff = np.zeros(ne)
+    err = None if b is None else np.zeros(ne)
+    u64p = C.POINTER(C.c_uint64)
+    _cabi.lib().pc_hip_relay_efficiencies(ne, a.ctypes.data_as(u64p), None if b is None else b.ctypes.data_as(u64p),
+                                          cnt.ctypes.data_as(c_int64_p), dptr(eff), None if err is None else dptr(err))
+    return eff, err
 
 
 SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}

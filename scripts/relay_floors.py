@@ -1,0 +1,52 @@
+"""The CPU oracle's own self-noise on the second optic of the relay tests (tests/test_gpu_relay.py): no GPU involved.
+
+    python scripts/relay_floors.py
+
+For each configuration of the tests: the oracle traces optic A (seed 20000, slots 0..19999, images kept), the exit records are flown
+to B's entrance by the numpy restatement of the relay contract (gap 1 cm, aligned), and the oracle's launch_batch on B is compared
+with itself after one start coordinate has been moved by 1 ulp -- x up, x down, y up, y down.  Printed per configuration: the share
+of photons whose return code or reflection count flips, and |delta| / sum * sqrt(n) of the transmitted product weight (largest over
+the energies), for each of the four and their maxima, which are the floors the tests use."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+SHAPE_B = (2, 9., 0.0585, 0.2065, 9.9153e-5, 0.00035, 0.5, 1000.)          # tests/common.py:TEST_SHAPE reversed
+SRC = (2000., 0.2065, 0.2065, 0., 0., 0., 0., 0.5)
+CONFIGS = {"pinned": ((10.0,), 0.), "ne12": (tuple(np.linspace(5., 27., 12)), 0.), "rough": ((10.0,), 5.)}
+
+
+def floors(oracle, name, seed=20000, n=20000, gap=1.0):
+    """(flip shares [4], weight c [4], rc-1 count) of configuration `name`"""
+    from tests.common import make_custom, make_pair
+    from tests.test_relay_cpu import np_fly
+    en, rough = CONFIGS[name]
+    optic_a, src, _, (E, A, S) = make_pair(oracle, "ellip", energies=en)
+    optic_b, _, _, _ = make_custom(oracle, SHAPE_B, 200000, SRC, energies=en, sig_rough=rough)
+    o = oracle.transmission(optic_a, src, E, A, S, seed, 0, n, images=True)
+    im, wa = o["images"], o["exit_weights"]
+    f = np_fly(im[:, 8], im[:, 9], im[:, 11], im[:, 12], im[:, 13], im[:, 14], gap, 0., 0.)
+    a = oracle.launch_batch(optic_b, E, A, S, f[:, 0:3], f[:, 3:6], f[:, 6:9])
+    ent = np.isin(a["rc"], (2, -2))
+    sa = (wa * a["weights"])[a["rc"] == 1].sum(axis=0)
+    flips, cs = [], []
+    for col in (0, 1):
+        for to in (1.0, -1.0):
+            st = f[:, 0:3].copy()
+            st[:, col] = np.nextafter(st[:, col], to)
+            b = oracle.launch_batch(optic_b, E, A, S, st, f[:, 3:6], f[:, 6:9])
+            assert np.array_equal(ent, np.isin(b["rc"], (2, -2))) and np.array_equal(a["rc"][ent], b["rc"][ent])   # entrance decisions hold
+            flips.append(float(((a["rc"] != b["rc"]) | (a["i_refl"] != b["i_refl"])).mean()))
+            sb = (wa * b["weights"])[b["rc"] == 1].sum(axis=0)
+            cs.append(float((np.abs(sa - sb) / sa * np.sqrt(n)).max()))
+    return flips, cs, int((a["rc"] == 1).sum())
+
+
+if __name__ == "__main__":
+    from oracle import pyoracle
+    pyoracle.build()
+    for name in CONFIGS:
+        fl, cs, n1 = floors(pyoracle, name)
+        print("%-7s rc 1 %5d  flips %s  max %.5f   c %s  max %.4f" % (name, n1, ["%.5f" % v for v in fl], max(fl), ["%.4f" % v for v in cs], max(cs)))
