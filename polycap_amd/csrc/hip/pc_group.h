@@ -160,7 +160,7 @@ static int pc_group_run_impl(pc_hip_group *g, uint64_t seed, int64_t n_slots, ui
 	 * context probes by itself (1e7 slots over 8 devices), and eight probes one after the other would serialise the enqueue. */
 	{
 		pc_hip_ctx *c0 = g->ctx[0];
-		if (!leak && c0->producer < 0 && c0->refl_per_launch < 0. && c0->host.pm.n_energies == 1 && n_slots >= 2000000) {
+		if (!leak && pc_wants_probe(c0, n_slots)) {
 			if (max_attempts < 1) max_attempts = 1;
 			int st = pc_probe_lifetime(c0, seed, 0, max_attempts);
 			if (st) return st;

@@ -33,12 +33,8 @@
 #include "pc_leak.h"
 #include "pc_problem.h"
 #include "pc_moments.h"
+#include "pc_plan.h"
 
-#ifndef PC_BLOCK
-#define PC_BLOCK 512            /* maximum workgroup size the trace kernel is compiled for */
-#endif
-#define PC_WAVE 64
-#define PC_MAX_PITCH 2048      /* largest profile kept in static LDS: (6 x 8 + 4 x 4) B x 2048 = 128 KB */
 #ifndef PC_MARCH_UNROLL
 #define PC_MARCH_UNROLL 4      /* march steps between two ballots of the burst loop.  With march_stop = 8 (a burst goes on while 8 lanes march):
                                 * 3: 23.6 ms, 4: 23.4, 5: 23.9, 8: 24.1 (scripts/ab_build.sh, xos1 10 keV, 1e7 slots) */
@@ -1180,13 +1176,10 @@ struct pc_event_handle {
 enum { PC_CALL_NONE = 0, PC_CALL_RUN, PC_CALL_RUN_LEAK, PC_CALL_EXPLICIT, PC_CALL_SCAN, PC_CALL_RELAY };
 
 struct pc_hip_ctx {
-	pc_stream_handle main_stream;          /* first: destroyed after everything that may still be queued on it */
+	pc_stream_handle stream;               /* first: destroyed after everything that may still be queued on it.  The context's one stream: a launch
+	                                        * that goes elsewhere says so in its pc_launch_site */
 	int device = 0;
 	int n_cu = 256;
-	int cu_share = 1;              /* option "cu_share": the context's launches fill n_cu / cu_share compute units.  Tried for device groups that list
-	                                * a device m times (m kernels side by side on a quarter of the CUs each): the kernels of one process's streams
-	                                * did not overlap (21.7 ms against 15.1 ms one after the other, xos1 5e6 slots, 4 members), so groups leave it at 1 */
-	hipStream_t stream = nullptr;          /* where the launch helpers enqueue: main_stream, or stream2 for the odd parts of a run */
 	pc_event_handle ev0, ev1;
 	pc_host_tables host;
 	pc_dev_buf<double> d_tables;           /* z, cap, zh, cap2, hexd, idz, ext: 7 x npts */
@@ -1194,50 +1187,11 @@ struct pc_hip_ctx {
 	pc_dev_buf<double> d_ec_soa;
 	pc_dev_buf<pc_marg4> d_mg;             /* block-certificate records, npts */
 	pc_dev_buf<pc_drdev> d_dr;             /* leak path: chord deviations of cap, npts */
-	/* options */
-	int literal = 0;
-	int event_threshold = 48;      /* lanes that must be marching for a MARCH burst to run before the waiting EVENTs.  With the short flights of
-	                                * the current march (5.5 steps) the wave works almost in lockstep: 20 -> 44..48 is 26.2 -> 23.3 ms on xos1
-	                                * (profiles/r02/kernel_history.md); optics with long flights (cone.inp) prefer ~24, ellip_l9 with roughness ~32 */
-	int new_threshold = 2;
-	int march_burst = 16;
-	int march_stop = 8;            /* a burst that has started goes on while this many lanes march (0: event_threshold): most flights end within it */
-	int blocks_per_cu = 2;
-	int block_size = 512;
-	int producer = -1;             /* single-energy source runs with a launching wave per workgroup (pc_producer_kernel.h): 1 always, 0 never,
-	                                * -1 when photons live long enough for one launching wave per CU to keep up (refl_per_launch, below):
-	                                * -5 % on xos1 and ellip_l9, but 2.3x slower on cone.inp, whose photons hardly reflect */
+	pc_launch_opts opts;                   /* the options that decide a launch (pc_plan.h) */
 	double refl_per_launch = -1.;  /* EVENT visits (reflections, mostly) per launch in the last source run of this context; < 0: not known.
 	                                * A big first run is preceded by a probe of 32768 slots (results unused) */
-	int in_probe = 0;
 	int last_kernel = -1;          /* pc_hip_last_kernel */
 	int last_run_plain = 0;        /* the last run was pc_hip_transmission_run (its counters tell refl_per_launch) */
-	int producer_new_min = 2, producer_new_first = 6;
-	int march_stats = 0;           /* option "march_stats": the launching-wave kernel counts march steps and their lanes (pc_hip_phase_stats); off in
-	                                * production runs, bench.py switches it on for one extra launch outside the timed steps */
-	int wave_per_photon = 0;       /* EXPERIMENT (pc_wave_kernel.h): 1 = single-energy histogram-only source runs with one wave per photon */
-	int pool = 0;                  /* 1: single-energy source runs on profiles of up to 1024 points use the per-wave photon pool in LDS (pc_pool_kernel.h).
-	                                * Was the default up to v14 (+6 %); since flights take 5.5 steps instead of 8.8 the exchanges with the pool cost more
-	                                * than its fuller phases save (26.3 ms against 23.3 ms for the one-photon-per-lane kernel) */
-	int pool_refill = 20;
-	int pool_march_min = 16;
-	int pool_event_min = 48;
-	int event_march = 0;
-	int pool_new_min = 48;
-	int lds_ec = 1;                /* many-energy runs: per-energy constants in LDS, one 1024-thread workgroup per CU */
-	int batch_reflections = 1;     /* more than 8 energies, source runs: 1 = reflections are logged and a photon's weights swept once per log
-	                                * (pc_sweep_kernel.h), 0 = every reflection sweeps the weights at once */
-	int log_cap = 0;               /* option "log_cap": reflections per log of pc_trace_log_kernel; 0 = 64 from 64 energies on, 32 below (shorter logs
-	                                * leave room in LDS for the logs of more photons per sweep, which few energies need to fill their passes) */
-	int sweep_skip = 1;            /* option "sweep_skip": histogram-only log runs stop multiplying a weight below 2^-64 */
-	int flush_max = 8;             /* option "flush_max": at most this many finished photons of a wave wait for a common sweep */
-	int log_min_energies = 9;      /* option "log_min_energies": source runs with at least this many energies log their reflections (9: every run whose
-	                                * weights are not in registers; measured 9 ... 100 energies: +2 ... +130 % against the immediate sweep) */
-	int sweep_fuse = 1;            /* option "sweep_fuse": histogram-only log runs add a finished photon's weights to the sums in its sweep; 2 = also when
-	                                * its proxies are dead, so that photons the sweep finds dead exercise the take-back pass (tests) */
-	int sweep_exact_every = 0;     /* option "sweep_exact_every" (test hook): > 0 = the logs of every photon whose slot is a multiple of it are swept by the
-	                                * EXACT loop, so that sweep passes that mix EXACT and FAST photons are common (0 = off) */
-	int weight_squares = 0;        /* option "weight_squares": source runs also sum the squared exit weights (pc_kargs::sumw2) */
 	int run_squares = 0;           /* the last run did so (pc_hip_transmission_moments) */
 	pc_dev_buf<double> d_rlog;
 	int sweep_cert = 0;            /* pc_sweep_certificate has run */
@@ -1261,7 +1215,6 @@ struct pc_hip_ctx {
 	int n_parts = 1;
 	long long part_end[PC_MAX_PARTS] = {0};
 	pc_event_handle ev_part[PC_MAX_PARTS];
-	bool rec_ev0 = true, rec_ev1 = true;
 	int fetch_threads = 0;                 /* host threads that scatter a fetched chunk into the caller's planes; 0 = min(16, cores) */
 	int img_valid = 0;
 	/* plane (SoA) copy of the image records on the device: 17 planes of the run's n_slots doubles, then the weights [slot][n_energies].
@@ -1273,7 +1226,7 @@ struct pc_hip_ctx {
 	 * plane and batch, and the planes are published block by block while the kernel runs (pc_kargs::img_cursor) */
 	int compact_images = 0;
 	int compact_parts = 1;                 /* option "compact_parts": launches a compact run of 4e6 slots or more is traced in (alternating between two
-	                                        * streams, each with its own half of the per-lane scratch: scratch_halves).  Measured, not adopted: 2 launches 20.95 ms against 19.6 ms for one (1e7 slots; profiles/r04/kernel_history.md) */
+	                                        * streams, each with its own half of the per-lane scratch: pc_launch_site).  Measured, not adopted: 2 launches 20.95 ms against 19.6 ms for one (1e7 slots; profiles/r04/kernel_history.md) */
 	int run_compact = 0;                   /* the last run did so */
 	int dst_prepinned = 0;                 /* the caller (a device group) has pinned the destination planes itself: the fetch pins nothing */
 	int keep_pinned = 0;                   /* option "keep_pinned": pc_hip_transmission_images leaves the destination planes pinned */
@@ -1288,11 +1241,6 @@ struct pc_hip_ctx {
 	pc_dev_buf<long long> d_ids;
 	pc_dev_buf<double> d_lane_start;
 	pc_dev_buf<double> d_wscratch;
-	/* per-lane scratch (d_wscratch, d_rlog, d_lane_start) of a run cut into parts: launches on the two streams overlap, so the
-	 * buffers are allocated twice over (scratch_halves = 2), each half sized for the largest launch the run can make, and the
-	 * launches on stream2 use the second half (scratch_half = 1).  Set by the parts loop of pc_hip_transmission_run only. */
-	int scratch_halves = 1;
-	int scratch_half = 0;
 	/* explicit-photon calls (polycap_photon_launch, polycap_source_get_photon): one device buffer and one pinned host
 	 * buffer, kept between calls, so that a single photon costs two copies and a launch instead of ten copies and
 	 * as many allocations */
@@ -1355,12 +1303,6 @@ struct pc_hip_ctx {
 	int64_t relay_counters[8] = {0};
 };
 
-static int pc_cus(const pc_hip_ctx *ctx)
-{
-	const int n = ctx->n_cu / (ctx->cu_share > 0 ? ctx->cu_share : 1);
-	return n > 0 ? n : 1;
-}
-
 static void pc_fill_common(pc_hip_ctx *ctx, pc_kargs &a)
 {
 	const size_t npts = (size_t)ctx->host.pm.nmax + 1;
@@ -1373,30 +1315,17 @@ static void pc_fill_common(pc_hip_ctx *ctx, pc_kargs &a)
 	a.ec = ctx->d_ec;
 	a.ec_soa = ctx->d_ec_soa;
 	a.pm = ctx->host.pm;
-	a.pm.literal = ctx->literal;
-	a.event_threshold = ctx->event_threshold;
-	a.new_threshold = ctx->new_threshold;
-	a.march_burst = ctx->march_burst;
-	a.march_stop = (ctx->march_stop > 0 && ctx->march_stop < ctx->event_threshold) ? ctx->march_stop : ctx->event_threshold;
-	a.pool_refill = ctx->pool_refill;
+	a.pm.literal = ctx->opts.literal;
+	a.event_threshold = ctx->opts.event_threshold;
+	a.new_threshold = ctx->opts.new_threshold;
+	a.march_burst = ctx->opts.march_burst;
+	a.march_stop = (ctx->opts.march_stop > 0 && ctx->opts.march_stop < ctx->opts.event_threshold) ? ctx->opts.march_stop : ctx->opts.event_threshold;
+	a.pool_refill = ctx->opts.pool_refill;
 	a.totals = ctx->d_totals;
 	a.work = &ctx->d_totals->next_slot;
 	a.sumw = (unsigned long long *)(ctx->d_totals + 1);
-	a.sumw2 = ctx->weight_squares ? a.sumw + 2*(size_t)ctx->host.pm.n_energies : nullptr;
+	a.sumw2 = ctx->opts.weight_squares ? a.sumw + 2*(size_t)ctx->host.pm.n_energies : nullptr;
 }
-
-/* u64 per energy of the exact sums a workgroup keeps in LDS: (lo, hi) of the weights, and of their squares with "weight_squares" */
-static size_t pc_acc_words(const pc_kargs &a)
-{
-	return a.sumw2 ? 4 : 2;
-}
-
-/* dynamic LDS of the any-n_energies kernel: exact sums and per-energy constants */
-static size_t pc_ne0_dyn_lds(size_t ne, int lds_acc, int lds_ec, size_t acc_words)
-{
-	return (lds_acc ? acc_words*ne*sizeof(unsigned long long) : 0) + (lds_ec ? 6*ne*sizeof(double) : 0);
-}
-
 
 /* What pc_trace_log_kernel needs to know about the run's energies (once per context):
  *   ct_tame -- a cosine of the angle to the surface normal above which every energy's reflectivity stays at least 1e-11 below 1
@@ -1453,213 +1382,91 @@ static void pc_sweep_certificate(pc_hip_ctx *ctx)
 	ctx->sweep_cert = 1;
 }
 
-/* pc_trace_log_kernel applies to source runs with more than 8 valid energies on a profile of up to 1024 points whose sums and
- * constants fit in LDS beside a stage of at least one log per wave; returns the stage size (doubles per wave), 0 if not */
-static size_t pc_log_stage_doubles(const pc_hip_ctx *ctx, int ne, int log_cap)
+/* The one place a trace kernel is launched from: grows the per-lane scratch the plan asks for, copies the plan into the kernel
+ * arguments, and launches between the context's events as far as the site wants them.  Only source runs have other than lane kernels. */
+template <int MODE>
+static int pc_launch_planned(pc_hip_ctx *ctx, const pc_launch_site &site, const pc_launch_plan &p, pc_kargs &a)
 {
-	const size_t fixed = 6*PCS_PITCH*sizeof(double) + PCS_PITCH*sizeof(pc_marg4) + pcs_dyn_lds((size_t)ne, PCS_BLOCK, 0, ctx->weight_squares != 0);
-	if (fixed >= 163840) return 0;
-	size_t per_wave = ((163840 - fixed)/(PCS_BLOCK/PC_WAVE))/sizeof(double);
-	const size_t one = PCS_ENT*(size_t)log_cap;
-	if (per_wave < one) return 0;
-	size_t ps = per_wave/one;
-	if (ps > PCS_MAXPS) ps = PCS_MAXPS;
-	return ps*one;
-}
-
-template <int NE, int MODE>
-static int pc_launch_one(pc_hip_ctx *ctx, const pc_kargs &a, int grid)
-{
-	/* table pitch: 1024 entries (48 KB of LDS) covers the reference's generated profiles (nmax = 999) and its example decks */
-	const int block = (int)(a.total_threads / grid);
-	const size_t dyn = (NE == 0) ? pc_ne0_dyn_lds((size_t)ctx->host.pm.n_energies, a.lds_acc, a.lds_ec, pc_acc_words(a))
-	                             : ((NE != 1 && a.lds_acc) ? pc_acc_words(a)*(size_t)ctx->host.pm.n_energies*sizeof(unsigned long long) : 0);
-	/* option "weight_squares": kernels of their own (SQ), so that the default kernels keep their registers */
+	constexpr bool SOURCE = MODE == PC_MODE_SRC_CIRCULAR || MODE == PC_MODE_SRC_GENERIC;
+	constexpr bool SCAN = MODE == PC_MODE_SCAN_CIRCULAR || MODE == PC_MODE_SCAN_GENERIC;
 	constexpr bool CAN_SQ = MODE != PC_MODE_EXPLICIT;
-	const bool sq = CAN_SQ && a.sumw2 != nullptr;
-	if (ctx->host.pm.nmax + 1 <= 1024) {
-		if (sq) hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, CAN_SQ>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-		else hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	} else if (NE <= 1) {   /* long profiles: only the NE = 1 and the any-n_energies kernels are built for the 2048 pitch */
-		if (sq) hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, CAN_SQ>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-		else hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	} else
-		return pc_fail(PC_HIP_ERR_INVALID, "internal: register-weight kernels are built for profiles of up to 1024 points");
-	PC_HIP_CHECK(hipGetLastError());
-	return PC_HIP_OK;
-}
-
-/* the pool kernel serves single-energy source runs on profiles of up to 1024 points (what its packed records hold) */
-template <int MODE>
-static bool pc_pool_applies(const pc_hip_ctx *ctx, const pc_kargs &a)
-{
-	const pc_params &pm = ctx->host.pm;
-	return MODE != PC_MODE_EXPLICIT && ctx->pool && pm.n_energies == 1 && !ctx->literal && pm.nmax + 1 <= PQ_PITCH
-	    && a.max_attempts <= (1u << 24) && pm.n_shells < 16000. && a.n_slots < (1ll << 39);
-}
-
-template <int MODE>
-static void pc_launch_pool(pc_hip_ctx *ctx, const pc_kargs &a, int grid)
-{
-	if constexpr (MODE != PC_MODE_EXPLICIT) {
-		if (a.sumw2) hipLaunchKernelGGL((pc_trace_pool_kernel<MODE, true>), dim3(grid), dim3(PQ_BLOCK), 0, ctx->stream, a);
-		else hipLaunchKernelGGL((pc_trace_pool_kernel<MODE>), dim3(grid), dim3(PQ_BLOCK), 0, ctx->stream, a);
-	}
-}
-
-template <int MODE>
-static int pc_launch_kernel(pc_hip_ctx *ctx, pc_kargs &a, long long n_items)
-{
-	const int ne = ctx->host.pm.n_energies;
-	/* weights in registers for up to 8 energies (kernels NE = 1, 4, 8), in the per-lane scratch beyond */
-	const int kne = (ne == 1) ? 1 : ((ne <= 4 && ctx->host.pm.nmax + 1 <= 1024) ? 4 : ((ne <= 8 && ctx->host.pm.nmax + 1 <= 1024) ? 8 : 0));
-	/* with "weight_squares" the squared weights' sums sit beside the weights' and fall back to global atomics with them */
-	a.lds_acc = (ne != 1 && pc_acc_words(a)*(size_t)ne*sizeof(unsigned long long) <= 16384) ? 1 : 0;
-	/* many energies on a profile of up to 1024 points: one workgroup of 1024 threads per CU (the same 16 waves as two of
-	 * 512) leaves room in LDS for the per-energy constants next to the tables and the sums */
-	a.lds_ec = (kne == 0 && a.lds_acc && ctx->lds_ec && ctx->host.pm.nmax + 1 <= 1024 && (48 + 8*pc_acc_words(a))*(size_t)ne <= 28672) ? 1 : 0;
-	bool all_valid = true;
-	a.sweep_rough = 0;
-	for (const pc_energy_const &c : ctx->host.ec) {
-		if (c.valid == 0.) all_valid = false;
-		if (c.rough_c != 0.) a.sweep_rough = 1;
-	}
-	/* source runs with more than 8 (valid) energies log their reflections (pc_trace_log_kernel); an explicit photon reports its
-	 * state at the absorbing reflection, which the logging kernel's speculation overwrites */
-	const bool want_log = kne == 0 && ctx->lds_ec && ctx->host.pm.nmax + 1 <= 1024 && ne >= ctx->log_min_energies && ctx->batch_reflections && all_valid
-	                      && MODE != PC_MODE_EXPLICIT;
-	if constexpr (MODE != PC_MODE_EXPLICIT) {
-#ifdef PC_EXPERIMENTS
-		if (ctx->wave_per_photon && ne == 1 && !a.keep_images && ctx->host.pm.nmax + 1 <= 1024) {
-			/* the experiment of pc_wave_kernel.h: one wave per photon, 16 waves per CU */
-			long long want = (n_items + 3) / 4;
-			int grid = (int)(want < 4ll*ctx->n_cu ? want : 4ll*ctx->n_cu);
-			if (grid < 1) grid = 1;
-			a.total_threads = (long long)grid * PCW_BLOCK;
-			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-			hipLaunchKernelGGL((pc_trace_wave_kernel<MODE>), dim3(grid), dim3(PCW_BLOCK), 0, ctx->stream, a);
-			ctx->last_kernel = 3;
-			PC_HIP_CHECK(hipGetLastError());
-			if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
-			return PC_HIP_OK;
-		}
-#endif
-		const pc_params &pm = ctx->host.pm;
-		const bool want_producer = ctx->producer == 1 || (ctx->producer < 0 && !ctx->in_probe && ctx->refl_per_launch >= PC3_MIN_REFL);
-		if (want_producer && pm.n_energies == 1 && !ctx->literal && pm.nmax + 1 <= PC3_PITCH && a.max_attempts <= (1u << 24)
-		    && pm.n_shells < 16000. && a.n_slots < (1ll << 39)) {
-			const long long per_block = (long long)PC3_CONSUMERS*PC_WAVE;
-			long long want = (n_items + per_block - 1) / per_block;
-			const long long per_cu = (PC3_BLOCK > 512) ? 1 : 2;
-			int grid = (int)(want < per_cu*pc_cus(ctx) ? want : per_cu*pc_cus(ctx));
-			if (grid < 1) grid = 1;
-			a.total_threads = (long long)grid * PC3_BLOCK;
-			a.event_threshold = ctx->event_threshold;
-			a.new_threshold = ctx->producer_new_min;
-			a.pool_event_min = ctx->producer_new_first;
-			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-			/* "weight_squares": one instantiation, without the march statistics (diagnostics) */
-			if (a.sumw2) hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, false, true>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
-			else if (ctx->march_stats) hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, true>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
-			else hipLaunchKernelGGL((pc_trace_producer_kernel<MODE, false>), dim3(grid), dim3(PC3_BLOCK), 0, ctx->stream, a);
-			ctx->last_kernel = 2;
-			PC_HIP_CHECK(hipGetLastError());
-			if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
-			return PC_HIP_OK;
-		}
-	}
-	if (pc_pool_applies<MODE>(ctx, a)) {
-		/* one 1024-thread workgroup per CU; a wave holds 64 + PQ_P photons */
-		const long long per_block = (long long)PQ_WAVES*(PC_WAVE + PQ_P);
-		long long want = (n_items + per_block - 1) / per_block;
-		int grid = (int)(want < pc_cus(ctx) ? want : pc_cus(ctx));
-		if (grid < 1) grid = 1;
-		a.total_threads = (long long)grid * PQ_BLOCK;
-		a.event_threshold = ctx->pool_march_min;
-		a.pool_event_min = ctx->pool_event_min;
-		a.event_march = ctx->event_march;
-		a.new_threshold = ctx->pool_new_min;
-		if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-		pc_launch_pool<MODE>(ctx, a, grid);
-		ctx->last_kernel = 1;
-		PC_HIP_CHECK(hipGetLastError());
-		if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
-		return PC_HIP_OK;
-	}
-	if constexpr (MODE != PC_MODE_EXPLICIT) {
-		/* log capacity: 64 reflections (32 below 64 energies), halved while not even one log per wave fits in the stage beside
-		 * the constants of very many energies (beyond ~450) */
-		int log_cap = ctx->log_cap > 0 ? ctx->log_cap : (ne >= 64 ? 64 : 32);
-		size_t stage = want_log ? pc_log_stage_doubles(ctx, ne, log_cap) : 0;
-		while (want_log && !stage && ctx->log_cap <= 0 && log_cap > 8) {
-			log_cap /= 2;
-			stage = pc_log_stage_doubles(ctx, ne, log_cap);
-		}
-		if (stage) {
-			/* reflections are logged, a photon's weights swept once per log (pc_sweep_kernel.h): one workgroup of 12 waves per CU */
-			pc_sweep_certificate(ctx);
-			long long want = (n_items + PCS_BLOCK - 1) / PCS_BLOCK;
-			int grid = (int)(want < pc_cus(ctx) ? want : pc_cus(ctx));
-			if (grid < 1) grid = 1;
-			a.total_threads = (long long)grid * PCS_BLOCK;
-			/* one launch: its own lanes; parts: halves for the largest launch, the second one for the launches on stream2 */
-			const size_t lanes = (ctx->scratch_halves > 1) ? (size_t)pc_cus(ctx) * PCS_BLOCK : (size_t)a.total_threads;
-			const size_t half_w = (size_t)ne * lanes, half_l = 3*(size_t)log_cap * lanes;
-			const size_t need_w = half_w * (size_t)ctx->scratch_halves, need_l = half_l * (size_t)ctx->scratch_halves;
-			int st = ctx->d_wscratch.grow(need_w, "could not allocate the per-lane weight scratch");
-			if (!st) st = ctx->d_rlog.grow(need_l, "could not allocate the reflection logs");
-			if (st) return st;
-			a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half_w;
-			a.rlog = ctx->d_rlog + (size_t)ctx->scratch_half * half_l;
-			a.log_cap = log_cap;
-			a.stage_ps = (int)(stage/(PCS_ENT*(size_t)log_cap));
-			{
-				/* photons that wait for a sweep before one is run: the fewest (up to the stage's capacity) whose last pass leaves at
-				 * most 3 % of the round's lanes idle, else the count that leaves the fewest */
-				int best = 1;
-				double best_w = 2.;
-				for (int n = 1; n <= a.stage_ps && n <= ctx->flush_max; n++) {
-					const double w = (double)((64 - (n*ne) % 64) % 64) / (double)(n*ne);
-					if (w < best_w - 1e-12) { best_w = w; best = n; }
-					if (w <= 0.03) { best = n; break; }
-				}
-				a.flush_min = best;
-			}
-			a.n_proxy = ctx->sweep_n_proxy; a.proxy_e[0] = ctx->sweep_proxy_e[0]; a.proxy_e[1] = ctx->sweep_proxy_e[1];
-			a.ct_tame = ctx->sweep_ct_tame;
-			a.sweep_skip = (ctx->sweep_skip && !a.keep_images) ? 1 : 0;
-			a.sweep_fuse = a.keep_images ? 0 : ctx->sweep_fuse;
-			a.sweep_exact_every = ctx->sweep_exact_every;
-			if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-			if (a.sumw2) hipLaunchKernelGGL((pc_trace_log_kernel<MODE, true>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage, true), ctx->stream, a);
-			else hipLaunchKernelGGL((pc_trace_log_kernel<MODE>), dim3(grid), dim3(PCS_BLOCK), pcs_dyn_lds((size_t)ne, PCS_BLOCK, stage, false), ctx->stream, a);
-			ctx->last_kernel = 4;
-			PC_HIP_CHECK(hipGetLastError());
-			if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
-			return PC_HIP_OK;
-		}
-	}
-	long long max_blocks = (long long)pc_cus(ctx) * ((kne == 0) ? 1 : ctx->blocks_per_cu);
-	const int block = ctx->block_size;
-	long long want_blocks = (n_items + block - 1) / block;
-	int grid = (int)(want_blocks < max_blocks ? want_blocks : max_blocks);
-	if (grid < 1) grid = 1;
-	a.total_threads = (long long)grid * block;
-	if (kne == 0) {
-		/* one launch: its own lanes; parts: halves for the largest launch, the second one for the launches on stream2 */
-		const size_t half = (size_t)ne * ((ctx->scratch_halves > 1) ? (size_t)max_blocks * (size_t)block : (size_t)a.total_threads);
-		const size_t need = half * (size_t)ctx->scratch_halves;
-		int st = ctx->d_wscratch.grow(need, "could not allocate the per-lane weight scratch");
-		if (st) return st;
-		a.wscratch = ctx->d_wscratch + (size_t)ctx->scratch_half * half;
-	}
-	if (ctx->rec_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-	ctx->last_kernel = 0;
-	int st = (kne == 1) ? pc_launch_one<1, MODE>(ctx, a, grid) : (kne == 4) ? pc_launch_one<4, MODE>(ctx, a, grid)
-	       : (kne == 8) ? pc_launch_one<8, MODE>(ctx, a, grid) : pc_launch_one<0, MODE>(ctx, a, grid);
+	/* a scan has buffers of its own, so that it leaves everything of the last run as it was */
+	pc_dev_buf<double> &wscratch = SCAN ? ctx->d_scan_wscratch : ctx->d_wscratch;
+	int st = wscratch.grow(p.half_w * (size_t)site.halves, SCAN ? "pc_hip_scan_run: could not allocate the per-lane weight scratch"
+	                                                            : "could not allocate the per-lane weight scratch");
+	if (!st) st = ctx->d_rlog.grow(p.half_l * (size_t)site.halves, "could not allocate the reflection logs");
 	if (st) return st;
-	if (ctx->rec_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
+	if (p.half_w) a.wscratch = wscratch + (size_t)site.half * p.half_w;
+	if (p.half_l) a.rlog = ctx->d_rlog + (size_t)site.half * p.half_l;
+	a.total_threads = (long long)p.grid * p.block;
+	a.lds_acc = p.lds_acc; a.lds_ec = p.lds_ec; a.sweep_rough = p.sweep_rough;
+	a.event_threshold = p.event_threshold; a.new_threshold = p.new_threshold;
+	a.pool_event_min = p.pool_event_min; a.event_march = p.event_march;
+	a.log_cap = p.log_cap; a.stage_ps = p.stage_ps; a.flush_min = p.flush_min;
+	a.sweep_skip = p.sweep_skip; a.sweep_fuse = p.sweep_fuse; a.sweep_exact_every = p.sweep_exact_every;
+	if (p.kernel == PC_KERNEL_LOG) {
+		pc_sweep_certificate(ctx);
+		a.n_proxy = ctx->sweep_n_proxy; a.proxy_e[0] = ctx->sweep_proxy_e[0]; a.proxy_e[1] = ctx->sweep_proxy_e[1];
+		a.ct_tame = ctx->sweep_ct_tame;
+	}
+	if (site.record_ev0) PC_HIP_CHECK(hipEventRecord(ctx->ev0, site.stream));
+#define PC_GO(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), p.dyn_lds, site.stream, a)
+#define PC_GO_SQ(K, ...) do { if (CAN_SQ && p.sq) PC_GO(K<__VA_ARGS__, CAN_SQ>); else PC_GO(K<__VA_ARGS__>); } while (0)
+	switch (p.kernel) {
+	case PC_KERNEL_LANE:     /* long profiles: only the NE = 1 and the any-n_energies kernels are built for the 2048 pitch */
+		switch (p.pitch == 1024 ? p.kne : -1 - p.kne) {
+		case 1: PC_GO_SQ(pc_trace_kernel, 1, MODE, 1024); break;
+		case 4: PC_GO_SQ(pc_trace_kernel, 4, MODE, 1024); break;
+		case 8: PC_GO_SQ(pc_trace_kernel, 8, MODE, 1024); break;
+		case 0: PC_GO_SQ(pc_trace_kernel, 0, MODE, 1024); break;
+		case -2: PC_GO_SQ(pc_trace_kernel, 1, MODE, PC_MAX_PITCH); break;
+		case -1: PC_GO_SQ(pc_trace_kernel, 0, MODE, PC_MAX_PITCH); break;
+		default: return pc_fail(PC_HIP_ERR_INVALID, "internal: register-weight kernels are built for profiles of up to 1024 points");
+		}
+		break;
+	case PC_KERNEL_POOL: if constexpr (SOURCE) PC_GO_SQ(pc_trace_pool_kernel, MODE); break;
+	case PC_KERNEL_LOG: if constexpr (SOURCE) PC_GO_SQ(pc_trace_log_kernel, MODE); break;
+	case PC_KERNEL_PRODUCER:
+		if constexpr (SOURCE) {
+			if (p.sq) PC_GO(pc_trace_producer_kernel<MODE, false, true>);
+			else if (p.march_stats) PC_GO(pc_trace_producer_kernel<MODE, true>);
+			else PC_GO(pc_trace_producer_kernel<MODE, false>);
+		}
+		break;
+#ifdef PC_EXPERIMENTS
+	case PC_KERNEL_WAVE: if constexpr (SOURCE) PC_GO(pc_trace_wave_kernel<MODE>); break;
+#endif
+	}
+#undef PC_GO_SQ
+#undef PC_GO
+	if (!SCAN) ctx->last_kernel = p.kernel;
+	PC_HIP_CHECK(hipGetLastError());
+	if (site.record_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, site.stream));
 	return PC_HIP_OK;
+}
+
+/* plan, then launch: n_items slots (source runs), photons (explicit launches) or flat indices (scans) with the arguments in a */
+template <int MODE>
+static int pc_launch_kernel(pc_hip_ctx *ctx, const pc_launch_site &site, pc_kargs &a, long long n_items)
+{
+	pc_plan_input in;
+	in.ne = ctx->host.pm.n_energies; in.npts = ctx->host.pm.nmax + 1; in.n_shells = ctx->host.pm.n_shells;
+	for (const pc_energy_const &c : ctx->host.ec) {
+		if (c.valid == 0.) in.all_valid = false;
+		if (c.rough_c != 0.) in.rough = true;
+	}
+	in.n_cu = ctx->n_cu; in.refl_per_launch = ctx->refl_per_launch;
+	in.mode = MODE == PC_MODE_EXPLICIT ? PC_PLAN_EXPLICIT : (MODE == PC_MODE_SCAN_CIRCULAR || MODE == PC_MODE_SCAN_GENERIC) ? PC_PLAN_SCAN : PC_PLAN_SOURCE;
+	in.n_items = n_items; in.n_slots = a.n_slots; in.max_attempts = a.max_attempts; in.keep_images = a.keep_images != 0;
+	in.squares = MODE != PC_MODE_EXPLICIT && ctx->opts.weight_squares != 0;
+	in.force_lane = site.force_lane; in.halves = site.halves;
+	return pc_launch_planned<MODE>(ctx, site, pc_plan_launch(in, ctx->opts), a);
+}
+
+/* a big single-energy run of a context that does not know yet how long its photons live is preceded by a probe (pc_probe_lifetime) */
+static bool pc_wants_probe(const pc_hip_ctx *ctx, long long n_slots)
+{
+	return ctx->opts.producer < 0 && ctx->refl_per_launch < 0. && ctx->host.pm.n_energies == 1 && n_slots >= 2000000;
 }
 
 #include "pc_leak_kernels.h"
@@ -1685,7 +1492,7 @@ void pc_hip_ctx_destroy(pc_hip_ctx *ctx)
 {
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->device);
-	if (ctx->main_stream) (void)hipStreamSynchronize(ctx->main_stream);
+	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	delete ctx;
 }
 
@@ -1710,10 +1517,9 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 	hipDeviceProp_t prop;
 	PC_CTX_CHECK(hipGetDeviceProperties(&prop, device));
 	ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-	PC_CTX_CHECK(ctx->main_stream.ensure());
-	ctx->stream = ctx->main_stream;
+	PC_CTX_CHECK(ctx->stream.ensure());
 	if (const char *e = getenv("POLYCAP_PRODUCER"))          /* tests: force (1) or forbid (0) the launching-wave kernel */
-		if (*e == '0' || *e == '1') ctx->producer = *e - '0';
+		if (*e == '0' || *e == '1') ctx->opts.producer = *e - '0';
 	PC_CTX_CHECK(ctx->ev0.ensure(hipEventDefault));
 	PC_CTX_CHECK(ctx->ev1.ensure(hipEventDefault));
 	PC_CTX_GROW(ctx->d_tables, 9*npts, "the profile tables");
@@ -1758,22 +1564,22 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 {
 	if (!ctx || !name) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_set_option: NULL argument");
 	std::string n(name);
-	if (n == "literal_march") ctx->literal = value ? 1 : 0;
-	else if (n == "event_threshold") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "event_threshold must be in [1,64]"); ctx->event_threshold = (int)value; }
-	else if (n == "new_threshold") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "new_threshold must be in [1,64]"); ctx->new_threshold = (int)value; }
-	else if (n == "march_stop") { if (value < 0 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "march_stop must be in [0,64]"); ctx->march_stop = (int)value; }
-	else if (n == "march_burst") { if (value < 1) return pc_fail(PC_HIP_ERR_INVALID, "march_burst must be >= 1"); ctx->march_burst = (int)value; }
-	else if (n == "block_size") { if (value < 64 || value > PC_BLOCK || (value % 64) != 0) return pc_fail(PC_HIP_ERR_INVALID, "block_size must be a multiple of 64 up to the compiled maximum"); ctx->block_size = (int)value; }
-	else if (n == "blocks_per_cu") { if (value < 1 || value > 8) return pc_fail(PC_HIP_ERR_INVALID, "blocks_per_cu must be in [1,8]"); ctx->blocks_per_cu = (int)value; }
-	else if (n == "lds_ec") ctx->lds_ec = value ? 1 : 0;
-	else if (n == "batch_reflections") ctx->batch_reflections = value ? 1 : 0;
-	else if (n == "log_cap") { if (value < 0 || value > 255) return pc_fail(PC_HIP_ERR_INVALID, "log_cap must be in [0,255] (0 = automatic)"); ctx->log_cap = (int)value; }
-	else if (n == "sweep_skip") ctx->sweep_skip = value ? 1 : 0;
-	else if (n == "log_min_energies") { if (value < 9) return pc_fail(PC_HIP_ERR_INVALID, "log_min_energies must be >= 9 (up to 8 energies have their weights in registers)"); ctx->log_min_energies = (int)value; }
-	else if (n == "flush_max") { if (value < 1 || value > 16) return pc_fail(PC_HIP_ERR_INVALID, "flush_max must be in [1,16]"); ctx->flush_max = (int)value; }
-	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->sweep_exact_every = (int)value; }
-	else if (n == "weight_squares") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "weight_squares must be 0 or 1"); ctx->weight_squares = (int)value; }
-	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->sweep_fuse = (int)value; }
+	if (n == "literal_march") ctx->opts.literal = value ? 1 : 0;
+	else if (n == "event_threshold") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "event_threshold must be in [1,64]"); ctx->opts.event_threshold = (int)value; }
+	else if (n == "new_threshold") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "new_threshold must be in [1,64]"); ctx->opts.new_threshold = (int)value; }
+	else if (n == "march_stop") { if (value < 0 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "march_stop must be in [0,64]"); ctx->opts.march_stop = (int)value; }
+	else if (n == "march_burst") { if (value < 1) return pc_fail(PC_HIP_ERR_INVALID, "march_burst must be >= 1"); ctx->opts.march_burst = (int)value; }
+	else if (n == "block_size") { if (value < 64 || value > PC_BLOCK || (value % 64) != 0) return pc_fail(PC_HIP_ERR_INVALID, "block_size must be a multiple of 64 up to the compiled maximum"); ctx->opts.block_size = (int)value; }
+	else if (n == "blocks_per_cu") { if (value < 1 || value > 8) return pc_fail(PC_HIP_ERR_INVALID, "blocks_per_cu must be in [1,8]"); ctx->opts.blocks_per_cu = (int)value; }
+	else if (n == "lds_ec") ctx->opts.lds_ec = value ? 1 : 0;
+	else if (n == "batch_reflections") ctx->opts.batch_reflections = value ? 1 : 0;
+	else if (n == "log_cap") { if (value < 0 || value > 255) return pc_fail(PC_HIP_ERR_INVALID, "log_cap must be in [0,255] (0 = automatic)"); ctx->opts.log_cap = (int)value; }
+	else if (n == "sweep_skip") ctx->opts.sweep_skip = value ? 1 : 0;
+	else if (n == "log_min_energies") { if (value < 9) return pc_fail(PC_HIP_ERR_INVALID, "log_min_energies must be >= 9 (up to 8 energies have their weights in registers)"); ctx->opts.log_min_energies = (int)value; }
+	else if (n == "flush_max") { if (value < 1 || value > 16) return pc_fail(PC_HIP_ERR_INVALID, "flush_max must be in [1,16]"); ctx->opts.flush_max = (int)value; }
+	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->opts.sweep_exact_every = (int)value; }
+	else if (n == "weight_squares") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "weight_squares must be 0 or 1"); ctx->opts.weight_squares = (int)value; }
+	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->opts.sweep_fuse = (int)value; }
 	else if (n == "plane_images") ctx->plane_images = value ? 1 : 0;
 	else if (n == "compact_images") ctx->compact_images = value ? 1 : 0;
 	else if (n == "compact_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "compact_parts must be in [1,16]"); ctx->compact_parts = (int)value; }
@@ -1783,24 +1589,24 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->run_parts = (int)value; }
 	else if (n == "relay_acc_lds") ctx->relay_acc_lds = value ? 1 : 0;
 	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->fetch_threads = (int)value; }
-	else if (n == "pool") ctx->pool = value ? 1 : 0;
+	else if (n == "pool") ctx->opts.pool = value ? 1 : 0;
 	else if (n == "wave_per_photon") {
 #ifdef PC_EXPERIMENTS
-		ctx->wave_per_photon = value ? 1 : 0;
+		ctx->opts.wave_per_photon = value ? 1 : 0;
 #else
 		if (value) return pc_fail(PC_HIP_ERR_INVALID, "wave_per_photon: the experiment kernel is compiled only with -DPC_EXPERIMENTS (scripts/analysis/wave_per_photon_ab.py)");
 #endif
 	}
-	else if (n == "march_stats") ctx->march_stats = value ? 1 : 0;
-	else if (n == "cu_share") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "cu_share must be in [1,64]"); ctx->cu_share = (int)value; }
-	else if (n == "producer") { if (value < -1 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "producer must be -1 (automatic), 0 or 1"); ctx->producer = (int)value; }
-	else if (n == "producer_new_min") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "producer_new_min must be in [1,64]"); ctx->producer_new_min = (int)value; }
-	else if (n == "producer_new_first") { if (value < 1 || value > 65) return pc_fail(PC_HIP_ERR_INVALID, "producer_new_first must be in [1,65]"); ctx->producer_new_first = (int)value; }
-	else if (n == "pool_refill") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "pool_refill must be in [1,64]"); ctx->pool_refill = (int)value; }
-	else if (n == "event_march") { if (value < 0 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "event_march must be in [0,64]"); ctx->event_march = (int)value; }
-	else if (n == "pool_event_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_event_min must be in [1,128]"); ctx->pool_event_min = (int)value; }
-	else if (n == "pool_new_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_new_min must be in [1,128]"); ctx->pool_new_min = (int)value; }
-	else if (n == "pool_march_min") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "pool_march_min must be in [1,64]"); ctx->pool_march_min = (int)value; }
+	else if (n == "march_stats") ctx->opts.march_stats = value ? 1 : 0;
+	else if (n == "cu_share") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "cu_share must be in [1,64]"); ctx->opts.cu_share = (int)value; }
+	else if (n == "producer") { if (value < -1 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "producer must be -1 (automatic), 0 or 1"); ctx->opts.producer = (int)value; }
+	else if (n == "producer_new_min") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "producer_new_min must be in [1,64]"); ctx->opts.producer_new_min = (int)value; }
+	else if (n == "producer_new_first") { if (value < 1 || value > 65) return pc_fail(PC_HIP_ERR_INVALID, "producer_new_first must be in [1,65]"); ctx->opts.producer_new_first = (int)value; }
+	else if (n == "pool_refill") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "pool_refill must be in [1,64]"); ctx->opts.pool_refill = (int)value; }
+	else if (n == "event_march") { if (value < 0 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "event_march must be in [0,64]"); ctx->opts.event_march = (int)value; }
+	else if (n == "pool_event_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_event_min must be in [1,128]"); ctx->opts.pool_event_min = (int)value; }
+	else if (n == "pool_new_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_new_min must be in [1,128]"); ctx->opts.pool_new_min = (int)value; }
+	else if (n == "pool_march_min") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "pool_march_min must be in [1,64]"); ctx->opts.pool_march_min = (int)value; }
 	else if (n == "leak_max_depth") { if (value < 2 || value > (1 << 20)) return pc_fail(PC_HIP_ERR_INVALID, "leak_max_depth must be in [2, 2^20]"); ctx->leak_max_depth = (int)value; }
 	else if (n == "leak_stack_mb") { if (value < 1) return pc_fail(PC_HIP_ERR_INVALID, "leak_stack_mb must be >= 1"); ctx->leak_stack_bytes = (size_t)value << 20; }
 	else if (n == "leak_order") { ctx->leak_order = value != 0; }
@@ -1878,7 +1684,7 @@ static int pc_batch_trace(pc_hip_ctx *ctx, const pc_batch &b, int leak)
 	a.in_start = b.d_start; a.in_dir = b.d_dir; a.in_elecv = b.d_ev;
 	a.out_rc = b.d_rc; a.out_weights = b.d_w; a.out_exit_coords = b.d_ec; a.out_exit_dir = b.d_ed; a.out_exit_elecv = b.d_ee;
 	a.out_irefl = b.d_ir; a.out_dtravel = b.d_dt;
-	if (!leak) return pc_launch_kernel<PC_MODE_EXPLICIT>(ctx, a, n);
+	if (!leak) return pc_launch_kernel<PC_MODE_EXPLICIT>(ctx, pc_launch_site{ctx->stream}, a, n);
 	/* polycap_photon_launch(..., leak_calc=true): rerun with a larger record buffer until every event fits */
 	long long capacity = ctx->leak_capacity > 0 ? ctx->leak_capacity : std::max<long long>(4096, (16 + 8*(long long)b.ne)*n);
 	ctx->leak_slot0 = 0;
@@ -2033,27 +1839,26 @@ static long long pc_part_begin(long long n_slots, int parts, int k)
 static const int PC_N_PLANES = 17;
 
 /* How long do photons live on this optic?  32768 slots with the default kernel (3 ms, results unused) set refl_per_launch, by
- * which the context -- or, for a device group, every member -- picks the kernel of its source runs. */
+ * which the context -- or, for a device group, every member -- picks the kernel of its source runs.  Called where pc_wants_probe
+ * holds: refl_per_launch is unknown, so the probe itself gets no launching wave, and it is too small to ask for a probe. */
 static int pc_probe_lifetime(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, uint32_t max_attempts)
 {
-	ctx->in_probe = 1;
 	int64_t c[6];
 	int st = pc_hip_transmission_run(ctx, seed, slot0, 32768, max_attempts, 0);
 	if (st == PC_HIP_OK) st = pc_hip_transmission_totals(ctx, nullptr, c, nullptr);
-	ctx->in_probe = 0;
 	return (st == PC_HIP_ERR_ATTEMPTS) ? PC_HIP_OK : st;
 }
 
 /* lanes of the largest launch the context makes: one 64-byte line of pc_kargs::lane_start each */
 static size_t pc_lane_start_lanes(const pc_hip_ctx *ctx)
 {
-	return (size_t)ctx->n_cu * (size_t)std::max(ctx->blocks_per_cu*ctx->block_size, 1024);
+	return (size_t)ctx->n_cu * (size_t)std::max(ctx->opts.blocks_per_cu*ctx->opts.block_size, 1024);
 }
 
 /* buffers of a compact run of n_slots (pc_kargs::img_cursor): position counter, per-block counters, the host-visible block
- * flags, the lanes' start-image lines (ctx->scratch_halves sets of them) and, on request, the plane of slot indices; counters
+ * flags, the lanes' start-image lines (`halves` sets of them) and, on request, the plane of slot indices; counters
  * and flags are cleared */
-static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots)
+static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots, int halves)
 {
 	/* the block flags are cleared from the host below: a run of this context that is still in flight would set flags of its own
 	 * after that (and the fetch of the new run would copy blocks the new kernel has not written) */
@@ -2069,7 +1874,7 @@ static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots)
 	if (!st) st = ctx->h_blk_flag.grow(blocks, "pc_hip_transmission_run: could not allocate the block flags", cap);
 	if (!st && ctx->slot_ids) st = ctx->d_ids.grow((size_t)n_slots, "pc_hip_transmission_run: could not allocate the slot-index plane");
 	/* one 64-byte line per lane of the largest launch the context makes, per half */
-	if (!st) st = ctx->d_lane_start.grow(8*pc_lane_start_lanes(ctx)*(size_t)ctx->scratch_halves, "pc_hip_transmission_run: could not allocate the lanes' start-image lines");
+	if (!st) st = ctx->d_lane_start.grow(8*pc_lane_start_lanes(ctx)*(size_t)halves, "pc_hip_transmission_run: could not allocate the lanes' start-image lines");
 	if (st) return st;
 	ctx->run_blk_shift = shift;
 	ctx->run_blocks = (long long)blocks;
@@ -2086,14 +1891,14 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	if (max_attempts < 1) max_attempts = 1;
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	if (ctx->producer < 0 && ctx->refl_per_launch < 0. && !ctx->in_probe && ne == 1 && n_slots >= 2000000) {
+	if (pc_wants_probe(ctx, n_slots)) {
 		/* first big run of the context: 32768 slots with the default kernel tell how long photons live here (3 ms, results unused) */
 		int st = pc_probe_lifetime(ctx, seed, slot0, max_attempts);
 		if (st != PC_HIP_OK) return st;
 	}
 	ctx->last_run_plain = 1;
 	ctx->leak_events_of_run = 0;
-	ctx->run_squares = ctx->weight_squares;
+	ctx->run_squares = ctx->opts.weight_squares;
 	ctx->last_call = PC_CALL_RUN;
 	pc_kargs a;
 	pc_fill_common(ctx, a);
@@ -2116,16 +1921,12 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	if (parts > PC_MAX_PARTS) parts = PC_MAX_PARTS;
 	if ((long long)parts > n_slots / 65536) parts = (int)(n_slots / 65536);
 	if (parts < 1) parts = 1;
-	hipStream_t main_stream = ctx->stream;
-	struct restore_ctx {          /* the launch helpers read the stream, the event flags and the scratch half from the context */
-		pc_hip_ctx *c; hipStream_t s;
-		~restore_ctx() { c->stream = s; c->rec_ev0 = c->rec_ev1 = true; c->scratch_halves = 1; c->scratch_half = 0; }
-	} restore{ctx, main_stream};
+	const hipStream_t main_stream = ctx->stream;
+	pc_launch_site site{main_stream};
 	/* launches in flight at the same time (parts on two streams) must not share per-lane scratch: two halves of it */
-	ctx->scratch_halves = (parts > 1) ? 2 : 1;
-	ctx->scratch_half = 0;
+	site.halves = (parts > 1) ? 2 : 1;
 	if (compact) {
-		int st = pc_compact_prepare(ctx, n_slots);
+		int st = pc_compact_prepare(ctx, n_slots, site.halves);
 		if (st) return st;
 		a.img_cursor = ctx->d_cursor;
 		a.img_ids = ctx->slot_ids ? ctx->d_ids : nullptr;
@@ -2156,7 +1957,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		PC_HIP_CHECK(hipEventRecord(ctx->ev0, main_stream));
 		PC_HIP_CHECK(hipEventRecord(ctx->ev_sync, main_stream));
 		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_sync, 0));     /* totals and counters are zero */
-		ctx->rec_ev0 = ctx->rec_ev1 = false;
+		site.record_ev0 = site.record_ev1 = false;
 	}
 	for (int k = 0; k < parts && status == PC_HIP_OK; k++) {
 		const long long lo = pc_part_begin(n_slots, parts, k), hi = pc_part_begin(n_slots, parts, k + 1);
@@ -2164,24 +1965,22 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		pc_set_img(ctx, a, compact ? 0 : lo, n_slots, keep_images != 0, planes);      /* compact: positions are the run's, not the part's */
 		if (parts > 1) {
 			a.work = ctx->d_work + k;
-			ctx->stream = (k & 1) ? ctx->stream2 : main_stream;
-			ctx->scratch_half = k & 1;       /* the launch before and the one after run on the other stream: the other half */
+			site.stream = (k & 1) ? (hipStream_t)ctx->stream2 : main_stream;
+			site.half = k & 1;               /* the launch before and the one after run on the other stream: the other half */
 			if (compact) {
 				a.lane_start = ctx->d_lane_start + (size_t)(k & 1)*8*pc_lane_start_lanes(ctx);
 				a.img_id0 = lo;           /* slot ids are the run's */
 			}
 		}
-		if (compact) ctx->rec_ev1 = false;       /* the kernel time ends behind the tail kernel below */
-		status = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, a, hi - lo)
-		                                  : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, a, hi - lo);
+		if (compact) site.record_ev1 = false;    /* the kernel time ends behind the tail kernel below */
+		status = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, site, a, hi - lo)
+		                                  : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, site, a, hi - lo);
 		ctx->part_end[k] = hi;
 		if (status == PC_HIP_OK && parts > 1) {
 			PC_HIP_CHECK(ctx->ev_part[k].ensure());
-			PC_HIP_CHECK(hipEventRecord(ctx->ev_part[k], ctx->stream));
+			PC_HIP_CHECK(hipEventRecord(ctx->ev_part[k], site.stream));
 		}
 	}
-	ctx->stream = main_stream;
-	ctx->scratch_half = 0;
 	if (parts > 1 && status == PC_HIP_OK) {
 		/* the main stream ends after every part: wait() synchronises it, and the kernel time runs to here */
 		for (int k = 0; k < parts; k++)
@@ -2217,7 +2016,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	ctx->run_planes = 0;
 	ctx->last_run_plain = 0;
 	ctx->leak_events_of_run = 1;
-	ctx->run_squares = ctx->weight_squares;
+	ctx->run_squares = ctx->opts.weight_squares;
 	ctx->leak_seed = seed; ctx->leak_slot0 = slot0; ctx->leak_n_slots = n_slots;
 	ctx->leak_max_attempts = max_attempts; ctx->leak_keep_images = keep_images ? 1 : 0;
 	/* record buffer: events per slot grow with the number of energies (a leak is kept while ANY energy holds >= 1e-4):
@@ -2851,12 +2650,10 @@ static int pc_leak_auto_order(pc_hip_ctx *ctx)
 	a.slot0 = ctx->leak_slot0; a.n_slots = n;
 	pc_set_img(ctx, a, 0, n, false, false);
 	a.work_est = ctx->d_work_est;
-	struct restore_ctx {          /* the lane kernel, no events of its own */
-		pc_hip_ctx *c; int producer, pool;
-		~restore_ctx() { c->producer = producer; c->pool = pool; c->rec_ev0 = c->rec_ev1 = true; }
-	} restore{ctx, ctx->producer, ctx->pool};
-	ctx->producer = 0; ctx->pool = 0; ctx->rec_ev0 = ctx->rec_ev1 = false;
-	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, a, n) : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, a, n);
+	pc_launch_site site{ctx->stream};     /* the lane kernel, no events of its own */
+	site.record_ev0 = site.record_ev1 = false;
+	site.force_lane = true;
+	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, site, a, n) : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, site, a, n);
 	if (st) return st;
 	std::vector<unsigned int> est((size_t)n);
 	PC_HIP_CHECK(hipMemcpyAsync(est.data(), ctx->d_work_est, (size_t)n*sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));

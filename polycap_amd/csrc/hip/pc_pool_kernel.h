@@ -21,16 +21,8 @@
 #ifndef PC_POOL_KERNEL_H
 #define PC_POOL_KERNEL_H
 
-#ifndef PQ_BLOCK
-#define PQ_BLOCK 768       /* one workgroup per CU */
-#endif
 #ifndef PQ_MIN_WAVES
 #define PQ_MIN_WAVES 3     /* waves per SIMD the register allocator leaves room for */
-#endif
-#define PQ_WAVES (PQ_BLOCK / PC_WAVE)
-#define PQ_PITCH 1024
-#ifndef PQ_P
-#define PQ_P 64            /* parked photons per wave (at most 64: one mask bit each) */
 #endif
 #ifndef PQ_UNROLL
 #define PQ_UNROLL 16        /* march steps between two top-ups of the wave (2: 32.0 ms, 4: 30.3, 8: 29.4, 12-24: 29.0, 32: 29.6:

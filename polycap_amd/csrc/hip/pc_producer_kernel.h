@@ -24,13 +24,7 @@
 #ifndef PC3_ROUTE_BND
 #define PC3_ROUTE_BND 1       /* photons of boundary capillaries are handed to the last tracing wave (see producer_step) */
 #endif
-#ifndef PC3_BLOCK
-#define PC3_BLOCK 1024         /* one workgroup per CU: 1 launching + 15 tracing waves, the tables once in LDS */
-#endif
-#define PC3_WAVES (PC3_BLOCK / PC_WAVE)
-#define PC3_CONSUMERS (PC3_WAVES - 1)
 #define PC3_MAXCONS PC3_WAVES
-#define PC3_PITCH 1024
 #ifndef PC3_CAP
 #define PC3_CAP 28            /* launched photons waiting per tracing wave */
 #endif
@@ -39,8 +33,6 @@
 #define PC3_DFIELDS 13        /* P, d, e (9), dtravel, weight, (slot, attempt), (reflections, return code) */
 #define PC3_MAX_POLLS 4000000
 #define PC3_MAX_OUTSTANDING (PC3_CONSUMERS*(PC_WAVE + PC3_CAP) + 20)
-#define PC3_MIN_REFL 4.0      /* option "producer" = -1: reflections per launch from which this kernel is used (xos1 at 10-30 keV: 26-12,
-                               * always 10-16 % faster; cone.inp: 0.3, 2x slower; scripts/analysis/producer_crossover.py) */
 #ifndef PC3_SLEEP
 #define PC3_SLEEP 127          /* the launching wave waits for room in the rings 90 % of the time: long naps (8128 clocks) */
 #endif

@@ -322,7 +322,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 	b->img_valid = 0; b->leak_events_of_run = 0; b->last_run_plain = 0;
 	b->last_call = PC_CALL_NONE;
 	b->run_planes = 0; b->run_compact = 0; b->n_parts = 1; b->run_pending = 0; b->run_slots = 0;
-	b->run_squares = b->weight_squares;
+	b->run_squares = b->opts.weight_squares;
 	b->last_ms = 0.f;
 	const size_t nw_a = (size_t)((n_a + 63)/64);
 	st = b->d_relay_scan.grow(nw_a + 1 + 8, "pc_hip_relay_run: could not allocate the compaction counters");
@@ -348,7 +348,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
 		st = pc_batch_trace(b, bt, 0);
 		if (st) return st;
-		b->run_squares = b->weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
+		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
 		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
 		if (st) return st;
 		st = b->d_img.grow(((size_t)PC_N_FIELDS + (size_t)ne) * (size_t)std::max<long long>(n_out, 1), "pc_hip_relay_run: could not allocate the image records");
@@ -356,11 +356,11 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
 		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
 		unsigned long long *sumw = (unsigned long long *)(b->d_totals + 1);
-		unsigned long long *sumw2 = b->weight_squares ? sumw + 2*(size_t)ne : nullptr;
+		unsigned long long *sumw2 = b->opts.weight_squares ? sumw + 2*(size_t)ne : nullptr;
 		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
 		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
 		long long grid = (n_in + 255)/256;
-		if (grid > 8ll*pc_cus(b)) grid = 8ll*pc_cus(b);
+		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
 		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
 		hipLaunchKernelGGL(pc_relay_finish_kernel, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
 		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->d_img,

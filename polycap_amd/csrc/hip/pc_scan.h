@@ -32,31 +32,8 @@ static int pc_scan_check(const char *fn, const pc_hip_scan_point *pts, int64_t n
 	return PC_HIP_OK;
 }
 
-/* one launch: NE = 1, 4, 8 (weights in registers) or 0 (any count, weights in the scan's own per-lane scratch) */
-template <int NE, int MODE>
-static int pc_scan_launch(pc_hip_ctx *ctx, const pc_kargs &a, int grid, int block, size_t dyn, bool sq)
-{
-	if (ctx->host.pm.nmax + 1 <= 1024) {
-		if (sq) hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, true>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-		else hipLaunchKernelGGL((pc_trace_kernel<NE, MODE, 1024, false>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	} else if (NE <= 1) {
-		if (sq) hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, true>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-		else hipLaunchKernelGGL((pc_trace_kernel<(NE <= 1 ? NE : 0), MODE, PC_MAX_PITCH, false>), dim3(grid), dim3(block), dyn, ctx->stream, a);
-	} else
-		return pc_fail(PC_HIP_ERR_INVALID, "internal: register-weight kernels are built for profiles of up to 1024 points");
-	PC_HIP_CHECK(hipGetLastError());
-	return PC_HIP_OK;
-}
-
-template <int MODE>
-static int pc_scan_launch_kne(pc_hip_ctx *ctx, int kne, const pc_kargs &a, int grid, int block, size_t dyn, bool sq)
-{
-	return (kne == 1) ? pc_scan_launch<1, MODE>(ctx, a, grid, block, dyn, sq) : (kne == 4) ? pc_scan_launch<4, MODE>(ctx, a, grid, block, dyn, sq)
-	     : (kne == 8) ? pc_scan_launch<8, MODE>(ctx, a, grid, block, dyn, sq) : pc_scan_launch<0, MODE>(ctx, a, grid, block, dyn, sq);
-}
-
-/* device buffers of a scan of n_points points and up to `lanes` lanes (kne == 0: per-lane weights) */
-static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points, size_t wscratch_elems)
+/* device buffers of a scan of n_points points (the per-lane weights of more than 8 energies: pc_launch_planned) */
+static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points)
 {
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	int st = ctx->d_scan_totals.grow(1, "pc_hip_scan_run: could not allocate the scan totals");
@@ -65,7 +42,6 @@ static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points, size_t wscratch_el
 	PC_HIP_CHECK(ctx->ev_scan1.ensure(hipEventDefault));
 	st = ctx->d_scan_pts.grow((size_t)n_points, "pc_hip_scan_run: could not allocate the point table");
 	if (!st) st = ctx->d_scan_tot.grow((size_t)n_points*pc_scan_stride(ne), "pc_hip_scan_run: could not allocate the per-point totals");
-	if (!st) st = ctx->d_scan_wscratch.grow(wscratch_elems, "pc_hip_scan_run: could not allocate the per-lane weight scratch");
 	return st;
 }
 
@@ -119,16 +95,7 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_sync, 0));
 	}
 	const int ne = ctx->host.pm.n_energies;
-	const int npts = ctx->host.pm.nmax + 1;
-	/* weights in registers for up to 8 energies (kernels NE = 1, 4, 8), in the scan's per-lane scratch beyond */
-	const int kne = (ne == 1) ? 1 : ((ne <= 4 && npts <= 1024) ? 4 : ((ne <= 8 && npts <= 1024) ? 8 : 0));
-	const long long max_blocks = (long long)pc_cus(ctx) * ((kne == 0) ? 1 : ctx->blocks_per_cu);
-	const int block = ctx->block_size;
-	const long long want_blocks = (count + block - 1) / block;
-	int grid = (int)(want_blocks < max_blocks ? want_blocks : max_blocks);
-	if (grid < 1) grid = 1;
-	const size_t wscratch = (kne == 0) ? (size_t)ne * (size_t)grid * (size_t)block : 0;
-	st = pc_scan_buffers(ctx, n_points, wscratch);
+	st = pc_scan_buffers(ctx, n_points);
 	if (st) return st;
 	PC_HIP_CHECK(hipMemcpy(ctx->d_scan_pts, points, (size_t)n_points*sizeof(pc_scan_point), hipMemcpyHostToDevice));
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_totals, 0, sizeof(pc_totals), ctx->stream));
@@ -144,21 +111,16 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	a.img_id0 = first;
 	a.img_n = n_per_point;
 	a.seed = seed; a.slot0 = slot0; a.n_slots = count; a.max_attempts = max_attempts; a.keep_images = 0;
-	a.lds_acc = 0;
-	a.lds_ec = (kne == 0 && ctx->lds_ec && npts <= 1024 && 48*(size_t)ne <= 28672) ? 1 : 0;
-	a.sweep_rough = 0;
-	for (const pc_energy_const &c : ctx->host.ec) if (c.rough_c != 0.) a.sweep_rough = 1;
-	a.total_threads = (long long)grid * block;
-	if (kne == 0) a.wscratch = ctx->d_scan_wscratch;
-	const size_t dyn = (kne == 0) ? pc_ne0_dyn_lds((size_t)ne, 0, a.lds_ec, 0) : 0;
-	const bool sq = ctx->weight_squares != 0;
+	/* the lane kernel in its scan mode (pc_plan_launch), between the scan's own events */
+	pc_launch_site site{ctx->stream};
+	site.record_ev0 = site.record_ev1 = false;
 	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan0, ctx->stream));
-	st = ctx->host.pm.generic_src ? pc_scan_launch_kne<PC_MODE_SCAN_GENERIC>(ctx, kne, a, grid, block, dyn, sq)
-	                              : pc_scan_launch_kne<PC_MODE_SCAN_CIRCULAR>(ctx, kne, a, grid, block, dyn, sq);
+	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SCAN_GENERIC>(ctx, site, a, count)
+	                              : pc_launch_kernel<PC_MODE_SCAN_CIRCULAR>(ctx, site, a, count);
 	if (st) return st;
 	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan1, ctx->stream));
 	ctx->scan_points = n_points;
-	ctx->scan_squares = sq ? 1 : 0;
+	ctx->scan_squares = ctx->opts.weight_squares ? 1 : 0;
 	ctx->scan_pending = 1;
 	return PC_HIP_OK;
 }

@@ -53,17 +53,9 @@
  *   registers.  Two waves per SIMD (512-thread workgroups), 239 registers, no scratch; the FAST loop evaluates two reflections
  *     per step as two interleaved dependent chains (pc_fresnel3xN).
  */
-#ifndef PCS_BLOCK
-#define PCS_BLOCK 512          /* 8 waves per CU, 2 per SIMD: 256 registers per lane (at 3 per SIMD and 168 registers a hundred of them lived in
-                                * scratch, on the path of every EVENT phase: 28.9 against 28.2 ms at 291 energies, 18.1 against 15.4 ms at 100:
-                                * profiles/r04/kernel_history.md); the sweeps keep the SIMD busy with two interleaved chains per wave */
-#endif
 #ifndef PCS_WAVES
 #define PCS_WAVES 2
 #endif
-#define PCS_PITCH 1024
-#define PCS_MAXPS 16           /* photons of a wave swept in one round (their logs are staged in LDS) */
-#define PCS_ENT 4              /* doubles of a staged log entry: cos sqrt(2), cos^2, fs, fp */
 #define PCS_DEAD 5.421010862427522e-20    /* 2^-64 */
 #ifndef PCS_CHAINS
 #define PCS_CHAINS 2           /* reflections the FAST loop takes per step (pc_fresnel3xN: that many interleaved chains) */
@@ -72,13 +64,7 @@
 #define PCS_LEASH 4            /* reflections between sweeps of a photon whose proxies are dead but which a sweep found alive */
 #endif
 
-/* dynamic LDS of pc_trace_log_kernel: exact sums (with `squares`, those of the squared weights too), per-energy constants
- * (5 fields), per wave the sweep tables (4 x 16 words + 16 doubles) and `stage` doubles of staged logs */
-static size_t pcs_dyn_lds(size_t ne, int block, size_t stage_doubles_per_wave, bool squares)
-{
-	return (squares ? 4 : 2)*ne*sizeof(unsigned long long) + 5*ne*sizeof(double)
-	     + (size_t)(block/PC_WAVE)*(4*PCS_MAXPS*sizeof(unsigned int) + PCS_MAXPS*sizeof(double) + stage_doubles_per_wave*sizeof(double));
-}
+static_assert(sizeof(pc_marg4) == PCS_MARG_BYTES, "pc_log_stage_doubles (pc_plan.h) counts the certificates in LDS");
 
 template <int MODE, bool SQ = false>
 __global__ void __launch_bounds__(PCS_BLOCK, PCS_WAVES)

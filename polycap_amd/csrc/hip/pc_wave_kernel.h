@@ -11,8 +11,6 @@
 #ifndef PC_WAVE_KERNEL_H
 #define PC_WAVE_KERNEL_H
 
-#define PCW_BLOCK 256
-
 template <int MODE>
 __global__ void __launch_bounds__(PCW_BLOCK, 4)
 pc_trace_wave_kernel(pc_kargs a)
