@@ -345,6 +345,83 @@ POLYCAP_EXTERN void pc_hip_beam_params(size_t n_energies, const uint64_t *sums, 
 POLYCAP_EXTERN void pc_hip_beam_at(size_t n_energies, const uint64_t *sums, size_t n_distances, const double *distances, double *out);
 /* the 26 column names of pc_hip_beam_params, comma-separated */
 POLYCAP_EXTERN const char *pc_hip_beam_columns(void);
+/* ---- histograms: weighted 1-D histograms of per-entry scalar quantities of the last run, one per axis and selected energy,
+ * accumulated on the device in exact integers from what the run left there (pc_hist.h): line and radial profiles of the focal
+ * spot at any bin width (full width at half maximum, encircled-energy radii), the distributions of reflection count and path
+ * length per energy, the z of the leak events, the entrance radii that transmit.  One pass reads every entry once for all axes.
+ *
+ * The contract (IEEE fp64, evaluated in the order written, no contraction):
+ *   entries    those pc_hip_spot_add reads: exit photons (kind 0; the records of a relay into the context count here), extleak (1)
+ *              and intleak (2) events of a leak_calc run.  Sums are kept per kind.
+ *   per entry  with position (x, y, z), direction (dx, dy, dz) and weights w[e]:
+ *              exit photons: dz = sqrt((1 - dx*dx) - dy*dy); leak events: the stored dz
+ *   value v    of an axis with quantity Q, distance d, centre (cx, cy); zp = z[nmax] + d, computed once on the host:
+ *              X_AT       t = (zp - z) / dz,  v = x + dx*t
+ *              Y_AT       v = y + dy*t
+ *              R_AT       a = (x + dx*t) - cx,  b = (y + dy*t) - cy,  v = sqrt(a*a + b*b)
+ *              SLOPE_X    v = dx / dz;    SLOPE_Y    v = dy / dz;    TAN_THETA  v = sqrt(dx*dx + dy*dy) / dz
+ *              N_REFL     v = (double)n: exit photons, the int64 pc_exit_nrefl; leak events, the record's n_refl
+ *              D_TRAVEL   v = pc_exit_dtravel (exit photons only)
+ *              R_START    v = sqrt(sx*sx + sy*sy) of pc_start_coords (exit photons only)
+ *              Z          v = z
+ *   bin        f = ((v - lo) / (hi - lo)) * n_bins; inside when 0 <= f < n_bins, bin = floor(f).  Anything else is outside: NaN,
+ *              !(dz > 0) for the six quantities that use dz, off the range, D_TRAVEL and R_START on a leak kind
+ *   weights    W = round_half_even(w[e] * 2^32) as uint64, 0 for w <= 0 and NaN (the spot maps' q(w)); a bin holds the sum of W
+ *              over its entries, and every (kind, axis, energy) has one outside counter for the rest, so that for each of them
+ *              sum(bins) + outside == sum over the kind's entries of W, exactly
+ *   entries    one kind takes at most 2^32 - 1 entries over all adds (then no uint64 can wrap); an add past that fails
+ * Sums are integer sums: they depend neither on launch shape ("run_parts", compact or slot order, records or planes, the kernel that
+ * traced the run, the regime), nor on how the slots were split into consecutive runs added to one object, nor on the device count.
+ * Output layout: bins [3][n_selected][total_bins] with the axes one after the other (total_bins = sum of n_bins), outside
+ * [3][n_axes][n_selected], n_entries [3].
+ *
+ * Host helpers on the bins of one (kind, axis, energy), c(b) = lo + ((b + 0.5) / n_bins) * (hi - lo) the centre of bin b:
+ *   quantile   T = sum(bins) in integers (the inside weight only); NaN when T == 0 or q is not in [0, 1].  target = q * dbl(T);
+ *              b = the first non-empty bin with dbl(C_b) >= target, C_b = bins[0] + .. + bins[b] in integers;
+ *              frac = (target - dbl(C_b - bins[b])) / dbl(bins[b]);  result = lo + ((b + frac) / n_bins) * (hi - lo)
+ *              (hi when no bin qualifies)
+ *   fwhm       p = the first bin of maximal count, half = dbl(bins[p]) / 2.0; i = the first bin below p, walking down, with
+ *              dbl(bins[i]) < half; j likewise above p.  NaN (also *left, *right) when the histogram is empty or a walk reaches
+ *              the end of the axis.  left = c(i) + (c(i+1) - c(i)) * ((half - bins[i]) / (bins[i+1] - bins[i])),
+ *              right = c(j) + (c(j-1) - c(j)) * ((half - bins[j]) / (bins[j-1] - bins[j])), counts as doubles; result = right - left */
+enum { PC_HIP_HIST_X_AT = 0, PC_HIP_HIST_Y_AT, PC_HIP_HIST_R_AT, PC_HIP_HIST_SLOPE_X, PC_HIP_HIST_SLOPE_Y,
+       PC_HIP_HIST_TAN_THETA, PC_HIP_HIST_N_REFL, PC_HIP_HIST_D_TRAVEL, PC_HIP_HIST_R_START, PC_HIP_HIST_Z };
+typedef struct {
+	int32_t quantity;             /* PC_HIP_HIST_* */
+	double d, cx, cy;             /* cm behind the exit face (X_AT, Y_AT, R_AT; 0 elsewhere), centre (R_AT; 0 elsewhere): finite, d >= 0 */
+	double lo, hi;                /* range: finite, lo < hi */
+	int32_t n_bins;               /* >= 1 */
+} pc_hip_hist_axis;
+typedef struct {
+	int32_t n_axes;               /* 1 .. 16 */
+	const pc_hip_hist_axis *axes;
+	int32_t n_energies;           /* selected energies: 0 = all, in order; (sum of n_bins) * n_selected <= 2^24 */
+	const int32_t *energies;      /* [n_energies] distinct indices into the problem's energies */
+	int32_t regime;               /* 0 automatic (pc_hist.h); 1 workgroup-private LDS histograms, 2 energies across lanes */
+} pc_hip_hist_spec;
+typedef struct pc_hip_hist pc_hip_hist;
+/* PC_HIP_ERR_INVALID with a message that names the field unless the spec is valid for a problem of n_energies energies (no device
+ * is touched) */
+POLYCAP_EXTERN int pc_hip_hist_validate(const pc_hip_hist_spec *spec, size_t n_energies);
+/* Empty histograms for all three kinds on the context's device (the context must outlive them).  The group variant keeps one set
+ * per member; reading it adds the members' sums exactly on the host. */
+POLYCAP_EXTERN int pc_hip_hist_create(pc_hip_ctx *ctx, const pc_hip_hist_spec *spec, pc_hip_hist **hist);
+POLYCAP_EXTERN int pc_hip_group_hist_create(pc_hip_group *group, const pc_hip_hist_spec *spec, pc_hip_hist **hist);
+POLYCAP_EXTERN void pc_hip_hist_destroy(pc_hip_hist *hist);
+/* Adds the entries of kind 0, 1 or 2 of the last run, as pc_hip_spot_add: enqueued on the context's stream behind the run; leak kinds
+ * wait for the run first (its events are ordered when it is waited for).  Anything else is PC_HIP_ERR_INVALID. */
+POLYCAP_EXTERN int pc_hip_hist_add(pc_hip_hist *hist, int kind);
+/* bins [3][n_selected][total_bins], outside [3][n_axes][n_selected], n_entries [3] (any may be NULL); waits for the adds */
+POLYCAP_EXTERN int pc_hip_hist_read(pc_hip_hist *hist, uint64_t *bins, uint64_t *outside, int64_t *n_entries);
+POLYCAP_EXTERN int pc_hip_hist_reset(pc_hip_hist *hist);
+/* dims = {n_axes, n_selected, total_bins}; offsets [n_axes + 1] (optional): axis a has the bins [offsets[a], offsets[a + 1]) of an
+ * energy's row; *regime (optional) = the regime in use, 1 or 2 */
+POLYCAP_EXTERN int pc_hip_hist_info(const pc_hip_hist *hist, int32_t dims[3], int32_t *offsets, int *regime);
+/* host only, on bins [n_bins] of one (kind, axis, energy): the value below which the fraction q of the inside weight lies (outside,
+ * that histogram's outside counter, is not used: the quantile is that of what the range holds) */
+POLYCAP_EXTERN double pc_hip_hist_quantile(int32_t n_bins, double lo, double hi, const uint64_t *bins, uint64_t outside, double q);
+/* host only: the full width at half maximum; *left and *right (optional) = where the profile crosses half its maximum */
+POLYCAP_EXTERN double pc_hip_hist_fwhm(int32_t n_bins, double lo, double hi, const uint64_t *bins, double *left, double *right);
 /* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
  * a focusing optic) in one launch, with exact totals per point.
  *
@@ -510,6 +587,16 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_moments(void *efficiencies, 
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_beam(void *efficiencies, int kind, size_t *n_energies, double **params, void *error);
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_beam_sums(void *efficiencies, int kind, size_t *n_energies, uint64_t **sums,
 	uint64_t **outside, int64_t *n_entries, void *error);
+
+/* Histograms of a result made with POLYCAP_HIST set (every path of the call that POLYCAP_BEAM serves), e.g.
+ * POLYCAP_HIST="axis=x,d=0.5,range=-0.01:0.01,bins=2048;axis=r,d=0.5,centre=0:0,range=0:0.02,bins=1024;axis=nrefl,range=0:256,bins=256;energies=all"
+ * (axes: x y r slope_x slope_y tan_theta nrefl dtravel r_start z; cm; energies as in POLYCAP_SPOT).  kind 0 = exit photons, 1 =
+ * extleak, 2 = intleak (leak_calc runs).  dims = {n_axes, n_selected, total_bins}; copies, to be freed with polycap_free (any may be
+ * NULL): *offsets [n_axes + 1], *axes [n_axes], *energies [n_selected] keV, the exact sums *bins [n_selected][total_bins] and
+ * *outside [n_axes][n_selected] of pc_hip_hist_read, so that the results of several seeds pool exactly; *n_entries.  A result made
+ * without the variable is an error.  Returns 1, or 0 with *error (a polycap_error**) set. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_hist(void *efficiencies, int kind, int32_t dims[3], int32_t **offsets,
+	pc_hip_hist_axis **axes, double **energies, uint64_t **bins, uint64_t **outside, int64_t *n_entries, void *error);
 
 #ifdef __cplusplus
 }

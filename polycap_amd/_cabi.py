@@ -54,6 +54,18 @@ class SpotSpecS(C.Structure):
                 ("n_energies", C.c_int32), ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
 
 
+class HistAxisS(C.Structure):
+    """struct pc_hip_hist_axis"""
+    _fields_ = [("quantity", C.c_int32), ("d", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double), ("n_bins", C.c_int32)]
+
+
+class HistSpecS(C.Structure):
+    """struct pc_hip_hist_spec"""
+    _fields_ = [("n_axes", C.c_int32), ("axes", C.POINTER(HistAxisS)), ("n_energies", C.c_int32),
+                ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -227,6 +239,26 @@ def lib():
     L.pc_hip_beam_at.restype = None
     L.pc_hip_beam_columns.argtypes = []
     L.pc_hip_beam_columns.restype = C.c_char_p
+    L.pc_hip_hist_validate.argtypes = [P(HistSpecS), C.c_size_t]
+    L.pc_hip_hist_validate.restype = C.c_int
+    L.pc_hip_hist_create.argtypes = [C.c_void_p, P(HistSpecS), P(C.c_void_p)]
+    L.pc_hip_hist_create.restype = C.c_int
+    L.pc_hip_group_hist_create.argtypes = [C.c_void_p, P(HistSpecS), P(C.c_void_p)]
+    L.pc_hip_group_hist_create.restype = C.c_int
+    L.pc_hip_hist_destroy.argtypes = [C.c_void_p]
+    L.pc_hip_hist_destroy.restype = None
+    L.pc_hip_hist_add.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_hist_add.restype = C.c_int
+    L.pc_hip_hist_read.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), c_int64_p]
+    L.pc_hip_hist_read.restype = C.c_int
+    L.pc_hip_hist_reset.argtypes = [C.c_void_p]
+    L.pc_hip_hist_reset.restype = C.c_int
+    L.pc_hip_hist_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int)]
+    L.pc_hip_hist_info.restype = C.c_int
+    L.pc_hip_hist_quantile.argtypes = [C.c_int32, C.c_double, C.c_double, P(C.c_uint64), C.c_uint64, C.c_double]
+    L.pc_hip_hist_quantile.restype = C.c_double
+    L.pc_hip_hist_fwhm.argtypes = [C.c_int32, C.c_double, C.c_double, P(C.c_uint64), c_double_p, c_double_p]
+    L.pc_hip_hist_fwhm.restype = C.c_double
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
     u64p = P(C.c_uint64)

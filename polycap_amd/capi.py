@@ -131,6 +131,8 @@ def _lib():
         "pc_transmission_efficiencies_get_spot": (C.c_int, [vp, C.c_int, P(C.c_int32), P(_dp), _dp, P(_dp), P(_dp), P(_dp), epp]),
         "pc_transmission_efficiencies_get_stderr": (C.c_int, [vp, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_moments": (C.c_int, [vp, P(C.c_int64), P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
+        "pc_transmission_efficiencies_get_hist": (C.c_int, [vp, C.c_int, P(C.c_int32), P(P(C.c_int32)), P(P(_cabi.HistAxisS)), P(_dp),
+                                                            P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -470,6 +472,27 @@ class TransmissionEfficiencies(_LeakData):
         out = {name: rows[:, j].copy() for j, name in enumerate(beam_columns())}
         out.update(sums=_take(a, ne * 30, np.uint64).reshape(ne, 15, 2), outside=_take(b, ne, np.uint64), n_entries=int(ni.value))
         return out
+
+    def hist(self, kind="exit"):
+        """Histograms of a run made with POLYCAP_HIST set (extension, pc_transmission_efficiencies_get_hist): dict of the exact
+        sums bins uint64 [energies, total_bins] and outside uint64 [axes, energies], n_entries, offsets [axes + 1], energies (keV)
+        and axes, a list of dicts (axis, d, centre, range, bins).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        from .hip import HIST_QUANTITIES
+        L = _lib()
+        dims = (C.c_int32 * 3)()
+        o, a, e = C.POINTER(C.c_int32)(), C.POINTER(_cabi.HistAxisS)(), _dp()
+        b, u = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        ni = C.c_int64(0)
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_hist(self._h, self.SPOT_KINDS[kind], dims, C.byref(o), C.byref(a), C.byref(e), C.byref(b),
+                                                C.byref(u), C.byref(ni), C.byref(err))
+        _check(err)
+        na, ns, tb = (int(v) for v in dims)
+        axes = [dict(axis=HIST_QUANTITIES[a[k].quantity], d=a[k].d, centre=(a[k].cx, a[k].cy), range=(a[k].lo, a[k].hi), bins=a[k].n_bins)
+                for k in range(na)]
+        L.polycap_free(C.cast(a, C.c_void_p))
+        return dict(bins=_take(b, ns * tb, np.uint64).reshape(ns, tb), outside=_take(u, na * ns, np.uint64).reshape(na, ns),
+                    n_entries=int(ni.value), offsets=_take(o, na + 1, np.int32), energies=_take(e, ns), axes=axes)
 
     def _start(self):
         L = _lib()

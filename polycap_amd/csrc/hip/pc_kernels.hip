@@ -2609,6 +2609,7 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 #include "pc_group.h"
 #include "pc_spot.h"
 #include "pc_beam.h"
+#include "pc_hist.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
 

@@ -21,7 +21,10 @@
  *
  *   extensions: /Transmission_Efficiencies_StdErr (POLYCAP_STDERR=1), /Spot (POLYCAP_SPOT), and with POLYCAP_BEAM=1, for <K> in Exit,
  *   ExtLeak, IntLeak (the kinds the run has): /Beam/<K>_Sums [nE, 15, 2] uint64, /Beam/<K>_Outside [nE] uint64,
- *   /Beam/<K>_Entries [1] uint64 and /Beam/<K> [nE, 26] fp64 with a "Columns" attribute (include/polycap-hip.h)
+ *   /Beam/<K>_Entries [1] uint64 and /Beam/<K> [nE, 26] fp64 with a "Columns" attribute (include/polycap-hip.h); with POLYCAP_HIST
+ *   the groups /Hist/<K>: Axes [n_axes, 8] fp64 (Columns: quantity,d,cx,cy,lo,hi,n_bins,offset), Energies [nS] keV, Bins
+ *   [nS, total_bins] and Outside [n_axes, nS] uint64 (the exact sums), Entries [1] uint64, and Efficiency [nS, total_bins] with
+ *   Efficiency_Outside [n_axes, nS] fp64: per axis and energy they sum to the efficiency
  *
  * libhdf5 is bound at run time (dlopen), like xraylib in pc_optconst.c, so libpolycap.so carries no link-time
  * dependency on it: hosts without HDF5 get POLYCAP_ERROR_UNSUPPORTED from this one function and nothing else changes.
@@ -414,6 +417,69 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		}
 		free(rows);
 		if (!bok) goto close;
+	}
+
+	if (efficiencies->hist != NULL) {
+		/* extension: the exact histograms of POLYCAP_HIST (include/polycap-hip.h) and the same in efficiency units */
+		const struct pc_hist_result *hr = efficiencies->hist;
+		static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+		const size_t na = (size_t)hr->n_axes, ns = (size_t)hr->n_sel, tb = (size_t)hr->total_bins;
+		bool hok = pc_h5_group(file, "/Hist", error);
+		double *table = malloc(sizeof(double) * 8 * na), *sel_e = malloc(sizeof(double) * (ns ? ns : 1));
+		double *in = malloc(sizeof(double) * ns * tb), *out = malloc(sizeof(double) * na * ns);      /* all three are >= 1 */
+		hok = hok && table != NULL && sel_e != NULL && in != NULL && out != NULL;
+		for (size_t a = 0; hok && a < na; a++) {
+			const pc_hip_hist_axis *x = &hr->axes[a];
+			const double row[8] = { (double)x->quantity, x->d, x->cx, x->cy, x->lo, x->hi, (double)x->n_bins, (double)hr->offsets[a] };
+			memcpy(table + 8*a, row, sizeof row);
+		}
+		for (size_t k = 0; hok && k < ns; k++)
+			sel_e[k] = efficiencies->energies[hr->sel[k]];
+		for (int k = 0; k < 3 && hok; k++) {
+			if (hr->bins[k] == NULL)
+				continue;
+			char g[32], name[64];
+			snprintf(g, sizeof g, "/Hist/%s", names[k]);
+			hok = hok && pc_h5_group(file, g, error);
+			pc_hsize hd[2] = { (pc_hsize)na, 8 };
+			snprintf(name, sizeof name, "%s/Axes", g);
+			hok = hok && pc_h5_typed(file, 2, hd, name, *h5.native_double, table, "a.u., cm", "quantity,d,cx,cy,lo,hi,n_bins,offset", error);
+			hd[0] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Energies", g);
+			hok = hok && pc_h5_dataset(file, 1, hd, name, sel_e, "keV", error);
+			hd[0] = (pc_hsize)ns; hd[1] = (pc_hsize)tb;
+			snprintf(name, sizeof name, "%s/Bins", g);
+			hok = hok && pc_h5_typed(file, 2, hd, name, *h5.native_ullong, hr->bins[k], "2^-32", NULL, error);
+			hd[0] = (pc_hsize)na; hd[1] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Outside", g);
+			hok = hok && pc_h5_typed(file, 2, hd, name, *h5.native_ullong, hr->outside[k], "2^-32", NULL, error);
+			const uint64_t n_entries = (uint64_t)hr->n_entries[k];
+			pc_hsize one = 1;
+			snprintf(name, sizeof name, "%s/Entries", g);
+			hok = hok && pc_h5_typed(file, 1, &one, name, *h5.native_ullong, &n_entries, "a.u.", NULL, error);
+			/* efficiency[e] * S_bin / (S_inside + S_outside), the spot maps' normalisation: per axis and energy the bins and the
+			 * outside part sum to the efficiency */
+			for (size_t a = 0; hok && a < na; a++)
+				for (size_t s = 0; s < ns; s++) {
+					const uint64_t *b = hr->bins[k] + s*tb + (size_t)hr->offsets[a];
+					const size_t nb = (size_t)(hr->offsets[a + 1] - hr->offsets[a]);
+					uint64_t total = hr->outside[k][a*ns + s];
+					for (size_t j = 0; j < nb; j++)
+						total += b[j];
+					const double eff_e = efficiencies->efficiencies[hr->sel[s]], tot = (double)total;
+					for (size_t j = 0; j < nb; j++)
+						in[s*tb + (size_t)hr->offsets[a] + j] = total ? eff_e * (double)b[j] / tot : 0.;
+					out[a*ns + s] = total ? eff_e * (double)hr->outside[k][a*ns + s] / tot : 0.;
+				}
+			hd[0] = (pc_hsize)ns; hd[1] = (pc_hsize)tb;
+			snprintf(name, sizeof name, "%s/Efficiency", g);
+			hok = hok && pc_h5_dataset(file, 2, hd, name, in, "a.u.", error);
+			hd[0] = (pc_hsize)na; hd[1] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Efficiency_Outside", g);
+			hok = hok && pc_h5_dataset(file, 2, hd, name, out, "a.u.", error);
+		}
+		free(table); free(sel_e); free(in); free(out);
+		if (!hok) goto close;
 	}
 
 	if (!pc_h5_group(file, "/Input", error)) goto close;

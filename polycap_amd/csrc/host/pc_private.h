@@ -143,6 +143,17 @@ struct pc_beam_result {
 	int64_t n_entries[3];
 };
 
+/* extension: exact histograms of a run made with POLYCAP_HIST set (pc_transmission_efficiencies_get_hist) */
+struct pc_hist_result {
+	int32_t n_axes, n_sel, total_bins;
+	pc_hip_hist_axis *axes;    /* [n_axes] */
+	int32_t *offsets;          /* [n_axes + 1] */
+	int32_t *sel;              /* [n_sel] energy indices */
+	uint64_t *bins[3];         /* exit photons, extleak, intleak: [energy][total_bins], NULL when the run has none */
+	uint64_t *outside[3];      /* [axis][energy] */
+	int64_t n_entries[3];
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -152,6 +163,7 @@ struct _polycap_transmission_efficiencies {
 	int synthetic_constants;   /* extension: see pc_transmission_efficiencies_synthetic */
 	struct pc_spot_result *spot;
 	struct pc_beam_result *beam;
+	struct pc_hist_result *hist;
 	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
 	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
 	int64_t n_started;
@@ -207,5 +219,6 @@ pc_hip_group *pc_group_for(pc_ctx_cache *c, polycap_description *description, si
 void pc_set_hip_error(polycap_error **error, const char *caller, int status);
 void pc_spot_result_free(struct pc_spot_result *spot);
 void pc_beam_result_free(struct pc_beam_result *beam);
+void pc_hist_result_free(struct pc_hist_result *hist);
 
 #endif

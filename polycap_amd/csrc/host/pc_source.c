@@ -473,6 +473,131 @@ static int pc_spot_request_parse(struct pc_spot_request *r, size_t n_energies, p
 	return 0;
 }
 
+/* POLYCAP_HIST, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=2048;axis=r,d=0.5,centre=0:0,range=0:0.02,bins=1024;axis=nrefl,range=0:256,bins=256;energies=all":
+ * histograms of the run (include/polycap-hip.h, pc_hip_hist_*).  Items are separated by ';': an axis (comma-separated key=value
+ * pairs, the first being axis=NAME) or energies= as in POLYCAP_SPOT.  Parsed and validated before any device is used. */
+struct pc_hist_request {
+	int set;
+	pc_hip_hist_axis axes[17];
+	int n_axes;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_hist_spec spec;
+};
+
+static int pc_hist_parse_pair(const char *v, double *a, double *b)
+{
+	char *end = NULL;
+	errno = 0;
+	*a = strtod(v, &end);
+	if (end == v || errno != 0 || *end != ':')
+		return -1;
+	v = end + 1;
+	*b = strtod(v, &end);
+	return (end == v || errno != 0 || *end != '\0') ? -1 : 0;
+}
+
+static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax)
+{
+	static const char *names[] = { "x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z" };
+	int have_axis = 0, have_range = 0, have_bins = 0;
+	char *save = NULL;
+	memset(ax, 0, sizeof(*ax));
+	for (char *kv = strtok_r(item, ",", &save); kv != NULL; kv = strtok_r(NULL, ",", &save)) {
+		char *eq = strchr(kv, '=');
+		if (eq == NULL)
+			return "every part of an axis must be key=value";
+		*eq = '\0';
+		const char *v = eq + 1;
+		char *end = NULL;
+		if (strcmp(kv, "axis") == 0) {
+			ax->quantity = -1;
+			for (int q = 0; q < 10; q++)
+				if (strcmp(v, names[q]) == 0)
+					ax->quantity = q;
+			if (ax->quantity < 0)
+				return "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z";
+			have_axis = 1;
+		} else if (strcmp(kv, "d") == 0) {
+			errno = 0;
+			ax->d = strtod(v, &end);
+			if (end == v || errno != 0 || *end != '\0')
+				return "d must be a distance in cm";
+		} else if (strcmp(kv, "centre") == 0) {
+			if (pc_hist_parse_pair(v, &ax->cx, &ax->cy) != 0)
+				return "centre must be CX:CY in cm";
+		} else if (strcmp(kv, "range") == 0) {
+			if (pc_hist_parse_pair(v, &ax->lo, &ax->hi) != 0)
+				return "range must be LO:HI";
+			have_range = 1;
+		} else if (strcmp(kv, "bins") == 0) {
+			const long n = strtol(v, &end, 10);
+			if (end == v || *end != '\0' || n < 0 || n > 1 << 24)
+				return "bins must be a count";
+			ax->n_bins = (int32_t)n;
+			have_bins = 1;
+		} else {
+			return "unknown key of an axis (axis, d, centre, range, bins)";
+		}
+	}
+	return (have_axis && have_range && have_bins) ? NULL : "an axis needs axis, range and bins";
+}
+
+static int pc_hist_request_parse(struct pc_hist_request *r, size_t n_energies, polycap_error **error)
+{
+	memset(r, 0, sizeof(*r));
+	const char *env = getenv("POLYCAP_HIST");
+	if (env == NULL)
+		return 0;
+	r->set = 1;
+	char *buf = strdup(env), *save = NULL;
+	const char *bad = NULL;
+	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save)) {
+		if (strncmp(item, "axis=", 5) == 0) {
+			if (r->n_axes >= 17) { bad = "at most 16 axes"; break; }
+			bad = pc_hist_parse_axis(item, &r->axes[r->n_axes++]);
+		} else if (strncmp(item, "energies=", 9) == 0) {
+			const char *v = item + 9;
+			free(r->energies);
+			r->energies = NULL;
+			r->n_energies = 0;
+			if (strcmp(v, "all") == 0)
+				continue;
+			r->energies = malloc(sizeof(int32_t) * (n_energies + 1));
+			while (r->energies != NULL && *v != '\0') {
+				char *end = NULL;
+				const long e = strtol(v, &end, 10);
+				if (end == v || (size_t)r->n_energies > n_energies) { bad = "energies must be all or a list of energy indices"; break; }
+				r->energies[r->n_energies++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
+				v = end;
+				if (*v == ',') v++;
+				else if (*v != '\0') { bad = "energies must be all or a list of energy indices"; break; }
+			}
+			if (bad == NULL && r->n_energies == 0) bad = "energies must be all or a list of energy indices";
+		} else {
+			bad = "every item must be an axis (axis=NAME,...) or energies=";
+		}
+	}
+	free(buf);
+	if (bad == NULL && r->n_axes == 0)
+		bad = "at least one axis is needed";
+	if (bad == NULL) {
+		r->spec.n_axes = r->n_axes;
+		r->spec.axes = r->axes;
+		r->spec.n_energies = r->n_energies;
+		r->spec.energies = r->energies;
+		if (pc_hip_hist_validate(&r->spec, n_energies) != PC_HIP_OK)
+			bad = pc_hip_last_error();
+	}
+	if (bad != NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_HIST=%s: %s", env, bad);
+		free(r->energies);
+		r->energies = NULL;
+		return -1;
+	}
+	return 0;
+}
+
 /* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
 static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 {
@@ -483,12 +608,12 @@ static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 	}
 }
 
-/* POLYCAP_IMAGES=0 with spot maps or beam moments on one context: the exit data of the run stay on the device, and a run whose exit
+/* POLYCAP_IMAGES=0 with spot maps, beam moments or histograms on one context: the exit data of the run stay on the device, and a run whose exit
  * data would take more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by
  * (seed, slot): the same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is
- * added to the map and to the beam sums (either may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
+ * added to the map, to the beam sums and to the histograms (any may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
  * POLYCAP_STDERR) those of the squared weights. */
-static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
+static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, pc_hip_hist *hist, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
 	size_t ne, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	uint64_t *part = malloc(2*ne*sizeof(uint64_t));
@@ -506,6 +631,8 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam
 			st = pc_hip_spot_add(spot, 0);
 		if (st == PC_HIP_OK && beam != NULL)
 			st = pc_hip_beam_add(beam, 0);
+		if (st == PC_HIP_OK && hist != NULL)
+			st = pc_hip_hist_add(hist, 0);
 		if (st == PC_HIP_OK)
 			st = pc_hip_transmission_totals(ctx, NULL, c, part);
 		if (st != PC_HIP_OK)
@@ -598,6 +725,41 @@ static int pc_beam_store(polycap_transmission_efficiencies *eff, pc_hip_beam *be
 	return st;
 }
 
+/* the exact histograms of every kind the run has into the result */
+static int pc_hist_store(polycap_transmission_efficiencies *eff, pc_hip_hist *hist, const struct pc_hist_request *r, int leak_calc)
+{
+	int32_t dims[3];
+	int st = pc_hip_hist_info(hist, dims, NULL, NULL);
+	if (st != PC_HIP_OK)
+		return st;
+	const size_t na = (size_t)dims[0], ns = (size_t)dims[1], tb = (size_t)dims[2];
+	struct pc_hist_result *hr = eff->hist = calloc(1, sizeof(*hr));
+	if (hr == NULL)
+		return PC_HIP_ERR_MEMORY;
+	hr->n_axes = dims[0]; hr->n_sel = dims[1]; hr->total_bins = dims[2];
+	hr->axes = pc_beam_dup(r->axes, sizeof(pc_hip_hist_axis)*na);
+	hr->offsets = malloc(sizeof(int32_t)*(na + 1));
+	hr->sel = malloc(sizeof(int32_t)*(ns ? ns : 1));
+	uint64_t *bins = malloc(sizeof(uint64_t)*3*ns*tb), *out = malloc(sizeof(uint64_t)*3*na*ns);
+	if (hr->axes == NULL || hr->offsets == NULL || hr->sel == NULL || bins == NULL || out == NULL)
+		st = PC_HIP_ERR_MEMORY;
+	if (st == PC_HIP_OK)
+		st = pc_hip_hist_info(hist, dims, hr->offsets, NULL);
+	if (st == PC_HIP_OK)
+		st = pc_hip_hist_read(hist, bins, out, hr->n_entries);
+	for (size_t k = 0; st == PC_HIP_OK && k < ns; k++)
+		hr->sel[k] = r->n_energies ? r->energies[k] : (int32_t)k;
+	for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++) {
+		hr->bins[kind] = pc_beam_dup(bins + kind*ns*tb, sizeof(uint64_t)*ns*tb);
+		hr->outside[kind] = pc_beam_dup(out + kind*na*ns, sizeof(uint64_t)*na*ns);
+		if (hr->bins[kind] == NULL || hr->outside[kind] == NULL)
+			st = PC_HIP_ERR_MEMORY;
+	}
+	free(bins);
+	free(out);
+	return st;
+}
+
 /* the argument checks of the reference call, in its order: the message of the first one that fails, or NULL */
 static const char *pc_transmission_args_bad(const polycap_source *source, const polycap_progress_monitor *progress_monitor, int n_photons)
 {
@@ -629,6 +791,7 @@ struct pc_run_request {
 	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
 	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
 	struct pc_spot_request spot;
+	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
 	int devices[64], n_devices;
 	int keep_images;
 	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
@@ -644,6 +807,7 @@ struct pc_run_request {
 static void pc_run_request_free(struct pc_run_request *r)
 {
 	free(r->spot.energies);
+	free(r->hist.energies);
 }
 
 static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_calc, int n_photons, polycap_error **error)
@@ -664,7 +828,9 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 	r->beam_on = beam_env != NULL && strcmp(beam_env, "1") == 0;
 	if (pc_spot_request_parse(&r->spot, ne, error) != 0)
 		return -1;
-	if (r->beam_on && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the beam moments' chunked runs too */
+	if (pc_hist_request_parse(&r->hist, ne, error) != 0)
+		return -1;
+	if ((r->beam_on || r->hist.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and histograms too */
 		r->spot.share = 0.5;
 		const char *share = getenv("POLYCAP_SPOT_SHARE");
 		if (share != NULL && *share != '\0') {
@@ -707,10 +873,10 @@ struct pc_target {
 };
 
 /* Trace stage: with POLYCAP_SPOT the maps are made first (exit photons; leak runs also extleak and intleak), with POLYCAP_BEAM the
- * beam sums, then the options are set and the run is enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the
- * totals and moments, and added every range to spot[0] and *beam. */
+ * beam sums, with POLYCAP_HIST the histograms, then the options are set and the run is enqueued.  *chunked = 1 when pc_spot_chunked
+ * traced the run: it also read the totals and moments, and added every range to spot[0], *beam and *hist. */
 static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak_calc, uint64_t seed, int64_t n_photons, size_t ne,
-	pc_hip_spot *spot[3], pc_hip_beam **beam, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
+	pc_hip_spot *spot[3], pc_hip_beam **beam, pc_hip_hist **hist, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	int st = PC_HIP_OK;
 	int64_t chunk = 0;
@@ -719,8 +885,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 			st = t.group != NULL ? pc_hip_group_spot_create(t.group, &r->spot.spec, &spot[kind]) : pc_hip_spot_create(t.ctx, &r->spot.spec, &spot[kind]);
 	if (r->beam_on && st == PC_HIP_OK)
 		st = t.group != NULL ? pc_hip_group_beam_create(t.group, beam) : pc_hip_beam_create(t.ctx, beam);
-	if (r->spot.set || r->beam_on) {
-		/* POLYCAP_IMAGES=0 with spot maps or beam moments is chunked on one device only: a group traces the whole run at once */
+	if (r->hist.set && st == PC_HIP_OK)
+		st = t.group != NULL ? pc_hip_group_hist_create(t.group, &r->hist.spec, hist) : pc_hip_hist_create(t.ctx, &r->hist.spec, hist);
+	if (r->spot.set || r->beam_on || r->hist.set) {
+		/* POLYCAP_IMAGES=0 with spot maps, beam moments or histograms is chunked on one device only: a group traces the whole run at once */
 		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
 			uint64_t total_b = 0;
 			st = pc_hip_device_memory(t.ctx, NULL, &total_b);
@@ -744,10 +912,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		return st;
 	if (chunk > 0 && chunk < n_photons) {
 		*chunked = 1;
-		return pc_spot_chunked(t.ctx, spot[0], *beam, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
+		return pc_spot_chunked(t.ctx, spot[0], *beam, *hist, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
 	}
-	/* POLYCAP_SPOT, POLYCAP_BEAM: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
-	const int device_images = r->keep_images || r->spot.set || r->beam_on;
+	/* POLYCAP_SPOT, POLYCAP_BEAM, POLYCAP_HIST: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
+	const int device_images = r->keep_images || r->spot.set || r->beam_on || r->hist.set;
 	if (leak_calc)
 		return t.group != NULL ? pc_hip_group_run_leak(t.group, seed, n_photons, r->max_attempts, 1)
 		                       : pc_hip_transmission_run_leak(t.ctx, seed, 0, n_photons, r->max_attempts, 1);
@@ -796,6 +964,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	uint64_t *sum_fixed = NULL, *sum_fixed2 = NULL;      /* the exact moments A and B; B and the result's copy only with POLYCAP_STDERR */
 	pc_hip_spot *spot[3] = { NULL, NULL, NULL };         /* exit photons, extleak, intleak */
 	pc_hip_beam *beam = NULL;                            /* POLYCAP_BEAM: the exact beam sums of every kind */
+	pc_hip_hist *hist = NULL;                            /* POLYCAP_HIST: the exact histograms of every kind */
 	int64_t counters[6] = { 0, 0, 0, 0, 0, 0 };
 	int status = PC_HIP_OK, chunked = 0, reduced_by = 0;      /* a failed HIP call: its error is set at `out` */
 	double t_stage[6];
@@ -827,7 +996,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	const uint64_t seed = req.have_seed ? req.seed : source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
 	source->run_index++;
 
-	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
+	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &hist, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
 	t_stage[2] = t_stage[3] = pc_now_ms();
 	if (status == PC_HIP_OK && req.keep_images)
 		status = pc_fetch_images(t, eff, n_photons, &t_stage[3]);
@@ -855,6 +1024,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			status = pc_hip_spot_add(spot[kind], kind);
 	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && beam != NULL; kind++)
 		status = pc_hip_beam_add(beam, kind);
+	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && hist != NULL; kind++)
+		status = pc_hip_hist_add(hist, kind);
 	if (status != PC_HIP_OK)
 		goto out;
 
@@ -873,6 +1044,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			status = pc_spot_store(eff, spot[kind], &req.spot, kind);
 	if (status == PC_HIP_OK && beam != NULL)
 		status = pc_beam_store(eff, beam, leak_calc);
+	if (status == PC_HIP_OK && hist != NULL)
+		status = pc_hist_store(eff, hist, &req.hist, leak_calc);
 	if (status != PC_HIP_OK)
 		goto out;
 	if (req.stderr_on) {      /* without POLYCAP_STDERR the result keeps no moments, and its stderr and moment getters fail */
@@ -897,6 +1070,7 @@ out:
 	for (int kind = 0; kind <= 2; kind++)
 		pc_hip_spot_destroy(spot[kind]);
 	pc_hip_beam_destroy(beam);
+	pc_hip_hist_destroy(hist);
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

@@ -205,6 +205,7 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	pc_images_free(efficiencies->images);
 	pc_spot_result_free(efficiencies->spot);
 	pc_beam_result_free(efficiencies->beam);
+	pc_hist_result_free(efficiencies->hist);
 	free(efficiencies->sumw_fixed);
 	free(efficiencies->sumw2_fixed);
 	free(efficiencies->stderrs);
@@ -350,6 +351,68 @@ int pc_transmission_efficiencies_get_beam_sums(void *efficiencies_, int kind, si
 	if (sums != NULL) *sums = a;
 	if (outside != NULL) *outside = b;
 	if (n_entries != NULL) *n_entries = br->n_entries[kind];
+	return 1;
+}
+
+void pc_hist_result_free(struct pc_hist_result *hist)
+{
+	if (hist == NULL)
+		return;
+	free(hist->axes);
+	free(hist->offsets);
+	free(hist->sel);
+	for (int k = 0; k < 3; k++) {
+		free(hist->bins[k]);
+		free(hist->outside[k]);
+	}
+	free(hist);
+}
+
+int pc_transmission_efficiencies_get_hist(void *efficiencies_, int kind, int32_t dims[3], int32_t **offsets, pc_hip_hist_axis **axes,
+	double **energies, uint64_t **bins, uint64_t **outside, int64_t *n_entries, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || dims == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_hist: efficiencies and dims cannot be NULL");
+		return 0;
+	}
+	const struct pc_hist_result *hr = efficiencies->hist;
+	if (hr == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_hist: the run was made without POLYCAP_HIST");
+		return 0;
+	}
+	if (kind < 0 || kind > 2 || hr->bins[kind] == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_hist: kind must be 0 (exit photons), or 1 (extleak) / 2 (intleak) for a leak_calc run");
+		return 0;
+	}
+	const size_t na = (size_t)hr->n_axes, ns = (size_t)hr->n_sel, tb = (size_t)hr->total_bins;
+	dims[0] = hr->n_axes; dims[1] = hr->n_sel; dims[2] = hr->total_bins;
+	int32_t *o = NULL;
+	pc_hip_hist_axis *a = NULL;
+	double *e = NULL;
+	uint64_t *b = NULL, *u = NULL;
+	int ok = 1;
+	if (offsets != NULL) ok = (o = pc_dup(hr->offsets, sizeof(int32_t)*(na + 1))) != NULL;
+	if (axes != NULL && ok) ok = (a = pc_dup(hr->axes, sizeof(pc_hip_hist_axis)*na)) != NULL;
+	if (energies != NULL && ok) {
+		ok = (e = malloc(sizeof(double)*(ns ? ns : 1))) != NULL;
+		for (size_t k = 0; ok && k < ns; k++)
+			e[k] = efficiencies->energies[hr->sel[k]];
+	}
+	if (bins != NULL && ok) ok = (b = pc_dup(hr->bins[kind], sizeof(uint64_t)*ns*tb)) != NULL;
+	if (outside != NULL && ok) ok = (u = pc_dup(hr->outside[kind], sizeof(uint64_t)*na*ns)) != NULL;
+	if (!ok) {
+		free(o); free(a); free(e); free(b); free(u);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_hist: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (offsets != NULL) *offsets = o;
+	if (axes != NULL) *axes = a;
+	if (energies != NULL) *energies = e;
+	if (bins != NULL) *bins = b;
+	if (outside != NULL) *outside = u;
+	if (n_entries != NULL) *n_entries = hr->n_entries[kind];
 	return 1;
 }
 

@@ -636,6 +636,134 @@ class BeamMoments:
         return beam_params(self.read()["sums"][k], distances)
 
 
+HIST_QUANTITIES = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z")
+
+
+def hist_axes(axes):
+    """A ctypes array of pc_hip_hist_axis from a list of dicts (keys as in POLYCAP_HIST: axis, d, centre=(cx, cy), range=(lo, hi),
+    bins) or tuples (axis, (lo, hi), bins[, d[, (cx, cy)]]); axis is a name of HIST_QUANTITIES or its index."""
+    arr = (_cabi.HistAxisS * max(len(axes), 1))()
+    for k, a in enumerate(axes):
+        if not isinstance(a, dict):
+            a = dict(zip(("axis", "range", "bins", "d", "centre"), a))
+        unknown = set(a) - {"axis", "range", "bins", "d", "centre"}
+        if unknown:
+            raise ValueError("histogram axis %d: unknown keys %s" % (k, sorted(unknown)))
+        q = a["axis"]
+        q = HIST_QUANTITIES.index(q) if isinstance(q, str) else int(q)
+        cx, cy = a.get("centre", (0., 0.))
+        lo, hi = a["range"]
+        arr[k] = _cabi.HistAxisS(q, float(a.get("d", 0.)), float(cx), float(cy), float(lo), float(hi), int(a["bins"]))
+    return arr
+
+
+def hist_fwhm(bins, lo, hi):
+    """(fwhm, left, right) of one histogram, uint64 bins over [lo, hi) (pc_hip_hist_fwhm, host only): NaN when the profile does not
+    fall below half its maximum on both sides inside the range."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+    l, r = C.c_double(0.), C.c_double(0.)
+    w = _cabi.lib().pc_hip_hist_fwhm(b.shape[0], float(lo), float(hi), b.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(l), C.byref(r))
+    return float(w), float(l.value), float(r.value)
+
+
+def hist_quantile(bins, lo, hi, q, outside=0):
+    """The value below which the fraction q of the inside weight of one histogram lies (pc_hip_hist_quantile, host only)."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64).ravel()
+    return float(_cabi.lib().pc_hip_hist_quantile(b.shape[0], float(lo), float(hi), b.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  int(outside), float(q)))
+
+
+class Histograms:
+    """Histograms of a TraceContext or a TraceGroup (pc_hip_hist_*): weighted 1-D histograms of per-entry quantities of the last
+    run, one per axis and selected energy (energies: indices, None = all), all filled in one pass.  Exact uint64 sums of
+    round_half_even(w * 2^32), kept per kind (exit, extleak, intleak); the contract is written down in include/polycap-hip.h.
+    axes: see hist_axes.  regime: 0 automatic, 1 workgroup-private LDS histograms, 2 energies across lanes."""
+
+    def __init__(self, owner, axes, energies=None, regime=0):
+        self._L = _cabi.lib()
+        self.owner = owner                      # keeps the context alive as long as the histograms
+        self._axes = hist_axes(axes)
+        self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
+        spec = _cabi.HistSpecS(len(axes), self._axes, 0 if self.energies is None else self.energies.shape[0],
+                               None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
+        h = C.c_void_p()
+        if isinstance(owner, TraceGroup):
+            st = self._L.pc_hip_group_hist_create(owner._h, C.byref(spec), C.byref(h))
+        else:
+            st = self._L.pc_hip_hist_create(owner._h, C.byref(spec), C.byref(h))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_hist_create", st)
+        self._h = h
+        dims = (C.c_int32 * 3)()
+        off = (C.c_int32 * (len(axes) + 1))()
+        reg = C.c_int(0)
+        self._L.pc_hip_hist_info(self._h, dims, off, C.byref(reg))
+        self.n_axes, self.n_selected, self.total_bins = (int(d) for d in dims)
+        self.offsets = [int(v) for v in off]
+        self.regime = int(reg.value)
+        self.axes = [dict(axis=HIST_QUANTITIES[a.quantity], d=a.d, centre=(a.cx, a.cy), range=(a.lo, a.hi), bins=a.n_bins)
+                     for a in self._axes[:self.n_axes]]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pc_hip_hist_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, kind="exit"):
+        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
+        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        st = self._L.pc_hip_hist_add(self._h, k)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_hist_add", st)
+
+    def reset(self):
+        st = self._L.pc_hip_hist_reset(self._h)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_hist_reset", st)
+
+    def read(self):
+        """bins uint64 [3, energies, total_bins] (kinds exit, extleak, intleak; the axes one after the other), outside uint64
+        [3, axes, energies], n_entries [3]; axes: per axis a view [3, energies, n_bins] of the bins; edges: per axis its n_bins + 1
+        bin edges."""
+        bins = np.zeros((3, self.n_selected, self.total_bins), dtype=np.uint64)
+        out = np.zeros((3, self.n_axes, self.n_selected), dtype=np.uint64)
+        n = (C.c_int64 * 3)()
+        st = self._L.pc_hip_hist_read(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_hist_read", st)
+        o = self.offsets
+        return dict(bins=bins, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
+                    axes=[bins[:, :, o[a]:o[a + 1]] for a in range(self.n_axes)],
+                    edges=[np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in self.axes])
+
+    def _one(self, axis, energy, kind):
+        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        r = self.read()
+        return r["axes"][axis][k, energy], self.axes[axis]["range"], r["outside"][k, axis, energy]
+
+    def fwhm(self, axis, energy, kind="exit"):
+        """(fwhm, left, right) of axis `axis` at the selected energy number `energy`, read now (hist_fwhm)"""
+        b, (lo, hi), _ = self._one(axis, energy, kind)
+        return hist_fwhm(b, lo, hi)
+
+    def quantile(self, axis, energy, q, kind="exit"):
+        """the q-quantile of the inside weight of axis `axis` at the selected energy number `energy`, read now (hist_quantile)"""
+        b, (lo, hi), out = self._one(axis, energy, kind)
+        return hist_quantile(b, lo, hi, q, out)
+
+
 def scan_points(x=(0.,), y=(0.,), d_source=None):
     """Points of a scan, [len(d) * len(y) * len(x), 3] rows of (d_source, src_shiftx, src_shifty) in cm: the grid of the axes with
     x varying fastest, then y, then d_source (row = (id * len(y) + iy) * len(x) + ix).  d_source None = the problem's own (NaN

@@ -107,6 +107,17 @@ cdef extern from "polycap.h" nogil:
         int64_t *n_entries, void *error)
     const char *pc_hip_beam_columns()
 
+    ctypedef struct pc_hip_hist_axis:
+        int32_t quantity
+        double d
+        double cx
+        double cy
+        double lo
+        double hi
+        int32_t n_bins
+    int pc_transmission_efficiencies_get_hist(void *efficiencies, int kind, int32_t *dims, int32_t **offsets, pc_hip_hist_axis **axes,
+        double **energies, uint64_t **bins, uint64_t **outside, int64_t *n_entries, void *error)
+
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
         double *pc_start_coords[2]
@@ -680,6 +691,41 @@ cdef class TransmissionEfficiencies:
         out = {name: rows[:, j].copy() for j, name in enumerate(names)}
         out.update(sums=S.reshape(n, 15, 2), outside=O, n_entries=int(ni))
         return out
+
+    def hist(self, kind="exit"):
+        """Extension of this build: the histograms of a run made with POLYCAP_HIST set (pc_transmission_efficiencies_get_hist): dict of
+        the exact sums bins uint64 [energies, total_bins] and outside uint64 [axes, energies], n_entries, offsets [axes + 1], energies
+        (keV) and axes, a list of dicts (axis, d, centre, range, bins).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        cdef polycap_error *error = NULL
+        cdef int32_t dims[3]
+        cdef int32_t *o = NULL
+        cdef pc_hip_hist_axis *ax = NULL
+        cdef double *e = NULL
+        cdef uint64_t *b = NULL
+        cdef uint64_t *u = NULL
+        cdef int64_t ni = 0
+        cdef size_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_hist(<void *>self._eff, k, dims, &o, &ax, &e, &b, &u, &ni, <void *>&error)
+        _raise_if(error)
+        na, ns, tb = dims[0], dims[1], dims[2]
+        names = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z")
+        axes = [dict(axis=names[ax[i].quantity], d=ax[i].d, centre=(ax[i].cx, ax[i].cy), range=(ax[i].lo, ax[i].hi), bins=ax[i].n_bins)
+                for i in range(na)]
+        B = np.empty(ns * tb, dtype=np.uint64)
+        U = np.empty(na * ns, dtype=np.uint64)
+        O = np.empty(na + 1, dtype=np.int32)
+        for i in range(ns * tb):
+            B[i] = b[i]
+        for i in range(na * ns):
+            U[i] = u[i]
+        for i in range(na + 1):
+            O[i] = o[i]
+        polycap_free(o)
+        polycap_free(ax)
+        polycap_free(b)
+        polycap_free(u)
+        return dict(bins=B.reshape(ns, tb), outside=U.reshape(na, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), axes=axes)
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
