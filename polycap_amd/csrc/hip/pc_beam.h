@@ -177,9 +177,7 @@ static __device__ __forceinline__ void pc_beam_mac(unsigned long long &lo, unsig
 		pl = ~pl + 1ull;
 		ph = ~ph + (pl == 0ull ? 1ull : 0ull);
 	}
-	const unsigned long long o = lo;
-	lo += pl;
-	hi += ph + (lo < o ? 1ull : 0ull);
+	pc_add128(lo, hi, pl, ph);
 }
 
 /* The sums [energy][16][2]: the 15 signed (lo, hi) sums, then the outside counter as (lo, 0).
@@ -198,23 +196,17 @@ __global__ void __launch_bounds__(PC_BEAM_BLOCK) pc_beam_kernel(pc_spot_src s, d
 	const int en = (ne - e0 < 64) ? ne - e0 : 64;
 	for (int k = threadIdx.x; k < 64*PC_BEAM_SLOTS*2; k += blockDim.x) red[k] = 0ull;
 	__syncthreads();
-	int gw = 1;
-	while (gw < en) gw <<= 1;
-	const int lane = threadIdx.x & 63, sub = lane & (gw - 1), per_wave = 64 / gw;
-	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
+	const pc_tally_lanes l = pc_tally_lane_map(en);
 	unsigned long long acc[PC_BEAM_SLOTS][2];
 #pragma unroll
 	for (int k = 0; k < PC_BEAM_SLOTS; k++) acc[k][0] = acc[k][1] = 0ull;
-	const int e = e0 + sub;
-	for (long long i = (sub < en) ? wave*per_wave + lane / gw : s.n; i < s.n; i += n_waves*per_wave) {
+	const int e = e0 + l.sub;
+	for (long long i = (l.sub < en) ? l.first : s.n; i < s.n; i += l.stride) {
 		const unsigned long long w = pc_spot_q(s.w[i*s.ws + e]);
 		if (!w) continue;
-		const double *p = s.p + i*s.ss;
-		const double x = p[(long long)s.f_x*s.fs], y = p[(long long)(s.f_x + 1)*s.fs], z = p[(long long)(s.f_x + 2)*s.fs];
-		const double dx = p[(long long)s.f_dx*s.fs], dy = p[(long long)(s.f_dx + 1)*s.fs];
-		const double dz = s.has_dz ? p[(long long)(s.f_dx + 2)*s.fs] : pc_spot_exit_dz(dx, dy);
+		const pc_entry t = pc_entry_load(s, i);
 		long long q[4];
-		if (!pc_beam_entry(x, y, z, dx, dy, dz, ze, q)) {
+		if (!pc_beam_entry(t.x, t.y, t.z, t.dx, t.dy, t.dz, ze, q)) {
 			acc[15][0] += w;
 			continue;
 		}
@@ -228,19 +220,17 @@ __global__ void __launch_bounds__(PC_BEAM_BLOCK) pc_beam_kernel(pc_spot_src s, d
 			for (int b = a; b < 4; b++, k++) pc_beam_mac(acc[k][0], acc[k][1], w, q[a]*q[b]);
 	}
 	/* lanes lane ^ gw, lane ^ 2gw, ... have the same energy */
-	for (int off = gw; off < 64; off <<= 1)
+	for (int off = l.gw; off < 64; off <<= 1)
 #pragma unroll
 		for (int k = 0; k < PC_BEAM_SLOTS; k++) {
 			const unsigned long long lo = __shfl_xor(acc[k][0], off), hi = __shfl_xor(acc[k][1], off);
-			const unsigned long long o = acc[k][0];
-			acc[k][0] += lo;
-			acc[k][1] += hi + (acc[k][0] < o ? 1ull : 0ull);
+			pc_add128(acc[k][0], acc[k][1], lo, hi);
 		}
-	if (lane < gw && sub < en)
+	if (l.lane < l.gw && l.sub < en)
 #pragma unroll
 		for (int k = 0; k < PC_BEAM_SLOTS; k++) {
 			if (!(acc[k][0] | acc[k][1])) continue;
-			unsigned long long *r = red + (sub*PC_BEAM_SLOTS + k)*2;
+			unsigned long long *r = red + (l.sub*PC_BEAM_SLOTS + k)*2;
 			const unsigned long long old = atomicAdd(&r[0], acc[k][0]);
 			const unsigned long long c = (old + acc[k][0] < old) ? 1ull : 0ull;
 			if (acc[k][1] + c) atomicAdd(&r[1], acc[k][1] + c);
@@ -252,18 +242,10 @@ __global__ void __launch_bounds__(PC_BEAM_BLOCK) pc_beam_kernel(pc_spot_src s, d
 	}
 }
 
-struct pc_beam_member {
-	pc_hip_ctx *ctx = nullptr;
-	pc_dev_buf<unsigned long long> d_sums;     /* [kind][energy][16][2] */
-};
-
-struct pc_hip_beam {
-	std::vector<pc_beam_member> m;
-	pc_hip_group *group = nullptr;
+/* cells [kind][energy][16][2] */
+struct pc_hip_beam : pc_tally {
 	int ne = 0;
 	double ze = 0.;
-	long long n_entries[3] = {0, 0, 0};
-	size_t elems = 0;
 };
 
 static int pc_beam_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *group, pc_hip_beam **out)
@@ -272,44 +254,21 @@ static int pc_beam_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *gro
 	*out = nullptr;
 	const pc_hip_ctx *c0 = ctxs[0];
 	pc_hip_beam *b = new pc_hip_beam();
-	b->group = group;
 	b->ne = c0->host.pm.n_energies;
 	b->ze = c0->host.z[c0->host.pm.nmax];
-	b->elems = (size_t)3*b->ne*PC_BEAM_SLOTS*2;
-	for (pc_hip_ctx *c : ctxs) {
-		b->m.emplace_back();
-		pc_beam_member &m = b->m.back();
-		m.ctx = c;
-		hipError_t e = hipSetDevice(c->device);
-		if (e == hipSuccess) {
-			const int st = m.d_sums.grow(b->elems, "pc_hip_beam_create: could not allocate the sums");
-			if (st) { pc_hip_beam_destroy(b); return st; }
-			e = hipMemsetAsync(m.d_sums, 0, b->elems*sizeof(unsigned long long), c->stream);
-		}
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			pc_hip_beam_destroy(b);
-			return pc_fail(e == hipErrorOutOfMemory ? PC_HIP_ERR_MEMORY : PC_HIP_ERR_RUNTIME, std::string("pc_hip_beam_create: ") + hipGetErrorString(e));
-		}
-	}
+	const int st = pc_tally_make(*b, ctxs, group, (size_t)3*b->ne*PC_BEAM_SLOTS*2, "pc_hip_beam_create");
+	if (st) { delete b; return st; }
 	*out = b;
 	return PC_HIP_OK;
 }
 
-static int pc_beam_launch(pc_hip_beam *b, pc_beam_member &m, const pc_spot_src &s, int kind)
+static int pc_beam_launch(pc_hip_beam *b, pc_tally_member &m, const pc_spot_src &s, int kind)
 {
-	if (s.n == 0) return PC_HIP_OK;
 	pc_hip_ctx *c = m.ctx;
 	const long long chunks = (b->ne + 63) / 64;
-	long long bx = (8ll*c->n_cu + chunks - 1) / chunks;
-	int gw = 1;
-	while (gw < b->ne && gw < 64) gw <<= 1;
-	const long long need = (s.n*gw + PC_BEAM_BLOCK - 1) / PC_BEAM_BLOCK;
-	if (bx > need) bx = need;
-	if (bx < 1) bx = 1;
-	unsigned long long *sums = m.d_sums + (size_t)kind*b->ne*PC_BEAM_SLOTS*2;
+	const long long bx = pc_tally_grid_wide(c->n_cu, chunks, b->ne, s.n, PC_BEAM_BLOCK).bx;
+	unsigned long long *sums = m.d_cells + (size_t)kind*b->ne*PC_BEAM_SLOTS*2;
 	hipLaunchKernelGGL(pc_beam_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_BEAM_BLOCK), 0, c->stream, s, b->ze, b->ne, sums);
-	PC_HIP_CHECK(hipGetLastError());
 	return PC_HIP_OK;
 }
 
@@ -329,60 +288,22 @@ int pc_hip_group_beam_create(pc_hip_group *group, pc_hip_beam **beam)
 
 void pc_hip_beam_destroy(pc_hip_beam *beam)
 {
-	if (!beam) return;
-	for (pc_beam_member &m : beam->m) {
-		if (!m.ctx) continue;
-		(void)hipSetDevice(m.ctx->device);
-		if (m.ctx->stream) (void)hipStreamSynchronize(m.ctx->stream);
-		m = pc_beam_member();
-	}
 	delete beam;
 }
 
 int pc_hip_beam_add(pc_hip_beam *beam, int kind)
 {
 	if (!beam) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_add: beam must not be NULL");
-	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_add: kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
-	pc_hip_group *g = beam->group;
-	if (g && kind == 0 && !g->keep_images)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_add: the last run kept no exit photons (run it with keep_images)");
-	if (g && kind > 0 && !g->leak_run)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_add: leak events need a leak_calc run of the group as the last run");
-	/* every member's source first: nothing is added unless the whole add can be */
-	std::vector<pc_spot_src> src(beam->m.size());
-	long long n = 0;
-	for (size_t k = 0; k < beam->m.size(); k++) {
-		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
-		PC_HIP_CHECK(hipSetDevice(beam->m[k].ctx->device));
-		const int st = pc_spot_source(beam->m[k].ctx, kind, src[k]);
-		if (st) return st;
-		n += src[k].n;
-	}
-	if (beam->n_entries[kind] + n > (long long)0xffffffffll)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_add: the sums of a kind take at most 2^32 - 1 entries (they could wrap beyond)");
-	for (size_t k = 0; k < beam->m.size(); k++) {
-		PC_HIP_CHECK(hipSetDevice(beam->m[k].ctx->device));
-		const int st = pc_beam_launch(beam, beam->m[k], src[k], kind);
-		if (st) return st;
-	}
-	beam->n_entries[kind] += n;
-	return PC_HIP_OK;
+	return pc_tally_add(*beam, kind, "pc_hip_beam_add",
+		[beam](size_t k, const pc_spot_src &s, int kd) { return pc_beam_launch(beam, beam->m[k], s, kd); });
 }
 
 int pc_hip_beam_read(pc_hip_beam *beam, uint64_t *sums, uint64_t *outside, int64_t *n_entries)
 {
 	if (!beam) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_read: beam must not be NULL");
-	std::vector<unsigned long long> sum(beam->elems, 0ull), part(beam->elems);
-	for (pc_beam_member &m : beam->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_sums, beam->elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
-		for (size_t k = 0; k < beam->elems; k += 2) {      /* 128-bit two's complement: exact below the entry cap */
-			const unsigned long long lo = sum[k] + part[k];
-			sum[k + 1] += part[k + 1] + (lo < sum[k] ? 1ull : 0ull);
-			sum[k] = lo;
-		}
-	}
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum(*beam, 2, sum);      /* 128-bit two's complement */
+	if (st) return st;
 	const size_t rows = (size_t)3*beam->ne;
 	for (size_t r = 0; r < rows; r++) {
 		const unsigned long long *q = sum.data() + r*PC_BEAM_SLOTS*2;
@@ -397,12 +318,7 @@ int pc_hip_beam_read(pc_hip_beam *beam, uint64_t *sums, uint64_t *outside, int64
 int pc_hip_beam_reset(pc_hip_beam *beam)
 {
 	if (!beam) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_beam_reset: beam must not be NULL");
-	for (pc_beam_member &m : beam->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemsetAsync(m.d_sums, 0, beam->elems*sizeof(unsigned long long), m.ctx->stream));
-	}
-	for (int k = 0; k < 3; k++) beam->n_entries[k] = 0;
-	return PC_HIP_OK;
+	return pc_tally_reset(*beam);
 }
 
 int pc_hip_beam_info(const pc_hip_beam *beam, int *n_energies)

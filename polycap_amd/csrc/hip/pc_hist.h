@@ -143,16 +143,14 @@ struct pc_hist_geo {
 
 static __device__ __forceinline__ void pc_hist_load(const pc_spot_src &s, const pc_hist_geo &g, long long i, pc_hist_entry &e)
 {
+	const pc_entry b = pc_entry_load(s, i);
 	const double *p = s.p + i*s.ss;
-	e.x = p[(long long)s.f_x*s.fs]; e.y = p[(long long)(s.f_x + 1)*s.fs]; e.z = p[(long long)(s.f_x + 2)*s.fs];
-	e.dx = p[(long long)s.f_dx*s.fs]; e.dy = p[(long long)(s.f_dx + 1)*s.fs];
+	e.x = b.x; e.y = b.y; e.z = b.z; e.dx = b.dx; e.dy = b.dy; e.dz = b.dz;
 	e.leak = s.has_dz;
 	e.n = e.dtravel = e.sx = e.sy = 0.;
 	if (s.has_dz) {          /* a leak event: slot, attempt, coords, direction, electric vector, n_refl */
-		e.dz = p[(long long)(s.f_dx + 2)*s.fs];
 		if (g.need_n) e.n = p[11*s.fs];
 	} else {                 /* an image record: pc_start_coords in planes 2, 3; pc_exit_nrefl (int64) in 15; pc_exit_dtravel in 16 */
-		e.dz = pc_spot_exit_dz(e.dx, e.dy);
 		if (g.need_n) e.n = (double)((const long long *)p)[15*s.fs];
 		if (g.need_travel) e.dtravel = p[16*s.fs];
 		if (g.need_start) { e.sx = p[2*s.fs]; e.sy = p[3*s.fs]; }
@@ -208,18 +206,15 @@ __global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spo
 	const int sn = (g.ns - s0 < PC_HIST_ECHUNK) ? g.ns - s0 : PC_HIST_ECHUNK;
 	for (int k = threadIdx.x; k < g.na*PC_HIST_ECHUNK; k += blockDim.x) out[k] = 0ull;
 	__syncthreads();
-	int gw = 1;
-	while (gw < sn && gw < 64) gw <<= 1;
-	const int lane = threadIdx.x & 63, sub = lane & (gw - 1), per_wave = 64 / gw;
-	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
-	for (long long i = wave*per_wave + lane / gw; i < s.n; i += n_waves*per_wave) {
+	const pc_tally_lanes l = pc_tally_lane_map(sn);
+	for (long long i = l.first; i < s.n; i += l.stride) {
 		pc_hist_entry e;
 		pc_hist_load(s, g, i, e);
 		int bin[PC_HIST_MAX_AXES];
 #pragma unroll
 		for (int a = 0; a < PC_HIST_MAX_AXES; a++)
 			bin[a] = (a < g.na) ? pc_hist_axis_bin(g.ax[a], e) : -1;
-		for (int k = sub; k < sn; k += gw) {
+		for (int k = l.sub; k < sn; k += l.gw) {
 			const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[s0 + k]]);
 			if (!q) continue;
 #pragma unroll
@@ -247,19 +242,11 @@ static int pc_hist_auto_regime(long long ns, long long tc)
 	return (ns*tc <= PC_HIST_TILE) ? 1 : 2;
 }
 
-struct pc_hist_member {
-	pc_hip_ctx *ctx = nullptr;
-	pc_dev_buf<unsigned long long> d_cells;      /* [kind][energy][tc] (regime 1) or [kind][tc][energy] (regime 2) */
-	pc_dev_buf<int> d_sel;
-};
-
-struct pc_hip_hist {
-	std::vector<pc_hist_member> m;
-	pc_hip_group *group = nullptr;
+/* cells [kind][energy][tc] (regime 1) or [kind][tc][energy] (regime 2) */
+struct pc_hip_hist : pc_tally {
 	pc_hist_geo geo;                  /* sel is the member's own */
-	std::vector<int> sel, offsets;    /* offsets [na + 1] into the bins of one energy */
+	std::vector<int> offsets;         /* [na + 1] into the bins of one energy */
 	int regime = 0;
-	long long n_entries[3] = {0, 0, 0};
 	size_t per_kind = 0;              /* ns * tc */
 };
 
@@ -271,15 +258,11 @@ static int pc_hist_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *gro
 	int st = pc_hip_hist_validate(spec, (size_t)c0->host.pm.n_energies);
 	if (st) return st;
 	pc_hip_hist *h = new pc_hip_hist();
-	h->group = group;
-	if (spec->n_energies == 0)
-		for (int e = 0; e < c0->host.pm.n_energies; e++) h->sel.push_back(e);
-	else
-		h->sel.assign(spec->energies, spec->energies + spec->n_energies);
+	const std::vector<int> sel = pc_sel_fill(spec->n_energies, spec->energies, (size_t)c0->host.pm.n_energies);
 	pc_hist_geo &g = h->geo;
 	memset(&g, 0, sizeof(g));
 	g.na = spec->n_axes;
-	g.ns = (int)h->sel.size();
+	g.ns = (int)sel.size();
 	const double zexit = c0->host.z[c0->host.pm.nmax];
 	int bins = 0;
 	for (int a = 0; a < g.na; a++) {
@@ -298,54 +281,28 @@ static int pc_hist_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *gro
 	g.tc = bins + g.na;
 	h->per_kind = (size_t)g.ns*g.tc;
 	h->regime = spec->regime ? spec->regime : pc_hist_auto_regime(g.ns, g.tc);
-	for (pc_hip_ctx *c : ctxs) {
-		h->m.emplace_back();
-		pc_hist_member &m = h->m.back();
-		m.ctx = c;
-		hipError_t e = hipSetDevice(c->device);
-		if (e == hipSuccess) {
-			st = m.d_cells.grow(3*h->per_kind, "pc_hip_hist_create: could not allocate the histograms");
-			if (!st) st = m.d_sel.grow(h->sel.size(), "pc_hip_hist_create: could not allocate the energy selection");
-			if (st) { pc_hip_hist_destroy(h); return st; }
-			e = hipMemcpy(m.d_sel, h->sel.data(), h->sel.size()*sizeof(int), hipMemcpyHostToDevice);
-		}
-		if (e == hipSuccess) e = hipMemsetAsync(m.d_cells, 0, 3*h->per_kind*sizeof(unsigned long long), c->stream);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			pc_hip_hist_destroy(h);
-			return pc_fail(e == hipErrorOutOfMemory ? PC_HIP_ERR_MEMORY : PC_HIP_ERR_RUNTIME, std::string("pc_hip_hist_create: ") + hipGetErrorString(e));
-		}
-	}
+	st = pc_tally_make(*h, ctxs, group, 3*h->per_kind, "pc_hip_hist_create");
+	if (!st) st = pc_tally_upload(*h, sel, std::vector<double>(), "pc_hip_hist_create");
+	if (st) { delete h; return st; }
 	*out = h;
 	return PC_HIP_OK;
 }
 
-static int pc_hist_launch(pc_hip_hist *h, pc_hist_member &m, const pc_spot_src &s, int kind)
+static int pc_hist_launch(pc_hip_hist *h, pc_tally_member &m, const pc_spot_src &s, int kind)
 {
-	if (s.n == 0) return PC_HIP_OK;
 	pc_hip_ctx *c = m.ctx;
 	pc_hist_geo g = h->geo;
 	g.sel = m.d_sel;
 	unsigned long long *cells = m.d_cells + (size_t)kind*h->per_kind;
-	const long long cus = c->n_cu;
 	if (h->regime == 1) {
 		const long long tiles = ((long long)h->per_kind + PC_HIST_TILE - 1)/PC_HIST_TILE;
-		long long bx = (2*cus + tiles - 1)/tiles;                       /* two workgroups per CU in all (LDS: 64 KiB each) */
-		const long long need = (s.n + PC_HIST_LDS_BLOCK - 1)/PC_HIST_LDS_BLOCK;
-		if (bx > need) bx = need;
-		if (bx < 1) bx = 1;
+		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_HIST_LDS_BLOCK).bx;
 		hipLaunchKernelGGL(pc_hist_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_HIST_LDS_BLOCK), 0, c->stream, s, g, cells);
 	} else {
 		const long long chunks = (g.ns + PC_HIST_ECHUNK - 1)/PC_HIST_ECHUNK;
-		long long bx = (8*cus + chunks - 1)/chunks;
-		int gw = 1;
-		while (gw < g.ns && gw < 64) gw <<= 1;
-		const long long need = (s.n*gw + PC_HIST_WIDE_BLOCK - 1)/PC_HIST_WIDE_BLOCK;
-		if (bx > need) bx = need;
-		if (bx < 1) bx = 1;
+		const long long bx = pc_tally_grid_wide(c->n_cu, chunks, g.ns, s.n, PC_HIST_WIDE_BLOCK).bx;
 		hipLaunchKernelGGL(pc_hist_wide_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_HIST_WIDE_BLOCK), 0, c->stream, s, g, cells);
 	}
-	PC_HIP_CHECK(hipGetLastError());
 	return PC_HIP_OK;
 }
 
@@ -376,16 +333,9 @@ int pc_hip_hist_validate(const pc_hip_hist_spec *spec, size_t n_energies)
 	}
 	if (spec->regime < 0 || spec->regime > 2)
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: regime must be 0 (automatic), 1 (private LDS histograms) or 2 (energies across lanes)");
-	if (spec->n_energies < 0 || (size_t)spec->n_energies > n_energies || (spec->n_energies > 0 && !spec->energies))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: n_energies: between 1 and the problem's energy count of indices (0 = all energies)");
-	std::vector<char> seen(n_energies, 0);
-	for (int k = 0; k < spec->n_energies; k++) {
-		const int e = spec->energies[k];
-		if (e < 0 || (size_t)e >= n_energies)
-			return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: energies: index " + std::to_string(e) + " out of range (" + std::to_string(n_energies) + " energies)");
-		if (seen[e]) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: energies: index " + std::to_string(e) + " given twice");
-		seen[e] = 1;
-	}
+	std::string why;
+	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &why))
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: " + why);
 	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
 	if (bins*ns > (double)(1ll << 24))
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: n_bins: (sum of n_bins) * selected energies exceeds 2^24");
@@ -406,57 +356,22 @@ int pc_hip_group_hist_create(pc_hip_group *group, const pc_hip_hist_spec *spec, 
 
 void pc_hip_hist_destroy(pc_hip_hist *hist)
 {
-	if (!hist) return;
-	for (pc_hist_member &m : hist->m) {
-		if (!m.ctx) continue;
-		(void)hipSetDevice(m.ctx->device);
-		if (m.ctx->stream) (void)hipStreamSynchronize(m.ctx->stream);
-		m = pc_hist_member();
-	}
 	delete hist;
 }
 
 int pc_hip_hist_add(pc_hip_hist *hist, int kind)
 {
 	if (!hist) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add: hist must not be NULL");
-	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add: kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
-	pc_hip_group *g = hist->group;
-	if (g && kind == 0 && !g->keep_images)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add: the last run kept no exit photons (run it with keep_images)");
-	if (g && kind > 0 && !g->leak_run)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add: leak events need a leak_calc run of the group as the last run");
-	/* every member's source first: nothing is added unless the whole add can be */
-	std::vector<pc_spot_src> src(hist->m.size());
-	long long n = 0;
-	for (size_t k = 0; k < hist->m.size(); k++) {
-		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
-		PC_HIP_CHECK(hipSetDevice(hist->m[k].ctx->device));
-		const int st = pc_spot_source(hist->m[k].ctx, kind, src[k]);
-		if (st) return st;
-		n += src[k].n;
-	}
-	if (hist->n_entries[kind] + n > (long long)0xffffffffll)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add: the histograms of a kind take at most 2^32 - 1 entries (their uint64 bins could wrap beyond)");
-	for (size_t k = 0; k < hist->m.size(); k++) {
-		PC_HIP_CHECK(hipSetDevice(hist->m[k].ctx->device));
-		const int st = pc_hist_launch(hist, hist->m[k], src[k], kind);
-		if (st) return st;
-	}
-	hist->n_entries[kind] += n;
-	return PC_HIP_OK;
+	return pc_tally_add(*hist, kind, "pc_hip_hist_add",
+		[hist](size_t k, const pc_spot_src &s, int kd) { return pc_hist_launch(hist, hist->m[k], s, kd); });
 }
 
 int pc_hip_hist_read(pc_hip_hist *hist, uint64_t *bins, uint64_t *outside, int64_t *n_entries)
 {
 	if (!hist) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_read: hist must not be NULL");
-	const size_t elems = 3*hist->per_kind;
-	std::vector<unsigned long long> sum(elems, 0ull), part(elems);
-	for (pc_hist_member &m : hist->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_cells, elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
-		for (size_t k = 0; k < elems; k++) sum[k] += part[k];       /* exact: the entry cap keeps every sum below 2^64 */
-	}
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum(*hist, 1, sum);
+	if (st) return st;
 	const pc_hist_geo &g = hist->geo;
 	const size_t ns = (size_t)g.ns, tc = (size_t)g.tc, tb = tc - (size_t)g.na;
 	for (size_t kind = 0; kind < 3; kind++)
@@ -477,12 +392,7 @@ int pc_hip_hist_read(pc_hip_hist *hist, uint64_t *bins, uint64_t *outside, int64
 int pc_hip_hist_reset(pc_hip_hist *hist)
 {
 	if (!hist) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_reset: hist must not be NULL");
-	for (pc_hist_member &m : hist->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemsetAsync(m.d_cells, 0, 3*hist->per_kind*sizeof(unsigned long long), m.ctx->stream));
-	}
-	for (int k = 0; k < 3; k++) hist->n_entries[k] = 0;
-	return PC_HIP_OK;
+	return pc_tally_reset(*hist);
 }
 
 int pc_hip_hist_info(const pc_hip_hist *hist, int32_t dims[3], int32_t *offsets, int *regime)

@@ -2604,9 +2604,21 @@ int pc_hip_device_synchronize(pc_hip_ctx *ctx)
 	return PC_HIP_OK;
 }
 
+int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes)
+{
+	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_device_memory: ctx must not be NULL");
+	PC_HIP_CHECK(hipSetDevice(ctx->device));
+	size_t f = 0, t = 0;
+	PC_HIP_CHECK(hipMemGetInfo(&f, &t));
+	if (free_bytes) *free_bytes = f;
+	if (total_bytes) *total_bytes = t;
+	return PC_HIP_OK;
+}
+
 } /* extern "C" */
 
 #include "pc_group.h"
+#include "pc_tally.h"
 #include "pc_spot.h"
 #include "pc_beam.h"
 #include "pc_hist.h"

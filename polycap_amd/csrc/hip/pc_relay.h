@@ -312,7 +312,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
 	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
 	pc_spot_src s;
-	st = pc_spot_source(a, 0, s);
+	st = pc_spot_source(a, 0, s, "pc_hip_relay_run");
 	if (st) return st;
 	const long long n_a = s.n;
 	const int ne = b->host.pm.n_energies;

@@ -47,16 +47,6 @@ static inline __host__ __device__ unsigned long long pc_spot_q(double w)
 
 #ifndef PC_SPOT_HOST_ONLY
 
-/* Where the entries are: field f of entry i at p[i*ss + f*fs], weight e at w[i*ws + e] */
-struct pc_spot_src {
-	const double *p;
-	long long ss, fs, n;
-	int f_x, f_dx;          /* x, y, z at f_x .. f_x + 2; dx, dy (, dz when has_dz) from f_dx on */
-	int has_dz;
-	const double *w;
-	long long ws;
-};
-
 struct pc_spot_geo {
 	const double *zp;       /* [np] plane positions */
 	const int *sel;         /* [ns] energy indices */
@@ -66,11 +56,8 @@ struct pc_spot_geo {
 
 static __device__ __forceinline__ long long pc_spot_entry_bin(const pc_spot_src &s, const pc_spot_geo &g, long long i, int p)
 {
-	const double *e = s.p + i*s.ss;
-	const double x = e[(long long)s.f_x*s.fs], y = e[(long long)(s.f_x + 1)*s.fs], z = e[(long long)(s.f_x + 2)*s.fs];
-	const double dx = e[(long long)s.f_dx*s.fs], dy = e[(long long)(s.f_dx + 1)*s.fs];
-	const double dz = s.has_dz ? e[(long long)(s.f_dx + 2)*s.fs] : pc_spot_exit_dz(dx, dy);
-	return pc_spot_bin(x, y, z, dx, dy, dz, g.zp[p], g.x0, g.x1, g.y0, g.y1, g.nx, g.ny);
+	const pc_entry e = pc_entry_load(s, i);
+	return pc_spot_bin(e.x, e.y, e.z, e.dx, e.dy, e.dz, g.zp[p], g.x0, g.x1, g.y0, g.y1, g.nx, g.ny);
 }
 
 /* Small maps.  The flat map [plane][energy][iy][ix] followed by the outside counters [plane][energy] is cut into tiles of
@@ -125,14 +112,11 @@ __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spo
 	const long long nb = (long long)g.nx*g.ny, n_bins = (long long)g.np*g.ns*nb;
 	for (int k = threadIdx.x; k < sn; k += blockDim.x) out[k] = 0ull;
 	__syncthreads();
-	int gw = 1;
-	while (gw < sn && gw < 64) gw <<= 1;
-	const int lane = threadIdx.x & 63, sub = lane & (gw - 1), per_wave = 64 / gw;
-	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
-	for (long long i = wave*per_wave + lane / gw; i < s.n; i += n_waves*per_wave) {
+	const pc_tally_lanes l = pc_tally_lane_map(sn);
+	for (long long i = l.first; i < s.n; i += l.stride) {
 		const long long b = pc_spot_entry_bin(s, g, i, p);
 		unsigned long long *cell = map + ((long long)p*nb + (b >= 0 ? b : 0))*g.ns + s0;
-		for (int k = sub; k < sn; k += gw) {
+		for (int k = l.sub; k < sn; k += l.gw) {
 			const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[s0 + k]]);
 			if (!q) continue;
 			if (b >= 0) atomicAdd(cell + k, q);
@@ -152,30 +136,11 @@ __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spo
  * LDS tiles won no measured case, so there is no crossover to apply: they stay available as regime 1 (maps of a single tile with
  * a very concentrated spot are where they could still win; not measured). */
 
-struct pc_spot_member {
-	pc_hip_ctx *ctx = nullptr;
-	pc_dev_buf<unsigned long long> d_map;
-	pc_dev_buf<double> d_zp;
-	pc_dev_buf<int> d_sel;
-};
-
-struct pc_hip_spot {
-	std::vector<pc_spot_member> m;
-	pc_hip_group *group = nullptr;
+/* one map for all kinds (pc_tally: shared): elems = np*ns*nx*ny bins + np*ns outside counters */
+struct pc_hip_spot : pc_tally {
 	int np = 0, ns = 0, nx = 0, ny = 0, wide = 0;
 	double x0 = 0., x1 = 0., y0 = 0., y1 = 0.;
-	std::vector<int> sel;
-	long long n_entries = 0;
-	size_t map_elems = 0;             /* np*ns*nx*ny bins + np*ns outside counters */
 };
-
-static void pc_spot_free_member(pc_spot_member &mb)
-{
-	if (!mb.ctx) return;
-	(void)hipSetDevice(mb.ctx->device);
-	if (mb.ctx->stream) (void)hipStreamSynchronize(mb.ctx->stream);
-	mb = pc_spot_member();
-}
 
 static int pc_spot_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *group, const pc_hip_spot_spec *spec, pc_hip_spot **out)
 {
@@ -185,107 +150,40 @@ static int pc_spot_make(const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *gro
 	int st = pc_hip_spot_validate(spec, (size_t)c0->host.pm.n_energies);
 	if (st) return st;
 	pc_hip_spot *sp = new pc_hip_spot();
-	sp->group = group;
+	sp->shared = 1;
 	sp->np = spec->n_planes; sp->nx = spec->nx; sp->ny = spec->ny;
 	sp->x0 = spec->x0; sp->x1 = spec->x1; sp->y0 = spec->y0; sp->y1 = spec->y1;
-	if (spec->n_energies == 0)
-		for (int e = 0; e < c0->host.pm.n_energies; e++) sp->sel.push_back(e);
-	else
-		sp->sel.assign(spec->energies, spec->energies + spec->n_energies);
-	sp->ns = (int)sp->sel.size();
-	const long long nb = (long long)sp->nx*sp->ny, total = (long long)sp->np*sp->ns*nb + (long long)sp->np*sp->ns;
-	sp->map_elems = (size_t)total;
+	const std::vector<int> sel = pc_sel_fill(spec->n_energies, spec->energies, (size_t)c0->host.pm.n_energies);
+	sp->ns = (int)sel.size();
 	sp->wide = spec->regime != 1;
 	/* zp = z[nmax] + d, once, on the host */
 	std::vector<double> zp(sp->np);
 	const double zexit = c0->host.z[c0->host.pm.nmax];
 	for (int k = 0; k < sp->np; k++) zp[k] = zexit + spec->distances[k];
-	for (pc_hip_ctx *c : ctxs) {
-		sp->m.emplace_back();
-		pc_spot_member &m = sp->m.back();
-		m.ctx = c;
-		hipError_t e = hipSetDevice(c->device);
-		if (e == hipSuccess) {
-			st = m.d_map.grow(sp->map_elems, "pc_hip_spot_create: could not allocate the maps");
-			if (!st) st = m.d_zp.grow(zp.size(), "pc_hip_spot_create: could not allocate the plane positions");
-			if (!st) st = m.d_sel.grow(sp->sel.size(), "pc_hip_spot_create: could not allocate the energy selection");
-			if (st) { pc_hip_spot_destroy(sp); return st; }
-			e = hipMemcpy(m.d_zp, zp.data(), zp.size()*sizeof(double), hipMemcpyHostToDevice);
-		}
-		if (e == hipSuccess) e = hipMemcpy(m.d_sel, sp->sel.data(), sp->sel.size()*sizeof(int), hipMemcpyHostToDevice);
-		if (e == hipSuccess) e = hipMemsetAsync(m.d_map, 0, sp->map_elems*sizeof(unsigned long long), c->stream);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			pc_hip_spot_destroy(sp);
-			return pc_fail(e == hipErrorOutOfMemory ? PC_HIP_ERR_MEMORY : PC_HIP_ERR_RUNTIME, std::string("pc_hip_spot_create: ") + hipGetErrorString(e));
-		}
-	}
+	const long long cells = (long long)sp->np*sp->ns*((long long)sp->nx*sp->ny + 1);
+	st = pc_tally_make(*sp, ctxs, group, (size_t)cells, "pc_hip_spot_create");
+	if (!st) st = pc_tally_upload(*sp, sel, zp, "pc_hip_spot_create");
+	if (st) { delete sp; return st; }
 	*out = sp;
 	return PC_HIP_OK;
 }
 
-/* the entries of `kind` that the last run of c left on its device */
-static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s)
+static int pc_spot_launch(pc_hip_spot *sp, pc_tally_member &m, const pc_spot_src &s)
 {
-	const long long ne = c->host.pm.n_energies;
-	memset(&s, 0, sizeof(s));
-	if (kind == 0) {
-		if (!c->img_valid)
-			return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: the last run kept no exit photons (run it with keep_images)");
-		if (c->leak_pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
-			int st = pc_hip_transmission_wait(c, nullptr);
-			if (st) return st;
-		}
-		const long long n = c->run_slots;
-		s.n = n; s.f_x = 8; s.f_dx = 11; s.has_dz = 0;          /* pc_exit_coords, pc_exit_dir: planes 8..10, 11..12 */
-		if (c->run_planes) {
-			s.p = c->d_soa; s.ss = 1; s.fs = n;
-			s.w = c->d_soa + (long long)PC_N_FIELDS*n; s.ws = ne;
-		} else {
-			s.p = c->d_img; s.ss = PC_N_FIELDS + ne; s.fs = 1;
-			s.w = c->d_img + PC_N_FIELDS; s.ws = PC_N_FIELDS + ne;
-		}
-		return PC_HIP_OK;
-	}
-	if (!c->leak_events_of_run)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: leak events need a leak_calc source run (pc_hip_transmission_run_leak) as the last run");
-	int st = pc_hip_transmission_wait(c, nullptr);      /* the events are ordered into d_leak_out when the run is waited for */
-	if (st) return st;
-	const long long stride = PC_HIP_LEAK_HDR + ne;
-	s.n = (kind == 1) ? c->leak_n_ext : c->leak_n_int;
-	s.p = c->d_leak_out + ((kind == 1) ? 0 : c->leak_n_ext*stride);
-	s.ss = stride; s.fs = 1; s.f_x = 2; s.f_dx = 5; s.has_dz = 1;
-	s.w = s.p + PC_HIP_LEAK_HDR; s.ws = stride;
-	return PC_HIP_OK;
-}
-
-static int pc_spot_launch(pc_hip_spot *sp, pc_spot_member &m, const pc_spot_src &s)
-{
-	if (s.n == 0) return PC_HIP_OK;
 	pc_hip_ctx *c = m.ctx;
 	pc_spot_geo g;
 	g.zp = m.d_zp; g.sel = m.d_sel;
 	g.x0 = sp->x0; g.x1 = sp->x1; g.y0 = sp->y0; g.y1 = sp->y1;
 	g.nx = sp->nx; g.ny = sp->ny; g.np = sp->np; g.ns = sp->ns;
-	const long long cus = c->n_cu;
 	if (!sp->wide) {
-		const long long tiles = ((long long)sp->map_elems + PC_SPOT_TILE - 1)/PC_SPOT_TILE;
-		long long bx = (2*cus + tiles - 1)/tiles;                       /* two workgroups per CU in all (LDS: 64 KiB each) */
-		const long long need = (s.n + PC_SPOT_LDS_BLOCK - 1)/PC_SPOT_LDS_BLOCK;
-		if (bx > need) bx = need;
-		if (bx < 1) bx = 1;
-		hipLaunchKernelGGL(pc_spot_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_map);
+		const long long tiles = ((long long)sp->elems + PC_SPOT_TILE - 1)/PC_SPOT_TILE;
+		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_SPOT_LDS_BLOCK).bx;
+		hipLaunchKernelGGL(pc_spot_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_cells);
 	} else {
 		const long long chunks = (sp->ns + PC_SPOT_ECHUNK - 1)/PC_SPOT_ECHUNK;
-		long long bx = (8*cus + sp->np*chunks - 1)/(sp->np*chunks);
-		int gw = 1;
-		while (gw < sp->ns && gw < 64) gw <<= 1;
-		const long long need = (s.n*gw + PC_SPOT_WIDE_BLOCK - 1)/PC_SPOT_WIDE_BLOCK;
-		if (bx > need) bx = need;
-		if (bx < 1) bx = 1;
-		hipLaunchKernelGGL(pc_spot_wide_kernel, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_map);
+		const long long bx = pc_tally_grid_wide(c->n_cu, sp->np*chunks, sp->ns, s.n, PC_SPOT_WIDE_BLOCK).bx;
+		hipLaunchKernelGGL(pc_spot_wide_kernel, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_cells);
 	}
-	PC_HIP_CHECK(hipGetLastError());
 	return PC_HIP_OK;
 }
 
@@ -306,16 +204,9 @@ int pc_hip_spot_validate(const pc_hip_spot_spec *spec, size_t n_energies)
 		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: nx and ny must be >= 1");
 	if (spec->regime < 0 || spec->regime > 2)
 		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: regime must be 0 (automatic), 1 (LDS tiles) or 2 (energies across lanes)");
-	if (spec->n_energies < 0 || (size_t)spec->n_energies > n_energies || (spec->n_energies > 0 && !spec->energies))
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: between 1 and n_energies energy indices (0 = all energies)");
-	std::vector<char> seen(n_energies, 0);
-	for (int k = 0; k < spec->n_energies; k++) {
-		const int e = spec->energies[k];
-		if (e < 0 || (size_t)e >= n_energies)
-			return pc_fail(PC_HIP_ERR_INVALID, "spot spec: energy index " + std::to_string(e) + " out of range (" + std::to_string(n_energies) + " energies)");
-		if (seen[e]) return pc_fail(PC_HIP_ERR_INVALID, "spot spec: energy index " + std::to_string(e) + " given twice");
-		seen[e] = 1;
-	}
+	std::string why;
+	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &why))
+		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: " + why);
 	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
 	if ((double)spec->n_planes*ns*(double)spec->nx*(double)spec->ny > (double)(1ll << 27))
 		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: n_planes * n_energies * nx * ny exceeds 2^27 bins");
@@ -336,52 +227,23 @@ int pc_hip_group_spot_create(pc_hip_group *group, const pc_hip_spot_spec *spec, 
 
 void pc_hip_spot_destroy(pc_hip_spot *spot)
 {
-	if (!spot) return;
-	for (pc_spot_member &m : spot->m) pc_spot_free_member(m);
 	delete spot;
 }
 
 int pc_hip_spot_add(pc_hip_spot *spot, int kind)
 {
 	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: spot must not be NULL");
-	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
-	pc_hip_group *g = spot->group;
-	if (g && kind == 0 && !g->keep_images)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: the last run kept no exit photons (run it with keep_images)");
-	if (g && kind > 0 && !g->leak_run)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: leak events need a leak_calc run of the group as the last run");
-	/* every member's source first: nothing is added unless the whole add can be */
-	std::vector<pc_spot_src> src(spot->m.size());
-	long long n = 0;
-	for (size_t k = 0; k < spot->m.size(); k++) {
-		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
-		PC_HIP_CHECK(hipSetDevice(spot->m[k].ctx->device));
-		int st = pc_spot_source(spot->m[k].ctx, kind, src[k]);
-		if (st) return st;
-		n += src[k].n;
-	}
-	if (spot->n_entries + n > (long long)0xffffffffll)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_add: a map takes at most 2^32 - 1 entries (its uint64 bins could wrap beyond)");
-	for (size_t k = 0; k < spot->m.size(); k++) {
-		PC_HIP_CHECK(hipSetDevice(spot->m[k].ctx->device));
-		int st = pc_spot_launch(spot, spot->m[k], src[k]);
-		if (st) return st;
-	}
-	spot->n_entries += n;
-	return PC_HIP_OK;
+	return pc_tally_add(*spot, kind, "pc_hip_spot_add",
+		[spot](size_t k, const pc_spot_src &s, int) { return pc_spot_launch(spot, spot->m[k], s); });
 }
 
 int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t *outside, int64_t *n_entries)
 {
 	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_read: spot must not be NULL");
 	const size_t nb = (size_t)spot->nx*spot->ny, n_bins = (size_t)spot->np*spot->ns*nb, n_out = (size_t)spot->np*spot->ns;
-	std::vector<unsigned long long> sum(spot->map_elems, 0ull), part(spot->map_elems);
-	for (pc_spot_member &m : spot->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_map, spot->map_elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
-		for (size_t k = 0; k < spot->map_elems; k++) sum[k] += part[k];       /* exact: the entry cap keeps every sum below 2^64 */
-	}
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum(*spot, 1, sum);
+	if (st) return st;
 	if (bins) {
 		if (!spot->wide)
 			memcpy(bins, sum.data(), n_bins*sizeof(uint64_t));
@@ -392,19 +254,14 @@ int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t *outside, int64
 						bins[((size_t)p*spot->ns + s)*nb + b] = sum[((size_t)p*nb + b)*spot->ns + s];
 	}
 	if (outside) memcpy(outside, sum.data() + n_bins, n_out*sizeof(uint64_t));
-	if (n_entries) *n_entries = spot->n_entries;
+	if (n_entries) *n_entries = spot->n_entries[0] + spot->n_entries[1] + spot->n_entries[2];
 	return PC_HIP_OK;
 }
 
 int pc_hip_spot_reset(pc_hip_spot *spot)
 {
 	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_reset: spot must not be NULL");
-	for (pc_spot_member &m : spot->m) {
-		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemsetAsync(m.d_map, 0, spot->map_elems*sizeof(unsigned long long), m.ctx->stream));
-	}
-	spot->n_entries = 0;
-	return PC_HIP_OK;
+	return pc_tally_reset(*spot);
 }
 
 int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide)
@@ -412,17 +269,6 @@ int pc_hip_spot_info(const pc_hip_spot *spot, int32_t dims[4], int *wide)
 	if (!spot || !dims) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_info: NULL argument");
 	dims[0] = spot->np; dims[1] = spot->ns; dims[2] = spot->ny; dims[3] = spot->nx;
 	if (wide) *wide = spot->wide;
-	return PC_HIP_OK;
-}
-
-int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes)
-{
-	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_device_memory: ctx must not be NULL");
-	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	size_t f = 0, t = 0;
-	PC_HIP_CHECK(hipMemGetInfo(&f, &t));
-	if (free_bytes) *free_bytes = f;
-	if (total_bytes) *total_bytes = t;
 	return PC_HIP_OK;
 }
 

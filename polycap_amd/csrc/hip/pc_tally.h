@@ -1,0 +1,321 @@
+/*
+ * pc_tally.h -- what spot maps (pc_spot.h), exit-beam moments (pc_beam.h) and histograms (pc_hist.h) share.  Each of them is a
+ * tally: a post-pass over the entries the last run left on the device (exit photons as image records or planes, the ordered leak
+ * event lists), accumulated exactly into uint64 cells, per kind, per member of a device group.  Here is the one copy of the
+ * energy selection, the grid sizing, the 128-bit carry add, the entry source and its loader, the lane mapping of the
+ * energies-across-lanes kernels, and the object's lifetime, add, read-back sum and reset.  A tally's own header keeps its per-entry
+ * arithmetic, kernels, cell layout and host formulas.
+ *
+ * The first part (plain functions, no HIP types) compiles for the host as well: -DPC_TALLY_HOST_ONLY stops the header after it.
+ */
+#ifndef PC_TALLY_H
+#define PC_TALLY_H
+
+#include <stddef.h>
+#include <string>
+#include <vector>
+
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
+
+/* The energy selection of a spec: n_sel indices into the problem's n_energies, each once; n_sel = 0 selects all.  false and the
+ * reason in *why (it starts with the spec's field at fault) when it is refused. */
+static inline bool pc_sel_check(int n_sel, const int *sel, size_t n_energies, std::string *why)
+{
+	if (n_sel < 0 || (size_t)n_sel > n_energies || (n_sel > 0 && !sel)) {
+		*why = "n_energies: between 1 and the problem's energy count of indices (0 = all energies)";
+		return false;
+	}
+	std::vector<char> seen(n_energies, 0);
+	for (int k = 0; k < n_sel; k++) {
+		const int e = sel[k];
+		if (e < 0 || (size_t)e >= n_energies) {
+			*why = "energies: index " + std::to_string(e) + " out of range (" + std::to_string(n_energies) + " energies)";
+			return false;
+		}
+		if (seen[e]) {
+			*why = "energies: index " + std::to_string(e) + " given twice";
+			return false;
+		}
+		seen[e] = 1;
+	}
+	return true;
+}
+
+/* the indices a checked selection stands for */
+static inline std::vector<int> pc_sel_fill(int n_sel, const int *sel, size_t n_energies)
+{
+	std::vector<int> out;
+	if (n_sel == 0)
+		for (size_t e = 0; e < n_energies; e++) out.push_back((int)e);
+	else
+		out.assign(sel, sel + n_sel);
+	return out;
+}
+
+/* lanes that share one entry when n energies go across the lanes of a wave: the next power of two, 64 at the most */
+static inline __host__ __device__ int pc_tally_gw(int n)
+{
+	int gw = 1;
+	while (gw < n && gw < 64) gw <<= 1;
+	return gw;
+}
+
+/* gridDim.x of an add, and gw where the energies go across the lanes (0 otherwise) */
+struct pc_tally_grid {
+	long long bx;
+	int gw;
+};
+
+/* no more workgroups than the entries fill, and one at least */
+static inline long long pc_tally_grid_cap(long long bx, long long work, int block)
+{
+	const long long need = (work + block - 1)/block;
+	if (bx > need) bx = need;
+	return (bx < 1) ? 1 : bx;
+}
+
+/* LDS-tile kernels, one lane per entry and gridDim.y = tiles: two workgroups per CU in all (LDS: 64 KiB each) */
+static inline pc_tally_grid pc_tally_grid_tiles(long long cus, long long tiles, long long n_entries, int block)
+{
+	const pc_tally_grid g = { pc_tally_grid_cap((2*cus + tiles - 1)/tiles, n_entries, block), 0 };
+	return g;
+}
+
+/* energies-across-lanes kernels, gw lanes per entry and `groups` workgroups for every gridDim.x: eight workgroups per CU in all */
+static inline pc_tally_grid pc_tally_grid_wide(long long cus, long long groups, int n_sel, long long n_entries, int block)
+{
+	const int gw = pc_tally_gw(n_sel);
+	const pc_tally_grid g = { pc_tally_grid_cap((8*cus + groups - 1)/groups, n_entries*gw, block), gw };
+	return g;
+}
+
+/* (lo, hi) += (add_lo, add_hi) mod 2^128: unsigned, and so two's complement signed as well */
+static inline __host__ __device__ void pc_add128(unsigned long long &lo, unsigned long long &hi, unsigned long long add_lo, unsigned long long add_hi)
+{
+	const unsigned long long o = lo;
+	lo += add_lo;
+	hi += add_hi + (lo < o ? 1ull : 0ull);
+}
+
+#ifndef PC_TALLY_HOST_ONLY
+
+/* Where the entries are: field f of entry i at p[i*ss + f*fs], weight e at w[i*ws + e] */
+struct pc_spot_src {
+	const double *p;
+	long long ss, fs, n;
+	int f_x, f_dx;          /* x, y, z at f_x .. f_x + 2; dx, dy (, dz when has_dz) from f_dx on */
+	int has_dz;
+	const double *w;
+	long long ws;
+};
+
+struct pc_entry { double x, y, z, dx, dy, dz; };
+
+static inline __host__ __device__ double pc_spot_exit_dz(double dx, double dy);      /* pc_spot.h, in the part its host tests compile */
+
+/* position and direction of entry i */
+static __device__ __forceinline__ pc_entry pc_entry_load(const pc_spot_src &s, long long i)
+{
+	const double *p = s.p + i*s.ss;
+	pc_entry e;
+	e.x = p[(long long)s.f_x*s.fs]; e.y = p[(long long)(s.f_x + 1)*s.fs]; e.z = p[(long long)(s.f_x + 2)*s.fs];
+	e.dx = p[(long long)s.f_dx*s.fs]; e.dy = p[(long long)(s.f_dx + 1)*s.fs];
+	e.dz = s.has_dz ? p[(long long)(s.f_dx + 2)*s.fs] : pc_spot_exit_dz(e.dx, e.dy);
+	return e;
+}
+
+/* Energies across lanes: the lanes of a wave take the n (<= 64 at a time) energies of one entry, 64 / gw entries per wave.  Lane
+ * `lane` holds energy sub, sub + gw, ... of the entries first, first + stride, ... */
+struct pc_tally_lanes {
+	int gw, lane, sub;
+	long long first, stride;
+};
+
+static __device__ __forceinline__ pc_tally_lanes pc_tally_lane_map(int n)
+{
+	pc_tally_lanes l;
+	l.gw = pc_tally_gw(n);
+	l.lane = threadIdx.x & 63;
+	l.sub = l.lane & (l.gw - 1);
+	const int per_wave = 64 / l.gw;
+	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
+	l.first = wave*per_wave + l.lane / l.gw;
+	l.stride = n_waves*per_wave;
+	return l;
+}
+
+/* the entries of `kind` that the last run of c left on its device; `who` is the call that asks */
+static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s, const char *who)
+{
+	const long long ne = c->host.pm.n_energies;
+	memset(&s, 0, sizeof(s));
+	if (kind == 0) {
+		if (!c->img_valid)
+			return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": the last run kept no exit photons (run it with keep_images)");
+		if (c->leak_pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
+			int st = pc_hip_transmission_wait(c, nullptr);
+			if (st) return st;
+		}
+		const long long n = c->run_slots;
+		s.n = n; s.f_x = 8; s.f_dx = 11; s.has_dz = 0;          /* pc_exit_coords, pc_exit_dir: planes 8..10, 11..12 */
+		if (c->run_planes) {
+			s.p = c->d_soa; s.ss = 1; s.fs = n;
+			s.w = c->d_soa + (long long)PC_N_FIELDS*n; s.ws = ne;
+		} else {
+			s.p = c->d_img; s.ss = PC_N_FIELDS + ne; s.fs = 1;
+			s.w = c->d_img + PC_N_FIELDS; s.ws = PC_N_FIELDS + ne;
+		}
+		return PC_HIP_OK;
+	}
+	if (!c->leak_events_of_run)
+		return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": leak events need a leak_calc source run (pc_hip_transmission_run_leak) as the last run");
+	int st = pc_hip_transmission_wait(c, nullptr);      /* the events are ordered into d_leak_out when the run is waited for */
+	if (st) return st;
+	const long long stride = PC_HIP_LEAK_HDR + ne;
+	s.n = (kind == 1) ? c->leak_n_ext : c->leak_n_int;
+	s.p = c->d_leak_out + ((kind == 1) ? 0 : c->leak_n_ext*stride);
+	s.ss = stride; s.fs = 1; s.f_x = 2; s.f_dx = 5; s.has_dz = 1;
+	s.w = s.p + PC_HIP_LEAK_HDR; s.ws = stride;
+	return PC_HIP_OK;
+}
+
+/* ---- the object: one set of cells per member of the group (one member without a group) */
+struct pc_tally_member {
+	pc_hip_ctx *ctx = nullptr;
+	pc_dev_buf<unsigned long long> d_cells;
+	pc_dev_buf<int> d_sel;          /* the selected energies' indices, where the tally selects */
+	pc_dev_buf<double> d_zp;        /* plane positions, where it has planes */
+};
+
+struct pc_tally {
+	std::vector<pc_tally_member> m;
+	pc_hip_group *group = nullptr;
+	long long n_entries[3] = {0, 0, 0};       /* added so far, per kind */
+	size_t elems = 0;                         /* cells of a member */
+	int shared = 0;                           /* the kinds add to the same cells: the entry cap holds for them together */
+	~pc_tally();
+};
+
+/* what was enqueued on a member's stream is over before its buffers go */
+static void pc_tally_destroy(pc_tally &t)
+{
+	for (pc_tally_member &m : t.m) {
+		if (!m.ctx) continue;
+		(void)hipSetDevice(m.ctx->device);
+		if (m.ctx->stream) (void)hipStreamSynchronize(m.ctx->stream);
+		m = pc_tally_member();
+	}
+	t.m.clear();
+}
+
+inline pc_tally::~pc_tally() { pc_tally_destroy(*this); }
+
+static int pc_tally_hip(hipError_t e, const char *who)
+{
+	if (e == hipSuccess) return PC_HIP_OK;
+	(void)hipGetLastError();
+	return pc_fail(e == hipErrorOutOfMemory ? PC_HIP_ERR_MEMORY : PC_HIP_ERR_RUNTIME, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+/* `elems` zeroed cells on every context's device; nothing stays allocated when it fails */
+static int pc_tally_make(pc_tally &t, const std::vector<pc_hip_ctx *> &ctxs, pc_hip_group *group, size_t elems, const char *who)
+{
+	const std::string msg = std::string(who) + ": could not allocate the cells";
+	t.group = group;
+	t.elems = elems;
+	for (pc_hip_ctx *c : ctxs) {
+		t.m.emplace_back();
+		pc_tally_member &m = t.m.back();
+		m.ctx = c;
+		int st = pc_tally_hip(hipSetDevice(c->device), who);
+		if (!st) st = m.d_cells.grow(elems, msg.c_str());
+		if (!st) st = pc_tally_hip(hipMemsetAsync(m.d_cells, 0, elems*sizeof(unsigned long long), c->stream), who);
+		if (st) { pc_tally_destroy(t); return st; }
+	}
+	return PC_HIP_OK;
+}
+
+/* the energy selection and the plane positions (either may be empty) to every member; as pc_tally_make when it fails */
+static int pc_tally_upload(pc_tally &t, const std::vector<int> &sel, const std::vector<double> &zp, const char *who)
+{
+	const std::string msg = std::string(who) + ": could not allocate the energy selection and the plane positions";
+	for (pc_tally_member &m : t.m) {
+		int st = pc_tally_hip(hipSetDevice(m.ctx->device), who);
+		if (!st) st = m.d_sel.grow(sel.size(), msg.c_str());
+		if (!st) st = m.d_zp.grow(zp.size(), msg.c_str());
+		if (!st && !sel.empty()) st = pc_tally_hip(hipMemcpy(m.d_sel, sel.data(), sel.size()*sizeof(int), hipMemcpyHostToDevice), who);
+		if (!st && !zp.empty()) st = pc_tally_hip(hipMemcpy(m.d_zp, zp.data(), zp.size()*sizeof(double), hipMemcpyHostToDevice), who);
+		if (st) { pc_tally_destroy(t); return st; }
+	}
+	return PC_HIP_OK;
+}
+
+/* Adds the entries of `kind` of the last run: launch(k, src, kind) enqueues member k's non-empty source on its stream (its device
+ * is current) and returns a status. */
+template <typename Launch>
+static int pc_tally_add(pc_tally &t, int kind, const char *who, Launch launch)
+{
+	const std::string w(who);
+	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, w + ": kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
+	const pc_hip_group *g = t.group;
+	if (g && kind == 0 && !g->keep_images)
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the last run kept no exit photons (run it with keep_images)");
+	if (g && kind > 0 && !g->leak_run)
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": leak events need a leak_calc run of the group as the last run");
+	/* every member's source first: nothing is added unless the whole add can be */
+	std::vector<pc_spot_src> src(t.m.size());
+	long long n = 0;
+	for (size_t k = 0; k < t.m.size(); k++) {
+		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
+		PC_HIP_CHECK(hipSetDevice(t.m[k].ctx->device));
+		const int st = pc_spot_source(t.m[k].ctx, kind, src[k], who);
+		if (st) return st;
+		n += src[k].n;
+	}
+	const long long held = t.shared ? t.n_entries[0] + t.n_entries[1] + t.n_entries[2] : t.n_entries[kind];
+	if (held + n > (long long)0xffffffffll)
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the cells of a kind take at most 2^32 - 1 entries (their exact sums could wrap beyond)");
+	for (size_t k = 0; k < t.m.size(); k++) {
+		if (src[k].n == 0) continue;
+		PC_HIP_CHECK(hipSetDevice(t.m[k].ctx->device));
+		const int st = launch(k, src[k], kind);
+		if (st) return st;
+		PC_HIP_CHECK(hipGetLastError());
+	}
+	t.n_entries[kind] += n;
+	return PC_HIP_OK;
+}
+
+/* The members' cells summed on the host.  limbs = 1: uint64 cells; 2: (lo, hi) pairs with carry.  Exact either way: the entry cap
+ * keeps every sum in range. */
+static int pc_tally_sum(pc_tally &t, int limbs, std::vector<unsigned long long> &sum)
+{
+	std::vector<unsigned long long> part(t.elems);
+	sum.assign(t.elems, 0ull);
+	for (pc_tally_member &m : t.m) {
+		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
+		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_cells, t.elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
+		if (limbs == 2)
+			for (size_t k = 0; k < t.elems; k += 2) pc_add128(sum[k], sum[k + 1], part[k], part[k + 1]);
+		else
+			for (size_t k = 0; k < t.elems; k++) sum[k] += part[k];
+	}
+	return PC_HIP_OK;
+}
+
+static int pc_tally_reset(pc_tally &t)
+{
+	for (pc_tally_member &m : t.m) {
+		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
+		PC_HIP_CHECK(hipMemsetAsync(m.d_cells, 0, t.elems*sizeof(unsigned long long), m.ctx->stream));
+	}
+	for (int k = 0; k < 3; k++) t.n_entries[k] = 0;
+	return PC_HIP_OK;
+}
+
+#endif /* PC_TALLY_HOST_ONLY */
+#endif /* PC_TALLY_H */

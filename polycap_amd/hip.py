@@ -466,39 +466,34 @@ def relay_efficiencies(sumw_fixed, sumw2_fixed, counters):
 SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}
 
 
-class SpotMap:
-    """Spot maps of a TraceContext or a TraceGroup (pc_hip_spot_*): weighted 2-D histograms of where the entries of the last run
-    cross planes `distances` cm behind the optic's exit face, inside the window (x0, x1, y0, y1) cm cut into bins = (nx, ny),
-    one map per selected energy (energies: indices, None = all).  Exact uint64 sums of round_half_even(w * 2^32); the contract is
-    written down in include/polycap-hip.h.  regime: 0 automatic, 1 LDS tiles, 2 energies across lanes."""
+def _kind(kind):
+    return SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
 
-    def __init__(self, owner, distances, window, bins, energies=None, regime=0):
+
+class _Tally:
+    """What SpotMap, BeamMoments and Histograms share: the handle of a pc_hip_<_stem>_* object made on a TraceContext or a
+    TraceGroup, its lifetime, add and reset."""
+    _stem = None
+
+    def _create(self, owner, spec=None):
         self._L = _cabi.lib()
-        self.owner = owner                      # keeps the context alive as long as the map
-        self.distances = np.ascontiguousarray(distances, dtype=np.float64).ravel()
-        self.window = tuple(float(v) for v in window)
-        self.nx, self.ny = (int(bins[0]), int(bins[1]))
-        self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
-        spec = _cabi.SpotSpecS(self.distances.shape[0], dptr(self.distances), *self.window, self.nx, self.ny,
-                               0 if self.energies is None else self.energies.shape[0],
-                               None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
+        self.owner = owner                      # keeps the context alive as long as the object
         h = C.c_void_p()
-        if isinstance(owner, TraceGroup):
-            st = self._L.pc_hip_group_spot_create(owner._h, C.byref(spec), C.byref(h))
-        else:
-            st = self._L.pc_hip_spot_create(owner._h, C.byref(spec), C.byref(h))
+        name = "pc_hip_%s%s_create" % ("group_" if isinstance(owner, TraceGroup) else "", self._stem)
+        st = getattr(self._L, name)(owner._h, *(() if spec is None else (C.byref(spec),)), C.byref(h))
         if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_spot_create", st)
+            raise HipError("pc_hip_%s_create" % self._stem, st)
         self._h = h
-        dims = (C.c_int32 * 4)()
-        wide = C.c_int(0)
-        self._L.pc_hip_spot_info(self._h, dims, C.byref(wide))
-        self.shape = tuple(int(d) for d in dims)       # (planes, selected energies, ny, nx)
-        self.wide = bool(wide.value)
+
+    def _call(self, what, *args):
+        name = "pc_hip_%s_%s" % (self._stem, what)
+        st = getattr(self._L, name)(self._h, *args)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError(name, st)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.pc_hip_spot_destroy(self._h)
+            getattr(self._L, "pc_hip_%s_destroy" % self._stem)(self._h)
             self._h = None
 
     def __del__(self):
@@ -515,15 +510,34 @@ class SpotMap:
 
     def add(self, kind="exit"):
         """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
-        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
-        st = self._L.pc_hip_spot_add(self._h, k)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_spot_add", st)
+        self._call("add", _kind(kind))
 
     def reset(self):
-        st = self._L.pc_hip_spot_reset(self._h)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_spot_reset", st)
+        self._call("reset")
+
+
+class SpotMap(_Tally):
+    """Spot maps of a TraceContext or a TraceGroup (pc_hip_spot_*): weighted 2-D histograms of where the entries of the last run
+    cross planes `distances` cm behind the optic's exit face, inside the window (x0, x1, y0, y1) cm cut into bins = (nx, ny),
+    one map per selected energy (energies: indices, None = all).  Exact uint64 sums of round_half_even(w * 2^32); the contract is
+    written down in include/polycap-hip.h.  regime: 0 automatic, 1 LDS tiles, 2 energies across lanes."""
+
+    _stem = "spot"
+
+    def __init__(self, owner, distances, window, bins, energies=None, regime=0):
+        self.distances = np.ascontiguousarray(distances, dtype=np.float64).ravel()
+        self.window = tuple(float(v) for v in window)
+        self.nx, self.ny = (int(bins[0]), int(bins[1]))
+        self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
+        spec = _cabi.SpotSpecS(self.distances.shape[0], dptr(self.distances), *self.window, self.nx, self.ny,
+                               0 if self.energies is None else self.energies.shape[0],
+                               None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
+        self._create(owner, spec)
+        dims = (C.c_int32 * 4)()
+        wide = C.c_int(0)
+        self._L.pc_hip_spot_info(self._h, dims, C.byref(wide))
+        self.shape = tuple(int(d) for d in dims)       # (planes, selected energies, ny, nx)
+        self.wide = bool(wide.value)
 
     def read(self):
         """bins [planes, energies, ny, nx] and outside [planes, energies] as uint64, the entry count, and the same as weights
@@ -532,10 +546,7 @@ class SpotMap:
         bins = np.zeros(self.shape, dtype=np.uint64)
         out = np.zeros((np_, ns), dtype=np.uint64)
         n = C.c_int64(0)
-        st = self._L.pc_hip_spot_read(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      C.byref(n))
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_spot_read", st)
+        self._call("read", bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n))
         return dict(bins=bins, outside=out, n_entries=int(n.value), maps=bins.astype(np.float64) * 2.0 ** -32,
                     outside_map=out.astype(np.float64) * 2.0 ** -32)
 
@@ -569,54 +580,18 @@ def beam_params(sums, distances=None):
     return out
 
 
-class BeamMoments:
+class BeamMoments(_Tally):
     """Exit-beam moments of a TraceContext or a TraceGroup (pc_hip_beam_*): the exact second-moment matrix of position and slope
     of the entries of the last run at the optic's exit face, per energy, as signed 128-bit integer sums on the device.  The
     contract is written down in include/polycap-hip.h.  One object keeps the sums of all three kinds (exit, extleak, intleak)."""
 
+    _stem = "beam"
+
     def __init__(self, owner):
-        self._L = _cabi.lib()
-        self.owner = owner                      # keeps the context alive as long as the sums
-        h = C.c_void_p()
-        if isinstance(owner, TraceGroup):
-            st = self._L.pc_hip_group_beam_create(owner._h, C.byref(h))
-        else:
-            st = self._L.pc_hip_beam_create(owner._h, C.byref(h))
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_beam_create", st)
-        self._h = h
+        self._create(owner)
         ne = C.c_int(0)
         self._L.pc_hip_beam_info(self._h, C.byref(ne))
         self.n_energies = int(ne.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.pc_hip_beam_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def add(self, kind="exit"):
-        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
-        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
-        st = self._L.pc_hip_beam_add(self._h, k)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_beam_add", st)
-
-    def reset(self):
-        st = self._L.pc_hip_beam_reset(self._h)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_beam_reset", st)
 
     def read(self):
         """sums uint64 [3, n_energies, 15, 2] of (lo, hi) pairs (kinds exit, extleak, intleak; sums in the order of BEAM_SUMS),
@@ -625,15 +600,12 @@ class BeamMoments:
         sums = np.zeros((3, ne, 15, 2), dtype=np.uint64)
         out = np.zeros((3, ne), dtype=np.uint64)
         n = (C.c_int64 * 3)()
-        st = self._L.pc_hip_beam_read(self._h, sums.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_beam_read", st)
+        self._call("read", sums.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
         return dict(sums=sums, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64))
 
     def params(self, distances=None, kind="exit"):
         """beam_params of the sums of `kind` read now"""
-        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
-        return beam_params(self.read()["sums"][k], distances)
+        return beam_params(self.read()["sums"][_kind(kind)], distances)
 
 
 HIST_QUANTITIES = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z")
@@ -673,27 +645,20 @@ def hist_quantile(bins, lo, hi, q, outside=0):
                                                   int(outside), float(q)))
 
 
-class Histograms:
+class Histograms(_Tally):
     """Histograms of a TraceContext or a TraceGroup (pc_hip_hist_*): weighted 1-D histograms of per-entry quantities of the last
     run, one per axis and selected energy (energies: indices, None = all), all filled in one pass.  Exact uint64 sums of
     round_half_even(w * 2^32), kept per kind (exit, extleak, intleak); the contract is written down in include/polycap-hip.h.
     axes: see hist_axes.  regime: 0 automatic, 1 workgroup-private LDS histograms, 2 energies across lanes."""
 
+    _stem = "hist"
+
     def __init__(self, owner, axes, energies=None, regime=0):
-        self._L = _cabi.lib()
-        self.owner = owner                      # keeps the context alive as long as the histograms
         self._axes = hist_axes(axes)
         self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
         spec = _cabi.HistSpecS(len(axes), self._axes, 0 if self.energies is None else self.energies.shape[0],
                                None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
-        h = C.c_void_p()
-        if isinstance(owner, TraceGroup):
-            st = self._L.pc_hip_group_hist_create(owner._h, C.byref(spec), C.byref(h))
-        else:
-            st = self._L.pc_hip_hist_create(owner._h, C.byref(spec), C.byref(h))
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_hist_create", st)
-        self._h = h
+        self._create(owner, spec)
         dims = (C.c_int32 * 3)()
         off = (C.c_int32 * (len(axes) + 1))()
         reg = C.c_int(0)
@@ -704,35 +669,6 @@ class Histograms:
         self.axes = [dict(axis=HIST_QUANTITIES[a.quantity], d=a.d, centre=(a.cx, a.cy), range=(a.lo, a.hi), bins=a.n_bins)
                      for a in self._axes[:self.n_axes]]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.pc_hip_hist_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def add(self, kind="exit"):
-        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
-        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
-        st = self._L.pc_hip_hist_add(self._h, k)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_hist_add", st)
-
-    def reset(self):
-        st = self._L.pc_hip_hist_reset(self._h)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_hist_reset", st)
-
     def read(self):
         """bins uint64 [3, energies, total_bins] (kinds exit, extleak, intleak; the axes one after the other), outside uint64
         [3, axes, energies], n_entries [3]; axes: per axis a view [3, energies, n_bins] of the bins; edges: per axis its n_bins + 1
@@ -740,16 +676,14 @@ class Histograms:
         bins = np.zeros((3, self.n_selected, self.total_bins), dtype=np.uint64)
         out = np.zeros((3, self.n_axes, self.n_selected), dtype=np.uint64)
         n = (C.c_int64 * 3)()
-        st = self._L.pc_hip_hist_read(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_hist_read", st)
+        self._call("read", bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
         o = self.offsets
         return dict(bins=bins, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
                     axes=[bins[:, :, o[a]:o[a + 1]] for a in range(self.n_axes)],
                     edges=[np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in self.axes])
 
     def _one(self, axis, energy, kind):
-        k = SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        k = _kind(kind)
         r = self.read()
         return r["axes"][axis][k, energy], self.axes[axis]["range"], r["outside"][k, axis, energy]
 

@@ -5,8 +5,9 @@
 Cases: xos1 at 10 keV with 1e7 exit photons kept on the device (images, not fetched); xos1 on its 291-energy grid with 1e6 slots;
 a leak_calc run of 262144 slots at 10 and 20 keV (exit photons, extleak and intleak added).  For each case: the run's kernel time
 (ctx.wait), then 5 timed passes of reset + add + read after one warm-up, as wall time around calls that end in a stream
-synchronisation, minus the time of a read alone (the copy of the sums and the synchronisation).  For the kernel time alone run the
-script under rocprofv3 --kernel-trace --stats (pc_beam_kernel).  Every pass must give the same sums bit for bit."""
+synchronisation, minus the median time of a read alone (the copy of the sums and the synchronisation), as median (min .. max).
+For the kernel time alone run the script under rocprofv3 --kernel-trace --stats (pc_beam_kernel).  Every pass must give the same
+sums bit for bit."""
 import os
 import sys
 import time
@@ -40,7 +41,8 @@ def timed(b, kinds, reps=5):
         t_pass.append((time.perf_counter() - t0) * 1e3)
         assert np.array_equal(r["sums"], ref["sums"]) and np.array_equal(r["outside"], ref["outside"]), "sums differ between passes"
         assert np.array_equal(r["n_entries"], ref["n_entries"])
-    return np.median(t_pass) - np.median(t_read), min(t_pass) - min(t_read), ref
+    base = np.median(t_read)
+    return np.median(t_pass) - base, min(t_pass) - base, max(t_pass) - base, ref
 
 
 def main():
@@ -54,11 +56,11 @@ def main():
             run_ms = ctx.wait()
             kern = ctx.last_kernel()
             with polycap_amd.BeamMoments(ctx) as b:
-                med, best, ref = timed(b, kinds)
+                med, best, worst, ref = timed(b, kinds)
             p = polycap_amd.beam_params(ref["sums"][0])
         share = 100.0 * med / run_ms
-        print("%s: run kernel %.2f ms (%s), beam pass %.3f ms median (best %.3f) = %.2f %% of the run; entries %s; bit-identical "
-              "over 6 passes" % (label, run_ms, kern, med, best, share,
+        print("%s: run kernel %.2f ms (%s), beam pass %.3f ms median (%.3f .. %.3f) = %.2f %% of the run; entries %s; bit-identical "
+              "over 6 passes" % (label, run_ms, kern, med, best, worst, share,
                                  ref["n_entries"].tolist()), flush=True)
         e = 0 if energies is not None else int(np.argmin(np.abs(np.asarray(prob.energies) - 10.0)))
         print("    at %.2f keV: waist_r %.4f cm, size_waist_r %.3e cm, size_exit_r %.3e cm, div_x %.3e rad" % (

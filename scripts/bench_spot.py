@@ -20,14 +20,17 @@ WIN = (-0.02, 0.02, -0.02, 0.02)
 
 
 def time_add(ctx, m, reps=5):
+    """one add, enqueue to the end of its kernel, `reps` times after a warm-up: "median (min .. max)" in ms"""
     m.add("exit")
-    ctx.device_synchronize()
     m.reset()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        m.add("exit")
     ctx.device_synchronize()
-    return (time.perf_counter() - t0) / reps * 1e3
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        m.add("exit")
+        ctx.device_synchronize()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return "%.3f ms per add median (%.3f .. %.3f)" % (float(np.median(t)), min(t), max(t))
 
 
 def kernel(n):
@@ -40,7 +43,7 @@ def kernel(n):
         for bins in (128, 1024):
             for regime in (1, 2):
                 with polycap_amd.SpotMap(ctx, [1.0], WIN, (bins, bins), regime=regime) as m:
-                    print("  map %4d^2, %s: %.3f ms per add" % (bins, "energies across lanes" if m.wide else "LDS tiles",
+                    print("  map %4d^2, %s: %s" % (bins, "energies across lanes" if m.wide else "LDS tiles",
                                                               time_add(ctx, m)), flush=True)
     prob = polycap_amd.problem_from_inp(INP)
     with polycap_amd.TraceContext(prob) as ctx:
@@ -50,8 +53,8 @@ def kernel(n):
         for regime in (1, 2):
             for sel in ([0, 100, 200], list(range(0, prob.n_energies, 36)), None):
                 with polycap_amd.SpotMap(ctx, [1.0], WIN, (64, 64), energies=sel, regime=regime) as m:
-                    print("  map 64^2 x %3d energies, %s: %.3f ms per add" % (m.shape[1], "energies across lanes" if m.wide else "LDS tiles",
-                                                                            time_add(ctx, m, reps=2)), flush=True)
+                    print("  map 64^2 x %3d energies, %s: %s" % (m.shape[1], "energies across lanes" if m.wide else "LDS tiles",
+                                                                            time_add(ctx, m, reps=3)), flush=True)
 
 
 def api(n):
