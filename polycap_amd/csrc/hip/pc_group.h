@@ -269,23 +269,15 @@ int pc_hip_group_images(pc_hip_group *g, const pc_hip_images *dst)
 	std::vector<int> status(N, PC_HIP_OK);
 	std::vector<std::string> msg(N);
 	const size_t ne = (size_t)g->ctx[0]->host.pm.n_energies;
+	void *planes[PC_N_FIELDS + 1];
+	pc_image_planes(dst, planes);
 	auto fetch = [&](size_t k) {
 		if (g->count[k] == 0) return;
 		const size_t o = (size_t)g->first[k];
-		pc_hip_images d = *dst;
-		for (int j = 0; j < 2; j++) {
-			if (d.src_start_coords[j]) d.src_start_coords[j] += o;
-			if (d.pc_start_coords[j]) d.pc_start_coords[j] += o;
-			if (d.pc_start_dir[j]) d.pc_start_dir[j] += o;
-			if (d.pc_start_elecv[j]) d.pc_start_elecv[j] += o;
-			if (d.pc_exit_dir[j]) d.pc_exit_dir[j] += o;
-			if (d.pc_exit_elecv[j]) d.pc_exit_elecv[j] += o;
-		}
-		for (int j = 0; j < 3; j++) if (d.pc_exit_coords[j]) d.pc_exit_coords[j] += o;
-		if (d.pc_exit_nrefl) d.pc_exit_nrefl += o;
-		if (d.pc_exit_dtravel) d.pc_exit_dtravel += o;
-		if (d.exit_coord_weights) d.exit_coord_weights += o*ne;
-		status[k] = pc_hip_transmission_images(g->ctx[k], 0, g->count[k], &d);
+		void *d[PC_N_FIELDS + 1];
+		for (int f = 0; f <= PC_N_FIELDS; f++)
+			d[f] = planes[f] ? (double *)planes[f] + o*(f < PC_N_FIELDS ? 1 : ne) : nullptr;
+		status[k] = pc_fetch_images(g->ctx[k], 0, g->count[k], d, nullptr);
 		if (status[k]) msg[k] = g_last_error;       /* the error text is per thread */
 	};
 	/* The destination planes are pinned here, once and whole: the members' sub-ranges share pages at their boundaries, and
@@ -293,25 +285,19 @@ int pc_hip_group_images(pc_hip_group *g, const pc_hip_images *dst)
 	 * find their ranges pinned already and leave them alone). */
 	std::vector<void *> pinned;
 	if (N > 1) {
-		void *planes[PC_N_FIELDS + 1] = {
-			dst->src_start_coords[0], dst->src_start_coords[1], dst->pc_start_coords[0], dst->pc_start_coords[1],
-			dst->pc_start_dir[0], dst->pc_start_dir[1], dst->pc_start_elecv[0], dst->pc_start_elecv[1],
-			dst->pc_exit_coords[0], dst->pc_exit_coords[1], dst->pc_exit_coords[2],
-			dst->pc_exit_dir[0], dst->pc_exit_dir[1], dst->pc_exit_elecv[0], dst->pc_exit_elecv[1],
-			dst->pc_exit_nrefl, dst->pc_exit_dtravel, dst->exit_coord_weights };
 		(void)hipSetDevice(g->devices[0]);
 		std::vector<std::pair<char *, size_t>> ranges;
 		for (int f = 0; f <= PC_N_FIELDS; f++)
 			if (planes[f]) ranges.emplace_back((char *)planes[f], (size_t)g->run_slots*sizeof(double)*(f < PC_N_FIELDS ? 1 : ne));
 		/* pinned or not, the members pin nothing themselves: they would pin neighbouring pieces of the same pages */
 		(void)pc_pin_ranges(ranges, hipHostRegisterPortable, pinned);
-		for (pc_hip_ctx *c : g->ctx) c->dst_prepinned = 1;
+		for (pc_hip_ctx *c : g->ctx) c->img.opts.dst_prepinned = 1;
 	}
 	std::vector<std::thread> th;
 	for (size_t k = 1; k < N; k++) th.emplace_back(fetch, k);
 	fetch(0);
 	for (auto &t : th) t.join();
-	for (pc_hip_ctx *c : g->ctx) c->dst_prepinned = 0;
+	for (pc_hip_ctx *c : g->ctx) c->img.opts.dst_prepinned = 0;
 	for (void *p : pinned) (void)hipHostUnregister(p);
 	for (size_t k = 0; k < N; k++)
 		if (status[k]) return pc_fail(status[k], msg[k]);

@@ -34,6 +34,7 @@
 #include "pc_problem.h"
 #include "pc_moments.h"
 #include "pc_plan.h"
+#include "pc_images.h"
 
 #ifndef PC_MARCH_UNROLL
 #define PC_MARCH_UNROLL 4      /* march steps between two ballots of the burst loop.  With march_stop = 8 (a burst goes on while 8 lanes march):
@@ -52,14 +53,6 @@
 #endif
 
 /* --------------------------------------------------------------------------- kernel arguments */
-
-/* Per-exit-photon image record in HBM: one contiguous record per slot (17 + n_energies doubles) so that a lane
- * writes whole 64/128-byte segments instead of 18 scattered 8-byte words; the host side of the fetch (pc_hip_transmission_images) turns a
- * range of records into the reference's SoA planes (struct _polycap_images) when the host asks for them.
- * Field order = pc_hip_images / the reference's plane order. */
-enum { PC_F_SRCX = 0, PC_F_SRCY, PC_F_STARTX, PC_F_STARTY, PC_F_SDIRX, PC_F_SDIRY, PC_F_SEVX, PC_F_SEVY,
-       PC_F_EXITX, PC_F_EXITY, PC_F_EXITZ, PC_F_EDIRX, PC_F_EDIRY, PC_F_EEVX, PC_F_EEVY, PC_F_NREFL, PC_F_DTRAVEL,
-       PC_F_WEIGHTS, PC_N_FIELDS = 17 };
 
 struct pc_totals {             /* device-resident totals of one run */
 	unsigned long long counters[8];   /* iexit, not_entered, not_transmitted, sum_irefl, failed_slots, launches */
@@ -942,94 +935,6 @@ __global__ void pc_sample_kernel(pc_params pm, unsigned long long seed, long lon
 	o[6] = s.ex; o[7] = s.ey; o[8] = s.ez; o[9] = s.srcx; o[10] = s.srcy; o[11] = 0.;
 }
 
-/* host threads that turn fetched image records (AoS, `rec` doubles per slot) into the caller's SoA planes */
-struct pc_copy_piece { const double *from; size_t slot; size_t n; };      /* n records at `from` belong to slots [slot, slot + n) */
-
-class pc_copy_workers {
-public:
-	explicit pc_copy_workers(int n)
-	{
-		for (int t = 1; t < n; t++) threads_.emplace_back([this]() { loop(); });
-	}
-	~pc_copy_workers()
-	{
-		{ std::lock_guard<std::mutex> g(m_); stop_ = true; }
-		cv_work_.notify_all();
-		for (auto &t : threads_) t.join();
-	}
-	/* scatters every piece; returns when all are done (the calling thread works too) */
-	void run(const std::vector<pc_copy_piece> &pieces, void *const *planes, double *weights, size_t rec, size_t ne, double *raw = nullptr)
-	{
-		{
-			std::lock_guard<std::mutex> g(m_);
-			pieces_ = &pieces; planes_ = planes; weights_ = weights; rec_ = rec; ne_ = ne; raw_ = raw;
-			next_.store(0); busy_ = (int)threads_.size(); gen_++;
-		}
-		cv_work_.notify_all();
-		drain();
-		std::unique_lock<std::mutex> g(m_);
-		cv_done_.wait(g, [this]() { return busy_ == 0; });
-		pieces_ = nullptr;
-	}
-private:
-	void drain()
-	{
-		const std::vector<pc_copy_piece> &pieces = *pieces_;
-		const size_t rec = rec_, ne = ne_;
-		const size_t nplanes = rec - ne;
-		for (size_t j = next_.fetch_add(1); j < pieces.size(); j = next_.fetch_add(1)) {
-			const pc_copy_piece &p = pieces[j];
-			if (raw_) { memcpy(raw_ + p.slot*rec, p.from, p.n*rec*sizeof(double)); continue; }     /* records as they are */
-			/* plane by plane: strided reads of a piece that fits the cache, contiguous writes (8-byte words: the
-			 * reflection count is an int64 plane) */
-			for (size_t k = 0; k < nplanes; k++) {
-				if (!planes_[k]) continue;
-				double *to = (double *)planes_[k] + p.slot;
-				const double *from = p.from + k;
-				for (size_t i = 0; i < p.n; i++) to[i] = from[i*rec];
-			}
-			if (weights_) {
-				if (ne == 1) {
-					double *to = weights_ + p.slot;
-					const double *from = p.from + nplanes;
-					for (size_t i = 0; i < p.n; i++) to[i] = from[i*rec];
-				} else {
-					for (size_t i = 0; i < p.n; i++)
-						memcpy(weights_ + (p.slot + i)*ne, p.from + i*rec + nplanes, ne*sizeof(double));
-				}
-			}
-		}
-	}
-	void loop()
-	{
-		unsigned long seen = 0;
-		for (;;) {
-			{
-				std::unique_lock<std::mutex> g(m_);
-				cv_work_.wait(g, [&]() { return stop_ || gen_ != seen; });
-				if (stop_) return;
-				seen = gen_;
-			}
-			drain();
-			{
-				std::lock_guard<std::mutex> g(m_);
-				if (--busy_ == 0) cv_done_.notify_all();
-			}
-		}
-	}
-	std::vector<std::thread> threads_;
-	std::mutex m_;
-	std::condition_variable cv_work_, cv_done_;
-	const std::vector<pc_copy_piece> *pieces_ = nullptr;
-	void *const *planes_ = nullptr;
-	double *weights_ = nullptr, *raw_ = nullptr;
-	size_t rec_ = 0, ne_ = 0;
-	std::atomic<size_t> next_{0};
-	unsigned long gen_ = 0;
-	int busy_ = 0;
-	bool stop_ = false;
-};
-
 static thread_local std::string g_last_error;
 
 static int pc_fail(int code, const std::string &msg)
@@ -1040,8 +945,6 @@ static int pc_fail(int code, const std::string &msg)
 
 #define PC_HIP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
 	return pc_fail(PC_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-
-#define PC_MAX_PARTS 16
 
 /* Owners of the GPU resources of a context: each frees what it holds when it is reset or destroyed.  None of them switches
  * devices; whoever resets or destroys one has made its device current. */
@@ -1172,6 +1075,9 @@ struct pc_event_handle {
 	hipError_t ensure(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
 };
 
+#define PC_IMAGES_STORE
+#include "pc_images.h"      /* the store and the fetch: behind the kernels and the owner types */
+
 /* what a context was last asked to do (pc_hip_ctx::last_call) */
 enum { PC_CALL_NONE = 0, PC_CALL_RUN, PC_CALL_RUN_LEAK, PC_CALL_EXPLICIT, PC_CALL_SCAN, PC_CALL_RELAY };
 
@@ -1200,46 +1106,8 @@ struct pc_hip_ctx {
 	/* last run */
 	pc_dev_buf<pc_totals> d_totals;        /* totals_bytes: pc_totals + 2*nE u64 weight sums + 2*nE u64 squared-weight sums */
 	size_t totals_bytes = 0;
-	pc_dev_buf<double> d_img;              /* image records: n_slots x (17 + n_energies) doubles */
-	pc_host_buf<double, PC_PIN_OR_PLAIN> h_stage; /* image fetches: two pinned chunks of records on the host */
-	pc_event_handle ev_fetch[2];
-	pc_stream_handle fetch_stream;         /* copies of finished parts run beside the kernel of the next part */
-	pc_stream_handle fetch_stream_b;       /* compact runs: the planes of a group of blocks alternate between two copy streams */
-	pc_event_handle ev_group[2][4];        /* compact runs: end of a group of copies, per stream, ring of 4 */
-	pc_stream_handle stream2;              /* odd parts: a part's first workgroups start as the previous part's last ones leave */
+	pc_image_store img;                    /* the exit-photon images of the last run, their options and the way out (pc_images.h) */
 	pc_dev_buf<unsigned long long> d_work; /* one work counter per part */
-	pc_event_handle ev_sync;
-	/* a transmission run can be cut into parts (kernel launches over consecutive slot ranges, same totals): the images of
-	 * a finished part are fetched while the next part is traced */
-	int run_parts = 1;
-	int n_parts = 1;
-	long long part_end[PC_MAX_PARTS] = {0};
-	pc_event_handle ev_part[PC_MAX_PARTS];
-	int fetch_threads = 0;                 /* host threads that scatter a fetched chunk into the caller's planes; 0 = min(16, cores) */
-	int img_valid = 0;
-	/* plane (SoA) copy of the image records on the device: 17 planes of the run's n_slots doubles, then the weights [slot][n_energies].
-	 * pc_hip_transmission_images copies from here straight into the caller's (registered) planes -- no host transposition */
-	pc_dev_buf<double> d_soa;
-	int plane_images = 0;                  /* option "plane_images": runs that keep images write the planes themselves (no records) */
-	int run_planes = 0;                    /* the last run did so */
-	/* option "compact_images" (with plane_images): exit photons are stored in the order of completion, one coalesced run per
-	 * plane and batch, and the planes are published block by block while the kernel runs (pc_kargs::img_cursor) */
-	int compact_images = 0;
-	int compact_parts = 1;                 /* option "compact_parts": launches a compact run of 4e6 slots or more is traced in (alternating between two
-	                                        * streams, each with its own half of the per-lane scratch: pc_launch_site).  Measured, not adopted: 2 launches 20.95 ms against 19.6 ms for one (1e7 slots; profiles/r04/kernel_history.md) */
-	int run_compact = 0;                   /* the last run did so */
-	int dst_prepinned = 0;                 /* the caller (a device group) has pinned the destination planes itself: the fetch pins nothing */
-	int keep_pinned = 0;                   /* option "keep_pinned": pc_hip_transmission_images leaves the destination planes pinned */
-	int slot_ids = 0;                      /* option "slot_ids": compact runs also store which slot sits at which position */
-	int blk_shift = 16;                    /* option "block_shift": published blocks of 2^blk_shift positions (65536: 512 KB per plane; the fetch
-	                                        * copies all the blocks that are complete at a time in one go) */
-	int run_blk_shift = 16;
-	long long run_blocks = 0;
-	pc_dev_buf<unsigned long long> d_cursor;
-	pc_dev_buf<unsigned int> d_blk_done;
-	pc_host_buf<unsigned int, PC_PIN_MAPPED> h_blk_flag; /* mapped into the device (h_blk_flag.dev): 1 when a block is complete */
-	pc_dev_buf<long long> d_ids;
-	pc_dev_buf<double> d_lane_start;
 	pc_dev_buf<double> d_wscratch;
 	/* explicit-photon calls (polycap_photon_launch, polycap_source_get_photon): one device buffer and one pinned host
 	 * buffer, kept between calls, so that a single photon costs two copies and a launch instead of ten copies and
@@ -1522,6 +1390,7 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 		if (*e == '0' || *e == '1') ctx->opts.producer = *e - '0';
 	PC_CTX_CHECK(ctx->ev0.ensure(hipEventDefault));
 	PC_CTX_CHECK(ctx->ev1.ensure(hipEventDefault));
+	ctx->img.bind(ctx->host.ec.size(), ctx->stream, ctx->ev1);
 	PC_CTX_GROW(ctx->d_tables, 9*npts, "the profile tables");
 	const std::vector<double> *src[9] = { &ctx->host.z, &ctx->host.cap, &ctx->host.zh, &ctx->host.cap2, &ctx->host.hexd, &ctx->host.idz, &ctx->host.ext,
 	                                      &ctx->host.stp, &ctx->host.istp };
@@ -1580,15 +1449,15 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->opts.sweep_exact_every = (int)value; }
 	else if (n == "weight_squares") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "weight_squares must be 0 or 1"); ctx->opts.weight_squares = (int)value; }
 	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->opts.sweep_fuse = (int)value; }
-	else if (n == "plane_images") ctx->plane_images = value ? 1 : 0;
-	else if (n == "compact_images") ctx->compact_images = value ? 1 : 0;
-	else if (n == "compact_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "compact_parts must be in [1,16]"); ctx->compact_parts = (int)value; }
-	else if (n == "slot_ids") ctx->slot_ids = value ? 1 : 0;
-	else if (n == "keep_pinned") ctx->keep_pinned = value ? 1 : 0;
-	else if (n == "block_shift") { if (value < 7 || value > 30) return pc_fail(PC_HIP_ERR_INVALID, "block_shift must be in [7,30]"); ctx->blk_shift = (int)value; }
-	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->run_parts = (int)value; }
+	else if (n == "plane_images") ctx->img.opts.plane_images = value ? 1 : 0;
+	else if (n == "compact_images") ctx->img.opts.compact_images = value ? 1 : 0;
+	else if (n == "compact_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "compact_parts must be in [1,16]"); ctx->img.opts.compact_parts = (int)value; }
+	else if (n == "slot_ids") ctx->img.opts.slot_ids = value ? 1 : 0;
+	else if (n == "keep_pinned") ctx->img.opts.keep_pinned = value ? 1 : 0;
+	else if (n == "block_shift") { if (value < 7 || value > 30) return pc_fail(PC_HIP_ERR_INVALID, "block_shift must be in [7,30]"); ctx->img.opts.blk_shift = (int)value; }
+	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->img.opts.run_parts = (int)value; }
 	else if (n == "relay_acc_lds") ctx->relay_acc_lds = value ? 1 : 0;
-	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->fetch_threads = (int)value; }
+	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->img.opts.fetch_threads = (int)value; }
 	else if (n == "pool") ctx->opts.pool = value ? 1 : 0;
 	else if (n == "wave_per_photon") {
 #ifdef PC_EXPERIMENTS
@@ -1744,7 +1613,7 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 	status = pc_batch_upload(ctx, b, start_coords, start_dir, start_elecv);
 	if (!status) status = pc_batch_trace(ctx, b, leak);
 	if (!status) status = pc_batch_download(ctx, b, start_elecv, rc, weights, exit_coords, exit_dir, exit_elecv, i_refl, d_travel, leak);
-	ctx->img_valid = 0;
+	ctx->img.valid = 0;
 	ctx->leak_events_of_run = 0;
 	return status;
 }
@@ -1792,52 +1661,6 @@ int pc_hip_sample_photons(pc_hip_ctx *ctx, uint64_t seed, int64_t n, const int64
 	return status;
 }
 
-/* where the launch for slots [lo, ...) of a run of n_total slots stores its images: see pc_kargs::img */
-static void pc_set_img(const pc_hip_ctx *ctx, pc_kargs &a, long long lo, long long n_total, bool keep, bool planes)
-{
-	const long long ne = ctx->host.pm.n_energies, rec = PC_N_FIELDS + ne;
-	if (!keep) { a.img = a.img_w = nullptr; a.img_ss = a.img_fs = a.img_ws = 0; return; }
-	if (planes) {
-		a.img = ctx->d_soa + lo; a.img_ss = 1; a.img_fs = n_total;
-		a.img_w = ctx->d_soa + (long long)PC_N_FIELDS*n_total + lo*ne; a.img_ws = ne;
-	} else {
-		a.img = ctx->d_img + lo*rec; a.img_ss = rec; a.img_fs = 1;
-		a.img_w = a.img + PC_N_FIELDS; a.img_ws = rec;
-	}
-}
-
-/* device plane buffer for a run of n_slots (see pc_soa_kernel) */
-static int pc_soa_ensure(pc_hip_ctx *ctx, long long n_slots)
-{
-	return ctx->d_soa.grow(((size_t)PC_N_FIELDS + (size_t)ctx->host.pm.n_energies) * (size_t)n_slots, "could not allocate the device image planes");
-}
-
-/* records of slots [lo, lo + count) of the current run -> planes (pitch = the run's n_slots), on `stream` */
-static int pc_soa_launch(pc_hip_ctx *ctx, hipStream_t stream, long long lo, long long count, long long n_total)
-{
-	const int ne = ctx->host.pm.n_energies;
-	const size_t lds = (size_t)PC_SOA_TILE*(PC_N_FIELDS + ne)*sizeof(double);
-	if (lds > 65536) return PC_HIP_ERR_INVALID;
-	const unsigned blocks = (unsigned)((count + PC_SOA_TILE - 1)/PC_SOA_TILE);
-	hipLaunchKernelGGL(pc_soa_kernel, dim3(blocks), dim3(256), lds, stream, ctx->d_img, ctx->d_soa, lo, count, n_total, ne);
-	PC_HIP_CHECK(hipGetLastError());
-	return PC_HIP_OK;
-}
-
-/* First slot of part k of `parts`.  The fetch of the images can start when the first part is done and has the last part
- * left when the kernel ends, so with three or more parts the first and the last are half the size of the others. */
-static long long pc_part_begin(long long n_slots, int parts, int k)
-{
-	if (k <= 0) return 0;
-	if (k >= parts) return n_slots;
-	if (parts < 3) return n_slots*k/parts;
-	const double unit = 1.0/(double)(parts - 1);           /* 1/2 + (parts - 2) + 1/2 units */
-	return (long long)((double)n_slots*unit*((double)k - 0.5));
-}
-
-/* image planes: 17 double-sized planes of n_slots entries followed by the weights plane */
-static const int PC_N_PLANES = 17;
-
 /* How long do photons live on this optic?  32768 slots with the default kernel (3 ms, results unused) set refl_per_launch, by
  * which the context -- or, for a device group, every member -- picks the kernel of its source runs.  Called where pc_wants_probe
  * holds: refl_per_launch is unknown, so the probe itself gets no launching wave, and it is too small to ask for a probe. */
@@ -1853,35 +1676,6 @@ static int pc_probe_lifetime(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, uint
 static size_t pc_lane_start_lanes(const pc_hip_ctx *ctx)
 {
 	return (size_t)ctx->n_cu * (size_t)std::max(ctx->opts.blocks_per_cu*ctx->opts.block_size, 1024);
-}
-
-/* buffers of a compact run of n_slots (pc_kargs::img_cursor): position counter, per-block counters, the host-visible block
- * flags, the lanes' start-image lines (`halves` sets of them) and, on request, the plane of slot indices; counters
- * and flags are cleared */
-static int pc_compact_prepare(pc_hip_ctx *ctx, long long n_slots, int halves)
-{
-	/* the block flags are cleared from the host below: a run of this context that is still in flight would set flags of its own
-	 * after that (and the fetch of the new run would copy blocks the new kernel has not written) */
-	if (ctx->run_pending) {
-		int st = pc_hip_transmission_wait(ctx, nullptr);
-		if (st) return st;
-	}
-	const int shift = ctx->blk_shift;
-	const size_t blocks = (size_t)((n_slots + (1ll << shift) - 1) >> shift);
-	const size_t cap = blocks + blocks/2 + 16;
-	int st = ctx->d_cursor.grow(1, "pc_hip_transmission_run: could not allocate the position counter");
-	if (!st) st = ctx->d_blk_done.grow(blocks, "pc_hip_transmission_run: could not allocate the block counters", cap);
-	if (!st) st = ctx->h_blk_flag.grow(blocks, "pc_hip_transmission_run: could not allocate the block flags", cap);
-	if (!st && ctx->slot_ids) st = ctx->d_ids.grow((size_t)n_slots, "pc_hip_transmission_run: could not allocate the slot-index plane");
-	/* one 64-byte line per lane of the largest launch the context makes, per half */
-	if (!st) st = ctx->d_lane_start.grow(8*pc_lane_start_lanes(ctx)*(size_t)halves, "pc_hip_transmission_run: could not allocate the lanes' start-image lines");
-	if (st) return st;
-	ctx->run_blk_shift = shift;
-	ctx->run_blocks = (long long)blocks;
-	memset(ctx->h_blk_flag, 0, blocks*sizeof(unsigned int));      /* the previous run has been waited for (above): nobody looks at them now */
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_cursor, 0, sizeof(unsigned long long), ctx->stream));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_blk_done, 0, blocks*sizeof(unsigned int), ctx->stream));
-	return PC_HIP_OK;
 }
 
 int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64_t n_slots, uint32_t max_attempts, int keep_images)
@@ -1902,92 +1696,67 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	ctx->last_call = PC_CALL_RUN;
 	pc_kargs a;
 	pc_fill_common(ctx, a);
-	ctx->img_valid = 0;
 	/* option "plane_images" (set by polycap_source_get_transmission_efficiencies): the kernels store the planes of struct
 	 * _polycap_images themselves -- 18 scattered 8-byte stores per exit photon instead of two contiguous pieces of a record,
 	 * 5 % of the HBM bandwidth at most -- and the fetch is a plain copy of planes into the caller's pinned memory */
-	const bool planes = keep_images && ctx->plane_images && pc_soa_ensure(ctx, n_slots) == PC_HIP_OK;
-	ctx->run_planes = planes ? 1 : 0;
-	const bool compact = planes && ctx->compact_images;
-	ctx->run_compact = compact ? 1 : 0;
-	/* parts: consecutive slot ranges traced by consecutive launches into the same totals and image records (a photon
-	 * depends on its global slot number only, so the result does not depend on the cut) */
-	/* A compact run publishes its blocks itself: it needs no parts for the copy-back.  Option "compact_parts" > 1 traces a big one
-	 * as that many launches on two streams all the same (the positions, block counters and totals are the run's, so a launch simply
-	 * goes on where the one before leaves off): meant to cover the tail of one launch with the head of the next, it costs more
-	 * than it saves (default 1). */
-	int parts = (keep_images && ctx->run_parts > 1 && !compact) ? ctx->run_parts : 1;
-	if (compact && ctx->compact_parts > 1 && n_slots >= 4000000) parts = ctx->compact_parts;
-	if (parts > PC_MAX_PARTS) parts = PC_MAX_PARTS;
-	if ((long long)parts > n_slots / 65536) parts = (int)(n_slots / 65536);
-	if (parts < 1) parts = 1;
+	ctx->img.reset();
+	pc_image_plan plan = pc_plan_images(n_slots, (int)ne, keep_images != 0, ctx->img.opts);
+	/* a compact run's block flags are cleared from the host: a run of this context that is still in flight would set flags of its own
+	 * after that (and the fetch of the new run would copy blocks the new kernel has not written) */
+	if (plan.layout == PC_IMG_COMPACT && ctx->run_pending) {
+		int st = pc_hip_transmission_wait(ctx, nullptr);
+		if (st) return st;
+	}
+	{
+		int st = ctx->img.prepare(plan, pc_lane_start_lanes(ctx));
+		if (st) return st;
+	}
+	const bool compact = plan.layout == PC_IMG_COMPACT;
+	const int parts = plan.parts;
 	const hipStream_t main_stream = ctx->stream;
 	pc_launch_site site{main_stream};
-	/* launches in flight at the same time (parts on two streams) must not share per-lane scratch: two halves of it */
-	site.halves = (parts > 1) ? 2 : 1;
-	if (compact) {
-		int st = pc_compact_prepare(ctx, n_slots, site.halves);
-		if (st) return st;
-		a.img_cursor = ctx->d_cursor;
-		a.img_ids = ctx->slot_ids ? ctx->d_ids : nullptr;
-		a.blk_done = ctx->d_blk_done;
-		a.blk_flag = ctx->h_blk_flag.dev;
-		a.blk_shift = ctx->run_blk_shift;
-		a.img_n = n_slots;
-		a.lane_start = ctx->d_lane_start;
-	}
-	if (keep_images && !planes) {
-		int st = ctx->d_img.grow(((size_t)PC_N_PLANES + ne) * (size_t)n_slots, "pc_hip_transmission_run: could not allocate the image planes; use keep_images=0");
-		if (st) return st;
-	}
+	site.halves = plan.halves;
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
 	a.seed = seed; a.max_attempts = max_attempts; a.keep_images = keep_images ? 1 : 0;
-	ctx->n_parts = compact ? 1 : parts;     /* what the fetch goes by: a compact run is fetched block by block whatever its launches */
-	const size_t rec = (size_t)PC_N_PLANES + ne;
 	int status = PC_HIP_OK;
 	if (parts > 1) {
 		/* Parts alternate between two streams.  Every launch fills the device with persistent workgroups, so the
 		 * workgroups of part k+1 start exactly as those of part k run out of slots and leave: the tail of one part (its
 		 * longest photons) is covered by the head of the next, and the parts still finish in order. */
-		PC_HIP_CHECK(ctx->stream2.ensure());
-		PC_HIP_CHECK(ctx->ev_sync.ensure());
+		PC_HIP_CHECK(ctx->img.stream2.ensure());
+		PC_HIP_CHECK(ctx->img.ev_sync.ensure());
 		int st = ctx->d_work.grow(PC_MAX_PARTS, "pc_hip_transmission_run: could not allocate the work counters of the parts");
 		if (st) return st;
 		PC_HIP_CHECK(hipMemsetAsync(ctx->d_work, 0, PC_MAX_PARTS*sizeof(unsigned long long), main_stream));
 		PC_HIP_CHECK(hipEventRecord(ctx->ev0, main_stream));
-		PC_HIP_CHECK(hipEventRecord(ctx->ev_sync, main_stream));
-		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_sync, 0));     /* totals and counters are zero */
+		PC_HIP_CHECK(hipEventRecord(ctx->img.ev_sync, main_stream));
+		PC_HIP_CHECK(hipStreamWaitEvent(ctx->img.stream2, ctx->img.ev_sync, 0));     /* totals and counters are zero */
 		site.record_ev0 = site.record_ev1 = false;
 	}
 	for (int k = 0; k < parts && status == PC_HIP_OK; k++) {
-		const long long lo = pc_part_begin(n_slots, parts, k), hi = pc_part_begin(n_slots, parts, k + 1);
+		const long long lo = plan.begin[k], hi = plan.begin[k + 1];
 		a.slot0 = slot0 + lo; a.n_slots = hi - lo;
-		pc_set_img(ctx, a, compact ? 0 : lo, n_slots, keep_images != 0, planes);      /* compact: positions are the run's, not the part's */
+		ctx->img.kargs(a, k);
 		if (parts > 1) {
 			a.work = ctx->d_work + k;
-			site.stream = (k & 1) ? (hipStream_t)ctx->stream2 : main_stream;
+			site.stream = (k & 1) ? (hipStream_t)ctx->img.stream2 : main_stream;
 			site.half = k & 1;               /* the launch before and the one after run on the other stream: the other half */
-			if (compact) {
-				a.lane_start = ctx->d_lane_start + (size_t)(k & 1)*8*pc_lane_start_lanes(ctx);
-				a.img_id0 = lo;           /* slot ids are the run's */
-			}
 		}
 		if (compact) site.record_ev1 = false;    /* the kernel time ends behind the tail kernel below */
 		status = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, site, a, hi - lo)
 		                                  : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, site, a, hi - lo);
-		ctx->part_end[k] = hi;
 		if (status == PC_HIP_OK && parts > 1) {
-			PC_HIP_CHECK(ctx->ev_part[k].ensure());
-			PC_HIP_CHECK(hipEventRecord(ctx->ev_part[k], site.stream));
+			PC_HIP_CHECK(ctx->img.ev_part[k].ensure());
+			PC_HIP_CHECK(hipEventRecord(ctx->img.ev_part[k], site.stream));
 		}
 	}
 	if (parts > 1 && status == PC_HIP_OK) {
 		/* the main stream ends after every part: wait() synchronises it, and the kernel time runs to here */
 		for (int k = 0; k < parts; k++)
-			if (k & 1) PC_HIP_CHECK(hipStreamWaitEvent(main_stream, ctx->ev_part[k], 0));
+			if (k & 1) PC_HIP_CHECK(hipStreamWaitEvent(main_stream, ctx->img.ev_part[k], 0));
 	}
 	if (compact && status == PC_HIP_OK) {
-		hipLaunchKernelGGL(pc_compact_tail_kernel, dim3(64), dim3(256), 0, main_stream, ctx->d_soa, (long long)n_slots, (int)ne, ctx->d_cursor);
+		hipLaunchKernelGGL(pc_compact_tail_kernel, dim3(64), dim3(256), 0, main_stream, ctx->img.d_soa, (long long)n_slots, (int)ne, ctx->img.d_cursor);
 		PC_HIP_CHECK(hipGetLastError());
 	}
 	if ((parts > 1 || compact) && status == PC_HIP_OK)
@@ -1995,7 +1764,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	if (status) return status;
 	ctx->run_slots = n_slots;
 	ctx->run_pending = 1;
-	ctx->img_valid = keep_images ? 1 : 0;
+	ctx->img.valid = keep_images ? 1 : 0;
 	return PC_HIP_OK;
 }
 
@@ -2006,14 +1775,12 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	if (max_attempts < 1) max_attempts = 1;
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	ctx->img_valid = 0;
+	ctx->img.reset();
 	ctx->last_call = PC_CALL_RUN_LEAK;
 	if (keep_images) {
-		int st = ctx->d_img.grow(((size_t)PC_N_PLANES + ne) * (size_t)n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
+		int st = ctx->img.keep_records(n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
 		if (st) return st;
 	}
-	ctx->n_parts = 1;
-	ctx->run_planes = 0;
 	ctx->last_run_plain = 0;
 	ctx->leak_events_of_run = 1;
 	ctx->run_squares = ctx->opts.weight_squares;
@@ -2031,7 +1798,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	ctx->run_slots = n_slots;
 	ctx->run_pending = 1;
 	ctx->leak_pending = 1;
-	ctx->img_valid = keep_images ? 1 : 0;
+	ctx->img.valid = keep_images ? 1 : 0;
 	return PC_HIP_OK;
 }
 
@@ -2200,329 +1967,28 @@ int pc_hip_sweep_stats(pc_hip_ctx *ctx, int64_t stats[4], double *ct_tame, int p
 	return PC_HIP_OK;
 }
 
-/* The stream of the image copies.  HIP multiplexes a process's streams over a few hardware queues (4 by default): with one
- * more context alive in the process the copies of a finished part landed in the queue of the next part's kernel and waited
- * for it (40 -> 54 ms per 1e7 photons through the C API, scripts/analysis/api_time2.py).  A stream of the highest priority
- * gets a queue of its own class, apart from the kernels' queues. */
-/* is this host address pinned already (an earlier fetch with "keep_pinned", a slab from the host pool, the caller's own
- * hipHostRegister / hipHostMalloc)?  Pinning a range inside an existing registration a second time is not something to try. */
-static bool pc_host_is_pinned(void *p)
+/* images [first, first + count) of the last run into the caller's planes (pc_image_planes; or null) or as records into raw */
+static int pc_fetch_images(pc_hip_ctx *ctx, int64_t first, int64_t count, void *const *planes, double *raw)
 {
-	unsigned int flags = 0;
-	if (hipHostGetFlags(&flags, p) == hipSuccess) return true;
-	(void)hipGetLastError();
-	return false;
-}
-
-/* Pins the host ranges (address, bytes) for the copy engine: rounded out to pages, overlapping or touching ranges merged (small
- * planes from malloc share pages with their neighbours, and a page cannot be registered twice), ranges that are pinned already
- * left alone.  All or nothing: when one range cannot be pinned the ones pinned here are released again and false is returned
- * -- a destination that is pinned only in part is not something to hand to hipMemcpyAsync.  `pinned` receives what to
- * hipHostUnregister afterwards. */
-static bool pc_pin_ranges(std::vector<std::pair<char *, size_t>> ranges, unsigned int flags, std::vector<void *> &pinned)
-{
-	const uintptr_t page = 4096;
-	std::vector<std::pair<uintptr_t, uintptr_t>> r;
-	for (auto &x : ranges) {
-		if (!x.first || !x.second) continue;
-		const uintptr_t lo = (uintptr_t)x.first & ~(page - 1), hi = ((uintptr_t)x.first + x.second + page - 1) & ~(page - 1);
-		r.emplace_back(lo, hi);
-	}
-	std::sort(r.begin(), r.end());
-	std::vector<std::pair<uintptr_t, uintptr_t>> m;
-	for (auto &x : r) {
-		if (!m.empty() && x.first <= m.back().second) m.back().second = std::max(m.back().second, x.second);
-		else m.push_back(x);
-	}
-	const size_t before = pinned.size();
-	for (auto &x : m) {
-		if (pc_host_is_pinned((void *)x.first) && pc_host_is_pinned((void *)(x.second - 1))) continue;
-		if (hipHostRegister((void *)x.first, (size_t)(x.second - x.first), flags) != hipSuccess) {
-			(void)hipGetLastError();
-			while (pinned.size() > before) { (void)hipHostUnregister(pinned.back()); pinned.pop_back(); }
-			return false;
-		}
-		pinned.push_back((void *)x.first);
-	}
-	return true;
-}
-
-static hipError_t pc_fetch_stream_ensure(pc_hip_ctx *ctx)
-{
-	return ctx->fetch_stream.ensure(!getenv("POLYCAP_FETCH_PRIORITY_OFF"));
-}
-
-/* see pc_fetch_images.  Returns PC_HIP_OK, an error, or 1 when the direct path cannot be used */
-static int pc_fetch_planes_direct(pc_hip_ctx *ctx, int64_t first, int64_t count, void *const *planes, double *weights)
-{
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	const long long n_total = ctx->run_slots;
-	if (!ctx->run_planes && ((size_t)PC_SOA_TILE*(PC_N_FIELDS + ne)*sizeof(double) > 65536 || pc_soa_ensure(ctx, n_total) != PC_HIP_OK)) return 1;
-	PC_HIP_CHECK(pc_fetch_stream_ensure(ctx));
-	PC_HIP_CHECK(ctx->ev_sync.ensure());
-	const bool timing = getenv("POLYCAP_TIMING") != nullptr;
-	auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double t_begin = now_ms();
-	/* pin the destinations */
-	std::vector<void *> pinned;
-	auto unpin = [&]() { for (void *p : pinned) (void)hipHostUnregister(p); pinned.clear(); };
-	/* Planes at one common stride (polycap_source_get_transmission_efficiencies allocates its result as one slab): pinned in one
-	 * piece, and a group of blocks is ONE pitched copy of 17 (one energy: 18, the weights are the 18th plane) rows instead of as
-	 * many linear ones -- a copy costs the engine 4-5 us whatever its size (scripts/analysis/copy2d_probe.hip: 56.5 against
-	 * 49 GB/s at 0.5 M positions per group). */
-	long long slab_stride = 0;      /* bytes between two planes, 0: no common stride */
-	int slab_rows = 0;
-	const bool pin_here = !ctx->dst_prepinned;
-	if (ctx->run_compact && planes[0] && planes[1]) {
-		const long long st = (long long)((char *)planes[1] - (char *)planes[0]);
-		bool uniform = st >= (long long)((size_t)count*sizeof(double));
-		for (int f = 2; f < PC_N_FIELDS && uniform; f++)
-			uniform = planes[f] && (char *)planes[f] - (char *)planes[0] == (long long)f*st;
-		if (uniform) {
-			slab_stride = st;
-			slab_rows = PC_N_FIELDS;
-			if (ne == 1 && weights && (char *)weights - (char *)planes[0] == (long long)PC_N_FIELDS*st) slab_rows = PC_N_FIELDS + 1;
-		}
-	}
-	if (slab_stride && pin_here) {
-		const bool w_in = weights && (char *)weights - (char *)planes[0] == (long long)PC_N_FIELDS*slab_stride;
-		const size_t bytes = w_in ? (size_t)PC_N_FIELDS*(size_t)slab_stride + (size_t)count*ne*sizeof(double)
-		                          : (size_t)(PC_N_FIELDS - 1)*(size_t)slab_stride + (size_t)count*sizeof(double);
-		const hipError_t re = pc_host_is_pinned(planes[0]) ? hipErrorHostMemoryAlreadyRegistered : hipHostRegister(planes[0], bytes, hipHostRegisterDefault);
-		if (re == hipSuccess) pinned.push_back(planes[0]);
-		else {
-			(void)hipGetLastError();
-			if (re != hipErrorHostMemoryAlreadyRegistered) { slab_stride = 0; slab_rows = 0; }      /* plane by plane below */
-		}
-		if (slab_stride && weights && !w_in) {
-			const hipError_t rw = pc_host_is_pinned(weights) ? hipErrorHostMemoryAlreadyRegistered : hipHostRegister(weights, (size_t)count*ne*sizeof(double), hipHostRegisterDefault);
-			if (rw == hipSuccess) pinned.push_back(weights); else (void)hipGetLastError();
-		}
-	}
-	if (!slab_stride && pin_here) {
-		std::vector<std::pair<char *, size_t>> ranges;
-		for (int k = 0; k <= PC_N_FIELDS; k++) {
-			void *p = (k < PC_N_FIELDS) ? planes[k] : (void *)weights;
-			if (p) ranges.emplace_back((char *)p, (size_t)count*sizeof(double)*(k < PC_N_FIELDS ? 1 : ne));
-		}
-		if (!pc_pin_ranges(ranges, hipHostRegisterDefault, pinned) && !ctx->run_planes) {
-			unpin();
-			return 1;         /* a record run: the staging pipeline copies without pinning the destination */
-		}
-		/* (a plane run whose destination cannot be pinned is copied unpinned: slower, still right) */
-	}
-	const double t_pinned = now_ms();
-	int status = PC_HIP_OK;
-	const int parts = ctx->run_compact ? 0 : (ctx->n_parts > 1 ? ctx->n_parts : 1);
-	if (ctx->run_compact) {
-		/* the kernel publishes its planes block by block (pc_blocks_written): every block is copied as soon as its flag is up,
-		 * while the kernel goes on.  The kernel's end also ends the wait (every block is complete then). */
-		const long long B = 1ll << ctx->run_blk_shift;
-		const long long b_end = std::min<long long>(ctx->run_blocks, (first + count + B - 1) >> ctx->run_blk_shift);
-		bool kernel_done = false;
-		long long b = first >> ctx->run_blk_shift;
-		int group = 0;
-		/* POLYCAP_FETCH_STREAMS (1 or 2, default 2): copy streams the planes of a group alternate between; POLYCAP_FETCH_DEPTH
-		 * (1..3, default 2): groups of copies in flight */
-		int n_streams = 2, depth = 2;
-		if (const char *ev = getenv("POLYCAP_FETCH_STREAMS")) n_streams = (*ev == '1') ? 1 : 2;
-		if (const char *ev = getenv("POLYCAP_FETCH_DEPTH")) depth = (*ev >= '1' && *ev <= '3') ? *ev - '0' : 2;
-		if (n_streams == 2) PC_HIP_CHECK(ctx->fetch_stream_b.ensure(true));
-		for (int k = 0; k < 2; k++)
-			for (int j = 0; j < 4; j++)
-				PC_HIP_CHECK(ctx->ev_group[k][j].ensure());
-		hipStream_t streams[2] = { ctx->fetch_stream, n_streams == 2 ? ctx->fetch_stream_b : ctx->fetch_stream };
-		while (b < b_end && status == PC_HIP_OK) {
-			volatile unsigned int *flag = ctx->h_blk_flag;
-			unsigned long spins = 0;
-			while (!kernel_done && flag[b] == 0u) {
-				if ((++spins & 63ul) == 0ul) {
-					const hipError_t q = hipEventQuery(ctx->ev1);
-					if (q == hipSuccess) kernel_done = true;
-					else if (q != hipErrorNotReady) { status = pc_fail(PC_HIP_ERR_RUNTIME, std::string("pc_hip_transmission_images (kernel event query): ") + hipGetErrorString(q)); break; }
-					(void)hipGetLastError();
-				}
-				std::this_thread::yield();
-			}
-			if (status != PC_HIP_OK) break;
-			/* `depth` groups of copies are kept in flight: the next one is put together when the oldest has finished, from every
-			 * block that is complete by then.  The first block is ready a fraction of a millisecond into the run; as the kernel
-			 * produces faster than PCIe carries, every group is larger than the one before (up to 64 blocks) and the copy engines
-			 * never wait -- nor are they fed thousands of small copies (4-5 us each, whatever their size). */
-			if (group >= depth) {
-				for (int k = 0; k < n_streams && status == PC_HIP_OK; k++) {
-					const hipError_t we = hipEventSynchronize(ctx->ev_group[k][(group - depth) & 3]);
-					if (we != hipSuccess) status = pc_fail(PC_HIP_ERR_RUNTIME, std::string("pc_hip_transmission_images (wait for a group of copies): ") + hipGetErrorString(we));
-				}
-				if (status != PC_HIP_OK) break;
-			}
-			long long e = b + 1;
-			while (e < b_end && e - b < 64 && (kernel_done || flag[e] != 0u)) e++;
-			std::atomic_thread_fence(std::memory_order_acquire);
-			const long long lo = std::max<long long>(b*B, first), hi = std::min<long long>(std::min<long long>(e*B, n_total), first + count);
-			hipError_t err = hipSuccess;
-			if (slab_stride) {
-				err = hipMemcpy2DAsync((double *)planes[0] + (lo - first), (size_t)slab_stride, ctx->d_soa + lo, (size_t)n_total*sizeof(double),
-				                       (size_t)(hi - lo)*sizeof(double), (size_t)slab_rows, hipMemcpyDeviceToHost, streams[0]);
-				if (err == hipSuccess && weights && slab_rows == PC_N_FIELDS)
-					err = hipMemcpyAsync(weights + (size_t)(lo - first)*ne, ctx->d_soa + (size_t)PC_N_FIELDS*n_total + (size_t)lo*ne,
-					                     (size_t)(hi - lo)*ne*sizeof(double), hipMemcpyDeviceToHost, streams[1]);
-			}
-			for (int f = 0; f <= PC_N_FIELDS && err == hipSuccess && !slab_stride; f++) {
-				if (f < PC_N_FIELDS) {
-					if (!planes[f]) continue;
-					err = hipMemcpyAsync((double *)planes[f] + (lo - first), ctx->d_soa + (size_t)f*n_total + lo, (size_t)(hi - lo)*sizeof(double),
-					                     hipMemcpyDeviceToHost, streams[f & 1]);
-				} else if (weights) {
-					err = hipMemcpyAsync(weights + (size_t)(lo - first)*ne, ctx->d_soa + (size_t)PC_N_FIELDS*n_total + (size_t)lo*ne,
-					                     (size_t)(hi - lo)*ne*sizeof(double), hipMemcpyDeviceToHost, streams[f & 1]);
-				}
-			}
-			if (err != hipSuccess) status = pc_fail(PC_HIP_ERR_RUNTIME, std::string("pc_hip_transmission_images (copy of a group of blocks): ") + hipGetErrorString(err));
-			for (int k = 0; k < n_streams && err == hipSuccess; k++) {
-				err = hipEventRecord(ctx->ev_group[k][group & 3], streams[k]);
-				if (err != hipSuccess) status = pc_fail(PC_HIP_ERR_RUNTIME, std::string("pc_hip_transmission_images (event after a group of copies): ") + hipGetErrorString(err));
-			}
-			b = e;
-			group++;
-		}
-		if (n_streams == 2 && hipStreamSynchronize(ctx->fetch_stream_b) != hipSuccess && status == PC_HIP_OK)
-			status = pc_fail(PC_HIP_ERR_RUNTIME, "pc_hip_transmission_images: the plane copies failed");
-	}
-	for (int k = 0; k < parts && status == PC_HIP_OK; k++) {
-		const long long plo = (parts > 1 && k > 0) ? ctx->part_end[k - 1] : 0, phi = (parts > 1) ? ctx->part_end[k] : n_total;
-		const long long lo = std::max<long long>(plo, first), hi = std::min<long long>(phi, first + count);
-		if (hi <= lo) continue;
-		hipError_t e = hipSuccess;
-		if (parts > 1) {
-			e = hipStreamWaitEvent(ctx->fetch_stream, ctx->ev_part[k], 0);         /* traced, and turned into planes if eager */
-		} else {
-			int st = pc_hip_transmission_wait(ctx, nullptr);
-			if (st) { status = st; break; }
-		}
-		if (e == hipSuccess && !ctx->run_planes) {
-			/* the run kept records: turn the part into planes now, behind its trace */
-			int st = pc_soa_launch(ctx, ctx->fetch_stream, plo, phi - plo, n_total);
-			if (st) { status = st; break; }
-		}
-		for (int f = 0; f <= PC_N_FIELDS && e == hipSuccess; f++) {
-			if (f < PC_N_FIELDS) {
-				if (!planes[f]) continue;
-				e = hipMemcpyAsync((double *)planes[f] + (lo - first), ctx->d_soa + (size_t)f*n_total + lo, (size_t)(hi - lo)*sizeof(double),
-				                   hipMemcpyDeviceToHost, ctx->fetch_stream);
-			} else if (weights) {
-				e = hipMemcpyAsync(weights + (size_t)(lo - first)*ne, ctx->d_soa + (size_t)PC_N_FIELDS*n_total + (size_t)lo*ne,
-				                   (size_t)(hi - lo)*ne*sizeof(double), hipMemcpyDeviceToHost, ctx->fetch_stream);
-			}
-		}
-		if (e != hipSuccess) status = pc_fail(PC_HIP_ERR_RUNTIME, std::string("pc_hip_transmission_images: ") + hipGetErrorString(e));
-	}
-	const double t_queued = now_ms();
-	if (hipStreamSynchronize(ctx->fetch_stream) != hipSuccess && status == PC_HIP_OK)
-		status = pc_fail(PC_HIP_ERR_RUNTIME, "pc_hip_transmission_images: the plane copies failed");
-	const double t_copied = now_ms();
-	if (ctx->keep_pinned && slab_stride) pinned.clear();      /* the caller keeps its slab pinned (and unpins it itself: pc_hip_host_unregister) */
-	unpin();
-	if (timing)
-		fprintf(stderr, "polycap timing [ms]: plane fetch: pin %.1f, enqueue %.1f, wait for trace + copies %.1f, unpin %.1f\n",
-		        t_pinned - t_begin, t_queued - t_pinned, t_copied - t_queued, now_ms() - t_copied);
-	return status;
-}
-
-static int pc_fetch_images(pc_hip_ctx *ctx, int64_t first, int64_t count, const pc_hip_images *dst, double *raw)
-{
-	if (!ctx->img_valid) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_images: the last run kept no images");
+	if (!ctx->img.valid) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_images: the last run kept no images");
 	if (first < 0 || count < 0 || first + count > ctx->run_slots) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_images: slot range out of bounds");
-	/* a leak run is complete (and possibly repeated) only after wait(); a plain run is fetched part by part below */
-	if (ctx->leak_pending || (ctx->n_parts <= 1 && !(ctx->run_compact && dst && !raw))) {
+	/* a leak run is complete (and possibly repeated) only after wait(); a plain run in parts is fetched part by part, and the planes
+	 * of a compact run block by block, while it is traced */
+	if (ctx->leak_pending || (ctx->img.plan.fetch_parts <= 1 && !(ctx->img.plan.layout == PC_IMG_COMPACT && planes && !raw))) {
 		int st = pc_hip_transmission_wait(ctx, nullptr);
 		if (st) return st;
 	}
 	if (count == 0) return PC_HIP_OK;
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	const size_t ne = (size_t)ctx->host.pm.n_energies, rec = (size_t)PC_N_PLANES + ne;
-	void *planes[PC_N_PLANES] = {nullptr};
-	if (dst) {
-		void *p[PC_N_PLANES] = {
-			dst->src_start_coords[0], dst->src_start_coords[1], dst->pc_start_coords[0], dst->pc_start_coords[1],
-			dst->pc_start_dir[0], dst->pc_start_dir[1], dst->pc_start_elecv[0], dst->pc_start_elecv[1],
-			dst->pc_exit_coords[0], dst->pc_exit_coords[1], dst->pc_exit_coords[2],
-			dst->pc_exit_dir[0], dst->pc_exit_dir[1], dst->pc_exit_elecv[0], dst->pc_exit_elecv[1],
-			dst->pc_exit_nrefl, dst->pc_exit_dtravel };
-		memcpy(planes, p, sizeof(p));
-	}
-	/* Fast path for plane destinations: the caller's planes are pinned for the duration of the call (hipHostRegister: 3 ms
-	 * for 1.4 GB of faulted-in memory) and the copy engine writes them straight from the device's plane copy of the records
-	 * (pc_soa_kernel), part by part behind the trace.  No host thread touches the data.  Anything that does not fit (a plane
-	 * that cannot be pinned, a record too long for the LDS tile) takes the staging pipeline below. */
-	if (ctx->run_planes && (!dst || raw))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_records: the last run stored planes (option plane_images); fetch them with pc_hip_transmission_images");
-	if (dst && !raw && (ctx->run_planes || (size_t)count*sizeof(double) >= ((size_t)1 << 20))) {
-		int st = pc_fetch_planes_direct(ctx, first, count, planes, dst->exit_coord_weights);
-		if (st != 1) return st;          /* 1 = not applicable (record runs only) */
-		if (ctx->run_planes) return pc_fail(PC_HIP_ERR_RUNTIME, "pc_hip_transmission_images: internal: plane run without a plane fetch");
-	}
-	/* Pipeline over chunks of <= 16 MB of records: one asynchronous copy (DMA engine, no compute units) of the chunk into
-	 * pinned host memory, then host threads turn the records of the previous chunk into the caller's SoA planes while the
-	 * next one is in flight.  The copies run on their own stream and wait only for the part of the run that holds the
-	 * chunk, so they overlap the kernel of the following parts. */
-	size_t chunk = ((size_t)16 << 20) / (rec*sizeof(double));
-	if (chunk < 256) chunk = 256;
-	if (chunk > (size_t)count) chunk = (size_t)count;
-	int st = ctx->h_stage.grow(2*chunk*rec, "pc_hip_transmission_images: could not allocate the staging buffer");
-	if (st) return st;
-	for (int k = 0; k < 2; k++)
-		PC_HIP_CHECK(ctx->ev_fetch[k].ensure());
-	PC_HIP_CHECK(pc_fetch_stream_ensure(ctx));
-	int nthreads = ctx->fetch_threads;
-	if (nthreads <= 0) {
-		const unsigned hw = std::thread::hardware_concurrency();
-		nthreads = (int)(hw == 0 ? 4 : (hw > 16 ? 16 : hw));
-	}
-	if ((size_t)count*rec*sizeof(double) < ((size_t)4 << 20)) nthreads = 1;
-	pc_copy_workers workers(nthreads);
-	std::vector<pc_copy_piece> pieces;
-	/* records [done, done + n) in the pinned buffer `src` -> planes: pieces of 4096 records for the worker threads */
-	auto scatter = [&](const double *src, size_t done, size_t n) {
-		pieces.clear();
-		for (size_t o = 0; o < n; o += 4096)
-			pieces.push_back({src + o*rec, done + o, n - o < 4096 ? n - o : 4096});
-		workers.run(pieces, planes, dst ? dst->exit_coord_weights : nullptr, rec, ne, raw);
-	};
-	size_t prev_done = 0, prev_n = 0;
-	int c = 0, part = 0, waited = -1;
-	for (size_t done = 0; done < (size_t)count; done += chunk, c++) {
-		const size_t n = ((size_t)count - done < chunk) ? (size_t)count - done : chunk;
-		const int b = c & 1;
-		double *h_buf = ctx->h_stage + (size_t)b*chunk*rec;
-		if (ctx->n_parts > 1) {
-			/* the last slot of the chunk decides which part has to be finished */
-			const long long last = first + (long long)(done + n) - 1;
-			while (part < ctx->n_parts - 1 && ctx->part_end[part] <= last) part++;
-			/* every part up to that one: consecutive parts run on two streams, so the event of part p says nothing
-			 * about part p-1, whose tail a chunk that straddles the boundary also reads */
-			for (int q = waited + 1; q <= part; q++)
-				PC_HIP_CHECK(hipStreamWaitEvent(ctx->fetch_stream, ctx->ev_part[q], 0));
-			if (part > waited) waited = part;
-		}
-		PC_HIP_CHECK(hipMemcpyAsync(h_buf, ctx->d_img + ((size_t)first + done)*rec, n*rec*sizeof(double), hipMemcpyDeviceToHost,
-		                            ctx->n_parts > 1 ? ctx->fetch_stream : ctx->stream));
-		PC_HIP_CHECK(hipEventRecord(ctx->ev_fetch[b], ctx->n_parts > 1 ? ctx->fetch_stream : ctx->stream));
-		if (c > 0) {
-			PC_HIP_CHECK(hipEventSynchronize(ctx->ev_fetch[b ^ 1]));
-			scatter(ctx->h_stage + (size_t)(b ^ 1)*chunk*rec, prev_done, prev_n);
-		}
-		prev_done = done; prev_n = n;
-	}
-	PC_HIP_CHECK(hipEventSynchronize(ctx->ev_fetch[(c - 1) & 1]));
-	scatter(ctx->h_stage + (size_t)((c - 1) & 1)*chunk*rec, prev_done, prev_n);
-	return PC_HIP_OK;
+	return pc_fetch_images(ctx->img, first, count, planes, raw);
 }
 
 int pc_hip_transmission_images(pc_hip_ctx *ctx, int64_t first, int64_t count, const pc_hip_images *dst)
 {
 	if (!ctx || !dst) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_images: NULL argument");
-	return pc_fetch_images(ctx, first, count, dst, nullptr);
+	void *planes[PC_N_FIELDS + 1];
+	pc_image_planes(dst, planes);
+	return pc_fetch_images(ctx, first, count, planes, nullptr);
 }
 
 int pc_hip_transmission_slot_ids(pc_hip_ctx *ctx, int64_t first, int64_t count, int64_t *slots)
@@ -2531,13 +1997,14 @@ int pc_hip_transmission_slot_ids(pc_hip_ctx *ctx, int64_t first, int64_t count, 
 	if (first < 0 || count < 0 || first + count > ctx->run_slots) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_slot_ids: range out of bounds");
 	int st = pc_hip_transmission_wait(ctx, nullptr);
 	if (st) return st;
-	if (!ctx->img_valid || !ctx->run_compact || !ctx->d_ids || !ctx->slot_ids) {
+	const long long *ids = ctx->img.valid ? ctx->img.device_view().ids : nullptr;
+	if (!ids) {
 		/* a run that stores every photon at its slot: the identity */
 		for (int64_t k = 0; k < count; k++) slots[k] = first + k;
 		return PC_HIP_OK;
 	}
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	if (count) PC_HIP_CHECK(hipMemcpy(slots, ctx->d_ids + first, (size_t)count*sizeof(long long), hipMemcpyDeviceToHost));
+	if (count) PC_HIP_CHECK(hipMemcpy(slots, ids + first, (size_t)count*sizeof(long long), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;
 }
 
@@ -2661,7 +2128,6 @@ static int pc_leak_auto_order(pc_hip_ctx *ctx)
 	pc_fill_common(ctx, a);
 	a.seed = ctx->leak_seed; a.max_attempts = ctx->leak_max_attempts; a.keep_images = 0;
 	a.slot0 = ctx->leak_slot0; a.n_slots = n;
-	pc_set_img(ctx, a, 0, n, false, false);
 	a.work_est = ctx->d_work_est;
 	pc_launch_site site{ctx->stream};     /* the lane kernel, no events of its own */
 	site.record_ev0 = site.record_ev1 = false;
@@ -2717,7 +2183,7 @@ static int pc_transmission_enqueue_leak(pc_hip_ctx *ctx)
 {
 	pc_kargs a;
 	pc_fill_common(ctx, a);
-	pc_set_img(ctx, a, 0, ctx->leak_n_slots, ctx->leak_keep_images != 0, false);
+	ctx->img.set_img(a, ctx->leak_keep_images ? PC_IMG_RECORDS : PC_IMG_NONE, ctx->leak_n_slots, 0);
 	a.seed = ctx->leak_seed; a.slot0 = ctx->leak_slot0; a.n_slots = ctx->leak_n_slots;
 	a.max_attempts = ctx->leak_max_attempts; a.keep_images = ctx->leak_keep_images;
 	return ctx->host.pm.generic_src ? pc_leak_enqueue<PC_MODE_SRC_GENERIC>(ctx, a, ctx->leak_n_slots, ctx->leak_capacity_used)

@@ -284,7 +284,7 @@ static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_place
 	case PC_CALL_RELAY: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context holds the result of a relay, not of a source run");
 	default: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context has made no source run");
 	}
-	if (!a->img_valid)
+	if (!a->img.valid)
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last run kept no exit photons (run it with keep_images)");
 	return PC_HIP_OK;
 }
@@ -319,9 +319,9 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 	const pc_relay_place pl = { placement->gap, placement->off_x, placement->off_y };
 
 	/* from here on the second context holds the relay, or nothing */
-	b->img_valid = 0; b->leak_events_of_run = 0; b->last_run_plain = 0;
+	b->img.reset(); b->leak_events_of_run = 0; b->last_run_plain = 0;
 	b->last_call = PC_CALL_NONE;
-	b->run_planes = 0; b->run_compact = 0; b->n_parts = 1; b->run_pending = 0; b->run_slots = 0;
+	b->run_pending = 0; b->run_slots = 0;
 	b->run_squares = b->opts.weight_squares;
 	b->last_ms = 0.f;
 	const size_t nw_a = (size_t)((n_a + 63)/64);
@@ -351,7 +351,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
 		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
 		if (st) return st;
-		st = b->d_img.grow(((size_t)PC_N_FIELDS + (size_t)ne) * (size_t)std::max<long long>(n_out, 1), "pc_hip_relay_run: could not allocate the image records");
+		st = b->img.keep_records(n_out, "pc_hip_relay_run: could not allocate the image records");
 		if (st) return st;
 		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
 		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
@@ -363,7 +363,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
 		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
 		hipLaunchKernelGGL(pc_relay_finish_kernel, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
-		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->d_img,
+		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
 		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
 		PC_HIP_CHECK(hipGetLastError());
 		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
@@ -380,7 +380,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 	b->relay_counters[6] = n_a - n_in;
 	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
 	b->run_slots = n_out;
-	b->img_valid = 1;
+	b->img.valid = 1;
 	b->last_call = PC_CALL_RELAY;
 	return PC_HIP_OK;
 }

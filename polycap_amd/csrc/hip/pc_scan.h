@@ -90,9 +90,9 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	ctx->last_call = PC_CALL_SCAN;
 	/* behind every launch of the last run: a run cut into parts ends its main stream behind the parts on stream2 already
 	 * (pc_hip_transmission_run); this also orders the scan after anything else enqueued there */
-	if (ctx->stream2) {
-		PC_HIP_CHECK(hipEventRecord(ctx->ev_sync, ctx->stream2));
-		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_sync, 0));
+	if (ctx->img.stream2) {
+		PC_HIP_CHECK(hipEventRecord(ctx->img.ev_sync, ctx->img.stream2));
+		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->img.ev_sync, 0));
 	}
 	const int ne = ctx->host.pm.n_energies;
 	st = pc_scan_buffers(ctx, n_points);

@@ -153,21 +153,16 @@ static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s, const char *w
 	const long long ne = c->host.pm.n_energies;
 	memset(&s, 0, sizeof(s));
 	if (kind == 0) {
-		if (!c->img_valid)
+		if (!c->img.valid)
 			return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": the last run kept no exit photons (run it with keep_images)");
 		if (c->leak_pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
 			int st = pc_hip_transmission_wait(c, nullptr);
 			if (st) return st;
 		}
-		const long long n = c->run_slots;
-		s.n = n; s.f_x = 8; s.f_dx = 11; s.has_dz = 0;          /* pc_exit_coords, pc_exit_dir: planes 8..10, 11..12 */
-		if (c->run_planes) {
-			s.p = c->d_soa; s.ss = 1; s.fs = n;
-			s.w = c->d_soa + (long long)PC_N_FIELDS*n; s.ws = ne;
-		} else {
-			s.p = c->d_img; s.ss = PC_N_FIELDS + ne; s.fs = 1;
-			s.w = c->d_img + PC_N_FIELDS; s.ws = PC_N_FIELDS + ne;
-		}
+		const pc_image_view v = c->img.device_view();
+		s.n = v.n; s.f_x = PC_F_EXITX; s.f_dx = PC_F_EDIRX; s.has_dz = 0;
+		s.p = v.p; s.ss = v.l.ss; s.fs = v.l.fs;
+		s.w = v.w; s.ws = v.l.ws;
 		return PC_HIP_OK;
 	}
 	if (!c->leak_events_of_run)
