@@ -422,6 +422,65 @@ POLYCAP_EXTERN int pc_hip_hist_info(const pc_hip_hist *hist, int32_t dims[3], in
 POLYCAP_EXTERN double pc_hip_hist_quantile(int32_t n_bins, double lo, double hi, const uint64_t *bins, uint64_t outside, double q);
 /* host only: the full width at half maximum; *left and *right (optional) = where the profile crosses half its maximum */
 POLYCAP_EXTERN double pc_hip_hist_fwhm(int32_t n_bins, double lo, double hi, const uint64_t *bins, double *left, double *right);
+/* ---- joint histograms: weighted 2-D histograms of two per-entry scalar quantities of the last run, one per pair of axes (u, v)
+ * and selected energy, accumulated on the device in exact integers from what the run left there (pc_joint.h): phase-space diagrams
+ * (x against dx/dz at the exit face or at any distance), the transmission map of the entrance face (start x against start y), the
+ * reflection count against the entrance radius, the z of a leak event against its reflection count.  One pass reads every entry
+ * once for all pairs.  A spot map of one plane is the pair (X_AT d, Y_AT d) over its window.
+ *
+ * The contract (IEEE fp64, evaluated in the order written, no contraction):
+ *   entries    those pc_hip_hist_add reads: exit photons (kind 0; the records of a relay into the context count here), extleak (1)
+ *              and intleak (2) events of a leak_calc run.  Sums are kept per kind.
+ *   axes       an axis is a pc_hip_hist_axis: the fields, their validation and the value v of the histogram contract above.  A joint
+ *              axis may also have one of two quantities a histogram cannot (pc_hip_hist_validate refuses them):
+ *              START_X    v = pc_start_coords[0] (exit photons only);    START_Y    v = pc_start_coords[1] (exit photons only)
+ *   bin        per axis as in the histogram contract: f = ((v - lo) / (hi - lo)) * n_bins, inside when 0 <= f < n_bins, bin =
+ *              floor(f).  An entry is inside a pair when both of its axes are inside, and its cell is iv * nu + iu.  Anything else
+ *              is outside: NaN, !(dz > 0) for a quantity that uses dz, D_TRAVEL, R_START, START_X or START_Y on a leak kind, a value
+ *              off either range
+ *   weights    W = round_half_even(w[e] * 2^32) as uint64, 0 for w <= 0 and NaN (the spot maps' q(w)); a cell holds the sum of W over
+ *              its entries, and every (kind, pair, energy) has one outside counter for the rest, so that for each of them
+ *              sum(cells) + outside == sum over the kind's entries of W, exactly
+ *   limits     1 .. 8 pairs; (sum over the pairs of nu * nv) * n_selected <= 2^26; one kind takes at most 2^32 - 1 entries over all
+ *              adds (then no uint64 can wrap); an add past that fails
+ * Sums are integer sums: they depend neither on launch shape ("run_parts", compact or slot order, records or planes, the kernel that
+ * traced the run, the regime), nor on how the slots were split into consecutive runs added to one object, nor on the device count.
+ * Output layout: cells [3][n_selected][total_cells] with the pairs one after the other, each [iv][iu] (total_cells = sum of
+ * nu * nv), outside [3][n_pairs][n_selected], n_entries [3]. */
+enum { PC_HIP_JOINT_START_X = 10, PC_HIP_JOINT_START_Y = 11 };
+typedef struct { pc_hip_hist_axis u, v; } pc_hip_joint_pair;
+typedef struct {
+	int32_t n_pairs;              /* 1 .. 8 */
+	const pc_hip_joint_pair *pairs;
+	int32_t n_energies;           /* selected energies: 0 = all, in order; (sum of nu * nv) * n_selected <= 2^26 */
+	const int32_t *energies;      /* [n_energies] distinct indices into the problem's energies */
+	int32_t regime;               /* 0 automatic (pc_joint.h); 1 workgroup-private LDS tiles, 2 energies across lanes */
+} pc_hip_joint_spec;
+typedef struct pc_hip_joint pc_hip_joint;
+/* PC_HIP_ERR_INVALID with a message that names the pair, the axis (u or v) and the field unless the spec is valid for a problem of
+ * n_energies energies (no device is touched) */
+POLYCAP_EXTERN int pc_hip_joint_validate(const pc_hip_joint_spec *spec, size_t n_energies);
+/* Empty joint histograms for all three kinds on the context's device (the context must outlive them).  The group variant keeps one
+ * set per member; reading it adds the members' sums exactly on the host. */
+POLYCAP_EXTERN int pc_hip_joint_create(pc_hip_ctx *ctx, const pc_hip_joint_spec *spec, pc_hip_joint **joint);
+POLYCAP_EXTERN int pc_hip_group_joint_create(pc_hip_group *group, const pc_hip_joint_spec *spec, pc_hip_joint **joint);
+POLYCAP_EXTERN void pc_hip_joint_destroy(pc_hip_joint *joint);
+/* Adds the entries of kind 0, 1 or 2 of the last run, as pc_hip_hist_add.  Anything else is PC_HIP_ERR_INVALID. */
+POLYCAP_EXTERN int pc_hip_joint_add(pc_hip_joint *joint, int kind);
+/* cells [3][n_selected][total_cells], outside [3][n_pairs][n_selected], n_entries [3] (any may be NULL); waits for the adds */
+POLYCAP_EXTERN int pc_hip_joint_read(pc_hip_joint *joint, uint64_t *cells, uint64_t *outside, int64_t *n_entries);
+POLYCAP_EXTERN int pc_hip_joint_reset(pc_hip_joint *joint);
+/* dims = {n_pairs, n_selected, total_cells}; offsets [n_pairs + 1] (optional): pair p has the cells [offsets[p], offsets[p + 1]) of
+ * an energy's row; *regime (optional) = the regime in use, 1 or 2 */
+POLYCAP_EXTERN int pc_hip_joint_info(const pc_hip_joint *joint, int32_t dims[3], int32_t *offsets, int *regime);
+/* host only, on cells [nv][nu] of one (kind, pair, energy): the exact sums over v (which = 0: out [nu], the histogram of u of what
+ * both ranges hold) or over u (which = 1: out [nv]) */
+POLYCAP_EXTERN int pc_hip_joint_marginal(int32_t nu, int32_t nv, const uint64_t *cells, int which, uint64_t *out);
+/* host only: a value of POLYCAP_JOINT (below) into pairs [8], *n_pairs, energies [n_energies] and *n_selected (0 = all), checked
+ * with pc_hip_joint_validate for a problem of n_energies energies.  PC_HIP_ERR_INVALID with the reason (it names the item) in
+ * why [why_len] otherwise. */
+POLYCAP_EXTERN int pc_hip_joint_parse(const char *value, size_t n_energies, pc_hip_joint_pair *pairs, int32_t *n_pairs,
+	int32_t *energies, int32_t *n_selected, char *why, size_t why_len);
 /* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
  * a focusing optic) in one launch, with exact totals per point.
  *
@@ -597,6 +656,17 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_beam_sums(void *efficiencies
  * without the variable is an error.  Returns 1, or 0 with *error (a polycap_error**) set. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_hist(void *efficiencies, int kind, int32_t dims[3], int32_t **offsets,
 	pc_hip_hist_axis **axes, double **energies, uint64_t **bins, uint64_t **outside, int64_t *n_entries, void *error);
+
+/* Joint histograms of a result made with POLYCAP_JOINT set (every path of the call that POLYCAP_HIST serves), e.g.
+ * POLYCAP_JOINT="axis=x,d=0.5,range=-0.01:0.01,bins=256*axis=slope_x,range=-0.005:0.005,bins=256;axis=start_x,range=-0.3:0.3,bins=512*axis=start_y,range=-0.3:0.3,bins=512;energies=all"
+ * (items separated by ';': a pair is two axes of the POLYCAP_HIST grammar joined by '*', u first; axes as there, and start_x
+ * start_y; energies as there).  kind 0 = exit photons, 1 = extleak, 2 = intleak (leak_calc runs).  dims = {n_pairs, n_selected,
+ * total_cells}; copies, to be freed with polycap_free (any may be NULL): *offsets [n_pairs + 1], *pairs [n_pairs], *energies
+ * [n_selected] keV, the exact sums *cells [n_selected][total_cells] and *outside [n_pairs][n_selected] of pc_hip_joint_read, so that
+ * the results of several seeds pool exactly; *n_entries.  A result made without the variable is an error.  Returns 1, or 0 with
+ * *error (a polycap_error**) set. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_joint(void *efficiencies, int kind, int32_t dims[3], int32_t **offsets,
+	pc_hip_joint_pair **pairs, double **energies, uint64_t **cells, uint64_t **outside, int64_t *n_entries, void *error);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,17 @@ class HistSpecS(C.Structure):
                 ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
 
 
+class JointPairS(C.Structure):
+    """struct pc_hip_joint_pair"""
+    _fields_ = [("u", HistAxisS), ("v", HistAxisS)]
+
+
+class JointSpecS(C.Structure):
+    """struct pc_hip_joint_spec"""
+    _fields_ = [("n_pairs", C.c_int32), ("pairs", C.POINTER(JointPairS)), ("n_energies", C.c_int32),
+                ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -259,6 +270,26 @@ def lib():
     L.pc_hip_hist_quantile.restype = C.c_double
     L.pc_hip_hist_fwhm.argtypes = [C.c_int32, C.c_double, C.c_double, P(C.c_uint64), c_double_p, c_double_p]
     L.pc_hip_hist_fwhm.restype = C.c_double
+    L.pc_hip_joint_validate.argtypes = [P(JointSpecS), C.c_size_t]
+    L.pc_hip_joint_validate.restype = C.c_int
+    L.pc_hip_joint_create.argtypes = [C.c_void_p, P(JointSpecS), P(C.c_void_p)]
+    L.pc_hip_joint_create.restype = C.c_int
+    L.pc_hip_group_joint_create.argtypes = [C.c_void_p, P(JointSpecS), P(C.c_void_p)]
+    L.pc_hip_group_joint_create.restype = C.c_int
+    L.pc_hip_joint_destroy.argtypes = [C.c_void_p]
+    L.pc_hip_joint_destroy.restype = None
+    L.pc_hip_joint_add.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_joint_add.restype = C.c_int
+    L.pc_hip_joint_read.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), c_int64_p]
+    L.pc_hip_joint_read.restype = C.c_int
+    L.pc_hip_joint_reset.argtypes = [C.c_void_p]
+    L.pc_hip_joint_reset.restype = C.c_int
+    L.pc_hip_joint_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int)]
+    L.pc_hip_joint_info.restype = C.c_int
+    L.pc_hip_joint_marginal.argtypes = [C.c_int32, C.c_int32, P(C.c_uint64), C.c_int, P(C.c_uint64)]
+    L.pc_hip_joint_marginal.restype = C.c_int
+    L.pc_hip_joint_parse.argtypes = [C.c_char_p, C.c_size_t, P(JointPairS), P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_char_p, C.c_size_t]
+    L.pc_hip_joint_parse.restype = C.c_int
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
     u64p = P(C.c_uint64)

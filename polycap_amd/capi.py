@@ -133,6 +133,8 @@ def _lib():
         "pc_transmission_efficiencies_get_moments": (C.c_int, [vp, P(C.c_int64), P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
         "pc_transmission_efficiencies_get_hist": (C.c_int, [vp, C.c_int, P(C.c_int32), P(P(C.c_int32)), P(P(_cabi.HistAxisS)), P(_dp),
                                                             P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
+        "pc_transmission_efficiencies_get_joint": (C.c_int, [vp, C.c_int, P(C.c_int32), P(P(C.c_int32)), P(P(_cabi.JointPairS)), P(_dp),
+                                                             P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -493,6 +495,27 @@ class TransmissionEfficiencies(_LeakData):
         L.polycap_free(C.cast(a, C.c_void_p))
         return dict(bins=_take(b, ns * tb, np.uint64).reshape(ns, tb), outside=_take(u, na * ns, np.uint64).reshape(na, ns),
                     n_entries=int(ni.value), offsets=_take(o, na + 1, np.int32), energies=_take(e, ns), axes=axes)
+
+    def joint(self, kind="exit"):
+        """Joint histograms of a run made with POLYCAP_JOINT set (extension, pc_transmission_efficiencies_get_joint): dict of the
+        exact sums cells uint64 [energies, total_cells] (the pairs one after the other, each [iv][iu]) and outside uint64
+        [pairs, energies], n_entries, offsets [pairs + 1], energies (keV) and pairs, a list of (u, v) axis dicts (axis, d, centre,
+        range, bins).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        from .hip import _axis_dict
+        L = _lib()
+        dims = (C.c_int32 * 3)()
+        o, a, e = C.POINTER(C.c_int32)(), C.POINTER(_cabi.JointPairS)(), _dp()
+        b, u = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        ni = C.c_int64(0)
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_joint(self._h, self.SPOT_KINDS[kind], dims, C.byref(o), C.byref(a), C.byref(e), C.byref(b),
+                                                 C.byref(u), C.byref(ni), C.byref(err))
+        _check(err)
+        n_pairs, ns, tc = (int(v) for v in dims)
+        pairs = [(_axis_dict(a[k].u), _axis_dict(a[k].v)) for k in range(n_pairs)]
+        L.polycap_free(C.cast(a, C.c_void_p))
+        return dict(cells=_take(b, ns * tc, np.uint64).reshape(ns, tc), outside=_take(u, n_pairs * ns, np.uint64).reshape(n_pairs, ns),
+                    n_entries=int(ni.value), offsets=_take(o, n_pairs + 1, np.int32), energies=_take(e, ns), pairs=pairs)
 
     def _start(self):
         L = _lib()

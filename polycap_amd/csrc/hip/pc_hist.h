@@ -23,7 +23,9 @@
 
 #define PC_HIST_MAX_AXES 16
 enum { PC_HIST_X_AT = 0, PC_HIST_Y_AT, PC_HIST_R_AT, PC_HIST_SLOPE_X, PC_HIST_SLOPE_Y, PC_HIST_TAN_THETA, PC_HIST_N_REFL,
-       PC_HIST_D_TRAVEL, PC_HIST_R_START, PC_HIST_Z, PC_HIST_N_QUANTITIES };
+       PC_HIST_D_TRAVEL, PC_HIST_R_START, PC_HIST_Z, PC_HIST_N_QUANTITIES,
+       /* joint histograms only (pc_joint.h): the start coordinates themselves; pc_hip_hist_validate refuses them */
+       PC_JOINT_START_X = PC_HIST_N_QUANTITIES, PC_JOINT_START_Y, PC_JOINT_N_QUANTITIES };
 
 /* one entry: position, direction, reflection count (as a double), and for exit photons the path length and the start
  * coordinates in the optic's entrance plane; leak = 1 for leak events, which have neither of the last two */
@@ -60,6 +62,8 @@ static inline __host__ __device__ double pc_hist_value(const pc_hist_axis_k &a, 
 	case PC_HIST_D_TRAVEL: *ok = !e.leak; return e.dtravel;
 	case PC_HIST_R_START: *ok = !e.leak; return sqrt(e.sx*e.sx + e.sy*e.sy);
 	case PC_HIST_Z: return e.z;
+	case PC_JOINT_START_X: *ok = !e.leak; return e.sx;
+	case PC_JOINT_START_Y: *ok = !e.leak; return e.sy;
 	}
 	*ok = 0;
 	return 0.;
@@ -141,7 +145,9 @@ struct pc_hist_geo {
 	int need_start, need_travel, need_n;      /* which of the optional fields some axis reads */
 };
 
-static __device__ __forceinline__ void pc_hist_load(const pc_spot_src &s, const pc_hist_geo &g, long long i, pc_hist_entry &e)
+/* entry i with the optional fields that g says some axis reads (Geo: pc_hist_geo, or pc_joint_geo of pc_joint.h) */
+template <typename Geo>
+static __device__ __forceinline__ void pc_hist_load(const pc_spot_src &s, const Geo &g, long long i, pc_hist_entry &e)
 {
 	const pc_entry b = pc_entry_load(s, i);
 	const double *p = s.p + i*s.ss;
@@ -306,29 +312,40 @@ static int pc_hist_launch(pc_hip_hist *h, pc_tally_member &m, const pc_spot_src 
 	return PC_HIP_OK;
 }
 
+/* One axis of a spec: false and the reason in *why (it names the field) when it is refused.  n_quantities = PC_HIST_N_QUANTITIES for
+ * a histogram, PC_JOINT_N_QUANTITIES for a joint histogram. */
+static bool pc_hist_axis_check(const pc_hip_hist_axis &x, int n_quantities, std::string *why)
+{
+	static const char *names[PC_JOINT_N_QUANTITIES] = { "X_AT", "Y_AT", "R_AT", "SLOPE_X", "SLOPE_Y", "TAN_THETA", "N_REFL", "D_TRAVEL", "R_START", "Z",
+	                                                    "START_X", "START_Y" };
+	*why = "";
+	if (x.quantity < 0 || x.quantity >= n_quantities)
+		*why = std::string("quantity must be one of PC_HIP_HIST_X_AT .. ") + (n_quantities == PC_HIST_N_QUANTITIES ? "PC_HIP_HIST_Z" : "PC_HIP_JOINT_START_Y")
+		     + ", got " + std::to_string(x.quantity);
+	else if (!std::isfinite(x.d) || !(x.d >= 0.) || (x.quantity > PC_HIST_R_AT && x.d != 0.))
+		*why = std::string("d must be finite and >= 0, and 0 for ") + names[x.quantity] + " (X_AT, Y_AT and R_AT use it)";
+	else if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || (x.quantity != PC_HIST_R_AT && (x.cx != 0. || x.cy != 0.)))
+		*why = std::string("cx and cy must be finite, and 0 for ") + names[x.quantity] + " (R_AT uses them)";
+	else if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi))
+		*why = "lo and hi must be finite with lo < hi";
+	else if (x.n_bins < 1)
+		*why = "n_bins must be >= 1";
+	return why->empty();
+}
+
 extern "C" {
 
 int pc_hip_hist_validate(const pc_hip_hist_spec *spec, size_t n_energies)
 {
-	static const char *names[PC_HIST_N_QUANTITIES] = { "X_AT", "Y_AT", "R_AT", "SLOPE_X", "SLOPE_Y", "TAN_THETA", "N_REFL", "D_TRAVEL", "R_START", "Z" };
 	if (!spec) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: spec must not be NULL");
 	if (spec->n_axes < 1 || spec->n_axes > PC_HIST_MAX_AXES || !spec->axes)
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: n_axes: 1 to 16 axes are needed, got " + std::to_string(spec->n_axes));
 	double bins = 0.;
 	for (int a = 0; a < spec->n_axes; a++) {
 		const pc_hip_hist_axis &x = spec->axes[a];
-		const std::string at = "pc_hip_hist_validate: axis " + std::to_string(a) + ": ";
-		if (x.quantity < 0 || x.quantity >= PC_HIST_N_QUANTITIES)
-			return pc_fail(PC_HIP_ERR_INVALID, at + "quantity must be one of PC_HIP_HIST_X_AT .. PC_HIP_HIST_Z, got " + std::to_string(x.quantity));
-		const bool plane = x.quantity <= PC_HIST_R_AT;
-		if (!std::isfinite(x.d) || !(x.d >= 0.) || (!plane && x.d != 0.))
-			return pc_fail(PC_HIP_ERR_INVALID, at + "d must be finite and >= 0, and 0 for " + names[x.quantity] + " (X_AT, Y_AT and R_AT use it)");
-		if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || (x.quantity != PC_HIST_R_AT && (x.cx != 0. || x.cy != 0.)))
-			return pc_fail(PC_HIP_ERR_INVALID, at + "cx and cy must be finite, and 0 for " + names[x.quantity] + " (R_AT uses them)");
-		if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi))
-			return pc_fail(PC_HIP_ERR_INVALID, at + "lo and hi must be finite with lo < hi");
-		if (x.n_bins < 1)
-			return pc_fail(PC_HIP_ERR_INVALID, at + "n_bins must be >= 1");
+		std::string why;
+		if (!pc_hist_axis_check(x, PC_HIST_N_QUANTITIES, &why))
+			return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: axis " + std::to_string(a) + ": " + why);
 		bins += (double)x.n_bins;
 	}
 	if (spec->regime < 0 || spec->regime > 2)

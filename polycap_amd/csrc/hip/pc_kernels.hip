@@ -2089,6 +2089,7 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_spot.h"
 #include "pc_beam.h"
 #include "pc_hist.h"
+#include "pc_joint.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
 

@@ -24,7 +24,10 @@
  *   /Beam/<K>_Entries [1] uint64 and /Beam/<K> [nE, 26] fp64 with a "Columns" attribute (include/polycap-hip.h); with POLYCAP_HIST
  *   the groups /Hist/<K>: Axes [n_axes, 8] fp64 (Columns: quantity,d,cx,cy,lo,hi,n_bins,offset), Energies [nS] keV, Bins
  *   [nS, total_bins] and Outside [n_axes, nS] uint64 (the exact sums), Entries [1] uint64, and Efficiency [nS, total_bins] with
- *   Efficiency_Outside [n_axes, nS] fp64: per axis and energy they sum to the efficiency
+ *   Efficiency_Outside [n_axes, nS] fp64: per axis and energy they sum to the efficiency; with POLYCAP_JOINT the groups /Joint/<K>,
+ *   shaped alike: Pairs [n_pairs, 15] fp64 (Columns: the seven axis fields of u, those of v, offset), Energies [nS] keV, Cells
+ *   [nS, total_cells] (the pairs one after the other, each [iv][iu]) and Outside [n_pairs, nS] uint64, Entries [1] uint64, Efficiency
+ *   [nS, total_cells] with Efficiency_Outside [n_pairs, nS] fp64
  *
  * libhdf5 is bound at run time (dlopen), like xraylib in pc_optconst.c, so libpolycap.so carries no link-time
  * dependency on it: hosts without HDF5 get POLYCAP_ERROR_UNSUPPORTED from this one function and nothing else changes.
@@ -480,6 +483,71 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		}
 		free(table); free(sel_e); free(in); free(out);
 		if (!hok) goto close;
+	}
+
+	if (efficiencies->joint != NULL) {
+		/* extension: the exact joint histograms of POLYCAP_JOINT (include/polycap-hip.h) and the same in efficiency units */
+		const struct pc_joint_result *jr = efficiencies->joint;
+		static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+		const size_t np = (size_t)jr->n_pairs, ns = (size_t)jr->n_sel, tc = (size_t)jr->total_cells;
+		bool jok = pc_h5_group(file, "/Joint", error);
+		double *table = malloc(sizeof(double) * 15 * np), *sel_e = malloc(sizeof(double) * (ns ? ns : 1));
+		double *in = malloc(sizeof(double) * ns * tc), *out = malloc(sizeof(double) * np * ns);      /* all three are >= 1 */
+		jok = jok && table != NULL && sel_e != NULL && in != NULL && out != NULL;
+		for (size_t p = 0; jok && p < np; p++) {
+			const pc_hip_hist_axis *u = &jr->pairs[p].u, *v = &jr->pairs[p].v;
+			const double row[15] = { (double)u->quantity, u->d, u->cx, u->cy, u->lo, u->hi, (double)u->n_bins,
+			                         (double)v->quantity, v->d, v->cx, v->cy, v->lo, v->hi, (double)v->n_bins, (double)jr->offsets[p] };
+			memcpy(table + 15*p, row, sizeof row);
+		}
+		for (size_t k = 0; jok && k < ns; k++)
+			sel_e[k] = efficiencies->energies[jr->sel[k]];
+		for (int k = 0; k < 3 && jok; k++) {
+			if (jr->cells[k] == NULL)
+				continue;
+			char g[32], name[64];
+			snprintf(g, sizeof g, "/Joint/%s", names[k]);
+			jok = jok && pc_h5_group(file, g, error);
+			pc_hsize jd[2] = { (pc_hsize)np, 15 };
+			snprintf(name, sizeof name, "%s/Pairs", g);
+			jok = jok && pc_h5_typed(file, 2, jd, name, *h5.native_double, table, "a.u., cm",
+			                         "u_quantity,u_d,u_cx,u_cy,u_lo,u_hi,u_n_bins,v_quantity,v_d,v_cx,v_cy,v_lo,v_hi,v_n_bins,offset", error);
+			jd[0] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Energies", g);
+			jok = jok && pc_h5_dataset(file, 1, jd, name, sel_e, "keV", error);
+			jd[0] = (pc_hsize)ns; jd[1] = (pc_hsize)tc;
+			snprintf(name, sizeof name, "%s/Cells", g);
+			jok = jok && pc_h5_typed(file, 2, jd, name, *h5.native_ullong, jr->cells[k], "2^-32", NULL, error);
+			jd[0] = (pc_hsize)np; jd[1] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Outside", g);
+			jok = jok && pc_h5_typed(file, 2, jd, name, *h5.native_ullong, jr->outside[k], "2^-32", NULL, error);
+			const uint64_t n_entries = (uint64_t)jr->n_entries[k];
+			pc_hsize one = 1;
+			snprintf(name, sizeof name, "%s/Entries", g);
+			jok = jok && pc_h5_typed(file, 1, &one, name, *h5.native_ullong, &n_entries, "a.u.", NULL, error);
+			/* efficiency[e] * S_cell / (S_inside + S_outside), the spot maps' normalisation: per pair and energy the cells and the
+			 * outside part sum to the efficiency */
+			for (size_t p = 0; jok && p < np; p++)
+				for (size_t s = 0; s < ns; s++) {
+					const uint64_t *b = jr->cells[k] + s*tc + (size_t)jr->offsets[p];
+					const size_t nb = (size_t)(jr->offsets[p + 1] - jr->offsets[p]);
+					uint64_t total = jr->outside[k][p*ns + s];
+					for (size_t j = 0; j < nb; j++)
+						total += b[j];
+					const double eff_e = efficiencies->efficiencies[jr->sel[s]], tot = (double)total;
+					for (size_t j = 0; j < nb; j++)
+						in[s*tc + (size_t)jr->offsets[p] + j] = total ? eff_e * (double)b[j] / tot : 0.;
+					out[p*ns + s] = total ? eff_e * (double)jr->outside[k][p*ns + s] / tot : 0.;
+				}
+			jd[0] = (pc_hsize)ns; jd[1] = (pc_hsize)tc;
+			snprintf(name, sizeof name, "%s/Efficiency", g);
+			jok = jok && pc_h5_dataset(file, 2, jd, name, in, "a.u.", error);
+			jd[0] = (pc_hsize)np; jd[1] = (pc_hsize)ns;
+			snprintf(name, sizeof name, "%s/Efficiency_Outside", g);
+			jok = jok && pc_h5_dataset(file, 2, jd, name, out, "a.u.", error);
+		}
+		free(table); free(sel_e); free(in); free(out);
+		if (!jok) goto close;
 	}
 
 	if (!pc_h5_group(file, "/Input", error)) goto close;

@@ -154,6 +154,17 @@ struct pc_hist_result {
 	int64_t n_entries[3];
 };
 
+/* extension: exact joint histograms of a run made with POLYCAP_JOINT set (pc_transmission_efficiencies_get_joint) */
+struct pc_joint_result {
+	int32_t n_pairs, n_sel, total_cells;
+	pc_hip_joint_pair *pairs;  /* [n_pairs] */
+	int32_t *offsets;          /* [n_pairs + 1] */
+	int32_t *sel;              /* [n_sel] energy indices */
+	uint64_t *cells[3];        /* exit photons, extleak, intleak: [energy][total_cells], NULL when the run has none */
+	uint64_t *outside[3];      /* [pair][energy] */
+	int64_t n_entries[3];
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -164,6 +175,7 @@ struct _polycap_transmission_efficiencies {
 	struct pc_spot_result *spot;
 	struct pc_beam_result *beam;
 	struct pc_hist_result *hist;
+	struct pc_joint_result *joint;
 	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
 	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
 	int64_t n_started;
@@ -220,5 +232,6 @@ void pc_set_hip_error(polycap_error **error, const char *caller, int status);
 void pc_spot_result_free(struct pc_spot_result *spot);
 void pc_beam_result_free(struct pc_beam_result *beam);
 void pc_hist_result_free(struct pc_hist_result *hist);
+void pc_joint_result_free(struct pc_joint_result *joint);
 
 #endif

@@ -497,9 +497,10 @@ static int pc_hist_parse_pair(const char *v, double *a, double *b)
 	return (end == v || errno != 0 || *end != '\0') ? -1 : 0;
 }
 
-static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax)
+/* n_names: 10 for a histogram axis, 12 for an axis of a joint histogram (start_x and start_y as well) */
+static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax, int n_names)
 {
-	static const char *names[] = { "x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z" };
+	static const char *names[] = { "x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z", "start_x", "start_y" };
 	int have_axis = 0, have_range = 0, have_bins = 0;
 	char *save = NULL;
 	memset(ax, 0, sizeof(*ax));
@@ -512,11 +513,12 @@ static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax)
 		char *end = NULL;
 		if (strcmp(kv, "axis") == 0) {
 			ax->quantity = -1;
-			for (int q = 0; q < 10; q++)
+			for (int q = 0; q < n_names; q++)
 				if (strcmp(v, names[q]) == 0)
 					ax->quantity = q;
 			if (ax->quantity < 0)
-				return "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z";
+				return n_names == 10 ? "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z"
+				                     : "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z start_x start_y";
 			have_axis = 1;
 		} else if (strcmp(kv, "d") == 0) {
 			errno = 0;
@@ -543,6 +545,29 @@ static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax)
 	return (have_axis && have_range && have_bins) ? NULL : "an axis needs axis, range and bins";
 }
 
+/* the value of an energies= item into *list (malloc'd, NULL for "all") and *n: NULL, or what is wrong */
+static const char *pc_hist_parse_energies(const char *v, size_t n_energies, int32_t **list, int *n)
+{
+	static const char *const bad = "energies must be all or a list of energy indices";
+	free(*list);
+	*list = NULL;
+	*n = 0;
+	if (strcmp(v, "all") == 0)
+		return NULL;
+	*list = malloc(sizeof(int32_t) * (n_energies + 1));
+	while (*list != NULL && *v != '\0') {
+		char *end = NULL;
+		const long e = strtol(v, &end, 10);
+		if (end == v || (size_t)*n > n_energies)
+			return bad;
+		(*list)[(*n)++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
+		v = end;
+		if (*v == ',') v++;
+		else if (*v != '\0') return bad;
+	}
+	return *n == 0 ? bad : NULL;
+}
+
 static int pc_hist_request_parse(struct pc_hist_request *r, size_t n_energies, polycap_error **error)
 {
 	memset(r, 0, sizeof(*r));
@@ -555,25 +580,9 @@ static int pc_hist_request_parse(struct pc_hist_request *r, size_t n_energies, p
 	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save)) {
 		if (strncmp(item, "axis=", 5) == 0) {
 			if (r->n_axes >= 17) { bad = "at most 16 axes"; break; }
-			bad = pc_hist_parse_axis(item, &r->axes[r->n_axes++]);
+			bad = pc_hist_parse_axis(item, &r->axes[r->n_axes++], 10);
 		} else if (strncmp(item, "energies=", 9) == 0) {
-			const char *v = item + 9;
-			free(r->energies);
-			r->energies = NULL;
-			r->n_energies = 0;
-			if (strcmp(v, "all") == 0)
-				continue;
-			r->energies = malloc(sizeof(int32_t) * (n_energies + 1));
-			while (r->energies != NULL && *v != '\0') {
-				char *end = NULL;
-				const long e = strtol(v, &end, 10);
-				if (end == v || (size_t)r->n_energies > n_energies) { bad = "energies must be all or a list of energy indices"; break; }
-				r->energies[r->n_energies++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
-				v = end;
-				if (*v == ',') v++;
-				else if (*v != '\0') { bad = "energies must be all or a list of energy indices"; break; }
-			}
-			if (bad == NULL && r->n_energies == 0) bad = "energies must be all or a list of energy indices";
+			bad = pc_hist_parse_energies(item + 9, n_energies, &r->energies, &r->n_energies);
 		} else {
 			bad = "every item must be an axis (axis=NAME,...) or energies=";
 		}
@@ -598,6 +607,99 @@ static int pc_hist_request_parse(struct pc_hist_request *r, size_t n_energies, p
 	return 0;
 }
 
+/* POLYCAP_JOINT, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=256*axis=slope_x,range=-0.005:0.005,bins=256;axis=start_x,range=-0.3:0.3,bins=512*axis=start_y,range=-0.3:0.3,bins=512;energies=all":
+ * joint histograms of the run (include/polycap-hip.h, pc_hip_joint_*).  Items are separated by ';': a pair (two axes of the
+ * POLYCAP_HIST grammar joined by '*', u first; start_x and start_y are axes here too) or energies= as in POLYCAP_HIST.  Parsed and
+ * validated before any device is used. */
+struct pc_joint_request {
+	int set;
+	pc_hip_joint_pair pairs[9];
+	int n_pairs;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_joint_spec spec;
+};
+
+/* `value` into r (r->energies is the caller's to free): NULL, or what is wrong; a refusal of pc_hip_joint_validate is its message */
+static const char *pc_joint_request_parse_value(struct pc_joint_request *r, const char *value, size_t n_energies)
+{
+	static _Thread_local char why[160];      /* the item at fault */
+	memset(r, 0, sizeof(*r));
+	r->set = 1;
+	char *buf = strdup(value), *save = NULL;
+	const char *bad = NULL;
+	int n_item = 0;
+	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save), n_item++) {
+		if (strncmp(item, "axis=", 5) == 0) {
+			char *star = strchr(item, '*');
+			if (r->n_pairs >= 9) { bad = "at most 8 pairs"; break; }
+			if (star == NULL || strncmp(star + 1, "axis=", 5) != 0 || strchr(star + 1, '*') != NULL)
+				bad = "a pair must be two axes joined by '*' (axis=NAME,...*axis=NAME,...)";
+			else {
+				*star = '\0';
+				pc_hip_joint_pair *pr = &r->pairs[r->n_pairs++];
+				bad = pc_hist_parse_axis(item, &pr->u, 12);
+				if (bad == NULL)
+					bad = pc_hist_parse_axis(star + 1, &pr->v, 12);
+			}
+		} else if (strncmp(item, "energies=", 9) == 0) {
+			bad = pc_hist_parse_energies(item + 9, n_energies, &r->energies, &r->n_energies);
+		} else {
+			bad = "every item must be a pair (axis=NAME,...*axis=NAME,...) or energies=";
+		}
+		if (bad != NULL) {
+			snprintf(why, sizeof why, "item %d: %s", n_item, bad);
+			bad = why;
+		}
+	}
+	free(buf);
+	if (bad == NULL && r->n_pairs == 0)
+		bad = "at least one pair is needed";
+	if (bad == NULL) {
+		r->spec.n_pairs = r->n_pairs;
+		r->spec.pairs = r->pairs;
+		r->spec.n_energies = r->n_energies;
+		r->spec.energies = r->energies;
+		if (pc_hip_joint_validate(&r->spec, n_energies) != PC_HIP_OK)
+			bad = pc_hip_last_error();
+	}
+	return bad;
+}
+
+static int pc_joint_request_parse(struct pc_joint_request *r, size_t n_energies, polycap_error **error)
+{
+	memset(r, 0, sizeof(*r));
+	const char *env = getenv("POLYCAP_JOINT");
+	if (env == NULL)
+		return 0;
+	const char *bad = pc_joint_request_parse_value(r, env, n_energies);
+	if (bad != NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_JOINT=%s: %s", env, bad);
+		free(r->energies);
+		r->energies = NULL;
+		return -1;
+	}
+	return 0;
+}
+
+int pc_hip_joint_parse(const char *value, size_t n_energies, pc_hip_joint_pair *pairs, int32_t *n_pairs, int32_t *energies, int32_t *n_selected,
+	char *why, size_t why_len)
+{
+	struct pc_joint_request r;
+	const char *bad = value != NULL ? pc_joint_request_parse_value(&r, value, n_energies) : "value must not be NULL";
+	if (why != NULL && why_len > 0)
+		snprintf(why, why_len, "%s", bad != NULL ? bad : "");
+	if (bad == NULL) {
+		if (pairs != NULL) memcpy(pairs, r.pairs, sizeof(pc_hip_joint_pair)*(size_t)r.n_pairs);
+		if (n_pairs != NULL) *n_pairs = r.n_pairs;
+		if (energies != NULL && r.n_energies > 0) memcpy(energies, r.energies, sizeof(int32_t)*(size_t)r.n_energies);
+		if (n_selected != NULL) *n_selected = r.n_energies;
+	}
+	if (value != NULL)
+		free(r.energies);
+	return bad == NULL ? PC_HIP_OK : PC_HIP_ERR_INVALID;
+}
+
 /* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
 static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 {
@@ -608,12 +710,12 @@ static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 	}
 }
 
-/* POLYCAP_IMAGES=0 with spot maps, beam moments or histograms on one context: the exit data of the run stay on the device, and a run whose exit
+/* POLYCAP_IMAGES=0 with spot maps, beam moments, histograms or joint histograms on one context: the exit data of the run stay on the device, and a run whose exit
  * data would take more than the stated share of the device's memory is traced as consecutive slot ranges (photons are keyed by
  * (seed, slot): the same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is
- * added to the map, to the beam sums and to the histograms (any may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
+ * added to the map, to the beam sums, to the histograms and to the joint histograms (any may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
  * POLYCAP_STDERR) those of the squared weights. */
-static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, pc_hip_hist *hist, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
+static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, pc_hip_hist *hist, pc_hip_joint *joint, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
 	size_t ne, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	uint64_t *part = malloc(2*ne*sizeof(uint64_t));
@@ -633,6 +735,8 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam
 			st = pc_hip_beam_add(beam, 0);
 		if (st == PC_HIP_OK && hist != NULL)
 			st = pc_hip_hist_add(hist, 0);
+		if (st == PC_HIP_OK && joint != NULL)
+			st = pc_hip_joint_add(joint, 0);
 		if (st == PC_HIP_OK)
 			st = pc_hip_transmission_totals(ctx, NULL, c, part);
 		if (st != PC_HIP_OK)
@@ -760,6 +864,41 @@ static int pc_hist_store(polycap_transmission_efficiencies *eff, pc_hip_hist *hi
 	return st;
 }
 
+/* the exact joint histograms of every kind the run has into the result */
+static int pc_joint_store(polycap_transmission_efficiencies *eff, pc_hip_joint *joint, const struct pc_joint_request *r, int leak_calc)
+{
+	int32_t dims[3];
+	int st = pc_hip_joint_info(joint, dims, NULL, NULL);
+	if (st != PC_HIP_OK)
+		return st;
+	const size_t np = (size_t)dims[0], ns = (size_t)dims[1], tc = (size_t)dims[2];
+	struct pc_joint_result *jr = eff->joint = calloc(1, sizeof(*jr));
+	if (jr == NULL)
+		return PC_HIP_ERR_MEMORY;
+	jr->n_pairs = dims[0]; jr->n_sel = dims[1]; jr->total_cells = dims[2];
+	jr->pairs = pc_beam_dup(r->pairs, sizeof(pc_hip_joint_pair)*np);
+	jr->offsets = malloc(sizeof(int32_t)*(np + 1));
+	jr->sel = malloc(sizeof(int32_t)*(ns ? ns : 1));
+	uint64_t *cells = malloc(sizeof(uint64_t)*3*ns*tc), *out = malloc(sizeof(uint64_t)*3*np*ns);
+	if (jr->pairs == NULL || jr->offsets == NULL || jr->sel == NULL || cells == NULL || out == NULL)
+		st = PC_HIP_ERR_MEMORY;
+	if (st == PC_HIP_OK)
+		st = pc_hip_joint_info(joint, dims, jr->offsets, NULL);
+	if (st == PC_HIP_OK)
+		st = pc_hip_joint_read(joint, cells, out, jr->n_entries);
+	for (size_t k = 0; st == PC_HIP_OK && k < ns; k++)
+		jr->sel[k] = r->n_energies ? r->energies[k] : (int32_t)k;
+	for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++) {
+		jr->cells[kind] = pc_beam_dup(cells + kind*ns*tc, sizeof(uint64_t)*ns*tc);
+		jr->outside[kind] = pc_beam_dup(out + kind*np*ns, sizeof(uint64_t)*np*ns);
+		if (jr->cells[kind] == NULL || jr->outside[kind] == NULL)
+			st = PC_HIP_ERR_MEMORY;
+	}
+	free(cells);
+	free(out);
+	return st;
+}
+
 /* the argument checks of the reference call, in its order: the message of the first one that fails, or NULL */
 static const char *pc_transmission_args_bad(const polycap_source *source, const polycap_progress_monitor *progress_monitor, int n_photons)
 {
@@ -792,6 +931,7 @@ struct pc_run_request {
 	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
 	struct pc_spot_request spot;
 	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
+	struct pc_joint_request joint; /* POLYCAP_JOINT: exact joint 2-D histograms per energy (pc_hip_joint_*) */
 	int devices[64], n_devices;
 	int keep_images;
 	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
@@ -808,6 +948,7 @@ static void pc_run_request_free(struct pc_run_request *r)
 {
 	free(r->spot.energies);
 	free(r->hist.energies);
+	free(r->joint.energies);
 }
 
 static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_calc, int n_photons, polycap_error **error)
@@ -830,7 +971,9 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 		return -1;
 	if (pc_hist_request_parse(&r->hist, ne, error) != 0)
 		return -1;
-	if ((r->beam_on || r->hist.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and histograms too */
+	if (pc_joint_request_parse(&r->joint, ne, error) != 0)
+		return -1;
+	if ((r->beam_on || r->hist.set || r->joint.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and (joint) histograms too */
 		r->spot.share = 0.5;
 		const char *share = getenv("POLYCAP_SPOT_SHARE");
 		if (share != NULL && *share != '\0') {
@@ -873,10 +1016,11 @@ struct pc_target {
 };
 
 /* Trace stage: with POLYCAP_SPOT the maps are made first (exit photons; leak runs also extleak and intleak), with POLYCAP_BEAM the
- * beam sums, with POLYCAP_HIST the histograms, then the options are set and the run is enqueued.  *chunked = 1 when pc_spot_chunked
- * traced the run: it also read the totals and moments, and added every range to spot[0], *beam and *hist. */
+ * beam sums, with POLYCAP_HIST the histograms, with POLYCAP_JOINT the joint histograms, then the options are set and the run is
+ * enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the totals and moments, and added every range to spot[0],
+ * *beam, *hist and *joint. */
 static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak_calc, uint64_t seed, int64_t n_photons, size_t ne,
-	pc_hip_spot *spot[3], pc_hip_beam **beam, pc_hip_hist **hist, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
+	pc_hip_spot *spot[3], pc_hip_beam **beam, pc_hip_hist **hist, pc_hip_joint **joint, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	int st = PC_HIP_OK;
 	int64_t chunk = 0;
@@ -887,8 +1031,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		st = t.group != NULL ? pc_hip_group_beam_create(t.group, beam) : pc_hip_beam_create(t.ctx, beam);
 	if (r->hist.set && st == PC_HIP_OK)
 		st = t.group != NULL ? pc_hip_group_hist_create(t.group, &r->hist.spec, hist) : pc_hip_hist_create(t.ctx, &r->hist.spec, hist);
-	if (r->spot.set || r->beam_on || r->hist.set) {
-		/* POLYCAP_IMAGES=0 with spot maps, beam moments or histograms is chunked on one device only: a group traces the whole run at once */
+	if (r->joint.set && st == PC_HIP_OK)
+		st = t.group != NULL ? pc_hip_group_joint_create(t.group, &r->joint.spec, joint) : pc_hip_joint_create(t.ctx, &r->joint.spec, joint);
+	if (r->spot.set || r->beam_on || r->hist.set || r->joint.set) {
+		/* POLYCAP_IMAGES=0 with spot maps, beam moments or (joint) histograms is chunked on one device only: a group traces the whole run at once */
 		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
 			uint64_t total_b = 0;
 			st = pc_hip_device_memory(t.ctx, NULL, &total_b);
@@ -912,10 +1058,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		return st;
 	if (chunk > 0 && chunk < n_photons) {
 		*chunked = 1;
-		return pc_spot_chunked(t.ctx, spot[0], *beam, *hist, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
+		return pc_spot_chunked(t.ctx, spot[0], *beam, *hist, *joint, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
 	}
-	/* POLYCAP_SPOT, POLYCAP_BEAM, POLYCAP_HIST: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
-	const int device_images = r->keep_images || r->spot.set || r->beam_on || r->hist.set;
+	/* POLYCAP_SPOT, POLYCAP_BEAM, POLYCAP_HIST, POLYCAP_JOINT: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
+	const int device_images = r->keep_images || r->spot.set || r->beam_on || r->hist.set || r->joint.set;
 	if (leak_calc)
 		return t.group != NULL ? pc_hip_group_run_leak(t.group, seed, n_photons, r->max_attempts, 1)
 		                       : pc_hip_transmission_run_leak(t.ctx, seed, 0, n_photons, r->max_attempts, 1);
@@ -965,6 +1111,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	pc_hip_spot *spot[3] = { NULL, NULL, NULL };         /* exit photons, extleak, intleak */
 	pc_hip_beam *beam = NULL;                            /* POLYCAP_BEAM: the exact beam sums of every kind */
 	pc_hip_hist *hist = NULL;                            /* POLYCAP_HIST: the exact histograms of every kind */
+	pc_hip_joint *joint = NULL;                          /* POLYCAP_JOINT: the exact joint histograms of every kind */
 	int64_t counters[6] = { 0, 0, 0, 0, 0, 0 };
 	int status = PC_HIP_OK, chunked = 0, reduced_by = 0;      /* a failed HIP call: its error is set at `out` */
 	double t_stage[6];
@@ -996,7 +1143,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	const uint64_t seed = req.have_seed ? req.seed : source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
 	source->run_index++;
 
-	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &hist, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
+	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &hist, &joint, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
 	t_stage[2] = t_stage[3] = pc_now_ms();
 	if (status == PC_HIP_OK && req.keep_images)
 		status = pc_fetch_images(t, eff, n_photons, &t_stage[3]);
@@ -1026,6 +1173,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		status = pc_hip_beam_add(beam, kind);
 	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && hist != NULL; kind++)
 		status = pc_hip_hist_add(hist, kind);
+	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && joint != NULL; kind++)
+		status = pc_hip_joint_add(joint, kind);
 	if (status != PC_HIP_OK)
 		goto out;
 
@@ -1046,6 +1195,8 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		status = pc_beam_store(eff, beam, leak_calc);
 	if (status == PC_HIP_OK && hist != NULL)
 		status = pc_hist_store(eff, hist, &req.hist, leak_calc);
+	if (status == PC_HIP_OK && joint != NULL)
+		status = pc_joint_store(eff, joint, &req.joint, leak_calc);
 	if (status != PC_HIP_OK)
 		goto out;
 	if (req.stderr_on) {      /* without POLYCAP_STDERR the result keeps no moments, and its stderr and moment getters fail */
@@ -1071,6 +1222,7 @@ out:
 		pc_hip_spot_destroy(spot[kind]);
 	pc_hip_beam_destroy(beam);
 	pc_hip_hist_destroy(hist);
+	pc_hip_joint_destroy(joint);
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

@@ -206,6 +206,7 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	pc_spot_result_free(efficiencies->spot);
 	pc_beam_result_free(efficiencies->beam);
 	pc_hist_result_free(efficiencies->hist);
+	pc_joint_result_free(efficiencies->joint);
 	free(efficiencies->sumw_fixed);
 	free(efficiencies->sumw2_fixed);
 	free(efficiencies->stderrs);
@@ -413,6 +414,68 @@ int pc_transmission_efficiencies_get_hist(void *efficiencies_, int kind, int32_t
 	if (bins != NULL) *bins = b;
 	if (outside != NULL) *outside = u;
 	if (n_entries != NULL) *n_entries = hr->n_entries[kind];
+	return 1;
+}
+
+void pc_joint_result_free(struct pc_joint_result *joint)
+{
+	if (joint == NULL)
+		return;
+	free(joint->pairs);
+	free(joint->offsets);
+	free(joint->sel);
+	for (int k = 0; k < 3; k++) {
+		free(joint->cells[k]);
+		free(joint->outside[k]);
+	}
+	free(joint);
+}
+
+int pc_transmission_efficiencies_get_joint(void *efficiencies_, int kind, int32_t dims[3], int32_t **offsets, pc_hip_joint_pair **pairs,
+	double **energies, uint64_t **cells, uint64_t **outside, int64_t *n_entries, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || dims == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_joint: efficiencies and dims cannot be NULL");
+		return 0;
+	}
+	const struct pc_joint_result *jr = efficiencies->joint;
+	if (jr == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_joint: the run was made without POLYCAP_JOINT");
+		return 0;
+	}
+	if (kind < 0 || kind > 2 || jr->cells[kind] == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_joint: kind must be 0 (exit photons), or 1 (extleak) / 2 (intleak) for a leak_calc run");
+		return 0;
+	}
+	const size_t np = (size_t)jr->n_pairs, ns = (size_t)jr->n_sel, tc = (size_t)jr->total_cells;
+	dims[0] = jr->n_pairs; dims[1] = jr->n_sel; dims[2] = jr->total_cells;
+	int32_t *o = NULL;
+	pc_hip_joint_pair *a = NULL;
+	double *e = NULL;
+	uint64_t *b = NULL, *u = NULL;
+	int ok = 1;
+	if (offsets != NULL) ok = (o = pc_dup(jr->offsets, sizeof(int32_t)*(np + 1))) != NULL;
+	if (pairs != NULL && ok) ok = (a = pc_dup(jr->pairs, sizeof(pc_hip_joint_pair)*np)) != NULL;
+	if (energies != NULL && ok) {
+		ok = (e = malloc(sizeof(double)*(ns ? ns : 1))) != NULL;
+		for (size_t k = 0; ok && k < ns; k++)
+			e[k] = efficiencies->energies[jr->sel[k]];
+	}
+	if (cells != NULL && ok) ok = (b = pc_dup(jr->cells[kind], sizeof(uint64_t)*ns*tc)) != NULL;
+	if (outside != NULL && ok) ok = (u = pc_dup(jr->outside[kind], sizeof(uint64_t)*np*ns)) != NULL;
+	if (!ok) {
+		free(o); free(a); free(e); free(b); free(u);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_joint: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	if (offsets != NULL) *offsets = o;
+	if (pairs != NULL) *pairs = a;
+	if (energies != NULL) *energies = e;
+	if (cells != NULL) *cells = b;
+	if (outside != NULL) *outside = u;
+	if (n_entries != NULL) *n_entries = jr->n_entries[kind];
 	return 1;
 }
 

@@ -609,11 +609,13 @@ class BeamMoments(_Tally):
 
 
 HIST_QUANTITIES = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z")
+JOINT_QUANTITIES = HIST_QUANTITIES + ("start_x", "start_y")      # the axes of a joint histogram: the start coordinates as well
 
 
-def hist_axes(axes):
+def hist_axes(axes, names=HIST_QUANTITIES):
     """A ctypes array of pc_hip_hist_axis from a list of dicts (keys as in POLYCAP_HIST: axis, d, centre=(cx, cy), range=(lo, hi),
-    bins) or tuples (axis, (lo, hi), bins[, d[, (cx, cy)]]); axis is a name of HIST_QUANTITIES or its index."""
+    bins) or tuples (axis, (lo, hi), bins[, d[, (cx, cy)]]); axis is a name of `names` (HIST_QUANTITIES, or JOINT_QUANTITIES for the
+    axes of a joint histogram) or its index."""
     arr = (_cabi.HistAxisS * max(len(axes), 1))()
     for k, a in enumerate(axes):
         if not isinstance(a, dict):
@@ -622,7 +624,7 @@ def hist_axes(axes):
         if unknown:
             raise ValueError("histogram axis %d: unknown keys %s" % (k, sorted(unknown)))
         q = a["axis"]
-        q = HIST_QUANTITIES.index(q) if isinstance(q, str) else int(q)
+        q = names.index(q) if isinstance(q, str) else int(q)
         cx, cy = a.get("centre", (0., 0.))
         lo, hi = a["range"]
         arr[k] = _cabi.HistAxisS(q, float(a.get("d", 0.)), float(cx), float(cy), float(lo), float(hi), int(a["bins"]))
@@ -696,6 +698,108 @@ class Histograms(_Tally):
         """the q-quantile of the inside weight of axis `axis` at the selected energy number `energy`, read now (hist_quantile)"""
         b, (lo, hi), out = self._one(axis, energy, kind)
         return hist_quantile(b, lo, hi, q, out)
+
+
+def _axis_dict(a):
+    return dict(axis=JOINT_QUANTITIES[a.quantity], d=a.d, centre=(a.cx, a.cy), range=(a.lo, a.hi), bins=a.n_bins)
+
+
+def joint_pairs(pairs):
+    """A ctypes array of pc_hip_joint_pair from a list of (u, v), each an axis as hist_axes takes it, by a name of JOINT_QUANTITIES"""
+    arr = (_cabi.JointPairS * max(len(pairs), 1))()
+    for k, uv in enumerate(pairs):
+        if len(uv) != 2:
+            raise ValueError("joint pair %d: a pair is two axes (u, v)" % k)
+        a = hist_axes(list(uv), JOINT_QUANTITIES)
+        arr[k] = _cabi.JointPairS(a[0], a[1])
+    return arr
+
+
+def joint_marginal(cells, which):
+    """The exact uint64 sums of the cells [nv, nu] of one (kind, pair, energy) over v (which "u": [nu], the histogram of u of what
+    both ranges hold) or over u (which "v": [nv]) (pc_hip_joint_marginal, host only)."""
+    c = np.ascontiguousarray(cells, dtype=np.uint64)
+    if c.ndim != 2 or which not in ("u", "v"):
+        raise ValueError("joint_marginal: cells [nv, nu] and which \"u\" or \"v\" are needed")
+    nv, nu = c.shape
+    out = np.zeros(nv if which == "v" else nu, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    st = _cabi.lib().pc_hip_joint_marginal(nu, nv, c.ctypes.data_as(u64p), 1 if which == "v" else 0, out.ctypes.data_as(u64p))
+    if st != _cabi.PC_HIP_OK:
+        raise HipError("pc_hip_joint_marginal", st)
+    return out
+
+
+def joint_parse(value, n_energies):
+    """A value of POLYCAP_JOINT into (pairs, energies): pairs a list of (u, v) axis dicts, energies a list of indices or None for all
+    (pc_hip_joint_parse, host only).  ValueError with the reason, which names the item, when it is refused."""
+    pairs = (_cabi.JointPairS * 8)()
+    sel = (C.c_int32 * max(int(n_energies), 1))()
+    n_pairs, n_sel = C.c_int32(0), C.c_int32(0)
+    why = C.create_string_buffer(512)
+    st = _cabi.lib().pc_hip_joint_parse(value.encode(), int(n_energies), pairs, C.byref(n_pairs), sel, C.byref(n_sel), why, len(why))
+    if st != _cabi.PC_HIP_OK:
+        raise ValueError("POLYCAP_JOINT=%s: %s" % (value, why.value.decode()))
+    return ([(_axis_dict(p.u), _axis_dict(p.v)) for p in pairs[:n_pairs.value]],
+            None if n_sel.value == 0 else [int(e) for e in sel[:n_sel.value]])
+
+
+class JointHistograms(_Tally):
+    """Joint histograms of a TraceContext or a TraceGroup (pc_hip_joint_*): weighted 2-D histograms of two per-entry quantities of
+    the last run, one per pair of axes (u, v) and selected energy (energies: indices, None = all), all filled in one pass.  Exact
+    uint64 sums of round_half_even(w * 2^32), kept per kind (exit, extleak, intleak); the contract is written down in
+    include/polycap-hip.h.  pairs: see joint_pairs.  regime: 0 automatic, 1 workgroup-private LDS tiles, 2 energies across lanes."""
+
+    _stem = "joint"
+
+    def __init__(self, owner, pairs, energies=None, regime=0):
+        self._pairs = joint_pairs(pairs)
+        self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
+        spec = _cabi.JointSpecS(len(pairs), self._pairs, 0 if self.energies is None else self.energies.shape[0],
+                                None if self.energies is None else self.energies.ctypes.data_as(C.POINTER(C.c_int32)), int(regime))
+        self._create(owner, spec)
+        dims = (C.c_int32 * 3)()
+        off = (C.c_int32 * (len(pairs) + 1))()
+        reg = C.c_int(0)
+        self._L.pc_hip_joint_info(self._h, dims, off, C.byref(reg))
+        self.n_pairs, self.n_selected, self.total_cells = (int(d) for d in dims)
+        self.offsets = [int(v) for v in off]
+        self.regime = int(reg.value)
+        self.pairs = [(_axis_dict(p.u), _axis_dict(p.v)) for p in self._pairs[:self.n_pairs]]
+
+    def read(self):
+        """cells uint64 [3, energies, total_cells] (kinds exit, extleak, intleak; the pairs one after the other, each [iv][iu]),
+        outside uint64 [3, pairs, energies], n_entries [3]; pairs: per pair a view [3, energies, nv, nu] of the cells; edges: per
+        pair the (u, v) bin edges."""
+        cells = np.zeros((3, self.n_selected, self.total_cells), dtype=np.uint64)
+        out = np.zeros((3, self.n_pairs, self.n_selected), dtype=np.uint64)
+        n = (C.c_int64 * 3)()
+        self._call("read", cells.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+        o = self.offsets
+        return dict(cells=cells, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
+                    pairs=[cells[:, :, o[p]:o[p + 1]].reshape(3, self.n_selected, v["bins"], u["bins"]) for p, (u, v) in enumerate(self.pairs)],
+                    edges=[tuple(np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in uv) for uv in self.pairs])
+
+    def marginal(self, pair, which, kind="exit"):
+        """uint64 [energies, nu] (which "u") or [energies, nv] ("v"): the exact marginal sums of pair `pair`, read now (joint_marginal)"""
+        c = self.read()["pairs"][pair][_kind(kind)]
+        return np.stack([joint_marginal(c[e], which) for e in range(self.n_selected)])
+
+    def density(self, pair, efficiencies, kind="exit"):
+        """[energies, nv, nu] in efficiency units as the spot maps of the public call are, read now: cell * efficiencies[e] /
+        (inside + outside) with efficiencies [energies] those of the selected energies; 0 where an energy holds no weight."""
+        r = self.read()
+        k = _kind(kind)
+        c, out = r["pairs"][pair][k], r["outside"][k, pair]
+        eff = np.asarray(efficiencies, dtype=np.float64).ravel()
+        if eff.shape[0] != self.n_selected:
+            raise ValueError("density: one efficiency per selected energy is needed")
+        dens = np.zeros(c.shape, dtype=np.float64)
+        for e in range(self.n_selected):
+            total = int(c[e].sum(dtype=np.uint64)) + int(out[e])
+            if total:
+                dens[e] = eff[e] * c[e].astype(np.float64) / float(total)
+        return dens
 
 
 def scan_points(x=(0.,), y=(0.,), d_source=None):

@@ -118,6 +118,12 @@ cdef extern from "polycap.h" nogil:
     int pc_transmission_efficiencies_get_hist(void *efficiencies, int kind, int32_t *dims, int32_t **offsets, pc_hip_hist_axis **axes,
         double **energies, uint64_t **bins, uint64_t **outside, int64_t *n_entries, void *error)
 
+    ctypedef struct pc_hip_joint_pair:
+        pc_hip_hist_axis u
+        pc_hip_hist_axis v
+    int pc_transmission_efficiencies_get_joint(void *efficiencies, int kind, int32_t *dims, int32_t **offsets, pc_hip_joint_pair **pairs,
+        double **energies, uint64_t **cells, uint64_t **outside, int64_t *n_entries, void *error)
+
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
         double *pc_start_coords[2]
@@ -726,6 +732,43 @@ cdef class TransmissionEfficiencies:
         polycap_free(b)
         polycap_free(u)
         return dict(bins=B.reshape(ns, tb), outside=U.reshape(na, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), axes=axes)
+
+    def joint(self, kind="exit"):
+        """Extension of this build: the joint histograms of a run made with POLYCAP_JOINT set (pc_transmission_efficiencies_get_joint):
+        dict of the exact sums cells uint64 [energies, total_cells] (the pairs one after the other, each [iv][iu]) and outside uint64
+        [pairs, energies], n_entries, offsets [pairs + 1], energies (keV) and pairs, a list of (u, v) axis dicts (axis, d, centre,
+        range, bins).  kind: "exit", or "extleak" / "intleak" after a leak_calc run."""
+        cdef polycap_error *error = NULL
+        cdef int32_t dims[3]
+        cdef int32_t *o = NULL
+        cdef pc_hip_joint_pair *pr = NULL
+        cdef double *e = NULL
+        cdef uint64_t *b = NULL
+        cdef uint64_t *u = NULL
+        cdef int64_t ni = 0
+        cdef size_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_joint(<void *>self._eff, k, dims, &o, &pr, &e, &b, &u, &ni, <void *>&error)
+        _raise_if(error)
+        n_pairs, ns, tc = dims[0], dims[1], dims[2]
+        names = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z", "start_x", "start_y")
+        pairs = [(dict(axis=names[pr[i].u.quantity], d=pr[i].u.d, centre=(pr[i].u.cx, pr[i].u.cy), range=(pr[i].u.lo, pr[i].u.hi), bins=pr[i].u.n_bins),
+                  dict(axis=names[pr[i].v.quantity], d=pr[i].v.d, centre=(pr[i].v.cx, pr[i].v.cy), range=(pr[i].v.lo, pr[i].v.hi), bins=pr[i].v.n_bins))
+                 for i in range(n_pairs)]
+        B = np.empty(ns * tc, dtype=np.uint64)
+        U = np.empty(n_pairs * ns, dtype=np.uint64)
+        O = np.empty(n_pairs + 1, dtype=np.int32)
+        for i in range(ns * tc):
+            B[i] = b[i]
+        for i in range(n_pairs * ns):
+            U[i] = u[i]
+        for i in range(n_pairs + 1):
+            O[i] = o[i]
+        polycap_free(o)
+        polycap_free(pr)
+        polycap_free(b)
+        polycap_free(u)
+        return dict(cells=B.reshape(ns, tc), outside=U.reshape(n_pairs, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), pairs=pairs)
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
