@@ -481,6 +481,66 @@ POLYCAP_EXTERN int pc_hip_joint_marginal(int32_t nu, int32_t nv, const uint64_t 
  * why [why_len] otherwise. */
 POLYCAP_EXTERN int pc_hip_joint_parse(const char *value, size_t n_energies, pc_hip_joint_pair *pairs, int32_t *n_pairs,
 	int32_t *energies, int32_t *n_selected, char *why, size_t why_len);
+/* ---- selections: cuts on per-entry quantities, evaluated once per entry on the device (pc_select.h), through which any of the four
+ * tallies above can be filled: the beam moments of the core without the halo tails, a spot map of the photons of few reflections, the
+ * flux through a pinhole in the focal plane, the phase space a downstream aperture accepts.
+ *
+ * The contract:
+ *   cut        a pc_hip_hist_axis and a flag negate (0 or 1).  The quantity may be any histogram quantity or START_X / START_Y of the
+ *              joint histograms; n_bins must be 1; the other fields are validated as a histogram axis is.  The entry's value v is the
+ *              histogram contract's, and the entry is inside exactly when it falls into bin 0 of that one-bin axis.  So NaN,
+ *              !(dz > 0) for a quantity that uses dz, a quantity the kind does not have (D_TRAVEL, R_START, START_X, START_Y on a leak
+ *              kind) and a value off [lo, hi) are all not inside.  pass_k = inside XOR negate
+ *   selection  1 .. 8 cuts; an entry passes when every cut passes
+ *   apply      evaluates the cuts on the entries of one kind of the last run (those pc_hip_hist_add reads; the records of a relay into
+ *              the context are kind 0) and leaves one mask byte per entry on every member's device, with the exact totals n_pass,
+ *              n_seen and, per energy, passed_w = the sum of W over the passing entries and rejected_w = that over the others, W =
+ *              round_half_even(w[e] * 2^32) as uint64 (the spot maps' q(w)): passed_w + rejected_w is the sum over all entries,
+ *              exactly.  passed_w / (passed_w + rejected_w) is the transmission of the selection, a pinhole's for a cut on R_AT
+ *   gated add  pc_hip_{spot,beam,hist,joint}_add_selected is the plain add for which an entry whose mask byte is 0 does not exist
+ *              (unlike the plain add it waits for the apply on the context's stream, to learn n_pass, before it enqueues):
+ *              it adds to no cell, no sum and no outside counter, n_entries grows by n_pass, and the cap of 2^32 - 1 entries counts
+ *              n_pass.  For histograms and joint histograms sum(bins) + outside == passed_w[e] per (kind, axis or pair, energy),
+ *              exactly.  Gated and plain adds may be mixed into one tally
+ *   refusals   PC_HIP_ERR_INVALID before anything is launched, every object unchanged: the selection and the tally have different
+ *              owners (another context, another group, a context against a group); the selection was not applied for that kind; the
+ *              mask is stale -- the entries of the kind were replaced since (a source run, a leak run, a relay into the context, an
+ *              explicit launch; a scan replaces nothing)
+ *   limits     a kind of more than 2^32 - 1 entries cannot be applied (the uint64 sums could wrap)
+ * Masks and totals are integers and depend on the set of entries only: not on the layout of the exit photons (records, planes in slot
+ * order, compact planes), "run_parts", the kernel that traced the run, how the slots were split into runs, or the device count. */
+typedef struct {
+	pc_hip_hist_axis axis;        /* n_bins = 1 */
+	int32_t negate;               /* 0: pass inside; 1: pass outside */
+} pc_hip_select_cut;
+typedef struct {
+	int32_t n_cuts;               /* 1 .. 8 */
+	const pc_hip_select_cut *cuts;
+} pc_hip_select_spec;
+typedef struct pc_hip_select pc_hip_select;
+/* PC_HIP_ERR_INVALID with a message that names the cut and the field unless the spec is valid (no device is touched) */
+POLYCAP_EXTERN int pc_hip_select_validate(const pc_hip_select_spec *spec);
+/* A selection on the context's device (the context must outlive it); the group variant keeps one mask per member */
+POLYCAP_EXTERN int pc_hip_select_create(pc_hip_ctx *ctx, const pc_hip_select_spec *spec, pc_hip_select **select);
+POLYCAP_EXTERN int pc_hip_group_select_create(pc_hip_group *group, const pc_hip_select_spec *spec, pc_hip_select **select);
+POLYCAP_EXTERN void pc_hip_select_destroy(pc_hip_select *select);
+/* Evaluates the cuts on the entries of kind 0, 1 or 2 of the last run: enqueued on the context's stream behind the run, as
+ * pc_hip_hist_add is (leak kinds wait for the run first).  A kind applied before is applied anew. */
+POLYCAP_EXTERN int pc_hip_select_apply(pc_hip_select *select, int kind);
+/* n_pass [3], n_seen [3], passed_w [3][n_energies], rejected_w [3][n_energies] (any may be NULL; all energies of the problem); zeros
+ * for a kind that was not applied; waits for the applies */
+POLYCAP_EXTERN int pc_hip_select_read(pc_hip_select *select, int64_t *n_pass, int64_t *n_seen, uint64_t *passed_w, uint64_t *rejected_w);
+/* *n_cuts, *n_energies (either may be NULL) and cuts [n_cuts] (optional) */
+POLYCAP_EXTERN int pc_hip_select_info(const pc_hip_select *select, int32_t *n_cuts, int32_t *n_energies, pc_hip_select_cut *cuts);
+/* The adds of the four tallies through a selection applied for that kind (the contract above) */
+POLYCAP_EXTERN int pc_hip_spot_add_selected(pc_hip_spot *spot, int kind, pc_hip_select *select);
+POLYCAP_EXTERN int pc_hip_beam_add_selected(pc_hip_beam *beam, int kind, pc_hip_select *select);
+POLYCAP_EXTERN int pc_hip_hist_add_selected(pc_hip_hist *hist, int kind, pc_hip_select *select);
+POLYCAP_EXTERN int pc_hip_joint_add_selected(pc_hip_joint *joint, int kind, pc_hip_select *select);
+/* host only: a list of cuts in the axis grammar of POLYCAP_HIST without bins, a cut ending in ",not" being negated, e.g.
+ * "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not", into cuts [8] and *n_cuts, checked with pc_hip_select_validate.
+ * PC_HIP_ERR_INVALID with the reason (it names the item) in why [why_len] otherwise. */
+POLYCAP_EXTERN int pc_hip_select_parse(const char *value, pc_hip_select_cut *cuts, int32_t *n_cuts, char *why, size_t why_len);
 /* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
  * a focusing optic) in one launch, with exact totals per point.
  *
@@ -667,6 +727,17 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_hist(void *efficiencies, int
  * *error (a polycap_error**) set. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_joint(void *efficiencies, int kind, int32_t dims[3], int32_t **offsets,
 	pc_hip_joint_pair **pairs, double **energies, uint64_t **cells, uint64_t **outside, int64_t *n_entries, void *error);
+
+/* The selection of a result made with POLYCAP_SELECT set (every path of the call that POLYCAP_JOINT serves), e.g.
+ * POLYCAP_SELECT="axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not"
+ * (cuts separated by ';' in the axis grammar of POLYCAP_HIST without bins, a cut with the word "not" being negated; the grammar of
+ * pc_hip_select_parse).  When set, every tally of the call (POLYCAP_SPOT, _BEAM, _HIST, _JOINT) is filled through the selection for
+ * every kind it tallies.  Returns 1 and (free each array with polycap_free): *n_cuts, *cuts [n_cuts][7] rows of quantity, d, cx, cy,
+ * lo, hi, negate; *n_energies; n_pass [3] and n_seen [3] (exit photons, extleak, intleak; zeros for the leak kinds of a plain run);
+ * the exact sums *passed_w [3][n_energies] and *rejected_w [3][n_energies] of pc_hip_select_read, so that the results of several
+ * seeds pool exactly.  A result made without POLYCAP_SELECT fails with POLYCAP_ERROR_INVALID_ARGUMENT. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies,
+	int64_t n_pass[3], int64_t n_seen[3], uint64_t **passed_w, uint64_t **rejected_w, void *error);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,16 @@ class JointSpecS(C.Structure):
                 ("energies", C.POINTER(C.c_int32)), ("regime", C.c_int32)]
 
 
+class SelectCutS(C.Structure):
+    """struct pc_hip_select_cut"""
+    _fields_ = [("axis", HistAxisS), ("negate", C.c_int32)]
+
+
+class SelectSpecS(C.Structure):
+    """struct pc_hip_select_spec"""
+    _fields_ = [("n_cuts", C.c_int32), ("cuts", C.POINTER(SelectCutS))]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -290,6 +300,26 @@ def lib():
     L.pc_hip_joint_marginal.restype = C.c_int
     L.pc_hip_joint_parse.argtypes = [C.c_char_p, C.c_size_t, P(JointPairS), P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_char_p, C.c_size_t]
     L.pc_hip_joint_parse.restype = C.c_int
+    L.pc_hip_select_validate.argtypes = [P(SelectSpecS)]
+    L.pc_hip_select_validate.restype = C.c_int
+    L.pc_hip_select_create.argtypes = [C.c_void_p, P(SelectSpecS), P(C.c_void_p)]
+    L.pc_hip_select_create.restype = C.c_int
+    L.pc_hip_group_select_create.argtypes = [C.c_void_p, P(SelectSpecS), P(C.c_void_p)]
+    L.pc_hip_group_select_create.restype = C.c_int
+    L.pc_hip_select_destroy.argtypes = [C.c_void_p]
+    L.pc_hip_select_destroy.restype = None
+    L.pc_hip_select_apply.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_select_apply.restype = C.c_int
+    L.pc_hip_select_read.argtypes = [C.c_void_p, c_int64_p, c_int64_p, P(C.c_uint64), P(C.c_uint64)]
+    L.pc_hip_select_read.restype = C.c_int
+    L.pc_hip_select_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(SelectCutS)]
+    L.pc_hip_select_info.restype = C.c_int
+    for stem in ("spot", "beam", "hist", "joint"):
+        fn = getattr(L, "pc_hip_%s_add_selected" % stem)
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        fn.restype = C.c_int
+    L.pc_hip_select_parse.argtypes = [C.c_char_p, P(SelectCutS), P(C.c_int32), C.c_char_p, C.c_size_t]
+    L.pc_hip_select_parse.restype = C.c_int
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
     u64p = P(C.c_uint64)

@@ -135,6 +135,8 @@ def _lib():
                                                             P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_joint": (C.c_int, [vp, C.c_int, P(C.c_int32), P(P(C.c_int32)), P(P(_cabi.JointPairS)), P(_dp),
                                                              P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
+        "pc_transmission_efficiencies_get_select": (C.c_int, [vp, P(C.c_int32), P(_dp), P(C.c_size_t), P(C.c_int64), P(C.c_int64),
+                                                              P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -495,6 +497,24 @@ class TransmissionEfficiencies(_LeakData):
         L.polycap_free(C.cast(a, C.c_void_p))
         return dict(bins=_take(b, ns * tb, np.uint64).reshape(ns, tb), outside=_take(u, na * ns, np.uint64).reshape(na, ns),
                     n_entries=int(ni.value), offsets=_take(o, na + 1, np.int32), energies=_take(e, ns), axes=axes)
+
+    def select(self):
+        """The selection of a run made with POLYCAP_SELECT set (extension, pc_transmission_efficiencies_get_select): dict of cuts (a
+        list of dicts axis, d, centre, range, not), n_pass [3] and n_seen [3] (exit, extleak, intleak; zeros for the leak kinds of a
+        plain run) and the exact sums passed_w and rejected_w uint64 [3, energies]."""
+        from .hip import JOINT_QUANTITIES
+        L = _lib()
+        nc, ne = C.c_int32(0), C.c_size_t(0)
+        c, p, r = _dp(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        n_pass, n_seen = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_select(self._h, C.byref(nc), C.byref(c), C.byref(ne), n_pass, n_seen, C.byref(p), C.byref(r), C.byref(err))
+        _check(err)
+        rows = _take(c, 7 * nc.value).reshape(nc.value, 7)
+        cuts = [{"axis": JOINT_QUANTITIES[int(q[0])], "d": float(q[1]), "centre": (float(q[2]), float(q[3])), "range": (float(q[4]), float(q[5])),
+                 "not": bool(q[6])} for q in rows]
+        return dict(cuts=cuts, n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
+                    passed_w=_take(p, 3 * ne.value, np.uint64).reshape(3, ne.value), rejected_w=_take(r, 3 * ne.value, np.uint64).reshape(3, ne.value))
 
     def joint(self, kind="exit"):
         """Joint histograms of a run made with POLYCAP_JOINT set (extension, pc_transmission_efficiencies_get_joint): dict of the

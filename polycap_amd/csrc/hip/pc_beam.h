@@ -189,6 +189,7 @@ static __device__ __forceinline__ void pc_beam_mac(unsigned long long &lo, unsig
  * ones with one 128-bit atomic per sum: one set per workgroup and energy, not per entry. */
 #define PC_BEAM_BLOCK 256
 #define PC_BEAM_SLOTS 16
+template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
 __global__ void __launch_bounds__(PC_BEAM_BLOCK) pc_beam_kernel(pc_spot_src s, double ze, int ne, unsigned long long *sums)
 {
 	__shared__ unsigned long long red[64*PC_BEAM_SLOTS*2];
@@ -202,6 +203,7 @@ __global__ void __launch_bounds__(PC_BEAM_BLOCK) pc_beam_kernel(pc_spot_src s, d
 	for (int k = 0; k < PC_BEAM_SLOTS; k++) acc[k][0] = acc[k][1] = 0ull;
 	const int e = e0 + l.sub;
 	for (long long i = (l.sub < en) ? l.first : s.n; i < s.n; i += l.stride) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		const unsigned long long w = pc_spot_q(s.w[i*s.ws + e]);
 		if (!w) continue;
 		const pc_entry t = pc_entry_load(s, i);
@@ -268,7 +270,8 @@ static int pc_beam_launch(pc_hip_beam *b, pc_tally_member &m, const pc_spot_src 
 	const long long chunks = (b->ne + 63) / 64;
 	const long long bx = pc_tally_grid_wide(c->n_cu, chunks, b->ne, s.n, PC_BEAM_BLOCK).bx;
 	unsigned long long *sums = m.d_cells + (size_t)kind*b->ne*PC_BEAM_SLOTS*2;
-	hipLaunchKernelGGL(pc_beam_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_BEAM_BLOCK), 0, c->stream, s, b->ze, b->ne, sums);
+	auto kern = s.mask ? pc_beam_kernel<true> : pc_beam_kernel<false>;
+	hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_BEAM_BLOCK), 0, c->stream, s, b->ze, b->ne, sums);
 	return PC_HIP_OK;
 }
 

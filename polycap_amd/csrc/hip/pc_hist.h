@@ -15,6 +15,8 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <cmath>
+#include <string>
 
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -133,6 +135,28 @@ static inline double pc_hist_fwhm(int32_t n_bins, double lo, double hi, const ui
 	return r - l;
 }
 
+/* One axis of a spec (Axis: pc_hip_hist_axis of include/polycap-hip.h): false and the reason in *why (it names the field) when it is
+ * refused.  n_quantities = PC_HIST_N_QUANTITIES for a histogram, PC_JOINT_N_QUANTITIES for a joint histogram or a cut (pc_select.h). */
+template <typename Axis>
+static bool pc_hist_axis_check(const Axis &x, int n_quantities, std::string *why)
+{
+	static const char *names[PC_JOINT_N_QUANTITIES] = { "X_AT", "Y_AT", "R_AT", "SLOPE_X", "SLOPE_Y", "TAN_THETA", "N_REFL", "D_TRAVEL", "R_START", "Z",
+	                                                    "START_X", "START_Y" };
+	*why = "";
+	if (x.quantity < 0 || x.quantity >= n_quantities)
+		*why = std::string("quantity must be one of PC_HIP_HIST_X_AT .. ") + (n_quantities == PC_HIST_N_QUANTITIES ? "PC_HIP_HIST_Z" : "PC_HIP_JOINT_START_Y")
+		     + ", got " + std::to_string(x.quantity);
+	else if (!std::isfinite(x.d) || !(x.d >= 0.) || (x.quantity > PC_HIST_R_AT && x.d != 0.))
+		*why = std::string("d must be finite and >= 0, and 0 for ") + names[x.quantity] + " (X_AT, Y_AT and R_AT use it)";
+	else if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || (x.quantity != PC_HIST_R_AT && (x.cx != 0. || x.cy != 0.)))
+		*why = std::string("cx and cy must be finite, and 0 for ") + names[x.quantity] + " (R_AT uses them)";
+	else if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi))
+		*why = "lo and hi must be finite with lo < hi";
+	else if (x.n_bins < 1)
+		*why = "n_bins must be >= 1";
+	return why->empty();
+}
+
 #ifndef PC_HIST_HOST_ONLY
 
 /* Cells.  Every axis has n_bins + 1 cells per selected energy: its bins, then its outside counter; the cells of the axes follow
@@ -169,6 +193,7 @@ static __device__ __forceinline__ void pc_hist_load(const pc_spot_src &s, const 
  * the entries. */
 #define PC_HIST_TILE 8192
 #define PC_HIST_LDS_BLOCK 512
+template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
 __global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells)
 {
 	__shared__ unsigned long long tile[PC_HIST_TILE];
@@ -179,6 +204,7 @@ __global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_
 	for (int k = threadIdx.x; k < PC_HIST_TILE; k += blockDim.x) tile[k] = 0ull;
 	__syncthreads();
 	for (long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x; i < s.n; i += (long long)gridDim.x*blockDim.x) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		pc_hist_entry e;
 		pc_hist_load(s, g, i, e);
 		for (int a = 0; a < g.na; a++) {
@@ -205,6 +231,7 @@ __global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_
  * outside counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters). */
 #define PC_HIST_ECHUNK 512
 #define PC_HIST_WIDE_BLOCK 256
+template <bool M>
 __global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells)
 {
 	__shared__ unsigned long long out[PC_HIST_MAX_AXES*PC_HIST_ECHUNK];
@@ -214,6 +241,7 @@ __global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spo
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		pc_hist_entry e;
 		pc_hist_load(s, g, i, e);
 		int bin[PC_HIST_MAX_AXES];
@@ -303,34 +331,15 @@ static int pc_hist_launch(pc_hip_hist *h, pc_tally_member &m, const pc_spot_src 
 	if (h->regime == 1) {
 		const long long tiles = ((long long)h->per_kind + PC_HIST_TILE - 1)/PC_HIST_TILE;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_HIST_LDS_BLOCK).bx;
-		hipLaunchKernelGGL(pc_hist_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_HIST_LDS_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = s.mask ? pc_hist_lds_kernel<true> : pc_hist_lds_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_HIST_LDS_BLOCK), 0, c->stream, s, g, cells);
 	} else {
 		const long long chunks = (g.ns + PC_HIST_ECHUNK - 1)/PC_HIST_ECHUNK;
 		const long long bx = pc_tally_grid_wide(c->n_cu, chunks, g.ns, s.n, PC_HIST_WIDE_BLOCK).bx;
-		hipLaunchKernelGGL(pc_hist_wide_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_HIST_WIDE_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = s.mask ? pc_hist_wide_kernel<true> : pc_hist_wide_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_HIST_WIDE_BLOCK), 0, c->stream, s, g, cells);
 	}
 	return PC_HIP_OK;
-}
-
-/* One axis of a spec: false and the reason in *why (it names the field) when it is refused.  n_quantities = PC_HIST_N_QUANTITIES for
- * a histogram, PC_JOINT_N_QUANTITIES for a joint histogram. */
-static bool pc_hist_axis_check(const pc_hip_hist_axis &x, int n_quantities, std::string *why)
-{
-	static const char *names[PC_JOINT_N_QUANTITIES] = { "X_AT", "Y_AT", "R_AT", "SLOPE_X", "SLOPE_Y", "TAN_THETA", "N_REFL", "D_TRAVEL", "R_START", "Z",
-	                                                    "START_X", "START_Y" };
-	*why = "";
-	if (x.quantity < 0 || x.quantity >= n_quantities)
-		*why = std::string("quantity must be one of PC_HIP_HIST_X_AT .. ") + (n_quantities == PC_HIST_N_QUANTITIES ? "PC_HIP_HIST_Z" : "PC_HIP_JOINT_START_Y")
-		     + ", got " + std::to_string(x.quantity);
-	else if (!std::isfinite(x.d) || !(x.d >= 0.) || (x.quantity > PC_HIST_R_AT && x.d != 0.))
-		*why = std::string("d must be finite and >= 0, and 0 for ") + names[x.quantity] + " (X_AT, Y_AT and R_AT use it)";
-	else if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || (x.quantity != PC_HIST_R_AT && (x.cx != 0. || x.cy != 0.)))
-		*why = std::string("cx and cy must be finite, and 0 for ") + names[x.quantity] + " (R_AT uses them)";
-	else if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi))
-		*why = "lo and hi must be finite with lo < hi";
-	else if (x.n_bins < 1)
-		*why = "n_bins must be >= 1";
-	return why->empty();
 }
 
 extern "C" {

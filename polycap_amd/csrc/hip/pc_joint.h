@@ -53,6 +53,7 @@ struct pc_joint_geo {
  * (pc_tally_grid_tiles). */
 #define PC_JOINT_TILE 8192
 #define PC_JOINT_LDS_BLOCK 512
+template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
 __global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells)
 {
 	__shared__ unsigned long long tile[PC_JOINT_TILE];
@@ -70,6 +71,7 @@ __global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spo
 	for (int k = threadIdx.x; k < PC_JOINT_TILE; k += blockDim.x) tile[k] = 0ull;
 	__syncthreads();
 	for (long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x; i < s.n; i += (long long)gridDim.x*blockDim.x) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		pc_hist_entry e;
 		pc_hist_load(s, g, i, e);
 		for (int p = 0; p < g.np; p++) {
@@ -97,6 +99,7 @@ __global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spo
  * counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters; 32 KiB). */
 #define PC_JOINT_ECHUNK 512
 #define PC_JOINT_WIDE_BLOCK 256
+template <bool M>
 __global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells)
 {
 	__shared__ unsigned long long out[PC_JOINT_MAX_PAIRS*PC_JOINT_ECHUNK];
@@ -106,6 +109,7 @@ __global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_s
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		pc_hist_entry e;
 		pc_hist_load(s, g, i, e);
 		int cell[PC_JOINT_MAX_PAIRS];
@@ -200,11 +204,13 @@ static int pc_joint_launch(pc_hip_joint *h, pc_tally_member &m, const pc_spot_sr
 	if (h->regime == 1) {
 		const long long tiles = ((long long)h->per_kind + PC_JOINT_TILE - 1)/PC_JOINT_TILE;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_JOINT_LDS_BLOCK).bx;
-		hipLaunchKernelGGL(pc_joint_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_JOINT_LDS_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = s.mask ? pc_joint_lds_kernel<true> : pc_joint_lds_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_JOINT_LDS_BLOCK), 0, c->stream, s, g, cells);
 	} else {
 		const long long chunks = (g.ns + PC_JOINT_ECHUNK - 1)/PC_JOINT_ECHUNK;
 		const long long bx = pc_tally_grid_wide(c->n_cu, chunks, g.ns, s.n, PC_JOINT_WIDE_BLOCK).bx;
-		hipLaunchKernelGGL(pc_joint_wide_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_JOINT_WIDE_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = s.mask ? pc_joint_wide_kernel<true> : pc_joint_wide_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_JOINT_WIDE_BLOCK), 0, c->stream, s, g, cells);
 	}
 	return PC_HIP_OK;
 }

@@ -1151,6 +1151,8 @@ struct pc_hip_ctx {
 	pc_dev_buf<char> d_leak_order_tmp;
 	long long leak_n_ext = 0, leak_n_int = 0;
 	int leak_events_of_run = 0;            /* the event lists are those of the last source run (a leak run): pc_hip_spot_add may read them */
+	unsigned long long entries_epoch = 0;  /* grows with every call that replaces the entries a tally reads (source run, leak run, relay into the
+	                                        * context, explicit launch; not a scan): a selection's mask belongs to one value (pc_select.h) */
 	/* scans (pc_scan.h): buffers of their own, so that a scan leaves everything of the last run as it was */
 	pc_dev_buf<pc_totals> d_scan_totals;   /* work counter and scheduler statistics of the last scan launch */
 	pc_dev_buf<unsigned long long> d_scan_tot; /* per point: 6 counters, 2*ne weight sums, 2*ne squared-weight sums (pc_kargs::sumw of a scan) */
@@ -1610,6 +1612,7 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 	int status = pc_batch_layout(ctx, n, true, b);
 	if (status) return status;
 	ctx->last_call = PC_CALL_EXPLICIT;
+	ctx->entries_epoch++;
 	status = pc_batch_upload(ctx, b, start_coords, start_dir, start_elecv);
 	if (!status) status = pc_batch_trace(ctx, b, leak);
 	if (!status) status = pc_batch_download(ctx, b, start_elecv, rc, weights, exit_coords, exit_dir, exit_elecv, i_refl, d_travel, leak);
@@ -1692,6 +1695,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	}
 	ctx->last_run_plain = 1;
 	ctx->leak_events_of_run = 0;
+	ctx->entries_epoch++;
 	ctx->run_squares = ctx->opts.weight_squares;
 	ctx->last_call = PC_CALL_RUN;
 	pc_kargs a;
@@ -1776,6 +1780,7 @@ int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, 
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	ctx->img.reset();
+	ctx->entries_epoch++;
 	ctx->last_call = PC_CALL_RUN_LEAK;
 	if (keep_images) {
 		int st = ctx->img.keep_records(n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
@@ -2090,6 +2095,7 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_beam.h"
 #include "pc_hist.h"
 #include "pc_joint.h"
+#include "pc_select.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
 

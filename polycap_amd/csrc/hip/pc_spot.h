@@ -66,6 +66,7 @@ static __device__ __forceinline__ long long pc_spot_entry_bin(const pc_spot_src 
  * several passes over the entries (blockIdx.y). */
 #define PC_SPOT_TILE 8192
 #define PC_SPOT_LDS_BLOCK 512
+template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
 __global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
 {
 	__shared__ unsigned long long tile[PC_SPOT_TILE];
@@ -75,6 +76,7 @@ __global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_
 	for (int k = threadIdx.x; k < PC_SPOT_TILE; k += blockDim.x) tile[k] = 0ull;
 	__syncthreads();
 	for (long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x; i < s.n; i += (long long)gridDim.x*blockDim.x) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		for (int p = 0; p < g.np; p++) {
 			const long long b = pc_spot_entry_bin(s, g, i, p);
 			/* the entry's cells for energies 0 .. ns-1: base + k*step */
@@ -104,6 +106,7 @@ __global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_
  * adds to the same few counters). */
 #define PC_SPOT_ECHUNK 4096
 #define PC_SPOT_WIDE_BLOCK 256
+template <bool M>
 __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
 {
 	__shared__ unsigned long long out[PC_SPOT_ECHUNK];
@@ -114,6 +117,7 @@ __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spo
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
+		if (M && !s.mask[i]) continue;      /* gated add: the entry does not exist */
 		const long long b = pc_spot_entry_bin(s, g, i, p);
 		unsigned long long *cell = map + ((long long)p*nb + (b >= 0 ? b : 0))*g.ns + s0;
 		for (int k = l.sub; k < sn; k += l.gw) {
@@ -178,11 +182,13 @@ static int pc_spot_launch(pc_hip_spot *sp, pc_tally_member &m, const pc_spot_src
 	if (!sp->wide) {
 		const long long tiles = ((long long)sp->elems + PC_SPOT_TILE - 1)/PC_SPOT_TILE;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_SPOT_LDS_BLOCK).bx;
-		hipLaunchKernelGGL(pc_spot_lds_kernel, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_cells);
+		auto kern = s.mask ? pc_spot_lds_kernel<true> : pc_spot_lds_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_cells);
 	} else {
 		const long long chunks = (sp->ns + PC_SPOT_ECHUNK - 1)/PC_SPOT_ECHUNK;
 		const long long bx = pc_tally_grid_wide(c->n_cu, sp->np*chunks, sp->ns, s.n, PC_SPOT_WIDE_BLOCK).bx;
-		hipLaunchKernelGGL(pc_spot_wide_kernel, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_cells);
+		auto kern = s.mask ? pc_spot_wide_kernel<true> : pc_spot_wide_kernel<false>;
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_cells);
 	}
 	return PC_HIP_OK;
 }

@@ -110,6 +110,7 @@ struct pc_spot_src {
 	int has_dz;
 	const double *w;
 	long long ws;
+	const unsigned char *mask;      /* a selection's byte per entry (pc_select.h): an entry with 0 does not exist for the tally; NULL: all do */
 };
 
 struct pc_entry { double x, y, z, dx, dy, dz; };
@@ -248,35 +249,63 @@ static int pc_tally_upload(pc_tally &t, const std::vector<int> &sel, const std::
 	return PC_HIP_OK;
 }
 
-/* Adds the entries of `kind` of the last run: launch(k, src, kind) enqueues member k's non-empty source on its stream (its device
- * is current) and returns a status. */
-template <typename Launch>
-static int pc_tally_add(pc_tally &t, int kind, const char *who, Launch launch)
+/* Every member's source of the entries of `kind` (zeroed for a member of a group that traced nothing), and their count: nothing is
+ * launched unless the whole call can be */
+static int pc_tally_sources(const std::vector<pc_hip_ctx *> &ctxs, const pc_hip_group *g, int kind, const char *who, std::vector<pc_spot_src> &src,
+	long long *n_total)
 {
 	const std::string w(who);
 	if (kind < 0 || kind > 2) return pc_fail(PC_HIP_ERR_INVALID, w + ": kind must be 0 (exit photons), 1 (extleak) or 2 (intleak)");
-	const pc_hip_group *g = t.group;
 	if (g && kind == 0 && !g->keep_images)
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": the last run kept no exit photons (run it with keep_images)");
 	if (g && kind > 0 && !g->leak_run)
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": leak events need a leak_calc run of the group as the last run");
-	/* every member's source first: nothing is added unless the whole add can be */
-	std::vector<pc_spot_src> src(t.m.size());
+	src.resize(ctxs.size());
 	long long n = 0;
-	for (size_t k = 0; k < t.m.size(); k++) {
+	for (size_t k = 0; k < ctxs.size(); k++) {
 		if (g && g->count[k] == 0) { memset(&src[k], 0, sizeof(src[k])); continue; }
-		PC_HIP_CHECK(hipSetDevice(t.m[k].ctx->device));
-		const int st = pc_spot_source(t.m[k].ctx, kind, src[k], who);
+		PC_HIP_CHECK(hipSetDevice(ctxs[k]->device));
+		const int st = pc_spot_source(ctxs[k], kind, src[k], who);
 		if (st) return st;
 		n += src[k].n;
+	}
+	*n_total = n;
+	return PC_HIP_OK;
+}
+
+/* A selection as an add sees it (pc_select.h): refuses (PC_HIP_ERR_INVALID, nothing changed) a selection of another owner than the
+ * tally's, one not applied for `kind`, and a mask that is not of the entries in src; otherwise src[k].mask = member k's mask, passing[k]
+ * = how many of its entries pass. */
+struct pc_hip_select;
+static int pc_select_gate(pc_hip_select *sel, const std::vector<pc_hip_ctx *> &ctxs, const pc_hip_group *g, int kind, const char *who,
+	std::vector<pc_spot_src> &src, std::vector<long long> &passing);
+
+/* Adds the entries of `kind` of the last run, through the selection `sel` if there is one: launch(k, src, kind) enqueues member k's
+ * non-empty source on its stream (its device is current) and returns a status. */
+template <typename Launch>
+static int pc_tally_add(pc_tally &t, int kind, const char *who, Launch launch, pc_hip_select *sel = nullptr)
+{
+	const std::string w(who);
+	std::vector<pc_hip_ctx *> ctxs;
+	for (const pc_tally_member &m : t.m) ctxs.push_back(m.ctx);
+	std::vector<pc_spot_src> src;
+	long long n = 0;
+	int st = pc_tally_sources(ctxs, t.group, kind, who, src, &n);
+	if (st) return st;
+	std::vector<long long> passing;          /* per member, with a selection */
+	if (sel) {
+		st = pc_select_gate(sel, ctxs, t.group, kind, who, src, passing);
+		if (st) return st;
+		n = 0;
+		for (long long p : passing) n += p;
 	}
 	const long long held = t.shared ? t.n_entries[0] + t.n_entries[1] + t.n_entries[2] : t.n_entries[kind];
 	if (held + n > (long long)0xffffffffll)
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": the cells of a kind take at most 2^32 - 1 entries (their exact sums could wrap beyond)");
 	for (size_t k = 0; k < t.m.size(); k++) {
-		if (src[k].n == 0) continue;
+		if (src[k].n == 0 || (sel && passing[k] == 0)) continue;
 		PC_HIP_CHECK(hipSetDevice(t.m[k].ctx->device));
-		const int st = launch(k, src[k], kind);
+		st = launch(k, src[k], kind);
 		if (st) return st;
 		PC_HIP_CHECK(hipGetLastError());
 	}

@@ -550,6 +550,35 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		if (!jok) goto close;
 	}
 
+	if (efficiencies->select != NULL) {
+		/* extension: the cuts of POLYCAP_SELECT and the exact totals of what passed them (include/polycap-hip.h); rows of Passed,
+		 * Rejected and Entries: exit photons, extleak, intleak */
+		const struct pc_select_result *sr = efficiencies->select;
+		const size_t nc = (size_t)sr->n_cuts, ne = efficiencies->n_energies;
+		bool sok = pc_h5_group(file, "/Select", error);
+		double *table = malloc(sizeof(double) * 7 * nc);
+		sok = sok && table != NULL;
+		for (size_t k = 0; sok && k < nc; k++) {
+			const pc_hip_hist_axis *x = &sr->cuts[k].axis;
+			const double row[7] = { (double)x->quantity, x->d, x->cx, x->cy, x->lo, x->hi, (double)sr->cuts[k].negate };
+			memcpy(table + 7*k, row, sizeof row);
+		}
+		pc_hsize sd[2] = { (pc_hsize)nc, 7 };
+		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Cuts", *h5.native_double, table, "a.u., cm", "quantity,d,cx,cy,lo,hi,negate", error);
+		sd[0] = 3; sd[1] = (pc_hsize)ne;
+		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Passed", *h5.native_ullong, sr->passed_w, "2^-32", NULL, error);
+		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Rejected", *h5.native_ullong, sr->rejected_w, "2^-32", NULL, error);
+		uint64_t entries[6];
+		for (int k = 0; k < 3; k++) {
+			entries[2*k] = (uint64_t)sr->n_pass[k];
+			entries[2*k + 1] = (uint64_t)sr->n_seen[k];
+		}
+		sd[0] = 3; sd[1] = 2;
+		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Entries", *h5.native_ullong, entries, "a.u.", "n_pass,n_seen", error);
+		free(table);
+		if (!sok) goto close;
+	}
+
 	if (!pc_h5_group(file, "/Input", error)) goto close;
 	{
 		double *const shape_ext[2] = { prof->z, prof->ext }, *const shape_cap[2] = { prof->z, prof->cap };

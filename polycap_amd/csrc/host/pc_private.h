@@ -165,6 +165,14 @@ struct pc_joint_result {
 	int64_t n_entries[3];
 };
 
+/* extension: the cuts and the exact totals of a run made with POLYCAP_SELECT set (pc_transmission_efficiencies_get_select) */
+struct pc_select_result {
+	int32_t n_cuts;
+	pc_hip_select_cut cuts[8];
+	int64_t n_pass[3], n_seen[3];   /* exit photons, extleak, intleak (zeros where the run has none) */
+	uint64_t *passed_w, *rejected_w; /* [3][n_energies] */
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -176,6 +184,7 @@ struct _polycap_transmission_efficiencies {
 	struct pc_beam_result *beam;
 	struct pc_hist_result *hist;
 	struct pc_joint_result *joint;
+	struct pc_select_result *select;
 	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
 	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
 	int64_t n_started;
@@ -233,5 +242,6 @@ void pc_spot_result_free(struct pc_spot_result *spot);
 void pc_beam_result_free(struct pc_beam_result *beam);
 void pc_hist_result_free(struct pc_hist_result *hist);
 void pc_joint_result_free(struct pc_joint_result *joint);
+void pc_select_result_free(struct pc_select_result *select);
 
 #endif

@@ -700,6 +700,76 @@ int pc_hip_joint_parse(const char *value, size_t n_energies, pc_hip_joint_pair *
 	return bad == NULL ? PC_HIP_OK : PC_HIP_ERR_INVALID;
 }
 
+/* POLYCAP_SELECT, e.g. "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not": cuts through which every tally of the call is
+ * filled (include/polycap-hip.h, pc_hip_select_*; the grammar is pc_hip_select_parse's).  Parsed and validated before any device is used. */
+struct pc_select_request {
+	int set;
+	pc_hip_select_cut cuts[8];
+	int32_t n_cuts;
+	pc_hip_select_spec spec;
+};
+
+static int pc_select_request_parse(struct pc_select_request *r, polycap_error **error)
+{
+	memset(r, 0, sizeof(*r));
+	const char *env = getenv("POLYCAP_SELECT");
+	if (env == NULL)
+		return 0;
+	char why[320];
+	if (pc_hip_select_parse(env, r->cuts, &r->n_cuts, why, sizeof why) != PC_HIP_OK) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT=%s: %s", env, why);
+		return -1;
+	}
+	r->set = 1;
+	r->spec.n_cuts = r->n_cuts;
+	r->spec.cuts = r->cuts;
+	return 0;
+}
+
+/* the tallies of one call and the selection they are filled through (any may be NULL); tot: the selection's totals summed over the
+ * applies of the call, n_pass [3], n_seen [3], then passed_w [3][ne], rejected_w [3][ne] */
+struct pc_tallies {
+	pc_hip_spot *spot[3];          /* exit photons, extleak, intleak */
+	pc_hip_beam *beam;
+	pc_hip_hist *hist;
+	pc_hip_joint *joint;
+	pc_hip_select *select;
+	int64_t sel_n[6];
+	uint64_t *sel_w;               /* [2][3][ne] */
+};
+
+/* the entries of `kind` of the last run into every tally, through the selection if there is one (applied here, its totals added) */
+static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
+{
+	int st = PC_HIP_OK;
+	pc_hip_select *s = ta->select;
+	if (s != NULL) {
+		int64_t n_pass[3], n_seen[3];
+		uint64_t *w = malloc(sizeof(uint64_t)*6*ne);
+		st = (w != NULL) ? pc_hip_select_apply(s, kind) : PC_HIP_ERR_MEMORY;
+		if (st == PC_HIP_OK)
+			st = pc_hip_select_read(s, n_pass, n_seen, w, w + 3*ne);
+		if (st == PC_HIP_OK) {
+			ta->sel_n[kind] += n_pass[kind];
+			ta->sel_n[3 + kind] += n_seen[kind];
+			for (size_t e = 0; e < ne; e++) {
+				ta->sel_w[kind*ne + e] += w[kind*ne + e];
+				ta->sel_w[(3 + kind)*ne + e] += w[(3 + kind)*ne + e];
+			}
+		}
+		free(w);
+	}
+	if (st == PC_HIP_OK && ta->spot[kind] != NULL)
+		st = s != NULL ? pc_hip_spot_add_selected(ta->spot[kind], kind, s) : pc_hip_spot_add(ta->spot[kind], kind);
+	if (st == PC_HIP_OK && ta->beam != NULL)
+		st = s != NULL ? pc_hip_beam_add_selected(ta->beam, kind, s) : pc_hip_beam_add(ta->beam, kind);
+	if (st == PC_HIP_OK && ta->hist != NULL)
+		st = s != NULL ? pc_hip_hist_add_selected(ta->hist, kind, s) : pc_hip_hist_add(ta->hist, kind);
+	if (st == PC_HIP_OK && ta->joint != NULL)
+		st = s != NULL ? pc_hip_joint_add_selected(ta->joint, kind, s) : pc_hip_joint_add(ta->joint, kind);
+	return st;
+}
+
 /* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
 static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
 {
@@ -715,7 +785,7 @@ static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
  * (seed, slot): the same photons).  Counters and the exact fixed-point sums of the ranges are added on the host, and every range is
  * added to the map, to the beam sums, to the histograms and to the joint histograms (any may be NULL).  fixed [2*ne] receives the weights' sums; fixed2 (NULL unless
  * POLYCAP_STDERR) those of the squared weights. */
-static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam, pc_hip_hist *hist, pc_hip_joint *joint, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
+static int pc_spot_chunked(pc_hip_ctx *ctx, struct pc_tallies *ta, uint64_t seed, int64_t n_photons, int64_t chunk, uint32_t max_attempts,
 	size_t ne, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	uint64_t *part = malloc(2*ne*sizeof(uint64_t));
@@ -729,14 +799,8 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, pc_hip_spot *spot, pc_hip_beam *beam
 		const int64_t n = (n_photons - lo < chunk) ? n_photons - lo : chunk;
 		int64_t c[6];
 		st = pc_hip_transmission_run(ctx, seed, lo, n, max_attempts, 1);
-		if (st == PC_HIP_OK && spot != NULL)
-			st = pc_hip_spot_add(spot, 0);
-		if (st == PC_HIP_OK && beam != NULL)
-			st = pc_hip_beam_add(beam, 0);
-		if (st == PC_HIP_OK && hist != NULL)
-			st = pc_hip_hist_add(hist, 0);
-		if (st == PC_HIP_OK && joint != NULL)
-			st = pc_hip_joint_add(joint, 0);
+		if (st == PC_HIP_OK)
+			st = pc_tallies_add(ta, 0, ne);      /* through POLYCAP_SELECT if it is set */
 		if (st == PC_HIP_OK)
 			st = pc_hip_transmission_totals(ctx, NULL, c, part);
 		if (st != PC_HIP_OK)
@@ -932,6 +996,7 @@ struct pc_run_request {
 	struct pc_spot_request spot;
 	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
 	struct pc_joint_request joint; /* POLYCAP_JOINT: exact joint 2-D histograms per energy (pc_hip_joint_*) */
+	struct pc_select_request select; /* POLYCAP_SELECT: cuts through which every tally is filled (pc_hip_select_*) */
 	int devices[64], n_devices;
 	int keep_images;
 	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
@@ -973,7 +1038,9 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 		return -1;
 	if (pc_joint_request_parse(&r->joint, ne, error) != 0)
 		return -1;
-	if ((r->beam_on || r->hist.set || r->joint.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and (joint) histograms too */
+	if (pc_select_request_parse(&r->select, error) != 0)
+		return -1;
+	if ((r->beam_on || r->hist.set || r->joint.set || r->select.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and (joint) histograms too */
 		r->spot.share = 0.5;
 		const char *share = getenv("POLYCAP_SPOT_SHARE");
 		if (share != NULL && *share != '\0') {
@@ -1020,10 +1087,19 @@ struct pc_target {
  * enqueued.  *chunked = 1 when pc_spot_chunked traced the run: it also read the totals and moments, and added every range to spot[0],
  * *beam, *hist and *joint. */
 static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak_calc, uint64_t seed, int64_t n_photons, size_t ne,
-	pc_hip_spot *spot[3], pc_hip_beam **beam, pc_hip_hist **hist, pc_hip_joint **joint, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
+	struct pc_tallies *ta, int *chunked, double *sum_weights, int64_t counters[6], uint64_t *fixed, uint64_t *fixed2)
 {
 	int st = PC_HIP_OK;
 	int64_t chunk = 0;
+	pc_hip_spot **spot = ta->spot;
+	pc_hip_beam **beam = &ta->beam;
+	pc_hip_hist **hist = &ta->hist;
+	pc_hip_joint **joint = &ta->joint;
+	if (r->select.set) {
+		ta->sel_w = calloc(6*ne, sizeof(uint64_t));
+		st = ta->sel_w == NULL ? PC_HIP_ERR_MEMORY
+		   : t.group != NULL ? pc_hip_group_select_create(t.group, &r->select.spec, &ta->select) : pc_hip_select_create(t.ctx, &r->select.spec, &ta->select);
+	}
 	if (r->spot.set)
 		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++)
 			st = t.group != NULL ? pc_hip_group_spot_create(t.group, &r->spot.spec, &spot[kind]) : pc_hip_spot_create(t.ctx, &r->spot.spec, &spot[kind]);
@@ -1033,7 +1109,7 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		st = t.group != NULL ? pc_hip_group_hist_create(t.group, &r->hist.spec, hist) : pc_hip_hist_create(t.ctx, &r->hist.spec, hist);
 	if (r->joint.set && st == PC_HIP_OK)
 		st = t.group != NULL ? pc_hip_group_joint_create(t.group, &r->joint.spec, joint) : pc_hip_joint_create(t.ctx, &r->joint.spec, joint);
-	if (r->spot.set || r->beam_on || r->hist.set || r->joint.set) {
+	if (r->spot.set || r->beam_on || r->hist.set || r->joint.set || r->select.set) {
 		/* POLYCAP_IMAGES=0 with spot maps, beam moments or (joint) histograms is chunked on one device only: a group traces the whole run at once */
 		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
 			uint64_t total_b = 0;
@@ -1058,10 +1134,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		return st;
 	if (chunk > 0 && chunk < n_photons) {
 		*chunked = 1;
-		return pc_spot_chunked(t.ctx, spot[0], *beam, *hist, *joint, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
+		return pc_spot_chunked(t.ctx, ta, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
 	}
 	/* POLYCAP_SPOT, POLYCAP_BEAM, POLYCAP_HIST, POLYCAP_JOINT: the run keeps its exit data on the device even with POLYCAP_IMAGES=0 (then nothing is copied back) */
-	const int device_images = r->keep_images || r->spot.set || r->beam_on || r->hist.set || r->joint.set;
+	const int device_images = r->keep_images || r->spot.set || r->beam_on || r->hist.set || r->joint.set || r->select.set;
 	if (leak_calc)
 		return t.group != NULL ? pc_hip_group_run_leak(t.group, seed, n_photons, r->max_attempts, 1)
 		                       : pc_hip_transmission_run_leak(t.ctx, seed, 0, n_photons, r->max_attempts, 1);
@@ -1108,10 +1184,9 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	polycap_transmission_efficiencies *eff = NULL, *result = NULL;
 	double *sum_weights = NULL;
 	uint64_t *sum_fixed = NULL, *sum_fixed2 = NULL;      /* the exact moments A and B; B and the result's copy only with POLYCAP_STDERR */
-	pc_hip_spot *spot[3] = { NULL, NULL, NULL };         /* exit photons, extleak, intleak */
-	pc_hip_beam *beam = NULL;                            /* POLYCAP_BEAM: the exact beam sums of every kind */
-	pc_hip_hist *hist = NULL;                            /* POLYCAP_HIST: the exact histograms of every kind */
-	pc_hip_joint *joint = NULL;                          /* POLYCAP_JOINT: the exact joint histograms of every kind */
+	struct pc_tallies ta;                                /* POLYCAP_SPOT, _BEAM, _HIST, _JOINT and the POLYCAP_SELECT they are filled through */
+	memset(&ta, 0, sizeof(ta));
+	pc_hip_spot **spot = ta.spot;
 	int64_t counters[6] = { 0, 0, 0, 0, 0, 0 };
 	int status = PC_HIP_OK, chunked = 0, reduced_by = 0;      /* a failed HIP call: its error is set at `out` */
 	double t_stage[6];
@@ -1143,7 +1218,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	const uint64_t seed = req.have_seed ? req.seed : source->rng->seed + 0x9E3779B97F4A7C15ull * source->run_index;
 	source->run_index++;
 
-	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, spot, &beam, &hist, &joint, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
+	status = pc_trace(t, &req, leak_calc, seed, n_photons, ne, &ta, &chunked, sum_weights, counters, sum_fixed, sum_fixed2);
 	t_stage[2] = t_stage[3] = pc_now_ms();
 	if (status == PC_HIP_OK && req.keep_images)
 		status = pc_fetch_images(t, eff, n_photons, &t_stage[3]);
@@ -1166,15 +1241,11 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			t.group != NULL ? (reduced_by ? " (devices summed by RCCL all-reduce)" : " (devices summed on the host)") : "");
 	if (status == PC_HIP_OK && leak_calc)
 		status = pc_transeff_fetch_leaks(eff, t.ctx, t.group);      /* reference :925-1032 */
-	for (int kind = chunked ? 1 : 0; kind <= 2 && status == PC_HIP_OK; kind++)      /* a chunked run has added its exit map */
-		if (spot[kind] != NULL)
-			status = pc_hip_spot_add(spot[kind], kind);
-	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && beam != NULL; kind++)
-		status = pc_hip_beam_add(beam, kind);
-	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && hist != NULL; kind++)
-		status = pc_hip_hist_add(hist, kind);
-	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK && joint != NULL; kind++)
-		status = pc_hip_joint_add(joint, kind);
+	pc_hip_beam *beam = ta.beam;
+	pc_hip_hist *hist = ta.hist;
+	pc_hip_joint *joint = ta.joint;
+	for (int kind = chunked ? 1 : 0; kind <= (leak_calc ? 2 : 0) && status == PC_HIP_OK; kind++)      /* a chunked run has added its exit photons */
+		status = pc_tallies_add(&ta, kind, ne);
 	if (status != PC_HIP_OK)
 		goto out;
 
@@ -1197,6 +1268,21 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		status = pc_hist_store(eff, hist, &req.hist, leak_calc);
 	if (status == PC_HIP_OK && joint != NULL)
 		status = pc_joint_store(eff, joint, &req.joint, leak_calc);
+	if (status == PC_HIP_OK && ta.select != NULL) {
+		struct pc_select_result *sr = eff->select = calloc(1, sizeof(*sr));
+		if (sr == NULL)
+			status = PC_HIP_ERR_MEMORY;
+		else {
+			sr->n_cuts = req.select.n_cuts;
+			memcpy(sr->cuts, req.select.cuts, sizeof(sr->cuts));
+			memcpy(sr->n_pass, ta.sel_n, sizeof(sr->n_pass));
+			memcpy(sr->n_seen, ta.sel_n + 3, sizeof(sr->n_seen));
+			sr->passed_w = pc_beam_dup(ta.sel_w, sizeof(uint64_t)*3*ne);
+			sr->rejected_w = pc_beam_dup(ta.sel_w + 3*ne, sizeof(uint64_t)*3*ne);
+			if (sr->passed_w == NULL || sr->rejected_w == NULL)
+				status = PC_HIP_ERR_MEMORY;
+		}
+	}
 	if (status != PC_HIP_OK)
 		goto out;
 	if (req.stderr_on) {      /* without POLYCAP_STDERR the result keeps no moments, and its stderr and moment getters fail */
@@ -1220,9 +1306,11 @@ out:
 		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
 	for (int kind = 0; kind <= 2; kind++)
 		pc_hip_spot_destroy(spot[kind]);
-	pc_hip_beam_destroy(beam);
-	pc_hip_hist_destroy(hist);
-	pc_hip_joint_destroy(joint);
+	pc_hip_beam_destroy(ta.beam);
+	pc_hip_hist_destroy(ta.hist);
+	pc_hip_joint_destroy(ta.joint);
+	pc_hip_select_destroy(ta.select);
+	free(ta.sel_w);
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

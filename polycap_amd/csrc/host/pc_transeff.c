@@ -207,6 +207,7 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	pc_beam_result_free(efficiencies->beam);
 	pc_hist_result_free(efficiencies->hist);
 	pc_joint_result_free(efficiencies->joint);
+	pc_select_result_free(efficiencies->select);
 	free(efficiencies->sumw_fixed);
 	free(efficiencies->sumw2_fixed);
 	free(efficiencies->stderrs);
@@ -476,6 +477,60 @@ int pc_transmission_efficiencies_get_joint(void *efficiencies_, int kind, int32_
 	if (cells != NULL) *cells = b;
 	if (outside != NULL) *outside = u;
 	if (n_entries != NULL) *n_entries = jr->n_entries[kind];
+	return 1;
+}
+
+void pc_select_result_free(struct pc_select_result *select)
+{
+	if (select == NULL)
+		return;
+	free(select->passed_w);
+	free(select->rejected_w);
+	free(select);
+}
+
+int pc_transmission_efficiencies_get_select(void *efficiencies_, int32_t *n_cuts, double **cuts, size_t *n_energies, int64_t n_pass[3], int64_t n_seen[3],
+	uint64_t **passed_w, uint64_t **rejected_w, void *error_)
+{
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || n_cuts == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_select: efficiencies and n_cuts cannot be NULL");
+		return 0;
+	}
+	const struct pc_select_result *sr = efficiencies->select;
+	if (sr == NULL) {
+		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "pc_transmission_efficiencies_get_select: the run was made without POLYCAP_SELECT");
+		return 0;
+	}
+	const size_t ne = efficiencies->n_energies, nc = (size_t)sr->n_cuts;
+	double *c = NULL;
+	uint64_t *p = NULL, *r = NULL;
+	int ok = 1;
+	if (cuts != NULL) {
+		ok = (c = malloc(sizeof(double)*7*nc)) != NULL;
+		for (size_t k = 0; ok && k < nc; k++) {
+			const pc_hip_hist_axis *x = &sr->cuts[k].axis;
+			const double row[7] = { (double)x->quantity, x->d, x->cx, x->cy, x->lo, x->hi, (double)sr->cuts[k].negate };
+			memcpy(c + 7*k, row, sizeof row);
+		}
+	}
+	if (passed_w != NULL && ok) ok = (p = pc_dup(sr->passed_w, sizeof(uint64_t)*3*ne)) != NULL;
+	if (rejected_w != NULL && ok) ok = (r = pc_dup(sr->rejected_w, sizeof(uint64_t)*3*ne)) != NULL;
+	if (!ok) {
+		free(c); free(p); free(r);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "pc_transmission_efficiencies_get_select: could not allocate memory -> %s", strerror(errno));
+		return 0;
+	}
+	*n_cuts = sr->n_cuts;
+	if (n_energies != NULL) *n_energies = ne;
+	if (cuts != NULL) *cuts = c;
+	if (passed_w != NULL) *passed_w = p;
+	if (rejected_w != NULL) *rejected_w = r;
+	for (int k = 0; k < 3; k++) {
+		if (n_pass != NULL) n_pass[k] = sr->n_pass[k];
+		if (n_seen != NULL) n_seen[k] = sr->n_seen[k];
+	}
 	return 1;
 }
 

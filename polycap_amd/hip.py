@@ -508,9 +508,13 @@ class _Tally:
     def __exit__(self, *exc):
         self.close()
 
-    def add(self, kind="exit"):
-        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run."""
-        self._call("add", _kind(kind))
+    def add(self, kind="exit", select=None):
+        """Adds the exit photons ("exit" / 0), extleak ("extleak" / 1) or intleak ("intleak" / 2) events of the last run; with a
+        Selection applied for that kind, only the entries that pass it (an entry it rejects does not exist for the tally)."""
+        if select is None:
+            self._call("add", _kind(kind))
+        else:
+            self._call("add_selected", _kind(kind), select._h)
 
     def reset(self):
         self._call("reset")
@@ -800,6 +804,100 @@ class JointHistograms(_Tally):
             if total:
                 dens[e] = eff[e] * c[e].astype(np.float64) / float(total)
         return dens
+
+
+def select_cuts(cuts):
+    """A ctypes array of pc_hip_select_cut from a list of cuts, each an axis as hist_axes takes it (a name of JOINT_QUANTITIES) without
+    bins, as a dict that may carry not=True (pass what the range does not hold), or as a tuple (axis, (lo, hi)[, d[, (cx, cy)[, not]]])."""
+    arr = (_cabi.SelectCutS * max(len(cuts), 1))()
+    for k, c in enumerate(cuts):
+        if not isinstance(c, dict):
+            c = dict(zip(("axis", "range", "d", "centre", "not"), c))
+        c = dict(c)
+        negate = c.pop("not", False)
+        if "bins" in c:
+            raise ValueError("selection cut %d: a cut has no bins" % k)
+        arr[k] = _cabi.SelectCutS(hist_axes([dict(c, bins=1)], JOINT_QUANTITIES)[0], 1 if negate else 0)
+    return arr
+
+
+def _cut_dict(c):
+    a = c.axis
+    d = dict(axis=JOINT_QUANTITIES[a.quantity], d=a.d, centre=(a.cx, a.cy), range=(a.lo, a.hi))
+    d["not"] = bool(c.negate)
+    return d
+
+
+def select_parse(value):
+    """A value of POLYCAP_SELECT into a list of cut dicts (pc_hip_select_parse, host only).  ValueError with the reason, which names the
+    item or the cut, when it is refused."""
+    cuts = (_cabi.SelectCutS * 8)()
+    n = C.c_int32(0)
+    why = C.create_string_buffer(512)
+    st = _cabi.lib().pc_hip_select_parse(value.encode(), cuts, C.byref(n), why, len(why))
+    if st != _cabi.PC_HIP_OK:
+        raise ValueError("POLYCAP_SELECT=%s: %s" % (value, why.value.decode()))
+    return [_cut_dict(c) for c in cuts[:n.value]]
+
+
+class Selection:
+    """A selection of a TraceContext or a TraceGroup (pc_hip_select_*): 1 to 8 cuts on per-entry quantities of the last run, ANDed
+    (cuts: see select_cuts).  apply(kind) evaluates them on the device and returns the exact totals; tally.add(kind, select=sel) then
+    fills any tally of the same owner with the passing entries only.  A mask belongs to the entries it was made from: after the next
+    run it is stale and has to be applied again.  The contract is written down in include/polycap-hip.h."""
+
+    def __init__(self, owner, cuts):
+        self._L = _cabi.lib()
+        self.owner = owner                      # keeps the context alive as long as the object
+        self._cuts = select_cuts(cuts)
+        spec = _cabi.SelectSpecS(len(cuts), self._cuts)
+        h = C.c_void_p()
+        name = "pc_hip_%sselect_create" % ("group_" if isinstance(owner, TraceGroup) else "")
+        st = getattr(self._L, name)(owner._h, C.byref(spec), C.byref(h))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_select_create", st)
+        self._h = h
+        nc, ne = C.c_int32(0), C.c_int32(0)
+        self._L.pc_hip_select_info(self._h, C.byref(nc), C.byref(ne), None)
+        self.n_cuts, self.n_energies = int(nc.value), int(ne.value)
+        self.cuts = [_cut_dict(c) for c in self._cuts[:self.n_cuts]]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pc_hip_select_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def read(self):
+        """n_pass [3], n_seen [3] (kinds exit, extleak, intleak; zeros for a kind not applied), passed_w and rejected_w uint64
+        [3, n_energies]: the exact sums of round_half_even(w * 2^32) over the passing and over the rejected entries."""
+        n_pass, n_seen = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        pw = np.zeros((3, self.n_energies), dtype=np.uint64)
+        rw = np.zeros((3, self.n_energies), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        st = self._L.pc_hip_select_read(self._h, n_pass, n_seen, pw.ctypes.data_as(u64p), rw.ctypes.data_as(u64p))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_select_read", st)
+        return dict(n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
+                    passed_w=pw, rejected_w=rw)
+
+    def apply(self, kind="exit"):
+        """Evaluates the cuts on the entries of `kind` of the last run; returns read()"""
+        st = self._L.pc_hip_select_apply(self._h, _kind(kind))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_select_apply", st)
+        return self.read()
 
 
 def scan_points(x=(0.,), y=(0.,), d_source=None):

@@ -124,6 +124,9 @@ cdef extern from "polycap.h" nogil:
     int pc_transmission_efficiencies_get_joint(void *efficiencies, int kind, int32_t *dims, int32_t **offsets, pc_hip_joint_pair **pairs,
         double **energies, uint64_t **cells, uint64_t **outside, int64_t *n_entries, void *error)
 
+    int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies, int64_t *n_pass,
+        int64_t *n_seen, uint64_t **passed_w, uint64_t **rejected_w, void *error)
+
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
         double *pc_start_coords[2]
@@ -769,6 +772,35 @@ cdef class TransmissionEfficiencies:
         polycap_free(b)
         polycap_free(u)
         return dict(cells=B.reshape(ns, tc), outside=U.reshape(n_pairs, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), pairs=pairs)
+
+    def select(self):
+        """Extension of this build: the selection of a run made with POLYCAP_SELECT set (pc_transmission_efficiencies_get_select): dict
+        of cuts (a list of dicts axis, d, centre, range, not), n_pass [3] and n_seen [3] (exit, extleak, intleak) and the exact sums
+        passed_w and rejected_w uint64 [3, energies]."""
+        cdef polycap_error *error = NULL
+        cdef int32_t nc = 0
+        cdef size_t ne = 0
+        cdef double *c = NULL
+        cdef uint64_t *p = NULL
+        cdef uint64_t *r = NULL
+        cdef int64_t n_pass[3]
+        cdef int64_t n_seen[3]
+        cdef size_t i
+        pc_transmission_efficiencies_get_select(<void *>self._eff, &nc, &c, &ne, n_pass, n_seen, &p, &r, <void *>&error)
+        _raise_if(error)
+        names = ("x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z", "start_x", "start_y")
+        cuts = [{"axis": names[<int>c[7*i]], "d": c[7*i + 1], "centre": (c[7*i + 2], c[7*i + 3]), "range": (c[7*i + 4], c[7*i + 5]),
+                 "not": bool(c[7*i + 6])} for i in range(nc)]
+        P = np.empty(3 * ne, dtype=np.uint64)
+        R = np.empty(3 * ne, dtype=np.uint64)
+        for i in range(3 * ne):
+            P[i] = p[i]
+            R[i] = r[i]
+        polycap_free(c)
+        polycap_free(p)
+        polycap_free(r)
+        return dict(cuts=cuts, n_pass=np.array([n_pass[0], n_pass[1], n_pass[2]], dtype=np.int64),
+                    n_seen=np.array([n_seen[0], n_seen[1], n_seen[2]], dtype=np.int64), passed_w=P.reshape(3, ne), rejected_w=R.reshape(3, ne))
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
