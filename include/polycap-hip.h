@@ -541,6 +541,51 @@ POLYCAP_EXTERN int pc_hip_joint_add_selected(pc_hip_joint *joint, int kind, pc_h
  * "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not", into cuts [8] and *n_cuts, checked with pc_hip_select_validate.
  * PC_HIP_ERR_INVALID with the reason (it names the item) in why [why_len] otherwise. */
 POLYCAP_EXTERN int pc_hip_select_parse(const char *value, pc_hip_select_cut *cuts, int32_t *n_cuts, char *why, size_t why_len);
+/* ---- standard errors of the tallies: a second exact sum per cell, of the squared weights, kept in the same pass as the first, so
+ * that every bin of a spot map, a histogram or a joint histogram and the transmission of a selection carry their Monte Carlo error.
+ *
+ * The contract:
+ *   entry      per entry and energy W = round_half_even(w[e] * 2^32) as today (the spot maps' q(w), W <= 2^32).  Its square is the
+ *              integer product W*W <= 2^64 in units of 2^-64 -- not a second quantisation of w*w, which at a quantum of 2^-32 would
+ *              round the squares of weights below about 1e-5 to nothing -- as a (lo, hi) pair of uint64: lo = W*W mod 2^64, hi = the
+ *              upper 64 bits of the product (1 for W = 2^32 only)
+ *   cell       wherever the object keeps a weight sum S -- a spot-map bin, a histogram bin, a joint cell, every outside counter --
+ *              it also keeps S2 = the sum of W*W over the cell's entries as one (lo, hi) pair.  With the cap of 2^32 - 1 entries
+ *              S2 < 2^97 cannot wrap.  For every map, axis or pair: sum(S2 of the cells) + S2 of outside == the sum over the entries
+ *              of W*W, exactly.  A gated add obeys the selection contract for S2 as for S: an entry the mask rejects adds to neither
+ *   selection  also keeps passed_w2 and rejected_w2 [3][n_energies] as (lo, hi) pairs: the sums of W*W over the passing and over the
+ *              rejected entries; gated sum(S2) + outside S2 == passed_w2[e] per (kind, axis or pair, energy)
+ * S2 is an integer sum and depends on the set of entries only: not on the layout of the exit photons, "run_parts", the kernel that
+ * traced the run, the regime of the tally, how the slots were split into runs, or the device count.
+ *
+ * pc_hip_{spot,hist,joint}_track_squares turns the tracking on and allocates the zeroed pairs on every member.  Allowed only while the
+ * object holds no entries (n_entries all zero: before the first add, or after _reset); PC_HIP_ERR_INVALID and the object unchanged
+ * otherwise.  From then on every add, plain or _add_selected, fills S and S2 in one pass that reads each entry once; an object that
+ * does not track squares adds exactly as before.  _reset zeroes the pairs and keeps the tracking.
+ * pc_hip_{spot,hist,joint}_read_squares: the shapes of the _read calls with a trailing [2] (either pointer may be NULL); they wait
+ * for the adds and sum the members of a group with carry; PC_HIP_ERR_INVALID on an object that does not track squares.
+ * pc_hip_select_track_squares: refused (PC_HIP_ERR_INVALID, nothing changed) once any kind has been applied.
+ * pc_hip_select_read_squares: passed_w2, rejected_w2 [3][n_energies][2] (either may be NULL), zeros for a kind not applied. */
+POLYCAP_EXTERN int pc_hip_spot_track_squares(pc_hip_spot *spot);
+POLYCAP_EXTERN int pc_hip_spot_read_squares(pc_hip_spot *spot, uint64_t *bins_sq, uint64_t *outside_sq);
+POLYCAP_EXTERN int pc_hip_hist_track_squares(pc_hip_hist *hist);
+POLYCAP_EXTERN int pc_hip_hist_read_squares(pc_hip_hist *hist, uint64_t *bins_sq, uint64_t *outside_sq);
+POLYCAP_EXTERN int pc_hip_joint_track_squares(pc_hip_joint *joint);
+POLYCAP_EXTERN int pc_hip_joint_read_squares(pc_hip_joint *joint, uint64_t *cells_sq, uint64_t *outside_sq);
+POLYCAP_EXTERN int pc_hip_select_track_squares(pc_hip_select *select);
+POLYCAP_EXTERN int pc_hip_select_read_squares(pc_hip_select *select, uint64_t *passed_w2, uint64_t *rejected_w2);
+/* host only: the standard error of n_cells cells in weight per started photon, pc_hip_efficiency_stderr's estimator.  sums [n_cells]
+ * = S, squares [n_cells][2] = S2, N = n_started = counters 0 + 1 + 2 of the run or runs that were added (the caller's).  Per cell, in
+ * long double: m = S 2^-32 / N, q = S2 2^-64 / N, out = sqrt(max(q - m*m, 0) / (N - 1)); NaN for N < 2.  The events of a leak kind
+ * that come from one photon are treated as independent entries: each adds its own W*W, so where one photon leaves several events in
+ * one cell the error is underestimated by their covariance. */
+POLYCAP_EXTERN void pc_hip_tally_stderr(size_t n_cells, const uint64_t *sums, const uint64_t *squares, int64_t n_started, double *out);
+/* host only: the transmission of a selection per energy and its error from one kind's rows of pc_hip_select_read and _read_squares:
+ * P = passed_w 2^-32, R = rejected_w 2^-32, P2 = passed_w2 2^-64, R2 = rejected_w2 2^-64 ([n_energies] and [n_energies][2]), in long
+ * double: T = P / (P + R), T_err = sqrt(R*R*P2 + P*P*R2) / ((P + R)*(P + R)) -- the delta method on two independent Poisson-thinned
+ * sums; both NaN when P + R == 0.  T or T_err may be NULL. */
+POLYCAP_EXTERN void pc_hip_select_transmission(size_t n_energies, const uint64_t *passed_w, const uint64_t *rejected_w,
+	const uint64_t *passed_w2, const uint64_t *rejected_w2, double *T, double *T_err);
 /* ---- scans: transmission as a function of where the source sits (alignment curves, the input focal spot, the depth response of
  * a focusing optic) in one launch, with exact totals per point.
  *
@@ -738,6 +783,27 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_joint(void *efficiencies, in
  * seeds pool exactly.  A result made without POLYCAP_SELECT fails with POLYCAP_ERROR_INVALID_ARGUMENT. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies,
 	int64_t n_pass[3], int64_t n_seen[3], uint64_t **passed_w, uint64_t **rejected_w, void *error);
+
+/* Standard errors of the tallies through the public call: POLYCAP_TALLY_STDERR=1 (0 or unset: none; anything else is
+ * POLYCAP_ERROR_INVALID_ARGUMENT; it is not POLYCAP_STDERR, whose outputs stay as they are) makes every tally of the call (POLYCAP_SPOT,
+ * _HIST, _JOINT) and its POLYCAP_SELECT selection track squares (pc_hip_*_track_squares), on every path those variables serve: chunked
+ * POLYCAP_IMAGES=0 runs, device groups, leak runs.  N is the call's own: counters 0 + 1 + 2.
+ * _get_tally_squares: which = 0 (POLYCAP_SPOT), 1 (_HIST), 2 (_JOINT); kind as in the tally's own getter.  Returns 1 and (free each array
+ * with polycap_free; any pointer may be NULL): *n_cells and *n_outside, the cell and outside counts of the tally's getter ([plane][energy]
+ * [iy][ix] and [plane][energy]; [energy][total_bins] and [axis][energy]; [energy][total_cells] and [pair][energy]); the exact sums
+ * *sums [n_cells] and *outside [n_outside] (for the spot maps these are the uint64 sums behind the maps); *squares [n_cells][2] and
+ * *outside_squares [n_outside][2]; *stderrs [n_cells] and *outside_stderrs [n_outside] = pc_hip_tally_stderr with N = *n_started.
+ * _get_select_squares: *passed_w2 and *rejected_w2 [3][n_energies][2], and *transmission and *transmission_stderr [3][n_energies] of
+ * pc_hip_select_transmission per kind.  A result made without POLYCAP_TALLY_STDERR=1, or without the tally's variable, fails with
+ * POLYCAP_ERROR_INVALID_ARGUMENT.  write_hdf5 adds, beside each bins or cells dataset: /Spot/<Kind>_Squares, _Outside_Squares, _StdErr,
+ * _Outside_StdErr; /Hist/<Kind>/Bins_Squares, Outside_Squares, Bins_StdErr, Outside_StdErr; /Joint/<Kind>/Cells_Squares, Outside_Squares,
+ * Cells_StdErr, Outside_StdErr; /Select/Passed_Squares, Rejected_Squares, Transmission, Transmission_StdErr (uint64 with a trailing
+ * dimension 2, and doubles). */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_tally_squares(void *efficiencies, int which, int kind, size_t *n_cells, size_t *n_outside,
+	uint64_t **sums, uint64_t **outside, uint64_t **squares, uint64_t **outside_squares, double **stderrs, double **outside_stderrs,
+	int64_t *n_started, void *error);
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_select_squares(void *efficiencies, size_t *n_energies, uint64_t **passed_w2,
+	uint64_t **rejected_w2, double **transmission, double **transmission_stderr, void *error);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ There is no CPU implementation of the trace path in this package.
 from ._cabi import Problem, lib  # noqa: F401
 from .hip import TraceContext, TraceGroup, SpotMap, BeamMoments, Histograms, JointHistograms, Selection, select_cuts, select_parse, joint_marginal, joint_parse, hist_fwhm, hist_quantile, beam_params, HipError, device_count, efficiencies, efficiency_stderr, fixed_to_double, IMG_FIELDS  # noqa: F401
 from .hip import scan_points, scan_efficiencies  # noqa: F401
+from .hip import tally_stderr, select_transmission, pairs_sum  # noqa: F401
 from .hip import relay_efficiencies, relay_placement_valid, RELAY_COUNTERS  # noqa: F401
 from .decks import problem_from_inp, optical_constants, optical_constants_provider  # noqa: F401
 

@@ -320,6 +320,17 @@ def lib():
         fn.restype = C.c_int
     L.pc_hip_select_parse.argtypes = [C.c_char_p, P(SelectCutS), P(C.c_int32), C.c_char_p, C.c_size_t]
     L.pc_hip_select_parse.restype = C.c_int
+    for stem in ("spot", "hist", "joint", "select"):
+        fn = getattr(L, "pc_hip_%s_track_squares" % stem)
+        fn.argtypes = [C.c_void_p]
+        fn.restype = C.c_int
+        fn = getattr(L, "pc_hip_%s_read_squares" % stem)
+        fn.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
+        fn.restype = C.c_int
+    L.pc_hip_tally_stderr.argtypes = [C.c_size_t, P(C.c_uint64), P(C.c_uint64), C.c_int64, c_double_p]
+    L.pc_hip_tally_stderr.restype = None
+    L.pc_hip_select_transmission.argtypes = [C.c_size_t, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64), P(C.c_uint64), c_double_p, c_double_p]
+    L.pc_hip_select_transmission.restype = None
     L.pc_hip_device_memory.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
     L.pc_hip_device_memory.restype = C.c_int
     u64p = P(C.c_uint64)

@@ -137,6 +137,9 @@ def _lib():
                                                              P(P(C.c_uint64)), P(P(C.c_uint64)), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_select": (C.c_int, [vp, P(C.c_int32), P(_dp), P(C.c_size_t), P(C.c_int64), P(C.c_int64),
                                                               P(P(C.c_uint64)), P(P(C.c_uint64)), epp]),
+        "pc_transmission_efficiencies_get_tally_squares": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_size_t), P(C.c_size_t)] + [P(P(C.c_uint64))] * 4 +
+                                                             [P(_dp), P(_dp), P(C.c_int64), epp]),
+        "pc_transmission_efficiencies_get_select_squares": (C.c_int, [vp, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)), P(_dp), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -417,6 +420,29 @@ class TransmissionEfficiencies(_LeakData):
 
     SPOT_KINDS = {"exit": 0, "extleak": 1, "intleak": 2}
 
+    def _squares(self, which, kind, cells_shape, outside_shape):
+        """What POLYCAP_TALLY_STDERR=1 adds to a tally's accessor (extension, pc_transmission_efficiencies_get_tally_squares): squares
+        and outside_squares uint64 [..., 2], stderr and outside_stderr (doubles shaped like the cells and the outside counters, weight
+        per started photon) and n_started; for the spot maps also the uint64 sums behind the maps.  {} for a run made without it."""
+        nc, no = C.c_size_t(0), C.c_size_t(0)
+        a, b, c, d = (C.POINTER(C.c_uint64)() for _ in range(4))
+        e, f = _dp(), _dp()
+        ns = C.c_int64(0)
+        err = _ErrP()
+        ok = _lib().pc_transmission_efficiencies_get_tally_squares(self._h, which, self.SPOT_KINDS[kind], C.byref(nc), C.byref(no), C.byref(a), C.byref(b),
+                                                                   C.byref(c), C.byref(d), C.byref(e), C.byref(f), C.byref(ns), C.byref(err))
+        if not ok:
+            if err:
+                _lib().polycap_error_free(err)
+            return {}
+        nc, no = nc.value, no.value
+        out = dict(squares=_take(c, 2 * nc, np.uint64).reshape(tuple(cells_shape) + (2,)), outside_squares=_take(d, 2 * no, np.uint64).reshape(tuple(outside_shape) + (2,)),
+                   stderr=_take(e, nc).reshape(cells_shape), outside_stderr=_take(f, no).reshape(outside_shape), n_started=int(ns.value))
+        sums, outside = _take(a, nc, np.uint64).reshape(cells_shape), _take(b, no, np.uint64).reshape(outside_shape)
+        if which == 0:
+            out.update(bins=sums, outside_bins=outside)
+        return out
+
     def spot_map(self, kind="exit"):
         """Spot maps of a run made with POLYCAP_SPOT set (extension, pc_transmission_efficiencies_get_spot): dict of
         maps [plane, energy, iy, ix] and outside [plane, energy] in efficiency units, distances (cm), window (x0, x1, y0, y1; cm)
@@ -430,7 +456,11 @@ class TransmissionEfficiencies(_LeakData):
         _check(err)
         npl, ns, ny, nx = (int(v) for v in dims)
         return dict(maps=_take(m, npl * ns * ny * nx).reshape(npl, ns, ny, nx), outside=_take(o, npl * ns).reshape(npl, ns),
-                    distances=_take(d, npl), energies=_take(e, ns), window=tuple(win))
+                    distances=_take(d, npl), energies=_take(e, ns), window=tuple(win), **self._squares(0, kind, (npl, ns, ny, nx), (npl, ns)))
+
+    def spot(self, kind="exit"):
+        """spot_map under the name of the other tallies' accessors"""
+        return self.spot_map(kind)
 
     def efficiency_stderr(self):
         """Standard error of every efficiency of a run made with POLYCAP_STDERR=1 (extension,
@@ -496,12 +526,14 @@ class TransmissionEfficiencies(_LeakData):
                 for k in range(na)]
         L.polycap_free(C.cast(a, C.c_void_p))
         return dict(bins=_take(b, ns * tb, np.uint64).reshape(ns, tb), outside=_take(u, na * ns, np.uint64).reshape(na, ns),
-                    n_entries=int(ni.value), offsets=_take(o, na + 1, np.int32), energies=_take(e, ns), axes=axes)
+                    n_entries=int(ni.value), offsets=_take(o, na + 1, np.int32), energies=_take(e, ns), axes=axes,
+                    **self._squares(1, kind, (ns, tb), (na, ns)))
 
     def select(self):
         """The selection of a run made with POLYCAP_SELECT set (extension, pc_transmission_efficiencies_get_select): dict of cuts (a
         list of dicts axis, d, centre, range, not), n_pass [3] and n_seen [3] (exit, extleak, intleak; zeros for the leak kinds of a
-        plain run) and the exact sums passed_w and rejected_w uint64 [3, energies]."""
+        plain run) and the exact sums passed_w and rejected_w uint64 [3, energies].  A run made with
+        POLYCAP_TALLY_STDERR=1 adds passed_w2 and rejected_w2 uint64 [3, energies, 2] and transmission, transmission_stderr [3, energies]."""
         from .hip import JOINT_QUANTITIES
         L = _lib()
         nc, ne = C.c_int32(0), C.c_size_t(0)
@@ -513,8 +545,17 @@ class TransmissionEfficiencies(_LeakData):
         rows = _take(c, 7 * nc.value).reshape(nc.value, 7)
         cuts = [{"axis": JOINT_QUANTITIES[int(q[0])], "d": float(q[1]), "centre": (float(q[2]), float(q[3])), "range": (float(q[4]), float(q[5])),
                  "not": bool(q[6])} for q in rows]
-        return dict(cuts=cuts, n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
-                    passed_w=_take(p, 3 * ne.value, np.uint64).reshape(3, ne.value), rejected_w=_take(r, 3 * ne.value, np.uint64).reshape(3, ne.value))
+        out = dict(cuts=cuts, n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
+                   passed_w=_take(p, 3 * ne.value, np.uint64).reshape(3, ne.value), rejected_w=_take(r, 3 * ne.value, np.uint64).reshape(3, ne.value))
+        # POLYCAP_TALLY_STDERR=1: the sums of W*W and the transmission per kind with its standard error
+        p2, r2, t, te = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), _dp(), _dp()
+        if L.pc_transmission_efficiencies_get_select_squares(self._h, C.byref(ne), C.byref(p2), C.byref(r2), C.byref(t), C.byref(te), C.byref(err)):
+            n = ne.value
+            out.update(passed_w2=_take(p2, 6 * n, np.uint64).reshape(3, n, 2), rejected_w2=_take(r2, 6 * n, np.uint64).reshape(3, n, 2),
+                       transmission=_take(t, 3 * n).reshape(3, n), transmission_stderr=_take(te, 3 * n).reshape(3, n))
+        elif err:
+            L.polycap_error_free(err)
+        return out
 
     def joint(self, kind="exit"):
         """Joint histograms of a run made with POLYCAP_JOINT set (extension, pc_transmission_efficiencies_get_joint): dict of the
@@ -535,7 +576,8 @@ class TransmissionEfficiencies(_LeakData):
         pairs = [(_axis_dict(a[k].u), _axis_dict(a[k].v)) for k in range(n_pairs)]
         L.polycap_free(C.cast(a, C.c_void_p))
         return dict(cells=_take(b, ns * tc, np.uint64).reshape(ns, tc), outside=_take(u, n_pairs * ns, np.uint64).reshape(n_pairs, ns),
-                    n_entries=int(ni.value), offsets=_take(o, n_pairs + 1, np.int32), energies=_take(e, ns), pairs=pairs)
+                    n_entries=int(ni.value), offsets=_take(o, n_pairs + 1, np.int32), energies=_take(e, ns), pairs=pairs,
+                    **self._squares(2, kind, (ns, tc), (n_pairs, ns)))
 
     def _start(self):
         L = _lib()

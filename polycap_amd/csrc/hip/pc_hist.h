@@ -190,16 +190,19 @@ static __device__ __forceinline__ void pc_hist_load(const pc_spot_src &s, const 
 /* Regime 1: workgroup-private histograms.  The cells [energy][tc] are cut into tiles of PC_HIST_TILE uint64; workgroup (x, y)
  * adds the entries x, x + gridDim.x, ... whose cells fall into tile y to a private copy of it in LDS (ds_add_u64), one entry per
  * lane, then adds every non-zero cell of the copy to the global cells with one atomic.  Several tiles are several passes over
- * the entries. */
+ * the entries.  Where the squares are tracked (Q) a tile is TC = PC_HIST_TILE / 3 cells (pc_tally_tile_cells): their weight sums
+ * in tile[0, TC), their square sums as (lo, hi) pairs behind them, flushed with pc_atomic_add128 to sq [cell][2]. */
 #define PC_HIST_TILE 8192
 #define PC_HIST_LDS_BLOCK 512
-template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
-__global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells)
+/* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask.  Q: the squares are tracked; the build without reads no sq */
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells, unsigned long long *sq)
 {
 	__shared__ unsigned long long tile[PC_HIST_TILE];
+	constexpr long long TC = pc_tally_tile_cells(PC_HIST_TILE, Q);
 	const long long total = (long long)g.ns*g.tc;
-	const long long t0 = (long long)blockIdx.y*PC_HIST_TILE;
-	const long long t1 = (t0 + PC_HIST_TILE < total) ? t0 + PC_HIST_TILE : total;
+	const long long t0 = (long long)blockIdx.y*TC;
+	const long long t1 = (t0 + TC < total) ? t0 + TC : total;
 	const int k0 = (int)(t0 / g.tc), k1 = (int)((t1 - 1) / g.tc);      /* the energies with cells in this tile */
 	for (int k = threadIdx.x; k < PC_HIST_TILE; k += blockDim.x) tile[k] = 0ull;
 	__syncthreads();
@@ -214,30 +217,41 @@ __global__ void __launch_bounds__(PC_HIST_LDS_BLOCK) pc_hist_lds_kernel(pc_spot_
 				const long long cell = (long long)k*g.tc + c;
 				if (cell < t0 || cell >= t1) continue;
 				const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[k]]);
-				if (q) atomicAdd(&tile[cell - t0], q);
+				if (q) {
+					atomicAdd(&tile[cell - t0], q);
+					if (Q) pc_tally_lds_add_sq(&tile[TC + 2*(cell - t0)], q);
+				}
 			}
 		}
 	}
 	__syncthreads();
 	for (long long k = threadIdx.x; k < t1 - t0; k += blockDim.x) {
 		const unsigned long long v = tile[k];
-		if (v) atomicAdd(&cells[t0 + k], v);
+		if (v) {
+			atomicAdd(&cells[t0 + k], v);
+			if (Q) pc_atomic_add128(sq + 2*(t0 + k), tile[TC + 2*k], tile[TC + 2*k + 1]);      /* a cell without weight has no square */
+		}
 	}
 }
 
 /* Regime 2: energies across lanes.  The cells are laid out [tc][energy] with the energies innermost: the lanes of a wave take
  * the energies of one entry (64 / gw entries per wave when fewer than 64 are selected, gw = the next power of two), so that one
  * wave instruction is a contiguous run of 8-byte global atomics.  Workgroup (x, c) does energies [c*PC_HIST_ECHUNK, ...); the
- * outside counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters). */
+ * outside counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters).
+ * Where the squares are tracked (Q) every add to a cell is followed by pc_tally_add_sq on its pair in sq [cell][2], the chunk is
+ * PC_HIST_ECHUNK_SQ energies and the outside counters' pairs follow the counters in LDS (48 KiB in all). */
 #define PC_HIST_ECHUNK 512
+#define PC_HIST_ECHUNK_SQ 128
 #define PC_HIST_WIDE_BLOCK 256
-template <bool M>
-__global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells)
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spot_src s, pc_hist_geo g, unsigned long long *cells, unsigned long long *sq)
 {
-	__shared__ unsigned long long out[PC_HIST_MAX_AXES*PC_HIST_ECHUNK];
-	const int s0 = blockIdx.y*PC_HIST_ECHUNK;
-	const int sn = (g.ns - s0 < PC_HIST_ECHUNK) ? g.ns - s0 : PC_HIST_ECHUNK;
-	for (int k = threadIdx.x; k < g.na*PC_HIST_ECHUNK; k += blockDim.x) out[k] = 0ull;
+	constexpr int EC = Q ? PC_HIST_ECHUNK_SQ : PC_HIST_ECHUNK;
+	__shared__ unsigned long long out[PC_HIST_MAX_AXES*EC*(Q ? 3 : 1)];
+	unsigned long long *out_sq = out + g.na*EC;      /* [axis*EC + k][2] behind the counters of the na axes, Q only */
+	const int s0 = blockIdx.y*EC;
+	const int sn = (g.ns - s0 < EC) ? g.ns - s0 : EC;
+	for (int k = threadIdx.x; k < g.na*EC*(Q ? 3 : 1); k += blockDim.x) out[k] = 0ull;
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
@@ -254,23 +268,36 @@ __global__ void __launch_bounds__(PC_HIST_WIDE_BLOCK) pc_hist_wide_kernel(pc_spo
 #pragma unroll
 			for (int a = 0; a < PC_HIST_MAX_AXES; a++) {
 				if (a >= g.na) break;
-				if (bin[a] >= 0) atomicAdd(cells + (long long)(g.cell0[a] + bin[a])*g.ns + s0 + k, q);
-				else atomicAdd(&out[a*PC_HIST_ECHUNK + k], q);
+				if (bin[a] >= 0) {
+					const long long c = (long long)(g.cell0[a] + bin[a])*g.ns + s0 + k;
+					atomicAdd(cells + c, q);
+					if (Q) pc_tally_add_sq(sq + 2*c, q);
+				} else {
+					atomicAdd(&out[a*EC + k], q);
+					if (Q) pc_tally_lds_add_sq(&out_sq[2*(a*EC + k)], q);
+				}
 			}
 		}
 	}
 	__syncthreads();
-	for (int k = threadIdx.x; k < g.na*PC_HIST_ECHUNK; k += blockDim.x) {
-		const int a = k / PC_HIST_ECHUNK, j = k % PC_HIST_ECHUNK;
+	for (int k = threadIdx.x; k < g.na*EC; k += blockDim.x) {
+		const int a = k / EC, j = k % EC;
 		const unsigned long long v = out[k];
-		if (v) atomicAdd(cells + (long long)(g.cell0[a] + g.ax[a].n_bins)*g.ns + s0 + j, v);
+		if (v) {
+			const long long c = (long long)(g.cell0[a] + g.ax[a].n_bins)*g.ns + s0 + j;
+			atomicAdd(cells + c, v);
+			if (Q) pc_atomic_add128(sq + 2*c, out_sq[2*k], out_sq[2*k + 1]);
+		}
 	}
 }
 
 /* Regime of an object (spec->regime 0): private LDS histograms (1) when all its cells fit one tile, energies across lanes (2)
  * otherwise, where regime 1 would pass over the entries once per tile.  Not measured: scripts/bench_hist.py times one add per
  * regime (one N_REFL axis of 256 bins, one X_AT axis of 2048 bins, eight mixed axes; xos1, 1e7 exit photons, 1 and 291 energies)
- * next to the spot map that holds the same X_AT axis.  A wave-level pre-sum of lanes that hit the same cell was not built. */
+ * next to the spot map that holds the same X_AT axis.  A wave-level pre-sum of lanes that hit the same cell was not built.
+ * The rule is applied when the object is made and not again when it starts to track squares: with 2731 to 8192 cells a tracking
+ * object stays in regime 1 and makes two or three passes over the entries (pc_tally_tile_split).  Whether regime 2 is faster there
+ * has not been measured. */
 static int pc_hist_auto_regime(long long ns, long long tc)
 {
 	return (ns*tc <= PC_HIST_TILE) ? 1 : 2;
@@ -328,18 +355,42 @@ static int pc_hist_launch(pc_hip_hist *h, pc_tally_member &m, const pc_spot_src 
 	pc_hist_geo g = h->geo;
 	g.sel = m.d_sel;
 	unsigned long long *cells = m.d_cells + (size_t)kind*h->per_kind;
+	unsigned long long *sq = h->squares ? m.d_sq + 2*(size_t)kind*h->per_kind : nullptr;
 	if (h->regime == 1) {
-		const long long tiles = ((long long)h->per_kind + PC_HIST_TILE - 1)/PC_HIST_TILE;
+		const long long tiles = pc_tally_tile_split((long long)h->per_kind, PC_HIST_TILE, h->squares).tiles;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_HIST_LDS_BLOCK).bx;
-		auto kern = s.mask ? pc_hist_lds_kernel<true> : pc_hist_lds_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_HIST_LDS_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = sq ? (s.mask ? pc_hist_lds_kernel<true, true> : pc_hist_lds_kernel<false, true>)
+		               : (s.mask ? pc_hist_lds_kernel<true, false> : pc_hist_lds_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_HIST_LDS_BLOCK), 0, c->stream, s, g, cells, sq);
 	} else {
-		const long long chunks = (g.ns + PC_HIST_ECHUNK - 1)/PC_HIST_ECHUNK;
+		const int ec = sq ? PC_HIST_ECHUNK_SQ : PC_HIST_ECHUNK;
+		const long long chunks = (g.ns + ec - 1)/ec;
 		const long long bx = pc_tally_grid_wide(c->n_cu, chunks, g.ns, s.n, PC_HIST_WIDE_BLOCK).bx;
-		auto kern = s.mask ? pc_hist_wide_kernel<true> : pc_hist_wide_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_HIST_WIDE_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = sq ? (s.mask ? pc_hist_wide_kernel<true, true> : pc_hist_wide_kernel<false, true>)
+		               : (s.mask ? pc_hist_wide_kernel<true, false> : pc_hist_wide_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_HIST_WIDE_BLOCK), 0, c->stream, s, g, cells, sq);
 	}
 	return PC_HIP_OK;
+}
+
+/* the members' summed cells (limbs = 1) or square pairs (limbs = 2) from the device layout of the regime into bins
+ * [3][ns][total_bins][limbs] and outside [3][na][ns][limbs]; either may be NULL */
+static void pc_hist_unpack(const pc_hip_hist *hist, const std::vector<unsigned long long> &sum, size_t limbs, uint64_t *bins, uint64_t *outside)
+{
+	const pc_hist_geo &g = hist->geo;
+	const size_t ns = (size_t)g.ns, tc = (size_t)g.tc, tb = tc - (size_t)g.na;
+	for (size_t kind = 0; kind < 3; kind++)
+		for (size_t s = 0; s < ns; s++)
+			for (int a = 0; a < g.na; a++) {
+				const size_t c0 = (size_t)g.cell0[a], nb = (size_t)g.ax[a].n_bins;
+				for (size_t b = 0; b <= nb; b++) {
+					const unsigned long long *v = &sum[limbs*(kind*hist->per_kind + (hist->regime == 1 ? s*tc + c0 + b : (c0 + b)*ns + s))];
+					uint64_t *to = nullptr;
+					if (b < nb) { if (bins) to = bins + limbs*((kind*ns + s)*tb + (size_t)hist->offsets[a] + b); }
+					else if (outside) to = outside + limbs*((kind*(size_t)g.na + (size_t)a)*ns + s);
+					for (size_t l = 0; to && l < limbs; l++) to[l] = v[l];
+				}
+			}
 }
 
 extern "C" {
@@ -398,20 +449,25 @@ int pc_hip_hist_read(pc_hip_hist *hist, uint64_t *bins, uint64_t *outside, int64
 	std::vector<unsigned long long> sum;
 	const int st = pc_tally_sum(*hist, 1, sum);
 	if (st) return st;
-	const pc_hist_geo &g = hist->geo;
-	const size_t ns = (size_t)g.ns, tc = (size_t)g.tc, tb = tc - (size_t)g.na;
-	for (size_t kind = 0; kind < 3; kind++)
-		for (size_t s = 0; s < ns; s++)
-			for (int a = 0; a < g.na; a++) {
-				const size_t c0 = (size_t)g.cell0[a], nb = (size_t)g.ax[a].n_bins;
-				for (size_t b = 0; b <= nb; b++) {
-					const unsigned long long v = sum[kind*hist->per_kind + (hist->regime == 1 ? s*tc + c0 + b : (c0 + b)*ns + s)];
-					if (b < nb) { if (bins) bins[(kind*ns + s)*tb + (size_t)hist->offsets[a] + b] = v; }
-					else if (outside) outside[(kind*(size_t)g.na + (size_t)a)*ns + s] = v;
-				}
-			}
+	pc_hist_unpack(hist, sum, 1, bins, outside);
 	if (n_entries)
 		for (int k = 0; k < 3; k++) n_entries[k] = hist->n_entries[k];
+	return PC_HIP_OK;
+}
+
+int pc_hip_hist_track_squares(pc_hip_hist *hist)
+{
+	if (!hist) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_track_squares: hist must not be NULL");
+	return pc_tally_track_squares(*hist, "pc_hip_hist_track_squares");
+}
+
+int pc_hip_hist_read_squares(pc_hip_hist *hist, uint64_t *bins_sq, uint64_t *outside_sq)
+{
+	if (!hist) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_read_squares: hist must not be NULL");
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum_squares(*hist, "pc_hip_hist_read_squares", sum);
+	if (st) return st;
+	pc_hist_unpack(hist, sum, 2, bins_sq, outside_sq);
 	return PC_HIP_OK;
 }
 

@@ -50,16 +50,19 @@ struct pc_joint_geo {
  * entries x, x + gridDim.x, ... whose cells fall into tile y to a private copy of it in LDS (ds_add_u64), one entry per lane, then
  * adds every non-zero cell of the copy to the global cells with one atomic.  Several tiles are several passes over the entries;
  * a pass evaluates only the pairs that have cells in its tile.  64 KiB of LDS per workgroup: two workgroups per CU
- * (pc_tally_grid_tiles). */
+ * (pc_tally_grid_tiles).  Where the squares are tracked (Q) a tile is TC = PC_JOINT_TILE / 3 cells (pc_tally_tile_cells): their
+ * weight sums in tile[0, TC), their square sums as (lo, hi) pairs behind them, flushed with pc_atomic_add128 to sq [cell][2]. */
 #define PC_JOINT_TILE 8192
 #define PC_JOINT_LDS_BLOCK 512
-template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
-__global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells)
+/* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask.  Q: the squares are tracked; the build without reads no sq */
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells, unsigned long long *sq)
 {
 	__shared__ unsigned long long tile[PC_JOINT_TILE];
+	constexpr long long TC = pc_tally_tile_cells(PC_JOINT_TILE, Q);
 	const long long total = (long long)g.ns*g.tc;
-	const long long t0 = (long long)blockIdx.y*PC_JOINT_TILE;
-	const long long t1 = (t0 + PC_JOINT_TILE < total) ? t0 + PC_JOINT_TILE : total;
+	const long long t0 = (long long)blockIdx.y*TC;
+	const long long t1 = (t0 + TC < total) ? t0 + TC : total;
 	const int k0 = (int)(t0 / g.tc), k1 = (int)((t1 - 1) / g.tc);      /* the energies with cells in this tile */
 	/* pair p has cells in [t0, t1) when its run of energy k0 ends behind t0 or that of a later energy starts before t1 */
 	unsigned active = 0u;
@@ -82,30 +85,41 @@ __global__ void __launch_bounds__(PC_JOINT_LDS_BLOCK) pc_joint_lds_kernel(pc_spo
 				const long long cell = (long long)k*g.tc + c;
 				if (cell < t0 || cell >= t1) continue;
 				const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[k]]);
-				if (q) atomicAdd(&tile[cell - t0], q);
+				if (q) {
+					atomicAdd(&tile[cell - t0], q);
+					if (Q) pc_tally_lds_add_sq(&tile[TC + 2*(cell - t0)], q);
+				}
 			}
 		}
 	}
 	__syncthreads();
 	for (long long k = threadIdx.x; k < t1 - t0; k += blockDim.x) {
 		const unsigned long long v = tile[k];
-		if (v) atomicAdd(&cells[t0 + k], v);
+		if (v) {
+			atomicAdd(&cells[t0 + k], v);
+			if (Q) pc_atomic_add128(sq + 2*(t0 + k), tile[TC + 2*k], tile[TC + 2*k + 1]);      /* a cell without weight has no square */
+		}
 	}
 }
 
 /* Regime 2: energies across lanes.  The cells are laid out [tc][energy] with the energies innermost: the lanes of a wave take the
  * energies of one entry (64 / gw entries per wave when fewer than 64 are selected, gw = the next power of two), so that one wave
  * instruction is a contiguous run of 8-byte global atomics.  Workgroup (x, c) does energies [c*PC_JOINT_ECHUNK, ...); the outside
- * counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters; 32 KiB). */
+ * counters of those energies are summed in LDS first (every entry that misses a range adds to the same few counters; 32 KiB).
+ * Where the squares are tracked (Q) every add to a cell is followed by pc_tally_add_sq on its pair in sq [cell][2], the chunk is
+ * PC_JOINT_ECHUNK_SQ energies and the outside counters' pairs follow the counters in LDS (48 KiB in all). */
 #define PC_JOINT_ECHUNK 512
+#define PC_JOINT_ECHUNK_SQ 256
 #define PC_JOINT_WIDE_BLOCK 256
-template <bool M>
-__global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells)
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_spot_src s, pc_joint_geo g, unsigned long long *cells, unsigned long long *sq)
 {
-	__shared__ unsigned long long out[PC_JOINT_MAX_PAIRS*PC_JOINT_ECHUNK];
-	const int s0 = blockIdx.y*PC_JOINT_ECHUNK;
-	const int sn = (g.ns - s0 < PC_JOINT_ECHUNK) ? g.ns - s0 : PC_JOINT_ECHUNK;
-	for (int k = threadIdx.x; k < g.np*PC_JOINT_ECHUNK; k += blockDim.x) out[k] = 0ull;
+	constexpr int EC = Q ? PC_JOINT_ECHUNK_SQ : PC_JOINT_ECHUNK;
+	__shared__ unsigned long long out[PC_JOINT_MAX_PAIRS*EC*(Q ? 3 : 1)];
+	unsigned long long *out_sq = out + g.np*EC;      /* [pair*EC + k][2] behind the counters of the np pairs, Q only */
+	const int s0 = blockIdx.y*EC;
+	const int sn = (g.ns - s0 < EC) ? g.ns - s0 : EC;
+	for (int k = threadIdx.x; k < g.np*EC*(Q ? 3 : 1); k += blockDim.x) out[k] = 0ull;
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
@@ -122,16 +136,26 @@ __global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_s
 #pragma unroll
 			for (int p = 0; p < PC_JOINT_MAX_PAIRS; p++) {
 				if (p >= g.np) break;
-				if (cell[p] >= 0) atomicAdd(cells + (long long)(g.cell0[p] + cell[p])*g.ns + s0 + k, q);
-				else atomicAdd(&out[p*PC_JOINT_ECHUNK + k], q);
+				if (cell[p] >= 0) {
+					const long long c = (long long)(g.cell0[p] + cell[p])*g.ns + s0 + k;
+					atomicAdd(cells + c, q);
+					if (Q) pc_tally_add_sq(sq + 2*c, q);
+				} else {
+					atomicAdd(&out[p*EC + k], q);
+					if (Q) pc_tally_lds_add_sq(&out_sq[2*(p*EC + k)], q);
+				}
 			}
 		}
 	}
 	__syncthreads();
-	for (int k = threadIdx.x; k < g.np*PC_JOINT_ECHUNK; k += blockDim.x) {
-		const int p = k / PC_JOINT_ECHUNK, j = k % PC_JOINT_ECHUNK;
+	for (int k = threadIdx.x; k < g.np*EC; k += blockDim.x) {
+		const int p = k / EC, j = k % EC;
 		const unsigned long long v = out[k];
-		if (v) atomicAdd(cells + (long long)(g.cell0[p] + g.nc[p])*g.ns + s0 + j, v);
+		if (v) {
+			const long long c = (long long)(g.cell0[p] + g.nc[p])*g.ns + s0 + j;
+			atomicAdd(cells + c, v);
+			if (Q) pc_atomic_add128(sq + 2*c, out_sq[2*k], out_sq[2*k + 1]);
+		}
 	}
 }
 
@@ -139,7 +163,8 @@ __global__ void __launch_bounds__(PC_JOINT_WIDE_BLOCK) pc_joint_wide_kernel(pc_s
  * across lanes (2) otherwise, where regime 1 would pass over the entries once per tile.  Not measured for this tally:
  * scripts/bench_joint.py times one add per regime (the pair (X_AT, Y_AT) at 256^2 and 1024^2 at one energy and at 64^2 with 291
  * energies, each next to the spot-map add of the same shape, and a four-pair spec; xos1, 1e7 exit photons) and writes
- * profiles/joint_ab.txt. */
+ * profiles/joint_ab.txt.  As for the histograms the rule is not applied again when the object starts to track squares (two or three
+ * passes in regime 1 with 2731 to 8192 cells; not measured against regime 2). */
 static int pc_joint_auto_regime(long long ns, long long tc)
 {
 	return (ns*tc <= PC_JOINT_TILE) ? 1 : 2;
@@ -201,18 +226,42 @@ static int pc_joint_launch(pc_hip_joint *h, pc_tally_member &m, const pc_spot_sr
 	pc_joint_geo g = h->geo;
 	g.sel = m.d_sel;
 	unsigned long long *cells = m.d_cells + (size_t)kind*h->per_kind;
+	unsigned long long *sq = h->squares ? m.d_sq + 2*(size_t)kind*h->per_kind : nullptr;
 	if (h->regime == 1) {
-		const long long tiles = ((long long)h->per_kind + PC_JOINT_TILE - 1)/PC_JOINT_TILE;
+		const long long tiles = pc_tally_tile_split((long long)h->per_kind, PC_JOINT_TILE, h->squares).tiles;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_JOINT_LDS_BLOCK).bx;
-		auto kern = s.mask ? pc_joint_lds_kernel<true> : pc_joint_lds_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_JOINT_LDS_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = sq ? (s.mask ? pc_joint_lds_kernel<true, true> : pc_joint_lds_kernel<false, true>)
+		               : (s.mask ? pc_joint_lds_kernel<true, false> : pc_joint_lds_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_JOINT_LDS_BLOCK), 0, c->stream, s, g, cells, sq);
 	} else {
-		const long long chunks = (g.ns + PC_JOINT_ECHUNK - 1)/PC_JOINT_ECHUNK;
+		const int ec = sq ? PC_JOINT_ECHUNK_SQ : PC_JOINT_ECHUNK;
+		const long long chunks = (g.ns + ec - 1)/ec;
 		const long long bx = pc_tally_grid_wide(c->n_cu, chunks, g.ns, s.n, PC_JOINT_WIDE_BLOCK).bx;
-		auto kern = s.mask ? pc_joint_wide_kernel<true> : pc_joint_wide_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_JOINT_WIDE_BLOCK), 0, c->stream, s, g, cells);
+		auto kern = sq ? (s.mask ? pc_joint_wide_kernel<true, true> : pc_joint_wide_kernel<false, true>)
+		               : (s.mask ? pc_joint_wide_kernel<true, false> : pc_joint_wide_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_JOINT_WIDE_BLOCK), 0, c->stream, s, g, cells, sq);
 	}
 	return PC_HIP_OK;
+}
+
+/* the members' summed cells (limbs = 1) or square pairs (limbs = 2) from the device layout of the regime into cells
+ * [3][ns][total_cells][limbs] and outside [3][np][ns][limbs]; either may be NULL */
+static void pc_joint_unpack(const pc_hip_joint *joint, const std::vector<unsigned long long> &sum, size_t limbs, uint64_t *cells, uint64_t *outside)
+{
+	const pc_joint_geo &g = joint->geo;
+	const size_t ns = (size_t)g.ns, tc = (size_t)g.tc, total = tc - (size_t)g.np;
+	for (size_t kind = 0; kind < 3; kind++)
+		for (size_t s = 0; s < ns; s++)
+			for (int p = 0; p < g.np; p++) {
+				const size_t c0 = (size_t)g.cell0[p], nc = (size_t)g.nc[p];
+				for (size_t b = 0; b <= nc; b++) {
+					const unsigned long long *v = &sum[limbs*(kind*joint->per_kind + (joint->regime == 1 ? s*tc + c0 + b : (c0 + b)*ns + s))];
+					uint64_t *to = nullptr;
+					if (b < nc) { if (cells) to = cells + limbs*((kind*ns + s)*total + (size_t)joint->offsets[p] + b); }
+					else if (outside) to = outside + limbs*((kind*(size_t)g.np + (size_t)p)*ns + s);
+					for (size_t l = 0; to && l < limbs; l++) to[l] = v[l];
+				}
+			}
 }
 
 extern "C" {
@@ -272,20 +321,25 @@ int pc_hip_joint_read(pc_hip_joint *joint, uint64_t *cells, uint64_t *outside, i
 	std::vector<unsigned long long> sum;
 	const int st = pc_tally_sum(*joint, 1, sum);
 	if (st) return st;
-	const pc_joint_geo &g = joint->geo;
-	const size_t ns = (size_t)g.ns, tc = (size_t)g.tc, total = tc - (size_t)g.np;
-	for (size_t kind = 0; kind < 3; kind++)
-		for (size_t s = 0; s < ns; s++)
-			for (int p = 0; p < g.np; p++) {
-				const size_t c0 = (size_t)g.cell0[p], nc = (size_t)g.nc[p];
-				for (size_t b = 0; b <= nc; b++) {
-					const unsigned long long v = sum[kind*joint->per_kind + (joint->regime == 1 ? s*tc + c0 + b : (c0 + b)*ns + s)];
-					if (b < nc) { if (cells) cells[(kind*ns + s)*total + (size_t)joint->offsets[p] + b] = v; }
-					else if (outside) outside[(kind*(size_t)g.np + (size_t)p)*ns + s] = v;
-				}
-			}
+	pc_joint_unpack(joint, sum, 1, cells, outside);
 	if (n_entries)
 		for (int k = 0; k < 3; k++) n_entries[k] = joint->n_entries[k];
+	return PC_HIP_OK;
+}
+
+int pc_hip_joint_track_squares(pc_hip_joint *joint)
+{
+	if (!joint) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_track_squares: joint must not be NULL");
+	return pc_tally_track_squares(*joint, "pc_hip_joint_track_squares");
+}
+
+int pc_hip_joint_read_squares(pc_hip_joint *joint, uint64_t *cells_sq, uint64_t *outside_sq)
+{
+	if (!joint) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_read_squares: joint must not be NULL");
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum_squares(*joint, "pc_hip_joint_read_squares", sum);
+	if (st) return st;
+	pc_joint_unpack(joint, sum, 2, cells_sq, outside_sq);
 	return PC_HIP_OK;
 }
 

@@ -184,18 +184,26 @@ static inline bool pc_select_parse(const char *value, pc_hip_select_cut *cuts, i
  * the lanes of one energy are summed across the wave (shuffles), the waves in LDS, and the workgroup adds its sums with one 64-bit
  * atomic per energy and sum: per workgroup, not per entry -- every entry would hit the same few addresses.
  * Every chunk loads its entries and evaluates the cuts again for the verdicts (a few fields next to the 64 weights per entry it reads).
- * tot: n_pass, a spare word, passed_w [ne], rejected_w [ne]. */
+ * tot: n_pass, a spare word, passed_w [ne], rejected_w [ne].
+ * Q: the selection tracks squares.  Every lane also keeps the sums of W*W (pc_tally_sq) of its passing and of its rejected entries as
+ * two (lo, hi) pairs in registers, and they take the same way: shuffles and LDS with carry, then one pc_atomic_add128 per workgroup,
+ * energy and sum into tot2: passed_w2 [ne][2], rejected_w2 [ne][2].  The build without reads no tot2. */
 #define PC_SELECT_BLOCK 256
-__global__ void __launch_bounds__(PC_SELECT_BLOCK) pc_select_kernel(pc_spot_src s, pc_select_geo g, int ne, unsigned char *mask, unsigned long long *tot)
+template <bool Q>
+__global__ void __launch_bounds__(PC_SELECT_BLOCK) pc_select_kernel(pc_spot_src s, pc_select_geo g, int ne, unsigned char *mask, unsigned long long *tot,
+	unsigned long long *tot2)
 {
-	__shared__ unsigned long long red[2*64 + 1];
+	constexpr int NRED = 2*64 + 1 + (Q ? 4*64 : 0);
+	__shared__ unsigned long long red[NRED];
+	unsigned long long *red2 = red + 2*64 + 1;      /* passed [64][2], rejected [64][2], Q only */
 	const int e0 = blockIdx.y*64;
 	const int en = (ne - e0 < 64) ? ne - e0 : 64;
-	for (int k = threadIdx.x; k < 2*64 + 1; k += blockDim.x) red[k] = 0ull;
+	for (int k = threadIdx.x; k < NRED; k += blockDim.x) red[k] = 0ull;
 	__syncthreads();
 	const int gw = pc_tally_gw(en), lane = threadIdx.x & 63, sub = lane & (gw - 1), per = 64 / gw;
 	const long long wave = ((long long)blockIdx.x*blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x*blockDim.x) >> 6;
 	unsigned long long acc_p = 0ull, acc_r = 0ull, n_pass = 0ull;
+	unsigned long long p2_lo = 0ull, p2_hi = 0ull, r2_lo = 0ull, r2_hi = 0ull;
 	for (long long base = wave*64; base < s.n; base += n_waves*64) {       /* uniform over the wave */
 		const long long i = base + lane;
 		int pass = 0;
@@ -212,24 +220,41 @@ __global__ void __launch_bounds__(PC_SELECT_BLOCK) pc_select_kernel(pc_spot_src 
 				const int j = t*per + lane / gw;
 				if (base + j >= s.n) break;
 				const unsigned long long q = pc_spot_q(s.w[(base + j)*s.ws + e0 + sub]);
-				if ((verdicts >> j) & 1ull) acc_p += q;
-				else acc_r += q;
+				unsigned long long q2_lo = 0ull, q2_hi = 0ull;
+				if (Q) pc_tally_sq(q, q2_lo, q2_hi);
+				if ((verdicts >> j) & 1ull) {
+					acc_p += q;
+					if (Q) pc_add128(p2_lo, p2_hi, q2_lo, q2_hi);
+				} else {
+					acc_r += q;
+					if (Q) pc_add128(r2_lo, r2_hi, q2_lo, q2_hi);
+				}
 			}
 	}
 	/* lanes lane ^ gw, lane ^ 2gw, ... have the same energy */
 	for (int off = gw; off < 64; off <<= 1) {
 		acc_p += __shfl_xor(acc_p, off);
 		acc_r += __shfl_xor(acc_r, off);
+		if (Q) {
+			const unsigned long long a_lo = __shfl_xor(p2_lo, off), a_hi = __shfl_xor(p2_hi, off);
+			const unsigned long long b_lo = __shfl_xor(r2_lo, off), b_hi = __shfl_xor(r2_hi, off);
+			pc_add128(p2_lo, p2_hi, a_lo, a_hi);
+			pc_add128(r2_lo, r2_hi, b_lo, b_hi);
+		}
 	}
 	if (lane < gw && sub < en) {
 		if (acc_p) atomicAdd(&red[sub], acc_p);
 		if (acc_r) atomicAdd(&red[64 + sub], acc_r);
+		if (Q && (p2_lo | p2_hi)) pc_atomic_add128(&red2[2*sub], p2_lo, p2_hi);
+		if (Q && (r2_lo | r2_hi)) pc_atomic_add128(&red2[2*64 + 2*sub], r2_lo, r2_hi);
 	}
 	if (lane == 0 && n_pass) atomicAdd(&red[128], n_pass);
 	__syncthreads();
 	for (int k = threadIdx.x; k < en; k += blockDim.x) {
 		if (red[k]) atomicAdd(tot + 2 + e0 + k, red[k]);
 		if (red[64 + k]) atomicAdd(tot + 2 + ne + e0 + k, red[64 + k]);
+		if (Q && (red2[2*k] | red2[2*k + 1])) pc_atomic_add128(tot2 + 2*(e0 + k), red2[2*k], red2[2*k + 1]);
+		if (Q && (red2[2*64 + 2*k] | red2[2*64 + 2*k + 1])) pc_atomic_add128(tot2 + 2*(ne + e0 + k), red2[2*64 + 2*k], red2[2*64 + 2*k + 1]);
 	}
 	if (threadIdx.x == 0 && blockIdx.y == 0 && red[128]) atomicAdd(tot, red[128]);
 }
@@ -239,6 +264,7 @@ struct pc_select_member {
 	pc_hip_ctx *ctx = nullptr;
 	pc_dev_buf<unsigned char> d_mask[3];
 	pc_dev_buf<unsigned long long> d_tot;       /* [3][2 + 2 ne] */
+	pc_dev_buf<unsigned long long> d_tot2;      /* [3][2][ne][2]: passed_w2, rejected_w2 as (lo, hi) pairs, where the selection tracks squares */
 	long long n[3] = {0, 0, 0};                  /* entries the mask of a kind covers */
 	long long n_pass[3] = {0, 0, 0};             /* of which pass (once fetched) */
 	unsigned long long epoch[3] = {0, 0, 0};     /* ctx->entries_epoch the mask of a kind was made at */
@@ -253,6 +279,8 @@ struct pc_hip_select {
 	int applied[3] = {0, 0, 0};
 	int fetched[3] = {0, 0, 0};                  /* the totals of the kind are on the host */
 	std::vector<unsigned long long> tot;         /* [3][2 + 2 ne], summed over the members */
+	int squares = 0;                             /* every apply also sums W*W (pc_hip_select_track_squares) */
+	std::vector<unsigned long long> tot2;        /* [3][2][ne][2], summed over the members with carry */
 	~pc_hip_select();
 };
 
@@ -310,6 +338,19 @@ static int pc_select_fetch(pc_hip_select *s, int kind)
 		mb.n_pass[kind] = (long long)part[0];
 		for (size_t k = 0; k < per_kind; k++) sum[k] += part[k];
 		sum[1] += (unsigned long long)mb.n[kind];          /* n_seen */
+	}
+	if (s->squares) {
+		const size_t per2 = 4*(size_t)s->ne;
+		std::vector<unsigned long long> part2(per2);
+		unsigned long long *sum2 = s->tot2.data() + (size_t)kind*per2;
+		for (size_t k = 0; k < per2; k++) sum2[k] = 0ull;
+		for (pc_select_member &mb : s->m) {
+			if (mb.n[kind] == 0) continue;
+			PC_HIP_CHECK(hipSetDevice(mb.ctx->device));
+			PC_HIP_CHECK(hipMemcpyAsync(part2.data(), mb.d_tot2 + (size_t)kind*per2, per2*sizeof(unsigned long long), hipMemcpyDeviceToHost, mb.ctx->stream));
+			PC_HIP_CHECK(hipStreamSynchronize(mb.ctx->stream));
+			for (size_t k = 0; k < per2; k += 2) pc_add128(sum2[k], sum2[k + 1], part2[k], part2[k + 1]);
+		}
 	}
 	s->fetched[kind] = 1;
 	return PC_HIP_OK;
@@ -391,11 +432,13 @@ int pc_hip_select_apply(pc_hip_select *sel, int kind)
 		st = mb.d_mask[kind].grow((size_t)src[k].n, "pc_hip_select_apply: could not allocate the mask");
 		if (st) return st;
 		unsigned long long *tot = mb.d_tot + (size_t)kind*per_kind;
+		unsigned long long *tot2 = sel->squares ? mb.d_tot2 + (size_t)kind*4*(size_t)sel->ne : nullptr;
 		PC_HIP_CHECK(hipMemsetAsync(tot, 0, per_kind*sizeof(unsigned long long), c->stream));
+		if (tot2) PC_HIP_CHECK(hipMemsetAsync(tot2, 0, 4*(size_t)sel->ne*sizeof(unsigned long long), c->stream));
 		const long long chunks = (sel->ne + 63)/64;
 		const long long bx = pc_tally_grid_cap((8ll*c->n_cu + chunks - 1)/chunks, src[k].n, PC_SELECT_BLOCK);
-		hipLaunchKernelGGL(pc_select_kernel, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_SELECT_BLOCK), 0, c->stream, src[k], sel->geo, sel->ne,
-		                   (unsigned char *)mb.d_mask[kind], tot);
+		hipLaunchKernelGGL(tot2 ? pc_select_kernel<true> : pc_select_kernel<false>, dim3((unsigned)bx, (unsigned)chunks), dim3(PC_SELECT_BLOCK), 0, c->stream,
+		                   src[k], sel->geo, sel->ne, (unsigned char *)mb.d_mask[kind], tot, tot2);
 		PC_HIP_CHECK(hipGetLastError());
 		mb.n[kind] = src[k].n;
 		mb.epoch[kind] = c->entries_epoch;
@@ -420,6 +463,53 @@ int pc_hip_select_read(pc_hip_select *sel, int64_t *n_pass, int64_t *n_seen, uin
 		for (size_t e = 0; e < ne; e++) {
 			if (passed_w) passed_w[kind*ne + e] = have ? t[2 + e] : 0;
 			if (rejected_w) rejected_w[kind*ne + e] = have ? t[2 + ne + e] : 0;
+		}
+	}
+	return PC_HIP_OK;
+}
+
+int pc_hip_select_track_squares(pc_hip_select *sel)
+{
+	static const char *who = "pc_hip_select_track_squares";
+	if (!sel) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_select_track_squares: select must not be NULL");
+	if (sel->applied[0] | sel->applied[1] | sel->applied[2])
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_select_track_squares: squares can be tracked only before the selection is applied for the first time");
+	if (sel->squares) return PC_HIP_OK;
+	const size_t n = 3*4*(size_t)sel->ne;
+	int st = PC_HIP_OK;
+	for (pc_select_member &mb : sel->m) {
+		st = pc_tally_hip(hipSetDevice(mb.ctx->device), who);
+		if (!st) st = mb.d_tot2.grow(n, "pc_hip_select_track_squares: could not allocate the totals of the squares");
+		if (st) break;
+	}
+	if (st) {
+		for (pc_select_member &mb : sel->m) {
+			(void)hipSetDevice(mb.ctx->device);
+			mb.d_tot2.reset();
+		}
+		return st;
+	}
+	sel->tot2.assign(n, 0ull);
+	sel->squares = 1;
+	return PC_HIP_OK;
+}
+
+int pc_hip_select_read_squares(pc_hip_select *sel, uint64_t *passed_w2, uint64_t *rejected_w2)
+{
+	if (!sel) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_select_read_squares: select must not be NULL");
+	if (!sel->squares)
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_select_read_squares: the selection does not track squares (pc_hip_select_track_squares before the first apply)");
+	const size_t ne = (size_t)sel->ne;
+	for (int kind = 0; kind < 3; kind++) {
+		if (sel->applied[kind]) {
+			const int st = pc_select_fetch(sel, kind);
+			if (st) return st;
+		}
+		const bool have = sel->applied[kind] != 0;
+		const unsigned long long *t = sel->tot2.data() + (size_t)kind*4*ne;
+		for (size_t k = 0; k < 2*ne; k++) {
+			if (passed_w2) passed_w2[kind*2*ne + k] = have ? t[k] : 0;
+			if (rejected_w2) rejected_w2[kind*2*ne + k] = have ? t[2*ne + k] : 0;
 		}
 	}
 	return PC_HIP_OK;

@@ -63,16 +63,20 @@ static __device__ __forceinline__ long long pc_spot_entry_bin(const pc_spot_src 
 /* Small maps.  The flat map [plane][energy][iy][ix] followed by the outside counters [plane][energy] is cut into tiles of
  * PC_SPOT_TILE uint64 bins; workgroup (x, y) adds the entries x, x + gridDim.x, ... that fall into tile y to a private copy of it
  * in LDS (ds_add_u64), then adds each non-zero bin of that copy to the map with one global atomic.  Maps of several tiles are
- * several passes over the entries (blockIdx.y). */
+ * several passes over the entries (blockIdx.y).  Where the squares are tracked (Q) a tile is TC = PC_SPOT_TILE / 3 bins
+ * (pc_tally_tile_cells): their weight sums in tile[0, TC), their square sums as (lo, hi) pairs behind them, flushed with
+ * pc_atomic_add128 to sq [bin][2]. */
 #define PC_SPOT_TILE 8192
 #define PC_SPOT_LDS_BLOCK 512
-template <bool M>      /* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask */
-__global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
+/* M: a gated add, s.mask is set (pc_select.h); the plain build reads no mask.  Q: the squares are tracked; the build without reads no sq */
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map, unsigned long long *sq)
 {
 	__shared__ unsigned long long tile[PC_SPOT_TILE];
+	constexpr long long TC = pc_tally_tile_cells(PC_SPOT_TILE, Q);
 	const long long nb = (long long)g.nx*g.ny, n_bins = (long long)g.np*g.ns*nb, total = n_bins + (long long)g.np*g.ns;
-	const long long t0 = (long long)blockIdx.y*PC_SPOT_TILE;
-	const long long t1 = (t0 + PC_SPOT_TILE < total) ? t0 + PC_SPOT_TILE : total;
+	const long long t0 = (long long)blockIdx.y*TC;
+	const long long t1 = (t0 + TC < total) ? t0 + TC : total;
 	for (int k = threadIdx.x; k < PC_SPOT_TILE; k += blockDim.x) tile[k] = 0ull;
 	__syncthreads();
 	for (long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x; i < s.n; i += (long long)gridDim.x*blockDim.x) {
@@ -88,14 +92,20 @@ __global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_
 			if (k_hi > g.ns) k_hi = g.ns;
 			for (long long k = k_lo; k < k_hi; k++) {
 				const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[k]]);
-				if (q) atomicAdd(&tile[base + k*step - t0], q);
+				if (q) {
+					atomicAdd(&tile[base + k*step - t0], q);
+					if (Q) pc_tally_lds_add_sq(&tile[TC + 2*(base + k*step - t0)], q);
+				}
 			}
 		}
 	}
 	__syncthreads();
 	for (long long k = threadIdx.x; k < t1 - t0; k += blockDim.x) {
 		const unsigned long long v = tile[k];
-		if (v) atomicAdd(&map[t0 + k], v);
+		if (v) {
+			atomicAdd(&map[t0 + k], v);
+			if (Q) pc_atomic_add128(sq + 2*(t0 + k), tile[TC + 2*k], tile[TC + 2*k + 1]);      /* a bin without weight has no square */
+		}
 	}
 }
 
@@ -103,17 +113,24 @@ __global__ void __launch_bounds__(PC_SPOT_LDS_BLOCK) pc_spot_lds_kernel(pc_spot_
  * the energies of one entry (64 / gw entries per wave when fewer than 64 are selected, gw = the next power of two), so that one
  * wave instruction is a contiguous run of 8-byte global atomics.  Workgroup (x, p, c) does plane p for energies
  * [c*PC_SPOT_ECHUNK, ...); the outside counters of those energies are summed in LDS first (every entry that misses the window
- * adds to the same few counters). */
+ * adds to the same few counters).  Where the squares are tracked (Q) every add to a bin is followed by pc_tally_add_sq on its pair
+ * in sq [bin][2], and the Q instance takes chunks of PC_SPOT_ECHUNK_SQ = 1024 energies: their outside counters and, behind them, the
+ * counters' pairs are 24 KiB of LDS. */
 #define PC_SPOT_ECHUNK 4096
+#define PC_SPOT_ECHUNK_SQ 1024
 #define PC_SPOT_WIDE_BLOCK 256
-template <bool M>
-__global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map)
+template <bool M, bool Q>
+__global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spot_src s, pc_spot_geo g, unsigned long long *map, unsigned long long *sq)
 {
-	__shared__ unsigned long long out[PC_SPOT_ECHUNK];
-	const int p = blockIdx.y, s0 = blockIdx.z*PC_SPOT_ECHUNK;
-	const int sn = (g.ns - s0 < PC_SPOT_ECHUNK) ? g.ns - s0 : PC_SPOT_ECHUNK;
+	constexpr int EC = Q ? PC_SPOT_ECHUNK_SQ : PC_SPOT_ECHUNK;
+	__shared__ unsigned long long out[EC*(Q ? 3 : 1)];
+	unsigned long long *out_sq = out + EC;      /* [k][2], Q only */
+	const int p = blockIdx.y, s0 = blockIdx.z*EC;
+	const int sn = (g.ns - s0 < EC) ? g.ns - s0 : EC;
 	const long long nb = (long long)g.nx*g.ny, n_bins = (long long)g.np*g.ns*nb;
 	for (int k = threadIdx.x; k < sn; k += blockDim.x) out[k] = 0ull;
+	if (Q)
+		for (int k = threadIdx.x; k < 2*sn; k += blockDim.x) out_sq[k] = 0ull;
 	__syncthreads();
 	const pc_tally_lanes l = pc_tally_lane_map(sn);
 	for (long long i = l.first; i < s.n; i += l.stride) {
@@ -123,14 +140,22 @@ __global__ void __launch_bounds__(PC_SPOT_WIDE_BLOCK) pc_spot_wide_kernel(pc_spo
 		for (int k = l.sub; k < sn; k += l.gw) {
 			const unsigned long long q = pc_spot_q(s.w[i*s.ws + g.sel[s0 + k]]);
 			if (!q) continue;
-			if (b >= 0) atomicAdd(cell + k, q);
-			else atomicAdd(&out[k], q);
+			if (b >= 0) {
+				atomicAdd(cell + k, q);
+				if (Q) pc_tally_add_sq(sq + 2*((cell - map) + k), q);
+			} else {
+				atomicAdd(&out[k], q);
+				if (Q) pc_tally_lds_add_sq(&out_sq[2*k], q);
+			}
 		}
 	}
 	__syncthreads();
 	for (int k = threadIdx.x; k < sn; k += blockDim.x) {
 		const unsigned long long v = out[k];
-		if (v) atomicAdd(&map[n_bins + (long long)p*g.ns + s0 + k], v);
+		if (v) {
+			atomicAdd(&map[n_bins + (long long)p*g.ns + s0 + k], v);
+			if (Q) pc_atomic_add128(sq + 2*(n_bins + (long long)p*g.ns + s0 + k), out_sq[2*k], out_sq[2*k + 1]);
+		}
 	}
 }
 
@@ -179,18 +204,40 @@ static int pc_spot_launch(pc_hip_spot *sp, pc_tally_member &m, const pc_spot_src
 	g.zp = m.d_zp; g.sel = m.d_sel;
 	g.x0 = sp->x0; g.x1 = sp->x1; g.y0 = sp->y0; g.y1 = sp->y1;
 	g.nx = sp->nx; g.ny = sp->ny; g.np = sp->np; g.ns = sp->ns;
+	unsigned long long *sq = sp->squares ? m.d_sq.p : nullptr;
 	if (!sp->wide) {
-		const long long tiles = ((long long)sp->elems + PC_SPOT_TILE - 1)/PC_SPOT_TILE;
+		const long long tiles = pc_tally_tile_split((long long)sp->elems, PC_SPOT_TILE, sp->squares).tiles;
 		const long long bx = pc_tally_grid_tiles(c->n_cu, tiles, s.n, PC_SPOT_LDS_BLOCK).bx;
-		auto kern = s.mask ? pc_spot_lds_kernel<true> : pc_spot_lds_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_cells);
+		auto kern = sq ? (s.mask ? pc_spot_lds_kernel<true, true> : pc_spot_lds_kernel<false, true>)
+		               : (s.mask ? pc_spot_lds_kernel<true, false> : pc_spot_lds_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)tiles), dim3(PC_SPOT_LDS_BLOCK), 0, c->stream, s, g, m.d_cells.p, sq);
 	} else {
-		const long long chunks = (sp->ns + PC_SPOT_ECHUNK - 1)/PC_SPOT_ECHUNK;
+		const int ec = sq ? PC_SPOT_ECHUNK_SQ : PC_SPOT_ECHUNK;
+		const long long chunks = (sp->ns + ec - 1)/ec;
 		const long long bx = pc_tally_grid_wide(c->n_cu, sp->np*chunks, sp->ns, s.n, PC_SPOT_WIDE_BLOCK).bx;
-		auto kern = s.mask ? pc_spot_wide_kernel<true> : pc_spot_wide_kernel<false>;
-		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_cells);
+		auto kern = sq ? (s.mask ? pc_spot_wide_kernel<true, true> : pc_spot_wide_kernel<false, true>)
+		               : (s.mask ? pc_spot_wide_kernel<true, false> : pc_spot_wide_kernel<false, false>);
+		hipLaunchKernelGGL(kern, dim3((unsigned)bx, (unsigned)sp->np, (unsigned)chunks), dim3(PC_SPOT_WIDE_BLOCK), 0, c->stream, s, g, m.d_cells.p, sq);
 	}
 	return PC_HIP_OK;
+}
+
+/* the members' summed bins (limbs = 1) or square pairs (limbs = 2) from the device layout into bins [np][ns][ny][nx][limbs] and
+ * outside [np][ns][limbs]; either may be NULL */
+static void pc_spot_unpack(const pc_hip_spot *spot, const std::vector<unsigned long long> &sum, size_t limbs, uint64_t *bins, uint64_t *outside)
+{
+	const size_t nb = (size_t)spot->nx*spot->ny, n_bins = (size_t)spot->np*spot->ns*nb, n_out = (size_t)spot->np*spot->ns;
+	if (bins) {
+		if (!spot->wide)
+			memcpy(bins, sum.data(), limbs*n_bins*sizeof(uint64_t));
+		else      /* [plane][iy][ix][energy] -> [plane][energy][iy][ix] */
+			for (int p = 0; p < spot->np; p++)
+				for (size_t b = 0; b < nb; b++)
+					for (int s = 0; s < spot->ns; s++)
+						for (size_t l = 0; l < limbs; l++)
+							bins[limbs*(((size_t)p*spot->ns + s)*nb + b) + l] = sum[limbs*(((size_t)p*nb + b)*spot->ns + s) + l];
+	}
+	if (outside) memcpy(outside, sum.data() + limbs*n_bins, limbs*n_out*sizeof(uint64_t));
 }
 
 extern "C" {
@@ -246,21 +293,27 @@ int pc_hip_spot_add(pc_hip_spot *spot, int kind)
 int pc_hip_spot_read(pc_hip_spot *spot, uint64_t *bins, uint64_t *outside, int64_t *n_entries)
 {
 	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_read: spot must not be NULL");
-	const size_t nb = (size_t)spot->nx*spot->ny, n_bins = (size_t)spot->np*spot->ns*nb, n_out = (size_t)spot->np*spot->ns;
 	std::vector<unsigned long long> sum;
 	const int st = pc_tally_sum(*spot, 1, sum);
 	if (st) return st;
-	if (bins) {
-		if (!spot->wide)
-			memcpy(bins, sum.data(), n_bins*sizeof(uint64_t));
-		else      /* [plane][iy][ix][energy] -> [plane][energy][iy][ix] */
-			for (int p = 0; p < spot->np; p++)
-				for (size_t b = 0; b < nb; b++)
-					for (int s = 0; s < spot->ns; s++)
-						bins[((size_t)p*spot->ns + s)*nb + b] = sum[((size_t)p*nb + b)*spot->ns + s];
-	}
-	if (outside) memcpy(outside, sum.data() + n_bins, n_out*sizeof(uint64_t));
+	pc_spot_unpack(spot, sum, 1, bins, outside);
 	if (n_entries) *n_entries = spot->n_entries[0] + spot->n_entries[1] + spot->n_entries[2];
+	return PC_HIP_OK;
+}
+
+int pc_hip_spot_track_squares(pc_hip_spot *spot)
+{
+	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_track_squares: spot must not be NULL");
+	return pc_tally_track_squares(*spot, "pc_hip_spot_track_squares");
+}
+
+int pc_hip_spot_read_squares(pc_hip_spot *spot, uint64_t *bins_sq, uint64_t *outside_sq)
+{
+	if (!spot) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_spot_read_squares: spot must not be NULL");
+	std::vector<unsigned long long> sum;
+	const int st = pc_tally_sum_squares(*spot, "pc_hip_spot_read_squares", sum);
+	if (st) return st;
+	pc_spot_unpack(spot, sum, 2, bins_sq, outside_sq);
 	return PC_HIP_OK;
 }
 

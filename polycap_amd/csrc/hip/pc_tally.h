@@ -4,14 +4,18 @@
  * event lists), accumulated exactly into uint64 cells, per kind, per member of a device group.  Here is the one copy of the
  * energy selection, the grid sizing, the 128-bit carry add, the entry source and its loader, the lane mapping of the
  * energies-across-lanes kernels, and the object's lifetime, add, read-back sum and reset.  A tally's own header keeps its per-entry
- * arithmetic, kernels, cell layout and host formulas.
+ * arithmetic, kernels, cell layout and host formulas.  Here too is what the standard errors of the tallies need (include/polycap-hip.h):
+ * the square of an entry's quantised weight as a (lo, hi) pair, its adds in LDS and in global memory, the split of the cells into LDS
+ * tiles with and without the pairs, the second buffer of a member and the two host estimators.
  *
  * The first part (plain functions, no HIP types) compiles for the host as well: -DPC_TALLY_HOST_ONLY stops the header after it.
  */
 #ifndef PC_TALLY_H
 #define PC_TALLY_H
 
+#include <math.h>
 #include <stddef.h>
+#include <stdint.h>
 #include <string>
 #include <vector>
 
@@ -84,6 +88,25 @@ static inline pc_tally_grid pc_tally_grid_tiles(long long cus, long long tiles, 
 	return g;
 }
 
+/* Cells of one LDS tile of `tile` uint64, and the tiles that `total` cells take.  A tile holds `tile` weight cells; where the squares
+ * are tracked (squares != 0) a cell is three uint64 -- its weight sum and the (lo, hi) pair of its square sum -- and a tile holds
+ * tile / 3 cells: [cells] weight sums, then [cells][2] pairs. */
+struct pc_tally_tiling {
+	long long cells, tiles;
+};
+
+static inline constexpr __host__ __device__ long long pc_tally_tile_cells(long long tile, int squares)
+{
+	return squares ? tile/3 : tile;
+}
+
+static inline pc_tally_tiling pc_tally_tile_split(long long total, long long tile, int squares)
+{
+	const long long cells = pc_tally_tile_cells(tile, squares);
+	const pc_tally_tiling t = { cells, (total + cells - 1)/cells };
+	return t;
+}
+
 /* energies-across-lanes kernels, gw lanes per entry and `groups` workgroups for every gridDim.x: eight workgroups per CU in all */
 static inline pc_tally_grid pc_tally_grid_wide(long long cus, long long groups, int n_sel, long long n_entries, int block)
 {
@@ -100,7 +123,72 @@ static inline __host__ __device__ void pc_add128(unsigned long long &lo, unsigne
 	hi += add_hi + (lo < o ? 1ull : 0ull);
 }
 
+/* The square of one entry's quantised weight W = pc_spot_q(w) <= 2^32: the integer product W*W <= 2^64 in units of 2^-64, as
+ * lo = W*W mod 2^64 and hi = the product's upper half (1 for W = 2^32 only) */
+static inline __host__ __device__ void pc_tally_sq(unsigned long long W, unsigned long long &lo, unsigned long long &hi)
+{
+	lo = W*W;
+#ifdef __HIP_DEVICE_COMPILE__
+	hi = __umul64hi(W, W);
+#else
+	hi = (unsigned long long)(((unsigned __int128)W*W) >> 64);
+#endif
+}
+
+/* pc_hip_tally_stderr: the formula of include/polycap-hip.h in its order */
+static inline void pc_tally_stderr(size_t n_cells, const uint64_t *sums, const uint64_t *squares, int64_t n_started, double *out)
+{
+	const long double n = (long double)n_started;
+	for (size_t k = 0; k < n_cells; k++) {
+		if (!(n >= 2.0L)) { out[k] = NAN; continue; }
+		const long double a = (long double)sums[k];
+		const long double b = (long double)squares[2*k + 1] * 18446744073709551616.0L + (long double)squares[2*k];
+		const long double m = a / (n * 4294967296.0L), q = b / (n * 18446744073709551616.0L);
+		long double v = q - m*m;
+		if (v < 0.0L) v = 0.0L;
+		out[k] = (double)sqrtl(v / (n - 1.0L));
+	}
+}
+
+/* pc_hip_select_transmission: the formula of include/polycap-hip.h in its order */
+static inline void pc_tally_transmission(size_t n_energies, const uint64_t *passed_w, const uint64_t *rejected_w, const uint64_t *passed_w2,
+	const uint64_t *rejected_w2, double *T, double *T_err)
+{
+	for (size_t e = 0; e < n_energies; e++) {
+		const long double P = (long double)passed_w[e] / 4294967296.0L, R = (long double)rejected_w[e] / 4294967296.0L;
+		const long double P2 = ((long double)passed_w2[2*e + 1] * 18446744073709551616.0L + (long double)passed_w2[2*e]) / 18446744073709551616.0L;
+		const long double R2 = ((long double)rejected_w2[2*e + 1] * 18446744073709551616.0L + (long double)rejected_w2[2*e]) / 18446744073709551616.0L;
+		const long double tot = P + R;
+		if (!(tot > 0.0L)) {
+			if (T) T[e] = NAN;
+			if (T_err) T_err[e] = NAN;
+			continue;
+		}
+		if (T) T[e] = (double)(P / tot);
+		if (T_err) T_err[e] = (double)(sqrtl(R*R*P2 + P*P*R2) / (tot*tot));
+	}
+}
+
 #ifndef PC_TALLY_HOST_ONLY
+
+/* W*W of one entry added to a (lo, hi) pair in LDS: ds_add_u64 on lo, the carry from the old value it returns, and with it the
+ * product's own upper half on hi.  Adds commute, so the pair is exact in whatever order the lanes arrive. */
+static __device__ __forceinline__ void pc_tally_lds_add_sq(unsigned long long *lohi, unsigned long long W)
+{
+	unsigned long long lo, hi;
+	pc_tally_sq(W, lo, hi);
+	const unsigned long long old = atomicAdd(&lohi[0], lo);
+	hi += (old + lo < old) ? 1ull : 0ull;
+	if (hi) atomicAdd(&lohi[1], hi);
+}
+
+/* the same on a pair of global cells: two 8-byte atomics at the most */
+static __device__ __forceinline__ void pc_tally_add_sq(unsigned long long *lohi, unsigned long long W)
+{
+	unsigned long long lo, hi;
+	pc_tally_sq(W, lo, hi);
+	pc_atomic_add128(lohi, lo, hi);
+}
 
 /* Where the entries are: field f of entry i at p[i*ss + f*fs], weight e at w[i*ws + e] */
 struct pc_spot_src {
@@ -182,6 +270,7 @@ static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s, const char *w
 struct pc_tally_member {
 	pc_hip_ctx *ctx = nullptr;
 	pc_dev_buf<unsigned long long> d_cells;
+	pc_dev_buf<unsigned long long> d_sq;           /* [elems][2]: the cells' square sums as (lo, hi) pairs, where the tally tracks them */
 	pc_dev_buf<int> d_sel;          /* the selected energies' indices, where the tally selects */
 	pc_dev_buf<double> d_zp;        /* plane positions, where it has planes */
 };
@@ -192,6 +281,7 @@ struct pc_tally {
 	long long n_entries[3] = {0, 0, 0};       /* added so far, per kind */
 	size_t elems = 0;                         /* cells of a member */
 	int shared = 0;                           /* the kinds add to the same cells: the entry cap holds for them together */
+	int squares = 0;                          /* every add fills d_sq beside d_cells (pc_tally_track_squares) */
 	~pc_tally();
 };
 
@@ -231,6 +321,34 @@ static int pc_tally_make(pc_tally &t, const std::vector<pc_hip_ctx *> &ctxs, pc_
 		if (!st) st = pc_tally_hip(hipMemsetAsync(m.d_cells, 0, elems*sizeof(unsigned long long), c->stream), who);
 		if (st) { pc_tally_destroy(t); return st; }
 	}
+	return PC_HIP_OK;
+}
+
+/* Turns the tracking of squares on: zeroed pairs beside the cells of every member.  Only while the tally holds no entries; refused
+ * (PC_HIP_ERR_INVALID) otherwise, and nothing stays allocated and nothing is changed when it fails. */
+static int pc_tally_track_squares(pc_tally &t, const char *who)
+{
+	const std::string w(who);
+	if (t.n_entries[0] | t.n_entries[1] | t.n_entries[2])
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": squares can be tracked only while the object holds no entries (before the first add, or after a reset)");
+	if (t.squares) return PC_HIP_OK;
+	const std::string msg = w + ": could not allocate the square cells";
+	int st = PC_HIP_OK;
+	for (pc_tally_member &m : t.m) {
+		st = pc_tally_hip(hipSetDevice(m.ctx->device), who);
+		if (!st) st = m.d_sq.grow(2*t.elems, msg.c_str());
+		if (!st) st = pc_tally_hip(hipMemsetAsync(m.d_sq, 0, 2*t.elems*sizeof(unsigned long long), m.ctx->stream), who);
+		if (st) break;
+	}
+	if (st) {
+		for (pc_tally_member &m : t.m) {
+			(void)hipSetDevice(m.ctx->device);
+			(void)hipStreamSynchronize(m.ctx->stream);
+			m.d_sq.reset();
+		}
+		return st;
+	}
+	t.squares = 1;
 	return PC_HIP_OK;
 }
 
@@ -313,22 +431,37 @@ static int pc_tally_add(pc_tally &t, int kind, const char *who, Launch launch, p
 	return PC_HIP_OK;
 }
 
-/* The members' cells summed on the host.  limbs = 1: uint64 cells; 2: (lo, hi) pairs with carry.  Exact either way: the entry cap
- * keeps every sum in range. */
-static int pc_tally_sum(pc_tally &t, int limbs, std::vector<unsigned long long> &sum)
+/* One buffer of n uint64 of every member, summed on the host.  limbs = 1: uint64 cells; 2: (lo, hi) pairs with carry.  Exact either
+ * way: the entry cap keeps every sum in range. */
+static int pc_tally_sum_of(pc_tally &t, pc_dev_buf<unsigned long long> pc_tally_member::*buf, size_t n, int limbs, std::vector<unsigned long long> &sum)
 {
-	std::vector<unsigned long long> part(t.elems);
-	sum.assign(t.elems, 0ull);
+	std::vector<unsigned long long> part(n);
+	sum.assign(n, 0ull);
 	for (pc_tally_member &m : t.m) {
 		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
-		PC_HIP_CHECK(hipMemcpyAsync(part.data(), m.d_cells, t.elems*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
+		const unsigned long long *d = (m.*buf).p;
+		PC_HIP_CHECK(hipMemcpyAsync(part.data(), d, n*sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ctx->stream));
 		PC_HIP_CHECK(hipStreamSynchronize(m.ctx->stream));
 		if (limbs == 2)
-			for (size_t k = 0; k < t.elems; k += 2) pc_add128(sum[k], sum[k + 1], part[k], part[k + 1]);
+			for (size_t k = 0; k < n; k += 2) pc_add128(sum[k], sum[k + 1], part[k], part[k + 1]);
 		else
-			for (size_t k = 0; k < t.elems; k++) sum[k] += part[k];
+			for (size_t k = 0; k < n; k++) sum[k] += part[k];
 	}
 	return PC_HIP_OK;
+}
+
+/* the members' cells */
+static int pc_tally_sum(pc_tally &t, int limbs, std::vector<unsigned long long> &sum)
+{
+	return pc_tally_sum_of(t, &pc_tally_member::d_cells, t.elems, limbs, sum);
+}
+
+/* the summed square pairs of a tally that tracks them; `who` is the call that asks */
+static int pc_tally_sum_squares(pc_tally &t, const char *who, std::vector<unsigned long long> &sum)
+{
+	if (!t.squares)
+		return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": the object does not track squares (turn it on with its _track_squares call before the first add)");
+	return pc_tally_sum_of(t, &pc_tally_member::d_sq, 2*t.elems, 2, sum);
 }
 
 static int pc_tally_reset(pc_tally &t)
@@ -336,10 +469,26 @@ static int pc_tally_reset(pc_tally &t)
 	for (pc_tally_member &m : t.m) {
 		PC_HIP_CHECK(hipSetDevice(m.ctx->device));
 		PC_HIP_CHECK(hipMemsetAsync(m.d_cells, 0, t.elems*sizeof(unsigned long long), m.ctx->stream));
+		if (t.squares) PC_HIP_CHECK(hipMemsetAsync(m.d_sq, 0, 2*t.elems*sizeof(unsigned long long), m.ctx->stream));
 	}
 	for (int k = 0; k < 3; k++) t.n_entries[k] = 0;
 	return PC_HIP_OK;
 }
+
+extern "C" {
+
+void pc_hip_tally_stderr(size_t n_cells, const uint64_t *sums, const uint64_t *squares, int64_t n_started, double *out)
+{
+	pc_tally_stderr(n_cells, sums, squares, n_started, out);
+}
+
+void pc_hip_select_transmission(size_t n_energies, const uint64_t *passed_w, const uint64_t *rejected_w, const uint64_t *passed_w2,
+	const uint64_t *rejected_w2, double *T, double *T_err)
+{
+	pc_tally_transmission(n_energies, passed_w, rejected_w, passed_w2, rejected_w2, T, T_err);
+}
+
+} /* extern "C" */
 
 #endif /* PC_TALLY_HOST_ONLY */
 #endif /* PC_TALLY_H */

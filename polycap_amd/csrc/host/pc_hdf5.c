@@ -225,6 +225,35 @@ fail:
 	return ok;
 }
 
+/* extension, POLYCAP_TALLY_STDERR=1: beside a bins or cells dataset `stem` of `rank` dimensions `dim` its squares (uint64, a trailing
+ * dimension 2) and its standard errors (double; pc_hip_tally_stderr with N = n_started); nothing when the result has none */
+static bool pc_h5_squares(pc_hid file, int rank, const pc_hsize *dim, const char *stem, const uint64_t *sums, const uint64_t *squares,
+	int64_t n_started, polycap_error **error)
+{
+	if (squares == NULL)
+		return true;
+	char name[96];
+	pc_hsize d[5] = { 1, 1, 1, 1, 2 };
+	size_t n = 1;
+	for (int k = 0; k < rank; k++) {
+		d[k] = dim[k];
+		n *= (size_t)dim[k];
+	}
+	d[rank] = 2;
+	double *err = malloc(sizeof(double) * (n ? n : 1));
+	if (err == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "polycap_transmission_efficiencies_write_hdf5: could not allocate memory -> %s", strerror(errno));
+		return false;
+	}
+	pc_hip_tally_stderr(n, sums, squares, n_started, err);
+	snprintf(name, sizeof name, "%s_Squares", stem);
+	bool ok = pc_h5_typed(file, rank + 1, d, name, *h5.native_ullong, squares, "2^-64", "lo,hi", error);
+	snprintf(name, sizeof name, "%s_StdErr", stem);
+	ok = ok && pc_h5_typed(file, rank, d, name, *h5.native_double, err, "weight per started photon", NULL, error);
+	free(err);
+	return ok;
+}
+
 /* planes[k][0..n) stacked into one [nplanes, n] dataset */
 static bool pc_h5_planes(pc_hid file, const char *name, int nplanes, double *const *planes, size_t n, const char *units, double *tmp,
 	polycap_error **error)
@@ -387,6 +416,10 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 			sok = sok && pc_h5_dataset(file, 4, sd, name, sp->maps[k], "a.u.", error);
 			snprintf(name, sizeof name, "/Spot/%s_Outside", names[k]);
 			sok = sok && pc_h5_dataset(file, 2, sd, name, sp->outside[k], "a.u.", error);
+			snprintf(name, sizeof name, "/Spot/%s", names[k]);
+			sok = sok && pc_h5_squares(file, 4, sd, name, sp->sq[k].sums, sp->sq[k].squares, efficiencies->tally_n_started, error);
+			snprintf(name, sizeof name, "/Spot/%s_Outside", names[k]);
+			sok = sok && pc_h5_squares(file, 2, sd, name, sp->sq[k].outside, sp->sq[k].outside_squares, efficiencies->tally_n_started, error);
 		}
 		free(sel_e);
 		if (!sok) goto close;
@@ -453,9 +486,11 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 			hd[0] = (pc_hsize)ns; hd[1] = (pc_hsize)tb;
 			snprintf(name, sizeof name, "%s/Bins", g);
 			hok = hok && pc_h5_typed(file, 2, hd, name, *h5.native_ullong, hr->bins[k], "2^-32", NULL, error);
+			hok = hok && pc_h5_squares(file, 2, hd, name, hr->bins[k], hr->sq[k].squares, efficiencies->tally_n_started, error);
 			hd[0] = (pc_hsize)na; hd[1] = (pc_hsize)ns;
 			snprintf(name, sizeof name, "%s/Outside", g);
 			hok = hok && pc_h5_typed(file, 2, hd, name, *h5.native_ullong, hr->outside[k], "2^-32", NULL, error);
+			hok = hok && pc_h5_squares(file, 2, hd, name, hr->outside[k], hr->sq[k].outside_squares, efficiencies->tally_n_started, error);
 			const uint64_t n_entries = (uint64_t)hr->n_entries[k];
 			pc_hsize one = 1;
 			snprintf(name, sizeof name, "%s/Entries", g);
@@ -518,9 +553,11 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 			jd[0] = (pc_hsize)ns; jd[1] = (pc_hsize)tc;
 			snprintf(name, sizeof name, "%s/Cells", g);
 			jok = jok && pc_h5_typed(file, 2, jd, name, *h5.native_ullong, jr->cells[k], "2^-32", NULL, error);
+			jok = jok && pc_h5_squares(file, 2, jd, name, jr->cells[k], jr->sq[k].squares, efficiencies->tally_n_started, error);
 			jd[0] = (pc_hsize)np; jd[1] = (pc_hsize)ns;
 			snprintf(name, sizeof name, "%s/Outside", g);
 			jok = jok && pc_h5_typed(file, 2, jd, name, *h5.native_ullong, jr->outside[k], "2^-32", NULL, error);
+			jok = jok && pc_h5_squares(file, 2, jd, name, jr->outside[k], jr->sq[k].outside_squares, efficiencies->tally_n_started, error);
 			const uint64_t n_entries = (uint64_t)jr->n_entries[k];
 			pc_hsize one = 1;
 			snprintf(name, sizeof name, "%s/Entries", g);
@@ -568,6 +605,19 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		sd[0] = 3; sd[1] = (pc_hsize)ne;
 		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Passed", *h5.native_ullong, sr->passed_w, "2^-32", NULL, error);
 		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Rejected", *h5.native_ullong, sr->rejected_w, "2^-32", NULL, error);
+		if (sr->passed_w2 != NULL) {      /* POLYCAP_TALLY_STDERR=1 */
+			pc_hsize qd[3] = { 3, (pc_hsize)ne, 2 };
+			double *t = malloc(sizeof(double) * 6 * (ne ? ne : 1));
+			sok = sok && t != NULL;
+			for (size_t k = 0; sok && k < 3; k++)
+				pc_hip_select_transmission(ne, sr->passed_w + k*ne, sr->rejected_w + k*ne, sr->passed_w2 + 2*k*ne, sr->rejected_w2 + 2*k*ne,
+				                           t + k*ne, t + (3 + k)*ne);
+			sok = sok && pc_h5_typed(file, 3, qd, "/Select/Passed_Squares", *h5.native_ullong, sr->passed_w2, "2^-64", "lo,hi", error);
+			sok = sok && pc_h5_typed(file, 3, qd, "/Select/Rejected_Squares", *h5.native_ullong, sr->rejected_w2, "2^-64", "lo,hi", error);
+			sok = sok && pc_h5_typed(file, 2, qd, "/Select/Transmission", *h5.native_double, t, "a.u.", NULL, error);
+			sok = sok && pc_h5_typed(file, 2, qd, "/Select/Transmission_StdErr", *h5.native_double, t + 3*ne, "a.u.", NULL, error);
+			free(t);
+		}
 		uint64_t entries[6];
 		for (int k = 0; k < 3; k++) {
 			entries[2*k] = (uint64_t)sr->n_pass[k];

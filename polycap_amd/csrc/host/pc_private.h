@@ -126,6 +126,16 @@ struct _polycap_images {
 	double *intleak_coord_weights;
 };
 
+/* extension: what POLYCAP_TALLY_STDERR=1 adds to a tally's result of one kind (pc_transmission_efficiencies_get_tally_squares); all
+ * NULL without it.  sums / outside: the exact weight sums the squares belong to (a copy for the spot maps, which keep doubles only;
+ * for the other tallies the result's own arrays, not owned) */
+struct pc_squares_result {
+	size_t n_cells, n_outside;
+	uint64_t *sums, *outside;
+	int owns_sums;
+	uint64_t *squares, *outside_squares;      /* [n_cells][2], [n_outside][2] */
+};
+
 /* extension: spot maps of a run made with POLYCAP_SPOT set, in efficiency units (pc_transmission_efficiencies_get_spot) */
 struct pc_spot_result {
 	int32_t n_planes, n_sel, ny, nx;
@@ -134,6 +144,7 @@ struct pc_spot_result {
 	int32_t *sel;              /* [n_sel] energy indices */
 	double *maps[3];           /* exit photons, extleak, intleak: [plane][energy][iy][ix], NULL when the run has none */
 	double *outside[3];        /* [plane][energy] */
+	struct pc_squares_result sq[3];
 };
 
 /* extension: exact exit-beam sums of a run made with POLYCAP_BEAM=1 (pc_transmission_efficiencies_get_beam / _get_beam_sums) */
@@ -152,6 +163,7 @@ struct pc_hist_result {
 	uint64_t *bins[3];         /* exit photons, extleak, intleak: [energy][total_bins], NULL when the run has none */
 	uint64_t *outside[3];      /* [axis][energy] */
 	int64_t n_entries[3];
+	struct pc_squares_result sq[3];
 };
 
 /* extension: exact joint histograms of a run made with POLYCAP_JOINT set (pc_transmission_efficiencies_get_joint) */
@@ -163,6 +175,7 @@ struct pc_joint_result {
 	uint64_t *cells[3];        /* exit photons, extleak, intleak: [energy][total_cells], NULL when the run has none */
 	uint64_t *outside[3];      /* [pair][energy] */
 	int64_t n_entries[3];
+	struct pc_squares_result sq[3];
 };
 
 /* extension: the cuts and the exact totals of a run made with POLYCAP_SELECT set (pc_transmission_efficiencies_get_select) */
@@ -171,6 +184,7 @@ struct pc_select_result {
 	pc_hip_select_cut cuts[8];
 	int64_t n_pass[3], n_seen[3];   /* exit photons, extleak, intleak (zeros where the run has none) */
 	uint64_t *passed_w, *rejected_w; /* [3][n_energies] */
+	uint64_t *passed_w2, *rejected_w2; /* [3][n_energies][2] with POLYCAP_TALLY_STDERR=1, NULL otherwise */
 };
 
 struct _polycap_transmission_efficiencies {
@@ -190,6 +204,7 @@ struct _polycap_transmission_efficiencies {
 	int64_t n_started;
 	uint64_t *sumw_fixed, *sumw2_fixed;
 	double *stderrs;           /* [n_energies] pc_hip_efficiency_stderr of the moments */
+	int64_t tally_n_started;   /* extension: POLYCAP_TALLY_STDERR=1: counters 0 + 1 + 2 of the call, the N of the tallies' standard errors; 0 otherwise */
 };
 
 /* internal helpers */
@@ -243,5 +258,6 @@ void pc_beam_result_free(struct pc_beam_result *beam);
 void pc_hist_result_free(struct pc_hist_result *hist);
 void pc_joint_result_free(struct pc_joint_result *joint);
 void pc_select_result_free(struct pc_select_result *select);
+void pc_squares_result_free(struct pc_squares_result *sq);
 
 #endif

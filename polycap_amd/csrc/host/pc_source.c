@@ -736,7 +736,31 @@ struct pc_tallies {
 	pc_hip_select *select;
 	int64_t sel_n[6];
 	uint64_t *sel_w;               /* [2][3][ne] */
+	int squares;                   /* POLYCAP_TALLY_STDERR=1: every tally and the selection track squares */
+	uint64_t *sel_w2;              /* [2][3][ne][2] with squares: passed_w2, rejected_w2 summed over the applies with carry */
 };
+
+/* every tally of the call and its selection track squares: before the first add and the first apply */
+static int pc_tallies_track_squares(struct pc_tallies *ta, size_t ne)
+{
+	int st = PC_HIP_OK;
+	ta->squares = 1;
+	if (ta->select != NULL) {
+		ta->sel_w2 = calloc(12*ne, sizeof(uint64_t));
+		st = ta->sel_w2 == NULL ? PC_HIP_ERR_MEMORY : pc_hip_select_track_squares(ta->select);
+	}
+	for (int kind = 0; kind <= 2 && st == PC_HIP_OK; kind++)
+		if (ta->spot[kind] != NULL)
+			st = pc_hip_spot_track_squares(ta->spot[kind]);
+	if (st == PC_HIP_OK && ta->hist != NULL)
+		st = pc_hip_hist_track_squares(ta->hist);
+	if (st == PC_HIP_OK && ta->joint != NULL)
+		st = pc_hip_joint_track_squares(ta->joint);
+	return st;
+}
+
+static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne);
+static void *pc_beam_dup(const void *p, size_t bytes);
 
 /* the entries of `kind` of the last run into every tally, through the selection if there is one (applied here, its totals added) */
 static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
@@ -758,6 +782,15 @@ static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
 			}
 		}
 		free(w);
+		if (st == PC_HIP_OK && ta->squares) {
+			uint64_t *w2 = malloc(sizeof(uint64_t)*12*ne);
+			st = (w2 != NULL) ? pc_hip_select_read_squares(s, w2, w2 + 6*ne) : PC_HIP_ERR_MEMORY;
+			if (st == PC_HIP_OK) {
+				pc_fixed_add(ta->sel_w2 + 2*kind*ne, w2 + 2*kind*ne, ne);
+				pc_fixed_add(ta->sel_w2 + 6*ne + 2*kind*ne, w2 + 6*ne + 2*kind*ne, ne);
+			}
+			free(w2);
+		}
 	}
 	if (st == PC_HIP_OK && ta->spot[kind] != NULL)
 		st = s != NULL ? pc_hip_spot_add_selected(ta->spot[kind], kind, s) : pc_hip_spot_add(ta->spot[kind], kind);
@@ -848,6 +881,16 @@ static int pc_spot_store(polycap_transmission_efficiencies *eff, pc_hip_spot *sp
 	uint64_t *bins = malloc(sizeof(uint64_t)*n_out*nb), *out = malloc(sizeof(uint64_t)*n_out);
 	double *map = malloc(sizeof(double)*n_out*nb), *outside = malloc(sizeof(double)*n_out);
 	st = (bins != NULL && out != NULL && map != NULL && outside != NULL) ? pc_hip_spot_read(spot, bins, out, NULL) : PC_HIP_ERR_MEMORY;
+	if (st == PC_HIP_OK && eff->tally_n_started > 0) {      /* POLYCAP_TALLY_STDERR: the sums behind the maps, and their squares */
+		struct pc_squares_result *sq = &sp->sq[kind];
+		sq->n_cells = n_out*nb; sq->n_outside = n_out; sq->owns_sums = 1;
+		sq->sums = pc_beam_dup(bins, sizeof(uint64_t)*n_out*nb);
+		sq->outside = pc_beam_dup(out, sizeof(uint64_t)*n_out);
+		sq->squares = malloc(sizeof(uint64_t)*2*n_out*nb);
+		sq->outside_squares = malloc(sizeof(uint64_t)*2*n_out);
+		st = (sq->sums != NULL && sq->outside != NULL && sq->squares != NULL && sq->outside_squares != NULL)
+		   ? pc_hip_spot_read_squares(spot, sq->squares, sq->outside_squares) : PC_HIP_ERR_MEMORY;
+	}
 	for (size_t m = 0; st == PC_HIP_OK && m < n_out; m++) {
 		/* map = efficiency[e] * S_bin / (S_inside + S_outside): a map and its outside part sum to the efficiency */
 		uint64_t total = out[m];
@@ -893,6 +936,17 @@ static int pc_beam_store(polycap_transmission_efficiencies *eff, pc_hip_beam *be
 	return st;
 }
 
+/* the squares of one kind of a histogram or joint result beside its own sums (not owned) */
+static int pc_squares_store(struct pc_squares_result *sq, size_t n_cells, size_t n_outside, uint64_t *sums, uint64_t *outside,
+	const uint64_t *squares, const uint64_t *outside_squares)
+{
+	sq->n_cells = n_cells; sq->n_outside = n_outside;
+	sq->sums = sums; sq->outside = outside; sq->owns_sums = 0;
+	sq->squares = pc_beam_dup(squares, sizeof(uint64_t)*2*n_cells);
+	sq->outside_squares = pc_beam_dup(outside_squares, sizeof(uint64_t)*2*n_outside);
+	return (sq->squares != NULL && sq->outside_squares != NULL) ? PC_HIP_OK : PC_HIP_ERR_MEMORY;
+}
+
 /* the exact histograms of every kind the run has into the result */
 static int pc_hist_store(polycap_transmission_efficiencies *eff, pc_hip_hist *hist, const struct pc_hist_request *r, int leak_calc)
 {
@@ -925,6 +979,14 @@ static int pc_hist_store(polycap_transmission_efficiencies *eff, pc_hip_hist *hi
 	}
 	free(bins);
 	free(out);
+	if (st == PC_HIP_OK && eff->tally_n_started > 0) {      /* POLYCAP_TALLY_STDERR */
+		uint64_t *sq = malloc(sizeof(uint64_t)*2*3*ns*tb), *osq = malloc(sizeof(uint64_t)*2*3*na*ns);
+		st = (sq != NULL && osq != NULL) ? pc_hip_hist_read_squares(hist, sq, osq) : PC_HIP_ERR_MEMORY;
+		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++)
+			st = pc_squares_store(&hr->sq[kind], ns*tb, na*ns, hr->bins[kind], hr->outside[kind], sq + 2*kind*ns*tb, osq + 2*kind*na*ns);
+		free(sq);
+		free(osq);
+	}
 	return st;
 }
 
@@ -960,6 +1022,14 @@ static int pc_joint_store(polycap_transmission_efficiencies *eff, pc_hip_joint *
 	}
 	free(cells);
 	free(out);
+	if (st == PC_HIP_OK && eff->tally_n_started > 0) {      /* POLYCAP_TALLY_STDERR */
+		uint64_t *sq = malloc(sizeof(uint64_t)*2*3*ns*tc), *osq = malloc(sizeof(uint64_t)*2*3*np*ns);
+		st = (sq != NULL && osq != NULL) ? pc_hip_joint_read_squares(joint, sq, osq) : PC_HIP_ERR_MEMORY;
+		for (int kind = 0; kind <= (leak_calc ? 2 : 0) && st == PC_HIP_OK; kind++)
+			st = pc_squares_store(&jr->sq[kind], ns*tc, np*ns, jr->cells[kind], jr->outside[kind], sq + 2*kind*ns*tc, osq + 2*kind*np*ns);
+		free(sq);
+		free(osq);
+	}
 	return st;
 }
 
@@ -991,6 +1061,7 @@ static const char *pc_transmission_args_bad(const polycap_source *source, const 
  * Numbers that do not parse fall back to their defaults; out-of-range option values fail when the option is set. */
 struct pc_run_request {
 	int timing;                /* POLYCAP_TIMING: stage times on stderr */
+	int tally_stderr_on;       /* POLYCAP_TALLY_STDERR=1: the tallies and the selection of the call track squares; unset or 0: not */
 	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
 	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
 	struct pc_spot_request spot;
@@ -1026,6 +1097,12 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 		return -1;
 	}
 	r->stderr_on = stderr_env != NULL && strcmp(stderr_env, "1") == 0;
+	const char *tally_env = getenv("POLYCAP_TALLY_STDERR");
+	if (tally_env != NULL && strcmp(tally_env, "0") != 0 && strcmp(tally_env, "1") != 0) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_TALLY_STDERR=%s: must be 0 or 1", tally_env);
+		return -1;
+	}
+	r->tally_stderr_on = tally_env != NULL && strcmp(tally_env, "1") == 0;
 	const char *beam_env = getenv("POLYCAP_BEAM");
 	if (beam_env != NULL && strcmp(beam_env, "0") != 0 && strcmp(beam_env, "1") != 0) {
 		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_BEAM=%s: must be 0 or 1", beam_env);
@@ -1109,6 +1186,8 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 		st = t.group != NULL ? pc_hip_group_hist_create(t.group, &r->hist.spec, hist) : pc_hip_hist_create(t.ctx, &r->hist.spec, hist);
 	if (r->joint.set && st == PC_HIP_OK)
 		st = t.group != NULL ? pc_hip_group_joint_create(t.group, &r->joint.spec, joint) : pc_hip_joint_create(t.ctx, &r->joint.spec, joint);
+	if (r->tally_stderr_on && st == PC_HIP_OK)
+		st = pc_tallies_track_squares(ta, ne);
 	if (r->spot.set || r->beam_on || r->hist.set || r->joint.set || r->select.set) {
 		/* POLYCAP_IMAGES=0 with spot maps, beam moments or (joint) histograms is chunked on one device only: a group traces the whole run at once */
 		if (st == PC_HIP_OK && t.group == NULL && !r->keep_images && !leak_calc) {
@@ -1259,6 +1338,7 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	printf("iexit: %" PRId64 ", no enter: %" PRId64 ", no trans: %" PRId64 "\n", sum_iexit, sum_not_entered, sum_not_transmitted);
 	pc_transeff_finish(eff, sum_weights, counters);
 	eff->synthetic_constants = source->cache.synthetic;
+	eff->tally_n_started = req.tally_stderr_on ? counters[0] + counters[1] + counters[2] : 0;
 	for (int kind = 0; kind <= 2 && status == PC_HIP_OK; kind++)
 		if (spot[kind] != NULL)
 			status = pc_spot_store(eff, spot[kind], &req.spot, kind);
@@ -1281,6 +1361,12 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			sr->rejected_w = pc_beam_dup(ta.sel_w + 3*ne, sizeof(uint64_t)*3*ne);
 			if (sr->passed_w == NULL || sr->rejected_w == NULL)
 				status = PC_HIP_ERR_MEMORY;
+			if (status == PC_HIP_OK && ta.sel_w2 != NULL) {      /* POLYCAP_TALLY_STDERR */
+				sr->passed_w2 = pc_beam_dup(ta.sel_w2, sizeof(uint64_t)*6*ne);
+				sr->rejected_w2 = pc_beam_dup(ta.sel_w2 + 6*ne, sizeof(uint64_t)*6*ne);
+				if (sr->passed_w2 == NULL || sr->rejected_w2 == NULL)
+					status = PC_HIP_ERR_MEMORY;
+			}
 		}
 	}
 	if (status != PC_HIP_OK)
@@ -1311,6 +1397,7 @@ out:
 	pc_hip_joint_destroy(ta.joint);
 	pc_hip_select_destroy(ta.select);
 	free(ta.sel_w);
+	free(ta.sel_w2);
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

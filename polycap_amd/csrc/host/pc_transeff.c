@@ -214,6 +214,17 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	free(efficiencies);
 }
 
+void pc_squares_result_free(struct pc_squares_result *sq)
+{
+	if (sq->owns_sums) {
+		free(sq->sums);
+		free(sq->outside);
+	}
+	free(sq->squares);
+	free(sq->outside_squares);
+	memset(sq, 0, sizeof(*sq));
+}
+
 void pc_spot_result_free(struct pc_spot_result *spot)
 {
 	if (spot == NULL)
@@ -221,6 +232,7 @@ void pc_spot_result_free(struct pc_spot_result *spot)
 	free(spot->distances);
 	free(spot->sel);
 	for (int k = 0; k < 3; k++) {
+		pc_squares_result_free(&spot->sq[k]);
 		free(spot->maps[k]);
 		free(spot->outside[k]);
 	}
@@ -364,6 +376,7 @@ void pc_hist_result_free(struct pc_hist_result *hist)
 	free(hist->offsets);
 	free(hist->sel);
 	for (int k = 0; k < 3; k++) {
+		pc_squares_result_free(&hist->sq[k]);
 		free(hist->bins[k]);
 		free(hist->outside[k]);
 	}
@@ -426,6 +439,7 @@ void pc_joint_result_free(struct pc_joint_result *joint)
 	free(joint->offsets);
 	free(joint->sel);
 	for (int k = 0; k < 3; k++) {
+		pc_squares_result_free(&joint->sq[k]);
 		free(joint->cells[k]);
 		free(joint->outside[k]);
 	}
@@ -486,6 +500,8 @@ void pc_select_result_free(struct pc_select_result *select)
 		return;
 	free(select->passed_w);
 	free(select->rejected_w);
+	free(select->passed_w2);
+	free(select->rejected_w2);
 	free(select);
 }
 
@@ -531,6 +547,93 @@ int pc_transmission_efficiencies_get_select(void *efficiencies_, int32_t *n_cuts
 		if (n_pass != NULL) n_pass[k] = sr->n_pass[k];
 		if (n_seen != NULL) n_seen[k] = sr->n_seen[k];
 	}
+	return 1;
+}
+
+int pc_transmission_efficiencies_get_tally_squares(void *efficiencies_, int which, int kind, size_t *n_cells, size_t *n_outside,
+	uint64_t **sums, uint64_t **outside, uint64_t **squares, uint64_t **outside_squares, double **stderrs, double **outside_stderrs,
+	int64_t *n_started, void *error_)
+{
+	static const char *fn = "pc_transmission_efficiencies_get_tally_squares";
+	static const char *const vars[3] = { "POLYCAP_SPOT", "POLYCAP_HIST", "POLYCAP_JOINT" };
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || which < 0 || which > 2 || kind < 0 || kind > 2) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: efficiencies cannot be NULL, which must be 0 (spot), 1 (hist) or 2 (joint) and kind 0, 1 or 2", fn);
+		return 0;
+	}
+	const struct pc_squares_result *sq = which == 0 ? (efficiencies->spot != NULL ? &efficiencies->spot->sq[kind] : NULL)
+	                                   : which == 1 ? (efficiencies->hist != NULL ? &efficiencies->hist->sq[kind] : NULL)
+	                                                : (efficiencies->joint != NULL ? &efficiencies->joint->sq[kind] : NULL);
+	if (sq == NULL || sq->squares == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run was made without POLYCAP_TALLY_STDERR=1 or without %s, or it has no entries of this kind", fn, vars[which]);
+		return 0;
+	}
+	const size_t nc = sq->n_cells, no = sq->n_outside;
+	uint64_t *a = NULL, *b = NULL, *c = NULL, *d = NULL;
+	double *e = NULL, *f = NULL;
+	int ok = 1;
+	if (sums != NULL) ok = (a = pc_dup(sq->sums, sizeof(uint64_t)*nc)) != NULL;
+	if (outside != NULL && ok) ok = (b = pc_dup(sq->outside, sizeof(uint64_t)*no)) != NULL;
+	if (squares != NULL && ok) ok = (c = pc_dup(sq->squares, sizeof(uint64_t)*2*nc)) != NULL;
+	if (outside_squares != NULL && ok) ok = (d = pc_dup(sq->outside_squares, sizeof(uint64_t)*2*no)) != NULL;
+	if (stderrs != NULL && ok) ok = (e = malloc(sizeof(double)*(nc ? nc : 1))) != NULL;
+	if (outside_stderrs != NULL && ok) ok = (f = malloc(sizeof(double)*(no ? no : 1))) != NULL;
+	if (!ok) {
+		free(a); free(b); free(c); free(d); free(e); free(f);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "%s: could not allocate memory -> %s", fn, strerror(errno));
+		return 0;
+	}
+	if (e != NULL) pc_hip_tally_stderr(nc, sq->sums, sq->squares, efficiencies->tally_n_started, e);
+	if (f != NULL) pc_hip_tally_stderr(no, sq->outside, sq->outside_squares, efficiencies->tally_n_started, f);
+	if (n_cells != NULL) *n_cells = nc;
+	if (n_outside != NULL) *n_outside = no;
+	if (sums != NULL) *sums = a;
+	if (outside != NULL) *outside = b;
+	if (squares != NULL) *squares = c;
+	if (outside_squares != NULL) *outside_squares = d;
+	if (stderrs != NULL) *stderrs = e;
+	if (outside_stderrs != NULL) *outside_stderrs = f;
+	if (n_started != NULL) *n_started = efficiencies->tally_n_started;
+	return 1;
+}
+
+int pc_transmission_efficiencies_get_select_squares(void *efficiencies_, size_t *n_energies, uint64_t **passed_w2, uint64_t **rejected_w2,
+	double **transmission, double **transmission_stderr, void *error_)
+{
+	static const char *fn = "pc_transmission_efficiencies_get_select_squares";
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: efficiencies cannot be NULL", fn);
+		return 0;
+	}
+	const struct pc_select_result *sr = efficiencies->select;
+	if (sr == NULL || sr->passed_w2 == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run was made without POLYCAP_TALLY_STDERR=1 or without POLYCAP_SELECT", fn);
+		return 0;
+	}
+	const size_t ne = efficiencies->n_energies;
+	uint64_t *p = NULL, *r = NULL;
+	double *t = NULL, *te = NULL;
+	int ok = 1;
+	if (passed_w2 != NULL) ok = (p = pc_dup(sr->passed_w2, sizeof(uint64_t)*6*ne)) != NULL;
+	if (rejected_w2 != NULL && ok) ok = (r = pc_dup(sr->rejected_w2, sizeof(uint64_t)*6*ne)) != NULL;
+	if (transmission != NULL && ok) ok = (t = malloc(sizeof(double)*3*ne)) != NULL;
+	if (transmission_stderr != NULL && ok) ok = (te = malloc(sizeof(double)*3*ne)) != NULL;
+	if (!ok) {
+		free(p); free(r); free(t); free(te);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "%s: could not allocate memory -> %s", fn, strerror(errno));
+		return 0;
+	}
+	for (size_t k = 0; k < 3 && (t != NULL || te != NULL); k++)
+		pc_hip_select_transmission(ne, sr->passed_w + k*ne, sr->rejected_w + k*ne, sr->passed_w2 + 2*k*ne, sr->rejected_w2 + 2*k*ne,
+		                           t != NULL ? t + k*ne : NULL, te != NULL ? te + k*ne : NULL);
+	if (n_energies != NULL) *n_energies = ne;
+	if (passed_w2 != NULL) *passed_w2 = p;
+	if (rejected_w2 != NULL) *rejected_w2 = r;
+	if (transmission != NULL) *transmission = t;
+	if (transmission_stderr != NULL) *transmission_stderr = te;
 	return 1;
 }
 

@@ -470,10 +470,63 @@ def _kind(kind):
     return SPOT_KINDS[kind] if isinstance(kind, str) else int(kind)
 
 
+def tally_stderr(sums, squares, n_started):
+    """Standard error of every cell in weight per started photon (pc_hip_tally_stderr, host only): sums uint64 [...] = S, squares
+    uint64 [..., 2] = S2 as (lo, hi) pairs, n_started = counters 0 + 1 + 2 of the run or runs that were added.  Doubles shaped like
+    sums; NaN when fewer than two photons were started."""
+    a = np.ascontiguousarray(sums, dtype=np.uint64)
+    b = np.ascontiguousarray(squares, dtype=np.uint64)
+    if b.shape != a.shape + (2,):
+        raise ValueError("tally_stderr: squares must be shaped like sums with a trailing [2]")
+    out = np.zeros(a.shape, dtype=np.float64)
+    u64p = C.POINTER(C.c_uint64)
+    _cabi.lib().pc_hip_tally_stderr(a.size, a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), int(n_started), dptr(out))
+    return out
+
+
+def select_transmission(passed_w, rejected_w, passed_w2, rejected_w2):
+    """(T, T_err) per energy of one kind of a selection's totals (pc_hip_select_transmission, host only): T = P / (P + R) and its
+    error by the delta method from the exact sums of W and of W*W over the passing and the rejected entries; NaN where P + R == 0."""
+    pw = np.ascontiguousarray(passed_w, dtype=np.uint64).ravel()
+    rw = np.ascontiguousarray(rejected_w, dtype=np.uint64).ravel()
+    p2 = np.ascontiguousarray(passed_w2, dtype=np.uint64).reshape(-1, 2)
+    r2 = np.ascontiguousarray(rejected_w2, dtype=np.uint64).reshape(-1, 2)
+    ne = pw.shape[0]
+    if rw.shape[0] != ne or p2.shape[0] != ne or r2.shape[0] != ne:
+        raise ValueError("select_transmission: passed_w, rejected_w [n_energies] and passed_w2, rejected_w2 [n_energies, 2] are needed")
+    T, err = np.zeros(ne), np.zeros(ne)
+    u64p = C.POINTER(C.c_uint64)
+    _cabi.lib().pc_hip_select_transmission(ne, pw.ctypes.data_as(u64p), rw.ctypes.data_as(u64p), p2.ctypes.data_as(u64p), r2.ctypes.data_as(u64p),
+                                           dptr(T), dptr(err))
+    return T, err
+
+
 class _Tally:
     """What SpotMap, BeamMoments and Histograms share: the handle of a pc_hip_<_stem>_* object made on a TraceContext or a
     TraceGroup, its lifetime, add and reset."""
     _stem = None
+    _cells = "bins"              # the key of read() that holds the cells
+    squares = False
+
+    def _track(self, squares):
+        """squares=True of the constructors: every add also keeps the exact sum of W*W per cell (pc_hip_<_stem>_track_squares)"""
+        if squares:
+            self._call("track_squares")
+            self.squares = True
+
+    def _read_squares(self, cells_shape, outside_shape):
+        sq = np.zeros(tuple(cells_shape) + (2,), dtype=np.uint64)
+        out = np.zeros(tuple(outside_shape) + (2,), dtype=np.uint64)
+        self._call("read_squares", sq.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(squares=sq, outside_squares=out)
+
+    def stderr(self, n_started):
+        """Standard error of every cell read now, in weight per started photon (tally_stderr): doubles shaped like the cells of
+        read().  n_started: counters 0 + 1 + 2 of the run or runs that were added.  Needs squares=True."""
+        if not self.squares:
+            raise ValueError("stderr: the object was made without squares=True")
+        r = self.read()
+        return tally_stderr(r[self._cells], r["squares"], n_started)
 
     def _create(self, owner, spec=None):
         self._L = _cabi.lib()
@@ -528,7 +581,7 @@ class SpotMap(_Tally):
 
     _stem = "spot"
 
-    def __init__(self, owner, distances, window, bins, energies=None, regime=0):
+    def __init__(self, owner, distances, window, bins, energies=None, regime=0, squares=False):
         self.distances = np.ascontiguousarray(distances, dtype=np.float64).ravel()
         self.window = tuple(float(v) for v in window)
         self.nx, self.ny = (int(bins[0]), int(bins[1]))
@@ -542,17 +595,22 @@ class SpotMap(_Tally):
         self._L.pc_hip_spot_info(self._h, dims, C.byref(wide))
         self.shape = tuple(int(d) for d in dims)       # (planes, selected energies, ny, nx)
         self.wide = bool(wide.value)
+        self._track(squares)
 
     def read(self):
         """bins [planes, energies, ny, nx] and outside [planes, energies] as uint64, the entry count, and the same as weights
-        (maps = bins * 2^-32, outside_map)."""
+        (maps = bins * 2^-32, outside_map).  With squares=True also squares [planes, energies, ny, nx, 2] and outside_squares
+        [planes, energies, 2]: the exact sums of W*W as (lo, hi) pairs in units of 2^-64."""
         np_, ns = self.shape[0], self.shape[1]
         bins = np.zeros(self.shape, dtype=np.uint64)
         out = np.zeros((np_, ns), dtype=np.uint64)
         n = C.c_int64(0)
         self._call("read", bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n))
-        return dict(bins=bins, outside=out, n_entries=int(n.value), maps=bins.astype(np.float64) * 2.0 ** -32,
-                    outside_map=out.astype(np.float64) * 2.0 ** -32)
+        r = dict(bins=bins, outside=out, n_entries=int(n.value), maps=bins.astype(np.float64) * 2.0 ** -32,
+                 outside_map=out.astype(np.float64) * 2.0 ** -32)
+        if self.squares:
+            r.update(self._read_squares(bins.shape, out.shape))
+        return r
 
 
 BEAM_SUMS = ("W", "WX", "WY", "WU", "WV", "WXX", "WXY", "WXU", "WXV", "WYY", "WYU", "WYV", "WUU", "WUV", "WVV")
@@ -659,7 +717,7 @@ class Histograms(_Tally):
 
     _stem = "hist"
 
-    def __init__(self, owner, axes, energies=None, regime=0):
+    def __init__(self, owner, axes, energies=None, regime=0, squares=False):
         self._axes = hist_axes(axes)
         self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
         spec = _cabi.HistSpecS(len(axes), self._axes, 0 if self.energies is None else self.energies.shape[0],
@@ -674,19 +732,24 @@ class Histograms(_Tally):
         self.regime = int(reg.value)
         self.axes = [dict(axis=HIST_QUANTITIES[a.quantity], d=a.d, centre=(a.cx, a.cy), range=(a.lo, a.hi), bins=a.n_bins)
                      for a in self._axes[:self.n_axes]]
+        self._track(squares)
 
     def read(self):
         """bins uint64 [3, energies, total_bins] (kinds exit, extleak, intleak; the axes one after the other), outside uint64
         [3, axes, energies], n_entries [3]; axes: per axis a view [3, energies, n_bins] of the bins; edges: per axis its n_bins + 1
-        bin edges."""
+        bin edges.  With squares=True also squares [3, energies, total_bins, 2] and outside_squares [3, axes, energies, 2]: the exact
+        sums of W*W as (lo, hi) pairs in units of 2^-64."""
         bins = np.zeros((3, self.n_selected, self.total_bins), dtype=np.uint64)
         out = np.zeros((3, self.n_axes, self.n_selected), dtype=np.uint64)
         n = (C.c_int64 * 3)()
         self._call("read", bins.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
         o = self.offsets
-        return dict(bins=bins, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
-                    axes=[bins[:, :, o[a]:o[a + 1]] for a in range(self.n_axes)],
-                    edges=[np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in self.axes])
+        r = dict(bins=bins, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
+                 axes=[bins[:, :, o[a]:o[a + 1]] for a in range(self.n_axes)],
+                 edges=[np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in self.axes])
+        if self.squares:
+            r.update(self._read_squares(bins.shape, out.shape))
+        return r
 
     def _one(self, axis, energy, kind):
         k = _kind(kind)
@@ -717,6 +780,19 @@ def joint_pairs(pairs):
         a = hist_axes(list(uv), JOINT_QUANTITIES)
         arr[k] = _cabi.JointPairS(a[0], a[1])
     return arr
+
+
+def pairs_sum(pairs, axis):
+    """(lo, hi) pairs uint64 [..., 2] summed exactly along `axis` of the leading dimensions (Python integers): the square sums of
+    cells add as their weights do, so a marginal, a rebinned profile or a region of interest keeps an exact S2."""
+    p = np.asarray(pairs, dtype=np.uint64)
+    if p.ndim < 2 or p.shape[-1] != 2:
+        raise ValueError("pairs_sum: (lo, hi) pairs [..., 2] are needed")
+    axis = axis % (p.ndim - 1)
+    v = p[..., 0].astype(object) + p[..., 1].astype(object) * (1 << 64)
+    t = np.asarray(v.sum(axis=axis), dtype=object)
+    lo, hi = np.frompyfunc(lambda x: x & ((1 << 64) - 1), 1, 1)(t), np.frompyfunc(lambda x: x >> 64, 1, 1)(t)
+    return np.stack([np.asarray(lo, dtype=np.uint64), np.asarray(hi, dtype=np.uint64)], axis=-1)
 
 
 def joint_marginal(cells, which):
@@ -755,8 +831,9 @@ class JointHistograms(_Tally):
     include/polycap-hip.h.  pairs: see joint_pairs.  regime: 0 automatic, 1 workgroup-private LDS tiles, 2 energies across lanes."""
 
     _stem = "joint"
+    _cells = "cells"
 
-    def __init__(self, owner, pairs, energies=None, regime=0):
+    def __init__(self, owner, pairs, energies=None, regime=0, squares=False):
         self._pairs = joint_pairs(pairs)
         self.energies = None if energies is None else np.ascontiguousarray(energies, dtype=np.int32).ravel()
         spec = _cabi.JointSpecS(len(pairs), self._pairs, 0 if self.energies is None else self.energies.shape[0],
@@ -770,28 +847,48 @@ class JointHistograms(_Tally):
         self.offsets = [int(v) for v in off]
         self.regime = int(reg.value)
         self.pairs = [(_axis_dict(p.u), _axis_dict(p.v)) for p in self._pairs[:self.n_pairs]]
+        self._track(squares)
 
     def read(self):
         """cells uint64 [3, energies, total_cells] (kinds exit, extleak, intleak; the pairs one after the other, each [iv][iu]),
         outside uint64 [3, pairs, energies], n_entries [3]; pairs: per pair a view [3, energies, nv, nu] of the cells; edges: per
-        pair the (u, v) bin edges."""
+        pair the (u, v) bin edges.  With squares=True also squares [3, energies, total_cells, 2], outside_squares [3, pairs, energies,
+        2] and pairs_squares (views [3, energies, nv, nu, 2]): the exact sums of W*W as (lo, hi) pairs in units of 2^-64."""
         cells = np.zeros((3, self.n_selected, self.total_cells), dtype=np.uint64)
         out = np.zeros((3, self.n_pairs, self.n_selected), dtype=np.uint64)
         n = (C.c_int64 * 3)()
         self._call("read", cells.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
         o = self.offsets
-        return dict(cells=cells, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
-                    pairs=[cells[:, :, o[p]:o[p + 1]].reshape(3, self.n_selected, v["bins"], u["bins"]) for p, (u, v) in enumerate(self.pairs)],
-                    edges=[tuple(np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in uv) for uv in self.pairs])
+        r = dict(cells=cells, outside=out, n_entries=np.array([int(v) for v in n], dtype=np.int64),
+                 pairs=[cells[:, :, o[p]:o[p + 1]].reshape(3, self.n_selected, v["bins"], u["bins"]) for p, (u, v) in enumerate(self.pairs)],
+                 edges=[tuple(np.linspace(x["range"][0], x["range"][1], x["bins"] + 1) for x in uv) for uv in self.pairs])
+        if self.squares:
+            r.update(self._read_squares(cells.shape, out.shape))
+            sq = r["squares"]
+            r["pairs_squares"] = [sq[:, :, o[p]:o[p + 1]].reshape(3, self.n_selected, v["bins"], u["bins"], 2) for p, (u, v) in enumerate(self.pairs)]
+        return r
 
-    def marginal(self, pair, which, kind="exit"):
-        """uint64 [energies, nu] (which "u") or [energies, nv] ("v"): the exact marginal sums of pair `pair`, read now (joint_marginal)"""
+    def marginal(self, pair, which, kind="exit", squares=False):
+        """uint64 [energies, nu] (which "u") or [energies, nv] ("v"): the exact marginal sums of pair `pair`, read now (joint_marginal).
+        squares=True (an object made with squares=True): the exact marginals of S2 instead, (lo, hi) pairs [energies, nu or nv, 2]
+        (pairs_sum): the square sums of cells add as their weights do."""
+        if which not in ("u", "v"):
+            raise ValueError("marginal: which \"u\" or \"v\" is needed")
+        if squares:
+            if not self.squares:
+                raise ValueError("marginal: the object was made without squares=True")
+            return pairs_sum(self.read()["pairs_squares"][pair][_kind(kind)], 1 if which == "u" else 2)
         c = self.read()["pairs"][pair][_kind(kind)]
         return np.stack([joint_marginal(c[e], which) for e in range(self.n_selected)])
 
-    def density(self, pair, efficiencies, kind="exit"):
+    def density(self, pair, efficiencies, kind="exit", n_started=None):
         """[energies, nv, nu] in efficiency units as the spot maps of the public call are, read now: cell * efficiencies[e] /
-        (inside + outside) with efficiencies [energies] those of the selected energies; 0 where an energy holds no weight."""
+        (inside + outside) with efficiencies [energies] those of the selected energies; 0 where an energy holds no weight.
+        With n_started (an object made with squares=True; counters 0 + 1 + 2 of the runs added): (density, error), the error map
+        being the cells' standard errors (tally_stderr) in the same units, efficiencies[e] * stderr * n_started / ((inside +
+        outside) 2^-32); the normalising total is taken as exact."""
+        if n_started is not None and not self.squares:
+            raise ValueError("density: the error map needs an object made with squares=True")
         r = self.read()
         k = _kind(kind)
         c, out = r["pairs"][pair][k], r["outside"][k, pair]
@@ -799,11 +896,15 @@ class JointHistograms(_Tally):
         if eff.shape[0] != self.n_selected:
             raise ValueError("density: one efficiency per selected energy is needed")
         dens = np.zeros(c.shape, dtype=np.float64)
+        err = np.zeros(c.shape, dtype=np.float64)
+        sig = None if n_started is None else tally_stderr(c, r["pairs_squares"][pair][k], n_started)
         for e in range(self.n_selected):
             total = int(c[e].sum(dtype=np.uint64)) + int(out[e])
             if total:
                 dens[e] = eff[e] * c[e].astype(np.float64) / float(total)
-        return dens
+                if sig is not None:
+                    err[e] = eff[e] * sig[e] * float(n_started) / (float(total) * 2.0 ** -32)
+        return dens if n_started is None else (dens, err)
 
 
 def select_cuts(cuts):
@@ -846,9 +947,10 @@ class Selection:
     fills any tally of the same owner with the passing entries only.  A mask belongs to the entries it was made from: after the next
     run it is stale and has to be applied again.  The contract is written down in include/polycap-hip.h."""
 
-    def __init__(self, owner, cuts):
+    def __init__(self, owner, cuts, squares=False):
         self._L = _cabi.lib()
         self.owner = owner                      # keeps the context alive as long as the object
+        self.squares = False
         self._cuts = select_cuts(cuts)
         spec = _cabi.SelectSpecS(len(cuts), self._cuts)
         h = C.c_void_p()
@@ -861,6 +963,11 @@ class Selection:
         self._L.pc_hip_select_info(self._h, C.byref(nc), C.byref(ne), None)
         self.n_cuts, self.n_energies = int(nc.value), int(ne.value)
         self.cuts = [_cut_dict(c) for c in self._cuts[:self.n_cuts]]
+        if squares:
+            st = self._L.pc_hip_select_track_squares(self._h)
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_select_track_squares", st)
+            self.squares = True
 
     def close(self):
         if getattr(self, "_h", None):
@@ -881,7 +988,8 @@ class Selection:
 
     def read(self):
         """n_pass [3], n_seen [3] (kinds exit, extleak, intleak; zeros for a kind not applied), passed_w and rejected_w uint64
-        [3, n_energies]: the exact sums of round_half_even(w * 2^32) over the passing and over the rejected entries."""
+        [3, n_energies]: the exact sums of round_half_even(w * 2^32) over the passing and over the rejected entries.  With
+        squares=True also passed_w2 and rejected_w2 uint64 [3, n_energies, 2]: the exact sums of W*W as (lo, hi) pairs."""
         n_pass, n_seen = (C.c_int64 * 3)(), (C.c_int64 * 3)()
         pw = np.zeros((3, self.n_energies), dtype=np.uint64)
         rw = np.zeros((3, self.n_energies), dtype=np.uint64)
@@ -889,8 +997,24 @@ class Selection:
         st = self._L.pc_hip_select_read(self._h, n_pass, n_seen, pw.ctypes.data_as(u64p), rw.ctypes.data_as(u64p))
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_select_read", st)
-        return dict(n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
-                    passed_w=pw, rejected_w=rw)
+        r = dict(n_pass=np.array([int(v) for v in n_pass], dtype=np.int64), n_seen=np.array([int(v) for v in n_seen], dtype=np.int64),
+                 passed_w=pw, rejected_w=rw)
+        if self.squares:
+            p2 = np.zeros((3, self.n_energies, 2), dtype=np.uint64)
+            r2 = np.zeros((3, self.n_energies, 2), dtype=np.uint64)
+            st = self._L.pc_hip_select_read_squares(self._h, p2.ctypes.data_as(u64p), r2.ctypes.data_as(u64p))
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_select_read_squares", st)
+            r.update(passed_w2=p2, rejected_w2=r2)
+        return r
+
+    def transmission(self, kind="exit"):
+        """(T, T_err) per energy of the kind's totals read now (select_transmission): the transmission of the selection, a pinhole's
+        for a cut on r, and its standard error.  Needs squares=True."""
+        if not self.squares:
+            raise ValueError("transmission: the selection was made without squares=True")
+        r, k = self.read(), _kind(kind)
+        return select_transmission(r["passed_w"][k], r["rejected_w"][k], r["passed_w2"][k], r["rejected_w2"][k])
 
     def apply(self, kind="exit"):
         """Evaluates the cuts on the entries of `kind` of the last run; returns read()"""

@@ -126,6 +126,11 @@ cdef extern from "polycap.h" nogil:
 
     int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies, int64_t *n_pass,
         int64_t *n_seen, uint64_t **passed_w, uint64_t **rejected_w, void *error)
+    int pc_transmission_efficiencies_get_tally_squares(void *efficiencies, int which, int kind, size_t *n_cells, size_t *n_outside,
+        uint64_t **sums, uint64_t **outside, uint64_t **squares, uint64_t **outside_squares, double **stderrs, double **outside_stderrs,
+        int64_t *n_started, void *error)
+    int pc_transmission_efficiencies_get_select_squares(void *efficiencies, size_t *n_energies, uint64_t **passed_w2, uint64_t **rejected_w2,
+        double **transmission, double **transmission_stderr, void *error)
 
     ctypedef struct pc_hip_images:
         double *src_start_coords[2]
@@ -639,7 +644,8 @@ cdef class TransmissionEfficiencies:
         _raise_if(error)
         npl, ns, ny, nx = dims[0], dims[1], dims[2], dims[3]
         return dict(maps=_take_doubles(m, npl * ns * ny * nx).reshape(npl, ns, ny, nx), outside=_take_doubles(o, npl * ns).reshape(npl, ns),
-                    distances=_take_doubles(d, npl), energies=_take_doubles(e, ns), window=(window[0], window[1], window[2], window[3]))
+                    distances=_take_doubles(d, npl), energies=_take_doubles(e, ns), window=(window[0], window[1], window[2], window[3]),
+                    **self._squares(0, kind, (npl, ns, ny, nx), (npl, ns)))
 
     def efficiency_stderr(self):
         """Extension of this build: the standard error of every efficiency of a run made with POLYCAP_STDERR=1
@@ -701,6 +707,52 @@ cdef class TransmissionEfficiencies:
         out.update(sums=S.reshape(n, 15, 2), outside=O, n_entries=int(ni))
         return out
 
+    def _squares(self, int which, kind, cells_shape, outside_shape):
+        """Extension of this build: what POLYCAP_TALLY_STDERR=1 adds to a tally's accessor
+        (pc_transmission_efficiencies_get_tally_squares): squares and outside_squares uint64 [..., 2], stderr and outside_stderr (weight
+        per started photon) and n_started; for the spot maps also the uint64 sums behind the maps.  {} for a run made without it."""
+        cdef polycap_error *error = NULL
+        cdef size_t nc = 0
+        cdef size_t no = 0
+        cdef uint64_t *a = NULL
+        cdef uint64_t *b = NULL
+        cdef uint64_t *c = NULL
+        cdef uint64_t *d = NULL
+        cdef double *e = NULL
+        cdef double *f = NULL
+        cdef int64_t ns = 0
+        cdef size_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        if not pc_transmission_efficiencies_get_tally_squares(<void *>self._eff, which, k, &nc, &no, &a, &b, &c, &d, &e, &f, &ns, <void *>&error):
+            if error != NULL:
+                polycap_error_free(error)
+            return {}
+        A = np.empty(nc, dtype=np.uint64)
+        B = np.empty(no, dtype=np.uint64)
+        Cq = np.empty(2 * nc, dtype=np.uint64)
+        Dq = np.empty(2 * no, dtype=np.uint64)
+        for i in range(nc):
+            A[i] = a[i]
+        for i in range(no):
+            B[i] = b[i]
+        for i in range(2 * nc):
+            Cq[i] = c[i]
+        for i in range(2 * no):
+            Dq[i] = d[i]
+        polycap_free(a)
+        polycap_free(b)
+        polycap_free(c)
+        polycap_free(d)
+        out = dict(squares=Cq.reshape(tuple(cells_shape) + (2,)), outside_squares=Dq.reshape(tuple(outside_shape) + (2,)),
+                   stderr=_take_doubles(e, nc).reshape(cells_shape), outside_stderr=_take_doubles(f, no).reshape(outside_shape), n_started=int(ns))
+        if which == 0:
+            out.update(bins=A.reshape(cells_shape), outside_bins=B.reshape(outside_shape))
+        return out
+
+    def spot(self, kind="exit"):
+        """spot_map under the name of the other tallies' accessors"""
+        return self.spot_map(kind)
+
     def hist(self, kind="exit"):
         """Extension of this build: the histograms of a run made with POLYCAP_HIST set (pc_transmission_efficiencies_get_hist): dict of
         the exact sums bins uint64 [energies, total_bins] and outside uint64 [axes, energies], n_entries, offsets [axes + 1], energies
@@ -734,7 +786,8 @@ cdef class TransmissionEfficiencies:
         polycap_free(ax)
         polycap_free(b)
         polycap_free(u)
-        return dict(bins=B.reshape(ns, tb), outside=U.reshape(na, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), axes=axes)
+        return dict(bins=B.reshape(ns, tb), outside=U.reshape(na, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), axes=axes,
+                    **self._squares(1, kind, (ns, tb), (na, ns)))
 
     def joint(self, kind="exit"):
         """Extension of this build: the joint histograms of a run made with POLYCAP_JOINT set (pc_transmission_efficiencies_get_joint):
@@ -771,7 +824,8 @@ cdef class TransmissionEfficiencies:
         polycap_free(pr)
         polycap_free(b)
         polycap_free(u)
-        return dict(cells=B.reshape(ns, tc), outside=U.reshape(n_pairs, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), pairs=pairs)
+        return dict(cells=B.reshape(ns, tc), outside=U.reshape(n_pairs, ns), n_entries=int(ni), offsets=O, energies=_take_doubles(e, ns), pairs=pairs,
+                    **self._squares(2, kind, (ns, tc), (n_pairs, ns)))
 
     def select(self):
         """Extension of this build: the selection of a run made with POLYCAP_SELECT set (pc_transmission_efficiencies_get_select): dict
@@ -799,8 +853,26 @@ cdef class TransmissionEfficiencies:
         polycap_free(c)
         polycap_free(p)
         polycap_free(r)
-        return dict(cuts=cuts, n_pass=np.array([n_pass[0], n_pass[1], n_pass[2]], dtype=np.int64),
-                    n_seen=np.array([n_seen[0], n_seen[1], n_seen[2]], dtype=np.int64), passed_w=P.reshape(3, ne), rejected_w=R.reshape(3, ne))
+        out = dict(cuts=cuts, n_pass=np.array([n_pass[0], n_pass[1], n_pass[2]], dtype=np.int64),
+                   n_seen=np.array([n_seen[0], n_seen[1], n_seen[2]], dtype=np.int64), passed_w=P.reshape(3, ne), rejected_w=R.reshape(3, ne))
+        # POLYCAP_TALLY_STDERR=1: the sums of W*W and the transmission per kind with its standard error
+        cdef uint64_t *p2 = NULL
+        cdef uint64_t *r2 = NULL
+        cdef double *t = NULL
+        cdef double *te = NULL
+        if pc_transmission_efficiencies_get_select_squares(<void *>self._eff, &ne, &p2, &r2, &t, &te, <void *>&error):
+            P2 = np.empty(6 * ne, dtype=np.uint64)
+            R2 = np.empty(6 * ne, dtype=np.uint64)
+            for i in range(6 * ne):
+                P2[i] = p2[i]
+                R2[i] = r2[i]
+            polycap_free(p2)
+            polycap_free(r2)
+            out.update(passed_w2=P2.reshape(3, ne, 2), rejected_w2=R2.reshape(3, ne, 2), transmission=_take_doubles(t, 3 * ne).reshape(3, ne),
+                       transmission_stderr=_take_doubles(te, 3 * ne).reshape(3, ne))
+        elif error != NULL:
+            polycap_error_free(error)
+        return out
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
