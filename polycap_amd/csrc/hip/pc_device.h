@@ -782,6 +782,10 @@ PC_HD int pc_reflect_geom(const pc_photon<NE> &ph, double nx, double ny, double 
 	double es = fma(ph.ex, sdx, fma(ph.ey, sdy, ph.ez*sdz));
 	g.es2 = es*es;
 	g.sd2 = fma(sdx, sdx, fma(sdy, sdy, sdz*sdz));
+	/* (E.s)^2 <= |E|^2 |s|^2 holds for the exact values only: with E along s the rounded es2 exceeds sd2 by an ulp or two, frac_s
+	 * = es2/sd2 comes out above 1 and frac_p = ep2/sd2 below 0.  Every other input keeps its bits;
+	 * a NaN stays a NaN (the comparison is false). */
+	if (g.es2 > g.sd2) g.es2 = g.sd2;
 	g.ep2 = g.sd2 - g.es2;
 	return 1;
 }

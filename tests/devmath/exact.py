@@ -178,3 +178,219 @@ def fma_neg_sq_one(c):
     """fma(-c, c, 1.0): 1 - c^2 rounded once, as pc_reflect_geom forms sin^2"""
     with mp.workdps(DPS):
         return float(1 - _m(c) * _m(c))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The geometric half of a reflection: the reference's definitions (src/polycap-capil.c:52-255 segment, :444-563 refl_polar,
+# :565-655 reflect) evaluated from the double inputs as stored, at GDPS digits.  Results stay mpf (errors of 1e-16 on
+# coordinates of order 1 are differences of nearly equal numbers); the *_err functions turn them into floats.
+GDPS = 70
+U = EPS                       # unit roundoff of one correctly rounded operation
+GUARD_LAST = 1.e-5            # the doubles the reference compares with (:134-171, :178)
+GUARD_PROJ = 1.e-10
+
+
+def _v(x):
+    return [mp.mpf(float(t)) for t in x]
+
+
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def segment(row):
+    """polycap_capil_segment in exact arithmetic on one probe row (z0, z1, cap0, cap1, zh0, zh1, kx, ky, P, d), every input finite.
+
+    Returns a dict: status (the reference's, or None where it divides by zero: dz = 0, a = 0 with the root asked for); hz, h
+    (3), n (3) as mpf when status is 1; roots; cond = the sensitivity of the selected root to relative changes of a, b, c (its
+    relative error per relative 2^-53 of each, summed); guards = [(name, value, err)]: every quantity the reference compares,
+    its exact distance from the threshold and the first-order running error bound of the reference's own evaluation of it (one
+    2^-53 per operation).  A guard decides the status safely when |value| is a multiple of err."""
+    with mp.workdps(GDPS):
+        z0, z1, R0, R1, zh0, zh1, kx, ky, Px, Py, Pz, dx, dy, dz = _v(row)
+        out = dict(status=None, guards=[], cond=None, roots=None, a=None, discr=None)
+        if dz < 0 or z1 <= z0 or R0 < 0 or R1 < 0 or z0 < 0:
+            out["status"] = -1
+            return out
+        if dz == 0:
+            return out
+        u = mp.mpf(U)
+        dn = mp.sqrt(dx * dx + dy * dy + dz * dz)
+        c0x, c0y, c1x, c1y = kx * zh0, ky * zh0, kx * zh1, ky * zh1
+        cdx, cdy, cdz = c1x - c0x, c1y - c0y, z1 - z0
+        sx, sy = dx / dz, dy / dz
+        t0 = z0 - Pz
+        p0x, p0y = Px + sx * t0, Py + sy * t0
+        ddx, ddy = sx - cdx / cdz, sy - cdy / cdz
+        rr = (R1 - R0) / cdz
+        qx, qy = p0x - c0x, p0y - c0y
+        a = ddx * ddx + ddy * ddy - rr * rr
+        b = 2 * (qx * ddx + qy * ddy - R0 * rr)
+        c = qx * qx + qy * qy - R0 * R0
+        D = b * b - 4 * a * c
+        # running error of the reference's evaluation, first order
+        e_ddx = u * (abs(sx) + (abs(c1x) + abs(c0x)) / cdz + 3 * abs(cdx / cdz) + abs(ddx))
+        e_ddy = u * (abs(sy) + (abs(c1y) + abs(c0y)) / cdz + 3 * abs(cdy / cdz) + abs(ddy))
+        e_rr = 3 * u * abs(rr)
+        e_qx = u * (abs(p0x) + 3 * abs(sx * t0) + abs(c0x) + abs(qx))
+        e_qy = u * (abs(p0y) + 3 * abs(sy * t0) + abs(c0y) + abs(qy))
+        e_a = 2 * (abs(ddx) * e_ddx + abs(ddy) * e_ddy + abs(rr) * e_rr) + 3 * u * (ddx * ddx + ddy * ddy + rr * rr)
+        e_b = 2 * (abs(ddx) * e_qx + abs(qx) * e_ddx + abs(ddy) * e_qy + abs(qy) * e_ddy + R0 * e_rr) \
+            + 6 * u * (abs(qx * ddx) + abs(qy * ddy) + abs(R0 * rr))
+        e_c = 2 * (abs(qx) * e_qx + abs(qy) * e_qy) + 3 * u * (qx * qx + qy * qy + R0 * R0)
+        e_D = 2 * abs(b) * e_b + 4 * (abs(a) * e_c + abs(c) * e_a) + 3 * u * (b * b + 4 * abs(a * c))
+        out["a"], out["discr"], out["b2"], out["rr2"] = a, D, b * b, rr * rr
+        out["guards"].append(("discr", D, e_D))
+        if D < 0:
+            out["status"] = -2
+            return out
+        if a == 0:
+            return out
+        s = mp.sqrt(D)
+        last = Pz
+        g_last, g_proj = mp.mpf(GUARD_LAST), mp.mpf(GUARD_PROJ)
+
+        def root(sign):
+            t = (-b + sign * s) / (2 * a)
+            # the errors of a, b, c move the root by (t^2 da + t db + dc) / sqrt(D) (they move -b and sqrt(D) together: no
+            # cancellation between them; sqrt(D) is floored at its own error for tangent rays); the roundings of -b +- sqrt(D)
+            # themselves do cancel against 2a
+            e_t = (t * t * e_a + abs(t) * e_b + e_c) / max(s, mp.sqrt(e_D)) + 3 * u * (abs(b) + s) / (2 * abs(a)) + 3 * u * abs(t)
+            zr = z0 + t
+            e_z = e_t + u * abs(zr)
+            return t, zr, e_t, e_z
+
+        def bad(zr):
+            return zr < z0 or zr - last < g_last or zr > z1
+
+        roots = [root(1), root(-1)] if D != 0 else [root(0)]
+        out["roots"] = [r[1] for r in roots]
+        reach = max(z1 - z0, abs(last + g_last - z0))
+        for k, (t, zr, e_t, e_z) in enumerate(roots):
+            if abs(t) > 4 * reach:
+                # a root far outside the segment (a ray nearly parallel to the wall: a -> 0) is rejected whatever its sign; its
+                # own error grows like t^2, that of 1/t does not: it stays rejected while 1/|t| stays below 1/reach
+                out["guards"].append(("far%d" % k, 1 / reach - 1 / abs(t), e_t / (t * t)))
+                continue
+            out["guards"] += [("zr%d-z0" % k, zr - z0, e_t + u * abs(z0)), ("z1-zr%d" % k, z1 - zr, e_z + u * abs(z1)),
+                              ("zr%d-last-1e-5" % k, zr - last - g_last, e_z + u * abs(zr - last))]
+        if D == 0:
+            sel = roots[0]
+        else:
+            b1, b2 = bad(roots[0][1]), bad(roots[1][1])
+            if b1 and b2:
+                out["status"] = -3
+                return out
+            if b1:
+                sel = roots[1]
+            elif b2:
+                sel = roots[0]
+            else:
+                sel = roots[1] if roots[1][1] - last < roots[0][1] - last else roots[0]
+                out["guards"].append(("zr1-zr0", roots[1][1] - roots[0][1], roots[0][3] + roots[1][3]))
+        t, hz, e_t, e_z = sel
+        out["cond"] = (abs(t * t * a) + abs(t * b) + abs(c)) / (s * abs(t)) if s != 0 and t != 0 else mp.inf
+        out["e_hz"] = e_z
+        if hz > z1:
+            out["status"] = -4
+            return out
+        if hz < z0 or hz - last < g_last:
+            out["status"] = -5
+            return out
+        ndz = dz / dn
+        d_proj = (hz - z0) / ndz
+        out["guards"].append(("d_proj-1e-10", d_proj - g_proj, e_t / ndz + 2 * u * abs(d_proj)))
+        if d_proj < g_proj:
+            out["status"] = -6
+            return out
+        hx, hy = p0x + d_proj * dx / dn, p0y + d_proj * dy / dn
+        # :225-246: the axis point opposite the hit, the radial unit vector, tilted by the wall angle
+        cap_dir = [cdx, cdy, cdz]
+        rel = [qx, qy, mp.mpf(0)]
+        pd = [dx / dn, dy / dn, dz / dn]
+        s2 = _dot(pd, cap_dir)
+        tpar = (d_proj + _dot(rel, cap_dir) / s2) / (_dot(cap_dir, cap_dir) / s2)
+        inn = [hx - (c0x + tpar * cdx), hy - (c0y + tpar * cdy), hz - (z0 + tpar * cdz)]
+        li, lc = mp.sqrt(_dot(inn, inn)), mp.sqrt(_dot(cap_dir, cap_dir))
+        gam = mp.atan((R0 - R1) / lc)
+        n = [mp.cos(gam) * inn[k] / li + mp.sin(gam) * cap_dir[k] / lc for k in range(3)]
+        ln = mp.sqrt(_dot(n, n))
+        out.update(status=1, hz=hz, h=[hx, hy, hz], n=[v / ln for v in n], p0=[p0x, p0y], d_proj=d_proj)
+        return out
+
+
+def segment_errors(ex, out_row):
+    """(|hz - hz*|, |h - h*|, angle(n, n*), | |n| - 1 |) of a probe or oracle result (hx, hy, hz, nx, ny, nz, ...) against
+    segment()'s result ex (status 1), as floats."""
+    with mp.workdps(GDPS):
+        h, n = _v(out_row[0:3]), _v(out_row[3:6])
+        dh = [h[k] - ex["h"][k] for k in range(3)]
+        cr = _cross(n, ex["n"])
+        ln = mp.sqrt(_dot(n, n))
+        ang = mp.atan2(mp.sqrt(_dot(cr, cr)), _dot(n, ex["n"]))
+        return float(abs(dh[2])), float(mp.sqrt(_dot(dh, dh))), float(ang), float(abs(ln - 1))
+
+
+def geom(row):
+    """The geometry of a reflection from (d, E, n) as stored.  'own': what pc_reflect_geom / pc_refl_geom3 evaluate, exactly
+    (no normalisation: the product relies on unit vectors); 'ref': the reference's definitions, which normalise d, n and E
+    (cos theta, sin^2 theta, (E.s)^2, 1 - (E.s)^2); 'bound': the first-order running error of the product's evaluation of each
+    own quantity (one 2^-53 per operation), the conditioning bound the measured errors are held against.  mpf throughout."""
+    with mp.workdps(GDPS):
+        d, E, n = _v(row[0:3]), _v(row[3:6]), _v(row[6:9])
+        u = mp.mpf(U)
+        alfa = _dot(d, n)
+        absdn = sum(abs(d[k] * n[k]) for k in range(3))
+        s = _cross(n, d)
+        sd2 = _dot(s, s)
+        es = _dot(E, s)
+        es2, st2 = es * es, 1 - alfa * alfa
+        ep2 = sd2 - es2
+        own = dict(alfa=alfa, st2=st2, es2=es2, ep2=ep2, sd2=sd2, c2=alfa * alfa)
+        b_alfa = 3 * u * absdn
+        b_s = [2 * u * (abs(n[(k + 1) % 3] * d[(k + 2) % 3]) + abs(d[(k + 1) % 3] * n[(k + 2) % 3])) for k in range(3)]
+        b_sd2 = 3 * u * sd2 + 2 * sum(abs(s[k]) * b_s[k] for k in range(3))
+        b_es = 3 * u * sum(abs(E[k] * s[k]) for k in range(3)) + sum(abs(E[k]) * b_s[k] for k in range(3))
+        b_es2 = 2 * abs(es) * b_es + u * es2 + b_es * b_es
+        b_ep2 = b_es2 + b_sd2 + u * abs(ep2)
+        bound = dict(alfa=b_alfa, st2=u * abs(st2) + 2 * abs(alfa) * b_alfa, es2=b_es2, ep2=b_ep2, sd2=b_sd2,
+                     c2=u * alfa * alfa + 2 * abs(alfa) * b_alfa)
+        ref = dict()
+        ld, ln, lE = (mp.sqrt(_dot(v, v)) for v in (d, n, E))
+        ref["cos"] = alfa / (ld * ln) if ld * ln != 0 else mp.nan
+        ref["sin2"] = 1 - ref["cos"] ** 2
+        if sd2 > 0:
+            own["fs"], own["fp"] = es2 / sd2, ep2 / sd2
+            bound["fs"] = (b_es2 + own["fs"] * b_sd2) / sd2 + u * own["fs"]
+            bound["fp"] = (b_ep2 + abs(own["fp"]) * b_sd2) / sd2 + u * abs(own["fp"])
+            ref["fs"] = es2 / (sd2 * lE * lE)
+            ref["fp"] = 1 - ref["fs"]
+        # the mirror image of d about the plane with normal n: as the product forms it (d - 2 (d.n) n) and exactly
+        own["mirror"] = [d[k] - 2 * alfa * n[k] for k in range(3)]
+        ref["mirror"] = [d[k] - 2 * alfa * n[k] / (ln * ln) for k in range(3)] if ln != 0 else None
+        bound["mirror"] = [u * abs(own["mirror"][k]) + 2 * abs(n[k]) * (b_alfa + u * abs(alfa)) for k in range(3)]
+        own["len_d"], own["len_n"] = ld, ln
+        return dict(own=own, ref=ref, bound=bound)
+
+
+def absdiff(got, exact_mpf):
+    """|got - exact| as a float, formed at GDPS digits"""
+    with mp.workdps(GDPS):
+        return float(abs(mp.mpf(float(got)) - exact_mpf))
+
+
+def vec_len_minus_one(v):
+    with mp.workdps(GDPS):
+        w = _v(v)
+        return float(mp.sqrt(_dot(w, w)) - 1)
+
+
+def unit(v):
+    """v / |v| rounded to doubles, from high precision"""
+    with mp.workdps(GDPS):
+        l = mp.sqrt(_dot(v, v))
+        return [float(t / l) for t in v]

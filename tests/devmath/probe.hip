@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "pc_problem.h"
 #include "probe_ops.h"
@@ -45,6 +46,32 @@ typedef void (*launch_fn)(int64_t, const pc_energy_const *, const int32_t *, con
 const launch_fn LAUNCH[PC_PROBE_NOPS] = {
 	launch<0>, launch<1>, launch<2>, launch<3>, launch<4>, launch<5>, launch<6>, launch<7>, launch<8>, launch<9>, launch<10>,
 	launch<11>, launch<12>};
+
+/* one thread per element of a geometry op; an element whose profile the setup rejected (code preset on the host) is left alone */
+template <int OP>
+__global__ void __launch_bounds__(256) pc_probe_geom_kernel(int64_t n, const pc_energy_const *__restrict__ ec,
+                                                            const int32_t *__restrict__ e, const double *__restrict__ in,
+                                                            const double *__restrict__ tab, double *__restrict__ out,
+                                                            int32_t *__restrict__ code)
+{
+	constexpr int WI = (OP == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : PC_PROBE_VEC_IN;
+	const int64_t i = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	if (code[i] == PC_PROBE_SETUP_REJECT) return;
+	double o[PC_PROBE_GEOM_OUT];
+	int cd = 0;
+	pc_probe_geom_eval<OP>(ec[e[i]], in + i*WI, (OP == PC_PROBE_SEGMENT) ? tab + i*PC_PROBE_SEG_TAB : nullptr, o, &cd);
+	for (int j = 0; j < PC_PROBE_GEOM_OUT; j++) out[i*PC_PROBE_GEOM_OUT + j] = o[j];
+	code[i] = cd;
+}
+
+template <int OP>
+void launch_geom(int64_t n, const pc_energy_const *ec, const int32_t *e, const double *in, const double *tab, double *out,
+                 int32_t *code)
+{
+	const unsigned blocks = (unsigned)((n + 255)/256);
+	hipLaunchKernelGGL(pc_probe_geom_kernel<OP>, dim3(blocks), dim3(256), 0, 0, n, ec, e, in, tab, out, code);
+}
 
 } // namespace
 
@@ -88,6 +115,61 @@ int probe_run(const pc_hip_problem *p, int op, int64_t n, const int32_t *e, cons
 	/* frees run whatever happened above; their status is reported only when everything before succeeded */
 	const hipError_t f[5] = {hipFree(d_ec), hipFree(d_e), hipFree(d_code), hipFree(d_in), hipFree(d_out)};
 	for (int j = 0; j < 5 && rc == 0; j++)
+		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
+#undef PC_PROBE_TRY
+	return rc;
+}
+
+/* A geometry op (PC_PROBE_SEGMENT, PC_PROBE_GEOM, PC_PROBE_BOUNCE) on n elements: in[n][in_w], out[n][out_w], code[n], widths as
+ * pc_probe_in_width / pc_probe_out_width give them.  Same return values as probe_run. */
+__attribute__((visibility("default")))
+int probe_run_geom(const pc_hip_problem *p, int op, int64_t n, const int32_t *e, const double *in, int in_w, double *out,
+                   int out_w, int32_t *code, char *err)
+{
+	err[0] = 0;
+	pc_host_tables t;
+	std::string msg;
+	if (pc_build_tables(p, t, msg)) { snprintf(err, 256, "%s", msg.c_str()); return -2; }
+	if (pc_probe_geom_check(op, n, in_w, out_w, e, (int)t.ec.size())) { snprintf(err, 256, "invalid op, size, width or energy index"); return -2; }
+	if (n == 0) return 0;
+	const bool seg = op == PC_PROBE_SEGMENT;
+	std::vector<double> tab(seg ? (size_t)n*PC_PROBE_SEG_TAB : 1);
+	for (int64_t i = 0; i < n; i++) {
+		code[i] = 0;
+		for (int j = 0; j < out_w; j++) out[i*out_w + j] = 0.;
+		if (seg && pc_probe_seg_table(p, in + i*in_w, tab.data() + i*PC_PROBE_SEG_TAB)) code[i] = PC_PROBE_SETUP_REJECT;
+	}
+	pc_energy_const *d_ec = nullptr;
+	int32_t *d_e = nullptr, *d_code = nullptr;
+	double *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
+	int rc = 0;
+	hipError_t s = hipSuccess;
+#define PC_PROBE_TRY(call) do { if (s == hipSuccess) { s = (call); if (s != hipSuccess) snprintf(err, 256, "%s: %s", #call, hipGetErrorString(s)); } } while (0)
+	const size_t ne = t.ec.size();
+	PC_PROBE_TRY(hipMalloc(&d_ec, ne*sizeof(pc_energy_const)));
+	PC_PROBE_TRY(hipMalloc(&d_e, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_code, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_in, n*in_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_out, n*out_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_tab, tab.size()*sizeof(double)));
+	PC_PROBE_TRY(hipMemcpy(d_ec, t.ec.data(), ne*sizeof(pc_energy_const), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_e, e, n*sizeof(int32_t), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_code, code, n*sizeof(int32_t), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_in, in, n*in_w*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_out, out, n*out_w*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
+	if (s == hipSuccess) {
+		if (op == PC_PROBE_SEGMENT) launch_geom<PC_PROBE_SEGMENT>(n, d_ec, d_e, d_in, d_tab, d_out, d_code);
+		else if (op == PC_PROBE_GEOM) launch_geom<PC_PROBE_GEOM>(n, d_ec, d_e, d_in, d_tab, d_out, d_code);
+		else launch_geom<PC_PROBE_BOUNCE>(n, d_ec, d_e, d_in, d_tab, d_out, d_code);
+		PC_PROBE_TRY(hipGetLastError());
+	}
+	PC_PROBE_TRY(hipDeviceSynchronize());
+	PC_PROBE_TRY(hipMemcpy(out, d_out, n*out_w*sizeof(double), hipMemcpyDeviceToHost));
+	PC_PROBE_TRY(hipMemcpy(code, d_code, n*sizeof(int32_t), hipMemcpyDeviceToHost));
+	if (s != hipSuccess) rc = -3;
+	const hipError_t f[6] = {hipFree(d_ec), hipFree(d_e), hipFree(d_code), hipFree(d_in), hipFree(d_out), hipFree(d_tab)};
+	for (int j = 0; j < 6 && rc == 0; j++)
 		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
 #undef PC_PROBE_TRY
 	return rc;

@@ -16,6 +16,14 @@ _LIB = None
 
 OPS = dict(sqrt=0, div=1, exp=2, f3=3, f3s=4, f3x1=5, f3x2=6, ff0=7, ff1=8, re_fast=9, re3=10, re0=11, re1=12)
 GROUP = dict(f3x2=2)              # elements one device thread evaluates (one energy per group)
+# geometry ops (probe_ops.h): rows of their own widths, one entry point of their own
+GEOM_OPS = dict(segment=13, geom=14, bounce=15)
+GEOM_IN = dict(segment=14, geom=9, bounce=9)
+GEOM_OUT = 8
+SETUP_REJECT = -100               # the product's setup rejects the element's two-node profile: pc_segment is never reached
+SEG_COLS = ("z0", "z1", "cap0", "cap1", "zh0", "zh1", "kx", "ky", "Px", "Py", "Pz", "dx", "dy", "dz")
+SEG_OUT = ("hx", "hy", "hz", "nx", "ny", "nz", "p0x", "p0y")
+GEOM_OUT_COLS = ("alfa", "st2", "es2", "ep2", "sd2", "c2", "fs", "fp")
 # columns of the input rows (probe_ops.h)
 COLS = ("c", "st2", "es2", "ep2", "sd2", "fs", "fp", "w")
 EC_FIELDS = ("n_re", "n_im", "ninv2_re", "ninv2_im", "rough_c", "valid", "d2", "n2_re", "n2_im", "zi2", "rough_k2")
@@ -50,6 +58,9 @@ def lib():
         L.probe_run.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, c_double_p,
                                 C.POINTER(C.c_int32), C.c_char_p]
         L.probe_run.restype = C.c_int
+        L.probe_run_geom.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, C.c_int, c_double_p,
+                                     C.c_int, C.POINTER(C.c_int32), C.c_char_p]
+        L.probe_run_geom.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -84,6 +95,29 @@ def run(problem, op, e, x, device=True):
                                         out.ctypes.data_as(c_double_p), code.ctypes.data_as(ip))
         if r:
             raise RuntimeError("emul_probe_run(%s) failed: %d" % (op, r))
+    return out, code
+
+
+def run_geom(problem, op, x, e=0, device=True):
+    """Evaluates the geometry op ('segment', 'geom', 'bounce') on the rows x [n, GEOM_IN[op]]: (out [n, 8], code [n])."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, GEOM_IN[op])
+    n = x.shape[0]
+    e = np.ascontiguousarray(np.broadcast_to(np.asarray(e, dtype=np.int32), (n,)))
+    out = np.zeros((n, GEOM_OUT))
+    code = np.zeros(n, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    args = (C.byref(problem.s), GEOM_OPS[op], n, e.ctypes.data_as(ip), x.ctypes.data_as(c_double_p), GEOM_IN[op],
+            out.ctypes.data_as(c_double_p), GEOM_OUT, code.ctypes.data_as(ip))
+    if device:
+        err = C.create_string_buffer(256)
+        r = lib().probe_run_geom(*args, err)
+        if r:
+            raise RuntimeError("probe_run_geom(%s) failed: %d %s" % (op, r, err.value.decode(errors="replace")))
+    else:
+        from tests.emul import pyemul
+        r = pyemul.lib().emul_probe_run_geom(*args)
+        if r:
+            raise RuntimeError("emul_probe_run_geom(%s) failed: %d" % (op, r))
     return out, code
 
 

@@ -336,6 +336,29 @@ int emul_probe_run(const pc_hip_problem *p, int op, int64_t n, const int32_t *e,
 	return 0;
 }
 
+/* the host build of probe.hip's probe_run_geom: segment hit and normal, reflection geometry, bounce */
+int emul_probe_run_geom(const pc_hip_problem *p, int op, int64_t n, const int32_t *e, const double *in, int in_w, double *out,
+                        int out_w, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_geom_check(op, n, in_w, out_w, e, (int)E.t.ec.size())) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		double tab[PC_PROBE_SEG_TAB];
+		int cd = 0;
+		double *o = out + i*out_w;
+		for (int j = 0; j < out_w; j++) o[j] = 0.;
+		if (op == PC_PROBE_SEGMENT) {
+			if (pc_probe_seg_table(p, in + i*in_w, tab)) { code[i] = PC_PROBE_SETUP_REJECT; continue; }
+			pc_probe_geom_eval<PC_PROBE_SEGMENT>(E.t.ec[e[i]], in + i*in_w, tab, o, &cd);
+		} else if (op == PC_PROBE_GEOM) pc_probe_geom_eval<PC_PROBE_GEOM>(E.t.ec[e[i]], in + i*in_w, nullptr, o, &cd);
+		else pc_probe_geom_eval<PC_PROBE_BOUNCE>(E.t.ec[e[i]], in + i*in_w, nullptr, o, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
 /* the per-energy constants pc_build_tables derives (struct pc_energy_const, field by field): ne x 11 doubles */
 int emul_energy_consts(const pc_hip_problem *p, double *out)
 {

@@ -48,6 +48,9 @@ def lib():
         L.emul_probe_run.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, c_double_p,
                                      C.POINTER(C.c_int32)]
         L.emul_probe_run.restype = C.c_int
+        L.emul_probe_run_geom.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, C.c_int, c_double_p,
+                                          C.c_int, C.POINTER(C.c_int32)]
+        L.emul_probe_run_geom.restype = C.c_int
         L.emul_energy_consts.argtypes = [C.POINTER(ProblemS), c_double_p]
         L.emul_energy_consts.restype = C.c_int
         _LIB = L
