@@ -607,8 +607,14 @@ POLYCAP_EXTERN void pc_hip_select_transmission(size_t n_energies, const uint64_t
  * A scan is not a run: the last run's totals, moments, images, records, slot ids, leak events and what pc_hip_spot_add reads
  * stay as they were.  The scan is enqueued on the context's stream behind every launch of the last run (also when that run was
  * cut into parts on two streams) and keeps buffers of its own; a scan call waits for the context's previous scan first.
- * Scans with more than 8 energies use the immediate weight sweep (option "batch_reflections" 0): same results, slower than the
- * logging kernel.  Invalid arguments give PC_HIP_ERR_INVALID with a message that names the function and the field. */
+ * Scans with more than 8 energies use the immediate weight sweep by default: with roughness their weights are those of a run
+ * with option "batch_reflections" 0, which differ from a default run's in the last bits (~4e-14), and the sweep is slower than
+ * the logging kernel.  Option "scan_log" = 1 (pc_hip_set_option, pc_hip_group_set_option; default 0, other values are refused)
+ * sends a scan through the logging kernel when it can log -- the conditions are a source run's: more than 8 energies and at
+ * least "log_min_energies", "batch_reflections" and "lds_ec" on, a profile of at most 1024 points, every energy valid, a log
+ * stage that fits -- with a source run's log capacity, so that every point equals a run with default options bit for bit,
+ * roughness included.  A scan that cannot log keeps the lane kernel; pc_hip_scan_last_kernel says which one ran.
+ * Invalid arguments give PC_HIP_ERR_INVALID with a message that names the function and the field. */
 typedef struct { double d_source, src_shiftx, src_shifty; } pc_hip_scan_point;
 /* host only: d_source > 0 and finite, finite shifts, n_points >= 1, n_per_point >= 1, n_points * n_per_point fits in int64 */
 POLYCAP_EXTERN int pc_hip_scan_validate(const pc_hip_scan_point *points, int64_t n_points, int64_t n_per_point);
@@ -632,6 +638,10 @@ POLYCAP_EXTERN int pc_hip_group_scan_run(pc_hip_group *group, uint64_t seed, int
 	int64_t n_points, int64_t n_per_point, uint32_t max_attempts);
 POLYCAP_EXTERN int pc_hip_group_scan_wait(pc_hip_group *group, float *kernel_ms);
 POLYCAP_EXTERN int pc_hip_group_scan_totals(pc_hip_group *group, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed);
+/* the kernel that traced the context's last scan call (member k's share of the group's), in the codes of pc_hip_last_kernel: 0 the
+ * lane kernel, 4 the logging kernel; -1 before the first scan.  pc_hip_last_kernel goes on ignoring scans. */
+POLYCAP_EXTERN int pc_hip_scan_last_kernel(pc_hip_ctx *ctx);
+POLYCAP_EXTERN int pc_hip_group_scan_last_kernel(pc_hip_group *group, int k);
 
 /* ---- relays: the exit beam of one optic through a second one (a focusing lens and a second lens that looks at its focus:
  * confocal set-ups), without a per-photon copy to the host.  Context A holds the first optic and has just made a source run that

@@ -340,6 +340,10 @@ def lib():
     L.pc_hip_scan_run.restype = C.c_int
     L.pc_hip_scan_wait.argtypes = [C.c_void_p, P(C.c_float)]
     L.pc_hip_scan_wait.restype = C.c_int
+    L.pc_hip_scan_last_kernel.argtypes = [C.c_void_p]
+    L.pc_hip_scan_last_kernel.restype = C.c_int
+    L.pc_hip_group_scan_last_kernel.argtypes = [C.c_void_p, C.c_int]
+    L.pc_hip_group_scan_last_kernel.restype = C.c_int
     L.pc_hip_scan_totals.argtypes = [C.c_void_p, c_int64_p, u64p, u64p]
     L.pc_hip_scan_totals.restype = C.c_int
     L.pc_hip_scan_efficiencies.argtypes = [C.c_size_t, C.c_int64, c_int64_p, u64p, u64p, c_double_p, c_double_p]

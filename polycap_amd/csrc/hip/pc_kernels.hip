@@ -1158,6 +1158,10 @@ struct pc_hip_ctx {
 	pc_dev_buf<unsigned long long> d_scan_tot; /* per point: 6 counters, 2*ne weight sums, 2*ne squared-weight sums (pc_kargs::sumw of a scan) */
 	pc_dev_buf<pc_scan_point> d_scan_pts;
 	pc_dev_buf<double> d_scan_wscratch;    /* more than 8 energies: the scan kernel's per-lane weights */
+	pc_dev_buf<double> d_scan_rlog;        /* a scan through the logging kernel: its per-lane reflection logs */
+	int scan_log = 0;                      /* option "scan_log": scans that can log their reflections do (pc_plan_input::scan_log; kept here
+	                                        * because pc_launch_opts is the fixed list tests/plan/plan_host.cpp counts) */
+	int scan_kernel = -1;                  /* pc_hip_scan_last_kernel */
 	pc_event_handle ev_scan0, ev_scan1;
 	long long scan_points = 0;             /* points of the last scan call (0: none yet) */
 	int scan_squares = 0;                  /* the last scan summed the squared weights */
@@ -1253,7 +1257,8 @@ static void pc_sweep_certificate(pc_hip_ctx *ctx)
 }
 
 /* The one place a trace kernel is launched from: grows the per-lane scratch the plan asks for, copies the plan into the kernel
- * arguments, and launches between the context's events as far as the site wants them.  Only source runs have other than lane kernels. */
+ * arguments, and launches between the context's events as far as the site wants them.  Only source runs have other than lane kernels,
+ * and scans the logging kernel (option "scan_log"). */
 template <int MODE>
 static int pc_launch_planned(pc_hip_ctx *ctx, const pc_launch_site &site, const pc_launch_plan &p, pc_kargs &a)
 {
@@ -1262,12 +1267,14 @@ static int pc_launch_planned(pc_hip_ctx *ctx, const pc_launch_site &site, const 
 	constexpr bool CAN_SQ = MODE != PC_MODE_EXPLICIT;
 	/* a scan has buffers of its own, so that it leaves everything of the last run as it was */
 	pc_dev_buf<double> &wscratch = SCAN ? ctx->d_scan_wscratch : ctx->d_wscratch;
+	pc_dev_buf<double> &rlog = SCAN ? ctx->d_scan_rlog : ctx->d_rlog;
 	int st = wscratch.grow(p.half_w * (size_t)site.halves, SCAN ? "pc_hip_scan_run: could not allocate the per-lane weight scratch"
 	                                                            : "could not allocate the per-lane weight scratch");
-	if (!st) st = ctx->d_rlog.grow(p.half_l * (size_t)site.halves, "could not allocate the reflection logs");
+	if (!st) st = rlog.grow(p.half_l * (size_t)site.halves, SCAN ? "pc_hip_scan_run: could not allocate the reflection logs"
+	                                                             : "could not allocate the reflection logs");
 	if (st) return st;
 	if (p.half_w) a.wscratch = wscratch + (size_t)site.half * p.half_w;
-	if (p.half_l) a.rlog = ctx->d_rlog + (size_t)site.half * p.half_l;
+	if (p.half_l) a.rlog = rlog + (size_t)site.half * p.half_l;
 	a.total_threads = (long long)p.grid * p.block;
 	a.lds_acc = p.lds_acc; a.lds_ec = p.lds_ec; a.sweep_rough = p.sweep_rough;
 	a.event_threshold = p.event_threshold; a.new_threshold = p.new_threshold;
@@ -1295,7 +1302,7 @@ static int pc_launch_planned(pc_hip_ctx *ctx, const pc_launch_site &site, const 
 		}
 		break;
 	case PC_KERNEL_POOL: if constexpr (SOURCE) PC_GO_SQ(pc_trace_pool_kernel, MODE); break;
-	case PC_KERNEL_LOG: if constexpr (SOURCE) PC_GO_SQ(pc_trace_log_kernel, MODE); break;
+	case PC_KERNEL_LOG: if constexpr (SOURCE || SCAN) PC_GO_SQ(pc_trace_log_kernel, MODE); break;
 	case PC_KERNEL_PRODUCER:
 		if constexpr (SOURCE) {
 			if (p.sq) PC_GO(pc_trace_producer_kernel<MODE, false, true>);
@@ -1309,7 +1316,7 @@ static int pc_launch_planned(pc_hip_ctx *ctx, const pc_launch_site &site, const 
 	}
 #undef PC_GO_SQ
 #undef PC_GO
-	if (!SCAN) ctx->last_kernel = p.kernel;
+	if (SCAN) ctx->scan_kernel = p.kernel; else ctx->last_kernel = p.kernel;
 	PC_HIP_CHECK(hipGetLastError());
 	if (site.record_ev1) PC_HIP_CHECK(hipEventRecord(ctx->ev1, site.stream));
 	return PC_HIP_OK;
@@ -1330,6 +1337,7 @@ static int pc_launch_kernel(pc_hip_ctx *ctx, const pc_launch_site &site, pc_karg
 	in.n_items = n_items; in.n_slots = a.n_slots; in.max_attempts = a.max_attempts; in.keep_images = a.keep_images != 0;
 	in.squares = MODE != PC_MODE_EXPLICIT && ctx->opts.weight_squares != 0;
 	in.force_lane = site.force_lane; in.halves = site.halves;
+	in.scan_log = ctx->scan_log != 0;
 	return pc_launch_planned<MODE>(ctx, site, pc_plan_launch(in, ctx->opts), a);
 }
 
@@ -1450,6 +1458,7 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "flush_max") { if (value < 1 || value > 16) return pc_fail(PC_HIP_ERR_INVALID, "flush_max must be in [1,16]"); ctx->opts.flush_max = (int)value; }
 	else if (n == "sweep_exact_every") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "sweep_exact_every must be in [0,2^31-1] (0 = off)"); ctx->opts.sweep_exact_every = (int)value; }
 	else if (n == "weight_squares") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "weight_squares must be 0 or 1"); ctx->opts.weight_squares = (int)value; }
+	else if (n == "scan_log") { if (value < 0 || value > 1) return pc_fail(PC_HIP_ERR_INVALID, "scan_log must be 0 or 1"); ctx->scan_log = (int)value; }
 	else if (n == "sweep_fuse") { if (value < 0 || value > 2) return pc_fail(PC_HIP_ERR_INVALID, "sweep_fuse must be 0, 1 or 2"); ctx->opts.sweep_fuse = (int)value; }
 	else if (n == "plane_images") ctx->img.opts.plane_images = value ? 1 : 0;
 	else if (n == "compact_images") ctx->img.opts.compact_images = value ? 1 : 0;

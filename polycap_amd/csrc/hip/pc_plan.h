@@ -136,6 +136,7 @@ struct pc_plan_input {
 	long long n_slots = 0; unsigned int max_attempts = 1;     /* of pc_kargs, like keep_images */
 	bool keep_images = false, squares = false;      /* squares: the launch sums the squared weights */
 	bool force_lane = false; int halves = 1;        /* of the pc_launch_site */
+	bool scan_log = false;         /* context option "scan_log" (not one of pc_launch_opts): a scan that can log its reflections does */
 };
 
 /* ---- what a launch needs */
@@ -161,6 +162,7 @@ static pc_launch_plan pc_plan_launch(const pc_plan_input &in, const pc_launch_op
 	pc_launch_plan p;
 	const int ne = in.ne, cus = pc_plan_cus(o, in.n_cu);
 	const bool source = in.mode == PC_PLAN_SOURCE, short_profile = in.npts <= 1024;
+	const bool scan_log = in.mode == PC_PLAN_SCAN && in.scan_log;
 	/* u64 per energy of the exact sums a workgroup keeps in LDS: (lo, hi) of the weights, and of their squares with "weight_squares" */
 	const size_t acc_words = (source && in.squares) ? 4 : 2;
 	p.kne = (ne == 1) ? 1 : ((ne <= 4 && short_profile) ? 4 : ((ne <= 8 && short_profile) ? 8 : 0));
@@ -209,8 +211,12 @@ static pc_launch_plan pc_plan_launch(const pc_plan_input &in, const pc_launch_op
 			p.pool_event_min = o.pool_event_min; p.event_march = o.event_march;
 			return p;
 		}
-		/* source runs with more than 8 (valid) energies log their reflections (pc_trace_log_kernel); an explicit photon reports its
-		 * state at the absorbing reflection, which the logging kernel's speculation overwrites */
+	}
+	if (source || scan_log) {
+		/* source runs with more than 8 (valid) energies log their reflections (pc_trace_log_kernel), and so do scans with option
+		 * "scan_log", by the same rules: a point's log cuts, and with roughness its weights, are then those of a separate run.  (A scan's
+		 * sums are per point in global memory: the workgroup's sum area in LDS sits unused, the layout is the source runs'.)  An explicit
+		 * photon reports its state at the absorbing reflection, which the logging kernel's speculation overwrites */
 		const bool want_log = p.kne == 0 && o.lds_ec && short_profile && ne >= o.log_min_energies && o.batch_reflections && in.all_valid;
 		/* log capacity: 64 reflections (32 below 64 energies), halved while not even one log per wave fits in the stage beside
 		 * the constants of very many energies (beyond ~450) */

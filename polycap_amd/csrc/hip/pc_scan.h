@@ -1,8 +1,9 @@
 /*
- * pc_scan.h -- scans: transmission as a function of the source position, one launch of the lane kernel for a whole grid of
- * points with exact totals per point (include/polycap-hip.h, pc_hip_scan_*).  The kernel is pc_trace_kernel with MODE
- * PC_MODE_SCAN_CIRCULAR / _GENERIC (pc_kernels.hip); the mapping of a flat index to its point and the per-point source are
- * pc_scan_map / pc_sample_photon_at of pc_device.h.  Included at the end of pc_kernels.hip.
+ * pc_scan.h -- scans: transmission as a function of the source position, one launch for a whole grid of points with exact
+ * totals per point (include/polycap-hip.h, pc_hip_scan_*).  The kernel is pc_trace_kernel with MODE PC_MODE_SCAN_CIRCULAR /
+ * _GENERIC (pc_kernels.hip) or, with option "scan_log" and a plan that can log (pc_plan_launch), pc_trace_log_kernel with those
+ * modes (pc_sweep_kernel.h); the mapping of a flat index to its point and the per-point source are pc_scan_map /
+ * pc_sample_photon_at of pc_device.h.  Included at the end of pc_kernels.hip.
  */
 #ifndef PC_SCAN_H
 #define PC_SCAN_H
@@ -32,7 +33,7 @@ static int pc_scan_check(const char *fn, const pc_hip_scan_point *pts, int64_t n
 	return PC_HIP_OK;
 }
 
-/* device buffers of a scan of n_points points (the per-lane weights of more than 8 energies: pc_launch_planned) */
+/* device buffers of a scan of n_points points (the per-lane weights and reflection logs of more than 8 energies: pc_launch_planned) */
 static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points)
 {
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
@@ -111,7 +112,7 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	a.img_id0 = first;
 	a.img_n = n_per_point;
 	a.seed = seed; a.slot0 = slot0; a.n_slots = count; a.max_attempts = max_attempts; a.keep_images = 0;
-	/* the lane kernel in its scan mode (pc_plan_launch), between the scan's own events */
+	/* the lane kernel or the logging kernel in its scan mode (pc_plan_launch), between the scan's own events */
 	pc_launch_site site{ctx->stream};
 	site.record_ev0 = site.record_ev1 = false;
 	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan0, ctx->stream));
@@ -123,6 +124,16 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	ctx->scan_squares = ctx->opts.weight_squares ? 1 : 0;
 	ctx->scan_pending = 1;
 	return PC_HIP_OK;
+}
+
+int pc_hip_scan_last_kernel(pc_hip_ctx *ctx)
+{
+	return ctx ? ctx->scan_kernel : -1;
+}
+
+int pc_hip_group_scan_last_kernel(pc_hip_group *g, int k)
+{
+	return (g && k >= 0 && (size_t)k < g->ctx.size()) ? g->ctx[(size_t)k]->scan_kernel : -1;
 }
 
 int pc_hip_scan_totals(pc_hip_ctx *ctx, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed)

@@ -52,6 +52,10 @@
  *     hundred photons and the others none: the sweeps, 92 % of the work, are as efficient for three photons as for sixty-four.
  *   registers.  Two waves per SIMD (512-thread workgroups), 239 registers, no scratch; the FAST loop evaluates two reflections
  *     per step as two interleaved dependent chains (pc_fresnel3xN).
+ *   scans (context option "scan_log", pc_scan.h; MODE PC_MODE_SCAN_*).  A slot is a flat index of the scan; its point is recomputed
+ *     from it where needed.  The counters are kept per point as in pc_trace_kernel; the sums are the points' global 128-bit pairs
+ *     (the cooperative sweep of the NEW phase and the fused finalisation add to them, the take-back adds the two's complement),
+ *     the LDS sums sit unused.  247 registers, no scratch (circular source); profiles/scan_log_resources.txt.
  */
 #ifndef PCS_WAVES
 #define PCS_WAVES 2
@@ -70,7 +74,12 @@ template <int MODE, bool SQ = false>
 __global__ void __launch_bounds__(PCS_BLOCK, PCS_WAVES)
 pc_trace_log_kernel(pc_kargs a)
 {
-	static_assert(MODE != PC_MODE_EXPLICIT, "the log kernel serves source runs");
+	static_assert(MODE != PC_MODE_EXPLICIT, "the log kernel serves source runs and scans");
+	/* scans (option "scan_log"; pc_scan.h): everything of theirs is under `if constexpr (SCAN)`, so that the source runs'
+	 * instantiations compile to what they were.  A slot is a flat index of the scan (PC_SCAN_FIRST(a) + slot = point k, slot j:
+	 * pc_scan_map); the point is recomputed from the slot where it is needed instead of living in two more registers per lane */
+	constexpr bool SCAN = (MODE == PC_MODE_SCAN_CIRCULAR || MODE == PC_MODE_SCAN_GENERIC);
+	constexpr bool GENERIC = (MODE == PC_MODE_SRC_GENERIC || MODE == PC_MODE_SCAN_GENERIC);
 	__shared__ double lds[6*PCS_PITCH];
 	__shared__ pc_marg4 ldsg[PCS_PITCH];
 	extern __shared__ unsigned long long l_acc[];
@@ -134,6 +143,21 @@ pc_trace_log_kernel(pc_kargs a)
 	long long chunk_next = 0, chunk_end = 0;
 	unsigned long long u_exit = 0, u_not_entered = 0, u_not_trans = 0, u_irefl = 0, u_failed = 0, u_launch = 0;
 	unsigned long long st_march = 0, st_march_l = 0, st_event = 0, st_event_l = 0, st_new = 0, st_new_l = 0, st_pass = 0, st_iter = 0;
+	long long u_pt = -1;          /* scans: the point the wave-uniform counters belong to (-1: none yet) */
+	/* scans: adds the wave-uniform counters to point u_pt (and to the launch's totals, where a source run's go at its end) and
+	 * clears them.  A macro, as in pc_trace_kernel */
+#define PCS_SCAN_FLUSH() do { \
+		if (u_pt >= 0 && lane == 0) { \
+			unsigned long long *t_ = a.sumw + u_pt*(6 + 4*(long long)ne); \
+			if (u_exit) { atomicAdd(&t_[0], u_exit); atomicAdd(&a.totals->counters[0], u_exit); } \
+			if (u_not_entered) { atomicAdd(&t_[1], u_not_entered); atomicAdd(&a.totals->counters[1], u_not_entered); } \
+			if (u_not_trans) { atomicAdd(&t_[2], u_not_trans); atomicAdd(&a.totals->counters[2], u_not_trans); } \
+			if (u_irefl) { atomicAdd(&t_[3], u_irefl); atomicAdd(&a.totals->counters[3], u_irefl); } \
+			if (u_failed) { atomicAdd(&t_[4], u_failed); atomicAdd(&a.totals->counters[4], u_failed); } \
+			if (u_launch) { atomicAdd(&t_[5], u_launch); atomicAdd(&a.totals->counters[5], u_launch); } \
+		} \
+		u_exit = u_not_entered = u_not_trans = u_irefl = u_failed = u_launch = 0; \
+	} while (0)
 
 	/* ---------------- the sweep of the photons in mR (at most PS of this wave): stage their logs, multiply, verdicts */
 	auto sweep_round = [&](unsigned long long mR) __attribute__((always_inline)) {
@@ -152,6 +176,15 @@ pc_trace_log_kernel(pc_kargs a)
 		if (mine) {
 			map[rank] = (unsigned)lane | (ph.wset ? 0x40u : 0u) | (untame ? 0x80u : 0u) | ((unsigned)npend << 8) | (fin ? 0x10000u : 0u);
 			vflag[rank] = 0u; vcnt[rank] = 0u; vbad[rank] = 255u;
+			if constexpr (SCAN) {
+				/* a fused photon's point travels in vcnt (low half) and vbad (high half): those are read back only for a photon
+				 * whose log is untame, which a fused one's is not, and the EXACT loop leaves a fused photon's alone below */
+				if (fin) {
+					long long k, j;
+					pc_scan_map(PC_SCAN_FIRST(a) + slot, PC_SCAN_NPP(a), k, j);
+					vcnt[rank] = (unsigned)((unsigned long long)k & 0xffffffffull); vbad[rank] = (unsigned)((unsigned long long)k >> 32);
+				}
+			}
 		}
 		/* the lanes' log entries (global stores of the EVENT phases) have arrived; the tables above are visible to the wave */
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -257,7 +290,7 @@ pc_trace_log_kernel(pc_kargs a)
 					}
 				}
 				st_iter += (unsigned long long)n_pass;
-				if (act) {
+				if (act && !(SCAN && (info & 0x10000u))) {
 					atomicMax(&vcnt[qc], cnt);
 					if (bad != 255u) atomicMin(&vbad[qc], bad);
 				}
@@ -271,7 +304,18 @@ pc_trace_log_kernel(pc_kargs a)
 						/* the take-back subtracts exactly what the first pass added: the same w, so the same f and f2 (w < 2^-62: f = 0 and
 						 * w*w < 2^-124, f2 = 0 as well -- nothing to add or take back) */
 						const unsigned long long f2 = SQ ? pc_fix_sq(w) : 0ull;
-						if (!undo) {
+						if constexpr (SCAN) {
+							/* the point's global sums; the take-back adds the two's complement (f, f2 > 0 here) */
+							const long long k = (long long)(((unsigned long long)vbad[qc] << 32) | (unsigned long long)vcnt[qc]);
+							unsigned long long *t = a.sumw + k*(6 + 4*(long long)ne) + 6;
+							if (!undo) {
+								pc_atomic_add128(t + 2*ee, f, 0ull);
+								if (f2) pc_atomic_add128(t + 2*ne + 2*ee, f2, 0ull);
+							} else {
+								pc_atomic_add128(t + 2*ee, 0ull - f, ~0ull);
+								if (f2) pc_atomic_add128(t + 2*ne + 2*ee, 0ull - f2, ~0ull);
+							}
+						} else if (!undo) {
 							const unsigned long long old = atomicAdd(&l_acc[2*ee], f);
 							if (old + f < old) atomicAdd(&l_acc[2*ee + 1], 1ull);
 							if (f2) pc_lds_add128(&l_sq[2*ee], f2);
@@ -355,6 +399,14 @@ pc_trace_log_kernel(pc_kargs a)
 				if (!(fr_c >= a.ct_tame && fr_c <= 1.0 && fs >= 0. && fs <= 1.0000001 && fp >= -1.e-7 && fp <= 1.0000001)) untame = 1;
 				/* test hook (option sweep_exact_every): the logs of every N-th slot are swept by the EXACT loop all the same -- always
 				 * correct (EXACT adds the range tests only), and it makes passes that mix EXACT and FAST photons common */
+				if constexpr (SCAN) {
+					/* the slot of the separate run at the photon's point: slot0 + j */
+					if (a.sweep_exact_every > 0) {
+						long long k, j;
+						pc_scan_map(PC_SCAN_FIRST(a) + slot, PC_SCAN_NPP(a), k, j);
+						if ((a.slot0 + j) % a.sweep_exact_every == 0) untame = 1;
+					}
+				} else
 				if (a.sweep_exact_every > 0 && (a.slot0 + slot) % a.sweep_exact_every == 0) untame = 1;
 				if (lim == K) {
 					{
@@ -445,6 +497,10 @@ pc_trace_log_kernel(pc_kargs a)
 			long long done_slot = slot;
 			int ok = 0;                   /* the photon left through the exit window: src/polycap-source.c:758-777 */
 			const bool fin_now = state == LS_DONE && npend == 0;       /* finished photons whose logs are still to be swept wait */
+			long long pk = 0, pj = 0;     /* scans: point and slot in the point of the lane's slot (this phase only) */
+			if constexpr (SCAN) {
+				if (fin_now) pc_scan_map(PC_SCAN_FIRST(a) + slot, PC_SCAN_NPP(a), pk, pj);
+			}
 			if (fin_now) {
 				const int rc = ph.rc;
 				if (rc == 0) f_not_trans = 1;
@@ -500,11 +556,20 @@ pc_trace_log_kernel(pc_kargs a)
 					const int what = __shfl(coop, p, PC_WAVE);
 					const int wset_p = __shfl(ph.wset, p, PC_WAVE);
 					const long long slot_p = __shfl(done_slot, p, PC_WAVE);
+					long long k_p = 0;        /* scans: the photon's point */
+					if constexpr (SCAN) k_p = __shfl(pk, p, PC_WAVE);
 					const double *wp = a.wscratch + (wave_gtid0 + p)*(long long)ne;
 					for (int e = lane; e < ne; e += PC_WAVE) {
 						const double w = (what == 2) ? 0. : (wset_p ? wp[e] : 1.0);
 						if (what == 1) {
 							const unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
+							if constexpr (SCAN) {
+								if (f) {
+									unsigned long long *t = a.sumw + k_p*(6 + 4*(long long)ne) + 6;
+									pc_atomic_add128(t + 2*e, f, 0ull);
+									if (SQ) { const unsigned long long f2 = pc_fix_sq(w); if (f2) pc_atomic_add128(t + 2*ne + 2*e, f2, 0ull); }
+								}
+							} else
 							if (f) {
 								const unsigned long long old = atomicAdd(&l_acc[2*e], f);
 								if (old + f < old) atomicAdd(&l_acc[2*e + 1], 1ull);
@@ -512,6 +577,26 @@ pc_trace_log_kernel(pc_kargs a)
 							}
 						}
 						if (a.keep_images) { if (compact) pc_store_wt(a.img_w + slot_p*ws + e, w); else a.img_w[slot_p*ws + e] = w; }
+					}
+				}
+			}
+			if constexpr (SCAN) {
+				/* the finished photons' counters, point by point over the lanes that share one (pc_trace_kernel does the same) */
+				const bool has = (f_exit | f_not_entered | f_not_trans | f_failed) != 0;
+				unsigned long long pend = __ballot(has);
+				while (pend) {
+					const long long k = __shfl(pk, __ffsll((long long)pend) - 1, PC_WAVE);
+					const bool mine = has && pk == k;
+					pend &= ~__ballot(mine);
+					if (k != u_pt) { PCS_SCAN_FLUSH(); u_pt = k; }
+					u_not_trans += (unsigned long long)__popcll(__ballot(mine && f_not_trans));
+					u_not_entered += (unsigned long long)__popcll(__ballot(mine && f_not_entered));
+					u_failed += (unsigned long long)__popcll(__ballot(mine && f_failed));
+					const bool mx = mine && f_exit;
+					const unsigned long long mX = __ballot(mx);
+					if (mX) {
+						u_exit += (unsigned long long)__popcll(mX);
+						u_irefl += pc_wave_sum_u64(mx ? (unsigned long long)f_irefl : 0ull);
 					}
 				}
 			}
@@ -552,7 +637,10 @@ pc_trace_log_kernel(pc_kargs a)
 					}
 					if (state == LS_NEED_SLOT) {
 						if (slot >= a.n_slots) { state = LS_IDLE; }
-						else { attempt = 0; state = LS_START; }
+						else {
+							attempt = 0; state = LS_START;
+							if constexpr (SCAN) pc_scan_map(PC_SCAN_FIRST(a) + slot, PC_SCAN_NPP(a), pk, pj);
+						}
 					}
 				}
 			}
@@ -560,6 +648,12 @@ pc_trace_log_kernel(pc_kargs a)
 			if (state == LS_START) {
 				f_launch = 1;
 				pc_start s;
+				if constexpr (SCAN) {
+					/* a lane that starts an attempt has its point from this phase: a new slot's from the hand-out, a retry's from
+					 * the finalisation above */
+					const pc_scan_point pt = PC_SCAN_PTS(a)[pk];
+					pc_sample_photon_at<GENERIC>(Pm, pt.d_source, pt.src_shiftx, pt.src_shifty, a.seed, (unsigned long long)(a.slot0 + pj), attempt, s);
+				} else
 				pc_sample_photon<MODE == PC_MODE_SRC_GENERIC>(Pm, a.seed, (unsigned long long)(a.slot0 + slot), attempt, s);
 				state = pc_launch_init(T, Pm, ph, s.x, s.y, s.z, s.dx, s.dy, s.dz, s.ex, s.ey, s.ez);
 				npend = 0; untame = 0; lim = K; okpre = -1; summed = 0;
@@ -578,6 +672,17 @@ pc_trace_log_kernel(pc_kargs a)
 					}
 				}
 			}
+			if constexpr (SCAN) {
+				/* the finished photons' counters went to their points above; the launches belong to the points of the lanes' slots now */
+				unsigned long long pend = __ballot(f_launch);
+				while (pend) {
+					const long long k = __shfl(pk, __ffsll((long long)pend) - 1, PC_WAVE);
+					const unsigned long long grp = __ballot(f_launch && pk == k);
+					pend &= ~grp;
+					if (k != u_pt) { PCS_SCAN_FLUSH(); u_pt = k; }
+					u_launch += (unsigned long long)__popcll(grp);
+				}
+			} else {
 			u_not_trans += (unsigned long long)__popcll(__ballot(f_not_trans));
 			u_not_entered += (unsigned long long)__popcll(__ballot(f_not_entered));
 			u_failed += (unsigned long long)__popcll(__ballot(f_failed));
@@ -587,15 +692,22 @@ pc_trace_log_kernel(pc_kargs a)
 				u_exit += (unsigned long long)__popcll(mX);
 				u_irefl += pc_wave_sum_u64((unsigned long long)f_irefl);
 			}
+			}
 		}
 	}
 
+	if constexpr (SCAN) {
+		/* the sums went to their points as they were made (the workgroup's LDS sums sit unused); what is left of the counters */
+		PCS_SCAN_FLUSH();
+	} else {
 	__syncthreads();          /* every wave of the workgroup has finished its photons */
 	for (int e = threadIdx.x; e < ne; e += blockDim.x)
 		if (l_acc[2*e] | l_acc[2*e + 1]) pc_atomic_add128(a.sumw + 2*e, l_acc[2*e], l_acc[2*e + 1]);
 	if (SQ)
 		for (int e = threadIdx.x; e < ne; e += blockDim.x)
 			if (l_sq[2*e] | l_sq[2*e + 1]) pc_atomic_add128(a.sumw2 + 2*e, l_sq[2*e], l_sq[2*e + 1]);
+	}
+#undef PCS_SCAN_FLUSH
 	if (lane == 0) {
 		atomicAdd(&a.totals->counters[0], u_exit);
 		atomicAdd(&a.totals->counters[1], u_not_entered);

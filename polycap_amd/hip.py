@@ -71,7 +71,8 @@ class TraceContext:
         [P, 3] of (d_source, src_shiftx, src_shifty), e.g. from scan_points() (NaN d_source = the problem's own); n_per_point
         slots per point, slot j of every point on the stream of slot slot0 + j; the flat indices [first, first + count) are traced
         (default: all).  Returns counters [P, 6], sumw_fixed [P, ne, 2], sumw2_fixed (option "weight_squares") or None,
-        efficiencies [P, ne], stderr [P, ne] or None, kernel_ms."""
+        efficiencies [P, ne], stderr [P, ne] or None, kernel_ms, kernel (the name of the kernel that traced the scan, from
+        KERNELS: with more than 8 energies the logging kernel if option "scan_log" is 1 and the scan can log)."""
         pts = _scan_array(points, self.problem)
         n_pts = pts.shape[0]
         count = n_pts * int(n_per_point) - int(first) if count is None else int(count)
@@ -85,6 +86,7 @@ class TraceContext:
             raise HipError("pc_hip_scan_wait", st)
         r = _scan_fetch(self._L.pc_hip_scan_totals, self._h, n_pts, self.problem.n_energies, getattr(self, "_weight_squares", False))
         r["kernel_ms"] = float(ms.value)
+        r["kernel"] = self.KERNELS.get(int(self._L.pc_hip_scan_last_kernel(self._h)))
         return r
 
     def device_synchronize(self):
@@ -375,7 +377,8 @@ class TraceGroup:
 
     def scan(self, seed, points, n_per_point, max_attempts=1, slot0=0):
         """TraceContext.scan over the group: the flat range [0, P * n_per_point) is split into one contiguous piece per member
-        (pc_hip_group_scan_run) and the members' totals are added exactly; kernel_ms is the longest member's."""
+        (pc_hip_group_scan_run) and the members' totals are added exactly; kernel_ms is the longest member's, kernel the list
+        of the members' kernel names."""
         pts = _scan_array(points, self.problem)
         n_pts = pts.shape[0]
         st = self._L.pc_hip_group_scan_run(self._h, int(seed), int(slot0), dptr(pts), n_pts, int(n_per_point), int(max_attempts))
@@ -387,6 +390,8 @@ class TraceGroup:
             raise HipError("pc_hip_group_scan_wait", st)
         r = _scan_fetch(self._L.pc_hip_group_scan_totals, self._h, n_pts, self.problem.n_energies, getattr(self, "_weight_squares", False))
         r["kernel_ms"] = float(ms.value)
+        n = int(self._L.pc_hip_group_size(self._h))
+        r["kernel"] = [TraceContext.KERNELS.get(int(self._L.pc_hip_group_scan_last_kernel(self._h, k))) for k in range(n)]
         return r
 
     def last_kernels(self):
