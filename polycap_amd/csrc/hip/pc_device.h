@@ -698,6 +698,10 @@ PC_HD int pc_segment(const pc_tables &T, const pc_photon<NE> &ph, int i,
 	double c = fma(qx, qx, fma(qy, qy, -R0*R0));
 	double discr = fma(b, b, -4.*a*c);
 	if (discr < 0) return -2;
+	/* a ray exactly as steep as the wall (a cylinder's segment and a ray parallel to its axis: a = b = 0): the reference's
+	 * quotients are 0 * inf, the NaN passes every comparison below and would come out as a hit at NaN.  With a = 0 and c < 0
+	 * the photon is inside the capillary, which is what the certified march finds at the two nodes: a miss, as there. */
+	if (a == 0.) return -3;
 	double last = ph.Pz;
 	const double i2a = 1.0/(2.*a);
 	if (discr == 0) {

@@ -94,7 +94,9 @@ static inline int pc_build_tables(const pc_hip_problem *p, pc_host_tables &t, st
 		if (!(e > 0.)) ratio = HUGE_VAL;          /* degenerate exterior: keep every hexagon test literal */
 	}
 	double m = std::fmax(1e-6*capmin*capmin, 1e-10*capmax*extmax);
-	pm.adj = 0.25*dr2max + m;
+	/* rounded up: dr, its square, m and the sum are each rounded to nearest (fewer than eight roundings of 2^-53 in all), and the
+	 * margin must not come out below dR^2max/4 + m */
+	pm.adj = (0.25*dr2max + m) * (1. + 4e-15);
 	pm.two_rmax = 2.*capmax;
 	/* float copies for the comparisons of pc_march_ok: rounded up, then inflated */
 	pm.adjf = std::nextafter((float)pm.adj, HUGE_VALF) * PC_MARGIN_INFLATE;

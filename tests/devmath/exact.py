@@ -394,3 +394,151 @@ def unit(v):
     with mp.workdps(GDPS):
         l = mp.sqrt(_dot(v, v))
         return [float(t / l) for t in v]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The certified march in rational arithmetic (tests/test_devmath_march_cpu.py).  Every double is an exact rational and
+# g_j(z) = |p(z) - (kx, ky) zh(z)|^2 - R(z)^2 is a polynomial in them, so nothing below has a tolerance.  The ray is the photon's
+# own: the line through the row's start P along the normalised direction d the probe reports -- not the rounded ox, oy, sx, sy
+# the certificates evaluate (the margin m exists to cover that difference).  zh and R are piecewise linear in the table doubles.
+# To keep every number dyadic (no division before the very end) g is carried as G = dz^2 g, which has g's sign.
+from fractions import Fraction
+
+TEN_MU = Fraction(1.0e-5)          # the double the code adds to P.z and the reference compares with (src/polycap-capil.c:134-171)
+
+
+def fr(x):
+    return Fraction(float(x))
+
+
+def march_profile(t):
+    """exact rationals of the tables of pyemul.march_tables"""
+    return {k: [fr(v) for v in t[k]] for k in ("z", "cap", "ext", "zh")}
+
+
+def admissible_from(Pz):
+    """Where the admissible range of the first segment of a flight begins, as a rational.  The reference admits a root zr (a
+    double) when fl(zr - P.z) >= 1e-5, which zr - P.z >= 1e-5 (1 - 2^-53) already allows; pc_march_first_ok starts its range at
+    the double fl(P.z + 1e-5), which may lie below P.z + 1e-5.  The smaller of P.z + 1e-5 (1 - 2^-52) and fl(P.z + 1e-5) is taken:
+    the range tested is then at least as wide as the reference's and as the code's own, so the maximum of g over it is at least
+    theirs -- the strict side for a test that asserts max g < 0."""
+    Pz = float(Pz)
+    return min(fr(Pz) + TEN_MU * (1 - Fraction(1, 2 ** 52)), fr(Pz + 1.0e-5))
+
+
+def _dy(x):
+    """a double as (integer, e) with x = integer / 2^e"""
+    n, d = float(x).as_integer_ratio()
+    return n, d.bit_length() - 1
+
+
+def _scaled(vals):
+    """doubles as integers over one common power of two: ([v 2^e], e)"""
+    pairs = [_dy(v) for v in vals]
+    e = max(q for _, q in pairs)
+    return [n << (e - q) for n, q in pairs], e
+
+
+class MarchRay:
+    """The exact ray of one MARCH row on one profile and the exact maximum of g per segment.  Doubles are dyadic, so all of it is
+    integer arithmetic over common powers of two (lengths over 2^E, the direction over 2^Ed, k over 2^Ek); a Fraction is formed
+    of the result only."""
+
+    def __init__(self, prof, P, d, k):
+        self.prof = prof
+        n = len(prof["z"])
+        ints, self.E = _scaled([float(v) for key in ("z", "zh", "cap") for v in prof[key]] + [float(v) for v in P])
+        self.z, self.zh, self.R, self.P = ints[:n], ints[n:2 * n], ints[2 * n:3 * n], ints[3 * n:]
+        self.d, self.Ed = _scaled(d)
+        self.k, self.Ek = _scaled(k)
+        # G = dz^2 g over 2^(2 (E + Ed + Ek)); g = G_int / den
+        self.den = self.d[2] * self.d[2] << (2 * (self.E + self.Ek))
+        self._Q = {}
+
+    def Q(self, j):
+        """dz (P_xy - k zh_j) + d_xy (z_j - P_z), over 2^(E + Ed + Ek): dz times the ray's offset from the capillary axis at node j"""
+        if j not in self._Q:
+            zh, dzj = self.zh[j], (self.z[j] - self.P[2]) << self.Ek
+            self._Q[j] = (self.d[2] * ((self.P[0] << self.Ek) - self.k[0] * zh) + self.d[0] * dzj,
+                          self.d[2] * ((self.P[1] << self.Ek) - self.k[1] * zh) + self.d[1] * dzj)
+        return self._Q[j]
+
+    def max_g(self, j, z_from=None):
+        """(max of g over segment j from z_from (a rational; None: the segment's first node) to its last node, u of the maximum),
+        None when that range is empty.  g(u) = A u^2 + B u + C on u = (z - z_j)/(z_j+1 - z_j): the ends, and the vertex when
+        A < 0 puts it inside."""
+        (ax, ay), (bx, by) = self.Q(j), self.Q(j + 1)
+        ex, ey = bx - ax, by - ay
+        s = self.d[2] << self.Ek                     # dz R over 2^(E + Ed + Ek) is s R_int
+        R0, dR = s * self.R[j], s * (self.R[j + 1] - self.R[j])
+        A = ex * ex + ey * ey - dR * dR
+        B = 2 * (ax * ex + ay * ey - R0 * dR)
+        Cc = ax * ax + ay * ay - R0 * R0
+        lo = 0
+        if z_from is not None:
+            zf = z_from * (1 << self.E)
+            if zf > self.z[j]:
+                lo = (zf - self.z[j]) / (self.z[j + 1] - self.z[j])
+                if lo >= 1:
+                    return None
+        best, at = (A * lo + B) * lo + Cc, lo
+        g1 = A + B + Cc
+        if g1 > best:
+            best, at = g1, 1
+        if A < 0 and B > 0:
+            u = Fraction(-B, 2 * A)
+            if lo < u < 1:
+                gv = Cc - Fraction(B * B, 4 * A)
+                if gv > best:
+                    best, at = gv, u
+        return Fraction(best) / self.den, Fraction(at)
+
+
+def march_table_bounds(t):
+    """What the certificate tables of pyemul.march_tables must be at least, exactly: m = max(1e-6 capmin^2, 1e-10 capmax extmax)
+    with the two constants as the doubles the setup multiplies with; adj = dR^2max/4 + m; and per stride L (PC_L1, PC_L2) and
+    start node i whose block fits: the chord deviation Dzh of zh (a piecewise linear table deviates most from a chord at a node),
+    the base dR^2/4 + 2 R_blk DR + m with DR the chord deviation of cap and R_blk the largest radius of the block, and 2 R_blk;
+    r2 also covers the clipped PC_L2 block of a start node near the end."""
+    p = march_profile(t)
+    z, cap, ext, zh = p["z"], p["cap"], p["ext"], p["zh"]
+    n = len(z)
+    m = max(fr(1e-6) * min(cap) ** 2, fr(1e-10) * max(cap) * max(abs(e) for e in ext))
+    dr2max = max((cap[i + 1] - cap[i]) ** 2 for i in range(n - 1))
+    out = dict(m=m, adj=dr2max / 4 + m, L={}, r2=[2 * max(cap[i:min(n, i + t["L2"] + 1)]) for i in range(n)])
+    for L in (t["L1"], t["L2"]):
+        rows = []
+        for i in range(n):
+            if i + L >= n:
+                rows.append(None)
+                continue
+            span = z[i + L] - z[i]
+            dzh = dr = Fraction(0)
+            for j in range(i + 1, i + L):
+                u = (z[j] - z[i]) / span
+                dzh = max(dzh, abs(zh[j] - (zh[i] + (zh[i + L] - zh[i]) * u)))
+                dr = max(dr, abs(cap[j] - (cap[i] + (cap[i + L] - cap[i]) * u)))
+            rblk = max(cap[i:i + L + 1])
+            dR = cap[i + L] - cap[i]
+            rows.append(dict(md=dzh, mb=dR * dR / 4 + 2 * rblk * dr + m, r2=2 * rblk))
+        out["L"][L] = rows
+    return out
+
+
+def circle_inside_hexagon(cx, cy, cap, ext):
+    """Exactly: the circle of radius cap about (cx, cy) lies strictly inside the hexagon of circum-radius ext > 0 with corners on
+    the x axis (polycap_photon_within_pc_boundary): for the three edge normals (0, 1), (sqrt 3/2, +-1/2) and both signs,
+    sqrt3/2 ext - sigma n.c - cap > 0.  The root is removed by comparing squares: sqrt3 alpha > beta."""
+    def s3_gt(alpha, beta):            # sqrt(3) * alpha > beta
+        if alpha > 0:
+            return beta < 0 or 3 * alpha * alpha > beta * beta
+        return beta < 0 and 3 * alpha * alpha < beta * beta
+    if not ext > 0:
+        return False
+    for sg in (1, -1):
+        if not s3_gt(ext, 2 * (cap + sg * cy)):                       # sqrt3/2 ext > cap + sg cy
+            return False
+        for t in (1, -1):                                             # sqrt3/2 (ext - sg cx) > cap + sg t cy / 2
+            if not s3_gt(ext - sg * cx, 2 * cap + sg * t * cy):
+                return False
+    return True

@@ -336,3 +336,283 @@ def geom_rows():
             for a in 10.0 ** np.arange(-13, 0.0, 1.0):
                 add("axis_d", a, _den_row(da, a, 0.4, rng, u=ua))
     return np.array(rows, dtype=np.float64), np.array(fam), np.array(alf)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The march grids (op MARCH, tests/test_devmath_march_cpu.py): whole profiles of at most 64 nodes and photons aimed at the
+# places where a certificate could be wrong.  Deterministic: no random numbers at all.
+#
+# Geometry that shapes the rays.  Within one segment the ray's offset from the axis is linear in z and so is R, hence the gap
+# R - |q| is concave there: over any stretch of a profile the closest approach to the wall lies at a node, and a closest approach
+# "mid-segment" exists only as a ray parallel to that segment's wall (the gap is then delta cap all along it).  So:
+#   end    the ray closes in on the wall at rate s (the grazing slope, relative to the steepest wall on its way) and is
+#          delta cap from it at node t, the end of a would-be block (t = i + L - 1, i + L, i + L + 1 for L = PC_L1, PC_L2);
+#          delta < 0: it has crossed the wall by |delta| cap there, i.e. just before t
+#   mid    delta > 0: parallel to the wall of one segment, delta cap from it; delta < 0: crosses that segment's wall at its middle
+#   kink   delta cap from the wall at the kink node, where the wall sticks into blocks whose ends look safe
+#   axis   parallel to z through the capillary's centre, from z = 0, from z > 0, and flying backwards (dz < 0)
+#   first  starts on the axis with P.z + 1e-5 just below, at and beyond the next node
+# A row is left out where doubles cannot place it: |delta| cap below 64 times the rounding of the start point and direction.
+MARCH_DELTAS = (1e-12, -1e-12, 1e-9, -1e-9, 1e-6, -1e-6, 1e-3, -1e-3, 1e-1)
+MARCH_SLOPES = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 3e-2)
+MARCH_K = 64
+M_DZ, M_CAP, M_EXT, M_NS = 0.008, 4.0e-3, 0.11, 10
+M_KINK = 31
+PHI = 0.7                      # radial direction of the rays of capillaries that have no preferred one
+
+
+def _n_cap(ns):
+    return 3 * ns * (ns + 1) + 1
+
+
+def march_problem(z, cap, ext, n_cap):
+    import polycap_amd
+    from tests.common import synthetic_constants
+    E = np.array([10.0])
+    amu, scatf = synthetic_constants(E)
+    return polycap_amd.Problem(z, cap, ext, 0.0, n_cap, 2.23, E, amu, scatf)
+
+
+def march_profiles():
+    """name -> dict(z, cap, ext, ns, kink, rays): the profiles of the issue.  `rays` names the ray families a profile gets."""
+    P = {}
+    n = 62                     # at most nmax + 2 passes per row (every segment on its own, one lowered stride, the exit): K = 64
+    j = np.arange(n)
+    z = M_DZ * j
+    u = z / z[-1]
+    one = np.ones(n)
+    full = ("axis", "first", "end", "mid")
+
+    def put(name, z, f_cap, f_ext=None, ns=M_NS, cap0=M_CAP, ext0=M_EXT, kink=None, rays=full):
+        f_ext = f_cap if f_ext is None else f_ext
+        P[name] = dict(z=np.asarray(z, dtype=np.float64), cap=cap0 * np.asarray(f_cap), ext=ext0 * np.asarray(f_ext), ns=ns,
+                       kink=kink, rays=rays)
+
+    put("cylinder", z, one)
+    put("taper", z, 1 - 0.6 * u)
+    put("bulge", z, 0.6 + 0.4 * np.sqrt(1 - 0.96 * (2 * u - 1) ** 2))
+    f = one.copy()
+    f[M_KINK] = 0.7
+    put("cap_kink", z, f, one, kink=M_KINK, rays=full + ("kink",))
+    # a large n_cap: |k| of the outer shells is about 500, the axis of such a capillary steps sideways by 0.3 cap at the node
+    ns, cap0, ext0 = 300, 8.0e-4, 0.6
+    f = one.copy()
+    f[M_KINK] = 1 + 0.3 * cap0 * (ns + 1) / (ns * ext0)
+    put("ext_kink", z, one, f, ns=ns, cap0=cap0, ext0=ext0, kink=M_KINK, rays=full + ("kink",))
+    # neighbouring segment lengths in ratio up to 1e4
+    dz = np.array([M_DZ * (1e-4, 1.0, 1e-2, 1.0, 1e-3, 0.5, 1.0)[k % 7] for k in range(n - 1)])
+    zi = np.concatenate([[0.0], np.cumsum(dz)])
+    put("irregular", zi, 1 - 0.3 * zi / zi[-1])
+    for nm in (1, 4, 5, 6, 24, 25, 26):
+        zz = M_DZ * np.arange(nm + 1)
+        put("nmax%d" % nm, zz, 1 - 0.3 * zz / zz[-1], rays=("axis", "last"))
+    put("tiny", z, 1 - 0.3 * u, one, cap0=1.0e-6, ext0=1.0, rays=("axis", "first", "end"))
+    put("last_zero", z, 1 - u, 1 - 0.5 * u, rays=("axis", "end"))
+    put("mono", z, 1 - 0.3 * u, ns=0, ext0=5.0e-3, rays=("axis", "first", "end", "mid"))
+    return P
+
+
+def march_capillaries(ns):
+    """(name, q, r): the centre, a middle shell, the outermost shell that is still classed non-boundary, and a boundary shell
+    (its centres lie on the outer hexagon)"""
+    if ns == 0:
+        return [("centre", 0, 0)]
+    a = int(round(0.3 * ns))
+    return [("centre", 0, 0), ("middle", a, a - 1), ("outer", -a, ns), ("boundary", -a, ns + 1)]
+
+
+def _ulp(x):
+    return float(np.spacing(abs(float(x))))
+
+
+class _Builder:
+    def __init__(self, name, prof):
+        from fractions import Fraction as F
+        self.F = F
+        self.name, self.prof = name, prof
+        self.z, self.cap, self.ext = prof["z"], prof["cap"], prof["ext"]
+        self.nmax = len(self.z) - 1
+        self.hexscale = 2.0 * 0.86602540378443864676 * (prof["ns"] + 1)
+        self.zh = self.ext / self.hexscale          # as pc_build_tables forms it (asserted against the accessor by the tests)
+        self.rows, self.meta = [], []
+
+    def k(self, q, r):
+        return ((2.0 * q + r) * 0.86602540378443864676, r * 1.5)
+
+    def axis_slope(self, k, j):
+        s = (self.zh[j + 1] - self.zh[j]) / (self.z[j + 1] - self.z[j])
+        return np.array([k[0] * s, k[1] * s])
+
+    def at(self, tab, zv):
+        return float(np.interp(zv, self.z, tab))
+
+    def seg_of(self, zv):
+        return int(min(self.nmax - 1, max(0, np.searchsorted(self.z, zv, side="right") - 1)))
+
+    def radial(self, capname, k):
+        kn = float(np.hypot(*k))
+        if kn > 0 and (capname == "boundary" or self.name == "ext_kink"):
+            return np.array([-k[0] / kn, -k[1] / kn])           # towards the optic's axis: where an ext kink pushes the wall in
+        return np.array([np.cos(PHI), np.sin(PHI)])
+
+    def add(self, capname, k, fam, P, d, delta=0.0, block=(0, 0), tnode=-1, s=0.0):
+        self.rows.append([P[0], P[1], P[2], d[0], d[1], d[2], 0.3, 0.5, 0.1, 0.0, float(MARCH_K)])
+        self.meta.append(dict(profile=self.name, cap=capname, k=k, fam=fam, delta=delta, block=block, tnode=tnode, s=s))
+
+    def aimed(self, capname, k, fam, zt, rt, D, zs, delta, block, tnode, s, flip=False):
+        """the ray with xy slope D that is at c(zt) + e rt at z = zt, started at zs: P in rational arithmetic, rounded once"""
+        F = self.F
+        e = self.radial(capname, k)
+        zh_t = F(self.at(self.zh, zt))
+        tgt = [F(k[0]) * zh_t + F(float(e[0])) * F(rt), F(k[1]) * zh_t + F(float(e[1])) * F(rt)]
+        back = F(zt) - F(zs)
+        P = [float(tgt[0] - F(float(D[0])) * back), float(tgt[1] - F(float(D[1])) * back), float(zs)]
+        # can doubles place it?  rounding of P, and of the direction's normalisation over the distance flown
+        noise = _ulp(max(abs(P[0]), abs(P[1]), abs(rt))) + 2.0 ** -52 * float(np.hypot(*D)) * float(back)
+        if delta != 0.0 and abs(delta) * self.at(self.cap, zt) < 64 * noise:
+            return False
+        d = [float(D[0]), float(D[1]), 1.0]
+        if flip:
+            d = [-v for v in d]
+        self.add(capname, k, fam, P, d, delta, block, tnode, s)
+        return True
+
+    def start_for(self, capname, k, zt, rt, D, first_choice, lo_frac, need):
+        """the earliest start among first_choice and the middles of the later segments at which the ray lies inside the capillary
+        by at least half of what it was built to (need(zt - zs)), its offset along e no further back than lo_frac R"""
+        e = self.radial(capname, k)
+        cands = [first_choice] + [0.5 * (self.z[j] + self.z[j + 1]) for j in range(self.seg_of(first_choice) + 1, self.seg_of(zt))]
+        cands.append(zt - 0.25 * (zt - self.z[max(0, self.seg_of(zt) - (1 if zt == self.z[self.seg_of(zt)] else 0))]))
+        ct = np.array(k) * self.at(self.zh, zt)
+        for zs in cands:
+            if not zs < zt:
+                continue
+            p = ct + e * rt - np.asarray(D) * (zt - zs)
+            q = p - np.array(k) * self.at(self.zh, zs)
+            R = self.at(self.cap, zs)
+            gap = R - float(np.hypot(*q))
+            if gap > 0 and gap >= 0.5 * need(zt - zs) and float(q @ e) >= lo_frac * R:
+                return zs
+        return None
+
+    def closing_rate(self, k, ja, jb, jt):
+        """steepest wall seen from the ray's frame over segments [ja, jb): dR/dz plus the bend of the axis against segment jt's"""
+        ct = self.axis_slope(k, jt)
+        w = 0.0
+        for j in range(ja, jb):
+            dz = self.z[j + 1] - self.z[j]
+            w = max(w, (self.cap[j + 1] - self.cap[j]) / dz + float(np.hypot(*(self.axis_slope(k, j) - ct))))
+        return w
+
+
+def _march_rows_of(name, prof):
+    B = _Builder(name, prof)
+    nmax, z, cap = B.nmax, B.z, B.cap
+    L1, L2 = 5, 25
+    count = 0
+    for capname, q, r in march_capillaries(prof["ns"]):
+        k = B.k(q, r)
+        bnd = capname == "boundary"
+        lo_frac = 0.05 if bnd else -0.9
+        e = B.radial(capname, k)
+        inward = e * (0.5 if bnd else 0.0)          # a boundary capillary's centre lies on the hexagon: stay on its inner half
+
+        def on_axis(zs):
+            c = np.array(k) * B.at(B.zh, zs) + inward * B.at(B.cap, zs)
+            return [float(c[0]), float(c[1]), float(zs)]
+
+        if "axis" in prof["rays"]:
+            B.add(capname, k, "axis", on_axis(0.0), [0.0, 0.0, 1.0])
+            if nmax >= 3:
+                zs = 0.5 * (z[1] + z[2])
+                B.add(capname, k, "axis", on_axis(zs), [0.0, 0.0, 1.0])
+                B.add(capname, k, "axis_back", on_axis(zs), [0.0, 0.0, -1.0])
+        if "first" in prof["rays"]:
+            base = z[3] - 1.0e-5
+            at = base
+            for _ in range(8):                       # the double whose sum with 1e-5 rounds to the node itself
+                if at + 1.0e-5 == z[3]:
+                    break
+                at = float(np.nextafter(at, 1.0 if at + 1.0e-5 < z[3] else 0.0))
+            for zs in (base - 1e-9, float(np.nextafter(at, 0.0)), at, float(np.nextafter(at, 1.0)), base + 1e-9, base - 1.0e-5):
+                D = B.axis_slope(k, 2) + 1e-4 * e
+                B.add(capname, k, "first", on_axis(zs), [float(D[0]), float(D[1]), 1.0])
+
+        def end_family(i0, t, fam, deltas):
+            nonlocal count
+            if t > nmax or t < 1 or not cap[t] > 0:
+                return
+            for delta in deltas:
+                s = MARCH_SLOPES[count % len(MARCH_SLOPES)]
+                count += 1
+                first = 0.0 if i0 <= 1 else 0.5 * (z[i0 - 1] + z[i0])
+                W = B.closing_rate(k, B.seg_of(first), t, t - 1)
+                D = B.axis_slope(k, t - 1) + (W + s) * e
+                rt = cap[t] * (1 - delta)
+                zs = B.start_for(capname, k, z[t], rt, D, first, lo_frac, lambda back: delta * cap[t] + s * back)
+                if zs is None:
+                    continue
+                B.aimed(capname, k, fam, z[t], rt, D, zs, delta, (B.seg_of(zs), t), t, s)
+                if fam == "end_L2" and t == i0 + L2 and delta in (1e-9, -1e-9):
+                    B.aimed(capname, k, fam + "_back", z[t], rt, D, zs, delta, (B.seg_of(zs), t), t, s, flip=True)
+
+        if "end" in prof["rays"]:
+            for L, i0, fam in ((L1, 1, "end_L1"), (L2, 2, "end_L2")):
+                for t in (i0 + L - 1, i0 + L, i0 + L + 1):
+                    end_family(i0, t, fam, MARCH_DELTAS)
+        if "last" in prof["rays"]:
+            end_family(0, nmax, "last", (1e-9, -1e-9, 1e-6, -1e-6, 1e-3, -1e-3))
+        if "mid" in prof["rays"]:
+            js = 14
+            zt = 0.5 * (z[js] + z[js + 1])
+            Rt = B.at(cap, zt)
+            w = (cap[js + 1] - cap[js]) / (z[js + 1] - z[js])
+            for delta in MARCH_DELTAS:
+                if delta > 0:
+                    D = B.axis_slope(k, js) + w * e
+                    rt = Rt - delta * Rt
+                    first = 0.5 * (z[1] + z[2])
+                    zs = B.start_for(capname, k, zt, rt, D, first, lo_frac, lambda back: delta * Rt)
+                    # a tangent to a bulging wall lies outside it further back: such a ray starts in the segment itself
+                    ok = zs is not None and all(
+                        float(np.hypot(*(np.array(k) * B.at(B.zh, zt) + e * rt - D * (zt - zz) - np.array(k) * B.at(B.zh, zz))))
+                        < B.at(cap, zz) - 0.5 * delta * Rt for zz in z[B.seg_of(zs) + 1:js + 1])
+                    if not ok:
+                        zs = z[js] + 0.25 * (z[js + 1] - z[js])
+                    B.aimed(capname, k, "mid", zt, rt, D, zs, delta, (js, js + 1), js, 0.0)
+                else:
+                    s = max(MARCH_SLOPES[count % len(MARCH_SLOPES)], 4 * abs(delta) * Rt / (z[js + 1] - z[js]))
+                    count += 1
+                    first = 0.5 * (z[1] + z[2])
+                    W = B.closing_rate(k, B.seg_of(first), js + 1, js)
+                    D = B.axis_slope(k, js) + (W + s) * e
+                    rt = Rt * (1 - delta)
+                    zs = B.start_for(capname, k, zt, rt, D, first, lo_frac, lambda back: delta * Rt + s * back)
+                    if zs is not None:
+                        B.aimed(capname, k, "mid", zt, rt, D, zs, delta, (js, js + 1), js, s)
+        if "kink" in prof["rays"] and not (name == "ext_kink" and capname == "centre"):      # the centre's axis has no kink
+            kn = prof["kink"]
+            for start_seg in (kn - 13, kn - 4):
+                zs = 0.5 * (z[start_seg] + z[start_seg + 1])
+                for delta in MARCH_DELTAS:
+                    s = (1e-6, -1e-4, 1e-3, -1e-3, 1e-2, 1e-4)[count % 6]
+                    count += 1
+                    D = B.axis_slope(k, kn - 3) + s * e
+                    # the start must lie inside the capillary (where nothing sticks in, a ray that leaves the wall comes from
+                    # outside it)
+                    q = np.array(k) * B.at(B.zh, z[kn]) + e * cap[kn] * (1 - delta) - D * (z[kn] - zs) - np.array(k) * B.at(B.zh, zs)
+                    if not (float(np.hypot(*q)) < 0.95 * B.at(cap, zs) and float(q @ e) >= lo_frac * B.at(cap, zs)):
+                        continue
+                    B.aimed(capname, k, "kink", z[kn], cap[kn] * (1 - delta), D, zs, delta, (kn - 1, kn + 1), kn, s)
+    return np.array(B.rows, dtype=np.float64).reshape(-1, 11), B.meta
+
+
+@functools.lru_cache(maxsize=None)
+def march_grids():
+    """name -> dict(problem, profile, rows [n, 11] of pyprobe.MARCH_COLS (literal 0, K = 64), meta [n])"""
+    out = {}
+    for name, prof in march_profiles().items():
+        rows, meta = _march_rows_of(name, prof)
+        out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof, rows=rows,
+                         meta=meta)
+    return out

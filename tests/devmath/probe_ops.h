@@ -8,6 +8,9 @@
  *
  * The geometry ops (PC_PROBE_SEGMENT, PC_PROBE_GEOM, PC_PROBE_BOUNCE: the other half of a reflection) have input and output rows
  * of their own widths (pc_probe_in_width, pc_probe_out_width) and an entry point of their own; see pc_probe_geom_eval.
+ *
+ * Op MARCH (PC_PROBE_MARCH) walks one photon per row through the certified march of a whole profile -- pc_launch_init, pc_march_step,
+ * pc_event_pre -- and reports every step; see pc_probe_march_eval.
  */
 #ifndef PC_PROBE_OPS_H
 #define PC_PROBE_OPS_H
@@ -111,8 +114,9 @@ enum { PC_PROBE_SEGMENT = 13, PC_PROBE_GEOM = 14, PC_PROBE_BOUNCE = 15, PC_PROBE
 #define PC_PROBE_SETUP_REJECT (-100)
 
 static inline int pc_probe_is_geom(int op) { return op >= PC_PROBE_SEGMENT && op < PC_PROBE_GEOM_END; }
-static inline int pc_probe_in_width(int op) { return (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
-static inline int pc_probe_out_width(int op) { return pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
+/* row widths per op (PC_PROBE_MARCH = 16 and its widths are defined with the op, further down) */
+static inline int pc_probe_in_width(int op) { return (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
+static inline int pc_probe_out_width(int op) { return (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
 
 /* the product's setup (pc_build_tables) of the two-node profile (z0, z1), (cap0, cap1) of a SEGMENT row, glass and energies
  * of p; returns 0, or -1 when the setup rejects the profile */
@@ -198,6 +202,115 @@ static inline int pc_probe_geom_check(int op, long long n, int in_w, int out_w, 
 	if (!pc_probe_is_geom(op) || n < 0 || in_w != pc_probe_in_width(op) || out_w != pc_probe_out_width(op)) return -2;
 	for (long long i = 0; i < n; i++)
 		if (e[i] < 0 || e[i] >= ne) return -2;
+	return 0;
+}
+
+/* ------------------------------------------------------------------ op MARCH
+ * One photon per row through the certified march of the WHOLE profile of the problem passed to the call, tables and parameters
+ * as pc_build_tables makes them (mg, adj / adjf, bnd_thresh, hexd: what a kernel gets).  Product code only, in this order:
+ * pc_launch_init with the row's start; then at most K times pc_march_step and, when that returns EVENT, pc_event_pre: a miss goes
+ * on, REFLECT or DONE ends the row.  No reflection is evaluated (no energy enters).  Numbered after the geometry ops; rows of its
+ * own widths and an entry point of its own (probe_run_march / emul_probe_run_march).
+ *   in[11]   = x, y, z, dx, dy, dz, ex, ey, ez, literal (0 / 1: Pm.literal of this row), K (0 .. PC_PROBE_MARCH_K)
+ *   out[278] = entrance [0..9]: state pc_launch_init returned, rc, qr, kx, ky, bnd, i, and the normalised direction d it left
+ *              end      [10..21]: how (PC_PROBE_END_*), i, rc, C0, Px, Py, Pz, nx, ny, nz, cosalfa (normal and cosine on REFLECT,
+ *                                 else 0), number of trail entries
+ *              trail    [22 + 4 t ..]: i before, i after, kind (PC_PROBE_STEP_*), segments the creep loop of pc_event_pre walked
+ *                                 in front of its literal visit (literal kinds only), one entry per pass of the loop
+ * code = ph.rc at the end. */
+enum { PC_PROBE_MARCH = 16 };
+#define PC_PROBE_MARCH_IN 11
+#define PC_PROBE_MARCH_K 64
+#define PC_PROBE_MARCH_HEAD 22
+#define PC_PROBE_MARCH_OUT (PC_PROBE_MARCH_HEAD + 4*PC_PROBE_MARCH_K)
+#define PC_PROBE_MARCH_NODES 64
+enum {
+	PC_PROBE_END_STEPS = 0,     /* K passes made, still marching */
+	PC_PROBE_END_REFLECT = 1,   /* pc_event_pre found a hit: P is the hit point */
+	PC_PROBE_END_EXIT = 2,      /* pc_march_step reached the end of the profile (rc 1) */
+	PC_PROBE_END_EVENT = 3,     /* pc_event_pre ended the photon (rc -1) */
+	PC_PROBE_END_ENTRANCE = 4   /* pc_launch_init did not let it in (rc 2 / -2) */
+};
+enum {
+	PC_PROBE_STEP_FIRST = 0,    /* first-segment certificate (pc_march_first_ok) */
+	PC_PROBE_STEP_SINGLE = 1,   /* pc_march_ok, one segment */
+	PC_PROBE_STEP_L1 = 2,       /* pc_march_ok, PC_L1 segments */
+	PC_PROBE_STEP_L2 = 3,       /* pc_march_ok, PC_L2 segments */
+	PC_PROBE_STEP_LOWER = 4,    /* failed probe that lowered lv; nothing skipped */
+	PC_PROBE_STEP_MISS = 5,     /* literal visit without a hit (after `creep` certified single segments) */
+	PC_PROBE_STEP_HIT = 6,      /* literal visit with a hit (REFLECT) */
+	PC_PROBE_STEP_DONE = 7      /* pc_event_pre ended the photon */
+};
+
+/* the device-side view of the profile tables of a MARCH call: n = nmax + 1 entries each, in this order in one buffer of
+ * PC_PROBE_MARCH_TAB*n doubles (z, cap, zh, cap2, hexd, idz, ext) plus n pc_marg4 */
+#define PC_PROBE_MARCH_TAB 7
+PC_HD void pc_probe_march_tables(pc_tables &T, const double *tab, const pc_marg4 *mg, int n)
+{
+	T.z = tab; T.cap = tab + n; T.zh = tab + 2*n; T.cap2 = tab + 3*n; T.hexd = tab + 4*n; T.idz = tab + 5*n; T.ext = tab + 6*n;
+	T.mg = mg;
+}
+
+PC_HD void pc_probe_march_eval(const pc_tables &T, const pc_params &Pm0, const double *in, double *out, int *code)
+{
+	for (int j = 0; j < PC_PROBE_MARCH_OUT; j++) out[j] = 0.;
+	pc_params Pm = Pm0;
+	Pm.literal = (in[9] != 0.) ? 1 : 0;
+	int K = (int)in[10];
+	if (K < 0) K = 0;
+	if (K > PC_PROBE_MARCH_K) K = PC_PROBE_MARCH_K;
+	pc_photon<1> ph;
+	const double zero[6] = {0., 0., 0., 0., 0., 0.};
+	pc_probe_photon(ph, zero);
+	int st = pc_launch_init(T, Pm, ph, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8]);
+	out[0] = st; out[1] = ph.rc; out[2] = ph.qr; out[3] = ph.kx; out[4] = ph.ky; out[5] = ph.bnd; out[6] = ph.i;
+	out[7] = ph.dx; out[8] = ph.dy; out[9] = ph.dz;
+	int how = PC_PROBE_END_STEPS, nt = 0;
+	pc_hit h;
+	h.nx = h.ny = h.nz = h.cosalfa = 0.; h.ix = 0;
+	if (st != PC_ST_MARCH) how = PC_PROBE_END_ENTRANCE;
+	for (int t = 0; t < K && how == PC_PROBE_END_STEPS; t++) {
+		const int i0 = ph.i, first = ph.first;
+		double *tr = out + PC_PROBE_MARCH_HEAD + 4*nt;
+		st = pc_march_step(T, Pm, ph);
+		if (st == PC_ST_DONE) { how = PC_PROBE_END_EXIT; break; }
+		int kind, creep = 0;
+		if (st == PC_ST_MARCH) {
+			const int adv = ph.i - i0;
+			kind = first ? PC_PROBE_STEP_FIRST : (adv == 0) ? PC_PROBE_STEP_LOWER : (adv == 1) ? PC_PROBE_STEP_SINGLE
+			     : (adv == PC_L1) ? PC_PROBE_STEP_L1 : PC_PROBE_STEP_L2;
+		} else {
+			const int crept = (ph.lv == 3);
+			st = pc_event_pre(T, Pm, ph, h);
+			if (st == PC_ST_MARCH) { kind = PC_PROBE_STEP_MISS; creep = ph.i - 1 - i0; }
+			else {
+				kind = (st == PC_ST_REFLECT) ? PC_PROBE_STEP_HIT : PC_PROBE_STEP_DONE;
+				/* rc 1 from pc_event_pre: its creep loop walked to the end of the profile, the exit pc_march_step reports otherwise */
+				how = (st == PC_ST_REFLECT) ? PC_PROBE_END_REFLECT : (ph.rc == 1) ? PC_PROBE_END_EXIT : PC_PROBE_END_EVENT;
+				creep = ph.i - i0;
+			}
+			if (!crept) creep = 0;
+		}
+		tr[0] = i0; tr[1] = ph.i; tr[2] = kind; tr[3] = creep;
+		nt++;
+	}
+	out[10] = how; out[11] = ph.i; out[12] = ph.rc; out[13] = ph.C0;
+	out[14] = ph.Px; out[15] = ph.Py; out[16] = ph.Pz;
+	if (how == PC_PROBE_END_REFLECT) { out[17] = h.nx; out[18] = h.ny; out[19] = h.nz; out[20] = h.cosalfa; }
+	out[21] = nt;
+	code[0] = ph.rc;
+}
+
+/* host-side checks of a MARCH call: widths, profile size, K and the literal flag of every row */
+static_assert(PC_PROBE_MARCH == 16 && PC_PROBE_MARCH_IN == 11 && PC_PROBE_MARCH_OUT == 22 + 4*64, "widths of op MARCH as pc_probe_in_width / pc_probe_out_width state them");
+static inline int pc_probe_march_check(const pc_hip_problem *p, long long n, int in_w, int out_w, const double *in)
+{
+	if (n < 0 || in_w != pc_probe_in_width(PC_PROBE_MARCH) || out_w != pc_probe_out_width(PC_PROBE_MARCH)) return -2;
+	if (p->nmax < 1 || p->nmax + 1 > PC_PROBE_MARCH_NODES) return -2;
+	for (long long i = 0; i < n; i++) {
+		const double lit = in[i*in_w + 9], K = in[i*in_w + 10];
+		if (!(lit == 0. || lit == 1.) || !(K >= 0. && K <= PC_PROBE_MARCH_K) || K != (double)(int)K) return -2;
+	}
 	return 0;
 }
 

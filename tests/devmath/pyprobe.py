@@ -1,6 +1,7 @@
 """TEST-ONLY: the arithmetic of pc_device.h element by element, on the device (probe.hip) or in the host compile of the same header
 (tests/emul/pc_emul.cpp, IEEE sqrt, division and exp).  Both take the per-energy constants from the product's own setup
-(pc_build_tables) of the Problem passed in."""
+(pc_build_tables) of the Problem passed in.  Op MARCH (run_march) walks photons through the certified march of the Problem's whole
+profile."""
 import ctypes as C
 import os
 import subprocess
@@ -61,6 +62,9 @@ def lib():
         L.probe_run_geom.argtypes = [C.POINTER(ProblemS), C.c_int, C.c_int64, C.POINTER(C.c_int32), c_double_p, C.c_int, c_double_p,
                                      C.c_int, C.POINTER(C.c_int32), C.c_char_p]
         L.probe_run_geom.restype = C.c_int
+        L.probe_run_march.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
+                                      C.POINTER(C.c_int32), C.c_char_p]
+        L.probe_run_march.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -119,6 +123,55 @@ def run_geom(problem, op, x, e=0, device=True):
         if r:
             raise RuntimeError("emul_probe_run_geom(%s) failed: %d" % (op, r))
     return out, code
+
+
+# op MARCH (probe_ops.h): one photon per row through the certified march of the problem's whole profile
+MARCH_OP = 16
+MARCH_IN = 11
+MARCH_K = 64
+MARCH_HEAD = 22
+MARCH_OUT = MARCH_HEAD + 4 * MARCH_K
+MARCH_COLS = ("x", "y", "z", "dx", "dy", "dz", "ex", "ey", "ez", "literal", "K")
+MARCH_HEAD_COLS = ("state", "rc0", "qr", "kx", "ky", "bnd", "i0", "dx", "dy", "dz",
+                   "how", "i", "rc", "C0", "Px", "Py", "Pz", "nx", "ny", "nz", "cosalfa", "n_trail")
+END_STEPS, END_REFLECT, END_EXIT, END_EVENT, END_ENTRANCE = range(5)
+STEP_FIRST, STEP_SINGLE, STEP_L1, STEP_L2, STEP_LOWER, STEP_MISS, STEP_HIT, STEP_DONE = range(8)
+STEP_NAMES = ("first", "single", "L1", "L2", "lowered", "literal miss", "literal hit", "literal end")
+ST_MARCH = 2
+
+
+def run_march(problem, x, device=True):
+    """Op MARCH on the rows x [n, MARCH_IN] (MARCH_COLS): (out [n, MARCH_OUT], code [n]); out[:, :MARCH_HEAD] are
+    MARCH_HEAD_COLS, then MARCH_K trail entries of (i before, i after, kind, creep)."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, MARCH_IN)
+    n = x.shape[0]
+    out = np.zeros((n, MARCH_OUT))
+    code = np.zeros(n, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    args = (C.byref(problem.s), n, x.ctypes.data_as(c_double_p), MARCH_IN, out.ctypes.data_as(c_double_p), MARCH_OUT,
+            code.ctypes.data_as(ip))
+    if device:
+        err = C.create_string_buffer(256)
+        r = lib().probe_run_march(*args, err)
+        if r:
+            raise RuntimeError("probe_run_march failed: %d %s" % (r, err.value.decode(errors="replace")))
+    else:
+        from tests.emul import pyemul
+        r = pyemul.lib().emul_probe_run_march(*args)
+        if r:
+            raise RuntimeError("emul_probe_run_march failed: %d" % r)
+    return out, code
+
+
+def march_head(out):
+    """the named columns of MARCH output rows"""
+    return {k: out[:, j] for j, k in enumerate(MARCH_HEAD_COLS)}
+
+
+def march_trail(row):
+    """trail of one MARCH output row: list of (i before, i after, kind, creep) as ints"""
+    nt = int(row[MARCH_HEAD_COLS.index("n_trail")])
+    return [tuple(int(v) for v in row[MARCH_HEAD + 4 * t: MARCH_HEAD + 4 * t + 4]) for t in range(nt)]
 
 
 def energy_consts(problem):

@@ -359,6 +359,46 @@ int emul_probe_run_geom(const pc_hip_problem *p, int op, int64_t n, const int32_
 	return 0;
 }
 
+/* the host build of probe.hip's probe_run_march: one photon per row through the certified march of p's whole profile */
+int emul_probe_run_march(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_march_check(p, n, in_w, out_w, in)) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		int cd = 0;
+		pc_probe_march_eval(E.T, E.t.pm, in + i*in_w, out + i*out_w, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
+/* Test-only accessor: the certificate tables pc_build_tables makes of p, as doubles (every float converts exactly).
+ * node[(nmax + 1) x 16] = z, cap, ext, zh, cap2, hexd, idz, mb1, md1, mb2, md2 (the float tables), then what pc_march_ok reads
+ * from the packed pc_marg4: mb of stride PC_L1 and of PC_L2 decoded, md1, md2, r2.
+ * scal[10] = adj, adjf, two_rmax, two_rmaxf, bnd_thresh, hexscale, n_shells, mono, PC_L1, PC_L2. */
+int emul_march_tables(const pc_hip_problem *p, double *node, double *scal)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	const pc_host_tables &t = E.t;
+	const int n = p->nmax + 1;
+	for (int i = 0; i < n; i++) {
+		double *o = node + 16*i;
+		const pc_marg4 g = t.mg[i];
+		o[0] = t.z[i]; o[1] = t.cap[i]; o[2] = t.ext[i]; o[3] = t.zh[i]; o[4] = t.cap2[i]; o[5] = t.hexd[i]; o[6] = t.idz[i];
+		o[7] = t.mb1[i]; o[8] = t.md1[i]; o[9] = t.mb2[i]; o[10] = t.md2[i];
+		o[11] = pc_bits_as_float(g.mb12 & 0xffff0000u); o[12] = pc_bits_as_float(g.mb12 << 16);
+		o[13] = g.md1; o[14] = g.md2; o[15] = g.r2;
+	}
+	const pc_params &pm = t.pm;
+	scal[0] = pm.adj; scal[1] = pm.adjf; scal[2] = pm.two_rmax; scal[3] = pm.two_rmaxf; scal[4] = pm.bnd_thresh;
+	scal[5] = pm.hexscale; scal[6] = pm.n_shells; scal[7] = pm.mono; scal[8] = PC_L1; scal[9] = PC_L2;
+	return 0;
+}
+
 /* the per-energy constants pc_build_tables derives (struct pc_energy_const, field by field): ne x 11 doubles */
 int emul_energy_consts(const pc_hip_problem *p, double *out)
 {

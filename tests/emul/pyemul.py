@@ -53,6 +53,11 @@ def lib():
         L.emul_probe_run_geom.restype = C.c_int
         L.emul_energy_consts.argtypes = [C.POINTER(ProblemS), c_double_p]
         L.emul_energy_consts.restype = C.c_int
+        L.emul_probe_run_march.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
+                                           C.POINTER(C.c_int32)]
+        L.emul_probe_run_march.restype = C.c_int
+        L.emul_march_tables.argtypes = [C.POINTER(ProblemS), c_double_p, c_double_p]
+        L.emul_march_tables.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -111,6 +116,25 @@ def sample(problem, seed, slots, attempts):
     if r:
         raise RuntimeError("emul_sample failed: %d" % r)
     return out
+
+
+MARCH_NODE_COLS = ("z", "cap", "ext", "zh", "cap2", "hexd", "idz", "mb1", "md1", "mb2", "md2", "mg_mb1", "mg_mb2", "mg_md1",
+                   "mg_md2", "mg_r2")
+MARCH_SCALARS = ("adj", "adjf", "two_rmax", "two_rmaxf", "bnd_thresh", "hexscale", "n_shells", "mono", "L1", "L2")
+
+
+def march_tables(problem):
+    """The certificate tables pc_build_tables makes of `problem` (emul_march_tables): dict of per-node arrays (MARCH_NODE_COLS;
+    mg_* as pc_march_ok decodes the packed pc_marg4) and scalars (MARCH_SCALARS).  Every float is held exactly by its double."""
+    node = np.zeros((problem.nmax + 1, len(MARCH_NODE_COLS)))
+    scal = np.zeros(len(MARCH_SCALARS))
+    r = lib().emul_march_tables(C.byref(problem.s), dptr(node), dptr(scal))
+    if r:
+        raise RuntimeError("emul_march_tables failed: %d" % r)
+    t = {k: node[:, j].copy() for j, k in enumerate(MARCH_NODE_COLS)}
+    t.update({k: float(scal[j]) for j, k in enumerate(MARCH_SCALARS)})
+    t["L1"], t["L2"], t["mono"] = int(t["L1"]), int(t["L2"]), int(t["mono"])
+    return t
 
 
 def sort_leak_records(rec):
