@@ -37,6 +37,9 @@
 #define PC3_SLEEP 127          /* the launching wave waits for room in the rings 90 % of the time: long naps (8128 clocks) */
 #endif
 
+/* phases of a tracing wave's loop */
+enum { PC3_PH_IDLE = 0, PC3_PH_MARCH = 1, PC3_PH_EVENT = 2, PC3_PH_NEW = 3, PC3_PH_WAIT = 4 };
+
 struct pc3_ctrl {
 	unsigned int q_head[16], q_tail[16];      /* rings of launched photons: tail written by the producer, head by the consumer */
 	unsigned int r_head[16], r_tail[16];      /* rings of finished photons: tail written by the consumer, head by the producer */
@@ -49,6 +52,14 @@ struct pc3_ctrl {
 __device__ __forceinline__ unsigned int pc3_load(const unsigned int *p)
 {
 	return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+/* the same load where every lane of the wave reads the same word (the tracing waves' ring ends and flags): the value is
+ * handed to the compiler as wave-uniform, so that what is decided from it -- which phase runs next, whether to leave -- is a
+ * scalar branch around the phase instead of a lane mask over it.  Precondition, not checked: every lane of the wave is
+ * active at the call and passes the same address (never call it under a branch that lanes take differently) */
+__device__ __forceinline__ unsigned int pc3_load_uniform(const unsigned int *p)
+{
+	return (unsigned int)__builtin_amdgcn_readfirstlane((int)pc3_load(p));
 }
 __device__ __forceinline__ void pc3_store(unsigned int *p, unsigned int v)
 {
@@ -408,30 +419,34 @@ pc_trace_producer_kernel(pc_kargs a)
 				if (cM < a.march_stop && (cM != nM || do_new || nE > 0)) break;
 			}
 		};
-		for (;;) {
+		/* The loop is shaped for the register allocator; the photon is 17 doubles and 6 ints that every phase changes in part.
+		 * (1) What the wave reads from its ring ends and flags is wave-uniform (pc3_load_uniform), so the choice of the phase is
+		 * scalar: as a per-lane value (an LDS read) it turned every phase into a lane mask over its code.  (2) The phase is
+		 * chosen first, as a number, and the phases stand side by side, each an `if` of its own; (3) one way round the loop and
+		 * one way out of it (`run`).  With an else-if chain of phases and a `break` / `continue` in the middle the photon had two
+		 * homes: 23 moves into the second at the head of an EVENT phase, 25 + 19 back before the back edge of every turn, 29 registers
+		 * spilled.  Now every phase changes the photon where it lives (profiles/producer_loop_resources.txt, _ab.txt). */
+		bool run = true;
+		while (run) {
 			const int nM = __popcll(__ballot(state == LS_MARCH)), nE = __popcll(__ballot(state == LS_EVENT));
 			const int nD = __popcll(__ballot(state == LS_DONE)), nQ = __popcll(__ballot(state == LS_NEED_SLOT));
-			const int avail = (int)(pc3_load(&ctl.q_tail[c]) - q_head);
-			if (nM + nE + nD == 0) {
-				if (avail == 0) {
-					/* nothing to trace: the launching wave says when to leave (it ends the run, or gives up after PC3_MAX_POLLS
-					 * polls without progress and marks the run failed) */
-					if (pc3_load(&ctl.done) || pc3_load(&ctl.failed)) break;
-					__builtin_amdgcn_s_sleep(32);
-					continue;
-				}
-			}
+			const int avail = (int)(pc3_load_uniform(&ctl.q_tail[c]) - q_head);
 			const int nN = nD + ((nQ < avail) ? nQ : avail);
 			const bool do_new = (nN >= a.new_threshold) || (nM == 0 && nE == 0);
-			if (nM > 0 && (nM >= a.event_threshold || (nE == 0 && !(do_new && nN > 0))) && !(nN >= a.pool_event_min)) {
-				/* ---------------- MARCH */
+			int phase;
+			if (nM + nE + nD == 0 && avail == 0) phase = PC3_PH_IDLE;
+			else if (nM > 0 && (nM >= a.event_threshold || (nE == 0 && !(do_new && nN > 0))) && !(nN >= a.pool_event_min)) phase = PC3_PH_MARCH;
+			else if (nE > 0 && !(do_new && nN > nE) && !(nN >= a.pool_event_min)) phase = PC3_PH_EVENT;
+			else if (nN > 0) phase = PC3_PH_NEW;
+			else phase = PC3_PH_WAIT;
+			if (phase == PC3_PH_MARCH)
 				march_burst(nM, do_new, nE);
-			} else if (nE > 0 && !(do_new && nN > nE) && !(nN >= a.pool_event_min)) {
-				/* ---------------- EVENT */
+			if (phase == PC3_PH_EVENT) {
 				st_event += 1; st_event_l += (unsigned)nE;
 				if (state == LS_EVENT)
 					state = pc_event<1, true>(T, Pm, a.ec, ph);
-			} else if (nN > 0) {
+			}
+			if (phase == PC3_PH_NEW) {
 				/* ---------------- NEW: finalise finished photons, pop launched ones */
 				st_new += 1; st_new_l += (unsigned)nN;
 				int moved = 0;                /* photons pushed or popped in this phase */
@@ -439,7 +454,7 @@ pc_trace_producer_kernel(pc_kargs a)
 					/* finished photons go to the launching wave (as many as its ring takes; the others wait for the next NEW phase) */
 					const unsigned long long mD = __ballot(state == LS_DONE);
 					if (mD) {
-						const int room = PC3_DCAP - (int)(r_tail - pc3_load(&ctl.r_head[c]));
+						const int room = PC3_DCAP - (int)(r_tail - pc3_load_uniform(&ctl.r_head[c]));
 						const int rk = __popcll(mD & below);
 						if (state == LS_DONE && rk < room) {
 							double *q = dring + ((r_tail + (unsigned)rk) % PC3_DCAP);
@@ -461,7 +476,7 @@ pc_trace_producer_kernel(pc_kargs a)
 				{
 					/* ---------------- pop launched photons */
 					const unsigned long long mQ = __ballot(state == LS_NEED_SLOT);
-					const int av = (int)(pc3_load(&ctl.q_tail[c]) - q_head);
+					const int av = (int)(pc3_load_uniform(&ctl.q_tail[c]) - q_head);
 					if (mQ && av > 0) {
 						const int rk = __popcll(mQ & below);
 						if (state == LS_NEED_SLOT && rk < av) {
@@ -492,17 +507,21 @@ pc_trace_producer_kernel(pc_kargs a)
 						if (lane == 0) pc3_store(&ctl.q_head[c], q_head);
 					}
 				}
-				if (moved == 0 && nM == 0 && nE == 0) {
-					/* nothing could move (the ring of finished photons is full and nothing is there to pop) and nothing else can
-					 * run: wait for the launching wave -- or leave when it has given up (this state used to spin, and
-					 * to spin forever after a give-up) */
-					if (pc3_load(&ctl.failed)) break;
-					__builtin_amdgcn_s_sleep(8);
-				}
-			} else {
+				/* nothing could move (the ring of finished photons is full and nothing is there to pop) and nothing else can
+				 * run: wait for the launching wave -- or leave when it has given up (this state used to spin, and
+				 * to spin forever after a give-up) */
+				if (moved == 0 && nM == 0 && nE == 0) phase = PC3_PH_WAIT;
+			}
+			if (phase == PC3_PH_IDLE) {
+				/* nothing to trace: the launching wave says when to leave (it ends the run, or gives up after PC3_MAX_POLLS
+				 * polls without progress and marks the run failed) */
+				if (pc3_load_uniform(&ctl.done) || pc3_load_uniform(&ctl.failed)) run = false;
+				else __builtin_amdgcn_s_sleep(32);
+			}
+			if (phase == PC3_PH_WAIT) {
 				/* lanes wait for launched photons and nothing else can run */
-				if (pc3_load(&ctl.failed)) break;
-				__builtin_amdgcn_s_sleep(8);
+				if (pc3_load_uniform(&ctl.failed)) run = false;
+				else __builtin_amdgcn_s_sleep(8);
 			}
 		}
 	}
