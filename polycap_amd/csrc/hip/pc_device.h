@@ -75,13 +75,23 @@ struct pc_params {
 /* Block-certificate data of one start node, one 16-byte read per march step: mb12 = margin bases of strides PC_L1 (high half)
  * and PC_L2 (low half) as the upper 16 bits of a float, rounded up; md1, md2 = chord deviations of zh over the two blocks;
  * r2 = twice the largest capillary radius of the PC_L2 block (which contains the PC_L1 block).  All rounded up and, except the
- * deviations, inflated by PC_MARGIN_INFLATE at build time (pc_problem.h). */
-struct pc_marg4 { unsigned int mb12; float md1, md2, r2; };
+ * deviations, inflated by PC_MARGIN_INFLATE at build time (pc_problem.h).  The two deviations lead, on an even register pair
+ * of the 16-byte read, and r2 follows in the low half of the next pair: what the packed margin arithmetic of pc_march_ok takes
+ * as its operands without a copy. */
+struct pc_marg4 { float md1, md2, r2; unsigned int mb12; };
 /* leak path: chord deviations of cap over the PC_L1 / PC_L2 block that starts at a node, rounded up (infinite where the block
  * does not fit) */
 struct pc_drdev { float d1, d2; };
 
 PC_HD float pc_bits_as_float(unsigned int u) { return __builtin_bit_cast(float, u); }
+
+/* pairs of floats for packed single-precision arithmetic (v_pk_mul_f32, v_pk_add_f32, v_pk_fma_f32): device compile only */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PC_PACKED_MARGINS 1
+typedef float pc_float2 __attribute__((ext_vector_type(2)));
+#else
+#define PC_PACKED_MARGINS 0
+#endif
 
 /* profile tables.  z/cap/zh/cap2 are the MARCH tables (LDS on the device), ext is only read on events.  Every kernel sets the
  * tables its path reads; the rest stay null (a forgotten table then faults in the host compile of the tests instead of reading
@@ -124,7 +134,8 @@ struct pc_photon {
 	double kx, ky;          /* capillary axis scale factors */
 	double sx, sy, ox, oy;  /* ray of the current trace call: p(z) = o + s*z */
 	double idzd;            /* 1 / dz of the current direction */
-	double C0;              /* |p - axis|^2 - cap^2 at node i (certificate chain) */
+	float C0;               /* |p - axis|^2 - cap^2 at node i (certificate chain), rounded to single precision: every reader
+	                         * compares exactly that rounding with a margin (pc_march_ok, pc_event_pre) */
 	double dtravel;
 	double kn;              /* |(kx, ky)| */
 	double w[NE > 0 ? NE : 1]; /* NE > 0: one weight per energy in registers */
@@ -568,51 +579,64 @@ PC_HD int pc_march_ok(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph
 	 * current node already satisfies */
 	const int cap = ph.lv;
 	const int i0 = ph.i;
-	int lv = 0;
-	/* The certificate VALUES are fp64 (they decide nothing by themselves: a node that is not certified is visited
-	 * literally); the comparison against the margins is made in single precision with every margin inflated by
+	/* The certificate VALUES are computed in fp64 (they decide nothing by themselves: a node that is not certified is visited
+	 * literally); the comparison against the margins is made in single precision (ph.C0 holds the value already rounded: the
+	 * conversion is made once, where the value is formed) with every margin inflated by
 	 * PC_MARGIN_INFLATE (2^-18, far above the three float roundings involved), so that "Cf < -mf" implies C < -m for the
 	 * exact values.  Margins of both strides are then 3 float operations each instead of 2 conversions + 3 fp64 operations. */
-	float marg = Pm.adjf;
-	const float C0f = (float)ph.C0;
-	{
-		/* a stride that does not fit before the end of the profile has an infinite margin: no index test needed */
-		const pc_marg4 g = T.mg[i0];
-		const float knf = (float)ph.kn * PC_MARGIN_INFLATE;
-		const float kd1 = knf * g.md1, kd2 = knf * g.md2;
-		const float m1 = fmaf(kd1, g.r2 + kd1, pc_bits_as_float(g.mb12 & 0xffff0000u));
-		const float m2 = fmaf(kd2, g.r2 + kd2, pc_bits_as_float(g.mb12 << 16));
-		if (cap >= 1 && C0f < -m1) { lv = 1; marg = m1; }
-		if (cap >= 2 && C0f < -m2) { lv = 2; marg = m2; }
-	}
-	const int L = (lv == 0) ? 1 : ((lv == 1) ? PC_L1 : PC_L2);
+	const float C0f = ph.C0;
+	/* a stride that does not fit before the end of the profile has an infinite margin: no index test needed */
+	const pc_marg4 g = T.mg[i0];
+	const float knf = (float)ph.kn * PC_MARGIN_INFLATE;
+#if PC_PACKED_MARGINS
+	/* the margins of the two strides are the same three single-precision operations on two operands each: formed as a pair
+	 * they are one packed multiply, add and fused multiply-add (the same IEEE operations lane by lane) */
+	const pc_float2 md = { g.md1, g.md2 }, mb = { pc_bits_as_float(g.mb12 & 0xffff0000u), pc_bits_as_float(g.mb12 << 16) };
+	const pc_float2 kd = md * knf;
+	const pc_float2 m12 = __builtin_elementwise_fma(kd, kd + g.r2, mb);
+	const float m1 = m12.x, m2 = m12.y;
+#else
+	const float kd1 = knf * g.md1, kd2 = knf * g.md2;
+	const float m1 = fmaf(kd1, g.r2 + kd1, pc_bits_as_float(g.mb12 & 0xffff0000u));
+	const float m2 = fmaf(kd2, g.r2 + kd2, pc_bits_as_float(g.mb12 << 16));
+#endif
+	/* stride of this step: PC_L2 (s2), PC_L1 (s1) or one segment.  A stride is chosen because the start node satisfies its
+	 * margin, so of "C0f < -marg & C1f < -marg" only the far node is left to test; the single segment tests both against adj */
+	const bool s2 = (cap >= 2) & (C0f < -m2);
+	const bool s1 = !s2 & (cap >= 1) & (C0f < -m1);
+	const int L = s2 ? PC_L2 : (s1 ? PC_L1 : 1);
 	const int i1 = i0 + L;
 	double z1 = T.z[i1], zh1 = T.zh[i1], c2 = T.cap2[i1];
 	double qx = fma(-ph.kx, zh1, fma(ph.sx, z1, ph.ox));
 	double qy = fma(-ph.ky, zh1, fma(ph.sy, z1, ph.oy));
 	double C1 = fma(qx, qx, fma(qy, qy, -c2));
-	int ok = (C0f < -marg) & ((float)C1 < -marg);
+	const float C1f = (float)C1, adjf = Pm.adjf;
+	bool ok = (s2 & (C1f < -m2)) | (s1 & (C1f < -m1)) | (!s2 & !s1 & (C0f < -adjf) & (C1f < -adjf));
 	if (ph.bnd) {
 		/* boundary capillary (or mono-capillary; always level 0): the hexagon tests of the visit are not implied, do them:
 		 * axis at both nodes (src/polycap-capil.c:1263) and the ray at z_i (:1296-1308) */
 		double z0 = T.z[i0], zh0 = T.zh[i0], h0 = T.hexd[i0], h1 = T.hexd[i1];
 		double px = fma(ph.sx, z0, ph.ox), py = fma(ph.sy, z0, ph.oy);
-		ok &= !pc_outside_hexd(h0, ph.kx*zh0, ph.ky*zh0);
-		ok &= !pc_outside_hexd(h1, ph.kx*zh1, ph.ky*zh1);
-		ok &= !pc_outside_hexd(h0, px, py);
+		const bool out0 = pc_outside_hexd(h0, ph.kx*zh0, ph.ky*zh0), out1 = pc_outside_hexd(h1, ph.kx*zh1, ph.ky*zh1);
+		ok = ok & !out0 & !out1 & !pc_outside_hexd(h0, px, py);
 	}
-	if (ok) { ph.C0 = C1; ph.i = i1; return 1; }
-	if (lv > 0) {
+	/* The outcome, one assignment per value and each a select on the live ones (as branches with early returns the step copied
+	 * the photon's node and certificate into a second home and back under nested lane masks).  Certified: advance.  The far
+	 * node of a block not certified: shorter strides for the rest of this flight; from PC_L2 the march goes on at PC_L1. */
+	const bool f2 = !ok & s2, f1 = !ok & s1;
 #if PC_CREEP
-		/* The node PC_L1 segments ahead is not certified: the wall is (nearly always) within those segments.  Walking up to it
-		 * one certified segment per step costs 1.8 steps per flight plus this one; pc_event_pre does that walk in straight-line
-		 * code in front of its literal visit instead (ph.lv == 3 asks for it). */
-		if (lv == 1) { ph.lv = 3; return 0; }
+	/* From PC_L1 the photon goes to the EVENT phase: the wall is (nearly always) within those segments.  Walking up to it one
+	 * certified segment per step costs 1.8 steps per flight plus this one; pc_event_pre does that walk in straight-line code
+	 * in front of its literal visit instead (ph.lv == 3 asks for it). */
+	ph.lv = f2 ? 1 : (f1 ? 3 : cap);
+	const bool go_on = ok | s2;
+#else
+	ph.lv = f2 ? 1 : (f1 ? 0 : cap);
+	const bool go_on = ok | s2 | s1;
 #endif
-		ph.lv = lv - 1;                             /* far node not certified: shorter strides for the rest of this flight */
-		return 1;
-	}
-	return 0;
+	ph.C0 = ok ? C1f : C0f;
+	ph.i = ok ? i1 : i0;
+	return go_on;
 }
 
 /* First segment of a trace call: the last interaction point P lies inside [z_i, z_i+1] and the reference only
@@ -630,9 +654,9 @@ PC_HD int pc_march_first_ok(const pc_tables &T, const pc_params &Pm, pc_photon<N
 	double qy1 = fma(-ph.ky, zh1, fma(ph.sy, z1, ph.oy));
 	double C1 = fma(qx1, qx1, fma(qy1, qy1, -R1*R1));
 	double zlo = fmax(z0, ph.Pz + 1.e-5);
-	int ok;
+	bool ok;
 	if (zlo >= z1) {
-		ok = 1;                     /* no admissible root can lie in this segment */
+		ok = true;                  /* no admissible root can lie in this segment */
 	} else {
 		double t = (zlo - z0) * T.idz[i0];
 		double zhl = fma(t, zh1 - zh0, zh0);
@@ -644,14 +668,15 @@ PC_HD int pc_march_first_ok(const pc_tables &T, const pc_params &Pm, pc_photon<N
 	}
 	/* ray at z_i inside the optic; boundary capillaries also test the axis at both nodes */
 	double px = fma(ph.sx, z0, ph.ox), py = fma(ph.sy, z0, ph.oy);
-	ok &= !(h0 > 0. && pc_outside_hexd(h0, px, py));
+	const bool ray_out = h0 > 0. && pc_outside_hexd(h0, px, py);
+	ok = ok & !ray_out;
 	if (ph.bnd) {
 		double h1 = T.hexd[i1];
-		ok &= !pc_outside_hexd(h0, ph.kx*zh0, ph.ky*zh0);
-		ok &= !pc_outside_hexd(h1, ph.kx*zh1, ph.ky*zh1);
+		const bool out0 = pc_outside_hexd(h0, ph.kx*zh0, ph.ky*zh0), out1 = pc_outside_hexd(h1, ph.kx*zh1, ph.ky*zh1);
+		ok = ok & !out0 & !out1;
 	}
-	ok &= (ph.dz >= 0.);            /* backwards-flying photons keep the reference's literal path */
-	if (ok) { ph.C0 = C1; ph.i = i1; ph.first = 0; }
+	ok = ok & (ph.dz >= 0.);        /* backwards-flying photons keep the reference's literal path */
+	if (ok) { ph.C0 = (float)C1; ph.i = i1; ph.first = 0; }
 	return ok;
 }
 
@@ -685,7 +710,6 @@ PC_HD int pc_segment(const pc_tables &T, const pc_photon<NE> &ph, int i,
 	p0y = fma(ph.sy, t0, ph.Py);
 	nx = 0.; ny = 0.; nz = 0.;
 	hx = hy = hz = 0.;
-	if (ph.dz < 0) return -1;          /* :85-88 */
 	double cdx = c1x - c0x, cdy = c1y - c0y, cdz = z1 - z0;
 	double icdz = T.idz[i];
 	double ddx = fma(-cdx, icdz, ph.sx);
@@ -697,6 +721,9 @@ PC_HD int pc_segment(const pc_tables &T, const pc_photon<NE> &ph, int i,
 	double b = 2.*fma(qx, ddx, fma(qy, ddy, -R0*rr));
 	double c = fma(qx, qx, fma(qy, qy, -R0*R0));
 	double discr = fma(b, b, -4.*a*c);
+	/* The ways out before the hit stand together, nothing computed between them, and the later ones are one code: every
+	 * return merges the six zeros above into the registers of hit and normal, once per nesting level of the device code. */
+	if (ph.dz < 0) return -1;          /* :85-88 */
 	if (discr < 0) return -2;
 	/* a ray exactly as steep as the wall (a cylinder's segment and a ray parallel to its axis: a = b = 0): the reference's
 	 * quotients are 0 * inf, the NaN passes every comparison below and would come out as a hit at NaN.  With a = 0 and c < 0
@@ -704,28 +731,27 @@ PC_HD int pc_segment(const pc_tables &T, const pc_photon<NE> &ph, int i,
 	if (a == 0.) return -3;
 	double last = ph.Pz;
 	const double i2a = 1.0/(2.*a);
+	double zr;
+	bool none = false;
 	if (discr == 0) {
-		hz = z0 + (-1.*b)*i2a;
+		zr = z0 + (-1.*b)*i2a;
 	} else {
 		double sq = sqrt(discr);
 		double zr1 = z0 + (-1.*b + sq)*i2a;
 		double zr2 = z0 + (-1.*b - sq)*i2a;
 		/* written as negated "valid" tests so NaN behaves as in the reference (all comparisons false) */
-		int bad1 = (zr1 < z0) || (zr1 - last < 1.e-5) || (zr1 > z1);
-		int bad2 = (zr2 < z0) || (zr2 - last < 1.e-5) || (zr2 > z1);
-		if (bad1) {
-			if (bad2) return -3;
-			hz = zr2;
-		} else if (bad2) {
-			hz = zr1;
-		} else {
-			hz = (zr2 - last < zr1 - last) ? zr2 : zr1;
-		}
+		const bool bad1 = (zr1 < z0) || (zr1 - last < 1.e-5) || (zr1 > z1);
+		const bool bad2 = (zr2 < z0) || (zr2 - last < 1.e-5) || (zr2 > z1);
+		none = bad1 & bad2;
+		zr = bad1 ? zr2 : (bad2 ? zr1 : ((zr2 - last < zr1 - last) ? zr2 : zr1));
 	}
-	if (hz > z1) return -4;
-	if (hz < z0 || hz - last < 1.e-5) return -5;
-	double d_proj = (hz - z0) * ph.idzd;
-	if (d_proj < 1.e-10) return -6;
+	const double d_proj = (zr - z0) * ph.idzd;
+	const int miss = none ? -3 : ((zr > z1) ? -4 : ((zr < z0 || zr - last < 1.e-5) ? -5 : ((d_proj < 1.e-10) ? -6 : 0)));
+	if (miss != 0) {
+		if (!none) hz = zr;
+		return miss;
+	}
+	hz = zr;
 	hx = fma(d_proj, ph.dx, p0x);
 	hy = fma(d_proj, ph.dy, p0y);
 	/* :225-246 surface normal: radial unit vector tilted by the wall angle gamma, tan(gamma) = (R0-R1)/|cap_dir| */
@@ -1159,8 +1185,8 @@ PC_HD int pc_event_pre(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &p
 #pragma unroll
 		for (int k = 1; k <= PC_L1; k++) {
 			const double C = pc_node_C(T, ph, i + 1);
-			if (!(((float)ph.C0 < -adjf) & ((float)C < -adjf))) break;
-			ph.C0 = C;
+			if (!((ph.C0 < -adjf) & ((float)C < -adjf))) break;
+			ph.C0 = (float)C;
 			i++;
 		}
 		ph.i = i;
@@ -1185,7 +1211,7 @@ PC_HD int pc_event_pre(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &p
 		if (T.hexd[i] > 0. && pc_outside_hexd(T.hexd[i], p0x, p0y)) { ph.rc = -1; return PC_ST_DONE; }
 		ph.i = i + 1;
 		ph.first = 0;
-		ph.C0 = pc_node_C(T, ph, i + 1);
+		ph.C0 = (float)pc_node_C(T, ph, i + 1);
 		return PC_ST_MARCH;
 	}
 
@@ -1248,20 +1274,28 @@ PC_HD int pc_event(const pc_tables &T, const pc_params &Pm, const pc_energy_cons
 }
 
 /* MARCH step wrapper: returns the next state (MARCH to keep going, EVENT, or DONE at the end of the optic) */
-template <int NE>
+template <int NE, bool RC_LATER = false>
 PC_HD int pc_march_step(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph)
 {
-	if (ph.i >= Pm.nmax) { ph.rc = 1; return PC_ST_DONE; }
+	if (ph.i >= Pm.nmax) {
+		if (!RC_LATER) ph.rc = 1;
+		return PC_ST_DONE;
+	}
 	if (Pm.literal) return PC_ST_EVENT;
 	if (ph.first) return pc_march_first_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
 	return pc_march_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
 }
 
-/* MARCH step of the tight loop: the lane is known not to sit on the first segment of a trace call */
-template <int NE>
+/* MARCH step of the tight loop: the lane is known not to sit on the first segment of a trace call.  RC_LATER: the caller
+ * sets ph.rc = 1 itself on the lanes that come back DONE (the end of the optic is the only way to DONE from here), once after
+ * a burst of steps: as a store in every step the return code costs the step three copies to merge its two ways out. */
+template <int NE, bool RC_LATER = false>
 PC_HD int pc_march_step_hot(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph)
 {
-	if (ph.i >= Pm.nmax) { ph.rc = 1; return PC_ST_DONE; }
+	if (ph.i >= Pm.nmax) {
+		if (!RC_LATER) ph.rc = 1;
+		return PC_ST_DONE;
+	}
 	return pc_march_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
 }
 

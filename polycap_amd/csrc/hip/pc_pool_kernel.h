@@ -104,7 +104,7 @@ __device__ __forceinline__ void pq_swap_in(const pc_tables &T, int X, unsigned l
 			ph.sy = ph.dy * ph.idzd;
 			ph.ox = ph.Px - ph.sx * ph.Pz;
 			ph.oy = ph.Py - ph.sy * ph.Pz;
-			ph.C0 = pc_node_C(T, ph, ph.i);
+			ph.C0 = (float)pc_node_C(T, ph, ph.i);
 		}
 	}
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

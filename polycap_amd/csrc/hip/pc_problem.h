@@ -150,7 +150,7 @@ static inline int pc_build_tables(const pc_hip_problem *p, pc_host_tables &t, st
 		double rblk = 0.;
 		for (int j = i; j < n && j <= i + PC_L2; j++) rblk = std::fmax(rblk, p->cap[j]);
 		const float r2 = std::nextafter((float)(2.*rblk), HUGE_VALF) * PC_MARGIN_INFLATE;
-		t.mg[i] = pc_marg4{(half[0] << 16) | half[1], t.md1[i], t.md2[i], std::nextafter(r2, HUGE_VALF)};
+		t.mg[i] = pc_marg4{t.md1[i], t.md2[i], std::nextafter(r2, HUGE_VALF), (half[0] << 16) | half[1]};
 	}
 	pm.bnd_thresh = ratio + 1e-9;
 

@@ -403,23 +403,26 @@ pc_trace_producer_kernel(pc_kargs a)
 		unsigned int attempt = 0;
 		unsigned int q_head = 0, r_tail = 0;      /* this wave's ends of its two rings */
 		auto march_burst = [&](int nM, bool do_new, int nE) {
+			const bool marching = (state == LS_MARCH);
 			if (state == LS_MARCH && ph.first)
-				state = pc_march_step(T, Pm, ph);
+				state = pc_march_step<1, true>(T, Pm, ph);      /* RC_LATER: see the end of the burst */
 			for (int b = 0; b < a.march_burst; b++) {
 				unsigned int lanes_in_burst = 0;
 #pragma unroll
 				for (int u = 0; u < PC_MARCH_UNROLL; u++) {
 					if (STATS) lanes_in_burst += (unsigned)__popcll(__ballot(state == LS_MARCH));
 					if (state == LS_MARCH)
-						state = pc_march_step_hot(T, Pm, ph);
+						state = pc_march_step_hot<1, true>(T, Pm, ph);
 				}
 				const int cM = __popcll(__ballot(state == LS_MARCH));
 				if (STATS) { st_march += PC_MARCH_UNROLL; st_march_l += lanes_in_burst; }
 				if (cM == 0) break;
 				if (cM < a.march_stop && (cM != nM || do_new || nE > 0)) break;
 			}
+			/* the return code of the photons that reached the end of the optic in this burst (pc_march_step_hot, RC_LATER) */
+			if (marching && state == LS_DONE) ph.rc = 1;
 		};
-		/* The loop is shaped for the register allocator; the photon is 17 doubles and 6 ints that every phase changes in part.
+		/* The loop is shaped for the register allocator; the photon is 16 doubles, a float and 6 ints that every phase changes in part.
 		 * (1) What the wave reads from its ring ends and flags is wave-uniform (pc3_load_uniform), so the choice of the phase is
 		 * scalar: as a per-lane value (an LDS read) it turned every phase into a lane mask over its code.  (2) The phase is
 		 * chosen first, as a number, and the phases stand side by side, each an `if` of its own; (3) one way round the loop and

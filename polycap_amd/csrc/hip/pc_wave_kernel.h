@@ -63,7 +63,7 @@ pc_trace_wave_kernel(pc_kargs a)
 				/* 64 nodes at a time */
 				st_scan++;
 				const int i0 = ph.i;
-				if (!((float)ph.C0 < -adjf)) { st = PC_ST_EVENT; continue; }
+				if (!(ph.C0 < -adjf)) { st = PC_ST_EVENT; continue; }
 				const int node = i0 + 1 + lane;
 				const int valid = node <= nmax;
 				const double Cn = valid ? pc_node_C(T, ph, node) : 0.;
@@ -72,11 +72,11 @@ pc_trace_wave_kernel(pc_kargs a)
 				if (mBad == 0ull) {
 					const int nv = __popcll(mValid);
 					ph.i = i0 + nv;
-					ph.C0 = __shfl(Cn, nv - 1, PC_WAVE);
+					ph.C0 = (float)__shfl(Cn, nv - 1, PC_WAVE);
 				} else {
 					const int f = __ffsll((long long)mBad) - 1;     /* node i0 + 1 + f is the first that is not certified */
 					ph.i = i0 + f;
-					if (f > 0) ph.C0 = __shfl(Cn, f - 1, PC_WAVE);
+					if (f > 0) ph.C0 = (float)__shfl(Cn, f - 1, PC_WAVE);
 					st = PC_ST_EVENT;
 				}
 			}

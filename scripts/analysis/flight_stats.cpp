@@ -59,7 +59,8 @@ extern "C" int flight_stats(const pc_hip_problem *p, int64_t n, const double *st
 				if (ph.i >= Pm.nmax) { ph.rc = 1; st = PC_ST_DONE; }
 				else if (ph.first) { st = pc_march_first_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT; if (!firstflight) kinds[0]++; }
 				else {
-					/* generic-level version of pc_march_ok */
+					/* generic-level version of pc_march_ok (ph.C0 is the certificate value rounded to single precision, as the
+				 * product keeps it; this model compares it with its own margins in double, which lie ~1e6 roundings away) */
 					const int i0 = ph.i;
 					if (nprobe > 0 && !ph.bnd) {
 						/* multi-probe step: level l > 0 probes nodes i0 + k*L/nprobe (k = 1..nprobe) against the block margin of stride L
