@@ -542,3 +542,205 @@ def circle_inside_hexagon(cx, cy, cap, ext):
             if not s3_gt(ext - sg * cx, 2 * cap + sg * t * cy):
                 return False
     return True
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The leak path's wall search in rational arithmetic (tests/test_devmath_leak_cpu.py).  The ray is the photon's own, through the
+# row's P along the row's d.  ext(z), cap(z), zh(z) (the table's doubles) and zz(z) = ext(z)/hexscale are piecewise linear between
+# the nodes; 2/3, 3/2, cos(pi/6) and hexscale are the doubles the code uses.
+#
+# Cell (q, r) of the cube rounding of pc_hex_index is where, with (dq, dr) the fractional axial coordinates minus (q, r),
+# |dq - dr| <= 1, |2 dq + dr| <= 1 and |dq + 2 dr| <= 1.  Multiplied by zz > 0 each bound is linear in z on a profile segment, so
+# membership over a stretch is decided at its ends and at the nodes inside it.
+import bisect
+
+COSPI_6 = Fraction(0.86602540378443864676)
+TWO_THIRDS = Fraction(2.0 / 3)
+U53 = Fraction(1, 2 ** 53)
+
+
+def hex_forms(x, y, zz, q, r):
+    """(a1, a2, a3) = zz (dq - dr, 2 dq + dr, dq + 2 dr) of the point (x, y) against cell (q, r): inside means |a_k| <= zz"""
+    Q = x / (2 * COSPI_6) - y / 3 - q * zz
+    R = y * TWO_THIRDS - r * zz
+    return Q - R, 2 * Q + R, Q + 2 * R
+
+
+def hex_cells(x, y, zz):
+    """exactly: the cells (q, r) whose closed hexagon holds (x, y) -- one, two on an edge, three at a corner -- and for each the
+    smallest of 1 - |a_k| / zz (0 on an edge)"""
+    x, y, zz = fr(x), fr(y), fr(zz)
+    qf, rf = (x / (2 * COSPI_6) - y / 3) / zz, y * TWO_THIRDS / zz
+    out = {}
+    for q in range(math_floor(qf) - 1, math_floor(qf) + 3):
+        for r in range(math_floor(rf) - 1, math_floor(rf) + 3):
+            a = hex_forms(x, y, zz, q, r)
+            m = min(zz - abs(v) for v in a)
+            if m >= 0:
+                out[(q, r)] = m / zz
+    return out, qf, rf
+
+
+def math_floor(v):
+    return v.numerator // v.denominator
+
+
+def hex_error_bound(x, y, zz, qf, rf):
+    """first-order running error bound (one 2^-53 per operation) of the fractional coordinates pc_hex_index forms and of the three
+    differences its cube rounding compares, as one number in cell units"""
+    x, y, zz = abs(fr(x)), abs(fr(y)), abs(fr(zz))
+    eq = U53 * ((x / (2 * COSPI_6) + y / 3 + abs(x / (2 * COSPI_6) - y / 3)) / zz + abs(qf))
+    er = 2 * U53 * abs(rf)
+    es = eq + er + 2 * U53 * (abs(qf) + abs(rf))
+    return 2 * (eq + er + es)
+
+
+class WallRay:
+    """One WALL row on one profile, exactly.  t: dict of the tables' doubles z, cap, ext, zh and hexscale."""
+
+    def __init__(self, t, P, d):
+        self.zf = [float(v) for v in t["z"]]
+        self.z = [fr(v) for v in t["z"]]
+        self.cap = [fr(v) for v in t["cap"]]
+        self.ext = [fr(v) for v in t["ext"]]
+        self.zh = [fr(v) for v in t["zh"]]
+        hs = fr(t["hexscale"])
+        self.zz = [e / hs for e in self.ext]
+        self.P = [fr(v) for v in P]
+        self.d = [fr(v) for v in d]
+        self.nmax = len(self.z) - 1
+
+    def xy(self, z):
+        s = (z - self.P[2]) / self.d[2]
+        return self.P[0] + self.d[0] * s, self.P[1] + self.d[1] * s
+
+    def seg(self, z):
+        return min(self.nmax - 1, max(0, bisect.bisect_right(self.z, z) - 1))
+
+    def at(self, tab, z, j=None):
+        j = self.seg(z) if j is None else j
+        return tab[j] + (tab[j + 1] - tab[j]) * (z - self.z[j]) / (self.z[j + 1] - self.z[j])
+
+    def pieces(self, za, zb):
+        """[za, zb] (za <= zb) cut at the nodes inside it: list of (z0, z1, segment)"""
+        pts = [za] + [z for z in self.z[bisect.bisect_right(self.z, za):bisect.bisect_left(self.z, zb)]] + [zb]
+        return [(a, b, self.seg((a + b) / 2)) for a, b in zip(pts[:-1], pts[1:])] if zb > za else [(za, zb, self.seg(za))]
+
+    def cell_slack(self, z, q, r, j=None):
+        """zz(z) - max |a_k| at z for cell (q, r), and zz(z): > 0 strictly inside"""
+        x, y = self.xy(z)
+        zz = self.at(self.zz, z, j)
+        return zz - max(abs(v) for v in hex_forms(x, y, zz, q, r)), zz
+
+    def min_cell_slack(self, za, zb, q, r):
+        """smallest (zz - max |a_k|) / zz over [za, zb]: the forms are linear on every piece, so the ends of the pieces decide the
+        sign; the value is the smallest of the end values"""
+        best = None
+        for a, b, j in self.pieces(za, zb):
+            for z in (a, b):
+                s, zz = self.cell_slack(z, q, r, j)
+                v = s / zz
+                best = v if best is None or v < best else best
+        return best
+
+    def min_gap2(self, za, zb, K, zt):
+        """exact minimum over [za, zb] of |p(z) - K zt(z)|^2 - cap(z)^2 for the axis table zt (self.zz or self.zh), with the z of
+        the minimum: a quadratic on every piece -- its ends, and the vertex where it opens upwards and lies inside"""
+        best, at = None, None
+        Kx, Ky = K
+        for a, b, j in self.pieces(za, zb):
+            xa, ya = self.xy(a)
+            xb, yb = self.xy(b)
+            ta, tb = self.at(zt, a, j), self.at(zt, b, j)
+            ca, cb = self.at(self.cap, a, j), self.at(self.cap, b, j)
+            ux, uy = xa - Kx * ta, ya - Ky * ta
+            ex, ey = xb - Kx * tb - ux, yb - Ky * tb - uy
+            dc = cb - ca
+            A = ex * ex + ey * ey - dc * dc
+            B = 2 * (ux * ex + uy * ey - ca * dc)
+            C0 = ux * ux + uy * uy - ca * ca
+            cands = [(C0, a), (A + B + C0, b)]
+            if A > 0 and 0 < -B < 2 * A:
+                s = -B / (2 * A)
+                cands.append((C0 - B * B / (4 * A), a + (b - a) * s))
+            for v, z in cands:
+                if best is None or v < best:
+                    best, at = v, z
+        return best, at
+
+    def first_exit(self, za, q, r):
+        """first z >= za at which the ray leaves the closed cell (q, r) going up in z, with the slacks zz - |a_k| of the three
+        forms there (the crossed one is 0); None when it stays inside up to the last node"""
+        zb = self.z[self.nmax]
+        if za >= zb:
+            return None
+        for a, b, j in self.pieces(za, zb):
+            xa, ya = self.xy(a)
+            xb, yb = self.xy(b)
+            zza, zzb = self.at(self.zz, a, j), self.at(self.zz, b, j)
+            fa, fb = hex_forms(xa, ya, zza, q, r), hex_forms(xb, yb, zzb, q, r)
+            s_best = None
+            for k in range(3):
+                for sg in (1, -1):
+                    ga, gb = zza - sg * fa[k], zzb - sg * fb[k]          # >= 0 inside, linear on the piece
+                    if gb < 0 and ga >= 0:
+                        s = ga / (ga - gb)
+                        s_best = s if s_best is None or s < s_best else s_best
+                    elif ga < 0:
+                        s_best = Fraction(0)
+            if s_best is not None:
+                z = a + (b - a) * s_best
+                x, y = self.xy(z)
+                zz = self.at(self.zz, z, j)
+                return z, sorted((zz - abs(v)) / zz for v in hex_forms(x, y, zz, q, r)), j
+        return None
+
+
+def cell_K(q, r):
+    """the doubles the wall search multiplies zz (or zh) with for the axis of capillary (q, r)"""
+    return fr((2.0 * q + r) * 0.86602540378443864676), fr(r * 1.5)
+
+
+def leak_table_bounds(t):
+    """per stride L (PC_L1, PC_L2) and start node i: the exact chord deviation of cap over the block, None where it does not fit"""
+    z, cap = [fr(v) for v in t["z"]], [fr(v) for v in t["cap"]]
+    n = len(z)
+    out = {}
+    for L in (t["L1"], t["L2"]):
+        rows = []
+        for i in range(n):
+            if i + L >= n:
+                rows.append(None)
+                continue
+            span = z[i + L] - z[i]
+            rows.append(max([abs(cap[j] - (cap[i] + (cap[i + L] - cap[i]) * (z[j] - z[i]) / span)) for j in range(i + 1, i + L)] + [Fraction(0)]))
+        out[L] = rows
+    return out
+
+
+def outer_scan(t, c, d):
+    """The backward scan of pc_outer_intersect, exactly, for a ray that ended at c on or beyond the last node flying along d
+    (dz > 0): the first node j = nmax - 1, nmax - 2, ... 0 at which the ray is not outside the outer hexagon (largest of |y|,
+    |C x + y/2|, |C x - y/2| <= sqrt(3)/2 ext, compared in squares) or ext <= 0; None when there is none.  Also the smallest, over
+    the nodes scanned, of |largest form - hexd| / bound, bound the first-order running error of the code's evaluation."""
+    z, ext, hexd = [fr(v) for v in t["z"]], [fr(v) for v in t["ext"]], [fr(v) for v in t["hexd"]]
+    c, d = [fr(v) for v in c], [fr(v) for v in d]
+    found, clear = None, None
+    # the end point itself comes first: inside the hexagon there (or ext <= 0) the search returns 0 at once
+    m = max(abs(c[1]), abs(COSPI_6 * c[0] + c[1] / 2), abs(COSPI_6 * c[0] - c[1] / 2))
+    clear = abs(m - hexd[-1]) / (U53 * (3 * (abs(c[0]) + abs(c[1])) + 3 * hexd[-1]))
+    if ext[-1] <= 0 or 4 * m * m <= 3 * ext[-1] * ext[-1]:
+        return None, clear
+    for j in range(len(z) - 2, -1, -1):
+        s = (z[j] - c[2]) / d[2]
+        dx_, dy_ = d[0] * s, d[1] * s
+        x, y = c[0] + dx_, c[1] + dy_
+        m = max(abs(y), abs(COSPI_6 * x + y / 2), abs(COSPI_6 * x - y / 2))
+        inside = ext[j] <= 0 or 4 * m * m <= 3 * ext[j] * ext[j]
+        bound = U53 * (abs(c[0]) + abs(c[1]) + 8 * (abs(dx_) + abs(dy_)) + 3 * (abs(x) + abs(y)) + 3 * hexd[j])
+        cl = abs(m - hexd[j]) / bound
+        clear = cl if clear is None or cl < clear else clear
+        if inside:
+            found = j
+            break
+    return found, clear

@@ -616,3 +616,508 @@ def march_grids():
         out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof, rows=rows,
                          meta=meta)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The leak grids (ops WALL, OUTER, HEX; tests/test_devmath_leak_cpu.py): photons in the glass aimed at the places where a skip
+# certificate of pc_leak.h could be wrong.  Deterministic.  Rays are laid out in double precision in the frame of a hexagon cell and
+# the graze points placed in rational arithmetic (one rounding of P); what a row really does is decided by the exact side
+# (check_built of the test), never by this file.
+#
+# A cell (q, r) has its centre at K zz(z), K = ((2 q + r) cos30, 1.5 r), inradius cos30 zz and corners at distance zz at 30 + 60 k
+# degrees; its edge k has the outward normal at 60 k degrees.  Families (meta["fam"]):
+#   cap    closest approach to the cell's own capillary is cap (1 + delta), at a node, mid-segment and at the kink node
+#   corner leaves the cell through an edge at delta zz from a corner
+#   edge   runs parallel to an edge, delta zz inside (delta > 0) or outside (delta < 0: in the neighbouring cell) of it
+#   xnode  crosses an edge within delta of a node in z
+#   exit   reaches the exit plane inside the glass;  side  leaves the stack sideways
+#   nbr    enters the neighbouring cell and passes its capillary at cap (1 + delta) at node t; the crossing lies in segment
+#          t - L + 1, t - L or t - L - 1 for both strides L, t also the kink node and the last three nodes
+#   back   dz < 0, at most 256 units;  begin  starts beyond the last node or outside the hexagon;  grid  the aligned profile's
+#          axis-parallel photons whose every step lands on a node;  mono  the mono-capillary, straight to the probe
+LEAK_SLOPES = (1e-4, 1e-3, 1e-2, 1e-1, 0.3)
+LEAK_UNITS = 4096                  # every row ends within this many units in certified mode
+C30 = 0.86602540378443864676
+G14 = 2.0 ** -14
+
+
+def leak_profiles():
+    P = dict(march_profiles())
+    for v in P.values():
+        v["leak"] = "basic"
+    for k in ("taper", "bulge", "cap_kink", "ext_kink", "irregular"):
+        P[k]["leak"] = "full"
+    P["cylinder"]["leak"] = P["tiny"]["leak"] = P["last_zero"]["leak"] = "cross"
+    P["mono"]["leak"] = "mono"
+    # every literal step of an axis-parallel photon lands on a node: steps of 2^-14 (cap 10 2^-14), nodes on multiples of 2^-8; in
+    # the second half the radius alternates between 10 and 20 2^-14, so the step over a node is taken with another size than the
+    # steps behind it
+    n = 41
+    j = np.arange(n)
+    P["aligned"] = dict(z=64 * G14 * j, cap=10 * G14 * np.where((j >= 20) & (j % 2 == 1), 2.0, 1.0), ext=0.03 * np.ones(n), ns=10,
+                        kink=None, rays=(), leak="aligned")
+    # room for more than 1e6 steps in one segment (the cap on the step count m)
+    z = np.array([0.0, 0.25, 0.5, 0.51, 0.52, 0.53, 0.54, 0.55])
+    P["long"] = dict(z=z, cap=1.0e-6 * np.ones(8), ext=np.ones(8), ns=10, kink=None, rays=(), leak="long")
+    return P
+
+
+def leak_cells(ns):
+    """march_capillaries' four, one more cell on the outermost shell and one just outside it"""
+    if ns == 0:
+        return [("centre", 0, 0)]
+    return march_capillaries(ns) + [("shell", ns, -3), ("beyond", ns + 1, -3)]
+
+
+def _rot(deg):
+    a = np.deg2rad(deg)
+    return np.array([np.cos(a), np.sin(a)])
+
+
+class _LeakBuilder(_Builder):
+    def __init__(self, name, prof):
+        super().__init__(name, prof)
+        self.ns = prof["ns"]
+        self.count = 0
+
+    def slope(self):
+        self.count += 1
+        return LEAK_SLOPES[self.count % len(LEAK_SLOPES)]
+
+    def inside_stack(self, q, r):
+        return abs(q) <= self.ns and abs(r) <= self.ns and abs(q + r) <= self.ns
+
+    def forms(self, p, zv, q, r):
+        """max |a_k| / zz of the point p at height zv against cell (q, r), in doubles"""
+        zz = self.at(self.zh, zv)
+        Q = p[0] / (2 * C30) - p[1] / 3 - q * zz
+        R = p[1] * (2.0 / 3) - r * zz
+        return max(abs(Q - R), abs(2 * Q + R), abs(Q + 2 * R)) / zz
+
+    def in_glass(self, p, zv, q, r, margin=1e-3):
+        k = np.array(self.k(q, r))
+        if not self.forms(p, zv, q, r) < 1 - margin:
+            return False
+        if self.prof["ns"] and not pc_inside_outer(self.at(self.ext, zv), p):
+            return False
+        return (not self.inside_stack(q, r)) or float(np.hypot(*(p - k * self.at(self.zh, zv)))) > self.at(self.cap, zv) * (1 + margin)
+
+    def exit_segment(self, P, D, q, r):
+        """segment in which the ray P + (D, 1) t first leaves cell (q, r), in doubles (None: not before the last node)"""
+        for j in range(self.seg_of(P[2]) + 1, self.nmax + 1):
+            p = np.array(P[:2]) + np.asarray(D) * (self.z[j] - P[2])
+            if self.forms(p, self.z[j], q, r) > 1:
+                return j - 1
+        return None
+
+    def put(self, cell, fam, P, D, delta=0.0, zt=None, tnode=-1, block=None, literal_cap=None, flip=False, **more):
+        """a row from the start P and the transverse slope D; the direction is normalised in doubles (the row's d is the ray)"""
+        d = np.array([D[0], D[1], 1.0])
+        d = d / np.sqrt(d @ d)
+        if flip:
+            d = -d
+        self.rows.append([P[0], P[1], P[2], d[0], d[1], d[2], 0.0, -1.0, float(256 if flip else LEAK_UNITS)])
+        m = dict(profile=self.name, cell=cell, fam=fam, delta=delta, zt=zt, tnode=tnode, block=block)
+        m.update(more)
+        self.meta.append(m)
+
+    def graze_ok(self, target, zt, D, zs, zhi, K, delta, cap_t):
+        """in doubles: |u|^2 - cap^2 of the ray through `target` at zt against the axis K zh is smallest at zt among the nodes and
+        the middles of the segments of [zs, zhi] (a row whose closest approach lies elsewhere is not what its family means)"""
+        want = delta * cap_t * (2 * cap_t + delta * cap_t)
+        tg = np.array([float(target[0]), float(target[1])])
+        zs_ = [zs, zhi] + [v for v in self.z if zs < v < zhi]
+        zs_ += [0.5 * (a + b) for a, b in zip(sorted(zs_)[:-1], sorted(zs_)[1:])]
+        zs_ += [zt + sg * f * (zhi - zs) for sg in (1, -1) for f in (1e-2, 1e-4, 1e-6, 1e-8) if zs <= zt + sg * f * (zhi - zs) <= zhi]
+        for zv in zs_:
+            u = tg + np.asarray(D) * (zv - zt) - np.asarray(K) * self.at(self.zh, zv)
+            f = float(u @ u) - self.at(self.cap, zv) ** 2
+            if f < (0.75 * want if delta > 0 else 1.5 * want):
+                return False
+        return True
+
+    def through(self, cell, fam, target, zt, D, zs, delta, scale, **more):
+        """the ray with transverse slope D that passes `target` (two Fractions) at z = zt, started at zs: P rounded once; left out
+        where doubles cannot place a deviation of delta `scale`"""
+        F = self.F
+        back = F(float(zt)) - F(float(zs))
+        P = [float(target[0] - F(float(D[0])) * back), float(target[1] - F(float(D[1])) * back), float(zs)]
+        noise = _ulp(max(abs(P[0]), abs(P[1]))) + 2.0 ** -52 * float(np.hypot(*D)) * abs(float(back))
+        if delta != 0.0 and abs(delta) * scale < 64 * noise:
+            return False
+        self.put(cell, fam, P, D, delta, zt=float(zt), **more)
+        return True
+
+
+def pc_inside_outer(ext, p):
+    d = np.sqrt(ext * ext - (ext / 2) * (ext / 2))
+    return max(abs(p[1]), abs(C30 * p[0] + 0.5 * p[1]), abs(C30 * p[0] - 0.5 * p[1])) < d * (1 - 1e-3)
+
+
+def _wall_rows_of(name, prof):
+    B = _LeakBuilder(name, prof)
+    F = B.F
+    z, cap, zh, nmax = B.z, B.cap, B.zh, B.nmax
+    kind = prof["leak"]
+    seg = lambda j: z[j + 1] - z[j]
+
+    def centre(q, r, zv):
+        return np.array(B.k(q, r)) * B.at(zh, zv)
+
+    def centre_slope(q, r, j):
+        return B.axis_slope(B.k(q, r), j)
+
+    def zh_slope(j):
+        return (zh[j + 1] - zh[j]) / seg(j)
+
+    def cap_slope(j):
+        return (cap[j + 1] - cap[j]) / seg(j)
+
+    def inward(q, r):
+        """unit vector from the cell towards the optic's axis (any direction for the centre cell)"""
+        k = np.array(B.k(q, r))
+        n = float(np.hypot(*k))
+        return -k / n if n > 0 else _rot(20.0)
+
+    cells = leak_cells(prof["ns"])
+
+    # ---- every profile: a photon that flies on to the exit plane inside the glass, one flying backwards, starts that return at once
+    for cell, q, r in cells[:1] + cells[2:3]:
+        e = inward(q, r)
+        j0 = max(0, nmax - 6)
+        zs = z[j0] + 0.5 * seg(j0) if nmax > 1 else 0.25 * z[1]
+        if kind in ("long", "cross") and name != "last_zero":
+            zs = z[nmax - 1] + 0.5 * seg(nmax - 1)
+        p = centre(q, r, zs) + 0.93 * B.at(zh, zs) * _rot(30.0 if q == r == 0 else np.rad2deg(np.arctan2(e[1], e[0])) + 30.0)
+        if prof["ns"] == 0:
+            p = 0.5 * (B.at(cap, zs) + B.at(B.ext, zs)) * _rot(30.0)
+        if prof["ns"] == 0 or B.in_glass(p, zs, q, r, 1e-2):
+            D = centre_slope(q, r, min(j0, nmax - 1)) + 1e-4 * _rot(100.0)
+            B.put(cell, "exit", [p[0], p[1], zs], D)
+            if kind not in ("long", "cross"):
+                B.put(cell, "back", [p[0], p[1], zs], D, flip=True)
+    zend = z[nmax]
+    c0 = centre(0, 0, zend) + 0.93 * zh[nmax] * _rot(30.0)
+    B.put("centre", "begin", [c0[0], c0[1], zend], [1e-3, 0.0], expect="beyond")
+    B.put("centre", "begin", [c0[0], c0[1], float(np.nextafter(zend, 0.0))], [1e-3, 0.0], expect="in")
+    B.put("centre", "begin", [1.5 * B.ext[0], 0.0, 0.5 * z[1]], [1e-3, 0.0], expect="outside")
+
+    if kind == "aligned":
+        # on the grid: d = (0, 0, 1), P.z a multiple of 2^-14, in the glass of four cells; every step lands on a multiple of 2^-14 and
+        # every 64th (32nd) on a node
+        for cell, q, r in cells[:3] + cells[4:5]:
+            for zs in (0.0, 64 * G14, 3 * G14, 20 * 64 * G14 + G14, 37 * 64 * G14):
+                p = centre(q, r, zs) + 0.93 * zh[0] * _rot(30.0)
+                B.put(cell, "grid", [p[0], p[1], zs], [0.0, 0.0])
+    if kind == "long":
+        for cell, q, r in cells[:2]:
+            for zs, s in ((0.0, 0.0), (1.0e-3, 1e-4), (0.2, 1e-3)):
+                p = centre(q, r, zs) + 0.5 * zh[0] * _rot(30.0)
+                B.put(cell, "exit", [p[0], p[1], zs], s * _rot(70.0))
+            # grazing the capillary inside the long segment
+            for delta in (1e-9, -1e-9, 1e-3, -1e-3):
+                if q == r == 0:
+                    e, zt = _rot(10.0), 0.1
+                    D = 0.1 * _rot(100.0)
+                    tgt = [F(float(e[0])) * F(float(cap[0] * (1 + delta))), F(float(e[1])) * F(float(cap[0] * (1 + delta)))]
+                    B.through(cell, "cap", tgt, zt, D, zt - 4e-5, delta, cap[0], block=(zt - 4e-5, zt + 4e-5))
+
+    # ---- crossing into the neighbour early: what gives the probe room for its widest blocks
+    if kind in ("full", "cross", "aligned") and nmax >= 27:
+        for cell, q, r in cells[:2]:
+            for jn, deltas in ((4, MARCH_DELTAS if kind != "cross" else (1e-9, -1e-9, 1e-3)),):
+                for delta in deltas:
+                    s = (0.3, 0.1)[B.count % 2] if kind != "full" else max(B.slope(), 1e-3)
+                    B.count += 1
+                    zx = z[jn] + delta * seg(jn)
+                    n_hat = _rot(0.0)
+                    D = centre_slope(q, r, jn) + (s + C30 * abs(zh_slope(jn))) * n_hat
+                    tgt = centre(q, r, zx) + C30 * B.at(zh, zx) * n_hat + 0.1 * B.at(zh, zx) * _rot(90.0)
+                    bt = 0.3 * (C30 * B.at(zh, zx) - B.at(cap, zx))
+                    zs = max(zx - bt / s, 0.5 * (z[0] + z[1]) if jn > 1 else 0.0)
+                    if not zs < zx - 4 * abs(delta) * seg(jn):
+                        continue
+                    P = [tgt[0] - D[0] * (zx - zs), tgt[1] - D[1] * (zx - zs), zs]
+                    if B.in_glass(np.array(P[:2]), zs, q, r):
+                        B.through(cell, "xnode", [F(float(tgt[0])), F(float(tgt[1]))], zx, D, zs, delta, s * seg(jn), tnode=jn, nbr=(q + 1, r))
+            # a shallow crossing next to a corner: the ray stays in the neighbour's glass for dozens of segments
+            for delta in (1e-3, -1e-3):
+                jn, s = 2, 1e-3
+                zx = z[jn] + delta * seg(jn)
+                n_hat = _rot(0.0)
+                D = centre_slope(q, r, jn) + (s + C30 * abs(zh_slope(jn))) * n_hat
+                tgt = centre(q, r, zx) + C30 * B.at(zh, zx) * n_hat + 0.47 * B.at(zh, zx) * _rot(90.0)
+                zs = 0.5 * (z[0] + z[1])
+                P = [tgt[0] - D[0] * (zx - zs), tgt[1] - D[1] * (zx - zs), zs]
+                if B.in_glass(np.array(P[:2]), zs, q, r):
+                    B.put(cell, "xnode", P, D, delta, zt=zx, tnode=jn, nbr=(q + 1, r))
+
+    if kind == "mono":
+        for t in (10, 30, 55):
+            for delta in MARCH_DELTAS:
+                s = B.slope()
+                e = _rot(40.0 * (B.count % 9))
+                rho = cap[t] * (1 + delta)
+                D = s * np.array([-e[1], e[0]]) + cap_slope(t - 1) * e
+                bt = min(0.8 * np.sqrt(max(B.at(B.ext, z[t]) ** 2 - rho ** 2, 0.0)), s * (z[t] - z[1]))
+                zs = z[t] - bt / s
+                p = rho * e - D * (z[t] - zs)
+                if not (np.hypot(*p) < 0.98 * B.at(B.ext, zs) and np.hypot(*p) > 1.001 * B.at(cap, zs)):
+                    continue
+                tgt = [F(float(e[0])) * F(float(rho)), F(float(e[1])) * F(float(rho))]
+                if not B.graze_ok(tgt, z[t], D, zs, z[min(nmax, t + 1)], (0.0, 0.0), delta, cap[t]):
+                    continue
+                B.through("centre", "mono", tgt, z[t], D, zs, delta, cap[t], tnode=t, block=(zs, z[min(nmax, t + 1)]), nbr=(0, 0))
+
+    if kind != "full":
+        return B
+
+    kink = prof["kink"]
+    for cell, q, r in cells:
+        K = np.array(B.k(q, r))
+        stack = B.inside_stack(q, r)
+        away = -inward(q, r)
+
+        # ---- cap: grazing the cell's own capillary
+        if stack:
+            places = [("node", 9, z[9]), ("mid", 14, 0.5 * (z[14] + z[15]))] + ([("kink", kink, z[kink])] if kink else [])
+            for where, jt, zt in places:
+                for delta in MARCH_DELTAS:
+                    s = B.slope()
+                    e = _rot(60.0 * (B.count % 6) + 11.0)
+                    tng = np.array([-e[1], e[0]])
+                    rho = B.at(cap, zt) * (1 + delta)
+                    # the gap |u| - cap has slope 0 at zt on one side; at a node the side that makes it a minimum
+                    sides = [jt] if where == "mid" else [jt, jt - 1]
+                    done = False
+                    for js in sides:
+                        if done:
+                            continue
+                        w = s * tng + cap_slope(js) * e
+                        D = centre_slope(q, r, js) + w
+                        if where != "mid":
+                            jo = jt - 1 if js == jt else jt
+                            wo = D - centre_slope(q, r, jo)
+                            go = float(e @ wo) - cap_slope(jo)          # slope of the gap on the other side
+                            if (jo < js and go > 0) or (jo > js and go < 0):
+                                continue
+                        inr = C30 * B.at(zh, zt)
+                        bt = min(0.5 * np.sqrt(max(inr * inr - rho * rho, 0.0)), s * (zt - 0.5 * z[1]))
+                        zs = zt - bt / s
+                        zhi = min(z[nmax], zt + 0.5 * bt / s)
+                        p = centre(q, r, zt) + rho * e - D * (zt - zs)
+                        if B.forms(p, zs, q, r) >= 1 - 1e-3 or not pc_inside_outer(B.at(B.ext, zs), p):
+                            continue
+                        ct = [F(K[0]) * F(B.at(zh, zt)) + F(float(e[0])) * F(float(rho)), F(K[1]) * F(B.at(zh, zt)) + F(float(e[1])) * F(float(rho))]
+                        if not B.graze_ok(ct, zt, D, zs, zhi, K, delta, B.at(cap, zt)):
+                            continue
+                        done = B.through(cell, "cap", ct, zt, D, zs, delta, B.at(cap, zt), tnode=jt, block=(zs, zhi), where=where)
+
+        # ---- corner, edge, xnode
+        for kedge in ((0, 2, 3, 5) if cell in ("centre", "outer", "shell", "beyond") else (2,)):
+            n_hat = _rot(60.0 * kedge)
+            t_hat = _rot(60.0 * kedge + 90.0)
+            if not stack and float(n_hat @ away) > 0.3:
+                continue                      # a cell on or beyond the rim: only its inner edges lie inside the optic
+            js = 20 + kedge
+            zt = z[js] + 0.5 * seg(js)
+            zz_t = B.at(zh, zt)
+            for delta in MARCH_DELTAS:
+                # corner: through the point delta zz along the edge from its corner at 60 k + 30 degrees
+                s = B.slope()
+                corner = zz_t * _rot(60.0 * kedge + 30.0)
+                tgt = centre(q, r, zt) + corner - delta * zz_t * t_hat
+                D = centre_slope(q, r, js) + (s + abs(zh_slope(js))) * n_hat
+                bt = 0.3 * (zz_t - B.at(cap, zt))
+                zs = max(zt - bt / s, 0.5 * z[1])
+                P = [tgt[0] - D[0] * (zt - zs), tgt[1] - D[1] * (zt - zs), zs]
+                if B.in_glass(np.array(P[:2]), zs, q, r, 1e-6):
+                    B.put(cell, "corner", P, D, delta, zt=zt, tnode=js, kedge=kedge)
+                # edge: parallel to the edge, delta zz from it
+                s = B.slope()
+                je = 33                       # an all-literal flight (inside the margin) from here to the end stays under LEAK_UNITS
+                zs = z[je] + 0.25 * seg(je)
+                zz_s = B.at(zh, zs)
+                p = centre(q, r, zs) + (C30 - delta) * zz_s * n_hat - 0.3 * zz_s * t_hat
+                D = centre_slope(q, r, je) + (C30 - delta) * zh_slope(je) * n_hat + s * t_hat
+                if pc_inside_outer(B.at(B.ext, zs), p):
+                    B.put(cell, "edge", [p[0], p[1], zs], D, delta, zt=zs, tnode=je, kedge=kedge, zb=zs + min(0.7 * seg(je), 0.4 * zz_s / s))
+            for jn in (30,):
+                for delta in MARCH_DELTAS:
+                    s = B.slope()
+                    zx = z[jn] + delta * seg(jn)
+                    jx = jn if delta > 0 else jn - 1
+                    D = centre_slope(q, r, jx) + (s + C30 * abs(zh_slope(jx))) * n_hat
+                    tgt = centre(q, r, zx) + C30 * B.at(zh, zx) * n_hat + 0.1 * B.at(zh, zx) * t_hat
+                    bt = 0.3 * (C30 * B.at(zh, zx) - B.at(cap, zx))
+                    zs = max(zx - bt / s, 0.5 * z[1])
+                    P = [tgt[0] - D[0] * (zx - zs), tgt[1] - D[1] * (zx - zs), zs]
+                    if zs < zx - 4 * abs(delta) * seg(jn) and B.in_glass(np.array(P[:2]), zs, q, r):
+                        B.through(cell, "xnode", [F(float(tgt[0])), F(float(tgt[1]))], zx, D, zs, delta, s * seg(jn), tnode=jn, kedge=kedge)
+
+        # ---- side: out of the stack
+        if cell in ("outer", "shell"):
+            for s in (0.05, 0.1, 0.3):
+                for zs in (z[10] + 0.3 * seg(10), z[40] + 0.3 * seg(40)):
+                    p = centre(q, r, zs) + 0.9 * B.at(zh, zs) * _rot(np.rad2deg(np.arctan2(away[1], away[0])) + 30.0)
+                    if B.in_glass(p, zs, q, r, 1e-2):
+                        B.put(cell, "side", [p[0], p[1], zs], centre_slope(q, r, 10) + s * away)
+
+        # ---- nbr: into the neighbour (q + 1, r), past its capillary at cap (1 + delta) at node t
+        qn, rn = q + 1, r
+        if stack and B.inside_stack(qn, rn):
+            KN = np.array(B.k(qn, rn))
+            plan = [(40, L, 40 - L + 1 - a, "L%d%+d" % (L, -a)) for L in (5, 25) for a in (0, 1, 2)]
+            plan += [(t, 5, t - 5, "end") for t in (nmax - 2, nmax - 1, nmax)]
+            if kink:
+                plan += [(kink, 5, kink - 3, "kink"), (kink, 25, kink - 12, "kink")]
+            for t, L, ic, tag in plan:
+                for delta in MARCH_DELTAS:
+                    zt, zx = z[t], z[ic] + 0.5 * seg(ic)
+                    rho = cap[t] * (1 + delta) if cap[t] > 0 else 0.0
+                    X = np.array([-C30, 0.3]) * B.at(zh, zx)                     # on the shared edge, seen from the neighbour's centre
+                    d0 = float(np.hypot(*X))
+                    if not rho < 0.98 * d0:
+                        continue
+                    th = np.arctan2(X[1], X[0]) - np.arccos(rho / d0)
+                    e = np.array([np.cos(th), np.sin(th)])
+                    G = rho * e
+                    run = G - X
+                    ell = float(np.hypot(*run))
+                    sig = ell / (zt - zx)
+                    tgt = [F(KN[0]) * F(B.at(zh, zt)) + F(float(e[0])) * F(float(rho)), F(KN[1]) * F(B.at(zh, zt)) + F(float(e[1])) * F(float(rho))]
+                    for js in (t - 1, min(t, nmax - 1)):         # the side of the node on which the gap has slope 0: the one that makes it a minimum
+                        D = B.axis_slope(KN, js) + sig * run / ell + cap_slope(js) * e
+                        bt = 0.25 * (B.at(zh, zx) - B.at(cap, zx))
+                        zs = max(zx - bt / sig, z[max(ic - 1, 0)] + 0.1 * seg(max(ic - 1, 0)))
+                        p = KN * B.at(zh, zt) + G - D * (zt - zs)
+                        if not B.in_glass(p, zs, q, r) or B.exit_segment([p[0], p[1], zs], D, q, r) != ic:
+                            continue
+                        if not B.graze_ok(tgt, zt, D, z[B.seg_of(zs)], z[min(nmax, t + 1)], KN, delta, cap[t]):
+                            continue
+                        if B.through(cell, "nbr", tgt, zt, D, zs, delta, cap[t], tnode=t, block=(zs, zt), nbr=(qn, rn), tag=tag, ic=ic, L=L):
+                            break
+    return B
+
+
+@functools.lru_cache(maxsize=None)
+def wall_grids():
+    """name -> dict(problem, profile, rows [n, 9] of pyprobe.WALL_COLS (literal 0, hint -1), meta [n])"""
+    out = {}
+    for name, prof in leak_profiles().items():
+        B = _wall_rows_of(name, prof)
+        out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof,
+                         rows=np.array(B.rows, dtype=np.float64).reshape(-1, 9), meta=B.meta)
+    return out
+
+
+# ---- OUTER: c on the exit plane outside the hexagon, dz > 0.  Going backwards along the edge with normal (0, 1):
+#   dip    the ray is inside the outer hexagon by delta ext at exactly one node j (y = hexd_j (1 - delta) there, dy/dz between the
+#          slopes of hexd on both sides): where the hexagon sticks out at a node (ext_kink's kink, every node of the bulge);
+#          delta < 0: nowhere inside (return 0)
+#   cross  the ray enters the hexagon between nodes j + 1 and j, delta ext deep at node j: on every profile
+# j takes the positions 1 .. L - 1 of the blocks the scan would skip (nodes nmax - L .. nmax and the block below, both strides).  A
+# row whose pattern of inside / outside nodes is not the one meant (in doubles) is left out.
+OUTER_PROFILES = ("ext_kink", "bulge", "irregular", "cylinder", "taper")
+
+
+@functools.lru_cache(maxsize=None)
+def outer_grids():
+    """name -> dict(problem, rows [n, 7] of pyprobe.OUTER_COLS (literal 0), meta [n])"""
+    from fractions import Fraction as F
+    out = {}
+    profs = leak_profiles()
+    for name in OUTER_PROFILES:
+        prof = profs[name]
+        z, ext = prof["z"], prof["ext"]
+        nmax = len(z) - 1
+        hexd = np.sqrt(ext * ext - (ext / 2) * (ext / 2))
+        rows, meta = [], []
+        nodes = []
+        for L in (5, 25):
+            for blk in (0, 1):
+                hi = nmax - blk * L
+                nodes += [(hi - L + pos, L, pos) for pos in range(1, L) if 1 <= hi - L + pos < nmax]
+        if prof["kink"]:
+            nodes.append((prof["kink"], 25, prof["kink"] - (nmax - 50)))
+
+        def add(fam, j, L, pos, delta, yj, Dy):
+            x = 0.01 * ext[j] * ((len(rows) % 5) - 2)
+            y = yj + Dy * (z - z[j])                                   # at every node, in doubles
+            inside = y <= hexd
+            want = np.zeros(nmax + 1, dtype=bool)
+            if fam == "dip":
+                want[j] = delta >= 0
+            else:
+                want[:j + 1] = True
+            lo = 0 if fam == "dip" else j
+            keep = np.ones(nmax + 1, dtype=bool)
+            keep[j] = delta != 0.0                                     # delta = 0: node j itself is on the edge
+            if not np.array_equal((inside & keep)[lo:], (want & keep)[lo:]):
+                return
+            cy = float(F(float(yj)) + F(float(Dy)) * (F(float(z[nmax])) - F(float(z[j]))))
+            d = np.array([0.0, Dy, 1.0])
+            d /= np.sqrt(d @ d)
+            rows.append([x, cy, z[nmax], d[0], d[1], d[2], 0.0])
+            meta.append(dict(profile=name, fam=fam, node=j, L=L, pos=pos, delta=delta))
+
+        seen = set()
+        for j, L, pos in nodes:
+            if (j, L) in seen:
+                continue
+            seen.add((j, L))
+            sl, sr = (hexd[j] - hexd[j - 1]) / (z[j] - z[j - 1]), (hexd[j + 1] - hexd[j]) / (z[j + 1] - z[j])
+            for delta in MARCH_DELTAS + (0.0, 1e-5, 1e-4):
+                add("dip", j, L, pos, delta, hexd[j] * (1 - delta), 0.5 * (sl + sr))
+            for delta in (1e-12, 1e-9, 1e-6, 1e-3):
+                # delta ext inside at node j, as far outside at node j + 1
+                add("cross", j, L, pos, delta, hexd[j] * (1 - delta), sr + 2 * delta * hexd[j] / (z[j + 1] - z[j]))
+        # inside at the exit plane (here == 1) and dz < 0: literal agreement only
+        for k in range(4):
+            rows.append([0.1 * ext[nmax] * k, 0.2 * ext[nmax], z[nmax], 0.01, 0.02 * k, 1.0, 0.0])
+            meta.append(dict(profile=name, fam="here", node=-1, L=0, pos=0, delta=0.0))
+            rows.append([0.0, 1.3 * ext[0], z[nmax // 2], 0.01 * k, -0.05, -1.0, 0.0])
+            meta.append(dict(profile=name, fam="down", node=-1, L=0, pos=0, delta=0.0))
+        out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof,
+                         rows=np.array(rows, dtype=np.float64).reshape(-1, 7), meta=meta)
+    return out
+
+
+# ---- HEX: points delta of a cell size inside (delta > 0) or outside (delta < 0) of each edge's middle and, along the bisector, of
+# each corner; delta = 0 and +-1 ulp (the rows placed on an edge or corner on purpose) for two cells only.  A row is left out where
+# doubles cannot place it (|delta| below 64 roundings of the coordinates).
+HEX_ZZ = (1e-4, 1e-3, 1e-2, 0.1, 1.0)
+HEX_NS = 258
+HEX_CELLS = ((0, 0), (1, 0), (0, -1), (-3, 2), (77, 76), (-77, 258), (258, 0), (-258, 0), (0, -258), (129, 129), (-258, 258), (200, -258))
+
+
+@functools.lru_cache(maxsize=None)
+def hex_rows():
+    """(rows [n, 3] = x, y, zz; meta [n])"""
+    rows, meta = [], []
+    for zz in HEX_ZZ:
+        for q, r in HEX_CELLS:
+            c = np.array([(2.0 * q + r) * C30, 1.5 * r]) * zz
+            rows.append([c[0], c[1], zz])
+            meta.append(dict(cell=(q, r), fam="centre", delta=1.0, k=-1))
+            noise = 64 * (_ulp(max(abs(c[0]), abs(c[1]), zz)) / zz)
+            on_purpose = (q, r) in ((1, 0), (-77, 258)) and zz in (1e-3, 1.0)
+            for k in range(6):
+                for fam, base in (("edge", C30 * _rot(60.0 * k)), ("corner", _rot(60.0 * k + 30.0))):
+                    inwards = -base / np.hypot(*base)
+                    for delta in MARCH_DELTAS + ((0.0, "+ulp", "-ulp") if on_purpose else ()):
+                        if isinstance(delta, str):
+                            p = c + base * zz
+                            i = int(np.argmax(np.abs(base)))
+                            p[i] = np.nextafter(p[i], np.inf if delta == "+ulp" else -np.inf)
+                            dl = 0.0
+                        else:
+                            if delta != 0.0 and abs(delta) < noise:
+                                continue
+                            # outside a corner the bisector is the edge between the two neighbours: go out along edge k's normal
+                            step = delta * inwards if (fam == "edge" or delta >= 0) else -delta * _rot(60.0 * k)
+                            p = c + (base + step) * zz
+                            dl = delta
+                        rows.append([p[0], p[1], zz])
+                        meta.append(dict(cell=(q, r), fam=fam, delta=dl, k=k, purpose=isinstance(delta, str) or delta == 0.0))
+    return np.array(rows, dtype=np.float64).reshape(-1, 3), meta

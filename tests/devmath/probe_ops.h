@@ -11,12 +11,16 @@
  *
  * Op MARCH (PC_PROBE_MARCH) walks one photon per row through the certified march of a whole profile -- pc_launch_init, pc_march_step,
  * pc_event_pre -- and reports every step; see pc_probe_march_eval.
+ *
+ * The leak ops (PC_PROBE_WALL, PC_PROBE_OUTER, PC_PROBE_HEX) call the wall search of pc_leak.h -- pc_wall_begin, pc_wall_step,
+ * pc_wall_probe as pc_leak_launch sequences them; pc_outer_intersect; pc_hex_index -- on the whole profile; see pc_probe_wall_eval.
  */
 #ifndef PC_PROBE_OPS_H
 #define PC_PROBE_OPS_H
 
 #include "pc_problem.h"
 #include "pc_device.h"
+#include "pc_leak.h"
 
 #define PC_PROBE_IN 8
 
@@ -114,9 +118,10 @@ enum { PC_PROBE_SEGMENT = 13, PC_PROBE_GEOM = 14, PC_PROBE_BOUNCE = 15, PC_PROBE
 #define PC_PROBE_SETUP_REJECT (-100)
 
 static inline int pc_probe_is_geom(int op) { return op >= PC_PROBE_SEGMENT && op < PC_PROBE_GEOM_END; }
-/* row widths per op (PC_PROBE_MARCH = 16 and its widths are defined with the op, further down) */
-static inline int pc_probe_in_width(int op) { return (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
-static inline int pc_probe_out_width(int op) { return (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
+/* row widths per op (PC_PROBE_MARCH = 16, PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19 and their widths are defined
+ * with the ops, further down) */
+static inline int pc_probe_in_width(int op) { return (op == 17) ? 9 : (op == 18) ? 7 : (op == 19) ? 3 : (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
+static inline int pc_probe_out_width(int op) { return (op == 17) ? 20 + 17*96 : (op == 18) ? 4 : (op == 19) ? 2 : (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
 
 /* the product's setup (pc_build_tables) of the two-node profile (z0, z1), (cap0, cap1) of a SEGMENT row, glass and energies
  * of p; returns 0, or -1 when the setup rejects the profile */
@@ -310,6 +315,148 @@ static inline int pc_probe_march_check(const pc_hip_problem *p, long long n, int
 	for (long long i = 0; i < n; i++) {
 		const double lit = in[i*in_w + 9], K = in[i*in_w + 10];
 		if (!(lit == 0. || lit == 1.) || !(K >= 0. && K <= PC_PROBE_MARCH_K) || K != (double)(int)K) return -2;
+	}
+	return 0;
+}
+
+/* ------------------------------------------------------------------ the leak ops
+ * Numbered after MARCH; rows of their own widths and an entry point each (probe_run_wall / _outer / _hex and their emul_ twins).
+ * Product code only (pc_leak.h), on the tables pc_build_tables makes of the whole profile: z, cap, zh, cap2, hexd, idz, ext, stp,
+ * istp, mg, dr.
+ *
+ * WALL   one photon in the glass per row.  A pc_leak_lane is filled with P, the direction d AS GIVEN (the caller passes a unit
+ *        vector; nothing is normalised here, so the row's doubles are the ray), kx = ky = 0 and pc_trace_begin; then
+ *        pc_wall_begin(T, Pm, L, PC_LS_INWALL_END, hint) and pc_wall_step / pc_wall_probe as pc_leak_launch sequences them, until the
+ *        state returned is PC_LS_INWALL_END or max_units units are spent.
+ *   in[9]     = Px, Py, Pz, dx, dy, dz, literal (0 / 1), hint (-1 or a node index), max_units
+ *   out[1652] = begin [0..3]: state pc_wall_begin returned, q_i, r_i, z_id (0 when it returned at once)
+ *               end   [4..19]: wt, d_travel, q_out, r_out, hx, hy, hz, px, py, pz, nst, dist, z_id, iesc, units used,
+ *                              how (PC_PROBE_WALL_FINISHED / _CAPPED)
+ *               trail [20 + 17 t ..], one entry for each of the first PC_PROBE_WALL_K units: state called, z_id before, z_id after,
+ *                              pz before, pz after, nst before, nst after, q_i, r_i, q_new, r_new, iesc (all after), then five
+ *                              columns only a build with PC_LEAK_STATS fills (-1 otherwise: the device has no counters), from the
+ *                              counters that moved during the unit: kind (0 certified stretch, 1 literal step, 2 probe unit), blocks
+ *                              skipped at level 0, 1, 2, and the visit (0 none, 6 miss, 7 hit).  Units beyond run without a trail.
+ *   code = W.wt at the end.
+ * OUTER  in[7] = cx, cy, cz, dx, dy, dz, literal;  out[4] = return value of pc_outer_intersect, ox, oy, oz (0 when it returned 0)
+ * HEX    in[3] = x, y, zz;  out[2] = q, r of pc_hex_index */
+enum { PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19 };
+#define PC_PROBE_WALL_IN 9
+#define PC_PROBE_WALL_K 96
+#define PC_PROBE_WALL_HEAD 20
+#define PC_PROBE_WALL_ENTRY 17
+#define PC_PROBE_WALL_SHARED 12       /* columns of a trail entry both builds fill */
+#define PC_PROBE_WALL_OUT (PC_PROBE_WALL_HEAD + PC_PROBE_WALL_ENTRY*PC_PROBE_WALL_K)
+#define PC_PROBE_OUTER_IN 7
+#define PC_PROBE_OUTER_OUT 4
+#define PC_PROBE_HEX_IN 3
+#define PC_PROBE_HEX_OUT 2
+#define PC_PROBE_WALL_UNITS_DEVICE 200000LL      /* a lane of the device build is never asked for more units than this */
+#define PC_PROBE_WALL_UNITS_HOST 50000000LL
+enum { PC_PROBE_WALL_FINISHED = 0, PC_PROBE_WALL_CAPPED = 1 };
+
+/* the device-side view of the tables of a leak op: n = nmax + 1 entries each, in this order in one buffer of PC_PROBE_LEAK_TAB*n
+ * doubles (z, cap, zh, cap2, hexd, idz, ext, stp, istp) plus n pc_marg4 and n pc_drdev */
+#define PC_PROBE_LEAK_TAB 9
+PC_HD void pc_probe_leak_tables(pc_tables &T, const double *tab, const pc_marg4 *mg, const pc_drdev *dr, int n)
+{
+	pc_probe_march_tables(T, tab, mg, n);
+	T.stp = tab + 7*n; T.istp = tab + 8*n;
+	T.dr = dr;
+}
+
+PC_HD void pc_probe_wall_eval(const pc_tables &T, const pc_params &Pm0, const double *in, double *out, int *code)
+{
+	for (int j = 0; j < PC_PROBE_WALL_HEAD; j++) out[j] = 0.;       /* the trail is zeroed by the caller */
+	pc_params Pm = Pm0;
+	Pm.literal = (in[6] != 0.) ? 1 : 0;
+	const long long max_units = (long long)in[8];
+	pc_leak_lane L;
+	L.w = pc_wall();
+	pc_photon<0> &ph = L.ph;
+	ph.Px = in[0]; ph.Py = in[1]; ph.Pz = in[2];
+	ph.dx = in[3]; ph.dy = in[4]; ph.dz = in[5];
+	ph.ex = ph.ey = ph.ez = 0.;
+	ph.kx = ph.ky = ph.kn = 0.;
+	ph.C0 = 0.f; ph.dtravel = 0.;
+	ph.w[0] = 1.;
+	ph.wmem = nullptr; ph.wstride = 0;
+	ph.i = ph.irefl = ph.first = ph.bnd = ph.wset = ph.lv = ph.rc = ph.qr = 0;
+	pc_trace_begin(ph);
+	pc_wall &W = L.w;
+	int st = pc_wall_begin(T, Pm, L, PC_LS_INWALL_END, (int)in[7]);
+	out[0] = st;
+	if (st != PC_LS_INWALL_END) { out[1] = W.q_i; out[2] = W.r_i; out[3] = W.z_id; }
+	long long units = 0;
+	int how = PC_PROBE_WALL_FINISHED;
+	while (st != PC_LS_INWALL_END) {
+		if (units >= max_units) { how = PC_PROBE_WALL_CAPPED; break; }
+		const int called = st, z0 = W.z_id;
+		const double pz0 = W.pz, nst0 = (double)W.nst;
+#ifdef PC_LEAK_STATS
+		long long c0[8];
+		for (int j = 0; j < 8; j++) c0[j] = pc_leak_stats[j];
+#endif
+		st = (called == PC_LS_WALL_STEP) ? pc_wall_step(T, Pm, L, L.after_wall) : pc_wall_probe(T, Pm, L, L.after_wall);
+		if (units < PC_PROBE_WALL_K) {
+			double *tr = out + PC_PROBE_WALL_HEAD + PC_PROBE_WALL_ENTRY*units;
+			tr[0] = called; tr[1] = z0; tr[2] = W.z_id; tr[3] = pz0; tr[4] = W.pz; tr[5] = nst0; tr[6] = (double)W.nst;
+			tr[7] = W.q_i; tr[8] = W.r_i; tr[9] = W.q_new; tr[10] = W.r_new; tr[11] = W.iesc;
+			for (int j = PC_PROBE_WALL_SHARED; j < PC_PROBE_WALL_ENTRY; j++) tr[j] = -1.;
+#ifdef PC_LEAK_STATS
+			long long c[8];
+			for (int j = 0; j < 8; j++) c[j] = pc_leak_stats[j] - c0[j];
+			tr[12] = (called == PC_LS_WALL_PROBE) ? 2. : (c[0] ? 0. : 1.);
+			tr[13] = (double)c[3]; tr[14] = (double)c[4]; tr[15] = (double)c[5];
+			tr[16] = c[7] ? 7. : (c[6] ? 6. : 0.);
+#endif
+		}
+		units++;
+	}
+	out[4] = W.wt; out[5] = W.d_travel; out[6] = W.q_out; out[7] = W.r_out;
+	out[8] = W.hx; out[9] = W.hy; out[10] = W.hz; out[11] = W.px; out[12] = W.py; out[13] = W.pz;
+	out[14] = (double)W.nst; out[15] = W.dist; out[16] = W.z_id; out[17] = W.iesc; out[18] = (double)units; out[19] = how;
+	code[0] = W.wt;
+}
+
+PC_HD void pc_probe_outer_eval(const pc_tables &T, const pc_params &Pm0, const double *in, double *out, int *code)
+{
+	pc_params Pm = Pm0;
+	Pm.literal = (in[6] != 0.) ? 1 : 0;
+	double ox = 0., oy = 0., oz = 0.;
+	const int r = pc_outer_intersect(T, Pm, in[0], in[1], in[2], in[3], in[4], in[5], ox, oy, oz);
+	out[0] = r; out[1] = r ? ox : 0.; out[2] = r ? oy : 0.; out[3] = r ? oz : 0.;
+	code[0] = r;
+}
+
+PC_HD void pc_probe_hex_eval(const double *in, double *out, int *code)
+{
+	pc_hex_index(in[0], in[1], in[2], out[0], out[1]);
+	code[0] = 0;
+}
+
+/* host-side checks of a leak op, in both builds, before anything runs: widths; every value finite; WALL: dz != 0 (pc_wall_step
+ * then runs 2^28 units by design -- a hang on a GPU), literal 0 / 1, hint -1 or a node index, max_units a whole number of at most
+ * `unit_cap`; OUTER: literal 0 / 1; HEX: zz > 0 */
+static_assert(PC_PROBE_WALL_OUT == 20 + 17*96, "widths of op WALL as pc_probe_out_width states them");
+static inline int pc_probe_leak_check(const pc_hip_problem *p, int op, long long n, int in_w, int out_w, const double *in, long long unit_cap)
+{
+	if (op < PC_PROBE_WALL || op > PC_PROBE_HEX || n < 0 || in_w != pc_probe_in_width(op) || out_w != pc_probe_out_width(op)) return -2;
+	if (p->nmax < 1) return -2;
+	for (long long i = 0; i < n; i++) {
+		const double *r = in + i*in_w;
+		for (int j = 0; j < in_w; j++)
+			if (!std::isfinite(r[j])) return -2;
+		if (op == PC_PROBE_WALL) {
+			if (r[5] == 0.) return -2;
+			if (!(r[6] == 0. || r[6] == 1.)) return -2;
+			if (!(r[7] >= -1. && r[7] <= (double)p->nmax) || r[7] != (double)(int)r[7]) return -2;
+			if (!(r[8] >= 0. && r[8] <= (double)unit_cap) || r[8] != (double)(long long)r[8]) return -2;
+		} else if (op == PC_PROBE_OUTER) {
+			if (!(r[6] == 0. || r[6] == 1.)) return -2;
+		} else {
+			if (!(r[2] > 0.)) return -2;
+		}
 	}
 	return 0;
 }

@@ -1,7 +1,7 @@
 """TEST-ONLY: the arithmetic of pc_device.h element by element, on the device (probe.hip) or in the host compile of the same header
 (tests/emul/pc_emul.cpp, IEEE sqrt, division and exp).  Both take the per-energy constants from the product's own setup
 (pc_build_tables) of the Problem passed in.  Op MARCH (run_march) walks photons through the certified march of the Problem's whole
-profile."""
+profile; ops WALL, OUTER and HEX (run_wall, run_outer, run_hex) call the wall search of pc_leak.h on it."""
 import ctypes as C
 import os
 import subprocess
@@ -33,7 +33,8 @@ EC_FIELDS = ("n_re", "n_im", "ninv2_re", "ninv2_im", "rough_c", "valid", "d2", "
 def _sources():
     hip = os.path.join(_ROOT, "polycap_amd", "csrc", "hip")
     return [os.path.join(_HERE, "probe.hip"), os.path.join(_HERE, "probe_ops.h"),
-            os.path.join(hip, "pc_device.h"), os.path.join(hip, "pc_problem.h"), os.path.join(_ROOT, "include", "polycap-hip.h")]
+            os.path.join(hip, "pc_device.h"), os.path.join(hip, "pc_problem.h"), os.path.join(hip, "pc_leak.h"),
+            os.path.join(_ROOT, "include", "polycap-hip.h")]
 
 
 def compile_cmd(out=SO):
@@ -65,6 +66,9 @@ def lib():
         L.probe_run_march.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
                                       C.POINTER(C.c_int32), C.c_char_p]
         L.probe_run_march.restype = C.c_int
+        for f in (L.probe_run_wall, L.probe_run_outer, L.probe_run_hex):
+            f.argtypes = L.probe_run_march.argtypes
+            f.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -172,6 +176,73 @@ def march_trail(row):
     """trail of one MARCH output row: list of (i before, i after, kind, creep) as ints"""
     nt = int(row[MARCH_HEAD_COLS.index("n_trail")])
     return [tuple(int(v) for v in row[MARCH_HEAD + 4 * t: MARCH_HEAD + 4 * t + 4]) for t in range(nt)]
+
+
+# the leak ops (probe_ops.h): the wall search of pc_leak.h on the problem's whole profile
+WALL_IN, WALL_K, WALL_HEAD, WALL_ENTRY, WALL_SHARED = 9, 96, 20, 17, 12
+WALL_OUT = WALL_HEAD + WALL_ENTRY * WALL_K
+WALL_COLS = ("Px", "Py", "Pz", "dx", "dy", "dz", "literal", "hint", "max_units")
+WALL_HEAD_COLS = ("begin", "q_i", "r_i", "z_id0",
+                  "wt", "d_travel", "q_out", "r_out", "hx", "hy", "hz", "px", "py", "pz", "nst", "dist", "z_id", "iesc", "units", "how")
+WALL_END_COLS = WALL_HEAD_COLS[4:18]          # what the certified and the literal search of a row must agree on
+WALL_TRAIL_COLS = ("state", "z_id_b", "z_id_a", "pz_b", "pz_a", "nst_b", "nst_a", "q_i", "r_i", "q_new", "r_new", "iesc",
+                   "kind", "skip0", "skip1", "skip2", "visit")
+WALL_FINISHED, WALL_CAPPED = 0, 1
+WALL_UNITS_DEVICE, WALL_UNITS_HOST = 200000, 50000000
+LS_WALL_STEP, LS_WALL_PROBE, LS_INWALL_END = 3, 4, 6
+KIND_CERTIFIED, KIND_LITERAL, KIND_PROBE = 0, 1, 2
+OUTER_IN, OUTER_OUT = 7, 4
+OUTER_COLS = ("cx", "cy", "cz", "dx", "dy", "dz", "literal")
+HEX_IN, HEX_OUT = 3, 2
+
+
+def _run_leak(problem, name, x, in_w, out_w, device):
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, in_w)
+    n = x.shape[0]
+    out = np.zeros((n, out_w))
+    code = np.zeros(n, dtype=np.int32)
+    args = (C.byref(problem.s), n, x.ctypes.data_as(c_double_p), in_w, out.ctypes.data_as(c_double_p), out_w,
+            code.ctypes.data_as(C.POINTER(C.c_int32)))
+    if device:
+        err = C.create_string_buffer(256)
+        r = getattr(lib(), "probe_run_" + name)(*args, err)
+        if r:
+            raise RuntimeError("probe_run_%s failed: %d %s" % (name, r, err.value.decode(errors="replace")))
+    else:
+        from tests.emul import pyemul
+        r = getattr(pyemul.wall_lib() if name == "wall" else pyemul.lib(), "emul_probe_run_" + name)(*args)
+        if r:
+            raise RuntimeError("emul_probe_run_%s failed: %d" % (name, r))
+    return out, code
+
+
+def run_wall(problem, x, device=True):
+    """Op WALL on the rows x [n, WALL_IN] (WALL_COLS): (out [n, WALL_OUT], code [n]); out[:, :WALL_HEAD] are WALL_HEAD_COLS, then
+    WALL_K trail entries of WALL_TRAIL_COLS.  The last five trail columns (the kind of the unit) are filled by the host compile only
+    (-1 on the device)."""
+    return _run_leak(problem, "wall", x, WALL_IN, WALL_OUT, device)
+
+
+def run_outer(problem, x, device=True):
+    """Op OUTER on the rows x [n, OUTER_IN] (OUTER_COLS): (out [n, 4] = return value, ox, oy, oz; code [n])"""
+    return _run_leak(problem, "outer", x, OUTER_IN, OUTER_OUT, device)
+
+
+def run_hex(problem, x, device=True):
+    """Op HEX on the rows x [n, 3] = x, y, zz: (out [n, 2] = q, r; code [n])"""
+    return _run_leak(problem, "hex", x, HEX_IN, HEX_OUT, device)
+
+
+def wall_trail(row):
+    """trail of one WALL output row: array [units recorded, WALL_ENTRY]"""
+    nt = min(int(row[WALL_HEAD_COLS.index("units")]), WALL_K)
+    return row[WALL_HEAD:WALL_HEAD + WALL_ENTRY * nt].reshape(nt, WALL_ENTRY)
+
+
+def wall_shared(out):
+    """the part of WALL output rows both builds fill: the head and the first WALL_SHARED columns of every trail entry"""
+    tr = out[:, WALL_HEAD:].reshape(out.shape[0], WALL_K, WALL_ENTRY)[:, :, :WALL_SHARED]
+    return np.concatenate([out[:, :WALL_HEAD], tr.reshape(out.shape[0], -1)], axis=1)
 
 
 def energy_consts(problem):

@@ -410,4 +410,44 @@ int emul_energy_consts(const pc_hip_problem *p, double *out)
 	return 0;
 }
 
+/* the host builds of probe.hip's probe_run_outer and probe_run_hex (op WALL has a library of its own, pc_emul_wall.cpp: it is
+ * compiled with the unit counters of pc_leak.h, which no entry point of this file sees) */
+int emul_probe_run_outer(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_leak_check(p, PC_PROBE_OUTER, n, in_w, out_w, in, 0)) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		int cd = 0;
+		pc_probe_outer_eval(E.T, E.t.pm, in + i*in_w, out + i*out_w, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
+int emul_probe_run_hex(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	if (pc_probe_leak_check(p, PC_PROBE_HEX, n, in_w, out_w, in, 0)) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		int cd = 0;
+		pc_probe_hex_eval(in + i*in_w, out + i*out_w, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
+/* Test-only accessor: the leak path's tables of p, node[(nmax + 1) x 4] = stp, istp, dr.d1, dr.d2 (every float converts exactly) */
+int emul_leak_tables(const pc_hip_problem *p, double *node)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	for (int i = 0; i <= p->nmax; i++) {
+		double *o = node + 4*i;
+		o[0] = E.t.stp[i]; o[1] = E.t.istp[i]; o[2] = E.t.dr[i].d1; o[3] = E.t.dr[i].d2;
+	}
+	return 0;
+}
+
 } // extern "C"

@@ -10,6 +10,7 @@ from polycap_amd._cabi import ProblemS, c_double_p, c_int64_p, dptr
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _LIB = None
+_WALL_LIB = None
 
 
 def lib():
@@ -58,8 +59,36 @@ def lib():
         L.emul_probe_run_march.restype = C.c_int
         L.emul_march_tables.argtypes = [C.POINTER(ProblemS), c_double_p, c_double_p]
         L.emul_march_tables.restype = C.c_int
+        for f in (L.emul_probe_run_outer, L.emul_probe_run_hex):
+            f.argtypes = L.emul_probe_run_march.argtypes
+            f.restype = C.c_int
+        L.emul_leak_tables.argtypes = [C.POINTER(ProblemS), c_double_p]
+        L.emul_leak_tables.restype = C.c_int
         _LIB = L
     return _LIB
+
+
+def wall_lib():
+    """Host compile of probe op WALL with the unit counters of pc_leak.h (pc_emul_wall.cpp): a library of its own, so that
+    libpc_emul.so is compiled as ever."""
+    global _WALL_LIB
+    if _WALL_LIB is None:
+        so = os.path.join(_HERE, "libpc_emul_wall.so")
+        hip = os.path.join(_ROOT, "polycap_amd", "csrc", "hip")
+        srcs = [os.path.join(_HERE, "pc_emul_wall.cpp"), os.path.join(hip, "pc_device.h"), os.path.join(hip, "pc_problem.h"),
+                os.path.join(hip, "pc_leak.h"), os.path.join(_ROOT, "tests", "devmath", "probe_ops.h")]
+        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+            tmp = so + ".%d.tmp" % os.getpid()
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
+                                   "-ffp-contract=off", "-mfma",             # the flags of libpc_emul.so: the same IEEE operation sequence
+                                   "-I" + os.path.join(_ROOT, "include"), "-I" + hip, "-o", tmp, srcs[0]])
+            os.replace(tmp, so)
+        L = C.CDLL(so)
+        L.emul_probe_run_wall.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
+                                          C.POINTER(C.c_int32)]
+        L.emul_probe_run_wall.restype = C.c_int
+        _WALL_LIB = L
+    return _WALL_LIB
 
 
 def launch_batch(problem, start, direction, elecv, literal=False, use_regs=True):
@@ -135,6 +164,15 @@ def march_tables(problem):
     t.update({k: float(scal[j]) for j, k in enumerate(MARCH_SCALARS)})
     t["L1"], t["L2"], t["mono"] = int(t["L1"]), int(t["L2"]), int(t["mono"])
     return t
+
+
+def leak_tables(problem):
+    """The leak path's tables of `problem` (emul_leak_tables): dict of per-node arrays stp, istp, d1, d2 (pc_drdev)."""
+    node = np.zeros((problem.nmax + 1, 4))
+    r = lib().emul_leak_tables(C.byref(problem.s), dptr(node))
+    if r:
+        raise RuntimeError("emul_leak_tables failed: %d" % r)
+    return {k: node[:, j].copy() for j, k in enumerate(("stp", "istp", "d1", "d2"))}
 
 
 def sort_leak_records(rec):
