@@ -616,7 +616,11 @@ PC_HD int pc_march_ok(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph
 		/* boundary capillary (or mono-capillary; always level 0): the hexagon tests of the visit are not implied, do them:
 		 * axis at both nodes (src/polycap-capil.c:1263) and the ray at z_i (:1296-1308) */
 		double z0 = T.z[i0], zh0 = T.zh[i0], h0 = T.hexd[i0], h1 = T.hexd[i1];
-		double px = fma(ph.sx, z0, ph.ox), py = fma(ph.sy, z0, ph.oy);
+		/* the ray at z_i as the literal visit forms it (pc_segment: from P, not from the ray's offset at z = 0): with the centre of
+		 * a boundary capillary on the outer hexagon a ray through its axis at a node meets the hexagon there, and the two forms
+		 * round to different sides of it -- the march then went on where the visit ends the photon */
+		const double t0 = z0 - ph.Pz;
+		double px = fma(ph.sx, t0, ph.Px), py = fma(ph.sy, t0, ph.Py);
 		const bool out0 = pc_outside_hexd(h0, ph.kx*zh0, ph.ky*zh0), out1 = pc_outside_hexd(h1, ph.kx*zh1, ph.ky*zh1);
 		ok = ok & !out0 & !out1 & !pc_outside_hexd(h0, px, py);
 	}
@@ -666,8 +670,10 @@ PC_HD int pc_march_first_ok(const pc_tables &T, const pc_params &Pm, pc_photon<N
 		double Cl = fma(qx, qx, fma(qy, qy, -Rl*Rl));
 		ok = (Cl < -Pm.adj) & (C1 < -Pm.adj);
 	}
-	/* ray at z_i inside the optic; boundary capillaries also test the axis at both nodes */
-	double px = fma(ph.sx, z0, ph.ox), py = fma(ph.sy, z0, ph.oy);
+	/* ray at z_i inside the optic, formed as the literal visit forms it (pc_segment); boundary capillaries also test the axis at
+	 * both nodes */
+	const double t0 = z0 - ph.Pz;
+	double px = fma(ph.sx, t0, ph.Px), py = fma(ph.sy, t0, ph.Py);
 	const bool ray_out = h0 > 0. && pc_outside_hexd(h0, px, py);
 	ok = ok & !ray_out;
 	if (ph.bnd) {

@@ -463,17 +463,19 @@ class MarchRay:
                           self.d[2] * ((self.P[1] << self.Ek) - self.k[1] * zh) + self.d[1] * dzj)
         return self._Q[j]
 
-    def max_g(self, j, z_from=None):
-        """(max of g over segment j from z_from (a rational; None: the segment's first node) to its last node, u of the maximum),
-        None when that range is empty.  g(u) = A u^2 + B u + C on u = (z - z_j)/(z_j+1 - z_j): the ends, and the vertex when
-        A < 0 puts it inside."""
+    def _quad(self, j):
+        """(A, B, C) of G(u) = A u^2 + B u + C on segment j, u = (z - z_j)/(z_j+1 - z_j): G = den g, integers"""
         (ax, ay), (bx, by) = self.Q(j), self.Q(j + 1)
         ex, ey = bx - ax, by - ay
         s = self.d[2] << self.Ek                     # dz R over 2^(E + Ed + Ek) is s R_int
         R0, dR = s * self.R[j], s * (self.R[j + 1] - self.R[j])
-        A = ex * ex + ey * ey - dR * dR
-        B = 2 * (ax * ex + ay * ey - R0 * dR)
-        Cc = ax * ax + ay * ay - R0 * R0
+        return ex * ex + ey * ey - dR * dR, 2 * (ax * ex + ay * ey - R0 * dR), ax * ax + ay * ay - R0 * R0
+
+    def max_g(self, j, z_from=None):
+        """(max of g over segment j from z_from (a rational; None: the segment's first node) to its last node, u of the maximum),
+        None when that range is empty.  g(u) = A u^2 + B u + C on u = (z - z_j)/(z_j+1 - z_j): the ends, and the vertex when
+        A < 0 puts it inside."""
+        A, B, Cc = self._quad(j)
         lo = 0
         if z_from is not None:
             zf = z_from * (1 << self.E)
@@ -492,6 +494,31 @@ class MarchRay:
                 if gv > best:
                     best, at = gv, u
         return Fraction(best) / self.den, Fraction(at)
+
+    def g_at(self, z):
+        """g at the rational z, on the segment that holds it (the last one for z at or beyond the last node, the first below the
+        first): the ray's own g, extended linearly in zh and R where z lies outside the profile"""
+        zf = z * (1 << self.E)
+        n = len(self.z)
+        j = 0
+        while j < n - 2 and self.z[j + 1] <= zf:
+            j += 1
+        A, B, Cc = self._quad(j)
+        u = (zf - self.z[j]) / (self.z[j + 1] - self.z[j])
+        return Fraction((A * u + B) * u + Cc) / self.den
+
+    def g_node(self, j):
+        """g at node j"""
+        ax, ay = self.Q(j)
+        s = (self.d[2] << self.Ek) * self.R[j]
+        return Fraction(ax * ax + ay * ay - s * s, self.den)
+
+
+def mirrored(d, n, cosalfa):
+    """The direction pc_event_post leaves: per component fma(-2 cosalfa, n, d), i.e. the exact d - 2 cosalfa n rounded once
+    (-2 cosalfa is exact in doubles; a Fraction converts to the nearest double)."""
+    c2 = Fraction(-2.0 * float(cosalfa))
+    return [float(fr(d[c]) + c2 * fr(n[c])) for c in range(3)]
 
 
 def march_table_bounds(t):

@@ -1121,3 +1121,314 @@ def hex_rows():
                         rows.append([p[0], p[1], zz])
                         meta.append(dict(cell=(q, r), fam=fam, delta=dl, k=k, purpose=isinstance(delta, str) or delta == 0.0))
     return np.array(rows, dtype=np.float64).reshape(-1, 3), meta
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The flight grids (op FLIGHTS, tests/test_devmath_flights_cpu.py): photons whose flights AFTER a reflection meet the places where
+# a certificate could be wrong.  Deterministic.  A later flight cannot be placed directly -- it starts where the flight before it
+# ended -- so it is aimed by time reversal: the wanted flight is laid out as the _Builder families lay out a first flight, its
+# ray is intersected backwards with the wall in mpmath (FLIGHT_DPS digits), mirrored there, and the earlier flight followed back to
+# z = 0 or to a start inside the capillary; the start and the direction are rounded once.  What a row really does is decided by
+# the exact side of the test from the P and d the probe reports for every flight, never by this file.
+#
+# Families (meta["fam"]):
+#   aimed_end   the wanted flight starts on the wall in segment i and is delta cap from the wall at node i + L - 1, i + L, i + L + 1
+#               (L = PC_L1, PC_L2; delta < 0: it has crossed the wall by |delta| cap there), as flight 1 and as flight 2
+#   aimed_kink  delta cap from the wall at the kink node;  aimed_mid  parallel to the wall of one segment, delta cap from it
+#   fan         from z = 0, off the axis, slopes 1e-3 ... 0.1 at eight azimuths: skew rays, which spiral from wall to wall
+#   node        the first crossing on a node and 1 ulp of z either side of it (ix = i + 1; on the last node i + 1 == nmax)
+#   guard       reflects eps before the node where cap_kink's wall turns inward; the second crossing lies 0.5, 1 - 1e-6, 1 + 1e-6 and 2
+#               times 1e-5 beyond the first (the reference's guard drops the two nearer ones: the photon goes on outside)
+#   guard0      the same four offsets on a first flight started inside the capillary
+#   limit       steep photons on nmax1 and nmax4 that reach irefl > nmax
+#   short       on `tiny` (cap 1e-6), started 3e-4 before a node at slopes 0.02 ... 0.1: flights of 2e-5 to 1e-4, so that flights start
+#               within 1e-5 to 1e-4 of the end of their first segment and cross the wall again inside it
+#   hexedge     boundary capillary of the cylinder, whose axis lies on the outer hexagon: the reflected ray passes through the axis, and
+#               so meets the hexagon, at the last node but one (R / (s dz) a whole number of segments), within rounding: the march's
+#               hexagon test of the ray and the literal visit's must fall on the same side, or one exits where the other ends with rc -1
+FLIGHT_NB = 12
+FLIGHT_K = 128
+FLIGHT_DPS = 60
+FLIGHT_DELTAS = tuple(d for d in MARCH_DELTAS if abs(d) >= 1e-9)
+THIN_CAP = 4.0e-4
+GUARD_OFFSETS = (0.5, 1 - 1e-6, 1 + 1e-6, 2.0)
+
+
+def flight_profiles():
+    """the 16 march profiles plus the thin variants (cap0 about 4e-4: at grazing slopes of 1e-3 to 3e-2 a photon makes 2 to 12
+    flights of 3 to 40 segments within 61 segments); ext_kink (cap0 8e-4) is thin as it is"""
+    P = dict(march_profiles())
+    for name in ("cylinder", "taper", "bulge", "cap_kink", "irregular"):
+        q = dict(P[name])
+        q["cap"] = q["cap"] * (THIN_CAP / M_CAP)
+        q["thin"] = True
+        P[name + "_thin"] = q
+    P["ext_kink"] = dict(P["ext_kink"], thin=True)
+    return P
+
+
+def _rot2(e, deg):
+    c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+    return np.array([c * e[0] - s * e[1], s * e[0] + c * e[1]])
+
+
+class _FlightBuilder(_Builder):
+    """adds to _Builder the wall of one capillary in mpmath: crossings of a ray going backwards, the wall's normal, the mirror"""
+
+    def __init__(self, name, prof):
+        super().__init__(name, prof)
+        from mpmath import mp, mpf
+        self.mp, self.mpf = mp, mpf
+        with mp.workdps(FLIGHT_DPS):
+            self.mz, self.mzh, self.mcap = [mpf(float(v)) for v in self.z], [mpf(float(v)) for v in self.zh], [mpf(float(v)) for v in self.cap]
+
+    def add(self, capname, k, fam, P, d, **meta):
+        self.rows.append([float(P[0]), float(P[1]), float(P[2]), float(d[0]), float(d[1]), float(d[2]), 0.3, 0.5, 0.1, 0.0,
+                          float(FLIGHT_K), float(FLIGHT_NB)])
+        self.meta.append(dict(dict(profile=self.name, cap=capname, k=k, fam=fam, delta=0.0, want=0, tnode=-1, L=0, s=0.0, off=0.0), **meta))
+
+    def centre(self, k, zv):
+        return np.array(k) * self.at(self.zh, zv)
+
+    # --- mpmath: the ray p(z) = p + D (z - zr) against segment j of capillary k
+    def _quad(self, k, j, p, D, zr):
+        z0, dz = self.mz[j], self.mz[j + 1] - self.mz[j]
+        sl = (self.mzh[j + 1] - self.mzh[j]) / dz
+        q0 = [p[c] + D[c] * (z0 - zr) - k[c] * self.mzh[j] for c in (0, 1)]
+        dq = [D[c] - k[c] * sl for c in (0, 1)]
+        R0, rr = self.mcap[j], (self.mcap[j + 1] - self.mcap[j]) / dz
+        return dq[0] ** 2 + dq[1] ** 2 - rr * rr, 2 * (q0[0] * dq[0] + q0[1] * dq[1] - R0 * rr), q0[0] ** 2 + q0[1] ** 2 - R0 * R0, dz
+
+    def back_cross(self, k, p, D, zr, z_from):
+        """the crossing of the ray with the wall next below z_from: (z, segment, g'(z)) or None when there is none down to z = 0"""
+        mp = self.mp
+        j = self.seg_of(float(z_from))
+        if float(z_from) <= float(self.z[j]) and j > 0:
+            j -= 1
+        while j >= 0:
+            a, b, c, dz = self._quad(k, j, p, D, zr)
+            ts = []
+            if a == 0:
+                if b != 0:
+                    ts = [-c / b]
+            else:
+                disc = b * b - 4 * a * c
+                if disc >= 0:
+                    sq = mp.sqrt(disc)
+                    ts = [(-b + sq) / (2 * a), (-b - sq) / (2 * a)]
+            hi = min(dz, z_from - self.mz[j])
+            ts = sorted((t for t in ts if 0 <= t <= dz and t < hi), reverse=True)
+            if ts:
+                return self.mz[j] + ts[0], j, 2 * a * ts[0] + b
+            j -= 1
+        return None
+
+    def g_at(self, k, p, D, zr, zv):
+        j = self.seg_of(float(zv))
+        a, b, c, dz = self._quad(k, j, p, D, zr)
+        t = zv - self.mz[j]
+        return (a * t + b) * t + c
+
+    def mirror(self, k, j, H, D):
+        """xy slope of the ray that, mirrored at the wall point H of segment j, leaves along (D, 1); None when it flies backwards"""
+        mp = self.mp
+        dz = self.mz[j + 1] - self.mz[j]
+        c0 = [k[0] * self.mzh[j], k[1] * self.mzh[j], self.mz[j]]
+        cd = [k[0] * (self.mzh[j + 1] - self.mzh[j]), k[1] * (self.mzh[j + 1] - self.mzh[j]), dz]
+        s3 = sum(v * v for v in cd)
+        tp = sum((H[c] - c0[c]) * cd[c] for c in range(3)) / s3
+        inn = [H[c] - (c0[c] + tp * cd[c]) for c in range(3)]
+        il = mp.sqrt(sum(v * v for v in inn))
+        tg = -(self.mcap[j + 1] - self.mcap[j]) / s3
+        n = [inn[c] / il + tg * cd[c] for c in range(3)]
+        nl = mp.sqrt(sum(v * v for v in n))
+        n = [v / nl for v in n]
+        d = [D[0], D[1], self.mpf(1)]
+        nd = sum(n[c] * d[c] for c in range(3))
+        di = [d[c] - 2 * nd * n[c] for c in range(3)]
+        if not di[2] > 0:
+            return None
+        return [di[0] / di[2], di[1] / di[2]]
+
+    def reversed_row(self, capname, k, fam, B, D, zt, want, crossed, **meta):
+        """The wanted flight passes B (xy) at z = zt with xy slope D.  It is followed backwards to its start on the wall and
+        through `want` mirrors in all (want = 1: it is flight 1), then to z = 0 or to the middle of the earliest flight; a row is
+        dropped when a flight on the way would leave the capillary.  crossed: B lies beyond the wall (delta < 0), the first crossing
+        met backwards is the wanted flight's own end."""
+        mp, mpf = self.mp, self.mpf
+        with mp.workdps(FLIGHT_DPS):
+            km = [mpf(float(k[0])), mpf(float(k[1]))]
+            p, Dm, zr = [mpf(float(B[0])), mpf(float(B[1]))], [mpf(float(D[0])), mpf(float(D[1]))], mpf(float(zt))
+            z_from = zr
+            if crossed:
+                c = self.back_cross(km, p, Dm, zr, z_from)
+                if c is None or not c[2] > 0:
+                    return False
+                z_from = c[0]
+            elif not self.g_at(km, p, Dm, zr, zr) < 0:
+                return False
+            made = 0
+            while True:
+                c = self.back_cross(km, p, Dm, zr, z_from)
+                if c is None:
+                    if made == 0 or not self.g_at(km, p, Dm, zr, mpf(0)) < 0:
+                        return False
+                    zs = mpf(0)
+                    break
+                if not c[2] < 0:          # going forwards the photon would come from outside: the flight before leaves the capillary
+                    return False
+                if made == want:
+                    zs = (c[0] + z_top) / 2
+                    break
+                H = [p[0] + Dm[0] * (c[0] - zr), p[1] + Dm[1] * (c[0] - zr), c[0]]
+                Dn = self.mirror(km, c[1], H, Dm)
+                if Dn is None:
+                    return False
+                p, Dm, zr, z_top = H[:2], Dn, H[2], H[2]
+                z_from = zr - mpf(10) ** -9      # a crossing that close is the mirror point itself
+                made += 1
+            P = [float(p[0] + Dm[0] * (zs - zr)), float(p[1] + Dm[1] * (zs - zr)), float(zs)]
+            d = [float(Dm[0]), float(Dm[1]), 1.0]
+        self.add(capname, k, fam, P, d, want=made, **meta)
+        return True
+
+
+def _flight_rows_of(name, prof):
+    B = _FlightBuilder(name, prof)
+    nmax, z, cap = B.nmax, B.z, B.cap
+    L1, L2 = 5, 25
+    thin = bool(prof.get("thin"))
+    small = nmax < 30
+    count = 0
+    for capname, q, r in march_capillaries(prof["ns"]):
+        k = B.k(q, r)
+        bnd = capname == "boundary"
+        e = B.radial(capname, k)
+        # where on the wall a flight ends (eB) and starts (eA): opposite ends of a diameter; on a boundary capillary, whose outer half
+        # lies outside the optic, the two ends of a chord on its inner half (a skew ray)
+        eB, eA = (_rot2(e, 50.0), _rot2(e, -50.0)) if bnd else (e, -e)
+        inward = e * (0.5 if bnd else 0.0)
+
+        def wall_pt(zv, ev, f=1.0):
+            return B.centre(k, zv) + ev * (B.at(cap, zv) * f)
+
+        # ---- aimed: end, kink, mid
+        if not small and name not in ("tiny", "last_zero"):
+            for L, i_s in ((L1, 22), (L2, 30)):
+                for off in (-1, 0, 1):
+                    t = i_s + L + off
+                    if t > nmax:
+                        continue
+                    zA = 0.5 * (z[i_s] + z[i_s + 1])
+                    for delta in FLIGHT_DELTAS:
+                        Bp = wall_pt(z[t], eB, 1 - delta)
+                        D = (Bp - wall_pt(zA, eA)) / (z[t] - zA)
+                        for want in (1, 2):
+                            B.reversed_row(capname, k, "aimed_end", Bp, D, z[t], want, delta < 0, delta=delta, tnode=t, L=L)
+            if prof["kink"] is not None and not (name == "ext_kink" and capname == "centre"):
+                kn = prof["kink"]
+                for i_s in (kn - 6, kn - 20):
+                    zA = 0.5 * (z[i_s] + z[i_s + 1])
+                    for delta in FLIGHT_DELTAS:
+                        Bp = wall_pt(z[kn], eB, 1 - delta)
+                        D = (Bp - wall_pt(zA, eA)) / (z[kn] - zA)
+                        for want in (1, 2):
+                            B.reversed_row(capname, k, "aimed_kink", Bp, D, z[kn], want, delta < 0, delta=delta, tnode=kn, L=kn - i_s)
+            for js in (40, 48):
+                zt = 0.5 * (z[js] + z[js + 1])
+                w = (cap[js + 1] - cap[js]) / (z[js + 1] - z[js])
+                for delta in FLIGHT_DELTAS:
+                    if delta > 0:
+                        D = B.axis_slope(k, js) + w * eB
+                        for want in (1, 2):
+                            B.reversed_row(capname, k, "aimed_mid", wall_pt(zt, eB, 1 - delta), D, zt, want, False, delta=delta, tnode=js)
+        # ---- fan
+        if name in ("nmax1", "nmax4"):
+            slopes, fam = (0.3, 1.5, 2.5, 4.0), "limit"
+        elif name == "tiny":
+            slopes, fam = (1e-5, 1e-4, 1e-3), "fan"
+        else:
+            slopes, fam = ((1e-3, 3e-3, 1e-2, 3e-2, 0.1) if thin else (2e-2, 5e-2, 0.1)), "fan"
+        P0 = B.centre(k, 0.0) + inward * cap[0] + 0.4 * cap[0] * _rot2(e, 35.0) * (0.5 if bnd else 1.0)
+        for s in slopes:
+            for a in range(8):
+                u = _rot2(e, 45.0 * a + 10.0)
+                D = B.axis_slope(k, 0) + s * u
+                B.add(capname, k, fam, [P0[0], P0[1], 0.0], [D[0], D[1], 1.0], s=s)
+        # ---- node: the first crossing on a node and 1 ulp of z either side of it
+        if name in ("cylinder", "taper", "irregular", "last_zero", "nmax6", "nmax25", "nmax26", "cylinder_thin", "mono"):
+            F = B.F
+            nodes = sorted(set(t for t in (3, nmax - 1, nmax, 33, 40, 47, 54) if 1 <= t <= nmax and cap[t] > 0))
+            for t in nodes:
+                for s in ((3e-3, 1e-2) if thin else (5e-2, 0.1)):
+                    for du in (-1, 0, 1):
+                        zw = float(z[t]) + du * _ulp(z[t])
+                        Rw = F(B.at(cap, z[t]))
+                        back = min(float(zw), 0.6 * float(Rw) / s)
+                        zs = float(zw - back)
+                        ct, cs = B.centre(k, zw), B.centre(k, zs)
+                        W = [F(float(ct[c])) + F(float(eB[c])) * Rw for c in (0, 1)]
+                        Dx = [F(float(eB[c])) * F(s) + F(float((ct[c] - cs[c]) / back)) for c in (0, 1)]
+                        P = [float(W[c] - Dx[c] * (F(zw) - F(zs))) for c in (0, 1)] + [zs]
+                        B.add(capname, k, "node", P, [float(Dx[0]), float(Dx[1]), 1.0], tnode=t, s=s, off=float(du))
+        # ---- short
+        if name == "tiny":
+            for t in (3, 40):
+                zs = float(z[t]) - 3.0e-4
+                Ps = B.centre(k, zs) + inward * B.at(cap, zs) + 0.3 * B.at(cap, zs) * _rot2(e, 35.0) * (0.5 if bnd else 1.0)
+                for s in (0.02, 0.05, 0.1):
+                    for a in range(8):
+                        D = B.axis_slope(k, t - 1) + s * _rot2(e, 45.0 * a + 10.0)
+                        B.add(capname, k, "short", [Ps[0], Ps[1], zs], [D[0], D[1], 1.0], s=s, tnode=t)
+        # ---- hexedge
+        if name == "cylinder" and bnd:
+            F = B.F
+            for nseg, s in ((2, 0.25), (4, 0.125), (5, 0.1), (8, 0.0625), (10, 0.05), (20, 0.025)):
+                t = nmax - 1 - nseg
+                for ang in np.linspace(-80.0, 80.0, 17):
+                    ev = _rot2(e, float(ang))
+                    for du in (-1, 0, 1):
+                        zw = float(z[t]) + du * _ulp(z[t])
+                        Rw = F(float(cap[t]))
+                        zs = zw - 0.6 * float(Rw) / s
+                        ct = B.centre(k, z[t])
+                        W = [F(float(ct[c])) + F(float(ev[c])) * Rw for c in (0, 1)]
+                        Dx = [F(float(ev[c])) * F(s) for c in (0, 1)]
+                        P = [float(W[c] - Dx[c] * (F(zw) - F(zs))) for c in (0, 1)] + [zs]
+                        B.add(capname, k, "hexedge", P, [float(Dx[0]), float(Dx[1]), 1.0], tnode=t, s=s, off=float(du))
+        # ---- guard, guard0 (cap_kink: cylinder up to node kink - 1, where the wall turns inward)
+        if name in ("cap_kink", "cap_kink_thin"):
+            F = B.F
+            kn = prof["kink"]
+            zk = F(float(z[kn - 1]))
+            R = F(float(cap[kn - 1]))
+            w = (R - F(float(cap[kn]))) / (F(float(z[kn])) - zk)          # the wall's inward slope beyond the node
+            ex = [F(float(eB[0])), F(float(eB[1]))]
+            cx = [F(float(v)) for v in B.centre(k, z[kn - 1])]            # zh is constant on cap_kink: the axis is parallel to z
+            for sf in (0.1, 0.3, 0.6):
+                s = F(float(w)) * F(sf)
+                for offv in GUARD_OFFSETS:
+                    # guard: reflected at zr = zk - eps it closes in at slope s; the wall comes in at w from zk on: they meet
+                    # eps w / (w - s) beyond zr
+                    eps = F(offv) * F(1.0e-5) * (w - s) / w
+                    zr = zk - eps
+                    back = R / s / 2
+                    P = [cx[c] + ex[c] * (R - s * back) for c in (0, 1)] + [zr - back]
+                    B.add(capname, k, "guard", P, [float(ex[0] * s), float(ex[1] * s), 1.0], s=float(s), off=offv, tnode=kn - 1)
+                    # guard0: starts inside, s off 1e-5 from the wall, flying outwards at slope s, mid-segment and across a node
+                    for zs in (F(float(0.5 * (z[10] + z[11]))), F(float(z[12])) - F(offv) * F(1.0e-5) / 2):
+                        gap = s * F(offv) * F(1.0e-5)
+                        P = [cx[c] + ex[c] * (R - gap) for c in (0, 1)] + [zs]
+                        B.add(capname, k, "guard0", P, [float(ex[0] * s), float(ex[1] * s), 1.0], s=float(s), off=offv)
+    return np.array(B.rows, dtype=np.float64).reshape(-1, 12), B.meta
+
+
+@functools.lru_cache(maxsize=None)
+def flight_grids():
+    """name -> dict(problem, profile, rows [n, 12] of pyprobe.FLIGHTS_COLS (literal 0, K = FLIGHT_K, NB = FLIGHT_NB), meta [n])"""
+    out = {}
+    for name, prof in flight_profiles().items():
+        rows, meta = _flight_rows_of(name, prof)
+        out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof, rows=rows,
+                         meta=meta)
+    return out

@@ -4,7 +4,8 @@
  * One kernel per primitive or Fresnel form (pc_probe_eval<OP>, tests/devmath/probe_ops.h); the per-energy constants come from
  * the product's own setup (pc_build_tables, pc_problem.h) of the problem passed in.  Op MARCH (tests/test_gpu_devmath_march.py) runs
  * one photon per thread through pc_launch_init, pc_march_step and pc_event_pre on the problem's whole profile, tables in global
- * memory.  Ops WALL, OUTER and HEX (tests/test_gpu_devmath_leak.py) run the wall search of pc_leak.h the same way.  Built by tests/devmath/pyprobe.py with the library's flags (polycap_amd._build.HIPFLAGS) into
+ * memory.  Ops WALL, OUTER and HEX (tests/test_gpu_devmath_leak.py) run the wall search of pc_leak.h the same way; op FLIGHTS
+ * (tests/test_gpu_devmath_flights.py) is op MARCH carried on through the reflections (pc_event_post).  Built by tests/devmath/pyprobe.py with the library's flags (polycap_amd._build.HIPFLAGS) into
  * tests/devmath/libpc_probe.so; never part of libpolycap.
  */
 #include <hip/hip_runtime.h>
@@ -89,6 +90,20 @@ __global__ void __launch_bounds__(64) pc_probe_march_kernel(int64_t n, pc_params
 	code[i] = cd;
 }
 
+/* one thread per photon of a FLIGHTS call; the profile tables lie in global memory */
+__global__ void __launch_bounds__(64) pc_probe_flights_kernel(int64_t n, pc_params pm, int nodes, const double *__restrict__ tab,
+                                                              const pc_marg4 *__restrict__ mg, const double *__restrict__ in,
+                                                              double *__restrict__ out, int32_t *__restrict__ code)
+{
+	const int64_t i = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	pc_tables T;
+	pc_probe_march_tables(T, tab, mg, nodes);
+	int cd = 0;
+	pc_probe_flights_eval(T, pm, in + i*PC_PROBE_FLIGHTS_IN, out + i*PC_PROBE_FLIGHTS_OUT, &cd);
+	code[i] = cd;
+}
+
 /* one thread per row of a leak op (WALL, OUTER, HEX); the profile tables lie in global memory */
 template <int OP>
 __global__ void __launch_bounds__(64) pc_probe_leak_kernel(int64_t n, pc_params pm, int nodes, const double *__restrict__ tab,
@@ -156,6 +171,54 @@ int run_leak(const pc_hip_problem *p, int op, int64_t n, const double *in, int i
 	if (s != hipSuccess) rc = -3;
 	const hipError_t f[6] = {hipFree(d_code), hipFree(d_in), hipFree(d_out), hipFree(d_tab), hipFree(d_mg), hipFree(d_dr)};
 	for (int j = 0; j < 6 && rc == 0; j++)
+		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
+#undef PC_PROBE_TRY
+	return rc;
+}
+
+/* op MARCH, or op FLIGHTS, on n photons through the whole profile of p: what their two entry points share */
+int run_march(const pc_hip_problem *p, bool flights, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code,
+              char *err)
+{
+	err[0] = 0;
+	pc_host_tables t;
+	std::string msg;
+	if (pc_build_tables(p, t, msg)) { snprintf(err, 256, "%s", msg.c_str()); return -2; }
+	if (flights ? pc_probe_flights_check(p, n, in_w, out_w, in) : pc_probe_march_check(p, n, in_w, out_w, in)) { snprintf(err, 256, "invalid size, width, profile, literal flag, K or NB"); return -2; }
+	if (n == 0) return 0;
+	const size_t nodes = (size_t)p->nmax + 1;
+	std::vector<double> tab;
+	tab.reserve(PC_PROBE_MARCH_TAB*nodes);
+	const std::vector<double> *cols[PC_PROBE_MARCH_TAB] = {&t.z, &t.cap, &t.zh, &t.cap2, &t.hexd, &t.idz, &t.ext};
+	for (int c = 0; c < PC_PROBE_MARCH_TAB; c++) tab.insert(tab.end(), cols[c]->begin(), cols[c]->end());
+	int32_t *d_code = nullptr;
+	double *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
+	pc_marg4 *d_mg = nullptr;
+	int rc = 0;
+	hipError_t s = hipSuccess;
+#define PC_PROBE_TRY(call) do { if (s == hipSuccess) { s = (call); if (s != hipSuccess) snprintf(err, 256, "%s: %s", #call, hipGetErrorString(s)); } } while (0)
+	PC_PROBE_TRY(hipMalloc(&d_code, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_in, n*in_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_out, n*out_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_tab, tab.size()*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_mg, nodes*sizeof(pc_marg4)));
+	PC_PROBE_TRY(hipMemset(d_code, 0, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMemset(d_out, 0, n*out_w*sizeof(double)));
+	PC_PROBE_TRY(hipMemcpy(d_in, in, n*in_w*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_mg, t.mg.data(), nodes*sizeof(pc_marg4), hipMemcpyHostToDevice));
+	if (s == hipSuccess) {
+		const unsigned blocks = (unsigned)((n + 63)/64);
+		if (flights) hipLaunchKernelGGL(pc_probe_flights_kernel, dim3(blocks), dim3(64), 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		else hipLaunchKernelGGL(pc_probe_march_kernel, dim3(blocks), dim3(64), 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		PC_PROBE_TRY(hipGetLastError());
+	}
+	PC_PROBE_TRY(hipDeviceSynchronize());
+	PC_PROBE_TRY(hipMemcpy(out, d_out, n*out_w*sizeof(double), hipMemcpyDeviceToHost));
+	PC_PROBE_TRY(hipMemcpy(code, d_code, n*sizeof(int32_t), hipMemcpyDeviceToHost));
+	if (s != hipSuccess) rc = -3;
+	const hipError_t f[5] = {hipFree(d_code), hipFree(d_in), hipFree(d_out), hipFree(d_tab), hipFree(d_mg)};
+	for (int j = 0; j < 5 && rc == 0; j++)
 		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
 #undef PC_PROBE_TRY
 	return rc;
@@ -269,47 +332,16 @@ __attribute__((visibility("default")))
 int probe_run_march(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code,
                     char *err)
 {
-	err[0] = 0;
-	pc_host_tables t;
-	std::string msg;
-	if (pc_build_tables(p, t, msg)) { snprintf(err, 256, "%s", msg.c_str()); return -2; }
-	if (pc_probe_march_check(p, n, in_w, out_w, in)) { snprintf(err, 256, "invalid size, width, profile, literal flag or K"); return -2; }
-	if (n == 0) return 0;
-	const size_t nodes = (size_t)p->nmax + 1;
-	std::vector<double> tab;
-	tab.reserve(PC_PROBE_MARCH_TAB*nodes);
-	const std::vector<double> *cols[PC_PROBE_MARCH_TAB] = {&t.z, &t.cap, &t.zh, &t.cap2, &t.hexd, &t.idz, &t.ext};
-	for (int c = 0; c < PC_PROBE_MARCH_TAB; c++) tab.insert(tab.end(), cols[c]->begin(), cols[c]->end());
-	int32_t *d_code = nullptr;
-	double *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
-	pc_marg4 *d_mg = nullptr;
-	int rc = 0;
-	hipError_t s = hipSuccess;
-#define PC_PROBE_TRY(call) do { if (s == hipSuccess) { s = (call); if (s != hipSuccess) snprintf(err, 256, "%s: %s", #call, hipGetErrorString(s)); } } while (0)
-	PC_PROBE_TRY(hipMalloc(&d_code, n*sizeof(int32_t)));
-	PC_PROBE_TRY(hipMalloc(&d_in, n*in_w*sizeof(double)));
-	PC_PROBE_TRY(hipMalloc(&d_out, n*out_w*sizeof(double)));
-	PC_PROBE_TRY(hipMalloc(&d_tab, tab.size()*sizeof(double)));
-	PC_PROBE_TRY(hipMalloc(&d_mg, nodes*sizeof(pc_marg4)));
-	PC_PROBE_TRY(hipMemset(d_code, 0, n*sizeof(int32_t)));
-	PC_PROBE_TRY(hipMemset(d_out, 0, n*out_w*sizeof(double)));
-	PC_PROBE_TRY(hipMemcpy(d_in, in, n*in_w*sizeof(double), hipMemcpyHostToDevice));
-	PC_PROBE_TRY(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
-	PC_PROBE_TRY(hipMemcpy(d_mg, t.mg.data(), nodes*sizeof(pc_marg4), hipMemcpyHostToDevice));
-	if (s == hipSuccess) {
-		const unsigned blocks = (unsigned)((n + 63)/64);
-		hipLaunchKernelGGL(pc_probe_march_kernel, dim3(blocks), dim3(64), 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
-		PC_PROBE_TRY(hipGetLastError());
-	}
-	PC_PROBE_TRY(hipDeviceSynchronize());
-	PC_PROBE_TRY(hipMemcpy(out, d_out, n*out_w*sizeof(double), hipMemcpyDeviceToHost));
-	PC_PROBE_TRY(hipMemcpy(code, d_code, n*sizeof(int32_t), hipMemcpyDeviceToHost));
-	if (s != hipSuccess) rc = -3;
-	const hipError_t f[5] = {hipFree(d_code), hipFree(d_in), hipFree(d_out), hipFree(d_tab), hipFree(d_mg)};
-	for (int j = 0; j < 5 && rc == 0; j++)
-		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
-#undef PC_PROBE_TRY
-	return rc;
+	return run_march(p, false, n, in, in_w, out, out_w, code, err);
+}
+
+/* Op FLIGHTS on n photons through the whole profile of p, flight after flight: in[n][PC_PROBE_FLIGHTS_IN],
+ * out[n][PC_PROBE_FLIGHTS_OUT], code[n].  Same return values as probe_run. */
+__attribute__((visibility("default")))
+int probe_run_flights(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code,
+                      char *err)
+{
+	return run_march(p, true, n, in, in_w, out, out_w, code, err);
 }
 
 /* Op WALL on n photons in the glass of p's whole profile: in[n][PC_PROBE_WALL_IN], out[n][PC_PROBE_WALL_OUT], code[n].  A row with

@@ -14,6 +14,9 @@
  *
  * The leak ops (PC_PROBE_WALL, PC_PROBE_OUTER, PC_PROBE_HEX) call the wall search of pc_leak.h -- pc_wall_begin, pc_wall_step,
  * pc_wall_probe as pc_leak_launch sequences them; pc_outer_intersect; pc_hex_index -- on the whole profile; see pc_probe_wall_eval.
+ *
+ * Op FLIGHTS (PC_PROBE_FLIGHTS) is op MARCH carried on through the reflections: after a hit pc_event_post mirrors the direction and
+ * the next flight is marched, up to NB flights; see pc_probe_flights_eval.
  */
 #ifndef PC_PROBE_OPS_H
 #define PC_PROBE_OPS_H
@@ -118,10 +121,10 @@ enum { PC_PROBE_SEGMENT = 13, PC_PROBE_GEOM = 14, PC_PROBE_BOUNCE = 15, PC_PROBE
 #define PC_PROBE_SETUP_REJECT (-100)
 
 static inline int pc_probe_is_geom(int op) { return op >= PC_PROBE_SEGMENT && op < PC_PROBE_GEOM_END; }
-/* row widths per op (PC_PROBE_MARCH = 16, PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19 and their widths are defined
- * with the ops, further down) */
-static inline int pc_probe_in_width(int op) { return (op == 17) ? 9 : (op == 18) ? 7 : (op == 19) ? 3 : (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
-static inline int pc_probe_out_width(int op) { return (op == 17) ? 20 + 17*96 : (op == 18) ? 4 : (op == 19) ? 2 : (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
+/* row widths per op (PC_PROBE_MARCH = 16, PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19, PC_PROBE_FLIGHTS = 20 and their
+ * widths are defined with the ops, further down) */
+static inline int pc_probe_in_width(int op) { return (op == 20) ? 12 : (op == 17) ? 9 : (op == 18) ? 7 : (op == 19) ? 3 : (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
+static inline int pc_probe_out_width(int op) { return (op == 20) ? 22 + 24*12 + 5*128 : (op == 17) ? 20 + 17*96 : (op == 18) ? 4 : (op == 19) ? 2 : (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
 
 /* the product's setup (pc_build_tables) of the two-node profile (z0, z1), (cap0, cap1) of a SEGMENT row, glass and energies
  * of p; returns 0, or -1 when the setup rejects the profile */
@@ -457,6 +460,126 @@ static inline int pc_probe_leak_check(const pc_hip_problem *p, int op, long long
 		} else {
 			if (!(r[2] > 0.)) return -2;
 		}
+	}
+	return 0;
+}
+
+/* ------------------------------------------------------------------ op FLIGHTS
+ * Op MARCH carried on through the reflections: one photon per row through the WHOLE profile, flight after flight, tables and
+ * parameters as pc_build_tables makes them.  Product code only, in the order the kernels call it: pc_launch_init; then passes of
+ * pc_march_step and, when that returns EVENT, pc_event_pre; on REFLECT pc_event_post(Pm, ph, h, 1) -- the geometric reflection -- and
+ * the loop goes on with the next flight.  No energy enters and pc_reflect is not called: it writes the weights, wset and the
+ * electric vector (its component-wise absolute value) and nothing else of the photon -- neither P, d, the ray nor i, first, lv,
+ * C0, irefl -- so the chain of flights is the one a kept reflection (r = 1) leaves at every energy.  Numbered after HEX; rows of
+ * its own widths and an entry point of its own (probe_run_flights / emul_probe_run_flights).
+ *   in[12]   = x, y, z, dx, dy, dz, ex, ey, ez, literal (0 / 1), K (passes, 0 .. PC_PROBE_FLIGHTS_K), NB (flights, 1 .. PC_PROBE_FLIGHTS_NB)
+ *   out[950] = entrance [0..9]: as op MARCH
+ *              chain    [10..21]: how it ended (PC_PROBE_CHAIN_*), rc, irefl, flights begun, trail entries, i, P, d at the end
+ *              flight f [22 + 24 f ..]: at its start, as pc_trace_begin left the photon: irefl, i, lv, bnd, first, P[3], d[3];
+ *                                 at its end: how (PC_PROBE_END_*), i, normal[3] and cosalfa (on a hit, else 0), ix (on a hit),
+ *                                 P[3] (the hit point on a hit), C0; two spare columns (0)
+ *              trail    [310 + 5 t ..]: flight, i before, i after, kind (PC_PROBE_STEP_*), creep -- one entry per pass, as op MARCH
+ * code = ph.rc at the end. */
+enum { PC_PROBE_FLIGHTS = 20 };
+#define PC_PROBE_FLIGHTS_IN 12
+#define PC_PROBE_FLIGHTS_K 128
+#define PC_PROBE_FLIGHTS_NB 12
+#define PC_PROBE_FLIGHTS_HEAD 22
+#define PC_PROBE_FLIGHTS_FL 24
+#define PC_PROBE_FLIGHTS_ENTRY 5
+#define PC_PROBE_FLIGHTS_TRAIL (PC_PROBE_FLIGHTS_HEAD + PC_PROBE_FLIGHTS_FL*PC_PROBE_FLIGHTS_NB)
+#define PC_PROBE_FLIGHTS_OUT (PC_PROBE_FLIGHTS_TRAIL + PC_PROBE_FLIGHTS_ENTRY*PC_PROBE_FLIGHTS_K)
+enum {
+	PC_PROBE_CHAIN_EXIT = 0,      /* the end of the profile (rc 1), from pc_march_step or the creep loop of pc_event_pre */
+	PC_PROBE_CHAIN_EVENT = 1,     /* pc_event_pre ended the photon (rc -1) */
+	PC_PROBE_CHAIN_LIMIT = 2,     /* irefl > nmax in pc_event_post (rc 1) */
+	PC_PROBE_CHAIN_FLIGHTS = 3,   /* NB flights marched, each ended in a hit; the photon stands at the start of the next */
+	PC_PROBE_CHAIN_PASSES = 4,    /* K passes made, still marching */
+	PC_PROBE_CHAIN_ENTRANCE = 5   /* pc_launch_init did not let it in (rc 2 / -2) */
+};
+
+PC_HD void pc_probe_flights_eval(const pc_tables &T, const pc_params &Pm0, const double *in, double *out, int *code)
+{
+	for (int j = 0; j < PC_PROBE_FLIGHTS_OUT; j++) out[j] = 0.;
+	pc_params Pm = Pm0;
+	Pm.literal = (in[9] != 0.) ? 1 : 0;
+	int K = (int)in[10], NB = (int)in[11];
+	if (K < 0) K = 0;
+	if (K > PC_PROBE_FLIGHTS_K) K = PC_PROBE_FLIGHTS_K;
+	if (NB < 1) NB = 1;
+	if (NB > PC_PROBE_FLIGHTS_NB) NB = PC_PROBE_FLIGHTS_NB;
+	pc_photon<1> ph;
+	const double zero[6] = {0., 0., 0., 0., 0., 0.};
+	pc_probe_photon(ph, zero);
+	int st = pc_launch_init(T, Pm, ph, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8]);
+	out[0] = st; out[1] = ph.rc; out[2] = ph.qr; out[3] = ph.kx; out[4] = ph.ky; out[5] = ph.bnd; out[6] = ph.i;
+	out[7] = ph.dx; out[8] = ph.dy; out[9] = ph.dz;
+	int how = (st == PC_ST_MARCH) ? -1 : PC_PROBE_CHAIN_ENTRANCE, nt = 0, nf = 0;
+	pc_hit h;
+	h.nx = h.ny = h.nz = h.cosalfa = 0.; h.ix = 0;
+	double *fl = nullptr;             /* the flight being marched */
+	while (how < 0) {
+		if (!fl) {
+			if (nf == NB) { how = PC_PROBE_CHAIN_FLIGHTS; break; }
+			fl = out + PC_PROBE_FLIGHTS_HEAD + PC_PROBE_FLIGHTS_FL*nf;
+			fl[0] = ph.irefl; fl[1] = ph.i; fl[2] = ph.lv; fl[3] = ph.bnd; fl[4] = ph.first;
+			fl[5] = ph.Px; fl[6] = ph.Py; fl[7] = ph.Pz; fl[8] = ph.dx; fl[9] = ph.dy; fl[10] = ph.dz;
+			nf++;
+		}
+		int end = -1;                 /* how this flight ended, once it has */
+		if (nt == K) { how = PC_PROBE_CHAIN_PASSES; end = PC_PROBE_END_STEPS; }
+		else {
+			const int i0 = ph.i, first = ph.first;
+			st = pc_march_step(T, Pm, ph);
+			if (st == PC_ST_DONE) { how = PC_PROBE_CHAIN_EXIT; end = PC_PROBE_END_EXIT; }
+			else {
+				int kind, creep = 0;
+				if (st == PC_ST_MARCH) {
+					const int adv = ph.i - i0;
+					kind = first ? PC_PROBE_STEP_FIRST : (adv == 0) ? PC_PROBE_STEP_LOWER : (adv == 1) ? PC_PROBE_STEP_SINGLE
+					     : (adv == PC_L1) ? PC_PROBE_STEP_L1 : PC_PROBE_STEP_L2;
+				} else {
+					const int crept = (ph.lv == 3);
+					st = pc_event_pre(T, Pm, ph, h);
+					if (st == PC_ST_MARCH) { kind = PC_PROBE_STEP_MISS; creep = ph.i - 1 - i0; }
+					else {
+						kind = (st == PC_ST_REFLECT) ? PC_PROBE_STEP_HIT : PC_PROBE_STEP_DONE;
+						end = (st == PC_ST_REFLECT) ? PC_PROBE_END_REFLECT : (ph.rc == 1) ? PC_PROBE_END_EXIT : PC_PROBE_END_EVENT;
+						if (st != PC_ST_REFLECT) how = (ph.rc == 1) ? PC_PROBE_CHAIN_EXIT : PC_PROBE_CHAIN_EVENT;
+						creep = ph.i - i0;
+					}
+					if (!crept) creep = 0;
+				}
+				double *tr = out + PC_PROBE_FLIGHTS_TRAIL + PC_PROBE_FLIGHTS_ENTRY*nt;
+				tr[0] = nf - 1; tr[1] = i0; tr[2] = ph.i; tr[3] = kind; tr[4] = creep;
+				nt++;
+			}
+		}
+		if (end < 0) continue;
+		fl[11] = end; fl[12] = ph.i;
+		if (end == PC_PROBE_END_REFLECT) { fl[13] = h.nx; fl[14] = h.ny; fl[15] = h.nz; fl[16] = h.cosalfa; fl[17] = h.ix; }
+		fl[18] = ph.Px; fl[19] = ph.Py; fl[20] = ph.Pz; fl[21] = ph.C0;
+		fl = nullptr;
+		if (end == PC_PROBE_END_REFLECT && pc_event_post(Pm, ph, h, 1) == PC_ST_DONE) how = PC_PROBE_CHAIN_LIMIT;
+	}
+	out[10] = how; out[11] = ph.rc; out[12] = ph.irefl; out[13] = nf; out[14] = nt; out[15] = ph.i;
+	out[16] = ph.Px; out[17] = ph.Py; out[18] = ph.Pz; out[19] = ph.dx; out[20] = ph.dy; out[21] = ph.dz;
+	code[0] = ph.rc;
+}
+
+/* host-side checks of a FLIGHTS call: widths, profile size, every value finite, the literal flag, K and NB of every row */
+static_assert(PC_PROBE_FLIGHTS == 20 && PC_PROBE_FLIGHTS_IN == 12 && PC_PROBE_FLIGHTS_OUT == 22 + 24*12 + 5*128, "widths of op FLIGHTS as pc_probe_in_width / pc_probe_out_width state them");
+static inline int pc_probe_flights_check(const pc_hip_problem *p, long long n, int in_w, int out_w, const double *in)
+{
+	if (n < 0 || in_w != pc_probe_in_width(PC_PROBE_FLIGHTS) || out_w != pc_probe_out_width(PC_PROBE_FLIGHTS)) return -2;
+	if (p->nmax < 1 || p->nmax + 1 > PC_PROBE_MARCH_NODES) return -2;
+	for (long long i = 0; i < n; i++) {
+		const double *r = in + i*in_w;
+		for (int j = 0; j < in_w; j++)
+			if (!std::isfinite(r[j])) return -2;
+		if (!(r[9] == 0. || r[9] == 1.)) return -2;
+		if (!(r[10] >= 0. && r[10] <= PC_PROBE_FLIGHTS_K) || r[10] != (double)(int)r[10]) return -2;
+		if (!(r[11] >= 1. && r[11] <= PC_PROBE_FLIGHTS_NB) || r[11] != (double)(int)r[11]) return -2;
 	}
 	return 0;
 }

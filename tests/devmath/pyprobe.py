@@ -1,7 +1,8 @@
 """TEST-ONLY: the arithmetic of pc_device.h element by element, on the device (probe.hip) or in the host compile of the same header
 (tests/emul/pc_emul.cpp, IEEE sqrt, division and exp).  Both take the per-energy constants from the product's own setup
 (pc_build_tables) of the Problem passed in.  Op MARCH (run_march) walks photons through the certified march of the Problem's whole
-profile; ops WALL, OUTER and HEX (run_wall, run_outer, run_hex) call the wall search of pc_leak.h on it."""
+profile; op FLIGHTS (run_flights) carries that march on through the reflections; ops WALL, OUTER and HEX (run_wall, run_outer,
+run_hex) call the wall search of pc_leak.h on the profile."""
 import ctypes as C
 import os
 import subprocess
@@ -66,7 +67,7 @@ def lib():
         L.probe_run_march.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
                                       C.POINTER(C.c_int32), C.c_char_p]
         L.probe_run_march.restype = C.c_int
-        for f in (L.probe_run_wall, L.probe_run_outer, L.probe_run_hex):
+        for f in (L.probe_run_wall, L.probe_run_outer, L.probe_run_hex, L.probe_run_flights):
             f.argtypes = L.probe_run_march.argtypes
             f.restype = C.c_int
         _LIB = L
@@ -176,6 +177,38 @@ def march_trail(row):
     """trail of one MARCH output row: list of (i before, i after, kind, creep) as ints"""
     nt = int(row[MARCH_HEAD_COLS.index("n_trail")])
     return [tuple(int(v) for v in row[MARCH_HEAD + 4 * t: MARCH_HEAD + 4 * t + 4]) for t in range(nt)]
+
+
+# op FLIGHTS (probe_ops.h): op MARCH carried on through the reflections, up to FLIGHTS_NB flights per row
+FLIGHTS_OP = 20
+FLIGHTS_IN, FLIGHTS_K, FLIGHTS_NB, FLIGHTS_HEAD, FLIGHTS_FL, FLIGHTS_ENTRY = 12, 128, 12, 22, 24, 5
+FLIGHTS_TRAIL = FLIGHTS_HEAD + FLIGHTS_FL * FLIGHTS_NB
+FLIGHTS_OUT = FLIGHTS_TRAIL + FLIGHTS_ENTRY * FLIGHTS_K
+FLIGHTS_COLS = MARCH_COLS + ("NB",)
+FLIGHTS_HEAD_COLS = MARCH_HEAD_COLS[:10] + ("how", "rc", "irefl", "n_flights", "n_trail", "i", "Px", "Py", "Pz", "ex_dx", "ex_dy", "ex_dz")
+FLIGHT_COLS = ("irefl", "i", "lv", "bnd", "first", "Px", "Py", "Pz", "dx", "dy", "dz",
+               "end", "i_end", "nx", "ny", "nz", "cosalfa", "ix", "hx", "hy", "hz", "C0", "spare0", "spare1")
+CHAIN_EXIT, CHAIN_EVENT, CHAIN_LIMIT, CHAIN_FLIGHTS, CHAIN_PASSES, CHAIN_ENTRANCE = range(6)
+CHAIN_NAMES = ("exit", "event", "limit", "flights", "passes", "entrance")
+LV_LATER = 2
+
+
+def run_flights(problem, x, device=True):
+    """Op FLIGHTS on the rows x [n, FLIGHTS_IN] (FLIGHTS_COLS): (out [n, FLIGHTS_OUT], code [n]); out[:, :FLIGHTS_HEAD] are
+    FLIGHTS_HEAD_COLS, then FLIGHTS_NB flights of FLIGHT_COLS, then FLIGHTS_K trail entries of (flight, i before, i after, kind, creep)."""
+    return _run_leak(problem, "flights", x, FLIGHTS_IN, FLIGHTS_OUT, device)
+
+
+def flights_of(row):
+    """the flights of one FLIGHTS output row: list of dicts of FLIGHT_COLS"""
+    nf = int(row[FLIGHTS_HEAD_COLS.index("n_flights")])
+    return [dict(zip(FLIGHT_COLS, row[FLIGHTS_HEAD + FLIGHTS_FL * f: FLIGHTS_HEAD + FLIGHTS_FL * (f + 1)])) for f in range(nf)]
+
+
+def flights_trail(row):
+    """trail of one FLIGHTS output row: list of (flight, i before, i after, kind, creep) as ints"""
+    nt = int(row[FLIGHTS_HEAD_COLS.index("n_trail")])
+    return [tuple(int(v) for v in row[FLIGHTS_TRAIL + 5 * t: FLIGHTS_TRAIL + 5 * t + 5]) for t in range(nt)]
 
 
 # the leak ops (probe_ops.h): the wall search of pc_leak.h on the problem's whole profile

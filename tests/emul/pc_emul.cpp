@@ -374,6 +374,21 @@ int emul_probe_run_march(const pc_hip_problem *p, int64_t n, const double *in, i
 	return 0;
 }
 
+/* the host build of probe.hip's probe_run_flights: op MARCH carried on through the reflections */
+int emul_probe_run_flights(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_flights_check(p, n, in_w, out_w, in)) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		int cd = 0;
+		pc_probe_flights_eval(E.T, E.t.pm, in + i*in_w, out + i*out_w, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
 /* Test-only accessor: the certificate tables pc_build_tables makes of p, as doubles (every float converts exactly).
  * node[(nmax + 1) x 16] = z, cap, ext, zh, cap2, hexd, idz, mb1, md1, mb2, md2 (the float tables), then what pc_march_ok reads
  * from the packed pc_marg4: mb of stride PC_L1 and of PC_L2 decoded, md1, md2, r2.
