@@ -123,6 +123,8 @@ POLYCAP_EXTERN void pc_hip_ctx_destroy(pc_hip_ctx *ctx);
  *   "fetch_threads"    host threads of the staging fallback of the image fetch (0 = min(16, cores))
  *   "relay_acc_lds"    relays into this context (pc_hip_relay_run): 1 (default) = the finish kernel gathers a workgroup's exact sums in
  *                      LDS when they fit in 32 KB, 0 = it adds every wave's sums to the global pairs at once, as it does beyond
+ *   "gather_tile", "gather_chunk_rows"   pc_hip_select_gather: entries per compaction tile (a multiple of 64 in 64 .. 65536) and rows
+ *                      per staging chunk; 0 (default) = automatic for both (see the gathers below)
  *   leak runs: "leak_max_depth" (stack frames per lane = walls one photon may cross), "leak_stack_mb" (HBM for those
  *                      stacks), "leak_capacity" (leak record buffer, 0 = automatic; a run that outgrows it is repeated). */
 POLYCAP_EXTERN int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value);
@@ -541,6 +543,36 @@ POLYCAP_EXTERN int pc_hip_joint_add_selected(pc_hip_joint *joint, int kind, pc_h
  * "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not", into cuts [8] and *n_cuts, checked with pc_hip_select_validate.
  * PC_HIP_ERR_INVALID with the reason (it names the item) in why [why_len] otherwise. */
 POLYCAP_EXTERN int pc_hip_select_parse(const char *value, pc_hip_select_cut *cuts, int32_t *n_cuts, char *why, size_t why_len);
+/* ---- gathers: the per-entry data of the entries a selection keeps, compacted in order on the device (pc_gather.h) and copied to the
+ * host without the rest of the run: the halo photons outside a radius, the photons of many reflections, what a pinhole accepts as the
+ * input of a downstream code, the leak events of one z range.
+ *
+ * The contract:
+ *   numbering  the passing entries of a kind are numbered 0 .. n_pass - 1 in the order of their positions in what pc_hip_select_apply
+ *              read.  Kind 0: the positions of the image store -- slot order by default, the order of completion for compact stores,
+ *              the records of a relay into the context; kinds 1 and 2: the ordered leak event lists.  For a group the members'
+ *              entries come one after the other in member order, and a position is the global one: the member's local position plus
+ *              the entry counts of the members before it, the numbering of pc_hip_group_images and pc_hip_group_leak_events
+ *   result     the passing entries numbered [first, first + count) are copied to the host
+ *   records    kind 0: [count][PC_HIP_N_PLANES + n_energies], row k bit for bit the row pc_hip_transmission_records returns for that
+ *              position, the reflection count as int64 bits; where _records is not available ("plane_images", compact stores) the
+ *              same row is assembled from the planes.  Kinds 1 and 2: [count][PC_HIP_LEAK_HDR + n_energies], the rows of
+ *              pc_hip_leak_events for those events.  Rows are copied as 64-bit patterns, never through a floating-point operation
+ *   positions  optional: [count] positions as defined above, strictly increasing
+ *   count 0    valid, touches nothing; records and positions may then be NULL
+ *   refusals   PC_HIP_ERR_INVALID with a message that names the function and the field, nothing launched, the selection and what it
+ *              has cached unchanged: select NULL; kind outside 0 .. 2; first < 0; count < 0; records NULL with count > 0; the
+ *              selection was not applied for that kind; the mask is stale (the rule and the wording of the gated adds); first + count
+ *              greater than n_pass of that kind
+ *   blocking   the call returns when the data are in the caller's memory; on every member's stream it is ordered behind the apply
+ * The list of the passing positions (uint32 [n_pass] per member and kind; a kind takes at most 2^32 - 1 entries) is built by the first
+ * gather after an apply and kept until that kind is applied again; a compaction that finds another count than the apply is
+ * PC_HIP_ERR_RUNTIME.  Two options of pc_hip_set_option / pc_hip_group_set_option, neither of which changes a result:
+ *   "gather_tile"       entries per tile of the compaction: a multiple of 64 in 64 .. 65536, 0 (default) = automatic (4096)
+ *   "gather_chunk_rows" rows per chunk of the device staging buffer, each chunk one copy to the host: 0 (default) = as many rows as
+ *                       fit in 128 MiB, at least 1
+ * Both exist so that tests reach many tiles and many chunks at small sizes. */
+POLYCAP_EXTERN int pc_hip_select_gather(pc_hip_select *select, int kind, int64_t first, int64_t count, double *records, int64_t *positions);
 /* ---- standard errors of the tallies: a second exact sum per cell, of the squared weights, kept in the same pass as the first, so
  * that every bin of a spot map, a histogram or a joint histogram and the transmission of a selection carry their Monte Carlo error.
  *
@@ -793,6 +825,21 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_joint(void *efficiencies, in
  * seeds pool exactly.  A result made without POLYCAP_SELECT fails with POLYCAP_ERROR_INVALID_ARGUMENT. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies,
 	int64_t n_pass[3], int64_t n_seen[3], uint64_t **passed_w, uint64_t **rejected_w, void *error);
+
+/* The selected photons themselves: POLYCAP_SELECT_RECORDS=N (an integer 1 .. 2^31 - 1; anything else, or the variable without
+ * POLYCAP_SELECT, is POLYCAP_ERROR_INVALID_ARGUMENT before any device is used) makes the result carry, for every kind the call applies
+ * the selection to (exit photons always, extleak and intleak for leak_calc runs), the first N passing entries in order as rows of
+ * pc_hip_select_gather: only those rows leave the device, on every path POLYCAP_SELECT serves.  N bounds the host memory; n_pass stays
+ * available from _get_select.  Order and position are those of the concatenation of everything the call's applies saw: the chunks of a
+ * POLYCAP_IMAGES=0 run in slot-range order, the members of a device group in member order; a row's position is the entries seen by
+ * the earlier applies plus its position inside its apply.  For a call that keeps its images these are the positions of the result's
+ * own exit arrays.  Returns 1 and (free each array with polycap_free; records and positions may be NULL): *n_rows = min(N, n_pass),
+ * *row_doubles (PC_HIP_N_PLANES + n_energies for kind 0 with the reflection count as int64 bits, PC_HIP_LEAK_HDR + n_energies for the
+ * leak kinds), *records [n_rows][row_doubles], *positions [n_rows].  A result made without the variable, or a kind the call did not
+ * apply, fails with POLYCAP_ERROR_INVALID_ARGUMENT.  write_hdf5 adds /Select/<Kind>_Records (double [n_rows][row_doubles]) and
+ * /Select/<Kind>_Positions (int64 [n_rows]) per kind present, and /Select/Records_Limit. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_select_records(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles,
+	double **records, int64_t **positions, void *error);
 
 /* Standard errors of the tallies through the public call: POLYCAP_TALLY_STDERR=1 (0 or unset: none; anything else is
  * POLYCAP_ERROR_INVALID_ARGUMENT; it is not POLYCAP_STDERR, whose outputs stay as they are) makes every tally of the call (POLYCAP_SPOT,

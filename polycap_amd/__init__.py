@@ -6,6 +6,7 @@ The package is a thin Python layer over libpolycap.so (host C + hand-written HIP
   * polycap_amd.hip.SpotMap       -- spot maps: 2-D histograms of the photons of a run on planes behind the optic, on the GPU;
   * polycap_amd.hip.Histograms    -- exact 1-D histograms of per-photon quantities per energy (FWHM, encircled energy), on the GPU;
   * polycap_amd.hip.Selection -- cuts on per-photon quantities evaluated on the GPU, through which any of the tallies is filled;
+    Selection.gather fetches the per-photon data of the selected photons alone, compacted in order on the GPU;
   * polycap_amd.hip.JointHistograms -- exact joint 2-D histograms of two per-photon quantities per energy (phase space), on the GPU;
   * polycap_amd.hip.BeamMoments   -- exact exit-beam moments per energy (focal distance, waist, divergence), on the GPU;
   * TraceContext.scan / scan_points -- transmission per source position (alignment curves, focal spot, depth response) in one

@@ -140,6 +140,7 @@ def _lib():
         "pc_transmission_efficiencies_get_tally_squares": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_size_t), P(C.c_size_t)] + [P(P(C.c_uint64))] * 4 +
                                                              [P(_dp), P(_dp), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_select_squares": (C.c_int, [vp, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)), P(_dp), P(_dp), epp]),
+        "pc_transmission_efficiencies_get_select_records": (C.c_int, [vp, C.c_int, P(C.c_int64), P(C.c_int32), P(_dp), P(P(C.c_int64)), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -556,6 +557,20 @@ class TransmissionEfficiencies(_LeakData):
         elif err:
             L.polycap_error_free(err)
         return out
+
+    def select_records(self, kind="exit"):
+        """The selected photons themselves of a run made with POLYCAP_SELECT and POLYCAP_SELECT_RECORDS=N (extension,
+        pc_transmission_efficiencies_get_select_records): dict of records [rows, 17 + energies] for the exit photons (the planes of a
+        photon in their order, the reflection count as int64 bits in column 15, then the weights) or [rows, 12 + energies] for
+        "extleak" / "intleak" after a leak_calc run, the first min(N, n_pass) passing entries in order, and their int64 positions
+        [rows] in what the call's selection saw (for a call that keeps its images: in the result's own exit arrays)."""
+        L = _lib()
+        n, row = C.c_int64(0), C.c_int32(0)
+        r, p = _dp(), C.POINTER(C.c_int64)()
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_select_records(self._h, self.SPOT_KINDS[kind], C.byref(n), C.byref(row), C.byref(r), C.byref(p), C.byref(err))
+        _check(err)
+        return dict(records=_take(r, n.value * row.value).reshape(n.value, row.value), positions=_take(p, n.value, np.int64))
 
     def joint(self, kind="exit"):
         """Joint histograms of a run made with POLYCAP_JOINT set (extension, pc_transmission_efficiencies_get_joint): dict of the

@@ -1175,6 +1175,9 @@ struct pc_hip_ctx {
 	pc_dev_buf<unsigned long long> d_relay_scan; /* per-wave counts and offsets of the two compactions, then the relay's device counters */
 	int relay_acc_lds = 1;                 /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
 	int64_t relay_counters[8] = {0};
+	/* gathers of a selection's entries (pc_gather.h) */
+	int gather_tile = 0;                   /* option "gather_tile": entries per compaction tile, 0 = automatic */
+	long long gather_chunk_rows = 0;       /* option "gather_chunk_rows": rows per staging chunk, 0 = as many as fit in 128 MiB */
 };
 
 static void pc_fill_common(pc_hip_ctx *ctx, pc_kargs &a)
@@ -1468,6 +1471,8 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "block_shift") { if (value < 7 || value > 30) return pc_fail(PC_HIP_ERR_INVALID, "block_shift must be in [7,30]"); ctx->img.opts.blk_shift = (int)value; }
 	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->img.opts.run_parts = (int)value; }
 	else if (n == "relay_acc_lds") ctx->relay_acc_lds = value ? 1 : 0;
+	else if (n == "gather_tile") { if (value < 0 || value > 65536 || (value != 0 && (value < 64 || value % 64 != 0))) return pc_fail(PC_HIP_ERR_INVALID, "gather_tile must be a multiple of 64 in [64,65536] (0 = automatic)"); ctx->gather_tile = (int)value; }
+	else if (n == "gather_chunk_rows") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "gather_chunk_rows must be in [0,2^31-1] (0 = automatic)"); ctx->gather_chunk_rows = (long long)value; }
 	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->img.opts.fetch_threads = (int)value; }
 	else if (n == "pool") ctx->opts.pool = value ? 1 : 0;
 	else if (n == "wave_per_photon") {
@@ -2105,6 +2110,7 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_hist.h"
 #include "pc_joint.h"
 #include "pc_select.h"
+#include "pc_gather.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
 

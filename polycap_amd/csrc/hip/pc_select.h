@@ -268,6 +268,11 @@ struct pc_select_member {
 	long long n[3] = {0, 0, 0};                  /* entries the mask of a kind covers */
 	long long n_pass[3] = {0, 0, 0};             /* of which pass (once fetched) */
 	unsigned long long epoch[3] = {0, 0, 0};     /* ctx->entries_epoch the mask of a kind was made at */
+	/* pc_gather.h: the ascending positions of a kind's passing entries [n_pass], built by the first gather after an apply */
+	pc_dev_buf<unsigned int> d_idx[3];
+	int idx_valid[3] = {0, 0, 0};
+	pc_dev_buf<unsigned int> d_tile_cnt, d_tile_off;      /* the compaction's tile counts [tiles] and offsets [tiles + 1] */
+	pc_dev_buf<unsigned long long> d_stage;               /* the gathered rows of one chunk */
 };
 
 struct pc_hip_select {
@@ -425,6 +430,7 @@ int pc_hip_select_apply(pc_hip_select *sel, int kind)
 		pc_select_member &mb = sel->m[k];
 		pc_hip_ctx *c = mb.ctx;
 		mb.n[kind] = 0;
+		mb.idx_valid[kind] = 0;          /* the index list of the old mask (pc_gather.h) */
 		if (src[k].n == 0) { mb.epoch[kind] = c->entries_epoch; continue; }
 		PC_HIP_CHECK(hipSetDevice(c->device));
 		/* a gated add of this stream may still read the old mask */

@@ -75,6 +75,7 @@ static struct {
 	pc_herr (*aclose)(pc_hid);
 	pc_hid *native_double;   /* H5T_NATIVE_DOUBLE_g, valid after H5open() */
 	pc_hid *native_ullong;   /* H5T_NATIVE_ULLONG_g (the /Beam sums) */
+	pc_hid *native_llong;    /* H5T_NATIVE_LLONG_g (the positions of /Select/<Kind>_Records) */
 	pc_hid *c_s1;            /* H5T_C_S1_g */
 	char name[256];
 } h5;
@@ -104,6 +105,7 @@ static int pc_h5_bind(void *handle)
 	PC_SYM(aclose, "H5Aclose");
 	PC_SYM(native_double, "H5T_NATIVE_DOUBLE_g");
 	PC_SYM(native_ullong, "H5T_NATIVE_ULLONG_g");
+	PC_SYM(native_llong, "H5T_NATIVE_LLONG_g");
 	PC_SYM(c_s1, "H5T_C_S1_g");
 #undef PC_SYM
 	unsigned maj = 0, min = 0, rel = 0;
@@ -625,6 +627,24 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		}
 		sd[0] = 3; sd[1] = 2;
 		sok = sok && pc_h5_typed(file, 2, sd, "/Select/Entries", *h5.native_ullong, entries, "a.u.", "n_pass,n_seen", error);
+		if (sr->rec_limit > 0) {      /* POLYCAP_SELECT_RECORDS: the first rows of what passed, per kind that has some */
+			static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+			const uint64_t limit = (uint64_t)sr->rec_limit;
+			pc_hsize one = 1;
+			sok = sok && pc_h5_typed(file, 1, &one, "/Select/Records_Limit", *h5.native_ullong, &limit, "a.u.", NULL, error);
+			for (int k = 0; k < 3 && sok; k++) {
+				if (!sr->rec_applied[k] || sr->rec_n[k] == 0)
+					continue;
+				char name[64];
+				pc_hsize rd[2] = { (pc_hsize)sr->rec_n[k], (pc_hsize)sr->rec_row[k] };
+				snprintf(name, sizeof name, "/Select/%s_Records", names[k]);
+				sok = sok && pc_h5_typed(file, 2, rd, name, *h5.native_double, sr->rec[k], "[cm,a.u.]",
+				                         k == 0 ? "the planes of an exit photon in their order (n_refl as int64 bits), then the weights"
+				                                : "slot,attempt,x,y,z,dir x y z,elecv x y z,n_refl, then the weights", error);
+				snprintf(name, sizeof name, "/Select/%s_Positions", names[k]);
+				sok = sok && pc_h5_typed(file, 1, rd, name, *h5.native_llong, sr->rec_pos[k], "a.u.", NULL, error);
+			}
+		}
 		free(table);
 		if (!sok) goto close;
 	}

@@ -185,6 +185,14 @@ struct pc_select_result {
 	int64_t n_pass[3], n_seen[3];   /* exit photons, extleak, intleak (zeros where the run has none) */
 	uint64_t *passed_w, *rejected_w; /* [3][n_energies] */
 	uint64_t *passed_w2, *rejected_w2; /* [3][n_energies][2] with POLYCAP_TALLY_STDERR=1, NULL otherwise */
+	/* POLYCAP_SELECT_RECORDS=N (pc_transmission_efficiencies_get_select_records): per kind the call applied the selection to, the first
+	 * min(N, n_pass) passing entries in order as rows of pc_hip_select_gather and their positions; rec_limit 0: the variable was not set */
+	int64_t rec_limit;
+	int rec_applied[3];
+	int64_t rec_n[3];
+	int32_t rec_row[3];             /* doubles per row */
+	double *rec[3];                 /* [rec_n][rec_row] */
+	int64_t *rec_pos[3];            /* [rec_n] */
 };
 
 struct _polycap_transmission_efficiencies {

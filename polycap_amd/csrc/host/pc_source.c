@@ -707,12 +707,28 @@ struct pc_select_request {
 	pc_hip_select_cut cuts[8];
 	int32_t n_cuts;
 	pc_hip_select_spec spec;
+	int64_t records;               /* POLYCAP_SELECT_RECORDS=N: the result keeps the first N passing entries of every kind; 0: unset */
 };
 
 static int pc_select_request_parse(struct pc_select_request *r, polycap_error **error)
 {
 	memset(r, 0, sizeof(*r));
 	const char *env = getenv("POLYCAP_SELECT");
+	const char *rec = getenv("POLYCAP_SELECT_RECORDS");
+	if (rec != NULL) {
+		char *end = NULL;
+		errno = 0;
+		const long long v = strtoll(rec, &end, 10);
+		if (end == rec || *end != '\0' || errno != 0 || v < 1 || v > 2147483647ll) {
+			polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT_RECORDS=%s: must be an integer in 1 .. 2^31 - 1", rec);
+			return -1;
+		}
+		if (env == NULL) {
+			polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT_RECORDS=%s needs POLYCAP_SELECT: there is no selection to take the rows from", rec);
+			return -1;
+		}
+		r->records = (int64_t)v;
+	}
 	if (env == NULL)
 		return 0;
 	char why[320];
@@ -738,6 +754,12 @@ struct pc_tallies {
 	uint64_t *sel_w;               /* [2][3][ne] */
 	int squares;                   /* POLYCAP_TALLY_STDERR=1: every tally and the selection track squares */
 	uint64_t *sel_w2;              /* [2][3][ne][2] with squares: passed_w2, rejected_w2 summed over the applies with carry */
+	/* POLYCAP_SELECT_RECORDS: the first rec_limit passing entries per kind over the applies of the call (pc_hip_select_gather) */
+	int64_t rec_limit;
+	int rec_applied[3];
+	int64_t rec_n[3];
+	double *rec[3];                /* [rec_n][PC_HIP_N_PLANES or PC_HIP_LEAK_HDR, + ne] */
+	int64_t *rec_pos[3];           /* positions in the concatenation of what the applies saw */
 };
 
 /* every tally of the call and its selection track squares: before the first add and the first apply */
@@ -773,6 +795,25 @@ static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
 		st = (w != NULL) ? pc_hip_select_apply(s, kind) : PC_HIP_ERR_MEMORY;
 		if (st == PC_HIP_OK)
 			st = pc_hip_select_read(s, n_pass, n_seen, w, w + 3*ne);
+		if (st == PC_HIP_OK && ta->rec_limit > 0) {
+			/* the rows of what passed, as long as the limit has room: only they leave the device */
+			const size_t row = (size_t)(kind == 0 ? PC_HIP_N_PLANES : PC_HIP_LEAK_HDR) + ne;
+			const int64_t have = ta->rec_n[kind], room = ta->rec_limit - have, take = n_pass[kind] < room ? n_pass[kind] : room;
+			ta->rec_applied[kind] = 1;
+			if (take > 0) {
+				double *rec = realloc(ta->rec[kind], sizeof(double)*row*(size_t)(have + take));
+				if (rec != NULL)
+					ta->rec[kind] = rec;
+				int64_t *pos = realloc(ta->rec_pos[kind], sizeof(int64_t)*(size_t)(have + take));
+				if (pos != NULL)
+					ta->rec_pos[kind] = pos;
+				st = (rec != NULL && pos != NULL) ? pc_hip_select_gather(s, kind, 0, take, rec + row*(size_t)have, pos + have) : PC_HIP_ERR_MEMORY;
+				for (int64_t k = 0; st == PC_HIP_OK && k < take; k++)
+					pos[have + k] += ta->sel_n[3 + kind];      /* behind the entries the earlier applies saw */
+				if (st == PC_HIP_OK)
+					ta->rec_n[kind] = have + take;
+			}
+		}
 		if (st == PC_HIP_OK) {
 			ta->sel_n[kind] += n_pass[kind];
 			ta->sel_n[3 + kind] += n_seen[kind];
@@ -1174,6 +1215,7 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 	pc_hip_joint **joint = &ta->joint;
 	if (r->select.set) {
 		ta->sel_w = calloc(6*ne, sizeof(uint64_t));
+		ta->rec_limit = r->select.records;
 		st = ta->sel_w == NULL ? PC_HIP_ERR_MEMORY
 		   : t.group != NULL ? pc_hip_group_select_create(t.group, &r->select.spec, &ta->select) : pc_hip_select_create(t.ctx, &r->select.spec, &ta->select);
 	}
@@ -1361,6 +1403,14 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 			sr->rejected_w = pc_beam_dup(ta.sel_w + 3*ne, sizeof(uint64_t)*3*ne);
 			if (sr->passed_w == NULL || sr->rejected_w == NULL)
 				status = PC_HIP_ERR_MEMORY;
+			sr->rec_limit = ta.rec_limit;
+			for (int kind = 0; kind <= 2; kind++) {      /* the result owns the rows from here on */
+				sr->rec_applied[kind] = ta.rec_applied[kind];
+				sr->rec_n[kind] = ta.rec_n[kind];
+				sr->rec_row[kind] = (int32_t)((kind == 0 ? PC_HIP_N_PLANES : PC_HIP_LEAK_HDR) + ne);
+				sr->rec[kind] = ta.rec[kind]; sr->rec_pos[kind] = ta.rec_pos[kind];
+				ta.rec[kind] = NULL; ta.rec_pos[kind] = NULL;
+			}
 			if (status == PC_HIP_OK && ta.sel_w2 != NULL) {      /* POLYCAP_TALLY_STDERR */
 				sr->passed_w2 = pc_beam_dup(ta.sel_w2, sizeof(uint64_t)*6*ne);
 				sr->rejected_w2 = pc_beam_dup(ta.sel_w2 + 6*ne, sizeof(uint64_t)*6*ne);
@@ -1398,6 +1448,10 @@ out:
 	pc_hip_select_destroy(ta.select);
 	free(ta.sel_w);
 	free(ta.sel_w2);
+	for (int kind = 0; kind <= 2; kind++) {
+		free(ta.rec[kind]);
+		free(ta.rec_pos[kind]);
+	}
 	pc_run_request_free(&req);
 	free(sum_weights);
 	free(sum_fixed);

@@ -502,7 +502,51 @@ void pc_select_result_free(struct pc_select_result *select)
 	free(select->rejected_w);
 	free(select->passed_w2);
 	free(select->rejected_w2);
+	for (int k = 0; k < 3; k++) {
+		free(select->rec[k]);
+		free(select->rec_pos[k]);
+	}
 	free(select);
+}
+
+int pc_transmission_efficiencies_get_select_records(void *efficiencies_, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,
+	int64_t **positions, void *error_)
+{
+	static const char *fn = "pc_transmission_efficiencies_get_select_records";
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || n_rows == NULL || kind < 0 || kind > 2) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: efficiencies and n_rows cannot be NULL and kind must be 0, 1 or 2", fn);
+		return 0;
+	}
+	const struct pc_select_result *sr = efficiencies->select;
+	if (sr == NULL || sr->rec_limit == 0) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run was made without POLYCAP_SELECT_RECORDS", fn);
+		return 0;
+	}
+	if (!sr->rec_applied[kind]) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run has no entries of kind %d (leak kinds need a leak_calc run)", fn, kind);
+		return 0;
+	}
+	const size_t n = (size_t)sr->rec_n[kind], row = (size_t)sr->rec_row[kind];
+	double *r = NULL;
+	int64_t *p = NULL;
+	int ok = 1;
+	/* one element at least, so that a result of no rows still hands out pointers polycap_free takes */
+	if (records != NULL) ok = (r = malloc(sizeof(double)*(n > 0 ? n*row : 1))) != NULL;
+	if (positions != NULL && ok) ok = (p = malloc(sizeof(int64_t)*(n ? n : 1))) != NULL;
+	if (!ok) {
+		free(r); free(p);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "%s: could not allocate memory -> %s", fn, strerror(errno));
+		return 0;
+	}
+	if (r != NULL && n > 0) memcpy(r, sr->rec[kind], sizeof(double)*n*row);
+	if (p != NULL && n > 0) memcpy(p, sr->rec_pos[kind], sizeof(int64_t)*n);
+	*n_rows = (int64_t)n;
+	if (row_doubles != NULL) *row_doubles = (int32_t)row;
+	if (records != NULL) *records = r;
+	if (positions != NULL) *positions = p;
+	return 1;
 }
 
 int pc_transmission_efficiencies_get_select(void *efficiencies_, int32_t *n_cuts, double **cuts, size_t *n_energies, int64_t n_pass[3], int64_t n_seen[3],

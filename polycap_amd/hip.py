@@ -1028,6 +1028,26 @@ class Selection:
             raise HipError("pc_hip_select_apply", st)
         return self.read()
 
+    def gather(self, kind="exit", first=0, count=None, positions=False):
+        """The per-entry data of the passing entries numbered [first, first + count) of a kind the selection was applied for
+        (pc_hip_select_gather; count None = all from first on), in the order of their positions: records [count, 17 + n_energies]
+        for the exit photons -- the rows TraceContext.records() has at those positions, the reflection count as int64 bits in
+        column 15 -- or [count, 12 + n_energies] for a leak kind, the rows of leaks().  With positions=True also the int64
+        positions [count] (global ones for a group), strictly increasing.  Only the selected rows leave the device."""
+        k = _kind(kind)
+        first = int(first)
+        if count is None:
+            count = max(int(self.read()["n_pass"][k]) - first, 0)
+        count = int(count)
+        row = (17 if k == 0 else _cabi.PC_HIP_LEAK_HDR) + self.n_energies
+        rec = np.empty((max(count, 0), row))
+        pos = np.empty(max(count, 0), dtype=np.int64) if positions else None
+        st = self._L.pc_hip_select_gather(self._h, k, first, count, dptr(rec) if count > 0 else None,
+                                          pos.ctypes.data_as(c_int64_p) if positions and count > 0 else None)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_select_gather", st)
+        return (rec, pos) if positions else rec
+
 
 def scan_points(x=(0.,), y=(0.,), d_source=None):
     """Points of a scan, [len(d) * len(y) * len(x), 3] rows of (d_source, src_shiftx, src_shifty) in cm: the grid of the axes with

@@ -126,6 +126,8 @@ cdef extern from "polycap.h" nogil:
 
     int pc_transmission_efficiencies_get_select(void *efficiencies, int32_t *n_cuts, double **cuts, size_t *n_energies, int64_t *n_pass,
         int64_t *n_seen, uint64_t **passed_w, uint64_t **rejected_w, void *error)
+    int pc_transmission_efficiencies_get_select_records(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,
+        int64_t **positions, void *error)
     int pc_transmission_efficiencies_get_tally_squares(void *efficiencies, int which, int kind, size_t *n_cells, size_t *n_outside,
         uint64_t **sums, uint64_t **outside, uint64_t **squares, uint64_t **outside_squares, double **stderrs, double **outside_stderrs,
         int64_t *n_started, void *error)
@@ -873,6 +875,27 @@ cdef class TransmissionEfficiencies:
         elif error != NULL:
             polycap_error_free(error)
         return out
+
+    def select_records(self, kind="exit"):
+        """Extension of this build: the selected photons themselves of a run made with POLYCAP_SELECT and POLYCAP_SELECT_RECORDS=N
+        (pc_transmission_efficiencies_get_select_records): dict of records [rows, 17 + energies] for the exit photons (the planes of a
+        photon in their order, the reflection count as int64 bits in column 15, then the weights) or [rows, 12 + energies] for
+        "extleak" / "intleak" after a leak_calc run, the first min(N, n_pass) passing entries in order, and their int64 positions
+        [rows] in what the call's selection saw."""
+        cdef polycap_error *error = NULL
+        cdef int64_t n = 0
+        cdef int32_t row = 0
+        cdef double *r = NULL
+        cdef int64_t *p = NULL
+        cdef int64_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_select_records(<void *>self._eff, k, &n, &row, &r, &p, <void *>&error)
+        _raise_if(error)
+        pos = np.empty(n, dtype=np.int64)
+        for i in range(n):
+            pos[i] = p[i]
+        polycap_free(p)
+        return dict(records=_take_doubles(r, <size_t>(n * row)).reshape(n, row), positions=pos)
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
