@@ -228,7 +228,9 @@ struct pc_start {
 };
 
 /* sin and cos on [0, pi/2] without the generic argument reduction (fdlibm-style kernels on [0, pi/4],
- * Cody-Waite pi/2 = hi + lo); < 1 ulp.  Keeps libm's large-argument paths out of the trace kernel. */
+ * Cody-Waite pi/2 = hi + lo); within 2 ulp (1.51 measured for the sine, 1.43 for the cosine, both just above pi/4, where the
+ * cosine kernel without a tail stands in for the sine; tests/test_devmath_ends_cpu.py asserts the 2).  Keeps libm's
+ * large-argument paths out of the trace kernel. */
 PC_HD void pc_sincos_quadrant(double x, double &sn, double &cs)
 {
 	const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
@@ -440,7 +442,9 @@ PC_HD void pc_axis_setup(pc_photon<NE> &ph, double q_i, double r_i)
 {
 	ph.ky = r_i * (3./2);
 	ph.kx = (2.*q_i + r_i) * PC_COSPI_6;
-	ph.kn = sqrt(ph.kx*ph.kx + ph.ky*ph.ky);
+	/* |k|^2 = 3/4 (2q + r)^2 + 9/4 r^2 = 3 (q^2 + q r + r^2): a whole number, exact in doubles, so that kn is the exact |k| rounded
+	 * once (from the rounded kx it was up to 1.2 ulp off far from the axis; tests/test_devmath_ends_cpu.py holds it within 1) */
+	ph.kn = sqrt(3.*(q_i*q_i + q_i*r_i + r_i*r_i));
 }
 
 /* begin a polycap_capil_trace call at segment ph.i: src/polycap-capil.c:1236-1243 */

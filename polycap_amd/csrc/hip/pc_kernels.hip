@@ -780,7 +780,9 @@ pc_trace_kernel(pc_kargs a)
 					}
 					if (state == LS_MARCH) {
 						/* src/polycap-source.c:779-798: start images of the attempt that is now inside a capillary;
-						 * the slot belongs to this lane, so a later (transmitted) attempt simply overwrites them */
+						 * the slot belongs to this lane, so a later (transmitted) attempt simply overwrites them.  The start
+						 * direction recorded is the photon's after the launch: polycap_photon_launch normalises it once more in
+						 * place (src/polycap-photon.c:492) before :785-786 read it */
 						cosalpha0 = s.ex*s.dx + s.ey*s.dy + s.ez*s.dz;
 						if (a.keep_images) {
 							double evx, evy;
@@ -788,9 +790,9 @@ pc_trace_kernel(pc_kargs a)
 							if (a.img_cursor) {
 								/* compact store: the position is known when the photon leaves; until then its line */
 								double *ls = a.lane_start + gtid*8;
-								ls[0] = s.srcx; ls[1] = s.srcy; ls[2] = s.x; ls[3] = s.y; ls[4] = s.dx; ls[5] = s.dy; ls[6] = evx; ls[7] = evy;
+								ls[0] = s.srcx; ls[1] = s.srcy; ls[2] = s.x; ls[3] = s.y; ls[4] = ph.dx; ls[5] = ph.dy; ls[6] = evx; ls[7] = evy;
 							} else {
-								pc_write_start_fields<false>(a, slot, s.srcx, s.srcy, s.x, s.y, s.dx, s.dy, evx, evy);
+								pc_write_start_fields<false>(a, slot, s.srcx, s.srcy, s.x, s.y, ph.dx, ph.dy, evx, evy);
 							}
 						}
 					}

@@ -301,7 +301,7 @@ pc_leak_kernel(pc_kargs a, pc_leak_kargs lk)
 								double *r = a.img + slot*rec;
 								r[PC_F_SRCX] = s.srcx; r[PC_F_SRCY] = s.srcy;
 								r[PC_F_STARTX] = s.x; r[PC_F_STARTY] = s.y;
-								r[PC_F_SDIRX] = s.dx; r[PC_F_SDIRY] = s.dy;
+								r[PC_F_SDIRX] = L.ph.dx; r[PC_F_SDIRY] = L.ph.dy;   /* the direction as the launch left it (src/polycap-photon.c:492) */
 								double tx = s.ex*c_ae + s.dx*c_be, ty = s.ey*c_ae + s.dy*c_be, tz = s.ez*c_ae + s.dz*c_be;
 								pc_norm3(tx, ty, tz);
 								r[PC_F_SEVX] = round(tx); r[PC_F_SEVY] = round(ty);

@@ -301,7 +301,7 @@ pc_trace_pool_kernel(pc_kargs a)
 					double *r = a.img + slot*ss;
 					r[PC_F_SRCX*fs] = s.srcx; r[PC_F_SRCY*fs] = s.srcy;
 					r[PC_F_STARTX*fs] = s.x; r[PC_F_STARTY*fs] = s.y;
-					r[PC_F_SDIRX*fs] = s.dx; r[PC_F_SDIRY*fs] = s.dy;
+					r[PC_F_SDIRX*fs] = ph.dx; r[PC_F_SDIRY*fs] = ph.dy;   /* the direction as the launch left it (src/polycap-photon.c:492) */
 					double tx = s.ex*c_ae + s.dx*c_be, ty = s.ey*c_ae + s.dy*c_be, tz = s.ez*c_ae + s.dz*c_be;
 					pc_norm3(tx, ty, tz);
 					r[PC_F_SEVX*fs] = round(tx); r[PC_F_SEVY*fs] = round(ty);

@@ -211,7 +211,10 @@ pc_trace_producer_kernel(pc_kargs a)
 							const double cosalpha0 = s.ex*s.dx + s.ey*s.dy + s.ez*s.dz;
 							double evx, evy;
 							pc_start_elecv_image(s, cosalpha0, evx, evy);
-							pc_write_start_fields<true>(a, pos, s.srcx, s.srcy, s.x, s.y, s.dx, s.dy, evx, evy);
+							/* the start direction as the launch left it: normalised once more (pc_launch_init, src/polycap-photon.c:492) */
+							double ndx = s.dx, ndy = s.dy, ndz = s.dz;
+							pc_norm3(ndx, ndy, ndz);
+							pc_write_start_fields<true>(a, pos, s.srcx, s.srcy, s.x, s.y, ndx, ndy, evx, evy);
 							pc_write_exit_fields<true>(a, Pm, pos, gPx, gPy, gPz, gdx, gdy, gdz, gex, gey, gez, cosalpha0, (long long)g_irefl, gdt);
 							pc_store_wt(a.img_w + pos*ws, gw);
 							if (a.img_ids) pc_store_wt(a.img_ids + pos, a.img_id0 + g_slot);
@@ -311,7 +314,7 @@ pc_trace_producer_kernel(pc_kargs a)
 						double *r = a.img + f_slot*ss;
 						r[PC_F_SRCX*fs] = s.srcx; r[PC_F_SRCY*fs] = s.srcy;
 						r[PC_F_STARTX*fs] = s.x; r[PC_F_STARTY*fs] = s.y;
-						r[PC_F_SDIRX*fs] = s.dx; r[PC_F_SDIRY*fs] = s.dy;
+						r[PC_F_SDIRX*fs] = np.dx; r[PC_F_SDIRY*fs] = np.dy;   /* the direction as the launch left it (src/polycap-photon.c:492) */
 						double tx = s.ex*c_ae + s.dx*c_be, ty = s.ey*c_ae + s.dy*c_be, tz = s.ez*c_ae + s.dz*c_be;
 						pc_norm3(tx, ty, tz);
 						r[PC_F_SEVX*fs] = round(tx); r[PC_F_SEVY*fs] = round(ty);

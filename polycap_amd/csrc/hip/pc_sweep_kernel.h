@@ -665,9 +665,9 @@ pc_trace_log_kernel(pc_kargs a)
 						pc_start_elecv_image(s, cosalpha0, evx, evy);
 						if (a.img_cursor) {
 							double *ls = a.lane_start + gtid*8;
-							ls[0] = s.srcx; ls[1] = s.srcy; ls[2] = s.x; ls[3] = s.y; ls[4] = s.dx; ls[5] = s.dy; ls[6] = evx; ls[7] = evy;
+							ls[0] = s.srcx; ls[1] = s.srcy; ls[2] = s.x; ls[3] = s.y; ls[4] = ph.dx; ls[5] = ph.dy; ls[6] = evx; ls[7] = evy;
 						} else {
-							pc_write_start_fields<false>(a, slot, s.srcx, s.srcy, s.x, s.y, s.dx, s.dy, evx, evy);
+							pc_write_start_fields<false>(a, slot, s.srcx, s.srcy, s.x, s.y, ph.dx, ph.dy, evx, evy);   /* the direction as the launch left it (src/polycap-photon.c:492) */
 						}
 					}
 				}

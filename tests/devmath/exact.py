@@ -595,8 +595,8 @@ def hex_forms(x, y, zz, q, r):
 
 def hex_cells(x, y, zz):
     """exactly: the cells (q, r) whose closed hexagon holds (x, y) -- one, two on an edge, three at a corner -- and for each the
-    smallest of 1 - |a_k| / zz (0 on an edge)"""
-    x, y, zz = fr(x), fr(y), fr(zz)
+    smallest of 1 - |a_k| / zz (0 on an edge).  A Fraction passed in is taken as it is (entrance: zz between two nodes)."""
+    x, y, zz = (v if isinstance(v, Fraction) else fr(v) for v in (x, y, zz))
     qf, rf = (x / (2 * COSPI_6) - y / 3) / zz, y * TWO_THIRDS / zz
     out = {}
     for q in range(math_floor(qf) - 1, math_floor(qf) + 3):
@@ -615,7 +615,7 @@ def math_floor(v):
 def hex_error_bound(x, y, zz, qf, rf):
     """first-order running error bound (one 2^-53 per operation) of the fractional coordinates pc_hex_index forms and of the three
     differences its cube rounding compares, as one number in cell units"""
-    x, y, zz = abs(fr(x)), abs(fr(y)), abs(fr(zz))
+    x, y, zz = (abs(v if isinstance(v, Fraction) else fr(v)) for v in (x, y, zz))
     eq = U53 * ((x / (2 * COSPI_6) + y / 3 + abs(x / (2 * COSPI_6) - y / 3)) / zz + abs(qf))
     er = 2 * U53 * abs(rf)
     es = eq + er + 2 * U53 * (abs(qf) + abs(rf))
@@ -771,3 +771,259 @@ def outer_scan(t, c, d):
             found = j
             break
     return found, clear
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The two ends of a photon's life (tests/test_devmath_ends_cpu.py): the random stream, the quadrant sine / cosine, the source
+# sampler (src/polycap-source.c:54-137), the entrance tests of polycap_photon_launch (src/polycap-photon.c:507-645) and the exit
+# window (src/polycap-source.c:762-777), from the reference's text: Python integers for the stream, Fractions where the quantities
+# are rational, mpmath at EDPS digits for roots and libm.  cos(pi/6) is the double the reference's macro holds wherever the
+# reference multiplies with it; its exact value sqrt(3)/2 only where the product's kx is judged.
+EDPS = 60
+M32 = 0xffffffff
+
+
+def philox(ctr, key):
+    """Philox4x32-10 (Random123) in Python integers: counter (4 words), key (2 words) -> 4 words"""
+    c0, c1, c2, c3 = (int(v) & M32 for v in ctr)
+    k0, k1 = (int(v) & M32 for v in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & M32, (p0 >> 32) ^ c3 ^ k1, p0 & M32
+        k0, k1 = (k0 + 0x9E3779B9) & M32, (k1 + 0xBB67AE85) & M32
+    return c0, c1, c2, c3
+
+
+def uniform(seed, slot, attempt, d):
+    """uniform #d of the stream (seed, slot, attempt) as a Fraction k / 2^53: counter (slot_lo, slot_hi, attempt, d >> 1), key
+    (seed_lo, seed_hi); even d takes words (0, 1) of the block, odd d words (2, 3); the 64-bit word's upper 53 bits"""
+    o = philox((slot & M32, (slot >> 32) & M32, attempt, d >> 1), (seed & M32, (seed >> 32) & M32))
+    w = (o[3] << 32 | o[2]) if d & 1 else (o[1] << 32 | o[0])
+    return Fraction(w >> 11, 1 << 53)
+
+
+def _mpq(q):
+    """a Fraction (or a double) as an mpf at the working precision"""
+    if isinstance(q, Fraction):
+        return mp.mpf(q.numerator) / q.denominator
+    return mp.mpf(float(q))
+
+
+def ulp_of(v):
+    """spacing of the doubles at |v| (v an mpf or a float; the smallest subnormal at 0)"""
+    a = abs(float(v))
+    if a < 2.0 ** -1022:
+        return 2.0 ** -1074
+    return 2.0 ** (math.frexp(a)[1] - 53)
+
+
+def ulp_err(got, exact_mpf):
+    """|got - exact| in units of the spacing of the doubles at the exact value, as a float"""
+    with mp.workdps(EDPS):
+        return float(abs(mp.mpf(float(got)) - exact_mpf) / mp.mpf(ulp_of(exact_mpf)))
+
+
+def sincos(x):
+    """(sin x, cos x) of the double x as mpf"""
+    with mp.workdps(EDPS):
+        v = mp.mpf(float(x))
+        return mp.sin(v), mp.cos(v)
+
+
+def hex_distance(radius, x, y):
+    """polycap_photon_within_pc_boundary as a signed distance (mpf; working precision of the caller): centre-to-edge distance
+    sqrt(radius^2 - (radius/2)^2) minus the largest of |y|, |C x + y/2|, |C x - y/2|, C the reference's double: > 0 inside.
+    radius, x, y Fractions."""
+    m = max(abs(y), abs(COSPI_6 * x + y / 2), abs(COSPI_6 * x - y / 2))
+    return mp.sqrt(_mpq(radius * radius - radius * radius / 4)) - _mpq(m)
+
+
+def sample_photon(source, cap0, ext0, mono, seed, slot, attempt):
+    """polycap_source_get_photon (src/polycap-source.c:54-137) on the stream (seed, slot, attempt).  source = (d_source, src_x,
+    src_y, src_sigx, src_sigy, src_shiftx, src_shifty, hor_pol), doubles.  Returns dict(out = the 12 outputs (start, direction,
+    electric vector, source point with z = 0) as mpf, hexdist = the smallest |hex_distance| of any tried (x, y) pair in units of
+    ext0 (None where no pair is tried), signs = (sign of cos phi, sign of sin phi) from the quadrant rules, e0 = 0 / 1 (horizontal /
+    vertical), tries = pairs tried, quadrant = 0..3)."""
+    with mp.workdps(EDPS):
+        d_source, src_x, src_y, sigx, sigy, shx, shy, hor_pol = (fr(v) for v in source)
+        d = 0
+
+        def draw():
+            nonlocal d
+            u = uniform(seed, slot, attempt, d)
+            d += 1
+            return u
+
+        r = draw()
+        phi = mp.atan(_mpq(src_y / src_x) * mp.tan(2 * mp.pi * _mpq(r) / 4))
+        r = draw()
+        quadrant = 0
+        if Fraction(1, 4) <= r < Fraction(1, 2):
+            phi, quadrant = mp.pi - phi, 1
+        if Fraction(1, 2) <= r < Fraction(3, 4):
+            phi, quadrant = mp.pi + phi, 2
+        if r >= Fraction(3, 4):
+            phi, quadrant = -phi, 3
+        c, s = mp.cos(phi), mp.sin(phi)
+        sx_, sy_ = _mpq(src_x), _mpq(src_y)
+        max_rad = sx_ * sy_ / mp.sqrt((sy_ * c) ** 2 + (sx_ * s) ** 2)
+        r = draw()
+        sr = mp.sqrt(_mpq(r))
+        srcx, srcy = sr * max_rad * c + _mpq(shx), sr * max_rad * s + _mpq(shy)
+        hexdist, tries = None, 0
+        if sigx < 0 or sigy < 0:
+            if mono:
+                x = (2 * draw() - 1) * fr(cap0)
+                y = (2 * draw() - 1) * fr(cap0)
+            else:
+                e0_ = fr(ext0)
+                while True:
+                    x = (2 * draw() - 1) * e0_
+                    y = (2 * draw() - 1) * e0_
+                    tries += 1
+                    hd = hex_distance(e0_, x, y)
+                    rel = abs(hd) / _mpq(e0_)
+                    hexdist = rel if hexdist is None or rel < hexdist else hexdist
+                    if hd >= 0:
+                        break
+            x, y = _mpq(x), _mpq(y)
+            dx, dy, dz = x - srcx, y - srcy, _mpq(d_source)
+        else:
+            dx = _mpq(sigx * (1 - 2 * abs(draw())))
+            dy = _mpq(sigy * (1 - 2 * abs(draw())))
+            dz = mp.mpf(1)
+            x, y = srcx + dx * _mpq(d_source) / dz, srcy + dy * _mpq(d_source) / dz
+        n = mp.sqrt(dx * dx + dy * dy + dz * dz)
+        dx, dy, dz = dx / n, dy / n, dz / n
+        frac_hor_pol = (1 + hor_pol) / 2
+        r = draw()
+        e0 = 0 if abs(r) <= frac_hor_pol else 1
+        ex, ey, ez = (mp.mpf(1), mp.mpf(0), mp.mpf(0)) if e0 == 0 else (mp.mpf(0), mp.mpf(1), mp.mpf(0))
+        cosalpha = ex * dx + ey * dy + ez * dz
+        c_ae = 1 / mp.sin(mp.acos(cosalpha))
+        c_be = -c_ae * cosalpha
+        ex, ey, ez = ex * c_ae + dx * c_be, ey * c_ae + dy * c_be, ez * c_ae + dz * c_be
+        n = mp.sqrt(ex * ex + ey * ey + ez * ez)
+        ex, ey, ez = ex / n, ey / n, ez / n
+        sign = lambda v: (v > 0) - (v < 0)
+        return dict(out=[x, y, mp.mpf(0), dx, dy, dz, ex, ey, ez, srcx, srcy, mp.mpf(0)], hexdist=hexdist, signs=(sign(c), sign(s)),
+                    e0=e0, tries=tries, quadrant=quadrant)
+
+
+def _cube_round(qf, rf):
+    """cube rounding of fractional axial coordinates in doubles: a first guess only, never a decision"""
+    sf = -qf - rf
+    rq, rr, rs = round(qf), round(rf), round(sf)
+    dq, dr, ds = abs(qf - rq), abs(rf - rr), abs(sf - rs)
+    if dq > dr and dq > ds:
+        rq = -rr - rs
+    elif dr > ds:
+        rr = -rq - rs
+    return int(rq), int(rr)
+
+
+def entrance_profile(z, cap, ext):
+    """the profile's doubles as Fractions, once per profile"""
+    return dict(z=[fr(v) for v in z], cap=[fr(v) for v in cap], ext=[fr(v) for v in ext], zf=[float(v) for v in z])
+
+
+def entrance(prof, n_shells, x, y, z):
+    """The entrance tests of polycap_photon_launch (src/polycap-photon.c:507-645) for a start point (x, y, z), exactly.
+    prof = entrance_profile(...).  Returns dict:
+      z_id     last node <= z among 0 .. nmax - 1 (0 for z <= 0): the segment the reference interpolates in
+      ix       last node <= z among 0 .. nmax (0 for z <= 0): the segment the photon starts in
+      cur_ext  the interpolated exterior radius (Fraction)
+      outer    signed distance to the outer boundary, > 0 inside: the hexagon of circum-radius cur_ext, the circle for n_shells = 0
+      cells    {(q, r): dict(slack, rad, cx, cy, wall)} for every cell whose closed hexagon holds the point or misses it by no
+               more than hex_error_bound (cell units): slack as hex_cells gives it (negative: missed by that much), the interpolated
+               radius and centre of the cell's capillary (Fractions) and the signed distance to its wall (float, > 0 inside)
+      cell_eb  hex_error_bound at the point
+    The mono-capillary has the one cell (0, 0)."""
+    with mp.workdps(EDPS):
+        Z, CAP, EXT = prof["z"], prof["cap"], prof["ext"]
+        nmax = len(Z) - 1
+        zf = float(z)
+        x, y, zq = fr(x), fr(y), fr(z)
+        z_id = ix = 0
+        if zf > 0:
+            ix = max(0, bisect.bisect_right(prof["zf"], zf) - 1)
+            z_id = min(ix, nmax - 1)
+        t = (zq - Z[z_id]) / (Z[z_id + 1] - Z[z_id])
+        cur_ext = EXT[z_id] + (EXT[z_id + 1] - EXT[z_id]) * t
+        out = dict(z_id=z_id, ix=ix, cur_ext=cur_ext, cell_eb=Fraction(0))
+        if n_shells == 0:
+            out["outer"] = float(_mpq(cur_ext) - mp.sqrt(_mpq(x * x + y * y)))
+            cands = {(0, 0): Fraction(1)}
+        else:
+            out["outer"] = float(hex_distance(cur_ext, x, y))
+            zz = cur_ext / (2 * COSPI_6 * (n_shells + 1))
+            qf, rf = (x / (2 * COSPI_6) - y / 3) / zz, y * TWO_THIRDS / zz
+            eb = hex_error_bound(x, y, zz, qf, rf)
+            out["cell_eb"] = eb
+            cands = {}
+            # The closed hexagons tile the plane: a point inside one cell by the relative slack m misses every other cell by at
+            # least m.  The cell that rounding in doubles suggests is tried first, and the neighbourhood only where it does not
+            # hold the point by 1e-6.
+            q0, r0 = _cube_round(float(qf), float(rf))
+            m = min(zz - abs(v) for v in hex_forms(x, y, zz, q0, r0)) / zz
+            if m > Fraction(1, 10 ** 6) and m > eb:
+                cands[(q0, r0)] = m
+            else:
+                for q in range(math_floor(qf) - 1, math_floor(qf) + 3):
+                    for r in range(math_floor(rf) - 1, math_floor(rf) + 3):
+                        m = min(zz - abs(v) for v in hex_forms(x, y, zz, q, r)) / zz
+                        if m >= -eb:
+                            cands[(q, r)] = m
+        cells = {}
+        for (q, r), m in cands.items():
+            # cap_x[i] = (2 q + r) C ext[i] / (2 C (n_shells + 1)), cap_y[i] = r (3/2) ext[i] / (2 C (n_shells + 1)): :622-627
+            hs = 2 * COSPI_6 * (n_shells + 1)
+            if zf > 0:
+                rad = CAP[z_id] + (CAP[z_id + 1] - CAP[z_id]) * t
+                e = cur_ext
+            else:
+                rad, e = CAP[0], EXT[0]
+            cx, cy = (2 * q + r) * COSPI_6 * e / hs, r * Fraction(3, 2) * e / hs
+            wall = float(_mpq(rad) - mp.sqrt(_mpq((x - cx) ** 2 + (y - cy) ** 2)))
+            cells[(q, r)] = dict(slack=m, rad=rad, cx=cx, cy=cy, wall=wall)
+        out["cells"] = cells
+        return out
+
+
+def unit3(v):
+    """v / |v| of three doubles as mpf"""
+    with mp.workdps(EDPS):
+        w = [mp.mpf(float(t)) for t in v]
+        n = mp.sqrt(_dot(w, w))
+        return [t / n for t in w]
+
+
+def ray_constants(P, d):
+    """(1 / dz, dx / dz, dy / dz, Px - dx/dz Pz, Py - dy/dz Pz) of the unit vector along d (doubles; the norm cancels in all but
+    the first), mpf: src/polycap-capil.c:1236-1243"""
+    with mp.workdps(EDPS):
+        w = [mp.mpf(float(t)) for t in d]
+        p = [mp.mpf(float(t)) for t in P]
+        n = mp.sqrt(_dot(w, w))
+        sx, sy = w[0] / w[2], w[1] / w[2]
+        return n / w[2], sx, sy, p[0] - sx * p[2], p[1] - sy * p[2]
+
+
+def axis_factors(q, r):
+    """(kx, ky, |k|) of capillary (q, r) with the exact cos(pi/6): (2 q + r) sqrt(3)/2, 3 r / 2, mpf (src/polycap-photon.c:624-627)"""
+    with mp.workdps(EDPS):
+        kx, ky = (2 * q + r) * mp.sqrt(3) / 2, mp.mpf(3 * r) / 2
+        return kx, ky, mp.sqrt(kx * kx + ky * ky)
+
+
+def exit_window(z_end, ext_end, mono, P, d):
+    """src/polycap-source.c:762-777 exactly: the photon at P flying along d (doubles) extrapolated to z_end; returns (tx, ty)
+    (Fractions), the signed distance to the exit hexagon of circum-radius ext_end (the circle for mono), > 0 inside (float), and the
+    scale max(|Px|, |Py|, |dx t|, |dy t|, ext_end) (float)"""
+    with mp.workdps(EDPS):
+        Px, Py, Pz, dx, dy, dz = (fr(v) for v in tuple(P) + tuple(d))
+        t = (fr(z_end) - Pz) / dz
+        tx, ty = Px + dx * t, Py + dy * t
+        e = fr(ext_end)
+        dist = float(_mpq(e) - mp.sqrt(_mpq(tx * tx + ty * ty))) if mono else float(hex_distance(e, tx, ty))
+        return (tx, ty), dist, float(max(abs(Px), abs(Py), abs(dx * t), abs(dy * t), e))

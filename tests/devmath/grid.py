@@ -1432,3 +1432,272 @@ def flight_grids():
         out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof, rows=rows,
                          meta=meta)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The grids of a photon's two ends (ops SINCOS, UNIFORM, ENTER, EXIT and the sampler; tests/test_devmath_ends_cpu.py).
+# Deterministic; the only random draws are the Philox streams themselves.  What a row really is -- which side of a boundary, how far
+# from it -- is decided by the exact side (tests/devmath/exact.py), never by this file.
+SINCOS_WORST = (0.793567278060035, 1.0650241763598487)      # the largest sine and cosine errors found on 300 000 points
+
+
+@functools.lru_cache(maxsize=None)
+def sincos_points():
+    """the arguments of op SINCOS: 0, the smallest subnormal, 2^-1022, 2^-27, 2^-26; pi/4 +- k 2^-53 for k <= 40; the 60 doubles
+    below pi/2 in steps of 2^-52; 2 pi (k / 2^53) / 4 as the sampler forms it for k in {0, 1, 2^51, 2^52 +- 1, 2^53 - 1}; 20 000
+    points of a fixed lattice in [0, pi/2]; 5 000 log-spaced points in [1e-12, 1]; the two worst points known"""
+    pio4, pio2 = 0.78539816339744830962, 1.57079632679489655800
+    x = [0.0, 2.0 ** -1074, 2.0 ** -1022, 2.0 ** -27, 2.0 ** -26]
+    x += [pio4 + k * 2.0 ** -53 for k in range(-40, 41)]
+    x += [pio2 - k * 2.0 ** -52 for k in range(1, 61)]
+    x += [2.0 * math.pi * (k / 2.0 ** 53) / 4. for k in (0, 1, 2 ** 51, 2 ** 52 - 1, 2 ** 52 + 1, 2 ** 53 - 1)]
+    x += list((np.arange(20000) + 0.5) * (pio2 / 20000))
+    x += list(10.0 ** np.linspace(-12, 0, 5000))
+    x += list(SINCOS_WORST)
+    return np.array(x, dtype=np.float64)
+
+
+UNIFORM_SEEDS = (0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1, 0x0123456789abcdef)
+UNIFORM_SLOTS = (0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1, 2 ** 40 + 5, 2 ** 63 - 1)
+UNIFORM_ATTEMPTS = (0, 1, 2 ** 32 - 1)
+UNIFORM_D = (0, 1, 2, 3, 4094, 4095)
+
+
+@functools.lru_cache(maxsize=None)
+def uniform_streams():
+    """every (seed, slot, attempt, d) of op UNIFORM, Python integers"""
+    return tuple((s, t, a, d) for s in UNIFORM_SEEDS for t in UNIFORM_SLOTS for a in UNIFORM_ATTEMPTS for d in UNIFORM_D)
+
+
+SAMPLER_SEED = 424242
+SAMPLER_SLOTS = tuple(range(1496)) + (2 ** 32 - 1, 2 ** 32, 2 ** 40 + 5, 2 ** 62 + 1)
+# name -> (optic, source, attempt); generic: the elliptical source, sampled through libm (not bit for bit between device and host)
+SAMPLER_CASES = dict(
+    xos1=("xos1", (2000., 0.2065, 0.2065, 0., 0., 0., 0., 0.0), 3),
+    divergent=("ellip", (0.05, 0.1, 0.1, 0.2, 0.2, 0., 0., 0.5), 3),
+    elliptical=("ellip", (2000., 0.2065, 0.1, 0., 0., 0.01, -0.02, 0.9), 3),
+    uniform=("ellip", (5., 0.01, 0.01, -1., 0., 0., 0., 0.0), 3),
+    mono=("MONO_CASE", None, 3),
+    seven=("SEVEN_CASE", None, 3),
+    ecc_flat=("ellip", (2000., 0.2, 0.2e-3, 0., 0., 0., 0., 0.5), 3),
+    ecc_tall=("ellip", (2000., 0.2e-3, 0.2, 0., 0., 0., 0., 0.5), 3),
+    pol_minus=("ellip", (2000., 0.2065, 0.2065, 0., 0., 0., 0., -1.0), 3),
+    pol_zero=("ellip", (2000., 0.2065, 0.2065, 0., 0., 0., 0., 0.0), 3),
+    pol_plus=("ellip", (2000., 0.2065, 0.2065, 0., 0., 0., 0., 1.0), 3),
+    last_attempt=("xos1", (2000., 0.2065, 0.2065, 0., 0., 0., 0., 0.0), 2 ** 32 - 1),
+)
+SAMPLER_GENERIC = ("elliptical", "ecc_flat", "ecc_tall")
+
+
+@functools.lru_cache(maxsize=None)
+def sampler_case(name):
+    """dict(optic, src (the oracle's), problem, source (the 8 doubles), attempt, mono, cap0, ext0)"""
+    from oracle import pyoracle
+    from tests import common
+    pyoracle.build()
+    which, source, attempt = SAMPLER_CASES[name]
+    if which in ("MONO_CASE", "SEVEN_CASE"):
+        c = getattr(common, which)
+        optic, src, prob, _ = common.make_custom(pyoracle, c["shape"], c["n_cap"], c["source"])
+        source = c["source"]
+    else:
+        optic, src, prob, _ = common.make_pair(pyoracle, which, source=source)
+    ns = round(math.sqrt(12. * prob.n_cap - 3.) / 6. - 0.5)
+    return dict(optic=optic, src=src, problem=prob, source=tuple(float(v) for v in source), attempt=attempt, mono=(ns == 0),
+                cap0=float(prob.cap[0]), ext0=float(prob.ext[0]))
+
+
+ENTER_PROFILES = ("taper", "ext_kink", "irregular", "tiny", "bulge", "mono", "nmax1")
+ENTER_OFFSETS = (0.0, 1.0, -1.0, 3.0, -3.0, 1e5, -1e5)                      # wall, cell: units of the spacing of the doubles at the scale
+ENTER_HEX_OFFSETS = (0.0, 1.0, -1.0, 2.0, -2.0, 3.0, -3.0, 1e5, -1e5)       # hexedge, hexcorner
+ENTER_NORMS = (1e-3, 1.0, 1.0 - 2.0 ** -52, 1.0 + 2.0 ** -52, 1e3)
+ENTER_D = (1.5e-3, -2.5e-3, 1.0)
+ENTER_E = (0.3, -0.9, 0.2)
+# Families (meta["fam"]): wall (150 capillaries per height, a point on the circle at ENTER_OFFSETS), cell (edges and corners of 6
+# cells), hexedge / hexcorner (the outer hexagon; the circle of the mono-capillary), axis (the 150 centres), norms (40 interior points
+# per height with |d| and |E| through ENTER_NORMS: 25 rows each, all decided -- with them the rows put inside a band on purpose, 5 of
+# the 7 wall offsets, stay below the 45 % the test allows).
+ENTER_CELLS, ENTER_NORM_CELLS, ENTER_EDGE_CELLS = 150, 40, 6
+GOLDEN_ANGLE = 2.399963229728653
+
+
+def enter_z(z):
+    """the ten start heights of a profile: 0; node 1 and half of it; node 5 and its two neighbour doubles; node nmax - 1; the
+    middle of the last segment; z[nmax] and the double below it (fewer where the profile has fewer nodes)"""
+    n = len(z) - 1
+    c = [0.0, float(z[1]), 0.5 * float(z[1])]
+    if n >= 6:
+        c += [float(z[5]), float(np.nextafter(z[5], 0.0)), float(np.nextafter(z[5], np.inf))]
+    c += [float(z[n - 1]), 0.5 * (float(z[n - 1]) + float(z[n])), float(z[n]), float(np.nextafter(z[n], 0.0))]
+    out = []
+    for v in c:
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def _ring_cell(ring, pos):
+    dirs = ((1, 0), (1, -1), (0, -1), (-1, 0), (-1, 1), (0, 1))
+    q, r = dirs[4][0] * ring, dirs[4][1] * ring
+    k = 0
+    for side in range(6):
+        for _ in range(ring):
+            if k == pos:
+                return q, r
+            q, r = q + dirs[side][0], r + dirs[side][1]
+            k += 1
+    return q, r
+
+
+def enter_cells(ns, n=ENTER_CELLS):
+    """n capillaries (q, r) of an optic of ns shells: the centre, the six corners of the outermost shell (q or r = +-ns), and a
+    fixed lattice over the shells"""
+    if ns == 0:
+        return [(0, 0)]
+    cells = [(0, 0), (ns, 0), (-ns, 0), (0, ns), (0, -ns), (ns, -ns), (-ns, ns)]
+    k = 0
+    while len(cells) < n:
+        ring = 1 + int((ns - 0.001) * math.sqrt((k % 97 + 0.5) / 97))
+        c = _ring_cell(ring, (k * 7919) % (6 * ring))
+        if c not in cells:
+            cells.append(c)
+        k += 1
+    return cells
+
+
+def _enter_rows_of(name, prof):
+    F = exact.Fraction
+    z, cap, ext, ns = prof["z"], prof["cap"], prof["ext"], prof["ns"]
+    P = exact.entrance_profile(z, cap, ext)
+    nmax = len(z) - 1
+    C = exact.COSPI_6
+    rows, meta = [], []
+
+    def put(fam, x, y, zv, d=ENTER_D, E=ENTER_E, **kw):
+        rows.append((x, y, zv) + tuple(d) + tuple(E))
+        meta.append(dict(fam=fam, **kw))
+
+    cells = enter_cells(ns)
+    for zi, zv in enumerate(enter_z(z)):
+        j = 0
+        if zv > 0:
+            j = min(max(0, int(np.searchsorted(z, zv, side="right")) - 1), nmax - 1)
+        t = (F(zv) - P["z"][j]) / (P["z"][j + 1] - P["z"][j])
+        e = float(P["ext"][j] + (P["ext"][j + 1] - P["ext"][j]) * t)
+        rad = float(P["cap"][j] + (P["cap"][j + 1] - P["cap"][j]) * t)
+        hs = float(2 * C * (ns + 1))
+        zz = e / hs
+
+        def centre(q, r):
+            return float((2 * q + r) * C) * zz, 1.5 * r * zz
+
+        for ci, (q, r) in enumerate(cells if ns else [(0, 0)] * ENTER_CELLS):
+            cx, cy = centre(q, r)
+            sc = float(np.spacing(max(abs(cx) + rad, abs(cy) + rad, e)))
+            a = (0.0, 0.5 * math.pi)[ci] if ci < 2 else 0.7 + GOLDEN_ANGLE * (ci + 17 * zi)
+            for k in ENTER_OFFSETS:
+                put("wall", cx + (rad + k * sc) * math.cos(a), cy + (rad + k * sc) * math.sin(a), zv, cell=(q, r), off=k)
+            if ns or ci == 0:
+                put("axis", cx, cy, zv, cell=(q, r), off=None)
+            if ci < ENTER_NORM_CELLS:
+                px, py = cx + 0.3 * rad * math.cos(a), cy + 0.3 * rad * math.sin(a)
+                for nd in ENTER_NORMS:
+                    for ne in ENTER_NORMS:
+                        dn, en = math.sqrt(sum(v * v for v in ENTER_D)), math.sqrt(sum(v * v for v in ENTER_E))
+                        put("norms", px, py, zv, d=[v / dn * nd for v in ENTER_D], E=[v / en * ne for v in ENTER_E], cell=(q, r), off=None)
+            if ns and (ci == 0 or 7 <= ci < 6 + ENTER_EDGE_CELLS):
+                for k in ENTER_OFFSETS:
+                    for ed in range(3):
+                        b = math.radians(60 * ed)
+                        put("cell", cx + (float(C) * zz + k * sc) * math.cos(b), cy + (float(C) * zz + k * sc) * math.sin(b), zv, cell=(q, r), off=k, at="edge")
+                    for co in range(2):
+                        b = math.radians(30 + 60 * co)
+                        put("cell", cx + (zz + k * sc) * math.cos(b), cy + (zz + k * sc) * math.sin(b), zv, cell=(q, r), off=k, at="corner")
+        sc = float(np.spacing(e))
+        for k in ENTER_HEX_OFFSETS:
+            if ns == 0:
+                for m in range(30):
+                    a = 0.3 + GOLDEN_ANGLE * m if m >= 2 else (0.0, 0.5 * math.pi)[m]
+                    put("hexedge", (e + k * sc) * math.cos(a), (e + k * sc) * math.sin(a), zv, off=k)
+                continue
+            inr = math.sqrt(3.0) / 2 * e
+            for ed in range(6):
+                b = math.radians(30 + 60 * ed)
+                for s in (-0.8, -0.45, -0.1, 0.3, 0.7):
+                    put("hexedge", (inr + k * sc) * math.cos(b) - s * 0.5 * e * math.sin(b), (inr + k * sc) * math.sin(b) + s * 0.5 * e * math.cos(b), zv, off=k)
+                b = math.radians(60 * ed)
+                put("hexcorner", (e + k * sc) * math.cos(b), (e + k * sc) * math.sin(b), zv, off=k)
+    # the first row of every profile flies along the axis with an electric vector of length exactly 1 (pc_launch_init divides E by
+    # its length only where that is not 1)
+    rows[0] = rows[0][:3] + (0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
+    return np.array(rows, dtype=np.float64), meta
+
+
+@functools.lru_cache(maxsize=None)
+def enter_grids():
+    """name -> dict(problem, profile, rows [n, 9] of pyprobe.ENTER_COLS, meta [n])"""
+    out = {}
+    profs = march_profiles()
+    for name in ENTER_PROFILES:
+        prof = profs[name]
+        rows, meta = _enter_rows_of(name, prof)
+        out[name] = dict(problem=march_problem(prof["z"], prof["cap"], prof["ext"], _n_cap(prof["ns"])), profile=prof, rows=rows, meta=meta)
+    return out
+
+
+EXIT_OFFSETS = ENTER_OFFSETS + (1e7, -1e7, 1e9, -1e9, 1e11, -1e11)
+EXIT_DZ = (1.0, 1e-2, 1e-8)
+
+
+def _exit_rows_of(name, prof):
+    z, ext, ns = prof["z"], prof["ext"], prof["ns"]
+    nmax = len(z) - 1
+    ze, e = float(z[nmax]), float(ext[nmax])
+    rows, meta = [], []
+    pz = []
+    for v in [float(z[max(0, nmax - k)]) for k in (3, 2, 1)] + [ze]:
+        if v not in pz:
+            pz.append(v)
+    targets = []
+    if ns == 0:
+        for m in range(24):
+            a = 0.3 + GOLDEN_ANGLE * m if m >= 2 else (0.0, 0.5 * math.pi)[m]
+            targets.append(("circle", math.cos(a), math.sin(a), e))
+    else:
+        inr = math.sqrt(3.0) / 2 * e
+        for ed in range(6):
+            b = math.radians(30 + 60 * ed)
+            for s in (-0.7, 0.0, 0.45):
+                targets.append(("edge", math.cos(b), math.sin(b), inr, -s * 0.5 * e * math.sin(b), s * 0.5 * e * math.cos(b)))
+            b = math.radians(60 * ed)
+            targets.append(("corner", math.cos(b), math.sin(b), e))
+    sc = float(np.spacing(e))
+    for Pz in pz:
+        for Pxy in ((0.0, 0.0), (0.3 * e, -0.2 * e)):
+            for tg in targets:
+                for k in EXIT_OFFSETS:
+                    tx = (tg[3] + k * sc) * tg[1] + (tg[4] if len(tg) > 4 else 0.0)
+                    ty = (tg[3] + k * sc) * tg[2] + (tg[5] if len(tg) > 4 else 0.0)
+                    for dz in EXIT_DZ:
+                        if Pz == ze:
+                            if Pxy != (0.0, 0.0):
+                                continue
+                            rows.append((tx, ty, Pz, 1e-3 * dz, 2e-3 * dz, dz))
+                        else:
+                            L = ze - Pz
+                            rows.append((Pxy[0], Pxy[1], Pz, (tx - Pxy[0]) / L * dz, (ty - Pxy[1]) / L * dz, dz))
+                        meta.append(dict(fam=tg[0], off=k, dz=dz, t0=(Pz == ze)))
+    return np.array(rows, dtype=np.float64), meta
+
+
+@functools.lru_cache(maxsize=None)
+def exit_grids():
+    """name -> dict(problem, profile, rows [n, 6] of pyprobe.EXIT_COLS, meta [n]): photons on the last three nodes and at z_end
+    itself, aimed at the exit hexagon's edges and corners (the circle for the mono-capillary)"""
+    out = {}
+    profs = march_profiles()
+    for name in ENTER_PROFILES:
+        prof = profs[name]
+        rows, meta = _exit_rows_of(name, prof)
+        out[name] = dict(problem=enter_grids()[name]["problem"], profile=prof, rows=rows, meta=meta)
+    return out

@@ -5,7 +5,9 @@
  * the product's own setup (pc_build_tables, pc_problem.h) of the problem passed in.  Op MARCH (tests/test_gpu_devmath_march.py) runs
  * one photon per thread through pc_launch_init, pc_march_step and pc_event_pre on the problem's whole profile, tables in global
  * memory.  Ops WALL, OUTER and HEX (tests/test_gpu_devmath_leak.py) run the wall search of pc_leak.h the same way; op FLIGHTS
- * (tests/test_gpu_devmath_flights.py) is op MARCH carried on through the reflections (pc_event_post).  Built by tests/devmath/pyprobe.py with the library's flags (polycap_amd._build.HIPFLAGS) into
+ * (tests/test_gpu_devmath_flights.py) is op MARCH carried on through the reflections (pc_event_post).  Ops SINCOS, UNIFORM, ENTER and EXIT
+ * (tests/test_gpu_devmath_ends.py) are the two ends of a photon's life: the sampler's sine / cosine and random stream, pc_launch_init
+ * and pc_in_exit_window.  Built by tests/devmath/pyprobe.py with the library's flags (polycap_amd._build.HIPFLAGS) into
  * tests/devmath/libpc_probe.so; never part of libpolycap.
  */
 #include <hip/hip_runtime.h>
@@ -224,6 +226,80 @@ int run_march(const pc_hip_problem *p, bool flights, int64_t n, const double *in
 	return rc;
 }
 
+/* one thread per row of an ends op (SINCOS, UNIFORM, ENTER, EXIT); the profile tables lie in global memory */
+template <int OP>
+__global__ void __launch_bounds__(64) pc_probe_ends_kernel(int64_t n, pc_params pm, int nodes, const double *__restrict__ tab,
+                                                           const pc_marg4 *__restrict__ mg, const double *__restrict__ in,
+                                                           double *__restrict__ out, int32_t *__restrict__ code)
+{
+	constexpr int WI = (OP == PC_PROBE_SINCOS) ? PC_PROBE_SINCOS_IN : (OP == PC_PROBE_UNIFORM) ? PC_PROBE_UNIFORM_IN
+	                 : (OP == PC_PROBE_ENTER) ? PC_PROBE_ENTER_IN : PC_PROBE_EXIT_IN;
+	constexpr int WO = (OP == PC_PROBE_SINCOS) ? PC_PROBE_SINCOS_OUT : (OP == PC_PROBE_UNIFORM) ? PC_PROBE_UNIFORM_OUT
+	                 : (OP == PC_PROBE_ENTER) ? PC_PROBE_ENTER_OUT : PC_PROBE_EXIT_OUT;
+	const int64_t i = (int64_t)blockIdx.x*blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	pc_tables T;
+	pc_probe_march_tables(T, tab, mg, nodes);
+	double o[WO];
+	int cd = 0;
+	pc_probe_ends_eval<OP>(T, pm, in + i*WI, o, &cd);
+	for (int j = 0; j < WO; j++) out[i*WO + j] = o[j];
+	code[i] = cd;
+}
+
+/* an ends op on n rows, tables and parameters of the whole profile of p: what the four entry points share */
+int run_ends(const pc_hip_problem *p, int op, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
+{
+	err[0] = 0;
+	pc_host_tables t;
+	std::string msg;
+	if (pc_build_tables(p, t, msg)) { snprintf(err, 256, "%s", msg.c_str()); return -2; }
+	if (pc_probe_ends_check(p, op, n, in_w, out_w, in)) { snprintf(err, 256, "invalid op, size, width or row (non-finite value, x outside [0, 2], not a 32-bit value, d too large)"); return -2; }
+	if (n == 0) return 0;
+	const size_t nodes = (size_t)p->nmax + 1;
+	std::vector<double> tab;
+	tab.reserve(PC_PROBE_MARCH_TAB*nodes);
+	const std::vector<double> *cols[PC_PROBE_MARCH_TAB] = {&t.z, &t.cap, &t.zh, &t.cap2, &t.hexd, &t.idz, &t.ext};
+	for (int c = 0; c < PC_PROBE_MARCH_TAB; c++) tab.insert(tab.end(), cols[c]->begin(), cols[c]->end());
+	int32_t *d_code = nullptr;
+	double *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
+	pc_marg4 *d_mg = nullptr;
+	int rc = 0;
+	hipError_t s = hipSuccess;
+#define PC_PROBE_TRY(call) do { if (s == hipSuccess) { s = (call); if (s != hipSuccess) snprintf(err, 256, "%s: %s", #call, hipGetErrorString(s)); } } while (0)
+	PC_PROBE_TRY(hipMalloc(&d_code, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMalloc(&d_in, n*in_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_out, n*out_w*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_tab, tab.size()*sizeof(double)));
+	PC_PROBE_TRY(hipMalloc(&d_mg, nodes*sizeof(pc_marg4)));
+	PC_PROBE_TRY(hipMemset(d_code, 0, n*sizeof(int32_t)));
+	PC_PROBE_TRY(hipMemset(d_out, 0, n*out_w*sizeof(double)));
+	PC_PROBE_TRY(hipMemcpy(d_in, in, n*in_w*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
+	PC_PROBE_TRY(hipMemcpy(d_mg, t.mg.data(), nodes*sizeof(pc_marg4), hipMemcpyHostToDevice));
+	if (s == hipSuccess) {
+		const dim3 blocks((unsigned)((n + 63)/64)), threads(64);
+		if (op == PC_PROBE_SINCOS)
+			hipLaunchKernelGGL(pc_probe_ends_kernel<PC_PROBE_SINCOS>, blocks, threads, 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		else if (op == PC_PROBE_UNIFORM)
+			hipLaunchKernelGGL(pc_probe_ends_kernel<PC_PROBE_UNIFORM>, blocks, threads, 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		else if (op == PC_PROBE_ENTER)
+			hipLaunchKernelGGL(pc_probe_ends_kernel<PC_PROBE_ENTER>, blocks, threads, 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		else
+			hipLaunchKernelGGL(pc_probe_ends_kernel<PC_PROBE_EXIT>, blocks, threads, 0, 0, n, t.pm, (int)nodes, d_tab, d_mg, d_in, d_out, d_code);
+		PC_PROBE_TRY(hipGetLastError());
+	}
+	PC_PROBE_TRY(hipDeviceSynchronize());
+	PC_PROBE_TRY(hipMemcpy(out, d_out, n*out_w*sizeof(double), hipMemcpyDeviceToHost));
+	PC_PROBE_TRY(hipMemcpy(code, d_code, n*sizeof(int32_t), hipMemcpyDeviceToHost));
+	if (s != hipSuccess) rc = -3;
+	const hipError_t f[5] = {hipFree(d_code), hipFree(d_in), hipFree(d_out), hipFree(d_tab), hipFree(d_mg)};
+	for (int j = 0; j < 5 && rc == 0; j++)
+		if (f[j] != hipSuccess) { snprintf(err, 256, "hipFree: %s", hipGetErrorString(f[j])); rc = -3; }
+#undef PC_PROBE_TRY
+	return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -365,6 +441,34 @@ __attribute__((visibility("default")))
 int probe_run_hex(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
 {
 	return run_leak(p, PC_PROBE_HEX, n, in, in_w, out, out_w, code, err);
+}
+
+/* Op SINCOS: pc_sincos_quadrant per row, in[n][1], out[n][2] */
+__attribute__((visibility("default")))
+int probe_run_sincos(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
+{
+	return run_ends(p, PC_PROBE_SINCOS, n, in, in_w, out, out_w, code, err);
+}
+
+/* Op UNIFORM: uniform #d of the stream (seed, slot, attempt) per row, in[n][6], out[n][1] */
+__attribute__((visibility("default")))
+int probe_run_uniform(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
+{
+	return run_ends(p, PC_PROBE_UNIFORM, n, in, in_w, out, out_w, code, err);
+}
+
+/* Op ENTER: everything pc_launch_init leaves, per row, in[n][9], out[n][PC_PROBE_ENTER_OUT] */
+__attribute__((visibility("default")))
+int probe_run_enter(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
+{
+	return run_ends(p, PC_PROBE_ENTER, n, in, in_w, out, out_w, code, err);
+}
+
+/* Op EXIT: pc_in_exit_window per row, in[n][6], out[n][1] */
+__attribute__((visibility("default")))
+int probe_run_exit(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code, char *err)
+{
+	return run_ends(p, PC_PROBE_EXIT, n, in, in_w, out, out_w, code, err);
 }
 
 } // extern "C"

@@ -17,6 +17,9 @@
  *
  * Op FLIGHTS (PC_PROBE_FLIGHTS) is op MARCH carried on through the reflections: after a hit pc_event_post mirrors the direction and
  * the next flight is marched, up to NB flights; see pc_probe_flights_eval.
+ *
+ * The ops of a photon's two ends (PC_PROBE_SINCOS, PC_PROBE_UNIFORM, PC_PROBE_ENTER, PC_PROBE_EXIT): the quadrant sine / cosine and
+ * the random stream of the sampler, everything pc_launch_init leaves, and pc_in_exit_window; see pc_probe_ends_eval.
  */
 #ifndef PC_PROBE_OPS_H
 #define PC_PROBE_OPS_H
@@ -121,10 +124,11 @@ enum { PC_PROBE_SEGMENT = 13, PC_PROBE_GEOM = 14, PC_PROBE_BOUNCE = 15, PC_PROBE
 #define PC_PROBE_SETUP_REJECT (-100)
 
 static inline int pc_probe_is_geom(int op) { return op >= PC_PROBE_SEGMENT && op < PC_PROBE_GEOM_END; }
-/* row widths per op (PC_PROBE_MARCH = 16, PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19, PC_PROBE_FLIGHTS = 20 and their
- * widths are defined with the ops, further down) */
-static inline int pc_probe_in_width(int op) { return (op == 20) ? 12 : (op == 17) ? 9 : (op == 18) ? 7 : (op == 19) ? 3 : (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
-static inline int pc_probe_out_width(int op) { return (op == 20) ? 22 + 24*12 + 5*128 : (op == 17) ? 20 + 17*96 : (op == 18) ? 4 : (op == 19) ? 2 : (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
+/* row widths per op (PC_PROBE_MARCH = 16, PC_PROBE_WALL = 17, PC_PROBE_OUTER = 18, PC_PROBE_HEX = 19, PC_PROBE_FLIGHTS = 20,
+ * PC_PROBE_SINCOS = 21, PC_PROBE_UNIFORM = 22, PC_PROBE_ENTER = 23, PC_PROBE_EXIT = 24 and their widths are defined with the ops,
+ * further down) */
+static inline int pc_probe_in_width(int op) { return (op == 21) ? 1 : (op == 22) ? 6 : (op == 23) ? 9 : (op == 24) ? 6 : (op == 20) ? 12 : (op == 17) ? 9 : (op == 18) ? 7 : (op == 19) ? 3 : (op == 16) ? 11 : (op == PC_PROBE_SEGMENT) ? PC_PROBE_SEG_IN : (pc_probe_is_geom(op) ? PC_PROBE_VEC_IN : PC_PROBE_IN); }
+static inline int pc_probe_out_width(int op) { return (op == 21) ? 2 : (op == 22) ? 1 : (op == 23) ? 31 : (op == 24) ? 1 : (op == 20) ? 22 + 24*12 + 5*128 : (op == 17) ? 20 + 17*96 : (op == 18) ? 4 : (op == 19) ? 2 : (op == 16) ? 22 + 4*64 : pc_probe_is_geom(op) ? PC_PROBE_GEOM_OUT : 2; }
 
 /* the product's setup (pc_build_tables) of the two-node profile (z0, z1), (cap0, cap1) of a SEGMENT row, glass and energies
  * of p; returns 0, or -1 when the setup rejects the profile */
@@ -580,6 +584,92 @@ static inline int pc_probe_flights_check(const pc_hip_problem *p, long long n, i
 		if (!(r[9] == 0. || r[9] == 1.)) return -2;
 		if (!(r[10] >= 0. && r[10] <= PC_PROBE_FLIGHTS_K) || r[10] != (double)(int)r[10]) return -2;
 		if (!(r[11] >= 1. && r[11] <= PC_PROBE_FLIGHTS_NB) || r[11] != (double)(int)r[11]) return -2;
+	}
+	return 0;
+}
+
+/* ------------------------------------------------------------------ the ops of a photon's two ends
+ * Numbered after FLIGHTS; rows of their own widths and an entry point each (probe_run_sincos / _uniform / _enter / _exit and their
+ * emul_ twins).  Product code only, called as the kernels call it.
+ *   SINCOS   in[1]  = x (0 <= x <= 2: the sampler passes [0, pi/2));  out[2] = sn, cs of pc_sincos_quadrant(x)
+ *   UNIFORM  in[6]  = seed_lo, seed_hi, slot_lo, slot_hi, attempt, d: 32-bit values carried in doubles, d <= PC_PROBE_UNIFORM_D
+ *            out[1] = uniform #d of the stream (seed, slot, attempt): pc_rng_init, then pc_rng_uniform d + 1 times, so that an odd
+ *                     d takes the second half of the block its predecessor drew
+ *   ENTER    in[9]  = x, y, z, dx, dy, dz, ex, ey, ez, as the first nine columns of op MARCH
+ *            out[31] = what pc_launch_init leaves (PC_PROBE_ENTER_OUT): the state it returned, rc, q, r (decoded from qr; 0 where it
+ *                     returned before qr was set: rc -2), qr, kx, ky, kn, bnd, i, P[3], d[3], E[3], first, lv, idzd, sx, sy, ox, oy,
+ *                     irefl, dtravel, C0, w[0], wset.  The photon is zeroed before the call (pc_probe_photon), so a field the call
+ *                     does not reach reads 0.  Tables and parameters as pc_build_tables makes them of the whole profile.
+ *   EXIT     in[6]  = Px, Py, Pz, dx, dy, dz;  out[1] = pc_in_exit_window on the problem's Pm (z_end, ext_end, mono)
+ * code = rc (ENTER), the answer (EXIT), 0 otherwise. */
+enum { PC_PROBE_SINCOS = 21, PC_PROBE_UNIFORM = 22, PC_PROBE_ENTER = 23, PC_PROBE_EXIT = 24 };
+#define PC_PROBE_SINCOS_IN 1
+#define PC_PROBE_SINCOS_OUT 2
+#define PC_PROBE_UNIFORM_IN 6
+#define PC_PROBE_UNIFORM_OUT 1
+#define PC_PROBE_UNIFORM_D 4095
+#define PC_PROBE_ENTER_IN 9
+#define PC_PROBE_ENTER_OUT 31
+#define PC_PROBE_EXIT_IN 6
+#define PC_PROBE_EXIT_OUT 1
+
+template <int OP>
+PC_HD void pc_probe_ends_eval(const pc_tables &T, const pc_params &Pm, const double *in, double *out, int *code)
+{
+	code[0] = 0;
+	if constexpr (OP == PC_PROBE_SINCOS) {
+		pc_sincos_quadrant(in[0], out[0], out[1]);
+	} else if constexpr (OP == PC_PROBE_UNIFORM) {
+		const uint64_t seed = ((uint64_t)(uint32_t)in[1] << 32) | (uint32_t)in[0], slot = ((uint64_t)(uint32_t)in[3] << 32) | (uint32_t)in[2];
+		const uint32_t d = (uint32_t)in[5];
+		pc_rng g;
+		pc_rng_init(g, seed, slot, (uint32_t)in[4]);
+		double u = 0.;
+		for (uint32_t j = 0; j <= d; j++) u = pc_rng_uniform(g);
+		out[0] = u;
+	} else if constexpr (OP == PC_PROBE_ENTER) {
+		pc_photon<1> ph;
+		const double zero[6] = {0., 0., 0., 0., 0., 0.};
+		pc_probe_photon(ph, zero);
+		const int st = pc_launch_init(T, Pm, ph, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8]);
+		const int has_qr = (st == PC_ST_MARCH || ph.rc == 2);
+		out[0] = st; out[1] = ph.rc;
+		out[2] = has_qr ? (double)((int)((unsigned)ph.qr >> 16) - 32768) : 0.;
+		out[3] = has_qr ? (double)((ph.qr & 0xffff) - 32768) : 0.;
+		out[4] = ph.qr; out[5] = ph.kx; out[6] = ph.ky; out[7] = ph.kn; out[8] = ph.bnd; out[9] = ph.i;
+		out[10] = ph.Px; out[11] = ph.Py; out[12] = ph.Pz; out[13] = ph.dx; out[14] = ph.dy; out[15] = ph.dz;
+		out[16] = ph.ex; out[17] = ph.ey; out[18] = ph.ez; out[19] = ph.first; out[20] = ph.lv;
+		out[21] = ph.idzd; out[22] = ph.sx; out[23] = ph.sy; out[24] = ph.ox; out[25] = ph.oy;
+		out[26] = ph.irefl; out[27] = ph.dtravel; out[28] = ph.C0; out[29] = ph.w[0]; out[30] = ph.wset;
+		code[0] = ph.rc;
+	} else {
+		pc_photon<1> ph;
+		const double v[6] = {in[3], in[4], in[5], 0., 0., 0.};
+		pc_probe_photon(ph, v);
+		ph.Px = in[0]; ph.Py = in[1]; ph.Pz = in[2];
+		const int ok = pc_in_exit_window(Pm, ph);
+		out[0] = ok;
+		code[0] = ok;
+	}
+}
+
+/* host-side checks of an ends op, in both builds, before anything runs: op, widths, every value finite; SINCOS: 0 <= x <= 2;
+ * UNIFORM: whole numbers below 2^32, d <= PC_PROBE_UNIFORM_D (a lane draws d + 1 uniforms) */
+static_assert(PC_PROBE_ENTER == 23 && PC_PROBE_ENTER_OUT == 31, "widths of the ends ops as pc_probe_in_width / pc_probe_out_width state them");
+static inline int pc_probe_ends_check(const pc_hip_problem *p, int op, long long n, int in_w, int out_w, const double *in)
+{
+	if (op < PC_PROBE_SINCOS || op > PC_PROBE_EXIT || n < 0 || in_w != pc_probe_in_width(op) || out_w != pc_probe_out_width(op)) return -2;
+	if (p->nmax < 1) return -2;
+	for (long long i = 0; i < n; i++) {
+		const double *r = in + i*in_w;
+		for (int j = 0; j < in_w; j++)
+			if (!std::isfinite(r[j])) return -2;
+		if (op == PC_PROBE_SINCOS && !(r[0] >= 0. && r[0] <= 2.)) return -2;
+		if (op == PC_PROBE_UNIFORM) {
+			for (int j = 0; j < in_w; j++)
+				if (!(r[j] >= 0. && r[j] <= 4294967295.) || r[j] != (double)(uint32_t)r[j]) return -2;
+			if (r[5] > (double)PC_PROBE_UNIFORM_D) return -2;
+		}
 	}
 	return 0;
 }

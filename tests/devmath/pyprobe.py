@@ -67,7 +67,8 @@ def lib():
         L.probe_run_march.argtypes = [C.POINTER(ProblemS), C.c_int64, c_double_p, C.c_int, c_double_p, C.c_int,
                                       C.POINTER(C.c_int32), C.c_char_p]
         L.probe_run_march.restype = C.c_int
-        for f in (L.probe_run_wall, L.probe_run_outer, L.probe_run_hex, L.probe_run_flights):
+        for f in (L.probe_run_wall, L.probe_run_outer, L.probe_run_hex, L.probe_run_flights,
+                  L.probe_run_sincos, L.probe_run_uniform, L.probe_run_enter, L.probe_run_exit):
             f.argtypes = L.probe_run_march.argtypes
             f.restype = C.c_int
         _LIB = L
@@ -264,6 +265,48 @@ def run_outer(problem, x, device=True):
 def run_hex(problem, x, device=True):
     """Op HEX on the rows x [n, 3] = x, y, zz: (out [n, 2] = q, r; code [n])"""
     return _run_leak(problem, "hex", x, HEX_IN, HEX_OUT, device)
+
+
+# the ops of a photon's two ends (probe_ops.h): sampler primitives, pc_launch_init, pc_in_exit_window
+SINCOS_IN, SINCOS_OUT = 1, 2
+UNIFORM_IN, UNIFORM_OUT, UNIFORM_D = 6, 1, 4095
+UNIFORM_COLS = ("seed_lo", "seed_hi", "slot_lo", "slot_hi", "attempt", "d")
+ENTER_IN = 9
+ENTER_COLS = MARCH_COLS[:9]
+ENTER_OUT_COLS = ("state", "rc", "q", "r", "qr", "kx", "ky", "kn", "bnd", "i", "Px", "Py", "Pz", "dx", "dy", "dz", "ex", "ey", "ez",
+                  "first", "lv", "idzd", "sx", "sy", "ox", "oy", "irefl", "dtravel", "C0", "w0", "wset")
+ENTER_OUT = len(ENTER_OUT_COLS)
+EXIT_IN, EXIT_OUT = 6, 1
+EXIT_COLS = ("Px", "Py", "Pz", "dx", "dy", "dz")
+
+
+def run_sincos(problem, x, device=True):
+    """Op SINCOS on x [n]: out [n, 2] = sn, cs of pc_sincos_quadrant"""
+    return _run_leak(problem, "sincos", x, SINCOS_IN, SINCOS_OUT, device)[0]
+
+
+def uniform_rows(seed, slot, attempt, d):
+    """rows of op UNIFORM from Python integers (broadcast): the 64-bit seed and slot split into 32-bit halves"""
+    seed, slot, attempt, d = np.broadcast_arrays(np.asarray(seed, dtype=object), np.asarray(slot, dtype=object),
+                                                 np.asarray(attempt, dtype=object), np.asarray(d, dtype=object))
+    M = 0xffffffff
+    return np.array([[int(s) & M, int(s) >> 32, int(t) & M, int(t) >> 32, int(a), int(k)]
+                     for s, t, a, k in zip(seed.ravel(), slot.ravel(), attempt.ravel(), d.ravel())], dtype=np.float64)
+
+
+def run_uniform(problem, x, device=True):
+    """Op UNIFORM on the rows x [n, 6] (UNIFORM_COLS; uniform_rows): out [n] = uniform #d of the stream"""
+    return _run_leak(problem, "uniform", x, UNIFORM_IN, UNIFORM_OUT, device)[0][:, 0]
+
+
+def run_enter(problem, x, device=True):
+    """Op ENTER on the rows x [n, 9] (ENTER_COLS): (out [n, ENTER_OUT] of ENTER_OUT_COLS, code [n] = rc)"""
+    return _run_leak(problem, "enter", x, ENTER_IN, ENTER_OUT, device)
+
+
+def run_exit(problem, x, device=True):
+    """Op EXIT on the rows x [n, 6] (EXIT_COLS): out [n] = pc_in_exit_window"""
+    return _run_leak(problem, "exit", x, EXIT_IN, EXIT_OUT, device)[0][:, 0]
 
 
 def wall_trail(row):

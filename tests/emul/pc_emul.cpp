@@ -452,6 +452,46 @@ int emul_probe_run_hex(const pc_hip_problem *p, int64_t n, const double *in, int
 	return 0;
 }
 
+/* the host builds of probe.hip's probe_run_sincos, _uniform, _enter and _exit: the two ends of a photon's life */
+static int emul_probe_run_ends(const pc_hip_problem *p, int op, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	if (pc_probe_ends_check(p, op, n, in_w, out_w, in)) return -2;
+	for (int64_t i = 0; i < n; i++) {
+		int cd = 0;
+		const double *x = in + i*in_w;
+		double *o = out + i*out_w;
+		if (op == PC_PROBE_SINCOS) pc_probe_ends_eval<PC_PROBE_SINCOS>(E.T, E.t.pm, x, o, &cd);
+		else if (op == PC_PROBE_UNIFORM) pc_probe_ends_eval<PC_PROBE_UNIFORM>(E.T, E.t.pm, x, o, &cd);
+		else if (op == PC_PROBE_ENTER) pc_probe_ends_eval<PC_PROBE_ENTER>(E.T, E.t.pm, x, o, &cd);
+		else pc_probe_ends_eval<PC_PROBE_EXIT>(E.T, E.t.pm, x, o, &cd);
+		code[i] = cd;
+	}
+	return 0;
+}
+
+int emul_probe_run_sincos(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	return emul_probe_run_ends(p, PC_PROBE_SINCOS, n, in, in_w, out, out_w, code);
+}
+
+int emul_probe_run_uniform(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	return emul_probe_run_ends(p, PC_PROBE_UNIFORM, n, in, in_w, out, out_w, code);
+}
+
+int emul_probe_run_enter(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	return emul_probe_run_ends(p, PC_PROBE_ENTER, n, in, in_w, out, out_w, code);
+}
+
+int emul_probe_run_exit(const pc_hip_problem *p, int64_t n, const double *in, int in_w, double *out, int out_w, int32_t *code)
+{
+	return emul_probe_run_ends(p, PC_PROBE_EXIT, n, in, in_w, out, out_w, code);
+}
+
 /* Test-only accessor: the leak path's tables of p, node[(nmax + 1) x 4] = stp, istp, dr.d1, dr.d2 (every float converts exactly) */
 int emul_leak_tables(const pc_hip_problem *p, double *node)
 {

@@ -59,7 +59,8 @@ def lib():
         L.emul_probe_run_march.restype = C.c_int
         L.emul_march_tables.argtypes = [C.POINTER(ProblemS), c_double_p, c_double_p]
         L.emul_march_tables.restype = C.c_int
-        for f in (L.emul_probe_run_outer, L.emul_probe_run_hex, L.emul_probe_run_flights):
+        for f in (L.emul_probe_run_outer, L.emul_probe_run_hex, L.emul_probe_run_flights,
+                  L.emul_probe_run_sincos, L.emul_probe_run_uniform, L.emul_probe_run_enter, L.emul_probe_run_exit):
             f.argtypes = L.emul_probe_run_march.argtypes
             f.restype = C.c_int
         L.emul_leak_tables.argtypes = [C.POINTER(ProblemS), c_double_p]
