@@ -119,6 +119,19 @@ struct pc_tables {
 #define PC_L2 25
 #endif
 #define PC_MARGIN_INFLATE 1.0000038f   /* 1 + 2^-18 */
+#ifndef PC_WALK_PIPE
+#define PC_WALK_PIPE 0     /* pc_event_pre's certified walk: 0 a node's loads after the test of the node before, 1 one node ahead,
+                            * 2 all PC_L1 nodes at once.  Neither pipelined form paid (profiles/trace_loop_ab.txt) */
+#endif
+#ifndef PC_FUSE_FIRST
+#define PC_FUSE_FIRST 0    /* pc_event<.., .., true>: a visit that ends in a reflection takes the next flight's first step itself
+                            * (pc_march_first_ok, the tables read again: kept in registers across the reflection they made the
+                            * launching-wave kernel spill).  Slower than without (profiles/trace_loop_ab.txt);
+                            * tests/test_trace_loop_cpu.py holds the fused step to the unfused path */
+#endif
+#ifndef PC_ONE_MARGIN_TEST
+#define PC_ONE_MARGIN_TEST 1   /* pc_march_ok: the far node is compared once, against the margin of the stride taken */
+#endif
 #ifndef PC_LV_LATER
 #ifndef PC_CREEP
 #define PC_CREEP 1     /* a failed probe at stride PC_L1 goes to the EVENT phase, which walks the last segments itself (pc_event_pre) */
@@ -568,7 +581,10 @@ PC_HD int pc_launch_init(const pc_tables &T, const pc_params &Pm, pc_photon<NE> 
  * adj = dRmax^2/4 + m with m ~ 1e6 x the rounding error of g.  Anything else goes to pc_event().
  * Cost: 6 FMA + 3 LDS reads per node.
  */
-template <int NE>
+/* BND = false: the caller knows that ph.bnd is 0 (the hexagon tests of a boundary capillary are left out of the code).
+ * ONE_TEST (the launching-wave kernel's tight loop, with PC_ONE_MARGIN_TEST): the far node is compared once, against the margin
+ * of the stride taken -- the same truth value from fewer lane-mask instructions; every other caller compiles to what it was. */
+template <int NE, bool BND = true, bool ONE_TEST = false>
 PC_HD int pc_march_ok(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph)
 {
 	/* Block certificate (stride L > 1).  Over nodes i..i+L let zh_c, R_c be the chords of zh and cap between the two
@@ -615,8 +631,15 @@ PC_HD int pc_march_ok(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph
 	double qy = fma(-ph.ky, zh1, fma(ph.sy, z1, ph.oy));
 	double C1 = fma(qx, qx, fma(qy, qy, -c2));
 	const float C1f = (float)C1, adjf = Pm.adjf;
-	bool ok = (s2 & (C1f < -m2)) | (s1 & (C1f < -m1)) | (!s2 & !s1 & (C0f < -adjf) & (C1f < -adjf));
-	if (ph.bnd) {
+	bool ok;
+	if (ONE_TEST && PC_ONE_MARGIN_TEST) {
+		/* the far node against the margin of the stride taken; the single segment tests its start node as well */
+		const float msel = s2 ? m2 : (s1 ? m1 : adjf);
+		ok = (C1f < -msel) & (s2 | s1 | (C0f < -adjf));
+	} else {
+		ok = (s2 & (C1f < -m2)) | (s1 & (C1f < -m1)) | (!s2 & !s1 & (C0f < -adjf) & (C1f < -adjf));
+	}
+	if (BND && ph.bnd) {
 		/* boundary capillary (or mono-capillary; always level 0): the hexagon tests of the visit are not implied, do them:
 		 * axis at both nodes (src/polycap-capil.c:1263) and the ray at z_i (:1296-1308) */
 		double z0 = T.z[i0], zh0 = T.zh[i0], h0 = T.hexd[i0], h1 = T.hexd[i1];
@@ -1192,6 +1215,34 @@ PC_HD int pc_event_pre(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &p
 		 * Nodes i+1 .. i+PC_L1 exist: the probe looked at the last of them (which may still pass the single-segment margin). */
 		ph.lv = 0;
 		const float adjf = Pm.adjf;
+#if PC_WALK_PIPE == 2
+		/* the ray is fixed during the walk, so the value at every node of the probe's block depends on the tables only: all
+		 * PC_L1 nodes are loaded and evaluated at once (one LDS wait instead of up to PC_L1, one behind the other), and the walk
+		 * is a chain of selects over them -- the values, tests and their order are those of the loop below */
+		float Cf[PC_L1];
+#pragma unroll
+		for (int k = 1; k <= PC_L1; k++) Cf[k - 1] = (float)pc_node_C(T, ph, i + k);
+		float c0 = ph.C0;
+		bool go = true;
+#pragma unroll
+		for (int k = 1; k <= PC_L1; k++) {
+			go = go & (c0 < -adjf) & (Cf[k - 1] < -adjf);
+			c0 = go ? Cf[k - 1] : c0;
+			i += go ? 1 : 0;
+		}
+		ph.C0 = c0;
+#elif PC_WALK_PIPE == 1
+		/* node k+1's loads are issued before node k's test */
+		double Cn = pc_node_C(T, ph, i + 1);
+#pragma unroll
+		for (int k = 1; k <= PC_L1; k++) {
+			const double C = Cn;
+			if (k < PC_L1) Cn = pc_node_C(T, ph, i + 2);
+			if (!((ph.C0 < -adjf) & ((float)C < -adjf))) break;
+			ph.C0 = (float)C;
+			i++;
+		}
+#else
 #pragma unroll
 		for (int k = 1; k <= PC_L1; k++) {
 			const double C = pc_node_C(T, ph, i + 1);
@@ -1199,6 +1250,7 @@ PC_HD int pc_event_pre(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &p
 			ph.C0 = (float)C;
 			i++;
 		}
+#endif
 		ph.i = i;
 	}
 	if (i >= nmax) { ph.rc = 1; return PC_ST_DONE; }           /* :1312-1313 -> launch returns 1 */
@@ -1273,13 +1325,25 @@ PC_HD int pc_event_post(const pc_params &Pm, pc_photon<NE> &ph, const pc_hit &h,
 }
 
 /* FASTF: the weights of a register-weight kernel are multiplied with pc_fresnel3s (source runs) instead of FORMs 0/1 */
-template <int NE, bool FASTF = false>
+/* FUSE_FIRST (the launching-wave kernel, with PC_FUSE_FIRST): the first step of the flight that a reflection begins is taken
+ * here, where the hit lies inside the segment visited (h.ix == i: the next flight's first segment is this one), the capillary is
+ * no boundary one and the photon flies forward.  Such a lane leaves as pc_march_step would leave it after its first step: MARCH
+ * with first = 0 at node i + 1, or EVENT where the certificate fails.  Every other lane keeps first = 1 and takes that step in
+ * the MARCH phase (pc_march_step), as all lanes do without FUSE_FIRST. */
+template <int NE, bool FASTF = false, bool FUSE_FIRST = false>
 PC_HD int pc_event(const pc_tables &T, const pc_params &Pm, const pc_energy_const *EC, pc_photon<NE> &ph)
 {
 	pc_hit h;
 	int st = pc_event_pre(T, Pm, ph, h);
 	if (st != PC_ST_REFLECT) return st;
 	int r = pc_reflect<NE, FASTF>(Pm, EC, ph, h.nx, h.ny, h.nz);
+	if (FUSE_FIRST && PC_FUSE_FIRST) {
+		const int iv = ph.i;
+		st = pc_event_post(Pm, ph, h, r);
+		if ((st == PC_ST_MARCH) & (h.ix == iv) & !ph.bnd & (ph.dz >= 0.) & !Pm.literal)
+			st = pc_march_first_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
+		return st;
+	}
 	return pc_event_post(Pm, ph, h, r);
 }
 
@@ -1299,14 +1363,23 @@ PC_HD int pc_march_step(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &
 /* MARCH step of the tight loop: the lane is known not to sit on the first segment of a trace call.  RC_LATER: the caller
  * sets ph.rc = 1 itself on the lanes that come back DONE (the end of the optic is the only way to DONE from here), once after
  * a burst of steps: as a store in every step the return code costs the step three copies to merge its two ways out. */
-template <int NE, bool RC_LATER = false>
+/* AT_ADVANCE: the caller keeps no lane in MARCH at the last node (precondition: ph.i < nmax), and the step that advances a
+ * photon to it returns DONE itself: one test on the way out, a select, instead of a lane mask around the step on the way in.
+ * A stride that does not fit before the end of the profile is never taken (infinite margin), so ph.i never passes nmax. */
+template <int NE, bool RC_LATER = false, bool BND = true, bool AT_ADVANCE = false, bool ONE_TEST = false>
 PC_HD int pc_march_step_hot(const pc_tables &T, const pc_params &Pm, pc_photon<NE> &ph)
 {
+	if (AT_ADVANCE) {
+		const int go_on = pc_march_ok<NE, BND, ONE_TEST>(T, Pm, ph);
+		const bool end = ph.i >= Pm.nmax;
+		if (!RC_LATER && end) ph.rc = 1;
+		return end ? PC_ST_DONE : (go_on ? PC_ST_MARCH : PC_ST_EVENT);
+	}
 	if (ph.i >= Pm.nmax) {
 		if (!RC_LATER) ph.rc = 1;
 		return PC_ST_DONE;
 	}
-	return pc_march_ok(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
+	return pc_march_ok<NE, BND, ONE_TEST>(T, Pm, ph) ? PC_ST_MARCH : PC_ST_EVENT;
 }
 
 /* ------------------------------------------------------------------ exit window + image record

@@ -36,6 +36,18 @@
 #ifndef PC3_SLEEP
 #define PC3_SLEEP 127          /* the launching wave waits for room in the rings 90 % of the time: long naps (8128 clocks) */
 #endif
+#ifndef PC3_DONE_AT_ADVANCE
+#define PC3_DONE_AT_ADVANCE 0  /* a photon is DONE where it is moved to the last node (march step, first step, visit), not where the
+                                * next step finds it there: no lane in MARCH stands at the last node, and the step has no test
+                                * on its way in (pc_march_step_hot, AT_ADVANCE).  Did not pay (profiles/trace_loop_ab.txt) */
+#endif
+#ifndef PC3_BND_PER_BURST
+#define PC3_BND_PER_BURST 0    /* the march burst chooses once, for the wave, whether its steps hold the boundary-capillary block.
+                                * Did not pay (profiles/trace_loop_ab.txt) */
+#endif
+#ifndef PC3_POLL_WHEN_NEEDED
+#define PC3_POLL_WHEN_NEEDED 1 /* a tracing wave reads its ring's tail at the head of a turn only when a lane waits for a photon */
+#endif
 
 /* phases of a tracing wave's loop */
 enum { PC3_PH_IDLE = 0, PC3_PH_MARCH = 1, PC3_PH_EVENT = 2, PC3_PH_NEW = 3, PC3_PH_WAIT = 4 };
@@ -407,16 +419,44 @@ pc_trace_producer_kernel(pc_kargs a)
 		unsigned int q_head = 0, r_tail = 0;      /* this wave's ends of its two rings */
 		auto march_burst = [&](int nM, bool do_new, int nE) {
 			const bool marching = (state == LS_MARCH);
-			if (state == LS_MARCH && ph.first)
+			if (state == LS_MARCH && ph.first) {
 				state = pc_march_step<1, true>(T, Pm, ph);      /* RC_LATER: see the end of the burst */
+#if PC3_DONE_AT_ADVANCE
+				if (state == LS_MARCH && ph.i >= Pm.nmax) state = LS_DONE;      /* the first step reached the last node */
+#endif
+			}
+#if PC3_BND_PER_BURST
+			/* no lane changes its capillary inside a burst: whether the steps need the hexagon tests of boundary capillaries is
+			 * decided here, once and for the wave (a scalar branch between two copies of the unrolled steps), instead of by a
+			 * lane mask inside every step.  With PC3_ROUTE_BND only the last tracing wave holds such lanes as a rule. */
+			const bool any_bnd = __ballot(state == LS_MARCH && ph.bnd) != 0ull;
+#endif
 			for (int b = 0; b < a.march_burst; b++) {
 				unsigned int lanes_in_burst = 0;
+#if PC3_BND_PER_BURST
+				if (any_bnd) {
+#pragma unroll
+					for (int u = 0; u < PC_MARCH_UNROLL; u++) {
+						if (STATS) lanes_in_burst += (unsigned)__popcll(__ballot(state == LS_MARCH));
+						if (state == LS_MARCH)
+							state = pc_march_step_hot<1, true, true, PC3_DONE_AT_ADVANCE != 0, true>(T, Pm, ph);
+					}
+				} else {
+#pragma unroll
+					for (int u = 0; u < PC_MARCH_UNROLL; u++) {
+						if (STATS) lanes_in_burst += (unsigned)__popcll(__ballot(state == LS_MARCH));
+						if (state == LS_MARCH)
+							state = pc_march_step_hot<1, true, false, PC3_DONE_AT_ADVANCE != 0, true>(T, Pm, ph);
+					}
+				}
+#else
 #pragma unroll
 				for (int u = 0; u < PC_MARCH_UNROLL; u++) {
 					if (STATS) lanes_in_burst += (unsigned)__popcll(__ballot(state == LS_MARCH));
 					if (state == LS_MARCH)
-						state = pc_march_step_hot<1, true>(T, Pm, ph);
+						state = pc_march_step_hot<1, true, true, PC3_DONE_AT_ADVANCE != 0, true>(T, Pm, ph);
 				}
+#endif
 				const int cM = __popcll(__ballot(state == LS_MARCH));
 				if (STATS) { st_march += PC_MARCH_UNROLL; st_march_l += lanes_in_burst; }
 				if (cM == 0) break;
@@ -436,7 +476,14 @@ pc_trace_producer_kernel(pc_kargs a)
 		while (run) {
 			const int nM = __popcll(__ballot(state == LS_MARCH)), nE = __popcll(__ballot(state == LS_EVENT));
 			const int nD = __popcll(__ballot(state == LS_DONE)), nQ = __popcll(__ballot(state == LS_NEED_SLOT));
+#if PC3_POLL_WHEN_NEEDED
+			/* `avail` enters the turn only through min(nQ, avail) and through the empty-wave test, which needs nQ == 64: with no lane
+			 * waiting for a photon the ring's tail is not read (an LDS round trip at the head of every turn), and the phase chosen
+			 * is the same.  nQ is wave-uniform: the load stands under a scalar branch with every lane active. */
+			const int avail = (nQ > 0) ? (int)(pc3_load_uniform(&ctl.q_tail[c]) - q_head) : 0;
+#else
 			const int avail = (int)(pc3_load_uniform(&ctl.q_tail[c]) - q_head);
+#endif
 			const int nN = nD + ((nQ < avail) ? nQ : avail);
 			const bool do_new = (nN >= a.new_threshold) || (nM == 0 && nE == 0);
 			int phase;
@@ -449,8 +496,14 @@ pc_trace_producer_kernel(pc_kargs a)
 				march_burst(nM, do_new, nE);
 			if (phase == PC3_PH_EVENT) {
 				st_event += 1; st_event_l += (unsigned)nE;
-				if (state == LS_EVENT)
-					state = pc_event<1, true>(T, Pm, a.ec, ph);
+				if (state == LS_EVENT) {
+					state = pc_event<1, true, true>(T, Pm, a.ec, ph);
+#if PC3_DONE_AT_ADVANCE
+					/* a visit without a hit (or its fused first step) that moved the photon to the last node: the end of the optic,
+					 * which the next march step would have found on its way in (pc_march_step: rc = 1, DONE) */
+					if (state == LS_MARCH && ph.i >= Pm.nmax) { ph.rc = 1; state = LS_DONE; }
+#endif
+				}
 			}
 			if (phase == PC3_PH_NEW) {
 				/* ---------------- NEW: finalise finished photons, pop launched ones */
