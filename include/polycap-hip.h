@@ -573,6 +573,41 @@ POLYCAP_EXTERN int pc_hip_select_parse(const char *value, pc_hip_select_cut *cut
  *                       fit in 128 MiB, at least 1
  * Both exist so that tests reach many tiles and many chunks at small sizes. */
 POLYCAP_EXTERN int pc_hip_select_gather(pc_hip_select *select, int kind, int64_t first, int64_t count, double *records, int64_t *positions);
+/* ---- draws: an unweighted sample of the entries a selection keeps (pc_draw.h).  A sample-side Monte Carlo, a detector model or a
+ * second run started from explicit photons wants N photons of equal weight, drawn in proportion to the transmitted weight at one
+ * energy; a gather returns weighted rows.  Systematic resampling in exact integers, on the device, of what the run left there.
+ *
+ * The contract:
+ *   inputs     a selection applied for `kind`; an energy index `energy` of the problem; a sample size n_draw = N, 1 <= N <= 2^31 - 1;
+ *              a phase r (any uint32)
+ *   entries    the entries of the kind in the position order of pc_hip_select_gather (the members of a group one after the other,
+ *              positions global).  Entry i has V_i = W_i[energy] = round_half_even(w[energy] * 2^32) (the spot maps' q(w)) where its
+ *              mask byte is set and 0 otherwise; C_i = V_0 + ... + V_i; T = C_{n-1}, which is passed_w[kind][energy] of
+ *              pc_hip_select_read exactly
+ *   draw k     0 <= k < N: t_k = floor((k * 2^32 + r) * T / (N * 2^32)), a 128-bit product, 0 <= t_k < T; pos_k = the smallest i with
+ *              C_i > t_k.  Positions do not decrease with k; entry i is drawn floor(N V_i / T) or ceil(N V_i / T) times; an entry with
+ *              V_i = 0 (one the selection rejects, one without weight at that energy) is never drawn
+ *   result     the draws [first, first + count) are copied to the host
+ *   records    [count][PC_HIP_N_PLANES + n_energies] for kind 0, [count][PC_HIP_LEAK_HDR + n_energies] for the leak kinds: row k - first
+ *              bit for bit the row pc_hip_select_gather / pc_hip_transmission_records / pc_hip_leak_events has at pos_k, copied as
+ *              64-bit patterns
+ *   positions  optional: [count] pos_k
+ *   total      optional: *total = T, so that the caller knows that every draw stands for T * 2^-32 / N of weight per started photon;
+ *              it is set whenever the arguments pass, count 0 included
+ *   count 0    valid, touches nothing beyond *total; records and positions may then be NULL
+ *   refusals   PC_HIP_ERR_INVALID with a message that names the function and the field, nothing launched, the selection and what it
+ *              has cached unchanged: the refusals of pc_hip_select_gather (select NULL; kind; first < 0; count < 0; records NULL with
+ *              count > 0; not applied; stale mask); energy outside the problem; n_draw outside 1 .. 2^31 - 1; first + count > n_draw;
+ *              T == 0 (no weight to draw from)
+ *   cost       device memory and time grow with the entries and with count, never with N: a window of 100 draws at the end of
+ *              N = 2^31 - 1 costs what it costs at the start
+ *   blocking   as pc_hip_select_gather
+ * The result depends on the entries, their order, the mask, energy, N and r only: not on "gather_tile" or "gather_chunk_rows" (the two
+ * options of the gathers, which the draws share), not on how a window is split into calls, on "run_parts", or on records against
+ * slot-ordered planes.  The sums of V over the tiles and their scan are kept per member for one (kind, energy, tile) until that kind
+ * is applied again; tile sums that do not add up to the apply's passed_w are PC_HIP_ERR_RUNTIME. */
+POLYCAP_EXTERN int pc_hip_select_draw(pc_hip_select *select, int kind, int32_t energy, int64_t n_draw, uint32_t phase, int64_t first,
+	int64_t count, double *records, int64_t *positions, uint64_t *total);
 /* ---- standard errors of the tallies: a second exact sum per cell, of the squared weights, kept in the same pass as the first, so
  * that every bin of a spot map, a histogram or a joint histogram and the transmission of a selection carry their Monte Carlo error.
  *
@@ -840,6 +875,23 @@ POLYCAP_EXTERN int pc_transmission_efficiencies_get_select(void *efficiencies, i
  * /Select/<Kind>_Positions (int64 [n_rows]) per kind present, and /Select/Records_Limit. */
 POLYCAP_EXTERN int pc_transmission_efficiencies_get_select_records(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles,
 	double **records, int64_t **positions, void *error);
+
+/* An unweighted sample of the beam: POLYCAP_DRAW="n=100000,energy=3,phase=12345" (n: the sample size, 1 .. 2^31 - 1; energy: an index
+ * into the source's energies, default 0; phase: a uint32, default 0, so that the call stays reproducible; an unknown key, a missing n,
+ * a value outside those ranges or an empty value is POLYCAP_ERROR_INVALID_ARGUMENT naming the item, before any device is used and
+ * behind the refusals of every other variable) makes the result carry, for every kind the call has (exit photons always, extleak and
+ * intleak for leak_calc runs), the n draws of pc_hip_select_draw at that energy: through the selection of POLYCAP_SELECT when it is
+ * set, through one that every entry passes otherwise (the result then reports no selection).  A kind without weight at that energy
+ * carries no rows and is not an error.  It works with POLYCAP_IMAGES=0 and POLYCAP_HIP_DEVICES; a POLYCAP_IMAGES=0 run whose exit data
+ * exceed POLYCAP_SPOT_SHARE of the device's memory, which is traced as several slot ranges, has no one beam on the device and is
+ * refused with POLYCAP_ERROR_INVALID_ARGUMENT.  Returns 1 and (free each array with polycap_free; any pointer but n_rows may be NULL):
+ * *n_rows = n or 0, *row_doubles, *records [n_rows][row_doubles] and *positions [n_rows] as in _get_select_records, *total = T of the
+ * kind (a draw stands for T * 2^-32 / n of weight per started photon), and the request in *n, *energy, *phase.  A result made without
+ * the variable, or a kind the call does not have, fails with POLYCAP_ERROR_INVALID_ARGUMENT.  write_hdf5 adds the group /Draw with the
+ * attributes n, energy_index, energy_keV, phase and, per kind present, <Kind>_total (uint64) and <Kind>_weight, and the datasets
+ * /Draw/<Kind>_Records and /Draw/<Kind>_Positions of every kind that has rows. */
+POLYCAP_EXTERN int pc_transmission_efficiencies_get_draw(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,
+	int64_t **positions, uint64_t *total, int64_t *n, int32_t *energy, uint32_t *phase, void *error);
 
 /* Standard errors of the tallies through the public call: POLYCAP_TALLY_STDERR=1 (0 or unset: none; anything else is
  * POLYCAP_ERROR_INVALID_ARGUMENT; it is not POLYCAP_STDERR, whose outputs stay as they are) makes every tally of the call (POLYCAP_SPOT,

@@ -7,6 +7,7 @@ The package is a thin Python layer over libpolycap.so (host C + hand-written HIP
   * polycap_amd.hip.Histograms    -- exact 1-D histograms of per-photon quantities per energy (FWHM, encircled energy), on the GPU;
   * polycap_amd.hip.Selection -- cuts on per-photon quantities evaluated on the GPU, through which any of the tallies is filled;
     Selection.gather fetches the per-photon data of the selected photons alone, compacted in order on the GPU;
+    Selection.draw an unweighted sample of them, n photons of equal weight, resampled in exact integers on the GPU;
   * polycap_amd.hip.JointHistograms -- exact joint 2-D histograms of two per-photon quantities per energy (phase space), on the GPU;
   * polycap_amd.hip.BeamMoments   -- exact exit-beam moments per energy (focal distance, waist, divergence), on the GPU;
   * TraceContext.scan / scan_points -- transmission per source position (alignment curves, focal spot, depth response) in one
@@ -19,7 +20,7 @@ The package is a thin Python layer over libpolycap.so (host C + hand-written HIP
 There is no CPU implementation of the trace path in this package.
 """
 from ._cabi import Problem, lib  # noqa: F401
-from .hip import TraceContext, TraceGroup, SpotMap, BeamMoments, Histograms, JointHistograms, Selection, select_cuts, select_parse, joint_marginal, joint_parse, hist_fwhm, hist_quantile, beam_params, HipError, device_count, efficiencies, efficiency_stderr, fixed_to_double, IMG_FIELDS  # noqa: F401
+from .hip import TraceContext, TraceGroup, SpotMap, BeamMoments, Histograms, JointHistograms, Selection, select_cuts, select_parse, select_all, joint_marginal, joint_parse, hist_fwhm, hist_quantile, beam_params, HipError, device_count, efficiencies, efficiency_stderr, fixed_to_double, IMG_FIELDS  # noqa: F401
 from .hip import scan_points, scan_efficiencies  # noqa: F401
 from .hip import tally_stderr, select_transmission, pairs_sum  # noqa: F401
 from .hip import relay_efficiencies, relay_placement_valid, RELAY_COUNTERS  # noqa: F401

@@ -316,6 +316,8 @@ def lib():
     L.pc_hip_select_info.restype = C.c_int
     L.pc_hip_select_gather.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_double_p, c_int64_p]
     L.pc_hip_select_gather.restype = C.c_int
+    L.pc_hip_select_draw.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, c_double_p, c_int64_p, P(C.c_uint64)]
+    L.pc_hip_select_draw.restype = C.c_int
     for stem in ("spot", "beam", "hist", "joint"):
         fn = getattr(L, "pc_hip_%s_add_selected" % stem)
         fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]

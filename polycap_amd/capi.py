@@ -141,6 +141,8 @@ def _lib():
                                                              [P(_dp), P(_dp), P(C.c_int64), epp]),
         "pc_transmission_efficiencies_get_select_squares": (C.c_int, [vp, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)), P(_dp), P(_dp), epp]),
         "pc_transmission_efficiencies_get_select_records": (C.c_int, [vp, C.c_int, P(C.c_int64), P(C.c_int32), P(_dp), P(P(C.c_int64)), epp]),
+        "pc_transmission_efficiencies_get_draw": (C.c_int, [vp, C.c_int, P(C.c_int64), P(C.c_int32), P(_dp), P(P(C.c_int64)), P(C.c_uint64), P(C.c_int64),
+                                                            P(C.c_int32), P(C.c_uint32), epp]),
         "pc_transmission_efficiencies_get_beam": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(_dp), epp]),
         "pc_transmission_efficiencies_get_beam_sums": (C.c_int, [vp, C.c_int, P(C.c_size_t), P(P(C.c_uint64)), P(P(C.c_uint64)),
                                                                P(C.c_int64), epp]),
@@ -571,6 +573,23 @@ class TransmissionEfficiencies(_LeakData):
         L.pc_transmission_efficiencies_get_select_records(self._h, self.SPOT_KINDS[kind], C.byref(n), C.byref(row), C.byref(r), C.byref(p), C.byref(err))
         _check(err)
         return dict(records=_take(r, n.value * row.value).reshape(n.value, row.value), positions=_take(p, n.value, np.int64))
+
+    def draw(self, kind="exit"):
+        """The unweighted sample of a run made with POLYCAP_DRAW="n=N[,energy=INDEX][,phase=UINT32]" (extension,
+        pc_transmission_efficiencies_get_draw): dict of records [rows, 17 + energies] for the exit photons or [rows, 12 + energies] for
+        "extleak" / "intleak" after a leak_calc run -- the rows of the N draws of pc_hip_select_draw at that energy, an entry as often as
+        it was drawn; rows is N, or 0 for a kind without weight at that energy -- their int64 positions [rows], total (the exact sum T
+        of the quantised weights drawn from), weight (T * 2^-32 / N: what a draw stands for per started photon), n, energy and phase."""
+        L = _lib()
+        rows, row, total = C.c_int64(0), C.c_int32(0), C.c_uint64(0)
+        n, energy, phase = C.c_int64(0), C.c_int32(0), C.c_uint32(0)
+        r, p = _dp(), C.POINTER(C.c_int64)()
+        err = _ErrP()
+        L.pc_transmission_efficiencies_get_draw(self._h, self.SPOT_KINDS[kind], C.byref(rows), C.byref(row), C.byref(r), C.byref(p), C.byref(total),
+                                                C.byref(n), C.byref(energy), C.byref(phase), C.byref(err))
+        _check(err)
+        return dict(records=_take(r, rows.value * row.value).reshape(rows.value, row.value), positions=_take(p, rows.value, np.int64),
+                    total=int(total.value), weight=int(total.value) * 2.0 ** -32 / n.value, n=int(n.value), energy=int(energy.value), phase=int(phase.value))
 
     def joint(self, kind="exit"):
         """Joint histograms of a run made with POLYCAP_JOINT set (extension, pc_transmission_efficiencies_get_joint): dict of the

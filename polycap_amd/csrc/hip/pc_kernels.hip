@@ -2113,6 +2113,7 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_joint.h"
 #include "pc_select.h"
 #include "pc_gather.h"
+#include "pc_draw.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
 

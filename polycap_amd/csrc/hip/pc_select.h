@@ -273,6 +273,12 @@ struct pc_select_member {
 	int idx_valid[3] = {0, 0, 0};
 	pc_dev_buf<unsigned int> d_tile_cnt, d_tile_off;      /* the compaction's tile counts [tiles] and offsets [tiles + 1] */
 	pc_dev_buf<unsigned long long> d_stage;               /* the gathered rows of one chunk */
+	/* pc_draw.h: the sums of V over the tiles [tiles] and their scan [tiles + 1] for one (kind, energy, tile), until the next apply */
+	pc_dev_buf<unsigned long long> d_draw_sum, d_draw_off;
+	pc_dev_buf<unsigned int> d_draw_list;                 /* the local positions of one call's draws */
+	int draw_valid = 0, draw_kind = 0, draw_energy = 0;
+	long long draw_tile = 0;
+	unsigned long long draw_total = 0;                    /* the member's T_j */
 };
 
 struct pc_hip_select {
@@ -431,6 +437,7 @@ int pc_hip_select_apply(pc_hip_select *sel, int kind)
 		pc_hip_ctx *c = mb.ctx;
 		mb.n[kind] = 0;
 		mb.idx_valid[kind] = 0;          /* the index list of the old mask (pc_gather.h) */
+		if (mb.draw_kind == kind) mb.draw_valid = 0;      /* and its tile sums (pc_draw.h) */
 		if (src[k].n == 0) { mb.epoch[kind] = c->entries_epoch; continue; }
 		PC_HIP_CHECK(hipSetDevice(c->device));
 		/* a gated add of this stream may still read the old mask */

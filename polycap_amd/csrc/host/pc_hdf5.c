@@ -282,6 +282,49 @@ static bool pc_h5_group(pc_hid file, const char *name, polycap_error **error)
 	return true;
 }
 
+/* one scalar attribute of a native type on an open object */
+static bool pc_h5_num_attr(pc_hid loc, const char *name, pc_hid type, const void *value)
+{
+	pc_hid aspace = -1, attr = -1;
+	bool ok = false;
+	if ((aspace = h5.screate(PC_H5S_SCALAR)) < 0) goto fail;
+	if ((attr = h5.acreate2(loc, name, type, aspace, PC_H5P_DEFAULT, PC_H5P_DEFAULT)) < 0) goto fail;
+	if (h5.awrite(attr, type, value) < 0) goto fail;
+	ok = true;
+fail:
+	if (attr >= 0 && h5.aclose(attr) < 0) ok = false;
+	if (aspace >= 0 && h5.sclose(aspace) < 0) ok = false;
+	return ok;
+}
+
+/* extension: the group /Draw of POLYCAP_DRAW with the request and the kinds' totals as its attributes */
+static bool pc_h5_draw_group(pc_hid file, const struct pc_draw_result *dr, double energy_keV, polycap_error **error)
+{
+	static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+	const pc_hid g = h5.gcreate2(file, "/Draw", PC_H5P_DEFAULT, PC_H5P_DEFAULT, PC_H5P_DEFAULT);
+	const long long n = (long long)dr->n, e = (long long)dr->energy;
+	const unsigned long long phase = dr->phase;
+	bool ok = g >= 0;
+	ok = ok && pc_h5_num_attr(g, "n", *h5.native_llong, &n) && pc_h5_num_attr(g, "energy_index", *h5.native_llong, &e)
+	        && pc_h5_num_attr(g, "energy_keV", *h5.native_double, &energy_keV) && pc_h5_num_attr(g, "phase", *h5.native_ullong, &phase);
+	for (int k = 0; k < 3 && ok; k++) {
+		if (!dr->applied[k])
+			continue;
+		char name[32];
+		const unsigned long long total = dr->total[k];
+		const double weight = (double)dr->total[k] / 4294967296.0 / (double)dr->n;
+		snprintf(name, sizeof name, "%s_total", names[k]);
+		ok = pc_h5_num_attr(g, name, *h5.native_ullong, &total);
+		snprintf(name, sizeof name, "%s_weight", names[k]);
+		ok = ok && pc_h5_num_attr(g, name, *h5.native_double, &weight);
+	}
+	if (g >= 0 && h5.gclose(g) < 0)
+		ok = false;
+	if (!ok)
+		polycap_set_error(error, POLYCAP_ERROR_IO, "polycap_transmission_efficiencies_write_hdf5: could not create group %s", "/Draw");
+	return ok;
+}
+
 bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficiencies *efficiencies, const char *filename, polycap_error **error)
 {
 	if (filename == NULL) {
@@ -647,6 +690,26 @@ bool polycap_transmission_efficiencies_write_hdf5(polycap_transmission_efficienc
 		}
 		free(table);
 		if (!sok) goto close;
+	}
+
+	if (efficiencies->draw != NULL) {
+		/* extension: the unweighted sample of POLYCAP_DRAW (include/polycap-hip.h): the rows of every kind that has some */
+		const struct pc_draw_result *dr = efficiencies->draw;
+		static const char *const names[3] = { "Exit", "ExtLeak", "IntLeak" };
+		bool dok = pc_h5_draw_group(file, dr, efficiencies->energies[dr->energy], error);
+		for (int k = 0; k < 3 && dok; k++) {
+			if (!dr->applied[k] || dr->rows[k] == 0)
+				continue;
+			char name[64];
+			pc_hsize rd[2] = { (pc_hsize)dr->rows[k], (pc_hsize)dr->row[k] };
+			snprintf(name, sizeof name, "/Draw/%s_Records", names[k]);
+			dok = dok && pc_h5_typed(file, 2, rd, name, *h5.native_double, dr->rec[k], "[cm,a.u.]",
+			                         k == 0 ? "the planes of an exit photon in their order (n_refl as int64 bits), then the weights"
+			                                : "slot,attempt,x,y,z,dir x y z,elecv x y z,n_refl, then the weights", error);
+			snprintf(name, sizeof name, "/Draw/%s_Positions", names[k]);
+			dok = dok && pc_h5_typed(file, 1, rd, name, *h5.native_llong, dr->pos[k], "a.u.", NULL, error);
+		}
+		if (!dok) goto close;
 	}
 
 	if (!pc_h5_group(file, "/Input", error)) goto close;

@@ -195,6 +195,21 @@ struct pc_select_result {
 	int64_t *rec_pos[3];            /* [rec_n] */
 };
 
+/* extension: the unweighted sample of a run made with POLYCAP_DRAW set (pc_transmission_efficiencies_get_draw): per kind the call has
+ * (exit photons, and extleak and intleak for leak_calc runs) the n draws of pc_hip_select_draw at one energy, none where the kind has
+ * no weight there */
+struct pc_draw_result {
+	int64_t n;                      /* the sample size asked for */
+	int32_t energy;                 /* index into the result's energies */
+	uint32_t phase;
+	int applied[3];
+	int64_t rows[3];                /* n, or 0 where total is 0 */
+	int32_t row[3];                 /* doubles per row */
+	uint64_t total[3];              /* T: the exact sum of the quantised weights drawn from */
+	double *rec[3];                 /* [rows][row] */
+	int64_t *pos[3];                /* [rows] */
+};
+
 struct _polycap_transmission_efficiencies {
 	size_t n_energies;
 	double *energies;
@@ -207,6 +222,7 @@ struct _polycap_transmission_efficiencies {
 	struct pc_hist_result *hist;
 	struct pc_joint_result *joint;
 	struct pc_select_result *select;
+	struct pc_draw_result *draw;
 	/* extension: the exact moments of a run made with POLYCAP_STDERR=1 (pc_transmission_efficiencies_get_stderr / _get_moments),
 	 * NULL otherwise: started photons, (lo, hi) sums of the weights and of the squared weights per energy (include/polycap-hip.h) */
 	int64_t n_started;
@@ -266,6 +282,7 @@ void pc_beam_result_free(struct pc_beam_result *beam);
 void pc_hist_result_free(struct pc_hist_result *hist);
 void pc_joint_result_free(struct pc_joint_result *joint);
 void pc_select_result_free(struct pc_select_result *select);
+void pc_draw_result_free(struct pc_draw_result *draw);
 void pc_squares_result_free(struct pc_squares_result *sq);
 
 #endif

@@ -742,6 +742,84 @@ static int pc_select_request_parse(struct pc_select_request *r, polycap_error **
 	return 0;
 }
 
+/* POLYCAP_DRAW, e.g. "n=100000,energy=3,phase=12345": the result carries an unweighted sample of n entries per kind, drawn at the
+ * energy of that index (default 0) with that phase (default 0: the call stays reproducible) through the call's selection, or through
+ * one that every entry passes when POLYCAP_SELECT is not set (include/polycap-hip.h, pc_hip_select_draw).  Parsed before any device is
+ * used; the reason of a refusal names the item. */
+struct pc_draw_request {
+	int set;
+	int implicit;                  /* the selection of the call is the all-pass one made for the draw: the result reports none */
+	int64_t n;
+	int32_t energy;
+	uint32_t phase;
+};
+
+/* 0, or -1 with the reason in why */
+static int pc_draw_request_parse(struct pc_draw_request *r, size_t ne, char *why, size_t why_len)
+{
+	memset(r, 0, sizeof(*r));
+	why[0] = '\0';
+	const char *env = getenv("POLYCAP_DRAW");
+	if (env == NULL)
+		return 0;
+	int have_n = 0;
+	if (*env == '\0') {
+		snprintf(why, why_len, "the value is empty: n=N[,energy=INDEX][,phase=UINT32] is needed");
+		return -1;
+	}
+	for (const char *at = env; ; ) {
+		const char *comma = strchr(at, ',');
+		const size_t len = comma != NULL ? (size_t)(comma - at) : strlen(at);
+		char item[64];
+		if (len >= sizeof item) {
+			snprintf(why, why_len, "item %.40s...: unknown key (n, energy, phase)", at);
+			return -1;
+		}
+		memcpy(item, at, len);
+		item[len] = '\0';
+		char *eq = strchr(item, '=');
+		char *end = NULL;
+		errno = 0;
+		const long long v = eq != NULL ? strtoll(eq + 1, &end, 10) : 0;
+		const int number = eq != NULL && end != eq + 1 && *end == '\0' && errno == 0;
+		if (eq != NULL)
+			*eq = '\0';
+		if (eq == NULL || (strcmp(item, "n") != 0 && strcmp(item, "energy") != 0 && strcmp(item, "phase") != 0)) {
+			snprintf(why, why_len, "item %s: unknown key (n, energy, phase)", item);
+			return -1;
+		}
+		if (strcmp(item, "n") == 0) {
+			if (!number || v < 1 || v > 2147483647ll) {
+				snprintf(why, why_len, "n=%s: must be an integer in 1 .. 2^31 - 1", eq + 1);
+				return -1;
+			}
+			r->n = (int64_t)v;
+			have_n = 1;
+		} else if (strcmp(item, "energy") == 0) {
+			if (!number || v < 0 || v >= (long long)ne) {
+				snprintf(why, why_len, "energy=%s: must be an index into the source's %zu energies", eq + 1, ne);
+				return -1;
+			}
+			r->energy = (int32_t)v;
+		} else {
+			if (!number || v < 0 || v > 4294967295ll) {
+				snprintf(why, why_len, "phase=%s: must be a uint32", eq + 1);
+				return -1;
+			}
+			r->phase = (uint32_t)v;
+		}
+		if (comma == NULL)
+			break;
+		at = comma + 1;
+	}
+	if (!have_n) {
+		snprintf(why, why_len, "n is missing: the size of the sample, n=N");
+		return -1;
+	}
+	r->set = 1;
+	return 0;
+}
+
 /* the tallies of one call and the selection they are filled through (any may be NULL); tot: the selection's totals summed over the
  * applies of the call, n_pass [3], n_seen [3], then passed_w [3][ne], rejected_w [3][ne] */
 struct pc_tallies {
@@ -760,6 +838,14 @@ struct pc_tallies {
 	int64_t rec_n[3];
 	double *rec[3];                /* [rec_n][PC_HIP_N_PLANES or PC_HIP_LEAK_HDR, + ne] */
 	int64_t *rec_pos[3];           /* positions in the concatenation of what the applies saw */
+	/* POLYCAP_DRAW: the draws of every kind (pc_hip_select_draw); a kind is applied once, a draw needs all its entries on the device */
+	struct pc_draw_request draw;
+	int draw_chunked;              /* the run would have been traced as several slot ranges: refused */
+	int draw_applied[3];
+	int64_t draw_rows[3];
+	uint64_t draw_total[3];
+	double *draw_rec[3];
+	int64_t *draw_pos[3];
 };
 
 /* every tally of the call and its selection track squares: before the first add and the first apply */
@@ -812,6 +898,21 @@ static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
 					pos[have + k] += ta->sel_n[3 + kind];      /* behind the entries the earlier applies saw */
 				if (st == PC_HIP_OK)
 					ta->rec_n[kind] = have + take;
+			}
+		}
+		if (st == PC_HIP_OK && ta->draw.set) {
+			/* the sample of this kind; one without weight at that energy carries no rows */
+			const size_t row = (size_t)(kind == 0 ? PC_HIP_N_PLANES : PC_HIP_LEAK_HDR) + ne;
+			const int64_t n = ta->draw.n;
+			ta->draw_applied[kind] = 1;
+			ta->draw_total[kind] = w[kind*ne + (size_t)ta->draw.energy];
+			if (ta->draw_total[kind] > 0) {
+				ta->draw_rec[kind] = malloc(sizeof(double)*row*(size_t)n);
+				ta->draw_pos[kind] = malloc(sizeof(int64_t)*(size_t)n);
+				st = (ta->draw_rec[kind] != NULL && ta->draw_pos[kind] != NULL)
+				   ? pc_hip_select_draw(s, kind, ta->draw.energy, n, ta->draw.phase, 0, n, ta->draw_rec[kind], ta->draw_pos[kind], NULL) : PC_HIP_ERR_MEMORY;
+				if (st == PC_HIP_OK)
+					ta->draw_rows[kind] = n;
 			}
 		}
 		if (st == PC_HIP_OK) {
@@ -1109,6 +1210,7 @@ struct pc_run_request {
 	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
 	struct pc_joint_request joint; /* POLYCAP_JOINT: exact joint 2-D histograms per energy (pc_hip_joint_*) */
 	struct pc_select_request select; /* POLYCAP_SELECT: cuts through which every tally is filled (pc_hip_select_*) */
+	struct pc_draw_request draw;   /* POLYCAP_DRAW: an unweighted sample of every kind (pc_hip_select_draw) */
 	int devices[64], n_devices;
 	int keep_images;
 	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
@@ -1158,6 +1260,20 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 		return -1;
 	if (pc_select_request_parse(&r->select, error) != 0)
 		return -1;
+	/* POLYCAP_DRAW is read here, for the selection it may need, and refused last: behind every other variable's refusal */
+	char draw_bad[256];
+	const int draw_st = pc_draw_request_parse(&r->draw, ne, draw_bad, sizeof draw_bad);
+	if (draw_st == 0 && r->draw.set && !r->select.set) {      /* no POLYCAP_SELECT: every entry passes, a reflection count in [0, 2^62) */
+		r->draw.implicit = 1;
+		r->select.cuts[0].axis.quantity = 6;      /* nrefl in the axis grammar of POLYCAP_HIST */
+		r->select.cuts[0].axis.lo = 0.;
+		r->select.cuts[0].axis.hi = 4611686018427387904.;
+		r->select.cuts[0].axis.n_bins = 1;
+		r->select.n_cuts = 1;
+		r->select.spec.n_cuts = 1;
+		r->select.spec.cuts = r->select.cuts;
+		r->select.set = 1;
+	}
 	if ((r->beam_on || r->hist.set || r->joint.set || r->select.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and (joint) histograms too */
 		r->spot.share = 0.5;
 		const char *share = getenv("POLYCAP_SPOT_SHARE");
@@ -1191,6 +1307,10 @@ static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_ca
 	r->rccl = (rccl != NULL && *rccl != '\0') ? atoi(rccl) : -1;
 	r->max_attempts = (uint32_t)pc_env_u64("POLYCAP_MAX_ATTEMPTS", 1u << 20, NULL);
 	r->seed = pc_env_u64("POLYCAP_SEED", 0, &r->have_seed);
+	if (draw_st != 0) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_DRAW=%s: %s", getenv("POLYCAP_DRAW"), draw_bad);
+		return -1;
+	}
 	return 0;
 }
 
@@ -1216,6 +1336,7 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 	if (r->select.set) {
 		ta->sel_w = calloc(6*ne, sizeof(uint64_t));
 		ta->rec_limit = r->select.records;
+		ta->draw = r->draw;
 		st = ta->sel_w == NULL ? PC_HIP_ERR_MEMORY
 		   : t.group != NULL ? pc_hip_group_select_create(t.group, &r->select.spec, &ta->select) : pc_hip_select_create(t.ctx, &r->select.spec, &ta->select);
 	}
@@ -1253,6 +1374,10 @@ static int pc_trace(struct pc_target t, const struct pc_run_request *r, int leak
 			st = t.group != NULL ? pc_hip_group_set_option(t.group, opt[k].name, opt[k].value) : pc_hip_set_option(t.ctx, opt[k].name, opt[k].value);
 	if (st != PC_HIP_OK)
 		return st;
+	if (chunk > 0 && chunk < n_photons && r->draw.set) {      /* a draw needs the exit data of the whole run on the device at once */
+		ta->draw_chunked = 1;
+		return PC_HIP_ERR_INVALID;
+	}
 	if (chunk > 0 && chunk < n_photons) {
 		*chunked = 1;
 		return pc_spot_chunked(t.ctx, ta, seed, n_photons, chunk, r->max_attempts, ne, sum_weights, counters, fixed, fixed2);
@@ -1390,7 +1515,23 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 		status = pc_hist_store(eff, hist, &req.hist, leak_calc);
 	if (status == PC_HIP_OK && joint != NULL)
 		status = pc_joint_store(eff, joint, &req.joint, leak_calc);
-	if (status == PC_HIP_OK && ta.select != NULL) {
+	if (status == PC_HIP_OK && ta.draw.set) {
+		struct pc_draw_result *dr = eff->draw = calloc(1, sizeof(*dr));
+		if (dr == NULL)
+			status = PC_HIP_ERR_MEMORY;
+		else {
+			dr->n = ta.draw.n; dr->energy = ta.draw.energy; dr->phase = ta.draw.phase;
+			for (int kind = 0; kind <= 2; kind++) {      /* the result owns the rows from here on */
+				dr->applied[kind] = ta.draw_applied[kind];
+				dr->rows[kind] = ta.draw_rows[kind];
+				dr->row[kind] = (int32_t)((kind == 0 ? PC_HIP_N_PLANES : PC_HIP_LEAK_HDR) + ne);
+				dr->total[kind] = ta.draw_total[kind];
+				dr->rec[kind] = ta.draw_rec[kind]; dr->pos[kind] = ta.draw_pos[kind];
+				ta.draw_rec[kind] = NULL; ta.draw_pos[kind] = NULL;
+			}
+		}
+	}
+	if (status == PC_HIP_OK && ta.select != NULL && !ta.draw.implicit) {
 		struct pc_select_result *sr = eff->select = calloc(1, sizeof(*sr));
 		if (sr == NULL)
 			status = PC_HIP_ERR_MEMORY;
@@ -1438,7 +1579,11 @@ polycap_transmission_efficiencies *polycap_source_get_transmission_efficiencies(
 	eff = NULL;
 
 out:
-	if (status != PC_HIP_OK)
+	if (ta.draw_chunked)
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_DRAW=%s: the exit data of %d photons "
+			"exceed POLYCAP_SPOT_SHARE of the device's memory, and a POLYCAP_IMAGES=0 run that is traced as several slot ranges has no one beam to draw from",
+			getenv("POLYCAP_DRAW"), n_photons);
+	else if (status != PC_HIP_OK)
 		pc_set_hip_error(error, "polycap_source_get_transmission_efficiencies", status);
 	for (int kind = 0; kind <= 2; kind++)
 		pc_hip_spot_destroy(spot[kind]);
@@ -1451,6 +1596,8 @@ out:
 	for (int kind = 0; kind <= 2; kind++) {
 		free(ta.rec[kind]);
 		free(ta.rec_pos[kind]);
+		free(ta.draw_rec[kind]);
+		free(ta.draw_pos[kind]);
 	}
 	pc_run_request_free(&req);
 	free(sum_weights);

@@ -208,6 +208,7 @@ void polycap_transmission_efficiencies_free(polycap_transmission_efficiencies *e
 	pc_hist_result_free(efficiencies->hist);
 	pc_joint_result_free(efficiencies->joint);
 	pc_select_result_free(efficiencies->select);
+	pc_draw_result_free(efficiencies->draw);
 	free(efficiencies->sumw_fixed);
 	free(efficiencies->sumw2_fixed);
 	free(efficiencies->stderrs);
@@ -507,6 +508,61 @@ void pc_select_result_free(struct pc_select_result *select)
 		free(select->rec_pos[k]);
 	}
 	free(select);
+}
+
+void pc_draw_result_free(struct pc_draw_result *draw)
+{
+	if (draw == NULL)
+		return;
+	for (int k = 0; k < 3; k++) {
+		free(draw->rec[k]);
+		free(draw->pos[k]);
+	}
+	free(draw);
+}
+
+int pc_transmission_efficiencies_get_draw(void *efficiencies_, int kind, int64_t *n_rows, int32_t *row_doubles, double **records, int64_t **positions,
+	uint64_t *total, int64_t *n_draw, int32_t *energy, uint32_t *phase, void *error_)
+{
+	static const char *fn = "pc_transmission_efficiencies_get_draw";
+	polycap_transmission_efficiencies *efficiencies = efficiencies_;
+	polycap_error **error = error_;
+	if (efficiencies == NULL || n_rows == NULL || kind < 0 || kind > 2) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: efficiencies and n_rows cannot be NULL and kind must be 0, 1 or 2", fn);
+		return 0;
+	}
+	const struct pc_draw_result *dr = efficiencies->draw;
+	if (dr == NULL) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run was made without POLYCAP_DRAW", fn);
+		return 0;
+	}
+	if (!dr->applied[kind]) {
+		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "%s: the run has no entries of kind %d (leak kinds need a leak_calc run)", fn, kind);
+		return 0;
+	}
+	const size_t n = (size_t)dr->rows[kind], row = (size_t)dr->row[kind];
+	double *r = NULL;
+	int64_t *p = NULL;
+	int ok = 1;
+	/* one element at least, so that a result of no rows still hands out pointers polycap_free takes */
+	if (records != NULL) ok = (r = malloc(sizeof(double)*(n > 0 ? n*row : 1))) != NULL;
+	if (positions != NULL && ok) ok = (p = malloc(sizeof(int64_t)*(n ? n : 1))) != NULL;
+	if (!ok) {
+		free(r); free(p);
+		polycap_set_error(error, POLYCAP_ERROR_MEMORY, "%s: could not allocate memory -> %s", fn, strerror(errno));
+		return 0;
+	}
+	if (r != NULL && n > 0) memcpy(r, dr->rec[kind], sizeof(double)*n*row);
+	if (p != NULL && n > 0) memcpy(p, dr->pos[kind], sizeof(int64_t)*n);
+	*n_rows = (int64_t)n;
+	if (row_doubles != NULL) *row_doubles = (int32_t)row;
+	if (records != NULL) *records = r;
+	if (positions != NULL) *positions = p;
+	if (total != NULL) *total = dr->total[kind];
+	if (n_draw != NULL) *n_draw = dr->n;
+	if (energy != NULL) *energy = dr->energy;
+	if (phase != NULL) *phase = dr->phase;
+	return 1;
 }
 
 int pc_transmission_efficiencies_get_select_records(void *efficiencies_, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,

@@ -342,6 +342,11 @@ class TraceContext:
             r["ext"], r["int"] = self.leaks(copy=not leak_views)
         return r
 
+    def draw(self, kind="exit", **kw):
+        """Selection.draw through a selection that every entry passes (select_all), made, applied and dropped here: an unweighted
+        sample of n entries of the last run, e.g. draw(energy=0, n=100000, seed=1)."""
+        return _draw_all(self, kind, kw)
+
 
 class TraceGroup:
     """One problem on several devices driven from this process (pc_hip_group_*): contiguous slot ranges per member, one
@@ -440,6 +445,11 @@ class TraceGroup:
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_group_moments", st)
         return fx.reshape(ne, 2)
+
+    def draw(self, kind="exit", **kw):
+        """Selection.draw through a selection that every entry passes (select_all), made, applied and dropped here: an unweighted
+        sample of n entries of the last run, e.g. draw(energy=0, n=100000, seed=1)."""
+        return _draw_all(self, kind, kw)
 
 
 RELAY_COUNTERS = ("n_in", "exit", "absorbed", "glass", "outside", "error", "skipped", "n_started_a")
@@ -946,6 +956,18 @@ def select_parse(value):
     return [_cut_dict(c) for c in cuts[:n.value]]
 
 
+def select_all():
+    """The list of one cut that every entry of every kind passes: a reflection count in [0, 2^62).  Selection(owner, select_all())
+    is the whole run as a selection, for draw() or gather() without a cut."""
+    return [dict(axis="nrefl", range=(0., 2.0 ** 62))]
+
+
+def _draw_all(owner, kind, kw):
+    with Selection(owner, select_all()) as sel:
+        sel.apply(kind)
+        return sel.draw(kind, **kw)
+
+
 class Selection:
     """A selection of a TraceContext or a TraceGroup (pc_hip_select_*): 1 to 8 cuts on per-entry quantities of the last run, ANDed
     (cuts: see select_cuts).  apply(kind) evaluates them on the device and returns the exact totals; tally.add(kind, select=sel) then
@@ -1047,6 +1069,45 @@ class Selection:
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_select_gather", st)
         return (rec, pos) if positions else rec
+
+
+    def draw(self, kind="exit", energy=0, n=None, phase=None, seed=None, first=0, count=None, positions=False):
+        """An unweighted sample of the passing entries of a kind the selection was applied for (pc_hip_select_draw): n draws in
+        proportion to the quantised weights at energy index `energy`, by systematic resampling in exact integers on the device; the
+        draws [first, first + count) are returned (count None = all from first on).  phase: a uint32; None takes one from
+        numpy.random.default_rng(seed).  A dict of records [count, row] (the rows gather() has at the drawn positions, an entry as
+        often as it was drawn), positions (int64 [count], not decreasing; with positions=True), total (T, the exact sum of the
+        quantised weights drawn from), weight (total * 2^-32 / n: what every draw stands for per started photon), phase and n."""
+        k = _kind(kind)
+        if n is None:
+            raise ValueError("draw: n, the size of the sample, is needed")
+        n, first = int(n), int(first)
+        if phase is None:
+            phase = int(np.random.default_rng(seed).integers(0, 1 << 32, dtype=np.uint64))
+        phase = int(phase)
+        if not 0 <= phase < (1 << 32):
+            raise ValueError("draw: phase must be a uint32, got %d" % phase)
+        if not -(1 << 63) <= n < (1 << 63):
+            raise ValueError("draw: n must be in [1, 2^31 - 1], got %d" % n)
+        if count is None:
+            count = max(n - first, 0)
+        count = int(count)
+        row = (17 if k == 0 else _cabi.PC_HIP_LEAK_HDR) + self.n_energies
+        if not (1 <= n < (1 << 31) and first >= 0 and 0 <= count <= n - first):
+            rows = min(max(count, 0), 1)          # the call refuses these before it writes: no array of a size nobody asked for in earnest
+        else:
+            rows = count
+        rec = np.empty((rows, row))
+        pos = np.empty(rows, dtype=np.int64) if positions else None
+        total = C.c_uint64(0)
+        st = self._L.pc_hip_select_draw(self._h, k, int(energy), n, phase, first, count, dptr(rec) if count > 0 else None,
+                                        pos.ctypes.data_as(c_int64_p) if positions and count > 0 else None, C.byref(total))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_select_draw", st)
+        r = dict(records=rec, total=int(total.value), weight=int(total.value) * 2.0 ** -32 / n, phase=phase, n=n)
+        if positions:
+            r["positions"] = pos
+        return r
 
 
 def scan_points(x=(0.,), y=(0.,), d_source=None):

@@ -5,7 +5,7 @@ to the same Python exceptions.  Every call goes straight to the C API of include
 Composition strings / element symbols are resolved by polycap_amd.capi's small parser (the reference calls xraylib's
 CompoundParser for this; it is not on the trace path)."""
 from collections import namedtuple
-from libc.stdint cimport int32_t, int64_t, uint64_t
+from libc.stdint cimport int32_t, int64_t, uint32_t, uint64_t
 from libc.stddef cimport size_t
 from libcpp cimport bool as cbool
 import numpy as np
@@ -128,6 +128,8 @@ cdef extern from "polycap.h" nogil:
         int64_t *n_seen, uint64_t **passed_w, uint64_t **rejected_w, void *error)
     int pc_transmission_efficiencies_get_select_records(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,
         int64_t **positions, void *error)
+    int pc_transmission_efficiencies_get_draw(void *efficiencies, int kind, int64_t *n_rows, int32_t *row_doubles, double **records,
+        int64_t **positions, uint64_t *total, int64_t *n, int32_t *energy, uint32_t *phase, void *error)
     int pc_transmission_efficiencies_get_tally_squares(void *efficiencies, int which, int kind, size_t *n_cells, size_t *n_outside,
         uint64_t **sums, uint64_t **outside, uint64_t **squares, uint64_t **outside_squares, double **stderrs, double **outside_stderrs,
         int64_t *n_started, void *error)
@@ -896,6 +898,32 @@ cdef class TransmissionEfficiencies:
             pos[i] = p[i]
         polycap_free(p)
         return dict(records=_take_doubles(r, <size_t>(n * row)).reshape(n, row), positions=pos)
+
+    def draw(self, kind="exit"):
+        """Extension of this build: the unweighted sample of a run made with POLYCAP_DRAW="n=N[,energy=INDEX][,phase=UINT32]"
+        (pc_transmission_efficiencies_get_draw): dict of records [rows, 17 + energies] for the exit photons or [rows, 12 + energies] for
+        "extleak" / "intleak" after a leak_calc run -- the rows of the N draws of pc_hip_select_draw at that energy; rows is N, or 0 for
+        a kind without weight at that energy -- their int64 positions [rows], total (the exact sum T of the quantised weights drawn
+        from), weight (T * 2^-32 / N), n, energy and phase."""
+        cdef polycap_error *error = NULL
+        cdef int64_t rows = 0
+        cdef int64_t n = 0
+        cdef int32_t row = 0
+        cdef int32_t energy = 0
+        cdef uint32_t phase = 0
+        cdef uint64_t total = 0
+        cdef double *r = NULL
+        cdef int64_t *p = NULL
+        cdef int64_t i
+        k = {"exit": 0, "extleak": 1, "intleak": 2}[kind]
+        pc_transmission_efficiencies_get_draw(<void *>self._eff, k, &rows, &row, &r, &p, &total, &n, &energy, &phase, <void *>&error)
+        _raise_if(error)
+        pos = np.empty(rows, dtype=np.int64)
+        for i in range(rows):
+            pos[i] = p[i]
+        polycap_free(p)
+        return dict(records=_take_doubles(r, <size_t>(rows * row)).reshape(rows, row), positions=pos, total=int(total),
+                    weight=int(total) * 2.0 ** -32 / n, n=int(n), energy=int(energy), phase=int(phase))
 
     def write_hdf5(self, filename):
         cdef polycap_error *error = NULL
