@@ -19,7 +19,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libpolycap.so")
 
 HOST_SRCS = ["pc_error.c", "pc_rng.c", "pc_profile.c", "pc_description.c", "pc_optconst.c",
-             "pc_photon.c", "pc_source.c", "pc_transeff.c", "pc_hdf5.c"]
+             "pc_photon.c", "pc_request.c", "pc_source.c", "pc_transeff.c", "pc_hdf5.c"]
 HIP_SRCS = ["pc_kernels.hip"]
 HIP_DEPS = ["pc_device.h", "pc_problem.h", "pc_leak.h", "pc_leak_kernels.h", "pc_pool_kernel.h", "pc_producer_kernel.h", "pc_wave_kernel.h", "pc_sweep_kernel.h", "pc_group.h", "pc_tally.h", "pc_spot.h", "pc_beam.h", "pc_hist.h", "pc_joint.h", "pc_select.h", "pc_gather.h", "pc_draw.h", "pc_moments.h", "pc_scan.h", "pc_relay.h", "pc_plan.h", "pc_images.h"]
 

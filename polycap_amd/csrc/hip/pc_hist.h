@@ -7,7 +7,7 @@
  * only: not on launch shape, entry order, how the slots were split into runs, or the device count.  Full width at half maximum
  * and quantiles (encircled-energy radii) follow on the host (pc_hip_hist_fwhm, pc_hip_hist_quantile).
  *
- * The first part (the per-entry arithmetic and the host formulas) compiles for the host as well: -DPC_HIST_HOST_ONLY stops the
+ * The first part (the per-entry arithmetic, the host formulas and the check of a spec) compiles for the host as well: -DPC_HIST_HOST_ONLY stops the
  * header after it.
  */
 #ifndef PC_HIST_H
@@ -17,6 +17,11 @@
 #include <stdint.h>
 #include <cmath>
 #include <string>
+
+#if defined(PC_HIST_HOST_ONLY) && !defined(PC_TALLY_HOST_ONLY)
+#define PC_TALLY_HOST_ONLY      /* the host part stands on pc_tally.h's (pc_sel_check) */
+#endif
+#include "pc_tally.h"
 
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -155,6 +160,31 @@ static bool pc_hist_axis_check(const Axis &x, int n_quantities, std::string *why
 	else if (x.n_bins < 1)
 		*why = "n_bins must be >= 1";
 	return why->empty();
+}
+
+/* pc_hip_hist_validate (Spec: pc_hip_hist_spec): false and the reason in *why (it names the field) when the spec is refused */
+template <typename Spec>
+static bool pc_hist_spec_check(const Spec *spec, size_t n_energies, std::string *why)
+{
+	const auto no = [why](const std::string &w) { *why = w; return false; };
+	if (!spec) return no("spec must not be NULL");
+	if (spec->n_axes < 1 || spec->n_axes > PC_HIST_MAX_AXES || !spec->axes)
+		return no("n_axes: 1 to 16 axes are needed, got " + std::to_string(spec->n_axes));
+	double bins = 0.;
+	for (int a = 0; a < spec->n_axes; a++) {
+		std::string w;
+		if (!pc_hist_axis_check(spec->axes[a], PC_HIST_N_QUANTITIES, &w))
+			return no("axis " + std::to_string(a) + ": " + w);
+		bins += (double)spec->axes[a].n_bins;
+	}
+	if (spec->regime < 0 || spec->regime > 2)
+		return no("regime must be 0 (automatic), 1 (private LDS histograms) or 2 (energies across lanes)");
+	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, why))
+		return false;
+	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
+	if (bins*ns > (double)(1ll << 24))
+		return no("n_bins: (sum of n_bins) * selected energies exceeds 2^24");
+	return true;
 }
 
 #ifndef PC_HIST_HOST_ONLY
@@ -397,26 +427,8 @@ extern "C" {
 
 int pc_hip_hist_validate(const pc_hip_hist_spec *spec, size_t n_energies)
 {
-	if (!spec) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: spec must not be NULL");
-	if (spec->n_axes < 1 || spec->n_axes > PC_HIST_MAX_AXES || !spec->axes)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: n_axes: 1 to 16 axes are needed, got " + std::to_string(spec->n_axes));
-	double bins = 0.;
-	for (int a = 0; a < spec->n_axes; a++) {
-		const pc_hip_hist_axis &x = spec->axes[a];
-		std::string why;
-		if (!pc_hist_axis_check(x, PC_HIST_N_QUANTITIES, &why))
-			return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: axis " + std::to_string(a) + ": " + why);
-		bins += (double)x.n_bins;
-	}
-	if (spec->regime < 0 || spec->regime > 2)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: regime must be 0 (automatic), 1 (private LDS histograms) or 2 (energies across lanes)");
 	std::string why;
-	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &why))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: " + why);
-	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
-	if (bins*ns > (double)(1ll << 24))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: n_bins: (sum of n_bins) * selected energies exceeds 2^24");
-	return PC_HIP_OK;
+	return pc_hist_spec_check(spec, n_energies, &why) ? PC_HIP_OK : pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_validate: " + why);
 }
 
 int pc_hip_hist_create(pc_hip_ctx *ctx, const pc_hip_hist_spec *spec, pc_hip_hist **hist)

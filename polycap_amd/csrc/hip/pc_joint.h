@@ -8,7 +8,7 @@
  * or the device count.
  *
  * The value and the bin of an axis are pc_hist.h's (pc_hist_value with the two start coordinates, pc_hist_bin), the weights are
- * pc_spot.h's (pc_spot_q), the object is pc_tally.h's.  The first part (the cell of an entry, the marginals) compiles for the host
+ * pc_spot.h's (pc_spot_q), the object is pc_tally.h's.  The first part (the cell of an entry, the marginals, the check of a spec) compiles for the host
  * as well: -DPC_JOINT_HOST_ONLY stops the header after it.
  */
 #ifndef PC_JOINT_H
@@ -32,6 +32,33 @@ static inline void pc_joint_marginal(int32_t nu, int32_t nv, const uint64_t *cel
 	for (int32_t iv = 0; iv < nv; iv++)
 		for (int32_t iu = 0; iu < nu; iu++)
 			out[which ? iv : iu] += cells[(size_t)iv*nu + iu];
+}
+
+/* pc_hip_joint_validate (Spec: pc_hip_joint_spec): false and the reason in *why (it names the field) when the spec is refused */
+template <typename Spec>
+static bool pc_joint_spec_check(const Spec *spec, size_t n_energies, std::string *why)
+{
+	const auto no = [why](const std::string &w) { *why = w; return false; };
+	if (!spec) return no("spec must not be NULL");
+	if (spec->n_pairs < 1 || spec->n_pairs > PC_JOINT_MAX_PAIRS || !spec->pairs)
+		return no("n_pairs: 1 to 8 pairs are needed, got " + std::to_string(spec->n_pairs));
+	double cells = 0.;
+	for (int p = 0; p < spec->n_pairs; p++) {
+		for (int w = 0; w < 2; w++) {
+			std::string bad;
+			if (!pc_hist_axis_check(w ? spec->pairs[p].v : spec->pairs[p].u, PC_JOINT_N_QUANTITIES, &bad))
+				return no("pair " + std::to_string(p) + ": axis " + (w ? "v" : "u") + ": " + bad);
+		}
+		cells += (double)spec->pairs[p].u.n_bins*(double)spec->pairs[p].v.n_bins;
+	}
+	if (spec->regime < 0 || spec->regime > 2)
+		return no("regime must be 0 (automatic), 1 (private LDS tiles) or 2 (energies across lanes)");
+	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, why))
+		return false;
+	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
+	if (cells*ns > (double)(1ll << 26))
+		return no("n_bins: (sum of the pairs' cells nu * nv) * selected energies exceeds 2^26");
+	return true;
 }
 
 #ifndef PC_JOINT_HOST_ONLY
@@ -268,27 +295,8 @@ extern "C" {
 
 int pc_hip_joint_validate(const pc_hip_joint_spec *spec, size_t n_energies)
 {
-	if (!spec) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: spec must not be NULL");
-	if (spec->n_pairs < 1 || spec->n_pairs > PC_JOINT_MAX_PAIRS || !spec->pairs)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: n_pairs: 1 to 8 pairs are needed, got " + std::to_string(spec->n_pairs));
-	double cells = 0.;
-	for (int p = 0; p < spec->n_pairs; p++) {
-		for (int w = 0; w < 2; w++) {
-			std::string why;
-			if (!pc_hist_axis_check(w ? spec->pairs[p].v : spec->pairs[p].u, PC_JOINT_N_QUANTITIES, &why))
-				return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: pair " + std::to_string(p) + ": axis " + (w ? "v" : "u") + ": " + why);
-		}
-		cells += (double)spec->pairs[p].u.n_bins*(double)spec->pairs[p].v.n_bins;
-	}
-	if (spec->regime < 0 || spec->regime > 2)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: regime must be 0 (automatic), 1 (private LDS tiles) or 2 (energies across lanes)");
 	std::string why;
-	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &why))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: " + why);
-	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
-	if (cells*ns > (double)(1ll << 26))
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: n_bins: (sum of the pairs' cells nu * nv) * selected energies exceeds 2^26");
-	return PC_HIP_OK;
+	return pc_joint_spec_check(spec, n_energies, &why) ? PC_HIP_OK : pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_validate: " + why);
 }
 
 int pc_hip_joint_create(pc_hip_ctx *ctx, const pc_hip_joint_spec *spec, pc_hip_joint **joint)

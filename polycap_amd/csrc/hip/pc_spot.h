@@ -5,13 +5,21 @@
  * involved.  Sums are exact integer sums (uint64, weights quantised to 2^-32), so a map depends on the set of entries only:
  * not on launch shape, entry order, how the slots were split into runs, or the device count.
  *
- * The first part (the per-entry arithmetic) compiles for the host as well: -DPC_SPOT_HOST_ONLY stops the header after it.
+ * The first part (the per-entry arithmetic and the check of a spec) compiles for the host as well: -DPC_SPOT_HOST_ONLY stops the
+ * header after it.
  */
 #ifndef PC_SPOT_H
 #define PC_SPOT_H
 
 #include <math.h>
 #include <stdint.h>
+#include <cmath>
+#include <string>
+
+#if defined(PC_SPOT_HOST_ONLY) && !defined(PC_TALLY_HOST_ONLY)
+#define PC_TALLY_HOST_ONLY      /* the host part stands on pc_tally.h's (pc_sel_check) */
+#endif
+#include "pc_tally.h"
 
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -43,6 +51,33 @@ static inline __host__ __device__ unsigned long long pc_spot_q(double w)
 {
 	const double v = w * 4294967296.0;
 	return (v > 0.) ? (unsigned long long)rint(v) : 0ull;
+}
+
+/* pc_hip_spot_validate (Spec: pc_hip_spot_spec of include/polycap-hip.h): false and the message in *why when the spec is refused */
+template <typename Spec>
+static bool pc_spot_spec_check(const Spec *spec, size_t n_energies, std::string *why)
+{
+	const auto no = [why](const std::string &w) { *why = w; return false; };
+	if (!spec) return no("spot spec must not be NULL");
+	if (spec->n_planes < 1 || spec->n_planes > 64 || !spec->distances)
+		return no("spot spec: 1 to 64 plane distances are needed, got " + std::to_string(spec->n_planes));
+	for (int k = 0; k < spec->n_planes; k++)
+		if (!(spec->distances[k] >= 0.) || !std::isfinite(spec->distances[k]))
+			return no("spot spec: plane distances must be finite and >= 0");
+	if (!std::isfinite(spec->x0) || !std::isfinite(spec->x1) || !std::isfinite(spec->y0) || !std::isfinite(spec->y1)
+	    || !(spec->x0 < spec->x1) || !(spec->y0 < spec->y1))
+		return no("spot spec: the window needs finite x0 < x1 and y0 < y1");
+	if (spec->nx < 1 || spec->ny < 1)
+		return no("spot spec: nx and ny must be >= 1");
+	if (spec->regime < 0 || spec->regime > 2)
+		return no("spot spec: regime must be 0 (automatic), 1 (LDS tiles) or 2 (energies across lanes)");
+	std::string sel;
+	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &sel))
+		return no("spot spec: " + sel);
+	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
+	if ((double)spec->n_planes*ns*(double)spec->nx*(double)spec->ny > (double)(1ll << 27))
+		return no("spot spec: n_planes * n_energies * nx * ny exceeds 2^27 bins");
+	return true;
 }
 
 #ifndef PC_SPOT_HOST_ONLY
@@ -244,26 +279,8 @@ extern "C" {
 
 int pc_hip_spot_validate(const pc_hip_spot_spec *spec, size_t n_energies)
 {
-	if (!spec) return pc_fail(PC_HIP_ERR_INVALID, "spot spec must not be NULL");
-	if (spec->n_planes < 1 || spec->n_planes > 64 || !spec->distances)
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: 1 to 64 plane distances are needed, got " + std::to_string(spec->n_planes));
-	for (int k = 0; k < spec->n_planes; k++)
-		if (!(spec->distances[k] >= 0.) || !std::isfinite(spec->distances[k]))
-			return pc_fail(PC_HIP_ERR_INVALID, "spot spec: plane distances must be finite and >= 0");
-	if (!std::isfinite(spec->x0) || !std::isfinite(spec->x1) || !std::isfinite(spec->y0) || !std::isfinite(spec->y1)
-	    || !(spec->x0 < spec->x1) || !(spec->y0 < spec->y1))
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: the window needs finite x0 < x1 and y0 < y1");
-	if (spec->nx < 1 || spec->ny < 1)
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: nx and ny must be >= 1");
-	if (spec->regime < 0 || spec->regime > 2)
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: regime must be 0 (automatic), 1 (LDS tiles) or 2 (energies across lanes)");
 	std::string why;
-	if (!pc_sel_check(spec->n_energies, spec->energies, n_energies, &why))
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: " + why);
-	const double ns = spec->n_energies ? (double)spec->n_energies : (double)n_energies;
-	if ((double)spec->n_planes*ns*(double)spec->nx*(double)spec->ny > (double)(1ll << 27))
-		return pc_fail(PC_HIP_ERR_INVALID, "spot spec: n_planes * n_energies * nx * ny exceeds 2^27 bins");
-	return PC_HIP_OK;
+	return pc_spot_spec_check(spec, n_energies, &why) ? PC_HIP_OK : pc_fail(PC_HIP_ERR_INVALID, why);
 }
 
 int pc_hip_spot_create(pc_hip_ctx *ctx, const pc_hip_spot_spec *spec, pc_hip_spot **spot)

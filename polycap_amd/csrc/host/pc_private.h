@@ -231,6 +231,96 @@ struct _polycap_transmission_efficiencies {
 	int64_t tally_n_started;   /* extension: POLYCAP_TALLY_STDERR=1: counters 0 + 1 + 2 of the call, the N of the tallies' standard errors; 0 otherwise */
 };
 
+/* POLYCAP_SPOT, e.g. "dist=0.5,1,2;window=-0.02,0.02,-0.02,0.02;bins=256x256;energies=all" (cm; energy indices into the source's
+ * list, or all): spot maps of the run (include/polycap-hip.h, pc_hip_spot_*) */
+struct pc_spot_request {
+	int set;
+	double dist[65];
+	int n_dist;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_spot_spec spec;
+	double share;              /* POLYCAP_SPOT_SHARE: fraction of the device's memory the exit data of one run may take (0.5) */
+};
+
+/* POLYCAP_HIST, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=2048;axis=r,d=0.5,centre=0:0,range=0:0.02,bins=1024;axis=nrefl,range=0:256,bins=256;energies=all":
+ * histograms of the run (include/polycap-hip.h, pc_hip_hist_*).  Items are separated by ';': an axis (comma-separated key=value
+ * pairs, the first being axis=NAME) or energies= as in POLYCAP_SPOT */
+struct pc_hist_request {
+	int set;
+	pc_hip_hist_axis axes[17];
+	int n_axes;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_hist_spec spec;
+};
+
+/* POLYCAP_JOINT, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=256*axis=slope_x,range=-0.005:0.005,bins=256;axis=start_x,range=-0.3:0.3,bins=512*axis=start_y,range=-0.3:0.3,bins=512;energies=all":
+ * joint histograms of the run (include/polycap-hip.h, pc_hip_joint_*).  Items are separated by ';': a pair (two axes of the
+ * POLYCAP_HIST grammar joined by '*', u first; start_x and start_y are axes here too) or energies= as in POLYCAP_HIST */
+struct pc_joint_request {
+	int set;
+	pc_hip_joint_pair pairs[9];
+	int n_pairs;
+	int32_t *energies;
+	int n_energies;
+	pc_hip_joint_spec spec;
+};
+
+/* POLYCAP_SELECT, e.g. "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not": cuts through which every tally of the call is
+ * filled (include/polycap-hip.h, pc_hip_select_*; the grammar is pc_hip_select_parse's) */
+struct pc_select_request {
+	int set;
+	pc_hip_select_cut cuts[8];
+	int32_t n_cuts;
+	pc_hip_select_spec spec;
+	int64_t records;               /* POLYCAP_SELECT_RECORDS=N: the result keeps the first N passing entries of every kind; 0: unset */
+};
+
+/* POLYCAP_DRAW, e.g. "n=100000,energy=3,phase=12345": the result carries an unweighted sample of n entries per kind, drawn at the
+ * energy of that index (default 0) with that phase (default 0: the call stays reproducible) through the call's selection, or through
+ * one that every entry passes when POLYCAP_SELECT is not set (include/polycap-hip.h, pc_hip_select_draw) */
+struct pc_draw_request {
+	int set;
+	int implicit;                  /* the selection of the call is the all-pass one made for the draw: the result reports none */
+	int64_t n;
+	int32_t energy;
+	uint32_t phase;
+};
+
+/* Everything polycap_source_get_transmission_efficiencies takes from the environment, read by pc_run_request_parse (pc_request.c)
+ * before any device is used.  These are extensions of the reference call, all through the environment so that the signature stays
+ * the reference's:
+ *   POLYCAP_HIP_DEVICES=all | i,j,...  the photon loop is sharded over these devices from this one process (the reference's OpenMP
+ *       team, :697-745, becomes a team of GPUs); totals are summed by one RCCL all-reduce (:973-980)
+ *   POLYCAP_IMAGES=0                   histogram-only result: efficiencies and counts, no per-photon planes (at 1e8 photons x 291
+ *       energies the weight plane alone is 233 GB); the start/exit getters then report no events */
+struct pc_run_request {
+	int timing;                /* POLYCAP_TIMING: stage times on stderr */
+	int tally_stderr_on;       /* POLYCAP_TALLY_STDERR=1: the tallies and the selection of the call track squares; unset or 0: not */
+	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
+	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
+	struct pc_spot_request spot;
+	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
+	struct pc_joint_request joint; /* POLYCAP_JOINT: exact joint 2-D histograms per energy (pc_hip_joint_*) */
+	struct pc_select_request select; /* POLYCAP_SELECT: cuts through which every tally is filled (pc_hip_select_*) */
+	struct pc_draw_request draw;   /* POLYCAP_DRAW: an unweighted sample of every kind (pc_hip_select_draw) */
+	int devices[64], n_devices;
+	int keep_images;
+	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
+	int compact;               /* POLYCAP_COMPACT, plain runs only */
+	int have_block_shift;      /* POLYCAP_BLOCK_SHIFT set (one device only) */
+	int64_t block_shift;
+	int rccl;                  /* POLYCAP_RCCL: 0 host sum, 1 RCCL or fail, -1 (unset) RCCL when possible */
+	uint32_t max_attempts;     /* POLYCAP_MAX_ATTEMPTS */
+	int have_seed;             /* POLYCAP_SEED given: seed, else derived from the source */
+	uint64_t seed;
+};
+
+/* 0, or -1 with the error set; after either, pc_run_request_free frees what the request holds */
+int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_calc, int n_photons, polycap_error **error);
+void pc_run_request_free(struct pc_run_request *r);
+
 /* internal helpers */
 char *polycap_read_input_line(FILE *fptr, polycap_error **error);
 void polycap_description_check_weight(size_t nelem, double wi[], polycap_error **error);

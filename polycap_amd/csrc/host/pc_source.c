@@ -304,520 +304,12 @@ polycap_photon *polycap_source_get_photon(polycap_source *source, polycap_rng *r
 	return photon;
 }
 
-static uint64_t pc_env_u64(const char *name, uint64_t fallback, int *present)
-{
-	const char *env = getenv(name);
-	if (present) *present = 0;
-	if (env == NULL || *env == '\0')
-		return fallback;
-	char *end = NULL;
-	unsigned long long v = strtoull(env, &end, 0);
-	if (end == env)
-		return fallback;
-	if (present) *present = 1;
-	return (uint64_t)v;
-}
-
-/* POLYCAP_HIP_DEVICES = "all" or a comma-separated list of device indices (an index may repeat).  *n = 0 when unset. */
-static int pc_env_devices(int devices[64], int *n, polycap_error **error)
-{
-	*n = 0;
-	const char *env = getenv("POLYCAP_HIP_DEVICES");
-	if (env == NULL || *env == '\0')
-		return 0;
-	if (strcmp(env, "all") == 0) {
-		int count = pc_hip_device_count();
-		if (count < 1) {
-			polycap_set_error_literal(error, POLYCAP_ERROR_RUNTIME, "polycap_source_get_transmission_efficiencies: POLYCAP_HIP_DEVICES=all but no HIP device is visible (the trace path has no CPU fallback)");
-			return -1;
-		}
-		if (count > 64) count = 64;
-		for (int k = 0; k < count; k++) devices[k] = k;
-		*n = count;
-		return 0;
-	}
-	const char *p = env;
-	while (*p != '\0') {
-		char *end = NULL;
-		long v = strtol(p, &end, 10);
-		if (end == p || v < 0 || *n >= 64 || (*end != ',' && *end != '\0')) {
-			polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: cannot parse POLYCAP_HIP_DEVICES=%s (all, or up to 64 comma-separated device indices)", env);
-			return -1;
-		}
-		devices[(*n)++] = (int)v;
-		p = (*end == ',') ? end + 1 : end;
-	}
-	return 0;
-}
-
 /* POLYCAP_TIMING=1: stage times of polycap_source_get_transmission_efficiencies on stderr */
 static double pc_now_ms(void)
 {
 	struct timespec ts;
 	clock_gettime(CLOCK_MONOTONIC, &ts);
 	return ts.tv_sec*1e3 + ts.tv_nsec*1e-6;
-}
-
-/* POLYCAP_SPOT, e.g. "dist=0.5,1,2;window=-0.02,0.02,-0.02,0.02;bins=256x256;energies=all" (cm; energy indices into the source's
- * list, or all): spot maps of the run (include/polycap-hip.h, pc_hip_spot_*).  Parsed and validated before any device is used. */
-struct pc_spot_request {
-	int set;
-	double dist[65];
-	int n_dist;
-	int32_t *energies;
-	int n_energies;
-	pc_hip_spot_spec spec;
-	double share;              /* POLYCAP_SPOT_SHARE: fraction of the device's memory the exit data of one run may take (0.5) */
-};
-
-static int pc_spot_parse_doubles(const char *v, double *out, int max, int *n)
-{
-	*n = 0;
-	while (*v != '\0') {
-		char *end = NULL;
-		errno = 0;
-		const double d = strtod(v, &end);
-		if (end == v || errno != 0 || *n >= max)
-			return -1;
-		out[(*n)++] = d;
-		v = end;
-		if (*v == ',')
-			v++;
-		else if (*v != '\0')
-			return -1;
-	}
-	return *n > 0 ? 0 : -1;
-}
-
-static int pc_spot_request_parse(struct pc_spot_request *r, size_t n_energies, polycap_error **error)
-{
-	memset(r, 0, sizeof(*r));
-	const char *env = getenv("POLYCAP_SPOT");
-	if (env == NULL || *env == '\0')
-		return 0;
-	r->set = 1;
-	char *buf = strdup(env), *save = NULL;
-	const char *bad = NULL;
-	int have_dist = 0, have_window = 0, have_bins = 0;
-	r->spec.n_energies = 0;
-	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save)) {
-		char *eq = strchr(item, '=');
-		if (eq == NULL) { bad = "every item must be key=value"; break; }
-		*eq = '\0';
-		const char *key = item, *v = eq + 1;
-		if (strcmp(key, "dist") == 0) {
-			if (pc_spot_parse_doubles(v, r->dist, 65, &r->n_dist) != 0) bad = "dist must be a list of at most 64 distances in cm";
-			have_dist = 1;
-		} else if (strcmp(key, "window") == 0) {
-			double w[4];
-			int n = 0;
-			if (pc_spot_parse_doubles(v, w, 4, &n) != 0 || n != 4) { bad = "window must be x0,x1,y0,y1 in cm"; break; }
-			r->spec.x0 = w[0]; r->spec.x1 = w[1]; r->spec.y0 = w[2]; r->spec.y1 = w[3];
-			have_window = 1;
-		} else if (strcmp(key, "bins") == 0) {
-			long nx = 0, ny = 0;
-			char *end = NULL;
-			nx = strtol(v, &end, 10);
-			if (end == v || (*end != 'x' && *end != 'X')) { bad = "bins must be NXxNY"; break; }
-			const char *v2 = end + 1;
-			ny = strtol(v2, &end, 10);
-			if (end == v2 || *end != '\0' || nx < 0 || ny < 0 || nx > 1 << 27 || ny > 1 << 27) { bad = "bins must be NXxNY"; break; }
-			r->spec.nx = (int32_t)nx; r->spec.ny = (int32_t)ny;
-			have_bins = 1;
-		} else if (strcmp(key, "energies") == 0) {
-			free(r->energies);
-			r->energies = NULL;
-			r->n_energies = 0;
-			if (strcmp(v, "all") == 0)
-				continue;
-			r->energies = malloc(sizeof(int32_t) * (n_energies + 1));
-			while (r->energies != NULL && *v != '\0') {
-				char *end = NULL;
-				const long e = strtol(v, &end, 10);
-				if (end == v || (size_t)r->n_energies > n_energies) { bad = "energies must be all or a list of energy indices"; break; }
-				r->energies[r->n_energies++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
-				v = end;
-				if (*v == ',') v++;
-				else if (*v != '\0') { bad = "energies must be all or a list of energy indices"; break; }
-			}
-			if (bad == NULL && r->n_energies == 0) bad = "energies must be all or a list of energy indices";
-		} else {
-			bad = "unknown key (dist, window, bins, energies)";
-		}
-	}
-	free(buf);
-	if (bad == NULL && !(have_dist && have_window && have_bins))
-		bad = "dist, window and bins are required";
-	r->share = 0.5;
-	const char *share = getenv("POLYCAP_SPOT_SHARE");
-	if (bad == NULL && share != NULL && *share != '\0') {
-		char *end = NULL;
-		r->share = strtod(share, &end);
-		if (*end != '\0' || !(r->share > 0. && r->share <= 1.))
-			bad = "POLYCAP_SPOT_SHARE must be a fraction in (0, 1]";
-	}
-	if (bad == NULL) {
-		r->spec.n_planes = r->n_dist;
-		r->spec.distances = r->dist;
-		r->spec.n_energies = r->n_energies;
-		r->spec.energies = r->energies;
-		if (pc_hip_spot_validate(&r->spec, n_energies) != PC_HIP_OK)
-			bad = pc_hip_last_error();
-	}
-	if (bad != NULL) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SPOT=%s: %s", env, bad);
-		free(r->energies);
-		r->energies = NULL;
-		return -1;
-	}
-	return 0;
-}
-
-/* POLYCAP_HIST, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=2048;axis=r,d=0.5,centre=0:0,range=0:0.02,bins=1024;axis=nrefl,range=0:256,bins=256;energies=all":
- * histograms of the run (include/polycap-hip.h, pc_hip_hist_*).  Items are separated by ';': an axis (comma-separated key=value
- * pairs, the first being axis=NAME) or energies= as in POLYCAP_SPOT.  Parsed and validated before any device is used. */
-struct pc_hist_request {
-	int set;
-	pc_hip_hist_axis axes[17];
-	int n_axes;
-	int32_t *energies;
-	int n_energies;
-	pc_hip_hist_spec spec;
-};
-
-static int pc_hist_parse_pair(const char *v, double *a, double *b)
-{
-	char *end = NULL;
-	errno = 0;
-	*a = strtod(v, &end);
-	if (end == v || errno != 0 || *end != ':')
-		return -1;
-	v = end + 1;
-	*b = strtod(v, &end);
-	return (end == v || errno != 0 || *end != '\0') ? -1 : 0;
-}
-
-/* n_names: 10 for a histogram axis, 12 for an axis of a joint histogram (start_x and start_y as well) */
-static const char *pc_hist_parse_axis(char *item, pc_hip_hist_axis *ax, int n_names)
-{
-	static const char *names[] = { "x", "y", "r", "slope_x", "slope_y", "tan_theta", "nrefl", "dtravel", "r_start", "z", "start_x", "start_y" };
-	int have_axis = 0, have_range = 0, have_bins = 0;
-	char *save = NULL;
-	memset(ax, 0, sizeof(*ax));
-	for (char *kv = strtok_r(item, ",", &save); kv != NULL; kv = strtok_r(NULL, ",", &save)) {
-		char *eq = strchr(kv, '=');
-		if (eq == NULL)
-			return "every part of an axis must be key=value";
-		*eq = '\0';
-		const char *v = eq + 1;
-		char *end = NULL;
-		if (strcmp(kv, "axis") == 0) {
-			ax->quantity = -1;
-			for (int q = 0; q < n_names; q++)
-				if (strcmp(v, names[q]) == 0)
-					ax->quantity = q;
-			if (ax->quantity < 0)
-				return n_names == 10 ? "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z"
-				                     : "axis must be one of x y r slope_x slope_y tan_theta nrefl dtravel r_start z start_x start_y";
-			have_axis = 1;
-		} else if (strcmp(kv, "d") == 0) {
-			errno = 0;
-			ax->d = strtod(v, &end);
-			if (end == v || errno != 0 || *end != '\0')
-				return "d must be a distance in cm";
-		} else if (strcmp(kv, "centre") == 0) {
-			if (pc_hist_parse_pair(v, &ax->cx, &ax->cy) != 0)
-				return "centre must be CX:CY in cm";
-		} else if (strcmp(kv, "range") == 0) {
-			if (pc_hist_parse_pair(v, &ax->lo, &ax->hi) != 0)
-				return "range must be LO:HI";
-			have_range = 1;
-		} else if (strcmp(kv, "bins") == 0) {
-			const long n = strtol(v, &end, 10);
-			if (end == v || *end != '\0' || n < 0 || n > 1 << 24)
-				return "bins must be a count";
-			ax->n_bins = (int32_t)n;
-			have_bins = 1;
-		} else {
-			return "unknown key of an axis (axis, d, centre, range, bins)";
-		}
-	}
-	return (have_axis && have_range && have_bins) ? NULL : "an axis needs axis, range and bins";
-}
-
-/* the value of an energies= item into *list (malloc'd, NULL for "all") and *n: NULL, or what is wrong */
-static const char *pc_hist_parse_energies(const char *v, size_t n_energies, int32_t **list, int *n)
-{
-	static const char *const bad = "energies must be all or a list of energy indices";
-	free(*list);
-	*list = NULL;
-	*n = 0;
-	if (strcmp(v, "all") == 0)
-		return NULL;
-	*list = malloc(sizeof(int32_t) * (n_energies + 1));
-	while (*list != NULL && *v != '\0') {
-		char *end = NULL;
-		const long e = strtol(v, &end, 10);
-		if (end == v || (size_t)*n > n_energies)
-			return bad;
-		(*list)[(*n)++] = (e < -1 || e > 1 << 30) ? -1 : (int32_t)e;
-		v = end;
-		if (*v == ',') v++;
-		else if (*v != '\0') return bad;
-	}
-	return *n == 0 ? bad : NULL;
-}
-
-static int pc_hist_request_parse(struct pc_hist_request *r, size_t n_energies, polycap_error **error)
-{
-	memset(r, 0, sizeof(*r));
-	const char *env = getenv("POLYCAP_HIST");
-	if (env == NULL)
-		return 0;
-	r->set = 1;
-	char *buf = strdup(env), *save = NULL;
-	const char *bad = NULL;
-	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save)) {
-		if (strncmp(item, "axis=", 5) == 0) {
-			if (r->n_axes >= 17) { bad = "at most 16 axes"; break; }
-			bad = pc_hist_parse_axis(item, &r->axes[r->n_axes++], 10);
-		} else if (strncmp(item, "energies=", 9) == 0) {
-			bad = pc_hist_parse_energies(item + 9, n_energies, &r->energies, &r->n_energies);
-		} else {
-			bad = "every item must be an axis (axis=NAME,...) or energies=";
-		}
-	}
-	free(buf);
-	if (bad == NULL && r->n_axes == 0)
-		bad = "at least one axis is needed";
-	if (bad == NULL) {
-		r->spec.n_axes = r->n_axes;
-		r->spec.axes = r->axes;
-		r->spec.n_energies = r->n_energies;
-		r->spec.energies = r->energies;
-		if (pc_hip_hist_validate(&r->spec, n_energies) != PC_HIP_OK)
-			bad = pc_hip_last_error();
-	}
-	if (bad != NULL) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_HIST=%s: %s", env, bad);
-		free(r->energies);
-		r->energies = NULL;
-		return -1;
-	}
-	return 0;
-}
-
-/* POLYCAP_JOINT, e.g. "axis=x,d=0.5,range=-0.01:0.01,bins=256*axis=slope_x,range=-0.005:0.005,bins=256;axis=start_x,range=-0.3:0.3,bins=512*axis=start_y,range=-0.3:0.3,bins=512;energies=all":
- * joint histograms of the run (include/polycap-hip.h, pc_hip_joint_*).  Items are separated by ';': a pair (two axes of the
- * POLYCAP_HIST grammar joined by '*', u first; start_x and start_y are axes here too) or energies= as in POLYCAP_HIST.  Parsed and
- * validated before any device is used. */
-struct pc_joint_request {
-	int set;
-	pc_hip_joint_pair pairs[9];
-	int n_pairs;
-	int32_t *energies;
-	int n_energies;
-	pc_hip_joint_spec spec;
-};
-
-/* `value` into r (r->energies is the caller's to free): NULL, or what is wrong; a refusal of pc_hip_joint_validate is its message */
-static const char *pc_joint_request_parse_value(struct pc_joint_request *r, const char *value, size_t n_energies)
-{
-	static _Thread_local char why[160];      /* the item at fault */
-	memset(r, 0, sizeof(*r));
-	r->set = 1;
-	char *buf = strdup(value), *save = NULL;
-	const char *bad = NULL;
-	int n_item = 0;
-	for (char *item = strtok_r(buf, ";", &save); item != NULL && bad == NULL; item = strtok_r(NULL, ";", &save), n_item++) {
-		if (strncmp(item, "axis=", 5) == 0) {
-			char *star = strchr(item, '*');
-			if (r->n_pairs >= 9) { bad = "at most 8 pairs"; break; }
-			if (star == NULL || strncmp(star + 1, "axis=", 5) != 0 || strchr(star + 1, '*') != NULL)
-				bad = "a pair must be two axes joined by '*' (axis=NAME,...*axis=NAME,...)";
-			else {
-				*star = '\0';
-				pc_hip_joint_pair *pr = &r->pairs[r->n_pairs++];
-				bad = pc_hist_parse_axis(item, &pr->u, 12);
-				if (bad == NULL)
-					bad = pc_hist_parse_axis(star + 1, &pr->v, 12);
-			}
-		} else if (strncmp(item, "energies=", 9) == 0) {
-			bad = pc_hist_parse_energies(item + 9, n_energies, &r->energies, &r->n_energies);
-		} else {
-			bad = "every item must be a pair (axis=NAME,...*axis=NAME,...) or energies=";
-		}
-		if (bad != NULL) {
-			snprintf(why, sizeof why, "item %d: %s", n_item, bad);
-			bad = why;
-		}
-	}
-	free(buf);
-	if (bad == NULL && r->n_pairs == 0)
-		bad = "at least one pair is needed";
-	if (bad == NULL) {
-		r->spec.n_pairs = r->n_pairs;
-		r->spec.pairs = r->pairs;
-		r->spec.n_energies = r->n_energies;
-		r->spec.energies = r->energies;
-		if (pc_hip_joint_validate(&r->spec, n_energies) != PC_HIP_OK)
-			bad = pc_hip_last_error();
-	}
-	return bad;
-}
-
-static int pc_joint_request_parse(struct pc_joint_request *r, size_t n_energies, polycap_error **error)
-{
-	memset(r, 0, sizeof(*r));
-	const char *env = getenv("POLYCAP_JOINT");
-	if (env == NULL)
-		return 0;
-	const char *bad = pc_joint_request_parse_value(r, env, n_energies);
-	if (bad != NULL) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_JOINT=%s: %s", env, bad);
-		free(r->energies);
-		r->energies = NULL;
-		return -1;
-	}
-	return 0;
-}
-
-int pc_hip_joint_parse(const char *value, size_t n_energies, pc_hip_joint_pair *pairs, int32_t *n_pairs, int32_t *energies, int32_t *n_selected,
-	char *why, size_t why_len)
-{
-	struct pc_joint_request r;
-	const char *bad = value != NULL ? pc_joint_request_parse_value(&r, value, n_energies) : "value must not be NULL";
-	if (why != NULL && why_len > 0)
-		snprintf(why, why_len, "%s", bad != NULL ? bad : "");
-	if (bad == NULL) {
-		if (pairs != NULL) memcpy(pairs, r.pairs, sizeof(pc_hip_joint_pair)*(size_t)r.n_pairs);
-		if (n_pairs != NULL) *n_pairs = r.n_pairs;
-		if (energies != NULL && r.n_energies > 0) memcpy(energies, r.energies, sizeof(int32_t)*(size_t)r.n_energies);
-		if (n_selected != NULL) *n_selected = r.n_energies;
-	}
-	if (value != NULL)
-		free(r.energies);
-	return bad == NULL ? PC_HIP_OK : PC_HIP_ERR_INVALID;
-}
-
-/* POLYCAP_SELECT, e.g. "axis=r,d=0.5,centre=0:0,range=0:0.005;axis=nrefl,range=0:40,not": cuts through which every tally of the call is
- * filled (include/polycap-hip.h, pc_hip_select_*; the grammar is pc_hip_select_parse's).  Parsed and validated before any device is used. */
-struct pc_select_request {
-	int set;
-	pc_hip_select_cut cuts[8];
-	int32_t n_cuts;
-	pc_hip_select_spec spec;
-	int64_t records;               /* POLYCAP_SELECT_RECORDS=N: the result keeps the first N passing entries of every kind; 0: unset */
-};
-
-static int pc_select_request_parse(struct pc_select_request *r, polycap_error **error)
-{
-	memset(r, 0, sizeof(*r));
-	const char *env = getenv("POLYCAP_SELECT");
-	const char *rec = getenv("POLYCAP_SELECT_RECORDS");
-	if (rec != NULL) {
-		char *end = NULL;
-		errno = 0;
-		const long long v = strtoll(rec, &end, 10);
-		if (end == rec || *end != '\0' || errno != 0 || v < 1 || v > 2147483647ll) {
-			polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT_RECORDS=%s: must be an integer in 1 .. 2^31 - 1", rec);
-			return -1;
-		}
-		if (env == NULL) {
-			polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT_RECORDS=%s needs POLYCAP_SELECT: there is no selection to take the rows from", rec);
-			return -1;
-		}
-		r->records = (int64_t)v;
-	}
-	if (env == NULL)
-		return 0;
-	char why[320];
-	if (pc_hip_select_parse(env, r->cuts, &r->n_cuts, why, sizeof why) != PC_HIP_OK) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SELECT=%s: %s", env, why);
-		return -1;
-	}
-	r->set = 1;
-	r->spec.n_cuts = r->n_cuts;
-	r->spec.cuts = r->cuts;
-	return 0;
-}
-
-/* POLYCAP_DRAW, e.g. "n=100000,energy=3,phase=12345": the result carries an unweighted sample of n entries per kind, drawn at the
- * energy of that index (default 0) with that phase (default 0: the call stays reproducible) through the call's selection, or through
- * one that every entry passes when POLYCAP_SELECT is not set (include/polycap-hip.h, pc_hip_select_draw).  Parsed before any device is
- * used; the reason of a refusal names the item. */
-struct pc_draw_request {
-	int set;
-	int implicit;                  /* the selection of the call is the all-pass one made for the draw: the result reports none */
-	int64_t n;
-	int32_t energy;
-	uint32_t phase;
-};
-
-/* 0, or -1 with the reason in why */
-static int pc_draw_request_parse(struct pc_draw_request *r, size_t ne, char *why, size_t why_len)
-{
-	memset(r, 0, sizeof(*r));
-	why[0] = '\0';
-	const char *env = getenv("POLYCAP_DRAW");
-	if (env == NULL)
-		return 0;
-	int have_n = 0;
-	if (*env == '\0') {
-		snprintf(why, why_len, "the value is empty: n=N[,energy=INDEX][,phase=UINT32] is needed");
-		return -1;
-	}
-	for (const char *at = env; ; ) {
-		const char *comma = strchr(at, ',');
-		const size_t len = comma != NULL ? (size_t)(comma - at) : strlen(at);
-		char item[64];
-		if (len >= sizeof item) {
-			snprintf(why, why_len, "item %.40s...: unknown key (n, energy, phase)", at);
-			return -1;
-		}
-		memcpy(item, at, len);
-		item[len] = '\0';
-		char *eq = strchr(item, '=');
-		char *end = NULL;
-		errno = 0;
-		const long long v = eq != NULL ? strtoll(eq + 1, &end, 10) : 0;
-		const int number = eq != NULL && end != eq + 1 && *end == '\0' && errno == 0;
-		if (eq != NULL)
-			*eq = '\0';
-		if (eq == NULL || (strcmp(item, "n") != 0 && strcmp(item, "energy") != 0 && strcmp(item, "phase") != 0)) {
-			snprintf(why, why_len, "item %s: unknown key (n, energy, phase)", item);
-			return -1;
-		}
-		if (strcmp(item, "n") == 0) {
-			if (!number || v < 1 || v > 2147483647ll) {
-				snprintf(why, why_len, "n=%s: must be an integer in 1 .. 2^31 - 1", eq + 1);
-				return -1;
-			}
-			r->n = (int64_t)v;
-			have_n = 1;
-		} else if (strcmp(item, "energy") == 0) {
-			if (!number || v < 0 || v >= (long long)ne) {
-				snprintf(why, why_len, "energy=%s: must be an index into the source's %zu energies", eq + 1, ne);
-				return -1;
-			}
-			r->energy = (int32_t)v;
-		} else {
-			if (!number || v < 0 || v > 4294967295ll) {
-				snprintf(why, why_len, "phase=%s: must be a uint32", eq + 1);
-				return -1;
-			}
-			r->phase = (uint32_t)v;
-		}
-		if (comma == NULL)
-			break;
-		at = comma + 1;
-	}
-	if (!have_n) {
-		snprintf(why, why_len, "n is missing: the size of the sample, n=N");
-		return -1;
-	}
-	r->set = 1;
-	return 0;
 }
 
 /* the tallies of one call and the selection they are filled through (any may be NULL); tot: the selection's totals summed over the
@@ -1192,126 +684,6 @@ static const char *pc_transmission_args_bad(const polycap_source *source, const 
 		if (source->energies[i] < 1. || source->energies[i] > 100.)
 			return "source->energies[i] must be greater than 1 and less than 100";
 	return n_photons < 1 ? "n_photons must be greater than 1" : NULL;
-}
-
-/* Everything polycap_source_get_transmission_efficiencies takes from the environment, read by pc_run_request_parse before any device
- * is used.  These are extensions of the reference call, all through the environment so that the signature stays the reference's:
- *   POLYCAP_HIP_DEVICES=all | i,j,...  the photon loop is sharded over these devices from this one process (the reference's OpenMP
- *       team, :697-745, becomes a team of GPUs); totals are summed by one RCCL all-reduce (:973-980)
- *   POLYCAP_IMAGES=0                   histogram-only result: efficiencies and counts, no per-photon planes (at 1e8 photons x 291
- *       energies the weight plane alone is 233 GB); the start/exit getters then report no events
- * Numbers that do not parse fall back to their defaults; out-of-range option values fail when the option is set. */
-struct pc_run_request {
-	int timing;                /* POLYCAP_TIMING: stage times on stderr */
-	int tally_stderr_on;       /* POLYCAP_TALLY_STDERR=1: the tallies and the selection of the call track squares; unset or 0: not */
-	int stderr_on;             /* POLYCAP_STDERR=1: a standard error per energy (option "weight_squares"); unset or 0: none */
-	int beam_on;               /* POLYCAP_BEAM=1: exact exit-beam moments per energy (pc_hip_beam_*); unset or 0: none */
-	struct pc_spot_request spot;
-	struct pc_hist_request hist;   /* POLYCAP_HIST: exact 1-D histograms per energy (pc_hip_hist_*) */
-	struct pc_joint_request joint; /* POLYCAP_JOINT: exact joint 2-D histograms per energy (pc_hip_joint_*) */
-	struct pc_select_request select; /* POLYCAP_SELECT: cuts through which every tally is filled (pc_hip_select_*) */
-	struct pc_draw_request draw;   /* POLYCAP_DRAW: an unweighted sample of every kind (pc_hip_select_draw) */
-	int devices[64], n_devices;
-	int keep_images;
-	int run_parts;             /* POLYCAP_RUN_PARTS, for big plain runs with images only */
-	int compact;               /* POLYCAP_COMPACT, plain runs only */
-	int have_block_shift;      /* POLYCAP_BLOCK_SHIFT set (one device only) */
-	int64_t block_shift;
-	int rccl;                  /* POLYCAP_RCCL: 0 host sum, 1 RCCL or fail, -1 (unset) RCCL when possible */
-	uint32_t max_attempts;     /* POLYCAP_MAX_ATTEMPTS */
-	int have_seed;             /* POLYCAP_SEED given: seed, else derived from the source */
-	uint64_t seed;
-};
-
-static void pc_run_request_free(struct pc_run_request *r)
-{
-	free(r->spot.energies);
-	free(r->hist.energies);
-	free(r->joint.energies);
-}
-
-static int pc_run_request_parse(struct pc_run_request *r, size_t ne, int leak_calc, int n_photons, polycap_error **error)
-{
-	memset(r, 0, sizeof(*r));
-	r->timing = getenv("POLYCAP_TIMING") != NULL;
-	const char *stderr_env = getenv("POLYCAP_STDERR");
-	if (stderr_env != NULL && strcmp(stderr_env, "0") != 0 && strcmp(stderr_env, "1") != 0) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_STDERR=%s: must be 0 or 1", stderr_env);
-		return -1;
-	}
-	r->stderr_on = stderr_env != NULL && strcmp(stderr_env, "1") == 0;
-	const char *tally_env = getenv("POLYCAP_TALLY_STDERR");
-	if (tally_env != NULL && strcmp(tally_env, "0") != 0 && strcmp(tally_env, "1") != 0) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_TALLY_STDERR=%s: must be 0 or 1", tally_env);
-		return -1;
-	}
-	r->tally_stderr_on = tally_env != NULL && strcmp(tally_env, "1") == 0;
-	const char *beam_env = getenv("POLYCAP_BEAM");
-	if (beam_env != NULL && strcmp(beam_env, "0") != 0 && strcmp(beam_env, "1") != 0) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_BEAM=%s: must be 0 or 1", beam_env);
-		return -1;
-	}
-	r->beam_on = beam_env != NULL && strcmp(beam_env, "1") == 0;
-	if (pc_spot_request_parse(&r->spot, ne, error) != 0)
-		return -1;
-	if (pc_hist_request_parse(&r->hist, ne, error) != 0)
-		return -1;
-	if (pc_joint_request_parse(&r->joint, ne, error) != 0)
-		return -1;
-	if (pc_select_request_parse(&r->select, error) != 0)
-		return -1;
-	/* POLYCAP_DRAW is read here, for the selection it may need, and refused last: behind every other variable's refusal */
-	char draw_bad[256];
-	const int draw_st = pc_draw_request_parse(&r->draw, ne, draw_bad, sizeof draw_bad);
-	if (draw_st == 0 && r->draw.set && !r->select.set) {      /* no POLYCAP_SELECT: every entry passes, a reflection count in [0, 2^62) */
-		r->draw.implicit = 1;
-		r->select.cuts[0].axis.quantity = 6;      /* nrefl in the axis grammar of POLYCAP_HIST */
-		r->select.cuts[0].axis.lo = 0.;
-		r->select.cuts[0].axis.hi = 4611686018427387904.;
-		r->select.cuts[0].axis.n_bins = 1;
-		r->select.n_cuts = 1;
-		r->select.spec.n_cuts = 1;
-		r->select.spec.cuts = r->select.cuts;
-		r->select.set = 1;
-	}
-	if ((r->beam_on || r->hist.set || r->joint.set || r->select.set) && !r->spot.set) {      /* POLYCAP_SPOT_SHARE covers the chunked runs of beam moments and (joint) histograms too */
-		r->spot.share = 0.5;
-		const char *share = getenv("POLYCAP_SPOT_SHARE");
-		if (share != NULL && *share != '\0') {
-			char *end = NULL;
-			r->spot.share = strtod(share, &end);
-			if (*end != '\0' || !(r->spot.share > 0. && r->spot.share <= 1.)) {
-				polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_SPOT_SHARE=%s: must be a fraction in (0, 1]", share);
-				return -1;
-			}
-		}
-	}
-	if (pc_env_devices(r->devices, &r->n_devices, error) != 0)
-		return -1;
-	const char *img_env = getenv("POLYCAP_IMAGES");
-	r->keep_images = !(img_env != NULL && strcmp(img_env, "0") == 0);
-	if (leak_calc && !r->keep_images) {
-		polycap_set_error_literal(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_IMAGES=0 cannot be combined with leak_calc (leak events are per-photon data)");
-		return -1;
-	}
-	/* big plain runs are traced in four parts so that the images of a finished part cross PCIe while the next part runs */
-	r->run_parts = (!leak_calc && r->keep_images && n_photons >= 2000000) ? (int)pc_env_u64("POLYCAP_RUN_PARTS", 4, NULL) : 1;
-	/* Plain runs store their exit photons in the order of completion (option "compact_images": coalesced plane stores, blocks
-	 * copied to the host while the kernel runs); the reference's own order is the order in which randomly seeded threads fill
-	 * the arrays.  POLYCAP_COMPACT=0 keeps every photon at the position of its slot (reproducible order for a given POLYCAP_SEED). */
-	const char *compact_env = getenv("POLYCAP_COMPACT");
-	r->compact = !(compact_env != NULL && strcmp(compact_env, "0") == 0) && !leak_calc;
-	r->have_block_shift = getenv("POLYCAP_BLOCK_SHIFT") != NULL;
-	r->block_shift = (int64_t)pc_env_u64("POLYCAP_BLOCK_SHIFT", 18, NULL);
-	const char *rccl = getenv("POLYCAP_RCCL");
-	r->rccl = (rccl != NULL && *rccl != '\0') ? atoi(rccl) : -1;
-	r->max_attempts = (uint32_t)pc_env_u64("POLYCAP_MAX_ATTEMPTS", 1u << 20, NULL);
-	r->seed = pc_env_u64("POLYCAP_SEED", 0, &r->have_seed);
-	if (draw_st != 0) {
-		polycap_set_error(error, POLYCAP_ERROR_INVALID_ARGUMENT, "polycap_source_get_transmission_efficiencies: POLYCAP_DRAW=%s: %s", getenv("POLYCAP_DRAW"), draw_bad);
-		return -1;
-	}
-	return 0;
 }
 
 /* where a run goes: one device or a device group, exactly one of them set (both belong to the source's context cache) */

@@ -59,6 +59,10 @@ SELECT_VALUES = [
     "axis=x,range=0:1,never", "axis=x,range=0", "axis=x,range=0:1x", "axis=x,range=0:1,d=far", "axis=r,range=0:1,centre=0",
     "axis=x,range=0:1;axis=nrefl,d=0.5,range=0:40", "axis=x,range=1:0", "axis=x,centre=0.1:0,range=0:1", ";".join(["axis=z,range=0:1"] * 9),
 ]
+DRAW_VALUES = [
+    "", "n=10,colour=red", "n", "n=10," + "x" * 64, "energy=3", "energy=3,phase=1", "n=0", "n=2147483648", "n=ten", "n=10,energy=291",
+    "n=10,energy=-1", "n=10,energy=x", "n=10,phase=4294967296", "n=10,phase=-1", "n=10,phase=", "n=10,",
+]
 FLAG_VALUES = ["2", "yes", "", "01", " 1", "1.0", "-1", "on", "true"]
 BAD_SHARES = ["1.5", "0", "abc", "0.5x"]
 BAD_DEVICES = "1,x"
@@ -117,6 +121,13 @@ case("order-hist-before-share", {"POLYCAP_HIST": "", "POLYCAP_SPOT_SHARE": "2"})
 case("order-share-before-devices", {"POLYCAP_BEAM": "1", "POLYCAP_SPOT_SHARE": "2", "POLYCAP_HIP_DEVICES": BAD_DEVICES})
 case("order-devices-before-images", dict(LEAK_WITHOUT_IMAGES, POLYCAP_HIP_DEVICES=BAD_DEVICES), leak_calc=True)
 case("order-stderr-before-images", dict(LEAK_WITHOUT_IMAGES, POLYCAP_STDERR="2"), leak_calc=True)
+# POLYCAP_DRAW: an empty value counts as set; one refusal per key and the items' form; and it is refused last
+for i, v in enumerate(DRAW_VALUES):
+    case("draw-%d" % i, {"POLYCAP_DRAW": v})
+case("order-devices-before-draw", {"POLYCAP_DRAW": "n=0", "POLYCAP_HIP_DEVICES": BAD_DEVICES})
+case("order-images-before-draw", dict(LEAK_WITHOUT_IMAGES, POLYCAP_DRAW=""), leak_calc=True)
+case("order-share-before-draw", {"POLYCAP_DRAW": "n=0", "POLYCAP_BEAM": "1", "POLYCAP_SPOT_SHARE": "2"})
+case("bad-draw-makes-no-selection", {"POLYCAP_DRAW": "n=0", "POLYCAP_SPOT_SHARE": "2"})
 
 CHILD = """
 import json, sys

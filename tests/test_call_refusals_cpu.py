@@ -1,7 +1,7 @@
 """What polycap_source_get_transmission_efficiencies answers to a bad environment, string for string: tests/golden/call_refusals.json,
 recorded from a build of this code kept outside the tree (scripts/record_call_refusals.py), against the tree's build.  Every refusal
-happens before a device is used, so no GPU is needed.  The table pins the messages of every key of the POLYCAP_SPOT, _HIST, _JOINT and
-_SELECT grammars, the 0|1 flags, POLYCAP_SELECT_RECORDS, POLYCAP_SPOT_SHARE and POLYCAP_HIP_DEVICES, what an empty value means, and with
+happens before a device is used, so no GPU is needed.  The table pins the messages of every key of the POLYCAP_SPOT, _HIST, _JOINT,
+_SELECT and _DRAW grammars, the 0|1 flags, POLYCAP_SELECT_RECORDS, POLYCAP_SPOT_SHARE and POLYCAP_HIP_DEVICES, what an empty value means, and with
 two bad variables the order of validation: what a change to the host code of the call must keep, or reword on purpose (an entry marked
 "changed" then carries the new message, and the recorded one as "recorded")."""
 import json
@@ -15,7 +15,7 @@ with open(os.path.join(ROOT, "tests", "golden", "call_refusals.json")) as f:
     TABLE = json.load(f)
 
 VARIABLES = ["POLYCAP_STDERR", "POLYCAP_TALLY_STDERR", "POLYCAP_BEAM", "POLYCAP_SPOT", "POLYCAP_SPOT_SHARE", "POLYCAP_HIST", "POLYCAP_JOINT",
-             "POLYCAP_SELECT", "POLYCAP_SELECT_RECORDS", "POLYCAP_HIP_DEVICES", "POLYCAP_IMAGES"]
+             "POLYCAP_SELECT", "POLYCAP_SELECT_RECORDS", "POLYCAP_DRAW", "POLYCAP_HIP_DEVICES", "POLYCAP_IMAGES"]
 EXCEPTIONS = {"ValueError": ValueError}
 
 
