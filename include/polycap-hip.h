@@ -717,7 +717,7 @@ POLYCAP_EXTERN int pc_hip_group_scan_last_kernel(pc_hip_group *group, int k);
  * explicit-photon kernel of pc_hip_launch_photons, and leaves on B what a source run leaves there.
  *
  * The contract (IEEE fp64, evaluated in the order written, no contraction).  Placement = {gap, off_x, off_y} in cm, all finite,
- * gap >= 0: B's axis is parallel to A's and displaced by (off_x, off_y); gap is measured from A's exit plane (pc_exit_coords[2] of
+ * gap >= 0: B's axis is parallel to A's (a tilted B: posed relays, below) and displaced by (off_x, off_y); gap is measured from A's exit plane (pc_exit_coords[2] of
  * A's records) to B's z = 0.
  *   entries    the entries of A's store in the order of their positions (slot order; the order of completion after a run with
  *              "compact_images").  An entry whose slot failed is skipped and counted: it has pc_exit_coords[2] <= 0 (compact
@@ -763,6 +763,57 @@ POLYCAP_EXTERN int pc_hip_relay_totals(pc_hip_ctx *ctx_b, int64_t counters[8], u
  * (rc 2), not a factor.  With sumw2_fixed and stderr_ (both or neither): pc_hip_efficiency_stderr with N = n_started_A. */
 POLYCAP_EXTERN void pc_hip_relay_efficiencies(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed,
 	const int64_t counters[8], double *efficiencies, double *stderr_);
+
+/* ---- posed relays: the second optic tilted against the first one's axis (the other half of a confocal alignment: a rocking curve is
+ * a host loop over relays with one tilt each), and an aperture -- a pinhole, a slit, a beam stop -- between the two optics, given as
+ * a selection (above) on A's exit photons.  pc_hip_relay_placement and the four calls above stay as they are; a pose is one more
+ * placement of one relay.
+ *
+ * The frame.  In A's exit frame the origin is the centre of A's exit plane and z runs along A's axis.  B's entrance centre is at
+ * c = (off_x, off_y, gap); B's x, y and z axes are u, v, n, the columns of Ry(tilt_x) * Rx(-tilt_y) (radians): a positive tilt_x
+ * turns B's axis towards +x, a positive tilt_y towards +y.  With sx = sin(tilt_x), cx = cos(tilt_x), sy = sin(tilt_y), cy = cos(tilt_y):
+ *   u = (cx, 0, 0 - sx)      v = (0 - sx*sy, cy, 0 - cx*sy)      n = (sx*cy, sy, cx*cy)
+ * each entry one fp64 product (and one subtraction from 0, which keeps a zero's plus sign: tilt (0, 0) gives the identity bit for
+ * bit).  The basis is computed once on the host and travels to the kernels as nine doubles: no trigonometric function runs on the
+ * device, and pc_hip_pose_basis returns exactly these nine numbers (u0 u1 u2 v0 v1 v2 n0 n1 n2).
+ * A pose is valid when its five fields are finite, gap >= 0 and |tilt_x|, |tilt_y| < pi/2 strictly (below the double nearest pi/2).
+ *
+ * The contract replaces the "inject" step of a relay and adds two outcomes to "entries"; every other step is the relay's (IEEE
+ * fp64, in the order written, no contraction; (x, y), (dx, dy), (ex, ey) from A's record as above):
+ *   dz = sqrt((1 - dx*dx) - dy*dy),  ez = -(ex*dx + ey*dy) / dz
+ *   nd = (n0*dx + n1*dy) + n2*dz
+ *   np = (n0*(off_x - x) + n1*(off_y - y)) + n2*gap
+ *   missed when !(nd > 0) or !(np >= 0): the photon runs parallel to B's entrance plane or away from it, or the plane lies behind
+ *          it.  A missed photon is not injected, and is counted.  (nd > 0 is also what lets B's records keep two components of a
+ *          direction.)
+ *   t = np / nd
+ *   r = ((x + dx*t) - off_x, (y + dy*t) - off_y, dz*t - gap)
+ *   start in B's frame = ((u0*r0 + u1*r1) + u2*r2, (v0*r0 + v1*r1) + v2*r2, 0)
+ *   direction = ((u0*dx + u1*dy) + u2*dz, (v0*dx + v1*dy) + v2*dz, nd)
+ *   electric vector = ((u0*ex + u1*ey) + u2*ez, (v0*ex + v1*ey) + v2*ez, (n0*ex + n1*ey) + n2*ez)
+ * pc_exit_dtravel = (dA + t) + dB with this t; the records' start fields are the x, y components of this state.
+ *   selection  optional: a selection made on context A and applied for kind 0 to A's last run.  An exit photon (the entries'
+ *              predicate above) whose mask byte is clear is rejected: not injected, and counted in `rejected`, not in `skipped`.
+ *              The mask is asked before the flight: a rejected photon is never counted as missed
+ *   counts     entries of A's store = n_in + skipped + missed + rejected, for every relay.  The efficiency of the train stays
+ *              sum / (n_started_A 2^62): a photon the aperture stops or that misses B is a photon lost
+ *   zero tilt  a pose with both tilts 0 and no selection is the relay of {gap, off_x, off_y}: pc_hip_pose_run then runs what
+ *              pc_hip_relay_run runs (the arithmetic of "inject" above, not the general form with the identity, whose sums of products
+ *              may turn the sign of a zero), bit for bit in records, sums, squares and counters, with missed = rejected = 0
+ * Refused with PC_HIP_ERR_INVALID and a message, before anything is launched and with both contexts and the selection left as they
+ * were: what pc_hip_relay_run refuses; an invalid pose; a selection of another owner (context B, any other context, a group); a
+ * selection that was not applied for kind 0; a stale mask (the rule and the wording of pc_hip_select_gather). */
+typedef struct { double gap, off_x, off_y, tilt_x, tilt_y; } pc_hip_pose;
+/* host only: the pose alone */
+POLYCAP_EXTERN int pc_hip_pose_validate(const pc_hip_pose *pose);
+/* host only: u, v, n of a valid pose */
+POLYCAP_EXTERN int pc_hip_pose_basis(const pc_hip_pose *pose, double basis[9]);
+/* the relay of ctx_a's exit photons into ctx_b placed at `pose`, through `select` (NULL: no aperture); pc_hip_relay_totals and
+ * everything else that reads a relay's result apply as after pc_hip_relay_run */
+POLYCAP_EXTERN int pc_hip_pose_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_pose *pose, pc_hip_select *select);
+/* of the last relay into ctx_b: counts = {missed, rejected} (both 0 after pc_hip_relay_run).  PC_HIP_ERR_INVALID when the last call
+ * into ctx_b was not a relay. */
+POLYCAP_EXTERN int pc_hip_pose_counts(pc_hip_ctx *ctx_b, int64_t counts[2]);
 
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);

@@ -13,6 +13,7 @@ The package is a thin Python layer over libpolycap.so (host C + hand-written HIP
   * TraceContext.scan / scan_points -- transmission per source position (alignment curves, focal spot, depth response) in one
     launch, exact totals per point;
   * TraceContext.relay            -- the exit beam of one optic through a second one (confocal set-ups), on the GPU;
+    the second optic may be tilted and a Selection may stand between the two as an aperture (relay_rocking_curve);
   * polycap_amd.capi              -- ctypes mirror of the reference's C API (polycap_profile/_description/
     _source/_photon/...), i.e. what the reference's Cython module binds;
   * polycap_amd.distributed       -- one-process-per-GPU sharding of the slot range + RCCL reduce of the
@@ -23,7 +24,7 @@ from ._cabi import Problem, lib  # noqa: F401
 from .hip import TraceContext, TraceGroup, SpotMap, BeamMoments, Histograms, JointHistograms, Selection, select_cuts, select_parse, select_all, joint_marginal, joint_parse, hist_fwhm, hist_quantile, beam_params, HipError, device_count, efficiencies, efficiency_stderr, fixed_to_double, IMG_FIELDS  # noqa: F401
 from .hip import scan_points, scan_efficiencies  # noqa: F401
 from .hip import tally_stderr, select_transmission, pairs_sum  # noqa: F401
-from .hip import relay_efficiencies, relay_placement_valid, RELAY_COUNTERS  # noqa: F401
+from .hip import relay_efficiencies, relay_placement_valid, relay_basis, relay_rocking_curve, RELAY_COUNTERS  # noqa: F401
 from .decks import problem_from_inp, optical_constants, optical_constants_provider  # noqa: F401
 
 __version__ = "1.2"

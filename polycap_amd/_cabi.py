@@ -366,6 +366,14 @@ def lib():
     L.pc_hip_relay_totals.restype = C.c_int
     L.pc_hip_relay_efficiencies.argtypes = [C.c_size_t, u64p, u64p, c_int64_p, c_double_p, c_double_p]
     L.pc_hip_relay_efficiencies.restype = None
+    L.pc_hip_pose_validate.argtypes = [c_double_p]                           # pose: 5 doubles = pc_hip_pose
+    L.pc_hip_pose_validate.restype = C.c_int
+    L.pc_hip_pose_basis.argtypes = [c_double_p, c_double_p]
+    L.pc_hip_pose_basis.restype = C.c_int
+    L.pc_hip_pose_run.argtypes = [C.c_void_p, C.c_void_p, c_double_p, C.c_void_p]
+    L.pc_hip_pose_run.restype = C.c_int
+    L.pc_hip_pose_counts.argtypes = [C.c_void_p, c_int64_p]
+    L.pc_hip_pose_counts.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

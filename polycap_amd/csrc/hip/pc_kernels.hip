@@ -1177,6 +1177,7 @@ struct pc_hip_ctx {
 	pc_dev_buf<unsigned long long> d_relay_scan; /* per-wave counts and offsets of the two compactions, then the relay's device counters */
 	int relay_acc_lds = 1;                 /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
 	int64_t relay_counters[8] = {0};
+	int64_t relay_lost[2] = {0, 0};        /* of a posed relay: photons that missed the entrance plane, photons its selection rejected */
 	/* gathers of a selection's entries (pc_gather.h) */
 	int gather_tile = 0;                   /* option "gather_tile": entries per compaction tile, 0 = automatic */
 	long long gather_chunk_rows = 0;       /* option "gather_chunk_rows": rows per staging chunk, 0 = as many as fit in 128 MiB */

@@ -5,7 +5,9 @@
  * (include/polycap-hip.h, pc_hip_relay_*).  Nothing per-photon crosses PCIe: an inject kernel writes the second context's
  * explicit-launch inputs from the first one's store, the explicit-photon trace kernel runs over them as it does for
  * pc_hip_launch_photons, and a finish kernel multiplies the weights, adds the exact sums and compacts the transmitted photons, in
- * the order of their positions in the first store, into the second context's image records.
+ * the order of their positions in the first store, into the second context's image records.  A posed relay (pc_hip_pose_*) tilts
+ * the second optic and takes a selection of the first context as an aperture between the two: the same kernels with one more
+ * predicate -- selected, and not missing the tilted entrance plane -- evaluated alike where the photons are counted and injected.
  *
  * The first part (the per-photon arithmetic) compiles for the host as well: -DPC_RELAY_HOST_ONLY stops the header after it.
  */
@@ -44,6 +46,45 @@ static inline __host__ __device__ void pc_relay_fly(double x, double y, double d
 	out[9] = t;
 }
 
+/* The axes u, v, n of a tilted second optic in the first one's exit frame: the columns of Ry(tilt_x) * Rx(-tilt_y), written out as
+ * products of the four sines and cosines (basis = u0 u1 u2 v0 v1 v2 n0 n1 n2).  Host only: the kernels get the nine numbers.
+ * "0. - a" where a sign is turned, so that a zero keeps its plus sign and the basis of tilt (0, 0) is the identity bit for bit. */
+static inline void pc_relay_pose_basis(double tilt_x, double tilt_y, double *basis)
+{
+	const double sx = sin(tilt_x), cx = cos(tilt_x), sy = sin(tilt_y), cy = cos(tilt_y);
+	basis[0] = cx;            basis[1] = 0.; basis[2] = 0. - sx;
+	basis[3] = 0. - sx*sy;    basis[4] = cy; basis[5] = 0. - cx*sy;
+	basis[6] = sx*cy;         basis[7] = sy; basis[8] = cx*cy;
+}
+
+/* pc_relay_fly for a second optic with the axes `basis` (u, v, n) whose entrance centre is at (off_x, off_y, gap): the contract of
+ * include/polycap-hip.h, operation by operation.  Returns 1 and out = {x, y, z, dx, dy, dz, ex, ey, ez, t} in the second optic's
+ * frame, or 0 for a photon that misses the entrance plane (it runs parallel to the plane or away from it, or the plane lies
+ * behind it): out is then not written. */
+static inline __host__ __device__ int pc_relay_fly_posed(double x, double y, double dx, double dy, double ex, double ey,
+	double gap, double off_x, double off_y, const double *basis, double *out)
+{
+	const double *u = basis, *v = basis + 3, *n = basis + 6;
+	const double dz = sqrt((1. - dx*dx) - dy*dy);
+	const double ez = -(ex*dx + ey*dy) / dz;
+	const double nd = (n[0]*dx + n[1]*dy) + n[2]*dz;
+	const double np = (n[0]*(off_x - x) + n[1]*(off_y - y)) + n[2]*gap;
+	if (!(nd > 0.) || !(np >= 0.)) return 0;
+	const double t = np / nd;
+	const double r0 = (x + dx*t) - off_x, r1 = (y + dy*t) - off_y, r2 = dz*t - gap;
+	out[0] = (u[0]*r0 + u[1]*r1) + u[2]*r2;
+	out[1] = (v[0]*r0 + v[1]*r1) + v[2]*r2;
+	out[2] = 0.;
+	out[3] = (u[0]*dx + u[1]*dy) + u[2]*dz;
+	out[4] = (v[0]*dx + v[1]*dy) + v[2]*dz;
+	out[5] = nd;
+	out[6] = (u[0]*ex + u[1]*ey) + u[2]*ez;
+	out[7] = (v[0]*ex + v[1]*ey) + v[2]*ez;
+	out[8] = (n[0]*ex + n[1]*ey) + n[2]*ez;
+	out[9] = t;
+	return 1;
+}
+
 /* weight of a photon behind both optics: one fp64 product */
 static inline __host__ __device__ double pc_relay_weight(double w_a, double w_b)
 {
@@ -68,6 +109,20 @@ static inline __host__ __device__ int pc_relay_placement_ok(double gap, double o
 	return (gap >= 0. && gap <= 1.7976931348623157e308 && fabs(off_x) <= 1.7976931348623157e308 && fabs(off_y) <= 1.7976931348623157e308) ? 1 : 0;
 }
 
+/* the pose of the second optic: a placement and two finite tilts strictly inside (-pi/2, pi/2) (the double below is the nearest to
+ * pi/2) */
+static inline __host__ __device__ int pc_relay_pose_ok(double gap, double off_x, double off_y, double tilt_x, double tilt_y)
+{
+	return (pc_relay_placement_ok(gap, off_x, off_y) && fabs(tilt_x) < 1.5707963267948966 && fabs(tilt_y) < 1.5707963267948966) ? 1 : 0;
+}
+
+/* A pose without a tilt (either zero) and without a selection is a plain relay: it runs pc_relay_fly, not pc_relay_fly_posed with
+ * the identity, whose sums of products may turn the sign of a zero. */
+static inline __host__ __device__ int pc_relay_pose_plain(double tilt_x, double tilt_y, int selected)
+{
+	return (tilt_x == 0. && tilt_y == 0. && !selected) ? 1 : 0;
+}
+
 /* efficiency of the train of optics from the exact sum (lo, hi) and the photons started into the first optic: sum / (N 2^62) in
  * long double, 0 when nothing was started */
 static inline double pc_relay_efficiency(uint64_t lo, uint64_t hi, int64_t n_started)
@@ -79,11 +134,37 @@ static inline double pc_relay_efficiency(uint64_t lo, uint64_t hi, int64_t n_sta
 
 #ifndef PC_RELAY_HOST_ONLY
 
-struct pc_relay_place { double gap, off_x, off_y; };
+struct pc_relay_place { double gap, off_x, off_y, basis[9]; };      /* basis: u, v, n of a posed relay (pc_relay_pose_basis) */
 
 static __device__ __forceinline__ int pc_relay_src_valid(const pc_spot_src &s, long long i)
 {
 	return pc_relay_entry_valid(s.p[i*s.ss + (long long)PC_F_EXITZ*s.fs], s.w[i*s.ws]);
+}
+
+/* the injected state of entry i, which is an exit photon: o = pc_relay_fly's ten numbers, or pc_relay_fly_posed's (POSED), whose
+ * verdict is returned (0: the photon misses the second optic's entrance plane) */
+template <bool POSED>
+static __device__ __forceinline__ int pc_relay_src_fly(const pc_spot_src &s, const pc_relay_place &pl, long long i, double *o)
+{
+	const double *e = s.p + i*s.ss;
+	const double x = e[(long long)PC_F_EXITX*s.fs], y = e[(long long)PC_F_EXITY*s.fs], dx = e[(long long)PC_F_EDIRX*s.fs], dy = e[(long long)PC_F_EDIRY*s.fs];
+	const double ex = e[(long long)PC_F_EEVX*s.fs], ey = e[(long long)PC_F_EEVY*s.fs];
+	if (POSED) return pc_relay_fly_posed(x, y, dx, dy, ex, ey, pl.gap, pl.off_x, pl.off_y, pl.basis, o);
+	pc_relay_fly(x, y, dx, dy, ex, ey, pl.gap, pl.off_x, pl.off_y, o);
+	return 1;
+}
+
+/* What becomes of entry i of the first store -- the one predicate of the count and the inject kernels, which recompute it from the
+ * entry: the same operations give the same bits.  PC_RELAY_SKIP: no exit photon (a failed slot); PC_RELAY_INJECT: o = its state at
+ * the second optic; posed relays only: PC_RELAY_REJECT: the selection's mask byte (s.mask, NULL = none) is clear; PC_RELAY_MISS: it
+ * misses the entrance plane. */
+enum { PC_RELAY_SKIP = 0, PC_RELAY_INJECT = 1, PC_RELAY_REJECT = 2, PC_RELAY_MISS = 3 };
+template <bool POSED>
+static __device__ __forceinline__ int pc_relay_entry(const pc_spot_src &s, const pc_relay_place &pl, long long i, double *o)
+{
+	if (!pc_relay_src_valid(s, i)) return PC_RELAY_SKIP;
+	if (POSED && s.mask && !s.mask[i]) return PC_RELAY_REJECT;
+	return pc_relay_src_fly<POSED>(s, pl, i, o) ? PC_RELAY_INJECT : PC_RELAY_MISS;
 }
 
 /* Stable compaction, step 1: how many of the 64 items of every wave are kept.  rc == NULL: item i is entry i of the first store,
@@ -95,6 +176,22 @@ __global__ void __launch_bounds__(256) pc_relay_count_kernel(pc_spot_src s, cons
 	const int keep = (i < n) ? (rc ? (rc[i] == 1) : pc_relay_src_valid(s, i)) : 0;
 	const unsigned long long m = __ballot(keep);
 	if ((threadIdx.x & 63) == 0 && i < n) counts[i >> 6] = (unsigned long long)__popcll(m);
+}
+
+/* Step 1 of a posed relay over the first store: an entry is kept when pc_relay_entry injects it; lost[0] += the photons that miss
+ * the entrance plane, lost[1] += those the selection rejects, one atomic per wave that has any. */
+__global__ void __launch_bounds__(256) pc_relay_count_posed_kernel(pc_spot_src s, pc_relay_place pl, long long n, unsigned long long *counts,
+	unsigned long long *lost)
+{
+	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+	double o[10];
+	const int what = (i < n) ? pc_relay_entry<true>(s, pl, i, o) : PC_RELAY_SKIP;
+	const unsigned long long m = __ballot(what == PC_RELAY_INJECT), mm = __ballot(what == PC_RELAY_MISS), mr = __ballot(what == PC_RELAY_REJECT);
+	if ((threadIdx.x & 63) == 0 && i < n) {
+		counts[i >> 6] = (unsigned long long)__popcll(m);
+		if (mm) atomicAdd(&lost[0], (unsigned long long)__popcll(mm));
+		if (mr) atomicAdd(&lost[1], (unsigned long long)__popcll(mr));
+	}
 }
 
 /* Step 2, one workgroup: counts[0 .. nw) -> their exclusive prefix sums in place, counts[nw] = the total */
@@ -127,22 +224,20 @@ __global__ void __launch_bounds__(1024) pc_relay_scan_kernel(unsigned long long 
 	if (tid == 0) counts[nw] = carry;
 }
 
-/* Inject: every exit photon of the first store becomes one explicit photon of the second context, at the position the prefix
- * sums give it (the order of the store); map[position] = its entry.  Reads are coalesced when the store is planes and strided by
- * the record when it is records. */
+/* Inject: every entry of the first store that pc_relay_entry injects becomes one explicit photon of the second context, at the
+ * position the prefix sums give it (the order of the store); map[position] = its entry.  Reads are coalesced when the store is
+ * planes and strided by the record when it is records. */
+template <bool POSED>
 __global__ void __launch_bounds__(256) pc_relay_inject_kernel(pc_spot_src s, pc_relay_place pl, const unsigned long long *offs, long long n,
 	double *in_start, double *in_dir, double *in_elecv, long long *map)
 {
 	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	const int keep = (i < n) ? pc_relay_src_valid(s, i) : 0;
+	double o[10];
+	const int keep = (i < n) ? (pc_relay_entry<POSED>(s, pl, i, o) == PC_RELAY_INJECT) : 0;
 	const unsigned long long m = __ballot(keep);
 	if (!keep) return;
 	const int lane = threadIdx.x & 63;
 	const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
-	const double *e = s.p + i*s.ss;
-	double o[10];
-	pc_relay_fly(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
-	             e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, o);
 	in_start[3*pos] = o[0]; in_start[3*pos + 1] = o[1]; in_start[3*pos + 2] = o[2];
 	in_dir[3*pos] = o[3]; in_dir[3*pos + 1] = o[4]; in_dir[3*pos + 2] = o[5];
 	in_elecv[3*pos] = o[6]; in_elecv[3*pos + 1] = o[7]; in_elecv[3*pos + 2] = o[8];
@@ -159,6 +254,7 @@ struct pc_relay_stage2 {          /* what the explicit-photon trace left in the 
  * squares' when sumw2 is given) and its image record at the position the prefix sums give it.  A wave takes 64 consecutive
  * photons at a time; the sums of a workgroup are gathered in LDS (acc_lds) when they fit, else go to the global pairs at once.
  * Integer sums only: the totals depend on the set of photons, not on the launch shape. */
+template <bool POSED>
 __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_relay_place pl, pc_relay_stage2 b, const long long *map,
 	const unsigned long long *offs, long long n_in, int ne, int acc_lds, double *rec_out, pc_totals *totals, unsigned long long *sumw,
 	unsigned long long *sumw2, unsigned long long *relay_cnt)
@@ -195,8 +291,7 @@ __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_
 			/* the injected state again, from A's entry: the same operations give the same bits as the inject kernel wrote, and the
 			 * flight t, which the batch buffer does not hold, comes with them */
 			double o[10];
-			pc_relay_fly(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
-			             e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, o);
+			(void)pc_relay_src_fly<POSED>(s, pl, ia, o);
 			const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
 			r = rec_out + pos*recd;
 			const long long n_a = ((const long long *)e)[(long long)PC_F_NREFL*s.fs], n_b = b.irefl[i];
@@ -265,27 +360,163 @@ static int pc_relay_compact_offsets(pc_hip_ctx *b, const pc_spot_src &s, const i
 	return PC_HIP_OK;
 }
 
-/* everything that can refuse a relay, before anything is launched */
-static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement *pl)
+/* the counts and prefix sums of a posed relay over the first store (pc_relay_count_posed_kernel); lost = {missed, rejected} */
+static int pc_relay_posed_offsets(pc_hip_ctx *b, const pc_spot_src &s, const pc_relay_place &pl, long long n, unsigned long long *d_lost,
+	long long *total, long long lost[2])
 {
-	if (!a || !b) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts must not be NULL");
-	if (a == b) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the second optic needs a context of its own");
-	int st = pc_hip_relay_validate(pl);
-	if (st) return st;
+	const long long nw = (n + 63)/64;
+	PC_HIP_CHECK(hipMemsetAsync(d_lost, 0, 2*sizeof(unsigned long long), b->stream));
+	hipLaunchKernelGGL(pc_relay_count_posed_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, b->stream, s, pl, n, (unsigned long long *)b->d_relay_scan, d_lost);
+	PC_HIP_CHECK(hipGetLastError());
+	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, (unsigned long long *)b->d_relay_scan, nw);
+	PC_HIP_CHECK(hipGetLastError());
+	unsigned long long t = 0, l[2] = {0, 0};
+	PC_HIP_CHECK(hipMemcpyAsync(&t, b->d_relay_scan + nw, sizeof(t), hipMemcpyDeviceToHost, b->stream));
+	PC_HIP_CHECK(hipMemcpyAsync(l, d_lost, sizeof(l), hipMemcpyDeviceToHost, b->stream));
+	PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+	*total = (long long)t;
+	lost[0] = (long long)l[0]; lost[1] = (long long)l[1];
+	return PC_HIP_OK;
+}
+
+/* the contexts of a relay */
+static int pc_relay_check_pair(pc_hip_ctx *a, pc_hip_ctx *b, const std::string &w)
+{
+	if (!a || !b) return pc_fail(PC_HIP_ERR_INVALID, w + ": the contexts must not be NULL");
+	if (a == b) return pc_fail(PC_HIP_ERR_INVALID, w + ": the second optic needs a context of its own");
+	return PC_HIP_OK;
+}
+
+/* everything else that can refuse a relay, before anything is launched */
+static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const std::string &w)
+{
 	if (a->device != b->device)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the contexts are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
 	if (a->energies.size() != b->energies.size() || memcmp(a->energies.data(), b->energies.data(), a->energies.size()*sizeof(double)) != 0)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the contexts need the same energy grid, bit for bit");
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the contexts need the same energy grid, bit for bit");
 	switch (a->last_call) {
 	case PC_CALL_RUN: break;
-	case PC_CALL_RUN_LEAK: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last run was a leak_calc run");
-	case PC_CALL_EXPLICIT: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last call was an explicit-photon launch, not a source run");
-	case PC_CALL_SCAN: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last call was a scan, not a source run");
-	case PC_CALL_RELAY: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context holds the result of a relay, not of a source run");
-	default: return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context has made no source run");
+	case PC_CALL_RUN_LEAK: return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context's last run was a leak_calc run");
+	case PC_CALL_EXPLICIT: return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context's last call was an explicit-photon launch, not a source run");
+	case PC_CALL_SCAN: return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context's last call was a scan, not a source run");
+	case PC_CALL_RELAY: return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context holds the result of a relay, not of a source run");
+	default: return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context has made no source run");
 	}
 	if (!a->img.valid)
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: the first context's last run kept no exit photons (run it with keep_images)");
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context's last run kept no exit photons (run it with keep_images)");
+	return PC_HIP_OK;
+}
+
+/* the selection of a posed relay: the first context's own, applied for kind 0 to the entries s that the relay reads (the rule and
+ * the wording of pc_hip_select_gather) */
+static int pc_relay_check_select(const pc_hip_ctx *a, const pc_hip_select *sel, const pc_spot_src &s, const std::string &w)
+{
+	if (sel->group || sel->m.size() != 1 || sel->m[0].ctx != a)
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the selection belongs to another owner than the first context (make it on that context, not on a group or on the second context)");
+	if (!sel->applied[0])
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the selection was not applied for kind 0 (pc_hip_select_apply)");
+	if (sel->m[0].epoch[0] != a->entries_epoch || sel->m[0].n[0] != s.n)
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": the selection's mask is stale: the entries of kind 0 were replaced after it was applied");
+	return PC_HIP_OK;
+}
+
+/* A relay behind its placement check.  basis == NULL: a plain relay (pc_relay_fly, every exit photon); else a posed one
+ * (pc_relay_fly_posed; sel, optional, stands between the optics). */
+static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double gap, double off_x, double off_y, const double *basis, pc_hip_select *sel)
+{
+	const std::string w(who);
+	const bool posed = basis != nullptr;
+	int st = pc_relay_check(a, b, w);
+	if (st) return st;
+	PC_HIP_CHECK(hipSetDevice(a->device));
+	/* the first run is complete (and the apply of the selection behind it), and nothing of the second context is in flight */
+	st = pc_hip_transmission_wait(a, nullptr);
+	if (!st) st = pc_hip_transmission_wait(b, nullptr);
+	if (st) return st;
+	int64_t cnt_a[6];
+	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
+	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
+	pc_spot_src s;
+	st = pc_spot_source(a, 0, s, who);
+	if (st) return st;
+	if (sel) {
+		st = pc_relay_check_select(a, sel, s, w);
+		if (st) return st;
+		s.mask = sel->m[0].d_mask[0];
+	}
+	const long long n_a = s.n;
+	const int ne = b->host.pm.n_energies;
+	pc_relay_place pl = { gap, off_x, off_y, { 1., 0., 0., 0., 1., 0., 0., 0., 1. } };
+	if (posed) memcpy(pl.basis, basis, sizeof(pl.basis));
+
+	/* from here on the second context holds the relay, or nothing */
+	b->img.reset(); b->leak_events_of_run = 0; b->last_run_plain = 0;
+	b->entries_epoch++;
+	b->last_call = PC_CALL_NONE;
+	b->run_pending = 0; b->run_slots = 0;
+	b->run_squares = b->opts.weight_squares;
+	b->last_ms = 0.f;
+	const size_t nw_a = (size_t)((n_a + 63)/64);
+	/* counts and offsets [nw_a + 1], the finish kernel's counters [8] behind the second compaction's, the posed count's two last */
+	st = b->d_relay_scan.grow(nw_a + 1 + 8 + 2, (w + ": could not allocate the compaction counters").c_str());
+	if (!st) st = b->d_relay_map.grow((size_t)n_a, (w + ": could not allocate the photon map").c_str());
+	if (st) return st;
+
+	long long n_in = 0, n_out = 0, lost[2] = {0, 0};
+	st = posed ? pc_relay_posed_offsets(b, s, pl, n_a, b->d_relay_scan + nw_a + 1 + 8, &n_in, lost) : pc_relay_compact_offsets(b, s, nullptr, n_a, &n_in);
+	if (st) return st;
+	const long long skipped = n_a - n_in - lost[0] - lost[1];
+	/* The predicate reads the first weight only.  Every entry it skips must be a failed slot of A's run: a grid whose first
+	 * energy has no valid constants, or a first weight that underflowed to 0, would otherwise vanish without a word */
+	if (skipped != cnt_a[4])
+		return pc_fail(PC_HIP_ERR_INVALID, w + ": " + std::to_string(skipped) + " entries of the first run have no exit plane or a zero first weight, but "
+		               + std::to_string(cnt_a[4]) + " of its slots failed: exit photons with a zero first weight cannot be relayed");
+	unsigned long long h_cnt[8] = {0};
+	if (n_in > 0) {
+		pc_batch bt;
+		st = pc_batch_layout(b, n_in, false, bt);
+		if (st) return st;
+		hipLaunchKernelGGL(posed ? pc_relay_inject_kernel<true> : pc_relay_inject_kernel<false>, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
+		                   (const unsigned long long *)b->d_relay_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)b->d_relay_map);
+		PC_HIP_CHECK(hipGetLastError());
+		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
+		st = pc_batch_trace(b, bt, 0);
+		if (st) return st;
+		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
+		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
+		if (st) return st;
+		st = b->img.keep_records(n_out, (w + ": could not allocate the image records").c_str());
+		if (st) return st;
+		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
+		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
+		unsigned long long *sumw = (unsigned long long *)(b->d_totals + 1);
+		unsigned long long *sumw2 = b->opts.weight_squares ? sumw + 2*(size_t)ne : nullptr;
+		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
+		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
+		long long grid = (n_in + 255)/256;
+		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
+		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
+		hipLaunchKernelGGL(posed ? pc_relay_finish_kernel<true> : pc_relay_finish_kernel<false>, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
+		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
+		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
+		PC_HIP_CHECK(hipGetLastError());
+		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+		float ms = 0.f;
+		PC_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+		b->last_ms = ms;
+	} else {
+		/* nothing to trace (pc_batch_trace clears the totals otherwise) */
+		PC_HIP_CHECK(hipMemsetAsync(b->d_totals, 0, b->totals_bytes, b->stream));
+		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
+	}
+	for (int k = 0; k < 6; k++) b->relay_counters[k] = (int64_t)h_cnt[k];
+	b->relay_counters[6] = skipped;
+	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
+	b->relay_lost[0] = lost[0]; b->relay_lost[1] = lost[1];
+	b->run_slots = n_out;
+	b->img.valid = 1;
+	b->last_call = PC_CALL_RELAY;
 	return PC_HIP_OK;
 }
 
@@ -301,88 +532,46 @@ int pc_hip_relay_validate(const pc_hip_relay_placement *pl)
 
 int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement *placement)
 {
-	int st = pc_relay_check(a, b, placement);
+	int st = pc_relay_check_pair(a, b, "pc_hip_relay_run");
+	if (!st) st = pc_hip_relay_validate(placement);
 	if (st) return st;
-	PC_HIP_CHECK(hipSetDevice(a->device));
-	/* the first run is complete, and nothing of the second context is in flight */
-	st = pc_hip_transmission_wait(a, nullptr);
-	if (!st) st = pc_hip_transmission_wait(b, nullptr);
-	if (st) return st;
-	int64_t cnt_a[6];
-	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
-	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
-	pc_spot_src s;
-	st = pc_spot_source(a, 0, s, "pc_hip_relay_run");
-	if (st) return st;
-	const long long n_a = s.n;
-	const int ne = b->host.pm.n_energies;
-	const pc_relay_place pl = { placement->gap, placement->off_x, placement->off_y };
+	return pc_relay_run(a, b, "pc_hip_relay_run", placement->gap, placement->off_x, placement->off_y, nullptr, nullptr);
+}
 
-	/* from here on the second context holds the relay, or nothing */
-	b->img.reset(); b->leak_events_of_run = 0; b->last_run_plain = 0;
-	b->entries_epoch++;
-	b->last_call = PC_CALL_NONE;
-	b->run_pending = 0; b->run_slots = 0;
-	b->run_squares = b->opts.weight_squares;
-	b->last_ms = 0.f;
-	const size_t nw_a = (size_t)((n_a + 63)/64);
-	st = b->d_relay_scan.grow(nw_a + 1 + 8, "pc_hip_relay_run: could not allocate the compaction counters");
-	if (!st) st = b->d_relay_map.grow((size_t)n_a, "pc_hip_relay_run: could not allocate the photon map");
-	if (st) return st;
+int pc_hip_pose_validate(const pc_hip_pose *pose)
+{
+	if (!pose) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_validate: pose must not be NULL");
+	if (!pc_relay_pose_ok(pose->gap, pose->off_x, pose->off_y, pose->tilt_x, pose->tilt_y))
+		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_validate: gap must be finite and >= 0, off_x and off_y finite, |tilt_x| and |tilt_y| below pi/2");
+	return PC_HIP_OK;
+}
 
-	long long n_in = 0, n_out = 0;
-	st = pc_relay_compact_offsets(b, s, nullptr, n_a, &n_in);
+int pc_hip_pose_basis(const pc_hip_pose *pose, double basis[9])
+{
+	if (!basis) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_basis: basis must not be NULL");
+	const int st = pc_hip_pose_validate(pose);
 	if (st) return st;
-	/* The predicate reads the first weight only.  Every entry it skips must be a failed slot of A's run: a grid whose first
-	 * energy has no valid constants, or a first weight that underflowed to 0, would otherwise vanish without a word */
-	if (n_a - n_in != cnt_a[4])
-		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_run: " + std::to_string(n_a - n_in) + " entries of the first run have no exit plane or a zero first weight, but "
-		               + std::to_string(cnt_a[4]) + " of its slots failed: exit photons with a zero first weight cannot be relayed");
-	unsigned long long h_cnt[8] = {0};
-	if (n_in > 0) {
-		pc_batch bt;
-		st = pc_batch_layout(b, n_in, false, bt);
-		if (st) return st;
-		hipLaunchKernelGGL(pc_relay_inject_kernel, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
-		                   (const unsigned long long *)b->d_relay_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)b->d_relay_map);
-		PC_HIP_CHECK(hipGetLastError());
-		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
-		st = pc_batch_trace(b, bt, 0);
-		if (st) return st;
-		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
-		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
-		if (st) return st;
-		st = b->img.keep_records(n_out, "pc_hip_relay_run: could not allocate the image records");
-		if (st) return st;
-		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
-		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
-		unsigned long long *sumw = (unsigned long long *)(b->d_totals + 1);
-		unsigned long long *sumw2 = b->opts.weight_squares ? sumw + 2*(size_t)ne : nullptr;
-		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
-		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
-		long long grid = (n_in + 255)/256;
-		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
-		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
-		hipLaunchKernelGGL(pc_relay_finish_kernel, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
-		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
-		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
-		PC_HIP_CHECK(hipGetLastError());
-		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-		float ms = 0.f;
-		PC_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-		b->last_ms = ms;
-	} else {
-		/* nothing to trace (pc_batch_trace clears the totals otherwise) */
-		PC_HIP_CHECK(hipMemsetAsync(b->d_totals, 0, b->totals_bytes, b->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-	}
-	for (int k = 0; k < 6; k++) b->relay_counters[k] = (int64_t)h_cnt[k];
-	b->relay_counters[6] = n_a - n_in;
-	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
-	b->run_slots = n_out;
-	b->img.valid = 1;
-	b->last_call = PC_CALL_RELAY;
+	pc_relay_pose_basis(pose->tilt_x, pose->tilt_y, basis);
+	return PC_HIP_OK;
+}
+
+int pc_hip_pose_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_pose *pose, pc_hip_select *select)
+{
+	int st = pc_relay_check_pair(a, b, "pc_hip_pose_run");
+	if (!st) st = pc_hip_pose_validate(pose);
+	if (st) return st;
+	if (pc_relay_pose_plain(pose->tilt_x, pose->tilt_y, select != nullptr))
+		return pc_relay_run(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, nullptr, nullptr);
+	double basis[9];
+	pc_relay_pose_basis(pose->tilt_x, pose->tilt_y, basis);
+	return pc_relay_run(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, basis, select);
+}
+
+int pc_hip_pose_counts(pc_hip_ctx *ctx, int64_t counts[2])
+{
+	if (!ctx || !counts) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_counts: ctx and counts must not be NULL");
+	if (ctx->last_call != PC_CALL_RELAY) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_counts: the context's last call was not a relay into it");
+	counts[0] = ctx->relay_lost[0]; counts[1] = ctx->relay_lost[1];
 	return PC_HIP_OK;
 }
 

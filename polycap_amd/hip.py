@@ -283,20 +283,31 @@ class TraceContext:
             raise HipError("pc_hip_leak_slot_units", st)
         return u
 
-    def relay(self, other, gap, offset=(0., 0.)):
+    def relay(self, other, gap, offset=(0., 0.), tilt=(0., 0.), select=None):
         """Relays the exit photons of this context's last source run (made with keep_images) through the optic of `other`, a
         context on the same device with the same energy grid whose z = 0 lies `gap` cm behind this optic's exit plane, its axis
         displaced by `offset` = (x, y) cm (pc_hip_relay_run; the contract is in include/polycap-hip.h).  Nothing per-photon
-        leaves the device.  Returns efficiencies of the train per energy, efficiency_stderr (option "weight_squares" on `other`,
-        else None), counters by name (RELAY_COUNTERS), sum_weights, sumw_fixed [ne, 2], sumw2_fixed or None, n_records and
-        kernel_ms of the second stage's trace.  Afterwards other.records() / images(), SpotMap(other, ...) and
-        BeamMoments(other) describe the beam behind the second optic."""
+        leaves the device.  With `tilt` = (x, y) rad the second optic's axis is turned towards +x and +y, and `select`, a Selection
+        of this context applied to its exit photons, stands between the two optics as an aperture: only the photons it passes
+        are relayed (pc_hip_pose_run; with the defaults the call is the one it was).  Returns efficiencies of the train per energy,
+        efficiency_stderr (option "weight_squares" on `other`, else None), counters by name (RELAY_COUNTERS, and missed and
+        rejected), sum_weights, sumw_fixed [ne, 2], sumw2_fixed or None, n_records and kernel_ms of the second stage's trace.
+        Afterwards other.records() / images(), SpotMap(other, ...) and BeamMoments(other) describe the beam behind the second
+        optic."""
         if not isinstance(other, TraceContext):
             raise TypeError("relay: other must be a TraceContext")
-        pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
-        st = self._L.pc_hip_relay_run(self._h, other._h, dptr(pl))
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_relay_run", st)
+        if select is not None and not isinstance(select, Selection):
+            raise TypeError("relay: select must be a Selection")
+        tilt = (float(tilt[0]), float(tilt[1]))
+        if select is None and tilt == (0., 0.):
+            pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
+            st = self._L.pc_hip_relay_run(self._h, other._h, dptr(pl))
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_relay_run", st)
+        else:
+            st = self._L.pc_hip_pose_run(self._h, other._h, dptr(_pose(gap, offset, tilt)), None if select is None else select._h)
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_pose_run", st)
         other._relay_squares = getattr(other, "_weight_squares", False)      # as the relay was made, whatever the option is set to later
         r = other.relay_totals()
         other._last_n = r["n_records"]
@@ -314,8 +325,13 @@ class TraceContext:
         st = self._L.pc_hip_relay_totals(self._h, cnt.ctypes.data_as(c_int64_p), a.ctypes.data_as(u64p), b.ctypes.data_as(u64p) if sq else None)
         if st != _cabi.PC_HIP_OK:
             raise HipError("pc_hip_relay_totals", st)
+        lost = np.zeros(2, dtype=np.int64)
+        st = self._L.pc_hip_pose_counts(self._h, lost.ctypes.data_as(c_int64_p))
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_pose_counts", st)
         eff, err = relay_efficiencies(a, b, cnt)
-        return dict(efficiencies=eff, efficiency_stderr=err, counters=dict(zip(RELAY_COUNTERS, (int(v) for v in cnt))),
+        counters = dict(zip(RELAY_COUNTERS, (int(v) for v in cnt)), missed=int(lost[0]), rejected=int(lost[1]))
+        return dict(efficiencies=eff, efficiency_stderr=err, counters=counters,
                     counters_array=cnt, sum_weights=np.array([fixed_to_double(a[2 * e], a[2 * e + 1]) for e in range(ne)]),
                     sumw_fixed=a.reshape(ne, 2), sumw2_fixed=None if b is None else b.reshape(ne, 2), n_records=int(cnt[1]))
 
@@ -455,10 +471,42 @@ class TraceGroup:
 RELAY_COUNTERS = ("n_in", "exit", "absorbed", "glass", "outside", "error", "skipped", "n_started_a")
 
 
-def relay_placement_valid(gap, offset=(0., 0.)):
-    """True when pc_hip_relay_validate accepts the placement (host only)."""
-    pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
-    return _cabi.lib().pc_hip_relay_validate(dptr(pl)) == _cabi.PC_HIP_OK
+def _pose(gap, offset, tilt):
+    return np.array([float(gap), float(offset[0]), float(offset[1]), float(tilt[0]), float(tilt[1])], dtype=np.float64)
+
+
+def relay_placement_valid(gap, offset=(0., 0.), tilt=(0., 0.)):
+    """True when pc_hip_relay_validate accepts the placement, or with a `tilt` pc_hip_pose_validate the pose (host only)."""
+    if tuple(tilt) == (0., 0.):
+        pl = np.array([float(gap), float(offset[0]), float(offset[1])], dtype=np.float64)
+        return _cabi.lib().pc_hip_relay_validate(dptr(pl)) == _cabi.PC_HIP_OK
+    return _cabi.lib().pc_hip_pose_validate(dptr(_pose(gap, offset, tilt))) == _cabi.PC_HIP_OK
+
+
+def relay_basis(gap, offset, tilt):
+    """The axes u, v, n of the second optic of a tilted relay in the first one's exit frame, float64 [9] = u0 u1 u2 v0 v1 v2 n0 n1 n2
+    (pc_hip_pose_basis, host only): the nine numbers the kernels get."""
+    b = np.zeros(9)
+    st = _cabi.lib().pc_hip_pose_basis(dptr(_pose(gap, offset, tilt)), dptr(b))
+    if st != _cabi.PC_HIP_OK:
+        raise HipError("pc_hip_pose_basis", st)
+    return b
+
+
+def relay_rocking_curve(ctx_a, ctx_b, gap, tilts, offset=(0., 0.), select=None):
+    """A rocking curve of the second optic: one relay of ctx_a's last run into ctx_b per (tilt_x, tilt_y) of `tilts`, a host loop.
+    Returns tilts [n, 2], efficiencies [n, n_energies], efficiency_stderr [n, n_energies] (option "weight_squares" on ctx_b, else
+    None) and the relays' counters as a list of dicts."""
+    tl = np.asarray(tilts, dtype=np.float64).reshape(-1, 2)
+    eff, err, cnt = [], [], []
+    for tx, ty in tl:
+        r = ctx_a.relay(ctx_b, gap, offset, (tx, ty), select)
+        eff.append(r["efficiencies"])
+        err.append(r["efficiency_stderr"])
+        cnt.append(r["counters"])
+    have = len(err) > 0 and all(e is not None for e in err)
+    return dict(tilts=tl, efficiencies=np.array(eff).reshape(len(tl), -1), efficiency_stderr=np.array(err).reshape(len(tl), -1) if have else None,
+                counters=cnt)
 
 
 def relay_efficiencies(sumw_fixed, sumw2_fixed, counters):
