@@ -564,7 +564,7 @@ pc_trace_kernel(pc_kargs a)
 					if (rc == 0) f_not_trans = 1;
 					else if (rc == 2) f_not_entered = 1;
 					else if (rc == 1) ok = pc_in_exit_window(Pm, ph);
-					/* what a leak run of the same slots is ordered by (pc_leak_auto_order) */
+					/* what a leak run of the same slots is ordered by (pc_leak_run::auto_order) */
 					if (a.work_est) atomicAdd(&a.work_est[slot], (unsigned int)ph.irefl + 1u);
 				}
 			}
@@ -1079,6 +1079,7 @@ struct pc_event_handle {
 
 #define PC_IMAGES_STORE
 #include "pc_images.h"      /* the store and the fetch: behind the kernels and the owner types */
+#include "pc_leak_run.h"    /* the owner of leak runs; its functions follow the context and the leak kernels */
 
 /* what a context was last asked to do (pc_hip_ctx::last_call) */
 enum { PC_CALL_NONE = 0, PC_CALL_RUN, PC_CALL_RUN_LEAK, PC_CALL_EXPLICIT, PC_CALL_SCAN, PC_CALL_RELAY };
@@ -1119,40 +1120,7 @@ struct pc_hip_ctx {
 	long long run_slots = 0;
 	int run_pending = 0;
 	float last_ms = 0.f;
-	/* leak_calc=true runs (pc_leak_kernels.h) */
-	int leak_max_depth = 0;                /* frames per lane; default 2*n_shells + 16 (one frame per wall crossed) */
-	size_t leak_stack_bytes = (size_t)8 << 30;
-	long long leak_capacity = 0;           /* record buffer size of the next run; 0 = 8 per slot, grown on demand */
-	long long leak_capacity_used = 0;
-	pc_dev_buf<double> d_leak_frames;
-	pc_dev_buf<double> d_leak_records;
-	pc_dev_buf<unsigned long long> d_leak_cursor;
-	pc_dev_buf<double> d_amu;              /* copied when it is allocated, once */
-	pc_dev_buf<unsigned int> d_leak_attempts;
-	pc_dev_buf<unsigned long long> d_leak_timing; /* POLYCAP_LEAK_TIMING diagnostics */
-	long long leak_timing_waves = 0;
-	pc_dev_buf<unsigned int> d_leak_order; /* order in which the next leak run hands out its slots (pc_hip_leak_set_order); empty: none */
-	int leak_order = 1;                    /* option: 1 = source runs of >= 196608 slots order their slots by a plain pre-pass, 0 = slot order */
-	int leak_order_user = 0;               /* the order was set by the caller */
-	unsigned long long leak_order_seed = 0; long long leak_order_slot0 = -1; unsigned int leak_order_attempts = 0;   /* what the automatic order was made for */
-	pc_dev_buf<unsigned int> d_work_est;
-	int leak_ev0_done = 0;                 /* ev0 of the run in flight was recorded before its pre-pass */
-	long long leak_order_n = 0, leak_n_heavy = 0;
-	int leak_heavy_lanes = 1, leak_heavy_every = 1;
-	int leak_slot_units = 0;               /* option: keep the units of work per slot of leak runs (pc_hip_leak_slot_units) */
-	pc_dev_buf<unsigned int> d_leak_slot_units;
-	int leak_pending = 0;                  /* a leak transmission run is in flight: wait() collects its events */
-	unsigned long long leak_seed = 0;
-	long long leak_slot0 = 0, leak_n_slots = 0;
-	unsigned int leak_max_attempts = 0;
-	int leak_keep_images = 0;
-	/* events of the last leak run in the reference's list order, PC_HIP_LEAK_HDR + n_energies doubles each: the extleak list, then
-	 * the intleak list, ordered on the device (pc_leak_collect) and kept in pinned host memory */
-	pc_dev_buf<double> d_leak_out;
-	pc_host_buf<double, PC_PIN_ONLY> h_leak_out;
-	pc_dev_buf<char> d_leak_order_tmp;
-	long long leak_n_ext = 0, leak_n_int = 0;
-	int leak_events_of_run = 0;            /* the event lists are those of the last source run (a leak run): pc_hip_spot_add may read them */
+	pc_leak_run leak;                      /* leak_calc=true runs: buffers, options, the run in flight and its event lists (pc_leak_run.h) */
 	unsigned long long entries_epoch = 0;  /* grows with every call that replaces the entries a tally reads (source run, leak run, relay into the
 	                                        * context, explicit launch; not a scan): a selection's mask belongs to one value (pc_select.h) */
 	/* scans (pc_scan.h): buffers of their own, so that a scan leaves everything of the last run as it was */
@@ -1354,9 +1322,8 @@ static bool pc_wants_probe(const pc_hip_ctx *ctx, long long n_slots)
 }
 
 #include "pc_leak_kernels.h"
-
-static int pc_transmission_enqueue_leak(pc_hip_ctx *ctx);
-static int pc_leak_auto_order(pc_hip_ctx *ctx);
+#define PC_LEAK_RUN_BODY
+#include "pc_leak_run.h"
 
 extern "C" {
 
@@ -1435,7 +1402,7 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 		PC_CTX_GROW(ctx->d_ec_soa, soa.size(), "the energy constants");
 		PC_CTX_CHECK(hipMemcpy(ctx->d_ec_soa, soa.data(), soa.size()*sizeof(double), hipMemcpyHostToDevice));
 	}
-	ctx->leak_max_depth = (int)std::min(65536.0, 2.0*ctx->host.pm.n_shells + 16.0);
+	ctx->leak.opts.max_depth = (int)std::min(65536.0, 2.0*ctx->host.pm.n_shells + 16.0);
 	ctx->totals_bytes = sizeof(pc_totals) + 4*ctx->host.ec.size()*sizeof(unsigned long long);
 	PC_CTX_GROW(ctx->d_totals, (ctx->totals_bytes + sizeof(pc_totals) - 1)/sizeof(pc_totals), "the totals");
 	PC_CTX_CHECK(hipMemset(ctx->d_totals, 0, ctx->totals_bytes));
@@ -1495,13 +1462,13 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "pool_event_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_event_min must be in [1,128]"); ctx->opts.pool_event_min = (int)value; }
 	else if (n == "pool_new_min") { if (value < 1 || value > 128) return pc_fail(PC_HIP_ERR_INVALID, "pool_new_min must be in [1,128]"); ctx->opts.pool_new_min = (int)value; }
 	else if (n == "pool_march_min") { if (value < 1 || value > 64) return pc_fail(PC_HIP_ERR_INVALID, "pool_march_min must be in [1,64]"); ctx->opts.pool_march_min = (int)value; }
-	else if (n == "leak_max_depth") { if (value < 2 || value > (1 << 20)) return pc_fail(PC_HIP_ERR_INVALID, "leak_max_depth must be in [2, 2^20]"); ctx->leak_max_depth = (int)value; }
-	else if (n == "leak_stack_mb") { if (value < 1) return pc_fail(PC_HIP_ERR_INVALID, "leak_stack_mb must be >= 1"); ctx->leak_stack_bytes = (size_t)value << 20; }
-	else if (n == "leak_order") { ctx->leak_order = value != 0; }
-	else if (n == "leak_slot_units") { ctx->leak_slot_units = value != 0; }
-	else if (n == "leak_heavy_lanes") { if (value < 0 || value > PC_WAVE) return pc_fail(PC_HIP_ERR_INVALID, "leak_heavy_lanes must be in 0..64"); ctx->leak_heavy_lanes = (int)value; }
-	else if (n == "leak_heavy_every") { if (value < 0) return pc_fail(PC_HIP_ERR_INVALID, "leak_heavy_every must be >= 0"); ctx->leak_heavy_every = (int)value; }
-	else if (n == "leak_capacity") { if (value < 0) return pc_fail(PC_HIP_ERR_INVALID, "leak_capacity must be >= 0"); ctx->leak_capacity = (long long)value; }
+	else if (n == "leak_max_depth") { if (value < 2 || value > (1 << 20)) return pc_fail(PC_HIP_ERR_INVALID, "leak_max_depth must be in [2, 2^20]"); ctx->leak.opts.max_depth = (int)value; }
+	else if (n == "leak_stack_mb") { if (value < 1) return pc_fail(PC_HIP_ERR_INVALID, "leak_stack_mb must be >= 1"); ctx->leak.opts.stack_bytes = (size_t)value << 20; }
+	else if (n == "leak_order") { ctx->leak.opts.order = value != 0; }
+	else if (n == "leak_slot_units") { ctx->leak.opts.slot_units = value != 0; }
+	else if (n == "leak_heavy_lanes") { if (value < 0 || value > PC_WAVE) return pc_fail(PC_HIP_ERR_INVALID, "leak_heavy_lanes must be in 0..64"); ctx->leak.opts.heavy_lanes = (int)value; }
+	else if (n == "leak_heavy_every") { if (value < 0) return pc_fail(PC_HIP_ERR_INVALID, "leak_heavy_every must be >= 0"); ctx->leak.opts.heavy_every = (int)value; }
+	else if (n == "leak_capacity") { if (value < 0) return pc_fail(PC_HIP_ERR_INVALID, "leak_capacity must be >= 0"); ctx->leak.opts.capacity = (long long)value; }
 	else return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_set_option: unknown option " + n);
 	return PC_HIP_OK;
 }
@@ -1574,19 +1541,13 @@ static int pc_batch_trace(pc_hip_ctx *ctx, const pc_batch &b, int leak)
 	a.out_irefl = b.d_ir; a.out_dtravel = b.d_dt;
 	if (!leak) return pc_launch_kernel<PC_MODE_EXPLICIT>(ctx, pc_launch_site{ctx->stream}, a, n);
 	/* polycap_photon_launch(..., leak_calc=true): rerun with a larger record buffer until every event fits */
-	long long capacity = ctx->leak_capacity > 0 ? ctx->leak_capacity : std::max<long long>(4096, (16 + 8*(long long)b.ne)*n);
-	ctx->leak_slot0 = 0;
-	for (;;) {
-		ctx->leak_capacity_used = capacity;
-		ctx->leak_ev0_done = 0;
-		int status = pc_leak_enqueue<PC_MODE_EXPLICIT>(ctx, a, n, capacity);
-		if (status) return status;
-		PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
-		long long needed = 0;
-		status = pc_leak_collect(ctx, n, true, &needed);
-		if (status == 1) { capacity = needed + needed/4 + 1024; continue; }
-		return status;
-	}
+	pc_leak_run &L = ctx->leak;
+	L.slot0 = 0;
+	L.begin(n, pc_plan_leak_capacity(L.opts.capacity, (int)b.ne, n, 4096));
+	int status = L.enqueue<PC_MODE_EXPLICIT>(*ctx, a);
+	if (status) return status;
+	PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
+	return L.run_until_fit(*ctx, &a);
 }
 
 static int pc_batch_download(pc_hip_ctx *ctx, const pc_batch &b, const double *start_elecv, int32_t *rc, double *weights, double *exit_coords,
@@ -1634,7 +1595,7 @@ static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *star
 	if (!status) status = pc_batch_trace(ctx, b, leak);
 	if (!status) status = pc_batch_download(ctx, b, start_elecv, rc, weights, exit_coords, exit_dir, exit_elecv, i_refl, d_travel, leak);
 	ctx->img.valid = 0;
-	ctx->leak_events_of_run = 0;
+	ctx->leak.events_of_run = 0;
 	return status;
 }
 
@@ -1711,7 +1672,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		if (st != PC_HIP_OK) return st;
 	}
 	ctx->last_run_plain = 1;
-	ctx->leak_events_of_run = 0;
+	ctx->leak.events_of_run = 0;
 	ctx->entries_epoch++;
 	ctx->run_squares = ctx->opts.weight_squares;
 	ctx->last_call = PC_CALL_RUN;
@@ -1789,59 +1750,15 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 	return PC_HIP_OK;
 }
 
-int pc_hip_transmission_run_leak(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64_t n_slots, uint32_t max_attempts, int keep_images)
-{
-	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_run_leak: ctx must not be NULL");
-	if (n_slots < 1 || slot0 < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_run_leak: n_slots must be >= 1 and slot0 >= 0");
-	if (max_attempts < 1) max_attempts = 1;
-	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	ctx->img.reset();
-	ctx->entries_epoch++;
-	ctx->last_call = PC_CALL_RUN_LEAK;
-	if (keep_images) {
-		int st = ctx->img.keep_records(n_slots, "pc_hip_transmission_run_leak: could not allocate the image planes; use keep_images=0");
-		if (st) return st;
-	}
-	ctx->last_run_plain = 0;
-	ctx->leak_events_of_run = 1;
-	ctx->run_squares = ctx->opts.weight_squares;
-	ctx->leak_seed = seed; ctx->leak_slot0 = slot0; ctx->leak_n_slots = n_slots;
-	ctx->leak_max_attempts = max_attempts; ctx->leak_keep_images = keep_images ? 1 : 0;
-	/* record buffer: events per slot grow with the number of energies (a leak is kept while ANY energy holds >= 1e-4):
-	 * 9 per slot at one energy, 29 at seven on the reference's test optic; a run that outgrows the buffer is repeated, so
-	 * the first guess is generous (16 + 8 n_energies records per slot) */
-	ctx->leak_capacity_used = ctx->leak_capacity > 0 ? ctx->leak_capacity : std::max<long long>(65536, (16 + 8*(long long)ne)*n_slots);
-	ctx->leak_ev0_done = 0;
-	int status = pc_leak_auto_order(ctx);
-	if (status) return status;
-	status = pc_transmission_enqueue_leak(ctx);
-	if (status) return status;
-	ctx->run_slots = n_slots;
-	ctx->run_pending = 1;
-	ctx->leak_pending = 1;
-	ctx->img.valid = keep_images ? 1 : 0;
-	return PC_HIP_OK;
-}
-
 int pc_hip_transmission_wait(pc_hip_ctx *ctx, float *kernel_ms)
 {
 	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_wait: ctx must not be NULL");
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	while (ctx->leak_pending) {
-		/* leak run: fetch and order its events; a run that outgrew the record buffer is repeated with a larger one
-		 * (the photon streams are counter-based, so the repetition is the same run) */
-		long long needed = 0;
-		int st = pc_leak_collect(ctx, ctx->leak_n_slots, false, &needed);
-		if (st == 1) {
-			ctx->leak_capacity_used = needed + needed/4 + 1024;
-			st = pc_transmission_enqueue_leak(ctx);
-			if (st) { ctx->leak_pending = 0; ctx->run_pending = 0; return st; }
-			PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-			continue;
-		}
-		ctx->leak_pending = 0;
+	if (ctx->leak.pending) {
+		/* leak run: fetch and order its events, repeating a launch that outgrew the record buffer */
+		int st = ctx->leak.run_until_fit(*ctx, nullptr);
+		ctx->leak.pending = 0;
 		if (st) { ctx->run_pending = 0; return st; }
 	}
 	if (ctx->run_pending) {
@@ -1862,42 +1779,6 @@ int pc_hip_host_is_pinned(const void *p)
 	if (hipHostGetFlags(&flags, const_cast<void *>(p)) == hipSuccess) return 1;
 	(void)hipGetLastError();
 	return 0;
-}
-
-int pc_hip_leak_counts(pc_hip_ctx *ctx, int64_t *n_ext, int64_t *n_int)
-{
-	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_counts: ctx must not be NULL");
-	int st = pc_hip_transmission_wait(ctx, nullptr);
-	if (st) return st;
-	if (n_ext) *n_ext = ctx->leak_n_ext;
-	if (n_int) *n_int = ctx->leak_n_int;
-	return PC_HIP_OK;
-}
-
-int pc_hip_leak_events(pc_hip_ctx *ctx, int kind, int64_t first, int64_t count, double *records)
-{
-	if (!ctx || (count > 0 && !records)) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_events: NULL argument");
-	if (kind != 0 && kind != 1) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_events: kind must be 0 (extleak) or 1 (intleak)");
-	int st = pc_hip_transmission_wait(ctx, nullptr);
-	if (st) return st;
-	const long long have = kind == 0 ? ctx->leak_n_ext : ctx->leak_n_int;
-	if (first < 0 || count < 0 || first + count > have) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_events: range out of bounds");
-	const size_t stride = PC_HIP_LEAK_HDR + (size_t)ctx->host.pm.n_energies;
-	const double *src = ctx->h_leak_out + (kind == 0 ? 0 : (size_t)ctx->leak_n_ext*stride);
-	if (count) memcpy(records, src + (size_t)first*stride, (size_t)count*stride*sizeof(double));
-	return PC_HIP_OK;
-}
-
-int pc_hip_leak_events_view(pc_hip_ctx *ctx, int kind, const double **records, int64_t *count)
-{
-	if (!ctx || !records || !count) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_events_view: NULL argument");
-	if (kind != 0 && kind != 1) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_events_view: kind must be 0 (extleak) or 1 (intleak)");
-	int st = pc_hip_transmission_wait(ctx, nullptr);
-	if (st) return st;
-	const size_t stride = PC_HIP_LEAK_HDR + (size_t)ctx->host.pm.n_energies;
-	*count = kind == 0 ? ctx->leak_n_ext : ctx->leak_n_int;
-	*records = (*count > 0) ? ctx->h_leak_out + (kind == 0 ? 0 : (size_t)ctx->leak_n_ext*stride) : nullptr;
-	return PC_HIP_OK;
 }
 
 double pc_hip_fixed_to_double(uint64_t lo, uint64_t hi)
@@ -1996,7 +1877,7 @@ static int pc_fetch_images(pc_hip_ctx *ctx, int64_t first, int64_t count, void *
 	if (first < 0 || count < 0 || first + count > ctx->run_slots) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_transmission_images: slot range out of bounds");
 	/* a leak run is complete (and possibly repeated) only after wait(); a plain run in parts is fetched part by part, and the planes
 	 * of a compact run block by block, while it is traced */
-	if (ctx->leak_pending || (ctx->img.plan.fetch_parts <= 1 && !(ctx->img.plan.layout == PC_IMG_COMPACT && planes && !raw))) {
+	if (ctx->leak.pending || (ctx->img.plan.fetch_parts <= 1 && !(ctx->img.plan.layout == PC_IMG_COMPACT && planes && !raw))) {
 		int st = pc_hip_transmission_wait(ctx, nullptr);
 		if (st) return st;
 	}
@@ -2027,41 +1908,6 @@ int pc_hip_transmission_slot_ids(pc_hip_ctx *ctx, int64_t first, int64_t count, 
 	}
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	if (count) PC_HIP_CHECK(hipMemcpy(slots, ids + first, (size_t)count*sizeof(long long), hipMemcpyDeviceToHost));
-	return PC_HIP_OK;
-}
-
-int pc_hip_leak_set_order(pc_hip_ctx *ctx, const uint32_t *order, int64_t n, int64_t n_heavy)
-{
-	if (!ctx || n < 0 || (n > 0 && !order) || n_heavy < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_set_order: invalid argument");
-	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	int st = pc_hip_transmission_wait(ctx, nullptr);
-	if (st) return st;
-	ctx->d_leak_order.reset();
-	ctx->leak_order_n = 0; ctx->leak_n_heavy = 0; ctx->leak_order_user = 0; ctx->leak_order_slot0 = -1;
-	if (n == 0) return PC_HIP_OK;
-	{
-		/* a permutation of 0 .. n-1, or slots would be traced twice or not at all */
-		std::vector<unsigned char> seen((size_t)n, 0);
-		for (int64_t k = 0; k < n; k++) {
-			if ((int64_t)order[k] >= n || seen[order[k]]) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_set_order: order is not a permutation of the slots");
-			seen[order[k]] = 1;
-		}
-	}
-	st = ctx->d_leak_order.grow((size_t)n, "pc_hip_leak_set_order: could not allocate the order");
-	if (st) return st;
-	PC_HIP_CHECK(hipMemcpy(ctx->d_leak_order, order, (size_t)n*sizeof(unsigned int), hipMemcpyHostToDevice));
-	ctx->leak_order_n = n; ctx->leak_n_heavy = n_heavy; ctx->leak_order_user = 1;
-	return PC_HIP_OK;
-}
-
-int pc_hip_leak_slot_units(pc_hip_ctx *ctx, int64_t first, int64_t count, uint32_t *units)
-{
-	if (!ctx || (count > 0 && !units) || first < 0 || count < 0) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_slot_units: invalid argument");
-	int st = pc_hip_transmission_wait(ctx, nullptr);
-	if (st) return st;
-	if (!ctx->d_leak_slot_units || (size_t)(first + count) > ctx->d_leak_slot_units.cap) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_leak_slot_units: no leak run with the option leak_slot_units covers this range");
-	PC_HIP_CHECK(hipSetDevice(ctx->device));
-	if (count) PC_HIP_CHECK(hipMemcpy(units, ctx->d_leak_slot_units + first, (size_t)count*sizeof(unsigned int), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;
 }
 
@@ -2117,101 +1963,3 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_draw.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
-
-/* Heaviest slots first.  A leak launch ends with its longest slot: 20 000 units of work on one lane, which advances several
- * times faster alone in its wave than among 63 others (a wave runs one class of work at a time).  Which slots are long is known
- * beforehand to a good approximation (correlation 0.95 with the units of the leak run, scripts/analysis/leak_units.py): a plain
- * run of the same slots -- the same photons without their leaks, a hundredth of the leak run's time -- counts the reflections
- * of every attempt per slot.  The slots are then handed out in descending order of that count, the first n/400 of them to lane
- * 0 of the waves, whose other lanes wait while such a slot is at work (pc_leak_kargs::order).  The results do not depend on the
- * order (photon streams are keyed by slot and attempt, events are ordered by slot on the host). */
-static int pc_leak_auto_order(pc_hip_ctx *ctx)
-{
-	const long long n = ctx->leak_n_slots;
-	if (ctx->leak_order_user) return PC_HIP_OK;                       /* the caller's order (used if it is for n slots) */
-	long long lanes = 0;
-	(void)pc_leak_grid(ctx, n, lanes);
-	/* considered when every lane gets two to five slots: with fewer there is nothing to order, with more the launch is not bound
-	 * by its longest slot (the check below, made beforehand with the reference optic's ratio of longest to mean slot, 11.6) */
-	if (!ctx->leak_order || n < 2*lanes || n >= 5*lanes || n >= (1ll << 32)) {
-		ctx->d_leak_order.reset();
-		ctx->leak_order_n = 0; ctx->leak_order_slot0 = -1;
-		return PC_HIP_OK;
-	}
-	if (ctx->d_leak_order && ctx->leak_order_n == n && ctx->leak_order_seed == ctx->leak_seed && ctx->leak_order_slot0 == ctx->leak_slot0
-	    && ctx->leak_order_attempts == ctx->leak_max_attempts)
-		return PC_HIP_OK;                                               /* the same slots as last time */
-	int st = ctx->d_work_est.grow((size_t)n, "leak run: could not allocate the work estimate");
-	if (st) return st;
-	const bool tim = getenv("POLYCAP_LEAK_TIMING") != nullptr;
-	const auto t_0 = std::chrono::steady_clock::now();
-	/* the time of the launch starts here */
-	PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-	ctx->leak_ev0_done = 1;
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_work_est, 0, (size_t)n*sizeof(unsigned int), ctx->stream));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
-	pc_kargs a;
-	pc_fill_common(ctx, a);
-	a.seed = ctx->leak_seed; a.max_attempts = ctx->leak_max_attempts; a.keep_images = 0;
-	a.slot0 = ctx->leak_slot0; a.n_slots = n;
-	a.work_est = ctx->d_work_est;
-	pc_launch_site site{ctx->stream};     /* the lane kernel, no events of its own */
-	site.record_ev0 = site.record_ev1 = false;
-	site.force_lane = true;
-	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SRC_GENERIC>(ctx, site, a, n) : pc_launch_kernel<PC_MODE_SRC_CIRCULAR>(ctx, site, a, n);
-	if (st) return st;
-	std::vector<unsigned int> est((size_t)n);
-	PC_HIP_CHECK(hipMemcpyAsync(est.data(), ctx->d_work_est, (size_t)n*sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	const auto t_1 = std::chrono::steady_clock::now();
-	/* Is the launch bound by its longest slot?  A lone lane works through a unit in about 4 us, a lane among the 64 of a busy wave
-	 * in about 13 us: with the slots in slot order the launch lasts about (all work / lanes) x 13 us, the longest slot alone
-	 * (its work) x 4 us.  When the second is not most of the first (launches of many slots per lane), handing the heaviest slots
-	 * to lanes of their own only takes lanes away from the rest: slot order stays (measured: 524288 and 1048576 slots lose 4-7 %,
-	 * 262144 gain 10-15 %). */
-	unsigned int top = 0;
-	unsigned long long total = 0;
-	for (long long k = 0; k < n; k++) { if (est[(size_t)k] > top) top = est[(size_t)k]; total += est[(size_t)k]; }
-	if (!((double)top * 4.0 * (double)lanes > 0.8 * 13.0 * (double)total)) {
-		ctx->leak_order_n = 0; ctx->leak_order_slot0 = -1;      /* the buffer stays for the next run; it is not used */
-		if (tim) fprintf(stderr, "leak order: slot order kept (longest slot %u of %llu predicted units, %lld lanes)\n", top, total, lanes);
-		return PC_HIP_OK;
-	}
-	/* descending counting sort (stable: equal counts keep slot order) */
-	std::vector<unsigned int> order((size_t)n);
-	if (top < (1u << 22)) {
-		std::vector<unsigned int> first((size_t)top + 2, 0);
-		for (long long k = 0; k < n; k++) first[(size_t)(top - est[(size_t)k]) + 1]++;
-		for (size_t v = 0; v + 1 < first.size(); v++) first[v + 1] += first[v];
-		for (long long k = 0; k < n; k++) order[first[(size_t)(top - est[(size_t)k])]++] = (unsigned int)k;
-	} else {
-		for (long long k = 0; k < n; k++) order[(size_t)k] = (unsigned int)k;
-		std::stable_sort(order.begin(), order.end(), [&](unsigned int x, unsigned int y) { return est[x] > est[y]; });
-	}
-	const auto t_2 = std::chrono::steady_clock::now();
-	st = ctx->d_leak_order.grow((size_t)n, "leak run: could not allocate the slot order");
-	if (st) return st;
-	PC_HIP_CHECK(hipMemcpyAsync(ctx->d_leak_order, order.data(), (size_t)n*sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
-	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));      /* `order` leaves scope */
-	if (tim) {
-		const auto t_3 = std::chrono::steady_clock::now();
-		auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-		fprintf(stderr, "leak order: plain pre-pass + copy %.2f ms, sort %.2f ms, upload %.2f ms\n", ms(t_0, t_1), ms(t_1, t_2), ms(t_2, t_3));
-	}
-	ctx->leak_order_n = n;
-	/* one heavy slot per wave at most: the wave is the heavy lane's alone while it lasts */
-	ctx->leak_n_heavy = std::min<long long>(n / 400, (long long)ctx->n_cu * 2);
-	ctx->leak_order_seed = ctx->leak_seed; ctx->leak_order_slot0 = ctx->leak_slot0; ctx->leak_order_attempts = ctx->leak_max_attempts;
-	return PC_HIP_OK;
-}
-
-static int pc_transmission_enqueue_leak(pc_hip_ctx *ctx)
-{
-	pc_kargs a;
-	pc_fill_common(ctx, a);
-	ctx->img.set_img(a, ctx->leak_keep_images ? PC_IMG_RECORDS : PC_IMG_NONE, ctx->leak_n_slots, 0);
-	a.seed = ctx->leak_seed; a.slot0 = ctx->leak_slot0; a.n_slots = ctx->leak_n_slots;
-	a.max_attempts = ctx->leak_max_attempts; a.keep_images = ctx->leak_keep_images;
-	return ctx->host.pm.generic_src ? pc_leak_enqueue<PC_MODE_SRC_GENERIC>(ctx, a, ctx->leak_n_slots, ctx->leak_capacity_used)
-	                                : pc_leak_enqueue<PC_MODE_SRC_CIRCULAR>(ctx, a, ctx->leak_n_slots, ctx->leak_capacity_used);
-}

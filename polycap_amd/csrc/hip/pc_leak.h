@@ -23,6 +23,7 @@
 #define PC_LEAK_H
 
 #include "pc_device.h"
+#include "pc_leak_plan.h"
 
 /* leak record, in doubles */
 enum { PC_LR_SLOT = 0, PC_LR_ATTEMPT, PC_LR_SEQ, PC_LR_KIND, PC_LR_X, PC_LR_Y, PC_LR_Z, PC_LR_DX, PC_LR_DY, PC_LR_DZ,
@@ -32,7 +33,7 @@ enum { PC_LEAK_EXT = 0, PC_LEAK_INT = 1, PC_LEAK_VOID = -1 };
 /* suspended parent frame, in doubles; the parent's weights follow */
 enum { PC_LF_PX = 0, PC_LF_PY, PC_LF_PZ, PC_LF_DX, PC_LF_DY, PC_LF_DZ, PC_LF_EX, PC_LF_EY, PC_LF_EZ, PC_LF_KX, PC_LF_KY,
        PC_LF_DTRAVEL, PC_LF_NX, PC_LF_NY, PC_LF_NZ, PC_LF_COSALFA, PC_LF_IX, PC_LF_IREFL, PC_LF_CALLS, PC_LF_KEEP,
-       PC_LF_BND, PC_LF_ENTRANCE, PC_LF_HDR = 24 };
+       PC_LF_BND, PC_LF_ENTRANCE };    /* PC_LF_HDR (pc_leak_plan.h) of them */
 
 struct pc_leak_sink {
 	double *records;               /* capacity x (PC_LR_HDR + n_energies) */

@@ -1,6 +1,7 @@
 /*
- * pc_leak_kernels.h -- leak_calc=true on the device: kernel + host code, included by pc_kernels.hip after the
- * context definition (same translation unit, so the two modes share tables, totals and image records).
+ * pc_leak_kernels.h -- leak_calc=true on the device: the kernels, included by pc_kernels.hip after the context
+ * definition (same translation unit, so the two modes share tables, totals and image records).  The host code that
+ * launches them and orders their events is pc_leak_run.h.
  *
  * Shape.  The leak run of one launched photon (pc_leak.h) is a long, irregular, strictly sequential job: blocks and
  * steps through the glass for every reflection, a depth-first tree of leaked fractions, every decision discrete.  A lane
@@ -16,9 +17,7 @@
 
 #include <algorithm>
 
-#ifndef PC_LEAK_BLOCK
-#define PC_LEAK_BLOCK 256
-#endif
+#include "pc_leak_plan.h"      /* PC_LEAK_BLOCK */
 #ifndef PC_LEAK_OTHER_REPS
 #define PC_LEAK_OTHER_REPS 2   /* short states a lane may pass in one unit of that class (1 / 2 / 3: mean wave life 125.1 / 122.4 / 125.7 ms) */
 #endif
@@ -340,100 +339,7 @@ pc_leak_kernel(pc_kargs a, pc_leak_kargs lk)
 	}
 }
 
-/* =========================================================================== host side */
-
-/* grid of the leak kernel: as many lanes as the stack budget allows, at most two resident blocks per CU */
-static int pc_leak_grid(pc_hip_ctx *ctx, long long n_items, long long &lanes)
-{
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	const size_t per_lane = (size_t)ctx->leak_max_depth * (PC_LF_HDR + ne) * sizeof(double);
-	long long by_mem = (long long)(ctx->leak_stack_bytes / per_lane);
-	long long want = (n_items + PC_LEAK_BLOCK - 1) / PC_LEAK_BLOCK;
-	long long max_blocks = (long long)ctx->n_cu * 2;
-	long long blocks = std::min(want, max_blocks);
-	blocks = std::min(blocks, std::max(1ll, by_mem / PC_LEAK_BLOCK));
-	if (blocks < 1) blocks = 1;
-	lanes = blocks * PC_LEAK_BLOCK;
-	return (int)blocks;
-}
-
-static int pc_leak_buffers(pc_hip_ctx *ctx, long long lanes, long long capacity, long long n_slots)
-{
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	const size_t frames = (size_t)lanes * (size_t)ctx->leak_max_depth * (PC_LF_HDR + ne);
-	int st = ctx->d_leak_frames.grow(frames, "leak run: could not allocate the per-lane stacks (lower leak_stack_mb or leak_max_depth)");
-	if (!st) st = ctx->d_leak_records.grow((size_t)capacity * (PC_LR_HDR + ne), "leak run: could not allocate the leak record buffer");
-	if (!st) st = ctx->d_leak_cursor.grow(4, "leak run: could not allocate the record cursor");
-	if (!st && !ctx->d_amu) {
-		st = ctx->d_amu.grow(ne, "leak run: could not allocate the attenuation table");
-		if (!st) PC_HIP_CHECK(hipMemcpy(ctx->d_amu, ctx->host.amu.data(), ne*sizeof(double), hipMemcpyHostToDevice));
-	}
-	if (!st) st = ctx->d_leak_attempts.grow((size_t)n_slots, "leak run: could not allocate the per-slot attempt table");
-	return st;
-}
-
-template <int MODE>
-static int pc_leak_enqueue(pc_hip_ctx *ctx, pc_kargs &a, long long n_items, long long capacity)
-{
-	long long lanes = 0;
-	const int grid = pc_leak_grid(ctx, n_items, lanes);
-	int st = pc_leak_buffers(ctx, lanes, capacity, n_items);
-	if (st) return st;
-	pc_leak_kargs lk;
-	lk.amu = ctx->d_amu; lk.frames = ctx->d_leak_frames; lk.max_depth = ctx->leak_max_depth;
-	lk.records = ctx->d_leak_records; lk.cursor = ctx->d_leak_cursor; lk.capacity = capacity;
-	lk.final_attempt = ctx->d_leak_attempts;
-	lk.timing = nullptr;
-	lk.order = nullptr; lk.n_heavy = 0; lk.heavy_lanes = 0; lk.heavy_every = 0; lk.slot_units = nullptr;
-	if (MODE != PC_MODE_EXPLICIT) {
-		if (ctx->d_leak_order && ctx->leak_order_n == n_items) {
-			lk.order = ctx->d_leak_order;
-			lk.heavy_lanes = ctx->leak_heavy_lanes; lk.heavy_every = ctx->leak_heavy_every;
-			lk.n_heavy = (lk.heavy_lanes > 0 && lk.heavy_every > 0) ? std::min<long long>(ctx->leak_n_heavy, n_items) : 0;
-		}
-		if (ctx->leak_slot_units) {
-			st = ctx->d_leak_slot_units.grow((size_t)n_items, "leak run: could not allocate the units of work per slot");
-			if (st) return st;
-			PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_slot_units, 0, (size_t)n_items*sizeof(unsigned int), ctx->stream));
-			lk.slot_units = ctx->d_leak_slot_units;
-		}
-	}
-	if (getenv("POLYCAP_LEAK_TIMING")) {
-		/* diagnostics: where the waves of the leak kernel spend their time (printed by pc_leak_collect) */
-		const size_t nb = (size_t)(lanes / PC_WAVE) * 8 * sizeof(unsigned long long);
-		st = ctx->d_leak_timing.grow(nb/sizeof(unsigned long long), "leak run: could not allocate the timing records");
-		if (st) return st;
-		PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_timing, 0, nb, ctx->stream));
-		lk.timing = ctx->d_leak_timing;
-		ctx->leak_timing_waves = lanes / PC_WAVE;
-	}
-	a.total_threads = lanes;
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_leak_cursor, 0, 4*sizeof(unsigned long long), ctx->stream));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
-	if (!ctx->leak_ev0_done) PC_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-	/* option "weight_squares": kernels of their own (SQ), so that the default kernels keep their registers */
-	constexpr bool CAN_SQ = MODE != PC_MODE_EXPLICIT;
-	const bool sq = CAN_SQ && a.sumw2 != nullptr;
-	if (ctx->host.pm.nmax + 1 <= 1024) {
-		if (sq) hipLaunchKernelGGL((pc_leak_kernel<MODE, 1024, CAN_SQ>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
-		else hipLaunchKernelGGL((pc_leak_kernel<MODE, 1024>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
-	} else {
-		if (sq) hipLaunchKernelGGL((pc_leak_kernel<MODE, PC_MAX_PITCH, CAN_SQ>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
-		else hipLaunchKernelGGL((pc_leak_kernel<MODE, PC_MAX_PITCH>), dim3(grid), dim3(PC_LEAK_BLOCK), 0, ctx->stream, a, lk);
-	}
-	PC_HIP_CHECK(hipGetLastError());
-	ctx->last_kernel = 5;
-	PC_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
-	return PC_HIP_OK;
-}
-
-/* ---------------------------------------------------------------------------------------------------------------------
- * The events of a finished run, put into the two lists of the reference (src/polycap-source.c:799-879) ON THE DEVICE: attempts
- * that appended a VOID record are dropped, the rest is ordered by slot, inside a slot the transmitted attempt first and then the
- * earlier attempts in attempt order, inside an attempt by seq; extleak and intleak events go to lists of their own in that
- * order.  Round 3 fetched the raw records (120 B each) and did this with host threads: 243 ms for the 2.46e6 events of the leak
- * bench, more than the kernel.  Now: keys -> two stable radix sorts (seq, then (slot, order)) -> flags and positions (prefix sums)
- * -> one gather into the output rows (PC_HIP_LEAK_HDR + n_energies doubles), which are copied once into pinned host memory. */
+/* ---- the kernels that order the event records of a finished launch (pc_leak_run::collect) */
 #include <hipcub/hipcub.hpp>
 
 #define PC_LEAK_ORDER_BITS 22          /* order = 0 (the transmitted attempt) or attempt + 1 <= 2^20 + 1 */
@@ -500,106 +406,5 @@ __global__ void __launch_bounds__(256) pc_leak_rows_kernel(const double *recs, l
 	out[pos*ostride + c] = r[from];
 }
 
-static int pc_leak_order_buffers(pc_hip_ctx *ctx, size_t n, size_t ostride, size_t temp_bytes)
-{
-	/* keys n x 8 x 3, seq n x 4 x 2, idx n x 4 x 3, flags + positions (n + 1) x 4 x 4, void keys n x 8 x 2, counters */
-	const size_t need = n*8*3 + n*4*2 + n*4*3 + (n + 1)*4*4 + n*8*2 + 256 + temp_bytes + 4096;
-	int st = ctx->d_leak_order_tmp.grow(need, "leak run: could not allocate the ordering buffers");
-	const size_t out_elems = (n ? n : 1)*ostride;
-	if (!st) st = ctx->d_leak_out.grow(out_elems, "leak run: could not allocate the event lists", out_elems + out_elems/8);
-	if (!st) st = ctx->h_leak_out.grow(out_elems, "leak run: could not allocate the event lists", out_elems + out_elems/8);
-	return st;
-}
-
-/* Orders the event records of the finished run on the device and brings the two lists to the host (pinned memory, kept by the
- * context until its next leak run).  Returns PC_HIP_OK, or 1 when the record buffer was too small (*needed = records the run
- * produced). */
-static int pc_leak_collect(pc_hip_ctx *ctx, long long n_slots, bool explicit_mode, long long *needed)
-{
-	unsigned long long cur[2] = {0, 0};
-	PC_HIP_CHECK(hipMemcpy(cur, ctx->d_leak_cursor, sizeof(cur), hipMemcpyDeviceToHost));
-	if (ctx->d_leak_timing && getenv("POLYCAP_LEAK_TIMING")) {
-		const size_t nw = (size_t)ctx->leak_timing_waves;
-		std::vector<unsigned long long> t(nw*8);
-		PC_HIP_CHECK(hipMemcpy(t.data(), ctx->d_leak_timing, nw*8*sizeof(unsigned long long), hipMemcpyDeviceToHost));
-		double sum[8] = {0}, mx[8] = {0}; size_t ran = 0;
-		unsigned long long t0 = ~0ull, t1 = 0;
-		for (size_t w = 0; w < nw; w++) {
-			if (t[w*8+5] == 0) continue;
-			ran++;
-			for (int k = 0; k < 7; k++) { sum[k] += (double)t[w*8+k]; if ((double)t[w*8+k] > mx[k]) mx[k] = (double)t[w*8+k]; }
-			if (t[w*8+7] < t0) t0 = t[w*8+7];
-			if (t[w*8+7] + t[w*8+5] > t1) t1 = t[w*8+7] + t[w*8+5];
-		}
-		std::vector<unsigned long long> life;
-		for (size_t w = 0; w < nw; w++) if (t[w*8+5]) life.push_back(t[w*8+5]);
-		std::sort(life.begin(), life.end());
-		const double tick = 1e-5;     /* wall_clock64: 100 MHz -> ms */
-		fprintf(stderr, "leak timing: %zu waves ran; span %.1f ms; per wave mean (max) in ms: wall %.1f (%.1f) probe %.1f (%.1f) march %.1f (%.1f) other %.1f (%.1f) driver %.1f (%.1f) | life %.1f (%.1f) median %.1f p90 %.1f | first idle lane after %.1f (%.1f)\n",
-		        ran, (double)(t1 - t0)*tick, sum[0]/ran*tick, mx[0]*tick, sum[1]/ran*tick, mx[1]*tick, sum[2]/ran*tick, mx[2]*tick, sum[3]/ran*tick, mx[3]*tick,
-		        sum[4]/ran*tick, mx[4]*tick, sum[5]/ran*tick, mx[5]*tick, life.empty() ? 0. : (double)life[life.size()/2]*tick, life.empty() ? 0. : (double)life[life.size()*9/10]*tick,
-		        sum[6]/ran*tick, mx[6]*tick);
-	}
-	ctx->leak_n_ext = ctx->leak_n_int = 0;
-	if (cur[1] != 0)
-		return pc_fail(PC_HIP_ERR_RUNTIME, "leak run: the chain of wall crossings was deeper than leak_max_depth for " + std::to_string(cur[1]) + " lane(s); raise the option leak_max_depth");
-	if ((long long)cur[0] > ctx->leak_capacity_used) { *needed = (long long)cur[0]; return 1; }
-	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = PC_LR_HDR + ne, ostride = PC_HIP_LEAK_HDR + ne, n = (size_t)cur[0];
-	if (n == 0) return PC_HIP_OK;
-	if (n >= (1ull << 31) - 2) return pc_fail(PC_HIP_ERR_INVALID, "leak run: more than 2^31 event records in one run (the sorts count in int); trace the slots in several runs");
-	hipStream_t st = ctx->stream;
-	const int end_bit = 64;
-	/* temporary storage of the library calls: the largest of the three sorts and the prefix sum */
-	size_t tb = 0, t1 = 0;
-	PC_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (const unsigned int *)nullptr, (unsigned int *)nullptr, (const unsigned int *)nullptr, (unsigned int *)nullptr, (int)n, 0, 32, st)); tb = std::max(tb, t1);
-	PC_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const unsigned int *)nullptr, (unsigned int *)nullptr, (int)n, 0, end_bit, st)); tb = std::max(tb, t1);
-	PC_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)n, 0, end_bit, st)); tb = std::max(tb, t1);
-	PC_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (const unsigned int *)nullptr, (unsigned int *)nullptr, (int)n + 1, st)); tb = std::max(tb, t1);
-	int rc = pc_leak_order_buffers(ctx, n, ostride, tb);
-	if (rc) return rc;
-	char *base = (char *)ctx->d_leak_order_tmp;
-	auto take = [&](size_t bytes) { char *p = base; base += (bytes + 255) & ~(size_t)255; return (void *)p; };
-	unsigned long long *key = (unsigned long long *)take(n*8), *key2 = (unsigned long long *)take(n*8), *key3 = (unsigned long long *)take(n*8);
-	unsigned int *seq = (unsigned int *)take(n*4), *seq2 = (unsigned int *)take(n*4);
-	unsigned int *idx = (unsigned int *)take(n*4), *idx2 = (unsigned int *)take(n*4), *idx3 = (unsigned int *)take(n*4);
-	unsigned int *f_ext = (unsigned int *)take((n + 1)*4), *f_int = (unsigned int *)take((n + 1)*4), *p_ext = (unsigned int *)take((n + 1)*4), *p_int = (unsigned int *)take((n + 1)*4);
-	unsigned long long *vk = (unsigned long long *)take(n*8), *vk2 = (unsigned long long *)take(n*8);
-	unsigned int *cnt = (unsigned int *)take(64);       /* [0] void records, [1] records with a slot or attempt outside the run */
-	void *tmp = take(tb);
-	const unsigned blocks = (unsigned)((n + 255)/256);
-	PC_HIP_CHECK(hipMemsetAsync(cnt, 0, 64, st));
-	hipLaunchKernelGGL(pc_leak_keys_kernel, dim3(blocks), dim3(256), 0, st, ctx->d_leak_records, (long long)stride, (long long)n, (long long)ctx->leak_slot0, n_slots,
-	                   explicit_mode ? (const unsigned int *)nullptr : ctx->d_leak_attempts, key, seq, idx, vk, cnt, cnt + 1);
-	PC_HIP_CHECK(hipGetLastError());
-	unsigned int hc[2] = {0, 0};
-	PC_HIP_CHECK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-	PC_HIP_CHECK(hipStreamSynchronize(st));
-	if (hc[1]) return pc_fail(PC_HIP_ERR_RUNTIME, "leak run: event record with a slot or attempt outside the run");
-	if (hc[0]) PC_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp, tb, vk, vk2, (int)hc[0], 0, end_bit, st));
-	/* stable sorts: by seq, then by (slot, order) */
-	PC_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, seq, seq2, idx, idx2, (int)n, 0, 32, st));
-	hipLaunchKernelGGL(pc_leak_gather_keys_kernel, dim3(blocks), dim3(256), 0, st, key, idx2, (long long)n, key2);
-	PC_HIP_CHECK(hipGetLastError());
-	PC_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key2, key3, idx2, idx3, (int)n, 0, end_bit, st));
-	hipLaunchKernelGGL(pc_leak_flags_kernel, dim3((unsigned)((n + 1 + 255)/256)), dim3(256), 0, st, ctx->d_leak_records, (long long)stride, key3, idx3, (long long)n,
-	                   hc[0] ? vk2 : vk, cnt, f_ext, f_int);
-	PC_HIP_CHECK(hipGetLastError());
-	PC_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, f_ext, p_ext, (int)n + 1, st));
-	PC_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, f_int, p_int, (int)n + 1, st));
-	const unsigned long long cells = (unsigned long long)n*ostride;
-	hipLaunchKernelGGL(pc_leak_rows_kernel, dim3((unsigned)((cells + 255)/256)), dim3(256), 0, st, ctx->d_leak_records, (long long)stride, idx3, (long long)n, (int)ne,
-	                   f_ext, f_int, p_ext, p_int, ctx->d_leak_out);
-	PC_HIP_CHECK(hipGetLastError());
-	unsigned int tot[2] = {0, 0};
-	PC_HIP_CHECK(hipMemcpyAsync(&tot[0], p_ext + n, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-	PC_HIP_CHECK(hipMemcpyAsync(&tot[1], p_int + n, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-	PC_HIP_CHECK(hipStreamSynchronize(st));
-	const size_t rows = (size_t)tot[0] + (size_t)tot[1];
-	if (rows) PC_HIP_CHECK(hipMemcpyAsync(ctx->h_leak_out, ctx->d_leak_out, rows*ostride*sizeof(double), hipMemcpyDeviceToHost, st));
-	PC_HIP_CHECK(hipStreamSynchronize(st));
-	ctx->leak_n_ext = (long long)tot[0];
-	ctx->leak_n_int = (long long)tot[1];
-	return PC_HIP_OK;
-}
 
 #endif /* PC_LEAK_KERNELS_H */

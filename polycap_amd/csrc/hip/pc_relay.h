@@ -450,7 +450,7 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 	if (posed) memcpy(pl.basis, basis, sizeof(pl.basis));
 
 	/* from here on the second context holds the relay, or nothing */
-	b->img.reset(); b->leak_events_of_run = 0; b->last_run_plain = 0;
+	b->img.reset(); b->leak.events_of_run = 0; b->last_run_plain = 0;
 	b->entries_epoch++;
 	b->last_call = PC_CALL_NONE;
 	b->run_pending = 0; b->run_slots = 0;

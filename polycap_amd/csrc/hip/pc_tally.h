@@ -244,7 +244,7 @@ static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s, const char *w
 	if (kind == 0) {
 		if (!c->img.valid)
 			return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": the last run kept no exit photons (run it with keep_images)");
-		if (c->leak_pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
+		if (c->leak.pending) {       /* a leak run may be repeated with a larger record buffer when it is waited for */
 			int st = pc_hip_transmission_wait(c, nullptr);
 			if (st) return st;
 		}
@@ -254,13 +254,14 @@ static int pc_spot_source(pc_hip_ctx *c, int kind, pc_spot_src &s, const char *w
 		s.w = v.w; s.ws = v.l.ws;
 		return PC_HIP_OK;
 	}
-	if (!c->leak_events_of_run)
+	if (!c->leak.events_of_run)
 		return pc_fail(PC_HIP_ERR_INVALID, std::string(who) + ": leak events need a leak_calc source run (pc_hip_transmission_run_leak) as the last run");
-	int st = pc_hip_transmission_wait(c, nullptr);      /* the events are ordered into d_leak_out when the run is waited for */
+	int st = pc_hip_transmission_wait(c, nullptr);      /* the events are ordered into their lists when the run is waited for */
 	if (st) return st;
 	const long long stride = PC_HIP_LEAK_HDR + ne;
-	s.n = (kind == 1) ? c->leak_n_ext : c->leak_n_int;
-	s.p = c->d_leak_out + ((kind == 1) ? 0 : c->leak_n_ext*stride);
+	const pc_leak_list l = c->leak.list(kind - 1, (size_t)ne);   /* a tally's kinds 1, 2 are the lists 0 (extleak), 1 (intleak) */
+	s.n = l.n;
+	s.p = l.dev;
 	s.ss = stride; s.fs = 1; s.f_x = 2; s.f_dx = 5; s.has_dz = 1;
 	s.w = s.p + PC_HIP_LEAK_HDR; s.ws = stride;
 	return PC_HIP_OK;

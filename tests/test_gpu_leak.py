@@ -245,6 +245,33 @@ def test_order_of_the_slots_does_not_change_a_leak_run(pa, oracle, optic, leaks)
         assert units.min() > 0 and units.max() > 20 * units.mean() / 4      # every slot traced; a heavy tail exists
 
 
+def test_automatic_order_on_one_block(pa, oracle, optic, leaks, monkeypatch, capfd):
+    """The automatic order at the smallest shape that takes it: leak_stack_mb = 1 leaves the leak kernel one block of 256 lanes, and
+    600 slots lie inside the window 2*lanes <= n < 5*lanes (tests/test_leak_plan_cpu.py), with a heavy tier of 600/400 = 1 slot.
+    The pre-pass, the planner and the ordered launch run (the diagnostic line says so) and change nothing in the results."""
+    amu, scatf = constants(leaks, 10)
+    src = (2000., 0.2065, 0.2065, -1., 0., 0., 0., 0.5)
+    prob = problem(pa, optic, [10.0], [amu], [scatf], source=src)
+    n, seed = 600, 20000        # of the seeds 1..7 and 20000, four make a launch that is bound by its longest slot: 3, 4, 6, 20000
+    with pa.TraceContext(prob) as ctx:
+        ctx.set_option("leak_stack_mb", 1)
+        ctx.set_option("leak_order", 0)
+        plain = ctx.transmission(seed, 0, n, leak_calc=True)
+        ctx.set_option("leak_order", 1)
+        ctx.set_option("leak_slot_units", 1)
+        monkeypatch.setenv("POLYCAP_LEAK_TIMING", "1")      # read when the run starts
+        capfd.readouterr()
+        ordered = ctx.transmission(seed, 0, n, leak_calc=True)
+        err = capfd.readouterr().err
+        units = ctx.leak_slot_units(0, n)
+    assert np.array_equal(ordered["counters"], plain["counters"]) and np.array_equal(ordered["sum_weights"], plain["sum_weights"])
+    assert np.array_equal(ordered["ext"], plain["ext"]) and np.array_equal(ordered["int"], plain["int"])
+    assert units.min() > 0
+    lines = [l for l in err.splitlines() if l.startswith("leak order:")]
+    assert len(lines) == 1, err
+    assert lines[0].startswith("leak order: plain pre-pass + copy ") and " sort " in lines[0], lines[0]
+
+
 # noise constants c = std(device - oracle, relative) x sqrt(N_started) of identical-seed leak runs, measured over the 16 seeds of
 # tests/golden/oracle_leak_seeds.json (test_leak_driver_against_the_oracle_seed_by_seed prints them; profiles/r04/leak_parity_seeds.txt)
 LEAK_NOISE = {"started": 0.47, "eff": 0.56, "n_ext": 1.76, "n_int": 0.52, "ext_w": 3.38, "int_w": 0.95}
