@@ -74,25 +74,20 @@ struct pc_hip_group {
 __global__ void pc_pack_totals_kernel(const pc_totals *t, int n_sums, long long *vec)
 {
 	const int k = blockIdx.x*blockDim.x + threadIdx.x;
-	if (k < 6) vec[k] = (long long)t->counters[k];
+	if (k < PC_N_COUNTERS) vec[k] = (long long)t->counters[k];
 	if (k < n_sums) {
-		const unsigned long long *sw = (const unsigned long long *)(t + 1);
-		const unsigned long long lo = sw[2*k], hi = sw[2*k + 1];
-		vec[6 + 4*k] = (long long)(lo & 0xffffffffull);
-		vec[6 + 4*k + 1] = (long long)(lo >> 32);
-		vec[6 + 4*k + 2] = (long long)(hi & 0xffffffffull);
-		vec[6 + 4*k + 3] = (long long)(hi >> 32);
+		const unsigned long long *sw = PC_TOTALS_SUMW(t);
+		pc_exact_split(sw[2*k], sw[2*k + 1], vec + PC_N_COUNTERS + 4*k);
 	}
 }
 
 static void pc_unpack_limbs(const long long *vec, size_t ne, int64_t counters[6], uint64_t *fixed)
 {
-	for (int k = 0; k < 6; k++) counters[k] = vec[k];
+	for (int k = 0; k < PC_N_COUNTERS; k++) counters[k] = vec[k];
 	for (size_t e = 0; e < ne; e++) {
-		unsigned __int128 v = 0;
-		for (int l = 3; l >= 0; l--) v = (v << 32) + (unsigned __int128)(unsigned long long)vec[6 + 4*e + l];
-		fixed[2*e] = (uint64_t)v;
-		fixed[2*e + 1] = (uint64_t)(v >> 64);
+		const pc_exact_pair v = pc_exact_join(vec + PC_N_COUNTERS + 4*e);
+		fixed[2*e] = v.lo;
+		fixed[2*e + 1] = v.hi;
 	}
 }
 
@@ -309,7 +304,7 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 {
 	if (!g || !counters) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_group_totals: NULL argument");
 	const size_t N = g->ctx.size(), ne = (size_t)g->ctx[0]->host.pm.n_energies;
-	const size_t n_sums = g->run_squares ? 2*ne : ne, len = 6 + 4*n_sums;
+	const size_t n_sums = g->run_squares ? 2*ne : ne, len = PC_N_COUNTERS + 4*n_sums;
 	float ms_max = 0.f;
 	for (size_t k = 0; k < N; k++) {
 		if (g->count[k] == 0) continue;
@@ -377,12 +372,11 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 				st = pc_hip_transmission_moments(g->ctx[k], fx.data() + 2*ne);
 				if (st) return st;
 			}
-			for (int j = 0; j < 6; j++) total[j] += c[j];
+			for (int j = 0; j < PC_N_COUNTERS; j++) total[j] += c[j];
 			for (size_t e = 0; e < n_sums; e++) {
-				total[6 + 4*e] += (long long)(fx[2*e] & 0xffffffffull);
-				total[6 + 4*e + 1] += (long long)(fx[2*e] >> 32);
-				total[6 + 4*e + 2] += (long long)(fx[2*e + 1] & 0xffffffffull);
-				total[6 + 4*e + 3] += (long long)(fx[2*e + 1] >> 32);
+				long long limb[4];
+				pc_exact_split(fx[2*e], fx[2*e + 1], limb);
+				for (int l = 0; l < 4; l++) total[PC_N_COUNTERS + 4*e + l] += limb[l];
 			}
 		}
 	}
@@ -397,7 +391,7 @@ int pc_hip_group_totals(pc_hip_group *g, int reduce, double *sum_weights, int64_
 		if (sum_weights) sum_weights[e] = pc_hip_fixed_to_double(fixed[2*e], fixed[2*e + 1]);
 		if (sumw_fixed) { sumw_fixed[2*e] = fixed[2*e]; sumw_fixed[2*e + 1] = fixed[2*e + 1]; }
 	}
-	if (counters[4] != 0)
+	if (counters[PC_CNT_FAILED] != 0)
 		return pc_fail(PC_HIP_ERR_ATTEMPTS, "pc_hip_group_totals: some slots exhausted max_attempts without a transmitted photon");
 	return PC_HIP_OK;
 }

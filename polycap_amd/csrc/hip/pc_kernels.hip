@@ -35,6 +35,8 @@
 #include "pc_moments.h"
 #include "pc_plan.h"
 #include "pc_images.h"
+#include "pc_exact.h"
+#include "pc_totals.h"      /* struct pc_totals: the block the kernels add to */
 
 #ifndef PC_MARCH_UNROLL
 #define PC_MARCH_UNROLL 4      /* march steps between two ballots of the burst loop.  With march_stop = 8 (a burst goes on while 8 lanes march):
@@ -53,15 +55,6 @@
 #endif
 
 /* --------------------------------------------------------------------------- kernel arguments */
-
-struct pc_totals {             /* device-resident totals of one run */
-	unsigned long long counters[8];   /* iexit, not_entered, not_transmitted, sum_irefl, failed_slots, launches */
-	unsigned long long phase[8];      /* scheduler statistics: march steps, march lane-steps, event phases, event lanes, new phases, new lanes */
-	unsigned long long next_slot;     /* work counter (relative slot index) */
-	unsigned long long pad;
-	/* followed by 2*n_energies u64: (lo, hi) fixed-point weight sums, then 2*n_energies u64: the same of the squared weights
-	 * (option "weight_squares") */
-};
 
 struct pc_kargs {
 	const double *g_z, *g_cap, *g_zh, *g_cap2, *g_hexd, *g_idz, *g_ext, *g_stp, *g_istp;
@@ -365,15 +358,15 @@ pc_trace_kernel(pc_kargs a)
 	 * would change how the source runs' instantiations are compiled) */
 #define PC_SCAN_FLUSH() do { \
 		if (u_pt >= 0 && lane == 0) { \
-			unsigned long long *t_ = a.sumw + u_pt*(6 + 4*(long long)a.pm.n_energies); \
-			if (u_exit) atomicAdd(&t_[0], u_exit); \
-			if (u_not_entered) atomicAdd(&t_[1], u_not_entered); \
-			if (u_not_trans) atomicAdd(&t_[2], u_not_trans); \
-			if (u_irefl) atomicAdd(&t_[3], u_irefl); \
-			if (u_failed) atomicAdd(&t_[4], u_failed); \
-			if (u_launch) atomicAdd(&t_[5], u_launch); \
-			if (NE == 1 && (u_acc_lo | u_acc_hi)) pc_atomic_add128(t_ + 6, u_acc_lo, u_acc_hi); \
-			if (NE == 1 && SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(t_ + 8, u_sq_lo, u_sq_hi); \
+			unsigned long long *t_ = a.sumw + u_pt*PC_SCAN_STRIDE((long long)a.pm.n_energies); \
+			if (u_exit) atomicAdd(&t_[PC_CNT_EXIT], u_exit); \
+			if (u_not_entered) atomicAdd(&t_[PC_CNT_NOT_ENTERED], u_not_entered); \
+			if (u_not_trans) atomicAdd(&t_[PC_CNT_NOT_TRANSMITTED], u_not_trans); \
+			if (u_irefl) atomicAdd(&t_[PC_CNT_IREFL], u_irefl); \
+			if (u_failed) atomicAdd(&t_[PC_CNT_FAILED], u_failed); \
+			if (u_launch) atomicAdd(&t_[PC_CNT_LAUNCHES], u_launch); \
+			if (NE == 1 && (u_acc_lo | u_acc_hi)) pc_atomic_add128(t_ + PC_SCAN_SUMS, u_acc_lo, u_acc_hi); \
+			if (NE == 1 && SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(t_ + PC_SCAN_SQUARES(1), u_sq_lo, u_sq_hi); \
 		} \
 		u_exit = u_not_entered = u_not_trans = u_irefl = u_failed = u_launch = 0; \
 		u_acc_lo = u_acc_hi = u_sq_lo = u_sq_hi = 0; \
@@ -654,7 +647,7 @@ pc_trace_kernel(pc_kargs a)
 							if (what == 1) {
 								unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
 								if constexpr (SCAN) {
-									unsigned long long *t = a.sumw + k_p*(6 + 4*(long long)a.pm.n_energies) + 6;
+									unsigned long long *t = a.sumw + k_p*PC_SCAN_STRIDE((long long)a.pm.n_energies) + PC_SCAN_SUMS;
 									pc_atomic_add128(t + 2*e, f, 0ull);
 									if (SQ) pc_atomic_add128(t + 2*ne + 2*e, pc_fix_sq(w), 0ull);
 								} else if (a.lds_acc) {
@@ -693,7 +686,7 @@ pc_trace_kernel(pc_kargs a)
 							if (SQ) pc_wave_acc128(mx ? f_w2 : 0ull, u_sq_lo, u_sq_hi);
 						} else if (NE > 1) {
 							/* a few energies: the group's exact sums go to the point at once (the weights are the lanes' until the launch below) */
-							unsigned long long *t = a.sumw + k*(6 + 4*(long long)a.pm.n_energies) + 6;
+							unsigned long long *t = a.sumw + k*PC_SCAN_STRIDE((long long)a.pm.n_energies) + PC_SCAN_SUMS;
 #pragma unroll
 							for (int e = 0; e < (NE > 0 ? NE : 1); e++) {
 								if (e < ner) {
@@ -836,9 +829,9 @@ pc_trace_kernel(pc_kargs a)
 	if constexpr (SCAN) {
 		PC_SCAN_FLUSH();
 		if (lane == 0) {
-			atomicAdd(&a.totals->phase[0], st_march); atomicAdd(&a.totals->phase[1], st_march_l);
-			atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event_l);
-			atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
+			atomicAdd(&a.totals->phase[PC_PH_MARCH], st_march); atomicAdd(&a.totals->phase[PC_PH_MARCH_LANES], st_march_l);
+			atomicAdd(&a.totals->phase[PC_PH_EVENT], st_event); atomicAdd(&a.totals->phase[PC_PH_EVENT_LANES], st_event_l);
+			atomicAdd(&a.totals->phase[PC_PH_NEW], st_new); atomicAdd(&a.totals->phase[PC_PH_NEW_LANES], st_new_l);
 		}
 		return;
 	}
@@ -857,15 +850,15 @@ pc_trace_kernel(pc_kargs a)
 		/* one set of atomics per wave */
 		const unsigned long long v0 = u_exit, v1 = u_not_entered, v2 = u_not_trans, v3 = u_irefl, v4 = u_failed, v5 = u_launch;
 		if (lane == 0) {
-			atomicAdd(&a.totals->counters[0], v0);
-			atomicAdd(&a.totals->counters[1], v1);
-			atomicAdd(&a.totals->counters[2], v2);
-			atomicAdd(&a.totals->counters[3], v3);
-			if (v4) atomicAdd(&a.totals->counters[4], v4);
-			atomicAdd(&a.totals->counters[5], v5);
-			atomicAdd(&a.totals->phase[0], st_march); atomicAdd(&a.totals->phase[1], st_march_l);
-			atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event_l);
-			atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
+			atomicAdd(&a.totals->counters[PC_CNT_EXIT], v0);
+			atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], v1);
+			atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], v2);
+			atomicAdd(&a.totals->counters[PC_CNT_IREFL], v3);
+			if (v4) atomicAdd(&a.totals->counters[PC_CNT_FAILED], v4);
+			atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], v5);
+			atomicAdd(&a.totals->phase[PC_PH_MARCH], st_march); atomicAdd(&a.totals->phase[PC_PH_MARCH_LANES], st_march_l);
+			atomicAdd(&a.totals->phase[PC_PH_EVENT], st_event); atomicAdd(&a.totals->phase[PC_PH_EVENT_LANES], st_event_l);
+			atomicAdd(&a.totals->phase[PC_PH_NEW], st_new); atomicAdd(&a.totals->phase[PC_PH_NEW_LANES], st_new_l);
 		}
 		if (NE == 1 && lane == 0)
 			pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
@@ -1107,7 +1100,7 @@ struct pc_hip_ctx {
 	double sweep_ct_tame = 1.;
 	int sweep_n_proxy = 0, sweep_proxy_e[2] = {0, 0};
 	/* last run */
-	pc_dev_buf<pc_totals> d_totals;        /* totals_bytes: pc_totals + 2*nE u64 weight sums + 2*nE u64 squared-weight sums */
+	pc_dev_buf<pc_totals> d_totals;        /* totals_bytes: the layout of pc_totals.h */
 	size_t totals_bytes = 0;
 	pc_image_store img;                    /* the exit-photon images of the last run, their options and the way out (pc_images.h) */
 	pc_dev_buf<unsigned long long> d_work; /* one work counter per part */
@@ -1171,8 +1164,8 @@ static void pc_fill_common(pc_hip_ctx *ctx, pc_kargs &a)
 	a.pool_refill = ctx->opts.pool_refill;
 	a.totals = ctx->d_totals;
 	a.work = &ctx->d_totals->next_slot;
-	a.sumw = (unsigned long long *)(ctx->d_totals + 1);
-	a.sumw2 = ctx->opts.weight_squares ? a.sumw + 2*(size_t)ctx->host.pm.n_energies : nullptr;
+	a.sumw = PC_TOTALS_SUMW(ctx->d_totals.p);
+	a.sumw2 = ctx->opts.weight_squares ? PC_TOTALS_SUMW2(ctx->d_totals.p, ctx->host.pm.n_energies) : nullptr;
 }
 
 /* What pc_trace_log_kernel needs to know about the run's energies (once per context):
@@ -1403,7 +1396,7 @@ int pc_hip_ctx_create(const pc_hip_problem *problem, int device, pc_hip_ctx **ou
 		PC_CTX_CHECK(hipMemcpy(ctx->d_ec_soa, soa.data(), soa.size()*sizeof(double), hipMemcpyHostToDevice));
 	}
 	ctx->leak.opts.max_depth = (int)std::min(65536.0, 2.0*ctx->host.pm.n_shells + 16.0);
-	ctx->totals_bytes = sizeof(pc_totals) + 4*ctx->host.ec.size()*sizeof(unsigned long long);
+	ctx->totals_bytes = PC_TOTALS_BYTES(ctx->host.ec.size());
 	PC_CTX_GROW(ctx->d_totals, (ctx->totals_bytes + sizeof(pc_totals) - 1)/sizeof(pc_totals), "the totals");
 	PC_CTX_CHECK(hipMemset(ctx->d_totals, 0, ctx->totals_bytes));
 #undef PC_CTX_CHECK
@@ -1513,8 +1506,6 @@ static int pc_batch_layout(pc_hip_ctx *ctx, int64_t n, bool host, pc_batch &b)
 	return PC_HIP_OK;
 }
 
-#define PC_LP_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return pc_fail(PC_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e)); } while (0)
-
 static int pc_batch_upload(pc_hip_ctx *ctx, const pc_batch &b, const double *start_coords, const double *start_dir, const double *start_elecv)
 {
 	const size_t N = b.N;
@@ -1522,7 +1513,7 @@ static int pc_batch_upload(pc_hip_ctx *ctx, const pc_batch &b, const double *sta
 	memcpy(h, start_coords, 3*N*sizeof(double));
 	memcpy(h + 3*N, start_dir, 3*N*sizeof(double));
 	memcpy(h + 6*N, start_elecv, 3*N*sizeof(double));
-	PC_LP_CHECK(hipMemcpyAsync(ctx->d_batch, h, 9*N*sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	PC_HIP_CHECK(hipMemcpyAsync(ctx->d_batch, h, 9*N*sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	return PC_HIP_OK;
 }
 
@@ -1530,7 +1521,7 @@ static int pc_batch_upload(pc_hip_ctx *ctx, const pc_batch &b, const double *sta
 static int pc_batch_trace(pc_hip_ctx *ctx, const pc_batch &b, int leak)
 {
 	const int64_t n = (int64_t)b.N;
-	PC_LP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->d_totals, 0, ctx->totals_bytes, ctx->stream));
 	ctx->run_squares = 0;          /* explicit launches keep no sums */
 	pc_kargs a;
 	pc_fill_common(ctx, a);
@@ -1546,7 +1537,7 @@ static int pc_batch_trace(pc_hip_ctx *ctx, const pc_batch &b, int leak)
 	L.begin(n, pc_plan_leak_capacity(L.opts.capacity, (int)b.ne, n, 4096));
 	int status = L.enqueue<PC_MODE_EXPLICIT>(*ctx, a);
 	if (status) return status;
-	PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
+	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	return L.run_until_fit(*ctx, &a);
 }
 
@@ -1555,8 +1546,8 @@ static int pc_batch_download(pc_hip_ctx *ctx, const pc_batch &b, const double *s
 {
 	const size_t N = b.N, ne = b.ne;
 	double *d = ctx->d_batch, *h = ctx->h_batch;
-	PC_LP_CHECK(hipMemcpyAsync(h + 9*N, d + 9*N, (b.doubles - 9*N)*sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	PC_LP_CHECK(hipStreamSynchronize(ctx->stream));
+	PC_HIP_CHECK(hipMemcpyAsync(h + 9*N, d + 9*N, (b.doubles - 9*N)*sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	PC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	{
 		const double *o = h + 9*N;        /* rc (ints, padded to N doubles), weights, exit coords / dir / elecv, irefl, dtravel */
 		memcpy(rc, o, N*sizeof(int)); o += N;
@@ -1576,7 +1567,6 @@ static int pc_batch_download(pc_hip_ctx *ctx, const pc_batch &b, const double *s
 	}
 	return PC_HIP_OK;
 }
-#undef PC_LP_CHECK
 
 static int pc_launch_photons_impl(pc_hip_ctx *ctx, int64_t n, const double *start_coords, const double *start_dir, const double *start_elecv,
                                   int32_t *rc, double *weights, double *exit_coords, double *exit_dir, double *exit_elecv,
@@ -1783,8 +1773,7 @@ int pc_hip_host_is_pinned(const void *p)
 
 double pc_hip_fixed_to_double(uint64_t lo, uint64_t hi)
 {
-	long double v = (long double)hi * 18446744073709551616.0L + (long double)lo;
-	return (double)(v / 4611686018427387904.0L);
+	return (double)(pc_exact_value(lo, hi) / PC_EXACT_2P62);
 }
 
 int pc_hip_transmission_totals(pc_hip_ctx *ctx, double *sum_weights, int64_t counters[6], uint64_t *sumw_fixed)
@@ -1794,19 +1783,19 @@ int pc_hip_transmission_totals(pc_hip_ctx *ctx, double *sum_weights, int64_t cou
 	if (st) return st;
 	std::vector<unsigned char> buf(ctx->totals_bytes);
 	PC_HIP_CHECK(hipMemcpy(buf.data(), ctx->d_totals, ctx->totals_bytes, hipMemcpyDeviceToHost));
-	const pc_totals *t = (const pc_totals *)buf.data();
-	const unsigned long long *sw = (const unsigned long long *)(t + 1);
+	const pc_totals &t = *(const pc_totals *)buf.data();
+	const unsigned long long *sw = PC_TOTALS_SUMW(&t);
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
 	if (counters)
-		for (int k = 0; k < 6; k++) counters[k] = (int64_t)t->counters[k];
-	if (t->counters[5] > 0 && ctx->last_run_plain)
-		ctx->refl_per_launch = (double)t->phase[3] / (double)t->counters[5];        /* segment visits (reflections, mostly) per launch,
+		for (int k = 0; k < PC_N_COUNTERS; k++) counters[k] = (int64_t)t.counters[k];
+	if (t.counters[PC_CNT_LAUNCHES] > 0 && ctx->last_run_plain)
+		ctx->refl_per_launch = (double)t.phase[PC_PH_EVENT_LANES] / (double)t.counters[PC_CNT_LAUNCHES];   /* segment visits (reflections, mostly) per launch,
 		                                                                              * absorbed photons included: what the next run chooses its kernel by */
 	for (size_t e = 0; e < ne; e++) {
 		if (sum_weights) sum_weights[e] = pc_hip_fixed_to_double(sw[2*e], sw[2*e+1]);
 		if (sumw_fixed) { sumw_fixed[2*e] = sw[2*e]; sumw_fixed[2*e+1] = sw[2*e+1]; }
 	}
-	if (t->counters[4] != 0)
+	if (t.counters[PC_CNT_FAILED] != 0)
 		return pc_fail(PC_HIP_ERR_ATTEMPTS, "pc_hip_transmission_totals: some slots exhausted max_attempts without a transmitted photon");
 	return PC_HIP_OK;
 }
@@ -1818,22 +1807,18 @@ int pc_hip_transmission_moments(pc_hip_ctx *ctx, uint64_t *sumw2_fixed)
 	int st = pc_hip_transmission_wait(ctx, nullptr);
 	if (st) return st;
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	PC_HIP_CHECK(hipMemcpy(sumw2_fixed, (const unsigned long long *)(ctx->d_totals + 1) + 2*ne, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	PC_HIP_CHECK(hipMemcpy(sumw2_fixed, PC_TOTALS_SUMW2(ctx->d_totals.p, ne), 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;
 }
 
 void pc_hip_efficiency_stderr(size_t n_energies, const uint64_t *sumw_fixed, const uint64_t *sumw2_fixed, const int64_t counters[6], double *out)
 {
 	/* N = every started photon: exit photons, not entered, not transmitted (the efficiency's denominator, open_area cancelled) */
-	const long double n = (long double)counters[0] + (long double)counters[1] + (long double)counters[2];
+	const long double n = (long double)counters[PC_CNT_EXIT] + (long double)counters[PC_CNT_NOT_ENTERED] + (long double)counters[PC_CNT_NOT_TRANSMITTED];
 	for (size_t e = 0; e < n_energies; e++) {
 		if (!(n >= 2.0L)) { out[e] = NAN; continue; }
-		const long double a = (long double)sumw_fixed[2*e + 1] * 18446744073709551616.0L + (long double)sumw_fixed[2*e];
-		const long double b = (long double)sumw2_fixed[2*e + 1] * 18446744073709551616.0L + (long double)sumw2_fixed[2*e];
-		const long double m = a / (n * 4611686018427387904.0L), q = b / (n * 4611686018427387904.0L);
-		long double v = q - m*m;
-		if (v < 0.0L) v = 0.0L;
-		out[e] = (double)sqrtl(v / (n - 1.0L));
+		const long double a = pc_exact_value(sumw_fixed[2*e], sumw_fixed[2*e + 1]), b = pc_exact_value(sumw2_fixed[2*e], sumw2_fixed[2*e + 1]);
+		out[e] = pc_exact_stderr(a / (n * PC_EXACT_2P62), b / (n * PC_EXACT_2P62), n);
 	}
 }
 
@@ -1849,7 +1834,7 @@ int pc_hip_phase_stats(pc_hip_ctx *ctx, int64_t stats[6])
 	if (st) return st;
 	pc_totals t;
 	PC_HIP_CHECK(hipMemcpy(&t, ctx->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-	for (int k = 0; k < 6; k++) stats[k] = (int64_t)t.phase[k];
+	for (int k = 0; k < PC_N_PHASE; k++) stats[k] = (int64_t)t.phase[k];
 	return PC_HIP_OK;
 }
 
@@ -1860,11 +1845,11 @@ int pc_hip_sweep_stats(pc_hip_ctx *ctx, int64_t stats[4], double *ct_tame, int p
 	if (st) return st;
 	pc_totals t;
 	PC_HIP_CHECK(hipMemcpy(&t, ctx->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-	const bool log_run = ctx->last_kernel == 4;
-	stats[0] = log_run ? (int64_t)t.phase[6] : 0;
-	stats[1] = log_run ? (int64_t)t.phase[7] : 0;
-	stats[2] = log_run ? (int64_t)t.counters[6] : 0;
-	stats[3] = log_run ? (int64_t)t.counters[7] : 0;
+	const bool log_run = ctx->last_kernel == PC_KERNEL_LOG;
+	stats[0] = log_run ? (int64_t)t.phase[PC_PH_LOG_PASSES] : 0;
+	stats[1] = log_run ? (int64_t)t.phase[PC_PH_LOG_ITERS] : 0;
+	stats[2] = log_run ? (int64_t)t.counters[PC_CNT_LOG_LIFE_SUM] : 0;
+	stats[3] = log_run ? (int64_t)t.counters[PC_CNT_LOG_LIFE_MAX] : 0;
 	if (ct_tame) *ct_tame = ctx->sweep_cert ? ctx->sweep_ct_tame : -1.;
 	if (proxies) { proxies[0] = ctx->sweep_cert ? ctx->sweep_proxy_e[0] : -1; proxies[1] = (ctx->sweep_cert && ctx->sweep_n_proxy > 1) ? ctx->sweep_proxy_e[1] : -1; }
 	return PC_HIP_OK;

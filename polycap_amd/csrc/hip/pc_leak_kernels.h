@@ -324,17 +324,17 @@ pc_leak_kernel(pc_kargs a, pc_leak_kargs lk)
 		unsigned long long v0 = pc_wave_sum_u64(n_exit), v1 = pc_wave_sum_u64(n_not_entered), v2 = pc_wave_sum_u64(n_not_trans);
 		unsigned long long v3 = pc_wave_sum_u64(s_irefl), v4 = pc_wave_sum_u64(n_failed), v5 = pc_wave_sum_u64(n_launch);
 		if (lane == 0) {
-			atomicAdd(&a.totals->counters[0], v0);
-			atomicAdd(&a.totals->counters[1], v1);
-			atomicAdd(&a.totals->counters[2], v2);
-			atomicAdd(&a.totals->counters[3], v3);
-			if (v4) atomicAdd(&a.totals->counters[4], v4);
-			atomicAdd(&a.totals->counters[5], v5);
+			atomicAdd(&a.totals->counters[PC_CNT_EXIT], v0);
+			atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], v1);
+			atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], v2);
+			atomicAdd(&a.totals->counters[PC_CNT_IREFL], v3);
+			if (v4) atomicAdd(&a.totals->counters[PC_CNT_FAILED], v4);
+			atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], v5);
 			/* scheduler statistics (pc_hip_phase_stats): units and lane-units of wall steps, wall probes, march */
-			atomicAdd(&a.totals->phase[0], st_units[0]); atomicAdd(&a.totals->phase[1], st_lanes[0]);
-			atomicAdd(&a.totals->phase[2], st_units[1]); atomicAdd(&a.totals->phase[3], st_lanes[1]);
-			atomicAdd(&a.totals->phase[4], st_units[2]); atomicAdd(&a.totals->phase[5], st_lanes[2]);
-			atomicAdd(&a.totals->phase[6], st_units[3]); atomicAdd(&a.totals->phase[7], st_lanes[3]);
+			atomicAdd(&a.totals->phase[PC_PH_LEAK_UNITS(0)], st_units[0]); atomicAdd(&a.totals->phase[PC_PH_LEAK_LANES(0)], st_lanes[0]);
+			atomicAdd(&a.totals->phase[PC_PH_LEAK_UNITS(1)], st_units[1]); atomicAdd(&a.totals->phase[PC_PH_LEAK_LANES(1)], st_lanes[1]);
+			atomicAdd(&a.totals->phase[PC_PH_LEAK_UNITS(2)], st_units[2]); atomicAdd(&a.totals->phase[PC_PH_LEAK_LANES(2)], st_lanes[2]);
+			atomicAdd(&a.totals->phase[PC_PH_LEAK_UNITS(3)], st_units[3]); atomicAdd(&a.totals->phase[PC_PH_LEAK_LANES(3)], st_lanes[3]);
 		}
 	}
 }

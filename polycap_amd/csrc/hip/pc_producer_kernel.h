@@ -586,24 +586,24 @@ pc_trace_producer_kernel(pc_kargs a)
 	}
 
 	if (lane == 0) {
-		if (u_exit) atomicAdd(&a.totals->counters[0], u_exit);
-		if (u_not_entered) atomicAdd(&a.totals->counters[1], u_not_entered);
-		if (u_not_trans) atomicAdd(&a.totals->counters[2], u_not_trans);
-		if (u_irefl) atomicAdd(&a.totals->counters[3], u_irefl);
-		if (u_failed) atomicAdd(&a.totals->counters[4], u_failed);
-		if (u_launch) atomicAdd(&a.totals->counters[5], u_launch);
+		if (u_exit) atomicAdd(&a.totals->counters[PC_CNT_EXIT], u_exit);
+		if (u_not_entered) atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], u_not_entered);
+		if (u_not_trans) atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], u_not_trans);
+		if (u_irefl) atomicAdd(&a.totals->counters[PC_CNT_IREFL], u_irefl);
+		if (u_failed) atomicAdd(&a.totals->counters[PC_CNT_FAILED], u_failed);
+		if (u_launch) atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], u_launch);
 		if (wave != 0) {
-			atomicAdd(&a.totals->phase[0], st_march); atomicAdd(&a.totals->phase[1], st_march_l);
-			atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event_l);
-			atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
+			atomicAdd(&a.totals->phase[PC_PH_MARCH], st_march); atomicAdd(&a.totals->phase[PC_PH_MARCH_LANES], st_march_l);
+			atomicAdd(&a.totals->phase[PC_PH_EVENT], st_event); atomicAdd(&a.totals->phase[PC_PH_EVENT_LANES], st_event_l);
+			atomicAdd(&a.totals->phase[PC_PH_NEW], st_new); atomicAdd(&a.totals->phase[PC_PH_NEW_LANES], st_new_l);
 		}
 		if (u_acc_lo | u_acc_hi) pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
 		if (SQ && (u_sq_lo | u_sq_hi)) pc_atomic_add128(a.sumw2, u_sq_lo, u_sq_hi);
-		if (wave == 0) atomicAdd(&a.totals->phase[6], st_batches);
+		if (wave == 0) atomicAdd(&a.totals->phase[PC_PH_PRODUCER_BATCHES], st_batches);
 	}
 	__syncthreads();
 	/* a wave that gave up waiting: the run is reported as failed (more failed slots than the run has slots) */
-	if (threadIdx.x == 0 && ctl.failed) atomicAdd(&a.totals->counters[4], (unsigned long long)a.n_slots + 1ull);
+	if (threadIdx.x == 0 && ctl.failed) atomicAdd(&a.totals->counters[PC_CNT_FAILED], (unsigned long long)a.n_slots + 1ull);
 }
 
 #endif /* PC_PRODUCER_KERNEL_H */

@@ -17,6 +17,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "pc_exact.h"
+
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
 #define __device__
@@ -128,8 +130,7 @@ static inline __host__ __device__ int pc_relay_pose_plain(double tilt_x, double 
 static inline double pc_relay_efficiency(uint64_t lo, uint64_t hi, int64_t n_started)
 {
 	if (n_started <= 0) return 0.;
-	const long double a = (long double)hi * 18446744073709551616.0L + (long double)lo;
-	return (double)(a / ((long double)n_started * 4611686018427387904.0L));
+	return (double)(pc_exact_value(lo, hi) / ((long double)n_started * PC_EXACT_2P62));
 }
 
 #ifndef PC_RELAY_HOST_ONLY
@@ -334,11 +335,11 @@ __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_
 	if (lane == 0 && c_in) {
 		/* the second context's totals as a source run of the injected photons would count them: exit, not entered (everything
 		 * that neither left nor was absorbed), not transmitted, reflections of the exit photons (both optics), launches */
-		atomicAdd(&totals->counters[0], c_exit);
-		atomicAdd(&totals->counters[1], c_in - c_exit - c_abs);
-		atomicAdd(&totals->counters[2], c_abs);
-		atomicAdd(&totals->counters[3], c_irefl);
-		atomicAdd(&totals->counters[5], c_in);
+		atomicAdd(&totals->counters[PC_CNT_EXIT], c_exit);
+		atomicAdd(&totals->counters[PC_CNT_NOT_ENTERED], c_in - c_exit - c_abs);
+		atomicAdd(&totals->counters[PC_CNT_NOT_TRANSMITTED], c_abs);
+		atomicAdd(&totals->counters[PC_CNT_IREFL], c_irefl);
+		atomicAdd(&totals->counters[PC_CNT_LAUNCHES], c_in);
 		atomicAdd(&relay_cnt[0], c_in); atomicAdd(&relay_cnt[1], c_exit); atomicAdd(&relay_cnt[2], c_abs);
 		atomicAdd(&relay_cnt[3], c_glass); atomicAdd(&relay_cnt[4], c_out); atomicAdd(&relay_cnt[5], c_err);
 	}
@@ -489,8 +490,8 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 		if (st) return st;
 		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
 		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
-		unsigned long long *sumw = (unsigned long long *)(b->d_totals + 1);
-		unsigned long long *sumw2 = b->opts.weight_squares ? sumw + 2*(size_t)ne : nullptr;
+		unsigned long long *sumw = PC_TOTALS_SUMW(b->d_totals.p);
+		unsigned long long *sumw2 = b->opts.weight_squares ? PC_TOTALS_SUMW2(b->d_totals.p, ne) : nullptr;
 		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
 		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
 		long long grid = (n_in + 255)/256;
@@ -583,10 +584,9 @@ int pc_hip_relay_totals(pc_hip_ctx *ctx, int64_t counters[8], uint64_t *sumw_fix
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_totals: the relay was made without option weight_squares");
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	const unsigned long long *sw = (const unsigned long long *)(ctx->d_totals + 1);
 	if (counters) memcpy(counters, ctx->relay_counters, sizeof(ctx->relay_counters));
-	if (sumw_fixed) PC_HIP_CHECK(hipMemcpy(sumw_fixed, sw, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
-	if (sumw2_fixed) PC_HIP_CHECK(hipMemcpy(sumw2_fixed, sw + 2*ne, 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (sumw_fixed) PC_HIP_CHECK(hipMemcpy(sumw_fixed, PC_TOTALS_SUMW(ctx->d_totals.p), 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (sumw2_fixed) PC_HIP_CHECK(hipMemcpy(sumw2_fixed, PC_TOTALS_SUMW2(ctx->d_totals.p, ne), 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;
 }
 

@@ -10,12 +10,6 @@
 
 static_assert(sizeof(pc_scan_point) == sizeof(pc_hip_scan_point), "pc_scan_point mirrors pc_hip_scan_point");
 
-/* u64 of exact totals per point: 6 counters, (lo, hi) weight sums, (lo, hi) squared-weight sums */
-static size_t pc_scan_stride(size_t ne)
-{
-	return 6 + 4*ne;
-}
-
 static int pc_scan_check(const char *fn, const pc_hip_scan_point *pts, int64_t n_points, int64_t n_per_point)
 {
 	const std::string f(fn);
@@ -42,7 +36,7 @@ static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points)
 	PC_HIP_CHECK(ctx->ev_scan0.ensure(hipEventDefault));
 	PC_HIP_CHECK(ctx->ev_scan1.ensure(hipEventDefault));
 	st = ctx->d_scan_pts.grow((size_t)n_points, "pc_hip_scan_run: could not allocate the point table");
-	if (!st) st = ctx->d_scan_tot.grow((size_t)n_points*pc_scan_stride(ne), "pc_hip_scan_run: could not allocate the per-point totals");
+	if (!st) st = ctx->d_scan_tot.grow((size_t)n_points*PC_SCAN_STRIDE(ne), "pc_hip_scan_run: could not allocate the per-point totals");
 	return st;
 }
 
@@ -100,7 +94,7 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	if (st) return st;
 	PC_HIP_CHECK(hipMemcpy(ctx->d_scan_pts, points, (size_t)n_points*sizeof(pc_scan_point), hipMemcpyHostToDevice));
 	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_totals, 0, sizeof(pc_totals), ctx->stream));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_tot, 0, (size_t)n_points*pc_scan_stride((size_t)ne)*sizeof(unsigned long long), ctx->stream));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_tot, 0, (size_t)n_points*PC_SCAN_STRIDE((size_t)ne)*sizeof(unsigned long long), ctx->stream));
 	pc_kargs a;
 	pc_fill_common(ctx, a);
 	a.totals = ctx->d_scan_totals;
@@ -144,14 +138,14 @@ int pc_hip_scan_totals(pc_hip_ctx *ctx, int64_t *counters, uint64_t *sumw_fixed,
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: sumw2_fixed: the last scan was made without option weight_squares");
 	int st = pc_hip_scan_wait(ctx, nullptr);
 	if (st) return st;
-	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = pc_scan_stride(ne), P = (size_t)ctx->scan_points;
+	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = PC_SCAN_STRIDE(ne), P = (size_t)ctx->scan_points;
 	std::vector<unsigned long long> buf(P*stride);
 	PC_HIP_CHECK(hipMemcpy(buf.data(), ctx->d_scan_tot, buf.size()*sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	for (size_t k = 0; k < P; k++) {
 		const unsigned long long *t = buf.data() + k*stride;
-		if (counters) for (int c = 0; c < 6; c++) counters[6*k + c] = (int64_t)t[c];
-		if (sumw_fixed) for (size_t e = 0; e < 2*ne; e++) sumw_fixed[2*ne*k + e] = t[6 + e];
-		if (sumw2_fixed) for (size_t e = 0; e < 2*ne; e++) sumw2_fixed[2*ne*k + e] = t[6 + 2*ne + e];
+		if (counters) for (int c = 0; c < PC_N_COUNTERS; c++) counters[PC_N_COUNTERS*k + c] = (int64_t)t[PC_SCAN_COUNTERS + c];
+		if (sumw_fixed) std::copy_n(t + PC_SCAN_SUMS, 2*ne, sumw_fixed + 2*ne*k);
+		if (sumw2_fixed) std::copy_n(t + PC_SCAN_SQUARES(ne), 2*ne, sumw2_fixed + 2*ne*k);
 	}
 	return PC_HIP_OK;
 }
@@ -241,22 +235,18 @@ int pc_hip_group_scan_totals(pc_hip_group *g, int64_t *counters, uint64_t *sumw_
 	const size_t P = (size_t)g->scan_points, ne2 = 2*(size_t)g->ctx[0]->host.pm.n_energies;
 	std::vector<int64_t> c(6*P), c_sum(6*P, 0);
 	std::vector<uint64_t> a(ne2*P), b(sumw2_fixed ? ne2*P : 0);
-	std::vector<unsigned __int128> a_sum(ne2/2*P, 0), b_sum(sumw2_fixed ? ne2/2*P : 0, 0);
+	std::vector<uint64_t> a_sum(ne2*P, 0), b_sum(sumw2_fixed ? ne2*P : 0, 0);
 	for (size_t k = 0; k < g->ctx.size(); k++) {
 		if (!g->scan_count[k]) continue;
 		int st = pc_hip_scan_totals(g->ctx[k], c.data(), a.data(), sumw2_fixed ? b.data() : nullptr);
 		if (st) return pc_fail(st, std::string("pc_hip_group_scan_totals: ") + g_last_error);
 		for (size_t i = 0; i < 6*P; i++) c_sum[i] += c[i];
-		for (size_t i = 0; i < ne2/2*P; i++) {
-			a_sum[i] += ((unsigned __int128)a[2*i + 1] << 64) | a[2*i];
-			if (sumw2_fixed) b_sum[i] += ((unsigned __int128)b[2*i + 1] << 64) | b[2*i];
-		}
+		pc_exact_add_pairs(a_sum.data(), a.data(), ne2/2*P);
+		if (sumw2_fixed) pc_exact_add_pairs(b_sum.data(), b.data(), ne2/2*P);
 	}
 	if (counters) memcpy(counters, c_sum.data(), 6*P*sizeof(int64_t));
-	for (size_t i = 0; i < ne2/2*P; i++) {
-		if (sumw_fixed) { sumw_fixed[2*i] = (uint64_t)a_sum[i]; sumw_fixed[2*i + 1] = (uint64_t)(a_sum[i] >> 64); }
-		if (sumw2_fixed) { sumw2_fixed[2*i] = (uint64_t)b_sum[i]; sumw2_fixed[2*i + 1] = (uint64_t)(b_sum[i] >> 64); }
-	}
+	if (sumw_fixed) std::copy(a_sum.begin(), a_sum.end(), sumw_fixed);
+	if (sumw2_fixed) std::copy(b_sum.begin(), b_sum.end(), sumw2_fixed);
 	return PC_HIP_OK;
 }
 

@@ -148,13 +148,13 @@ pc_trace_log_kernel(pc_kargs a)
 	 * clears them.  A macro, as in pc_trace_kernel */
 #define PCS_SCAN_FLUSH() do { \
 		if (u_pt >= 0 && lane == 0) { \
-			unsigned long long *t_ = a.sumw + u_pt*(6 + 4*(long long)ne); \
-			if (u_exit) { atomicAdd(&t_[0], u_exit); atomicAdd(&a.totals->counters[0], u_exit); } \
-			if (u_not_entered) { atomicAdd(&t_[1], u_not_entered); atomicAdd(&a.totals->counters[1], u_not_entered); } \
-			if (u_not_trans) { atomicAdd(&t_[2], u_not_trans); atomicAdd(&a.totals->counters[2], u_not_trans); } \
-			if (u_irefl) { atomicAdd(&t_[3], u_irefl); atomicAdd(&a.totals->counters[3], u_irefl); } \
-			if (u_failed) { atomicAdd(&t_[4], u_failed); atomicAdd(&a.totals->counters[4], u_failed); } \
-			if (u_launch) { atomicAdd(&t_[5], u_launch); atomicAdd(&a.totals->counters[5], u_launch); } \
+			unsigned long long *t_ = a.sumw + u_pt*PC_SCAN_STRIDE((long long)ne); \
+			if (u_exit) { atomicAdd(&t_[PC_CNT_EXIT], u_exit); atomicAdd(&a.totals->counters[PC_CNT_EXIT], u_exit); } \
+			if (u_not_entered) { atomicAdd(&t_[PC_CNT_NOT_ENTERED], u_not_entered); atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], u_not_entered); } \
+			if (u_not_trans) { atomicAdd(&t_[PC_CNT_NOT_TRANSMITTED], u_not_trans); atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], u_not_trans); } \
+			if (u_irefl) { atomicAdd(&t_[PC_CNT_IREFL], u_irefl); atomicAdd(&a.totals->counters[PC_CNT_IREFL], u_irefl); } \
+			if (u_failed) { atomicAdd(&t_[PC_CNT_FAILED], u_failed); atomicAdd(&a.totals->counters[PC_CNT_FAILED], u_failed); } \
+			if (u_launch) { atomicAdd(&t_[PC_CNT_LAUNCHES], u_launch); atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], u_launch); } \
 		} \
 		u_exit = u_not_entered = u_not_trans = u_irefl = u_failed = u_launch = 0; \
 	} while (0)
@@ -307,7 +307,7 @@ pc_trace_log_kernel(pc_kargs a)
 						if constexpr (SCAN) {
 							/* the point's global sums; the take-back adds the two's complement (f, f2 > 0 here) */
 							const long long k = (long long)(((unsigned long long)vbad[qc] << 32) | (unsigned long long)vcnt[qc]);
-							unsigned long long *t = a.sumw + k*(6 + 4*(long long)ne) + 6;
+							unsigned long long *t = a.sumw + k*PC_SCAN_STRIDE((long long)ne) + PC_SCAN_SUMS;
 							if (!undo) {
 								pc_atomic_add128(t + 2*ee, f, 0ull);
 								if (f2) pc_atomic_add128(t + 2*ne + 2*ee, f2, 0ull);
@@ -565,7 +565,7 @@ pc_trace_log_kernel(pc_kargs a)
 							const unsigned long long f = (unsigned long long)(w * PC_FIX_SCALE);
 							if constexpr (SCAN) {
 								if (f) {
-									unsigned long long *t = a.sumw + k_p*(6 + 4*(long long)ne) + 6;
+									unsigned long long *t = a.sumw + k_p*PC_SCAN_STRIDE((long long)ne) + PC_SCAN_SUMS;
 									pc_atomic_add128(t + 2*e, f, 0ull);
 									if (SQ) { const unsigned long long f2 = pc_fix_sq(w); if (f2) pc_atomic_add128(t + 2*ne + 2*e, f2, 0ull); }
 								}
@@ -709,18 +709,18 @@ pc_trace_log_kernel(pc_kargs a)
 	}
 #undef PCS_SCAN_FLUSH
 	if (lane == 0) {
-		atomicAdd(&a.totals->counters[0], u_exit);
-		atomicAdd(&a.totals->counters[1], u_not_entered);
-		atomicAdd(&a.totals->counters[2], u_not_trans);
-		atomicAdd(&a.totals->counters[3], u_irefl);
-		if (u_failed) atomicAdd(&a.totals->counters[4], u_failed);
-		atomicAdd(&a.totals->counters[5], u_launch);
-		atomicAdd(&a.totals->phase[0], st_march); atomicAdd(&a.totals->phase[1], st_march_l);
-		atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event_l);
-		atomicAdd(&a.totals->phase[4], st_new); atomicAdd(&a.totals->phase[5], st_new_l);
-		atomicAdd(&a.totals->phase[6], st_pass); atomicAdd(&a.totals->phase[7], st_iter);
+		atomicAdd(&a.totals->counters[PC_CNT_EXIT], u_exit);
+		atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], u_not_entered);
+		atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], u_not_trans);
+		atomicAdd(&a.totals->counters[PC_CNT_IREFL], u_irefl);
+		if (u_failed) atomicAdd(&a.totals->counters[PC_CNT_FAILED], u_failed);
+		atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], u_launch);
+		atomicAdd(&a.totals->phase[PC_PH_MARCH], st_march); atomicAdd(&a.totals->phase[PC_PH_MARCH_LANES], st_march_l);
+		atomicAdd(&a.totals->phase[PC_PH_EVENT], st_event); atomicAdd(&a.totals->phase[PC_PH_EVENT_LANES], st_event_l);
+		atomicAdd(&a.totals->phase[PC_PH_NEW], st_new); atomicAdd(&a.totals->phase[PC_PH_NEW_LANES], st_new_l);
+		atomicAdd(&a.totals->phase[PC_PH_LOG_PASSES], st_pass); atomicAdd(&a.totals->phase[PC_PH_LOG_ITERS], st_iter);
 		const unsigned long long life = __builtin_readcyclecounter() - t_begin;
-		atomicAdd(&a.totals->counters[6], life);
-		atomicMax(&a.totals->counters[7], life);
+		atomicAdd(&a.totals->counters[PC_CNT_LOG_LIFE_SUM], life);
+		atomicMax(&a.totals->counters[PC_CNT_LOG_LIFE_MAX], life);
 	}
 }

@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "pc_exact.h"
+
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
 #define __device__
@@ -115,12 +117,11 @@ static inline pc_tally_grid pc_tally_grid_wide(long long cus, long long groups, 
 	return g;
 }
 
-/* (lo, hi) += (add_lo, add_hi) mod 2^128: unsigned, and so two's complement signed as well */
+/* (lo, hi) += (add_lo, add_hi) mod 2^128: the device spelling of pc_exact_add */
 static inline __host__ __device__ void pc_add128(unsigned long long &lo, unsigned long long &hi, unsigned long long add_lo, unsigned long long add_hi)
 {
-	const unsigned long long o = lo;
-	lo += add_lo;
-	hi += add_hi + (lo < o ? 1ull : 0ull);
+	const pc_exact_pair s = pc_exact_add(lo, hi, add_lo, add_hi);
+	lo = s.lo; hi = s.hi;
 }
 
 /* The square of one entry's quantised weight W = pc_spot_q(w) <= 2^32: the integer product W*W <= 2^64 in units of 2^-64, as
@@ -141,12 +142,8 @@ static inline void pc_tally_stderr(size_t n_cells, const uint64_t *sums, const u
 	const long double n = (long double)n_started;
 	for (size_t k = 0; k < n_cells; k++) {
 		if (!(n >= 2.0L)) { out[k] = NAN; continue; }
-		const long double a = (long double)sums[k];
-		const long double b = (long double)squares[2*k + 1] * 18446744073709551616.0L + (long double)squares[2*k];
-		const long double m = a / (n * 4294967296.0L), q = b / (n * 18446744073709551616.0L);
-		long double v = q - m*m;
-		if (v < 0.0L) v = 0.0L;
-		out[k] = (double)sqrtl(v / (n - 1.0L));
+		const long double a = (long double)sums[k], b = pc_exact_value(squares[2*k], squares[2*k + 1]);
+		out[k] = pc_exact_stderr(a / (n * PC_EXACT_2P32), b / (n * PC_EXACT_2P64), n);
 	}
 }
 
@@ -155,9 +152,9 @@ static inline void pc_tally_transmission(size_t n_energies, const uint64_t *pass
 	const uint64_t *rejected_w2, double *T, double *T_err)
 {
 	for (size_t e = 0; e < n_energies; e++) {
-		const long double P = (long double)passed_w[e] / 4294967296.0L, R = (long double)rejected_w[e] / 4294967296.0L;
-		const long double P2 = ((long double)passed_w2[2*e + 1] * 18446744073709551616.0L + (long double)passed_w2[2*e]) / 18446744073709551616.0L;
-		const long double R2 = ((long double)rejected_w2[2*e + 1] * 18446744073709551616.0L + (long double)rejected_w2[2*e]) / 18446744073709551616.0L;
+		const long double P = (long double)passed_w[e] / PC_EXACT_2P32, R = (long double)rejected_w[e] / PC_EXACT_2P32;
+		const long double P2 = pc_exact_value(passed_w2[2*e], passed_w2[2*e + 1]) / PC_EXACT_2P64;
+		const long double R2 = pc_exact_value(rejected_w2[2*e], rejected_w2[2*e + 1]) / PC_EXACT_2P64;
 		const long double tot = P + R;
 		if (!(tot > 0.0L)) {
 			if (T) T[e] = NAN;

@@ -97,14 +97,14 @@ pc_trace_wave_kernel(pc_kargs a)
 		}
 	}
 	if (lane == 0) {
-		if (u_exit) atomicAdd(&a.totals->counters[0], u_exit);
-		if (u_not_entered) atomicAdd(&a.totals->counters[1], u_not_entered);
-		if (u_not_trans) atomicAdd(&a.totals->counters[2], u_not_trans);
-		if (u_irefl) atomicAdd(&a.totals->counters[3], u_irefl);
-		if (u_failed) atomicAdd(&a.totals->counters[4], u_failed);
-		if (u_launch) atomicAdd(&a.totals->counters[5], u_launch);
-		atomicAdd(&a.totals->phase[0], st_scan); atomicAdd(&a.totals->phase[1], st_scan*64ull);
-		atomicAdd(&a.totals->phase[2], st_event); atomicAdd(&a.totals->phase[3], st_event);
+		if (u_exit) atomicAdd(&a.totals->counters[PC_CNT_EXIT], u_exit);
+		if (u_not_entered) atomicAdd(&a.totals->counters[PC_CNT_NOT_ENTERED], u_not_entered);
+		if (u_not_trans) atomicAdd(&a.totals->counters[PC_CNT_NOT_TRANSMITTED], u_not_trans);
+		if (u_irefl) atomicAdd(&a.totals->counters[PC_CNT_IREFL], u_irefl);
+		if (u_failed) atomicAdd(&a.totals->counters[PC_CNT_FAILED], u_failed);
+		if (u_launch) atomicAdd(&a.totals->counters[PC_CNT_LAUNCHES], u_launch);
+		atomicAdd(&a.totals->phase[PC_PH_MARCH], st_scan); atomicAdd(&a.totals->phase[PC_PH_MARCH_LANES], st_scan*64ull);
+		atomicAdd(&a.totals->phase[PC_PH_EVENT], st_event); atomicAdd(&a.totals->phase[PC_PH_EVENT_LANES], st_event);
 		if (u_acc_lo | u_acc_hi) pc_atomic_add128(a.sumw, u_acc_lo, u_acc_hi);
 	}
 }

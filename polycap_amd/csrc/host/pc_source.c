@@ -12,6 +12,7 @@
  */
 #define _GNU_SOURCE
 #include "pc_private.h"
+#include "pc_exact.h"
 
 #include <errno.h>
 #include <inttypes.h>
@@ -359,7 +360,6 @@ static int pc_tallies_track_squares(struct pc_tallies *ta, size_t ne)
 	return st;
 }
 
-static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne);
 static void *pc_beam_dup(const void *p, size_t bytes);
 
 /* the entries of `kind` of the last run into every tally, through the selection if there is one (applied here, its totals added) */
@@ -420,8 +420,8 @@ static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
 			uint64_t *w2 = malloc(sizeof(uint64_t)*12*ne);
 			st = (w2 != NULL) ? pc_hip_select_read_squares(s, w2, w2 + 6*ne) : PC_HIP_ERR_MEMORY;
 			if (st == PC_HIP_OK) {
-				pc_fixed_add(ta->sel_w2 + 2*kind*ne, w2 + 2*kind*ne, ne);
-				pc_fixed_add(ta->sel_w2 + 6*ne + 2*kind*ne, w2 + 6*ne + 2*kind*ne, ne);
+				pc_exact_add_pairs(ta->sel_w2 + 2*kind*ne, w2 + 2*kind*ne, ne);
+				pc_exact_add_pairs(ta->sel_w2 + 6*ne + 2*kind*ne, w2 + 6*ne + 2*kind*ne, ne);
 			}
 			free(w2);
 		}
@@ -435,16 +435,6 @@ static int pc_tallies_add(struct pc_tallies *ta, int kind, size_t ne)
 	if (st == PC_HIP_OK && ta->joint != NULL)
 		st = s != NULL ? pc_hip_joint_add_selected(ta->joint, kind, s) : pc_hip_joint_add(ta->joint, kind);
 	return st;
-}
-
-/* adds (lo, hi) sums of 2*ne u64 to `acc` exactly */
-static void pc_fixed_add(uint64_t *acc, const uint64_t *part, size_t ne)
-{
-	for (size_t e = 0; e < ne; e++) {
-		const uint64_t l = acc[2*e] + part[2*e];
-		acc[2*e + 1] += part[2*e + 1] + (l < acc[2*e] ? 1 : 0);
-		acc[2*e] = l;
-	}
 }
 
 /* POLYCAP_IMAGES=0 with spot maps, beam moments, histograms or joint histograms on one context: the exit data of the run stay on the device, and a run whose exit
@@ -474,12 +464,12 @@ static int pc_spot_chunked(pc_hip_ctx *ctx, struct pc_tallies *ta, uint64_t seed
 			break;
 		for (int k = 0; k < 6; k++)
 			counters[k] += c[k];
-		pc_fixed_add(fixed, part, ne);      /* 128-bit (lo, hi) sums */
+		pc_exact_add_pairs(fixed, part, ne);      /* 128-bit (lo, hi) sums */
 		if (fixed2 != NULL) {
 			st = pc_hip_transmission_moments(ctx, part);
 			if (st != PC_HIP_OK)
 				break;
-			pc_fixed_add(fixed2, part, ne);
+			pc_exact_add_pairs(fixed2, part, ne);
 		}
 	}
 	for (size_t e = 0; st == PC_HIP_OK && e < ne; e++)
