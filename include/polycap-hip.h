@@ -815,6 +815,70 @@ POLYCAP_EXTERN int pc_hip_pose_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const p
  * into ctx_b was not a relay. */
 POLYCAP_EXTERN int pc_hip_pose_counts(pc_hip_ctx *ctx_b, int64_t counts[2]);
 
+/* ---- emit relays: a thin sample between the two optics (confocal XRF: the sample sits in A's focus and re-emits isotropically, B
+ * stands at an angle, 90 degrees as a rule, and collects).  A relay flies A's exit photons straight into B; an emit relay flies them
+ * to a thin sheet, lets every photon that reaches it re-emit one photon towards a square target in B's entrance plane, and carries
+ * the target's solid angle over 4 pi as a weight.  The entries, the second stage, the finish, the records and the totals are the
+ * relay's (above); what follows replaces "inject".  IEEE fp64, evaluated in the order written, no contraction.
+ *
+ * The frame is A's exit frame of the posed relays: origin at the centre of A's exit plane, z along A's axis, a photon at (x, y, 0).
+ * The nominal confocal point is c0 = (0, 0, focus).  With b = sample_angle, a = det_angle (radians), sb = sin(b), cb = cos(b),
+ * sa = sin(a), ca = cos(a):
+ *   n_s = (sb, 0, cb)                                   the sheet's normal; the sheet passes through c0 + depth n_s
+ *   h_s = (n_s0*(depth*n_s0) + n_s1*(depth*n_s1)) + n_s2*(focus + depth*n_s2)        its offset n_s . (c0 + depth n_s)
+ *   u = (ca, 0, 0 - sa)     v = (0, 1, 0)     n = (sa, 0, ca)        B's x, y and z axes; n points from B's entrance into B
+ *   c_B[k] = ((c0[k] + wd*n[k]) + off_u*u[k]) + off_v*v[k]           B's entrance centre
+ * det_angle 0 is the in-line geometry, pi/2 the confocal one.  The sixteen numbers (n_s, h_s, u, v, n, c_B in this order) are computed
+ * once on the host, a turned sign as "0 - x" so that angles (0, 0) give the identity with plus-signed zeros, and travel to the
+ * kernels: no trigonometric function runs on the device, and pc_hip_emit_frame returns exactly these numbers.
+ * A spec is valid when its eight doubles are finite, focus >= 0, |sample_angle| < pi/2 strictly (below the double nearest pi/2),
+ * |det_angle| <= pi (the double nearest pi), wd > 0 and target_half > 0; map is NULL with n_map 0, or n_map >= 1 indices >= 0.
+ *   energies   fluorescence is detected at another energy than it was excited with: with a map, n_map must be B's energy count and
+ *              B's energy e takes A's weight of energy map[e], an index into A's grid; the two grids need not agree.  Without a map
+ *              both grids must be bit-equal (the relay's rule) and the map is the identity
+ *   entries    those of a posed relay, an optional selection included (asked first: a rejected photon is never counted as missed).
+ *              Every entry has the slot s of A's run it came from: slot0 + position in a slot-ordered store, slot0 + the id plane's
+ *              value in a compact store made with option "slot_ids"; a compact store without it is refused.  The random numbers of
+ *              an entry are keyed by s, so the result does not depend on the store's order
+ *   emission   from A's record (x, y), (dx, dy) and s, with R = target_half:
+ *              dz = sqrt((1 - dx*dx) - dy*dy)
+ *              sd = (n_s0*dx + n_s1*dy) + n_s2*dz,   sp = h_s - (n_s0*x + n_s1*y)
+ *              missed the sample when !(sd > 0) or !(sp >= 0): not injected, counted
+ *              t = sp / sd,   p = (x + dx*t, y + dy*t, dz*t)
+ *              u1, u2 = uniforms 0 and 1 of the stream (seed, s, attempt 0) of the source sampler (Philox4x32-10, 53 bits each)
+ *              a = (2*u1 - 1)*R,   b = (2*u2 - 1)*R         a point uniform on a square in B's entrance plane: no trigonometry, no
+ *                                                           rejection loop; what falls outside B's hexagon is rc -2 of stage 2
+ *              q = c_B - p;   f = (a + ((u0*q0 + u1*q1) + u2*q2),  b + ((v0*q0 + v1*q1) + v2*q2),  (n0*q0 + n1*q1) + n2*q2)
+ *              missed the detector when !(f2 > 0): the point of emission lies in B's entrance plane or behind it; not injected, counted
+ *              r2 = (f0*f0 + f1*f1) + f2*f2,   r = sqrt(r2),   d = (f0/r, f1/r, f2/r)
+ *              g = ((R*R)*d2) / (pi*r2)   with pi = 0x1.921fb54442d18p+1: the target's solid angle over 4 pi, per photon
+ *              electric vector (unpolarised emission without a random angle): h = sqrt(d2*d2 + d0*d0),
+ *              e1 = (d2/h, 0, 0 - d0/h),   e2 = (0 - (d0*d1)/h, h, 0 - (d1*d2)/h);   e1 for even s, e2 for odd s
+ *   stage 2    pc_hip_launch_photons of B on the photons (a, b, 0), d, e
+ *   finish     for every photon with rc 1 and every energy e of B: w = (wA[map[e]] * g) * wB[e]; sums, squares and counters as a relay
+ *   records    as a relay's, with pc_start_* = the injected state, pc_exit_dtravel = ((dA + t) + r) + dB, pc_exit_nrefl = nA + nB
+ *   counts     entries of A's store = n_in + skipped + missed_sample + missed_detector + rejected, always
+ * pc_hip_relay_totals and pc_hip_relay_efficiencies apply unchanged (pc_hip_pose_counts: missed = missed_sample + missed_detector).
+ * The efficiency is that of detected photons per photon started into A, per unit interaction probability in the sheet, for isotropic
+ * emission: the caller multiplies by mu t / cos and the yield.
+ * Refused with PC_HIP_ERR_INVALID and a message, before anything is launched and with both contexts and the selection left as they
+ * were: what pc_hip_pose_run refuses (without a map: unequal grids); an invalid spec; a compact A without slot ids; a map of the wrong
+ * length or with an index outside A's grid. */
+typedef struct {
+	double focus, sample_angle, depth, det_angle, wd, off_u, off_v, target_half;
+	uint64_t seed;
+	int32_t n_map;
+	const int32_t *map;
+} pc_hip_emit;
+/* host only: the spec alone (the map against the contexts' grids: pc_hip_emit_run) */
+POLYCAP_EXTERN int pc_hip_emit_validate(const pc_hip_emit *spec);
+/* host only: n_s (3), h_s, u (3), v (3), n (3), c_B (3) of a valid spec */
+POLYCAP_EXTERN int pc_hip_emit_frame(const pc_hip_emit *spec, double frame[16]);
+/* the emit relay of ctx_a's exit photons into ctx_b, through `select` (NULL: no aperture) */
+POLYCAP_EXTERN int pc_hip_emit_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_emit *spec, pc_hip_select *select);
+/* of the last relay into ctx_b, which must have been an emit relay: counts = {missed_sample, missed_detector, rejected} */
+POLYCAP_EXTERN int pc_hip_emit_counts(pc_hip_ctx *ctx_b, int64_t counts[3]);
+
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 

@@ -87,6 +87,13 @@ class SelectSpecS(C.Structure):
     _fields_ = [("n_cuts", C.c_int32), ("cuts", C.POINTER(SelectCutS))]
 
 
+class EmitS(C.Structure):
+    """struct pc_hip_emit"""
+    _fields_ = [("focus", C.c_double), ("sample_angle", C.c_double), ("depth", C.c_double), ("det_angle", C.c_double),
+                ("wd", C.c_double), ("off_u", C.c_double), ("off_v", C.c_double), ("target_half", C.c_double),
+                ("seed", C.c_uint64), ("n_map", C.c_int32), ("map", C.POINTER(C.c_int32))]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -374,6 +381,14 @@ def lib():
     L.pc_hip_pose_run.restype = C.c_int
     L.pc_hip_pose_counts.argtypes = [C.c_void_p, c_int64_p]
     L.pc_hip_pose_counts.restype = C.c_int
+    L.pc_hip_emit_validate.argtypes = [P(EmitS)]
+    L.pc_hip_emit_validate.restype = C.c_int
+    L.pc_hip_emit_frame.argtypes = [P(EmitS), c_double_p]
+    L.pc_hip_emit_frame.restype = C.c_int
+    L.pc_hip_emit_run.argtypes = [C.c_void_p, C.c_void_p, P(EmitS), C.c_void_p]
+    L.pc_hip_emit_run.restype = C.c_int
+    L.pc_hip_emit_counts.argtypes = [C.c_void_p, c_int64_p]
+    L.pc_hip_emit_counts.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

@@ -1139,6 +1139,11 @@ struct pc_hip_ctx {
 	int relay_acc_lds = 1;                 /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
 	int64_t relay_counters[8] = {0};
 	int64_t relay_lost[2] = {0, 0};        /* of a posed relay: photons that missed the entrance plane, photons its selection rejected */
+	/* emit relays (pc_emit.h) */
+	long long run_slot0 = 0;               /* first slot of the last source run: an emission draws on the stream of its photon's slot */
+	pc_dev_buf<int> d_emit_map;            /* which of the first optic's energies every energy of this context takes its weight from */
+	int relay_emit = 0;                    /* the relay this context holds is an emit relay */
+	int64_t emit_lost[3] = {0, 0, 0};      /* of an emit relay: missed the sample, missed the detector, rejected */
 	/* gathers of a selection's entries (pc_gather.h) */
 	int gather_tile = 0;                   /* option "gather_tile": entries per compaction tile, 0 = automatic */
 	long long gather_chunk_rows = 0;       /* option "gather_chunk_rows": rows per staging chunk, 0 = as many as fit in 128 MiB */
@@ -1735,6 +1740,7 @@ int pc_hip_transmission_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, int64
 		PC_HIP_CHECK(hipEventRecord(ctx->ev1, main_stream));
 	if (status) return status;
 	ctx->run_slots = n_slots;
+	ctx->run_slot0 = slot0;
 	ctx->run_pending = 1;
 	ctx->img.valid = keep_images ? 1 : 0;
 	return PC_HIP_OK;
@@ -1948,3 +1954,4 @@ int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_
 #include "pc_draw.h"
 #include "pc_scan.h"
 #include "pc_relay.h"
+#include "pc_emit.h"

@@ -388,12 +388,13 @@ static int pc_relay_check_pair(pc_hip_ctx *a, pc_hip_ctx *b, const std::string &
 	return PC_HIP_OK;
 }
 
-/* everything else that can refuse a relay, before anything is launched */
-static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const std::string &w)
+/* everything else that can refuse a relay, before anything is launched (same_grid false: an emit relay with an energy map, whose
+ * contexts have a grid each) */
+static int pc_relay_check(pc_hip_ctx *a, pc_hip_ctx *b, const std::string &w, bool same_grid = true)
 {
 	if (a->device != b->device)
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": the contexts are on different devices (" + std::to_string(a->device) + " and " + std::to_string(b->device) + ")");
-	if (a->energies.size() != b->energies.size() || memcmp(a->energies.data(), b->energies.data(), a->energies.size()*sizeof(double)) != 0)
+	if (same_grid && (a->energies.size() != b->energies.size() || memcmp(a->energies.data(), b->energies.data(), a->energies.size()*sizeof(double)) != 0))
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": the contexts need the same energy grid, bit for bit");
 	switch (a->last_call) {
 	case PC_CALL_RUN: break;
@@ -515,6 +516,7 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 	b->relay_counters[6] = skipped;
 	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
 	b->relay_lost[0] = lost[0]; b->relay_lost[1] = lost[1];
+	b->relay_emit = 0;
 	b->run_slots = n_out;
 	b->img.valid = 1;
 	b->last_call = PC_CALL_RELAY;

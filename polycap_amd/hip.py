@@ -314,6 +314,37 @@ class TraceContext:
         r["kernel_ms"] = other.wait()
         return r
 
+    def emit(self, other, focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=None, seed=0, energy_map=None,
+             select=None):
+        """An emit relay: the exit photons of this context's last source run (made with keep_images) hit a thin sample sheet
+        through the point `depth` cm along its normal from (0, 0, focus) behind this optic's exit plane, the normal turned by
+        `sample_angle` rad from this optic's axis towards +x; every photon that reaches the sheet re-emits one photon towards
+        `other`, whose axis is turned by `det_angle` rad (pi/2: the confocal geometry) and whose entrance centre lies `wd` cm from
+        the focus, displaced by `offset` = (u, v) cm in its own entrance plane (pc_hip_emit_run; the contract is in
+        include/polycap-hip.h).  The emitted direction is drawn towards a square of half-side `target_half` in the entrance plane
+        of `other`, with the stream (seed, slot of the photon), and carries the square's solid angle over 4 pi as a weight.
+        target_half defaults to ext[0] of `other`, the circumradius of its entrance hexagon (pc_outside_hex tests |y| and the two
+        other edge normals against ext * cos(pi/6), so the hexagon's corners lie at |x| = ext): the square covers the entrance
+        face.  `energy_map`[e] = the energy of this context whose weight energy e of `other` takes (fluorescence: excited at one
+        energy, detected at another); None: both contexts share one grid.  `select`: a Selection of this context, as in relay().
+        Returns what relay() returns, with missed_sample, missed_detector (their sum is `missed`) and rejected in counters; the
+        efficiencies are per photon started into this optic and per unit interaction probability in the sheet."""
+        if not isinstance(other, TraceContext):
+            raise TypeError("emit: other must be a TraceContext")
+        if select is not None and not isinstance(select, Selection):
+            raise TypeError("emit: select must be a Selection")
+        if target_half is None:
+            target_half = float(other.problem.ext[0])
+        spec, keep = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map)
+        st = self._L.pc_hip_emit_run(self._h, other._h, C.byref(spec), None if select is None else select._h)
+        if st != _cabi.PC_HIP_OK:
+            raise HipError("pc_hip_emit_run", st)
+        other._relay_squares = getattr(other, "_weight_squares", False)
+        r = other.relay_totals()
+        other._last_n = r["n_records"]
+        r["kernel_ms"] = other.wait()
+        return r
+
     def relay_totals(self):
         """Totals of the last relay into this context (pc_hip_relay_totals, pc_hip_relay_efficiencies): see relay()."""
         ne = self.problem.n_energies
@@ -331,6 +362,9 @@ class TraceContext:
             raise HipError("pc_hip_pose_counts", st)
         eff, err = relay_efficiencies(a, b, cnt)
         counters = dict(zip(RELAY_COUNTERS, (int(v) for v in cnt)), missed=int(lost[0]), rejected=int(lost[1]))
+        el = np.zeros(3, dtype=np.int64)
+        if self._L.pc_hip_emit_counts(self._h, el.ctypes.data_as(c_int64_p)) == _cabi.PC_HIP_OK:      # the relay was an emit relay
+            counters.update(missed_sample=int(el[0]), missed_detector=int(el[1]))
         return dict(efficiencies=eff, efficiency_stderr=err, counters=counters,
                     counters_array=cnt, sum_weights=np.array([fixed_to_double(a[2 * e], a[2 * e + 1]) for e in range(ne)]),
                     sumw_fixed=a.reshape(ne, 2), sumw2_fixed=None if b is None else b.reshape(ne, 2), n_records=int(cnt[1]))
@@ -506,6 +540,54 @@ def relay_rocking_curve(ctx_a, ctx_b, gap, tilts, offset=(0., 0.), select=None):
         cnt.append(r["counters"])
     have = len(err) > 0 and all(e is not None for e in err)
     return dict(tilts=tl, efficiencies=np.array(eff).reshape(len(tl), -1), efficiency_stderr=np.array(err).reshape(len(tl), -1) if have else None,
+                counters=cnt)
+
+
+def _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map):
+    """(pc_hip_emit, what its map points to)"""
+    s = _cabi.EmitS(float(focus), float(sample_angle), float(depth), float(det_angle), float(wd), float(offset[0]), float(offset[1]),
+                    float(target_half), int(seed), 0, None)
+    m = None
+    if energy_map is not None:
+        m = np.ascontiguousarray(energy_map, dtype=np.int32).reshape(-1)
+        s.n_map = int(m.shape[0])
+        s.map = m.ctypes.data_as(C.POINTER(C.c_int32))
+    return s, m
+
+
+def emit_valid(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1., energy_map=None):
+    """True when pc_hip_emit_validate accepts the spec (host only; the map against two contexts' grids is checked by emit())."""
+    spec, keep = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, energy_map)
+    return _cabi.lib().pc_hip_emit_validate(C.byref(spec)) == _cabi.PC_HIP_OK
+
+
+def emit_frame(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1.):
+    """The frame of an emit relay in the first optic's exit frame (pc_hip_emit_frame, host only): the sixteen numbers the kernels
+    get, as a dict of n_s [3] (the sheet's normal), h_s (its offset), u, v, n [3 each] (the second optic's axes), c_b [3] (its
+    entrance centre) and frame [16] (all of them in this order)."""
+    spec, keep = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, None)
+    f = np.zeros(16)
+    st = _cabi.lib().pc_hip_emit_frame(C.byref(spec), dptr(f))
+    if st != _cabi.PC_HIP_OK:
+        raise HipError("pc_hip_emit_frame", st)
+    return dict(n_s=f[0:3], h_s=float(f[3]), u=f[4:7], v=f[7:10], n=f[10:13], c_b=f[13:16], frame=f)
+
+
+def emit_depth_scan(ctx_a, ctx_b, depths, focus, sample_angle, det_angle, wd, offset=(0., 0.), target_half=None, seed=0,
+                    energy_map=None, select=None):
+    """A depth scan of the sample: one emit of ctx_a's last run into ctx_b per depth of `depths`, a host loop with one seed, so
+    that every depth re-emits with the same random numbers (common random numbers: smooth curves).  Returns depths [n],
+    efficiencies [n, n_energies], efficiency_stderr [n, n_energies] (option "weight_squares" on ctx_b, else None) and the emits'
+    counters as a list of dicts."""
+    dl = np.asarray(depths, dtype=np.float64).reshape(-1)
+    eff, err, cnt = [], [], []
+    for d in dl:
+        r = ctx_a.emit(ctx_b, focus, sample_angle, float(d), det_angle, wd, offset, target_half, seed, energy_map, select)
+        eff.append(r["efficiencies"])
+        err.append(r["efficiency_stderr"])
+        cnt.append(r["counters"])
+    have = len(err) > 0 and all(e is not None for e in err)
+    return dict(depths=dl, efficiencies=np.array(eff).reshape(len(dl), -1), efficiency_stderr=np.array(err).reshape(len(dl), -1) if have else None,
                 counters=cnt)
 
 
