@@ -134,173 +134,35 @@ struct pc_emit_place {
 	const int *emap;            /* energy e of the second optic takes the first one's weight emap[e] */
 };
 
-/* pc_emit_state of entry i, which is an exit photon, on the stream of its slot */
-static __device__ __forceinline__ int pc_emit_src_state(const pc_spot_src &s, const pc_emit_place &pl, long long i, double *o)
-{
-	const double *e = s.p + i*s.ss;
-	const double x = e[(long long)PC_F_EXITX*s.fs], y = e[(long long)PC_F_EXITY*s.fs], dx = e[(long long)PC_F_EDIRX*s.fs], dy = e[(long long)PC_F_EDIRY*s.fs];
-	const long long slot = pl.slot0 + (pl.ids ? pl.ids[i] : i);
-	return pc_emit_state(x, y, dx, dy, (uint64_t)slot, pl.fr, pl.R, pl.seed, o);
-}
+static_assert(PC_EMIT_SKIP == PC_RELAY_SKIP && PC_EMIT_INJECT == PC_RELAY_INJECT && PC_EMIT_REJECT == PC_RELAY_REJECT && PC_EMIT_MISS_SAMPLE == PC_RELAY_MISS
+              && PC_EMIT_MISS_DETECTOR == PC_RELAY_MISS_DETECTOR, "the emission's outcomes are the relay's");
 
-/* What becomes of entry i of the first store: the one predicate of the count and the inject kernels (pc_relay_entry's order: a
- * failed slot is skipped, the selection is asked before the flight) */
-static __device__ __forceinline__ int pc_emit_entry(const pc_spot_src &s, const pc_emit_place &pl, long long i, double *o)
-{
-	if (!pc_relay_src_valid(s, i)) return PC_EMIT_SKIP;
-	if (s.mask && !s.mask[i]) return PC_EMIT_REJECT;
-	return pc_emit_src_state(s, pl, i, o);
-}
-
-/* Stable compaction, step 1 (pc_relay_count_posed_kernel with three ways to be lost): counts[i / 64] = the entries of wave i / 64
- * that are injected; lost[0] += those that miss the sample, lost[1] += those that miss the detector, lost[2] += those the selection
- * rejects, one atomic per wave that has any. */
-__global__ void __launch_bounds__(256) pc_emit_count_kernel(pc_spot_src s, pc_emit_place pl, long long n, unsigned long long *counts,
-	unsigned long long *lost)
-{
-	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	double o[12];
-	const int what = (i < n) ? pc_emit_entry(s, pl, i, o) : PC_EMIT_SKIP;
-	const unsigned long long m = __ballot(what == PC_EMIT_INJECT), ms = __ballot(what == PC_EMIT_MISS_SAMPLE);
-	const unsigned long long md = __ballot(what == PC_EMIT_MISS_DETECTOR), mr = __ballot(what == PC_EMIT_REJECT);
-	if ((threadIdx.x & 63) == 0 && i < n) {
-		counts[i >> 6] = (unsigned long long)__popcll(m);
-		if (ms) atomicAdd(&lost[0], (unsigned long long)__popcll(ms));
-		if (md) atomicAdd(&lost[1], (unsigned long long)__popcll(md));
-		if (mr) atomicAdd(&lost[2], (unsigned long long)__popcll(mr));
+/* The emission as an injection rule of the relay's kernels (pc_relay.h): pc_emit_state on the stream of the entry's slot; the
+ * weight (wA[emap[e]] * g) * wB[e], the only place that reads the energy map; the path with the two flights. */
+struct pc_rule_emit {
+	typedef pc_emit_place place;
+	enum { N_STATE = 12, KIND = PC_RELAY_KIND_EMIT };
+	static __device__ __forceinline__ int fly(const pc_spot_src &s, const place &pl, long long i, double *o)
+	{
+		const double *e = s.p + i*s.ss;
+		const double x = e[(long long)PC_F_EXITX*s.fs], y = e[(long long)PC_F_EXITY*s.fs], dx = e[(long long)PC_F_EDIRX*s.fs], dy = e[(long long)PC_F_EDIRY*s.fs];
+		const long long slot = pl.slot0 + (pl.ids ? pl.ids[i] : i);
+		return pc_emit_state(x, y, dx, dy, (uint64_t)slot, pl.fr, pl.R, pl.seed, o);
 	}
-}
-
-/* Inject (pc_relay_inject_kernel with pc_emit_entry): every entry that is injected becomes one explicit photon of the second
- * context at the position the prefix sums give it; map[position] = its entry. */
-__global__ void __launch_bounds__(256) pc_emit_inject_kernel(pc_spot_src s, pc_emit_place pl, const unsigned long long *offs, long long n,
-	double *in_start, double *in_dir, double *in_elecv, long long *map)
-{
-	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	double o[12];
-	const int keep = (i < n) ? (pc_emit_entry(s, pl, i, o) == PC_EMIT_INJECT) : 0;
-	const unsigned long long m = __ballot(keep);
-	if (!keep) return;
-	const int lane = threadIdx.x & 63;
-	const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
-	in_start[3*pos] = o[0]; in_start[3*pos + 1] = o[1]; in_start[3*pos + 2] = o[2];
-	in_dir[3*pos] = o[3]; in_dir[3*pos + 1] = o[4]; in_dir[3*pos + 2] = o[5];
-	in_elecv[3*pos] = o[6]; in_elecv[3*pos + 1] = o[7]; in_elecv[3*pos + 2] = o[8];
-	map[pos] = i;
-}
-
-/* Finish (pc_relay_finish_kernel with the emission's state, weight and path): counters of the second stage's outcomes; for every
- * transmitted photon the weights (wA[emap[e]] * g) * wB[e], their exact sums (and the squares' when sumw2 is given) and its image
- * record at the position the prefix sums give it.  Integer sums only. */
-__global__ void __launch_bounds__(256) pc_emit_finish_kernel(pc_spot_src s, pc_emit_place pl, pc_relay_stage2 b, const long long *map,
-	const unsigned long long *offs, long long n_in, int ne, int acc_lds, double *rec_out, pc_totals *totals, unsigned long long *sumw,
-	unsigned long long *sumw2, unsigned long long *relay_cnt)
-{
-	extern __shared__ unsigned long long l_acc[];
-	const int tid = threadIdx.x, lane = tid & 63;
-	const int words = sumw2 ? 4 : 2;
-	if (acc_lds) {
-		for (int k = tid; k < words*ne; k += blockDim.x) l_acc[k] = 0ull;
-		__syncthreads();
+	static __device__ __forceinline__ void state(const pc_spot_src &s, const place &pl, long long ia, double *o) { (void)fly(s, pl, ia, o); }
+	/* pc_rule_posed's order: a failed slot is skipped, the selection is asked before the flight */
+	static __device__ __forceinline__ int entry(const pc_spot_src &s, const place &pl, long long i, double *o)
+	{
+		if (!pc_relay_src_valid(s, i)) return PC_RELAY_SKIP;
+		if (s.mask && !s.mask[i]) return PC_RELAY_REJECT;
+		return fly(s, pl, i, o);
 	}
-	unsigned long long *acc = acc_lds ? l_acc : sumw, *acc2 = acc_lds ? l_acc + 2*ne : sumw2;
-	const long long recd = PC_N_FIELDS + ne;
-	unsigned long long c_in = 0, c_exit = 0, c_abs = 0, c_glass = 0, c_out = 0, c_err = 0, c_irefl = 0;
-	for (long long i0 = (long long)blockIdx.x*blockDim.x + (tid - lane); i0 < n_in; i0 += (long long)gridDim.x*blockDim.x) {
-		const long long i = i0 + lane;
-		const bool act = i < n_in;
-		const int rc = act ? b.rc[i] : -99;
-		const bool ok = rc == 1;
-		const unsigned long long m = __ballot(ok);
-		c_in += (unsigned long long)__popcll(__ballot(act));
-		c_exit += (unsigned long long)__popcll(m);
-		c_abs += (unsigned long long)__popcll(__ballot(rc == 0));
-		c_glass += (unsigned long long)__popcll(__ballot(rc == 2));
-		c_out += (unsigned long long)__popcll(__ballot(rc == -2));
-		c_err += (unsigned long long)__popcll(__ballot(act && rc != 1 && rc != 0 && rc != 2 && rc != -2));
-		if (!m) continue;
-		long long ia = 0;
-		double *r = nullptr;
-		double g = 0.;
-		unsigned long long f_irefl = 0ull;
-		if (ok) {
-			ia = map[i];
-			const double *e = s.p + ia*s.ss;
-			/* the injected state again, from A's entry and its slot's stream: the same bits as the inject kernel wrote, and t, r and
-			 * g, which the batch buffer does not hold, come with them */
-			double o[12];
-			(void)pc_emit_src_state(s, pl, ia, o);
-			g = o[11];
-			const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
-			r = rec_out + pos*recd;
-			const long long n_a = ((const long long *)e)[(long long)PC_F_NREFL*s.fs], n_b = b.irefl[i];
-			r[PC_F_SRCX] = e[(long long)PC_F_SRCX*s.fs]; r[PC_F_SRCY] = e[(long long)PC_F_SRCY*s.fs];
-			r[PC_F_STARTX] = o[0]; r[PC_F_STARTY] = o[1];
-			r[PC_F_SDIRX] = o[3]; r[PC_F_SDIRY] = o[4];
-			r[PC_F_SEVX] = o[6]; r[PC_F_SEVY] = o[7];
-			r[PC_F_EXITX] = b.exit_coords[3*i]; r[PC_F_EXITY] = b.exit_coords[3*i + 1]; r[PC_F_EXITZ] = b.exit_coords[3*i + 2];
-			r[PC_F_EDIRX] = b.exit_dir[3*i]; r[PC_F_EDIRY] = b.exit_dir[3*i + 1];
-			/* a photon that met no wall keeps the electric vector it was given (as pc_hip_launch_photons reports it) */
-			r[PC_F_EEVX] = n_b ? b.exit_elecv[3*i] : o[6]; r[PC_F_EEVY] = n_b ? b.exit_elecv[3*i + 1] : o[7];
-			((long long *)r)[PC_F_NREFL] = n_a + n_b;
-			r[PC_F_DTRAVEL] = pc_emit_dtravel(e[(long long)PC_F_DTRAVEL*s.fs], o[9], o[10], b.dtravel[i]);
-			f_irefl = (unsigned long long)(n_a + n_b);
-		}
-		c_irefl += pc_wave_sum_u64(f_irefl);
-		for (int en = 0; en < ne; en++) {
-			double w = 0.;
-			if (ok) {
-				w = pc_emit_weight(s.w[ia*s.ws + pl.emap[en]], g, b.w[i*ne + en]);
-				r[PC_F_WEIGHTS + en] = w;
-			}
-			unsigned long long lo = 0ull, hi = 0ull;
-			pc_wave_acc128(ok ? pc_relay_fix(w) : 0ull, lo, hi);
-			if (lane == 0 && (lo | hi)) pc_atomic_add128(acc + 2*en, lo, hi);
-			if (sumw2) {
-				lo = hi = 0ull;
-				pc_wave_acc128(ok ? pc_fix_sq(w) : 0ull, lo, hi);
-				if (lane == 0 && (lo | hi)) pc_atomic_add128(acc2 + 2*en, lo, hi);
-			}
-		}
+	static __device__ __forceinline__ double weight(const pc_spot_src &s, const place &pl, long long ia, int en, const double *o, double w_b)
+	{
+		return pc_emit_weight(s.w[ia*s.ws + pl.emap[en]], o[11], w_b);
 	}
-	if (acc_lds) {
-		__syncthreads();
-		for (int en = tid; en < ne; en += blockDim.x) {
-			if (l_acc[2*en] | l_acc[2*en + 1]) pc_atomic_add128(sumw + 2*en, l_acc[2*en], l_acc[2*en + 1]);
-			if (sumw2 && (l_acc[2*ne + 2*en] | l_acc[2*ne + 2*en + 1])) pc_atomic_add128(sumw2 + 2*en, l_acc[2*ne + 2*en], l_acc[2*ne + 2*en + 1]);
-		}
-	}
-	if (lane == 0 && c_in) {
-		/* the second context's totals and the relay's counters, as pc_relay_finish_kernel counts them */
-		atomicAdd(&totals->counters[PC_CNT_EXIT], c_exit);
-		atomicAdd(&totals->counters[PC_CNT_NOT_ENTERED], c_in - c_exit - c_abs);
-		atomicAdd(&totals->counters[PC_CNT_NOT_TRANSMITTED], c_abs);
-		atomicAdd(&totals->counters[PC_CNT_IREFL], c_irefl);
-		atomicAdd(&totals->counters[PC_CNT_LAUNCHES], c_in);
-		atomicAdd(&relay_cnt[0], c_in); atomicAdd(&relay_cnt[1], c_exit); atomicAdd(&relay_cnt[2], c_abs);
-		atomicAdd(&relay_cnt[3], c_glass); atomicAdd(&relay_cnt[4], c_out); atomicAdd(&relay_cnt[5], c_err);
-	}
-}
-
-/* the counts and prefix sums over the first store (pc_emit_count_kernel, pc_relay_scan_kernel); lost = {missed the sample, missed
- * the detector, rejected} (waits for the stream) */
-static int pc_emit_offsets(pc_hip_ctx *b, const pc_spot_src &s, const pc_emit_place &pl, long long n, unsigned long long *d_lost,
-	long long *total, long long lost[3])
-{
-	const long long nw = (n + 63)/64;
-	PC_HIP_CHECK(hipMemsetAsync(d_lost, 0, 3*sizeof(unsigned long long), b->stream));
-	hipLaunchKernelGGL(pc_emit_count_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, b->stream, s, pl, n, (unsigned long long *)b->d_relay_scan, d_lost);
-	PC_HIP_CHECK(hipGetLastError());
-	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, (unsigned long long *)b->d_relay_scan, nw);
-	PC_HIP_CHECK(hipGetLastError());
-	unsigned long long t = 0, l[3] = {0, 0, 0};
-	PC_HIP_CHECK(hipMemcpyAsync(&t, b->d_relay_scan + nw, sizeof(t), hipMemcpyDeviceToHost, b->stream));
-	PC_HIP_CHECK(hipMemcpyAsync(l, d_lost, sizeof(l), hipMemcpyDeviceToHost, b->stream));
-	PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-	*total = (long long)t;
-	for (int k = 0; k < 3; k++) lost[k] = (long long)l[k];
-	return PC_HIP_OK;
-}
+	static __device__ __forceinline__ double dtravel(double d_a, const double *o, double d_b) { return pc_emit_dtravel(d_a, o[9], o[10], d_b); }
+};
 
 /* the spec alone: its eight doubles, and a map that is either absent or a list of indices */
 static int pc_emit_check_spec(const pc_hip_emit *sp, const std::string &w)
@@ -324,15 +186,12 @@ static void pc_emit_spec_frame(const pc_hip_emit *sp, double *fr)
 	pc_emit_frame(f, fr);
 }
 
-/* An emit relay behind its spec check: pc_relay_run's steps with the emission as the injection rule. */
-static int pc_emit_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_emit *sp, pc_hip_select *sel)
+/* what the pair of contexts can refuse of a valid spec: the map against the two grids (emap = the map, or the identity), then a
+ * first store without the slots of its entries */
+static int pc_emit_check_pair(const pc_hip_ctx *a, const pc_hip_ctx *b, const pc_hip_emit *sp, const std::string &w, std::vector<int> &emap)
 {
-	const char *who = "pc_hip_emit_run";
-	const std::string w(who);
-	int st = pc_relay_check(a, b, w, sp->map == nullptr);
-	if (st) return st;
 	const int ne = b->host.pm.n_energies;
-	std::vector<int> emap((size_t)ne);
+	emap.resize((size_t)ne);
 	if (sp->map) {
 		if ((size_t)sp->n_map != b->energies.size())
 			return pc_fail(PC_HIP_ERR_INVALID, w + ": n_map is " + std::to_string(sp->n_map) + ", but the second context has " + std::to_string(b->energies.size()) + " energies");
@@ -349,104 +208,6 @@ static int pc_emit_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_emit *sp, pc_h
 	if (a->img.plan.layout == PC_IMG_COMPACT && !a->img.device_view().ids)
 		return pc_fail(PC_HIP_ERR_INVALID, w + ": the first context's run was stored compact without its slots, which the emission's random numbers are keyed by: "
 		               "run it with option \"slot_ids\" 1, or without option \"compact_images\"");
-	PC_HIP_CHECK(hipSetDevice(a->device));
-	/* the first run is complete (and the apply of the selection behind it), and nothing of the second context is in flight */
-	st = pc_hip_transmission_wait(a, nullptr);
-	if (!st) st = pc_hip_transmission_wait(b, nullptr);
-	if (st) return st;
-	int64_t cnt_a[6];
-	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
-	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
-	pc_spot_src s;
-	st = pc_spot_source(a, 0, s, who);
-	if (st) return st;
-	if (sel) {
-		st = pc_relay_check_select(a, sel, s, w);
-		if (st) return st;
-		s.mask = sel->m[0].d_mask[0];
-	}
-	const long long n_a = s.n;
-	pc_emit_place pl;
-	pc_emit_spec_frame(sp, pl.fr);
-	pl.R = sp->target_half;
-	pl.seed = sp->seed;
-	pl.slot0 = a->run_slot0;
-	pl.ids = a->img.device_view().ids;
-	st = b->d_emit_map.grow((size_t)ne, (w + ": could not allocate the energy map").c_str());
-	if (st) return st;
-	pl.emap = b->d_emit_map;
-
-	/* from here on the second context holds the relay, or nothing */
-	b->img.reset(); b->leak.events_of_run = 0; b->last_run_plain = 0;
-	b->entries_epoch++;
-	b->last_call = PC_CALL_NONE;
-	b->run_pending = 0; b->run_slots = 0;
-	b->run_squares = b->opts.weight_squares;
-	b->last_ms = 0.f;
-	const size_t nw_a = (size_t)((n_a + 63)/64);
-	/* counts and offsets [nw_a + 1], the finish kernel's counters [8] behind the second compaction's, the count kernel's three last */
-	st = b->d_relay_scan.grow(nw_a + 1 + 8 + 3, (w + ": could not allocate the compaction counters").c_str());
-	if (!st) st = b->d_relay_map.grow((size_t)n_a, (w + ": could not allocate the photon map").c_str());
-	if (st) return st;
-	PC_HIP_CHECK(hipMemcpy(b->d_emit_map, emap.data(), (size_t)ne*sizeof(int), hipMemcpyHostToDevice));
-
-	long long n_in = 0, n_out = 0, lost[3] = {0, 0, 0};
-	st = pc_emit_offsets(b, s, pl, n_a, b->d_relay_scan + nw_a + 1 + 8, &n_in, lost);
-	if (st) return st;
-	const long long skipped = n_a - n_in - lost[0] - lost[1] - lost[2];
-	/* as in a relay: every entry the predicate skips must be a failed slot of A's run */
-	if (skipped != cnt_a[4])
-		return pc_fail(PC_HIP_ERR_INVALID, w + ": " + std::to_string(skipped) + " entries of the first run have no exit plane or a zero first weight, but "
-		               + std::to_string(cnt_a[4]) + " of its slots failed: exit photons with a zero first weight cannot be relayed");
-	unsigned long long h_cnt[8] = {0};
-	if (n_in > 0) {
-		pc_batch bt;
-		st = pc_batch_layout(b, n_in, false, bt);
-		if (st) return st;
-		hipLaunchKernelGGL(pc_emit_inject_kernel, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
-		                   (const unsigned long long *)b->d_relay_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)b->d_relay_map);
-		PC_HIP_CHECK(hipGetLastError());
-		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
-		st = pc_batch_trace(b, bt, 0);
-		if (st) return st;
-		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
-		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
-		if (st) return st;
-		st = b->img.keep_records(n_out, (w + ": could not allocate the image records").c_str());
-		if (st) return st;
-		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
-		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
-		unsigned long long *sumw = PC_TOTALS_SUMW(b->d_totals.p);
-		unsigned long long *sumw2 = b->opts.weight_squares ? PC_TOTALS_SUMW2(b->d_totals.p, ne) : nullptr;
-		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
-		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
-		long long grid = (n_in + 255)/256;
-		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
-		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
-		hipLaunchKernelGGL(pc_emit_finish_kernel, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
-		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
-		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
-		PC_HIP_CHECK(hipGetLastError());
-		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-		float ms = 0.f;
-		PC_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-		b->last_ms = ms;
-	} else {
-		/* nothing to trace (pc_batch_trace clears the totals otherwise) */
-		PC_HIP_CHECK(hipMemsetAsync(b->d_totals, 0, b->totals_bytes, b->stream));
-		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-	}
-	for (int k = 0; k < 6; k++) b->relay_counters[k] = (int64_t)h_cnt[k];
-	b->relay_counters[6] = skipped;
-	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
-	/* pc_hip_pose_counts goes on telling what it tells: missed = a photon that reached no entrance plane, for either reason */
-	b->relay_lost[0] = lost[0] + lost[1]; b->relay_lost[1] = lost[2];
-	for (int k = 0; k < 3; k++) b->emit_lost[k] = lost[k];
-	b->relay_emit = 1;
-	b->run_slots = n_out;
-	b->img.valid = 1;
-	b->last_call = PC_CALL_RELAY;
 	return PC_HIP_OK;
 }
 
@@ -468,18 +229,37 @@ int pc_hip_emit_frame(const pc_hip_emit *spec, double frame[16])
 
 int pc_hip_emit_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_emit *spec, pc_hip_select *select)
 {
-	int st = pc_relay_check_pair(a, b, "pc_hip_emit_run");
-	if (!st) st = pc_emit_check_spec(spec, "pc_hip_emit_run");
+	const char *who = "pc_hip_emit_run";
+	const std::string w(who);
+	int st = pc_relay_check_pair(a, b, w);
+	if (!st) st = pc_emit_check_spec(spec, w);
 	if (st) return st;
-	return pc_emit_run(a, b, spec, select);
+	std::vector<int> emap;
+	pc_spot_src s;
+	int64_t cnt_a[6];
+	st = pc_relay_open(a, b, who, select, spec->map == nullptr, [&] { return pc_emit_check_pair(a, b, spec, w, emap); }, s, cnt_a);
+	if (st) return st;
+	pc_emit_place pl;
+	pc_emit_spec_frame(spec, pl.fr);
+	pl.R = spec->target_half;
+	pl.seed = spec->seed;
+	pl.slot0 = a->run_slot0;
+	pl.ids = a->img.device_view().ids;
+	/* the last refusal: the second context still holds what it held (a map of an earlier emit relay served that relay's kernels only) */
+	st = b->relay.d_emap.grow(emap.size(), (w + ": could not allocate the energy map").c_str());
+	if (st) return st;
+	PC_HIP_CHECK(hipMemcpy(b->relay.d_emap, emap.data(), emap.size()*sizeof(int), hipMemcpyHostToDevice));
+	pl.emap = b->relay.d_emap;
+	return pc_relay_drive<pc_rule_emit>(b, who, s, cnt_a, pl);
 }
 
 int pc_hip_emit_counts(pc_hip_ctx *ctx, int64_t counts[3])
 {
 	if (!ctx || !counts) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_emit_counts: ctx and counts must not be NULL");
-	if (ctx->last_call != PC_CALL_RELAY || !ctx->relay_emit)
+	if (ctx->last_call != PC_CALL_RELAY || ctx->relay.kind != PC_RELAY_KIND_EMIT)
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_emit_counts: the context's last call was not an emit relay into it");
-	for (int k = 0; k < 3; k++) counts[k] = ctx->emit_lost[k];
+	const int64_t *lost = ctx->relay.lost;
+	counts[0] = lost[PC_RELAY_MISS - PC_RELAY_REJECT]; counts[1] = lost[PC_RELAY_MISS_DETECTOR - PC_RELAY_REJECT]; counts[2] = lost[0];
 	return PC_HIP_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -1077,6 +1078,18 @@ struct pc_event_handle {
 /* what a context was last asked to do (pc_hip_ctx::last_call) */
 enum { PC_CALL_NONE = 0, PC_CALL_RUN, PC_CALL_RUN_LEAK, PC_CALL_EXPLICIT, PC_CALL_SCAN, PC_CALL_RELAY };
 
+/* what the context a relay was traced into keeps of it, and the scratch of relays into it (pc_relay.h, pc_emit.h) */
+struct pc_relay_state {
+	pc_dev_buf<long long> d_map;           /* position in the first optic's store of every injected photon */
+	pc_dev_buf<unsigned long long> d_scan; /* the scratch of the two compactions, then the finish kernel's counters (PC_RELAY_SCAN_WORDS) */
+	pc_dev_buf<int> d_emap;                /* emit relays: which of the first optic's energies every energy of this context takes its weight from */
+	int acc_lds = 1;                       /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
+	int64_t counters[8] = {0};
+	int64_t lost[3] = {0, 0, 0};           /* photons lost between the optics, at [outcome - PC_RELAY_REJECT]: rejected by the selection, missed
+	                                        * the entrance plane (emit: the sample), missed the detector (emit only) */
+	int kind = 0;                          /* PC_RELAY_KIND_*: what the relay it holds was */
+};
+
 struct pc_hip_ctx {
 	pc_stream_handle stream;               /* first: destroyed after everything that may still be queued on it.  The context's one stream: a launch
 	                                        * that goes elsewhere says so in its pc_launch_site */
@@ -1134,16 +1147,8 @@ struct pc_hip_ctx {
 	 * traced into keeps the relay's counters beside what a source run leaves */
 	int last_call = PC_CALL_NONE;
 	std::vector<double> energies;          /* the problem's energy grid as given: two contexts relay only over bit-equal grids */
-	pc_dev_buf<long long> d_relay_map;     /* position in the first optic's store of every injected photon */
-	pc_dev_buf<unsigned long long> d_relay_scan; /* per-wave counts and offsets of the two compactions, then the relay's device counters */
-	int relay_acc_lds = 1;                 /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
-	int64_t relay_counters[8] = {0};
-	int64_t relay_lost[2] = {0, 0};        /* of a posed relay: photons that missed the entrance plane, photons its selection rejected */
-	/* emit relays (pc_emit.h) */
-	long long run_slot0 = 0;               /* first slot of the last source run: an emission draws on the stream of its photon's slot */
-	pc_dev_buf<int> d_emit_map;            /* which of the first optic's energies every energy of this context takes its weight from */
-	int relay_emit = 0;                    /* the relay this context holds is an emit relay */
-	int64_t emit_lost[3] = {0, 0, 0};      /* of an emit relay: missed the sample, missed the detector, rejected */
+	pc_relay_state relay;
+	long long run_slot0 = 0;               /* first slot of the last source run: an emission draws on the stream of its photon's slot (pc_emit.h) */
 	/* gathers of a selection's entries (pc_gather.h) */
 	int gather_tile = 0;                   /* option "gather_tile": entries per compaction tile, 0 = automatic */
 	long long gather_chunk_rows = 0;       /* option "gather_chunk_rows": rows per staging chunk, 0 = as many as fit in 128 MiB */
@@ -1438,7 +1443,7 @@ int pc_hip_set_option(pc_hip_ctx *ctx, const char *name, int64_t value)
 	else if (n == "keep_pinned") ctx->img.opts.keep_pinned = value ? 1 : 0;
 	else if (n == "block_shift") { if (value < 7 || value > 30) return pc_fail(PC_HIP_ERR_INVALID, "block_shift must be in [7,30]"); ctx->img.opts.blk_shift = (int)value; }
 	else if (n == "run_parts") { if (value < 1 || value > PC_MAX_PARTS) return pc_fail(PC_HIP_ERR_INVALID, "run_parts must be in [1,16]"); ctx->img.opts.run_parts = (int)value; }
-	else if (n == "relay_acc_lds") ctx->relay_acc_lds = value ? 1 : 0;
+	else if (n == "relay_acc_lds") ctx->relay.acc_lds = value ? 1 : 0;
 	else if (n == "gather_tile") { if (value < 0 || value > 65536 || (value != 0 && (value < 64 || value % 64 != 0))) return pc_fail(PC_HIP_ERR_INVALID, "gather_tile must be a multiple of 64 in [64,65536] (0 = automatic)"); ctx->gather_tile = (int)value; }
 	else if (n == "gather_chunk_rows") { if (value < 0 || value > 0x7fffffff) return pc_fail(PC_HIP_ERR_INVALID, "gather_chunk_rows must be in [0,2^31-1] (0 = automatic)"); ctx->gather_chunk_rows = (long long)value; }
 	else if (n == "fetch_threads") { if (value < 0 || value > 256) return pc_fail(PC_HIP_ERR_INVALID, "fetch_threads must be in [0,256]"); ctx->img.opts.fetch_threads = (int)value; }

@@ -142,56 +142,93 @@ static __device__ __forceinline__ int pc_relay_src_valid(const pc_spot_src &s, l
 	return pc_relay_entry_valid(s.p[i*s.ss + (long long)PC_F_EXITZ*s.fs], s.w[i*s.ws]);
 }
 
-/* the injected state of entry i, which is an exit photon: o = pc_relay_fly's ten numbers, or pc_relay_fly_posed's (POSED), whose
- * verdict is returned (0: the photon misses the second optic's entrance plane) */
-template <bool POSED>
-static __device__ __forceinline__ int pc_relay_src_fly(const pc_spot_src &s, const pc_relay_place &pl, long long i, double *o)
-{
-	const double *e = s.p + i*s.ss;
-	const double x = e[(long long)PC_F_EXITX*s.fs], y = e[(long long)PC_F_EXITY*s.fs], dx = e[(long long)PC_F_EDIRX*s.fs], dy = e[(long long)PC_F_EDIRY*s.fs];
-	const double ex = e[(long long)PC_F_EEVX*s.fs], ey = e[(long long)PC_F_EEVY*s.fs];
-	if (POSED) return pc_relay_fly_posed(x, y, dx, dy, ex, ey, pl.gap, pl.off_x, pl.off_y, pl.basis, o);
-	pc_relay_fly(x, y, dx, dy, ex, ey, pl.gap, pl.off_x, pl.off_y, o);
-	return 1;
-}
+/* What becomes of entry i of the first store.  PC_RELAY_SKIP: no exit photon (a failed slot); PC_RELAY_INJECT: it starts into the
+ * second optic; the rest are the ways to be lost between the optics, counted at lost[code - PC_RELAY_REJECT]: the selection's mask
+ * byte (s.mask, NULL = none) is clear; it misses the entrance plane (of an emit relay: the sample); emit relays only: it misses the
+ * detector. */
+enum { PC_RELAY_SKIP = 0, PC_RELAY_INJECT = 1, PC_RELAY_REJECT = 2, PC_RELAY_MISS = 3, PC_RELAY_MISS_DETECTOR = 4, PC_RELAY_N_LOST = 3 };
+/* what a context holds of a relay (pc_relay_state::kind) */
+enum { PC_RELAY_KIND_NONE = 0, PC_RELAY_KIND_RELAY, PC_RELAY_KIND_EMIT };
 
-/* What becomes of entry i of the first store -- the one predicate of the count and the inject kernels, which recompute it from the
- * entry: the same operations give the same bits.  PC_RELAY_SKIP: no exit photon (a failed slot); PC_RELAY_INJECT: o = its state at
- * the second optic; posed relays only: PC_RELAY_REJECT: the selection's mask byte (s.mask, NULL = none) is clear; PC_RELAY_MISS: it
- * misses the entrance plane. */
-enum { PC_RELAY_SKIP = 0, PC_RELAY_INJECT = 1, PC_RELAY_REJECT = 2, PC_RELAY_MISS = 3 };
-template <bool POSED>
-static __device__ __forceinline__ int pc_relay_entry(const pc_spot_src &s, const pc_relay_place &pl, long long i, double *o)
-{
-	if (!pc_relay_src_valid(s, i)) return PC_RELAY_SKIP;
-	if (POSED && s.mask && !s.mask[i]) return PC_RELAY_REJECT;
-	return pc_relay_src_fly<POSED>(s, pl, i, o) ? PC_RELAY_INJECT : PC_RELAY_MISS;
-}
+/* An injection rule: how an exit photon of the first store becomes a photon of the second optic.  The kernels below are written
+ * once over a rule, a struct of
+ *   place      what the rule needs to know of the geometry, passed to the kernels by value
+ *   N_STATE    the numbers of an injected state: {x, y, z, dx, dy, dz, ex, ey, ez} at the second optic, then what the weight and
+ *              the path need
+ *   KIND       what the second context then holds
+ *   entry()    the outcome code of entry i, and its state when it is PC_RELAY_INJECT: the one predicate of the count and the inject
+ *              kernels, which recompute it from the entry -- the same operations give the same bits
+ *   state()    the state of an entry known to be injected (the finish kernel)
+ *   weight()   the weight behind both optics at energy en of the second one
+ *   dtravel()  the path behind both optics
+ * The plain rule flies every exit photon with pc_relay_fly; the posed rule asks the selection, then pc_relay_fly_posed; the emit
+ * rule is pc_emit.h's. */
+struct pc_rule_plain {
+	typedef pc_relay_place place;
+	enum { N_STATE = 10, KIND = PC_RELAY_KIND_RELAY };
+	static __device__ __forceinline__ void state(const pc_spot_src &s, const place &pl, long long ia, double *o)
+	{
+		const double *e = s.p + ia*s.ss;
+		pc_relay_fly(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
+		             e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, o);
+	}
+	static __device__ __forceinline__ int entry(const pc_spot_src &s, const place &pl, long long i, double *o)
+	{
+		if (!pc_relay_src_valid(s, i)) return PC_RELAY_SKIP;
+		state(s, pl, i, o);
+		return PC_RELAY_INJECT;
+	}
+	static __device__ __forceinline__ double weight(const pc_spot_src &s, const place &, long long ia, int en, const double *, double w_b)
+	{
+		return pc_relay_weight(s.w[ia*s.ws + en], w_b);
+	}
+	static __device__ __forceinline__ double dtravel(double d_a, const double *o, double d_b) { return pc_relay_dtravel(d_a, o[9], d_b); }
+};
 
-/* Stable compaction, step 1: how many of the 64 items of every wave are kept.  rc == NULL: item i is entry i of the first store,
- * kept when it is an exit photon; else item i is photon i of the second stage, kept when it was transmitted (rc 1).
- * One thread per item; counts[i / 64] for every wave that holds an item. */
-__global__ void __launch_bounds__(256) pc_relay_count_kernel(pc_spot_src s, const int *rc, long long n, unsigned long long *counts)
+struct pc_rule_posed : pc_rule_plain {      /* the plain rule's weight and path */
+	static __device__ __forceinline__ int fly(const pc_spot_src &s, const place &pl, long long i, double *o)
+	{
+		const double *e = s.p + i*s.ss;
+		return pc_relay_fly_posed(e[(long long)PC_F_EXITX*s.fs], e[(long long)PC_F_EXITY*s.fs], e[(long long)PC_F_EDIRX*s.fs], e[(long long)PC_F_EDIRY*s.fs],
+		                          e[(long long)PC_F_EEVX*s.fs], e[(long long)PC_F_EEVY*s.fs], pl.gap, pl.off_x, pl.off_y, pl.basis, o);
+	}
+	static __device__ __forceinline__ void state(const pc_spot_src &s, const place &pl, long long ia, double *o) { (void)fly(s, pl, ia, o); }
+	static __device__ __forceinline__ int entry(const pc_spot_src &s, const place &pl, long long i, double *o)
+	{
+		if (!pc_relay_src_valid(s, i)) return PC_RELAY_SKIP;
+		if (s.mask && !s.mask[i]) return PC_RELAY_REJECT;
+		return fly(s, pl, i, o) ? PC_RELAY_INJECT : PC_RELAY_MISS;
+	}
+};
+
+/* Stable compaction, step 1: how many of the 64 items of every wave are kept.  Item i is photon i of the second stage, kept when
+ * it was transmitted (rc 1).  One thread per item; counts[i / 64] for every wave that holds an item. */
+__global__ void __launch_bounds__(256) pc_relay_count_kernel(const int *rc, long long n, unsigned long long *counts)
 {
 	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	const int keep = (i < n) ? (rc ? (rc[i] == 1) : pc_relay_src_valid(s, i)) : 0;
+	const int keep = (i < n) ? (rc[i] == 1) : 0;
 	const unsigned long long m = __ballot(keep);
 	if ((threadIdx.x & 63) == 0 && i < n) counts[i >> 6] = (unsigned long long)__popcll(m);
 }
 
-/* Step 1 of a posed relay over the first store: an entry is kept when pc_relay_entry injects it; lost[0] += the photons that miss
- * the entrance plane, lost[1] += those the selection rejects, one atomic per wave that has any. */
-__global__ void __launch_bounds__(256) pc_relay_count_posed_kernel(pc_spot_src s, pc_relay_place pl, long long n, unsigned long long *counts,
+/* Step 1 over the first store under a rule: an entry is kept when the rule injects it; lost[code - PC_RELAY_REJECT] += the entries
+ * of every other outcome but a skip, one atomic per wave that has any. */
+template <class RULE>
+__global__ void __launch_bounds__(256) pc_relay_count_rule_kernel(pc_spot_src s, typename RULE::place pl, long long n, unsigned long long *counts,
 	unsigned long long *lost)
 {
 	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	double o[10];
-	const int what = (i < n) ? pc_relay_entry<true>(s, pl, i, o) : PC_RELAY_SKIP;
-	const unsigned long long m = __ballot(what == PC_RELAY_INJECT), mm = __ballot(what == PC_RELAY_MISS), mr = __ballot(what == PC_RELAY_REJECT);
+	double o[RULE::N_STATE];
+	const int what = (i < n) ? RULE::entry(s, pl, i, o) : PC_RELAY_SKIP;
+	const unsigned long long m = __ballot(what == PC_RELAY_INJECT);
+	unsigned long long ml[PC_RELAY_N_LOST];
+#pragma unroll
+	for (int k = 0; k < PC_RELAY_N_LOST; k++) ml[k] = __ballot(what == PC_RELAY_REJECT + k);
 	if ((threadIdx.x & 63) == 0 && i < n) {
 		counts[i >> 6] = (unsigned long long)__popcll(m);
-		if (mm) atomicAdd(&lost[0], (unsigned long long)__popcll(mm));
-		if (mr) atomicAdd(&lost[1], (unsigned long long)__popcll(mr));
+#pragma unroll
+		for (int k = 0; k < PC_RELAY_N_LOST; k++)
+			if (ml[k]) atomicAdd(&lost[k], (unsigned long long)__popcll(ml[k]));
 	}
 }
 
@@ -225,16 +262,16 @@ __global__ void __launch_bounds__(1024) pc_relay_scan_kernel(unsigned long long 
 	if (tid == 0) counts[nw] = carry;
 }
 
-/* Inject: every entry of the first store that pc_relay_entry injects becomes one explicit photon of the second context, at the
+/* Inject: every entry of the first store that the rule injects becomes one explicit photon of the second context, at the
  * position the prefix sums give it (the order of the store); map[position] = its entry.  Reads are coalesced when the store is
  * planes and strided by the record when it is records. */
-template <bool POSED>
-__global__ void __launch_bounds__(256) pc_relay_inject_kernel(pc_spot_src s, pc_relay_place pl, const unsigned long long *offs, long long n,
+template <class RULE>
+__global__ void __launch_bounds__(256) pc_relay_inject_kernel(pc_spot_src s, typename RULE::place pl, const unsigned long long *offs, long long n,
 	double *in_start, double *in_dir, double *in_elecv, long long *map)
 {
 	const long long i = (long long)blockIdx.x*blockDim.x + threadIdx.x;
-	double o[10];
-	const int keep = (i < n) ? (pc_relay_entry<POSED>(s, pl, i, o) == PC_RELAY_INJECT) : 0;
+	double o[RULE::N_STATE];
+	const int keep = (i < n) ? (RULE::entry(s, pl, i, o) == PC_RELAY_INJECT) : 0;
 	const unsigned long long m = __ballot(keep);
 	if (!keep) return;
 	const int lane = threadIdx.x & 63;
@@ -251,12 +288,12 @@ struct pc_relay_stage2 {          /* what the explicit-photon trace left in the 
 	const long long *irefl;
 };
 
-/* Finish: counters of the second stage's outcomes; for every transmitted photon the product weights, their exact sums (and the
+/* Finish: counters of the second stage's outcomes; for every transmitted photon the rule's weights, their exact sums (and the
  * squares' when sumw2 is given) and its image record at the position the prefix sums give it.  A wave takes 64 consecutive
  * photons at a time; the sums of a workgroup are gathered in LDS (acc_lds) when they fit, else go to the global pairs at once.
  * Integer sums only: the totals depend on the set of photons, not on the launch shape. */
-template <bool POSED>
-__global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_relay_place pl, pc_relay_stage2 b, const long long *map,
+template <class RULE>
+__global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, typename RULE::place pl, pc_relay_stage2 b, const long long *map,
 	const unsigned long long *offs, long long n_in, int ne, int acc_lds, double *rec_out, pc_totals *totals, unsigned long long *sumw,
 	unsigned long long *sumw2, unsigned long long *relay_cnt)
 {
@@ -285,14 +322,14 @@ __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_
 		if (!m) continue;
 		long long ia = 0;
 		double *r = nullptr;
+		double o[RULE::N_STATE];
 		unsigned long long f_irefl = 0ull;
 		if (ok) {
 			ia = map[i];
 			const double *e = s.p + ia*s.ss;
-			/* the injected state again, from A's entry: the same operations give the same bits as the inject kernel wrote, and the
-			 * flight t, which the batch buffer does not hold, comes with them */
-			double o[10];
-			(void)pc_relay_src_fly<POSED>(s, pl, ia, o);
+			/* the injected state again, from A's entry: the same operations give the same bits as the inject kernel wrote, and what
+			 * the batch buffer does not hold of it (the flight; of an emission its solid angle too) comes with them */
+			RULE::state(s, pl, ia, o);
 			const long long pos = (long long)offs[i >> 6] + __popcll(m & ((1ull << lane) - 1ull));
 			r = rec_out + pos*recd;
 			const long long n_a = ((const long long *)e)[(long long)PC_F_NREFL*s.fs], n_b = b.irefl[i];
@@ -305,14 +342,14 @@ __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_
 			/* a photon that met no wall keeps the electric vector it was given (as pc_hip_launch_photons reports it) */
 			r[PC_F_EEVX] = n_b ? b.exit_elecv[3*i] : o[6]; r[PC_F_EEVY] = n_b ? b.exit_elecv[3*i + 1] : o[7];
 			((long long *)r)[PC_F_NREFL] = n_a + n_b;
-			r[PC_F_DTRAVEL] = pc_relay_dtravel(e[(long long)PC_F_DTRAVEL*s.fs], o[9], b.dtravel[i]);
+			r[PC_F_DTRAVEL] = RULE::dtravel(e[(long long)PC_F_DTRAVEL*s.fs], o, b.dtravel[i]);
 			f_irefl = (unsigned long long)(n_a + n_b);
 		}
 		c_irefl += pc_wave_sum_u64(f_irefl);
 		for (int en = 0; en < ne; en++) {
 			double w = 0.;
 			if (ok) {
-				w = pc_relay_weight(s.w[ia*s.ws + en], b.w[i*ne + en]);
+				w = RULE::weight(s, pl, ia, en, o, b.w[i*ne + en]);
 				r[PC_F_WEIGHTS + en] = w;
 			}
 			unsigned long long lo = 0ull, hi = 0ull;
@@ -345,38 +382,34 @@ __global__ void __launch_bounds__(256) pc_relay_finish_kernel(pc_spot_src s, pc_
 	}
 }
 
-/* counts + prefix sums of n items on the context's stream (pc_relay_count_kernel, pc_relay_scan_kernel); *total = how many are
- * kept (waits for the stream) */
-static int pc_relay_compact_offsets(pc_hip_ctx *b, const pc_spot_src &s, const int *rc, long long n, long long *total)
-{
-	const long long nw = (n + 63)/64;
-	hipLaunchKernelGGL(pc_relay_count_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, b->stream, s, rc, n, (unsigned long long *)b->d_relay_scan);
-	PC_HIP_CHECK(hipGetLastError());
-	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, (unsigned long long *)b->d_relay_scan, nw);
-	PC_HIP_CHECK(hipGetLastError());
-	unsigned long long t = 0;
-	PC_HIP_CHECK(hipMemcpyAsync(&t, b->d_relay_scan + nw, sizeof(t), hipMemcpyDeviceToHost, b->stream));
-	PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-	*total = (long long)t;
-	return PC_HIP_OK;
-}
+/* The scratch of a compaction of n items in pc_relay_state::d_scan: the per-wave counts [(n + 63)/64], which become their offsets,
+ * the total, the loss counters.  The finish kernel's counters follow the second compaction's. */
+#define PC_RELAY_SCAN_WORDS(n) ((size_t)(((n) + 63)/64) + 1 + PC_RELAY_N_LOST)
 
-/* the counts and prefix sums of a posed relay over the first store (pc_relay_count_posed_kernel); lost = {missed, rejected} */
-static int pc_relay_posed_offsets(pc_hip_ctx *b, const pc_spot_src &s, const pc_relay_place &pl, long long n, unsigned long long *d_lost,
-	long long *total, long long lost[2])
+/* counts + prefix sums of n items on the context's stream.  rc == NULL: the entries of the first store under the rule, lost = how
+ * many were lost in each way; else the photons of the second stage that were transmitted.  *total = how many are kept (waits for
+ * the stream) */
+template <class RULE>
+static int pc_relay_offsets(pc_hip_ctx *b, const pc_spot_src &s, const typename RULE::place &pl, const int *rc, long long n, long long *total,
+	long long *lost)
 {
 	const long long nw = (n + 63)/64;
-	PC_HIP_CHECK(hipMemsetAsync(d_lost, 0, 2*sizeof(unsigned long long), b->stream));
-	hipLaunchKernelGGL(pc_relay_count_posed_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, b->stream, s, pl, n, (unsigned long long *)b->d_relay_scan, d_lost);
+	unsigned long long *d = b->relay.d_scan;
+	const dim3 grid((unsigned)((n + 255)/256));
+	if (rc) {
+		hipLaunchKernelGGL(pc_relay_count_kernel, grid, dim3(256), 0, b->stream, rc, n, d);
+	} else {
+		PC_HIP_CHECK(hipMemsetAsync(d + nw + 1, 0, PC_RELAY_N_LOST*sizeof(unsigned long long), b->stream));
+		hipLaunchKernelGGL(pc_relay_count_rule_kernel<RULE>, grid, dim3(256), 0, b->stream, s, pl, n, d, d + nw + 1);
+	}
 	PC_HIP_CHECK(hipGetLastError());
-	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, (unsigned long long *)b->d_relay_scan, nw);
+	hipLaunchKernelGGL(pc_relay_scan_kernel, dim3(1), dim3(1024), 0, b->stream, d, nw);
 	PC_HIP_CHECK(hipGetLastError());
-	unsigned long long t = 0, l[2] = {0, 0};
-	PC_HIP_CHECK(hipMemcpyAsync(&t, b->d_relay_scan + nw, sizeof(t), hipMemcpyDeviceToHost, b->stream));
-	PC_HIP_CHECK(hipMemcpyAsync(l, d_lost, sizeof(l), hipMemcpyDeviceToHost, b->stream));
+	unsigned long long t[1 + PC_RELAY_N_LOST] = {0};
+	PC_HIP_CHECK(hipMemcpyAsync(t, d + nw, (rc ? 1 : 1 + PC_RELAY_N_LOST)*sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
 	PC_HIP_CHECK(hipStreamSynchronize(b->stream));
-	*total = (long long)t;
-	lost[0] = (long long)l[0]; lost[1] = (long long)l[1];
+	*total = (long long)t[0];
+	for (int k = 0; !rc && k < PC_RELAY_N_LOST; k++) lost[k] = (long long)t[1 + k];
 	return PC_HIP_OK;
 }
 
@@ -422,23 +455,23 @@ static int pc_relay_check_select(const pc_hip_ctx *a, const pc_hip_select *sel, 
 	return PC_HIP_OK;
 }
 
-/* A relay behind its placement check.  basis == NULL: a plain relay (pc_relay_fly, every exit photon); else a posed one
- * (pc_relay_fly_posed; sel, optional, stands between the optics). */
-static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double gap, double off_x, double off_y, const double *basis, pc_hip_select *sel)
+/* The opening of every relay: all that can refuse it, while the second context still holds what it held.  more (optional): what the
+ * kind of relay checks of the pair before anything waits.  s = the entries the relay reads, under the selection's mask if there is
+ * one; cnt_a = the first run's counters. */
+static int pc_relay_open(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, pc_hip_select *sel, bool same_grid, const std::function<int()> &more,
+	pc_spot_src &s, int64_t cnt_a[6])
 {
 	const std::string w(who);
-	const bool posed = basis != nullptr;
-	int st = pc_relay_check(a, b, w);
+	int st = pc_relay_check(a, b, w, same_grid);
+	if (!st && more) st = more();
 	if (st) return st;
 	PC_HIP_CHECK(hipSetDevice(a->device));
 	/* the first run is complete (and the apply of the selection behind it), and nothing of the second context is in flight */
 	st = pc_hip_transmission_wait(a, nullptr);
 	if (!st) st = pc_hip_transmission_wait(b, nullptr);
 	if (st) return st;
-	int64_t cnt_a[6];
 	st = pc_hip_transmission_totals(a, nullptr, cnt_a, nullptr);
-	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted below */
-	pc_spot_src s;
+	if (st && st != PC_HIP_ERR_ATTEMPTS) return st;         /* failed slots of the first run are skipped and counted by the pipeline */
 	st = pc_spot_source(a, 0, s, who);
 	if (st) return st;
 	if (sel) {
@@ -446,10 +479,17 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 		if (st) return st;
 		s.mask = sel->m[0].d_mask[0];
 	}
+	return PC_HIP_OK;
+}
+
+/* The pipeline of every relay behind its opening: the entries s of the first store into the second context b under RULE at pl. */
+template <class RULE>
+static int pc_relay_drive(pc_hip_ctx *b, const char *who, const pc_spot_src &s, const int64_t cnt_a[6], const typename RULE::place &pl)
+{
+	const std::string w(who);
+	pc_relay_state &rs = b->relay;
 	const long long n_a = s.n;
 	const int ne = b->host.pm.n_energies;
-	pc_relay_place pl = { gap, off_x, off_y, { 1., 0., 0., 0., 1., 0., 0., 0., 1. } };
-	if (posed) memcpy(pl.basis, basis, sizeof(pl.basis));
 
 	/* from here on the second context holds the relay, or nothing */
 	b->img.reset(); b->leak.events_of_run = 0; b->last_run_plain = 0;
@@ -458,16 +498,15 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 	b->run_pending = 0; b->run_slots = 0;
 	b->run_squares = b->opts.weight_squares;
 	b->last_ms = 0.f;
-	const size_t nw_a = (size_t)((n_a + 63)/64);
-	/* counts and offsets [nw_a + 1], the finish kernel's counters [8] behind the second compaction's, the posed count's two last */
-	st = b->d_relay_scan.grow(nw_a + 1 + 8 + 2, (w + ": could not allocate the compaction counters").c_str());
-	if (!st) st = b->d_relay_map.grow((size_t)n_a, (w + ": could not allocate the photon map").c_str());
+	/* the first compaction's scratch holds the second one's, which is over fewer items, and the finish kernel's counters [8] behind it */
+	int st = rs.d_scan.grow(PC_RELAY_SCAN_WORDS(n_a) + 8, (w + ": could not allocate the compaction counters").c_str());
+	if (!st) st = rs.d_map.grow((size_t)n_a, (w + ": could not allocate the photon map").c_str());
 	if (st) return st;
 
-	long long n_in = 0, n_out = 0, lost[2] = {0, 0};
-	st = posed ? pc_relay_posed_offsets(b, s, pl, n_a, b->d_relay_scan + nw_a + 1 + 8, &n_in, lost) : pc_relay_compact_offsets(b, s, nullptr, n_a, &n_in);
+	long long n_in = 0, n_out = 0, lost[PC_RELAY_N_LOST] = {0, 0, 0};
+	st = pc_relay_offsets<RULE>(b, s, pl, nullptr, n_a, &n_in, lost);
 	if (st) return st;
-	const long long skipped = n_a - n_in - lost[0] - lost[1];
+	const long long skipped = n_a - n_in - lost[0] - lost[1] - lost[2];
 	/* The predicate reads the first weight only.  Every entry it skips must be a failed slot of A's run: a grid whose first
 	 * energy has no valid constants, or a first weight that underflowed to 0, would otherwise vanish without a word */
 	if (skipped != cnt_a[4])
@@ -478,28 +517,28 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 		pc_batch bt;
 		st = pc_batch_layout(b, n_in, false, bt);
 		if (st) return st;
-		hipLaunchKernelGGL(posed ? pc_relay_inject_kernel<true> : pc_relay_inject_kernel<false>, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
-		                   (const unsigned long long *)b->d_relay_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)b->d_relay_map);
+		hipLaunchKernelGGL(pc_relay_inject_kernel<RULE>, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
+		                   (const unsigned long long *)rs.d_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)rs.d_map);
 		PC_HIP_CHECK(hipGetLastError());
 		/* stage 2: the explicit-photon trace kernel over the injected photons (many energies: the immediate sweep) */
 		st = pc_batch_trace(b, bt, 0);
 		if (st) return st;
 		b->run_squares = b->opts.weight_squares;      /* the finish kernel keeps the sums an explicit launch does not */
-		st = pc_relay_compact_offsets(b, s, bt.d_rc, n_in, &n_out);
+		st = pc_relay_offsets<RULE>(b, s, pl, bt.d_rc, n_in, &n_out, nullptr);
 		if (st) return st;
 		st = b->img.keep_records(n_out, (w + ": could not allocate the image records").c_str());
 		if (st) return st;
-		unsigned long long *d_cnt = b->d_relay_scan + (size_t)((n_in + 63)/64) + 1;
+		unsigned long long *d_cnt = rs.d_scan + PC_RELAY_SCAN_WORDS(n_in);
 		PC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8*sizeof(unsigned long long), b->stream));
 		unsigned long long *sumw = PC_TOTALS_SUMW(b->d_totals.p);
 		unsigned long long *sumw2 = b->opts.weight_squares ? PC_TOTALS_SUMW2(b->d_totals.p, ne) : nullptr;
 		const size_t lds = (size_t)(sumw2 ? 4 : 2)*(size_t)ne*sizeof(unsigned long long);
-		const int acc_lds = (b->relay_acc_lds && lds <= 32768) ? 1 : 0;
+		const int acc_lds = (rs.acc_lds && lds <= 32768) ? 1 : 0;
 		long long grid = (n_in + 255)/256;
 		if (grid > 8ll*pc_plan_cus(b->opts, b->n_cu)) grid = 8ll*pc_plan_cus(b->opts, b->n_cu);
 		const pc_relay_stage2 s2 = { bt.d_rc, bt.d_w, bt.d_ec, bt.d_ed, bt.d_ee, bt.d_dt, bt.d_ir };
-		hipLaunchKernelGGL(posed ? pc_relay_finish_kernel<true> : pc_relay_finish_kernel<false>, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
-		                   (const long long *)b->d_relay_map, (const unsigned long long *)b->d_relay_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
+		hipLaunchKernelGGL(pc_relay_finish_kernel<RULE>, dim3((unsigned)grid), dim3(256), acc_lds ? lds : 0, b->stream, s, pl, s2,
+		                   (const long long *)rs.d_map, (const unsigned long long *)rs.d_scan, n_in, ne, acc_lds, (double *)b->img.d_img,
 		                   (pc_totals *)b->d_totals, sumw, sumw2, d_cnt);
 		PC_HIP_CHECK(hipGetLastError());
 		PC_HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, b->stream));
@@ -512,15 +551,28 @@ static int pc_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double ga
 		PC_HIP_CHECK(hipMemsetAsync(b->d_totals, 0, b->totals_bytes, b->stream));
 		PC_HIP_CHECK(hipStreamSynchronize(b->stream));
 	}
-	for (int k = 0; k < 6; k++) b->relay_counters[k] = (int64_t)h_cnt[k];
-	b->relay_counters[6] = skipped;
-	b->relay_counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
-	b->relay_lost[0] = lost[0]; b->relay_lost[1] = lost[1];
-	b->relay_emit = 0;
+	for (int k = 0; k < 6; k++) rs.counters[k] = (int64_t)h_cnt[k];
+	rs.counters[6] = skipped;
+	rs.counters[7] = cnt_a[0] + cnt_a[1] + cnt_a[2];
+	for (int k = 0; k < PC_RELAY_N_LOST; k++) rs.lost[k] = lost[k];
+	rs.kind = RULE::KIND;
 	b->run_slots = n_out;
 	b->img.valid = 1;
 	b->last_call = PC_CALL_RELAY;
 	return PC_HIP_OK;
+}
+
+/* a relay behind the check of its placement: posed (basis, and sel, optional, between the optics) or plain (basis == NULL) */
+static int pc_relay_at(pc_hip_ctx *a, pc_hip_ctx *b, const char *who, double gap, double off_x, double off_y, const double *basis, pc_hip_select *sel)
+{
+	pc_spot_src s;
+	int64_t cnt_a[6];
+	const int st = pc_relay_open(a, b, who, sel, true, nullptr, s, cnt_a);
+	if (st) return st;
+	pc_relay_place pl = { gap, off_x, off_y, { 1., 0., 0., 0., 1., 0., 0., 0., 1. } };
+	if (!basis) return pc_relay_drive<pc_rule_plain>(b, who, s, cnt_a, pl);
+	memcpy(pl.basis, basis, sizeof(pl.basis));
+	return pc_relay_drive<pc_rule_posed>(b, who, s, cnt_a, pl);
 }
 
 extern "C" {
@@ -538,7 +590,7 @@ int pc_hip_relay_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_relay_placement 
 	int st = pc_relay_check_pair(a, b, "pc_hip_relay_run");
 	if (!st) st = pc_hip_relay_validate(placement);
 	if (st) return st;
-	return pc_relay_run(a, b, "pc_hip_relay_run", placement->gap, placement->off_x, placement->off_y, nullptr, nullptr);
+	return pc_relay_at(a, b, "pc_hip_relay_run", placement->gap, placement->off_x, placement->off_y, nullptr, nullptr);
 }
 
 int pc_hip_pose_validate(const pc_hip_pose *pose)
@@ -564,17 +616,18 @@ int pc_hip_pose_run(pc_hip_ctx *a, pc_hip_ctx *b, const pc_hip_pose *pose, pc_hi
 	if (!st) st = pc_hip_pose_validate(pose);
 	if (st) return st;
 	if (pc_relay_pose_plain(pose->tilt_x, pose->tilt_y, select != nullptr))
-		return pc_relay_run(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, nullptr, nullptr);
+		return pc_relay_at(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, nullptr, nullptr);
 	double basis[9];
 	pc_relay_pose_basis(pose->tilt_x, pose->tilt_y, basis);
-	return pc_relay_run(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, basis, select);
+	return pc_relay_at(a, b, "pc_hip_pose_run", pose->gap, pose->off_x, pose->off_y, basis, select);
 }
 
 int pc_hip_pose_counts(pc_hip_ctx *ctx, int64_t counts[2])
 {
 	if (!ctx || !counts) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_counts: ctx and counts must not be NULL");
 	if (ctx->last_call != PC_CALL_RELAY) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_pose_counts: the context's last call was not a relay into it");
-	counts[0] = ctx->relay_lost[0]; counts[1] = ctx->relay_lost[1];
+	const int64_t *lost = ctx->relay.lost;      /* missed: a photon that reached no entrance plane, for either reason */
+	counts[0] = lost[PC_RELAY_MISS - PC_RELAY_REJECT] + lost[PC_RELAY_MISS_DETECTOR - PC_RELAY_REJECT]; counts[1] = lost[0];
 	return PC_HIP_OK;
 }
 
@@ -586,7 +639,7 @@ int pc_hip_relay_totals(pc_hip_ctx *ctx, int64_t counters[8], uint64_t *sumw_fix
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_relay_totals: the relay was made without option weight_squares");
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	if (counters) memcpy(counters, ctx->relay_counters, sizeof(ctx->relay_counters));
+	if (counters) memcpy(counters, ctx->relay.counters, sizeof(ctx->relay.counters));
 	if (sumw_fixed) PC_HIP_CHECK(hipMemcpy(sumw_fixed, PC_TOTALS_SUMW(ctx->d_totals.p), 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
 	if (sumw2_fixed) PC_HIP_CHECK(hipMemcpy(sumw2_fixed, PC_TOTALS_SUMW2(ctx->d_totals.p, ne), 2*ne*sizeof(uint64_t), hipMemcpyDeviceToHost));
 	return PC_HIP_OK;

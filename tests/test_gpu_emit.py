@@ -381,3 +381,66 @@ def test_oracle_second_stage(pa, oracle, host):
           % (eff_g, err_g, r["counters"]["exit"], eff_o, err_o, int(ok.sum()), (eff_g - eff_o) / math.hypot(err_g, err_o)))
     assert r["counters"]["exit"] > 100 and ok.sum() > 100
     assert abs(eff_g - eff_o) <= 4. * math.hypot(err_g, err_o)
+
+
+# ---- 9 ------------------------------------------------------------------------------------------------------------------------
+def test_kinds_of_relay_share_one_state(pa, oracle):
+    """Plain, posed and emit relays keep one state on the second context and share its scratch buffers.  A sequence of all three
+    kinds into one B -- with a shorter run of A in the middle, so that every offset into the scratch shrinks -- leaves after every
+    step what the same single call leaves on a B made for it: relay_totals (counters, missed, rejected, both exact sums),
+    pc_hip_emit_counts (the three counts after an emit, status -2 after anything else), totals() and records(), bit for bit.
+    The posed relay without a selection stands at gap 0: there the tilted entrance plane cuts A's exit face, and the photons on
+    its far side miss it, so that `missed` is not zero without an aperture.  (On the MI355X: the pinhole rejects 1722 of the 2000
+    and lets 278 in, of which 66 leave B; at gap 0 254 of the 500 miss and none of the other 246 leaves B; the emits inject
+    every photon, 176 of 2000 and 50 of 500 leave B.)"""
+    import ctypes as C
+    _, _, prob_a, _, prob_b, _ = problems(oracle, "pinned")
+    tilt = (0.003, 0.001)
+
+    def state(ctx_b):
+        r = ctx_b.relay_totals()
+        c = r["counters"]
+        el = np.zeros(3, dtype=np.int64)
+        st = pa.lib().pc_hip_emit_counts(ctx_b._h, el.ctypes.data_as(C.POINTER(C.c_int64)))
+        t = ctx_b.totals()
+        return ((r["counters_array"].tolist(), c["missed"], c["rejected"], as_ints(r["sumw_fixed"]), as_ints(r["sumw2_fixed"])),
+                (st, el.tolist() if st == 0 else None),
+                (t["counters"].tolist(), as_ints(t["sumw_fixed"]), t["sum_weights"].tobytes()), ctx_b.records())
+
+    with pa.TraceContext(prob_a) as ctx_a, pa.TraceContext(prob_b) as ctx_b, pa.Selection(ctx_a, [PINHOLE]) as S:
+        ctx_b.set_option("weight_squares", 1)
+
+        def step(name, call, acc_lds=1):
+            ctx_b.set_option("relay_acc_lds", acc_lds)
+            r = call(ctx_b)
+            got = state(ctx_b)
+            with pa.TraceContext(prob_b) as fresh:
+                fresh.set_option("weight_squares", 1)
+                fresh.set_option("relay_acc_lds", acc_lds)
+                call(fresh)
+                want = state(fresh)
+            print(name, r["counters"], "emit counts", got[1])
+            assert got[0] == want[0], (name, "relay_totals", got[0], want[0])
+            assert got[1] == want[1], (name, "pc_hip_emit_counts", got[1], want[1])
+            assert got[2] == want[2], (name, "totals", got[2], want[2])
+            assert same_bits(got[3], want[3]), (name, "records")
+            c = r["counters"]
+            if name.startswith("emit"):
+                assert got[1][0] == 0 and got[1][1] == [c["missed_sample"], c["missed_detector"], c["rejected"]]
+                assert c["missed_detector"] + c["missed_sample"] >= 0 and c["n_in"] > 0
+            else:
+                assert got[1] == (-2, None)
+            if name.startswith("posed"):
+                assert c["missed"] + c["rejected"] > 0
+            return r
+
+        ctx_a.run(SEED, 0, 2000, keep_images=True)
+        S.apply("exit")
+        step("emit", lambda b: emit(ctx_a, b))
+        r = step("posed, pinhole", lambda b: ctx_a.relay(b, 1.0, tilt=tilt, select=S))
+        assert r["counters"]["rejected"] > 0 and r["counters"]["n_in"] > 0
+        ctx_a.run(SEED, 0, 500, keep_images=True)
+        step("emit, 500 slots", lambda b: emit(ctx_a, b))
+        step("plain", lambda b: ctx_a.relay(b, 1.0))
+        step("posed, no selection", lambda b: ctx_a.relay(b, 0., tilt=tilt))
+        step("emit, sums to the global pairs", lambda b: emit(ctx_a, b), acc_lds=0)
