@@ -879,6 +879,58 @@ POLYCAP_EXTERN int pc_hip_emit_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const p
 /* of the last relay into ctx_b, which must have been an emit relay: counts = {missed_sample, missed_detector, rejected} */
 POLYCAP_EXTERN int pc_hip_emit_counts(pc_hip_ctx *ctx_b, int64_t counts[3]);
 
+/* ---- slab emits: an emit relay through a thick sample.  The sample is a laterally infinite slab whose front face is the emit's sheet
+ * (the plane through c0 + depth n_s with the normal n_s) and which extends `thickness` (T, cm) along +n_s.  The excitation is
+ * attenuated on its way to the depth of interaction, the fluorescence on its way out towards B; the sample's linear attenuation
+ * coefficients (1/cm) come as two tables, mu_in[n_energies of A] and mu_out[n_energies of B].  IEEE fp64, evaluated in the order
+ * written, no contraction, no fma.
+ *   frame      the emit's sixteen numbers (the same code, the same bits), then k = (n_s.u, n_s.v, n_s.n), every dot product as
+ *              (a0*b0 + a1*b1) + a2*b2, then T: twenty numbers, computed once on the host (pc_hip_slab_frame)
+ *   entries, selection, slots: the emit's
+ *   emission   dz, sd, sp, "missed the sample", t and p as in an emit, then
+ *              L = T / sd                                       the path through the whole slab
+ *              u1, u2, u3 = uniforms 0, 1 and 2 of the entry's stream: 0 and 1 are the emit's, so that a thin and a thick emit with
+ *                                                               one seed aim at the same target point
+ *              s = u3*L,   zn = s*sd                            the path to the interaction, uniform on [0, L), and its depth
+ *              p' = (p0 + dx*s, p1 + dy*s, p2 + dz*s)
+ *              a, b, q = c_B - p', f, "missed the detector", r2, r, d, g and the electric vector as in an emit, p' in the place of p
+ *              cn = ((k0*f0 + k1*f1) + k2*f2) / r               the emitted ray's cosine to n_s
+ *              cn > 0 (it leaves through the back):   tz = T - zn, set to 0 when negative;   s_out = tz/cn
+ *              cn < 0 (through the front, the reflection geometry):   s_out = zn/(0 - cn)
+ *              otherwise: missed the detector
+ *              gl = g*L;   missed the sample when !(gl < 1): grazing incidence on a slab so thick that the estimator's weight would
+ *              leave the range of the exact sums
+ *   finish     for every photon with rc 1 and every energy e of B:
+ *              a_e = mu_in[map[e]]*s + mu_out[e]*s_out,   att = E(0 - a_e),   w = ((wA[map[e]]*gl)*att)*wB[e]
+ *              E(x), x <= 0: +0 when x < -700 (no subnormal arises), else with k = rint(x*1.4426950408889634074):
+ *              r = (x - k*6.93147180369123816490e-01) - k*1.90821492927058770002e-10,   the degree-11 Horner polynomial
+ *              p = p*r + c with c = 1/11!, 1/10!, ..., 1/2, 1, 1 (the doubles pc_emit.h writes),   E = ldexp(p, k); within 1e-14
+ *              relative of exp(x); E(0) = 1 exactly; a NaN gives a NaN
+ *   records    as an emit's, with pc_exit_dtravel = (((dA + t) + s) + r) + dB
+ *   counts     the emit's, and their identity; pc_hip_emit_counts and pc_hip_pose_counts answer after a slab emit too
+ * The interaction depth is sampled uniformly along the path, not exponentially: one geometry serves every energy, and a depth scan
+ * keeps common random numbers.  The efficiency is that of detected photons per photon started into A, per unit fluorescence-
+ * production coefficient (1/cm), for isotropic emission: the caller multiplies by that coefficient and the yield.
+ * A spec is valid when its emit is, thickness is finite and in (0, 1] cm, both tables are given with at least one entry, and every mu
+ * is finite and >= 0.  Refused with PC_HIP_ERR_INVALID and a message that names the field, before anything is launched and with both
+ * contexts and the selection left as they were: what pc_hip_emit_run refuses; an invalid spec; n_mu_in other than A's energy count,
+ * n_mu_out other than B's. */
+typedef struct {
+	pc_hip_emit emit;
+	double thickness;
+	int32_t n_mu_in;
+	const double *mu_in;
+	int32_t n_mu_out;
+	const double *mu_out;
+} pc_hip_slab;
+/* host only: the spec alone (the map and the tables' lengths against the contexts' grids: pc_hip_slab_run) */
+POLYCAP_EXTERN int pc_hip_slab_validate(const pc_hip_slab *spec);
+/* host only: the emit's sixteen numbers, k (3), T of a valid spec */
+POLYCAP_EXTERN int pc_hip_slab_frame(const pc_hip_slab *spec, double frame[20]);
+/* the slab emit of ctx_a's exit photons into ctx_b, through `select` (NULL: no aperture); everything that reads an emit relay's
+ * result applies unchanged */
+POLYCAP_EXTERN int pc_hip_slab_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_slab *spec, pc_hip_select *select);
+
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 

@@ -94,6 +94,12 @@ class EmitS(C.Structure):
                 ("seed", C.c_uint64), ("n_map", C.c_int32), ("map", C.POINTER(C.c_int32))]
 
 
+class SlabS(C.Structure):
+    """struct pc_hip_slab"""
+    _fields_ = [("emit", EmitS), ("thickness", C.c_double), ("n_mu_in", C.c_int32), ("mu_in", c_double_p),
+                ("n_mu_out", C.c_int32), ("mu_out", c_double_p)]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -389,6 +395,12 @@ def lib():
     L.pc_hip_emit_run.restype = C.c_int
     L.pc_hip_emit_counts.argtypes = [C.c_void_p, c_int64_p]
     L.pc_hip_emit_counts.restype = C.c_int
+    L.pc_hip_slab_validate.argtypes = [P(SlabS)]
+    L.pc_hip_slab_validate.restype = C.c_int
+    L.pc_hip_slab_frame.argtypes = [P(SlabS), c_double_p]
+    L.pc_hip_slab_frame.restype = C.c_int
+    L.pc_hip_slab_run.argtypes = [C.c_void_p, C.c_void_p, P(SlabS), C.c_void_p]
+    L.pc_hip_slab_run.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

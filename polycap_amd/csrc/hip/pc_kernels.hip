@@ -1083,6 +1083,7 @@ struct pc_relay_state {
 	pc_dev_buf<long long> d_map;           /* position in the first optic's store of every injected photon */
 	pc_dev_buf<unsigned long long> d_scan; /* the scratch of the two compactions, then the finish kernel's counters (PC_RELAY_SCAN_WORDS) */
 	pc_dev_buf<int> d_emap;                /* emit relays: which of the first optic's energies every energy of this context takes its weight from */
+	pc_dev_buf<double> d_mu;               /* slab emits: the sample's attenuation coefficients, mu_in [the first optic's energies] before mu_out [this context's] */
 	int acc_lds = 1;                       /* option "relay_acc_lds": 0 = the finish kernel adds to the global sums at once (tests) */
 	int64_t counters[8] = {0};
 	int64_t lost[3] = {0, 0, 0};           /* photons lost between the optics, at [outcome - PC_RELAY_REJECT]: rejected by the selection, missed

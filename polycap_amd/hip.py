@@ -315,7 +315,7 @@ class TraceContext:
         return r
 
     def emit(self, other, focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=None, seed=0, energy_map=None,
-             select=None):
+             select=None, thickness=None, mu_in=None, mu_out=None):
         """An emit relay: the exit photons of this context's last source run (made with keep_images) hit a thin sample sheet
         through the point `depth` cm along its normal from (0, 0, focus) behind this optic's exit plane, the normal turned by
         `sample_angle` rad from this optic's axis towards +x; every photon that reaches the sheet re-emits one photon towards
@@ -328,17 +328,29 @@ class TraceContext:
         face.  `energy_map`[e] = the energy of this context whose weight energy e of `other` takes (fluorescence: excited at one
         energy, detected at another); None: both contexts share one grid.  `select`: a Selection of this context, as in relay().
         Returns what relay() returns, with missed_sample, missed_detector (their sum is `missed`) and rejected in counters; the
-        efficiencies are per photon started into this optic and per unit interaction probability in the sheet."""
+        efficiencies are per photon started into this optic and per unit interaction probability in the sheet.
+        With `thickness` (cm), `mu_in` [this context's energies] and `mu_out` [the energies of `other`] (1/cm) the sample is a slab
+        behind the sheet: every photon interacts at a depth drawn uniformly along its path through the slab, attenuated by mu_in
+        on the way there and by mu_out on the emitted ray's way out, through the back or, in the reflection geometry, through the
+        front (pc_hip_slab_run).  The efficiencies are then per unit fluorescence-production coefficient (1/cm).  The three come
+        together or not at all (ValueError)."""
         if not isinstance(other, TraceContext):
             raise TypeError("emit: other must be a TraceContext")
         if select is not None and not isinstance(select, Selection):
             raise TypeError("emit: select must be a Selection")
         if target_half is None:
             target_half = float(other.problem.ext[0])
-        spec, keep = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map)
-        st = self._L.pc_hip_emit_run(self._h, other._h, C.byref(spec), None if select is None else select._h)
-        if st != _cabi.PC_HIP_OK:
-            raise HipError("pc_hip_emit_run", st)
+        sel = None if select is None else select._h
+        if _slab_given("emit", thickness, mu_in, mu_out):
+            spec, keep = _slab_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map, thickness, mu_in, mu_out)
+            st = self._L.pc_hip_slab_run(self._h, other._h, C.byref(spec), sel)
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_slab_run", st)
+        else:
+            spec, keep = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map)
+            st = self._L.pc_hip_emit_run(self._h, other._h, C.byref(spec), sel)
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_emit_run", st)
         other._relay_squares = getattr(other, "_weight_squares", False)
         r = other.relay_totals()
         other._last_n = r["n_records"]
@@ -573,16 +585,58 @@ def emit_frame(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), targe
     return dict(n_s=f[0:3], h_s=float(f[3]), u=f[4:7], v=f[7:10], n=f[10:13], c_b=f[13:16], frame=f)
 
 
+def _slab_given(who, thickness, mu_in, mu_out):
+    """False: none of a slab's three arguments is given; True: all of them are"""
+    given = [v is not None for v in (thickness, mu_in, mu_out)]
+    if any(given) and not all(given):
+        raise ValueError(who + ": thickness, mu_in and mu_out describe a slab together: give all three or none")
+    return all(given)
+
+
+def _slab_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map, thickness, mu_in, mu_out):
+    """(pc_hip_slab, what its pointers point to)"""
+    e, m = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map)
+    mi = np.ascontiguousarray(mu_in, dtype=np.float64).reshape(-1)
+    mo = np.ascontiguousarray(mu_out, dtype=np.float64).reshape(-1)
+    s = _cabi.SlabS(e, float(thickness), int(mi.shape[0]), dptr(mi), int(mo.shape[0]), dptr(mo))
+    return s, (m, mi, mo)
+
+
+def emit_slab_valid(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1., energy_map=None, thickness=None,
+                    mu_in=None, mu_out=None):
+    """True when pc_hip_slab_validate accepts the spec of a slab emit (host only; the map and the tables' lengths against two
+    contexts' grids are checked by emit())."""
+    if not _slab_given("emit_slab_valid", thickness, mu_in, mu_out):
+        raise ValueError("emit_slab_valid: thickness, mu_in and mu_out are needed")
+    spec, keep = _slab_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, energy_map, thickness, mu_in, mu_out)
+    return _cabi.lib().pc_hip_slab_validate(C.byref(spec)) == _cabi.PC_HIP_OK
+
+
+def emit_slab_frame(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1., thickness=None):
+    """The frame of a slab emit (pc_hip_slab_frame, host only): what emit_frame returns, with k [3] (the slab's normal in the second
+    optic's axes) and thickness, and frame [20] = the emit's sixteen numbers, k, thickness."""
+    if thickness is None:
+        raise ValueError("emit_slab_frame: thickness is needed")
+    spec, keep = _slab_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, None, thickness, [0.], [0.])
+    f = np.zeros(20)
+    st = _cabi.lib().pc_hip_slab_frame(C.byref(spec), dptr(f))
+    if st != _cabi.PC_HIP_OK:
+        raise HipError("pc_hip_slab_frame", st)
+    return dict(n_s=f[0:3], h_s=float(f[3]), u=f[4:7], v=f[7:10], n=f[10:13], c_b=f[13:16], k=f[16:19], thickness=float(f[19]), frame=f)
+
+
 def emit_depth_scan(ctx_a, ctx_b, depths, focus, sample_angle, det_angle, wd, offset=(0., 0.), target_half=None, seed=0,
-                    energy_map=None, select=None):
+                    energy_map=None, select=None, thickness=None, mu_in=None, mu_out=None):
     """A depth scan of the sample: one emit of ctx_a's last run into ctx_b per depth of `depths`, a host loop with one seed, so
     that every depth re-emits with the same random numbers (common random numbers: smooth curves).  Returns depths [n],
     efficiencies [n, n_energies], efficiency_stderr [n, n_energies] (option "weight_squares" on ctx_b, else None) and the emits'
-    counters as a list of dicts."""
+    counters as a list of dicts.  thickness, mu_in, mu_out: a slab behind the sheet, as in emit(); the curve is then the one an
+    instrument records, self-absorption included."""
     dl = np.asarray(depths, dtype=np.float64).reshape(-1)
     eff, err, cnt = [], [], []
     for d in dl:
-        r = ctx_a.emit(ctx_b, focus, sample_angle, float(d), det_angle, wd, offset, target_half, seed, energy_map, select)
+        r = ctx_a.emit(ctx_b, focus, sample_angle, float(d), det_angle, wd, offset, target_half, seed, energy_map, select,
+                       thickness, mu_in, mu_out)
         eff.append(r["efficiencies"])
         err.append(r["efficiency_stderr"])
         cnt.append(r["counters"])
