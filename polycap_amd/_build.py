@@ -21,7 +21,6 @@ LIB = os.path.join(LIBDIR, "libpolycap.so")
 HOST_SRCS = ["pc_error.c", "pc_rng.c", "pc_profile.c", "pc_description.c", "pc_optconst.c",
              "pc_photon.c", "pc_request.c", "pc_source.c", "pc_transeff.c", "pc_hdf5.c"]
 HIP_SRCS = ["pc_kernels.hip"]
-HIP_DEPS = ["pc_device.h", "pc_problem.h", "pc_leak.h", "pc_leak_kernels.h", "pc_leak_plan.h", "pc_leak_run.h", "pc_pool_kernel.h", "pc_producer_kernel.h", "pc_wave_kernel.h", "pc_sweep_kernel.h", "pc_group.h", "pc_tally.h", "pc_spot.h", "pc_beam.h", "pc_hist.h", "pc_joint.h", "pc_select.h", "pc_gather.h", "pc_draw.h", "pc_moments.h", "pc_scan.h", "pc_relay.h", "pc_emit.h", "pc_plan.h", "pc_images.h", "pc_exact.h", "pc_totals.h"]
 
 # -I HIPD: pc_exact.h, the one header the host C shares with the kernels' translation unit
 CFLAGS = ["-std=c11", "-O2", "-fPIC", "-Wall", "-Wextra", "-fvisibility=hidden", "-I" + INC, "-I" + HOST, "-I" + HIPD]
@@ -64,7 +63,8 @@ def build(force=False, verbose=False):
     for s in HIP_SRCS:
         src = os.path.join(HIPD, s)
         obj = os.path.join(OBJDIR, s + ".o")
-        deps = [src] + [os.path.join(HIPD, d) for d in HIP_DEPS] + headers[:2]
+        # the one translation unit includes every header of its directory
+        deps = [src] + [os.path.join(HIPD, d) for d in sorted(os.listdir(HIPD)) if d.endswith(".h")] + headers[:2]
         if force or _newer(obj, deps):
             _run(["hipcc"] + HIPFLAGS + ["-c", src, "-o", obj], verbose)
         objs.append(obj)

@@ -2,7 +2,7 @@
  * pc_device.h -- per-photon device logic of the MI355X trace path (fp64).
  *
  * One lane owns one photon.  The logic is written as small state-transition functions so the
- * kernels (pc_kernels.hip) can schedule the three phases of a photon's life wave-wide:
+ * kernels (pc_trace_kernel.h and its siblings) can schedule the three phases of a photon's life wave-wide:
  *   MARCH  : walk profile nodes with a 6-FMA "still strictly inside the capillary" certificate
  *   EVENT  : the reference's full segment quadratic + wall hit + Fresnel reflection
  *   NEW    : source sampling (Philox4x32-10) + entrance tests

@@ -12,9 +12,9 @@
  *
  * Two halves.  The pure one -- what a run stores and in how many launches (pc_plan_images), where an element lies
  * (pc_layout_of), which positions a group of blocks holds (pc_block_span), the caller's planes in field order (pc_image_planes) --
- * works on plain values and compiles for the host (tests/plan/images_host.cpp).  pc_kernels.hip includes it ahead of the kernels,
- * which use the record fields, and the header once more with PC_IMAGES_STORE defined behind them: the store and the fetch need
- * the kernels, the owner types and pc_kargs.
+ * works on plain values and compiles for the host (tests/plan/images_host.cpp).  The store and the fetch, with the two kernels
+ * they launch, need the owner types (pc_host.h) and pc_kargs (pc_kargs.h) and are for hipcc alone.  pc_kernels.hip includes the
+ * header once, ahead of the trace kernels, which use the record fields.
  */
 #ifndef PC_IMAGES_H
 #define PC_IMAGES_H
@@ -141,10 +141,50 @@ static void pc_image_planes(const pc_hip_images *d, void *out[PC_N_FIELDS + 1])
 	std::copy(p, p + PC_N_FIELDS + 1, out);
 }
 
-#endif /* PC_IMAGES_H */
+/* ---- the store and the fetch: device code and the owner types, so nothing below is for a host compiler */
+#ifdef __HIPCC__
 
-#if defined(PC_IMAGES_STORE) && !defined(PC_IMAGES_STORE_H)
-#define PC_IMAGES_STORE_H
+/* Compact store: slots that used up their attempts without a transmitted photon wrote nothing (the slot-ordered store writes
+ * zero weights for them), so the positions behind the run's cursor hold whatever the buffer held: zero them once the trace
+ * kernel has ended -- every plane and the weights -- so that a result with failed slots never carries stale data. */
+__global__ void __launch_bounds__(256) pc_compact_tail_kernel(double *soa, long long n_total, int ne, const unsigned long long *cursor)
+{
+	const long long c = (long long)*cursor;
+	if (c >= n_total) return;
+	const long long cells = (n_total - c)*(long long)(PC_N_FIELDS + ne);
+	for (long long t = (long long)blockIdx.x*blockDim.x + threadIdx.x; t < cells; t += (long long)gridDim.x*blockDim.x) {
+		const long long p = c + t / (PC_N_FIELDS + ne);
+		const int f = (int)(t % (PC_N_FIELDS + ne));
+		if (f < PC_N_FIELDS) soa[(long long)f*n_total + p] = 0.;
+		else soa[(long long)PC_N_FIELDS*n_total + p*ne + (f - PC_N_FIELDS)] = 0.;
+	}
+}
+
+/* Image records (one contiguous record of 17 + n_energies doubles per slot) -> the planes of struct _polycap_images: 17
+ * planes of n_total doubles each, then the weights as [slot][n_energies].  A workgroup stages PC_SOA_TILE records in LDS
+ * with coalesced reads and writes every plane with coalesced stores: 2 x 144 B of HBM traffic per photon, about a
+ * millisecond per 1e7 photons, instead of a strided gather by host threads behind PCIe. */
+#define PC_SOA_TILE 128
+__global__ void __launch_bounds__(256) pc_soa_kernel(const double *rec, double *soa, long long first, long long count, long long n_total, int ne)
+{
+	extern __shared__ double tile[];
+	const int recd = PC_N_FIELDS + ne;
+	const long long j0 = first + (long long)blockIdx.x*PC_SOA_TILE;
+	const int m = (int)((first + count - j0 < PC_SOA_TILE) ? first + count - j0 : PC_SOA_TILE);
+	if (m <= 0) return;
+	const double *src = rec + j0*recd;
+	for (int k = threadIdx.x; k < m*recd; k += blockDim.x) tile[k] = src[k];
+	__syncthreads();
+	for (int k = threadIdx.x; k < m*PC_N_FIELDS; k += blockDim.x) {
+		const int plane = k / m, t = k - plane*m;
+		soa[(long long)plane*n_total + j0 + t] = tile[t*recd + plane];
+	}
+	double *w = soa + (long long)PC_N_FIELDS*n_total + j0*ne;
+	for (int k = threadIdx.x; k < m*ne; k += blockDim.x) {
+		const int t = k / ne, e = k - t*ne;
+		w[k] = tile[t*recd + PC_N_FIELDS + e];
+	}
+}
 
 /* what a reader on the device gets: n entries at p and their weights at w, strides in l */
 struct pc_image_view {
@@ -711,4 +751,6 @@ static int pc_fetch_images(pc_image_store &st, int64_t first, int64_t count, voi
 	return pc_fetch_staged(st, first, count, planes, weights, raw);
 }
 
-#endif /* PC_IMAGES_STORE */
+#endif /* __HIPCC__ */
+
+#endif /* PC_IMAGES_H */

@@ -2,8 +2,8 @@
  * pc_leak_run.h -- the host side of leak_calc=true runs: one owner (pc_leak_run, held as pc_hip_ctx::leak) of their buffers,
  * options and the run in flight, and the C calls that start a leak run and read its events.  What it decides -- grid, record
  * capacity, the order of the slots -- it asks pc_leak_plan.h; the kernels are in pc_leak_kernels.h.  Included twice by
- * pc_kernels.hip like pc_images.h: the struct before the context that holds it, and with PC_LEAK_RUN_BODY everything that needs
- * the context and the kernels behind them.
+ * pc_kernels.hip, the only header that is: the struct before the context that holds it (pc_ctx.h), and everything that needs
+ * the context, the launch code (pc_launch.h) and the kernels once pc_leak_kernels.h has been included.
  */
 #ifndef PC_LEAK_RUN_H
 #define PC_LEAK_RUN_H
@@ -81,7 +81,8 @@ struct pc_leak_run {
 
 #endif /* PC_LEAK_RUN_H */
 
-#if defined(PC_LEAK_RUN_BODY) && !defined(PC_LEAK_RUN_BODY_H)
+/* ---- the second pass: behind the context, the launch code and the leak kernels */
+#if defined(PC_LEAK_KERNELS_H) && !defined(PC_LEAK_RUN_BODY_H)
 #define PC_LEAK_RUN_BODY_H
 
 static pc_leak_grid pc_leak_grid_of(const pc_hip_ctx &ctx, long long n_items)
@@ -465,4 +466,4 @@ int pc_hip_leak_slot_units(pc_hip_ctx *ctx, int64_t first, int64_t count, uint32
 
 } /* extern "C" */
 
-#endif /* PC_LEAK_RUN_BODY */
+#endif /* PC_LEAK_RUN_BODY_H */

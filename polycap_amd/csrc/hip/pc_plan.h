@@ -2,7 +2,7 @@
  * pc_plan.h -- which kernel a trace launch runs and in what shape: the options the decision reads (pc_launch_opts), what a launch
  * needs (pc_launch_plan) and the one function between them (pc_plan_launch), which works on plain values: no HIP call, no context.
  * So the header compiles for the host (-DPC_PLAN_HOST_ONLY leaves out pc_launch_site; tests/plan/plan_host.cpp).  The only reader
- * of a plan is pc_launch_planned of pc_kernels.hip.  Also here, because the decision needs them: the kernels' workgroup shapes
+ * of a plan is pc_launch_planned of pc_launch.h.  Also here, because the decision needs them: the kernels' workgroup shapes
  * and LDS size formulas.
  */
 #ifndef PC_PLAN_H
@@ -154,7 +154,7 @@ struct pc_launch_plan {
 	size_t stage_doubles = 0;      /* logging kernel: staged logs per wave */
 	int log_cap = 0, stage_ps = 0, flush_min = 0, sweep_skip = 0, sweep_fuse = 0, sweep_exact_every = 0;
 	int event_threshold = 0, new_threshold = 0, pool_event_min = 0, event_march = 0;   /* pc_kargs, per kernel */
-	size_t half_w = 0, half_l = 0; /* elements of d_wscratch and d_rlog per half (pc_launch_site::halves of them) */
+	size_t half_w = 0, half_l = 0; /* elements of pc_lane_scratch's d_wscratch and d_rlog per half (pc_launch_site::halves of them) */
 };
 
 static pc_launch_plan pc_plan_launch(const pc_plan_input &in, const pc_launch_opts &o)
@@ -266,7 +266,7 @@ static pc_launch_plan pc_plan_launch(const pc_plan_input &in, const pc_launch_op
 struct pc_launch_site {
 	hipStream_t stream;
 	bool record_ev0 = true, record_ev1 = true;   /* record pc_hip_ctx::ev0 before and ev1 behind the kernel */
-	/* per-lane scratch (d_wscratch, d_rlog) of a run cut into parts: launches on the two streams overlap, so the buffers are
+	/* per-lane scratch (pc_lane_scratch) of a run cut into parts: launches on the two streams overlap, so the buffers are
 	 * allocated twice over (halves = 2), each half sized for the largest launch the run can make, and the launches on
 	 * stream2 use the second half (half = 1) */
 	int halves = 1, half = 0;

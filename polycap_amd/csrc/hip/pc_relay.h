@@ -515,7 +515,7 @@ static int pc_relay_drive(pc_hip_ctx *b, const char *who, const pc_spot_src &s, 
 	unsigned long long h_cnt[8] = {0};
 	if (n_in > 0) {
 		pc_batch bt;
-		st = pc_batch_layout(b, n_in, false, bt);
+		st = b->batch.layout((size_t)ne, n_in, false, bt);
 		if (st) return st;
 		hipLaunchKernelGGL(pc_relay_inject_kernel<RULE>, dim3((unsigned)((n_a + 255)/256)), dim3(256), 0, b->stream, s, pl,
 		                   (const unsigned long long *)rs.d_scan, n_a, bt.d_start, bt.d_dir, bt.d_ev, (long long *)rs.d_map);

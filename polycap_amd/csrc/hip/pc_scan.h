@@ -1,7 +1,7 @@
 /*
  * pc_scan.h -- scans: transmission as a function of the source position, one launch for a whole grid of points with exact
  * totals per point (include/polycap-hip.h, pc_hip_scan_*).  The kernel is pc_trace_kernel with MODE PC_MODE_SCAN_CIRCULAR /
- * _GENERIC (pc_kernels.hip) or, with option "scan_log" and a plan that can log (pc_plan_launch), pc_trace_log_kernel with those
+ * _GENERIC (pc_trace_kernel.h) or, with option "scan_log" and a plan that can log (pc_plan_launch), pc_trace_log_kernel with those
  * modes (pc_sweep_kernel.h); the mapping of a flat index to its point and the per-point source are pc_scan_map /
  * pc_sample_photon_at of pc_device.h.  Included at the end of pc_kernels.hip.
  */
@@ -28,15 +28,14 @@ static int pc_scan_check(const char *fn, const pc_hip_scan_point *pts, int64_t n
 }
 
 /* device buffers of a scan of n_points points (the per-lane weights and reflection logs of more than 8 energies: pc_launch_planned) */
-static int pc_scan_buffers(pc_hip_ctx *ctx, int64_t n_points)
+int pc_scan_state::buffers(size_t ne, int64_t n_points)
 {
-	const size_t ne = (size_t)ctx->host.pm.n_energies;
-	int st = ctx->d_scan_totals.grow(1, "pc_hip_scan_run: could not allocate the scan totals");
+	int st = d_totals.grow(1, "pc_hip_scan_run: could not allocate the scan totals");
 	if (st) return st;
-	PC_HIP_CHECK(ctx->ev_scan0.ensure(hipEventDefault));
-	PC_HIP_CHECK(ctx->ev_scan1.ensure(hipEventDefault));
-	st = ctx->d_scan_pts.grow((size_t)n_points, "pc_hip_scan_run: could not allocate the point table");
-	if (!st) st = ctx->d_scan_tot.grow((size_t)n_points*PC_SCAN_STRIDE(ne), "pc_hip_scan_run: could not allocate the per-point totals");
+	PC_HIP_CHECK(ev0.ensure(hipEventDefault));
+	PC_HIP_CHECK(ev1.ensure(hipEventDefault));
+	st = d_pts.grow((size_t)n_points, "pc_hip_scan_run: could not allocate the point table");
+	if (!st) st = d_tot.grow((size_t)n_points*PC_SCAN_STRIDE(ne), "pc_hip_scan_run: could not allocate the per-point totals");
 	return st;
 }
 
@@ -50,16 +49,16 @@ int pc_hip_scan_validate(const pc_hip_scan_point *points, int64_t n_points, int6
 int pc_hip_scan_wait(pc_hip_ctx *ctx, float *kernel_ms)
 {
 	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_wait: ctx must not be NULL");
-	if (!ctx->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_wait: no scan has been made on this context");
-	if (ctx->scan_pending) {
+	if (!ctx->scan.points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_wait: no scan has been made on this context");
+	if (ctx->scan.pending) {
 		PC_HIP_CHECK(hipSetDevice(ctx->device));
-		PC_HIP_CHECK(hipEventSynchronize(ctx->ev_scan1));
+		PC_HIP_CHECK(hipEventSynchronize(ctx->scan.ev1));
 		float ms = 0.f;
-		PC_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_scan0, ctx->ev_scan1));
-		ctx->scan_ms = ms;
-		ctx->scan_pending = 0;
+		PC_HIP_CHECK(hipEventElapsedTime(&ms, ctx->scan.ev0, ctx->scan.ev1));
+		ctx->scan.ms = ms;
+		ctx->scan.pending = 0;
 	}
-	if (kernel_ms) *kernel_ms = ctx->scan_ms;
+	if (kernel_ms) *kernel_ms = ctx->scan.ms;
 	return PC_HIP_OK;
 }
 
@@ -77,11 +76,11 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	if (max_attempts < 1) max_attempts = 1;
 	PC_HIP_CHECK(hipSetDevice(ctx->device));
 	/* the previous scan's kernel may still read the point table and add to the totals that are reused below */
-	if (ctx->scan_pending) {
+	if (ctx->scan.pending) {
 		st = pc_hip_scan_wait(ctx, nullptr);
 		if (st) return st;
 	}
-	ctx->scan_points = 0;       /* until this scan is enqueued */
+	ctx->scan.points = 0;       /* until this scan is enqueued */
 	ctx->last_call = PC_CALL_SCAN;
 	/* behind every launch of the last run: a run cut into parts ends its main stream behind the parts on stream2 already
 	 * (pc_hip_transmission_run); this also orders the scan after anything else enqueued there */
@@ -90,18 +89,18 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 		PC_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->img.ev_sync, 0));
 	}
 	const int ne = ctx->host.pm.n_energies;
-	st = pc_scan_buffers(ctx, n_points);
+	st = ctx->scan.buffers((size_t)ne, n_points);
 	if (st) return st;
-	PC_HIP_CHECK(hipMemcpy(ctx->d_scan_pts, points, (size_t)n_points*sizeof(pc_scan_point), hipMemcpyHostToDevice));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_totals, 0, sizeof(pc_totals), ctx->stream));
-	PC_HIP_CHECK(hipMemsetAsync(ctx->d_scan_tot, 0, (size_t)n_points*PC_SCAN_STRIDE((size_t)ne)*sizeof(unsigned long long), ctx->stream));
+	PC_HIP_CHECK(hipMemcpy(ctx->scan.d_pts, points, (size_t)n_points*sizeof(pc_scan_point), hipMemcpyHostToDevice));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->scan.d_totals, 0, sizeof(pc_totals), ctx->stream));
+	PC_HIP_CHECK(hipMemsetAsync(ctx->scan.d_tot, 0, (size_t)n_points*PC_SCAN_STRIDE((size_t)ne)*sizeof(unsigned long long), ctx->stream));
 	pc_kargs a;
 	pc_fill_common(ctx, a);
-	a.totals = ctx->d_scan_totals;
-	a.work = &ctx->d_scan_totals->next_slot;
+	a.totals = ctx->scan.d_totals;
+	a.work = &ctx->scan.d_totals->next_slot;
 	/* the scan's arguments in pc_kargs (PC_SCAN_*): point table, per-point totals, first flat index, slots per point */
-	a.in_start = (const double *)ctx->d_scan_pts.p;
-	a.sumw = ctx->d_scan_tot;
+	a.in_start = (const double *)ctx->scan.d_pts.p;
+	a.sumw = ctx->scan.d_tot;
 	a.sumw2 = nullptr;
 	a.img_id0 = first;
 	a.img_n = n_per_point;
@@ -109,38 +108,38 @@ int pc_hip_scan_run(pc_hip_ctx *ctx, uint64_t seed, int64_t slot0, const pc_hip_
 	/* the lane kernel or the logging kernel in its scan mode (pc_plan_launch), between the scan's own events */
 	pc_launch_site site{ctx->stream};
 	site.record_ev0 = site.record_ev1 = false;
-	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan0, ctx->stream));
+	PC_HIP_CHECK(hipEventRecord(ctx->scan.ev0, ctx->stream));
 	st = ctx->host.pm.generic_src ? pc_launch_kernel<PC_MODE_SCAN_GENERIC>(ctx, site, a, count)
 	                              : pc_launch_kernel<PC_MODE_SCAN_CIRCULAR>(ctx, site, a, count);
 	if (st) return st;
-	PC_HIP_CHECK(hipEventRecord(ctx->ev_scan1, ctx->stream));
-	ctx->scan_points = n_points;
-	ctx->scan_squares = ctx->opts.weight_squares ? 1 : 0;
-	ctx->scan_pending = 1;
+	PC_HIP_CHECK(hipEventRecord(ctx->scan.ev1, ctx->stream));
+	ctx->scan.points = n_points;
+	ctx->scan.squares = ctx->opts.weight_squares ? 1 : 0;
+	ctx->scan.pending = 1;
 	return PC_HIP_OK;
 }
 
 int pc_hip_scan_last_kernel(pc_hip_ctx *ctx)
 {
-	return ctx ? ctx->scan_kernel : -1;
+	return ctx ? ctx->scan.kernel : -1;
 }
 
 int pc_hip_group_scan_last_kernel(pc_hip_group *g, int k)
 {
-	return (g && k >= 0 && (size_t)k < g->ctx.size()) ? g->ctx[(size_t)k]->scan_kernel : -1;
+	return (g && k >= 0 && (size_t)k < g->ctx.size()) ? g->ctx[(size_t)k]->scan.kernel : -1;
 }
 
 int pc_hip_scan_totals(pc_hip_ctx *ctx, int64_t *counters, uint64_t *sumw_fixed, uint64_t *sumw2_fixed)
 {
 	if (!ctx) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: ctx must not be NULL");
-	if (!ctx->scan_points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: no scan has been made on this context");
-	if (sumw2_fixed && !ctx->scan_squares)
+	if (!ctx->scan.points) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: no scan has been made on this context");
+	if (sumw2_fixed && !ctx->scan.squares)
 		return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_scan_totals: sumw2_fixed: the last scan was made without option weight_squares");
 	int st = pc_hip_scan_wait(ctx, nullptr);
 	if (st) return st;
-	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = PC_SCAN_STRIDE(ne), P = (size_t)ctx->scan_points;
+	const size_t ne = (size_t)ctx->host.pm.n_energies, stride = PC_SCAN_STRIDE(ne), P = (size_t)ctx->scan.points;
 	std::vector<unsigned long long> buf(P*stride);
-	PC_HIP_CHECK(hipMemcpy(buf.data(), ctx->d_scan_tot, buf.size()*sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	PC_HIP_CHECK(hipMemcpy(buf.data(), ctx->scan.d_tot, buf.size()*sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	for (size_t k = 0; k < P; k++) {
 		const unsigned long long *t = buf.data() + k*stride;
 		if (counters) for (int c = 0; c < PC_N_COUNTERS; c++) counters[PC_N_COUNTERS*k + c] = (int64_t)t[PC_SCAN_COUNTERS + c];
@@ -204,7 +203,7 @@ int pc_hip_group_scan_run(pc_hip_group *g, uint64_t seed, int64_t slot0, const p
 	for (size_t k = 0; k < N; k++) {
 		if (status[k] == PC_HIP_OK) continue;
 		for (size_t j = 0; j < N; j++)
-			if (g->ctx[j]->scan_pending) (void)pc_hip_scan_wait(g->ctx[j], nullptr);
+			if (g->ctx[j]->scan.pending) (void)pc_hip_scan_wait(g->ctx[j], nullptr);
 		g->scan_count.assign(N, 0);
 		return pc_fail(status[k], msg[k]);
 	}

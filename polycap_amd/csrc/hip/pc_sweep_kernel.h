@@ -23,7 +23,7 @@
  *     reference ends it.
  *   tame reflections.  The reference rejects a reflectivity outside [0, 1] at any energy (:633-637, photon ends with rc -1).
  *     The host certifies a grazing cosine ct_tame above which no energy of the run can come within 1e-11 of 1
- *     (pc_sweep_certificate: scan of 1 - R_s, 1 - R_p in extended precision over 13 decades of cos theta, per energy); a
+ *     (pc_sweep_certify, pc_sweep_cert.h: scan of 1 - R_s, 1 - R_p in extended precision over 13 decades of cos theta, per energy); a
  *     reflection with cos theta >= ct_tame and sane fractions is "tame": every factor is in [0, 1).  A log of tame reflections
  *     is swept by the FAST loop -- no range test, no counting: weights only fall, so the photon is alive iff some energy ends
  *     >= 1e-4, and dead means absorbed (rc 0), since no factor was rejected.  A log with a reflection that is not tame (3e-8

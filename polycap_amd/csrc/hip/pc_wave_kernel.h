@@ -7,8 +7,9 @@
  * ballot + ffs finds the first node that is not certified and the photon goes to EVENT at the segment in front of it.  The
  * literal visits, hence every photon and the exact totals, are those of the lane kernels (certified skipping at any stride
  * visits the same segments: tests/test_gpu_parity.py), which the A/B script checks.  Histogram only (no image planes),
- * single energy, source modes.  Measured: profiles/r03/wave_per_photon_ab.txt. */
-#ifndef PC_WAVE_KERNEL_H
+ * single energy, source modes.  Measured: profiles/r03/wave_per_photon_ab.txt.  Not part of the product build: the header
+ * is empty without -DPC_EXPERIMENTS. */
+#if defined(PC_EXPERIMENTS) && !defined(PC_WAVE_KERNEL_H)
 #define PC_WAVE_KERNEL_H
 
 template <int MODE>
@@ -109,4 +110,4 @@ pc_trace_wave_kernel(pc_kargs a)
 	}
 }
 
-#endif /* PC_WAVE_KERNEL_H */
+#endif /* PC_EXPERIMENTS, PC_WAVE_KERNEL_H */

@@ -1,5 +1,5 @@
 """Experiment (needs a build whose log-kernel condition admits fewer than 9 energies: `kne == 0 &&` dropped from want_log and the
-option's lower bound lowered in pc_kernels.hip): the logging kernel against the register-weight kernels at 2 ... 8 energies
+option's lower bound lowered in pc_options.h): the logging kernel against the register-weight kernels at 2 ... 8 energies
 (xos1, 1e6 slots, histogram only).  Result, round 4: 2 energies 3.55e8 against 1.17e8 started photons/s, 3: 3.66e8 / 2.11e8,
 4: 3.58e8 / 2.11e8, 6: 2.78e8 / 2.10e8, 8: 2.69e8 / 2.15e8 -- the register kernels keep their range."""
 import sys

@@ -8,8 +8,10 @@
                                                                 # hot march step around one photon, alone)
     python scripts/analysis/producer_listing.py --keep DIR      # leave the .hip and .s files in DIR
 
-The unit is pc_kernels.hip up to and including its `#include "pc_producer_kernel.h"` plus explicit instantiations; the
-kernel's code is the same as in the full build (same flags, nothing after that line is visible to it).  Nothing is run: the
+The unit is pc_kernels.hip -- a list of includes in dependency order -- up to and including its
+`#include "pc_producer_kernel.h"`, plus explicit instantiations; the kernel's code is the same as in the full build (same flags,
+nothing after that line is visible to it).  The few plain kernels of the headers in front of that line (pc_images.h,
+pc_trace_kernel.h) compile along and are left out of the listing.  Nothing is run: the
 compile is for the device only.  Per kernel: vector-ALU instructions (mnemonics that start with v_), how many of them are
 plain register copies or selects (v_mov_b32, v_mov_b64, v_cndmask_b32, v_accvgpr_read/write/mov, in their _e32 / _e64
 encodings only: DPP and SDWA forms move data between lanes and are not counted as copies), and the registers, spills and
@@ -109,6 +111,8 @@ def main():
     subprocess.check_call(["hipcc"] + flags(root) + [src, "-o", s], stderr=subprocess.DEVNULL)
     demangle = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
     for name, c, body, line0 in count(open(s).read()):
+        if not a.probe and "pc_trace_producer_kernel" not in name:
+            continue
         if demangle:
             name = subprocess.check_output([demangle, name]).decode().strip()
         print("%-56s VALU %5d  mov/cndmask %4d  all %5d  vgpr %s agpr %s vspill %s sspill %s scratch %s" % (

@@ -18,6 +18,7 @@
 
 #include "pc_problem.h"
 #include "pc_leak.h"
+#include "pc_sweep_cert.h"
 #include "../devmath/probe_ops.h"
 
 namespace {
@@ -502,6 +503,18 @@ int emul_leak_tables(const pc_hip_problem *p, double *node)
 		double *o = node + 4*i;
 		o[0] = E.t.stp[i]; o[1] = E.t.istp[i]; o[2] = E.t.dr[i].d1; o[3] = E.t.dr[i].d2;
 	}
+	return 0;
+}
+
+/* Test-only accessor: what pc_sweep_certify makes of p's per-energy constants; proxies[3] = n_proxy, proxy_e[0], proxy_e[1] */
+int emul_sweep_cert(const pc_hip_problem *p, double *ct_tame, int32_t *proxies)
+{
+	Emul E;
+	int r = setup(p, 0, E);
+	if (r) return r;
+	const pc_sweep_cert c = pc_sweep_certify(E.t.ec);
+	*ct_tame = c.ct_tame;
+	proxies[0] = c.n_proxy; proxies[1] = c.proxy_e[0]; proxies[2] = c.proxy_e[1];
 	return 0;
 }
 

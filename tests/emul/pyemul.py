@@ -22,6 +22,7 @@ def lib():
                 os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_device.h"),
                 os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_problem.h"),
                 os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_leak.h"),
+                os.path.join(_ROOT, "polycap_amd", "csrc", "hip", "pc_sweep_cert.h"),
                 os.path.join(_ROOT, "tests", "devmath", "probe_ops.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
@@ -65,6 +66,8 @@ def lib():
             f.restype = C.c_int
         L.emul_leak_tables.argtypes = [C.POINTER(ProblemS), c_double_p]
         L.emul_leak_tables.restype = C.c_int
+        L.emul_sweep_cert.argtypes = [C.POINTER(ProblemS), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.emul_sweep_cert.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -174,6 +177,17 @@ def leak_tables(problem):
     if r:
         raise RuntimeError("emul_leak_tables failed: %d" % r)
     return {k: node[:, j].copy() for j, k in enumerate(("stp", "istp", "d1", "d2"))}
+
+
+def sweep_cert(problem):
+    """The sweep certificate of `problem`'s energies (pc_sweep_certify of pc_sweep_cert.h on the host): ct_tame, n_proxy and the
+    proxies as TraceContext.sweep_stats reports them (the second one -1 when both angles pick the same energy)."""
+    ct = C.c_double(0.)
+    pr = (C.c_int32 * 3)(0, 0, 0)
+    r = lib().emul_sweep_cert(C.byref(problem.s), C.byref(ct), pr)
+    if r:
+        raise RuntimeError("emul_sweep_cert failed: %d" % r)
+    return dict(ct_tame=float(ct.value), n_proxy=int(pr[0]), proxies=[int(pr[1]), int(pr[2]) if pr[0] > 1 else -1])
 
 
 def sort_leak_records(rec):

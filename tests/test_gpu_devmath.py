@@ -168,7 +168,7 @@ def test_return_codes_match_the_host(glass, sig_rough):
 @pytest.mark.parametrize("deck,sig_rough", [("xos1", None), ("ellip_l9", 5.0)])
 def test_tame_reflections_cannot_fail_the_range_test(deck, sig_rough):
     """pc_trace_log_kernel skips the reference's range test rtot in [0, 1] (src/polycap-capil.c:633-637) for reflections with cos
-    theta >= ct_tame (pc_sweep_certificate).  For every energy of the 291-energy decks the device's FORM 3 factor at 64 points per
+    theta >= ct_tame (pc_sweep_certify).  For every energy of the 291-energy decks the device's FORM 3 factor at 64 points per
     decade over [ct_tame, 1], with fractions 1/0, 0/1, 1/2 and random, lies in [0, 1 - 1e-12]: the skipped test cannot fire."""
     import polycap_amd
     from tests.conftest import EXAMPLE
@@ -191,3 +191,24 @@ def test_tame_reflections_cannot_fail_the_range_test(deck, sig_rough):
     f = y[:, 0]
     print("%s: ct_tame %.3e, %d factors over %d energies: min %.3e, max 1 - %.3e" % (deck, ct, f.size, ne, f.min(), 1.0 - f.max()))
     assert np.all(f >= 0.0) and np.all(f <= 1.0 - 1e-12), (deck, f.min(), f.max(), cc[np.argmax(f)], e[np.argmax(f)])
+
+
+@pytest.mark.parametrize("case", ["grid12", "deck291"])
+def test_sweep_certificate_is_the_host_functions(case):
+    """A context makes its sweep certificate with pc_sweep_certify (pc_sweep_cert.h) on the first launch of the logging kernel.  The
+    function is pure, so the host compile of it (tests/emul) returns the same ct_tame and proxies bit for bit;
+    tests/test_sweep_cert_cpu.py checks those against mpmath."""
+    import polycap_amd
+    from tests.emul import pyemul
+    from tests.test_sweep_cert_cpu import PROBLEMS
+    prob = PROBLEMS[case]()
+    want = pyemul.sweep_cert(prob)
+    with polycap_amd.TraceContext(prob) as ctx:
+        before = ctx.sweep_stats()
+        assert before["ct_tame"] == -1.0 and before["proxies"] == [-1, -1]      # unknown until a logging launch
+        ctx.transmission(5, 0, 2000)
+        assert ctx.last_kernel() == "pc_trace_log_kernel"
+        got = ctx.sweep_stats()
+    print("%s: ct_tame %r proxies %s" % (case, got["ct_tame"], got["proxies"]))
+    assert np.float64(got["ct_tame"]).tobytes() == np.float64(want["ct_tame"]).tobytes(), (got["ct_tame"], want["ct_tame"])
+    assert got["proxies"] == want["proxies"]
