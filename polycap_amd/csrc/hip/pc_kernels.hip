@@ -59,7 +59,7 @@
 #include "pc_tally.h"
 #include "pc_spot.h"
 #include "pc_beam.h"
-#include "pc_hist.h"
+#include "pc_hist.h"            /* with pc_cells.h, which it includes between its host part and its C functions */
 #include "pc_joint.h"
 #include "pc_select.h"
 #include "pc_gather.h"

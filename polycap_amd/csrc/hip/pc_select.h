@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(PC_SELECT_BLOCK) pc_select_kernel(pc_spot_src 
 		int pass = 0;
 		if (i < s.n) {
 			pc_hist_entry e;
-			pc_hist_load(s, g, i, e);
+			pc_hist_load(s, i, g.need_start, g.need_travel, g.need_n, e);
 			pass = pc_select_pass(g, e);
 			if (blockIdx.y == 0) mask[i] = (unsigned char)pass;
 		}
@@ -555,15 +555,13 @@ int pc_hip_beam_add_selected(pc_hip_beam *beam, int kind, pc_hip_select *sel)
 int pc_hip_hist_add_selected(pc_hip_hist *hist, int kind, pc_hip_select *sel)
 {
 	if (!hist || !sel) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_hist_add_selected: hist and select must not be NULL");
-	return pc_tally_add(*hist, kind, "pc_hip_hist_add_selected",
-		[hist](size_t k, const pc_spot_src &s, int kd) { return pc_hist_launch(hist, hist->m[k], s, kd); }, sel);
+	return pc_cells_add<1>(hist, kind, "pc_hip_hist_add_selected", sel);
 }
 
 int pc_hip_joint_add_selected(pc_hip_joint *joint, int kind, pc_hip_select *sel)
 {
 	if (!joint || !sel) return pc_fail(PC_HIP_ERR_INVALID, "pc_hip_joint_add_selected: joint and select must not be NULL");
-	return pc_tally_add(*joint, kind, "pc_hip_joint_add_selected",
-		[joint](size_t k, const pc_spot_src &s, int kd) { return pc_joint_launch(joint, joint->m[k], s, kd); }, sel);
+	return pc_cells_add<2>(joint, kind, "pc_hip_joint_add_selected", sel);
 }
 
 int pc_hip_select_parse(const char *value, pc_hip_select_cut *cuts, int32_t *n_cuts, char *why, size_t why_len)

@@ -109,7 +109,7 @@ def test_carry_add_equals_python_integers(host):
 
 # ---- the tiles -------------------------------------------------------------------------------------------------------------------
 def test_tile_split_at_its_seams(host):
-    for header, name in (("pc_spot.h", "PC_SPOT_TILE"), ("pc_hist.h", "PC_HIST_TILE"), ("pc_joint.h", "PC_JOINT_TILE")):
+    for header, name in (("pc_spot.h", "PC_SPOT_TILE"), ("pc_cells.h", "PC_CELLS_TILE")):      # the histograms and the joint histograms share one
         tile = int(re.search(r"#define %s (\d+)" % name, open(os.path.join(HIPD, header)).read()).group(1))
         assert tile * 8 == 65536                                                           # all of the 64 KiB a workgroup's tile has
         cells, _ = tile_split(host, 1, tile, True)
