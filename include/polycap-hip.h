@@ -931,6 +931,64 @@ POLYCAP_EXTERN int pc_hip_slab_frame(const pc_hip_slab *spec, double frame[20]);
  * result applies unchanged */
 POLYCAP_EXTERN int pc_hip_slab_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_slab *spec, pc_hip_select *select);
 
+/* ---- layered emits: an emit relay through a stack of sample layers (varnish over paint over ground, a coating on a substrate, a
+ * buried marker layer).  The stack sits behind the emit's sheet as the slab does: layer 0 starts at the front face, each further
+ * layer lies along +n_s.  Layer j has a thickness T_j (cm), attenuation coefficients mu_in[j][eA] at A's energies and mu_out[j][eB]
+ * at B's (1/cm), and a fluorescence-production coefficient production[j][eB] (1/cm): the coefficient a slab emit leaves to the
+ * caller, here per layer.  The tables are row-major by layer.  1 <= n_layers <= PC_HIP_MAX_LAYERS.  IEEE fp64, evaluated in the
+ * order written, no contraction, no fma.
+ *   bounds     Z_0 = 0,   Z_{j+1} = Z_j + T_j   summed left to right on the host;   T = Z_n
+ *   tables     summed once per call on the host in plain doubles, each product formed before its add:
+ *              Pin[j][ea]  = sum_{k<j} mu_in[k][ea]*T_k    added left to right
+ *              Pout[j][e]  = sum_{k<j} mu_out[k][e]*T_k    added left to right
+ *              Sout[j][e]  = sum_{k>j} mu_out[k][e]*T_k    added right to left
+ *              qmax = the largest entry of production
+ *   frame      the slab's twenty numbers for the thickness T (the same code, the same bits), then qmax: twenty-one numbers
+ *              (pc_hip_layers_frame)
+ *   entries, selection, slots: the emit's
+ *   emission   the slab's for the thickness T, operation for operation: dz, sd, sp, "missed the sample", t, p, L = T/sd, u1, u2, u3,
+ *              s = u3*L, zn = s*sd, p', a, b, q, f, "missed the detector", r2, r, d, g, the electric vector,
+ *              cn = ((k0*f0 + k1*f1) + k2*f2) / r,   missed the detector unless cn > 0 or cn < 0,   gl = g*L.  Then, once per photon:
+ *              missed the sample when !(gl*qmax < 1): the slab's guard for a production coefficient other than 1.  With wA <= 1,
+ *              E <= 1, wB <= 1 and monotone rounding every weight then stays below 1, inside the range of the exact sums
+ *              j = the number of inner boundaries Z_k, k = 1 .. n_layers - 1, with zn >= Z_k: the layer of the interaction.  A point
+ *              on a boundary belongs to the layer behind it; a zn that rounding carried past T stays in the last layer
+ *              za = zn - Z_j,   zb = Z_{j+1} - zn, set to 0 when negative
+ *   finish     for every photon with rc 1 and every energy e of B, with ea = map[e]:
+ *              tau_in  = (Pin[j][ea] + mu_in[j][ea]*za) / sd
+ *              tau_out = (Sout[j][e] + mu_out[j][e]*zb) / cn              when cn > 0 (out through the back)
+ *                      = (Pout[j][e] + mu_out[j][e]*za) / (0 - cn)        when cn < 0 (out through the front)
+ *              w = ((wA[ea]*gl) * (production[j][e] * E(0 - (tau_in + tau_out)))) * wB[e]          E: the slab's
+ *   records    the slab's: pc_start_* = the injected state, pc_exit_dtravel = (((dA + t) + s) + r) + dB.  Every column but the weights
+ *              is bit for bit that of a slab emit of thickness T
+ *   counts     the emit's, and their identity; pc_hip_emit_counts and pc_hip_pose_counts answer after a layered emit too
+ * The efficiency is that of detected photons per photon started into A, for isotropic emission: the production coefficients are in
+ * the weights, the caller multiplies by the yield only.  Since the weight is linear in production, the emit with a table equals, photon
+ * by photon and in the exact sums, the sum of the emits with one layer's row kept and the others zero.
+ * A spec is valid when its emit is, 1 <= n_layers <= PC_HIP_MAX_LAYERS, every thickness is finite and in (0, 1] cm, T <= 1 cm, the
+ * four arrays are given with n_mu_in >= 1 and n_mu_out >= 1, and every mu and production entry is finite and >= 0.  Refused with
+ * PC_HIP_ERR_INVALID and a message that names the table, the layer and the index, before anything is launched and with both contexts
+ * and the selection left as they were: what pc_hip_emit_run refuses; an invalid spec; n_mu_in other than A's energy count, n_mu_out
+ * other than B's. */
+#define PC_HIP_MAX_LAYERS 16
+typedef struct {
+	pc_hip_emit emit;
+	int32_t n_layers;
+	const double *thickness;           /* [n_layers] */
+	int32_t n_mu_in;
+	const double *mu_in;               /* [n_layers*n_mu_in] */
+	int32_t n_mu_out;
+	const double *mu_out;              /* [n_layers*n_mu_out] */
+	const double *production;          /* [n_layers*n_mu_out] */
+} pc_hip_layers;
+/* host only: the spec alone (the map and the tables' row lengths against the contexts' grids: pc_hip_layers_run) */
+POLYCAP_EXTERN int pc_hip_layers_validate(const pc_hip_layers *spec);
+/* host only: the slab's twenty numbers with T = the total thickness, then qmax */
+POLYCAP_EXTERN int pc_hip_layers_frame(const pc_hip_layers *spec, double frame[21]);
+/* the layered emit of ctx_a's exit photons into ctx_b, through `select` (NULL: no aperture); everything that reads an emit relay's
+ * result applies unchanged */
+POLYCAP_EXTERN int pc_hip_layers_run(pc_hip_ctx *ctx_a, pc_hip_ctx *ctx_b, const pc_hip_layers *spec, pc_hip_select *select);
+
 /* free and total memory of the context's device, bytes */
 POLYCAP_EXTERN int pc_hip_device_memory(pc_hip_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 

@@ -16,7 +16,8 @@ The package is a thin Python layer over libpolycap.so (host C + hand-written HIP
     the second optic may be tilted and a Selection may stand between the two as an aperture (relay_rocking_curve);
   * TraceContext.emit             -- a thin sample between the two optics: the first one's exit photons re-emit isotropically
     in the sheet and the second optic, at 90 degrees as a rule, collects (emit_frame, emit_valid, emit_depth_scan); with
-    thickness, mu_in and mu_out the sample is a slab that attenuates both ways (emit_slab_frame, emit_slab_valid);
+    thickness, mu_in and mu_out the sample is a slab that attenuates both ways (emit_slab_frame, emit_slab_valid); with layers
+    it is a stack of layers, each with its attenuation and its production coefficient (emit_layers_frame, emit_layers_valid);
   * polycap_amd.capi              -- ctypes mirror of the reference's C API (polycap_profile/_description/
     _source/_photon/...), i.e. what the reference's Cython module binds;
   * polycap_amd.distributed       -- one-process-per-GPU sharding of the slot range + RCCL reduce of the
@@ -28,7 +29,7 @@ from .hip import TraceContext, TraceGroup, SpotMap, BeamMoments, Histograms, Joi
 from .hip import scan_points, scan_efficiencies  # noqa: F401
 from .hip import tally_stderr, select_transmission, pairs_sum  # noqa: F401
 from .hip import relay_efficiencies, relay_placement_valid, relay_basis, relay_rocking_curve, RELAY_COUNTERS  # noqa: F401
-from .hip import emit_valid, emit_frame, emit_depth_scan, emit_slab_valid, emit_slab_frame  # noqa: F401
+from .hip import emit_valid, emit_frame, emit_depth_scan, emit_slab_valid, emit_slab_frame, emit_layers_valid, emit_layers_frame  # noqa: F401
 from .decks import problem_from_inp, optical_constants, optical_constants_provider  # noqa: F401
 
 __version__ = "1.2"

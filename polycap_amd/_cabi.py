@@ -100,6 +100,12 @@ class SlabS(C.Structure):
                 ("n_mu_out", C.c_int32), ("mu_out", c_double_p)]
 
 
+class LayersS(C.Structure):
+    """struct pc_hip_layers"""
+    _fields_ = [("emit", EmitS), ("n_layers", C.c_int32), ("thickness", c_double_p), ("n_mu_in", C.c_int32), ("mu_in", c_double_p),
+                ("n_mu_out", C.c_int32), ("mu_out", c_double_p), ("production", c_double_p)]
+
+
 def dptr(a):
     return a.ctypes.data_as(c_double_p)
 
@@ -401,6 +407,12 @@ def lib():
     L.pc_hip_slab_frame.restype = C.c_int
     L.pc_hip_slab_run.argtypes = [C.c_void_p, C.c_void_p, P(SlabS), C.c_void_p]
     L.pc_hip_slab_run.restype = C.c_int
+    L.pc_hip_layers_validate.argtypes = [P(LayersS)]
+    L.pc_hip_layers_validate.restype = C.c_int
+    L.pc_hip_layers_frame.argtypes = [P(LayersS), c_double_p]
+    L.pc_hip_layers_frame.restype = C.c_int
+    L.pc_hip_layers_run.argtypes = [C.c_void_p, C.c_void_p, P(LayersS), C.c_void_p]
+    L.pc_hip_layers_run.restype = C.c_int
     L.pc_transmission_efficiencies_from_totals.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_int64_p, P(ImagesS), C.c_void_p]
     L.pc_transmission_efficiencies_from_totals.restype = C.c_void_p
     _LIB = L

@@ -67,3 +67,4 @@
 #include "pc_scan.h"
 #include "pc_relay.h"
 #include "pc_emit.h"
+#include "pc_emit_layers.h"

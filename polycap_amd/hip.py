@@ -315,7 +315,7 @@ class TraceContext:
         return r
 
     def emit(self, other, focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=None, seed=0, energy_map=None,
-             select=None, thickness=None, mu_in=None, mu_out=None):
+             select=None, thickness=None, mu_in=None, mu_out=None, layers=None):
         """An emit relay: the exit photons of this context's last source run (made with keep_images) hit a thin sample sheet
         through the point `depth` cm along its normal from (0, 0, focus) behind this optic's exit plane, the normal turned by
         `sample_angle` rad from this optic's axis towards +x; every photon that reaches the sheet re-emits one photon towards
@@ -333,7 +333,12 @@ class TraceContext:
         behind the sheet: every photon interacts at a depth drawn uniformly along its path through the slab, attenuated by mu_in
         on the way there and by mu_out on the emitted ray's way out, through the back or, in the reflection geometry, through the
         front (pc_hip_slab_run).  The efficiencies are then per unit fluorescence-production coefficient (1/cm).  The three come
-        together or not at all (ValueError)."""
+        together or not at all (ValueError).
+        With `layers`, a list of mappings with `thickness` (cm), `mu_in` [this context's energies], `mu_out` and optionally
+        `production` [the energies of `other`] (1/cm; production defaults to ones), the sample is a stack of up to 16 layers
+        behind the sheet, the first one in front (pc_hip_layers_run): the interaction takes its layer's production coefficient and
+        both rays are attenuated through every layer they cross.  The efficiencies then hold the production coefficients.
+        `layers` excludes thickness, mu_in and mu_out (ValueError)."""
         if not isinstance(other, TraceContext):
             raise TypeError("emit: other must be a TraceContext")
         if select is not None and not isinstance(select, Selection):
@@ -341,7 +346,12 @@ class TraceContext:
         if target_half is None:
             target_half = float(other.problem.ext[0])
         sel = None if select is None else select._h
-        if _slab_given("emit", thickness, mu_in, mu_out):
+        if _layers_given("emit", layers, thickness, mu_in, mu_out):
+            spec, keep = _layers_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map, layers)
+            st = self._L.pc_hip_layers_run(self._h, other._h, C.byref(spec), sel)
+            if st != _cabi.PC_HIP_OK:
+                raise HipError("pc_hip_layers_run", st)
+        elif _slab_given("emit", thickness, mu_in, mu_out):
             spec, keep = _slab_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map, thickness, mu_in, mu_out)
             st = self._L.pc_hip_slab_run(self._h, other._h, C.byref(spec), sel)
             if st != _cabi.PC_HIP_OK:
@@ -625,18 +635,83 @@ def emit_slab_frame(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), 
     return dict(n_s=f[0:3], h_s=float(f[3]), u=f[4:7], v=f[7:10], n=f[10:13], c_b=f[13:16], k=f[16:19], thickness=float(f[19]), frame=f)
 
 
+def _layers_given(who, layers, thickness, mu_in, mu_out):
+    """False: no stack of layers is given; True: one is, and none of a slab's three arguments beside it"""
+    if layers is None:
+        return False
+    if any(v is not None for v in (thickness, mu_in, mu_out)):
+        raise ValueError(who + ": layers describes the whole sample: give it without thickness, mu_in and mu_out")
+    return True
+
+
+def _layers_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map, layers):
+    """(pc_hip_layers, what its pointers point to).  layers: mappings with thickness, mu_in, mu_out and optionally production
+    (ones); the rows of a table must have one length (ValueError)."""
+    e, m = _emit_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, seed, energy_map)
+    layers = list(layers)
+    for j, lay in enumerate(layers):
+        missing = [k for k in ("thickness", "mu_in", "mu_out") if k not in lay]
+        unknown = [k for k in lay if k not in ("thickness", "mu_in", "mu_out", "production")]
+        if missing or unknown:
+            raise ValueError("layers[%d]: a layer has thickness, mu_in, mu_out and optionally production (missing %s, unknown %s)" % (j, missing, unknown))
+    th = np.ascontiguousarray([float(lay["thickness"]) for lay in layers], dtype=np.float64).reshape(-1)
+    rows_in = [np.asarray(lay["mu_in"], dtype=np.float64).reshape(-1) for lay in layers]
+    rows_out = [np.asarray(lay["mu_out"], dtype=np.float64).reshape(-1) for lay in layers]
+    rows_q = [np.ones(len(o)) if lay.get("production") is None else np.asarray(lay["production"], dtype=np.float64).reshape(-1)
+              for lay, o in zip(layers, rows_out)]
+    n_in = len(rows_in[0]) if layers else 0
+    n_out = len(rows_out[0]) if layers else 0
+    for j in range(len(layers)):
+        if len(rows_in[j]) != n_in:
+            raise ValueError("layers[%d]: mu_in has %d entries, layers[0]'s has %d" % (j, len(rows_in[j]), n_in))
+        if len(rows_out[j]) != n_out or len(rows_q[j]) != n_out:
+            raise ValueError("layers[%d]: mu_out has %d and production %d entries, layers[0]'s mu_out has %d" % (j, len(rows_out[j]), len(rows_q[j]), n_out))
+    flat = lambda rows: np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0), dtype=np.float64)
+    mi, mo, q = flat(rows_in), flat(rows_out), flat(rows_q)
+    s = _cabi.LayersS(e, len(layers), dptr(th), int(n_in), dptr(mi), int(n_out), dptr(mo), dptr(q))
+    return s, (m, th, mi, mo, q)
+
+
+def emit_layers_valid(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1., energy_map=None, layers=None):
+    """True when pc_hip_layers_validate accepts the spec of a layered emit (host only; the map and the tables' row lengths against
+    two contexts' grids are checked by emit())."""
+    if layers is None:
+        raise ValueError("emit_layers_valid: layers is needed")
+    spec, keep = _layers_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, energy_map, layers)
+    return _cabi.lib().pc_hip_layers_validate(C.byref(spec)) == _cabi.PC_HIP_OK
+
+
+def emit_layers_frame(focus, sample_angle, depth, det_angle, wd, offset=(0., 0.), target_half=1., layers=None):
+    """The frame of a layered emit (pc_hip_layers_frame, host only): what emit_slab_frame returns for the stack's total thickness,
+    with qmax (the largest production coefficient), bounds [n_layers + 1] (the layers' boundaries, summed left to right as the
+    library sums them) and frame [21] = the slab's twenty numbers, qmax."""
+    if layers is None:
+        raise ValueError("emit_layers_frame: layers is needed")
+    spec, keep = _layers_spec(focus, sample_angle, depth, det_angle, wd, offset, target_half, 0, None, layers)
+    f = np.zeros(21)
+    st = _cabi.lib().pc_hip_layers_frame(C.byref(spec), dptr(f))
+    if st != _cabi.PC_HIP_OK:
+        raise HipError("pc_hip_layers_frame", st)
+    bounds = np.zeros(len(keep[1]) + 1)
+    for j, t in enumerate(keep[1]):
+        bounds[j + 1] = bounds[j] + t
+    return dict(n_s=f[0:3], h_s=float(f[3]), u=f[4:7], v=f[7:10], n=f[10:13], c_b=f[13:16], k=f[16:19], thickness=float(f[19]), qmax=float(f[20]),
+                bounds=bounds, frame=f)
+
+
 def emit_depth_scan(ctx_a, ctx_b, depths, focus, sample_angle, det_angle, wd, offset=(0., 0.), target_half=None, seed=0,
-                    energy_map=None, select=None, thickness=None, mu_in=None, mu_out=None):
+                    energy_map=None, select=None, thickness=None, mu_in=None, mu_out=None, layers=None):
     """A depth scan of the sample: one emit of ctx_a's last run into ctx_b per depth of `depths`, a host loop with one seed, so
     that every depth re-emits with the same random numbers (common random numbers: smooth curves).  Returns depths [n],
     efficiencies [n, n_energies], efficiency_stderr [n, n_energies] (option "weight_squares" on ctx_b, else None) and the emits'
     counters as a list of dicts.  thickness, mu_in, mu_out: a slab behind the sheet, as in emit(); the curve is then the one an
-    instrument records, self-absorption included."""
+    instrument records, self-absorption included.  layers: a stack of layers in their place, as in emit(): the depth profile of a
+    layered sample."""
     dl = np.asarray(depths, dtype=np.float64).reshape(-1)
     eff, err, cnt = [], [], []
     for d in dl:
         r = ctx_a.emit(ctx_b, focus, sample_angle, float(d), det_angle, wd, offset, target_half, seed, energy_map, select,
-                       thickness, mu_in, mu_out)
+                       thickness, mu_in, mu_out, layers)
         eff.append(r["efficiencies"])
         err.append(r["efficiency_stderr"])
         cnt.append(r["counters"])
